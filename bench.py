@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Msamples/s of the ReflectiveSpheres scene, 1920x1080 @ 500 spp, 5 bounces (config C2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one full pass of the hot path over the workload: every pixel of the 1920x1080 frame receives all 500
 samples (rmd_render_tiles over this rank's share of the 32x32 host tiles, sample_begin 0, sample_count 500) and, for
@@ -11,10 +11,20 @@ work split over the ranks (tile i -> rank i mod N), so scaling is "strong".  Sce
 in HBM before the timed region; the timed region is bracketed by barrier + synchronize and the maximum over ranks
 is reported.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line; its roofline_c2 (= roofline) block is priced from
+the timed launches and committed counters, without runs of its own.  --dump-outputs DIR then writes the frame of the last
+timed step as DIR/framebuffer.npy: rank 0's assembled framebuffer, (H, W, 3) float64 sample sums, what a caller of
+rmd_render_tiles receives (a frame over 64 MB is written at every s-th pixel of every s-th row, s the smallest that fits).
+The inputs (scene, camera, seed, tiles) are fixed, so two builds can be compared output for output.
+
+With --full the JSON line also carries what takes runs of its own:
+  gpu           GPU 0's clocks and power as rocm-smi reports them before and after the timed steps;
+  tracing_black_paths  the same frame with every path traced to its end (the reference's segment count);
   roofline      HBM roofline of the traversal (same kernel, GoldDragon-standin mesh, config C3 at its 500 spp, one launch): the
                 spheres workload touches ~0.05 B/sample and is FP64-VALU bound, so its HBM fraction is reported
-                separately as roofline_c2 and is not the figure to optimise;
+                separately as roofline_c2 and is not the figure to optimise; with it, the C3 leg ending black paths and
+                the other mesh configurations (configs);
+  host_api      C2 and C3 end to end through the C++ host mirror;
   cpu_baseline  the CPU oracle (reference-equivalent C++ restatement, kind "port") timed on this box's host cores
                 on a bounded sample of the same workload (rank 0, N = 1 only).
 """
@@ -28,6 +38,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 VALU_ISSUE_NS = 1.667  # one wave64 FP64 / INT32 vector instruction per SIMD every 4 cycles at the 2.4 GHz peak clock
 
@@ -48,8 +59,11 @@ def parse():
                          "rmd_comm_* / rmd_reduce_framebuffer (RCCL, one rank per GPU); all bit-identical to the 1-GPU frame")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline-leg", action="store_true")
-    ap.add_argument("--lean", action="store_true", help="only the timed workload and the roofline leg in its default mode (tools/profile_round.sh: the rocprofv3 "
-                                                         "kernel-trace then averages each kernel over one workload, as the bench line does)")
+    ap.add_argument("--lean", action="store_true", help="with --full: only the timed workload and the roofline leg in its default mode (tools/profile_round.sh: "
+                                                         "the rocprofv3 kernel-trace then averages each kernel over one workload, as the bench line does)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: GPU clocks, the frame tracing black paths, the C3 roofline "
+                                                         "leg and the other configurations, the host API and the CPU baseline (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's frame to DIR/framebuffer.npy (float64)")
     return ap.parse_args()
 
 
@@ -237,6 +251,17 @@ def host_api_block(ctx):
     return block
 
 
+def dump_frame(dump_dir, frame):
+    """--dump-outputs: the frame (H, W, 3) float64 as DIR/framebuffer.npy; a frame over DUMP_LIMIT_BYTES at every s-th pixel of every s-th row."""
+    import numpy as np
+
+    s = 1
+    while frame[::s, ::s].numel() * frame.element_size() > DUMP_LIMIT_BYTES:
+        s += 1
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "framebuffer.npy"), frame[::s, ::s].cpu().numpy())
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` outside a launcher: start the N ranks as FRESH child processes, one per GPU, through
     torch.distributed.run (the form the driver uses), let rank 0's JSON line through on stdout, and return their exit status.
@@ -338,7 +363,7 @@ def main():
         abi_comm = C.c_void_p()
         ctx.check(ctx.L.rmd_comm_create(ctx.handle, uid, rank, world, C.byref(abi_comm)))
 
-    def run_workload(name, spp, steps, warmup, reduce, mode="default"):
+    def run_workload(name, spp, steps, warmup, reduce, mode="default", dump_dir=None):
         st, cam, sc, tiles, share = setup(name, spp, mode)
         W, H = cam.backbuffer_width, cam.backbuffer_height
         ds = render.DeviceScene(ctx, sc)
@@ -389,6 +414,8 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if dump_dir is not None and rank == 0:
+            dump_frame(dump_dir, fb_t.view(H, W, 3))
         # the frame's checksum: the sum of its finite values (a reference-identical mesh frame holds the pixels the reference itself makes NaN) and,
         # beside it, how many pixels hold a non-finite channel
         checksum, nonfinite = 0.0, 0
@@ -405,8 +432,8 @@ def main():
 
     name = args.workload
     spp = args.spp if args.spp is not None else scenes.CONFIGS[name][3]
-    gpu_before = gpu_state() if rank == 0 else None
-    main_run = run_workload(name, spp, args.steps, args.warmup, reduce=True)
+    gpu_before = gpu_state() if rank == 0 and args.full else None
+    main_run = run_workload(name, spp, args.steps, args.warmup, reduce=True, dump_dir=args.dump_outputs)
     ms_per_step = main_run["elapsed"] / args.steps * 1e3
     value = main_run["samples_per_step"] * args.steps / main_run["elapsed"] / 1e6
 
@@ -435,7 +462,7 @@ def main():
         },
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         out["gpu"] = {"before_the_timed_steps": gpu_before, "after_the_timed_steps": gpu_state()}
     # who took part (N > 1): every rank's own view — its rank, the world size IT saw, its device and the samples of its tile share — gathered to rank 0
     if dist is not None:
@@ -447,7 +474,7 @@ def main():
 
     # for the record, beside `value`: the same frame with every path traced to its end as the reference does (RMD_RENDER_TRACE_BLACK_PATHS) —
     # the same checksum, the reference's full number of path segments
-    if world == 1 and not args.no_roofline_leg and not args.lean:
+    if world == 1 and args.full and not args.no_roofline_leg and not args.lean:
         full = run_workload(name, spp, 1, 1, reduce=False, mode="trace")
         out["tracing_black_paths"] = {
             "value": round(full["samples_per_step"] / full["elapsed"] / 1e6, 3), "unit": "Msamples/s", "ms_per_step": round(full["elapsed"] * 1e3, 3),
@@ -489,7 +516,7 @@ def main():
 
     # roofline leg: the traversal on the ~100k-triangle mesh — config C3 at its 500 spp, ONE launch per step — in the reference-identical
     # mode (flags 0: every path traced to its end on a mesh scene) and, beside it, with RMD_RENDER_END_BLACK_PATHS
-    if not args.no_roofline_leg and world == 1:
+    if args.full and not args.no_roofline_leg and world == 1:
         rspp = args.roofline_spp if args.roofline_spp is not None else scenes.CONFIGS["C3"][3]
         counters = load_counters()
 
@@ -581,9 +608,9 @@ def main():
     # What a drop-in caller gets: C2 and C3 end to end through the reference-shaped API — raymond_amd/host's render_tiled (the C++ stand-in for
     # integration/gpu.rs: tile queue, progressive passes, TileProgressed / TileFinished messages), wall time from the call to the last
     # TileFinished, once in one pass (samples_per_iteration 0) and once progressively (8 samples a pass: src/trace.rs:207-219).
-    if rank == 0 and world == 1 and not args.no_roofline_leg and not args.lean:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline_leg and not args.lean:
         out["host_api"] = host_api_block(ctx)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib
 

@@ -331,10 +331,10 @@ def test_gpu_grid_build_is_byte_identical_to_the_host_builder(gpu_ctx, oracle):
     assert e.value.status == abi.RMD_ERR_GRID_INDEX
 
 
-def test_bench_contract_and_two_rank_rehearsal(gpu_ctx):
-    """bench.py prints ONE JSON line with the driver's keys; a 2-rank run (rehearsal mode: both ranks on this GPU, the
-    collective over gloo — RCCL refuses two ranks on one device) assembles the same frame as the 1-rank run, bit for bit, by
-    either route (gather of owned tiles, reduce of full frames)."""
+def test_bench_contract_and_two_rank_rehearsal(gpu_ctx, tmp_path):
+    """bench.py prints ONE JSON line with the driver's keys and, with --dump-outputs, writes the frame it timed; a 2-rank run
+    (rehearsal mode: both ranks on this GPU, the collective over gloo — RCCL refuses two ranks on one device) assembles the same
+    frame as the 1-rank run, bit for bit, by either route (gather of owned tiles, reduce of full frames)."""
     import json
     import os
     import subprocess
@@ -342,7 +342,8 @@ def test_bench_contract_and_two_rank_rehearsal(gpu_ctx):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--steps", "1", "--warmup", "1", "--spp", "24", "--no-cpu-baseline", "--no-roofline-leg"]
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=300, cwd=root)
+    dump = tmp_path / "outputs"
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dump-outputs", str(dump)] + common, capture_output=True, text=True, timeout=300, cwd=root)
     assert one.returncode == 0, one.stderr[-2000:]
     lines = [l for l in one.stdout.split("\n") if l.strip()]
     assert len(lines) == 1
@@ -351,6 +352,9 @@ def test_bench_contract_and_two_rank_rehearsal(gpu_ctx):
         assert key in a, key
     assert a["unit"] == "Msamples/s" and a["n_gpus"] == 1 and a["dtype"] == "f64" and a["vs_baseline"] is None and "workload" in a["config"]
     assert abs(a["value"] - 1920 * 1080 * 24 / (a["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * a["value"]
+    frame = np.load(dump / "framebuffer.npy")  # the last timed step's frame: sample sums, what rmd_render_tiles gives its caller
+    assert frame.shape == (1080, 1920, 3) and frame.dtype == np.float64
+    assert np.isclose(frame[np.isfinite(frame)].sum(), a["kernel"]["checksum"], rtol=1e-12, atol=0.0)
     # N > 1 without a launcher: bench.py starts its own ranks as fresh child processes (the form the driver uses at N = 1)
     env = dict(os.environ, RMD_BENCH_BACKEND="gloo")
     two = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + common, capture_output=True, text=True, timeout=600, cwd=root, env=env)

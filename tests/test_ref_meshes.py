@@ -3,8 +3,8 @@
 
 tests/golden/ref_meshes.json and ref_mesh_<name>.npz were written by tools/gen_ref_fixtures.py from those files with a
 third, plain-Python implementation.  Held against them here: the oracle's loader and grid builder, the product's Python and
-C++ PLY loaders, and the product's host grid builder.  The loaders need the PLY files themselves and so run only where
-/root/reference exists (the build container); everything else runs from the committed arrays.
+C++ PLY loaders, and the product's host grid builder.  The loaders read the PLY files themselves: byte-for-byte copies of the
+reference's assets, committed under tests/golden/ply/; everything else runs from the committed arrays.
 """
 import ctypes as C
 import hashlib
@@ -20,12 +20,11 @@ from raymond_amd.scene import AccGrid, Mesh
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-REF_MESHES = "/root/reference/assets/meshes"
+REF_MESHES = os.path.join(GOLD, "ply")  # the reference's assets/meshes/*.ply, copied as data
 with open(os.path.join(GOLD, "ref_meshes.json")) as _f:
     FIX = json.load(_f)
 NAMES = sorted(FIX["meshes"])
 BAKE = tuple(FIX["bake_translation"])
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF_MESHES), reason="the reference checkout is only present in the build container")
 
 
 def sha(a):
@@ -51,7 +50,6 @@ def test_fixture_arrays_match_their_digests():
     assert FIX["meshes"]["cube"]["vertex_properties"][-2:] == ["s", "t"] and FIX["meshes"]["suzanne"]["vertex_properties"][-1] == "nz"
 
 
-@needs_reference
 @pytest.mark.parametrize("name", NAMES)
 def test_ply_loaders_on_the_reference_assets(name, oracle, product_lib, tmp_path):
     """Mesh::load_ply + bake_transform: oracle, Python mirror and C++ mirror parse the reference's files to the fixture's bits."""

@@ -1,22 +1,22 @@
 #!/usr/bin/env python3
 """Fixtures from the reference's OWN mesh assets (the only real inputs it ships for core/src/geometry/mesh.rs:58-140
-and acc_grid.rs:36-83).  Run in the build container, where /root/reference exists:
+and acc_grid.rs:36-83), committed as data under tests/golden/ply/:
 
     python tools/gen_ref_fixtures.py
 
-Reads /root/reference/assets/meshes/{cube,ico_sphere,monkeysmooth,suzanne,suzanne_flat}.ply AS DATA and writes
+Reads tests/golden/ply/{cube,ico_sphere,monkeysmooth,suzanne,suzanne_flat}.ply (the reference's assets/meshes/) AS DATA and writes
 
   tests/golden/ref_meshes.json        per mesh: the counts its header declares, triangle count, sha256 of the parsed
                                       (N, 9) f64 position / normal arrays, bounds (hex floats), and for the mesh as loaded
                                       and as baked by cli_old's translation (0, -0.3, 2.9): grid resolution, table sizes,
                                       sha256 of cells / mapping_table — or "panics" where the reference's index
                                       `x + res.x*(y + z*res.z)` (acc_grid.rs:61, Q5) runs past the cell array
-  tests/golden/ref_mesh_<name>.npz    the parsed arrays (tri_pos, tri_nrm), so that the GPU box — which has no
-                                      /root/reference — can build scenes from the reference's meshes
+  tests/golden/ref_mesh_<name>.npz    the parsed arrays (tri_pos, tri_nrm), so that tests can build scenes from the
+                                      reference's meshes without parsing them
 
 Everything here is computed by a THIRD implementation (plain Python / numpy below), independent of the two PLY loaders
 (raymond_amd/scene.py, raymond_amd/host/raymond.cpp), of the product's grid builders and of the oracle; the tests hold all
-of them against these values.  No PLY text is stored in the repo.
+of them against these values.
 """
 import hashlib
 import json
@@ -28,7 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-SRC = "/root/reference/assets/meshes"
+SRC = os.path.join(GOLD, "ply")  # the reference's assets/meshes/*.ply, committed as data
 NAMES = ["cube", "ico_sphere", "monkeysmooth", "suzanne", "suzanne_flat"]
 BAKE = (0.0, -0.3, 2.9)  # cli_old/src/main.rs:61
 
@@ -136,7 +136,7 @@ def main():
         g = out[name]["grid_baked"]
         print(name, out[name]["triangles"], "triangles; baked grid", g.get("resolution"), g.get("panics", "ok"), flush=True)
     with open(os.path.join(GOLD, "ref_meshes.json"), "w") as f:
-        json.dump({"_source": "/root/reference/assets/meshes/*.ply read as data by tools/gen_ref_fixtures.py", "bake_translation": list(BAKE), "meshes": out}, f, indent=1)
+        json.dump({"_source": "tests/golden/ply/*.ply (the reference's assets/meshes/) read as data by tools/gen_ref_fixtures.py", "bake_translation": list(BAKE), "meshes": out}, f, indent=1)
 
 
 if __name__ == "__main__":

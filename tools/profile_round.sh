@@ -10,7 +10,7 @@ root=$(pwd)
 out=$root/gpurun_out/$name
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 "$root/bench.py" --no-cpu-baseline --lean > "$out/bench_profiled.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 "$root/bench.py" --full --no-cpu-baseline --lean > "$out/bench_profiled.log" 2>&1
 echo "trace done" | tee -a "$out/progress.txt"
 for wl in C3:500 C3-end:500 C2:500; do
   w=${wl%%:*}; spp=${wl##*:}
@@ -31,7 +31,7 @@ f=$(find "$out/trace" -name "*kernel_stats.csv" | head -1); cp "$f" "$out/kernel
 f=$(find "$out/trace" -name "*kernel_trace.csv" | head -1); python3 tools/summarize_trace.py "$f" > "$out/render_kernel_dispatches.txt"
 # the un-profiled bench line, reading the traffic / VALU figures just collected
 cp "$out/pmc_latest.json" "$out/hbm_traffic.json" profiles/
-python3 bench.py > "$out/bench_line.json" 2> "$out/bench_stderr.log"
+python3 bench.py --full > "$out/bench_line.json" 2> "$out/bench_stderr.log"
 cat "$out/bench_line.json"
 # the raw traces are large: keep the summaries only
 rm -rf "$out/trace" "$out"/C?*_500_sq "$out"/C?*_500_fetch "$out"/C?*_500_write "$out"/C?*_500_mix? "$out"/C?*_500_wait
