@@ -445,10 +445,7 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 	}
 	// pair_opposite_planes: plane j is tested together with the first earlier, still unpaired plane i whose normal is its exact negation
 	// (device_core.hpp: plane_pair_intersect — the facing conditions of such planes exclude each other, one division serves both)
-#ifndef RMD_PAIR_PLANES
-#define RMD_PAIR_PLANES 1
-#endif
-	for (uint32_t j = 0; j < n_objects && RMD_PAIR_PLANES; j++) {
+	for (uint32_t j = 0; j < n_objects; j++) {
 		if (hobj[j].geometry_kind != RMD_GEOM_PLANE) continue;
 		for (uint32_t i = 0; i < j; i++) {
 			if (hobj[i].geometry_kind != RMD_GEOM_PLANE || hobj[i].pair_info != 0u) continue;
@@ -462,10 +459,7 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 	// ... and a pair whose normals are exactly +e_k and -e_k — the walls of an axis-aligned room — is tested with one component of the ray instead of
 	// three dot products (scene_split.hpp: axis_pairs_visit has the argument for "same bits"): one pair per axis, in scenes of regular parameters
 	uint32_t axis_pairs = 0;
-#ifndef RMD_AXIS_PAIRS
-#define RMD_AXIS_PAIRS 1
-#endif
-	for (uint32_t j = 0; j < n_objects && j < 1023u && regular && RMD_AXIS_PAIRS && ctx->tunable[RMD_TUNE_AXIS_PAIRS] != 1; j++) {
+	for (uint32_t j = 0; j < n_objects && j < 1023u && regular && ctx->tunable[RMD_TUNE_AXIS_PAIRS] != 1; j++) {
 		if (hobj[j].geometry_kind != RMD_GEOM_PLANE || hobj[j].pair_info == 0u || (hobj[j].pair_info & rmd::kPairTestedAtPartner)) continue;
 		const uint32_t i = hobj[j].pair_info - 1u;
 		int k = -1, nonzero = 0;

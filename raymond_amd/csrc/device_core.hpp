@@ -8,16 +8,12 @@
 #include "device_types.hpp"
 
 #define RMD_DEV __device__ __forceinline__
-// measured micro-optimisations, each bit-exact; the switches exist for tools/ab_multi.sh
 #ifndef RMD_OPT_BITOP3
 #if defined(__gfx950__) || !defined(__HIP_DEVICE_COMPILE__)
 #define RMD_OPT_BITOP3 1 // v_bitop3_b32 exists on gfx950 only (the host pass just parses the builtin)
 #else
 #define RMD_OPT_BITOP3 0 // `make ARCH=...` for another target: the two-XOR form, bit-identical
 #endif
-#endif
-#ifndef RMD_OPT_SHARED_SQRT
-#define RMD_OPT_SHARED_SQRT 1
 #endif
 // Pointers read out of structs in memory are generic-address-space to the compiler, which then emits flat_load +
 // full waits; these casts state that they point to global memory (HBM), giving global_load and counted waits.
@@ -45,47 +41,25 @@ RMD_DEV V3 operator/(V3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
 RMD_DEV V3 hadamard(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
 RMD_DEV double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; } // cgmath: mul_element_wise().sum()
 RMD_DEV V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-#if RMD_NO_BRANCH_HINTS
-#define RMD_UNLIKELY(c) (c)
-#else
 #define RMD_UNLIKELY(c) __builtin_expect(!!(c), 0) // the fallback of a wave-level range test: laid out away from the path every trip takes
-#endif
 // IEEE square root.  The compiler's expansion of sqrt(double) pre-scales arguments below 2^-767 (compare, two selects, two ldexp around the
 // refinement) and ends with a select that returns +-0 and +inf unchanged (class compare, two selects); no length, discriminant or area on this
 // path is that small, zero or infinite in the ordinary course, so when every lane of the wave holds a finite argument >= 2^-767 — ONE unsigned
 // range test on the high word: 0x10000000 <= hi < 0x7FF00000 excludes small, zero, negative, infinite and NaN arguments alike — the same
 // refinement runs without the scaling and without the final select: identical operations on identical values, hence identical results
 // (tools/microbench: 0 mismatches in 3.4e11 arguments).  Otherwise (one ballot) the whole wave takes the compiler's sequence.
-// RMD_SQRT_RANGE_TEST: 1 = this form (two integer instructions of special-casing per root); 0 = round 4's (two f64 compares in front for the small
-// arguments, the class select behind: five instructions, three of them at the price of an f64 addition each — tools/microbench/valu_rate.hip);
-// 2 = one integer compare in front, the select behind.  Measured with the branch-free object tests (C2 / every path traced / C3 / C3 with black
-// paths ended): 49.0 / 86.9 / 418.0 / 263.2 ms with 0, 49.0 / 86.0 / 410.5 / 260.2 with 1, 49.0 / 86.8 / 417.1 / 262.8 with 2.
-#ifndef RMD_SQRT_RANGE_TEST
-#define RMD_SQRT_RANGE_TEST 1
-#endif
+// Two integer instructions of special-casing per root, against five (three of them f64 compares) for two f64 compares in front and the class
+// select behind: C3 418.0 -> 410.5 ms, every path traced 86.9 -> 86.0 ms (tools/microbench/valu_rate.hip prices the instructions).
 RMD_DEV double sqrt64(double x) {
-#if RMD_SQRT_RANGE_TEST == 1
 	const uint32_t hi = (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32);
 	if (RMD_UNLIKELY(__ballot(hi - 0x10000000u >= 0x7FF00000u - 0x10000000u) != 0ull)) return __builtin_sqrt(x);
-#elif RMD_SQRT_RANGE_TEST == 2
-	// +0 and positive arguments below 2^-767 as ONE unsigned compare of the high word (an f64 compare costs as much as an f64 addition, an integer
-	// one half: tools/microbench/valu_rate.hip); negative, infinite and NaN arguments take the refinement as before
-	const uint32_t hi = (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32);
-	if (__ballot(hi < 0x10000000u) != 0ull) return __builtin_sqrt(x);
-#else
-	if (__ballot(x < 0x1p-767 && x > 0.0) != 0ull) return __builtin_sqrt(x);
-#endif
 	const double y = __builtin_amdgcn_rsq(x);
 	double g = x * y, h = y * 0.5;
 	const double r = __builtin_fma(-h, g, 0.5);
 	g = __builtin_fma(g, r, g), h = __builtin_fma(h, r, h);
 	g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
 	g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
-#if RMD_SQRT_RANGE_TEST == 1
 	return g;
-#else
-	return __builtin_amdgcn_class(x, 0x260) ? x : g; // +-0 and +inf return themselves (class mask: -0 | +0 | +inf)
-#endif
 }
 RMD_DEV double length(V3 a) { return sqrt64(dot(a, a)); }
 // a / b for a divisor whose correctly rounded reciprocal r = 1.0 / b was computed beforehand (host: exact_reciprocal(),
@@ -111,19 +85,12 @@ RMD_DEV double fast_rcp(double b) {
 // numerators below 2^-969), or a = +0 over a positive b; NOT a zero in general: the sequence loses the quotient's sign of zero (-0 / b comes out +0).
 // NaNs give NaNs.  The CALLER guarantees the range (see the call sites): there is no test in here.
 // Four to five instructions fewer per division, five divisions per path segment on a scene of planes and spheres.
-#ifndef RMD_LEAN_DIVISION
-#define RMD_LEAN_DIVISION 1
-#endif
 RMD_DEV double div_lean(double a, double b) {
-#if RMD_LEAN_DIVISION
 	double y = __builtin_amdgcn_rcp(b);
 	y = __builtin_fma(y, __builtin_fma(-b, y, 1.0), y);
 	y = __builtin_fma(y, __builtin_fma(-b, y, 1.0), y);
 	const double q = a * y;
 	return __builtin_fma(__builtin_fma(-b, q, a), y, q);
-#else
-	return a / b;
-#endif
 }
 RMD_DEV double div_by(double a, double b, double r) {
 	const double q = a * r;
@@ -139,15 +106,10 @@ RMD_DEV double div_by(double a, double b, double r) {
 // down the plain sqrt + division (one ballot).  tools/microbench/inv_length_check.hip compares the shortcut with
 // sqrt + division bit for bit: 0 mismatches in 3.4e11 arguments, 4.8e9 of them with all-ones roots.
 RMD_DEV void sqrt_and_inverse(double x, double &root, double &inv) {
-#ifndef RMD_SQRT_INV_RANGE_TEST
-#define RMD_SQRT_INV_RANGE_TEST 1 // an f64 compare costs as much as an f64 addition, an integer compare half (tools/microbench/valu_rate.hip): C2 51.3 -> 50.6 ms
-#endif
-#if RMD_SQRT_INV_RANGE_TEST
-	const uint32_t hi = (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32); // 2^-700 <= x < 2^700 as one unsigned range test on the high word
+	// 2^-700 <= x < 2^700 as one unsigned range test on the high word: an f64 compare costs as much as an f64 addition, an integer compare half
+	// (tools/microbench/valu_rate.hip): C2 51.3 -> 50.6 ms
+	const uint32_t hi = (uint32_t)(__builtin_bit_cast(unsigned long long, x) >> 32);
 	if (RMD_UNLIKELY(__ballot(hi - 0x14300000u >= 0x6BB00000u - 0x14300000u) != 0ull)) {
-#else
-	if (__ballot(!(x >= 0x1p-700 && x <= 0x1p700)) != 0ull) {
-#endif
 		root = sqrt64(x);
 		inv = 1.0 / root;
 		return;
@@ -174,20 +136,8 @@ RMD_DEV V3 normalize(V3 a) { // cgmath normalize_to(1.0): a * (1.0 / magnitude)
 RMD_DEV double dist(V3 a, V3 b) { return length(b - a); }     // MetricSpace::distance
 // a / |a| to within a few ulp: the hardware reciprocal square root and two Newton steps (16 instructions for normalize()'s 27).
 // For vectors that only enter a sample's weight (the half vector of the BRDF terms).
-// A dot product for quantities that only scale a sample's weight (RMD_WEIGHT_FMA: fused, three instructions for five; the reference's
-// unfused sum otherwise)
-#ifndef RMD_WEIGHT_FMA
-#define RMD_WEIGHT_FMA 0
-#endif
-RMD_DEV double dot_w(V3 a, V3 b) {
-#if RMD_WEIGHT_FMA
-	return __builtin_fma(a.x, b.x, __builtin_fma(a.y, b.y, a.z * b.z));
-#else
-	return dot(a, b);
-#endif
-}
 RMD_DEV V3 normalize_for_weight(V3 a) {
-	const double x = dot_w(a, a), h = 0.5 * x;
+	const double x = dot(a, a), h = 0.5 * x;
 	double y = __builtin_amdgcn_rsq(x);
 	y = y * __builtin_fma(-(h * y), y, 1.5);
 	y = y * __builtin_fma(-(h * y), y, 1.5);
@@ -323,7 +273,7 @@ RMD_DEV bool plane_pair_intersect(V3 origin_a, V3 normal_a, V3 origin_b, V3 norm
 	plane_pair_visit(origin_a, normal_a, origin_b, normal_b, ro, rd, [&](double t, bool f) { t_out = t, first = f, hit = true; });
 	return hit;
 }
-// The same three tests without control flow (RMD_FLAT_OBJECT_TESTS, the closest-hit loops): every lane computes the whole test and ONE condition
+// The same three tests without control flow (the closest-hit loops): every lane computes the whole test and ONE condition
 // says whether its result counts.  The operations that produce a counted distance are those of the branching forms, in the same order, on the
 // same values; a lane whose ray misses computes a quotient or root nobody reads (a division by a small or zero denominator, the root of a negative
 // number: no traps on this hardware).  Why: a value that lives across a divergent branch and is assigned inside it — the closest distance and
@@ -335,11 +285,7 @@ RMD_DEV bool sphere_test_flat(V3 center, double radius, V3 ro, V3 rd, double &t_
 	V3 q = c - t * rd;
 	double p = dot(q, q);
 	double r2 = radius * radius;
-#if RMD_SQRT_RANGE_TEST == 1
-	t -= sqrt64(__builtin_fabs(r2 - p)); // (that form sends the wave down the compiler's sequence for a negative argument: a lane that misses takes the root of |r2 - p|, which nobody reads)
-#else
-	t -= sqrt64(r2 - p); // NaN where p > r2 (sqrt64's fast path takes negative arguments: only SMALL POSITIVE ones send the wave to the compiler's sequence)
-#endif
+	t -= sqrt64(__builtin_fabs(r2 - p)); // (sqrt64 sends the wave down the compiler's sequence for a negative argument: a lane that misses takes the root of |r2 - p|, which nobody reads)
 	t_out = t;
 	return !(p > r2) && !(t <= 0.0);
 }
@@ -393,23 +339,6 @@ RMD_DEV bool triangle_intersect(V3 v0, V3 edge1, V3 edge2, V3 ro, V3 rd, double 
 		return true;
 	}
 	return false;
-}
-// The same test without control flow (RMD_FLAT_TRIANGLE_TEST, the walk's chunk loop): a chunk tests 64 (ray, triangle) pairs of different rays and
-// cells, so an early exit is only taken when all 64 fail the same test — practically never — while the four nested branches cost their scalar
-// bookkeeping and a copy of `t` per level every time.  The conditions are the negations of the exits above, written so that a NaN takes the same
-// way through them (every compare with a NaN is false there and here).
-RMD_DEV bool triangle_test_flat(V3 v0, V3 edge1, V3 edge2, V3 ro, V3 rd, double &t_out) {
-	constexpr double EPSILON = 0.00000001;
-	V3 h = cross(rd, edge2);
-	double a = dot(edge1, h);
-	double f = 1.0 / a;
-	V3 s = ro - v0;
-	double u = f * dot(s, h);
-	V3 q = cross(s, edge1);
-	double v = f * dot(rd, q);
-	double t = f * dot(edge2, q);
-	t_out = t;
-	return !(a < EPSILON && a > -EPSILON) && !(u < 0.0 || u > 1.0) && !(v < 0.0 || u + v > 1.0) && t > EPSILON;
 }
 // triangle.rs:47-68
 RMD_DEV double heron_area_of_sides(double ab, double ac, double bc) {
@@ -598,11 +527,7 @@ RMD_DEV V3 sel(bool c, V3 a, V3 b) { return mk(c ? a.x : b.x, c ? a.y : b.y, c ?
 // performs exactly its own branch's operations in the reference's order.
 // Must be called in wave-uniform control flow; a lane with neither flag set is left untouched.
 // A register (pair) the compiler may fill with anything: the value of a variable in the lanes that never use it.
-#ifndef RMD_NO_UNDEF
 #define RMD_UNDEF(v) asm volatile("" : "=v"(v));
-#else
-#define RMD_UNDEF(v) v = 0.0; // (A/B: the stand-in values of rounds 1 - 4)
-#endif
 struct NextRayShadeIn {
 	V3 normal, frag, color;
 	double roughness, metal;
@@ -638,13 +563,9 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 		double phi, st, ct, sp, cp;
 		V3 axis;
 		// both samplers begin with a square root — sqrt(r1) (:399) or sqrt(r2 / (1 - r2)) (:289): one sequence for the lanes of either kind
-#if RMD_OPT_SHARED_SQRT
 		double root_arg = r1;
 		if (!diffuse) root_arg = div_lean(r2, 1.0 - r2); // (r2 a multiple of 2^-53 in [0, 1): +0 or >= 2^-53 over a divisor in [2^-53, 1] — inside div_lean's range)
 		const double root = sqrt64(root_arg);
-#else
-		const double root = diffuse ? sqrt64(r1) : sqrt64(r2 / (1.0 - r2));
-#endif
 		if (diffuse) {
 			// uniform_sample_hemisphere (:396-406), frame around the normal (:261-262)
 			hemisphere_sincos(root, st, ct);
@@ -682,7 +603,7 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 	// ---- SHADE, second half: the bounce's weight (:275-282 / :301-318) and the bounce ray's origin (:269 / :300)
 	if (do_shade) {
 		const V3 normal = in.normal;
-		const double n_dot_sw = dot_w(normal, sw);
+		const double n_dot_sw = dot(normal, sw);
 		// Weight of the bounce.  trace() returns  diffuse (:281-282)  ((A (.) radiance) * cos) / (prob_d * pdf)
 		//                                         specular (:315-318) (((A (.) radiance) * cos) / (1 - prob_d)) / pdf
 		// i.e. radiance times a per-channel weight known before the recursive call; the kernel multiplies the weights forward
@@ -697,7 +618,7 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 		// :276 halfway of (sample_world, view); :307-308 normalise sample_world once more first — it is a unit vector already, the
 		// second normalisation moves it by at most an ulp, and only this weight would see that
 		const V3 halfway = normalize_for_weight(sw + view);
-		const double h_dot_v = dot_w(halfway, view);
+		const double h_dot_v = dot(halfway, view);
 		const double fc = diffuse ? fmax(h_dot_v, 0.0) : h_dot_v; // :277 clamps, :309 does not
 		const V3 F = f0 + (mk(1.0, 1.0, 1.0) - f0) * pow5(1.0 - fc); // fresnel_schlick :384-386
 		V3 vec;
@@ -709,11 +630,11 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 			Dn = prob_d * pdf_d;     // :282
 		} else {
 			const double a2 = in.roughness * in.roughness; // Q4
-			const double ndh = dot_w(normal, halfway);
+			const double ndh = dot(normal, halfway);
 			const double den = (ndh * ndh) * (a2 - 1.0) + 1.0;
 			const double Dd = fmax(kPi * den * den, 1e-7); // :367-368
 			const double k = (in.roughness * in.roughness) / 8.0; // :374
-			const double n_dot_v = dot_w(normal, view);
+			const double n_dot_v = dot(normal, view);
 			const double g1n = fmax(n_dot_v, 0.0), g2n = fmax(n_dot_sw, 0.0); // :373
 			const double g1d = g1n * (1.0 - k) + k, g2d = g2n * (1.0 - k) + k;         // :375-377
 			const double denominator = 4.0 * n_dot_v * n_dot_sw + 0.001;     // :312

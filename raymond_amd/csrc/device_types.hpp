@@ -60,10 +60,7 @@ struct CellEntry {
 	uint32_t first, count;
 };
 constexpr uint32_t kEntrySlots = 8; // entries per cell (slot 7 unused: a cell's row is one 64-byte line)
-#ifndef RMD_TRI_REC_STRIDE
-#define RMD_TRI_REC_STRIDE 80
-#endif
-constexpr uint32_t kTriRecStride = RMD_TRI_REC_STRIDE; // bytes between triangle records (72 used)
+constexpr uint32_t kTriRecStride = 80; // bytes between triangle records (72 used)
 
 struct alignas(16) DevGrid {
 	double bbox_min[3];

@@ -105,30 +105,11 @@ RMD_DEV uint32_t steps_to_exit(int32_t c, int32_t s, int32_t r) {
 }
 
 // Candidates a lane may collect per round (speculative look-ahead along its own DDA path).
-#ifndef RMD_WALK_CANDIDATES
-#define RMD_WALK_CANDIDATES 4
-#endif
-constexpr uint32_t kWalkCand = RMD_WALK_CANDIDATES;
-static_assert(kWalkCand >= 1 && kWalkCand <= 8, "1..8 candidates per round");
+constexpr uint32_t kWalkCand = 4;
 // After its first candidate a lane keeps stepping at most this many cells looking for more (the non-empty cells of
 // one surface crossing are adjacent); further cells wait for the next round.
-#ifndef RMD_WALK_ASM_STEP
-#define RMD_WALK_ASM_STEP 1
-#endif
-#ifndef RMD_WALK_LOOKAHEAD
-#define RMD_WALK_LOOKAHEAD 16
-#endif
-constexpr uint32_t kWalkLookahead = RMD_WALK_LOOKAHEAD;
-// chunks the owner search (and the load of the triangle indices) runs ahead of the tests: 1 or 2
-#ifndef RMD_WALK_STEP_PRIO
-#define RMD_WALK_STEP_PRIO 2 // s_setprio level of a round's stepping loop (0 = not raised)
-#endif
-constexpr int kWalkStepPrio = RMD_WALK_STEP_PRIO;
-#ifndef RMD_WALK_SEARCH_AHEAD
-#define RMD_WALK_SEARCH_AHEAD 2
-#endif
-constexpr uint32_t kWalkSearchAhead = RMD_WALK_SEARCH_AHEAD;
-static_assert(kWalkSearchAhead == 1u || kWalkSearchAhead == 2u, "the search runs one or two chunks ahead");
+constexpr uint32_t kWalkLookahead = 16;
+constexpr int kWalkStepPrio = 2; // s_setprio level of a round's stepping loop
 
 // Per-wave LDS scratch of the cooperative triangle tests.  A (lane, candidate slot) pair has the key lane * kWalkCand + slot.
 struct alignas(16) WalkScratch {
@@ -179,39 +160,13 @@ struct alignas(16) WalkCarry {
 		             : [tdx] "v"(tdx), [tdy] "v"(tdy), [tdz] "v"(tdz), [dix] "v"(dix), [diy] "v"(diy), [diz] "v"(diz)                      \
 		             : "vcc", "scc");                                                                                                    \
 	}
-#if !RMD_WALK_ASM_STEP
-#undef RMD_DDA_STEP_ASM
-#define RMD_DDA_STEP_ASM()                                                \
-	{                                                                     \
-		const bool lt_xy = tmx < tmy, lt_xz = tmx < tmz, lt_yz = tmy < tmz; \
-		if (lt_xy && lt_xz) {                                             \
-			tmx += tdx, remx--, idx += (uint32_t)dix;                     \
-		} else if (!lt_xy && lt_yz) {                                     \
-			tmy += tdy, remy--, idx += (uint32_t)diy;                     \
-		} else {                                                          \
-			tmz += tdz, remz--, idx += (uint32_t)diz;                     \
-		}                                                                 \
-	}
-#endif
-// The occupancy bit of the cell a lane stands on, then the step, then the exit test — the body of both stepping loops.
-// LEAN: one mask bit per cell (no shift) and no test of the index against the cell array (see grid_intersect_wave).
-#define RMD_DDA_ITERATION(LEAN)                                                                                          \
-	uint32_t bit = LEAN ? idx : idx >> mask_shift;                                                                       \
-	bit = bit < mask_pad_bit ? bit : mask_pad_bit; /* indices past the mask read the zero word that pads it */          \
-	const uint32_t word = lds_mask[bit >> 5];                                                                            \
-	const uint32_t here = idx;                                                                                           \
-	RMD_DDA_STEP_ASM() /* computed while the mask word is in flight */                                                    \
-	const uint32_t rem_min = remx < remy ? (remx < remz ? remx : remz) : (remy < remz ? remy : remz);                    \
-	/* left the grid (a range test fired), or the next cell is past the cell array (:129-131): the walk returns None */ \
-	walking = LEAN ? rem_min != 0u : (rem_min != 0u && idx < idx_limit);                                                 \
-	const bool occupied = __builtin_amdgcn_ubfe(word, bit, 1u) != 0u; /* v_bfe_u32 takes the bit position modulo 32 */
 // The round's stepping: up to kWalkCand candidate cells per lane.  A candidate is stepped over at once — speculating that it
 // yields no hit — so that one round can gather the adjacent non-empty cells of a surface crossing; after its first candidate
 // a lane steps at most kWalkLookahead further cells, the rest waits for the next round.  Candidates are parked in this lane's
 // column of scr.first (slot m at [m * 64 + lane]).  `budget` = steps the lane may still take in this round: unlimited until its
 // first candidate, kWalkLookahead after it, 0 once kWalkCand candidates are recorded.  (One loop for both parts: split in two,
 // the look-ahead of the early lanes no longer overlaps the search of the late ones — 3 % fewer instructions, 3 % more time.)
-template <bool LEAN>
+// This C++ form serves coarse masks and the DIAG event counters; dda_collect_candidates_asm below is the loop for one mask bit per cell.
 RMD_DEV void dda_collect_candidates(const uint32_t *lds_mask, uint32_t mask_shift, uint32_t mask_pad_bit, uint32_t idx_limit, WalkScratch &scr,
                                     uint32_t lane, bool &walking, uint32_t &n_cand, uint32_t &idx, uint32_t &prev, uint32_t &remx, uint32_t &remy, uint32_t &remz,
                                     double &tmx, double &tmy, double &tmz, double tdx, double tdy, double tdz, int32_t dix, int32_t diy, int32_t diz,
@@ -234,7 +189,16 @@ RMD_DEV void dda_collect_candidates(const uint32_t *lds_mask, uint32_t mask_shif
 			}
 		}
 #endif
-		RMD_DDA_ITERATION(LEAN)
+		// the occupancy bit of the cell the lane stands on, then the step, then the exit test
+		uint32_t bit = idx >> mask_shift;
+		bit = bit < mask_pad_bit ? bit : mask_pad_bit; // indices past the mask read the zero word that pads it
+		const uint32_t word = lds_mask[bit >> 5];
+		const uint32_t here = idx;
+		RMD_DDA_STEP_ASM() // computed while the mask word is in flight
+		const uint32_t rem_min = remx < remy ? (remx < remz ? remx : remz) : (remy < remz ? remy : remz);
+		// left the grid (a range test fired), or the next cell is past the cell array (:129-131): the walk returns None
+		walking = rem_min != 0u && idx < idx_limit;
+		const bool occupied = __builtin_amdgcn_ubfe(word, bit, 1u) != 0u; // v_bfe_u32 takes the bit position modulo 32
 		budget--;
 		if (occupied) {
 			scr.first[n_cand * 64u + lane] = here, scr.start[n_cand * 64u + lane] = prev; // the candidate and the cell the ray entered it from
@@ -250,7 +214,7 @@ RMD_DEV void dda_collect_candidates(const uint32_t *lds_mask, uint32_t mask_shif
 }
 
 // The stepping loop of a round for grids with one mask bit per cell, written out as one block of gfx950 assembly
-// (RMD_WALK_ASM_LOOP; dda_collect_candidates above is the same algorithm in C++ and serves coarser masks).  A SIMD issues at
+// (dda_collect_candidates above is the same algorithm in C++ and serves coarser masks).  A SIMD issues at
 // most one vector and one scalar instruction per 4 cycles, from different waves, so the loop is as slow as the LONGER of
 // its two streams: the compiler's rendering of the C++ loop has 26 vector + 20 scalar instructions per step (32 + 22 when
 // a candidate is recorded), this one 19 + 17 (22 + 18):
@@ -264,16 +228,7 @@ RMD_DEV void dda_collect_candidates(const uint32_t *lds_mask, uint32_t mask_shif
 // Executed by the lanes that are walking (divergent call); exec is saved on entry and restored on exit; the scalar temporaries
 // are fixed registers named in the clobber list (an asm statement takes at most 30 operands).  Every step uses up one of the
 // lane's exit counters, so a lane leaves the loop after at most res.x + res.y + res.z steps.  Arithmetic on t_max, the axis
-// choice, the index, the end-of-array test and the order of the recorded candidates are those of RMD_DDA_ITERATION, bit for bit.
-#ifndef RMD_SPHERE_PREFILTER
-#define RMD_SPHERE_PREFILTER 1 // grid_intersect_wave: the triangle tests of a round behind a bounding-sphere pre-test
-#endif
-#ifndef RMD_FLAT_TRIANGLE_TEST
-#define RMD_FLAT_TRIANGLE_TEST 0 // device_core.hpp: triangle_test_flat — measured: seven more spilled registers, C3 426.5 vs 421.0 ms: not used
-#endif
-#ifndef RMD_WALK_ASM_LOOP
-#define RMD_WALK_ASM_LOOP 1
-#endif
+// choice, the index, the end-of-array test and the order of the recorded candidates are those of dda_collect_candidates, bit for bit.
 // cand_base: LDS address of this lane's column of WalkScratch::start (the cells before the candidates); the candidates go to the same column
 // of WalkScratch::first, sizeof(start) bytes further on.
 #define RMD_DDA_LOOP_ASM(CLAMP_AND_WORD, BIT_POSITION, LIMIT_TEST, LIMIT_JOIN) \
@@ -346,7 +301,7 @@ RMD_DEV void dda_collect_candidates(const uint32_t *lds_mask, uint32_t mask_shif
 	    : [tmx] "+v"(tmx), [tmy] "+v"(tmy), [tmz] "+v"(tmz), [idx] "+v"(idx), [prev] "+v"(prev), [rx] "+v"(remx), [ry] "+v"(remy), [rz] "+v"(remz), \
 	      [caddr] "+v"(caddr), [bit] "=&v"(bit), [word] "=&v"(word), [budget] "=&v"(budget), [cleft] "=&v"(cleft) \
 	    : [tdx] "v"(tdx), [tdy] "v"(tdy), [tdz] "v"(tdz), [dix] "v"(dix), [diy] "v"(diy), [diz] "v"(diz), [pad] "s"(mask_pad_bit), [mbase] "s"(mask_base), \
-	      [limit] "s"(idx_limit), [cut] "s"(cut_lanes), [ncand1] "n"(RMD_WALK_CANDIDATES - 1), [look1] "n"(RMD_WALK_LOOKAHEAD - 1), \
+	      [limit] "s"(idx_limit), [cut] "s"(cut_lanes), [ncand1] "n"(kWalkCand - 1), [look1] "n"(kWalkLookahead - 1), \
 	      [firstoff] "n"(sizeof(WalkScratch::start)) \
 	    : "vcc", "scc", "memory", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", "s98");
 // LEAN (uniform per round): the mask holds a bit for every cell of the array, every cell inside the grid has an index inside the array
@@ -367,7 +322,7 @@ RMD_DEV void dda_collect_candidates_asm(uint32_t mask_base, uint32_t mask_pad_bi
 	walking = bit == 0u;
 }
 
-// The walk's sphere pre-test (RMD_SPHERE_PREFILTER): does the LINE of the ray (origin pro, direction prd) pass the centre c of a triangle's sphere
+// The walk's sphere pre-test: does the LINE of the ray (origin pro, direction prd) pass the centre c of a triangle's sphere
 // within sqrt(r2a + kb * |c - pro|^2)?  c, r2a: DevGrid::tri_sph (internal.hpp: triangle_sphere has the error argument); kb: DevGrid::sph_kb, the
 // largest of the grid's triangles'.  This is the one piece of arithmetic on the hot path that is not the reference's: explicit fused multiply-adds
 // (fewer instructions, smaller errors than the allowance assumes).  Precondition: |prd| = 1 to rounding — every ray of the render loop is a
@@ -428,17 +383,13 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 	// every cell inside the grid has an index inside the cell array when res.z <= res.y (the Q5 index x + res.x*(y + z*res.z) of a
 	// cell with y < res.y, z < res.z is then below res.x*res.y*res.z); with one mask bit per cell as well, the stepping loops need
 	// neither the mask shift nor the index test — unless a lane starts from a cell outside the grid (Q6)
-	[[maybe_unused]] const bool lean_grid = mask_shift == 0u && g.res[2] <= g.res[1];
+	const bool lean_grid = mask_shift == 0u && g.res[2] <= g.res[1];
 	bool walking = false;
-	[[maybe_unused]] bool start_outside = false;
+	bool start_outside = false;
 	int32_t dix = 0, diy = 0, diz = 0;
 	uint32_t idx = 0, remx = 1, remy = 1, remz = 1;
 	uint32_t prev = kNoCell; // the cell the ray stood on before `idx`: selects the triangle list of a candidate (device_types.hpp: cell_entries)
-#if RMD_WALK_STATE_STAND_IN
-	double tmx = 0.0, tmy = 0.0, tmz = 0.0, tdx = 0.0, tdy = 0.0, tdz = 0.0;
-#else
 	double tmx, tmy, tmz, tdx, tdy, tdz; // set where a walk starts (or goes on) and only read by lanes that walk
-#endif
 #if RMD_DIAG
 	const bool skip_walk = (debug_flags & 2u) != 0u, skip_tests = (debug_flags & 1u) != 0u; // timing ablations: wrong results, DIAG builds only
 #else
@@ -456,11 +407,7 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 			// could provide one (device_core.hpp: div_by — three instructions for an IEEE division's fourteen; a non-finite position gives NaN
 			// where the division gives an infinity: the cast refuses both)
 			const V3 ics = ld3(g.inv_cell_size);
-#if RMD_NO_CELL_RECIPROCAL
-			const bool by_reciprocal = false; // (A/B)
-#else
 			const bool by_reciprocal = ics.x == ics.x && ics.y == ics.y && ics.z == ics.z; // uniform
-#endif
 			auto cell_of = [&](V3 p, int32_t &ix, int32_t &iy, int32_t &iz) {
 				if (RMD_UNLIKELY(!by_reciprocal)) return cast_i32(p.x / cs.x, ix) && cast_i32(p.y / cs.y, iy) && cast_i32(p.z / cs.z, iz);
 				return cast_i32(div_by(p.x, cs.x, ics.x), ix) && cast_i32(div_by(p.y, cs.y, ics.y), iy) && cast_i32(div_by(p.z, cs.z, ics.z), iz);
@@ -547,13 +494,9 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 		// after it, 0 once kWalkCand candidates are recorded.
 		uint32_t n_cand = 0;
 		// the stepping loop is a chain of dependent LDS reads and branches run by a quarter of the wave's lanes: at a raised priority it is through sooner, and
-		// what it yields the SIMD's other waves — their trips are dense vector code — take up (RMD_WALK_STEP_PRIO: measured −1.4 %)
-		if constexpr (kWalkStepPrio != 0) __builtin_amdgcn_s_setprio(kWalkStepPrio);
+		// what it yields the SIMD's other waves — their trips are dense vector code — take up (measured −1.4 %)
+		__builtin_amdgcn_s_setprio(kWalkStepPrio);
 		if (count_events && lane == 0) atomicAdd(&dbg[3], 1ull);
-		// LEAN (uniform per round): the mask has one bit per cell and every cell inside the grid has an index inside the cell
-		// array (res.z <= res.y), so neither the shift nor the index test is needed as long as no lane of the wave started
-		// from a cell outside the grid (Q6).
-#if RMD_WALK_ASM_LOOP
 		if (mask_shift == 0u && !count_events) { // one mask bit per cell (uniform): the assembly loop (the event counters are in the C++ loop)
 			// its lean form when the mask has a bit for every cell of the array, every cell inside the grid has an index inside the array and no
 			// lane's walk started from a cell outside the grid (uniform per round)
@@ -565,13 +508,8 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 			} else if (walking)
 				dda_collect_candidates_asm<false>((uint32_t)(uintptr_t)lds_mask, mask_pad_bit, idx_limit, (uint32_t)(uintptr_t)&scr.start[lane], walking, n_cand, idx,
 				                                  prev, remx, remy, remz, tmx, tmy, tmz, tdx, tdy, tdz, dix, diy, diz, cut_lanes);
-		}
-#else
-		const bool lean = lean_grid && __ballot(walking && start_outside) == 0ull;
-		if (lean) dda_collect_candidates<true>(lds_mask, mask_shift, mask_pad_bit, idx_limit, scr, lane, walking, n_cand, idx, prev, remx, remy, remz, tmx, tmy, tmz, tdx, tdy, tdz, dix, diy, diz, cut_lanes);
-#endif
-		else dda_collect_candidates<false>(lds_mask, mask_shift, mask_pad_bit, idx_limit, scr, lane, walking, n_cand, idx, prev, remx, remy, remz, tmx, tmy, tmz, tdx, tdy, tdz, dix, diy, diz, cut_lanes, count_events ? dbg : nullptr);
-		if constexpr (kWalkStepPrio != 0) __builtin_amdgcn_s_setprio(0);
+		} else dda_collect_candidates(lds_mask, mask_shift, mask_pad_bit, idx_limit, scr, lane, walking, n_cand, idx, prev, remx, remy, remz, tmx, tmy, tmz, tdx, tdy, tdz, dix, diy, diz, cut_lanes, count_events ? dbg : nullptr);
+		__builtin_amdgcn_s_setprio(0);
 		RMD_STAMP(1)
 		if (cut_lanes != 0u && walking && n_cand == 0u) put_aside(); // the stepping was cut short under a lane that has found nothing to test yet
 		if (__ballot(n_cand != 0u) == 0ull) {
@@ -637,8 +575,8 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 			}
 			RMD_STAMP(3)
 			// Owner search of one chunk: which (lane, candidate) pair test number base + lane belongs to, and its triangle record.
-			// It runs ONE CHUNK AHEAD of the tests (RMD_WALK_SEARCH_AHEAD): a chunk's record loads are issued first, then the
-			// rays are fetched and the next chunk is searched while the records are on their way.
+			// It runs ahead of the tests: a chunk's record loads are issued first, then the rays are fetched and a later chunk is
+			// searched while the records are on their way.
 			auto search = [&](uint32_t base, uint32_t &own, uint32_t &tri_id) {
 				const uint32_t w = base + lane;
 				scr.marker[lane] = 0u;
@@ -661,9 +599,11 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 				tri_id = ids[id_index]; // (a lane without a test reads entry 0) — on its way while the current chunk is tested
 				__builtin_amdgcn_wave_barrier(); // every lane has read the markers before the next search rewrites them
 			};
-			// One chunk of tests.  (own_x, tri_x): the chunk's owner pairs and triangle indices, searched TWO chunks ago (RMD_WALK_SEARCH_AHEAD = 2) —
-			// the index load has had a whole chunk to arrive — and overwritten here by the search of the chunk two ahead.
-			constexpr uint32_t ahead = DEEP ? kWalkSearchAhead : 1u;
+			// Chunks the search runs ahead of the tests: two for the pre-tested chunks of DEEP (the index load has had a whole chunk to arrive), one
+			// for the plain chunks.
+			constexpr uint32_t ahead = DEEP ? 2u : 1u;
+			// One chunk of tests (the plain form).  (own_x, tri_x): the chunk's owner pairs and triangle indices, searched a chunk ago, and
+			// overwritten here by the search of the next chunk.
 			auto chunk = [&](uint32_t base, uint32_t &own_x, uint32_t &tri_x) {
 				const uint32_t w = base + lane;
 				// every lane loads a record (a lane without a test: some triangle's) and tests it — no zero-filled stand-in, no branch around the loads
@@ -675,20 +615,10 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 				const V3 prd = mk(bperm_f64(src, rd.x), bperm_f64(src, rd.y), bperm_f64(src, rd.z));
 				const uint32_t own_now = own_x;
 				if (base + 64u * ahead < total) search(base + 64u * ahead, own_x, tri_x);
-#if RMD_FLAT_TRIANGLE_TEST
-				double t;
-				const bool h = triangle_test_flat(r.v0, r.e1, r.e2, pro, prd, t) && w < total;
-#else
-#if RMD_TRIANGLE_T_STAND_IN
-				double t = 0.0; // (A/B: round 4's form — a stand-in costs a 64-bit copy at each of the test's four exits)
-#else
 				double t; // set by a hit and only read — below, by readlane — for the lanes of `h`
-#endif
+				// (the test's early exits stay: a branch-free form measured seven more spilled registers, C3 426.5 vs 421.0 ms)
 				const bool h = triangle_intersect(r.v0, r.e1, r.e2, pro, prd, t) && w < total;
-#endif
-#if !defined(RMD_STAMP_OUTER_ONLY)
 				RMD_STAMP(5)
-#endif
 				unsigned long long hits = __ballot(h);
 				while (hits) {
 					const int l = (int)__builtin_ctzll(hits);
@@ -707,7 +637,7 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 					}
 				}
 			};
-			// One chunk of tests behind the sphere pre-test (RMD_SPHERE_PREFILTER; the walks of the split launches, DEEP).  85 % of the (ray, triangle)
+			// One chunk of tests behind the sphere pre-test (the walks of the split launches, DEEP).  85 % of the (ray, triangle)
 			// pairs a round numbers fail a test that costs a quarter of triangle.rs:11-44: the ray's line passes the triangle's sphere (DevGrid::tri_sph,
 			// 32 bytes instead of the 72-byte record) by.  pretest() runs that on a chunk — owner search, ray fetch and index lookahead as in chunk() —
 			// and appends the pairs that pass, in their order, to a ring in LDS (the wave's WalkCarry: its contents are loaded when a call begins and
@@ -715,6 +645,8 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 			// reference's test on them and applies the hits exactly as chunk() does.  The pairs that pass keep their ascending (lane, candidate,
 			// triangle) order, so the hit rule sees the same hits in the same order; a pair that is dropped is a pair whose test fails
 			// (internal.hpp: triangle_sphere has the argument; tests/test_pretest_allowance.py checks it on adversarial pairs; tests/test_gpu_faults.py counts, in a DIAG build, that no dropped pair passes the test).
+			// (Requesting the next chunk's spheres while this chunk is tested was measured slower: 38 spilled registers for 7, C3 at 200 spp 130.6 ms
+			// against 123.4.)
 			[[maybe_unused]] unsigned long long *ring = reinterpret_cast<unsigned long long *>(carry); // 128 entries of {owner | slot << 8, triangle}
 			[[maybe_unused]] uint32_t ring_head = 0u, ring_tail = 0u;
 			[[maybe_unused]] const RMD_GLOBAL double *spheres = as_global(g.tri_sph);
@@ -780,79 +712,18 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 				if (count_events && lane == 0) atomicAdd(&dbg[17], (unsigned long long)__popcll(pm));
 				if (ring_tail - ring_head >= 64u) full();
 			};
-			// RMD_SPHERE_AHEAD: the same with the NEXT chunk's spheres requested while this chunk is tested.  The chunk loop is what a walk's time is
-			// (DIAG phase clocks of render_wave_queued: the chunks are ~85 % of a walk call, the walks ~60 % of the kernel) and what it waits for is the
-			// 32-byte gather of each pair's sphere — scattered over 3.2 MB, behind an L2 that the scene's tables overflow.  pretest() requests a
-			// chunk's spheres where it needs them (under the ray fetch and the search of the chunk after next: half a chunk of cover); here the
-			// search comes first, then the request for the spheres of the chunk that is tested NEXT (its triangle indices were requested a chunk
-			// ago), then this chunk's tests on the spheres the previous chunk requested: a whole chunk of cover for 8 more live registers.
-			struct Sph {
-				V3 c;
-				double r2a;
-			};
-			[[maybe_unused]] auto load_sph = [&](uint32_t tri) {
-				const RMD_GLOBAL double *sp = spheres + (size_t)tri * 4u;
-				Sph sph;
-				sph.c = ld3(sp), sph.r2a = sp[3];
-				return sph;
-			};
-			[[maybe_unused]] auto pretest_ahead = [&](uint32_t base, uint32_t &own_x, uint32_t &tri_x, const Sph &cur, const uint32_t &tri_next, Sph &next, bool have_next) {
-				const uint32_t w = base + lane;
-				const uint32_t tri = tri_x, own_now = own_x;
-				if (base + 64u * ahead < total) search(base + 64u * ahead, own_x, tri_x);
-				if (have_next) next = load_sph(tri_next);
-				const int src = (int)((own_now & 63u) << 2);
-				const V3 pro = mk(bperm_f64(src, ro.x), bperm_f64(src, ro.y), bperm_f64(src, ro.z));
-				const V3 prd = mk(bperm_f64(src, rd.x), bperm_f64(src, rd.y), bperm_f64(src, rd.z));
-				const bool pass = w < total && sphere_pretest(cur.c, cur.r2a, sph_kb, pro, prd);
-#if RMD_DIAG
-				if (count_events && (debug_flags & 64u)) { // cross-check: a pair the pre-test drops must fail the reference's test (dbg[16] stays 0)
-					const TriRecord r = load_record(recs + (size_t)tri * kTriRecStride);
-					double tt;
-					const bool hh = triangle_intersect(r.v0, r.e1, r.e2, pro, prd, tt) && w < total;
-					const unsigned long long bad = __ballot(hh && !pass);
-					if (bad != 0ull && lane == 0) atomicAdd(&dbg[16], (unsigned long long)__popcll(bad));
-				}
-#endif
-				const unsigned long long pm = __ballot(pass);
-				if (pass) ring[(ring_tail + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u))) & 127u] = (unsigned long long)own_now | ((unsigned long long)tri << 32);
-				ring_tail += (uint32_t)__popcll(pm);
-				if (count_events && lane == 0) atomicAdd(&dbg[17], (unsigned long long)__popcll(pm));
-				if (ring_tail - ring_head >= 64u) full();
-			};
-#ifndef RMD_SPHERE_AHEAD
-#define RMD_SPHERE_AHEAD 0 // measured (round 6): 38 spilled registers for 7 in the queued mesh kernel (53 for 11 in the lane-per-path one), C3 at 200 spp 130.6 ms against 123.4: not used
-#endif
 			uint32_t own_a = 0, tri_a = 0;
 			search(0u, own_a, tri_a);
-			if constexpr (DEEP && RMD_SPHERE_PREFILTER) {
+			if constexpr (DEEP) {
 				static_assert(sizeof(WalkCarry) >= 128u * sizeof(unsigned long long), "the ring of pairs that passed the pre-test lives in the wave's WalkCarry");
-				uint32_t own_b = 0, tri_b = 0;
-				if (64u < total) search(64u, own_b, tri_b);
-				if constexpr (RMD_SPHERE_AHEAD && ahead == 2u) {
-					Sph sph_a = load_sph(tri_a), sph_b;
-					RMD_UNDEF(sph_b.c.x) RMD_UNDEF(sph_b.c.y) RMD_UNDEF(sph_b.c.z) RMD_UNDEF(sph_b.r2a)
-					for (uint32_t base = 0; base < total; base += 128u) {
-						pretest_ahead(base, own_a, tri_a, sph_a, tri_b, sph_b, base + 64u < total);
-						if (base + 64u >= total) break;
-						pretest_ahead(base + 64u, own_b, tri_b, sph_b, tri_a, sph_a, base + 128u < total);
-					}
-				} else {
-					for (uint32_t base = 0; base < total; base += 128u) {
-						pretest(base, own_a, tri_a);
-						if (base + 64u >= total) break;
-						pretest(base + 64u, own_b, tri_b);
-					}
-				}
-				if (ring_tail != ring_head) full(); // (fewer than 64 are left: full() is run as soon as 64 wait)
-			} else if constexpr (ahead == 2u) { // two register pairs take turns (no copies: a copy would wait for the load it copies)
-				uint32_t own_b = 0, tri_b = 0;
+				uint32_t own_b = 0, tri_b = 0; // two register pairs take turns (no copies: a copy would wait for the load it copies)
 				if (64u < total) search(64u, own_b, tri_b);
 				for (uint32_t base = 0; base < total; base += 128u) {
-					chunk(base, own_a, tri_a);
+					pretest(base, own_a, tri_a);
 					if (base + 64u >= total) break;
-					chunk(base + 64u, own_b, tri_b);
+					pretest(base + 64u, own_b, tri_b);
 				}
+				if (ring_tail != ring_head) full(); // (fewer than 64 are left: full() is run as soon as 64 wait)
 			} else {
 				for (uint32_t base = 0; base < total; base += 64u) chunk(base, own_a, tri_a);
 			}

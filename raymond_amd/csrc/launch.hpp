@@ -44,23 +44,14 @@ constexpr uint32_t kSampleStride = 4;
 // walk batching (kernels.hip): lanes of a wave that must be waiting for a grid walk before one is run
 constexpr uint32_t kWalkBatchDefault = 32;
 // fewest samples per pixel a work item of a split launch of a grid scene may hold (api.cpp: choose_split; RMD_TUNE_SPLIT_MIN_SAMPLES overrides)
-#ifndef RMD_SPLIT_MIN_SAMPLES_GRID
-#define RMD_SPLIT_MIN_SAMPLES_GRID 4
-#endif
-constexpr uint32_t kSplitMinSamplesGrid = RMD_SPLIT_MIN_SAMPLES_GRID;
+constexpr uint32_t kSplitMinSamplesGrid = 4;
 // scenes without grids: fewest samples per pixel a launch that is too short to split runs as ONE buffered item per wave tile (role-sorted trips)
 // instead of in direct mode (api.cpp: choose_split)
-#ifndef RMD_SORTED_MIN_SAMPLES
-#define RMD_SORTED_MIN_SAMPLES 128
-#endif
-constexpr uint32_t kSortedMinSamples = RMD_SORTED_MIN_SAMPLES;
+constexpr uint32_t kSortedMinSamples = 128;
 // split launches of scenes with grids of at most this many samples per pixel run the instantiation whose waves chain their work items: all of
 // them since the round's second half (the chained instantiation used to spill 27 registers against 15 and lost 2.6 % at 500 samples per pixel —
 // hence a limit of 96 —; at 11 against 9 it wins at every size: C3 at 128 / 200 / 500 spp 101.7 / 157.2 / 387.8 -> 98.9 / 154.1 / 384.5 ms)
-#ifndef RMD_CHAIN_MAX_SAMPLES
-#define RMD_CHAIN_MAX_SAMPLES 0x7FFFFFFF
-#endif
-constexpr uint32_t kChainMaxSamples = RMD_CHAIN_MAX_SAMPLES;
+constexpr uint32_t kChainMaxSamples = 0x7FFFFFFF;
 // walks put aside (grid_walk.hpp: cut_lanes): a walk call leaves its last K walkers to the wave's next call
 constexpr uint32_t kWalkCutDefault = 7; // (round 6: 4 -> 7 — the queued form's walks have 60 rays: C3 at 200 spp 120.1 -> 118.9 ms; the lane-per-path form times within 1 % for 2 .. 12)
 // largest |roughness| a material may have: keeps the GGX sampling angle below 2^45 (device_core.hpp, sincos_cw)
@@ -69,28 +60,15 @@ constexpr double kMaxRoughness = 512.0;
 constexpr double kMinRoughness = 1e-12;
 // waves per workgroup of the grid instantiation (they share the LDS occupancy masks)
 // 4-wave workgroups: 4 of them (16 waves) fit a CU's LDS beside their staged masks and retire at a finer grain than 8-wave ones
-#ifndef RMD_GRID_WAVES
-#define RMD_GRID_WAVES 4
-#endif
-constexpr uint32_t kGridWavesPerWg = RMD_GRID_WAVES;
+constexpr uint32_t kGridWavesPerWg = 4;
 // waves of a persistent workgroup (one per CU: all 16 wave slots that 128 registers per lane leave)
 constexpr uint32_t kPersistWavesPerWg = 16;
-#ifndef RMD_GRID_PERSIST_WAVES
-#define RMD_GRID_PERSIST_WAVES 16
-#endif
-constexpr uint32_t kGridPersistWavesPerWg = RMD_GRID_PERSIST_WAVES; // ... of the grid instantiation
+constexpr uint32_t kGridPersistWavesPerWg = 16; // ... of the grid instantiation
 // the spheres kernel's split launches (render_kernel.hpp: render_wave_sorted): path slots of a wave's pool and waves of a persistent workgroup —
 // 16 pools of 112 slots (86 bytes each) and the object table fit the CU's 160 KB
-#ifndef RMD_SORT_SLOTS
-#define RMD_SORT_SLOTS 120
-#endif
-#ifndef RMD_SORT_WAVES
-#define RMD_SORT_WAVES 16 // waves of one persistent workgroup
-#endif
-#ifndef RMD_SORT_WGS_PER_CU
-#define RMD_SORT_WGS_PER_CU 1 // persistent workgroups per CU (a workgroup holds at most 16 waves)
-#endif
-constexpr size_t kSortPoolBytes = 84u * RMD_SORT_SLOTS; // per-wave LDS (sizeof(HitStack): 9 doubles + 3 words an entry)
+constexpr uint32_t kSortSlots = 120;
+constexpr uint32_t kSortedWavesPerWg = 16; // waves of one persistent workgroup (one per CU)
+constexpr size_t kSortPoolBytes = 84u * kSortSlots; // per-wave LDS (sizeof(HitStack): 9 doubles + 3 words an entry)
 // every wave's LDS area ends with 16 bytes of bookkeeping (render_kernel.hpp: word 0 = 1 + the work item a persistent wave drew last)
 constexpr size_t kWaveHeadBytes = 16u;
 // the form a render launch was made in (render_kernel.hpp: launch_render) -> rmd_launch_info
@@ -98,10 +76,7 @@ struct LaunchShape {
 	uint32_t persistent = 0, waves_per_wg = 0, queued = 0, resident_waves = 0;
 };
 // paths a wave of the queued form may have in flight (render_kernel.hpp: render_wave_queued; at least 192, a multiple of 64)
-#ifndef RMD_QUEUE_PATHS
-#define RMD_QUEUE_PATHS 256
-#endif
-constexpr uint32_t kQueuePaths = RMD_QUEUE_PATHS;
+constexpr uint32_t kQueuePaths = 256;
 inline size_t path_queue_bytes_host(uint32_t cap) { return (size_t)cap * (9u * 8u + 13u * 8u + 4u * 4u + 9u * 4u); } // (render_kernel.hpp: path_queue_bytes)
 static_assert(kQueuePaths >= 192u && kQueuePaths % 64u == 0u, "two stacks short of a full trip + the 64 paths of a generation trip");
 size_t render_lds_bytes(uint32_t n_objects, uint32_t mask_words_total, uint32_t waves_per_wg);

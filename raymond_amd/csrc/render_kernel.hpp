@@ -47,16 +47,6 @@ RMD_DEV void report_fault(const RenderParams &P, uint32_t code, uint32_t detail)
 		if (P.work_counter != nullptr) __hip_atomic_fetch_or(P.work_counter, kWorkCounterPoison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
 }
-// (A/B switches for tools/ab_multi.sh: what the bounds cost — 0 compiles a check out)
-#ifndef RMD_BOUND_TRIPS
-#define RMD_BOUND_TRIPS 1
-#endif
-#ifndef RMD_FLAT_OBJECT_TESTS
-#define RMD_FLAT_OBJECT_TESTS 1
-#endif
-#ifndef RMD_BOUND_DRAWS
-#define RMD_BOUND_DRAWS 1
-#endif
 // render_wave_sorted: trips a wave may take per (pixel, sample) pair of its work item, as if ONE lane ran them all one after the other (a path has
 // at most RMD_MAX_BOUNCE_LIMIT segments and one more trip ends it; a wave runs its pairs 64 at a time, so a real item takes a fraction of this).
 constexpr uint32_t kTripBoundPerPair = RMD_MAX_BOUNCE_LIMIT_DEV + 4u;
@@ -75,7 +65,6 @@ RMD_DEV int scene_intersect_wave(const DevObject *__restrict__ objs, uint32_t n_
 	int best = -1;
 	uint32_t sub = 0;
 	axis_pairs_visit(objs, n_objects, axis_pairs, want, ro, rd, closest, best, arbitrary_rays); // (the room's walls: scene_split.hpp; `sub` stays 0 for a plane)
-#if RMD_FLAT_OBJECT_TESTS
 	if constexpr (!GRID) {
 		// without grid objects: tests without control flow, the running minimum updated by selects (device_core.hpp: *_test_flat)
 		for (uint32_t i = next_turn(~0u, turns); i < n_objects; i = next_turn(i, turns)) {
@@ -102,7 +91,6 @@ RMD_DEV int scene_intersect_wave(const DevObject *__restrict__ objs, uint32_t n_
 		t_best = closest, sub_best = 0u;
 		return best;
 	}
-#endif
 	for (uint32_t i = next_turn(~0u, turns); i < n_objects; i = next_turn(i, turns)) {
 		const DevObject &o = objs[i];
 		// planes and spheres: the hit is consumed where it is found (device_core.hpp: *_visit)
@@ -142,74 +130,34 @@ RMD_DEV int scene_intersect_wave(const DevObject *__restrict__ objs, uint32_t n_
 // A walk is run when RenderParams::walk_batch lanes of the wave wait for one (launch.hpp: kWalkBatchDefault = 32; with the persistent
 // workgroups 40 / 24 / 6 / look-ahead 16 measured 1.7 % faster on the benchmark mesh than round 1's 32 / 16 / 4 / 12),
 // ... or fewer than this many lanes could do anything else on this trip (a trip costs the same for 5 lanes as for 50)
-#ifndef RMD_WALK_MIN_RUNNABLE
-#define RMD_WALK_MIN_RUNNABLE 24
-#endif
-constexpr uint32_t kWalkMinRunnable = RMD_WALK_MIN_RUNNABLE;
+constexpr uint32_t kWalkMinRunnable = 24;
 // ... or this many trips have passed since the wave's last walk (scenes where few rays reach a grid: bounds the wait)
-#ifndef RMD_WALK_MAX_WAIT
-#define RMD_WALK_MAX_WAIT 6
-#endif
-constexpr uint32_t kWalkMaxWait = RMD_WALK_MAX_WAIT;
+constexpr uint32_t kWalkMaxWait = 6;
 // walks put aside (grid_walk.hpp: cut_lanes = RenderParams::walk_cut): only in calls with at least this many walkers ...
-#ifndef RMD_WALK_CUT_MIN_WALKERS
-#define RMD_WALK_CUT_MIN_WALKERS 16
-#endif
-constexpr uint32_t kWalkCutMinWalkers = RMD_WALK_CUT_MIN_WALKERS;
+constexpr uint32_t kWalkCutMinWalkers = 16;
 // ... while at least this many lanes of the wave have something else to do
-#ifndef RMD_WALK_CUT_MIN_RUNNABLE
-#define RMD_WALK_CUT_MIN_RUNNABLE 0
-#endif
-constexpr uint32_t kWalkCutMinRunnable = RMD_WALK_CUT_MIN_RUNNABLE;
+constexpr uint32_t kWalkCutMinRunnable = 0;
 
 // Occupancy targets (waves per SIMD), measured on MI355X: the grid walk is latency-bound and gains 1.6x from 4 waves/SIMD
 // (128 VGPRs, a few dozen spills) over 2; the grid-less kernel is VALU-bound and is fastest at 3 (168 VGPRs).
-#ifndef RMD_GRID_MINW
-#define RMD_GRID_MINW 4
-#endif
-#ifndef RMD_NOGRID_MINW
-#define RMD_NOGRID_MINW 3
-#endif
+constexpr uint32_t kGridMinWaves = 4, kNoGridMinWaves = 3;
 // MODE: 0 = wave tiles, the lane keeps its pixel's sum (one wave per tile); 1 = wave tiles with the samples of a tile split
 // over several waves, every sample's radiance stored to the sample buffer for sum_kernel; 2 = explicit (x, y, sample) list.
 // (A template parameter rather than a launch parameter: the buffer mode then carries no accumulator and the direct mode no
 // buffer addressing — the grid kernel runs at its register limit.)
 enum { kModeTiles = 0, kModeTilesBuffered = 1, kModeList = 2 };
-#ifndef RMD_TRIP_RELOAD
-#define RMD_TRIP_RELOAD 1
-#endif
 // A finished sample into its 32-byte sector of the per-sample buffer (spheres kernel).  Plain stores; the end of a work item releases them at
 // agent scope (finish_sample_range) — on this part that writes back every dirty line of the XCD's L2 (buffer_wbl2) and is what a work item
 // costs at its end: 66.4 ms per C2 frame at 16 items per wave tile against 53.5 at 4, 53.4 / 53.3 with the fence taken out (timing only).
-// RMD_SAMPLE_STORE_WT = 1 is the measured alternative: two WRITE-THROUGH stores (sc1: the data goes to memory at once and leaves no dirty line),
-// the wave then only waits for its own stores (vmcnt(0)) before it bumps the tile's counter.  Bit-identical (all tests, tools/stress_sum.py), the
-// frame time no longer depends on the item size (54.2 ms at 7 .. 16 items per wave tile) — but the full frame is 1.3 % slower than plain stores at
-// their best item size (same box: 54.2 vs 53.5 ms; an N = 8 tile share 7.16 vs 7.42 ms): the default stays plain stores + release.
-#ifndef RMD_SAMPLE_STORE_WT
-#define RMD_SAMPLE_STORE_WT 0
-#endif
-RMD_DEV void store_sample(RMD_GLOBAL double *dst, V3 L) {
-#if RMD_SAMPLE_STORE_WT == 2 // non-temporal stores (what the queued mesh kernel uses: its samples are read by another kernel) — here the samples are read back by a wave of THIS kernel
-	__builtin_nontemporal_store(L.x, dst), __builtin_nontemporal_store(L.y, dst + 1), __builtin_nontemporal_store(L.z, dst + 2);
-#elif RMD_SAMPLE_STORE_WT
-	typedef double d2 __attribute__((ext_vector_type(2)));
-	const d2 xy = {L.x, L.y};
-	asm volatile("global_store_dwordx4 %0, %1, off sc1\n\tglobal_store_dwordx2 %0, %2, off offset:16 sc1" : : "v"(dst), "v"(xy), "v"(L.z) : "memory");
-#else
-	dst[0] = L.x, dst[1] = L.y, dst[2] = L.z;
-#endif
-}
+// Write-through stores that leave no dirty line were measured 1.3 % slower over the full frame (54.2 vs 53.5 ms).
+RMD_DEV void store_sample(RMD_GLOBAL double *dst, V3 L) { dst[0] = L.x, dst[1] = L.y, dst[2] = L.z; }
 // The end of a (wave tile, sample range) work item of the spheres kernel: the wave that finishes a wave tile's LAST sample range adds the tile's
 // samples to the pixels, strictly in sample order (src/trace.rs:203: the reference's sequential sum, bit for bit) — inside the render kernel, where
 // the reads (bandwidth) overlap the other waves' arithmetic; as a kernel of its own the sum cost 5.5 ms per 1080p / 500 spp frame.  Release: an
 // agent-scope fence writes this wave's sample stores back before its count; acquire: the last wave invalidates its caches before it reads.
 RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, uint32_t wt, uint32_t lane, double *__restrict__ out) {
 	if (P.tile_done == nullptr || wt >= P.n_work) return;
-#if RMD_SAMPLE_STORE_WT == 1
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's write-through sample stores have reached memory before its count is seen
-#else
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // this wave's samples leave the XCD's L2 before its count is seen
-#endif
 	uint32_t before = 0;
 	if (lane == 0u) before = __hip_atomic_fetch_add(P.tile_done + wt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	before = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
@@ -391,24 +339,20 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 		// carried in scalar registers across trips — the grid kernel was spilling scalars into vector lanes all through the trip (168
 		// v_readlane / v_writelane at trip level, 41 now; 496.4 -> 487.3 ms on C3), the spheres kernel less so (112.2 -> 110.6 ms on
 		// C2).  The empty asm keeps the compiler from hoisting the loads out of the loop.
-		auto trip_params = [&]() -> decltype(auto) {
-			if constexpr (RMD_TRIP_RELOAD) {
-				// `kernarg_params`: where the calling kernel's RenderParams argument lies in its kernel-argument segment (the kernel, which knows its
-				// own signature, passes it: KernargWords below)
-				KernargWords src = kernarg_params;
-				asm volatile("" : "+s"(src));
-				static_assert(sizeof(RenderParams) % 8 == 0, "copied in 8-byte words");
-				unsigned long long w[sizeof(RenderParams) / 8];
+		// `kernarg_params`: where the calling kernel's RenderParams argument lies in its kernel-argument segment (the kernel, which knows its
+		// own signature, passes it: KernargWords below)
+		auto trip_params = [&]() {
+			KernargWords src = kernarg_params;
+			asm volatile("" : "+s"(src));
+			static_assert(sizeof(RenderParams) % 8 == 0, "copied in 8-byte words");
+			unsigned long long w[sizeof(RenderParams) / 8];
 #pragma unroll
-				for (unsigned i = 0; i < sizeof(RenderParams) / 8; i++) w[i] = src[i];
-				RenderParams copy;
-				__builtin_memcpy(&copy, w, sizeof(copy));
-				return copy; // by value; only the fields a trip uses are loaded
-			} else {
-				return (P);
-			}
+			for (unsigned i = 0; i < sizeof(RenderParams) / 8; i++) w[i] = src[i];
+			RenderParams copy;
+			__builtin_memcpy(&copy, w, sizeof(copy));
+			return copy; // by value; only the fields a trip uses are loaded
 		};
-		decltype(auto) Pt = trip_params();
+		RenderParams Pt = trip_params();
 		if constexpr (CHAIN) {
 			// the item's pool has run dry: the wave draws its next work item (the persistent work loop's draw, render_kernel below, with the same
 			// bound: a draw must be larger than the wave's last).  pool_items = 0xFFFFFFFF marks "the launch has no item left".
@@ -428,9 +372,7 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 				if (drawn >= Pt.n_work * Pt.split_k) {
 					pool_items = 0xFFFFFFFFu, next_item = 0xFFFFFFFFu;
 				} else {
-#if RMD_BOUND_DRAWS
 					if (RMD_UNLIKELY(drawn < floor)) report_fault(Pt, kFaultWorkLoop, drawn); // (never reached; the poisoned counter ends the launch)
-#endif
 					wt = drawn / Pt.split_k;
 					const uint32_t part = drawn - wt * Pt.split_k;
 					tile = reinterpret_cast<const WaveTile *>(work)[wt];
@@ -441,7 +383,6 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 				}
 			}
 		}
-#if RMD_BOUND_TRIPS
 		// (no `break` here: a second way out of this loop cost the mesh kernel 40 spilled registers.  A stalled wave reports, drops every path
 		// and pair it holds and leaves through the loop's own exit below.)
 		trips_since_walk += 0x100u;
@@ -453,7 +394,6 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 			else if constexpr (to_buffer) next_item = pool_items;
 			else s = s_end;
 		}
-#endif
 		// ---------------- (C) the hits the previous trip found (`complete`): miss, emission, or a surface to shade.  The loop is entered here: a
 		// trip is (C) classification -> (B) hand-out and next rays -> (A) intersection; a surface classified here is shaded a few lines
 		// further down, with nothing but the hand-out in between (the mesh kernel: two spilled registers instead of four).
@@ -710,14 +650,7 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 // sample, the samples are added in order afterwards).  A generation trip runs while the stack has room for the 64 hits it may park, so a
 // shading trip finds more than kSortSlots - 64 hits (57 .. 64 lanes at 120 entries) until the item runs out of pairs; the remaining hits are
 // then shaded in ever smaller trips.
-#ifndef RMD_SORT_OBJ_PRIO
-#define RMD_SORT_OBJ_PRIO 1 // s_setprio level of the closest-hit loop over the objects in the role-sorted spheres kernel (0 = not raised)
-#endif
-constexpr int kSortObjPrio = RMD_SORT_OBJ_PRIO;
-#ifndef RMD_SORTED_TRIPS
-#define RMD_SORTED_TRIPS 1
-#endif
-constexpr uint32_t kSortSlots = RMD_SORT_SLOTS; // (launch.hpp)
+constexpr int kSortObjPrio = 1; // s_setprio level of the closest-hit loop over the objects in the role-sorted spheres kernel
 // The wave's parked hits: a dense STACK in LDS (round 5; round 4 kept a path in a fixed slot of a pool and two lists of slot numbers).  A hit is
 // pushed where the stack ends — the lanes of a trip that park write to consecutive entries — and a shading trip pops the top 64, lane i entry
 // n_hit - 64 + i: every access of a trip is 64 consecutive 8-byte (or 4-byte) words, the one pattern the LDS serves without a bank conflict
@@ -732,8 +665,6 @@ struct alignas(16) HitStack {
 static_assert(kSortSlots >= 72u && kSortSlots <= 512u && kSortSlots % 8u == 0u, "a generation trip needs room for 64 more hits");
 static_assert(sizeof(HitStack) == kSortPoolBytes, "launch.hpp: kSortPoolBytes");
 using SortPool = HitStack;
-// waves of a persistent workgroup of this kernel: 16 stacks + the object table fit the CU's 160 KB
-constexpr uint32_t kSortedWavesPerWg = RMD_SORT_WAVES;
 
 // A register pair the compiler may fill with anything: the value of a variable in the lanes that never use it.
 #define RMD_UNDEF3(v) RMD_UNDEF(v.x) RMD_UNDEF(v.y) RMD_UNDEF(v.z)
@@ -760,10 +691,6 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 #endif
 	for (;;) {
 		// the launch parameters a trip needs, re-read from the kernel arguments (see render_wave)
-#ifndef RMD_SORT_RELOAD
-#define RMD_SORT_RELOAD 1
-#endif
-#if RMD_SORT_RELOAD
 		KernargWords src = kernarg_params;
 		asm volatile("" : "+s"(src));
 		unsigned long long w[sizeof(RenderParams) / 8];
@@ -771,19 +698,15 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		for (unsigned i = 0; i < sizeof(RenderParams) / 8; i++) w[i] = src[i];
 		RenderParams Pt;
 		__builtin_memcpy(&Pt, w, sizeof(Pt));
-#else
-		const RenderParams &Pt = P;
-#endif
 
 		// Which kind of trip.  A generation trip (64 new samples) needs room for the 64 hits it may park: it runs while the item has pairs and
 		// the stack holds at most kSortSlots - 64 hits; else the top min(n_hit, 64) hits are shaded — more than kSortSlots - 64 of them (57 .. 64
-		// lanes at 120 entries) unless the item has run out of pairs, when what is left is shaded in ever smaller trips.  (RMD_SORT_FULL_SI = 1
-		// is the other way round — shading trips only when 64 hits wait, generation trips of min(64, kSortSlots - n_hit) pairs: measured 0.4 %
-		// slower on C2, 0.8 % with every path traced.)
-		// Every trip makes progress, for every stack size the static_assert admits: a generation trip hands out 64 pairs (kSortSlots - n_hit >= 9
-		// with RMD_SORT_FULL_SI) — next_item grows; a shading trip runs when no pair is left (n_hit > 0 then, else the loop has ended) or n_hit >
-		// kSortSlots - 64 >= 8 (>= 64), so at least one path advances by a segment, and a path has at most bounce_limit of them.  There is no
-		// state in which a trip runs with no lane —
+		// lanes at 120 entries) unless the item has run out of pairs, when what is left is shaded in ever smaller trips.  (The other way round —
+		// shading trips only when 64 hits wait, generation trips of min(64, kSortSlots - n_hit) pairs — measured 0.4 % slower on C2, 0.8 % with
+		// every path traced.)
+		// Every trip makes progress, for every stack size the static_assert admits: a generation trip hands out 64 pairs — next_item grows; a
+		// shading trip runs when no pair is left (n_hit > 0 then, else the loop has ended) or n_hit > kSortSlots - 64 >= 8, so at least one path
+		// advances by a segment, and a path has at most bounce_limit of them.  There is no state in which a trip runs with no lane —
 		// unlike a pool with THREE lists, where all three can be short of a full trip while the empty list holds nothing
 		// (tools/experiments/README.md: the run that was killed for silence in round 4).
 		if (RMD_UNLIKELY(trips_left-- == 0ull)) { // (never reached: see above) — the wave reports, drops what it holds and leaves through the loop's own exit
@@ -792,10 +715,7 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		}
 		const bool items_left = next_item < pool_items;
 		if (n_hit == 0u && !items_left) break;
-#ifndef RMD_SORT_FULL_SI
-#define RMD_SORT_FULL_SI 0
-#endif
-		const bool shade_trip = !items_left || (RMD_SORT_FULL_SI ? n_hit >= 64u : n_hit > kSortSlots - 64u);
+		const bool shade_trip = !items_left || n_hit > kSortSlots - 64u;
 		bool active;
 		uint32_t item = 0, depth = 1;
 		Rng rng;
@@ -822,13 +742,9 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			const V3 frag = mk(stack.frag[0][e], stack.frag[1][e], stack.frag[2][e]);
 			const uint32_t x = tile.x0 + (item & 7u), y = tile.y0 + ((item >> 3) & 7u);
 			rng.pixel = y * Pt.W + x, rng.sample = Pt.sample_begin + pool_first + (item >> 6);
-#if RMD_SORT_PREDICATED_ARMS
-			if (active) {
-#else
 			{ // every lane shades — a lane beyond the trip's n the stack's entry 0, a hit of this work item like any other; what it computes is never
 			  // stored (`active` gates everything below).  Shading under `if (active)` made ro, rd and T values that are assigned inside a divergent
 			  // branch: nine 64-bit copies of the other lanes' undefined values per trip.
-#endif
 				shade(Pt, normal, frag, ld3(o.color), o.roughness, o.metalness, cam_pos, rng, ro, rd, T);
 				depth++;
 				// (see render_wave: a path whose throughput is exactly zero is ended unless the caller traces such paths on)
@@ -837,18 +753,13 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			}
 		} else {
 			// ---------------- GI: the work item's next 64 (pixel, sample) pairs, one per lane (slots outside a ragged tile are skipped)
-			const uint32_t room = kSortSlots - n_hit, n = RMD_SORT_FULL_SI && room < 64u ? room : 64u;
 			item = next_item + lane;
-			next_item += n;
-			active = lane < n && item < pool_items && (item & 7u) < tile.w && ((item >> 3) & 7u) < tile.h;
+			next_item += 64u;
+			active = item < pool_items && (item & 7u) < tile.w && ((item >> 3) & 7u) < tile.h;
 			const uint32_t x = tile.x0 + (item & 7u), y = tile.y0 + ((item >> 3) & 7u);
 			rng.pixel = y * Pt.W + x, rng.sample = Pt.sample_begin + pool_first + (item >> 6);
 			T = mk(1.0, 1.0, 1.0);
-#if RMD_SORT_PREDICATED_ARMS
-			if (active) {
-#else
 			{ // (likewise: a lane without a pair computes the ray of a pixel position outside the tile, which nobody reads)
-#endif
 				double u0, u1;
 				rng.next2(Pt.key0, Pt.key1, u0, u1); // block 0: the pixel jitter (:326-327)
 				primary_ray(Pt, x, y, u0, u1, ro, rd);
@@ -860,10 +771,10 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		double t = 0.0;
 		uint32_t sub = 0;
 		// (the object loop is a chain of scalar loads with a few vector instructions behind each: at a raised priority it is through sooner and the SIMD's
-		// other waves fill what it leaves with their shading — RMD_SORT_OBJ_PRIO, measured −1.7 %)
-		if constexpr (kSortObjPrio != 0) __builtin_amdgcn_s_setprio(kSortObjPrio);
+		// other waves fill what it leaves with their shading — measured −1.7 %)
+		__builtin_amdgcn_s_setprio(kSortObjPrio);
 		const int oi = scene_intersect_wave<false>(objs, Pt.n_objects, grids, nullptr, *no_scratch, want, ro, rd, t, sub, Pt.axis_pairs, 0u, nullptr, false, Pt.visit_mask);
-		if constexpr (kSortObjPrio != 0) __builtin_amdgcn_s_setprio(0);
+		__builtin_amdgcn_s_setprio(0);
 		// ---------------- classification (the rules of render_wave's phase C)
 		bool terminal = failed, park = false, emitted = false;
 		V3 frag, normal;
@@ -957,38 +868,21 @@ RMD_DEV uint32_t sample_of_sector(const RenderParams &P, uint32_t sector) {
 constexpr uint32_t kQueuedTripBoundPerPath = 2u * RMD_MAX_BOUNCE_LIMIT_DEV + 4u; // trips per path, as if ONE lane ran them all: a segment is at most a SHADE and a WALK trip
 // LDS of a wave of the queued form: the walk scratch, the walk's carry area (grid_walk.hpp: WalkCarry — during a call the ring of its pre-test; around a
 // call the DDA states of the walks it takes up / puts aside, on their way from / to the ray stack), per lane what a walking path does not need
-// during its walk (throughput, RNG state: 32 bytes a lane), then the head — 7,184 bytes: 16 waves beside the benchmark mesh's 36.7 KB of masks
-#ifndef RMD_QUEUE_SIDE_ALL
-#define RMD_QUEUE_SIDE_ALL 1 // 1: pixel and sector wait in LDS too (40 bytes a lane: 7,696 bytes a wave, 16 waves beside the benchmark mesh's masks) instead of being fetched again behind the walk
-#endif
-constexpr size_t kQueuedSideBytes = 64u * (3u * sizeof(double) + (RMD_QUEUE_SIDE_ALL ? 4u : 2u) * sizeof(uint32_t));
+// during its walk (throughput, RNG state, pixel and sector: 40 bytes a lane), then the head — 7,696 bytes: 16 waves beside the benchmark mesh's
+// 36.7 KB of masks
+constexpr size_t kQueuedSideBytes = 64u * (3u * sizeof(double) + 4u * sizeof(uint32_t));
 constexpr size_t kQueuedDiagBytes = RMD_DIAG ? 24u * sizeof(unsigned long long) : 0u; // DIAG builds: the wave's phase clocks (RMD_DEBUG = 16)
 __host__ __device__ inline size_t queued_wave_lds_bytes() { return sizeof(WalkScratch) + sizeof(WalkCarry) + kQueuedSideBytes + kQueuedDiagBytes + kWaveHeadBytes; }
 
-// Queue traffic is non-temporal (RMD_QUEUE_NT): an entry is written once and read once, the waves' working set is several times the L2, and what it
-// displaces there are the scene's tables, which every walk gathers from (measured with plain accesses: L2 hit rate 73 -> 59 %, mean L1 -> L2 read
-// latency 227 -> 373 cycles against the lane-per-path form).
-#ifndef RMD_QUEUE_NT
-#define RMD_QUEUE_NT 0
-#endif
-#ifndef RMD_SAMPLE_NT
-#define RMD_SAMPLE_NT 1
-#endif
+// Queue entries are read and written with plain accesses: the tops of the stacks are read back from the L2 (non-temporal accesses measured
+// 176.7 against 135.2 ms).
 template <class T>
 RMD_DEV T qld(const RMD_GLOBAL T *p) {
-#if RMD_QUEUE_NT
-	return __builtin_nontemporal_load(p);
-#else
 	return *p;
-#endif
 }
 template <class T, class U>
 RMD_DEV void qst(RMD_GLOBAL T *p, U v) {
-#if RMD_QUEUE_NT
-	__builtin_nontemporal_store((T)v, p);
-#else
 	*p = (T)v;
-#endif
 }
 RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_params, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids,
                                 const void *__restrict__ work, const DevObject *lobjs, const uint32_t *lds_masks, unsigned char *wave_lds, uint32_t first_item) {
@@ -1040,22 +934,16 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 #if RMD_DIAG
 	if (P.debug_flags & 32u) trips_left = 1ull; // tests/test_gpu_faults.py: forces the bound
 #endif
-	// Hits HELD in their lanes (RMD_QUEUE_HOLD_HITS).  A hit that a trip has classified goes onto the hit stack and comes back off it for the SHADE trip
+	// Hits HELD in their lanes.  A hit that a trip has classified goes onto the hit stack and comes back off it for the SHADE trip
 	// that takes it — 92 bytes written and 92 read through an L2 that the queues' working set overflows several times (measured: L2 hit rate
 	// 73 -> 59 %, L1 -> L2 read latency 227 -> 373 cycles against the lane-per-path form).  When the very next trip is a SHADE trip anyway — no full
 	// walk waits, and the stack's hits and this trip's together fill a trip — this trip's hits stay where they are, in their lanes' registers, and
 	// the SHADE trip pops only what it needs to fill the other lanes.  Same trips, same lanes per trip; a hit's values are the ones it would have
 	// read back.
-#ifndef RMD_QUEUE_HOLD_HITS
-#define RMD_QUEUE_HOLD_HITS 1
-#endif
-	// Rays held likewise (RMD_QUEUE_HOLD_RAYS): when the rays a GEN / SHADE trip sends to the grids fill a WALK trip together with the stack's, they
+	// Rays held likewise: when the rays a GEN / SHADE trip sends to the grids fill a WALK trip together with the stack's, they
 	// do not travel through the stack: each waits in its lane's columns of the wave's LDS — origin, direction, closest plane / sphere hit in the walk
 	// scratch and the carry area (free between walks), the rest where a walking path keeps it anyway (the side area) — and the WALK trip pops only
 	// what fills the other lanes.
-#ifndef RMD_QUEUE_HOLD_RAYS
-#define RMD_QUEUE_HOLD_RAYS 1
-#endif
 	bool rheld = false;
 	double *stash_a = reinterpret_cast<double *>(wave_lds) + lane;                        // [0], [64], [128], [192]: origin, direction.x
 	int32_t *stash_oi = reinterpret_cast<int32_t *>(wave_lds + 256u * sizeof(double)) + lane; // the closest plane / sphere so far
@@ -1140,8 +1028,8 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 		// (the stacks' counters are wave-uniform by construction; said once per trip, because with the held hits in the loop the compiler's uniformity
 		// analysis gives up on them and keeps them — and every address and branch made from them — in vector registers)
 		n_hit = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_hit), n_ray = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_ray);
-		const unsigned long long held_mask = RMD_QUEUE_HOLD_HITS ? __ballot(held) : 0ull;
-		const unsigned long long rheld_mask = RMD_QUEUE_HOLD_RAYS ? __ballot(rheld) : 0ull;
+		const unsigned long long held_mask = __ballot(held);
+		const unsigned long long rheld_mask = __ballot(rheld);
 		if (rheld_mask != 0ull) kind = kWalk;      // (decided when the rays were held: the stack's rays and the held ones fill the trip)
 		else if (held_mask != 0ull) kind = kShade; // (likewise the hits)
 		else if (n_ray >= 64u) kind = kWalk;
@@ -1179,9 +1067,7 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 				// the rest of the path's state goes from its entry to the lane's column of the side area, and comes back behind the walk
 				side_d[0] = qld(&q.ray_d[6u * cap + e]), side_d[64] = qld(&q.ray_d[7u * cap + e]), side_d[128] = qld(&q.ray_d[8u * cap + e]);
 				side_w[0] = st, side_w[64] = lb;
-#if RMD_QUEUE_SIDE_ALL
 				side_w[128] = qld(&q.ray_w[2u * cap + e]), side_w[192] = qld(&q.ray_w[3u * cap + e]);
-#endif
 			} else { // a held ray: out of its lane's columns (its side-area column was filled when it was held)
 				ro = mk(stash_a[0], stash_a[64], stash_a[128]);
 				rd = mk(stash_a[192], stash_b[0], stash_b[64]);
@@ -1212,14 +1098,7 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 			rng_block = side_w[0] >> 16;
 			const uint32_t lb2 = side_w[64];
 			lobe_bits = lb2 & 0x3FFFFFu, depth = lb2 >> 24;
-			// (pixel, sample and sector are not needed before the trip's stores: fetched from the entry here — it stays as it is until this trip's own pushes —
-			// with the classification to arrive under)
-#if RMD_QUEUE_SIDE_ALL
 			pxw = side_w[128], sector = side_w[192];
-#else
-			const uint32_t e2 = n_ray + (active ? lane : 0u); // (= e, made again: one register fewer across the walk)
-			pxw = qld(&q.ray_w[2u * cap + e2]), sector = qld(&q.ray_w[3u * cap + e2]);
-#endif
 			to_ray = carried; // an unfinished walk: back onto the stack (its closest plane / sphere hit is unchanged: a walk that has found nothing yet merges nothing)
 			classify = active && !carried;
 		} else {
@@ -1295,16 +1174,14 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 			const unsigned long long pm = __ballot(to_ray);
 			// held where they are when the next trip walks them anyway: this trip's rays and the stack's fill a WALK trip (a WALK trip's own rays — the
 			// walks it puts aside — go back onto the stack: their DDA state sits in the carry area's columns)
-			rhold = RMD_QUEUE_HOLD_RAYS && kind != kWalk && pm != 0ull && n_ray + (uint32_t)__popcll(pm) >= 64u;
+			rhold = kind != kWalk && pm != 0ull && n_ray + (uint32_t)__popcll(pm) >= 64u;
 			if (rhold) {
 				if (to_ray) {
 					stash_a[0] = ro.x, stash_a[64] = ro.y, stash_a[128] = ro.z, stash_a[192] = rd.x, stash_b[0] = rd.y, stash_b[64] = rd.z, stash_b[128] = t;
 					stash_oi[0] = oi;
 					side_d[0] = T.x, side_d[64] = T.y, side_d[128] = T.z;
 					side_w[0] = (uint32_t)(oi + 1) | (rng_block << 16), side_w[64] = lobe_bits | (depth << 24);
-#if RMD_QUEUE_SIDE_ALL
 					side_w[128] = pxw, side_w[192] = sector;
-#endif
 				}
 				rheld = to_ray;
 #if RMD_DIAG
@@ -1372,17 +1249,14 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 			if (emitted) L = ld3(lobjs[oi].color); // (fetched here, outside the nest of branches that found the light)
 			L = hadamard(T, L);
 			RMD_GLOBAL double *dst = (RMD_GLOBAL double *)Pt.sample_buf + (size_t)sector * kSampleStride;
-#if RMD_SAMPLE_NT
-			__builtin_nontemporal_store(L.x, dst), __builtin_nontemporal_store(L.y, dst + 1), __builtin_nontemporal_store(L.z, dst + 2); // (written once, read by sum_kernel)
-#else
-			dst[0] = L.x, dst[1] = L.y, dst[2] = L.z;
-#endif
+			// non-temporal: written once, read by sum_kernel (measured 135.2 against 141.0 ms with plain stores)
+			__builtin_nontemporal_store(L.x, dst), __builtin_nontemporal_store(L.y, dst + 1), __builtin_nontemporal_store(L.z, dst + 2);
 		}
 		// ---------------- the hits that go on: held where they are when the next trip shades them anyway, else pushed onto the hit stack
 		{
 			const unsigned long long pm = __ballot(park);
 			const uint32_t n_park = (uint32_t)__popcll(pm);
-			const bool hold = RMD_QUEUE_HOLD_HITS && n_park != 0u && !rhold && n_ray < 64u && n_hit + n_park >= 64u; // = the rule above would select a full SHADE trip next (no rays are held: the next trip would be theirs)
+			const bool hold = n_park != 0u && !rhold && n_ray < 64u && n_hit + n_park >= 64u; // = the rule above would select a full SHADE trip next (no rays are held: the next trip would be theirs)
 			// (unconditional copies: the held values are made here for every lane, so that nothing of them is live across the trip's other phases)
 			h_frag = frag, h_normal = normal, h_T = T;
 			h_st = (uint32_t)oi | (rng_block << 16), h_lb = lobe_bits | (depth << 24), h_px = pxw, h_sector = sector;
@@ -1421,26 +1295,20 @@ RMD_DEV void render_wave_queued(const RenderParams &P, KernargWords kernarg_para
 // counter (P.work_counter, zeroed by the host) until none is left — the masks cost one copy per CU instead of one per
 // 4-wave workgroup, which leaves each wave 8 KB of LDS, and no wave slot idles while the rest of a workgroup finishes.
 template <int MODE, bool GRID>
-constexpr bool kSortedTrips = RMD_SORTED_TRIPS && MODE == kModeTilesBuffered && !GRID;
-#ifndef RMD_CHAIN_ITEMS
-#define RMD_CHAIN_ITEMS 1
-#endif
+constexpr bool kSortedTrips = MODE == kModeTilesBuffered && !GRID;
 template <int MODE, bool GRID>
-constexpr bool kChainItems = RMD_CHAIN_ITEMS && MODE == kModeTilesBuffered && GRID; // (persistent form only: render_wave, CHAIN)
+constexpr bool kChainItems = MODE == kModeTilesBuffered && GRID; // (persistent form only: render_wave, CHAIN)
 // LDS of one wave of an instantiation
 // QUEUED (persistent split launches of scenes with grids): the wave body with the paths in queues in device memory (render_wave_queued)
-#ifndef RMD_PATH_QUEUES
-#define RMD_PATH_QUEUES 1
-#endif
 template <int MODE, bool GRID>
-constexpr bool kPathQueues = RMD_PATH_QUEUES && MODE == kModeTilesBuffered && GRID;
+constexpr bool kPathQueues = MODE == kModeTilesBuffered && GRID;
 template <int MODE, bool GRID, bool QUEUED = false>
 __host__ __device__ inline size_t wave_lds_of(uint32_t n_grids) { return QUEUED ? queued_wave_lds_bytes() : kSortedTrips<MODE, GRID> ? kWaveHeadBytes + sizeof(SortPool) : wave_lds_bytes(n_grids); }
 template <int MODE, bool GRID>
 constexpr uint32_t kPersistWaves = kSortedTrips<MODE, GRID> ? kSortedWavesPerWg : GRID ? kGridPersistWavesPerWg : kPersistWavesPerWg;
 template <int MODE, bool GRID, bool PERSIST, bool CHAIN = false, bool QUEUED = false>
 __global__ __launch_bounds__(PERSIST ? 64 * (kPersistWaves<MODE, GRID>) : GRID ? 64 * kGridWavesPerWg : 64,
-                             GRID ? RMD_GRID_MINW : (kSortedTrips<MODE, GRID>) ? (RMD_SORT_WAVES * RMD_SORT_WGS_PER_CU / 4) : (PERSIST ? 4 : RMD_NOGRID_MINW)) void render_kernel(
+                             GRID ? kGridMinWaves : (kSortedTrips<MODE, GRID>) ? kSortedWavesPerWg / 4 : (PERSIST ? 4 : kNoGridMinWaves)) void render_kernel(
     RenderParams P, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids, const void *__restrict__ work, double *__restrict__ out,
     int32_t *__restrict__ path_obj, uint32_t *__restrict__ path_sub) {
 	extern __shared__ __align__(16) unsigned char smem[];
@@ -1492,13 +1360,11 @@ __global__ __launch_bounds__(PERSIST ? 64 * (kPersistWaves<MODE, GRID>) : GRID ?
 			}
 			item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
 			if (item >= n_items) break;
-#if RMD_BOUND_DRAWS
 			floor = (uint32_t)__builtin_amdgcn_readfirstlane((int)floor);
 			if (RMD_UNLIKELY(item < floor)) { // (never reached)
 				report_fault(P, kFaultWorkLoop, item);
 				break;
 			}
-#endif
 			if constexpr (QUEUED) render_wave_queued(P, kernarg_params, objs, grids, work, lobjs, lds_masks, wave_lds, item);
 			else if constexpr (kSortedTrips<MODE, GRID>) render_wave_sorted(P, kernarg_params, objs, grids, work, out, lobjs, wave_lds, item);
 			else render_wave<MODE, GRID, CHAIN>(P, kernarg_params, objs, grids, work, out, path_obj, path_sub, lobjs, lds_masks, wave_lds, item);
@@ -1537,7 +1403,7 @@ inline hipError_t launch_render(hipStream_t stream, const RenderParams &P, const
 			                                           : reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true>),
 			                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
 			if (e != hipSuccess) return e;
-			const uint32_t wgs = (n_waves + pw - 1u) / pw, resident = n_cus * (kSortedTrips<MODE, GRID> ? RMD_SORT_WGS_PER_CU : 1u);
+			const uint32_t wgs = (n_waves + pw - 1u) / pw, resident = n_cus;
 			if (queued)
 				hipLaunchKernelGGL((render_kernel<MODE, GRID, true, false, (kPathQueues<MODE, GRID>)>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs,
 				                   grids, work, out, path_obj, path_sub);

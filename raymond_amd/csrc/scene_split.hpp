@@ -15,20 +15,13 @@ namespace rmd {
 // An object loop's next turn: objects 0 .. 63 by the bits of a mask made at scene creation (RenderParams::visit_mask / grid_mask: an object the
 // loop has nothing to do for would cost it a scalar round trip to find that out), objects from 64 on one by one.  Start with i = ~0u.  All-ones =
 // every object (the probes).  The order of the turns is the index order either way.
-#ifndef RMD_VISIT_MASKS
-#define RMD_VISIT_MASKS 1
-#endif
 RMD_DEV uint32_t next_turn(uint32_t i, unsigned long long &m) {
-#if RMD_VISIT_MASKS
 	if (m != 0ull) {
 		i = (uint32_t)__builtin_ctzll(m);
 		m &= m - 1ull;
 		return i;
 	}
 	return i + 1u < 64u ? 64u : i + 1u;
-#else
-	return i + 1u;
-#endif
 }
 RMD_DEV bool lex_less(double t, int obj, double t_best, int obj_best) { return (t < t_best) | ((t == t_best) & (obj < obj_best)); } // (no short circuit: three compares and two scalar mask operations, no branch)
 // The walls of an axis-aligned room: up to three pairs of opposite planes with normals exactly +e_k / -e_k (RenderParams::axis_pairs, made by
@@ -44,22 +37,10 @@ RMD_DEV bool lex_less(double t, int obj, double t_best, int obj_best) { return (
 // Hits are merged with the lexicographic rule (distance, object index), so the order in which the planes are visited does not matter
 // (core/src/scene.rs:54-74 keeps the first object of the closest distance).
 template <int K>
-RMD_DEV void axis_pair_test(const DevObject *__restrict__ objs, [[maybe_unused]] const AxisWalls *__restrict__ walls, uint32_t j, bool want, V3 ro, V3 rd, double &closest, int &best, bool arbitrary_rays) {
-#ifndef RMD_AXIS_WALLS_TABLE
-#define RMD_AXIS_WALLS_TABLE 1
-#endif
-#if RMD_AXIS_WALLS_TABLE
+RMD_DEV void axis_pair_test(const DevObject *__restrict__ objs, const AxisWalls *__restrict__ walls, uint32_t j, bool want, V3 ro, V3 rd, double &closest, int &best, bool arbitrary_rays) {
 	const AxisWalls &w = walls[K]; // (device_types.hpp: behind the table's last record)
 	const double o_plus = w.o_plus, o_minus = w.o_minus; // the planes with normal +e_k / -e_k (uniform)
 	const int idx_plus = (int)w.idx_plus, idx_minus = (int)w.idx_minus;
-#else
-	const DevObject &o = objs[j];
-	const uint32_t e = o.pair_info & 0x3FFFFFFFu; // the earlier plane of the pair
-	const bool e_plus = (o.flags & kObjAxisEarlierIsPlus) != 0u;
-	const double o_e = o.partner_origin_k, o_j = o.origin[K]; // (the partner's coordinate sits in this object's record: one round of scalar loads, not two)
-	const double o_plus = e_plus ? o_e : o_j, o_minus = e_plus ? o_j : o_e; // the planes with normal +e_k / -e_k (uniform)
-	const int idx_plus = e_plus ? (int)e : (int)j, idx_minus = e_plus ? (int)j : (int)e;
-#endif
 	const double rk = K == 0 ? rd.x : K == 1 ? rd.y : rd.z, pk = K == 0 ? ro.x : K == 1 ? ro.y : ro.z;
 	const bool faces_plus = -rk > 1e-6, faces_minus = rk > 1e-6;
 	double num_minus = o_minus - pk, num_plus = -(o_plus - pk);
@@ -75,10 +56,8 @@ RMD_DEV void axis_pair_test(const DevObject *__restrict__ objs, [[maybe_unused]]
 	if (RMD_UNLIKELY(arbitrary_rays || (__builtin_amdgcn_ballot_w64(num_hi - 0x14300000u >= 0x6BB00000u - 0x14300000u) & __builtin_amdgcn_ballot_w64(want)) != 0ull)) {
 		double t;
 		bool first;
-#if RMD_AXIS_WALLS_TABLE
 		const DevObject &o = objs[j];
 		const uint32_t e = o.pair_info & 0x3FFFFFFFu; // the earlier plane of the pair
-#endif
 		const bool hit = plane_pair_test_flat(ld3(objs[e].origin), ld3(objs[e].normal), ld3(o.origin), ld3(o.normal), ro, rd, t, first);
 		const int idx = first ? (int)e : (int)j;
 		const bool ok = hit && want && lex_less(t, idx, closest, best);
@@ -97,15 +76,11 @@ RMD_DEV void axis_pairs_visit(const DevObject *__restrict__ objs, uint32_t n_obj
 	if ((axis_pairs >> 10) & 1023u) axis_pair_test<1>(objs, walls, ((axis_pairs >> 10) & 1023u) - 1u, want, ro, rd, closest, best, arbitrary_rays);
 	if ((axis_pairs >> 20) & 1023u) axis_pair_test<2>(objs, walls, ((axis_pairs >> 20) & 1023u) - 1u, want, ro, rd, closest, best, arbitrary_rays);
 }
-#ifndef RMD_FLAT_OBJECT_TESTS
-#define RMD_FLAT_OBJECT_TESTS 1
-#endif
 RMD_DEV bool intersect_simple(const DevObject *__restrict__ objs, uint32_t n_objects, const DevGrid *__restrict__ grids, bool want, V3 ro, V3 rd,
                               double &closest, int &best, uint32_t axis_pairs, unsigned long long turns = ~0ull) {
 	closest = scalar_const(kFMax), best = -1;
 	bool enters = false;
 	axis_pairs_visit(objs, n_objects, axis_pairs, want, ro, rd, closest, best);
-#if RMD_FLAT_OBJECT_TESTS
 	// tests without control flow, the running minimum updated by selects (device_core.hpp: *_test_flat)
 	for (uint32_t i = next_turn(~0u, turns); i < n_objects; i = next_turn(i, turns)) {
 		const DevObject &o = objs[i];
@@ -132,31 +107,6 @@ RMD_DEV bool intersect_simple(const DevObject *__restrict__ objs, uint32_t n_obj
 			continue;
 		}
 		closest = ok ? t : closest, best = ok ? idx : best;
-	}
-	return enters;
-#endif
-	for (uint32_t i = next_turn(~0u, turns); i < n_objects; i = next_turn(i, turns)) {
-		const DevObject &o = objs[i];
-		if (o.geometry_kind == 0u) {
-			if (o.pair_info != 0u) { // a plane with an exactly opposite partner (device_core.hpp: plane_pair_visit), tested at the later one's turn
-				if (o.pair_info & kPairTestedAtPartner) continue;
-				const uint32_t e = o.pair_info - 1u;
-				if (want)
-					plane_pair_visit(ld3(objs[e].origin), ld3(objs[e].normal), ld3(o.origin), ld3(o.normal), ro, rd, [&](double t, bool first) {
-						const int idx = first ? (int)e : (int)i;
-						if (lex_less(t, idx, closest, best)) closest = t, best = idx;
-					});
-				continue;
-			}
-			// index order + strict '<' = the lexicographic minimum so far
-			if (want) plane_visit(ld3(o.origin), ld3(o.normal), ro, rd, [&](double t) { if (lex_less(t, (int)i, closest, best)) closest = t, best = (int)i; });
-		} else if (o.geometry_kind == 1u) {
-			if (want) sphere_visit(ld3(o.origin), o.radius, ro, rd, [&](double t) { if (lex_less(t, (int)i, closest, best)) closest = t, best = (int)i; });
-		} else {
-			const DevGrid &g = grids[o.grid_index];
-			double t_outer;
-			if (want && aabb_intersect(ld3(g.bbox_min), ld3(g.bbox_max), ro, rd, t_outer)) enters = true;
-		}
 	}
 	return enters;
 }
