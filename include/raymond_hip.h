@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define RMD_ABI_VERSION 5u
+#define RMD_ABI_VERSION 6u
 
 typedef int32_t rmd_status;
 enum {
@@ -60,7 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_reduce_framebuffer) */
+	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -203,7 +203,8 @@ typedef struct rmd_tile_rect {
  *                           rmd_settings.flags value ends black paths in scenes with grids; ABI 4 changed no sample either: it added
  *                           RMD_ERR_DEVICE_FAULT, rmd_reduce_framebuffer_async, rmd_launch_info.waves_per_workgroup and the rule for
  *                           non-finite scene parameters below; ABI 5 changed no sample: rmd_launch_info.queued, RMD_TUNE_PATH_QUEUES,
- *                           and every allocating entry point behind a catch.)
+ *                           and every allocating entry point behind a catch; ABI 6 changed no sample: it added the per-pixel second
+ *                           moments — rmd_render_tiles_moments[_async] — and rmd_tile_error.)
  * (One Philox evaluation per path segment, and no RNG state beyond a block counter and those 22 bits.)
  */
 
@@ -306,6 +307,31 @@ rmd_status rmd_render_tiles_async(rmd_context *ctx, const rmd_scene *scene, cons
                                   const rmd_settings *settings, const rmd_tile_rect *tiles, uint32_t n_tiles,
                                   double *accum_dev);
 rmd_status rmd_context_synchronize(rmd_context *ctx);
+/*
+ * The same render that also accumulates each pixel's SECOND MOMENT (since ABI 6).  `accum_sq_dev` is a second DEVICE buffer laid out like
+ * `accum_dev` (W*H*3 doubles, row-major RGB); for every pixel of every rect and every channel c:
+ *     accum   [i] += L_s.c          for s = sample_begin .. sample_begin+sample_count-1, in that order   (exactly as rmd_render_tiles)
+ *     accum_sq[i] += L_s.c * L_s.c  the same samples in the same order; the product rounded, then added (no fused multiply-add)
+ * Both sums are the same bits whatever form the launch takes (direct or buffered, any split, persistent or one wave per item, queued, chained,
+ * any number of scratch passes), and two calls over [0, k) and [k, n) give the bits of one call over [0, n).  accum_sq_dev = NULL is exactly
+ * rmd_render_tiles[_async]; accum_sq_dev == accum_dev is RMD_ERR_INVALID_ARGUMENT.  rmd_framebuffer_alloc / _zero / _download_tiles /
+ * _upload_tiles serve the second buffer like the first.
+ */
+rmd_status rmd_render_tiles_moments(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                    const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev, double *accum_sq_dev);
+rmd_status rmd_render_tiles_moments_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                          const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev, double *accum_sq_dev);
+/*
+ * Per-tile noise estimate from the two sums after n = sample_count samples.  For each pixel and channel, with S = accum, Q = accum_sq:
+ *     m = S / n;   v = (Q - S*m) / (n - 1), set to 0 if negative;   e_c = sqrt(v / n) / max(|m|, floor)
+ *     e_pixel = max_c e_c       (+inf if any S or Q of the pixel is not finite, or n < 2)
+ *     out_err_host[r] = the largest e_pixel over rect r's pixels   (0 for a rect without pixels)
+ * — the relative standard error of the pixel's mean, worst channel, worst pixel: one firefly keeps its tile's error high.  Rects may have any
+ * size and must lie inside the W x H frame; `floor` must be finite and > 0; accum_sq_dev == accum_dev is RMD_ERR_INVALID_ARGUMENT.
+ * Synchronous (waits for the renders enqueued before it on the context; reports a device fault of one of them like rmd_context_synchronize).
+ */
+rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                          uint32_t sample_count, double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host);
 /* Host-buffer convenience for a caller that keeps Tile.data in RAM, as the
  * reference does: upload accum, render, download (PCIe-inclusive). */
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera,

@@ -51,7 +51,7 @@ pub enum rmd_scene {}
 
 #[link(name = "raymond_hip")]
 /// include/raymond_hip.h: RMD_ABI_VERSION this module's struct definitions were written against
-const RMD_ABI_VERSION: u32 = 5;
+const RMD_ABI_VERSION: u32 = 6;
 
 extern "C" {
     fn rmd_abi_version() -> u32;

@@ -7,7 +7,7 @@ compiled library.
 """
 import ctypes as C
 
-RMD_ABI_VERSION = 5
+RMD_ABI_VERSION = 6
 
 RMD_OK = 0
 RMD_ERR_INVALID_ARGUMENT = 1

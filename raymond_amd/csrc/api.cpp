@@ -716,7 +716,7 @@ static uint32_t choose_split(const rmd_context *ctx, bool has_grid, uint32_t n_w
 }
 
 static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
-                                          const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev) {
+                                          const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev, double *accum_sq_dev) {
 	if (rmd_status s = bind(ctx)) return s;
 	if (rmd_status s = check_render_args(ctx, scene, camera, settings)) return s;
 	if (!accum_dev || (n_tiles && !tiles)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_tiles: null tiles/accum pointer");
@@ -839,7 +839,8 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 			Q.tile_done = ctx->d_tile_done;
 		}
 		rmd::LaunchShape shape;
-		RMD_HIP(ctx, rmd::launch_render_tiles(ctx->stream, Q, scene->d_objects, scene->d_grids, ctx->d_wave_tiles, accum_dev, persistent_pass ? ctx->n_cus : 0u, &shape));
+		RMD_HIP(ctx, rmd::launch_render_tiles(ctx->stream, Q, scene->d_objects, scene->d_grids, ctx->d_wave_tiles, accum_dev, persistent_pass ? ctx->n_cus : 0u, &shape,
+		                                      accum_sq_dev));
 		ctx->last_launch.passes++, ctx->last_launch.split_k = Q.split_k, ctx->last_launch.buffered = Q.buffered;
 		ctx->last_launch.persistent = shape.persistent, ctx->last_launch.waves_per_workgroup = shape.waves_per_wg; // the form it was launched in, not the one asked for
 		ctx->last_launch.queued = shape.queued;
@@ -876,7 +877,15 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 rmd_status rmd_render_tiles_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
                                   const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev) {
 	// (the wave-tile table and the cached rectangle list are std::vectors: nothing throws across the boundary)
-	return rmd::guarded(ctx, "rmd_render_tiles", [&] { return render_tiles_async_impl(ctx, scene, camera, settings, tiles, n_tiles, accum_dev); });
+	return rmd::guarded(ctx, "rmd_render_tiles", [&] { return render_tiles_async_impl(ctx, scene, camera, settings, tiles, n_tiles, accum_dev, nullptr); });
+}
+
+rmd_status rmd_render_tiles_moments_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                          const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev, double *accum_sq_dev) {
+	if (accum_sq_dev != nullptr && accum_sq_dev == accum_dev)
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_tiles_moments: accum_sq_dev must not alias accum_dev");
+	return rmd::guarded(ctx, "rmd_render_tiles_moments",
+	                    [&] { return render_tiles_async_impl(ctx, scene, camera, settings, tiles, n_tiles, accum_dev, accum_sq_dev); });
 }
 
 rmd_status rmd_context_set_tunable(rmd_context *ctx, uint32_t key, int64_t value) {
@@ -911,6 +920,46 @@ rmd_status rmd_render_tiles(rmd_context *ctx, const rmd_scene *scene, const rmd_
                             const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev) {
 	if (rmd_status s = rmd_render_tiles_async(ctx, scene, camera, settings, tiles, n_tiles, accum_dev)) return s;
 	return rmd_context_synchronize(ctx);
+}
+
+rmd_status rmd_render_tiles_moments(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                    const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev, double *accum_sq_dev) {
+	if (rmd_status s = rmd_render_tiles_moments_async(ctx, scene, camera, settings, tiles, n_tiles, accum_dev, accum_sq_dev)) return s;
+	return rmd_context_synchronize(ctx);
+}
+
+static rmd_status tile_error_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                                  uint32_t sample_count, double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host, void *&d) {
+	if (rmd_status s = bind(ctx)) return s;
+	for (uint32_t i = 0; i < n_rects; i++)
+		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: tile rectangle outside the framebuffer");
+	if (n_rects != 0) {
+		// device buffer: [rects: 16 bytes each][errors: 8 bytes each]
+		const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect);
+		RMD_HIP(ctx, hipMalloc(&d, rect_bytes + (size_t)n_rects * sizeof(double)));
+		rmd_tile_rect *d_rects = static_cast<rmd_tile_rect *>(d);
+		double *d_err = reinterpret_cast<double *>(static_cast<unsigned char *>(d) + rect_bytes);
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, rmd::launch_tile_error(ctx->stream, accum_dev, accum_sq_dev, d_rects, n_rects, width, sample_count, floor, d_err));
+		RMD_HIP(ctx, hipMemcpyAsync(out_err_host, d_err, (size_t)n_rects * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
+}
+
+rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, uint32_t sample_count,
+                          double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host) {
+	if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !out_err_host)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: bad argument");
+	if (accum_sq_dev == accum_dev) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: accum_sq_dev must not alias accum_dev");
+	if (!(floor > 0.0) || !std::isfinite(floor)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: floor must be finite and > 0");
+	void *d = nullptr; // the device scratch: freed here whichever way the body leaves
+	const rmd_status s = rmd::guarded(ctx, "rmd_tile_error", [&] {
+		return tile_error_impl(ctx, accum_dev, accum_sq_dev, width, height, sample_count, floor, rects, n_rects, out_err_host, d);
+	});
+	if (d) (void)hipFree(d);
+	return s;
 }
 
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,

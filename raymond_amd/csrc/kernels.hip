@@ -40,6 +40,69 @@ __global__ __launch_bounds__(64) void sum_kernel(RenderParams P, const WaveTile 
 	out[pix + 0] = acc.x, out[pix + 1] = acc.y, out[pix + 2] = acc.z;
 }
 
+// The same sum for rmd_render_tiles_moments: out_sq += sample(s)^2 per channel beside it, same samples, same order — the square rounded, then
+// added.  (A kernel of its own: sum_kernel stays exactly what a render without moments runs.)
+__global__ __launch_bounds__(64) void sum_moments_kernel(RenderParams P, const WaveTile *__restrict__ tiles, const double *__restrict__ buf,
+                                                         double *__restrict__ out, double *__restrict__ out_sq) {
+	const uint32_t wt = blockIdx.x, lane = threadIdx.x;
+	const WaveTile t = tiles[wt];
+	const uint32_t lx = lane & 7u, ly = lane >> 3;
+	if (lx >= t.w || ly >= t.h) return;
+	const size_t pix = ((size_t)(t.x0 + lx) + (size_t)(t.y0 + ly) * P.W) * 3;
+	V3 acc = ld3(out + pix), sq = ld3(out_sq + pix);
+	const double *src = buf + ((size_t)wt * P.sample_count * 64u + lane) * kSampleStride;
+	for (uint32_t s = 0; s < P.sample_count; s++) {
+		const V3 v = ld3(src);
+		acc = acc + v;
+		sq = sq + hadamard(v, v);
+		src += 64u * kSampleStride;
+	}
+	out[pix + 0] = acc.x, out[pix + 1] = acc.y, out[pix + 2] = acc.z;
+	out_sq[pix + 0] = sq.x, out_sq[pix + 1] = sq.y, out_sq[pix + 2] = sq.z;
+}
+
+// ---------------------------------------------------------------- per-tile error (rmd_tile_error)
+// One workgroup per rect, striding over its pixels.  For n samples, S = accum, Q = accum_sq, per channel:
+//     m = S / n;  v = (Q - S*m) / (n - 1), 0 if negative;  e_c = sqrt(v / n) / max(|m|, floor)
+// a pixel's error is its largest e_c (+inf when one of its S or Q is not finite, or n < 2), the rect's the largest of its pixels'.  A maximum
+// is the same whatever order it is taken in: the result does not depend on how the pixels are dealt to lanes.  (With finite inputs and a
+// floor > 0 no e_c is NaN: S*m >= 0, so Q - S*m cannot overflow upwards, and an overflow of S*m makes v -inf, which is clamped.)
+__global__ __launch_bounds__(256) void tile_error_kernel(const double *__restrict__ S, const double *__restrict__ Q, const rmd_tile_rect *__restrict__ rects,
+                                                          uint32_t W, uint32_t n, double floor, double *__restrict__ out) {
+	const rmd_tile_rect r = rects[blockIdx.x];
+	const uint64_t n_px = (uint64_t)r.width * r.height;
+	const double nd = (double)n;
+	double e = 0.0;
+	for (uint64_t i = threadIdx.x; i < n_px; i += 256u) {
+		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
+		const size_t p = ((size_t)(r.left + x) + (size_t)(r.top + y) * W) * 3;
+		bool bad = n < 2u;
+		double ep = 0.0;
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			const double s = S[p + c], q = Q[p + c];
+			bad = bad || !(__builtin_fabs(s) < __builtin_inf()) || !(__builtin_fabs(q) < __builtin_inf());
+			const double m = s / nd;
+			double v = (q - s * m) / (nd - 1.0);
+			if (v < 0.0) v = 0.0;
+			const double ec = __builtin_sqrt(v / nd) / __builtin_fmax(__builtin_fabs(m), floor);
+			ep = __builtin_fmax(ep, ec);
+		}
+		e = __builtin_fmax(e, bad ? __builtin_inf() : ep);
+	}
+	for (int off = 32; off > 0; off >>= 1) e = __builtin_fmax(e, __shfl_xor(e, off, 64));
+	__shared__ double wave_max[4];
+	if ((threadIdx.x & 63u) == 0u) wave_max[threadIdx.x >> 6] = e;
+	__syncthreads();
+	if (threadIdx.x == 0u) out[blockIdx.x] = __builtin_fmax(__builtin_fmax(wave_max[0], wave_max[1]), __builtin_fmax(wave_max[2], wave_max[3]));
+}
+hipError_t launch_tile_error(hipStream_t stream, const double *accum, const double *accum_sq, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W,
+                             uint32_t sample_count, double floor, double *out) {
+	if (n_rects == 0) return hipSuccess;
+	hipLaunchKernelGGL(tile_error_kernel, dim3(n_rects), dim3(256), 0, stream, accum, accum_sq, rects, W, sample_count, floor, out);
+	return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- resolve + tone-map (cli_old/src/main.rs:161-181, src/trace.rs:95)
 // The reference's 8-bit value is trunc(255 * (1 - exp(-p * exposure))^(1/gamma)) with the HOST libm's exp and powf.  The device's exp / pow
 // differ from a host libm by an ulp or two, which can only change the byte when 255 * tm lies within a few 1e-13 of an integer.  So the
@@ -112,17 +175,18 @@ uint32_t render_waves_per_wg(uint32_t n_objects, uint32_t mask_words_total) {
 }
 
 hipError_t launch_render_tiles(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
-                               const WaveTile *wave_tiles, double *accum, uint32_t n_cus, LaunchShape *shape) {
+                               const WaveTile *wave_tiles, double *accum, uint32_t n_cus, LaunchShape *shape, double *accum_sq) {
 	if (P.n_work == 0) return hipSuccess;
 	const bool buffered = P.buffered != 0u;
 	const uint32_t n_waves = P.n_work * (buffered ? P.split_k : 1u);
 	hipError_t e;
 	if (P.n_grids) e = buffered ? launch_render<kModeTilesBuffered, true>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape)
-	                            : launch_render<kModeTiles, true>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape);
-	else e = buffered ? launch_render<kModeTilesBuffered, false>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape)
-	                  : launch_render<kModeTiles, false>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape);
+	                            : launch_render<kModeTiles, true>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape, accum_sq);
+	else e = buffered ? launch_render<kModeTilesBuffered, false>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape, accum_sq)
+	                  : launch_render<kModeTiles, false>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape, accum_sq);
 	if (e != hipSuccess || !buffered || P.tile_done != nullptr) return e; // with tile_done the render kernel's waves add the samples themselves
-	hipLaunchKernelGGL(sum_kernel, dim3(P.n_work), dim3(64), 0, stream, P, wave_tiles, (const double *)P.sample_buf, accum);
+	if (accum_sq) hipLaunchKernelGGL(sum_moments_kernel, dim3(P.n_work), dim3(64), 0, stream, P, wave_tiles, (const double *)P.sample_buf, accum, accum_sq);
+	else hipLaunchKernelGGL(sum_kernel, dim3(P.n_work), dim3(64), 0, stream, P, wave_tiles, (const double *)P.sample_buf, accum);
 	return hipGetLastError();
 }
 

@@ -81,9 +81,13 @@ inline size_t path_queue_bytes_host(uint32_t cap) { return (size_t)cap * (9u * 8
 static_assert(kQueuePaths >= 192u && kQueuePaths % 64u == 0u, "two stacks short of a full trip + the 64 paths of a generation trip");
 size_t render_lds_bytes(uint32_t n_objects, uint32_t mask_words_total, uint32_t waves_per_wg);
 uint32_t render_waves_per_wg(uint32_t n_objects, uint32_t mask_words_total);
-// n_cus > 0 and P.work_counter set: grid scenes run as persistent workgroups (render_kernel.hpp)
+// n_cus > 0 and P.work_counter set: grid scenes run as persistent workgroups (render_kernel.hpp).  accum_sq (optional): every sample's square is
+// added there too, in the same order (rmd_render_tiles_moments)
 hipError_t launch_render_tiles(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
-                               const WaveTile *wave_tiles, double *accum, uint32_t n_cus = 0, LaunchShape *shape = nullptr);
+                               const WaveTile *wave_tiles, double *accum, uint32_t n_cus = 0, LaunchShape *shape = nullptr, double *accum_sq = nullptr);
+// out[i] = the relative standard error of rect i's worst pixel and channel (kernels.hip: tile_error_kernel; rects and out are device memory)
+hipError_t launch_tile_error(hipStream_t stream, const double *accum, const double *accum_sq, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W,
+                             uint32_t sample_count, double floor, double *out);
 hipError_t launch_render_list(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
                               const ListWork *list, double *rgb_out, int32_t *path_obj, uint32_t *path_sub);
 // tile rectangles of a frame <-> a packed buffer (kernels.hip: tile_copy_kernel); `first[i]` = pixels in front of rect i

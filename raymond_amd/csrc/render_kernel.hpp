@@ -155,7 +155,9 @@ RMD_DEV void store_sample(RMD_GLOBAL double *dst, V3 L) { dst[0] = L.x, dst[1] =
 // samples to the pixels, strictly in sample order (src/trace.rs:203: the reference's sequential sum, bit for bit) — inside the render kernel, where
 // the reads (bandwidth) overlap the other waves' arithmetic; as a kernel of its own the sum cost 5.5 ms per 1080p / 500 spp frame.  Release: an
 // agent-scope fence writes this wave's sample stores back before its count; acquire: the last wave invalidates its caches before it reads.
-RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, uint32_t wt, uint32_t lane, double *__restrict__ out) {
+// MOM (rmd_render_tiles_moments): the same pass adds each sample's square to out_sq from the values it has loaded anyway.
+template <bool MOM = false>
+RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, uint32_t wt, uint32_t lane, double *__restrict__ out, double *__restrict__ out_sq = nullptr) {
 	if (P.tile_done == nullptr || wt >= P.n_work) return;
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // this wave's samples leave the XCD's L2 before its count is seen
 	uint32_t before = 0;
@@ -167,22 +169,31 @@ RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, ui
 	if (lx < tile.w && ly < tile.h) {
 		const size_t pix = ((size_t)(tile.x0 + lx) + (size_t)(tile.y0 + ly) * P.W) * 3;
 		V3 sum = ld3(out + pix);
+		[[maybe_unused]] V3 sq = mk(0.0, 0.0, 0.0);
+		if constexpr (MOM) sq = ld3(out_sq + pix);
 		const RMD_GLOBAL double *src = (const RMD_GLOBAL double *)P.sample_buf + ((size_t)wt * P.sample_count * 64u + lane) * kSampleStride;
-		// 16 samples' loads in flight at a time (the additions stay in sample order)
+		// 16 samples' loads in flight at a time (the additions stay in sample order); 8 beside the squares' sums (at 16 the kernel spilled two registers)
+		constexpr uint32_t kInFlight = MOM ? 8u : 16u;
 		uint32_t k = 0;
-		for (; k + 16u <= P.sample_count; k += 16u) {
-			V3 v[16];
+		for (; k + kInFlight <= P.sample_count; k += kInFlight) {
+			V3 v[kInFlight];
 #pragma unroll
-			for (uint32_t j = 0; j < 16u; j++) v[j] = ld3(src + (size_t)j * 64u * kSampleStride);
+			for (uint32_t j = 0; j < kInFlight; j++) v[j] = ld3(src + (size_t)j * 64u * kSampleStride);
 #pragma unroll
-			for (uint32_t j = 0; j < 16u; j++) sum = sum + v[j];
-			src += 16u * 64u * kSampleStride;
+			for (uint32_t j = 0; j < kInFlight; j++) {
+				sum = sum + v[j];
+				if constexpr (MOM) sq = sq + hadamard(v[j], v[j]); // the square rounded, then added (no contraction: -ffp-contract=off)
+			}
+			src += kInFlight * 64u * kSampleStride;
 		}
 		for (; k < P.sample_count; k++) {
-			sum = sum + ld3(src);
+			const V3 v = ld3(src);
+			sum = sum + v;
+			if constexpr (MOM) sq = sq + hadamard(v, v);
 			src += 64u * kSampleStride;
 		}
 		out[pix + 0] = sum.x, out[pix + 1] = sum.y, out[pix + 2] = sum.z;
+		if constexpr (MOM) out_sq[pix + 0] = sq.x, out_sq[pix + 1] = sq.y, out_sq[pix + 2] = sq.z;
 	}
 }
 
@@ -195,11 +206,14 @@ typedef const __attribute__((address_space(4))) unsigned long long *KernargWords
 // used to end with a drain of ~7 trips of ever fewer lanes (2 % of a 55-sample item's trips, 20 % of a 4-sample item's: a progressive pass).
 // A path's identity — pixel, sample, scratch sector — therefore lives per lane (PathId, in LDS), not in wave-uniform item state.  Which lane
 // and which trip compute a sample changes nothing: same bits.
-template <int MODE, bool GRID, bool CHAIN = false>
+// MOM (direct mode only, rmd_render_tiles_moments): every finished sample's square is added to out_sq beside the sum — in registers, or in memory
+// where the sum is (acc_in_memory).
+template <int MODE, bool GRID, bool CHAIN = false, bool MOM = false>
 RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids,
                          const void *__restrict__ work, double *__restrict__ out, int32_t *__restrict__ path_obj, uint32_t *__restrict__ path_sub,
-                         const DevObject *lobjs, const uint32_t *lds_masks, unsigned char *wave_lds, uint32_t first) {
+                         const DevObject *lobjs, const uint32_t *lds_masks, unsigned char *wave_lds, uint32_t first, double *__restrict__ out_sq = nullptr) {
 	static_assert(!CHAIN || (MODE == kModeTilesBuffered && GRID), "items are chained in split launches of scenes with grids");
+	static_assert(!MOM || MODE == kModeTiles, "split launches add the squares where they add the samples (finish_sample_range, sum_moments_kernel)");
 	constexpr bool LIST = MODE == kModeList;
 	const uint32_t lane = threadIdx.x & 63u;
 	WalkScratch &scr = *reinterpret_cast<WalkScratch *>(wave_lds); // unused (and not allocated) when the scene has no grid
@@ -257,6 +271,9 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 	constexpr bool acc_in_memory = GRID && MODE == kModeTiles;
 	V3 acc = mk(0.0, 0.0, 0.0);
 	if (!LIST && alive && !to_buffer && !acc_in_memory) acc = ld3(out + out_index);
+	[[maybe_unused]] V3 acc_sq = mk(0.0, 0.0, 0.0);
+	if constexpr (MOM && !acc_in_memory)
+		if (alive) acc_sq = ld3(out_sq + out_index);
 	if (P.bounce_limit == 0u) { // trace(.., 1) with depth 1 > bounce_limit returns 0 unintersected (:235-237): every sample is (0, 0, 0)
 		if (LIST && writes) out[out_index + 0] = 0.0, out[out_index + 1] = 0.0, out[out_index + 2] = 0.0;
 		return; // tile launches with bounce_limit 0 are not made at all (api.cpp): the frame is unchanged
@@ -470,8 +487,13 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 				if constexpr (acc_in_memory) {
 					RMD_GLOBAL double *px = (RMD_GLOBAL double *)out + ((size_t)(tile.x0 + (lane & 7u)) + (size_t)(tile.y0 + (lane >> 3)) * Pt.W) * 3;
 					px[0] += L.x, px[1] += L.y, px[2] += L.z; // src/trace.rs:203
+					if constexpr (MOM) {
+						RMD_GLOBAL double *pq = (RMD_GLOBAL double *)out_sq + ((size_t)(tile.x0 + (lane & 7u)) + (size_t)(tile.y0 + (lane >> 3)) * Pt.W) * 3;
+						pq[0] += L.x * L.x, pq[1] += L.y * L.y, pq[2] += L.z * L.z;
+					}
 				} else {
 					acc = acc + L; // src/trace.rs:203
+					if constexpr (MOM) acc_sq = acc_sq + hadamard(L, L);
 				}
 				s++;
 			}
@@ -630,6 +652,7 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 		out[out_index + 0] = acc.x;
 		out[out_index + 1] = acc.y;
 		out[out_index + 2] = acc.z;
+		if constexpr (MOM && !acc_in_memory) out_sq[out_index + 0] = acc_sq.x, out_sq[out_index + 1] = acc_sq.y, out_sq[out_index + 2] = acc_sq.z;
 	}
 }
 
@@ -668,8 +691,10 @@ using SortPool = HitStack;
 
 // A register pair the compiler may fill with anything: the value of a variable in the lanes that never use it.
 #define RMD_UNDEF3(v) RMD_UNDEF(v.x) RMD_UNDEF(v.y) RMD_UNDEF(v.z)
+template <bool MOM = false>
 RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_params, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids,
-                                const void *__restrict__ work, double *__restrict__ out, const DevObject *lobjs, unsigned char *wave_lds, uint32_t work_item) {
+                                const void *__restrict__ work, double *__restrict__ out, const DevObject *lobjs, unsigned char *wave_lds, uint32_t work_item,
+                                double *__restrict__ out_sq = nullptr) {
 	const uint32_t lane = threadIdx.x & 63u;
 	HitStack &stack = *reinterpret_cast<HitStack *>(wave_lds);
 	WalkScratch *no_scratch = nullptr; // (scene_intersect_wave<false> never touches it)
@@ -823,7 +848,7 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		}
 	}
-	finish_sample_range(P, tile, wt, lane, out);
+	finish_sample_range<MOM>(P, tile, wt, lane, out, out_sq);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1306,14 +1331,22 @@ template <int MODE, bool GRID, bool QUEUED = false>
 __host__ __device__ inline size_t wave_lds_of(uint32_t n_grids) { return QUEUED ? queued_wave_lds_bytes() : kSortedTrips<MODE, GRID> ? kWaveHeadBytes + sizeof(SortPool) : wave_lds_bytes(n_grids); }
 template <int MODE, bool GRID>
 constexpr uint32_t kPersistWaves = kSortedTrips<MODE, GRID> ? kSortedWavesPerWg : GRID ? kGridPersistWavesPerWg : kPersistWavesPerWg;
-template <int MODE, bool GRID, bool PERSIST, bool CHAIN = false, bool QUEUED = false>
-__global__ __launch_bounds__(PERSIST ? 64 * (kPersistWaves<MODE, GRID>) : GRID ? 64 * kGridWavesPerWg : 64,
-                             GRID ? kGridMinWaves : (kSortedTrips<MODE, GRID>) ? kSortedWavesPerWg / 4 : (PERSIST ? 4 : kNoGridMinWaves)) void render_kernel(
-    RenderParams P, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids, const void *__restrict__ work, double *__restrict__ out,
-    int32_t *__restrict__ path_obj, uint32_t *__restrict__ path_sub) {
+// launch bounds of an instantiation: threads of a workgroup, waves per SIMD
+template <int MODE, bool GRID, bool PERSIST>
+constexpr int kWgThreads = PERSIST ? 64 * (kPersistWaves<MODE, GRID>) : GRID ? 64 * kGridWavesPerWg : 64;
+template <int MODE, bool GRID, bool PERSIST>
+constexpr int kMinWavesPerSimd = GRID ? kGridMinWaves : (kSortedTrips<MODE, GRID>) ? kSortedWavesPerWg / 4 : (PERSIST ? 4 : kNoGridMinWaves);
+// The instantiations that add the squares of the samples themselves (rmd_render_tiles_moments): direct mode, and the spheres kernel's split launches
+// (finish_sample_range).  Split launches of scenes with grids leave both sums to sum_moments_kernel (kernels.hip).
+template <int MODE, bool GRID>
+constexpr bool kMomentsInKernel = MODE == kModeTiles || (MODE == kModeTilesBuffered && !GRID);
+// The body of render_kernel and render_kernel_moments.  P is the calling kernel's FIRST by-value argument: it starts at offset 0 of the
+// kernel-argument segment, from where render_wave re-reads the launch parameters on every trip instead of carrying them in registers.
+template <int MODE, bool GRID, bool PERSIST, bool CHAIN, bool QUEUED, bool MOM>
+RMD_DEV void render_kernel_body(const RenderParams &P, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids, const void *__restrict__ work,
+                                double *__restrict__ out, int32_t *__restrict__ path_obj, uint32_t *__restrict__ path_sub, double *__restrict__ out_sq) {
+	static_assert(!MOM || (kMomentsInKernel<MODE, GRID> && !CHAIN && !QUEUED), "the squares are added where the samples are");
 	extern __shared__ __align__(16) unsigned char smem[];
-	// P is this kernel's FIRST by-value argument: it starts at offset 0 of the kernel-argument segment, from where render_wave re-reads
-	// the launch parameters on every trip instead of carrying them in registers
 	const KernargWords kernarg_params = (KernargWords)__builtin_amdgcn_kernarg_segment_ptr();
 	// LDS: [object table][grid occupancy masks][one walk scratch per wave]
 	DevObject *lobjs = reinterpret_cast<DevObject *>(smem);
@@ -1366,22 +1399,39 @@ __global__ __launch_bounds__(PERSIST ? 64 * (kPersistWaves<MODE, GRID>) : GRID ?
 				break;
 			}
 			if constexpr (QUEUED) render_wave_queued(P, kernarg_params, objs, grids, work, lobjs, lds_masks, wave_lds, item);
-			else if constexpr (kSortedTrips<MODE, GRID>) render_wave_sorted(P, kernarg_params, objs, grids, work, out, lobjs, wave_lds, item);
-			else render_wave<MODE, GRID, CHAIN>(P, kernarg_params, objs, grids, work, out, path_obj, path_sub, lobjs, lds_masks, wave_lds, item);
+			else if constexpr (kSortedTrips<MODE, GRID>) render_wave_sorted<MOM>(P, kernarg_params, objs, grids, work, out, lobjs, wave_lds, item, out_sq);
+			else render_wave<MODE, GRID, CHAIN, MOM>(P, kernarg_params, objs, grids, work, out, path_obj, path_sub, lobjs, lds_masks, wave_lds, item, out_sq);
 		}
 	} else {
 		const uint32_t unit = work_item_of_block(blockIdx.x, gridDim.x) * waves_per_wg + wave;
-		if constexpr (kSortedTrips<MODE, GRID>) render_wave_sorted(P, kernarg_params, objs, grids, work, out, lobjs, wave_lds, unit);
-		else render_wave<MODE, GRID>(P, kernarg_params, objs, grids, work, out, path_obj, path_sub, lobjs, lds_masks, wave_lds, MODE == kModeList ? unit * 64u : unit);
+		if constexpr (kSortedTrips<MODE, GRID>) render_wave_sorted<MOM>(P, kernarg_params, objs, grids, work, out, lobjs, wave_lds, unit, out_sq);
+		else render_wave<MODE, GRID, false, MOM>(P, kernarg_params, objs, grids, work, out, path_obj, path_sub, lobjs, lds_masks, wave_lds, MODE == kModeList ? unit * 64u : unit, out_sq);
 	}
+}
+template <int MODE, bool GRID, bool PERSIST, bool CHAIN = false, bool QUEUED = false>
+__global__ __launch_bounds__((kWgThreads<MODE, GRID, PERSIST>), (kMinWavesPerSimd<MODE, GRID, PERSIST>)) void render_kernel(
+    RenderParams P, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids, const void *__restrict__ work, double *__restrict__ out,
+    int32_t *__restrict__ path_obj, uint32_t *__restrict__ path_sub) {
+	render_kernel_body<MODE, GRID, PERSIST, CHAIN, QUEUED, false>(P, objs, grids, work, out, path_obj, path_sub, nullptr);
+}
+// The same launch that also adds every sample's square to out_sq (rmd_render_tiles_moments): instantiations of their own, so that the ones above
+// are compiled exactly as without the feature.
+template <int MODE, bool GRID, bool PERSIST>
+__global__ __launch_bounds__((kWgThreads<MODE, GRID, PERSIST>), (kMinWavesPerSimd<MODE, GRID, PERSIST>)) void render_kernel_moments(
+    RenderParams P, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids, const void *__restrict__ work, double *__restrict__ out,
+    int32_t *__restrict__ path_obj, uint32_t *__restrict__ path_sub, double *__restrict__ out_sq) {
+	render_kernel_body<MODE, GRID, PERSIST, false, false, true>(P, objs, grids, work, out, path_obj, path_sub, out_sq);
 }
 
 // n_cus > 0 (tile modes of grid scenes): the persistent form, one 16-wave workgroup per CU (fewer when there are fewer work items);
 // P.work_counter must point at a zeroed device word.
 // `shape` (optional) receives the form the kernel was actually launched in.
+// `out_sq` (optional, the instantiations of kMomentsInKernel): the render_kernel_moments launch of the same form.
 template <int MODE, bool GRID>
 inline hipError_t launch_render(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const void *work,
-                                uint32_t n_waves, double *out, int32_t *path_obj, uint32_t *path_sub, uint32_t n_cus = 0, LaunchShape *shape = nullptr) {
+                                uint32_t n_waves, double *out, int32_t *path_obj, uint32_t *path_sub, uint32_t n_cus = 0, LaunchShape *shape = nullptr,
+                                double *out_sq = nullptr) {
+	[[maybe_unused]] const bool moments = kMomentsInKernel<MODE, GRID> && out_sq != nullptr;
 	// LDS of a workgroup of `waves` waves of this instantiation: [object table][grid occupancy masks][per-wave area]
 	[[maybe_unused]] const bool queued = kPathQueues<MODE, GRID> && P.queue_buf != nullptr; // (api.cpp provides the queues for the launches that take this form)
 	auto lds_for = [&](uint32_t waves) {
@@ -1404,6 +1454,16 @@ inline hipError_t launch_render(hipStream_t stream, const RenderParams &P, const
 			                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
 			if (e != hipSuccess) return e;
 			const uint32_t wgs = (n_waves + pw - 1u) / pw, resident = n_cus;
+			if constexpr (kMomentsInKernel<MODE, GRID>) {
+				if (moments) { // (never queued or chained: those are split launches of scenes with grids)
+					e = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel_moments<MODE, GRID, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
+					if (e != hipSuccess) return e;
+					hipLaunchKernelGGL((render_kernel_moments<MODE, GRID, true>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs, grids, work, out,
+					                   path_obj, path_sub, out_sq);
+					if (shape) shape->persistent = 1u, shape->waves_per_wg = pw, shape->queued = 0u, shape->resident_waves = (wgs < resident ? wgs : resident) * pw;
+					return hipGetLastError();
+				}
+			}
 			if (queued)
 				hipLaunchKernelGGL((render_kernel<MODE, GRID, true, false, (kPathQueues<MODE, GRID>)>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs,
 				                   grids, work, out, path_obj, path_sub);
@@ -1419,6 +1479,19 @@ inline hipError_t launch_render(hipStream_t stream, const RenderParams &P, const
 	}
 	const uint32_t wpw = render_waves_per_wg(P.n_objects, P.mask_words_total);
 	const size_t lds = lds_for(wpw);
+	if constexpr (kMomentsInKernel<MODE, GRID>) {
+		if (moments) {
+			if (lds > 64u * 1024u) {
+				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel_moments<MODE, GRID, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+				                                   (int)kLdsBudgetBytes);
+				if (e != hipSuccess) return e;
+			}
+			hipLaunchKernelGGL((render_kernel_moments<MODE, GRID, false>), dim3((n_waves + wpw - 1u) / wpw), dim3(64u * wpw), lds, stream, P, objs, grids, work, out,
+			                   path_obj, path_sub, out_sq);
+			if (shape) shape->persistent = 0u, shape->waves_per_wg = wpw;
+			return hipGetLastError();
+		}
+	}
 	if (lds > 64u * 1024u) { // above the default dynamic-LDS limit: opt in on the current device (cheap, and correct per device)
 		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel<MODE, GRID, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
 		                                   (int)kLdsBudgetBytes);

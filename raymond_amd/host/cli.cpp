@@ -2,6 +2,7 @@
 // (build scene -> Settings -> render_tiled -> await -> tone-map -> image file).
 //
 //   raymond_cli render <spheres|dragon[:n]> W H SPP BOUNCES out.ppm [--raw out.f64] [--gpus N] [--spi K] [--aperture R] [--end-black-paths 1]
+//                                                                    [--adaptive THRESHOLD [--adaptive-floor F]]   (needs --spi)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -173,6 +174,8 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--spi")) st.samples_per_iteration = std::atoi(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--aperture")) st.camera_settings.aperture_radius = std::atof(argv[i + 1]), st.use_dof = true;
 				else if (!std::strcmp(argv[i], "--end-black-paths")) st.end_black_paths = std::atoi(argv[i + 1]) != 0; // opt-in on mesh scenes (raymond_hip.h)
+				else if (!std::strcmp(argv[i], "--adaptive")) st.adaptive_threshold = std::atof(argv[i + 1]); // (render_tiled refuses it without --spi)
+				else if (!std::strcmp(argv[i], "--adaptive-floor")) st.adaptive_floor = std::atof(argv[i + 1]);
 			}
 			Scene scene;
 			if (what == "spheres") scene = reflective_spheres();

@@ -186,7 +186,7 @@ struct BlockPool : std::enable_shared_from_this<BlockPool> {
 void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, size_t workers, Scene scene, Settings st, size_t batch) {
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
-	double *fb = nullptr;
+	double *fb = nullptr, *fb_sq = nullptr; // fb_sq: the sums of squares of an adaptive render
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	// a batch whose download is on its way: the tiles that become messages, in message order
 	struct Pending {
@@ -213,6 +213,8 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 		flatten(scene, objs, grids);
 		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
 		check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb), ctx, "rmd_framebuffer_alloc"); // zeroed: a fresh tile's sums
+		const bool adaptive = st.adaptive_threshold > 0.0;
+		if (adaptive) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_sq), ctx, "rmd_framebuffer_alloc");
 		{
 			std::lock_guard<std::mutex> lock(sh->m);
 			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
@@ -249,14 +251,20 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 			// tiles that arrive with their sums in RAM (another GPU rendered their earlier passes): into this GPU's framebuffer
 			{
 				std::vector<rmd_tile_rect> rects;
-				std::vector<double> packed;
+				std::vector<double> packed, packed_sq;
 				for (Tile &t : mine)
 					if (t.resident != me && t.sample_count != 0) {
 						rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
 						const double *src = reinterpret_cast<const double *>(t.data.data());
 						packed.insert(packed.end(), src, src + t.data.size() * 3);
+						if (adaptive) {
+							const double *sq = reinterpret_cast<const double *>(t.data_sq.data());
+							packed_sq.insert(packed_sq.end(), sq, sq + t.data_sq.size() * 3);
+						}
 					}
 				if (!rects.empty()) check(rmd_framebuffer_upload_tiles(ctx, packed.data(), fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
+				if (!rects.empty() && adaptive)
+					check(rmd_framebuffer_upload_tiles(ctx, packed_sq.data(), fb_sq, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
 			}
 			// tiles of one batch may be at different sample counts: one launch per count (enqueued, not waited for)
 			std::map<size_t, std::vector<size_t>> by_count;
@@ -268,11 +276,29 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 				rmd_settings rs;
 				std::memset(&rs, 0, sizeof(rs));
 				rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)begin, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
-				check(rmd_render_tiles_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb), ctx, "rmd_render_tiles");
-				for (size_t i : grp.second) mine[i].sample_count += n, mine[i].resident = me, mine[i].data = TileData(); // :207 — the sums are on this GPU now
+				if (adaptive) check(rmd_render_tiles_moments_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb, fb_sq), ctx, "rmd_render_tiles_moments");
+				else check(rmd_render_tiles_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb), ctx, "rmd_render_tiles");
+				for (size_t i : grp.second) mine[i].sample_count += n, mine[i].resident = me, mine[i].data = TileData(), mine[i].data_sq = TileData(); // :207 — the sums are on this GPU now
 			}
 			// the previous batch's messages go out while this batch renders
 			flush();
+			// adaptive: the error of every tile this pass has left below sample_count, one rmd_tile_error per sample count (it waits for the pass); a
+			// tile at or below the threshold is finished at the samples it has
+			std::vector<bool> converged(mine.size(), false);
+			if (adaptive) {
+				std::map<size_t, std::vector<size_t>> live;
+				for (size_t i = 0; i < mine.size(); i++)
+					if (mine[i].sample_count < st.sample_count) live[mine[i].sample_count].push_back(i);
+				for (auto &grp : live) {
+					std::vector<rmd_tile_rect> rects;
+					for (size_t i : grp.second) rects.push_back(rmd_tile_rect{(uint32_t)mine[i].left, (uint32_t)mine[i].top, (uint32_t)mine[i].width, (uint32_t)mine[i].height});
+					std::vector<double> err(rects.size());
+					check(rmd_tile_error(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, (uint32_t)grp.first, st.adaptive_floor, rects.data(), (uint32_t)rects.size(), err.data()), ctx,
+					      "rmd_tile_error");
+					for (size_t k = 0; k < err.size(); k++) converged[grp.second[k]] = err[k] <= st.adaptive_threshold;
+				}
+			}
+			auto is_finished = [&](size_t i) { return mine[i].sample_count == st.sample_count || converged[i]; };
 			// what of this batch has to come to the host: finished tiles (:211-212), progress snapshots (:217-219), and — with several GPUs — every
 			// tile that goes back to the shared queue (another GPU may take it next)
 			Pending next;
@@ -280,14 +306,22 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 			std::vector<size_t> want;
 			std::vector<Tile> resident_requeue;
 			size_t pixels = 0;
+			std::vector<rmd_tile_rect> rects_sq; // adaptive, several GPUs: the sums of squares of the tiles that go back to the shared queue
+			std::vector<size_t> want_sq;
+			size_t pixels_sq = 0;
 			for (size_t i = 0; i < mine.size(); i++) {
 				Tile &t = mine[i];
-				const bool finished = t.sample_count == st.sample_count;
+				const bool finished = is_finished(i);
 				const bool progressed = !finished && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
 				if (finished || progressed || workers > 1) {
 					want.push_back(i);
 					rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
 					pixels += t.width * t.height;
+				}
+				if (adaptive && !finished && workers > 1) {
+					want_sq.push_back(i);
+					rects_sq.push_back(rects.back());
+					pixels_sq += t.width * t.height;
 				}
 			}
 			if (!want.empty()) {
@@ -299,8 +333,19 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 					p += mine[i].width * mine[i].height;
 				}
 			}
-			for (Tile &t : mine) {
-				const bool finished = t.sample_count == st.sample_count;
+			if (!want_sq.empty()) {
+				std::shared_ptr<void> block = pool->get(ctx, pixels_sq * 24);
+				check(rmd_framebuffer_download_tiles_async(ctx, fb_sq, (uint32_t)W, (uint32_t)H, rects_sq.data(), (uint32_t)rects_sq.size(), static_cast<double *>(block.get())), ctx,
+				      "rmd_framebuffer_download_tiles");
+				Vector3 *p = static_cast<Vector3 *>(block.get());
+				for (size_t i : want_sq) {
+					mine[i].data_sq = TileData(block, p, mine[i].width * mine[i].height);
+					p += mine[i].width * mine[i].height;
+				}
+			}
+			for (size_t i = 0; i < mine.size(); i++) {
+				Tile &t = mine[i];
+				const bool finished = is_finished(i);
 				const bool progressed = !finished && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
 				if (finished) {
 					t.resident = -1;
@@ -308,7 +353,11 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 					next.taken++;
 				} else if (workers > 1) { // back to the shared queue with its sums in RAM, once they have arrived
 					t.resident = -1;
-					if (progressed) next.messages.push_back(Message{Message::TileProgressed, t});
+					if (progressed) {
+						Tile snapshot = t;
+						snapshot.data_sq = TileData(); // (the sums of squares stay with the scheduler)
+						next.messages.push_back(Message{Message::TileProgressed, std::move(snapshot)});
+					}
 					next.requeue.push_back(std::move(t));
 					next.taken++;
 				} else { // one GPU: the tile goes back to the queue at once, sums resident; its snapshot follows when it has arrived
@@ -337,6 +386,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 		sh->cv.notify_all();
 	}
 	if (fb) rmd_framebuffer_free(ctx, fb);
+	if (fb_sq) rmd_framebuffer_free(ctx, fb_sq);
 	rmd_scene_destroy(dscene);
 	rmd_context_destroy(ctx);
 	std::lock_guard<std::mutex> lock(sh->m);
@@ -347,6 +397,10 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 } // namespace
 
 TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
+	if (!(settings.adaptive_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold must be >= 0 (0 = off)");
+	if (settings.adaptive_threshold > 0.0 && settings.samples_per_iteration == 0)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)");
+	if (!(settings.adaptive_floor > 0.0) || !std::isfinite(settings.adaptive_floor)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_floor must be finite and > 0");
 	TaskHandle h;
 	h.settings = settings;
 	h.shared_ = std::make_shared<TaskHandle::Shared>();

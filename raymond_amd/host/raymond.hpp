@@ -123,6 +123,11 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	bool use_dof = false; // opt-in: generate_primary_ray_with_dof (src/trace.rs:335-360); the reference's loop never calls it (:199)
 	// opt-in (raymond_hip.h: RMD_RENDER_END_BLACK_PATHS): end zero-throughput paths in scenes with meshes too; false = reference-identical
 	bool end_black_paths = false;
+	// Adaptive tile sampling (an extension; 0 = off, the reference's behaviour): after every progressive pass a tile whose relative standard error
+	// (raymond_hip.h: rmd_tile_error, floor `adaptive_floor`) is at most `adaptive_threshold` is finished at the samples it has.  Needs
+	// samples_per_iteration > 0; render_tiled throws raymond::Error otherwise, and for a negative threshold.
+	double adaptive_threshold = 0.0;
+	double adaptive_floor = 1e-3;
 };
 
 // core/src/tile.rs:13 `data: Vec<Vector3>` — the running sums of a tile, width * height of them, row-major.  Here a VIEW: the tiles of one
@@ -158,6 +163,8 @@ struct Tile { // core/src/tile.rs:7-14
 	size_t sample_count = 0, width = 0, height = 0, left = 0, top = 0;
 	TileData data; // running sums, width*height.  EMPTY while the tile waits in the queue with its sums resident on a GPU (`resident`)
 	int resident = -1; // the worker (GPU) whose device framebuffer holds the tile's sums; -1: `data` does (an extension: the reference's tiles live in RAM)
+	TileData data_sq;  // adaptive renders with several GPUs: the running sums of squares (rmd_render_tiles_moments), travelling through RAM with `data`
+	                   // while the tile waits in the queue; empty otherwise
 };
 struct Message { // src/trace.rs:62-66
 	enum Kind { TileFinished, TileProgressed } kind;

@@ -48,6 +48,18 @@ SIGNATURES = {
         C.c_int32,
         [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, _vp],
     ),
+    "rmd_render_tiles_moments": (
+        C.c_int32,
+        [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, _vp, _vp],
+    ),
+    "rmd_render_tiles_moments_async": (
+        C.c_int32,
+        [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, _vp, _vp],
+    ),
+    "rmd_tile_error": (
+        C.c_int32,
+        [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _P(abi.TileRect), C.c_uint32, _vp],
+    ),
     "rmd_context_synchronize": (C.c_int32, [_vp]),
     "rmd_render_tiles_host": (
         C.c_int32,

@@ -139,13 +139,26 @@ class Framebuffer:
             self.ptr = C.c_void_p()
 
 
-def render_tiles(ctx, dscene, camera_settings, settings, tiles, framebuffer, sample_begin=0, sample_count=None, sync=True):
-    """rmd_render_tiles[_async]: add `sample_count` samples per pixel of `tiles` into `framebuffer`."""
+def render_tiles(ctx, dscene, camera_settings, settings, tiles, framebuffer, sample_begin=0, sample_count=None, sync=True, framebuffer_sq=None):
+    """rmd_render_tiles[_async]: add `sample_count` samples per pixel of `tiles` into `framebuffer`.  With `framebuffer_sq`:
+    rmd_render_tiles_moments[_async], which also adds every sample's square to it."""
     cam = camera_settings.pod()
     st = settings.pod(sample_begin, sample_count)
     arr = tiles if isinstance(tiles, tuple) and len(tiles) == 2 and hasattr(tiles[0], "_length_") else (tile_array(tiles), len(tiles))
-    fn = ctx.L.rmd_render_tiles if sync else ctx.L.rmd_render_tiles_async
-    ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], framebuffer.ptr))
+    if framebuffer_sq is None:
+        fn = ctx.L.rmd_render_tiles if sync else ctx.L.rmd_render_tiles_async
+        ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], framebuffer.ptr))
+    else:
+        fn = ctx.L.rmd_render_tiles_moments if sync else ctx.L.rmd_render_tiles_moments_async
+        ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], framebuffer.ptr, framebuffer_sq.ptr))
+
+
+def tile_error(ctx, framebuffer, framebuffer_sq, sample_count, floor, tiles):
+    """rmd_tile_error: per tile, the relative standard error of its worst pixel and channel after `sample_count` samples (float64 array)."""
+    out = np.empty(max(1, len(tiles)), dtype=np.float64)
+    ctx.check(ctx.L.rmd_tile_error(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, int(sample_count), float(floor),
+                                   tile_array(tiles), len(tiles), out.ctypes.data_as(C.c_void_p)))
+    return out[: len(tiles)]
 
 
 def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
@@ -160,10 +173,11 @@ def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
 
 # ---------------------------------------------------------------- the reference-shaped API
 class Tile:  # core/src/tile.rs:7-14
-    def __init__(self, left, top, width, height, sample_count, data):
+    def __init__(self, left, top, width, height, sample_count, data, error=None):
         self.left, self.top, self.width, self.height = left, top, width, height
         self.sample_count = sample_count
         self.data = data  # (height, width, 3) running sums, like Tile.data
+        self.error = error  # adaptive renders (an extension): the tile's rmd_tile_error at sample_count when it was checked, else None
 
 
 class Message:  # src/trace.rs:62-66
@@ -211,41 +225,58 @@ class TaskHandle:  # src/trace.rs:70-135
 
 
 def render_tiled(scene, settings, devices=(0,)):
-    """render_tiled (src/trace.rs:137): tiles -> workers -> TaskHandle.  Workers are GPU contexts."""
+    """render_tiled (src/trace.rs:137): tiles -> workers -> TaskHandle.  Workers are GPU contexts.
+
+    Adaptive (settings.adaptive_threshold > 0, an extension): every pass renders the tiles that are still live with their second moments, and
+    after each pass that leaves them below sample_count a tile whose rmd_tile_error is at most the threshold is sent as TileFinished at its
+    current sample count and takes no further passes; the others are sent as TileProgressed and go on."""
+    settings.check_adaptive()
+    adaptive = settings.adaptive_threshold > 0.0
     cam = settings.camera_settings
     W, H = cam.backbuffer_width, cam.backbuffer_height
     tiles = generate_tiles(W, H, settings.tile_size)
     workers = []
     for d in devices:
         ctx = Context(d)
-        workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H)))
-    shares = [tiles[i :: len(workers)] for i in range(len(workers))]
+        workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H), Framebuffer(ctx, W, H) if adaptive else None))
+    shares = [tiles[i :: len(workers)] for i in range(len(workers))]  # adaptive: the tiles of a share that are still live
     step = settings.samples_per_iteration if settings.samples_per_iteration else settings.sample_count
     messages = []
+    finished = []
     done = 0
     try:
         while done < settings.sample_count:
             n = min(step, settings.sample_count - done)
-            for (ctx, ds, fb), share in zip(workers, shares):
+            for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
                 if share:
-                    render_tiles(ctx, ds, cam, settings, share, fb, done, n, sync=False)
-            for ctx, _, _ in workers:
+                    render_tiles(ctx, ds, cam, settings, share, fb, done, n, sync=False, framebuffer_sq=fb_sq)
+            for ctx, _, _, _ in workers:
                 ctx.synchronize()
             done += n
             if done < settings.sample_count and settings.samples_per_iteration:
-                for (ctx, ds, fb), share in zip(workers, shares):
+                for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
+                    share = shares[i]
+                    errors = tile_error(ctx, fb, fb_sq, done, settings.adaptive_floor, share) if adaptive and share else [None] * len(share)
                     img = fb.download()
-                    for (l, t, w, h) in share:
-                        messages.append(Message.TileProgressed(Tile(l, t, w, h, done, img[t : t + h, l : l + w].copy())))
-        finished = []
-        for (ctx, ds, fb), share in zip(workers, shares):
+                    live = []
+                    for (l, t, w, h), e in zip(share, errors):
+                        tile = Tile(l, t, w, h, done, img[t : t + h, l : l + w].copy(), None if e is None else float(e))
+                        if adaptive and e <= settings.adaptive_threshold:
+                            finished.append(Message.TileFinished(tile))  # converged: finished at the samples it has
+                        else:
+                            messages.append(Message.TileProgressed(tile))
+                            live.append((l, t, w, h))
+                    shares[i] = live
+        for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
             img = fb.download()
             for (l, t, w, h) in share:
                 finished.append(Message.TileFinished(Tile(l, t, w, h, settings.sample_count, img[t : t + h, l : l + w].copy())))
         messages = messages + finished  # progress snapshots first, then the finished tiles
     finally:
-        for ctx, ds, fb in workers:
+        for ctx, ds, fb, fb_sq in workers:
             fb.close()
+            if fb_sq is not None:
+                fb_sq.close()
             ds.close()
             ctx.close()
     handle = TaskHandle(settings, messages)

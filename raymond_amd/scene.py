@@ -243,7 +243,8 @@ class Settings:
     """src/trace.rs:42-55 plus the RNG seed the reference lacks."""
 
     def __init__(self, camera_settings, sample_count, tile_size=(32, 32), bounce_limit=5, samples_per_iteration=0,
-                 worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False):
+                 worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
+                 adaptive_floor=1e-3):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -259,6 +260,20 @@ class Settings:
         # reference's sample 0 x NaN = NaN).  end_black_paths=True ends them in grid scenes too; trace_black_paths=True never ends one.
         self.trace_black_paths = bool(trace_black_paths)
         self.end_black_paths = bool(end_black_paths)
+        # Adaptive tile sampling (an extension; 0.0 = off, the reference's behaviour): after every progressive pass a tile whose relative standard
+        # error (raymond_hip.h: rmd_tile_error, with `adaptive_floor` as its floor) is at most `adaptive_threshold` is finished at the samples it has.
+        self.adaptive_threshold = float(adaptive_threshold)
+        self.adaptive_floor = float(adaptive_floor)
+        self.check_adaptive()
+
+    def check_adaptive(self):
+        """Raises ValueError for adaptive settings render_tiled cannot follow."""
+        if not self.adaptive_threshold >= 0.0:
+            raise ValueError("adaptive_threshold must be >= 0 (0 = off)")
+        if self.adaptive_threshold > 0.0 and self.samples_per_iteration == 0:
+            raise ValueError("adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)")
+        if not (self.adaptive_floor > 0.0 and np.isfinite(self.adaptive_floor)):
+            raise ValueError("adaptive_floor must be finite and > 0")
 
     def pod(self, sample_begin=0, sample_count=None):
         s = abi.Settings()
