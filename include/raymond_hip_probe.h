@@ -74,6 +74,18 @@ rmd_status rmd_probe_triangle_sphere(size_t n, const double *pos9, double *out5)
  * chooses the allowance: the triangle's own, or a grid's largest); pass[i] = the pre-test lets the pair through, hit[i] / t[i] = the reference's test.
  * A pair with hit = 1 and pass = 0 would be a silently missed hit: tests/test_gpu_reference_pins.py asserts there is none among the adversarial
  * pairs of tests/test_pretest_allowance.py. */
+/* Host only (no device needed): the form of a render launch as launch_render chooses it (raymond_amd/csrc/launch.hpp: LaunchPlan).  mode 0 = tiles
+ * (direct), 1 = tiles buffered (split), 2 = list; grid = 1: the grid instantiation.  Per entry in5 = n_objects, mask_words_total, flags (1 = path
+ * queues attached, 2 = persistence asked for — CUs and a work counter given —, 4 = chain_items, 8 = the squares asked for), n_waves, n_cus;
+ * out8 = persistent, queued, chained, moments (the instantiation launched), waves per workgroup, workgroups, the per-wave LDS area charged, the
+ * workgroup's dynamic LDS bytes.  tests/test_launch_plan.py checks it over every scene the library admits. */
+rmd_status rmd_probe_launch_plan(uint32_t mode, uint32_t grid, size_t n, const uint32_t *in5, uint64_t *out8);
+/* Host only: the sizes the plan is made of for instantiation (mode, grid): out8 = the LDS budget, sizeof(DevObject), the per-wave area of the
+ * instantiation's unqueued kernels, the queued wave's area, waves of its persistent workgroup, waves of a one-wave-per-item workgroup of a scene with
+ * grids, the spheres kernel's per-wave pool bytes (admission), the grids' mask budget bytes. */
+rmd_status rmd_probe_launch_sizes(uint32_t mode, uint32_t grid, uint64_t *out8);
+/* Host only: the LDS layout of an uploaded scene — objects in the table, grids, and words of the grids' occupancy masks. */
+rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total);
 rmd_status rmd_probe_pretest_pairs(rmd_context *ctx, size_t n, const double *sphere5, const double *pos9, const double *ray6, int32_t *pass,
                                    int32_t *hit, double *t);
 

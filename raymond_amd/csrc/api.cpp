@@ -75,7 +75,7 @@ rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, r
 		const char *form = std::getenv("RMD_LAUNCH_FORM");
 		ctx->tunable[RMD_TUNE_LAUNCH_FORM] = !form ? 0 : (std::strcmp(form, "per-item") == 0 || std::strcmp(form, "1") == 0) ? 1 : (std::strcmp(form, "persistent") == 0 || std::strcmp(form, "2") == 0) ? 2 : 0;
 #if RMD_DIAG
-		ctx->debug_flags = (uint32_t)env_int("RMD_DEBUG"); // DIAG builds only: 1 | 2 are timing ablations that change results, 8 | 16 count events
+		ctx->debug_flags = (uint32_t)env_int("RMD_DEBUG"); // DIAG builds only: 1 | 2 are timing ablations that change results, 8 | 16 count events, 256 fails the path queues' allocation
 #endif
 	}
 	if (hipEventCreate(&ctx->ev_start) != hipSuccess || hipEventCreate(&ctx->ev_stop) != hipSuccess) {
@@ -812,7 +812,12 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 			if (ctx->queue_buf_bytes < need) {
 				if (ctx->d_queue_buf) RMD_HIP(ctx, hipFree(ctx->d_queue_buf));
 				ctx->d_queue_buf = nullptr, ctx->queue_buf_bytes = 0;
+#if RMD_DIAG
+				// RMD_DEBUG bit 256 (DIAG builds): the device has no memory for the queues — the fallback below (tests/test_gpu_launch_edges.py)
+				const hipError_t qe = (ctx->debug_flags & 256u) ? hipErrorOutOfMemory : hipMalloc((void **)&ctx->d_queue_buf, need);
+#else
 				const hipError_t qe = hipMalloc((void **)&ctx->d_queue_buf, need);
+#endif
 				if (qe == hipSuccess) {
 					ctx->queue_buf_bytes = need;
 					// (zeroed once: a trip's idle lanes read the trip's first entry, never one nobody wrote — but a fresh allocation should not hold another process's data)
@@ -844,7 +849,7 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		ctx->last_launch.passes++, ctx->last_launch.split_k = Q.split_k, ctx->last_launch.buffered = Q.buffered;
 		ctx->last_launch.persistent = shape.persistent, ctx->last_launch.waves_per_workgroup = shape.waves_per_wg; // the form it was launched in, not the one asked for
 		ctx->last_launch.queued = shape.queued;
-		ctx->last_launch.chained = (shape.persistent && !shape.queued) ? Q.chain_items : 0u;
+		ctx->last_launch.chained = shape.chained;
 		if (settings->sample_count == 0) break;
 	}
 	RMD_HIP(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));

@@ -165,13 +165,34 @@ size_t render_lds_bytes(uint32_t n_objects, uint32_t mask_words_total, uint32_t 
 	       (size_t)waves_per_wg * wave_lds_bytes(mask_words_total ? 1u : 0u);
 }
 
-// Waves per workgroup: one for grid-less scenes (finest load balance); with grids the waves of a workgroup share the
-// occupancy masks staged in LDS.
-uint32_t render_waves_per_wg(uint32_t n_objects, uint32_t mask_words_total) {
-	if (mask_words_total == 0) return 1;
-	uint32_t w = kGridWavesPerWg;
-	while (w > 1 && render_lds_bytes(n_objects, mask_words_total, w) > kLdsBudgetBytes) w--;
-	return w;
+LaunchPlan plan_render_launch(int mode, bool grid, uint32_t n_objects, uint32_t mask_words_total, bool queues, bool persist, bool chain_items, bool moments,
+                              uint32_t n_waves, uint32_t n_cus) {
+	switch (mode * 2 + (grid ? 1 : 0)) {
+	case kModeTiles * 2: return plan_launch<kModeTiles, false>(n_objects, mask_words_total, queues, persist, chain_items, moments, n_waves, n_cus);
+	case kModeTiles * 2 + 1: return plan_launch<kModeTiles, true>(n_objects, mask_words_total, queues, persist, chain_items, moments, n_waves, n_cus);
+	case kModeTilesBuffered * 2: return plan_launch<kModeTilesBuffered, false>(n_objects, mask_words_total, queues, persist, chain_items, moments, n_waves, n_cus);
+	case kModeTilesBuffered * 2 + 1: return plan_launch<kModeTilesBuffered, true>(n_objects, mask_words_total, queues, persist, chain_items, moments, n_waves, n_cus);
+	case kModeList * 2: return plan_launch<kModeList, false>(n_objects, mask_words_total, queues, persist, chain_items, moments, n_waves, n_cus);
+	case kModeList * 2 + 1: return plan_launch<kModeList, true>(n_objects, mask_words_total, queues, persist, chain_items, moments, n_waves, n_cus);
+	}
+	return LaunchPlan{};
+}
+
+template <int MODE, bool GRID>
+static void lds_sizes_of(uint64_t out[8]) {
+	out[0] = kLdsBudgetBytes, out[1] = sizeof(DevObject), out[2] = wave_lds_of<MODE, GRID>(GRID ? 1u : 0u), out[3] = queued_wave_lds_bytes();
+	out[4] = kPersistWaves<MODE, GRID>, out[5] = kGridWavesPerWg, out[6] = kSortPoolBytes, out[7] = kMaskBudgetBytes;
+}
+void render_lds_sizes(int mode, bool grid, uint64_t out[8]) {
+	switch (mode * 2 + (grid ? 1 : 0)) {
+	case kModeTiles * 2: return lds_sizes_of<kModeTiles, false>(out);
+	case kModeTiles * 2 + 1: return lds_sizes_of<kModeTiles, true>(out);
+	case kModeTilesBuffered * 2: return lds_sizes_of<kModeTilesBuffered, false>(out);
+	case kModeTilesBuffered * 2 + 1: return lds_sizes_of<kModeTilesBuffered, true>(out);
+	case kModeList * 2: return lds_sizes_of<kModeList, false>(out);
+	case kModeList * 2 + 1: return lds_sizes_of<kModeList, true>(out);
+	}
+	for (int i = 0; i < 8; i++) out[i] = 0;
 }
 
 hipError_t launch_render_tiles(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,

@@ -73,14 +73,29 @@ constexpr size_t kSortPoolBytes = 84u * kSortSlots; // per-wave LDS (sizeof(HitS
 constexpr size_t kWaveHeadBytes = 16u;
 // the form a render launch was made in (render_kernel.hpp: launch_render) -> rmd_launch_info
 struct LaunchShape {
-	uint32_t persistent = 0, waves_per_wg = 0, queued = 0, resident_waves = 0;
+	uint32_t persistent = 0, waves_per_wg = 0, queued = 0, resident_waves = 0, chained = 0;
 };
+// The form of one render launch, decided on the host from the scene's LDS alone (render_kernel.hpp: plan_launch): which instantiation —
+// render_kernel<MODE, GRID, persistent, chained, queued> or render_kernel_moments<MODE, GRID, persistent> —, its waves per workgroup, the per-wave
+// area it is charged, its dynamic LDS and its workgroups.  launch_render launches exactly this; tests/test_launch_plan.py checks it over every
+// scene check_render_args admits (rmd_probe_launch_plan).
+struct LaunchPlan {
+	uint32_t persistent = 0, queued = 0, chained = 0, moments = 0, waves_per_wg = 0, workgroups = 0;
+	size_t wave_lds = 0, lds = 0;
+};
+// mode: render_kernel.hpp's kModeTiles / kModeTilesBuffered / kModeList.  queues: path queues are attached (P.queue_buf); persist: the persistent
+// form was asked for (n_cus and P.work_counter); chain_items: P.chain_items; moments: the squares are asked for (out_sq)
+LaunchPlan plan_render_launch(int mode, bool grid, uint32_t n_objects, uint32_t mask_words_total, bool queues, bool persist, bool chain_items, bool moments,
+                              uint32_t n_waves, uint32_t n_cus);
+// the sizes the plan is made of, for instantiation (mode, grid): out[0] the LDS budget, [1] sizeof(DevObject), [2] the per-wave area of the
+// instantiation's unqueued kernels, [3] the queued form's, [4] waves of its persistent workgroup, [5] kGridWavesPerWg, [6] kSortPoolBytes,
+// [7] kMaskBudgetBytes
+void render_lds_sizes(int mode, bool grid, uint64_t out[8]);
 // paths a wave of the queued form may have in flight (render_kernel.hpp: render_wave_queued; at least 192, a multiple of 64)
 constexpr uint32_t kQueuePaths = 256;
 inline size_t path_queue_bytes_host(uint32_t cap) { return (size_t)cap * (9u * 8u + 13u * 8u + 4u * 4u + 9u * 4u); } // (render_kernel.hpp: path_queue_bytes)
 static_assert(kQueuePaths >= 192u && kQueuePaths % 64u == 0u, "two stacks short of a full trip + the 64 paths of a generation trip");
 size_t render_lds_bytes(uint32_t n_objects, uint32_t mask_words_total, uint32_t waves_per_wg);
-uint32_t render_waves_per_wg(uint32_t n_objects, uint32_t mask_words_total);
 // n_cus > 0 and P.work_counter set: grid scenes run as persistent workgroups (render_kernel.hpp).  accum_sq (optional): every sample's square is
 // added there too, in the same order (rmd_render_tiles_moments)
 hipError_t launch_render_tiles(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,

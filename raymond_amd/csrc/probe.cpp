@@ -233,6 +233,30 @@ rmd_status rmd_probe_triangle_sphere(size_t n, const double *pos9, double *out5)
 	return RMD_OK;
 }
 
+rmd_status rmd_probe_launch_plan(uint32_t mode, uint32_t grid, size_t n, const uint32_t *in5, uint64_t *out8) {
+	if (mode > 2u || grid > 1u || (n != 0 && (!in5 || !out8))) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	for (size_t i = 0; i < n; i++) {
+		const uint32_t *a = in5 + i * 5;
+		const rmd::LaunchPlan L = rmd::plan_render_launch((int)mode, grid != 0u, a[0], a[1], (a[2] & 1u) != 0u, (a[2] & 2u) != 0u, (a[2] & 4u) != 0u,
+		                                                  (a[2] & 8u) != 0u, a[3], a[4]);
+		uint64_t *o = out8 + i * 8;
+		o[0] = L.persistent, o[1] = L.queued, o[2] = L.chained, o[3] = L.moments, o[4] = L.waves_per_wg, o[5] = L.workgroups, o[6] = L.wave_lds, o[7] = L.lds;
+	}
+	return RMD_OK;
+}
+
+rmd_status rmd_probe_launch_sizes(uint32_t mode, uint32_t grid, uint64_t *out8) {
+	if (mode > 2u || grid > 1u || !out8) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	rmd::render_lds_sizes((int)mode, grid != 0u, out8);
+	return RMD_OK;
+}
+
+rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total) {
+	if (!scene || !n_objects || !n_grids || !mask_words_total) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	*n_objects = scene->n_objects, *n_grids = scene->n_grids, *mask_words_total = scene->mask_words_total;
+	return RMD_OK;
+}
+
 rmd_status rmd_probe_pretest_pairs(rmd_context *ctx, size_t n, const double *sphere5, const double *pos9, const double *ray6, int32_t *pass, int32_t *hit,
                                    double *t) {
 	if (n != 0 && (!sphere5 || !pos9 || !ray6 || !pass || !hit || !t)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");

@@ -1423,85 +1423,94 @@ __global__ __launch_bounds__((kWgThreads<MODE, GRID, PERSIST>), (kMinWavesPerSim
 	render_kernel_body<MODE, GRID, PERSIST, false, false, true>(P, objs, grids, work, out, path_obj, path_sub, out_sq);
 }
 
-// n_cus > 0 (tile modes of grid scenes): the persistent form, one 16-wave workgroup per CU (fewer when there are fewer work items);
-// P.work_counter must point at a zeroed device word.
+// The form of a launch (launch.hpp: LaunchPlan), from the LDS of a workgroup of this instantiation: [object table][grid occupancy masks][one area
+// per wave].  persist (n_cus > 0 and a work counter; tile modes only): persistent workgroups of kPersistWaves waves, fewer when a large object table
+// (128 bytes an object) or several grids' masks leave room for fewer per-wave areas — pools of the spheres kernel, walk scratch + throughputs +
+// carried walks of the mesh kernel —, down to 4 (the kernel takes its wave count from blockDim).  Below 4 waves, or when persistence was not asked
+// for, one wave per work item in workgroups of kGridWavesPerWg waves or fewer (scenes with grids: the waves share the staged masks) or of one.
+// Each form is charged the area of the kernel it launches: the queued wave's (queued_wave_lds_bytes) exactly when the queued kernel runs.
+template <int MODE, bool GRID>
+inline LaunchPlan plan_launch(uint32_t n_objects, uint32_t mask_words_total, bool queues, bool persist, bool chain_items, bool moments, uint32_t n_waves,
+                              uint32_t n_cus) {
+	LaunchPlan L;
+	const size_t fixed = (size_t)n_objects * sizeof(DevObject) + (size_t)((mask_words_total + 3u) & ~3u) * 4u;
+	// the kernel's own area: wave_lds_of<MODE, GRID, QUEUED>(P.n_grids), and the GRID instantiation runs exactly when P.n_grids != 0
+	const size_t wave = wave_lds_of<MODE, GRID>(GRID ? 1u : 0u);
+	L.moments = kMomentsInKernel<MODE, GRID> && moments ? 1u : 0u;
+	if (MODE != kModeList && persist) {
+		const bool queued = kPathQueues<MODE, GRID> && queues; // (api.cpp attaches the queues to the launches that take this form)
+		const size_t pwave = queued ? wave_lds_of<MODE, GRID, true>(1u) : wave;
+		uint32_t pw = kPersistWaves<MODE, GRID>;
+		while (pw > 4u && fixed + pw * pwave > kLdsBudgetBytes) pw--;
+		if (fixed + pw * pwave <= kLdsBudgetBytes) {
+			const uint32_t wgs = (n_waves + pw - 1u) / pw;
+			L.persistent = 1u, L.waves_per_wg = pw, L.wave_lds = pwave, L.lds = fixed + pw * pwave, L.workgroups = wgs < n_cus ? wgs : n_cus;
+			L.queued = queued ? 1u : 0u;
+			L.chained = kChainItems<MODE, GRID> && chain_items && !queued ? 1u : 0u; // short launches of scenes with grids: the waves chain their work items
+			return L;
+		}
+	}
+	// one wave per work item: the unqueued kernel, whatever queues were attached
+	uint32_t w = GRID ? kGridWavesPerWg : 1u;
+	while (w > 1u && fixed + w * wave > kLdsBudgetBytes) w--;
+	L.waves_per_wg = w, L.wave_lds = wave, L.lds = fixed + w * wave, L.workgroups = (n_waves + w - 1u) / w;
+	return L;
+}
+
+// n_cus > 0 (tile modes): the persistent form, one workgroup per CU (fewer when there are fewer work items); P.work_counter must point at a zeroed
+// device word.  The form is plan_launch's.
 // `shape` (optional) receives the form the kernel was actually launched in.
 // `out_sq` (optional, the instantiations of kMomentsInKernel): the render_kernel_moments launch of the same form.
 template <int MODE, bool GRID>
 inline hipError_t launch_render(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const void *work,
                                 uint32_t n_waves, double *out, int32_t *path_obj, uint32_t *path_sub, uint32_t n_cus = 0, LaunchShape *shape = nullptr,
                                 double *out_sq = nullptr) {
-	[[maybe_unused]] const bool moments = kMomentsInKernel<MODE, GRID> && out_sq != nullptr;
-	// LDS of a workgroup of `waves` waves of this instantiation: [object table][grid occupancy masks][per-wave area]
-	[[maybe_unused]] const bool queued = kPathQueues<MODE, GRID> && P.queue_buf != nullptr; // (api.cpp provides the queues for the launches that take this form)
-	auto lds_for = [&](uint32_t waves) {
-		return (size_t)P.n_objects * sizeof(DevObject) + (size_t)((P.mask_words_total + 3u) & ~3u) * 4u +
-		       (size_t)waves * (queued ? wave_lds_of<MODE, GRID, true>(1u) : wave_lds_of<MODE, GRID>(P.mask_words_total ? 1u : 0u));
-	};
+	const LaunchPlan L = plan_launch<MODE, GRID>(P.n_objects, P.mask_words_total, P.queue_buf != nullptr, n_cus != 0u && P.work_counter != nullptr,
+	                                             P.chain_items != 0u, out_sq != nullptr, n_waves, n_cus);
+	if (L.lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never: tests/test_launch_plan.py)
+	const void *fn = nullptr;
 	if constexpr (MODE != kModeList) {
-		uint32_t pw = kPersistWaves<MODE, GRID>;
-		// a large object table (128 bytes an object) or several grids' masks leave room for fewer per-wave areas — pools of the spheres kernel,
-		// walk scratch + throughputs + carried walks (6,656 bytes) of the mesh kernel: fewer waves per workgroup (the kernel takes its wave count
-		// from blockDim); below 4 waves the launch runs as one wave per item
-		while (pw > 4u && lds_for(pw) > kLdsBudgetBytes) pw--;
-		if (n_cus != 0u && P.work_counter != nullptr && lds_for(pw) <= kLdsBudgetBytes) {
-			const size_t lds = lds_for(pw);
-			// short launches of scenes with grids: the instantiation whose waves chain their work items (render_wave, CHAIN)
-			const bool chain = kChainItems<MODE, GRID> && P.chain_items != 0u && !queued;
-			hipError_t e = hipFuncSetAttribute(queued  ? reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true, false, (kPathQueues<MODE, GRID>)>)
-			                                   : chain ? reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true, (kChainItems<MODE, GRID>)>)
-			                                           : reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true>),
-			                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
-			if (e != hipSuccess) return e;
-			const uint32_t wgs = (n_waves + pw - 1u) / pw, resident = n_cus;
+		if (L.persistent) {
+			fn = L.queued    ? reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true, false, (kPathQueues<MODE, GRID>)>)
+			     : L.chained ? reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true, (kChainItems<MODE, GRID>)>)
+			                 : reinterpret_cast<const void *>(&render_kernel<MODE, GRID, true>);
 			if constexpr (kMomentsInKernel<MODE, GRID>) {
-				if (moments) { // (never queued or chained: those are split launches of scenes with grids)
-					e = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel_moments<MODE, GRID, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
-					if (e != hipSuccess) return e;
-					hipLaunchKernelGGL((render_kernel_moments<MODE, GRID, true>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs, grids, work, out,
-					                   path_obj, path_sub, out_sq);
-					if (shape) shape->persistent = 1u, shape->waves_per_wg = pw, shape->queued = 0u, shape->resident_waves = (wgs < resident ? wgs : resident) * pw;
-					return hipGetLastError();
-				}
+				if (L.moments) fn = reinterpret_cast<const void *>(&render_kernel_moments<MODE, GRID, true>);
 			}
-			if (queued)
-				hipLaunchKernelGGL((render_kernel<MODE, GRID, true, false, (kPathQueues<MODE, GRID>)>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs,
-				                   grids, work, out, path_obj, path_sub);
-			else if (chain)
-				hipLaunchKernelGGL((render_kernel<MODE, GRID, true, (kChainItems<MODE, GRID>)>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs,
-				                   grids, work, out, path_obj, path_sub);
-			else
-				hipLaunchKernelGGL((render_kernel<MODE, GRID, true>), dim3(wgs < resident ? wgs : resident), dim3(64u * pw), lds, stream, P, objs, grids, work, out,
-				                   path_obj, path_sub);
-			if (shape) shape->persistent = 1u, shape->waves_per_wg = pw, shape->queued = queued ? 1u : 0u, shape->resident_waves = (wgs < resident ? wgs : resident) * pw;
-			return hipGetLastError();
 		}
 	}
-	const uint32_t wpw = render_waves_per_wg(P.n_objects, P.mask_words_total);
-	const size_t lds = lds_for(wpw);
-	if constexpr (kMomentsInKernel<MODE, GRID>) {
-		if (moments) {
-			if (lds > 64u * 1024u) {
-				hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel_moments<MODE, GRID, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-				                                   (int)kLdsBudgetBytes);
-				if (e != hipSuccess) return e;
-			}
-			hipLaunchKernelGGL((render_kernel_moments<MODE, GRID, false>), dim3((n_waves + wpw - 1u) / wpw), dim3(64u * wpw), lds, stream, P, objs, grids, work, out,
-			                   path_obj, path_sub, out_sq);
-			if (shape) shape->persistent = 0u, shape->waves_per_wg = wpw;
-			return hipGetLastError();
+	if (!fn) {
+		if constexpr (kMomentsInKernel<MODE, GRID>) {
+			if (L.moments) fn = reinterpret_cast<const void *>(&render_kernel_moments<MODE, GRID, false>);
 		}
+		if (!fn) fn = reinterpret_cast<const void *>(&render_kernel<MODE, GRID, false>);
 	}
-	if (lds > 64u * 1024u) { // above the default dynamic-LDS limit: opt in on the current device (cheap, and correct per device)
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&render_kernel<MODE, GRID, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-		                                   (int)kLdsBudgetBytes);
+	// persistent workgroups, and any above the default dynamic-LDS limit: opt in on the current device (cheap, and correct per device)
+	if (L.persistent || L.lds > 64u * 1024u) {
+		hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
 		if (e != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL((render_kernel<MODE, GRID, false>), dim3((n_waves + wpw - 1u) / wpw), dim3(64u * wpw), lds, stream, P, objs, grids, work, out,
-	                   path_obj, path_sub);
-	if (shape) shape->persistent = 0u, shape->waves_per_wg = wpw;
+	const dim3 grid_dim(L.workgroups), block_dim(64u * L.waves_per_wg);
+	if (L.moments) {
+		if constexpr (kMomentsInKernel<MODE, GRID>) {
+			if (L.persistent) hipLaunchKernelGGL((render_kernel_moments<MODE, GRID, true>), grid_dim, block_dim, L.lds, stream, P, objs, grids, work, out, path_obj, path_sub, out_sq);
+			else hipLaunchKernelGGL((render_kernel_moments<MODE, GRID, false>), grid_dim, block_dim, L.lds, stream, P, objs, grids, work, out, path_obj, path_sub, out_sq);
+		}
+	} else if (L.persistent) {
+		if constexpr (MODE != kModeList) {
+			if (L.queued)
+				hipLaunchKernelGGL((render_kernel<MODE, GRID, true, false, (kPathQueues<MODE, GRID>)>), grid_dim, block_dim, L.lds, stream, P, objs, grids, work, out, path_obj,
+				                   path_sub);
+			else if (L.chained)
+				hipLaunchKernelGGL((render_kernel<MODE, GRID, true, (kChainItems<MODE, GRID>)>), grid_dim, block_dim, L.lds, stream, P, objs, grids, work, out, path_obj, path_sub);
+			else hipLaunchKernelGGL((render_kernel<MODE, GRID, true>), grid_dim, block_dim, L.lds, stream, P, objs, grids, work, out, path_obj, path_sub);
+		}
+	} else hipLaunchKernelGGL((render_kernel<MODE, GRID, false>), grid_dim, block_dim, L.lds, stream, P, objs, grids, work, out, path_obj, path_sub);
+	if (shape) {
+		shape->persistent = L.persistent, shape->waves_per_wg = L.waves_per_wg, shape->queued = L.queued, shape->chained = L.chained;
+		shape->resident_waves = L.persistent ? L.workgroups * L.waves_per_wg : 0u;
+	}
 	return hipGetLastError();
 }
-
 
 } // namespace rmd

@@ -32,6 +32,9 @@ _SIGS = {
     "rmd_probe_trace_samples": [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _sz, _vp, _vp, _vp, _vp, _vp],
     "rmd_probe_triangle_sphere": [_sz, _vp, _vp],
     "rmd_probe_pretest_pairs": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rmd_probe_launch_plan": [C.c_uint32, C.c_uint32, _sz, _vp, _vp],
+    "rmd_probe_launch_sizes": [C.c_uint32, C.c_uint32, _vp],
+    "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
 }
 PATH_STRIDE = 17
 _ready = False
@@ -183,3 +186,42 @@ def pretest_pairs(ctx, sphere5, pos9, ray6):
     passed, hit, t = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n)
     ctx.check(L.rmd_probe_pretest_pairs(ctx.handle, n, _p(sphere5), _p(pos9), _p(ray6), _p(passed), _p(hit), _p(t)))
     return passed.astype(bool), hit.astype(bool), t
+
+
+# rmd_probe_launch_plan: modes, input flags and output columns
+MODE_TILES, MODE_TILES_BUFFERED, MODE_LIST = 0, 1, 2
+PLAN_QUEUES, PLAN_PERSIST, PLAN_CHAIN, PLAN_MOMENTS = 1, 2, 4, 8
+PLAN_FIELDS = ("persistent", "queued", "chained", "moments", "waves_per_wg", "workgroups", "wave_lds", "lds")
+SIZE_FIELDS = ("budget", "object", "wave", "queued_wave", "persist_waves", "grid_waves", "sort_pool", "mask_budget")
+
+
+def _host_check(st, name):
+    if st != abi.RMD_OK:
+        raise RuntimeError("%s: status %d" % (name, st))
+
+
+def launch_plan(mode, grid, n_objects, mask_words_total, flags, n_waves, n_cus):
+    """Host only (no GPU): the form launch_render gives each launch -> dict of uint64 arrays keyed by PLAN_FIELDS; the inputs broadcast against
+    each other.  api: rmd_probe_launch_plan."""
+    L = _L()
+    cols = np.broadcast_arrays(*(np.asarray(a, dtype=np.int64) for a in (n_objects, mask_words_total, flags, n_waves, n_cus)))
+    inp = np.ascontiguousarray(np.stack([c.ravel() for c in cols], axis=1).astype(np.uint32))
+    out = np.zeros((inp.shape[0], 8), dtype=np.uint64)
+    _host_check(L.rmd_probe_launch_plan(mode, int(grid), inp.shape[0], _p(inp), _p(out)), "rmd_probe_launch_plan")
+    return {k: out[:, i].astype(np.int64).reshape(cols[0].shape) for i, k in enumerate(PLAN_FIELDS)}
+
+
+def launch_sizes(mode, grid):
+    """Host only: the sizes of the launch plan of instantiation (mode, grid) -> dict keyed by SIZE_FIELDS.  api: rmd_probe_launch_sizes."""
+    L = _L()
+    out = np.zeros(8, dtype=np.uint64)
+    _host_check(L.rmd_probe_launch_sizes(mode, int(grid), _p(out)), "rmd_probe_launch_sizes")
+    return {k: int(v) for k, v in zip(SIZE_FIELDS, out)}
+
+
+def scene_layout(dscene):
+    """(n_objects, n_grids, mask_words_total) of an uploaded scene.  api: rmd_probe_scene_layout."""
+    L = _L()
+    n, g, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _host_check(L.rmd_probe_scene_layout(dscene.handle, C.byref(n), C.byref(g), C.byref(m)), "rmd_probe_scene_layout")
+    return n.value, g.value, m.value

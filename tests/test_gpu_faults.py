@@ -161,15 +161,17 @@ def test_the_product_build_ignores_the_diag_switches(gpu_ctx):
     """RMD_DEBUG is honoured by DIAG builds only: the product library renders the same frame with it set."""
     import numpy as np
 
-    from raymond_amd import render, scenes
+    from raymond_amd import abi, render, scenes
     from raymond_amd.scene import Settings, generate_tiles
 
     sc = scenes.reflective_spheres()
+    mesh = scenes.mesh_scene(scenes.lumpy_sphere_mesh(13))
     cam = scenes.camera(96, 64)
     st = Settings(cam, sample_count=4, bounce_limit=5, seed=scenes.SEED)
+    st_mesh = Settings(cam, sample_count=8, bounce_limit=4, seed=scenes.SEED)
     tiles = generate_tiles(96, 64, st.tile_size)
-    frames = []
-    for dbg in (None, "32", "224"):
+    frames, mesh_frames = [], []
+    for dbg in (None, "32", "224", "256"):  # 256: the path queues' allocation fails (tests/test_gpu_launch_edges.py)
         if dbg is None:
             os.environ.pop("RMD_DEBUG", None)
         else:
@@ -179,7 +181,17 @@ def test_the_product_build_ignores_the_diag_switches(gpu_ctx):
                 ds, fb = render.DeviceScene(ctx, sc), render.Framebuffer(ctx, 96, 64)
                 render.render_tiles(ctx, ds, cam, st, tiles, fb)
                 frames.append(fb.download())
+                ds.close()
+                # a persistent split launch of a mesh scene: the path queues are allocated whatever RMD_DEBUG says
+                ctx.set_tunable(abi.RMD_TUNE_SAMPLE_SPLIT, 2), ctx.set_tunable(abi.RMD_TUNE_LAUNCH_FORM, 2)
+                ds = render.DeviceScene(ctx, mesh)
+                fb.zero()
+                render.render_tiles(ctx, ds, cam, st_mesh, tiles, fb)
+                info = ctx.last_launch_info()
+                assert (info.persistent, info.queued) == (1, 1), (dbg, info.persistent, info.queued)
+                mesh_frames.append(fb.download())
                 fb.close(), ds.close()
         finally:
             os.environ.pop("RMD_DEBUG", None)
-    assert np.array_equal(frames[0], frames[1]) and np.array_equal(frames[0], frames[2])
+    assert all(np.array_equal(frames[0], f) for f in frames[1:])
+    assert all(f.tobytes() == mesh_frames[0].tobytes() for f in mesh_frames[1:])

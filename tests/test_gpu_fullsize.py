@@ -137,6 +137,8 @@ def test_spot_pixels_of_the_production_kernel_at_full_size(gpu_ctx, oracle, drag
     info = gpu_ctx.last_launch_info()
     assert info.split_k > 1 and info.persistent == 1 and info.passes == 1, (info.split_k, info.persistent, info.passes)
     assert info.has_grid == (0 if config == "C2" else 1) and info.end_black_paths == (1 if config == "C2" or mode == "end" else 0)
+    # the production form of each scene: mesh scenes keep their paths in queues, the spheres kernel has none
+    assert info.buffered == 1 and info.queued == (0 if config == "C2" else 1), (info.buffered, info.queued)
     full = fb.download()
     fb.close(), ds.close()
     rng = np.random.default_rng(17)
@@ -179,6 +181,7 @@ def test_whole_frame_of_the_production_kernel_against_the_oracle(gpu_ctx, oracle
     render.render_tiles(gpu_ctx, ds, cam, st, tiles, fb)
     info = gpu_ctx.last_launch_info()
     assert info.split_k > 1 and info.persistent == 1 and info.end_black_paths == (1 if config == "C2" or mode == "end" else 0)
+    assert info.buffered == 1 and info.queued == (0 if config == "C2" else 1), (info.buffered, info.queued)
     dev = fb.download()
     fb.close(), ds.close()
     ref = oracle.OracleScene(sc, fast=True).render_tiles(cam, st, tiles, threads=16)

@@ -761,6 +761,7 @@ def test_a_mesh_scene_with_many_objects_keeps_the_persistent_form_with_fewer_wav
         assert asked.persistent == want_persistent, (n_spheres, asked.persistent, asked.waves_per_workgroup)
         if want_persistent:
             assert 4 <= asked.waves_per_workgroup < 16, asked.waves_per_workgroup
+            assert asked.queued == 1  # the production form of a persistent split launch of a mesh scene: the paths in queues
         assert infos[(3, 1)].persistent == 0
         for key, img in frames.items():
             assert same_bits(img, frames[(3, 2)]).all(), key
