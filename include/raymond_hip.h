@@ -60,7 +60,8 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error) */
+	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
+	                                 rmd_denoise) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -332,6 +333,35 @@ rmd_status rmd_render_tiles_moments_async(rmd_context *ctx, const rmd_scene *sce
  */
 rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
                           uint32_t sample_count, double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host);
+/*
+ * Denoises a frame from its two sums: non-local means with the variance-normalised patch distance of Rousselle, Knaus and Zwicker, "Adaptive
+ * Rendering with Non-Local Means Filtering" (SIGGRAPH Asia 2012).  An addition within ABI 6: RMD_ABI_VERSION stays 6, no struct or entry point
+ * changes, and a caller finds the function by its symbol.
+ * S = accum_dev, Q = accum_sq_dev (W*H*3 doubles each, row-major RGB, as rmd_render_tiles_moments writes them); pixel i of rect j holds
+ * n_i = rect_sample_counts[j] samples, a pixel that no rect covers n_i = 0.  For pixel i and channel c:
+ *     u_ic = S_ic / n_i;   v_ic = max(0, (Q_ic - S_ic*u_ic) / (n_i - 1)) / n_i      (the variance of the mean, as rmd_tile_error)
+ *     pixel i is VALID if n_i >= 2 and its six S and Q values are finite
+ *     term_c(a, b) = ((u_ac - u_bc)^2 - alpha*(v_ac + min(v_ac, v_bc))) / (eps + k^2*(v_ac + v_bc)),   eps = 1e-10, k^2 = k*k
+ * For a valid p and a neighbour q = p + d with |d_x|, |d_y| <= radius, q inside the frame (not clamped) and valid: for every patch offset o with
+ * |o_x|, |o_y| <= patch_radius, a = clamp(p + o), b = clamp(q + o) (clamped to the frame: the border pixel repeats); the three terms at o are
+ * taken if a and b are both valid, summed over c in order 0, 1, 2.
+ *     D(p, q) = (sum of the taken terms) / (3 * the number of offsets taken)     — the centre offset is always taken
+ *             the offsets summed row by row (o_x ascending), then the row sums over o_y ascending
+ *     w(p, q) = exp(-max(0, D(p, q)))                                             — w(p, p) = 1 for alpha >= 0
+ *     out_pc  = sum_q w(p,q)*u_qc / sum_q w(p,q)     q in raster order (d_y, then d_x, ascending), for a valid p
+ *     out_pc  = S_pc / n_p                           exactly as IEEE gives it, for a p that is not valid (a NaN stays NaN)
+ * A pixel that is not valid is never a neighbour or a patch term, so a NaN does not spread.  out_dev holds MEANS, not sums:
+ * rmd_resolve_tonemap(out_dev, sample_count = 1) tone-maps it.  radius = 0 gives S / n bit for bit.
+ * Arguments (all checked before the device is touched): 0 <= radius <= 12, 0 <= patch_radius <= 4, k finite and > 0, alpha finite and >= 0;
+ * width, height > 0; accum_dev, accum_sq_dev and out_dev non-NULL, and no two of the three W*H*3-double ranges overlap; rects and
+ * rect_sample_counts are HOST arrays of n_rects entries (non-NULL when n_rects > 0); every rect lies inside the frame and no two overlap.
+ * Anything else is RMD_ERR_INVALID_ARGUMENT.  Synchronous (waits for the renders enqueued before it on the context; reports a device fault of
+ * one of them like rmd_context_synchronize).  Defaults a caller may start from: radius 10, patch_radius 3, k 0.45, alpha 1 (DESIGN.md
+ * section 11).
+ */
+rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                       const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                       uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev);
 /* Host-buffer convenience for a caller that keeps Tile.data in RAM, as the
  * reference does: upload accum, render, download (PCIe-inclusive). */
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera,

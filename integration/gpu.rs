@@ -67,6 +67,9 @@ extern "C" {
     fn rmd_framebuffer_download_tiles(ctx: *mut rmd_context, dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, n_rects: u32, host_packed: *mut f64) -> i32;
     fn rmd_render_tiles(ctx: *mut rmd_context, scene: *const rmd_scene, camera: *const rmd_camera, settings: *const rmd_settings,
                         tiles: *const rmd_tile_rect, n_tiles: u32, accum_dev: *mut f64) -> i32;
+    // an addition within ABI 6 (found by its symbol): the variance-guided non-local means of a frame from its sums and sums of squares
+    fn rmd_denoise(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                   rect_sample_counts: *const u32, n_rects: u32, radius: u32, patch_radius: u32, k: f64, alpha: f64, out_dev: *mut f64) -> i32;
 }
 
 fn check(ctx: *const rmd_context, status: i32) {

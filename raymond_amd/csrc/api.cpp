@@ -967,6 +967,76 @@ rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const doubl
 	return s;
 }
 
+static rmd_status denoise_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                               const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t patch_radius,
+                               double k, double alpha, double *out_dev, void *&d) {
+	if (rmd_status s = bind(ctx)) return s;
+	// device scratch: [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each]
+	const size_t img_bytes = ((size_t)width * height * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
+	RMD_HIP(ctx, hipMalloc(&d, img_bytes + rect_bytes + count_bytes));
+	uint32_t *d_img = static_cast<uint32_t *>(d);
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(static_cast<unsigned char *>(d) + img_bytes);
+	uint32_t *d_counts = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d) + img_bytes + rect_bytes);
+	if (n_rects != 0) {
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+	}
+	uint64_t largest = 0; // pixels of the largest rect: the count image gives each rect a column of 256-thread workgroups that covers it, up to 1,024
+	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
+	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
+	RMD_HIP(ctx, rmd::launch_denoise(ctx->stream, accum_dev, accum_sq_dev, d_rects, d_counts, n_rects, columns, width, height, radius, patch_radius, k, alpha,
+	                                 d_img, out_dev));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
+}
+
+// Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
+// start before it ends.
+static bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height, const char **why) {
+	std::vector<uint32_t> order;
+	for (uint32_t i = 0; i < n_rects; i++) {
+		const rmd_tile_rect &r = rects[i];
+		if ((uint64_t)r.left + r.width > width || (uint64_t)r.top + r.height > height) return *why = "rmd_denoise: tile rectangle outside the framebuffer", false;
+		if (r.width != 0 && r.height != 0) order.push_back(i);
+	}
+	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rects[a].left < rects[b].left; });
+	for (size_t i = 0; i < order.size(); i++) {
+		const rmd_tile_rect &a = rects[order[i]];
+		for (size_t j = i + 1; j < order.size() && rects[order[j]].left < (uint64_t)a.left + a.width; j++) {
+			const rmd_tile_rect &b = rects[order[j]];
+			if (b.top < (uint64_t)a.top + a.height && a.top < (uint64_t)b.top + b.height) return *why = "rmd_denoise: tile rectangles overlap", false;
+		}
+	}
+	return true;
+}
+
+rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                       const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha,
+                       double *out_dev) {
+	if (!accum_dev || !accum_sq_dev || !out_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: bad argument");
+	{ // no two of the three W*H*3-double ranges overlap
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		const unsigned __int128 s = (uintptr_t)accum_dev, q = (uintptr_t)accum_sq_dev, o = (uintptr_t)out_dev;
+		auto overlap = [&](unsigned __int128 a, unsigned __int128 b) { return a < b + bytes && b < a + bytes; };
+		if (overlap(s, q) || overlap(s, o) || overlap(q, o))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: accum_dev, accum_sq_dev and out_dev must not alias");
+	}
+	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: radius must be <= 12");
+	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: patch_radius must be <= 4");
+	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: k must be finite and > 0");
+	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: alpha must be finite and >= 0");
+	void *d = nullptr; // the device scratch: freed here whichever way the body leaves
+	const rmd_status s = rmd::guarded(ctx, "rmd_denoise", [&] {
+		const char *why = nullptr;
+		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, why);
+		return denoise_impl(ctx, accum_dev, accum_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k, alpha, out_dev, d);
+	});
+	if (d) (void)hipFree(d);
+	return s;
+}
+
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
                                  const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_host) {
 	if (rmd_status s = bind(ctx)) return s;

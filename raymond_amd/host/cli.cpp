@@ -3,6 +3,8 @@
 //
 //   raymond_cli render <spheres|dragon[:n]> W H SPP BOUNCES out.ppm [--raw out.f64] [--gpus N] [--spi K] [--aperture R] [--end-black-paths 1]
 //                                                                    [--adaptive THRESHOLD [--adaptive-floor F]]   (needs --spi)
+//                                                                    [--denoise 1 [--denoise-radius R] [--denoise-patch F] [--denoise-k K]
+//                                                                     [--denoise-alpha A]]   (the image is rmd_denoise's, on GPU 0)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -25,7 +27,8 @@ using namespace raymond;
 
 // A consumer of a progressive render: every message through poll() (src/trace.rs:115-117) as it arrives — TileProgressed snapshots are counted,
 // TileFinished tiles are assembled into the image as await() would (:93-99).  (await() itself stops collecting at the first message that is not
-// TileFinished, :101-103: with snapshots of several workers in the channel it is only safe once they have been drained.)
+// TileFinished, :101-103: with snapshots of several workers in the channel it is only safe once they have been drained.)  With st.denoise the
+// finished tiles go through denoise_tiles on GPU 0 once the workers have left, as await() would.
 static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size_t &progressed, double *last_finished_s = nullptr,
                                     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now()) {
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
@@ -44,6 +47,10 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 		}
 		if (done || finished_tiles.size() == n_tiles) break;
 		std::this_thread::sleep_for(std::chrono::microseconds(100));
+	}
+	if (st.denoise) {
+		handle.await(); // (its channel is drained: it only waits for the workers and rethrows a worker's error)
+		return finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0}) : denoise_tiles(finished_tiles, st, 0);
 	}
 	std::vector<Vector3> image(W * H, Vector3{0, 0, 0});
 	for (const Tile &t : finished_tiles)
@@ -176,6 +183,11 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--end-black-paths")) st.end_black_paths = std::atoi(argv[i + 1]) != 0; // opt-in on mesh scenes (raymond_hip.h)
 				else if (!std::strcmp(argv[i], "--adaptive")) st.adaptive_threshold = std::atof(argv[i + 1]); // (render_tiled refuses it without --spi)
 				else if (!std::strcmp(argv[i], "--adaptive-floor")) st.adaptive_floor = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise")) st.denoise = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--denoise-radius")) st.denoise_radius = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
+				else if (!std::strcmp(argv[i], "--denoise-patch")) st.denoise_patch = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
+				else if (!std::strcmp(argv[i], "--denoise-k")) st.denoise_k = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-alpha")) st.denoise_alpha = std::atof(argv[i + 1]);
 			}
 			Scene scene;
 			if (what == "spheres") scene = reflective_spheres();

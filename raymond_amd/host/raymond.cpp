@@ -186,7 +186,7 @@ struct BlockPool : std::enable_shared_from_this<BlockPool> {
 void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, size_t workers, Scene scene, Settings st, size_t batch) {
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
-	double *fb = nullptr, *fb_sq = nullptr; // fb_sq: the sums of squares of an adaptive render
+	double *fb = nullptr, *fb_sq = nullptr; // fb_sq: the sums of squares of an adaptive or denoised render
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	// a batch whose download is on its way: the tiles that become messages, in message order
 	struct Pending {
@@ -213,8 +213,8 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 		flatten(scene, objs, grids);
 		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
 		check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb), ctx, "rmd_framebuffer_alloc"); // zeroed: a fresh tile's sums
-		const bool adaptive = st.adaptive_threshold > 0.0;
-		if (adaptive) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_sq), ctx, "rmd_framebuffer_alloc");
+		const bool adaptive = st.adaptive_threshold > 0.0, moments = adaptive || st.denoise;
+		if (moments) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_sq), ctx, "rmd_framebuffer_alloc");
 		{
 			std::lock_guard<std::mutex> lock(sh->m);
 			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
@@ -257,13 +257,13 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 						rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
 						const double *src = reinterpret_cast<const double *>(t.data.data());
 						packed.insert(packed.end(), src, src + t.data.size() * 3);
-						if (adaptive) {
+						if (moments) {
 							const double *sq = reinterpret_cast<const double *>(t.data_sq.data());
 							packed_sq.insert(packed_sq.end(), sq, sq + t.data_sq.size() * 3);
 						}
 					}
 				if (!rects.empty()) check(rmd_framebuffer_upload_tiles(ctx, packed.data(), fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
-				if (!rects.empty() && adaptive)
+				if (!rects.empty() && moments)
 					check(rmd_framebuffer_upload_tiles(ctx, packed_sq.data(), fb_sq, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
 			}
 			// tiles of one batch may be at different sample counts: one launch per count (enqueued, not waited for)
@@ -276,7 +276,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 				rmd_settings rs;
 				std::memset(&rs, 0, sizeof(rs));
 				rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)begin, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
-				if (adaptive) check(rmd_render_tiles_moments_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb, fb_sq), ctx, "rmd_render_tiles_moments");
+				if (moments) check(rmd_render_tiles_moments_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb, fb_sq), ctx, "rmd_render_tiles_moments");
 				else check(rmd_render_tiles_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb), ctx, "rmd_render_tiles");
 				for (size_t i : grp.second) mine[i].sample_count += n, mine[i].resident = me, mine[i].data = TileData(), mine[i].data_sq = TileData(); // :207 — the sums are on this GPU now
 			}
@@ -306,7 +306,8 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 			std::vector<size_t> want;
 			std::vector<Tile> resident_requeue;
 			size_t pixels = 0;
-			std::vector<rmd_tile_rect> rects_sq; // adaptive, several GPUs: the sums of squares of the tiles that go back to the shared queue
+			// the sums of squares: of the tiles that go back to the shared queue (adaptive or denoised, several GPUs) and of the finished tiles (denoised)
+			std::vector<rmd_tile_rect> rects_sq;
 			std::vector<size_t> want_sq;
 			size_t pixels_sq = 0;
 			for (size_t i = 0; i < mine.size(); i++) {
@@ -318,7 +319,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 					rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
 					pixels += t.width * t.height;
 				}
-				if (adaptive && !finished && workers > 1) {
+				if ((moments && !finished && workers > 1) || (st.denoise && finished)) {
 					want_sq.push_back(i);
 					rects_sq.push_back(rects.back());
 					pixels_sq += t.width * t.height;
@@ -397,6 +398,10 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 } // namespace
 
 TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
+	if (settings.denoise_radius > 12 || settings.denoise_patch > 4) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_radius must be <= 12, denoise_patch <= 4");
+	if (!(settings.denoise_k > 0.0) || !std::isfinite(settings.denoise_k)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_k must be finite and > 0");
+	if (!(settings.denoise_alpha >= 0.0) || !std::isfinite(settings.denoise_alpha))
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_alpha must be finite and >= 0");
 	if (!(settings.adaptive_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_threshold > 0.0 && settings.samples_per_iteration == 0)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)");
@@ -432,10 +437,15 @@ std::vector<Vector3> TaskHandle::await() {
 	std::unique_lock<std::mutex> lock(shared_->m);
 	shared_->cv.wait(lock, [&] { return shared_->alive == 0; }); // the reference polls every 500 ms (:88-110)
 	if (!shared_->error.empty()) throw Error(RMD_ERR_HIP, shared_->error); // the reference would hang after a worker panic
+	std::vector<Tile> collected; // settings.denoise
 	while (!shared_->channel.empty()) {
 		Message m = std::move(shared_->channel.front());
 		shared_->channel.pop_front();
 		if (m.kind != Message::TileFinished) break; // :101-103
+		if (settings.denoise) {
+			collected.push_back(std::move(m.tile));
+			continue;
+		}
 		const Tile &t = m.tile;
 		for (size_t y = 0; y < t.height; y++)
 			for (size_t x = 0; x < t.width; x++) {
@@ -444,6 +454,48 @@ std::vector<Vector3> TaskHandle::await() {
 				out[x + t.left + (y + t.top) * cam.backbuffer_width] = s;
 			}
 	}
+	lock.unlock();
+	if (!collected.empty()) out = denoise_tiles(collected, settings, 0); // render_tiled's first GPU
+	return out;
+}
+
+std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device) {
+	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
+	std::vector<double> sums(W * H * 3, 0.0), sums_sq(W * H * 3, 0.0);
+	std::vector<rmd_tile_rect> rects;
+	std::vector<uint32_t> counts;
+	for (const Tile &t : tiles) {
+		if (t.data.size() != t.width * t.height || t.data_sq.size() != t.width * t.height)
+			throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_tiles: a tile without its sums and sums of squares");
+		for (size_t y = 0; y < t.height; y++)
+			for (size_t x = 0; x < t.width; x++)
+				for (int c = 0; c < 3; c++) {
+					const size_t at = (x + t.left + (y + t.top) * W) * 3 + c;
+					sums[at] = t.data[x + y * t.width][c], sums_sq[at] = t.data_sq[x + y * t.width][c];
+				}
+		rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+		counts.push_back((uint32_t)t.sample_count);
+	}
+	std::vector<Vector3> out(W * H);
+	rmd_context *ctx = nullptr;
+	double *dev[3] = {nullptr, nullptr, nullptr};
+	try {
+		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
+		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
+		check(rmd_framebuffer_upload(ctx, sums.data(), dev[0], sums.size()), ctx, "rmd_framebuffer_upload");
+		check(rmd_framebuffer_upload(ctx, sums_sq.data(), dev[1], sums_sq.size()), ctx, "rmd_framebuffer_upload");
+		check(rmd_denoise(ctx, dev[0], dev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), settings.denoise_radius,
+		                  settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, dev[2]),
+		      ctx, "rmd_denoise");
+		check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
+	} catch (...) {
+		for (double *d : dev)
+			if (d) rmd_framebuffer_free(ctx, d);
+		rmd_context_destroy(ctx);
+		throw;
+	}
+	for (double *d : dev) rmd_framebuffer_free(ctx, d);
+	rmd_context_destroy(ctx);
 	return out;
 }
 

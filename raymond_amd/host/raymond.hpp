@@ -128,6 +128,12 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// samples_per_iteration > 0; render_tiled throws raymond::Error otherwise, and for a negative threshold.
 	double adaptive_threshold = 0.0;
 	double adaptive_floor = 1e-3;
+	// Denoising (an extension; false = off): await() returns the assembled frame filtered by rmd_denoise (raymond_hip.h) with these parameters; the
+	// passes then render with second moments and TileFinished tiles carry them in `data_sq`.  render_tiled throws raymond::Error for values
+	// rmd_denoise refuses (radius <= 12, patch <= 4, k finite and > 0, alpha finite and >= 0).
+	bool denoise = false;
+	uint32_t denoise_radius = 10, denoise_patch = 3;
+	double denoise_k = 0.45, denoise_alpha = 1.0;
 };
 
 // core/src/tile.rs:13 `data: Vec<Vector3>` — the running sums of a tile, width * height of them, row-major.  Here a VIEW: the tiles of one
@@ -164,7 +170,7 @@ struct Tile { // core/src/tile.rs:7-14
 	TileData data; // running sums, width*height.  EMPTY while the tile waits in the queue with its sums resident on a GPU (`resident`)
 	int resident = -1; // the worker (GPU) whose device framebuffer holds the tile's sums; -1: `data` does (an extension: the reference's tiles live in RAM)
 	TileData data_sq;  // adaptive renders with several GPUs: the running sums of squares (rmd_render_tiles_moments), travelling through RAM with `data`
-	                   // while the tile waits in the queue; empty otherwise
+	                   // while the tile waits in the queue; denoised renders: also every TileFinished tile's; empty otherwise
 };
 struct Message { // src/trace.rs:62-66
 	enum Kind { TileFinished, TileProgressed } kind;
@@ -177,7 +183,8 @@ class TaskHandle {
 	using TileCallback = std::function<void(const Tile &)>;
 	Settings settings;
 	void set_callback(TileCallback cb) { callback_ = std::move(cb); }
-	// Blocks until every worker is done, then assembles W*H radiance values (tile sums / sample_count), row-major (:82-113)
+	// Blocks until every worker is done, then assembles W*H radiance values (tile sums / sample_count), row-major (:82-113).  settings.denoise: the
+	// collected tiles go through denoise_tiles on GPU 0 instead (none collected: the zero frame, as without it)
 	std::vector<Vector3> await();
 	std::optional<Message> poll();        // :115-117
 	void async_await();                   // :119-134: drains leading TileProgressed messages into the callback
@@ -197,6 +204,10 @@ class TaskHandle {
 
 // src/trace.rs:137-230
 TaskHandle render_tiled(const Scene &scene, const Settings &settings);
+
+// Extension (settings.denoise): the W*H denoised means, row-major — the tiles' sums (`data`), sums of squares (`data_sq`) and sample counts
+// assembled into one frame and filtered by rmd_denoise on GPU `device` with the settings' parameters.  A pixel that no tile covers has n = 0 (0 / 0).
+std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0);
 
 // Tile generation of render_tiled (:142-173): column-major, edge tiles clamped
 std::vector<rmd_tile_rect> generate_tiles(size_t width, size_t height, std::pair<size_t, size_t> tile_size);

@@ -60,6 +60,10 @@ SIGNATURES = {
         C.c_int32,
         [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, _P(abi.TileRect), C.c_uint32, _vp],
     ),
+    "rmd_denoise": (
+        C.c_int32,
+        [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _vp],
+    ),
     "rmd_context_synchronize": (C.c_int32, [_vp]),
     "rmd_render_tiles_host": (
         C.c_int32,

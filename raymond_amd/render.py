@@ -161,6 +161,31 @@ def tile_error(ctx, framebuffer, framebuffer_sq, sample_count, floor, tiles):
     return out[: len(tiles)]
 
 
+def denoise(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuffer, radius=10, patch_radius=3, k=0.45, alpha=1.0):
+    """rmd_denoise: `out_framebuffer` = the variance-guided non-local means of the frame whose sums are `framebuffer` and sums of squares
+    `framebuffer_sq`; rect i of `rects` (left, top, width, height) holds counts[i] samples per pixel.  The result holds means, not sums."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != len(rects):
+        raise ValueError("one sample count per rect")
+    ctx.check(ctx.L.rmd_denoise(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(rects),
+                                counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius), int(patch_radius), float(k), float(alpha),
+                                out_framebuffer.ptr))
+
+
+def denoise_arrays(ctx, sums, sums_sq, rects, counts, **params):
+    """denoise() for host arrays: (H, W, 3) sums and sums of squares in, the (H, W, 3) denoised means out."""
+    H, W = sums.shape[0], sums.shape[1]
+    bufs = [Framebuffer(ctx, W, H) for _ in range(3)]
+    try:
+        bufs[0].upload(sums)
+        bufs[1].upload(sums_sq)
+        denoise(ctx, bufs[0], bufs[1], rects, counts, bufs[2], **params)
+        return bufs[2].download()
+    finally:
+        for b in bufs:
+            b.close()
+
+
 def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
     """TaskHandle::await's divide + cli_old's tone-map/gamma/u8 cast (cli_old/src/main.rs:161-181) -> (H, W, 3) uint8."""
     out = np.empty((framebuffer.height, framebuffer.width, 3), dtype=np.uint8)
@@ -173,11 +198,12 @@ def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
 
 # ---------------------------------------------------------------- the reference-shaped API
 class Tile:  # core/src/tile.rs:7-14
-    def __init__(self, left, top, width, height, sample_count, data, error=None):
+    def __init__(self, left, top, width, height, sample_count, data, error=None, data_sq=None):
         self.left, self.top, self.width, self.height = left, top, width, height
         self.sample_count = sample_count
         self.data = data  # (height, width, 3) running sums, like Tile.data
         self.error = error  # adaptive renders (an extension): the tile's rmd_tile_error at sample_count when it was checked, else None
+        self.data_sq = data_sq  # denoised renders (an extension): the finished tile's running sums of squares, like data; else None
 
 
 class Message:  # src/trace.rs:62-66
@@ -194,10 +220,11 @@ class Message:  # src/trace.rs:62-66
 
 
 class TaskHandle:  # src/trace.rs:70-135
-    def __init__(self, settings, messages):
+    def __init__(self, settings, messages, device=0):
         self.settings = settings
         self._messages = list(messages)
         self.callback = None
+        self.device = device  # settings.denoise: the GPU await_() denoises on (render_tiled's first)
 
     def set_callback(self, callback):
         self.callback = callback
@@ -212,15 +239,33 @@ class TaskHandle:  # src/trace.rs:70-135
                 self.callback(m.tile)
 
     def await_(self):
-        """`await`: W*H radiance values, row-major, each the tile sum divided by its sample count (:93-99)."""
+        """`await`: W*H radiance values, row-major, each the tile sum divided by its sample count (:93-99).
+
+        With settings.denoise (an extension): the finished tiles' sums, sums of squares and sample counts are assembled and the frame comes
+        back through rmd_denoise on `device` — means as well; a pixel that no finished tile covers has n = 0 and comes back as 0 / 0."""
         cam = self.settings.camera_settings
-        out = np.zeros((cam.backbuffer_height, cam.backbuffer_width, 3), dtype=np.float64)
+        shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
+        out = np.zeros(shape, dtype=np.float64)
+        denoised = self.settings.denoise
+        if denoised:
+            sums, sums_sq, rects, counts = np.zeros(shape), np.zeros(shape), [], []
         while self._messages:
             m = self._messages.pop(0)
             if m.kind != "TileFinished":
                 break  # the reference stops collecting at the first non-TileFinished message (:101-103)
             t = m.tile
-            out[t.top : t.top + t.height, t.left : t.left + t.width] = t.data / float(t.sample_count)
+            if denoised:
+                sums[t.top : t.top + t.height, t.left : t.left + t.width] = t.data
+                sums_sq[t.top : t.top + t.height, t.left : t.left + t.width] = t.data_sq
+                rects.append((t.left, t.top, t.width, t.height))
+                counts.append(t.sample_count)
+            else:
+                out[t.top : t.top + t.height, t.left : t.left + t.width] = t.data / float(t.sample_count)
+        if denoised:
+            st = self.settings
+            with Context(self.device) as ctx:
+                out = denoise_arrays(ctx, sums, sums_sq, rects, counts, radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k,
+                                     alpha=st.denoise_alpha)
         return out
 
 
@@ -229,16 +274,21 @@ def render_tiled(scene, settings, devices=(0,)):
 
     Adaptive (settings.adaptive_threshold > 0, an extension): every pass renders the tiles that are still live with their second moments, and
     after each pass that leaves them below sample_count a tile whose rmd_tile_error is at most the threshold is sent as TileFinished at its
-    current sample count and takes no further passes; the others are sent as TileProgressed and go on."""
+    current sample count and takes no further passes; the others are sent as TileProgressed and go on.
+
+    Denoised (settings.denoise, an extension): the passes render with second moments, every TileFinished tile carries them as `data_sq`, and
+    TaskHandle.await_() denoises the assembled frame on the first of `devices`."""
     settings.check_adaptive()
+    settings.check_denoise()
     adaptive = settings.adaptive_threshold > 0.0
+    moments = adaptive or settings.denoise
     cam = settings.camera_settings
     W, H = cam.backbuffer_width, cam.backbuffer_height
     tiles = generate_tiles(W, H, settings.tile_size)
     workers = []
     for d in devices:
         ctx = Context(d)
-        workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H), Framebuffer(ctx, W, H) if adaptive else None))
+        workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H), Framebuffer(ctx, W, H) if moments else None))
     shares = [tiles[i :: len(workers)] for i in range(len(workers))]  # adaptive: the tiles of a share that are still live
     step = settings.samples_per_iteration if settings.samples_per_iteration else settings.sample_count
     messages = []
@@ -258,10 +308,13 @@ def render_tiled(scene, settings, devices=(0,)):
                     share = shares[i]
                     errors = tile_error(ctx, fb, fb_sq, done, settings.adaptive_floor, share) if adaptive and share else [None] * len(share)
                     img = fb.download()
+                    img_sq = fb_sq.download() if settings.denoise else None
                     live = []
                     for (l, t, w, h), e in zip(share, errors):
                         tile = Tile(l, t, w, h, done, img[t : t + h, l : l + w].copy(), None if e is None else float(e))
                         if adaptive and e <= settings.adaptive_threshold:
+                            if img_sq is not None:
+                                tile.data_sq = img_sq[t : t + h, l : l + w].copy()
                             finished.append(Message.TileFinished(tile))  # converged: finished at the samples it has
                         else:
                             messages.append(Message.TileProgressed(tile))
@@ -269,8 +322,10 @@ def render_tiled(scene, settings, devices=(0,)):
                     shares[i] = live
         for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
             img = fb.download()
+            img_sq = fb_sq.download() if settings.denoise else None
             for (l, t, w, h) in share:
-                finished.append(Message.TileFinished(Tile(l, t, w, h, settings.sample_count, img[t : t + h, l : l + w].copy())))
+                sq = None if img_sq is None else img_sq[t : t + h, l : l + w].copy()
+                finished.append(Message.TileFinished(Tile(l, t, w, h, settings.sample_count, img[t : t + h, l : l + w].copy(), data_sq=sq)))
         messages = messages + finished  # progress snapshots first, then the finished tiles
     finally:
         for ctx, ds, fb, fb_sq in workers:
@@ -279,5 +334,5 @@ def render_tiled(scene, settings, devices=(0,)):
                 fb_sq.close()
             ds.close()
             ctx.close()
-    handle = TaskHandle(settings, messages)
+    handle = TaskHandle(settings, messages, devices[0])
     return handle

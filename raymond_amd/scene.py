@@ -244,7 +244,7 @@ class Settings:
 
     def __init__(self, camera_settings, sample_count, tile_size=(32, 32), bounce_limit=5, samples_per_iteration=0,
                  worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
-                 adaptive_floor=1e-3):
+                 adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -265,6 +265,14 @@ class Settings:
         self.adaptive_threshold = float(adaptive_threshold)
         self.adaptive_floor = float(adaptive_floor)
         self.check_adaptive()
+        # Denoising (an extension; False = off): TaskHandle.await_() returns the assembled frame filtered by rmd_denoise (raymond_hip.h) with
+        # these parameters; render_tiled then renders with second moments.
+        self.denoise = bool(denoise)
+        self.denoise_radius = denoise_radius
+        self.denoise_patch = denoise_patch
+        self.denoise_k = float(denoise_k)
+        self.denoise_alpha = float(denoise_alpha)
+        self.check_denoise()
 
     def check_adaptive(self):
         """Raises ValueError for adaptive settings render_tiled cannot follow."""
@@ -274,6 +282,17 @@ class Settings:
             raise ValueError("adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)")
         if not (self.adaptive_floor > 0.0 and np.isfinite(self.adaptive_floor)):
             raise ValueError("adaptive_floor must be finite and > 0")
+
+    def check_denoise(self):
+        """Raises ValueError for denoise settings rmd_denoise refuses (checked whether or not denoise is on)."""
+        for name, hi in (("denoise_radius", 12), ("denoise_patch", 4)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
+                raise ValueError("%s must be an integer in [0, %d]" % (name, hi))
+        if not (self.denoise_k > 0.0 and np.isfinite(self.denoise_k)):
+            raise ValueError("denoise_k must be finite and > 0")
+        if not (self.denoise_alpha >= 0.0 and np.isfinite(self.denoise_alpha)):
+            raise ValueError("denoise_alpha must be finite and >= 0")
 
     def pod(self, sample_begin=0, sample_count=None):
         s = abi.Settings()

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""How much rmd_denoise brings a preview frame towards the converged one (one GPU):
+
+    python tools/denoise_quality.py [--out profiles/r08_denoise/denoise_quality.json] [--ref-spp 2048]
+
+For ReflectiveSpheres and the small GoldDragon stand-in (n = 24) at 256x144: frames of 16, 64 and 256 spp with moments are denoised, and the
+RMSE of the noisy and of the denoised frame against a --ref-spp frame of another seed is reported with its ratio, first at the default
+parameters (r 10, f 3, k 0.45, alpha 1), then over a small sweep of k, alpha, r and f at 16 and 64 spp.  The converged-frame check denoises a
+--ref-spp frame and compares its distance to a second --ref-spp frame (a third seed) with their own distance.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from raymond_amd import render, scenes  # noqa: E402
+from raymond_amd.scene import Settings, generate_tiles  # noqa: E402
+
+DEFAULT = dict(radius=10, patch_radius=3, k=0.45, alpha=1.0)
+SWEEP = [dict(DEFAULT, k=k) for k in (0.3, 0.6, 0.8)] + [dict(DEFAULT, alpha=a) for a in (0.5, 2.0)] + \
+        [dict(DEFAULT, radius=r, patch_radius=f) for r, f in ((5, 2), (12, 4), (10, 1))]
+
+
+def moments(ctx, ds, W, H, spp, seed):
+    st = Settings(scenes.camera(W, H), sample_count=spp, bounce_limit=5, seed=seed)
+    fb, fb_sq = render.Framebuffer(ctx, W, H), render.Framebuffer(ctx, W, H)
+    try:
+        render.render_tiles(ctx, ds, st.camera_settings, st, generate_tiles(W, H, (32, 32)), fb, 0, spp, framebuffer_sq=fb_sq)
+        return fb.download(), fb_sq.download()
+    finally:
+        fb.close(), fb_sq.close()
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a - b) ** 2)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--ref-spp", type=int, default=2048)
+    a = ap.parse_args()
+    W, H = 256, 144
+    out = {"width": W, "height": H, "ref_spp": a.ref_spp, "default": DEFAULT, "scenes": {}}
+    with render.Context(0) as ctx:
+        for name, scene in (("reflective_spheres", scenes.reflective_spheres()), ("gold_dragon_standin_n24", scenes.gold_dragon_standin(n=24))):
+            ds = render.DeviceScene(ctx, scene)
+            try:
+                S_ref, Q_ref = moments(ctx, ds, W, H, a.ref_spp, seed=0x1234567)
+                S_ref2, _ = moments(ctx, ds, W, H, a.ref_spp, seed=0x7654321)
+                ref, ref2 = S_ref / a.ref_spp, S_ref2 / a.ref_spp
+                rec = {"levels": [], "sweep": []}
+                for spp in (16, 64, 256):
+                    S, Q = moments(ctx, ds, W, H, spp, seed=scenes.SEED)
+                    noisy = rmse(S / spp, ref)
+                    den = rmse(render.denoise_arrays(ctx, S, Q, [(0, 0, W, H)], [spp], **DEFAULT), ref)
+                    rec["levels"].append({"spp": spp, "rmse_noisy": noisy, "rmse_denoised": den, "ratio": den / noisy})
+                    if spp in (16, 64):
+                        for p in SWEEP:
+                            d = rmse(render.denoise_arrays(ctx, S, Q, [(0, 0, W, H)], [spp], **p), ref)
+                            rec["sweep"].append({"spp": spp, "params": p, "rmse_denoised": d, "ratio": d / noisy})
+                own = rmse(ref, ref2)
+                den = rmse(render.denoise_arrays(ctx, S_ref, Q_ref, [(0, 0, W, H)], [a.ref_spp], **DEFAULT), ref2)
+                rec["converged"] = {"rmse_between_refs": own, "rmse_denoised_to_second": den, "ratio": den / own}
+                out["scenes"][name] = rec
+                print(name, json.dumps(rec["levels"]), json.dumps(rec["converged"]), flush=True)
+            finally:
+                ds.close()
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
