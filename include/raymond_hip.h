@@ -61,7 +61,7 @@ enum {
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
-	                                 rmd_denoise) */
+	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -362,6 +362,59 @@ rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const doubl
 rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
                        const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
                        uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev);
+/*
+ * FIRST-HIT FEATURE BUFFERS (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes; a caller finds the functions by their
+ * symbols).  A feature buffer is W*H*RMD_FEATURE_CHANNELS doubles, pixel-interleaved: feat[(x + y*W)*7 + j], j = 0..2 the normal's x, y, z,
+ * 3..5 the albedo's r, g, b, 6 the depth.  rmd_feature_buffer_alloc allocates one, zeroed; rmd_framebuffer_free / _zero / _download / _upload
+ * take a pointer and a count of doubles and serve feature buffers as they are.
+ * rmd_render_features: for every pixel i of every rect and s = sample_begin .. sample_begin + sample_count - 1, in that order, the PRIMARY RAY
+ * exactly as rmd_render_tiles takes it for (pixel, s) — Philox block 0 for the jitter, and with RMD_RENDER_DOF (aperture_radius > 0) the lens'
+ * rounds after it — is intersected with the scene once (Scene::intersect).  The sample's feature vector phi_s:
+ *     hit on object o at distance t (frag = ro + rd*t):
+ *         normal  plane: o.normal as stored (not normalised); sphere: normalize(frag - origin); grid: the interpolated normal of the hit triangle
+ *                 at frag (it may be NaN, and then stays NaN) — the functions the shading calls, for every material kind, Emission included
+ *         albedo  o.material.color (for Emission: the emitted radiance — a light's outline is an edge too)
+ *         depth   t as Scene::intersect returns it
+ *     miss, or a sample for which the thin lens yields no ray (the render's sample is zero there): seven zeros
+ *     feat   [i*7+j] += phi_s.j
+ *     feat_sq[i*7+j] += phi_s.j * phi_s.j      the product rounded, then added (no fused multiply-add)
+ * — the contract of rmd_render_tiles_moments: calls over [0, k) and [k, n) give the bits of one call over [0, n), and the bits do not depend on
+ * how the rects cut the frame.  bounce_limit and the black-path flags are ignored (RMD_RENDER_END_BLACK_PATHS and _TRACE_BLACK_PATHS together
+ * are still refused).  feat_sq_dev = NULL skips the squares.  feat_dev NULL, feat_sq_dev == feat_dev, tiles NULL with n_tiles > 0, a rect outside
+ * the frame or two rects that overlap are RMD_ERR_INVALID_ARGUMENT before the device is touched.  The pass does not change what
+ * rmd_last_launch_info and rmd_last_kernel_ms report.  rmd_render_features waits for the launch like rmd_render_tiles and, like
+ * every call that waits, returns RMD_ERR_DEVICE_FAULT if a render enqueued before it on the context reported one; the pass itself raises no
+ * fault code: its own loop runs sample_count times, and the grid walk it calls is bounded by the rays' exit counters and has nothing to
+ * report (the render loops' reports watch what a wave does BETWEEN walks, which this kernel does not have).  The _async form only enqueues.
+ */
+#define RMD_FEATURE_CHANNELS 7u /* 0..2 normal xyz, 3..5 albedo rgb, 6 depth */
+rmd_status rmd_feature_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, double **out_dev); /* zeroed W*H*7 */
+rmd_status rmd_render_features(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                               const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev);
+rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                     const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev);
+/*
+ * rmd_denoise with a FEATURE WEIGHT (Rousselle, Manzi and Zwicker, "Robust Denoising using Feature and Color Information", 2013; an addition
+ * within ABI 6).  Everything rmd_denoise defines stays word for word (validity, D(p, q), w_c = exp(-max(0, D)), clamping, sum orders, the output
+ * for a pixel that is not valid).  Added, with F = feat_dev, G = feat_sq_dev (feature buffers as rmd_render_features writes them) and n_i the
+ * pixel's count as before, for j = 0..6:
+ *     f_ij = F_ij / n_i;   g_ij = max(0, (G_ij - F_ij*f_ij) / (n_i - 1)) / n_i          (as u and v)
+ *     pixel i is FEATURE-VALID if it is valid and its fourteen F and G values are finite
+ *     s_ij = 1 for j = 0..5;   s_i6 = f_i6 * f_i6                  (depth is judged relative to the pixel's own depth)
+ *     Phi_j(p, q) = ((f_pj - f_qj)^2 - (g_pj + min(g_pj, g_qj))) / (eps + k_f^2 * max(tau * s_pj, g_pj)),   eps = 1e-10, k_f^2 = k_f*k_f
+ *     D_f = 0;  for j = 0..6:  if Phi_j > D_f then D_f = Phi_j     (a NaN Phi_j is skipped by the comparison)
+ *     w_f = exp(-D_f)
+ *     w(p, q) = w_f if p and q are both feature-valid and w_f < w_c, else w_c
+ * and out is the w-weighted mean as before.  So w(p, p) = 1, a pixel whose mesh normal is NaN is filtered by colour alone, a miss never mixes
+ * with a hit (Phi_6 = t^2 / eps), and two misses do.  The gradient term of the 2013 paper and its second filtering pass are left out on
+ * purpose.  feat_dev = feat_sq_dev = NULL is exactly rmd_denoise (k_f and tau are then not read), and rmd_denoise is that call.  Beyond
+ * rmd_denoise's rules: one of the two NULL and the other not, k_f or tau not finite or not > 0, the two W*H*7-double feature ranges overlapping
+ * each other or out_dev's range: RMD_ERR_INVALID_ARGUMENT before the device is touched.  Values a caller may start from: k_f 1.0, tau 1e-2 (the
+ * best of the sweep in DESIGN.md section 12; the paper's 0.6 and 1e-3 filter less and measured worse on the two test scenes).  Synchronous, like rmd_denoise.
+ */
+rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                              uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                              uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev);
 /* Host-buffer convenience for a caller that keeps Tile.data in RAM, as the
  * reference does: upload accum, render, download (PCIe-inclusive). */
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera,

@@ -70,6 +70,15 @@ extern "C" {
     // an addition within ABI 6 (found by its symbol): the variance-guided non-local means of a frame from its sums and sums of squares
     fn rmd_denoise(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                    rect_sample_counts: *const u32, n_rects: u32, radius: u32, patch_radius: u32, k: f64, alpha: f64, out_dev: *mut f64) -> i32;
+    // additions within ABI 6 (found by their symbols): first-hit feature buffers (W*H*7 f64: normal xyz, albedo rgb, depth) and the filter guided by them
+    fn rmd_feature_buffer_alloc(ctx: *mut rmd_context, width: u32, height: u32, out_dev: *mut *mut f64) -> i32;
+    fn rmd_render_features(ctx: *mut rmd_context, scene: *const rmd_scene, camera: *const rmd_camera, settings: *const rmd_settings,
+                           tiles: *const rmd_tile_rect, n_tiles: u32, feat_dev: *mut f64, feat_sq_dev: *mut f64) -> i32;
+    fn rmd_render_features_async(ctx: *mut rmd_context, scene: *const rmd_scene, camera: *const rmd_camera, settings: *const rmd_settings,
+                                 tiles: *const rmd_tile_rect, n_tiles: u32, feat_dev: *mut f64, feat_sq_dev: *mut f64) -> i32;
+    fn rmd_denoise_guided(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
+                          width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, radius: u32,
+                          patch_radius: u32, k: f64, alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64) -> i32;
 }
 
 fn check(ctx: *const rmd_context, status: i32) {

@@ -967,26 +967,29 @@ rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const doubl
 	return s;
 }
 
-static rmd_status denoise_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
-                               const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t patch_radius,
-                               double k, double alpha, double *out_dev, void *&d) {
+static rmd_status denoise_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                               uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                               uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, void *&d) {
 	if (rmd_status s = bind(ctx)) return s;
-	// device scratch: [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each]
+	// device scratch: [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each, padded to 16 bytes]
+	// [guided: the planar per-pixel f and g, 14 planes of W*H doubles]
 	const size_t img_bytes = ((size_t)width * height * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
-	RMD_HIP(ctx, hipMalloc(&d, img_bytes + rect_bytes + count_bytes));
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = ((size_t)n_rects * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t plane_bytes = feat_dev ? (size_t)width * height * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
+	RMD_HIP(ctx, hipMalloc(&d, img_bytes + rect_bytes + count_bytes + plane_bytes));
 	uint32_t *d_img = static_cast<uint32_t *>(d);
 	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(static_cast<unsigned char *>(d) + img_bytes);
 	uint32_t *d_counts = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d) + img_bytes + rect_bytes);
+	double *d_planes = feat_dev ? reinterpret_cast<double *>(static_cast<unsigned char *>(d) + img_bytes + rect_bytes + count_bytes) : nullptr;
 	if (n_rects != 0) {
 		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, (size_t)n_rects * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
 	}
 	uint64_t largest = 0; // pixels of the largest rect: the count image gives each rect a column of 256-thread workgroups that covers it, up to 1,024
 	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
 	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise(ctx->stream, accum_dev, accum_sq_dev, d_rects, d_counts, n_rects, columns, width, height, radius, patch_radius, k, alpha,
-	                                 d_img, out_dev));
+	RMD_HIP(ctx, rmd::launch_denoise_guided(ctx->stream, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, d_rects, d_counts, n_rects, columns, width, height, radius,
+	                                        patch_radius, k, alpha, k_f, tau, d_img, d_planes, out_dev));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
 }
@@ -994,10 +997,11 @@ static rmd_status denoise_impl(rmd_context *ctx, const double *accum_dev, const 
 // Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
 // start before it ends.
 static bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height, const char **why) {
+	// (*why: the rule that was broken; the caller puts its own name in front)
 	std::vector<uint32_t> order;
 	for (uint32_t i = 0; i < n_rects; i++) {
 		const rmd_tile_rect &r = rects[i];
-		if ((uint64_t)r.left + r.width > width || (uint64_t)r.top + r.height > height) return *why = "rmd_denoise: tile rectangle outside the framebuffer", false;
+		if ((uint64_t)r.left + r.width > width || (uint64_t)r.top + r.height > height) return *why = "tile rectangle outside the framebuffer", false;
 		if (r.width != 0 && r.height != 0) order.push_back(i);
 	}
 	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rects[a].left < rects[b].left; });
@@ -1005,36 +1009,109 @@ static bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint3
 		const rmd_tile_rect &a = rects[order[i]];
 		for (size_t j = i + 1; j < order.size() && rects[order[j]].left < (uint64_t)a.left + a.width; j++) {
 			const rmd_tile_rect &b = rects[order[j]];
-			if (b.top < (uint64_t)a.top + a.height && a.top < (uint64_t)b.top + b.height) return *why = "rmd_denoise: tile rectangles overlap", false;
+			if (b.top < (uint64_t)a.top + a.height && a.top < (uint64_t)b.top + b.height) return *why = "tile rectangles overlap", false;
 		}
 	}
 	return true;
 }
 
-rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                       const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha,
-                       double *out_dev) {
+// rmd_denoise and rmd_denoise_guided: one argument check, one launch path (`what`: the entry point's name, for the messages)
+static rmd_status denoise_checked(const char *what, rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev,
+                                  const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts,
+                                  uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev) {
+	const std::string name = std::string(what) + ": ";
 	if (!accum_dev || !accum_sq_dev || !out_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: bad argument");
-	{ // no two of the three W*H*3-double ranges overlap
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
+	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
+	{ // no two of the three W*H*3-double ranges overlap; nor do the two W*H*7-double feature ranges, each other or out_dev's
 		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		const unsigned __int128 s = (uintptr_t)accum_dev, q = (uintptr_t)accum_sq_dev, o = (uintptr_t)out_dev;
-		auto overlap = [&](unsigned __int128 a, unsigned __int128 b) { return a < b + bytes && b < a + bytes; };
-		if (overlap(s, q) || overlap(s, o) || overlap(q, o))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: accum_dev, accum_sq_dev and out_dev must not alias");
+		const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
+		const unsigned __int128 s = (uintptr_t)accum_dev, q = (uintptr_t)accum_sq_dev, o = (uintptr_t)out_dev, f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
+		auto overlap = [&](unsigned __int128 a, unsigned __int128 na, unsigned __int128 b, unsigned __int128 nb) { return a < b + nb && b < a + na; };
+		if (overlap(s, bytes, q, bytes) || overlap(s, bytes, o, bytes) || overlap(q, bytes, o, bytes))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "accum_dev, accum_sq_dev and out_dev must not alias");
+		if (feat_dev && (overlap(f, fbytes, g, fbytes) || overlap(f, fbytes, o, bytes) || overlap(g, fbytes, o, bytes)))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev, feat_sq_dev and out_dev must not alias");
 	}
-	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: radius must be <= 12");
-	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: patch_radius must be <= 4");
-	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: k must be finite and > 0");
-	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise: alpha must be finite and >= 0");
+	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
+	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
+	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
+	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
+	if (feat_dev) {
+		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
+		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
+	}
 	void *d = nullptr; // the device scratch: freed here whichever way the body leaves
-	const rmd_status s = rmd::guarded(ctx, "rmd_denoise", [&] {
+	const rmd_status s = rmd::guarded(ctx, what, [&] {
 		const char *why = nullptr;
-		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, why);
-		return denoise_impl(ctx, accum_dev, accum_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k, alpha, out_dev, d);
+		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
+		return denoise_impl(ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k, alpha, k_f,
+		                    tau, out_dev, d);
 	});
 	if (d) (void)hipFree(d);
 	return s;
+}
+
+rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                       const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha,
+                       double *out_dev) {
+	return denoise_checked("rmd_denoise", ctx, accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k,
+	                       alpha, 0.0, 0.0, out_dev);
+}
+
+rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                              uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                              uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev) {
+	return denoise_checked("rmd_denoise_guided", ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius,
+	                       patch_radius, k, alpha, k_f, tau, out_dev);
+}
+
+// ---------------------------------------------------------------- first-hit feature buffers (features.hip)
+rmd_status rmd_feature_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, double **out_dev) {
+	if (rmd_status s = bind(ctx)) return s;
+	if (!out_dev || width == 0 || height == 0) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_feature_buffer_alloc: bad argument");
+	const size_t bytes = (size_t)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
+	RMD_HIP(ctx, hipMalloc((void **)out_dev, bytes));
+	RMD_HIP(ctx, hipMemsetAsync(*out_dev, 0, bytes, ctx->stream));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return RMD_OK;
+}
+
+static rmd_status render_features_impl(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                       const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev) {
+	rmd_settings st = *settings;
+	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
+	{
+		const char *why = nullptr;
+		if (!denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string("rmd_render_features: ") + why);
+	}
+	if (rmd_status s = bind(ctx)) return s;
+	if (rmd_status s = check_render_args(ctx, scene, camera, &st)) return s;
+	if (rmd_status s = prepare_wave_tiles(ctx, camera, tiles, n_tiles)) return s;
+	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, &st);
+	P.n_work = ctx->n_wave_tiles;
+	// (neither the context's events nor its launch record are touched: rmd_last_kernel_ms / rmd_last_launch_info keep describing the last render)
+	RMD_HIP(ctx, rmd::launch_features(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->d_wave_tiles, feat_dev, feat_sq_dev));
+	return RMD_OK;
+}
+
+rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                     const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev) {
+	if (!scene || !camera || !settings) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_features: null scene/camera/settings");
+	if (!feat_dev || (n_tiles && !tiles)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_features: null tiles/feat pointer");
+	if (feat_sq_dev != nullptr) { // the two W*H*7-double ranges must not overlap
+		const unsigned __int128 bytes = (unsigned __int128)camera->backbuffer_width * camera->backbuffer_height * RMD_FEATURE_CHANNELS * sizeof(double);
+		const unsigned __int128 f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
+		if (f < g + bytes && g < f + bytes) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_features: feat_sq_dev must not alias feat_dev");
+	}
+	return rmd::guarded(ctx, "rmd_render_features", [&] { return render_features_impl(ctx, scene, camera, settings, tiles, n_tiles, feat_dev, feat_sq_dev); });
+}
+
+rmd_status rmd_render_features(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                               const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev) {
+	if (rmd_status s = rmd_render_features_async(ctx, scene, camera, settings, tiles, n_tiles, feat_dev, feat_sq_dev)) return s;
+	return rmd_context_synchronize(ctx);
 }
 
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,

@@ -11,6 +11,11 @@
 //      patch's 2f+1 columns, then each thread's column sum over 2f+1 rows: D(p, p + d) without recomputing a patch per pixel.  Each window
 //      is summed directly: a running sum that subtracts would lose the small terms beside a (du)^2 / eps one;
 //   3. w = exp(-max(0, D)) and w * u_q are accumulated in registers.
+// GUIDED (rmd_denoise_guided; denoise_kernel<TW, DenoiseGuide>, instantiations of their own so that the unguided ones are compiled exactly as
+// without the feature): step 3 also makes the feature weight w_f of the pixel pair and takes min(w, w_f).  p's seven f, g and denominators live in registers;
+// q's f and g are read per offset straight from planar images in global memory (feature_planes_kernel writes them: 14 planes of W*H doubles, a
+// pixel that is not feature-valid keeps a NaN in its f of channel 0) — neighbouring lanes read neighbouring doubles and consecutive offsets shift
+// by one pixel, so these are cache hits; f64 planes for the apron do not fit in LDS beside the colour planes.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -34,9 +39,50 @@ __device__ inline double denoise_term(double ua, double ub, double va, double vb
 	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
 }
 
-template <int TW>
+// Per pixel: f_j = F_j / n, g_j = max(0, (G_j - F_j*f_j) / (n - 1)) / n (as u and v), into planes j and 7 + j of `planes` (N = W*H doubles each).
+// A pixel that is not FEATURE-VALID (valid, and its fourteen F and G values finite) gets a NaN in plane 0.
+__global__ __launch_bounds__(256) void feature_planes_kernel(const double *__restrict__ S, const double *__restrict__ Q, const double *__restrict__ F,
+                                                             const double *__restrict__ G, const uint32_t *__restrict__ n_img, size_t N,
+                                                             double *__restrict__ planes) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const uint32_t n = n_img[i];
+	const double nd = (double)n;
+	bool valid = n >= 2u;
+#pragma unroll
+	for (int c = 0; c < 3; c++) valid = valid && __builtin_fabs(S[i * 3 + c]) < __builtin_inf() && __builtin_fabs(Q[i * 3 + c]) < __builtin_inf();
+	double fv[kDenoiseFeat], gv[kDenoiseFeat];
+#pragma unroll
+	for (int j = 0; j < kDenoiseFeat; j++) {
+		const double s = F[i * kDenoiseFeat + j], q = G[i * kDenoiseFeat + j];
+		valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
+		fv[j] = s / nd;
+		double t = (q - s * fv[j]) / (nd - 1.0);
+		if (t < 0.0) t = 0.0;
+		gv[j] = t / nd;
+	}
+#pragma unroll
+	for (int j = 0; j < kDenoiseFeat; j++) planes[(size_t)j * N + i] = (j == 0 && !valid) ? __builtin_nan("") : fv[j], planes[(size_t)(kDenoiseFeat + j) * N + i] = gv[j];
+}
+
+// the guided kernel's extra arguments: the planar f and g images, k_f^2 and tau
+struct DenoiseGuide {
+	const double *planes;
+	double kf2, tau;
+};
+// GUIDED is the presence of a DenoiseGuide argument: denoise_kernel<TW> (no such argument) keeps the signature and the code it had before the
+// guided filter existed, denoise_kernel<TW, DenoiseGuide> is the guided instantiation.
+template <int TW, class... G>
 __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restrict__ S, const double *__restrict__ Q, const uint32_t *__restrict__ n_img,
-                                                          uint32_t W, uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ out) {
+                                                          uint32_t W, uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ out, G... guide) {
+	constexpr bool GUIDED = sizeof...(G) != 0;
+	static_assert(sizeof...(G) <= 1, "at most one DenoiseGuide");
+	[[maybe_unused]] const double *planes = nullptr;
+	[[maybe_unused]] double kf2 = 0.0, tau = 0.0;
+	if constexpr (GUIDED) {
+		const DenoiseGuide gd = (guide, ...);
+		planes = gd.planes, kf2 = gd.kf2, tau = gd.tau;
+	}
 	extern __shared__ double lds[];
 	constexpr int TH = (int)kDenoiseTile, NT = TW * TH;
 	const int R = r + f, AW = TW + 2 * R, AA = AW * (TH + 2 * R), PW = TW + 2 * f, PP = PW * (TH + 2 * f);
@@ -92,6 +138,20 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 	const int dx_lo = (int)max((int64_t)-r, -gx), dx_hi = (int)min((int64_t)r, (int64_t)W - 1 - gx);
 	const int dy_lo = (int)max((int64_t)-r, -gy), dy_hi = (int)min((int64_t)r, (int64_t)H - 1 - gy);
 	double acc0 = -0.0, acc1 = -0.0, acc2 = -0.0, wsum = -0.0; // -0.0 + x == x for every x, so r = 0 gives S / n bit for bit
+	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .): eps + k_f^2 * max(tau * s_pj, g_pj), s = 1 but for the depth
+	[[maybe_unused]] double fp[kDenoiseFeat], gp[kDenoiseFeat], den[kDenoiseFeat];
+	[[maybe_unused]] bool p_fok = false;
+	[[maybe_unused]] const size_t N = (size_t)W * H;
+	[[maybe_unused]] const size_t pixp = inside ? (size_t)gx + (size_t)gy * W : 0;
+	if constexpr (GUIDED) {
+#pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) {
+			fp[j] = planes[(size_t)j * N + pixp], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pixp];
+			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
+			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+		}
+		p_fok = p_ok && fp[0] == fp[0];
+	}
 
 	for (int dy = -r; dy <= r; dy++) {
 		for (int dx = -r; dx <= r; dx++) {
@@ -132,7 +192,25 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 					uint32_t cnt = Hc[py * TW + px];
 					for (int o = 1; o <= 2 * f; o++) ds = ds + Hs[(py + o) * TW + px], cnt += Hc[(py + o) * TW + px];
 					const double D = ds / (3.0 * (double)cnt);
-					const double w = exp(-(D > 0.0 ? D : 0.0));
+					double w = exp(-(D > 0.0 ? D : 0.0));
+					if constexpr (GUIDED) {
+						if (p_fok) {
+							const size_t pixq = (size_t)((int64_t)pixp + (int64_t)dy * (int64_t)W + dx); // (inside the frame: dx, dy are within the lo / hi bounds)
+							const double fq0 = planes[pixq];
+							if (fq0 == fq0) { // q is feature-valid too
+								double Df = 0.0;
+#pragma unroll
+								for (int j = 0; j < kDenoiseFeat; j++) {
+									const double fq = j == 0 ? fq0 : planes[(size_t)j * N + pixq], gq = planes[(size_t)(kDenoiseFeat + j) * N + pixq];
+									const double df = fp[j] - fq;
+									const double phi = (df * df - (gp[j] + __builtin_fmin(gp[j], gq))) / den[j];
+									if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
+								}
+								const double wf = exp(-Df);
+								if (wf < w) w = wf;
+							}
+						}
+					}
 					acc0 = acc0 + w * uq0, acc1 = acc1 + w * U[AA + iq], acc2 = acc2 + w * U[2 * AA + iq];
 					wsum = wsum + w;
 				}
@@ -157,24 +235,41 @@ size_t denoise_lds_bytes(uint32_t tile_width, uint32_t radius, uint32_t patch_ra
 }
 uint32_t denoise_tile_width(uint32_t radius, uint32_t patch_radius) { return denoise_lds_bytes(32u, radius, patch_radius) <= kLdsBudgetBytes ? 32u : 24u; }
 
-hipError_t launch_denoise(hipStream_t stream, const double *accum, const double *accum_sq, const rmd_tile_rect *rects, const uint32_t *rect_counts,
-                          uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k,
-                          double alpha, uint32_t *n_img, double *out) {
+hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
+                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
+                                 uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
+                                 double *out) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+	const bool guided = feat != nullptr;
+	if (guided && (feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
 	hipError_t e = hipMemsetAsync(n_img, 0, (size_t)W * H * sizeof(uint32_t), stream);
 	if (e != hipSuccess) return e;
 	if (n_rects) { // a column of workgroups per rect, enough for the largest (a full-frame rect is one rect)
 		hipLaunchKernelGGL(count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, rect_counts, W, n_img);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
+	if (guided) {
+		const size_t N = (size_t)W * H;
+		hipLaunchKernelGGL(feature_planes_kernel, dim3((uint32_t)((N + 255u) / 256u)), dim3(256), 0, stream, accum, accum_sq, feat, feat_sq, n_img, N, feat_planes);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits: 145,152 B at r = 12, f = 4)
-	const void *fn = tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32>) : reinterpret_cast<const void *>(&denoise_kernel<24>);
+	const void *fn = guided ? (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32, DenoiseGuide>) : reinterpret_cast<const void *>(&denoise_kernel<24, DenoiseGuide>))
+	                        : (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32>) : reinterpret_cast<const void *>(&denoise_kernel<24>));
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
 	const dim3 grid((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
-	if (tw == 32u) hipLaunchKernelGGL(denoise_kernel<32>, grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, (int)radius, (int)patch_radius, k * k, alpha, out);
-	else hipLaunchKernelGGL(denoise_kernel<24>, grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, (int)radius, (int)patch_radius, k * k, alpha, out);
+	const int ri = (int)radius, fi = (int)patch_radius;
+	const double k2 = k * k, kf2 = k_f * k_f;
+	if (guided) {
+		const DenoiseGuide gd{feat_planes, kf2, tau};
+		if (tw == 32u) hipLaunchKernelGGL((denoise_kernel<32, DenoiseGuide>), grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out, gd);
+		else hipLaunchKernelGGL((denoise_kernel<24, DenoiseGuide>), grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out, gd);
+	} else {
+		if (tw == 32u) hipLaunchKernelGGL(denoise_kernel<32>, grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out);
+		else hipLaunchKernelGGL(denoise_kernel<24>, grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out);
+	}
 	return hipGetLastError();
 }
 

@@ -107,16 +107,24 @@ hipError_t launch_tile_error(hipStream_t stream, const double *accum, const doub
 constexpr uint32_t kDenoiseTile = 16;
 constexpr double kDenoiseEps = 1e-10;
 constexpr uint32_t kDenoiseMaxRadius = 12, kDenoiseMaxPatch = 4;
+constexpr int kDenoiseFeat = (int)RMD_FEATURE_CHANNELS; // rmd_denoise_guided: feature channels per pixel
 // dynamic LDS of denoise_kernel<tile_width>: the apron's u and v (48 B a pixel) and the term image with its row sums
 size_t denoise_lds_bytes(uint32_t tile_width, uint32_t radius, uint32_t patch_radius);
 // 32 when that tile's LDS fits the budget (every (r, f) but r = 12 with f = 4: 168,192 B), else 24 (145,152 B there)
 uint32_t denoise_tile_width(uint32_t radius, uint32_t patch_radius);
 // out = the denoised means of the W x H frame (accum, accum_sq) whose rect i holds rect_counts[i] samples; n_img is W*H uint32 of scratch for the
 // per-pixel counts, count_image_columns the workgroups given to each rect.  rects and rect_counts are device memory; k and alpha are checked by
-// the caller
-hipError_t launch_denoise(hipStream_t stream, const double *accum, const double *accum_sq, const rmd_tile_rect *rects, const uint32_t *rect_counts,
-                          uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k,
-                          double alpha, uint32_t *n_img, double *out);
+// the caller.  With the feature weight (rmd_denoise_guided) when feat / feat_sq are given (W*H*7 doubles each, pixel-interleaved); both null = the
+// unguided kernel (rmd_denoise), feat_planes unused.  feat_planes is 14 * W*H doubles of scratch for the planar per-pixel f and g; k_f and tau are
+// checked by the caller
+hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
+                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
+                                 uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
+                                 double *out);
+// rmd_render_features (features.hip): for each of the P.n_work wave tiles, the first-hit features of samples P.sample_begin .. + P.sample_count - 1
+// added to feat (and their squares to feat_sq when it is not null), W*H*RMD_FEATURE_CHANNELS doubles each
+hipError_t launch_features(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const WaveTile *wave_tiles, double *feat,
+                           double *feat_sq);
 hipError_t launch_render_list(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
                               const ListWork *list, double *rgb_out, int32_t *path_obj, uint32_t *path_sub);
 // tile rectangles of a frame <-> a packed buffer (kernels.hip: tile_copy_kernel); `first[i]` = pixels in front of rect i

@@ -5,6 +5,9 @@
 //                                                                    [--adaptive THRESHOLD [--adaptive-floor F]]   (needs --spi)
 //                                                                    [--denoise 1 [--denoise-radius R] [--denoise-patch F] [--denoise-k K]
 //                                                                     [--denoise-alpha A]]   (the image is rmd_denoise's, on GPU 0)
+//                                                                    [--denoise-features 1 [--denoise-feature-k K] [--denoise-feature-tau T]]
+//                                                                      (needs --denoise 1: first-hit features guide the filter, rmd_denoise_guided)
+//                                                                    [--dump-features FILE]   (the W*H*7 feature means as raw f64: the AOVs)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -30,7 +33,8 @@ using namespace raymond;
 // TileFinished, :101-103: with snapshots of several workers in the channel it is only safe once they have been drained.)  With st.denoise the
 // finished tiles go through denoise_tiles on GPU 0 once the workers have left, as await() would.
 static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size_t &progressed, double *last_finished_s = nullptr,
-                                    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now()) {
+                                    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), const Scene *scene = nullptr,
+                                    std::vector<double> *feature_means = nullptr, std::vector<Tile> *finished_out = nullptr) {
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	const size_t n_tiles = generate_tiles(W, H, st.tile_size).size();
 	std::vector<Tile> finished_tiles; // (zero-copy views of the download's block: taking them is cheap; the image is assembled afterwards)
@@ -50,8 +54,11 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 	}
 	if (st.denoise) {
 		handle.await(); // (its channel is drained: it only waits for the workers and rethrows a worker's error)
-		return finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0}) : denoise_tiles(finished_tiles, st, 0);
+		std::vector<Vector3> den = finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0}) : denoise_tiles(finished_tiles, st, 0, scene, feature_means);
+		if (finished_out) *finished_out = std::move(finished_tiles);
+		return den;
 	}
+	if (finished_out) *finished_out = finished_tiles; // (views: cheap)
 	std::vector<Vector3> image(W * H, Vector3{0, 0, 0});
 	for (const Tile &t : finished_tiles)
 		for (size_t y = 0; y < t.height; y++)
@@ -167,7 +174,7 @@ int main(int argc, char **argv) {
 		}
 		if (argc >= 8 && !std::strcmp(argv[1], "render")) {
 			const auto t0 = std::chrono::steady_clock::now(); // cli_old/src/main.rs:36
-			std::string what = argv[2], raw;
+			std::string what = argv[2], raw, dump_features;
 			Settings st;
 			st.camera_settings.backbuffer_width = std::atoi(argv[3]);
 			st.camera_settings.backbuffer_height = std::atoi(argv[4]);
@@ -188,6 +195,10 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-patch")) st.denoise_patch = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-k")) st.denoise_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-alpha")) st.denoise_alpha = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--denoise-feature-k")) st.denoise_feature_k = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-feature-tau")) st.denoise_feature_tau = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--dump-features")) dump_features = argv[i + 1];
 			}
 			Scene scene;
 			if (what == "spheres") scene = reflective_spheres();
@@ -197,8 +208,32 @@ int main(int argc, char **argv) {
 			TaskHandle handle = render_tiled(scene, st); // :152
 			size_t progressed = 0;
 			// progressive mode: every message is taken as it arrives (consume); else await() (:153)
-			std::vector<Vector3> image = st.samples_per_iteration ? consume(handle, st, progressed) : handle.await();
+			// (--dump-features: every message is taken by consume, which keeps the finished tiles' rects and counts)
+			std::vector<double> feature_means;
+			std::vector<Tile> finished;
+			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty();
+			std::vector<Vector3> image = by_consume ? consume(handle, st, progressed, nullptr, t0, &scene, dump_features.empty() ? nullptr : &feature_means, &finished)
+			                                        : handle.await();
 			const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
+			if (!dump_features.empty()) {
+				if (feature_means.empty()) { // not a guided render: a feature pass of its own over the finished tiles, each at its count
+					std::vector<rmd_tile_rect> rects;
+					std::vector<uint32_t> counts;
+					for (const Tile &t : finished) {
+						rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+						counts.push_back((uint32_t)t.sample_count);
+					}
+					feature_means = render_features(scene, st, rects, counts, 0);
+					std::vector<double> n_img(W * H, 0.0);
+					for (size_t i = 0; i < rects.size(); i++)
+						for (size_t y = rects[i].top; y < (size_t)rects[i].top + rects[i].height; y++)
+							for (size_t x = rects[i].left; x < (size_t)rects[i].left + rects[i].width; x++) n_img[x + y * W] = (double)counts[i];
+					for (size_t p = 0; p < W * H; p++)
+						for (size_t j = 0; j < RMD_FEATURE_CHANNELS; j++) feature_means[p * RMD_FEATURE_CHANNELS + j] /= n_img[p];
+				}
+				std::ofstream f(dump_features, std::ios::binary);
+				f.write(reinterpret_cast<const char *>(feature_means.data()), (std::streamsize)(feature_means.size() * 8));
+			}
 			write_ppm(argv[7], tone_map(image), W, H); // :161-197
 			if (!raw.empty()) {
 				std::ofstream f(raw, std::ios::binary);

@@ -402,6 +402,11 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 	if (!(settings.denoise_k > 0.0) || !std::isfinite(settings.denoise_k)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_k must be finite and > 0");
 	if (!(settings.denoise_alpha >= 0.0) || !std::isfinite(settings.denoise_alpha))
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_alpha must be finite and >= 0");
+	if (!(settings.denoise_feature_k > 0.0) || !std::isfinite(settings.denoise_feature_k))
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_feature_k must be finite and > 0");
+	if (!(settings.denoise_feature_tau > 0.0) || !std::isfinite(settings.denoise_feature_tau))
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_feature_tau must be finite and > 0");
+	if (settings.denoise_features && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_features needs denoise");
 	if (!(settings.adaptive_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_threshold > 0.0 && settings.samples_per_iteration == 0)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)");
@@ -409,6 +414,7 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 	TaskHandle h;
 	h.settings = settings;
 	h.shared_ = std::make_shared<TaskHandle::Shared>();
+	if (settings.denoise_features) h.scene_ = std::make_shared<const Scene>(scene);
 	const CameraSettings &cam = settings.camera_settings;
 	for (const rmd_tile_rect &r : generate_tiles(cam.backbuffer_width, cam.backbuffer_height, settings.tile_size)) {
 		Tile t;
@@ -455,11 +461,80 @@ std::vector<Vector3> TaskHandle::await() {
 			}
 	}
 	lock.unlock();
-	if (!collected.empty()) out = denoise_tiles(collected, settings, 0); // render_tiled's first GPU
+	if (!collected.empty()) out = denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
 	return out;
 }
 
-std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device) {
+namespace {
+rmd_camera camera_pod(const Settings &st) {
+	rmd_camera cam;
+	std::memset(&cam, 0, sizeof(cam));
+	cam.backbuffer_width = (uint32_t)st.camera_settings.backbuffer_width, cam.backbuffer_height = (uint32_t)st.camera_settings.backbuffer_height;
+	cam.fov_vert = st.camera_settings.fov_vert;
+	for (int a = 0; a < 3; a++) cam.position[a] = st.camera_settings.transform.position[a];
+	cam.focal_length = st.camera_settings.focal_length, cam.aperture_radius = st.camera_settings.aperture_radius;
+	return cam;
+}
+// the feature sums of the rects, each at its own count, into feat / feat_sq (zeroed device buffers of ctx): one call per distinct sample count
+void render_features_on(rmd_context *ctx, const Scene &scene, const Settings &st, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
+                        double *feat, double *feat_sq) {
+	rmd_scene *dscene = nullptr;
+	std::vector<rmd_object> objs;
+	std::vector<rmd_grid_desc> grids;
+	flatten(scene, objs, grids);
+	check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
+	try {
+		const rmd_camera cam = camera_pod(st);
+		std::vector<uint32_t> distinct(counts);
+		std::sort(distinct.begin(), distinct.end());
+		distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+		for (uint32_t n : distinct) {
+			if (n == 0) continue;
+			std::vector<rmd_tile_rect> share;
+			for (size_t i = 0; i < rects.size(); i++)
+				if (counts[i] == n) share.push_back(rects[i]);
+			rmd_settings s;
+			std::memset(&s, 0, sizeof(s));
+			s.bounce_limit = (uint32_t)st.bounce_limit, s.sample_begin = 0, s.sample_count = n, s.seed = st.seed;
+			s.flags = st.use_dof ? RMD_RENDER_DOF : 0u;
+			check(rmd_render_features_async(ctx, dscene, &cam, &s, share.data(), (uint32_t)share.size(), feat, feat_sq), ctx, "rmd_render_features");
+		}
+		check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize");
+	} catch (...) {
+		rmd_scene_destroy(dscene);
+		throw;
+	}
+	rmd_scene_destroy(dscene);
+}
+} // namespace
+
+std::vector<double> render_features(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
+                                    int device, std::vector<double> *sums_sq) {
+	if (rects.size() != counts.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_features: one sample count per rect");
+	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
+	std::vector<double> out(W * H * RMD_FEATURE_CHANNELS);
+	if (sums_sq) sums_sq->assign(out.size(), 0.0);
+	rmd_context *ctx = nullptr;
+	double *dev[2] = {nullptr, nullptr};
+	try {
+		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
+		for (double *&d : dev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
+		render_features_on(ctx, scene, settings, rects, counts, dev[0], sums_sq ? dev[1] : nullptr);
+		check(rmd_framebuffer_download(ctx, dev[0], out.data(), out.size()), ctx, "rmd_framebuffer_download");
+		if (sums_sq) check(rmd_framebuffer_download(ctx, dev[1], sums_sq->data(), sums_sq->size()), ctx, "rmd_framebuffer_download");
+	} catch (...) {
+		for (double *d : dev)
+			if (d) rmd_framebuffer_free(ctx, d);
+		rmd_context_destroy(ctx);
+		throw;
+	}
+	for (double *d : dev) rmd_framebuffer_free(ctx, d);
+	rmd_context_destroy(ctx);
+	return out;
+}
+
+std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, const Scene *scene, std::vector<double> *feature_means) {
+	if (settings.denoise_features && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_tiles: settings.denoise_features needs the scene");
 	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
 	std::vector<double> sums(W * H * 3, 0.0), sums_sq(W * H * 3, 0.0);
 	std::vector<rmd_tile_rect> rects;
@@ -479,22 +554,43 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 	std::vector<Vector3> out(W * H);
 	rmd_context *ctx = nullptr;
 	double *dev[3] = {nullptr, nullptr, nullptr};
+	double *fdev[2] = {nullptr, nullptr}; // settings.denoise_features: the feature sums and sums of squares
 	try {
 		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
 		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
+		if (settings.denoise_features) {
+			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
+			render_features_on(ctx, *scene, settings, rects, counts, fdev[0], fdev[1]);
+			if (feature_means) {
+				feature_means->assign(W * H * RMD_FEATURE_CHANNELS, 0.0);
+				check(rmd_framebuffer_download(ctx, fdev[0], feature_means->data(), feature_means->size()), ctx, "rmd_framebuffer_download");
+				std::vector<double> n_img(W * H, 0.0);
+				for (size_t i = 0; i < rects.size(); i++)
+					for (size_t y = rects[i].top; y < (size_t)rects[i].top + rects[i].height; y++)
+						for (size_t x = rects[i].left; x < (size_t)rects[i].left + rects[i].width; x++) n_img[x + y * W] = (double)counts[i];
+				for (size_t p = 0; p < W * H; p++)
+					for (size_t j = 0; j < RMD_FEATURE_CHANNELS; j++) (*feature_means)[p * RMD_FEATURE_CHANNELS + j] /= n_img[p];
+			}
+		}
 		check(rmd_framebuffer_upload(ctx, sums.data(), dev[0], sums.size()), ctx, "rmd_framebuffer_upload");
 		check(rmd_framebuffer_upload(ctx, sums_sq.data(), dev[1], sums_sq.size()), ctx, "rmd_framebuffer_upload");
-		check(rmd_denoise(ctx, dev[0], dev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), settings.denoise_radius,
-		                  settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, dev[2]),
-		      ctx, "rmd_denoise");
+		// (fdev both null without denoise_features: exactly rmd_denoise)
+		check(rmd_denoise_guided(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+		                         settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,
+		                         settings.denoise_feature_tau, dev[2]),
+		      ctx, "rmd_denoise_guided");
 		check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
 	} catch (...) {
 		for (double *d : dev)
+			if (d) rmd_framebuffer_free(ctx, d);
+		for (double *d : fdev)
 			if (d) rmd_framebuffer_free(ctx, d);
 		rmd_context_destroy(ctx);
 		throw;
 	}
 	for (double *d : dev) rmd_framebuffer_free(ctx, d);
+	for (double *d : fdev)
+		if (d) rmd_framebuffer_free(ctx, d);
 	rmd_context_destroy(ctx);
 	return out;
 }

@@ -134,6 +134,11 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	bool denoise = false;
 	uint32_t denoise_radius = 10, denoise_patch = 3;
 	double denoise_k = 0.45, denoise_alpha = 1.0;
+	// Feature-guided denoising (needs denoise; false = off): await() also uploads the scene to its GPU, renders the finished tiles' first-hit features
+	// there (rmd_render_features: one call per distinct sample count, each tile at its own count, this seed and DOF flag) and filters with
+	// rmd_denoise_guided, k_f = denoise_feature_k, tau = denoise_feature_tau (both finite and > 0, or render_tiled throws).
+	bool denoise_features = false;
+	double denoise_feature_k = 1.0, denoise_feature_tau = 1e-2; // (the best of the sweep in DESIGN.md section 12)
 };
 
 // core/src/tile.rs:13 `data: Vec<Vector3>` — the running sums of a tile, width * height of them, row-major.  Here a VIEW: the tiles of one
@@ -197,6 +202,7 @@ class TaskHandle {
   private:
 	friend TaskHandle render_tiled(const Scene &, const Settings &);
 	TaskHandle() = default;
+	std::shared_ptr<const Scene> scene_; // settings.denoise_features: the scene whose features await() renders
 	std::shared_ptr<Shared> shared_;
 	std::vector<std::thread> workers_;
 	TileCallback callback_;
@@ -207,7 +213,14 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings);
 
 // Extension (settings.denoise): the W*H denoised means, row-major — the tiles' sums (`data`), sums of squares (`data_sq`) and sample counts
 // assembled into one frame and filtered by rmd_denoise on GPU `device` with the settings' parameters.  A pixel that no tile covers has n = 0 (0 / 0).
-std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0);
+// settings.denoise_features: `scene` (required then) is uploaded to that GPU, the tiles' first-hit features are rendered and the filter is
+// rmd_denoise_guided.  feature_means (optional): receives the W*H*7 feature means (sums / the tile's count; 0 / 0 where no tile lies).
+std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, const Scene *scene = nullptr,
+                                   std::vector<double> *feature_means = nullptr);
+// The W*H*7 first-hit feature sums (and, when asked for, sums of squares) of a frame whose rect i holds counts[i] samples, rendered on GPU `device`
+// with the settings' camera, seed and DOF flag: the AOVs (normal xyz, albedo rgb, depth) of raymond_hip.h's rmd_render_features.
+std::vector<double> render_features(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
+                                    int device = 0, std::vector<double> *sums_sq = nullptr);
 
 // Tile generation of render_tiled (:142-173): column-major, edge tiles clamped
 std::vector<rmd_tile_rect> generate_tiles(size_t width, size_t height, std::pair<size_t, size_t> tile_size);

@@ -64,6 +64,20 @@ SIGNATURES = {
         C.c_int32,
         [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _vp],
     ),
+    "rmd_denoise_guided": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
+         C.c_double, C.c_double, _vp],
+    ),
+    "rmd_feature_buffer_alloc": (C.c_int32, [_vp, C.c_uint32, C.c_uint32, _P(_vp)]),
+    "rmd_render_features": (
+        C.c_int32,
+        [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, _vp, _vp],
+    ),
+    "rmd_render_features_async": (
+        C.c_int32,
+        [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, _vp, _vp],
+    ),
     "rmd_context_synchronize": (C.c_int32, [_vp]),
     "rmd_render_tiles_host": (
         C.c_int32,

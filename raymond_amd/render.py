@@ -139,6 +139,39 @@ class Framebuffer:
             self.ptr = C.c_void_p()
 
 
+class FeatureBuffer(Framebuffer):
+    """W*H*7 f64 first-hit feature sums in HBM (rmd_feature_buffer_alloc): per pixel normal xyz, albedo rgb, depth."""
+
+    def __init__(self, ctx, width, height):
+        self.ctx, self.width, self.height = ctx, width, height
+        self.n = width * height * abi.RMD_FEATURE_CHANNELS
+        self.owned = True
+        p = C.c_void_p()
+        ctx.check(ctx.L.rmd_feature_buffer_alloc(ctx.handle, width, height, C.byref(p)))
+        self.ptr = p
+
+    def download(self):
+        out = np.empty((self.height, self.width, abi.RMD_FEATURE_CHANNELS), dtype=np.float64)
+        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
+        return out
+
+    def download_tiles(self, tiles):
+        raise NotImplementedError("feature buffers have no tile-rect transfers")
+
+    def upload_tiles(self, tiles, datas):
+        raise NotImplementedError("feature buffers have no tile-rect transfers")
+
+
+def render_features(ctx, dscene, camera_settings, settings, tiles, features, sample_begin=0, sample_count=None, sync=True, features_sq=None):
+    """rmd_render_features[_async]: add the first-hit features (normal, albedo, depth) of `sample_count` samples per pixel of `tiles` into the
+    FeatureBuffer `features`, and their squares into `features_sq` when given."""
+    cam = camera_settings.pod()
+    st = settings.pod(sample_begin, sample_count)
+    arr = tiles if isinstance(tiles, tuple) and len(tiles) == 2 and hasattr(tiles[0], "_length_") else (tile_array(tiles), len(tiles))
+    fn = ctx.L.rmd_render_features if sync else ctx.L.rmd_render_features_async
+    ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], features.ptr, None if features_sq is None else features_sq.ptr))
+
+
 def render_tiles(ctx, dscene, camera_settings, settings, tiles, framebuffer, sample_begin=0, sample_count=None, sync=True, framebuffer_sq=None):
     """rmd_render_tiles[_async]: add `sample_count` samples per pixel of `tiles` into `framebuffer`.  With `framebuffer_sq`:
     rmd_render_tiles_moments[_async], which also adds every sample's square to it."""
@@ -186,6 +219,38 @@ def denoise_arrays(ctx, sums, sums_sq, rects, counts, **params):
             b.close()
 
 
+def denoise_guided(ctx, framebuffer, framebuffer_sq, features, features_sq, rects, counts, out_framebuffer, radius=10, patch_radius=3, k=0.45, alpha=1.0,
+                   k_f=1.0, tau=1e-2):
+    """rmd_denoise_guided: denoise() with the feature weight of the FeatureBuffers `features` / `features_sq` (both None: exactly denoise())."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != len(rects):
+        raise ValueError("one sample count per rect")
+    ctx.check(ctx.L.rmd_denoise_guided(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr,
+                                       None if features_sq is None else features_sq.ptr, framebuffer.width, framebuffer.height, tile_array(rects),
+                                       counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius), int(patch_radius), float(k), float(alpha),
+                                       float(k_f), float(tau), out_framebuffer.ptr))
+
+
+def denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **params):
+    """denoise_guided() for host arrays: (H, W, 3) sums and sums of squares and (H, W, 7) feature sums and sums of squares in (the latter two may
+    both be None), the (H, W, 3) denoised means out."""
+    H, W = sums.shape[0], sums.shape[1]
+    bufs = [Framebuffer(ctx, W, H) for _ in range(3)]
+    fbufs = [FeatureBuffer(ctx, W, H) for _ in range(2)] if feats is not None else [None, None]
+    try:
+        bufs[0].upload(sums)
+        bufs[1].upload(sums_sq)
+        if feats is not None:
+            fbufs[0].upload(feats)
+            fbufs[1].upload(feats_sq)
+        denoise_guided(ctx, bufs[0], bufs[1], fbufs[0], fbufs[1], rects, counts, bufs[2], **params)
+        return bufs[2].download()
+    finally:
+        for b in bufs + fbufs:
+            if b is not None:
+                b.close()
+
+
 def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
     """TaskHandle::await's divide + cli_old's tone-map/gamma/u8 cast (cli_old/src/main.rs:161-181) -> (H, W, 3) uint8."""
     out = np.empty((framebuffer.height, framebuffer.width, 3), dtype=np.uint8)
@@ -220,8 +285,9 @@ class Message:  # src/trace.rs:62-66
 
 
 class TaskHandle:  # src/trace.rs:70-135
-    def __init__(self, settings, messages, device=0):
+    def __init__(self, settings, messages, device=0, scene=None):
         self.settings = settings
+        self.scene = scene  # settings.denoise_features: await_() uploads it to `device` for the feature pass
         self._messages = list(messages)
         self.callback = None
         self.device = device  # settings.denoise: the GPU await_() denoises on (render_tiled's first)
@@ -242,11 +308,17 @@ class TaskHandle:  # src/trace.rs:70-135
         """`await`: W*H radiance values, row-major, each the tile sum divided by its sample count (:93-99).
 
         With settings.denoise (an extension): the finished tiles' sums, sums of squares and sample counts are assembled and the frame comes
-        back through rmd_denoise on `device` — means as well; a pixel that no finished tile covers has n = 0 and comes back as 0 / 0."""
+        back through rmd_denoise on `device` — means as well; a pixel that no finished tile covers has n = 0 and comes back as 0 / 0.  With
+        settings.denoise_features as well: the scene is uploaded to `device`, the finished tiles' first-hit features are rendered there
+        (finished_tile_features) and the filter is rmd_denoise_guided."""
         cam = self.settings.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         out = np.zeros(shape, dtype=np.float64)
         denoised = self.settings.denoise
+        if denoised and self.settings.denoise_features:
+            self.settings.check_denoise()
+            if self.scene is None:
+                raise ValueError("settings.denoise_features: this TaskHandle was made without the scene whose features await_() has to render")
         if denoised:
             sums, sums_sq, rects, counts = np.zeros(shape), np.zeros(shape), [], []
         while self._messages:
@@ -264,9 +336,41 @@ class TaskHandle:  # src/trace.rs:70-135
         if denoised:
             st = self.settings
             with Context(self.device) as ctx:
-                out = denoise_arrays(ctx, sums, sums_sq, rects, counts, radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k,
-                                     alpha=st.denoise_alpha)
+                params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
+                if st.denoise_features:
+                    feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts)
+                    out = denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
+                                                **params)
+                else:
+                    out = denoise_arrays(ctx, sums, sums_sq, rects, counts, **params)
         return out
+
+
+def finished_tile_features(ctx, scene, settings, rects, counts):
+    """The (H, W, 7) first-hit feature sums and sums of squares of a frame whose rect i holds counts[i] samples: one rmd_render_features call per
+    distinct sample count, each tile at its own count, with the settings' seed and DOF flag.  Pixels no rect covers stay zero."""
+    cam = settings.camera_settings
+    W, H = cam.backbuffer_width, cam.backbuffer_height
+    opened = []  # closed in reverse order whichever way the body leaves, each on its own
+    try:
+        ds = DeviceScene(ctx, scene)
+        opened.append(ds)
+        fb = FeatureBuffer(ctx, W, H)
+        opened.append(fb)
+        fb_sq = FeatureBuffer(ctx, W, H)
+        opened.append(fb_sq)
+        for n in sorted(set(int(c) for c in counts)):
+            share = [r for r, c in zip(rects, counts) if int(c) == n]
+            if n > 0:
+                render_features(ctx, ds, cam, settings, share, fb, 0, n, sync=False, features_sq=fb_sq)
+        ctx.synchronize()
+        return fb.download(), fb_sq.download()
+    finally:
+        for o in reversed(opened):
+            try:
+                o.close()
+            except Exception:  # noqa: BLE001 (a failing close must not keep the others open, nor hide the body's own error)
+                pass
 
 
 def render_tiled(scene, settings, devices=(0,)):
@@ -334,5 +438,5 @@ def render_tiled(scene, settings, devices=(0,)):
                 fb_sq.close()
             ds.close()
             ctx.close()
-    handle = TaskHandle(settings, messages, devices[0])
+    handle = TaskHandle(settings, messages, devices[0], scene if settings.denoise_features else None)
     return handle

@@ -244,7 +244,8 @@ class Settings:
 
     def __init__(self, camera_settings, sample_count, tile_size=(32, 32), bounce_limit=5, samples_per_iteration=0,
                  worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
-                 adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0):
+                 adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
+                 denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -272,6 +273,12 @@ class Settings:
         self.denoise_patch = denoise_patch
         self.denoise_k = float(denoise_k)
         self.denoise_alpha = float(denoise_alpha)
+        # Feature-guided denoising (an extension of the extension; False = off): await_() also renders the finished tiles' first-hit features
+        # (rmd_render_features) and filters with rmd_denoise_guided, k_f = denoise_feature_k and tau = denoise_feature_tau (defaults: the best of the
+        # sweep in DESIGN.md section 12).  Needs denoise.
+        self.denoise_features = bool(denoise_features)
+        self.denoise_feature_k = float(denoise_feature_k)
+        self.denoise_feature_tau = float(denoise_feature_tau)
         self.check_denoise()
 
     def check_adaptive(self):
@@ -284,7 +291,7 @@ class Settings:
             raise ValueError("adaptive_floor must be finite and > 0")
 
     def check_denoise(self):
-        """Raises ValueError for denoise settings rmd_denoise refuses (checked whether or not denoise is on)."""
+        """Raises ValueError for denoise settings rmd_denoise / rmd_denoise_guided refuse (checked whether or not denoise is on)."""
         for name, hi in (("denoise_radius", 12), ("denoise_patch", 4)):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= hi:
@@ -293,6 +300,12 @@ class Settings:
             raise ValueError("denoise_k must be finite and > 0")
         if not (self.denoise_alpha >= 0.0 and np.isfinite(self.denoise_alpha)):
             raise ValueError("denoise_alpha must be finite and >= 0")
+        if not (self.denoise_feature_k > 0.0 and np.isfinite(self.denoise_feature_k)):
+            raise ValueError("denoise_feature_k must be finite and > 0")
+        if not (self.denoise_feature_tau > 0.0 and np.isfinite(self.denoise_feature_tau)):
+            raise ValueError("denoise_feature_tau must be finite and > 0")
+        if self.denoise_features and not self.denoise:
+            raise ValueError("denoise_features needs denoise")
 
     def pod(self, sample_begin=0, sample_count=None):
         s = abi.Settings()
