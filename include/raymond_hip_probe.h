@@ -57,6 +57,13 @@ rmd_status rmd_probe_scene_intersect(rmd_context *ctx, const rmd_scene *scene, s
 /* core/src/geometry/acc_grid.rs:89-185 on grid `g` of the scene */
 rmd_status rmd_probe_grid_intersect(rmd_context *ctx, const rmd_scene *scene, uint32_t g, size_t n, const double *ray6, int32_t *hit,
                                     double *t, uint32_t *tri);
+/* The same through the DEEP form of the walk — the form of the split / queued launches: the sphere pre-test in place, the ring of pairs in the wave's
+ * carry area, walks put aside by cut_lanes / cut_round and taken up again from the carried DDA state (grid_walk.hpp).  One wave serves
+ * `rays_per_wave` consecutive rays (a multiple of 64) the way the render loops do: a lane whose walk was put aside presents the same ray again, a lane
+ * that is done takes the wave's next unserved ray, and the cuts reach only calls with at least 16 walkers (0 otherwise: every walk finishes).
+ * cut_lanes = cut_round = 0: every call finishes every walk.  The wave's call loop is bounded; RMD_ERR_DEVICE_FAULT if a wave reaches the bound. */
+rmd_status rmd_probe_grid_intersect_deep(rmd_context *ctx, const rmd_scene *scene, uint32_t g, size_t n, const double *ray6, uint32_t cut_lanes,
+                                         uint32_t cut_round, uint32_t rays_per_wave, int32_t *hit, double *t, uint32_t *tri);
 /* One sample per entry (src/trace.rs:199-200) through the render kernel's own code path:
  * rgb_out[3i..] = radiance of (xy2[2i], xy2[2i+1], sample[i]).  path_obj/path_sub (optional, n*17 each):
  * object index (-1 = miss) and triangle index per trace() depth, -2 beyond the path's end. */

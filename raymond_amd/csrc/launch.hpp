@@ -140,5 +140,8 @@ hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,
                               const DevGrid *grids, uint32_t n_grids, uint32_t mask_words_total, uint32_t axis_pairs, const double *rays, double *out);
+// the DEEP walk on grid `g`, one wave per `rays_per_wave` rays (probe_kernels.hip: probe_grid_deep_kernel); *stuck is raised by a wave that reaches its call bound
+hipError_t launch_probe_grid_deep(hipStream_t stream, uint32_t g, uint32_t n, const DevGrid *grids, uint32_t n_grids, uint32_t mask_words_total, const double *rays,
+                                  uint32_t cut_lanes, uint32_t cut_round, uint32_t rays_per_wave, uint32_t walk_steps_bound, double *out, uint32_t *stuck);
 
 } // namespace rmd

@@ -223,6 +223,33 @@ rmd_status rmd_probe_grid_intersect(rmd_context *ctx, const rmd_scene *scene, ui
 	return scene_probe(ctx, scene, 1, g, n, ray6, hit, t, tri);
 }
 
+rmd_status rmd_probe_grid_intersect_deep(rmd_context *ctx, const rmd_scene *scene, uint32_t g, size_t n, const double *ray6, uint32_t cut_lanes,
+                                         uint32_t cut_round, uint32_t rays_per_wave, int32_t *hit, double *t, uint32_t *tri) {
+	if (!ctx || !scene || scene->ctx != ctx || !ray6 || !hit || !t || !tri) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	if (g >= scene->n_grids) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: grid index out of range");
+	if (rays_per_wave == 0u || rays_per_wave % 64u != 0u || rays_per_wave > (1u << 20) || cut_lanes > 255u || cut_round > 255u || n > 0x7FFFFFFFull)
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: rays_per_wave must be a multiple of 64 up to 2^20, the cuts at most 255, n below 2^31");
+	RMD_HIP(ctx, hipSetDevice(ctx->device));
+	if (n == 0) return RMD_OK;
+	DevBuf din, dout, dstuck;
+	RMD_HIP(ctx, hipMalloc(&din.p, n * 6 * sizeof(double)));
+	RMD_HIP(ctx, hipMalloc(&dout.p, n * 3 * sizeof(double)));
+	RMD_HIP(ctx, hipMalloc(&dstuck.p, sizeof(uint32_t)));
+	RMD_HIP(ctx, hipMemcpyAsync(din.p, ray6, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	RMD_HIP(ctx, hipMemsetAsync(dout.p, 0, n * 3 * sizeof(double), ctx->stream));
+	RMD_HIP(ctx, hipMemsetAsync(dstuck.p, 0, sizeof(uint32_t), ctx->stream));
+	RMD_HIP(ctx, rmd::launch_probe_grid_deep(ctx->stream, g, (uint32_t)n, scene->d_grids, scene->n_grids, scene->mask_words_total, (const double *)din.p, cut_lanes,
+	                                         cut_round, rays_per_wave, scene->walk_steps_bound, (double *)dout.p, (uint32_t *)dstuck.p));
+	std::vector<double> out(n * 3);
+	uint32_t stuck = 0;
+	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipMemcpyAsync(&stuck, dstuck.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	if (stuck) return rmd::fail(ctx, RMD_ERR_DEVICE_FAULT, "probe: a wave of the DEEP walk reached its bound of walk calls with rays unfinished (it cannot: an internal fault)");
+	for (size_t i = 0; i < n; i++) hit[i] = (int32_t)out[3 * i], t[i] = out[3 * i + 1], tri[i] = (uint32_t)out[3 * i + 2];
+	return RMD_OK;
+}
+
 rmd_status rmd_probe_triangle_sphere(size_t n, const double *pos9, double *out5) {
 	if (n != 0 && (!pos9 || !out5)) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
 	for (size_t i = 0; i < n; i++) {

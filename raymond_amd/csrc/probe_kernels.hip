@@ -143,6 +143,80 @@ __global__ __launch_bounds__(64) void probe_scene_kernel(int mode, uint32_t g, u
 	}
 }
 
+// AccGrid::intersects on grid `g` through the DEEP form of the walk (grid_walk.hpp: the split / queued launches' form — sphere pre-test, the ring in the
+// wave's WalkCarry, walks put aside and taken up again), driven the way the render loops drive it.  One wave serves the `rays_per_wave` consecutive rays
+// that begin at blockIdx.x * rays_per_wave: a lane whose call comes back `carried` presents the SAME ray again with the flag set, a lane that is done
+// takes the wave's next unserved ray, so carried walks go on beside fresh ones.  cut_lanes / cut_round reach only calls with at least
+// kWalkCutMinWalkers walkers (render_kernel.hpp: queued_wave) and are 0 otherwise — the rule under which every walk finishes.
+// The call loop has a bound of its own: a call that is given a cut has at least kWalkCutMinWalkers walkers, each of which takes at least one step or
+// finishes (grid_walk.hpp: a round's stepping loop runs its body at least once for every walking lane), a walk has at most res.x + res.y + res.z + 3 steps,
+// and a call without a cut finishes every walk it is given — which happens only once fewer than kWalkCutMinWalkers rays are left, i.e. once.  So a wave
+// makes at most rays_per_wave * (res.x + res.y + res.z + 4) / kWalkCutMinWalkers + 2 calls (`max_calls`: launch_probe_grid_deep); one that reaches the
+// bound stops and raises *stuck.
+__global__ __launch_bounds__(64) void probe_grid_deep_kernel(uint32_t g, uint32_t n, const DevGrid *__restrict__ grids, uint32_t n_grids, uint32_t mask_words_total,
+                                                             const double *__restrict__ rays, uint32_t cut_lanes, uint32_t cut_round, uint32_t rays_per_wave,
+                                                             uint32_t max_calls, double *__restrict__ out, uint32_t *__restrict__ stuck) {
+	extern __shared__ __align__(16) unsigned char smem[];
+	uint32_t *lmasks = reinterpret_cast<uint32_t *>(smem);
+	for (uint32_t gi = 0; gi < n_grids && mask_words_total; gi++) {
+		const DevGrid &gg = grids[gi];
+		if (gg.mask_lds_word == 0xFFFFFFFFu) continue;
+		for (uint32_t i = threadIdx.x; i < gg.mask_n_words; i += 64u) lmasks[gg.mask_lds_word + i] = as_global(gg.mask_words)[i];
+	}
+	__syncthreads();
+	unsigned char *wave_lds = smem + (size_t)((mask_words_total + 3u) & ~3u) * 4u;
+	WalkScratch &scr = *reinterpret_cast<WalkScratch *>(wave_lds);
+	WalkCarry *carry = reinterpret_cast<WalkCarry *>(wave_lds + sizeof(WalkScratch));
+	const DevGrid &gg = grids[g];
+	const uint32_t *mask = (mask_words_total && gg.mask_lds_word != 0xFFFFFFFFu) ? lmasks + gg.mask_lds_word : nullptr;
+	const uint32_t begin = blockIdx.x * rays_per_wave; // (the host launches no wave past the batch, and n + rays_per_wave fits 32 bits)
+	const uint32_t end = n - begin < rays_per_wave ? n : begin + rays_per_wave;
+	uint32_t served = begin; // the wave's next unserved ray (uniform)
+	bool has = false, carried = false;
+	uint32_t mine = 0;
+	V3 ro = mk(0.0, 0.0, 0.0), rd = mk(0.0, 0.0, 0.0);
+	for (uint32_t calls = 0;; calls++) {
+		const unsigned long long free_mask = __ballot(!has);
+		const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(free_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)free_mask, 0u)); // free lanes before this one
+		if (!has && rank < end - served) {
+			mine = served + rank, has = true, carried = false;
+			ro = ld3(rays + (size_t)mine * 6), rd = ld3(rays + (size_t)mine * 6 + 3);
+		}
+		served += umin((uint32_t)__popcll(free_mask), end - served);
+		const uint32_t n_walkers = (uint32_t)__popcll(__ballot(has));
+		if (n_walkers == 0u) break;
+		if (calls >= max_calls) { // cannot happen (see above): stop, and say so
+			if ((threadIdx.x & 63u) == 0u) *stuck = 1u;
+			break;
+		}
+		const bool cut = n_walkers >= kWalkCutMinWalkers;
+		bool h = false;
+		double t = 0.0;
+		uint32_t tri = 0;
+		grid_intersect_wave<true>(gg, mask, scr, has, ro, rd, h, t, tri, 0u, nullptr, cut ? cut_lanes : 0u, carry, &carried, cut ? cut_round : 0u);
+		if (has && !carried) { // (an unfinished walk comes back with `carried` set and no result)
+			double *o = out + (size_t)mine * 3;
+			o[0] = h, o[1] = h ? t : 0.0, o[2] = h ? tri : 0u;
+			has = false;
+		}
+	}
+}
+
+hipError_t launch_probe_grid_deep(hipStream_t stream, uint32_t g, uint32_t n, const DevGrid *grids, uint32_t n_grids, uint32_t mask_words_total, const double *rays,
+                                  uint32_t cut_lanes, uint32_t cut_round, uint32_t rays_per_wave, uint32_t walk_steps_bound, double *out, uint32_t *stuck) {
+	if (n == 0) return hipSuccess;
+	// (walk_steps_bound: rmd_scene::walk_steps_bound = res.x + res.y + res.z + 3 of the scene's largest grid)
+	const uint32_t max_calls = (uint32_t)std::min<uint64_t>((uint64_t)rays_per_wave * ((uint64_t)walk_steps_bound + 1u) / kWalkCutMinWalkers + 2u, 0xFFFFFFFFull);
+	const size_t probe_lds = (size_t)((mask_words_total + 3u) & ~3u) * 4u + sizeof(WalkScratch) + sizeof(WalkCarry);
+	if (probe_lds > 64u * 1024u) {
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&probe_grid_deep_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes);
+		if (e != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(probe_grid_deep_kernel, dim3((n + rays_per_wave - 1u) / rays_per_wave), dim3(64), probe_lds, stream, g, n, grids, n_grids, mask_words_total, rays,
+	                   cut_lanes, cut_round, rays_per_wave, max_calls, out, stuck);
+	return hipGetLastError();
+}
+
 hipError_t launch_render_list(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
                               const ListWork *list, double *rgb_out, int32_t *path_obj, uint32_t *path_sub) {
 	if (P.n_work == 0) return hipSuccess;

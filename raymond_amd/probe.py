@@ -29,6 +29,7 @@ _SIGS = {
     "rmd_probe_elementary": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "rmd_probe_scene_intersect": [_vp, _vp, _sz, _vp, _vp, _vp, _vp],
     "rmd_probe_grid_intersect": [_vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp],
+    "rmd_probe_grid_intersect_deep": [_vp, _vp, C.c_uint32, _sz, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp],
     "rmd_probe_trace_samples": [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _sz, _vp, _vp, _vp, _vp, _vp],
     "rmd_probe_triangle_sphere": [_sz, _vp, _vp],
     "rmd_probe_pretest_pairs": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -145,6 +146,19 @@ def grid_intersect(ctx, dscene, g, rays):
     t = np.zeros(n)
     tri = np.zeros(n, dtype=np.uint32)
     ctx.check(L.rmd_probe_grid_intersect(ctx.handle, dscene.handle, g, n, _p(rays), _p(hit), _p(t), _p(tri)))
+    return hit, t, tri
+
+
+def grid_intersect_deep(ctx, dscene, g, rays, cut_lanes=0, cut_round=0, rays_per_wave=64):
+    """AccGrid::intersects through the DEEP form of the walk (pre-test, ring, walks put aside and taken up again), one wave per `rays_per_wave`
+    consecutive rays.  api: rmd_probe_grid_intersect_deep."""
+    L = _L()
+    rays = _f(rays, 6)
+    n = rays.shape[0]
+    hit = np.zeros(n, dtype=np.int32)
+    t = np.zeros(n)
+    tri = np.zeros(n, dtype=np.uint32)
+    ctx.check(L.rmd_probe_grid_intersect_deep(ctx.handle, dscene.handle, g, n, _p(rays), cut_lanes, cut_round, rays_per_wave, _p(hit), _p(t), _p(tri)))
     return hit, t, tri
 
 

@@ -10,7 +10,8 @@ Cody-Waite + fdlibm-kernel sin/cos (<= 1.6 ulp) and sin/cos(acos(s)) taken as sq
 Schlick term (libm pow vs three multiplications) and in the association of the bounce weights, which the kernel
 multiplies forward into a throughput instead of applying them on the way back up the recursion):
   * RNG, integer outputs, hit/miss flags, object/triangle ids: bit-exact;
-  * arithmetic-only device functions (intersections, ONB, normals): <= 4 ulp, in practice 0;
+  * arithmetic-only device functions (intersections, ONB, normals): <= 4 ulp, in practice 0 (the grid walk in all its forms — plain and DEEP,
+    exact and coarse masks, adversarial ray classes, hand-built grids — is held to this bound ray by ray in tests/test_gpu_grid_walk.py);
   * libm-bound device functions: relative 1e-13;
   * per-sample radiance: relative 1e-9 for >= 99.9 % of samples; the remainder must be explained by
     a changed hit sequence (an ulp-level direction difference flipping a hit/miss or a branch);
@@ -349,7 +350,9 @@ def test_paired_planes_keep_the_scan_order_on_ties(gpu_ctx, oracle):
 
 
 def test_grid_walk(gpu_ctx, oracle, small_mesh_scene):
-    """AccGrid::intersects incl. origins inside the box, on the max side (Q6) and axis-parallel rays (Q8)."""
+    """AccGrid::intersects incl. origins inside the box, on the max side (Q6) and axis-parallel rays (Q8) — the plain form on one grid; the walk's
+    other forms (DEEP with its pre-test, ring and carried walks; coarse masks; grids with res.z > res.y) and the adversarial ray classes are in
+    tests/test_gpu_grid_walk.py."""
     sc = small_mesh_scene
     ds, osc = render.DeviceScene(gpu_ctx, sc), oracle.OracleScene(sc)
     g = sc.objects[1].geometry.grid
