@@ -472,12 +472,17 @@ rmd_status rmd_reduce_framebuffer_async(rmd_comm *comm, double *accum_dev, size_
 /* ---- host-side grid build (AccGrid::build_from_mesh, core/src/geometry/acc_grid.rs:6-83) ---- */
 typedef struct rmd_grid_build rmd_grid_build; /* owns the arrays a rmd_grid_desc points at */
 /* tri_pos/tri_nrm: n_tris*9 doubles each (host).  Computes mesh bounds (mesh.rs:123-140), resolution,
- * cell_size, cells, mapping_table.  RMD_ERR_GRID_INDEX where the reference would panic on the
- * `x + res.x*(y + z*res.z)` index (acc_grid.rs:61) running past the cell array. */
+ * cell_size, cells, mapping_table.  RMD_ERR_GRID_INDEX where the reference would panic: the
+ * `x + res.x*(y + z*res.z)` index (acc_grid.rs:61) running past the cell array, a cell bound that does not fit usize (:44-51: a
+ * triangle of NaNs), a zero resolution (:54: an infinite vertex, a volume that overflows or underflows).
+ * The bounds are folded over the vertices in order from the reference's seeds; a NaN coordinate is skipped, and where a bound is
+ * zero — the reference leaves the sign of a +0.0 / -0.0 tie to the platform's f64::min / max — the LATER vertex's zero is the bound. */
 rmd_status rmd_grid_build_from_mesh(const double *tri_pos, const double *tri_nrm, uint64_t n_tris,
                                     rmd_grid_build **out);
-/* The same build on the GPU of `ctx` (bounds reduction, per-cell atomic counts, device scan, fill, per-cell sort);
- * the resulting tables are byte-identical to rmd_grid_build_from_mesh's. */
+/* The same build on the GPU of `ctx` (bounds and resolution on the host as above; per-cell atomic counts, device scan, fill and
+ * per-cell sort on the device).  Status for status, and bounds (with the signs of their zeros), resolution, cell size and both tables byte
+ * for byte, what rmd_grid_build_from_mesh gives (tests/test_gpu_grid_build.py).  The per-cell sort is an insertion sort in one lane,
+ * quadratic in the length of a cell's run: a mesh with tens of thousands of triangles in ONE cell is better built on the host. */
 rmd_status rmd_grid_build_from_mesh_gpu(rmd_context *ctx, const double *tri_pos, const double *tri_nrm, uint64_t n_tris,
                                         rmd_grid_build **out);
 /* Fills `desc` with pointers into `build` (valid until rmd_grid_build_destroy). */

@@ -47,14 +47,7 @@ static rmd_status grid_build_from_mesh_impl(const double *tri_pos, const double 
 	if (!g) return rmd::fail(nullptr, RMD_ERR_OUT_OF_MEMORY, "rmd_grid_build_from_mesh: allocation failed");
 
 	// Mesh::find_mesh_bounds (mesh.rs:123-140)
-	for (int a = 0; a < 3; a++) g->bbox_min[a] = kSeedMin[a], g->bbox_max[a] = kSeedMax[a];
-	for (uint64_t i = 0; i < n_tris; i++)
-		for (int k = 0; k < 3; k++)
-			for (int a = 0; a < 3; a++) {
-				double v = tri_pos[i * 9 + k * 3 + a];
-				g->bbox_min[a] = std::fmin(g->bbox_min[a], v);
-				g->bbox_max[a] = std::fmax(g->bbox_max[a], v);
-			}
+	rmd::mesh_bounds(tri_pos, n_tris, g->bbox_min, g->bbox_max);
 
 	// estimate_grid_resolution (acc_grid.rs:6-17)
 	double size[3];

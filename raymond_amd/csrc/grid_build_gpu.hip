@@ -1,14 +1,19 @@
 // GPU-side AccGrid::build_from_mesh (reference core/src/geometry/acc_grid.rs:36-83) — SURVEY.md section 8f row N4.
-// Produces the same cells / mapping_table bytes as the host builder (grid_build.cpp) and the oracle:
-//   1. bounds_kernel   Mesh::find_mesh_bounds (mesh.rs:123-140): min/max over all vertices, seeded with the reference's
-//                      odd constants (Q9); per-block partials, finished on the host (min/max are order-independent).
+// Produces the same bounds, cell size and cells / mapping_table bytes as the host builder (grid_build.cpp) and the oracle
+// (tests/test_gpu_grid_build.py, on the adversarial meshes of tests/grid_meshes.py):
+//   1. host            Mesh::find_mesh_bounds (mesh.rs:123-140): rmd::mesh_bounds (internal.hpp), the fold the host builder uses, in vertex order.
+//                      On the host, not a device reduction (there was one, bounds_kernel): a tree of v_min_f64 / v_max_f64 gives the value of
+//                      a bound in any order but not the SIGN OF A ZERO bound — it ordered -0.0 < +0.0 where the project's rule is "the later
+//                      vertex wins" — and an O(n) fold over an array the host already holds needs no kernel.
 //   2. host            estimate_grid_resolution + cell_size (acc_grid.rs:6-17, :38) with the host libm pow, exactly as
 //                      grid_build.cpp does, so the truncations agree.
 //   3. count_kernel    per triangle: its cell range (:43-56) and one atomicAdd per overlapped cell.
 //   4. scan            cells[c] = sum over c' < c of (1 + count[c'])  (:67-74), three-phase device scan.
 //   5. fill_kernel     per triangle: claim a slot in each overlapped cell's run with an atomic cursor.
 //   6. sort_kernel     per cell: sort its run ascending — the reference pushes indices while iterating the triangles in
-//                      order (:42,:61), so every run is ascending; the atomics above fill it in arbitrary order.
+//                      order (:42,:61), so every run is ascending; the atomics above fill it in arbitrary order.  An insertion sort in one
+//                      lane, quadratic in the run's length: fine for the dozens of entries of a mesh's cells, some 10^8 dependent memory steps for one of 10^4
+//                      (the tests keep to runs of at most 1024).
 #define RMD_WITH_HIP 1
 #include <hip/hip_runtime.h>
 
@@ -31,28 +36,6 @@ struct GridDims {
 	double bmin[3], cell[3];
 	unsigned long long res[3], n_cells;
 };
-
-__global__ __launch_bounds__(256) void bounds_kernel(const double *__restrict__ pos, unsigned long long n_tris, double *__restrict__ partial) {
-	double mn[3] = {kSeedMinDev[0], kSeedMinDev[1], kSeedMinDev[2]}, mx[3] = {kSeedMaxDev[0], kSeedMaxDev[1], kSeedMaxDev[2]};
-	for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n_tris; i += (unsigned long long)gridDim.x * 256)
-		for (int k = 0; k < 3; k++)
-			for (int a = 0; a < 3; a++) {
-				double v = pos[i * 9 + k * 3 + a];
-				mn[a] = fmin(mn[a], v), mx[a] = fmax(mx[a], v);
-			}
-	__shared__ double red[6][256];
-	for (int a = 0; a < 3; a++) red[a][threadIdx.x] = mn[a], red[3 + a][threadIdx.x] = mx[a];
-	__syncthreads();
-	for (int s = 128; s > 0; s >>= 1) {
-		if ((int)threadIdx.x < s)
-			for (int a = 0; a < 3; a++) {
-				red[a][threadIdx.x] = fmin(red[a][threadIdx.x], red[a][threadIdx.x + s]);
-				red[3 + a][threadIdx.x] = fmax(red[3 + a][threadIdx.x], red[3 + a][threadIdx.x + s]);
-			}
-		__syncthreads();
-	}
-	if (threadIdx.x < 6) partial[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
-}
 
 // triangle.rs:70-84 + acc_grid.rs:43-56: cell range of one triangle; false where the reference's usize cast fails
 __device__ bool tri_range(const double *p9, const GridDims &g, unsigned lo[3], unsigned hi[3]) {
@@ -185,29 +168,9 @@ static rmd_status grid_build_from_mesh_gpu_impl(rmd_context *ctx, const double *
 	if (!ctx) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "rmd_grid_build_from_mesh_gpu: null context");
 	if (!tri_pos || !tri_nrm || !out || n_tris == 0) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_grid_build_from_mesh_gpu: null/empty input");
 	if (n_tris >= (1ull << 32)) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, "rmd_grid_build_from_mesh_gpu: more than 2^32-1 triangles");
-	RMD_HIP(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = ctx->stream;
-	Dev dev;
-	double *d_pos = nullptr, *d_partial = nullptr;
-	RMD_HIP(ctx, dev.alloc((void **)&d_pos, n_tris * 9 * sizeof(double)));
-	RMD_HIP(ctx, hipMemcpyAsync(d_pos, tri_pos, n_tris * 9 * sizeof(double), hipMemcpyHostToDevice, st));
-	const unsigned bounds_blocks = (unsigned)std::min<uint64_t>((n_tris + 255) / 256, 1024);
-	RMD_HIP(ctx, dev.alloc((void **)&d_partial, bounds_blocks * 6 * sizeof(double)));
-	hipLaunchKernelGGL(bounds_kernel, dim3(bounds_blocks), dim3(256), 0, st, d_pos, (unsigned long long)n_tris, d_partial);
-	RMD_HIP(ctx, hipGetLastError());
-	std::vector<double> partial(bounds_blocks * 6);
-	RMD_HIP(ctx, hipMemcpyAsync(partial.data(), d_partial, partial.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-	RMD_HIP(ctx, hipStreamSynchronize(st));
-
 	std::unique_ptr<rmd_grid_build> g(new (std::nothrow) rmd_grid_build());
 	if (!g) return rmd::fail(ctx, RMD_ERR_OUT_OF_MEMORY, "rmd_grid_build_from_mesh_gpu: allocation failed");
-	for (int a = 0; a < 3; a++) {
-		g->bbox_min[a] = partial[a], g->bbox_max[a] = partial[3 + a];
-		for (unsigned b = 1; b < bounds_blocks; b++) {
-			g->bbox_min[a] = std::fmin(g->bbox_min[a], partial[b * 6 + a]);
-			g->bbox_max[a] = std::fmax(g->bbox_max[a], partial[b * 6 + 3 + a]);
-		}
-	}
+	rmd::mesh_bounds(tri_pos, n_tris, g->bbox_min, g->bbox_max); // on the host, in vertex order (header, step 1)
 	// estimate_grid_resolution (acc_grid.rs:6-17) and cell_size (:38): same expressions, same libm as grid_build.cpp
 	double size[3];
 	for (int a = 0; a < 3; a++) size[a] = g->bbox_max[a] - g->bbox_min[a];
@@ -226,6 +189,12 @@ static rmd_status grid_build_from_mesh_gpu_impl(rmd_context *ctx, const double *
 	dims.n_cells = dims.res[0] * dims.res[1] * dims.res[2];
 	if (dims.n_cells > (1ull << 31)) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, "grid has more than 2^31 cells");
 
+	RMD_HIP(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = ctx->stream;
+	Dev dev;
+	double *d_pos = nullptr;
+	RMD_HIP(ctx, dev.alloc((void **)&d_pos, n_tris * 9 * sizeof(double)));
+	RMD_HIP(ctx, hipMemcpyAsync(d_pos, tri_pos, n_tris * 9 * sizeof(double), hipMemcpyHostToDevice, st));
 	const unsigned long long n_cells = dims.n_cells;
 	const unsigned tri_blocks = (unsigned)((n_tris + 255) / 256), scan_blocks = (unsigned)((n_cells + 1023) / 1024);
 	unsigned *d_count = nullptr, *d_cells = nullptr, *d_map = nullptr;
@@ -267,7 +236,7 @@ static rmd_status grid_build_from_mesh_gpu_impl(rmd_context *ctx, const double *
 	*out = g.release();
 	return RMD_OK;
 }
-// (host vectors for the partial bounds and the downloaded tables, device buffers behind RAII: nothing throws across the boundary)
+// (host vectors for the downloaded tables, device buffers behind RAII: nothing throws across the boundary)
 extern "C" rmd_status rmd_grid_build_from_mesh_gpu(rmd_context *ctx, const double *tri_pos, const double *tri_nrm, uint64_t n_tris,
                                                    rmd_grid_build **out) {
 	if (out) *out = nullptr;

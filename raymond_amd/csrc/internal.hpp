@@ -94,6 +94,21 @@ struct rmd_grid_build {
 };
 
 namespace rmd {
+// Mesh::find_mesh_bounds (mesh.rs:123-140) for both grid builders: the fold over all vertices in order, from the reference's seeds (Q9).  The
+// reference folds with f64::min / f64::max and leaves the sign of a zero bound — a tie of +0.0 and -0.0 — to the platform; std::fmin leaves it to
+// the compiler (g++ calls glibc, where the second operand wins; clang expands it inline, and which zero survives depends on how it orders the
+// operands — in the builders' loop the first).  The project's rule is the oracle's: the LATER vertex wins the tie, a NaN coordinate is skipped.
+// Written as comparisons so that every compiler gives the same bytes.
+inline void mesh_bounds(const double *tri_pos, uint64_t n_tris, double bbox_min[3], double bbox_max[3]) {
+	static const double seed_min[3] = {125125.0, 1251251.0, 12512512.0}, seed_max[3] = {-123125.0, -125123.0, -512123.0};
+	for (int a = 0; a < 3; a++) bbox_min[a] = seed_min[a], bbox_max[a] = seed_max[a];
+	for (uint64_t i = 0; i < n_tris * 3; i++)
+		for (int a = 0; a < 3; a++) {
+			const double v = tri_pos[i * 3 + a];
+			if (v <= bbox_min[a]) bbox_min[a] = v;
+			if (v >= bbox_max[a]) bbox_max[a] = v;
+		}
+}
 // Per-triangle constants of the Heron normal (triangle.rs:47-68): the two sides and the area that do not depend on the
 // hit point, with exactly the operations of device_core.hpp (dist = sqrt(((dx*dx + dy*dy) + dz*dz)), heron_area_of_sides):
 // every operation is a correctly rounded IEEE one and this file is compiled with -ffp-contract=off, so the values are

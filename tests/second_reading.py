@@ -207,6 +207,91 @@ def grid_intersects(grid, origin, direction):
         t_max[axis] += t_delta[axis]
 
 
+# ---------------------------------------------------------------- the grid build: mesh.rs:123-140, triangle.rs:70-84, acc_grid.rs:6-83
+# Written from the reference's source, not from raymond_amd/csrc/grid_build.cpp or oracle/oracle.cpp; tests/test_grid_meshes_host.py holds the oracle
+# to it on the adversarial meshes of tests/grid_meshes.py (all but the two largest: a plain-Python build of 10^5 triangles takes minutes).
+# ONE POINT IS A CONVENTION: the reference folds the bounds with f64::min / f64::max, whose result on a tie of +0.0 and -0.0 is whatever the
+# platform's minnum gives.  The project's rule is the oracle's: fold in vertex order, and on such a tie the LATER operand wins — which is what
+# fmin(acc, v) / fmax(acc, v) above do (`a if a < b else b` returns b on a tie).  A NaN coordinate is skipped (f64::min returns the other operand).
+BOUNDS_SEED_MIN = (125125.0, 1251251.0, 12512512.0)
+BOUNDS_SEED_MAX = (-123125.0, -125123.0, -512123.0)
+ISIZE_MAX = (1 << 63) - 1
+
+
+def as_usize(v):
+    """Rust's `as usize` of an f64: truncates, saturates, NaN -> 0"""
+    if v != v or v <= 0.0:
+        return 0
+    if v >= 18446744073709551616.0:
+        return MASK64
+    return int(v)
+
+
+def cast_usize(v):
+    """num-traits cast::<usize>(): truncation toward zero; None (the caller's expect() panics) for NaN and values outside (-1, 2^64)"""
+    if v != v or not (-1.0 < v < 18446744073709551616.0):
+        raise Panic("Failed to cast cell bounds to usize: %r" % (v,))
+    return int(v)
+
+
+def find_bounds(vertices):
+    """Mesh::find_mesh_bounds over all vertices of all triangles in order (mesh.rs:123-140) and Triangle::find_bounds over a triangle's three
+    (triangle.rs:70-84) are the same fold from the same seeds; per axis the order is vertex 0, 1, 2 of triangle 0, then of triangle 1, ..."""
+    mn, mx = list(BOUNDS_SEED_MIN), list(BOUNDS_SEED_MAX)
+    for v in vertices:
+        for i in range(3):
+            mn[i] = fmin(mn[i], v[i])
+            mx[i] = fmax(mx[i], v[i])
+    return tuple(mn), tuple(mx)
+
+
+def estimate_grid_resolution(bmin, bmax, triangle_count):  # acc_grid.rs:6-17
+    size = sub(bmax, bmin)
+    volume = abs(size[0] * size[1] * size[2])
+    density = powf(div(3.0 * float(triangle_count), volume), 1.0 / 3.0)
+    return tuple(as_usize(abs(size[i]) * density) for i in range(3))
+
+
+def grid_build(tri_pos):
+    """AccGrid::build_from_mesh (acc_grid.rs:36-83) of a mesh given as a list of 9-tuples -> dict(bbox_min, bbox_max, resolution, cell_size, cells,
+    mapping_table); raises Panic where the reference panics."""
+    tris = [(tuple(p[0:3]), tuple(p[3:6]), tuple(p[6:9])) for p in tri_pos]
+    bmin, bmax = find_bounds([v for t in tris for v in t])
+    res = estimate_grid_resolution(bmin, bmax, len(tris))
+    size = sub(bmax, bmin)
+    cell_size = tuple(div(size[i], float(res[i])) for i in range(3))
+    n_cells = (res[0] * res[1] * res[2]) & MASK64  # (a debug build panics on the overflow; a release build wraps)
+    if n_cells * 24 > ISIZE_MAX:
+        raise Panic("vec![NaiveCell; %d]: capacity overflow" % n_cells)  # (:39; below that and above the machine's memory the process aborts: not reached here)
+    if 0 in res:
+        # :54 `grid_res[i] - 1` underflows: a panic in a debug build; a release build wraps, and the first push (:61) then indexes an empty Vec —
+        # or the cast of a NaN quotient fails first (:44-51).  Every triangle reaches one of the two: a panic either way.
+        raise Panic("a zero resolution: %r" % (res,))
+    naive = [[] for _ in range(n_cells)]
+    for index, tri in enumerate(tris):
+        tmin, tmax = find_bounds(tri)
+        lo = sub(tmin, bmin)
+        hi = sub(tmax, bmin)
+        cell_min = [cast_usize(div(lo[i], cell_size[i])) for i in range(3)]
+        cell_max = [cast_usize(div(hi[i], cell_size[i])) for i in range(3)]
+        for i in range(3):
+            cell_min[i] = min(max(cell_min[i], 0), res[i] - 1)
+            cell_max[i] = min(max(cell_max[i], 0), res[i] - 1)
+        for z in range(cell_min[2], cell_max[2] + 1):
+            for y in range(cell_min[1], cell_max[1] + 1):
+                for x in range(cell_min[0], cell_max[0] + 1):
+                    at = x + res[0] * (y + z * res[2])  # :61 — res.z where res.y is meant (Q5)
+                    if at >= n_cells:
+                        raise Panic("index %d out of bounds of %d cells" % (at, n_cells))
+                    naive[at].append(index)
+    cells, mapping_table = [], []
+    for c in naive:  # :67-74
+        cells.append(len(mapping_table))
+        mapping_table.append(len(c))
+        mapping_table.extend(c)
+    return {"bbox_min": bmin, "bbox_max": bmax, "resolution": res, "cell_size": cell_size, "cells": cells, "mapping_table": mapping_table}
+
+
 # ================================================================ the rest of the path: Scene::intersect, the primitives, trace(), ray generation
 #     Sphere::intersects / get_surface_properties   core/src/geometry/primitives/sphere.rs:11-35
 #     Plane::intersects / get_surface_properties    core/src/geometry/primitives/plane.rs:11-32
