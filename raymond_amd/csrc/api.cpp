@@ -15,13 +15,6 @@
 namespace {
 thread_local std::string tl_last_error;
 
-#define RMD_HIP(ctx, call)                                                                                      \
-	do {                                                                                                        \
-		hipError_t e_ = (call);                                                                                 \
-		if (e_ != hipSuccess) return rmd::fail(ctx, e_ == hipErrorOutOfMemory ? RMD_ERR_OUT_OF_MEMORY : RMD_ERR_HIP, \
-		                                       std::string(#call) + ": " + hipGetErrorString(e_));              \
-	} while (0)
-
 rmd_status bind(rmd_context *ctx) {
 	if (!ctx) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "null context");
 	RMD_HIP(ctx, hipSetDevice(ctx->device));
@@ -41,21 +34,18 @@ rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, r
 	RMD_HIP(nullptr, hipGetDeviceProperties(&prop, device));
 	if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
 		return rmd::fail(nullptr, RMD_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library carries gfx950 code only");
-	rmd_context *ctx = new (std::nothrow) rmd_context();
+	std::unique_ptr<rmd_context> ctx(new (std::nothrow) rmd_context()); // (an early return below destroys what exists by then: ~rmd_context)
 	if (!ctx) return rmd::fail(nullptr, RMD_ERR_OUT_OF_MEMORY, "rmd_context_create: allocation failed");
 	ctx->device = device;
 	ctx->n_cus = (uint32_t)prop.multiProcessorCount;
 	ctx->wave_slots = (uint32_t)prop.multiProcessorCount * 16u; // both render kernels fit 4 waves per SIMD (<= 128 VGPRs)
-	ctx->hbm_bytes = (size_t)prop.totalGlobalMem;
+	ctx->owns_stream = own_stream, ctx->stream = stream;
 	if (own_stream) {
 		hipError_t se = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
 		if (se != hipSuccess) {
-			delete ctx;
+			ctx->stream = nullptr; // nothing for ~rmd_context to wait for or destroy
 			return rmd::fail(nullptr, RMD_ERR_HIP, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(se));
 		}
-		ctx->owns_stream = true;
-	} else {
-		ctx->stream = stream;
 	}
 	// environment hooks are read here, once; rmd_context_set_tunable changes them afterwards
 	{
@@ -78,10 +68,8 @@ rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, r
 		ctx->debug_flags = (uint32_t)env_int("RMD_DEBUG"); // DIAG builds only: 1 | 2 are timing ablations that change results, 8 | 16 count events, 256 fails the path queues' allocation
 #endif
 	}
-	if (hipEventCreate(&ctx->ev_start) != hipSuccess || hipEventCreate(&ctx->ev_stop) != hipSuccess) {
-		rmd_context_destroy(ctx);
+	if (hipEventCreate(&ctx->ev_start) != hipSuccess || hipEventCreate(&ctx->ev_stop) != hipSuccess)
 		return rmd::fail(nullptr, RMD_ERR_HIP, "hipEventCreate failed");
-	}
 	// the fault words: pinned host memory the device writes through (coherent: visible to the host once the launch has completed)
 	{
 		void *h = nullptr, *d = nullptr;
@@ -91,13 +79,10 @@ rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, r
 			std::memset(h, 0, rmd::kFaultWords * sizeof(uint32_t));
 			fe = hipHostGetDevicePointer(&d, h, 0);
 		}
-		if (fe != hipSuccess) {
-			rmd_context_destroy(ctx);
-			return rmd::fail(nullptr, RMD_ERR_HIP, std::string("fault words (hipHostMalloc): ") + hipGetErrorString(fe));
-		}
+		if (fe != hipSuccess) return rmd::fail(nullptr, RMD_ERR_HIP, std::string("fault words (hipHostMalloc): ") + hipGetErrorString(fe));
 		ctx->d_fault = (uint32_t *)d;
 	}
-	*out = ctx;
+	*out = ctx.release();
 	return RMD_OK;
 }
 
@@ -105,7 +90,7 @@ rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, r
 // rect list stays the same (a progressive render re-submits the same tiles every pass).
 rmd_status prepare_wave_tiles(rmd_context *ctx, const rmd_camera *cam, const rmd_tile_rect *tiles, uint32_t n_tiles) {
 	const uint32_t W = cam->backbuffer_width, H = cam->backbuffer_height;
-	if (ctx->d_wave_tiles && ctx->cached_W == W && ctx->cached_H == H && ctx->cached_rects.size() == n_tiles &&
+	if (ctx->wave_tiles.bytes() && ctx->cached_W == W && ctx->cached_H == H && ctx->cached_rects.size() == n_tiles &&
 	    (n_tiles == 0 || std::memcmp(ctx->cached_rects.data(), tiles, sizeof(rmd_tile_rect) * n_tiles) == 0))
 		return RMD_OK;
 	std::vector<rmd::WaveTile> wt;
@@ -124,14 +109,9 @@ rmd_status prepare_wave_tiles(rmd_context *ctx, const rmd_camera *cam, const rmd
 				wt.push_back(t);
 			}
 	}
-	if (wt.size() > ctx->wave_tiles_capacity) {
-		if (ctx->d_wave_tiles) RMD_HIP(ctx, hipFree(ctx->d_wave_tiles));
-		ctx->d_wave_tiles = nullptr, ctx->wave_tiles_capacity = 0;
-		RMD_HIP(ctx, hipMalloc((void **)&ctx->d_wave_tiles, wt.size() * sizeof(rmd::WaveTile)));
-		ctx->wave_tiles_capacity = wt.size();
-	}
+	RMD_HIP(ctx, ctx->wave_tiles.grow(wt.size() * sizeof(rmd::WaveTile)));
 	if (!wt.empty()) {
-		RMD_HIP(ctx, hipMemcpyAsync(ctx->d_wave_tiles, wt.data(), wt.size() * sizeof(rmd::WaveTile), hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(ctx->wave_tiles.as<rmd::WaveTile>(), wt.data(), wt.size() * sizeof(rmd::WaveTile), hipMemcpyHostToDevice, ctx->stream));
 		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // wt is a stack-owned staging vector
 	}
 	ctx->n_wave_tiles = (uint32_t)wt.size();
@@ -260,30 +240,24 @@ rmd_status rmd_context_create_on_stream(int32_t device_ordinal, void *hip_stream
 	return context_create(device_ordinal, (hipStream_t)hip_stream, false, out);
 }
 
-void rmd_context_destroy(rmd_context *ctx) {
-	if (!ctx) return;
-	(void)hipSetDevice(ctx->device);
-	if (ctx->stream || !ctx->owns_stream) (void)hipStreamSynchronize(ctx->stream);
-	if (ctx->d_wave_tiles) (void)hipFree(ctx->d_wave_tiles);
-	if (ctx->d_sample_buf) (void)hipFree(ctx->d_sample_buf);
-	if (ctx->d_debug_counters) (void)hipFree(ctx->d_debug_counters);
-	if (ctx->d_work_counter) (void)hipFree(ctx->d_work_counter);
-	if (ctx->d_queue_buf) (void)hipFree(ctx->d_queue_buf);
-	if (ctx->d_tile_done) (void)hipFree(ctx->d_tile_done);
-	if (ctx->h_fault) (void)hipHostFree(ctx->h_fault);
-	if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-	for (auto &sl : ctx->transfer) {
-		if (sl.d_packed) (void)hipFree(sl.d_packed);
-		if (sl.d_table) (void)hipFree(sl.d_table);
+// The device is selected and both streams are waited for here, in the body: the member buffers are freed after it, and no block may go while a
+// stream can still use it.  (A context whose own stream was never created has nothing to wait for.)
+rmd_context::~rmd_context() {
+	(void)hipSetDevice(device);
+	if (stream || !owns_stream) (void)hipStreamSynchronize(stream);
+	if (h_fault) (void)hipHostFree(h_fault);
+	if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+	for (auto &sl : transfer) {
 		if (sl.packed_ready) (void)hipEventDestroy(sl.packed_ready);
 		if (sl.copied) (void)hipEventDestroy(sl.copied);
 	}
-	if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-	if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-	if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-	if (ctx->owns_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-	delete ctx;
+	if (copy_stream) (void)hipStreamDestroy(copy_stream);
+	if (ev_start) (void)hipEventDestroy(ev_start);
+	if (ev_stop) (void)hipEventDestroy(ev_stop);
+	if (owns_stream && stream) (void)hipStreamDestroy(stream);
 }
+
+void rmd_context_destroy(rmd_context *ctx) { delete ctx; }
 
 const char *rmd_last_error(const rmd_context *ctx) { return ctx ? ctx->last_error.c_str() : tl_last_error.c_str(); }
 
@@ -396,13 +370,10 @@ static rmd_status derive_grid_tables(rmd_context *ctx, const rmd_grid_desc &g, G
 	return RMD_OK;
 }
 
-// (`sc`: the scene under construction, owned by the caller's frame so that an exception — std::bad_alloc from one of the host-side tables: a
-// 256^3 grid needs a gigabyte for its cell entries alone — can still release what has been uploaded)
 static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects, uint32_t n_objects, const rmd_grid_desc *grids, uint32_t n_grids,
-                                    rmd_scene **out, rmd_scene *&sc) {
+                                    rmd_scene **out) {
 	if (rmd_status s = bind(ctx)) return s;
 	if (!out || (n_objects && !objects) || (n_grids && !grids)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_scene_create: null argument");
-	*out = nullptr;
 	std::vector<rmd::DevObject> hobj(n_objects);
 	bool regular = true;
 	for (uint32_t i = 0; i < n_objects; i++) {
@@ -473,8 +444,9 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 		hobj[j].pair_info = rmd::kPairTestedAtPartner | rmd::kPairAxis | i; // the object loops pass both planes by ("tested at its partner's turn"):
 		hobj[i].pair_info |= rmd::kPairAxis;                                 // their turn is axis_pairs_visit's, ahead of the loop
 	}
-	sc = new (std::nothrow) rmd_scene();
-	if (!sc) return rmd::fail(ctx, RMD_ERR_OUT_OF_MEMORY, "rmd_scene_create: allocation failed");
+	// (the scene under construction: an early return or an exception — std::bad_alloc from one of the host-side tables: a 256^3 grid needs a
+	// gigabyte for its cell entries alone — releases what has been uploaded)
+	auto sc = std::make_unique<rmd_scene>();
 	sc->ctx = ctx, sc->n_objects = n_objects, sc->n_grids = n_grids, sc->regular = regular;
 	sc->axis_pairs = axis_pairs;
 	// the object loops' turns (device_types.hpp: RenderParams::visit_mask): a plane tested at its partner's turn or by the axis rule has none
@@ -502,22 +474,14 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 	for (uint32_t i = 0; i < n_objects; i++) sc->n_grid_objects += objects[i].geometry_kind == RMD_GEOM_GRID ? 1u : 0u;
 	auto upload = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
 		*dst = nullptr;
-		hipError_t e = hipMalloc(dst, bytes ? bytes : 16);
+		rmd::DeviceBuffer b;
+		hipError_t e = b.alloc(bytes ? bytes : 16);
 		if (e != hipSuccess) return e;
-		sc->owned.push_back(*dst);
+		*dst = b.as<void>();
+		sc->owned.push_back(std::move(b));
 		if (bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
 		return e;
 	};
-#define RMD_SCENE_HIP(call)                                                                     \
-	do {                                                                                        \
-		hipError_t e_ = (call);                                                                 \
-		if (e_ != hipSuccess) {                                                                 \
-			rmd_scene_destroy(sc), sc = nullptr;                                                              \
-			return rmd::fail(ctx, e_ == hipErrorOutOfMemory ? RMD_ERR_OUT_OF_MEMORY : RMD_ERR_HIP, \
-			                 std::string("rmd_scene_create: ") + hipGetErrorString(e_));         \
-		}                                                                                       \
-	} while (0)
-
 	std::vector<rmd::DevGrid> hgrid(n_grids);
 	for (uint32_t gi = 0; gi < n_grids; gi++) {
 		const rmd_grid_desc &g = grids[gi];
@@ -536,10 +500,7 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 			}
 			if (!derived) {
 				auto fresh = std::make_shared<GridDerived>();
-				if (rmd_status st = derive_grid_tables(ctx, g, *fresh)) {
-					rmd_scene_destroy(sc), sc = nullptr;
-					return st;
-				}
+				if (rmd_status st = derive_grid_tables(ctx, g, *fresh)) return st;
 				derived = fresh;
 				if (from_build) gb->derived = fresh;
 			}
@@ -568,10 +529,8 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 		if (budget_bytes < 64) budget_bytes = 64;
 		if (budget_bytes > rmd::kMaskBudgetBytes) budget_bytes = rmd::kMaskBudgetBytes;
 		const size_t budget_words = budget_bytes / 4 / n_grids;
-		if (budget_words < 2) { // one data word + the all-zero pad word is the smallest mask
-			rmd_scene_destroy(sc), sc = nullptr;
+		if (budget_words < 2) // one data word + the all-zero pad word is the smallest mask
 			return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, "rmd_scene_create: too many grids for the LDS occupancy-mask budget");
-		}
 		if ((g.n_cells + 31) / 32 + 1 <= budget_words) covered = g.n_cells;
 		uint32_t shift = 0;
 		while (shift < 63 && ((covered >> shift) + 31) / 32 + 1 > budget_words) shift++;
@@ -583,60 +542,48 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 		d.mask_lds_word = sc->mask_words_total;
 		sc->mask_words_total += (uint32_t)((mask.size() + 3) & ~(size_t)3);
 		void *p = nullptr;
-		RMD_SCENE_HIP(upload(entries.data(), entries.size() * sizeof(rmd::CellEntry), &p));
+		RMD_HIP(ctx, upload(entries.data(), entries.size() * sizeof(rmd::CellEntry), &p));
 		d.cell_entries = (const rmd::CellEntry *)p;
-		RMD_SCENE_HIP(upload(ids.data(), ids.size() * sizeof(uint32_t), &p));
+		RMD_HIP(ctx, upload(ids.data(), ids.size() * sizeof(uint32_t), &p));
 		d.tri_ids = (const uint32_t *)p;
-		RMD_SCENE_HIP(upload(recs.data(), recs.size(), &p));
+		RMD_HIP(ctx, upload(recs.data(), recs.size(), &p));
 		d.tri_recs = p;
-		RMD_SCENE_HIP(upload(mask.data(), mask.size() * sizeof(uint32_t), &p));
+		RMD_HIP(ctx, upload(mask.data(), mask.size() * sizeof(uint32_t), &p));
 		d.mask_words = (const uint32_t *)p;
-		RMD_SCENE_HIP(upload(g.tri_pos, g.n_tris * 9 * sizeof(double), &p));
+		RMD_HIP(ctx, upload(g.tri_pos, g.n_tris * 9 * sizeof(double), &p));
 		d.tri_pos = (const double *)p;
-		RMD_SCENE_HIP(upload(g.tri_nrm, g.n_tris * 9 * sizeof(double), &p));
+		RMD_HIP(ctx, upload(g.tri_nrm, g.n_tris * 9 * sizeof(double), &p));
 		d.tri_nrm = (const double *)p;
-		RMD_SCENE_HIP(upload(aux.data(), aux.size() * sizeof(double), &p));
+		RMD_HIP(ctx, upload(aux.data(), aux.size() * sizeof(double), &p));
 		d.tri_aux = (const double *)p;
-		RMD_SCENE_HIP(upload(derived->spheres.data(), derived->spheres.size() * sizeof(double), &p));
+		RMD_HIP(ctx, upload(derived->spheres.data(), derived->spheres.size() * sizeof(double), &p));
 		d.tri_sph = (const double *)p, d.sph_kb = derived->sphere_kb;
 	}
 	void *p = nullptr;
 	hobj.push_back(walls_block); // (uploaded behind the table; n_objects does not count it)
-	RMD_SCENE_HIP(upload(hobj.data(), hobj.size() * sizeof(rmd::DevObject), &p));
+	RMD_HIP(ctx, upload(hobj.data(), hobj.size() * sizeof(rmd::DevObject), &p));
 	sc->d_objects = (rmd::DevObject *)p;
-	RMD_SCENE_HIP(upload(hgrid.data(), hgrid.size() * sizeof(rmd::DevGrid), &p));
+	RMD_HIP(ctx, upload(hgrid.data(), hgrid.size() * sizeof(rmd::DevGrid), &p));
 	sc->d_grids = (rmd::DevGrid *)p;
-#undef RMD_SCENE_HIP
-	*out = sc;
-	sc = nullptr; // handed over
+	*out = sc.release();
 	return RMD_OK;
 }
 
 rmd_status rmd_scene_create(rmd_context *ctx, const rmd_object *objects, uint32_t n_objects, const rmd_grid_desc *grids, uint32_t n_grids,
                             rmd_scene **out) {
-	rmd_scene *sc = nullptr;
-	try {
-		return scene_create_impl(ctx, objects, n_objects, grids, n_grids, out, sc);
-	} catch (const std::bad_alloc &) {
-		if (sc) rmd_scene_destroy(sc);
-		if (out) *out = nullptr;
-		return rmd::fail(ctx, RMD_ERR_OUT_OF_MEMORY, "rmd_scene_create: the host ran out of memory building the scene's tables");
-	} catch (const std::exception &e) { // nothing throws across the boundary
-		if (sc) rmd_scene_destroy(sc);
-		if (out) *out = nullptr;
-		return rmd::fail(ctx, RMD_ERR_HIP, std::string("rmd_scene_create: ") + e.what());
+	if (out) *out = nullptr;
+	return rmd::guarded(ctx, "rmd_scene_create", [&] { return scene_create_impl(ctx, objects, n_objects, grids, n_grids, out); });
+}
+
+// (the launches that read the scene's tables are waited for in the body; `owned` is freed after it)
+rmd_scene::~rmd_scene() {
+	if (ctx) {
+		(void)hipSetDevice(ctx->device);
+		(void)hipStreamSynchronize(ctx->stream);
 	}
 }
 
-void rmd_scene_destroy(rmd_scene *scene) {
-	if (!scene) return;
-	if (scene->ctx) {
-		(void)hipSetDevice(scene->ctx->device);
-		(void)hipStreamSynchronize(scene->ctx->stream);
-	}
-	for (void *p : scene->owned) (void)hipFree(p);
-	delete scene;
-}
+void rmd_scene_destroy(rmd_scene *scene) { delete scene; }
 
 rmd_status rmd_framebuffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, double **out_dev) {
 	if (rmd_status s = bind(ctx)) return s;
@@ -730,9 +677,9 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, settings);
 	P.n_work = ctx->n_wave_tiles;
 	if (P.debug_flags & 24u) {
-		if (!ctx->d_debug_counters) RMD_HIP(ctx, hipMalloc((void **)&ctx->d_debug_counters, 40 * sizeof(unsigned long long)));
-		RMD_HIP(ctx, hipMemsetAsync(ctx->d_debug_counters, 0, 40 * sizeof(unsigned long long), ctx->stream));
-		P.debug_counters = ctx->d_debug_counters;
+		RMD_HIP(ctx, ctx->debug_counters.grow(40 * sizeof(unsigned long long)));
+		RMD_HIP(ctx, hipMemsetAsync(ctx->debug_counters.as<void>(), 0, 40 * sizeof(unsigned long long), ctx->stream));
+		P.debug_counters = ctx->debug_counters.as<unsigned long long>();
 	}
 	bool buffered = false;
 	uint32_t split = choose_split(ctx, scene->n_grids != 0, P.n_work, P.sample_count, &buffered);
@@ -740,7 +687,7 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	// item — round 1's; 4.7 % slower on the benchmark mesh, 2.4 % on the spheres frame, where a workgroup launch per item cost ~100 us
 	// of a wave slot each: 152 vs 113.6 ms at 32 items per wave tile)
 	const bool persistent = ctx->tunable[RMD_TUNE_LAUNCH_FORM] != 1;
-	if (persistent && !ctx->d_work_counter) RMD_HIP(ctx, hipMalloc((void **)&ctx->d_work_counter, 256));
+	if (persistent) RMD_HIP(ctx, ctx->work_counter.grow(256));
 	// Samples per pass of a split launch: the scratch buffer holds n_wave_tiles x 64 x samples x 32 bytes (the whole C3 frame at 500 spp
 	// is 33 GB, one launch).  By default it may take an eighth of the device memory that is free right now (RMD_TUNE_SCRATCH_CAP_MB
 	// overrides), never less than 8 samples per pass; what does not fit runs as several passes.  The device may still refuse the
@@ -755,7 +702,7 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		else {
 			size_t free_b = 0, total_b = 0;
 			RMD_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-			cap = (free_b + ctx->sample_buf_bytes) / 8; // the buffer this context already holds counts as available to it
+			cap = (free_b + ctx->sample_buf.bytes()) / 8; // the buffer this context already holds counts as available to it
 		}
 		if (bytes_per_sample * per_pass > cap) per_pass = (uint32_t)(cap / bytes_per_sample);
 		// (the mesh kernel numbers a pass's 32-byte sectors in 32 bits: render_kernel.hpp, PathId)
@@ -765,12 +712,11 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		if (per_pass > P.sample_count) per_pass = P.sample_count;
 		// (a frame of more than 2^32 / 8 / 64 = 8.4 M wave tiles — 537 Mpixel — cannot number even the smallest pass's sectors in 32 bits: unsplit, no scratch)
 		if (sectors_per_sample * per_pass > 0xFFFFFFFFull) split = 1u, buffered = false, per_pass = P.sample_count;
-		while (buffered && bytes_per_sample * per_pass > ctx->sample_buf_bytes) {
-			double *fresh = nullptr;
-			const hipError_t e = hipMalloc((void **)&fresh, bytes_per_sample * per_pass);
+		while (buffered && bytes_per_sample * per_pass > ctx->sample_buf.bytes()) {
+			rmd::DeviceBuffer fresh; // allocate first: a pass that finally fits the old block runs in it
+			const hipError_t e = fresh.alloc(bytes_per_sample * per_pass);
 			if (e == hipSuccess) {
-				if (ctx->d_sample_buf) (void)hipFree(ctx->d_sample_buf);
-				ctx->d_sample_buf = fresh, ctx->sample_buf_bytes = bytes_per_sample * per_pass;
+				ctx->sample_buf = std::move(fresh);
 				break;
 			}
 			(void)hipGetLastError(); // the failure is handled here: it must not surface at the next launch check
@@ -796,12 +742,12 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 			const int64_t force = ctx->tunable[RMD_TUNE_CHAIN_ITEMS];
 			Q.chain_items = (buffered && scene->n_grids != 0u && (force == 2 || (force == 0 && Q.sample_count <= rmd::kChainMaxSamples))) ? 1u : 0u;
 		}
-		Q.sample_buf = ctx->d_sample_buf;
+		Q.sample_buf = ctx->sample_buf.as<double>();
 		// (a launch with fewer work items than the device has wave slots spreads better as one wave per item)
 		const bool persistent_pass = persistent && ((uint64_t)P.n_work * Q.split_k >= ctx->wave_slots || ctx->tunable[RMD_TUNE_LAUNCH_FORM] == 2);
 		if (persistent_pass) {
-			RMD_HIP(ctx, hipMemsetAsync(ctx->d_work_counter, 0, sizeof(uint32_t), ctx->stream));
-			Q.work_counter = ctx->d_work_counter;
+			RMD_HIP(ctx, hipMemsetAsync(ctx->work_counter.as<void>(), 0, sizeof(uint32_t), ctx->stream));
+			Q.work_counter = ctx->work_counter.as<uint32_t>();
 		}
 		// Persistent split launches of scenes with grids keep their paths in queues in device memory (render_kernel.hpp: render_wave_queued;
 		// RMD_TUNE_PATH_QUEUES: 1 = never): kQueuePaths entries on each of a resident wave's two stacks, 192 bytes a path — 49 KB a wave, 200 MB
@@ -809,42 +755,30 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		// the lane-per-path form (render_wave): the same frame bit for bit.
 		if (persistent_pass && buffered && scene->n_grids != 0u && ctx->tunable[RMD_TUNE_PATH_QUEUES] != 1) {
 			const size_t wave_bytes = rmd::path_queue_bytes_host(rmd::kQueuePaths), need = wave_bytes * ctx->wave_slots;
-			if (ctx->queue_buf_bytes < need) {
-				if (ctx->d_queue_buf) RMD_HIP(ctx, hipFree(ctx->d_queue_buf));
-				ctx->d_queue_buf = nullptr, ctx->queue_buf_bytes = 0;
-#if RMD_DIAG
-				// RMD_DEBUG bit 256 (DIAG builds): the device has no memory for the queues — the fallback below (tests/test_gpu_launch_edges.py)
-				const hipError_t qe = (ctx->debug_flags & 256u) ? hipErrorOutOfMemory : hipMalloc((void **)&ctx->d_queue_buf, need);
-#else
-				const hipError_t qe = hipMalloc((void **)&ctx->d_queue_buf, need);
-#endif
+			if (ctx->queue_buf.bytes() < need) {
+				// RMD_DEBUG bit 256 (DIAG builds; debug_flags is 0 in any other): the device has no memory for the queues — the fallback below
+				// (tests/test_gpu_launch_edges.py)
+				const hipError_t qe = (ctx->debug_flags & 256u) ? hipErrorOutOfMemory : ctx->queue_buf.grow(need);
 				if (qe == hipSuccess) {
-					ctx->queue_buf_bytes = need;
 					// (zeroed once: a trip's idle lanes read the trip's first entry, never one nobody wrote — but a fresh allocation should not hold another process's data)
-					RMD_HIP(ctx, hipMemsetAsync(ctx->d_queue_buf, 0, need, ctx->stream));
+					RMD_HIP(ctx, hipMemsetAsync(ctx->queue_buf.as<void>(), 0, need, ctx->stream));
 				} else {
 					(void)hipGetLastError();
-					ctx->d_queue_buf = nullptr;
 					if (qe != hipErrorOutOfMemory) return rmd::fail(ctx, RMD_ERR_HIP, std::string("hipMalloc(path queues): ") + hipGetErrorString(qe));
 				}
 			}
-			if (ctx->d_queue_buf) Q.queue_buf = ctx->d_queue_buf, Q.queue_wave_bytes = (uint32_t)wave_bytes, Q.queue_paths = rmd::kQueuePaths;
+			if (ctx->queue_buf.bytes()) Q.queue_buf = ctx->queue_buf.as<unsigned char>(), Q.queue_wave_bytes = (uint32_t)wave_bytes, Q.queue_paths = rmd::kQueuePaths;
 		}
 		// spheres kernel: the wave that finishes a wave tile last adds the tile's samples to the pixels itself (no second kernel: 120.3 ->
 		// 117.0 ms per C2 frame).  Mesh scenes keep sum_kernel: their kernel waits on memory a third of the time, and the sum's 33 GB of
 		// streaming reads in between cost it more (491.4 vs 487.3 ms on C3) than the separate kernel's 5.5 ms
 		if (buffered && scene->n_grids == 0) {
-			if (ctx->tile_done_words < P.n_work) {
-				if (ctx->d_tile_done) RMD_HIP(ctx, hipFree(ctx->d_tile_done));
-				ctx->d_tile_done = nullptr, ctx->tile_done_words = 0;
-				RMD_HIP(ctx, hipMalloc((void **)&ctx->d_tile_done, (size_t)P.n_work * sizeof(uint32_t)));
-				ctx->tile_done_words = P.n_work;
-			}
-			RMD_HIP(ctx, hipMemsetAsync(ctx->d_tile_done, 0, (size_t)P.n_work * sizeof(uint32_t), ctx->stream));
-			Q.tile_done = ctx->d_tile_done;
+			RMD_HIP(ctx, ctx->tile_done.grow((size_t)P.n_work * sizeof(uint32_t)));
+			RMD_HIP(ctx, hipMemsetAsync(ctx->tile_done.as<void>(), 0, (size_t)P.n_work * sizeof(uint32_t), ctx->stream));
+			Q.tile_done = ctx->tile_done.as<uint32_t>();
 		}
 		rmd::LaunchShape shape;
-		RMD_HIP(ctx, rmd::launch_render_tiles(ctx->stream, Q, scene->d_objects, scene->d_grids, ctx->d_wave_tiles, accum_dev, persistent_pass ? ctx->n_cus : 0u, &shape,
+		RMD_HIP(ctx, rmd::launch_render_tiles(ctx->stream, Q, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), accum_dev, persistent_pass ? ctx->n_cus : 0u, &shape,
 		                                      accum_sq_dev));
 		ctx->last_launch.passes++, ctx->last_launch.split_k = Q.split_k, ctx->last_launch.buffered = Q.buffered;
 		ctx->last_launch.persistent = shape.persistent, ctx->last_launch.waves_per_workgroup = shape.waves_per_wg; // the form it was launched in, not the one asked for
@@ -856,7 +790,7 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	ctx->timed = true;
 	if (P.debug_flags & 24u) {
 		unsigned long long h[40];
-		RMD_HIP(ctx, hipMemcpyAsync(h, ctx->d_debug_counters, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(h, ctx->debug_counters.as<void>(), sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
 		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		if ((P.debug_flags & 16u) && ctx->last_launch.queued) {
 			static const char *kinds[3] = {"GEN  ", "SHADE", "WALK "};
@@ -934,17 +868,18 @@ rmd_status rmd_render_tiles_moments(rmd_context *ctx, const rmd_scene *scene, co
 }
 
 static rmd_status tile_error_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
-                                  uint32_t sample_count, double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host, void *&d) {
+                                  uint32_t sample_count, double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host) {
 	if (rmd_status s = bind(ctx)) return s;
 	for (uint32_t i = 0; i < n_rects; i++)
 		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
 			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: tile rectangle outside the framebuffer");
+	rmd::DeviceBuffer d; // the device scratch (it outlives the wait below)
 	if (n_rects != 0) {
 		// device buffer: [rects: 16 bytes each][errors: 8 bytes each]
 		const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect);
-		RMD_HIP(ctx, hipMalloc(&d, rect_bytes + (size_t)n_rects * sizeof(double)));
-		rmd_tile_rect *d_rects = static_cast<rmd_tile_rect *>(d);
-		double *d_err = reinterpret_cast<double *>(static_cast<unsigned char *>(d) + rect_bytes);
+		RMD_HIP(ctx, d.alloc(rect_bytes + (size_t)n_rects * sizeof(double)));
+		rmd_tile_rect *d_rects = d.as<rmd_tile_rect>();
+		double *d_err = reinterpret_cast<double *>(d.as<unsigned char>() + rect_bytes);
 		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
 		RMD_HIP(ctx, rmd::launch_tile_error(ctx->stream, accum_dev, accum_sq_dev, d_rects, n_rects, width, sample_count, floor, d_err));
 		RMD_HIP(ctx, hipMemcpyAsync(out_err_host, d_err, (size_t)n_rects * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -959,28 +894,27 @@ rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const doubl
 		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: bad argument");
 	if (accum_sq_dev == accum_dev) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: accum_sq_dev must not alias accum_dev");
 	if (!(floor > 0.0) || !std::isfinite(floor)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error: floor must be finite and > 0");
-	void *d = nullptr; // the device scratch: freed here whichever way the body leaves
-	const rmd_status s = rmd::guarded(ctx, "rmd_tile_error", [&] {
-		return tile_error_impl(ctx, accum_dev, accum_sq_dev, width, height, sample_count, floor, rects, n_rects, out_err_host, d);
+	return rmd::guarded(ctx, "rmd_tile_error", [&] {
+		return tile_error_impl(ctx, accum_dev, accum_sq_dev, width, height, sample_count, floor, rects, n_rects, out_err_host);
 	});
-	if (d) (void)hipFree(d);
-	return s;
 }
 
 static rmd_status denoise_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
                                uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
-                               uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, void *&d) {
+                               uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev) {
 	if (rmd_status s = bind(ctx)) return s;
 	// device scratch: [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each, padded to 16 bytes]
 	// [guided: the planar per-pixel f and g, 14 planes of W*H doubles]
 	const size_t img_bytes = ((size_t)width * height * sizeof(uint32_t) + 15u) & ~(size_t)15u;
 	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = ((size_t)n_rects * sizeof(uint32_t) + 15u) & ~(size_t)15u;
 	const size_t plane_bytes = feat_dev ? (size_t)width * height * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
-	RMD_HIP(ctx, hipMalloc(&d, img_bytes + rect_bytes + count_bytes + plane_bytes));
-	uint32_t *d_img = static_cast<uint32_t *>(d);
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(static_cast<unsigned char *>(d) + img_bytes);
-	uint32_t *d_counts = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(d) + img_bytes + rect_bytes);
-	double *d_planes = feat_dev ? reinterpret_cast<double *>(static_cast<unsigned char *>(d) + img_bytes + rect_bytes + count_bytes) : nullptr;
+	rmd::DeviceBuffer scratch;
+	RMD_HIP(ctx, scratch.alloc(img_bytes + rect_bytes + count_bytes + plane_bytes));
+	unsigned char *d = scratch.as<unsigned char>();
+	uint32_t *d_img = scratch.as<uint32_t>();
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + img_bytes);
+	uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + img_bytes + rect_bytes);
+	double *d_planes = feat_dev ? reinterpret_cast<double *>(d + img_bytes + rect_bytes + count_bytes) : nullptr;
 	if (n_rects != 0) {
 		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
 		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, (size_t)n_rects * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -1041,15 +975,12 @@ static rmd_status denoise_checked(const char *what, rmd_context *ctx, const doub
 		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
 		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
 	}
-	void *d = nullptr; // the device scratch: freed here whichever way the body leaves
-	const rmd_status s = rmd::guarded(ctx, what, [&] {
+	return rmd::guarded(ctx, what, [&] {
 		const char *why = nullptr;
 		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
 		return denoise_impl(ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k, alpha, k_f,
-		                    tau, out_dev, d);
+		                    tau, out_dev);
 	});
-	if (d) (void)hipFree(d);
-	return s;
 }
 
 rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
@@ -1092,7 +1023,7 @@ static rmd_status render_features_impl(rmd_context *ctx, const rmd_scene *scene,
 	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, &st);
 	P.n_work = ctx->n_wave_tiles;
 	// (neither the context's events nor its launch record are touched: rmd_last_kernel_ms / rmd_last_launch_info keep describing the last render)
-	RMD_HIP(ctx, rmd::launch_features(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->d_wave_tiles, feat_dev, feat_sq_dev));
+	RMD_HIP(ctx, rmd::launch_features(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), feat_dev, feat_sq_dev));
 	return RMD_OK;
 }
 
@@ -1119,12 +1050,11 @@ rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const
 	if (rmd_status s = bind(ctx)) return s;
 	if (!camera || !accum_host) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_tiles_host: null argument");
 	size_t n = (size_t)camera->backbuffer_width * camera->backbuffer_height * 3;
-	double *dev = nullptr;
-	RMD_HIP(ctx, hipMalloc((void **)&dev, n * sizeof(double)));
-	rmd_status s = rmd_framebuffer_upload(ctx, accum_host, dev, n);
-	if (!s) s = rmd_render_tiles(ctx, scene, camera, settings, tiles, n_tiles, dev);
-	if (!s) s = rmd_framebuffer_download(ctx, dev, accum_host, n);
-	(void)hipFree(dev);
+	rmd::DeviceBuffer dev;
+	RMD_HIP(ctx, dev.alloc(n * sizeof(double)));
+	rmd_status s = rmd_framebuffer_upload(ctx, accum_host, dev.as<double>(), n);
+	if (!s) s = rmd_render_tiles(ctx, scene, camera, settings, tiles, n_tiles, dev.as<double>());
+	if (!s) s = rmd_framebuffer_download(ctx, dev.as<double>(), accum_host, n);
 	return s;
 }
 
@@ -1143,19 +1073,8 @@ rmd_status prepare_transfer(rmd_context *ctx, rmd_context::TransferSlot &sl, uin
 		hr[i] = r, hf[i] = n_pixels;
 		n_pixels += (uint64_t)r.width * r.height;
 	}
-	const size_t need = (size_t)n_pixels * 3 * sizeof(double);
-	if (need > sl.packed_bytes) {
-		if (sl.d_packed) RMD_HIP(ctx, hipFree(sl.d_packed));
-		sl.d_packed = nullptr, sl.packed_bytes = 0;
-		RMD_HIP(ctx, hipMalloc((void **)&sl.d_packed, need));
-		sl.packed_bytes = need;
-	}
-	if (sl.h_table.size() > sl.table_bytes) {
-		if (sl.d_table) RMD_HIP(ctx, hipFree(sl.d_table));
-		sl.d_table = nullptr, sl.table_bytes = 0;
-		RMD_HIP(ctx, hipMalloc(&sl.d_table, sl.h_table.size()));
-		sl.table_bytes = sl.h_table.size();
-	}
+	RMD_HIP(ctx, sl.packed.grow((size_t)n_pixels * 3 * sizeof(double)));
+	RMD_HIP(ctx, sl.table.grow(sl.h_table.size()));
 	if (!sl.packed_ready) RMD_HIP(ctx, hipEventCreateWithFlags(&sl.packed_ready, hipEventDisableTiming));
 	if (!sl.copied) RMD_HIP(ctx, hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
 	if (!ctx->copy_stream) RMD_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
@@ -1180,14 +1099,14 @@ static rmd_status download_tiles_async_impl(rmd_context *ctx, const double *dev,
 	if (rmd_status s = wait_slot(ctx, sl)) return s; // a third download waits for the first
 	uint64_t n_pixels = 0;
 	if (rmd_status s = prepare_transfer(ctx, sl, width, height, rects, n_rects, n_pixels)) return s;
-	const rmd_tile_rect *d_rects = reinterpret_cast<const rmd_tile_rect *>(sl.d_table);
-	const uint64_t *d_first = reinterpret_cast<const uint64_t *>(reinterpret_cast<const unsigned char *>(sl.d_table) + (size_t)n_rects * sizeof(rmd_tile_rect));
+	const rmd_tile_rect *d_rects = sl.table.as<rmd_tile_rect>();
+	const uint64_t *d_first = reinterpret_cast<const uint64_t *>(sl.table.as<unsigned char>() + (size_t)n_rects * sizeof(rmd_tile_rect));
 	// main stream: table, pack (behind the renders enqueued before); copy stream: the download (renders enqueued after this overlap it)
-	RMD_HIP(ctx, hipMemcpyAsync(sl.d_table, sl.h_table.data(), sl.h_table.size(), hipMemcpyHostToDevice, ctx->stream));
-	RMD_HIP(ctx, rmd::launch_tile_copy(ctx->stream, true, const_cast<double *>(dev), sl.d_packed, d_rects, d_first, n_rects, width));
+	RMD_HIP(ctx, hipMemcpyAsync(sl.table.as<void>(), sl.h_table.data(), sl.h_table.size(), hipMemcpyHostToDevice, ctx->stream));
+	RMD_HIP(ctx, rmd::launch_tile_copy(ctx->stream, true, const_cast<double *>(dev), sl.packed.as<double>(), d_rects, d_first, n_rects, width));
 	RMD_HIP(ctx, hipEventRecord(sl.packed_ready, ctx->stream));
 	RMD_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, sl.packed_ready, 0));
-	RMD_HIP(ctx, hipMemcpyAsync(host_packed, sl.d_packed, (size_t)n_pixels * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->copy_stream));
+	RMD_HIP(ctx, hipMemcpyAsync(host_packed, sl.packed.as<double>(), (size_t)n_pixels * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->copy_stream));
 	RMD_HIP(ctx, hipEventRecord(sl.copied, ctx->copy_stream));
 	sl.in_flight = true;
 	return RMD_OK;
@@ -1221,11 +1140,11 @@ static rmd_status upload_tiles_impl(rmd_context *ctx, const double *host_packed,
 	if (rmd_status s = wait_slot(ctx, sl)) return s;
 	uint64_t n_pixels = 0;
 	if (rmd_status s = prepare_transfer(ctx, sl, width, height, rects, n_rects, n_pixels)) return s;
-	const rmd_tile_rect *d_rects = reinterpret_cast<const rmd_tile_rect *>(sl.d_table);
-	const uint64_t *d_first = reinterpret_cast<const uint64_t *>(reinterpret_cast<const unsigned char *>(sl.d_table) + (size_t)n_rects * sizeof(rmd_tile_rect));
-	RMD_HIP(ctx, hipMemcpyAsync(sl.d_table, sl.h_table.data(), sl.h_table.size(), hipMemcpyHostToDevice, ctx->stream));
-	RMD_HIP(ctx, hipMemcpyAsync(sl.d_packed, host_packed, (size_t)n_pixels * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	RMD_HIP(ctx, rmd::launch_tile_copy(ctx->stream, false, dev, sl.d_packed, d_rects, d_first, n_rects, width));
+	const rmd_tile_rect *d_rects = sl.table.as<rmd_tile_rect>();
+	const uint64_t *d_first = reinterpret_cast<const uint64_t *>(sl.table.as<unsigned char>() + (size_t)n_rects * sizeof(rmd_tile_rect));
+	RMD_HIP(ctx, hipMemcpyAsync(sl.table.as<void>(), sl.h_table.data(), sl.h_table.size(), hipMemcpyHostToDevice, ctx->stream));
+	RMD_HIP(ctx, hipMemcpyAsync(sl.packed.as<double>(), host_packed, (size_t)n_pixels * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	RMD_HIP(ctx, rmd::launch_tile_copy(ctx->stream, false, dev, sl.packed.as<double>(), d_rects, d_first, n_rects, width));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the caller's buffer and the table are free again
 	return rmd::check_fault(ctx); // (this wait has also waited for every render enqueued before it)
 }
@@ -1264,7 +1183,7 @@ rmd_status rmd_last_launch_info(const rmd_context *ctx, rmd_launch_info *out) {
 }
 
 static rmd_status resolve_tonemap_impl(rmd_context *ctx, const double *accum_dev, uint32_t width, uint32_t height, uint32_t sample_count,
-                                       double exposure, double gamma, uint8_t *out_rgb8_host, uint8_t *&d) {
+                                       double exposure, double gamma, uint8_t *out_rgb8_host) {
 	if (rmd_status s = bind(ctx)) return s;
 	if (!accum_dev || !out_rgb8_host || width == 0 || height == 0 || sample_count == 0)
 		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_resolve_tonemap: bad argument");
@@ -1272,7 +1191,9 @@ static rmd_status resolve_tonemap_impl(rmd_context *ctx, const double *accum_dev
 	if (n_pixels > 0xFFFFFFFFull) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, "rmd_resolve_tonemap: more than 2^32-1 pixels");
 	// device buffer: [rgb8: 3 n bytes, padded to 4][count: 1 word][flagged pixel indices: n words]
 	const size_t rgb_bytes = (n_pixels * 3 + 3) & ~(size_t)3;
-	RMD_HIP(ctx, hipMalloc((void **)&d, rgb_bytes + 4 + n_pixels * 4));
+	rmd::DeviceBuffer scratch;
+	RMD_HIP(ctx, scratch.alloc(rgb_bytes + 4 + n_pixels * 4));
+	uint8_t *d = scratch.as<uint8_t>();
 	uint32_t *d_count = reinterpret_cast<uint32_t *>(d + rgb_bytes), *d_list = d_count + 1;
 	const double sc = (double)sample_count, inv_gamma = 1.0 / gamma;
 	uint32_t n_flagged = 0;
@@ -1316,10 +1237,7 @@ static rmd_status resolve_tonemap_impl(rmd_context *ctx, const double *accum_dev
 }
 rmd_status rmd_resolve_tonemap(rmd_context *ctx, const double *accum_dev, uint32_t width, uint32_t height, uint32_t sample_count,
                                double exposure, double gamma, uint8_t *out_rgb8_host) {
-	uint8_t *d = nullptr; // the device scratch: freed here whichever way the body leaves
-	const rmd_status s = rmd::guarded(ctx, "rmd_resolve_tonemap", [&] { return resolve_tonemap_impl(ctx, accum_dev, width, height, sample_count, exposure, gamma, out_rgb8_host, d); });
-	if (d) (void)hipFree(d);
-	return s;
+	return rmd::guarded(ctx, "rmd_resolve_tonemap", [&] { return resolve_tonemap_impl(ctx, accum_dev, width, height, sample_count, exposure, gamma, out_rgb8_host); });
 }
 
 } // extern "C"

@@ -144,24 +144,6 @@ __global__ __launch_bounds__(256) void sort_kernel(const unsigned *__restrict__ 
 	}
 }
 
-struct Dev {
-	std::vector<void *> ptrs;
-	~Dev() {
-		for (void *p : ptrs) (void)hipFree(p);
-	}
-	hipError_t alloc(void **p, size_t bytes) {
-		hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-		if (e == hipSuccess) ptrs.push_back(*p);
-		return e;
-	}
-};
-
-#define RMD_HIP(ctx, call)                                                                            \
-	do {                                                                                              \
-		hipError_t e_ = (call);                                                                       \
-		if (e_ != hipSuccess) return rmd::fail(ctx, RMD_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-	} while (0)
-
 } // namespace
 
 static rmd_status grid_build_from_mesh_gpu_impl(rmd_context *ctx, const double *tri_pos, const double *tri_nrm, uint64_t n_tris, rmd_grid_build **out) {
@@ -191,20 +173,21 @@ static rmd_status grid_build_from_mesh_gpu_impl(rmd_context *ctx, const double *
 
 	RMD_HIP(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = ctx->stream;
-	Dev dev;
-	double *d_pos = nullptr;
-	RMD_HIP(ctx, dev.alloc((void **)&d_pos, n_tris * 9 * sizeof(double)));
+	// (freed whichever way this function leaves; every size is at least one element — n_tris, n_cells >= 1 — but the mapping table's, which the device computes)
+	rmd::DeviceBuffer pos_b, count_b, cells_b, sums_b, total_b, err_b, map_b;
+	RMD_HIP(ctx, pos_b.alloc(n_tris * 9 * sizeof(double)));
+	double *d_pos = pos_b.as<double>();
 	RMD_HIP(ctx, hipMemcpyAsync(d_pos, tri_pos, n_tris * 9 * sizeof(double), hipMemcpyHostToDevice, st));
 	const unsigned long long n_cells = dims.n_cells;
 	const unsigned tri_blocks = (unsigned)((n_tris + 255) / 256), scan_blocks = (unsigned)((n_cells + 1023) / 1024);
-	unsigned *d_count = nullptr, *d_cells = nullptr, *d_map = nullptr;
-	unsigned long long *d_sums = nullptr, *d_total = nullptr;
-	int *d_err = nullptr;
-	RMD_HIP(ctx, dev.alloc((void **)&d_count, n_cells * sizeof(unsigned)));
-	RMD_HIP(ctx, dev.alloc((void **)&d_cells, n_cells * sizeof(unsigned)));
-	RMD_HIP(ctx, dev.alloc((void **)&d_sums, scan_blocks * sizeof(unsigned long long)));
-	RMD_HIP(ctx, dev.alloc((void **)&d_total, sizeof(unsigned long long)));
-	RMD_HIP(ctx, dev.alloc((void **)&d_err, sizeof(int)));
+	RMD_HIP(ctx, count_b.alloc(n_cells * sizeof(unsigned)));
+	RMD_HIP(ctx, cells_b.alloc(n_cells * sizeof(unsigned)));
+	RMD_HIP(ctx, sums_b.alloc(scan_blocks * sizeof(unsigned long long)));
+	RMD_HIP(ctx, total_b.alloc(sizeof(unsigned long long)));
+	RMD_HIP(ctx, err_b.alloc(sizeof(int)));
+	unsigned *d_count = count_b.as<unsigned>(), *d_cells = cells_b.as<unsigned>();
+	unsigned long long *d_sums = sums_b.as<unsigned long long>(), *d_total = total_b.as<unsigned long long>();
+	int *d_err = err_b.as<int>();
 	RMD_HIP(ctx, hipMemsetAsync(d_count, 0, n_cells * sizeof(unsigned), st));
 	RMD_HIP(ctx, hipMemsetAsync(d_err, 0, sizeof(int), st));
 	hipLaunchKernelGGL(scatter_kernel, dim3(tri_blocks), dim3(256), 0, st, 0, d_pos, (unsigned long long)n_tris, dims, d_count, (const unsigned *)nullptr,
@@ -220,7 +203,8 @@ static rmd_status grid_build_from_mesh_gpu_impl(rmd_context *ctx, const double *
 	if (err == 1) return rmd::fail(ctx, RMD_ERR_GRID_INDEX, "cell bound does not fit usize (reference: \"Failed to cast cell bounds to usize\", acc_grid.rs:44-51)");
 	if (err == 2) return rmd::fail(ctx, RMD_ERR_GRID_INDEX, "cell index past the cell array (reference panics at acc_grid.rs:61)");
 	if (total > 0xFFFFFFFFull) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, "mapping_table exceeds 2^32 entries");
-	RMD_HIP(ctx, dev.alloc((void **)&d_map, total * sizeof(unsigned)));
+	RMD_HIP(ctx, map_b.alloc(total ? total * sizeof(unsigned) : 16)); // (a 0-byte table allocates 16 bytes, as in rmd_scene_create)
+	unsigned *d_map = map_b.as<unsigned>();
 	hipLaunchKernelGGL(scan_write, dim3(scan_blocks), dim3(256), 0, st, d_count, n_cells, d_sums, d_cells, d_map);
 	RMD_HIP(ctx, hipMemsetAsync(d_count, 0, n_cells * sizeof(unsigned), st)); // reused as the per-cell fill cursor
 	hipLaunchKernelGGL(scatter_kernel, dim3(tri_blocks), dim3(256), 0, st, 1, d_pos, (unsigned long long)n_tris, dims, d_count, d_cells, d_map, d_err);

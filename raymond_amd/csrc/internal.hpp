@@ -1,4 +1,4 @@
-// Library-internal declarations shared by api.cpp, probe.cpp, comm.cpp and grid_build.cpp.
+// Library-internal declarations shared by api.cpp, probe.cpp, comm.cpp, grid_build.cpp and grid_build_gpu.hip.
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +19,51 @@
 
 #include "device_types.hpp"
 
+// The one mapping of a failed HIP call to a status: returns from the calling function with the call's text and HIP's own.
+#define RMD_HIP(ctx, call)                                                                                      \
+	do {                                                                                                        \
+		hipError_t e_ = (call);                                                                                 \
+		if (e_ != hipSuccess) return rmd::fail(ctx, e_ == hipErrorOutOfMemory ? RMD_ERR_OUT_OF_MEMORY : RMD_ERR_HIP, \
+		                                       std::string(#call) + ": " + hipGetErrorString(e_));              \
+	} while (0)
+
+namespace rmd {
+// Device memory the library holds: one hipMalloc block and its size in bytes, freed when its owner goes — a context, a scene, or the frame of
+// an entry point whichever way it leaves.  Pointers handed to the caller (rmd_framebuffer_alloc, rmd_feature_buffer_alloc) stay raw.
+class DeviceBuffer {
+public:
+	DeviceBuffer() = default;
+	DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr, o.bytes_ = 0; }
+	// (what `o` held replaces this buffer's block only once it exists: the allocate-first order of the sample scratch, api.cpp)
+	DeviceBuffer &operator=(DeviceBuffer &&o) noexcept {
+		if (this != &o) (void)release(), p_ = o.p_, bytes_ = o.bytes_, o.p_ = nullptr, o.bytes_ = 0;
+		return *this;
+	}
+	~DeviceBuffer() { (void)release(); }
+	hipError_t release() {
+		const hipError_t e = p_ ? hipFree(p_) : hipSuccess;
+		p_ = nullptr, bytes_ = 0;
+		return e;
+	}
+	// Free first, then allocate: after a refused allocation the buffer is empty and its size 0, so the next call tries again.
+	hipError_t alloc(size_t bytes) {
+		hipError_t e = release();
+		if (e == hipSuccess) e = hipMalloc(&p_, bytes);
+		if (e == hipSuccess) bytes_ = bytes;
+		else p_ = nullptr;
+		return e;
+	}
+	hipError_t grow(size_t bytes) { return bytes <= bytes_ ? hipSuccess : alloc(bytes); }
+	size_t bytes() const { return bytes_; }
+	template <class T>
+	T *as() const { return static_cast<T *>(p_); }
+
+private:
+	void *p_ = nullptr;
+	size_t bytes_ = 0;
+};
+} // namespace rmd
+
 struct rmd_context {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -29,31 +74,23 @@ struct rmd_context {
 	// cached wave-tile table (device) for the rect list of the previous call
 	std::vector<rmd_tile_rect> cached_rects;
 	uint32_t cached_W = 0, cached_H = 0;
-	rmd::WaveTile *d_wave_tiles = nullptr;
+	rmd::DeviceBuffer wave_tiles; // rmd::WaveTile
 	uint32_t n_wave_tiles = 0;
-	size_t wave_tiles_capacity = 0;
-	// per-sample radiance scratch of split launches (api.cpp: choose_split)
-	double *d_sample_buf = nullptr;
-	size_t sample_buf_bytes = 0;
+	rmd::DeviceBuffer sample_buf; // per-sample radiance scratch of split launches (api.cpp: choose_split)
 	uint32_t wave_slots = 0; // CUs x waves per CU the render kernels can keep resident
 	uint32_t n_cus = 0;
-	size_t hbm_bytes = 0; // totalGlobalMem of the device
-	uint32_t *d_work_counter = nullptr; // next work item of a persistent launch (render_kernel.hpp)
-	unsigned char *d_queue_buf = nullptr; // the resident waves' path queues (render_kernel.hpp: render_wave_queued), allocated at the first launch that uses them
-	size_t queue_buf_bytes = 0;
-	uint32_t *d_tile_done = nullptr;    // split launches: finished waves per wave tile (render_kernel.hpp)
-	size_t tile_done_words = 0;
-	unsigned long long *d_debug_counters = nullptr; // walk diagnostics (DIAG builds, RMD_DEBUG=8|16)
+	rmd::DeviceBuffer work_counter;   // next work item of a persistent launch (render_kernel.hpp)
+	rmd::DeviceBuffer queue_buf;      // the resident waves' path queues (render_kernel.hpp: render_wave_queued), allocated at the first launch that uses them
+	rmd::DeviceBuffer tile_done;      // split launches: finished waves per wave tile, a uint32 each (render_kernel.hpp)
+	rmd::DeviceBuffer debug_counters; // walk diagnostics (DIAG builds, RMD_DEBUG=8|16)
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound
 	// writes here; the host looks after every wait for the stream (api.cpp: check_fault) — a plain host load, no copy
 	uint32_t *h_fault = nullptr, *d_fault = nullptr;
 	// tile transfers (rmd_framebuffer_{download,upload}_tiles): two staging slots — packed pixels, rect table, prefix table on the device — so that a
 	// second download can be packed while the first is still being copied; the copy stream; per slot the event its copy ends with
 	struct TransferSlot {
-		double *d_packed = nullptr;
-		size_t packed_bytes = 0;
-		void *d_table = nullptr; // n_rects x (rmd_tile_rect, uint64 first)
-		size_t table_bytes = 0;
+		rmd::DeviceBuffer packed; // doubles
+		rmd::DeviceBuffer table;  // n_rects x (rmd_tile_rect, uint64 first)
 		hipEvent_t packed_ready = nullptr, copied = nullptr;
 		bool in_flight = false;
 		std::vector<unsigned char> h_table; // the host copy of the table stays alive until its upload has completed
@@ -65,6 +102,8 @@ struct rmd_context {
 	int64_t tunable[RMD_TUNE_COUNT] = {};
 	uint32_t debug_flags = 0; // RMD_DEBUG, honoured by DIAG builds only
 	rmd_launch_info last_launch = {}; // rmd_last_launch_info
+	// Waits for both streams, then destroys them, the events and the fault words; the buffers above are freed after that (api.cpp).
+	~rmd_context();
 };
 
 struct rmd_scene {
@@ -78,7 +117,8 @@ struct rmd_scene {
 	bool regular = true; // every parameter the kernel reads is finite and inside the class for which ending zero-throughput paths is exact (api.cpp: rmd_scene_create)
 	rmd::DevObject *d_objects = nullptr;
 	rmd::DevGrid *d_grids = nullptr;
-	std::vector<void *> owned; // every device allocation of this scene
+	std::vector<rmd::DeviceBuffer> owned; // every device allocation of this scene
+	~rmd_scene(); // waits for the context's stream before they are freed (api.cpp)
 };
 #endif
 
@@ -198,5 +238,6 @@ rmd_status guarded(rmd_context *ctx, const char *what, F &&body) noexcept {
 #ifdef RMD_WITH_HIP
 // After a wait for the context's stream: RMD_ERR_DEVICE_FAULT (and the fault words cleared) when a wave of a launch reported one, else RMD_OK.
 rmd_status check_fault(rmd_context *ctx);
+RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st);
 #endif
 } // namespace rmd

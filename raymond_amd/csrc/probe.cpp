@@ -8,24 +8,7 @@
 #include "internal.hpp"
 #include "launch.hpp"
 
-namespace rmd {
-RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st);
-}
-
 namespace {
-
-#define RMD_HIP(ctx, call)                                                                            \
-	do {                                                                                              \
-		hipError_t e_ = (call);                                                                       \
-		if (e_ != hipSuccess) return rmd::fail(ctx, RMD_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-	} while (0)
-
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() {
-		if (p) (void)hipFree(p);
-	}
-};
 
 struct Column {
 	const double *src;
@@ -52,16 +35,16 @@ rmd_status run_probe(rmd_context *ctx, int op, size_t n, const std::vector<Colum
 	}
 	out.assign(n * out_stride, 0.0);
 	if (n == 0) return RMD_OK;
-	DevBuf din, dout;
-	RMD_HIP(ctx, hipMalloc(&din.p, in.size() * sizeof(double)));
-	RMD_HIP(ctx, hipMalloc(&dout.p, out.size() * sizeof(double)));
-	RMD_HIP(ctx, hipMemcpyAsync(din.p, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	RMD_HIP(ctx, hipMemsetAsync(dout.p, 0, out.size() * sizeof(double), ctx->stream));
+	rmd::DeviceBuffer din, dout;
+	RMD_HIP(ctx, din.alloc(in.size() * sizeof(double)));
+	RMD_HIP(ctx, dout.alloc(out.size() * sizeof(double)));
+	RMD_HIP(ctx, hipMemcpyAsync(din.as<void>(), in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	RMD_HIP(ctx, hipMemsetAsync(dout.as<void>(), 0, out.size() * sizeof(double), ctx->stream));
 	rmd::RenderParams P;
 	std::memset(&P, 0, sizeof(P));
 	if (params) P = *params;
-	RMD_HIP(ctx, rmd::launch_probe(ctx->stream, op, (uint32_t)n, (const double *)din.p, in_stride, (double *)dout.p, out_stride, P));
-	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, rmd::launch_probe(ctx->stream, op, (uint32_t)n, din.as<const double>(), in_stride, dout.as<double>(), out_stride, P));
+	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.as<void>(), out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return RMD_OK;
 }
@@ -201,14 +184,14 @@ static rmd_status scene_probe(rmd_context *ctx, const rmd_scene *scene, int mode
 	if (mode == 1 && g >= scene->n_grids) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: grid index out of range");
 	RMD_HIP(ctx, hipSetDevice(ctx->device));
 	if (n == 0) return RMD_OK;
-	DevBuf din, dout;
-	RMD_HIP(ctx, hipMalloc(&din.p, n * 6 * sizeof(double)));
-	RMD_HIP(ctx, hipMalloc(&dout.p, n * 3 * sizeof(double)));
-	RMD_HIP(ctx, hipMemcpyAsync(din.p, ray6, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	rmd::DeviceBuffer din, dout;
+	RMD_HIP(ctx, din.alloc(n * 6 * sizeof(double)));
+	RMD_HIP(ctx, dout.alloc(n * 3 * sizeof(double)));
+	RMD_HIP(ctx, hipMemcpyAsync(din.as<void>(), ray6, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
 	RMD_HIP(ctx, rmd::launch_probe_scene(ctx->stream, mode, g, (uint32_t)n, scene->d_objects, scene->n_objects, scene->d_grids,
-	                                     scene->n_grids, scene->mask_words_total, scene->axis_pairs, (const double *)din.p, (double *)dout.p));
+	                                     scene->n_grids, scene->mask_words_total, scene->axis_pairs, din.as<const double>(), dout.as<double>()));
 	std::vector<double> out(n * 3);
-	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.as<void>(), out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	for (size_t i = 0; i < n; i++) a[i] = (int32_t)out[3 * i], t[i] = out[3 * i + 1], b[i] = (uint32_t)out[3 * i + 2];
 	return RMD_OK;
@@ -231,19 +214,19 @@ rmd_status rmd_probe_grid_intersect_deep(rmd_context *ctx, const rmd_scene *scen
 		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: rays_per_wave must be a multiple of 64 up to 2^20, the cuts at most 255, n below 2^31");
 	RMD_HIP(ctx, hipSetDevice(ctx->device));
 	if (n == 0) return RMD_OK;
-	DevBuf din, dout, dstuck;
-	RMD_HIP(ctx, hipMalloc(&din.p, n * 6 * sizeof(double)));
-	RMD_HIP(ctx, hipMalloc(&dout.p, n * 3 * sizeof(double)));
-	RMD_HIP(ctx, hipMalloc(&dstuck.p, sizeof(uint32_t)));
-	RMD_HIP(ctx, hipMemcpyAsync(din.p, ray6, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-	RMD_HIP(ctx, hipMemsetAsync(dout.p, 0, n * 3 * sizeof(double), ctx->stream));
-	RMD_HIP(ctx, hipMemsetAsync(dstuck.p, 0, sizeof(uint32_t), ctx->stream));
-	RMD_HIP(ctx, rmd::launch_probe_grid_deep(ctx->stream, g, (uint32_t)n, scene->d_grids, scene->n_grids, scene->mask_words_total, (const double *)din.p, cut_lanes,
-	                                         cut_round, rays_per_wave, scene->walk_steps_bound, (double *)dout.p, (uint32_t *)dstuck.p));
+	rmd::DeviceBuffer din, dout, dstuck;
+	RMD_HIP(ctx, din.alloc(n * 6 * sizeof(double)));
+	RMD_HIP(ctx, dout.alloc(n * 3 * sizeof(double)));
+	RMD_HIP(ctx, dstuck.alloc(sizeof(uint32_t)));
+	RMD_HIP(ctx, hipMemcpyAsync(din.as<void>(), ray6, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+	RMD_HIP(ctx, hipMemsetAsync(dout.as<void>(), 0, n * 3 * sizeof(double), ctx->stream));
+	RMD_HIP(ctx, hipMemsetAsync(dstuck.as<void>(), 0, sizeof(uint32_t), ctx->stream));
+	RMD_HIP(ctx, rmd::launch_probe_grid_deep(ctx->stream, g, (uint32_t)n, scene->d_grids, scene->n_grids, scene->mask_words_total, din.as<const double>(), cut_lanes,
+	                                         cut_round, rays_per_wave, scene->walk_steps_bound, dout.as<double>(), dstuck.as<uint32_t>()));
 	std::vector<double> out(n * 3);
 	uint32_t stuck = 0;
-	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	RMD_HIP(ctx, hipMemcpyAsync(&stuck, dstuck.p, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipMemcpyAsync(out.data(), dout.as<void>(), out.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipMemcpyAsync(&stuck, dstuck.as<void>(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	if (stuck) return rmd::fail(ctx, RMD_ERR_DEVICE_FAULT, "probe: a wave of the DEEP walk reached its bound of walk calls with rays unfinished (it cannot: an internal fault)");
 	for (size_t i = 0; i < n; i++) hit[i] = (int32_t)out[3 * i], t[i] = out[3 * i + 1], tri[i] = (uint32_t)out[3 * i + 2];
@@ -304,26 +287,26 @@ rmd_status rmd_probe_trace_samples(rmd_context *ctx, const rmd_scene *scene, con
 	std::vector<rmd::ListWork> list(n);
 	for (size_t i = 0; i < n; i++) list[i] = rmd::ListWork{xy2[2 * i], xy2[2 * i + 1], sample[i], 0u};
 	size_t n_pad = (n + 63) / 64 * 64;
-	DevBuf dl, drgb, dpo, dps;
-	RMD_HIP(ctx, hipMalloc(&dl.p, n * sizeof(rmd::ListWork)));
-	RMD_HIP(ctx, hipMalloc(&drgb.p, n_pad * 3 * sizeof(double)));
-	RMD_HIP(ctx, hipMemcpyAsync(dl.p, list.data(), n * sizeof(rmd::ListWork), hipMemcpyHostToDevice, ctx->stream));
+	rmd::DeviceBuffer dl, drgb, dpo, dps;
+	RMD_HIP(ctx, dl.alloc(n * sizeof(rmd::ListWork)));
+	RMD_HIP(ctx, drgb.alloc(n_pad * 3 * sizeof(double)));
+	RMD_HIP(ctx, hipMemcpyAsync(dl.as<void>(), list.data(), n * sizeof(rmd::ListWork), hipMemcpyHostToDevice, ctx->stream));
 	if (path_obj) {
-		RMD_HIP(ctx, hipMalloc(&dpo.p, n_pad * RMD_PATH_STRIDE * sizeof(int32_t)));
-		RMD_HIP(ctx, hipMalloc(&dps.p, n_pad * RMD_PATH_STRIDE * sizeof(uint32_t)));
+		RMD_HIP(ctx, dpo.alloc(n_pad * RMD_PATH_STRIDE * sizeof(int32_t)));
+		RMD_HIP(ctx, dps.alloc(n_pad * RMD_PATH_STRIDE * sizeof(uint32_t)));
 		std::vector<int32_t> init(n_pad * RMD_PATH_STRIDE, -2);
-		RMD_HIP(ctx, hipMemcpyAsync(dpo.p, init.data(), init.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemsetAsync(dps.p, 0, n_pad * RMD_PATH_STRIDE * sizeof(uint32_t), ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(dpo.as<void>(), init.data(), init.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemsetAsync(dps.as<void>(), 0, n_pad * RMD_PATH_STRIDE * sizeof(uint32_t), ctx->stream));
 		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	rmd::RenderParams P = rmd::make_params(ctx, scene, cam, settings);
 	P.n_work = (uint32_t)n;
-	RMD_HIP(ctx, rmd::launch_render_list(ctx->stream, P, scene->d_objects, scene->d_grids, (const rmd::ListWork *)dl.p, (double *)drgb.p,
-	                                     (int32_t *)dpo.p, (uint32_t *)dps.p));
-	RMD_HIP(ctx, hipMemcpyAsync(rgb_out, drgb.p, n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, rmd::launch_render_list(ctx->stream, P, scene->d_objects, scene->d_grids, dl.as<const rmd::ListWork>(), drgb.as<double>(),
+	                                     dpo.as<int32_t>(), dps.as<uint32_t>()));
+	RMD_HIP(ctx, hipMemcpyAsync(rgb_out, drgb.as<void>(), n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
 	if (path_obj) {
-		RMD_HIP(ctx, hipMemcpyAsync(path_obj, dpo.p, n * RMD_PATH_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(path_sub, dps.p, n * RMD_PATH_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(path_obj, dpo.as<void>(), n * RMD_PATH_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(path_sub, dps.as<void>(), n * RMD_PATH_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 	}
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return RMD_OK;
