@@ -248,7 +248,10 @@ enum {
 	                              2 = always                                                                                                  */
 	RMD_TUNE_AXIS_PAIRS = 8,   /* RMD_AXIS_PAIRS: read by rmd_scene_create — pairs of opposite planes whose normals are exactly +e_k / -e_k (the walls of an
 	                              axis-aligned room) tested with one component of the ray: 0 = the library's choice (yes, in scenes of regular
-	                              parameters), 1 = never (every pair takes the general test: same samples, bit for bit)                      */
+	                              parameters — and, in such a scene without a grid, a launch without the thin lens gives the generation trips of the
+	                              spheres kernel their own candidate sets: the spheres and the one pair their tile's primary rays can hit),
+	                              1 = never (every pair takes the general test, no candidate sets), 2 = the pairs as for 0, no candidate sets.
+	                              Same samples, bit for bit, whatever the value                                                              */
 	RMD_TUNE_PATH_QUEUES = 9,  /* RMD_PATH_QUEUES: persistent split launches of scenes with grids keep their paths in queues in device memory — ray
 	                              compaction between bounces: a wave's trips are 64 new samples, 64 parked hits or one grid walk for 64 parked rays
 	                              (rmd_launch_info.queued): 0 = the library's choice (yes), 1 = never (a lane keeps its path: same samples, bit for bit) */

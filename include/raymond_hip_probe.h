@@ -81,6 +81,15 @@ rmd_status rmd_probe_triangle_sphere(size_t n, const double *pos9, double *out5)
  * chooses the allowance: the triangle's own, or a grid's largest); pass[i] = the pre-test lets the pair through, hit[i] / t[i] = the reference's test.
  * A pair with hit = 1 and pass = 0 would be a silently missed hit: tests/test_gpu_reference_pins.py asserts there is none among the adversarial
  * pairs of tests/test_pretest_allowance.py. */
+/* Host only (no device needed): what the generation trips of the role-sorted spheres kernel visit for the primary rays of each 8x8 wave tile
+ * (raymond_amd/csrc/primary_candidates.hpp — the function the kernel itself evaluates once per work item).  The scene is given as rmd_scene_create
+ * would get it (objects, the number of grids, the value of RMD_TUNE_AXIS_PAIRS), the launch by its camera and settings; tiles4 = x0, y0, w, h per
+ * tile (w, h in 1 .. 8).  launch3 = the launch's own visit mask (objects 0 .. 63), its axis pairs (three 10-bit fields: index + 1 of the later
+ * plane of the pair of axis k, 0 = none) and whether the candidate sets are on for this launch; out2 = per tile the visit mask and the axis
+ * pairs of its generation trips — the launch's own values when the sets are off.  tests/test_primary_candidates.py holds every object the
+ * predicate drops to the oracle's primary rays. */
+rmd_status rmd_probe_primary_candidates(const rmd_camera *cam, const rmd_settings *settings, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids,
+                                        int64_t axis_pairs_tunable, size_t n_tiles, const uint32_t *tiles4, uint64_t *launch3, uint64_t *out2);
 /* Host only (no device needed): the form of a render launch as launch_render chooses it (raymond_amd/csrc/launch.hpp: LaunchPlan).  mode 0 = tiles
  * (direct), 1 = tiles buffered (split), 2 = list; grid = 1: the grid instantiation.  Per entry in5 = n_objects, mask_words_total, flags (1 = path
  * queues attached, 2 = persistence asked for — CUs and a work counter given —, 4 = chain_items, 8 = the squares asked for), n_waves, n_cus;

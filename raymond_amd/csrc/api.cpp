@@ -182,6 +182,15 @@ rmd_status check_fault(rmd_context *ctx) {
 	                "; the launch was cut short and the framebuffer it wrote to is not valid");
 }
 
+// The launch's half of the conditions under which the generation trips get candidate sets of their own (primary_candidates.hpp): no thin lens
+// and a finite camera; the scene's half — regular, no grid, not switched off — is rmd_scene::primary_cull.
+bool primary_cull_allowed(const RenderParams &P) {
+	CullCamera c;
+	for (int a = 0; a < 3; a++) c.pos[a] = P.cam_pos[a];
+	c.width = P.width, c.height = P.height, c.aspect = P.aspect, c.tan_half_fov = P.tan_half_fov;
+	return P.use_dof == 0u && cull_camera_ok(c);
+}
+
 // generate_primary_ray's loop-invariant terms (src/trace.rs:323-330), evaluated with the host libm
 RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st) {
 	const double PI = 3.14159265358979323846;
@@ -211,6 +220,7 @@ RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const r
 	P.shade_last_depth = (scene && !scene->regular) ? 1u : 0u;
 	P.axis_pairs = scene ? scene->axis_pairs : 0u;
 	P.visit_mask = scene ? scene->visit_mask : ~0ull, P.grid_mask = scene ? scene->grid_mask : ~0ull;
+	P.primary_cull = (scene && scene->primary_cull && rmd::primary_cull_allowed(P)) ? 1u : 0u;
 	P.fault = ctx ? ctx->d_fault : nullptr;
 	P.walk_batch = rmd::kWalkBatchDefault;
 	if (ctx && ctx->tunable[RMD_TUNE_WALK_BATCH] > 0) P.walk_batch = (uint32_t)ctx->tunable[RMD_TUNE_WALK_BATCH]; // any value gives the same image
@@ -370,11 +380,12 @@ static rmd_status derive_grid_tables(rmd_context *ctx, const rmd_grid_desc &g, G
 	return RMD_OK;
 }
 
-static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects, uint32_t n_objects, const rmd_grid_desc *grids, uint32_t n_grids,
-                                    rmd_scene **out) {
-	if (rmd_status s = bind(ctx)) return s;
-	if (!out || (n_objects && !objects) || (n_grids && !grids)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_scene_create: null argument");
-	std::vector<rmd::DevObject> hobj(n_objects);
+// What rmd_scene_create derives from the caller's objects on the host, before anything is uploaded: the device records, whether the scene's
+// parameters are regular, the pairs of opposite planes, the axis rule's walls and the object loops' turns.  A function of its own because the
+// host-only probe rmd_probe_primary_candidates (probe.cpp) needs exactly what a scene would hold, without a device.
+extern "C++" rmd_status rmd::derive_scene_objects(rmd_context *ctx, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids, int64_t axis_pairs_tunable, rmd::SceneObjects &out) {
+	std::vector<rmd::DevObject> &hobj = out.objs;
+	hobj.assign(n_objects, rmd::DevObject{});
 	bool regular = true;
 	for (uint32_t i = 0; i < n_objects; i++) {
 		const rmd_object &o = objects[i];
@@ -430,7 +441,7 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 	// ... and a pair whose normals are exactly +e_k and -e_k — the walls of an axis-aligned room — is tested with one component of the ray instead of
 	// three dot products (scene_split.hpp: axis_pairs_visit has the argument for "same bits"): one pair per axis, in scenes of regular parameters
 	uint32_t axis_pairs = 0;
-	for (uint32_t j = 0; j < n_objects && j < 1023u && regular && ctx->tunable[RMD_TUNE_AXIS_PAIRS] != 1; j++) {
+	for (uint32_t j = 0; j < n_objects && j < 1023u && regular && axis_pairs_tunable != 1; j++) {
 		if (hobj[j].geometry_kind != RMD_GEOM_PLANE || hobj[j].pair_info == 0u || (hobj[j].pair_info & rmd::kPairTestedAtPartner)) continue;
 		const uint32_t i = hobj[j].pair_info - 1u;
 		int k = -1, nonzero = 0;
@@ -444,18 +455,10 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 		hobj[j].pair_info = rmd::kPairTestedAtPartner | rmd::kPairAxis | i; // the object loops pass both planes by ("tested at its partner's turn"):
 		hobj[i].pair_info |= rmd::kPairAxis;                                 // their turn is axis_pairs_visit's, ahead of the loop
 	}
-	// (the scene under construction: an early return or an exception — std::bad_alloc from one of the host-side tables: a 256^3 grid needs a
-	// gigabyte for its cell entries alone — releases what has been uploaded)
-	auto sc = std::make_unique<rmd_scene>();
-	sc->ctx = ctx, sc->n_objects = n_objects, sc->n_grids = n_grids, sc->regular = regular;
-	sc->axis_pairs = axis_pairs;
-	// the object loops' turns (device_types.hpp: RenderParams::visit_mask): a plane tested at its partner's turn or by the axis rule has none
-	// the axis pairs as the axis rule reads them, behind the table's last record (device_types.hpp: AxisWalls)
-	rmd::DevObject walls_block;
-	std::memset(&walls_block, 0, sizeof(walls_block));
+	// the axis pairs as the axis rule reads them (device_types.hpp: AxisWalls)
 	{
-		rmd::AxisWalls walls[3];
-		std::memset(walls, 0, sizeof(walls));
+		rmd::AxisWalls *walls = out.walls;
+		std::memset(walls, 0, 3 * sizeof(rmd::AxisWalls));
 		for (int k = 0; k < 3; k++) {
 			const uint32_t f = (axis_pairs >> (10 * k)) & 1023u;
 			if (f == 0u) continue;
@@ -464,13 +467,38 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 			walls[k].o_plus = e_plus ? hobj[i].origin[k] : hobj[j].origin[k], walls[k].o_minus = e_plus ? hobj[j].origin[k] : hobj[i].origin[k];
 			walls[k].idx_plus = e_plus ? i : j, walls[k].idx_minus = e_plus ? j : i;
 		}
-		std::memcpy(&walls_block, walls, sizeof(walls));
 	}
-	sc->visit_mask = 0ull, sc->grid_mask = 0ull;
+	// the object loops' turns (device_types.hpp: RenderParams::visit_mask): a plane tested at its partner's turn or by the axis rule has none
+	out.visit_mask = 0ull, out.grid_mask = 0ull;
 	for (uint32_t i = 0; i < n_objects && i < 64u; i++) {
-		if (!(hobj[i].geometry_kind == RMD_GEOM_PLANE && (hobj[i].pair_info & rmd::kPairTestedAtPartner))) sc->visit_mask |= 1ull << i;
-		if (hobj[i].geometry_kind == RMD_GEOM_GRID) sc->grid_mask |= 1ull << i;
+		if (!(hobj[i].geometry_kind == RMD_GEOM_PLANE && (hobj[i].pair_info & rmd::kPairTestedAtPartner))) out.visit_mask |= 1ull << i;
+		if (hobj[i].geometry_kind == RMD_GEOM_GRID) out.grid_mask |= 1ull << i;
 	}
+	out.regular = regular, out.axis_pairs = axis_pairs;
+	return RMD_OK;
+}
+
+static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects, uint32_t n_objects, const rmd_grid_desc *grids, uint32_t n_grids,
+                                    rmd_scene **out) {
+	if (rmd_status s = bind(ctx)) return s;
+	if (!out || (n_objects && !objects) || (n_grids && !grids)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_scene_create: null argument");
+	rmd::SceneObjects derived;
+	if (rmd_status s = rmd::derive_scene_objects(ctx, objects, n_objects, n_grids, ctx->tunable[RMD_TUNE_AXIS_PAIRS], derived)) return s;
+	std::vector<rmd::DevObject> &hobj = derived.objs;
+	const bool regular = derived.regular;
+	const uint32_t axis_pairs = derived.axis_pairs;
+	// (the scene under construction: an early return or an exception — std::bad_alloc from one of the host-side tables: a 256^3 grid needs a
+	// gigabyte for its cell entries alone — releases what has been uploaded)
+	auto sc = std::make_unique<rmd_scene>();
+	sc->ctx = ctx, sc->n_objects = n_objects, sc->n_grids = n_grids, sc->regular = regular;
+	sc->axis_pairs = axis_pairs;
+	// the axis pairs as the axis rule reads them, behind the table's last record (device_types.hpp: AxisWalls)
+	rmd::DevObject walls_block;
+	std::memset(&walls_block, 0, sizeof(walls_block));
+	std::memcpy(&walls_block, derived.walls, sizeof(derived.walls));
+	sc->visit_mask = derived.visit_mask, sc->grid_mask = derived.grid_mask;
+	// the generation trips' own candidate sets (primary_candidates.hpp): a regular scene without a grid, unless RMD_TUNE_AXIS_PAIRS says 1 or 2
+	sc->primary_cull = regular && n_grids == 0u && ctx->tunable[RMD_TUNE_AXIS_PAIRS] == 0;
 	for (uint32_t i = 0; i < n_objects; i++) sc->n_grid_objects += objects[i].geometry_kind == RMD_GEOM_GRID ? 1u : 0u;
 	auto upload = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
 		*dst = nullptr;
@@ -807,6 +835,9 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 			             h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[8], h[9], h[10], h[11], h[12], h[7], h[13], h[14], h[15]);
 		if ((P.debug_flags & 16u) == 0u)
 			std::fprintf(stderr, "[rmd debug] sphere pre-test: pairs passed=%llu full chunks=%llu | pairs dropped that pass the reference's test (flag 64; must be 0)=%llu\n", h[17], h[18], h[16]);
+		if ((P.debug_flags & 16u) == 0u && (P.debug_flags & 512u))
+			std::fprintf(stderr, "[rmd debug] primary candidates: lanes checked=%llu sphere turns left out=%llu trips with two axis pairs left out=%llu | cleared spheres that register a hit (must be 0)=%llu closest hits that differ from the full visit's (must be 0)=%llu\n",
+			             h[32], h[35], h[36], h[33], h[34]);
 		if ((P.debug_flags & 16u) == 0u && ctx->last_launch.queued)
 			std::fprintf(stderr, "[rmd debug] path queues: rays pushed=%llu (of them walks put aside=%llu) rays held in their lanes=%llu hits pushed=%llu hits held in their lanes=%llu\n", h[19], h[22], h[23], h[20], h[21]);
 	}

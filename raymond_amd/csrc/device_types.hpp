@@ -126,7 +126,8 @@ struct RenderParams {
 	                                    // NaN with finite inputs (roughness 0: 0 / 0 in geometry_schlick_ggx) and the reference's sample NaN x 0 = NaN
 	uint32_t chain_items;               // 1: persistent waves of a split launch of a scene with grids draw their next work item while the last paths of the current one
 	                                    // finish (render_kernel.hpp: render_wave, CHAIN) — launches of few samples per pixel, where an item's drain is a fifth of it
-	uint32_t _pad1;
+	uint32_t primary_cull;              // 1: the role-sorted spheres kernel gives every work item's generation trips their own visit mask and axis pairs — what the
+	                                    // tile's primary rays can hit (primary_candidates.hpp has the conditions and the argument; api.cpp: make_params sets it)
 	uint32_t buffered;                  // 1: the tiles-buffered instantiation (pooled (pixel, sample) hand-out, per-sample scratch, ordered sum) — also with split_k = 1
 	uint32_t axis_pairs;                // three 10-bit fields, one per axis k: index + 1 of the later plane of THE pair of opposite planes with normals +-e_k that is
 	uint32_t _pad2;                     //   tested ahead of the object loop (kObjAxisPair), 0 = none

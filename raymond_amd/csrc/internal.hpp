@@ -18,6 +18,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "device_types.hpp"
+#include "primary_candidates.hpp"
 
 // The one mapping of a failed HIP call to a status: returns from the calling function with the call's text and HIP's own.
 #define RMD_HIP(ctx, call)                                                                                      \
@@ -114,6 +115,7 @@ struct rmd_scene {
 	uint32_t axis_pairs = 0; // RenderParams::axis_pairs
 	unsigned long long visit_mask = ~0ull, grid_mask = ~0ull; // RenderParams::visit_mask / grid_mask
 	uint32_t walk_steps_bound = 0; // RenderParams::walk_steps_bound
+	bool primary_cull = false; // the scene's half of RenderParams::primary_cull: regular, no grid, RMD_TUNE_AXIS_PAIRS = 0 when it was created
 	bool regular = true; // every parameter the kernel reads is finite and inside the class for which ending zero-throughput paths is exact (api.cpp: rmd_scene_create)
 	rmd::DevObject *d_objects = nullptr;
 	rmd::DevGrid *d_grids = nullptr;
@@ -239,5 +241,15 @@ rmd_status guarded(rmd_context *ctx, const char *what, F &&body) noexcept {
 // After a wait for the context's stream: RMD_ERR_DEVICE_FAULT (and the fault words cleared) when a wave of a launch reported one, else RMD_OK.
 rmd_status check_fault(rmd_context *ctx);
 RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st);
+bool primary_cull_allowed(const RenderParams &P);
+// The host half of rmd_scene_create (api.cpp), also for the host-only probe of the primary rays' candidate sets (probe.cpp)
+struct SceneObjects {
+	std::vector<DevObject> objs;
+	bool regular = true;
+	uint32_t axis_pairs = 0;
+	AxisWalls walls[3] = {};
+	unsigned long long visit_mask = 0ull, grid_mask = 0ull;
+};
+rmd_status derive_scene_objects(rmd_context *ctx, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids, int64_t axis_pairs_tunable, SceneObjects &out);
 #endif
 } // namespace rmd

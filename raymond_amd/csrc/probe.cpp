@@ -243,6 +243,36 @@ rmd_status rmd_probe_triangle_sphere(size_t n, const double *pos9, double *out5)
 	return RMD_OK;
 }
 
+rmd_status rmd_probe_primary_candidates(const rmd_camera *cam, const rmd_settings *settings, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids,
+                                        int64_t axis_pairs_tunable, size_t n_tiles, const uint32_t *tiles4, uint64_t *launch3, uint64_t *out2) {
+	if (!cam || !settings || (n_objects && !objects) || !launch3 || (n_tiles != 0 && (!tiles4 || !out2))) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	return rmd::guarded(nullptr, "rmd_probe_primary_candidates", [&]() -> rmd_status {
+		rmd::SceneObjects sc;
+		if (rmd_status s = rmd::derive_scene_objects(nullptr, objects, n_objects, n_grids, axis_pairs_tunable, sc)) return s;
+		// (the launch's parameters as make_params makes them; the scene's half of the switch as rmd_scene_create sets it)
+		const rmd::RenderParams P = rmd::make_params(nullptr, nullptr, cam, settings);
+		const bool on = sc.regular && n_grids == 0u && axis_pairs_tunable == 0 && rmd::primary_cull_allowed(P);
+		launch3[0] = sc.visit_mask, launch3[1] = sc.axis_pairs, launch3[2] = on ? 1u : 0u;
+		rmd::CullCamera cc;
+		for (int a = 0; a < 3; a++) cc.pos[a] = P.cam_pos[a];
+		cc.width = P.width, cc.height = P.height, cc.aspect = P.aspect, cc.tan_half_fov = P.tan_half_fov;
+		for (size_t i = 0; i < n_tiles; i++) {
+			const uint32_t *t = tiles4 + i * 4;
+			uint64_t visit = sc.visit_mask;
+			uint32_t pairs = sc.axis_pairs;
+			if (on) {
+				if (t[2] == 0u || t[2] > 8u || t[3] == 0u || t[3] > 8u || t[0] > 65535u || t[1] > 65535u) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: a wave tile is 1..8 pixels a side");
+				const rmd::TileCone cone = rmd::primary_tile_cone(cc, t[0], t[1], t[2], t[3]);
+				for (uint32_t j = 0; j < n_objects && j < 64u; j++)
+					if (sc.objs[j].geometry_kind == 1u && rmd::primary_sphere_cleared(cone, cc, sc.objs[j].origin, sc.objs[j].radius)) visit &= ~(1ull << j);
+				pairs = rmd::primary_pairs_kept(cone, cc, sc.walls, sc.axis_pairs);
+			}
+			out2[i * 2] = visit, out2[i * 2 + 1] = pairs;
+		}
+		return RMD_OK;
+	});
+}
+
 rmd_status rmd_probe_launch_plan(uint32_t mode, uint32_t grid, size_t n, const uint32_t *in5, uint64_t *out8) {
 	if (mode > 2u || grid > 1u || (n != 0 && (!in5 || !out8))) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
 	for (size_t i = 0; i < n; i++) {

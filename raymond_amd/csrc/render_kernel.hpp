@@ -6,6 +6,7 @@
 #include "device_core.hpp"
 #include "grid_walk.hpp"
 #include "launch.hpp"
+#include "primary_candidates.hpp"
 #include "scene_split.hpp"
 
 namespace rmd {
@@ -689,6 +690,43 @@ static_assert(kSortSlots >= 72u && kSortSlots <= 512u && kSortSlots % 8u == 0u, 
 static_assert(sizeof(HitStack) == kSortPoolBytes, "launch.hpp: kSortPoolBytes");
 using SortPool = HitStack;
 
+// What a work item's primary rays can hit (primary_candidates.hpp: the conditions, the margins and why the frame keeps its bits): a generation
+// trip's 64 rays leave one camera position through one tile, so most turns of the object loop and two of the three axis pairs are known in
+// advance to register nothing, or nothing that is closest.  Computed once per item from this launch's camera and scene — one lane per object
+// for the spheres among objects 0 .. 63 — and handed to the generation trips in place of the launch's visit mask and axis pairs; shading trips,
+// whose rays go anywhere, keep the launch's.  The two values wait in the wave's LDS head (sets[0]: pairs, sets[1 .. 2]: mask) rather than in
+// scalar registers across the trip loop: the kernel sits at 128 vector registers, and measured in spilled registers the head costs none.
+RMD_DEV void item_candidates(KernargWords kernarg_params, WaveTile tile, const DevObject *__restrict__ objs, const DevObject *lobjs, uint32_t *sets) {
+	const uint32_t lane = threadIdx.x & 63u;
+	// the launch's parameters, re-read from the kernel arguments as a trip does (render_wave: the empty asm keeps what is computed from them here,
+	// the same for every item, from being hoisted out of the persistent work loop and kept in registers across it)
+	KernargWords src = kernarg_params;
+	asm volatile("" : "+s"(src));
+	unsigned long long w[sizeof(RenderParams) / 8];
+#pragma unroll
+	for (unsigned i = 0; i < sizeof(RenderParams) / 8; i++) w[i] = src[i];
+	RenderParams P;
+	__builtin_memcpy(&P, w, sizeof(P));
+	unsigned long long visit = P.visit_mask;
+	uint32_t pairs = P.axis_pairs;
+	if (P.primary_cull != 0u) {
+		CullCamera cc;
+		cc.pos[0] = P.cam_pos[0], cc.pos[1] = P.cam_pos[1], cc.pos[2] = P.cam_pos[2];
+		cc.width = P.width, cc.height = P.height, cc.aspect = P.aspect, cc.tan_half_fov = P.tan_half_fov;
+		const TileCone cone = primary_tile_cone(cc, tile.x0, tile.y0, tile.w, tile.h);
+		const DevObject &o = lobjs[lane < P.n_objects ? lane : 0u];
+		const double centre[3] = {o.origin[0], o.origin[1], o.origin[2]};
+		const bool cleared = lane < P.n_objects && o.geometry_kind == 1u && primary_sphere_cleared(cone, cc, centre, o.radius);
+		visit &= ~__ballot(cleared);
+		const AxisWalls *walls = reinterpret_cast<const AxisWalls *>(objs + P.n_objects);
+		const AxisWalls w3[3] = {walls[0], walls[1], walls[2]};
+		pairs = primary_pairs_kept(cone, cc, w3, P.axis_pairs);
+	}
+	if (lane == 0u) sets[0] = pairs, sets[1] = (uint32_t)visit, sets[2] = (uint32_t)(visit >> 32);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // A register pair the compiler may fill with anything: the value of a variable in the lanes that never use it.
 #define RMD_UNDEF3(v) RMD_UNDEF(v.x) RMD_UNDEF(v.y) RMD_UNDEF(v.z)
 template <bool MOM = false>
@@ -707,6 +745,10 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 	const uint32_t pool_first = s_lo, pool_items = have ? (s_hi - s_lo) * 64u : 0u;
 	if (P.bounce_limit == 0u) return; // (such launches are not made: api.cpp)
 	const V3 cam_pos = ld3(P.cam_pos);
+
+	// What this item's primary rays can hit (item_candidates above): into the wave's LDS head, from where the generation trips read it
+	uint32_t *item_sets = reinterpret_cast<uint32_t *>(wave_lds + sizeof(HitStack)) + 1; // [0]: axis pairs, [1], [2]: visit mask (word 0 of the head is the work loop's)
+	item_candidates(kernarg_params, tile, objs, lobjs, item_sets);
 
 	uint32_t n_hit = 0, next_item = 0; // wave-uniform: entries on the stack, pairs handed out
 	// the trip loop's bound (report_fault): every trip hands out 64 pairs or advances at least one path by a segment
@@ -750,6 +792,8 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		V3 ro, rd, T;
 		RMD_UNDEF3(ro) RMD_UNDEF3(rd) RMD_UNDEF3(T)
 		bool failed = false; // lens_failed / cut: the path ends with the sample T (.) 0
+		unsigned long long turns = Pt.visit_mask; // the object loop's turns and the axis pairs of this trip: the launch's, or (GI) the item's own
+		uint32_t pairs = Pt.axis_pairs;
 		if (shade_trip) {
 			// ---------------- SI: the top (up to) 64 parked hits, lane i the entry n_hit - n + i
 			const uint32_t n = n_hit < 64u ? n_hit : 64u;
@@ -790,6 +834,9 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 				primary_ray(Pt, x, y, u0, u1, ro, rd);
 				if (Pt.use_dof) failed = active && !thin_lens_from_pinhole(Pt, ro, rd, rng, ro, rd); // the reference panics there; the sample contributes zero
 			}
+			// what this tile's primary rays can hit (item_candidates)
+			pairs = (uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[0]);
+			turns = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[1]) | (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[2]) << 32;
 		}
 		// ---------------- src/trace.rs:239 — closest hit of every lane that has a ray
 		const bool want = active && !failed;
@@ -798,8 +845,32 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		// (the object loop is a chain of scalar loads with a few vector instructions behind each: at a raised priority it is through sooner and the SIMD's
 		// other waves fill what it leaves with their shading — measured −1.7 %)
 		__builtin_amdgcn_s_setprio(kSortObjPrio);
-		const int oi = scene_intersect_wave<false>(objs, Pt.n_objects, grids, nullptr, *no_scratch, want, ro, rd, t, sub, Pt.axis_pairs, 0u, nullptr, false, Pt.visit_mask);
+		const int oi = scene_intersect_wave<false>(objs, Pt.n_objects, grids, nullptr, *no_scratch, want, ro, rd, t, sub, pairs, 0u, nullptr, false, turns);
 		__builtin_amdgcn_s_setprio(0);
+#if RMD_DIAG
+		// RMD_DEBUG bits 8 | 512: a generation trip ALSO runs the full visit.  Counted per lane: [33] a sphere whose bit was cleared registers a hit,
+		// [34] the closest (distance, object) of the full visit differs from the candidate visit's — both stay 0; [32] lanes checked, [35] sphere
+		// turns and [36] trips with two axis pairs left out.
+		if ((Pt.debug_flags & 512u) && (Pt.debug_flags & 8u) && Pt.debug_counters && !shade_trip) {
+			double t_full = 0.0;
+			uint32_t sub_full = 0;
+			const int oi_full = scene_intersect_wave<false>(objs, Pt.n_objects, grids, nullptr, *no_scratch, want, ro, rd, t_full, sub_full, Pt.axis_pairs, 0u, nullptr, false, Pt.visit_mask);
+			const bool differs = want && (oi_full != oi || __builtin_bit_cast(unsigned long long, t_full) != __builtin_bit_cast(unsigned long long, t));
+			unsigned long long wrong = 0ull;
+			const unsigned long long dropped = Pt.visit_mask & ~turns;
+			for (unsigned long long m = dropped; m != 0ull; m &= m - 1ull) {
+				const DevObject &o = objs[__builtin_ctzll(m)];
+				double ts;
+				wrong += (unsigned long long)__popcll(__ballot(want && sphere_test_flat(ld3(o.origin), o.radius, ro, rd, ts)));
+			}
+			const unsigned long long dm = __ballot(differs), wm = __ballot(want);
+			if (lane == 0u) {
+				atomicAdd(&Pt.debug_counters[32], (unsigned long long)__popcll(wm)), atomicAdd(&Pt.debug_counters[33], wrong);
+				atomicAdd(&Pt.debug_counters[34], (unsigned long long)__popcll(dm)), atomicAdd(&Pt.debug_counters[35], (unsigned long long)__popcll(dropped));
+				atomicAdd(&Pt.debug_counters[36], pairs != Pt.axis_pairs ? 1ull : 0ull);
+			}
+		}
+#endif
 		// ---------------- classification (the rules of render_wave's phase C)
 		bool terminal = failed, park = false, emitted = false;
 		V3 frag, normal;

@@ -33,6 +33,7 @@ _SIGS = {
     "rmd_probe_trace_samples": [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _sz, _vp, _vp, _vp, _vp, _vp],
     "rmd_probe_triangle_sphere": [_sz, _vp, _vp],
     "rmd_probe_pretest_pairs": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "rmd_probe_primary_candidates": [_P(abi.Camera), _P(abi.Settings), _P(abi.Object), C.c_uint32, C.c_uint32, C.c_int64, _sz, _vp, _vp, _vp],
     "rmd_probe_launch_plan": [C.c_uint32, C.c_uint32, _sz, _vp, _vp],
     "rmd_probe_launch_sizes": [C.c_uint32, C.c_uint32, _vp],
     "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
@@ -200,6 +201,21 @@ def pretest_pairs(ctx, sphere5, pos9, ray6):
     passed, hit, t = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n)
     ctx.check(L.rmd_probe_pretest_pairs(ctx.handle, n, _p(sphere5), _p(pos9), _p(ray6), _p(passed), _p(hit), _p(t)))
     return passed.astype(bool), hit.astype(bool), t
+
+
+def primary_candidates(cam, settings, scene, tiles, axis_pairs_tunable=0):
+    """Host only (no GPU): what the spheres kernel's generation trips visit for the primary rays of each wave tile (x0, y0, w, h) ->
+    (launch_visit_mask int, launch_axis_pairs int, on bool, visit uint64[n], pairs uint32[n]); api: rmd_probe_primary_candidates."""
+    L = _L()
+    objs, n, _descs, ng, keep = scene.flatten()
+    tiles = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1, 4)
+    launch, out = np.zeros(3, dtype=np.uint64), np.zeros((tiles.shape[0], 2), dtype=np.uint64)
+    c, s = cam.pod(), settings.pod()
+    st = L.rmd_probe_primary_candidates(C.byref(c), C.byref(s), objs, n, ng, int(axis_pairs_tunable), tiles.shape[0], _p(tiles), _p(launch), _p(out))
+    del keep
+    if st != abi.RMD_OK:
+        raise RuntimeError("rmd_probe_primary_candidates: status %d" % st)
+    return int(launch[0]), int(launch[1]), bool(launch[2]), out[:, 0].copy(), out[:, 1].astype(np.uint32)
 
 
 # rmd_probe_launch_plan: modes, input flags and output columns
