@@ -61,7 +61,8 @@ enum {
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
-	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided) */
+	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
+	                                 rmd_tile_error_dual) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -418,6 +419,54 @@ rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, c
 rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
                               uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
                               uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev);
+/*
+ * DUAL-BUFFER denoising (the cross filter of Rousselle, Knaus and Zwicker 2012, the paper rmd_denoise follows; an addition within ABI 6:
+ * RMD_ABI_VERSION stays 6, no struct changes, a caller finds the functions by their symbols).  The samples are split into two disjoint sets A
+ * and B; each half is filtered with weights computed from the OTHER half, so that a weight never depends on the noise of the value it
+ * multiplies, and the difference of the two filtered halves estimates the error of the frame that is delivered.
+ * S_A = accum_a_dev, Q_A = accum_sq_a_dev, S_B = accum_b_dev, Q_B = accum_sq_b_dev (W*H*3 doubles each, as rmd_render_tiles_moments writes
+ * them); pixel i of rect j holds n_Ai = rect_counts_a[j] samples in A and n_Bi = rect_counts_b[j] in B, a pixel no rect covers 0 and 0.
+ *     u_A, v_A and the validity of half A are exactly rmd_denoise's u, v and VALID on (S_A, Q_A, n_A); likewise u_B, v_B for half B
+ *     pixel i is DUAL-VALID if it is valid in both halves
+ *     w_B(p, q) is rmd_denoise's w(p, q) word for word — D, clamping, the offsets taken, the sum orders, exp(-max(0, D)) — evaluated on
+ *             (u_B, v_B) with "valid" read as dual-valid everywhere; w_A(p, q) the same on (u_A, v_A)
+ * For a dual-valid p, q = p + d over the dual-valid neighbours inside the frame in raster order as in rmd_denoise:
+ *     f_Ac(p) = sum_q w_B(p,q)*u_Aqc / sum_q w_B(p,q)          f_Bc(p) = sum_q w_A(p,q)*u_Bqc / sum_q w_A(p,q)
+ *     out_pc  = (n_A*f_Ac + n_B*f_Bc) / (n_A + n_B)            the two products, their sum, one division (n_A + n_B is exact)
+ *     h_c     = (f_Ac - f_Bc) / 2
+ *     err_p   = (h_0*h_0 + h_1*h_1 + h_2*h_2) / 3              summed in channel order
+ * For a p that is not dual-valid:
+ *     out_pc  = (S_Apc + S_Bpc) / (n_A + n_B)                  exactly as IEEE gives it (a NaN stays NaN, 0 / 0 is NaN)
+ *     err_p   = NaN
+ * and such a pixel is never a neighbour or a patch term.  h_c is the one-degree-of-freedom estimate of the standard error of the delivered
+ * mean: f_A and f_B are two estimates of the same value from disjoint samples, and half their difference has the variance of their mean
+ * (for n_A = n_B).  It measures VARIANCE and not the filter's bias, which both halves share and which cancels in the difference — so it
+ * reads LOW: on the test scene its per-tile RMS is about half the true error of the delivered frame.  It ranks
+ * tiles; it is not a bound.  radius = 0 gives f_A = u_A and f_B = u_B bit for bit, so out and err are exact there.  With the two halves equal
+ * (the same sums and counts) f_A = f_B = rmd_denoise of either half bit for bit and err = 0; out is then (n*f + n*f) / (2n), which is f
+ * again bit for bit when n is a power of two and may differ from it in the last bit otherwise.
+ * out_dev: W*H*3 MEANS, as rmd_denoise's.  err_dev: W*H doubles, or NULL when the estimate is not wanted.
+ * Arguments (all checked before the device is touched): rmd_denoise's rules for radius, patch_radius, k, alpha, width, height and the rects;
+ * the four sum buffers and out_dev non-NULL; no two of the six ranges (five of W*H*3 doubles, err_dev's W*H) overlap; rect_counts_a and
+ * rect_counts_b are HOST arrays of n_rects entries, non-NULL when n_rects > 0.  Anything else is RMD_ERR_INVALID_ARGUMENT.  Synchronous, and
+ * reports an earlier device fault, like rmd_denoise.  The feature weight of rmd_denoise_guided is not part of this call.
+ */
+rmd_status rmd_denoise_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                            const double *accum_sq_b_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+                            const uint32_t *rect_counts_b, uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha,
+                            double *out_dev, double *err_dev);
+/*
+ * Per-tile error of the delivered frame from rmd_denoise_dual's err_dev (W*H doubles):
+ *     out_err_host[r] = sqrt((sum of err_p over rect r's pixels) / the rect's pixel count)
+ * +inf if any err_p of the rect is NaN (a pixel that is not dual-valid), 0 for a rect without pixels.  An ABSOLUTE root mean square in
+ * linear radiance — not relative like rmd_tile_error —, and low by what rmd_denoise_dual says of err.  Sum order: with the rect's pixels
+ * numbered row-major, partial sum t (0 <= t < 256) adds pixels t, t + 256, t + 512, ... in that order; the 256 partial sums are then added
+ * pairwise in halving steps (t with t ^ 32, ^ 16, ... ^ 1 within each group of 64, then the four groups as (g0 + g1) + (g2 + g3)).  Rects
+ * as in rmd_tile_error: any size, inside the W x H frame.  err_dev NULL, width or height 0, rects or out_err_host NULL with n_rects > 0:
+ * RMD_ERR_INVALID_ARGUMENT.  Synchronous, like rmd_tile_error.
+ */
+rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
+                               double *out_err_host);
 /* Host-buffer convenience for a caller that keeps Tile.data in RAM, as the
  * reference does: upload accum, render, download (PCIe-inclusive). */
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera,

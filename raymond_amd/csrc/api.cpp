@@ -1028,6 +1028,95 @@ rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const d
 	                       patch_radius, k, alpha, k_f, tau, out_dev);
 }
 
+// ---------------------------------------------------------------- dual-buffer denoising (denoise_dual.hip)
+static rmd_status denoise_dual_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, uint32_t width, uint32_t height,
+                                    const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, uint32_t radius,
+                                    uint32_t patch_radius, double k, double alpha, double *out_dev, double *err_dev) {
+	if (rmd_status s = bind(ctx)) return s;
+	// device scratch: [the twelve u / v planes: 12 * W*H doubles][f_B: 3 * W*H doubles][both halves' per-pixel counts: 2 * W*H uint32, padded to 16 bytes]
+	// [rects: 16 bytes each][counts of A, then of B: 4 bytes each]
+	const size_t N = (size_t)width * height;
+	const size_t plane_bytes = N * 12u * sizeof(double), fb_bytes = N * 3u * sizeof(double);
+	const size_t img_bytes = (2u * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
+	rmd::DeviceBuffer scratch;
+	RMD_HIP(ctx, scratch.alloc(plane_bytes + fb_bytes + img_bytes + rect_bytes + 2u * count_bytes));
+	unsigned char *d = scratch.as<unsigned char>();
+	double *d_planes = scratch.as<double>();
+	double *d_fb = reinterpret_cast<double *>(d + plane_bytes);
+	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + plane_bytes + fb_bytes);
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + plane_bytes + fb_bytes + img_bytes);
+	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(d + plane_bytes + fb_bytes + img_bytes + rect_bytes), *d_counts_b = d_counts_a + n_rects;
+	if (n_rects != 0) {
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+	}
+	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
+	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
+	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
+	RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, sa, qa, sb, qb, d_rects, d_counts_a, d_counts_b, n_rects, columns, width, height, radius, patch_radius, k, alpha,
+	                                      d_img, d_planes, d_fb, out_dev, err_dev));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
+}
+
+rmd_status rmd_denoise_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                            uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
+                            uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev, double *err_dev) {
+	const std::string name = "rmd_denoise_dual: ";
+	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
+	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
+	{ // no two of the six ranges overlap: five of W*H*3 doubles, err_dev's W*H
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		const unsigned __int128 at[6] = {(uintptr_t)accum_a_dev, (uintptr_t)accum_sq_a_dev, (uintptr_t)accum_b_dev, (uintptr_t)accum_sq_b_dev, (uintptr_t)out_dev, (uintptr_t)err_dev};
+		const unsigned __int128 len[6] = {bytes, bytes, bytes, bytes, bytes, bytes / 3u};
+		for (int i = 0; i < (err_dev ? 6 : 5); i++)
+			for (int j = i + 1; j < (err_dev ? 6 : 5); j++)
+				if (at[i] < at[j] + len[j] && at[j] < at[i] + len[i])
+					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, out_dev and err_dev must not alias");
+	}
+	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
+	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
+	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
+	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
+	return rmd::guarded(ctx, "rmd_denoise_dual", [&] {
+		const char *why = nullptr;
+		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
+		return denoise_dual_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, width, height, rects, rect_counts_a, rect_counts_b, n_rects, radius,
+		                         patch_radius, k, alpha, out_dev, err_dev);
+	});
+}
+
+static rmd_status tile_error_dual_impl(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
+                                       double *out_err_host) {
+	if (rmd_status s = bind(ctx)) return s;
+	rmd::DeviceBuffer d; // the device scratch (it outlives the wait below)
+	if (n_rects != 0) {
+		// device buffer: [rects: 16 bytes each][errors: 8 bytes each]
+		const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect);
+		RMD_HIP(ctx, d.alloc(rect_bytes + (size_t)n_rects * sizeof(double)));
+		rmd_tile_rect *d_rects = d.as<rmd_tile_rect>();
+		double *d_out = reinterpret_cast<double *>(d.as<unsigned char>() + rect_bytes);
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, rmd::launch_tile_error_dual(ctx->stream, err_dev, d_rects, n_rects, width, d_out));
+		RMD_HIP(ctx, hipMemcpyAsync(out_err_host, d_out, (size_t)n_rects * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx);
+}
+
+rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
+                               double *out_err_host) {
+	if (!err_dev || width == 0 || height == 0 || (n_rects && (!rects || !out_err_host)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error_dual: bad argument");
+	for (uint32_t i = 0; i < n_rects; i++)
+		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error_dual: tile rectangle outside the framebuffer");
+	return rmd::guarded(ctx, "rmd_tile_error_dual", [&] { return tile_error_dual_impl(ctx, err_dev, width, height, rects, n_rects, out_err_host); });
+}
+
 // ---------------------------------------------------------------- first-hit feature buffers (features.hip)
 rmd_status rmd_feature_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, double **out_dev) {
 	if (rmd_status s = bind(ctx)) return s;

@@ -1,0 +1,280 @@
+// Dual-buffer (cross) non-local means and its per-pixel error estimate (rmd_denoise_dual, rmd_tile_error_dual; include/raymond_hip.h states
+// the definition, DESIGN.md section 13 the structure and its cost).  A translation unit of its own: the code objects of denoise.hip and of the
+// render kernels do not change.
+//
+// dual_planes_kernel       — per pixel, both halves' u and v (exactly denoise_kernel's staging arithmetic) into twelve planar images of W*H
+//                            doubles: half h's u in planes 6h + c, its v in planes 6h + 3 + c.  A pixel that is not DUAL-VALID keeps a NaN in
+//                            the u of channel 0 of BOTH halves, so one test reads "valid" as dual-valid everywhere.
+// denoise_dual_kernel<TW>  — one cross pass: the weights from the six planes of the WEIGHT half, staged into LDS as denoise_kernel stages its
+//                            own (same apron, term image, row and column sums, two barriers per offset, each window summed directly), applied
+//                            to the u of the VALUE half.  Launched twice with the roles swapped: f_A (weights from B), then f_B (weights from A).
+//   Why six planes in LDS and the value half from global memory, not nine planes under a narrower tile: at r = 10, f = 3 nine f64 planes of a
+//   32-wide tile's apron are 175 KB, over the 160 KB budget, and a 24-wide tile's 151 KB leave no room for the term image (165 KB together).
+//   Nine planes fit only from TW = 16 down (137 KB): four waves a workgroup, one workgroup a CU, 6.9 apron pixels staged and 1.9 term
+//   positions computed per output pixel against 4.8 and 1.6 at TW = 32 — and at r = 12, f = 4 not even TW = 16 fits (166 KB).  The
+//   value half is read once per taken neighbour, three doubles from planar images: neighbouring lanes read neighbouring doubles and
+//   consecutive offsets shift by one pixel, the access the guided kernel makes fourteen times per neighbour and found to be cache hits.  The
+//   LDS layout, its size (denoise_lds_bytes) and the tile width (denoise_tile_width) are therefore denoise_kernel's own.
+// dual_combine_kernel      — out = (n_A f_A + n_B f_B) / (n_A + n_B) and err = mean_c ((f_A - f_B) / 2)^2 for a dual-valid pixel, the merged
+//                            mean and NaN for any other.
+// tile_error_dual_kernel   — one workgroup per rect: sqrt(sum err / pixels), +inf when an err of the rect is NaN.
+// f64 throughout, built with -ffp-contract=off like the rest of the library.
+#include <hip/hip_runtime.h>
+
+#include "launch.hpp"
+
+namespace rmd {
+
+// rmd_denoise's term, word for word (denoise.hip: denoise_term — restated here so that that translation unit stays as it is)
+__device__ inline double dual_term(double ua, double ub, double va, double vb, double k2, double alpha) {
+	const double du = ua - ub;
+	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
+}
+
+// (count_image_kernel of denoise.hip, for two count arrays at once: n_a and n_b are zeroed by the caller)
+__global__ __launch_bounds__(256) void dual_count_image_kernel(const rmd_tile_rect *__restrict__ rects, const uint32_t *__restrict__ counts_a,
+                                                               const uint32_t *__restrict__ counts_b, uint32_t W, uint32_t *__restrict__ n_a,
+                                                               uint32_t *__restrict__ n_b) {
+	const rmd_tile_rect r = rects[blockIdx.x];
+	const uint32_t na = counts_a[blockIdx.x], nb = counts_b[blockIdx.x];
+	const uint64_t n_px = (uint64_t)r.width * r.height;
+	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
+		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
+		const size_t p = (size_t)(r.left + x) + (size_t)(r.top + y) * W;
+		n_a[p] = na, n_b[p] = nb;
+	}
+}
+
+__global__ __launch_bounds__(256) void dual_planes_kernel(const double *__restrict__ SA, const double *__restrict__ QA, const double *__restrict__ SB,
+                                                          const double *__restrict__ QB, const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b,
+                                                          size_t N, double *__restrict__ planes) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	double u[2][3], v[2][3];
+	bool dual = true;
+#pragma unroll
+	for (int h = 0; h < 2; h++) {
+		const double *S = h ? SB : SA, *Q = h ? QB : QA;
+		const uint32_t n = h ? n_b[i] : n_a[i];
+		const double nd = (double)n;
+		dual = dual && n >= 2u;
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			const double s = S[i * 3 + c], q = Q[i * 3 + c];
+			dual = dual && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
+			u[h][c] = s / nd;
+			double t = (q - s * u[h][c]) / (nd - 1.0);
+			if (t < 0.0) t = 0.0;
+			v[h][c] = t / nd;
+		}
+	}
+#pragma unroll
+	for (int h = 0; h < 2; h++) {
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			planes[(size_t)(6 * h + c) * N + i] = (c == 0 && !dual) ? __builtin_nan("") : u[h][c];
+			planes[(size_t)(6 * h + 3 + c) * N + i] = v[h][c];
+		}
+	}
+}
+
+// Pw: the weight half's six planes (u, then v); Uv: the value half's three u planes; fout: W*H*3 doubles, pixel-interleaved, written at dual-valid
+// pixels only (dual_combine_kernel gives the others their value).
+template <int TW>
+__global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__restrict__ Pw, const double *__restrict__ Uv, uint32_t W, uint32_t H, int r, int f,
+                                                               double k2, double alpha, double *__restrict__ fout) {
+	extern __shared__ double lds[];
+	constexpr int TH = (int)kDenoiseTile, NT = TW * TH;
+	const int R = r + f, AW = TW + 2 * R, AA = AW * (TH + 2 * R), PW = TW + 2 * f, PP = PW * (TH + 2 * f);
+	double *U = lds, *V = lds + 3 * AA;           // planes c * AA + (apron row * AW + apron column)
+	double *T = lds + 6 * AA, *Hs = T + PP;        // the term image (TH + 2f rows of PW) and its row sums (TH + 2f rows of TW)
+	uint32_t *Tc = reinterpret_cast<uint32_t *>(Hs + (TH + 2 * f) * TW), *Hc = Tc + PP;
+	const int64_t x0 = (int64_t)blockIdx.x * TW, y0 = (int64_t)blockIdx.y * TH;
+	const int tid = threadIdx.x;
+	const size_t N = (size_t)W * H;
+
+	for (int i = tid; i < AA; i += NT) {
+		const int ly = i / AW, lx = i - ly * AW;
+		const int64_t gx = min(max(x0 - R + lx, (int64_t)0), (int64_t)W - 1), gy = min(max(y0 - R + ly, (int64_t)0), (int64_t)H - 1);
+		const size_t pix = (size_t)gx + (size_t)gy * W;
+#pragma unroll
+		for (int c = 0; c < 3; c++) U[c * AA + i] = Pw[(size_t)c * N + pix], V[c * AA + i] = Pw[(size_t)(3 + c) * N + pix];
+	}
+	__syncthreads();
+
+	// this thread's term-image positions (at most 3: PP <= (TW + 8) * 24 <= 3 * TW * 16) and their own u, v
+	constexpr int kSlots = 3;
+	int ia[kSlots];
+	bool oka[kSlots];
+	double ua[kSlots][3], va[kSlots][3];
+#pragma unroll
+	for (int s = 0; s < kSlots; s++) {
+		const int j = tid + NT * s;
+		const int ty = j / PW, tx = j - ty * PW;
+		ia[s] = j < PP ? (ty + r) * AW + (tx + r) : 0;
+#pragma unroll
+		for (int c = 0; c < 3; c++) ua[s][c] = U[c * AA + ia[s]], va[s][c] = V[c * AA + ia[s]];
+		oka[s] = j < PP && ua[s][0] == ua[s][0];
+	}
+
+	// this thread's output pixel; the offsets that keep q = p + d inside the frame
+	const int px = tid % TW, py = tid / TW;
+	const int64_t gx = x0 + px, gy = y0 + py;
+	const bool inside = gx < (int64_t)W && gy < (int64_t)H;
+	const int ip = (py + R) * AW + (px + R);
+	const bool p_ok = inside && U[ip] == U[ip];
+	const int dx_lo = (int)max((int64_t)-r, -gx), dx_hi = (int)min((int64_t)r, (int64_t)W - 1 - gx);
+	const int dy_lo = (int)max((int64_t)-r, -gy), dy_hi = (int)min((int64_t)r, (int64_t)H - 1 - gy);
+	const size_t pixp = inside ? (size_t)gx + (size_t)gy * W : 0;
+	double acc0 = -0.0, acc1 = -0.0, acc2 = -0.0, wsum = -0.0; // -0.0 + x == x for every x, so r = 0 gives the value half's u bit for bit
+
+	for (int dy = -r; dy <= r; dy++) {
+		for (int dx = -r; dx <= r; dx++) {
+			const int db = dy * AW + dx;
+#pragma unroll
+			for (int s = 0; s < kSlots; s++) {
+				const int j = tid + NT * s;
+				if (j < PP) {
+					const int ib = ia[s] + db;
+					const double ub0 = U[ib];
+					double t = 0.0;
+					uint32_t taken = 0u;
+					if (oka[s] && ub0 == ub0) {
+						t = dual_term(ua[s][0], ub0, va[s][0], V[ib], k2, alpha);
+						t = t + dual_term(ua[s][1], U[AA + ib], va[s][1], V[AA + ib], k2, alpha);
+						t = t + dual_term(ua[s][2], U[2 * AA + ib], va[s][2], V[2 * AA + ib], k2, alpha);
+						taken = 1u;
+					}
+					T[j] = t, Tc[j] = taken;
+				}
+			}
+			__syncthreads();
+			for (int j = tid; j < (TH + 2 * f) * TW; j += NT) {
+				const int ty = j / TW, x = j - ty * TW;
+				const double *row = T + ty * PW + x;
+				const uint32_t *crow = Tc + ty * PW + x;
+				double h = row[0];
+				uint32_t hc = crow[0];
+				for (int o = 1; o <= 2 * f; o++) h = h + row[o], hc += crow[o];
+				Hs[j] = h, Hc[j] = hc;
+			}
+			__syncthreads();
+			if (p_ok && dx >= dx_lo && dx <= dx_hi && dy >= dy_lo && dy <= dy_hi) {
+				const double wq0 = U[ip + db];
+				if (wq0 == wq0) { // q is dual-valid
+					double ds = Hs[py * TW + px];
+					uint32_t cnt = Hc[py * TW + px];
+					for (int o = 1; o <= 2 * f; o++) ds = ds + Hs[(py + o) * TW + px], cnt += Hc[(py + o) * TW + px];
+					const double D = ds / (3.0 * (double)cnt);
+					const double w = exp(-(D > 0.0 ? D : 0.0));
+					const size_t pixq = (size_t)((int64_t)pixp + (int64_t)dy * (int64_t)W + dx); // (inside the frame: dx, dy are within the lo / hi bounds)
+					acc0 = acc0 + w * Uv[pixq], acc1 = acc1 + w * Uv[N + pixq], acc2 = acc2 + w * Uv[2 * N + pixq];
+					wsum = wsum + w;
+				}
+			}
+		}
+	}
+
+	if (p_ok) {
+		const size_t o = pixp * 3;
+		fout[o + 0] = acc0 / wsum, fout[o + 1] = acc1 / wsum, fout[o + 2] = acc2 / wsum;
+	}
+}
+
+// fa = out (in place), fb: the two cross passes' results.  Dual-valid p: out = (n_A*f_A + n_B*f_B) / (n_A + n_B) — the two products, their sum, one
+// division —, err = (h_0^2 + h_1^2 + h_2^2) / 3 with h_c = (f_Ac - f_Bc) / 2, summed in channel order.  Any other p: the merged mean as IEEE gives it
+// and err = NaN.  err may be null.
+__global__ __launch_bounds__(256) void dual_combine_kernel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
+                                                           const uint32_t *__restrict__ n_b, const double *__restrict__ planes, const double *__restrict__ fb,
+                                                           size_t N, double *out, double *__restrict__ err) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const double na = (double)n_a[i], nb = (double)n_b[i];
+	const double nsum = na + nb;
+	const double ua0 = planes[i];
+	if (ua0 == ua0) {
+		double e = 0.0;
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			const double a = out[i * 3 + c], b = fb[i * 3 + c];
+			out[i * 3 + c] = (na * a + nb * b) / nsum;
+			const double h = (a - b) / 2.0;
+			e = c == 0 ? h * h : e + h * h;
+		}
+		if (err) err[i] = e / 3.0;
+	} else {
+#pragma unroll
+		for (int c = 0; c < 3; c++) out[i * 3 + c] = (SA[i * 3 + c] + SB[i * 3 + c]) / nsum;
+		if (err) err[i] = __builtin_nan("");
+	}
+}
+
+hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                               const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, uint32_t count_image_columns,
+                               uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k, double alpha, uint32_t *n_img, double *planes,
+                               double *f_b, double *out, double *err) {
+	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+	const size_t N = (size_t)W * H;
+	uint32_t *n_a = n_img, *n_b = n_img + N;
+	hipError_t e = hipMemsetAsync(n_img, 0, 2u * N * sizeof(uint32_t), stream);
+	if (e != hipSuccess) return e;
+	if (n_rects) {
+		hipLaunchKernelGGL(dual_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_a, counts_b, W, n_a, n_b);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
+	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
+	hipLaunchKernelGGL(dual_planes_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, n_a, n_b, N, planes);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	const uint32_t tw = denoise_tile_width(radius, patch_radius);
+	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
+	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits, as for denoise_kernel)
+	const void *fn = tw == 32u ? reinterpret_cast<const void *>(&denoise_dual_kernel<32>) : reinterpret_cast<const void *>(&denoise_dual_kernel<24>);
+	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
+	const dim3 grid((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
+	const int ri = (int)radius, fi = (int)patch_radius;
+	const double k2 = k * k;
+	const double *PA = planes, *PB = planes + 6u * N;
+	for (int pass = 0; pass < 2; pass++) { // f_A: weights from B applied to u_A, into out; f_B: weights from A applied to u_B, into f_b
+		const double *Pw = pass == 0 ? PB : PA, *Uv = pass == 0 ? PA : PB;
+		double *fout = pass == 0 ? out : f_b;
+		if (tw == 32u) hipLaunchKernelGGL(denoise_dual_kernel<32>, grid, dim3(32 * kDenoiseTile), lds, stream, Pw, Uv, W, H, ri, fi, k2, alpha, fout);
+		else hipLaunchKernelGGL(denoise_dual_kernel<24>, grid, dim3(24 * kDenoiseTile), lds, stream, Pw, Uv, W, H, ri, fi, k2, alpha, fout);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(dual_combine_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, N, out, err);
+	return hipGetLastError();
+}
+
+// One workgroup per rect.  Thread t adds the err of the rect's pixels t, t + 256, t + 512, ... (row-major within the rect) in that order; the 256
+// partial sums are then added pairwise, halving: first lanes 32 apart within each wave, down to neighbours, then the four waves' sums as
+// (w0 + w1) + (w2 + w3).  A NaN err anywhere in the rect makes the result +inf.
+__global__ __launch_bounds__(256) void tile_error_dual_kernel(const double *__restrict__ err, const rmd_tile_rect *__restrict__ rects, uint32_t W,
+                                                               double *__restrict__ out) {
+	const rmd_tile_rect r = rects[blockIdx.x];
+	const uint64_t n_px = (uint64_t)r.width * r.height;
+	double s = 0.0;
+	uint32_t bad = 0u;
+	for (uint64_t i = threadIdx.x; i < n_px; i += 256u) {
+		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
+		const double e = err[(size_t)(r.left + x) + (size_t)(r.top + y) * W];
+		if (e == e) s = s + e;
+		else bad = 1u;
+	}
+	for (int off = 32; off > 0; off >>= 1) s = s + __shfl_xor(s, off, 64), bad |= __shfl_xor(bad, off, 64);
+	__shared__ double wave_sum[4];
+	__shared__ uint32_t wave_bad[4];
+	if ((threadIdx.x & 63u) == 0u) wave_sum[threadIdx.x >> 6] = s, wave_bad[threadIdx.x >> 6] = bad;
+	__syncthreads();
+	if (threadIdx.x == 0u) {
+		const double total = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+		const bool any_bad = (wave_bad[0] | wave_bad[1] | wave_bad[2] | wave_bad[3]) != 0u;
+		out[blockIdx.x] = any_bad ? __builtin_inf() : (n_px ? __builtin_sqrt(total / (double)n_px) : 0.0);
+	}
+}
+hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W, double *out) {
+	if (n_rects == 0) return hipSuccess;
+	hipLaunchKernelGGL(tile_error_dual_kernel, dim3(n_rects), dim3(256), 0, stream, err, rects, W, out);
+	return hipGetLastError();
+}
+
+} // namespace rmd

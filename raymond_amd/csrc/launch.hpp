@@ -121,6 +121,15 @@ hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const 
                                  const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
                                  uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
                                  double *out);
+// rmd_denoise_dual (denoise_dual.hip): out = the cross-filtered means of the two halves (accum_a, accum_sq_a) and (accum_b, accum_sq_b) whose rect i
+// holds counts_a[i] and counts_b[i] samples, err (may be null) the per-pixel error estimate, W*H doubles.  Scratch: n_img 2 * W*H uint32, planes
+// 12 * W*H doubles, f_b 3 * W*H doubles.  rects and the counts are device memory; the tile shape and LDS are denoise_kernel's
+hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                               const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, uint32_t count_image_columns,
+                               uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k, double alpha, uint32_t *n_img, double *planes,
+                               double *f_b, double *out, double *err);
+// out[i] = sqrt(the mean of err over rect i's pixels), +inf if one of them is NaN (denoise_dual.hip: tile_error_dual_kernel; rects and out are device memory)
+hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W, double *out);
 // rmd_render_features (features.hip): for each of the P.n_work wave tiles, the first-hit features of samples P.sample_begin .. + P.sample_count - 1
 // added to feat (and their squares to feat_sq when it is not null), W*H*RMD_FEATURE_CHANNELS doubles each
 hipError_t launch_features(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const WaveTile *wave_tiles, double *feat,

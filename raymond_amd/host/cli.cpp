@@ -8,6 +8,9 @@
 //                                                                    [--denoise-features 1 [--denoise-feature-k K] [--denoise-feature-tau T]]
 //                                                                      (needs --denoise 1: first-hit features guide the filter, rmd_denoise_guided)
 //                                                                    [--dump-features FILE]   (the W*H*7 feature means as raw f64: the AOVs)
+//                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
+//                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
+//                                                                       the image is rmd_denoise_dual's; T: tiles finish by rmd_tile_error_dual)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -54,7 +57,9 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 	}
 	if (st.denoise) {
 		handle.await(); // (its channel is drained: it only waits for the workers and rethrows a worker's error)
-		std::vector<Vector3> den = finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0}) : denoise_tiles(finished_tiles, st, 0, scene, feature_means);
+		std::vector<Vector3> den = finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0})
+		                           : st.denoise_dual      ? denoise_dual_tiles(finished_tiles, st, 0)
+		                                                  : denoise_tiles(finished_tiles, st, 0, scene, feature_means);
 		if (finished_out) *finished_out = std::move(finished_tiles);
 		return den;
 	}
@@ -195,6 +200,9 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-patch")) st.denoise_patch = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-k")) st.denoise_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-alpha")) st.denoise_alpha = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-dual")) st.denoise_dual = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--adaptive-denoised")) st.adaptive_denoised_threshold = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--adaptive-min")) st.adaptive_min_samples = (size_t)std::strtoull(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-feature-k")) st.denoise_feature_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-feature-tau")) st.denoise_feature_tau = std::atof(argv[i + 1]);

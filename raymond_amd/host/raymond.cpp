@@ -395,6 +395,142 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 	sh->cv.notify_all();
 }
 
+// settings.denoise_dual: the one worker of a dual-buffer render, a plain loop over passes (every live tile takes every pass).  Four framebuffers:
+// pass j, counted from 0, adds its samples to half A (fbs 0, 1) when j is even and to half B (fbs 2, 3) when j is odd.  With
+// adaptive_denoised_threshold > 0, after every even number of passes that leaves the live tiles below sample_count with at least
+// adaptive_min_samples: rmd_denoise_dual over the whole frame (finished tiles at the counts they finished with), rmd_tile_error_dual over the live
+// tiles, and the tiles at or below the threshold are finished.  Progress snapshots go out as they are made, the finished tiles at the end.
+void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene scene, Settings st) {
+	rmd_context *ctx = nullptr;
+	rmd_scene *dscene = nullptr;
+	double *fbs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
+	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
+	try {
+		const auto t_setup = std::chrono::steady_clock::now();
+		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
+		std::vector<rmd_object> objs;
+		std::vector<rmd_grid_desc> grids;
+		flatten(scene, objs, grids);
+		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
+		const bool adaptive = st.adaptive_denoised_threshold > 0.0;
+		for (int i = 0; i < (adaptive ? 6 : 4); i++) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fbs[i]), ctx, "rmd_framebuffer_alloc");
+		{
+			std::lock_guard<std::mutex> lock(sh->m);
+			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
+		}
+		rmd_camera cam;
+		std::memset(&cam, 0, sizeof(cam));
+		cam.backbuffer_width = (uint32_t)W, cam.backbuffer_height = (uint32_t)H, cam.fov_vert = st.camera_settings.fov_vert;
+		for (int a = 0; a < 3; a++) cam.position[a] = st.camera_settings.transform.position[a];
+		cam.focal_length = st.camera_settings.focal_length, cam.aperture_radius = st.camera_settings.aperture_radius;
+		const uint32_t flags = (st.use_dof ? RMD_RENDER_DOF : 0u) | (st.end_black_paths ? RMD_RENDER_END_BLACK_PATHS : 0u);
+		std::vector<rmd_tile_rect> live = generate_tiles(W, H, st.tile_size);
+		std::vector<rmd_tile_rect> done_rects;
+		std::vector<uint32_t> done_a, done_b;
+		std::vector<Message> finished;
+		size_t n_half[2] = {0, 0}, done = 0, j = 0;
+		// the rects' pixels of one framebuffer, tile after tile in Tile.data layout
+		auto download = [&](double *fb, const std::vector<rmd_tile_rect> &rects) {
+			size_t pixels = 0;
+			for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
+			std::vector<Vector3> packed(pixels);
+			if (pixels)
+				check(rmd_framebuffer_download_tiles(ctx, fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), reinterpret_cast<double *>(packed.data())), ctx,
+				      "rmd_framebuffer_download_tiles");
+			return packed;
+		};
+		auto finish = [&](const std::vector<rmd_tile_rect> &rects, const std::vector<double> &errors) {
+			if (rects.empty()) return;
+			std::vector<Vector3> packed[4];
+			for (int i = 0; i < 4; i++) packed[i] = download(fbs[i], rects);
+			size_t at = 0;
+			for (size_t k = 0; k < rects.size(); k++) {
+				const rmd_tile_rect &r = rects[k];
+				const size_t n = (size_t)r.width * r.height;
+				Tile t;
+				t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height;
+				t.count_a = n_half[0], t.count_b = n_half[1], t.sample_count = n_half[0] + n_half[1];
+				if (!errors.empty()) t.error = errors[k];
+				TileData *half[4] = {&t.data_a, &t.data_sq_a, &t.data_b, &t.data_sq_b};
+				for (int i = 0; i < 4; i++) {
+					*half[i] = TileData(n);
+					std::copy(packed[i].begin() + (long)at, packed[i].begin() + (long)(at + n), half[i]->data());
+				}
+				t.data = TileData(n), t.data_sq = TileData(n);
+				for (size_t p = 0; p < n; p++)
+					for (int c = 0; c < 3; c++) t.data[p][c] = t.data_a[p][c] + t.data_b[p][c], t.data_sq[p][c] = t.data_sq_a[p][c] + t.data_sq_b[p][c];
+				at += n;
+				finished.push_back(Message{Message::TileFinished, std::move(t)});
+				done_rects.push_back(r), done_a.push_back((uint32_t)n_half[0]), done_b.push_back((uint32_t)n_half[1]);
+			}
+		};
+		while (done < st.sample_count && !live.empty()) {
+			const size_t n = std::min(st.samples_per_iteration, st.sample_count - done), half = j & 1;
+			rmd_settings rs;
+			std::memset(&rs, 0, sizeof(rs));
+			rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)done, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
+			check(rmd_render_tiles_moments(ctx, dscene, &cam, &rs, live.data(), (uint32_t)live.size(), fbs[2 * half], fbs[2 * half + 1]), ctx, "rmd_render_tiles_moments");
+			done += n, j++, n_half[half] += n;
+			if (done >= st.sample_count) break;
+			std::vector<double> errors;
+			if (adaptive && j % 2 == 0 && done >= st.adaptive_min_samples) {
+				std::vector<rmd_tile_rect> rects(done_rects);
+				std::vector<uint32_t> ca(done_a), cb(done_b);
+				rects.insert(rects.end(), live.begin(), live.end());
+				ca.insert(ca.end(), live.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), live.size(), (uint32_t)n_half[1]);
+				check(rmd_denoise_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(), (uint32_t)rects.size(), st.denoise_radius,
+				                       st.denoise_patch, st.denoise_k, st.denoise_alpha, fbs[4], fbs[5]),
+				      ctx, "rmd_denoise_dual");
+				errors.resize(live.size());
+				check(rmd_tile_error_dual(ctx, fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), errors.data()), ctx, "rmd_tile_error_dual");
+			}
+			std::vector<rmd_tile_rect> converged, still;
+			std::vector<double> converged_err, still_err;
+			for (size_t k = 0; k < live.size(); k++) {
+				const bool conv = !errors.empty() && errors[k] <= st.adaptive_denoised_threshold;
+				(conv ? converged : still).push_back(live[k]);
+				if (!errors.empty()) (conv ? converged_err : still_err).push_back(errors[k]);
+			}
+			finish(converged, converged_err);
+			// progress snapshots of the tiles that go on: the two halves' sums added
+			std::vector<Vector3> pa = download(fbs[0], still), pb = download(fbs[2], still);
+			std::vector<Message> snapshots;
+			size_t at = 0;
+			for (size_t k = 0; k < still.size(); k++) {
+				const rmd_tile_rect &r = still[k];
+				const size_t px = (size_t)r.width * r.height;
+				Tile t;
+				t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height, t.sample_count = done;
+				if (!still_err.empty()) t.error = still_err[k];
+				t.data = TileData(px);
+				for (size_t p = 0; p < px; p++)
+					for (int c = 0; c < 3; c++) t.data[p][c] = pa[at + p][c] + pb[at + p][c];
+				at += px;
+				snapshots.push_back(Message{Message::TileProgressed, std::move(t)});
+			}
+			{
+				std::lock_guard<std::mutex> lock(sh->m);
+				for (Message &m : snapshots) sh->channel.push_back(std::move(m));
+				sh->cv.notify_all();
+			}
+			live = std::move(still);
+		}
+		finish(live, {});
+		std::lock_guard<std::mutex> lock(sh->m);
+		for (Message &m : finished) sh->channel.push_back(std::move(m));
+	} catch (const std::exception &e) {
+		std::lock_guard<std::mutex> lock(sh->m);
+		if (sh->error.empty()) sh->error = e.what();
+	}
+	for (double *fb : fbs)
+		if (fb) rmd_framebuffer_free(ctx, fb);
+	rmd_scene_destroy(dscene);
+	rmd_context_destroy(ctx);
+	std::lock_guard<std::mutex> lock(sh->m);
+	sh->alive--;
+	sh->cv.notify_all();
+}
+
 } // namespace
 
 TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
@@ -411,9 +547,26 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 	if (settings.adaptive_threshold > 0.0 && settings.samples_per_iteration == 0)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)");
 	if (!(settings.adaptive_floor > 0.0) || !std::isfinite(settings.adaptive_floor)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_floor must be finite and > 0");
+	if (settings.denoise_dual && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual needs denoise");
+	if (settings.denoise_dual && settings.samples_per_iteration == 0)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)");
+	if (settings.denoise_dual && settings.denoise_features)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight");
+	if (!(settings.adaptive_denoised_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold must be >= 0 (0 = off)");
+	if (settings.adaptive_denoised_threshold > 0.0 && !settings.denoise_dual)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)");
+	if (settings.adaptive_denoised_threshold > 0.0 && settings.adaptive_threshold > 0.0)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold and adaptive_threshold are mutually exclusive");
+	if (settings.denoise_dual && settings.worker_count > 1)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own");
 	TaskHandle h;
 	h.settings = settings;
 	h.shared_ = std::make_shared<TaskHandle::Shared>();
+	if (settings.denoise_dual) {
+		h.shared_->alive = 1;
+		h.workers_.emplace_back(dual_worker_main, h.shared_, 0, scene, settings);
+		return h;
+	}
 	if (settings.denoise_features) h.scene_ = std::make_shared<const Scene>(scene);
 	const CameraSettings &cam = settings.camera_settings;
 	for (const rmd_tile_rect &r : generate_tiles(cam.backbuffer_width, cam.backbuffer_height, settings.tile_size)) {
@@ -461,7 +614,7 @@ std::vector<Vector3> TaskHandle::await() {
 			}
 	}
 	lock.unlock();
-	if (!collected.empty()) out = denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
+	if (!collected.empty()) out = settings.denoise_dual ? denoise_dual_tiles(collected, settings, 0) : denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
 	return out;
 }
 
@@ -591,6 +744,49 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 	for (double *d : dev) rmd_framebuffer_free(ctx, d);
 	for (double *d : fdev)
 		if (d) rmd_framebuffer_free(ctx, d);
+	rmd_context_destroy(ctx);
+	return out;
+}
+
+std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors) {
+	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
+	std::vector<double> halves[4];
+	for (std::vector<double> &h : halves) h.assign(W * H * 3, 0.0);
+	std::vector<rmd_tile_rect> rects;
+	std::vector<uint32_t> counts_a, counts_b;
+	for (const Tile &t : tiles) {
+		const TileData *src[4] = {&t.data_a, &t.data_sq_a, &t.data_b, &t.data_sq_b};
+		for (int i = 0; i < 4; i++) {
+			if (src[i]->size() != t.width * t.height) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: a tile without its two halves' sums and sums of squares");
+			for (size_t y = 0; y < t.height; y++)
+				for (size_t x = 0; x < t.width; x++)
+					for (int c = 0; c < 3; c++) halves[i][(x + t.left + (y + t.top) * W) * 3 + c] = (*src[i])[x + y * t.width][c];
+		}
+		rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+		counts_a.push_back((uint32_t)t.count_a), counts_b.push_back((uint32_t)t.count_b);
+	}
+	std::vector<Vector3> out(W * H);
+	rmd_context *ctx = nullptr;
+	double *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // the four halves, the frame, the error image
+	try {
+		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
+		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
+		for (int i = 0; i < 4; i++) check(rmd_framebuffer_upload(ctx, halves[i].data(), dev[i], halves[i].size()), ctx, "rmd_framebuffer_upload");
+		check(rmd_denoise_dual(ctx, dev[0], dev[1], dev[2], dev[3], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(), (uint32_t)rects.size(),
+		                       settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, dev[4], tile_errors ? dev[5] : nullptr),
+		      ctx, "rmd_denoise_dual");
+		if (tile_errors) {
+			tile_errors->assign(rects.size(), 0.0);
+			check(rmd_tile_error_dual(ctx, dev[5], (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), tile_errors->data()), ctx, "rmd_tile_error_dual");
+		}
+		check(rmd_framebuffer_download(ctx, dev[4], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
+	} catch (...) {
+		for (double *d : dev)
+			if (d) rmd_framebuffer_free(ctx, d);
+		rmd_context_destroy(ctx);
+		throw;
+	}
+	for (double *d : dev) rmd_framebuffer_free(ctx, d);
 	rmd_context_destroy(ctx);
 	return out;
 }

@@ -139,6 +139,15 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// rmd_denoise_guided, k_f = denoise_feature_k, tau = denoise_feature_tau (both finite and > 0, or render_tiled throws).
 	bool denoise_features = false;
 	double denoise_feature_k = 1.0, denoise_feature_tau = 1e-2; // (the best of the sweep in DESIGN.md section 12)
+	// Dual-buffer denoising (needs denoise and samples_per_iteration > 0, one GPU, not with denoise_features; false = off): pass j of a tile, counted
+	// from 0, adds its samples to half A when j is even and to half B when j is odd; TileFinished tiles carry both halves and await() returns
+	// rmd_denoise_dual's frame (raymond_hip.h).
+	bool denoise_dual = false;
+	// Adaptive sampling by the filtered frame's error (needs denoise_dual, excludes adaptive_threshold > 0; 0 = off): after every even number of
+	// passes that leaves live tiles with at least adaptive_min_samples samples, rmd_denoise_dual runs over the whole frame and a live tile whose
+	// rmd_tile_error_dual — an absolute RMS in linear radiance that reads low — is at most the threshold is finished at the samples it has.
+	double adaptive_denoised_threshold = 0.0;
+	size_t adaptive_min_samples = 32;
 };
 
 // core/src/tile.rs:13 `data: Vec<Vector3>` — the running sums of a tile, width * height of them, row-major.  Here a VIEW: the tiles of one
@@ -176,6 +185,11 @@ struct Tile { // core/src/tile.rs:7-14
 	int resident = -1; // the worker (GPU) whose device framebuffer holds the tile's sums; -1: `data` does (an extension: the reference's tiles live in RAM)
 	TileData data_sq;  // adaptive renders with several GPUs: the running sums of squares (rmd_render_tiles_moments), travelling through RAM with `data`
 	                   // while the tile waits in the queue; denoised renders: also every TileFinished tile's; empty otherwise
+	// dual-buffer renders (settings.denoise_dual): a TileFinished tile's two sample halves — sums, sums of squares and samples per pixel —; `data` and
+	// `data_sq` are then the halves' sums added and sample_count = count_a + count_b.  Empty / 0 otherwise
+	TileData data_a, data_sq_a, data_b, data_sq_b;
+	size_t count_a = 0, count_b = 0;
+	double error = -1.0; // dual-buffer adaptive renders: the tile's rmd_tile_error_dual when it was last checked; -1: never
 };
 struct Message { // src/trace.rs:62-66
 	enum Kind { TileFinished, TileProgressed } kind;
@@ -189,7 +203,7 @@ class TaskHandle {
 	Settings settings;
 	void set_callback(TileCallback cb) { callback_ = std::move(cb); }
 	// Blocks until every worker is done, then assembles W*H radiance values (tile sums / sample_count), row-major (:82-113).  settings.denoise: the
-	// collected tiles go through denoise_tiles on GPU 0 instead (none collected: the zero frame, as without it)
+	// collected tiles go through denoise_tiles (settings.denoise_dual: denoise_dual_tiles) on GPU 0 instead (none collected: the zero frame, as without it)
 	std::vector<Vector3> await();
 	std::optional<Message> poll();        // :115-117
 	void async_await();                   // :119-134: drains leading TileProgressed messages into the callback
@@ -217,6 +231,9 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings);
 // rmd_denoise_guided.  feature_means (optional): receives the W*H*7 feature means (sums / the tile's count; 0 / 0 where no tile lies).
 std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, const Scene *scene = nullptr,
                                    std::vector<double> *feature_means = nullptr);
+// Extension (settings.denoise_dual): the W*H means of rmd_denoise_dual on GPU `device` over the tiles' two halves (data_a .. count_b) with the
+// settings' parameters.  tile_errors (optional): receives rmd_tile_error_dual of every tile, in the tiles' order.
+std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, std::vector<double> *tile_errors = nullptr);
 // The W*H*7 first-hit feature sums (and, when asked for, sums of squares) of a frame whose rect i holds counts[i] samples, rendered on GPU `device`
 // with the settings' camera, seed and DOF flag: the AOVs (normal xyz, albedo rgb, depth) of raymond_hip.h's rmd_render_features.
 std::vector<double> render_features(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,

@@ -251,6 +251,65 @@ def denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **
                 b.close()
 
 
+class ErrorImage(Framebuffer):
+    """W*H f64 in HBM: rmd_denoise_dual's per-pixel error estimate (the allocation is a framebuffer's; its first W*H doubles are used)."""
+
+    def __init__(self, ctx, width, height):
+        Framebuffer.__init__(self, ctx, width, height)
+        self.n = width * height
+
+    def download(self):
+        out = np.empty((self.height, self.width), dtype=np.float64)
+        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
+        return out
+
+    def download_tiles(self, tiles):
+        raise NotImplementedError("error images have no tile-rect transfers")
+
+    def upload_tiles(self, tiles, datas):
+        raise NotImplementedError("error images have no tile-rect transfers")
+
+
+def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0):
+    """rmd_denoise_dual: `out_framebuffer` = the cross-filtered means of the two sample halves `half_a` and `half_b`, each a (sums, sums of squares)
+    pair of Framebuffers; rect i holds counts_a[i] and counts_b[i] samples per pixel in them.  `error_image` (an ErrorImage, optional) receives the
+    per-pixel error estimate."""
+    counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
+    counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
+    if len(counts_a) != len(rects) or len(counts_b) != len(rects):
+        raise ValueError("one sample count per rect and half")
+    fb = half_a[0]
+    ctx.check(ctx.L.rmd_denoise_dual(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, fb.width, fb.height, tile_array(rects),
+                                     counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius),
+                                     int(patch_radius), float(k), float(alpha), out_framebuffer.ptr, None if error_image is None else error_image.ptr))
+
+
+def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, **params):
+    """denoise_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate out."""
+    H, W = sums_a.shape[0], sums_a.shape[1]
+    opened = []
+    try:
+        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, None):
+            opened.append(Framebuffer(ctx, W, H))
+            if arr is not None:
+                opened[-1].upload(arr)
+        opened.append(ErrorImage(ctx, W, H))
+        denoise_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5], **params)
+        return opened[4].download(), opened[5].download()
+    finally:
+        for b in opened:
+            b.close()
+
+
+def tile_error_dual(ctx, error_image, tiles):
+    """rmd_tile_error_dual: per tile, the root mean square of `error_image` (rmd_denoise_dual's estimate) over its pixels; +inf for a tile with a
+    pixel that is not dual-valid (float64 array)."""
+    out = np.empty(max(1, len(tiles)), dtype=np.float64)
+    ctx.check(ctx.L.rmd_tile_error_dual(ctx.handle, error_image.ptr, error_image.width, error_image.height, tile_array(tiles), len(tiles),
+                                        out.ctypes.data_as(C.c_void_p)))
+    return out[: len(tiles)]
+
+
 def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
     """TaskHandle::await's divide + cli_old's tone-map/gamma/u8 cast (cli_old/src/main.rs:161-181) -> (H, W, 3) uint8."""
     out = np.empty((framebuffer.height, framebuffer.width, 3), dtype=np.uint8)
@@ -269,6 +328,9 @@ class Tile:  # core/src/tile.rs:7-14
         self.data = data  # (height, width, 3) running sums, like Tile.data
         self.error = error  # adaptive renders (an extension): the tile's rmd_tile_error at sample_count when it was checked, else None
         self.data_sq = data_sq  # denoised renders (an extension): the finished tile's running sums of squares, like data; else None
+        # dual-buffer renders (an extension): the finished tile's two sample halves — sums, sums of squares (like data) and samples per pixel —;
+        # data and data_sq are then the halves' sums added, sample_count = count_a + count_b.  Else None
+        self.data_a = self.data_sq_a = self.count_a = self.data_b = self.data_sq_b = self.count_b = None
 
 
 class Message:  # src/trace.rs:62-66
@@ -314,6 +376,8 @@ class TaskHandle:  # src/trace.rs:70-135
         cam = self.settings.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         out = np.zeros(shape, dtype=np.float64)
+        if self.settings.denoise and self.settings.denoise_dual:
+            return self._await_dual()
         denoised = self.settings.denoise
         if denoised and self.settings.denoise_features:
             self.settings.check_denoise()
@@ -343,6 +407,30 @@ class TaskHandle:  # src/trace.rs:70-135
                                                 **params)
                 else:
                     out = denoise_arrays(ctx, sums, sums_sq, rects, counts, **params)
+        return out
+
+
+    def _await_dual(self):
+        """await_() with settings.denoise_dual: the finished tiles' two halves through rmd_denoise_dual on `device`."""
+        st = self.settings
+        st.check_denoise()
+        cam = st.camera_settings
+        shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
+        halves = [np.zeros(shape) for _ in range(4)]
+        rects, counts_a, counts_b = [], [], []
+        while self._messages:
+            m = self._messages.pop(0)
+            if m.kind != "TileFinished":
+                break
+            t = m.tile
+            for dst, src in zip(halves, (t.data_a, t.data_sq_a, t.data_b, t.data_sq_b)):
+                dst[t.top : t.top + t.height, t.left : t.left + t.width] = src
+            rects.append((t.left, t.top, t.width, t.height))
+            counts_a.append(t.count_a)
+            counts_b.append(t.count_b)
+        with Context(self.device) as ctx:
+            out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k,
+                                         alpha=st.denoise_alpha)
         return out
 
 
@@ -381,9 +469,13 @@ def render_tiled(scene, settings, devices=(0,)):
     current sample count and takes no further passes; the others are sent as TileProgressed and go on.
 
     Denoised (settings.denoise, an extension): the passes render with second moments, every TileFinished tile carries them as `data_sq`, and
-    TaskHandle.await_() denoises the assembled frame on the first of `devices`."""
+    TaskHandle.await_() denoises the assembled frame on the first of `devices`.
+
+    Dual-buffer (settings.denoise_dual, an extension): _render_tiled_dual."""
     settings.check_adaptive()
     settings.check_denoise()
+    if settings.denoise_dual:
+        return _render_tiled_dual(scene, settings, devices)
     adaptive = settings.adaptive_threshold > 0.0
     moments = adaptive or settings.denoise
     cam = settings.camera_settings
@@ -440,3 +532,82 @@ def render_tiled(scene, settings, devices=(0,)):
             ctx.close()
     handle = TaskHandle(settings, messages, devices[0], scene if settings.denoise_features else None)
     return handle
+
+
+def _render_tiled_dual(scene, settings, devices):
+    """render_tiled with settings.denoise_dual: one device, four framebuffers.  Pass j (counted from 0; every live tile takes every pass) adds its
+    samples to half A when j is even and to half B when j is odd, so after an even NUMBER of full passes both halves hold the same count.  Every
+    TileFinished tile carries both halves; await_() returns rmd_denoise_dual's frame.
+
+    With settings.adaptive_denoised_threshold > 0: after every even number of passes that leaves live tiles below sample_count with at least
+    adaptive_min_samples samples, rmd_denoise_dual runs over the whole frame (finished tiles at the counts they finished with), rmd_tile_error_dual
+    over the live tiles, and a live tile at or below the threshold is sent as TileFinished, with that error, and takes no further passes."""
+    if len(devices) != 1:
+        raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
+    st = settings
+    cam = st.camera_settings
+    W, H = cam.backbuffer_width, cam.backbuffer_height
+    tiles = generate_tiles(W, H, st.tile_size)
+    adaptive = st.adaptive_denoised_threshold > 0.0
+    params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
+    opened = []  # closed in reverse order whichever way the body leaves
+    messages, finished = [], []
+    try:
+        ctx = Context(devices[0])
+        opened.append(ctx)
+        ds = DeviceScene(ctx, scene)
+        opened.append(ds)
+        fbs = [Framebuffer(ctx, W, H) for _ in range(4)]  # S_A, Q_A, S_B, Q_B
+        opened.extend(fbs)
+        if adaptive:
+            out_fb, err_img = Framebuffer(ctx, W, H), ErrorImage(ctx, W, H)
+            opened.extend([out_fb, err_img])
+        live = list(tiles)
+        done_rects, done_a, done_b = [], [], []  # the finished tiles and the counts they finished with
+        n_half = [0, 0]  # samples per pixel of a live tile in A and B
+        done, j = 0, 0
+
+        def finish(imgs, rect, error=None):
+            l, t, w, h = rect
+            a, a_sq, b, b_sq = (img[t : t + h, l : l + w].copy() for img in imgs)
+            tile = Tile(l, t, w, h, n_half[0] + n_half[1], a + b, error, a_sq + b_sq)
+            tile.data_a, tile.data_sq_a, tile.count_a, tile.data_b, tile.data_sq_b, tile.count_b = a, a_sq, n_half[0], b, b_sq, n_half[1]
+            finished.append(Message.TileFinished(tile))
+            done_rects.append(rect), done_a.append(n_half[0]), done_b.append(n_half[1])
+
+        while done < st.sample_count and live:
+            n = min(st.samples_per_iteration, st.sample_count - done)
+            half = j & 1
+            render_tiles(ctx, ds, cam, st, live, fbs[2 * half], done, n, sync=False, framebuffer_sq=fbs[2 * half + 1])
+            ctx.synchronize()
+            done, j = done + n, j + 1
+            n_half[half] += n
+            if done < st.sample_count:
+                errors = [None] * len(live)
+                if adaptive and j % 2 == 0 and done >= st.adaptive_min_samples:
+                    denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, done_a + [n_half[0]] * len(live), done_b + [n_half[1]] * len(live),
+                                 out_fb, err_img, **params)
+                    errors = tile_error_dual(ctx, err_img, live)
+                imgs = [fb.download() for fb in fbs]
+                still = []
+                for rect, e in zip(live, errors):
+                    if e is not None and e <= st.adaptive_denoised_threshold:
+                        finish(imgs, rect, float(e))  # converged: finished at the samples it has
+                    else:
+                        l, t, w, h = rect
+                        messages.append(Message.TileProgressed(Tile(l, t, w, h, done, imgs[0][t : t + h, l : l + w] + imgs[2][t : t + h, l : l + w],
+                                                                    None if e is None else float(e))))
+                        still.append(rect)
+                live = still
+        if live:
+            imgs = [fb.download() for fb in fbs]
+            for rect in live:
+                finish(imgs, rect)
+        messages = messages + finished  # progress snapshots first, then the finished tiles
+    finally:
+        for o in reversed(opened):
+            try:
+                o.close()
+            except Exception:  # noqa: BLE001 (a failing close must not keep the others open, nor hide the body's own error)
+                pass
+    return TaskHandle(settings, messages, devices[0])

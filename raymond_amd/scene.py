@@ -245,7 +245,8 @@ class Settings:
     def __init__(self, camera_settings, sample_count, tile_size=(32, 32), bounce_limit=5, samples_per_iteration=0,
                  worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
                  adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
-                 denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2):
+                 denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
+                 adaptive_min_samples=32):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -279,6 +280,15 @@ class Settings:
         self.denoise_features = bool(denoise_features)
         self.denoise_feature_k = float(denoise_feature_k)
         self.denoise_feature_tau = float(denoise_feature_tau)
+        # Dual-buffer denoising (an extension of the extension; False = off): a tile's passes go alternately into two half buffers A (even passes,
+        # counted from 0) and B (odd ones), and await_() returns rmd_denoise_dual's frame: each half filtered with the other's weights.  Needs
+        # denoise and samples_per_iteration > 0; one device only.
+        self.denoise_dual = bool(denoise_dual)
+        # Adaptive sampling by the FILTERED frame's error (0.0 = off; needs denoise_dual, excludes adaptive_threshold > 0): after every even pass
+        # that leaves live tiles with at least `adaptive_min_samples` samples, a live tile whose rmd_tile_error_dual — an absolute RMS in linear
+        # radiance that reads low (raymond_hip.h) — is at most the threshold is finished at the samples it has.
+        self.adaptive_denoised_threshold = float(adaptive_denoised_threshold)
+        self.adaptive_min_samples = adaptive_min_samples
         self.check_denoise()
 
     def check_adaptive(self):
@@ -306,6 +316,21 @@ class Settings:
             raise ValueError("denoise_feature_tau must be finite and > 0")
         if self.denoise_features and not self.denoise:
             raise ValueError("denoise_features needs denoise")
+        if self.denoise_dual and not self.denoise:
+            raise ValueError("denoise_dual needs denoise")
+        if self.denoise_dual and self.samples_per_iteration == 0:
+            raise ValueError("denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)")
+        if self.denoise_dual and self.denoise_features:
+            raise ValueError("denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight")
+        if not self.adaptive_denoised_threshold >= 0.0:
+            raise ValueError("adaptive_denoised_threshold must be >= 0 (0 = off)")
+        if self.adaptive_denoised_threshold > 0.0 and not self.denoise_dual:
+            raise ValueError("adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)")
+        if self.adaptive_denoised_threshold > 0.0 and self.adaptive_threshold > 0.0:
+            raise ValueError("adaptive_denoised_threshold and adaptive_threshold are mutually exclusive")
+        v = self.adaptive_min_samples
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("adaptive_min_samples must be an integer >= 0")
 
     def pod(self, sample_begin=0, sample_count=None):
         s = abi.Settings()
