@@ -62,7 +62,7 @@ enum {
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
-	                                 rmd_tile_error_dual) */
+	                                 rmd_tile_error_dual, rmd_denoise_dual_region) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -455,6 +455,29 @@ rmd_status rmd_denoise_dual(rmd_context *ctx, const double *accum_a_dev, const d
                             const double *accum_sq_b_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
                             const uint32_t *rect_counts_b, uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha,
                             double *out_dev, double *err_dev);
+/*
+ * rmd_denoise_dual for SOME PIXELS of the frame (an addition within ABI 6, found by its symbol).  Everything rmd_denoise_dual defines stays word
+ * for word: validity, dual validity, both weights, clamping, sum orders, out, err, the values of a pixel that is not dual-valid.  rects,
+ * rect_counts_a and rect_counts_b describe the WHOLE frame as there — neighbours and patch terms come from anywhere in it.  Added:
+ *     for every pixel inside a rect of `region`, out_dev and err_dev receive exactly the bytes rmd_denoise_dual would write there
+ *     every other double of out_dev and err_dev is not written at all: whatever it held before the call it holds after
+ * (the value of a pixel does not depend on how the frame is cut into workgroups: every sum order above is fixed per pixel).  So calls over
+ * disjoint regions into the same buffers compose to rmd_denoise_dual's frame, in any order, and the cost of a call follows the region's
+ * area.  `region` is a HOST array of n_region rects under the rules of `rects` — inside the frame, no two overlapping —,
+ * of any size and alignment; it need not coincide with `rects`.  n_region = 0 (region may then be NULL), or a region without pixels, writes
+ * nothing and returns RMD_OK; the call still waits and still reports an earlier device fault.  region NULL with n_region > 0, and every
+ * failure of rmd_denoise_dual, is RMD_ERR_INVALID_ARGUMENT before the device is touched.  Synchronous, like rmd_denoise_dual.  rmd_denoise and
+ * rmd_denoise_guided have no region form: nothing would call one.
+ */
+rmd_status rmd_denoise_dual_region(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, uint32_t n_rects,
+    const rmd_tile_rect *region, uint32_t n_region,
+    uint32_t radius, uint32_t patch_radius, double k, double alpha,
+    double *out_dev, double *err_dev);
 /*
  * Per-tile error of the delivered frame from rmd_denoise_dual's err_dev (W*H doubles):
  *     out_err_host[r] = sqrt((sum of err_p over rect r's pixels) / the rect's pixel count)

@@ -8,6 +8,10 @@
 // denoise_dual_kernel<TW>  — one cross pass: the weights from the six planes of the WEIGHT half, staged into LDS as denoise_kernel stages its
 //                            own (same apron, term image, row and column sums, two barriers per offset, each window summed directly), applied
 //                            to the u of the VALUE half.  Launched twice with the roles swapped: f_A (weights from B), then f_B (weights from A).
+//                            REGION = false: workgroup (bx, by) owns the TW x 16 pixels at (bx * TW, by * 16), the whole frame.  REGION = true
+//                            (rmd_denoise_dual_region): workgroup b owns the pixels of entry b of a BLOCK TABLE — a DualBlock: the block's origin
+//                            and the far corner (exclusive) of the region rect it was cut from — and writes only the pixels before that corner.
+//                            Nothing else differs: a pixel's value does not depend on where its workgroup's origin lies.
 //   Why six planes in LDS and the value half from global memory, not nine planes under a narrower tile: at r = 10, f = 3 nine f64 planes of a
 //   32-wide tile's apron are 175 KB, over the 160 KB budget, and a 24-wide tile's 151 KB leave no room for the term image (165 KB together).
 //   Nine planes fit only from TW = 16 down (137 KB): four waves a workgroup, one workgroup a CU, 6.9 apron pixels staged and 1.9 term
@@ -16,7 +20,7 @@
 //   consecutive offsets shift by one pixel, the access the guided kernel makes fourteen times per neighbour and found to be cache hits.  The
 //   LDS layout, its size (denoise_lds_bytes) and the tile width (denoise_tile_width) are therefore denoise_kernel's own.
 // dual_combine_kernel      — out = (n_A f_A + n_B f_B) / (n_A + n_B) and err = mean_c ((f_A - f_B) / 2)^2 for a dual-valid pixel, the merged
-//                            mean and NaN for any other.
+//                            mean and NaN for any other.  dual_combine_region_kernel: the same per pixel, over a block table's pixels only.
 // tile_error_dual_kernel   — one workgroup per rect: sqrt(sum err / pixels), +inf when an err of the rect is NaN.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
@@ -80,16 +84,23 @@ __global__ __launch_bounds__(256) void dual_planes_kernel(const double *__restri
 
 // Pw: the weight half's six planes (u, then v); Uv: the value half's three u planes; fout: W*H*3 doubles, pixel-interleaved, written at dual-valid
 // pixels only (dual_combine_kernel gives the others their value).
-template <int TW>
-__global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__restrict__ Pw, const double *__restrict__ Uv, uint32_t W, uint32_t H, int r, int f,
-                                                               double k2, double alpha, double *__restrict__ fout) {
+// table: REGION only (null otherwise), one entry per workgroup.
+template <int TW, bool REGION>
+__global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__restrict__ Pw, const double *__restrict__ Uv, const DualBlock *__restrict__ table, uint32_t W,
+                                                               uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ fout) {
 	extern __shared__ double lds[];
 	constexpr int TH = (int)kDenoiseTile, NT = TW * TH;
 	const int R = r + f, AW = TW + 2 * R, AA = AW * (TH + 2 * R), PW = TW + 2 * f, PP = PW * (TH + 2 * f);
 	double *U = lds, *V = lds + 3 * AA;           // planes c * AA + (apron row * AW + apron column)
 	double *T = lds + 6 * AA, *Hs = T + PP;        // the term image (TH + 2f rows of PW) and its row sums (TH + 2f rows of TW)
 	uint32_t *Tc = reinterpret_cast<uint32_t *>(Hs + (TH + 2 * f) * TW), *Hc = Tc + PP;
-	const int64_t x0 = (int64_t)blockIdx.x * TW, y0 = (int64_t)blockIdx.y * TH;
+	int64_t x0, y0, x_end, y_end; // the tile's origin; the pixels it may write lie before (x_end, y_end)
+	if constexpr (REGION) {
+		const DualBlock e = table[blockIdx.x];
+		x0 = e.x0, y0 = e.y0, x_end = e.x_end, y_end = e.y_end;
+	} else {
+		x0 = (int64_t)blockIdx.x * TW, y0 = (int64_t)blockIdx.y * TH, x_end = W, y_end = H;
+	}
 	const int tid = threadIdx.x;
 	const size_t N = (size_t)W * H;
 
@@ -120,7 +131,7 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 	// this thread's output pixel; the offsets that keep q = p + d inside the frame
 	const int px = tid % TW, py = tid / TW;
 	const int64_t gx = x0 + px, gy = y0 + py;
-	const bool inside = gx < (int64_t)W && gy < (int64_t)H;
+	const bool inside = gx < x_end && gy < y_end; // (a table entry's far corner lies inside the frame)
 	const int ip = (py + R) * AW + (px + R);
 	const bool p_ok = inside && U[ip] == U[ip];
 	const int dx_lo = (int)max((int64_t)-r, -gx), dx_hi = (int)min((int64_t)r, (int64_t)W - 1 - gx);
@@ -184,11 +195,9 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 // fa = out (in place), fb: the two cross passes' results.  Dual-valid p: out = (n_A*f_A + n_B*f_B) / (n_A + n_B) — the two products, their sum, one
 // division —, err = (h_0^2 + h_1^2 + h_2^2) / 3 with h_c = (f_Ac - f_Bc) / 2, summed in channel order.  Any other p: the merged mean as IEEE gives it
 // and err = NaN.  err may be null.
-__global__ __launch_bounds__(256) void dual_combine_kernel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
-                                                           const uint32_t *__restrict__ n_b, const double *__restrict__ planes, const double *__restrict__ fb,
-                                                           size_t N, double *out, double *__restrict__ err) {
-	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-	if (i >= N) return;
+__device__ inline void dual_combine_pixel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
+                                          const uint32_t *__restrict__ n_b, const double *__restrict__ planes, const double *__restrict__ fb, size_t i, double *out,
+                                          double *__restrict__ err) {
 	const double na = (double)n_a[i], nb = (double)n_b[i];
 	const double nsum = na + nb;
 	const double ua0 = planes[i];
@@ -208,12 +217,27 @@ __global__ __launch_bounds__(256) void dual_combine_kernel(const double *__restr
 		if (err) err[i] = __builtin_nan("");
 	}
 }
+__global__ __launch_bounds__(256) void dual_combine_kernel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
+                                                           const uint32_t *__restrict__ n_b, const double *__restrict__ planes, const double *__restrict__ fb,
+                                                           size_t N, double *out, double *__restrict__ err) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i < N) dual_combine_pixel(SA, SB, n_a, n_b, planes, fb, i, out, err);
+}
+// One workgroup of tw * 16 threads per block-table entry, thread t at (t % tw, t / tw) from the entry's origin: the pixels denoise_dual_kernel wrote.
+__global__ __launch_bounds__(512) void dual_combine_region_kernel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
+                                                                  const uint32_t *__restrict__ n_b, const double *__restrict__ planes, const double *__restrict__ fb,
+                                                                  const DualBlock *__restrict__ table, uint32_t tw, uint32_t W, double *out, double *__restrict__ err) {
+	const DualBlock e = table[blockIdx.x];
+	const uint32_t x = e.x0 + threadIdx.x % tw, y = e.y0 + threadIdx.x / tw; // (no wrap: the origin lies before the far corner, 512 pixels at most beyond it)
+	if (x < e.x_end && y < e.y_end) dual_combine_pixel(SA, SB, n_a, n_b, planes, fb, (size_t)x + (size_t)y * W, out, err);
+}
 
 hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
                                const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, uint32_t count_image_columns,
                                uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k, double alpha, uint32_t *n_img, double *planes,
-                               double *f_b, double *out, double *err) {
+                               double *f_b, const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+	if (table && n_blocks == 0) return hipSuccess; // a region without pixels: nothing would read the planes
 	const size_t N = (size_t)W * H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
 	hipError_t e = hipMemsetAsync(n_img, 0, 2u * N * sizeof(uint32_t), stream);
@@ -228,20 +252,24 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits, as for denoise_kernel)
-	const void *fn = tw == 32u ? reinterpret_cast<const void *>(&denoise_dual_kernel<32>) : reinterpret_cast<const void *>(&denoise_dual_kernel<24>);
+	const void *fn = table ? (tw == 32u ? reinterpret_cast<const void *>(&denoise_dual_kernel<32, true>) : reinterpret_cast<const void *>(&denoise_dual_kernel<24, true>))
+	                       : (tw == 32u ? reinterpret_cast<const void *>(&denoise_dual_kernel<32, false>) : reinterpret_cast<const void *>(&denoise_dual_kernel<24, false>));
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-	const dim3 grid((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
+	const dim3 grid = table ? dim3(n_blocks) : dim3((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
 	const int ri = (int)radius, fi = (int)patch_radius;
 	const double k2 = k * k;
 	const double *PA = planes, *PB = planes + 6u * N;
 	for (int pass = 0; pass < 2; pass++) { // f_A: weights from B applied to u_A, into out; f_B: weights from A applied to u_B, into f_b
 		const double *Pw = pass == 0 ? PB : PA, *Uv = pass == 0 ? PA : PB;
 		double *fout = pass == 0 ? out : f_b;
-		if (tw == 32u) hipLaunchKernelGGL(denoise_dual_kernel<32>, grid, dim3(32 * kDenoiseTile), lds, stream, Pw, Uv, W, H, ri, fi, k2, alpha, fout);
-		else hipLaunchKernelGGL(denoise_dual_kernel<24>, grid, dim3(24 * kDenoiseTile), lds, stream, Pw, Uv, W, H, ri, fi, k2, alpha, fout);
+		if (table && tw == 32u) hipLaunchKernelGGL((denoise_dual_kernel<32, true>), grid, dim3(32 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
+		else if (table) hipLaunchKernelGGL((denoise_dual_kernel<24, true>), grid, dim3(24 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
+		else if (tw == 32u) hipLaunchKernelGGL((denoise_dual_kernel<32, false>), grid, dim3(32 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
+		else hipLaunchKernelGGL((denoise_dual_kernel<24, false>), grid, dim3(24 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
-	hipLaunchKernelGGL(dual_combine_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, N, out, err);
+	if (table) hipLaunchKernelGGL(dual_combine_region_kernel, grid, dim3(tw * kDenoiseTile), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, table, tw, W, out, err);
+	else hipLaunchKernelGGL(dual_combine_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, N, out, err);
 	return hipGetLastError();
 }
 

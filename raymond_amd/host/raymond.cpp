@@ -398,8 +398,8 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 // settings.denoise_dual: the one worker of a dual-buffer render, a plain loop over passes (every live tile takes every pass).  Four framebuffers:
 // pass j, counted from 0, adds its samples to half A (fbs 0, 1) when j is even and to half B (fbs 2, 3) when j is odd.  With
 // adaptive_denoised_threshold > 0, after every even number of passes that leaves the live tiles below sample_count with at least
-// adaptive_min_samples: rmd_denoise_dual over the whole frame (finished tiles at the counts they finished with), rmd_tile_error_dual over the live
-// tiles, and the tiles at or below the threshold are finished.  Progress snapshots go out as they are made, the finished tiles at the end.
+// adaptive_min_samples: rmd_denoise_dual_region over the live tiles' pixels of the whole frame (finished tiles at the counts they finished with),
+// rmd_tile_error_dual over the live tiles, and the tiles at or below the threshold are finished.  Progress snapshots go out as they are made, the finished tiles at the end.
 void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene scene, Settings st) {
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
@@ -478,9 +478,10 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 				std::vector<uint32_t> ca(done_a), cb(done_b);
 				rects.insert(rects.end(), live.begin(), live.end());
 				ca.insert(ca.end(), live.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), live.size(), (uint32_t)n_half[1]);
-				check(rmd_denoise_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(), (uint32_t)rects.size(), st.denoise_radius,
-				                       st.denoise_patch, st.denoise_k, st.denoise_alpha, fbs[4], fbs[5]),
-				      ctx, "rmd_denoise_dual");
+				// only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
+				check(rmd_denoise_dual_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(), (uint32_t)rects.size(), live.data(),
+				                              (uint32_t)live.size(), st.denoise_radius, st.denoise_patch, st.denoise_k, st.denoise_alpha, fbs[4], fbs[5]),
+				      ctx, "rmd_denoise_dual_region");
 				errors.resize(live.size());
 				check(rmd_tile_error_dual(ctx, fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), errors.data()), ctx, "rmd_tile_error_dual");
 			}

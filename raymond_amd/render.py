@@ -270,31 +270,40 @@ class ErrorImage(Framebuffer):
         raise NotImplementedError("error images have no tile-rect transfers")
 
 
-def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0):
+def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0, region=None):
     """rmd_denoise_dual: `out_framebuffer` = the cross-filtered means of the two sample halves `half_a` and `half_b`, each a (sums, sums of squares)
     pair of Framebuffers; rect i holds counts_a[i] and counts_b[i] samples per pixel in them.  `error_image` (an ErrorImage, optional) receives the
-    per-pixel error estimate."""
+    per-pixel error estimate.  `region` (a list of rects, possibly empty): rmd_denoise_dual_region — only the pixels of those rects are written, with
+    the bytes the whole-frame call gives them; None is the whole-frame call."""
     counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
     counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
     if len(counts_a) != len(rects) or len(counts_b) != len(rects):
         raise ValueError("one sample count per rect and half")
     fb = half_a[0]
-    ctx.check(ctx.L.rmd_denoise_dual(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, fb.width, fb.height, tile_array(rects),
-                                     counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius),
-                                     int(patch_radius), float(k), float(alpha), out_framebuffer.ptr, None if error_image is None else error_image.ptr))
+    head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, fb.width, fb.height, tile_array(rects),
+            counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects))
+    tail = (int(radius), int(patch_radius), float(k), float(alpha), out_framebuffer.ptr, None if error_image is None else error_image.ptr)
+    if region is None:
+        ctx.check(ctx.L.rmd_denoise_dual(*head, *tail))
+    else:
+        region = list(region)
+        ctx.check(ctx.L.rmd_denoise_dual_region(*head, tile_array(region), len(region), *tail))
 
 
-def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, **params):
-    """denoise_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate out."""
+def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, region=None, out_init=None, err_init=None, **params):
+    """denoise_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate out.
+    `out_init` (H, W, 3) and `err_init` (H, W): what the two outputs hold before the call — what a pixel outside `region` still holds after it."""
     H, W = sums_a.shape[0], sums_a.shape[1]
     opened = []
     try:
-        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, None):
+        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, out_init):
             opened.append(Framebuffer(ctx, W, H))
             if arr is not None:
                 opened[-1].upload(arr)
         opened.append(ErrorImage(ctx, W, H))
-        denoise_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5], **params)
+        if err_init is not None:
+            opened[-1].upload(err_init)
+        denoise_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5], region=region, **params)
         return opened[4].download(), opened[5].download()
     finally:
         for b in opened:
@@ -540,8 +549,8 @@ def _render_tiled_dual(scene, settings, devices):
     TileFinished tile carries both halves; await_() returns rmd_denoise_dual's frame.
 
     With settings.adaptive_denoised_threshold > 0: after every even number of passes that leaves live tiles below sample_count with at least
-    adaptive_min_samples samples, rmd_denoise_dual runs over the whole frame (finished tiles at the counts they finished with), rmd_tile_error_dual
-    over the live tiles, and a live tile at or below the threshold is sent as TileFinished, with that error, and takes no further passes."""
+    adaptive_min_samples samples, rmd_denoise_dual_region filters the live tiles' pixels of the whole frame (finished tiles at the counts they
+    finished with: the bytes rmd_denoise_dual would give those pixels), rmd_tile_error_dual runs over the live tiles, and a live tile at or below the threshold is sent as TileFinished, with that error, and takes no further passes."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     st = settings
@@ -567,13 +576,18 @@ def _render_tiled_dual(scene, settings, devices):
         n_half = [0, 0]  # samples per pixel of a live tile in A and B
         done, j = 0, 0
 
-        def finish(imgs, rect, error=None):
-            l, t, w, h = rect
-            a, a_sq, b, b_sq = (img[t : t + h, l : l + w].copy() for img in imgs)
-            tile = Tile(l, t, w, h, n_half[0] + n_half[1], a + b, error, a_sq + b_sq)
-            tile.data_a, tile.data_sq_a, tile.count_a, tile.data_b, tile.data_sq_b, tile.count_b = a, a_sq, n_half[0], b, b_sq, n_half[1]
-            finished.append(Message.TileFinished(tile))
-            done_rects.append(rect), done_a.append(n_half[0]), done_b.append(n_half[1])
+        def finish(rects, errors=None):
+            """TileFinished for `rects`: both halves' sums and sums of squares, the tiles' pixels only."""
+            if not rects:
+                return
+            packed = [fb.download_tiles(rects) for fb in fbs]
+            for i, rect in enumerate(rects):
+                l, t, w, h = rect
+                a, a_sq, b, b_sq = (p[i].copy() for p in packed)
+                tile = Tile(l, t, w, h, n_half[0] + n_half[1], a + b, None if errors is None else errors[i], a_sq + b_sq)
+                tile.data_a, tile.data_sq_a, tile.count_a, tile.data_b, tile.data_sq_b, tile.count_b = a, a_sq, n_half[0], b, b_sq, n_half[1]
+                finished.append(Message.TileFinished(tile))
+                done_rects.append(rect), done_a.append(n_half[0]), done_b.append(n_half[1])
 
         while done < st.sample_count and live:
             n = min(st.samples_per_iteration, st.sample_count - done)
@@ -585,24 +599,19 @@ def _render_tiled_dual(scene, settings, devices):
             if done < st.sample_count:
                 errors = [None] * len(live)
                 if adaptive and j % 2 == 0 and done >= st.adaptive_min_samples:
+                    # only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
                     denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, done_a + [n_half[0]] * len(live), done_b + [n_half[1]] * len(live),
-                                 out_fb, err_img, **params)
+                                 out_fb, err_img, region=live, **params)
                     errors = tile_error_dual(ctx, err_img, live)
-                imgs = [fb.download() for fb in fbs]
-                still = []
-                for rect, e in zip(live, errors):
-                    if e is not None and e <= st.adaptive_denoised_threshold:
-                        finish(imgs, rect, float(e))  # converged: finished at the samples it has
-                    else:
-                        l, t, w, h = rect
-                        messages.append(Message.TileProgressed(Tile(l, t, w, h, done, imgs[0][t : t + h, l : l + w] + imgs[2][t : t + h, l : l + w],
-                                                                    None if e is None else float(e))))
-                        still.append(rect)
+                conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
+                finish([r for r, c in zip(live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
+                still = [r for r, c in zip(live, conv) if not c]
+                if still:  # progress snapshots: the two halves' sums added
+                    pa, pb = fbs[0].download_tiles(still), fbs[2].download_tiles(still)
+                    for (l, t, w, h), e, a, b in zip(still, [e for e, c in zip(errors, conv) if not c], pa, pb):
+                        messages.append(Message.TileProgressed(Tile(l, t, w, h, done, a + b, None if e is None else float(e))))
                 live = still
-        if live:
-            imgs = [fb.download() for fb in fbs]
-            for rect in live:
-                finish(imgs, rect)
+        finish(live)
         messages = messages + finished  # progress snapshots first, then the finished tiles
     finally:
         for o in reversed(opened):
