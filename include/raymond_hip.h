@@ -62,7 +62,8 @@ enum {
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
-	                                 rmd_tile_error_dual, rmd_denoise_dual_region) */
+	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
+	                                 rmd_denoise_dual_guided_region) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -449,7 +450,8 @@ rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const d
  * Arguments (all checked before the device is touched): rmd_denoise's rules for radius, patch_radius, k, alpha, width, height and the rects;
  * the four sum buffers and out_dev non-NULL; no two of the six ranges (five of W*H*3 doubles, err_dev's W*H) overlap; rect_counts_a and
  * rect_counts_b are HOST arrays of n_rects entries, non-NULL when n_rects > 0.  Anything else is RMD_ERR_INVALID_ARGUMENT.  Synchronous, and
- * reports an earlier device fault, like rmd_denoise.  The feature weight of rmd_denoise_guided is not part of this call.
+ * reports an earlier device fault, like rmd_denoise.  The feature weight of rmd_denoise_guided is not part of this call:
+ * rmd_denoise_dual_guided adds it.
  */
 rmd_status rmd_denoise_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
                             const double *accum_sq_b_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
@@ -477,6 +479,56 @@ rmd_status rmd_denoise_dual_region(rmd_context *ctx,
     const uint32_t *rect_counts_b, uint32_t n_rects,
     const rmd_tile_rect *region, uint32_t n_region,
     uint32_t radius, uint32_t patch_radius, double k, double alpha,
+    double *out_dev, double *err_dev);
+/*
+ * rmd_denoise_dual with the FEATURE WEIGHT of rmd_denoise_guided (an addition within ABI 6, found by its symbol).  Everything rmd_denoise_dual
+ * defines stays word for word: validity, dual validity, w_A, w_B, clamping, every sum order, out, err, the values of a pixel that is not
+ * dual-valid.  Added, with F = feat_dev, G = feat_sq_dev (feature buffers as rmd_render_features writes them):
+ *     pixel i of rect j holds n_Fi = rect_counts_f[j] feature samples, a pixel no rect covers 0.  The features are NOT split into halves:
+ *     they carry their own count, so a caller may render them at any count (the render loops pass n_A + n_B)
+ *     for j = 0..6:  f_ij = F_ij / n_Fi;   g_ij = max(0, (G_ij - F_ij*f_ij) / (n_Fi - 1)) / n_Fi
+ *     pixel i is FEATURE-VALID if it is dual-valid, n_Fi >= 2 and its fourteen F and G values are finite
+ *     s_ij, Phi_j(p, q), D_f and w_f = exp(-D_f) are exactly rmd_denoise_guided's: the same operations in the same order, the division by
+ *             eps + k_f^2 * max(tau * s_pj, g_pj), a NaN Phi_j skipped by the comparison
+ *     the weight of the pass that filters A:  w_f if p and q are both feature-valid and w_f < w_B(p, q), else w_B(p, q)
+ *     the weight of the pass that filters B:  the same with w_A(p, q); the same w_f enters both passes
+ * So the features cut a weight, never raise one; they are noise-free beside the colour (one first hit per sample) and are shared by both
+ * halves, which keeps an edge that lies below the noise out of BOTH filtered halves: the bias that rmd_denoise_dual's err cannot see, because
+ * both halves share it, is removed rather than estimated.  With the two halves equal and rect_counts_f equal to their
+ * counts, f_A = f_B = rmd_denoise_guided of either half bit for bit and err = 0.  All-zero features with counts >= 2 give w_f = 1 for every pair
+ * and hence rmd_denoise_dual's bytes.
+ * feat_dev = feat_sq_dev = NULL is exactly rmd_denoise_dual (rect_counts_f, k_f and tau are then not read).  Beyond rmd_denoise_dual's rules:
+ * one of the two NULL and the other not; with features present, rect_counts_f (a HOST array of n_rects entries) NULL while n_rects > 0, k_f or
+ * tau not finite or not > 0, either W*H*7-double feature range overlapping the other or any of the six ranges of rmd_denoise_dual:
+ * RMD_ERR_INVALID_ARGUMENT before the device is touched.  Values a caller may start from: k_f 1.0, tau 1e-2, as for rmd_denoise_guided.
+ * Synchronous, and reports an earlier device fault, like rmd_denoise_dual.
+ */
+rmd_status rmd_denoise_dual_guided(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau,
+    double *out_dev, double *err_dev);
+/*
+ * rmd_denoise_dual_guided for SOME PIXELS of the frame: rmd_denoise_dual_region's rules unchanged, on rmd_denoise_dual_guided's definition.  For
+ * every pixel inside a rect of `region`, out_dev and err_dev receive exactly the bytes rmd_denoise_dual_guided would write there; every other
+ * double of the two is not written at all.  rects and the three count arrays describe the WHOLE frame.  n_region = 0 (region may then be NULL),
+ * or a region without pixels, writes nothing and returns RMD_OK; the call still waits and still reports an earlier device fault.
+ * feat_dev = feat_sq_dev = NULL is exactly rmd_denoise_dual_region (rect_counts_f, k_f and tau are then not read).  Every failure of
+ * rmd_denoise_dual_region or of rmd_denoise_dual_guided is RMD_ERR_INVALID_ARGUMENT before the device is touched.  Synchronous.
+ */
+rmd_status rmd_denoise_dual_guided_region(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    const rmd_tile_rect *region, uint32_t n_region,
+    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau,
     double *out_dev, double *err_dev);
 /*
  * Per-tile error of the delivered frame from rmd_denoise_dual's err_dev (W*H doubles):

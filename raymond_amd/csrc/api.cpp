@@ -1029,10 +1029,12 @@ rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const d
 }
 
 // ---------------------------------------------------------------- dual-buffer denoising (denoise_dual.hip)
-// region null: rmd_denoise_dual, every pixel.  region not null: rmd_denoise_dual_region, the pixels of its n_region rects only
-static rmd_status denoise_dual_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, uint32_t width, uint32_t height,
-                                    const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, const rmd_tile_rect *region,
-                                    uint32_t n_region, uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev, double *err_dev) {
+// region null: rmd_denoise_dual, every pixel.  region not null: rmd_denoise_dual_region, the pixels of its n_region rects only.  feat / feat_sq not
+// null: the guided forms (counts_f: the features' own counts)
+static rmd_status denoise_dual_impl(const char *what, rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
+                                    const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
+                                    const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region,
+                                    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
 	if (rmd_status s = bind(ctx)) return s;
 	// the block table: each region rect cut into tiles of the kernel's own shape from the rect's corner, row by row
 	std::vector<rmd::DualBlock> table;
@@ -1043,7 +1045,7 @@ static rmd_status denoise_dual_impl(rmd_context *ctx, const double *sa, const do
 			for (uint32_t y = 0; y < r.height; y += th)
 				for (uint32_t x = 0; x < r.width; x += tw) table.push_back(rmd::DualBlock{r.left + x, r.top + y, r.left + r.width, r.top + r.height});
 		}
-		if (table.size() > 0x7fffffffu) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_denoise_dual_region: region of more than 2^31 - 1 workgroups");
+		if (table.size() > 0x7fffffffu) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(what) + ": region of more than 2^31 - 1 workgroups");
 		if (table.empty()) { // nothing to write: the call still waits and reports an earlier fault
 			RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 			return rmd::check_fault(ctx);
@@ -1051,15 +1053,22 @@ static rmd_status denoise_dual_impl(rmd_context *ctx, const double *sa, const do
 	}
 	// device scratch: [the twelve u / v planes: 12 * W*H doubles][f_B: 3 * W*H doubles][both halves' per-pixel counts: 2 * W*H uint32, padded to 16 bytes]
 	// [the block table: 16 bytes each][rects: 16 bytes each][counts of A, then of B: 4 bytes each]
+	// guided only, from the next 16-byte boundary: [the planar per-pixel f and g: 14 * W*H doubles][the features' per-pixel counts: W*H uint32, padded to
+	// 16 bytes][the features' counts: 4 bytes each]
 	const size_t N = (size_t)width * height;
 	const size_t plane_bytes = N * 12u * sizeof(double), fb_bytes = N * 3u * sizeof(double);
 	const size_t img_bytes = (2u * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
 	const size_t table_bytes = table.size() * sizeof(rmd::DualBlock);
 	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
+	const size_t plain_bytes = plane_bytes + fb_bytes + img_bytes + table_bytes + rect_bytes + 2u * count_bytes, base_bytes = (plain_bytes + 15u) & ~(size_t)15u;
+	const size_t fplane_bytes = N * 2u * RMD_FEATURE_CHANNELS * sizeof(double), fimg_bytes = (N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
 	rmd::DeviceBuffer scratch;
-	RMD_HIP(ctx, scratch.alloc(plane_bytes + fb_bytes + img_bytes + table_bytes + rect_bytes + 2u * count_bytes));
+	RMD_HIP(ctx, scratch.alloc(feat ? base_bytes + fplane_bytes + fimg_bytes + count_bytes : plain_bytes));
 	unsigned char *d = scratch.as<unsigned char>();
 	double *d_planes = scratch.as<double>();
+	double *d_fplanes = feat ? reinterpret_cast<double *>(d + base_bytes) : nullptr;
+	uint32_t *d_fimg = feat ? reinterpret_cast<uint32_t *>(d + base_bytes + fplane_bytes) : nullptr;
+	uint32_t *d_counts_f = feat ? reinterpret_cast<uint32_t *>(d + base_bytes + fplane_bytes + fimg_bytes) : nullptr;
 	double *d_fb = reinterpret_cast<double *>(d + plane_bytes);
 	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + plane_bytes + fb_bytes);
 	rmd::DualBlock *d_table = region ? reinterpret_cast<rmd::DualBlock *>(d + plane_bytes + fb_bytes + img_bytes) : nullptr;
@@ -1069,28 +1078,33 @@ static rmd_status denoise_dual_impl(rmd_context *ctx, const double *sa, const do
 		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
 		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
 		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		if (feat) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
 	}
 	if (region) RMD_HIP(ctx, hipMemcpyAsync(d_table, table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
 	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
 	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
 	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, sa, qa, sb, qb, d_rects, d_counts_a, d_counts_b, n_rects, columns, width, height, radius, patch_radius, k, alpha,
-	                                      d_img, d_planes, d_fb, d_table, (uint32_t)table.size(), out_dev, err_dev));
+	RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, sa, qa, sb, qb, feat, feat_sq, d_rects, d_counts_a, d_counts_b, d_counts_f, n_rects, columns, width, height, radius,
+	                                      patch_radius, k, alpha, k_f, tau, d_img, d_planes, d_fb, d_fimg, d_fplanes, d_table, (uint32_t)table.size(), out_dev, err_dev));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the table is read by the copy until here)
 	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
 }
 
-// rmd_denoise_dual and rmd_denoise_dual_region: one argument check, one launch path (`what`: the entry point's name, for the messages; `regional`: the
-// second of the two, whose region may still be NULL when n_region is 0)
+// rmd_denoise_dual, rmd_denoise_dual_region and their guided forms: one argument check, one launch path (`what`: the entry point's name, for the
+// messages; `regional`: a region form, whose region may still be NULL when n_region is 0; feat_dev / feat_sq_dev both NULL: no feature weight —
+// rect_counts_f, k_f and tau are then not read)
 static rmd_status denoise_dual_checked(const char *what, bool regional, rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev,
-                                       const double *accum_b_dev, const double *accum_sq_b_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                                       const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region,
-                                       uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev, double *err_dev) {
+                                       const double *accum_b_dev, const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width,
+                                       uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
+                                       const uint32_t *rect_counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius,
+                                       uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
 	const std::string name = std::string(what) + ": ";
 	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
 	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
 		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
 	if (regional && n_region && !region) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region is NULL with n_region > 0");
+	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
+	if (feat_dev && n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "rect_counts_f is NULL with n_rects > 0");
 	{ // no two of the six ranges overlap: five of W*H*3 doubles, err_dev's W*H
 		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
 		const unsigned __int128 at[6] = {(uintptr_t)accum_a_dev, (uintptr_t)accum_sq_a_dev, (uintptr_t)accum_b_dev, (uintptr_t)accum_sq_b_dev, (uintptr_t)out_dev, (uintptr_t)err_dev};
@@ -1099,34 +1113,63 @@ static rmd_status denoise_dual_checked(const char *what, bool regional, rmd_cont
 			for (int j = i + 1; j < (err_dev ? 6 : 5); j++)
 				if (at[i] < at[j] + len[j] && at[j] < at[i] + len[i])
 					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, out_dev and err_dev must not alias");
+		if (feat_dev) { // nor do the two W*H*7-double feature ranges, each other or any of the six
+			const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
+			const unsigned __int128 f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
+			bool bad = f < g + fbytes && g < f + fbytes;
+			for (int i = 0; i < (err_dev ? 6 : 5); i++) bad = bad || (f < at[i] + len[i] && at[i] < f + fbytes) || (g < at[i] + len[i] && at[i] < g + fbytes);
+			if (bad) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must not alias each other, the sum buffers, out_dev or err_dev");
+		}
 	}
 	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
 	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
 	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
 	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
+	if (feat_dev) {
+		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
+		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
+	}
 	return rmd::guarded(ctx, what, [&] {
 		const char *why = nullptr;
 		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
 		if (regional && !denoise_rects_ok(region, n_region, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region: " + why);
 		const rmd_tile_rect none{0, 0, 0, 0}; // (an empty region may come as NULL: the launch path tells the two calls apart by the pointer)
-		return denoise_dual_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, width, height, rects, rect_counts_a, rect_counts_b, n_rects,
-		                         regional ? (region ? region : &none) : nullptr, regional ? n_region : 0u, radius, patch_radius, k, alpha, out_dev, err_dev);
+		return denoise_dual_impl(what, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
+		                         rect_counts_b, rect_counts_f, n_rects, regional ? (region ? region : &none) : nullptr, regional ? n_region : 0u, radius, patch_radius, k,
+		                         alpha, k_f, tau, out_dev, err_dev);
 	});
 }
 
 rmd_status rmd_denoise_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
                             uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
                             uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev, double *err_dev) {
-	return denoise_dual_checked("rmd_denoise_dual", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, width, height, rects, rect_counts_a, rect_counts_b,
-	                            n_rects, nullptr, 0u, radius, patch_radius, k, alpha, out_dev, err_dev);
+	return denoise_dual_checked("rmd_denoise_dual", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, nullptr, nullptr, width, height, rects,
+	                            rect_counts_a, rect_counts_b, nullptr, n_rects, nullptr, 0u, radius, patch_radius, k, alpha, 0.0, 0.0, out_dev, err_dev);
 }
 
 rmd_status rmd_denoise_dual_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
                                    uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
                                    uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius, uint32_t patch_radius, double k, double alpha,
                                    double *out_dev, double *err_dev) {
-	return denoise_dual_checked("rmd_denoise_dual_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, width, height, rects, rect_counts_a,
-	                            rect_counts_b, n_rects, region, n_region, radius, patch_radius, k, alpha, out_dev, err_dev);
+	return denoise_dual_checked("rmd_denoise_dual_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, nullptr, nullptr, width, height, rects,
+	                            rect_counts_a, rect_counts_b, nullptr, n_rects, region, n_region, radius, patch_radius, k, alpha, 0.0, 0.0, out_dev, err_dev);
+}
+
+rmd_status rmd_denoise_dual_guided(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t radius,
+                                   uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
+	return denoise_dual_checked("rmd_denoise_dual_guided", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects,
+	                            rect_counts_a, rect_counts_b, rect_counts_f, n_rects, nullptr, 0u, radius, patch_radius, k, alpha, k_f, tau, out_dev, err_dev);
+}
+
+rmd_status rmd_denoise_dual_guided_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                          const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                          const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
+                                          uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius, uint32_t patch_radius, double k,
+                                          double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
+	return denoise_dual_checked("rmd_denoise_dual_guided_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height,
+	                            rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, region, n_region, radius, patch_radius, k, alpha, k_f, tau, out_dev, err_dev);
 }
 
 static rmd_status tile_error_dual_impl(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,

@@ -21,6 +21,12 @@
 //   LDS layout, its size (denoise_lds_bytes) and the tile width (denoise_tile_width) are therefore denoise_kernel's own.
 // dual_combine_kernel      — out = (n_A f_A + n_B f_B) / (n_A + n_B) and err = mean_c ((f_A - f_B) / 2)^2 for a dual-valid pixel, the merged
 //                            mean and NaN for any other.  dual_combine_region_kernel: the same per pixel, over a block table's pixels only.
+// GUIDED (rmd_denoise_dual_guided; denoise_dual_kernel<TW, REGION, DualGuide>, instantiations of their own so that the unguided four are compiled
+// exactly as without the feature): dual_feature_planes_kernel writes the planar per-pixel f and g of the feature buffers at their OWN count n_F
+// (14 planes of W*H doubles; a pixel that is not feature-valid — dual-valid by dual_planes_kernel's mark, n_F >= 2, fourteen finite sums — keeps a
+// NaN in its f of channel 0), and step 3 of each cross pass makes rmd_denoise_guided's w_f of the pixel pair and takes min(w, w_f): p's seven f, g
+// and denominators in registers, q's fourteen values per taken neighbour from the planes in global memory.  w_f is evaluated in BOTH passes
+// (DESIGN.md section 15); the LDS layout is unchanged.
 // tile_error_dual_kernel   — one workgroup per rect: sqrt(sum err / pixels), +inf when an err of the rect is NaN.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
@@ -82,12 +88,65 @@ __global__ __launch_bounds__(256) void dual_planes_kernel(const double *__restri
 	}
 }
 
+// (count_image_kernel of denoise.hip for the features' own counts: n_f is zeroed by the caller)
+__global__ __launch_bounds__(256) void dual_feature_count_image_kernel(const rmd_tile_rect *__restrict__ rects, const uint32_t *__restrict__ counts_f, uint32_t W,
+                                                                       uint32_t *__restrict__ n_f) {
+	const rmd_tile_rect r = rects[blockIdx.x];
+	const uint32_t nf = counts_f[blockIdx.x];
+	const uint64_t n_px = (uint64_t)r.width * r.height;
+	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
+		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
+		n_f[(size_t)(r.left + x) + (size_t)(r.top + y) * W] = nf;
+	}
+}
+
+// feature_planes_kernel of denoise.hip at the features' own count n_F: f_j = F_j / n_F, g_j = max(0, (G_j - F_j*f_j) / (n_F - 1)) / n_F into planes j
+// and 7 + j of `fplanes`.  A pixel that is not FEATURE-VALID (dual-valid: planes[i], dual_planes_kernel's mark, is no NaN; n_F >= 2; its fourteen F and G
+// values finite) gets a NaN in plane 0.
+__global__ __launch_bounds__(256) void dual_feature_planes_kernel(const double *__restrict__ planes, const double *__restrict__ F, const double *__restrict__ G,
+                                                                  const uint32_t *__restrict__ n_f, size_t N, double *__restrict__ fplanes) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const uint32_t n = n_f[i];
+	const double nd = (double)n;
+	const double ua0 = planes[i];
+	bool valid = ua0 == ua0 && n >= 2u;
+	double fv[kDenoiseFeat], gv[kDenoiseFeat];
+#pragma unroll
+	for (int j = 0; j < kDenoiseFeat; j++) {
+		const double s = F[i * kDenoiseFeat + j], q = G[i * kDenoiseFeat + j];
+		valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
+		fv[j] = s / nd;
+		double t = (q - s * fv[j]) / (nd - 1.0);
+		if (t < 0.0) t = 0.0;
+		gv[j] = t / nd;
+	}
+#pragma unroll
+	for (int j = 0; j < kDenoiseFeat; j++) fplanes[(size_t)j * N + i] = (j == 0 && !valid) ? __builtin_nan("") : fv[j], fplanes[(size_t)(kDenoiseFeat + j) * N + i] = gv[j];
+}
+
+// the guided kernel's extra arguments: the planar f and g images, k_f^2 and tau (denoise.hip: DenoiseGuide, restated as dual_term is)
+struct DualGuide {
+	const double *planes;
+	double kf2, tau;
+};
+
 // Pw: the weight half's six planes (u, then v); Uv: the value half's three u planes; fout: W*H*3 doubles, pixel-interleaved, written at dual-valid
 // pixels only (dual_combine_kernel gives the others their value).
 // table: REGION only (null otherwise), one entry per workgroup.
-template <int TW, bool REGION>
+// GUIDED is the presence of a DualGuide argument: denoise_dual_kernel<TW, REGION> (no such argument) keeps the signature and the code it had before the
+// feature weight existed, denoise_dual_kernel<TW, REGION, DualGuide> is the guided instantiation.
+template <int TW, bool REGION, class... G>
 __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__restrict__ Pw, const double *__restrict__ Uv, const DualBlock *__restrict__ table, uint32_t W,
-                                                               uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ fout) {
+                                                               uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ fout, G... guide) {
+	constexpr bool GUIDED = sizeof...(G) != 0;
+	static_assert(sizeof...(G) <= 1, "at most one DualGuide");
+	[[maybe_unused]] const double *fplanes = nullptr;
+	[[maybe_unused]] double kf2 = 0.0, tau = 0.0;
+	if constexpr (GUIDED) {
+		const DualGuide gd = (guide, ...);
+		fplanes = gd.planes, kf2 = gd.kf2, tau = gd.tau;
+	}
 	extern __shared__ double lds[];
 	constexpr int TH = (int)kDenoiseTile, NT = TW * TH;
 	const int R = r + f, AW = TW + 2 * R, AA = AW * (TH + 2 * R), PW = TW + 2 * f, PP = PW * (TH + 2 * f);
@@ -138,6 +197,18 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 	const int dy_lo = (int)max((int64_t)-r, -gy), dy_hi = (int)min((int64_t)r, (int64_t)H - 1 - gy);
 	const size_t pixp = inside ? (size_t)gx + (size_t)gy * W : 0;
 	double acc0 = -0.0, acc1 = -0.0, acc2 = -0.0, wsum = -0.0; // -0.0 + x == x for every x, so r = 0 gives the value half's u bit for bit
+	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .): eps + k_f^2 * max(tau * s_pj, g_pj), s = 1 but for the depth
+	[[maybe_unused]] double fp[kDenoiseFeat], gp[kDenoiseFeat], den[kDenoiseFeat];
+	[[maybe_unused]] bool p_fok = false;
+	if constexpr (GUIDED) {
+#pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) {
+			fp[j] = fplanes[(size_t)j * N + pixp], gp[j] = fplanes[(size_t)(kDenoiseFeat + j) * N + pixp];
+			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
+			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+		}
+		p_fok = p_ok && fp[0] == fp[0];
+	}
 
 	for (int dy = -r; dy <= r; dy++) {
 		for (int dx = -r; dx <= r; dx++) {
@@ -177,8 +248,25 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 					uint32_t cnt = Hc[py * TW + px];
 					for (int o = 1; o <= 2 * f; o++) ds = ds + Hs[(py + o) * TW + px], cnt += Hc[(py + o) * TW + px];
 					const double D = ds / (3.0 * (double)cnt);
-					const double w = exp(-(D > 0.0 ? D : 0.0));
+					double w = exp(-(D > 0.0 ? D : 0.0));
 					const size_t pixq = (size_t)((int64_t)pixp + (int64_t)dy * (int64_t)W + dx); // (inside the frame: dx, dy are within the lo / hi bounds)
+					if constexpr (GUIDED) {
+						if (p_fok) {
+							const double fq0 = fplanes[pixq];
+							if (fq0 == fq0) { // q is feature-valid too
+								double Df = 0.0;
+#pragma unroll
+								for (int j = 0; j < kDenoiseFeat; j++) {
+									const double fq = j == 0 ? fq0 : fplanes[(size_t)j * N + pixq], gq = fplanes[(size_t)(kDenoiseFeat + j) * N + pixq];
+									const double df = fp[j] - fq;
+									const double phi = (df * df - (gp[j] + __builtin_fmin(gp[j], gq))) / den[j];
+									if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
+								}
+								const double wf = exp(-Df);
+								if (wf < w) w = wf;
+							}
+						}
+					}
 					acc0 = acc0 + w * Uv[pixq], acc1 = acc1 + w * Uv[N + pixq], acc2 = acc2 + w * Uv[2 * N + pixq];
 					wsum = wsum + w;
 				}
@@ -232,11 +320,26 @@ __global__ __launch_bounds__(512) void dual_combine_region_kernel(const double *
 	if (x < e.x_end && y < e.y_end) dual_combine_pixel(SA, SB, n_a, n_b, planes, fb, (size_t)x + (size_t)y * W, out, err);
 }
 
+template <int TW, bool REGION>
+static hipError_t launch_dual_pass(hipStream_t stream, dim3 grid, size_t lds, const double *Pw, const double *Uv, const DualBlock *table, uint32_t W, uint32_t H, int r,
+                                   int f, double k2, double alpha, double *fout, const DualGuide *gd) {
+	if (gd) hipLaunchKernelGGL((denoise_dual_kernel<TW, REGION, DualGuide>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, r, f, k2, alpha, fout, *gd);
+	else hipLaunchKernelGGL((denoise_dual_kernel<TW, REGION>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, r, f, k2, alpha, fout);
+	return hipGetLastError();
+}
+template <int TW, bool REGION>
+static const void *dual_pass_fn(bool guided) {
+	return guided ? reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION, DualGuide>) : reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION>);
+}
+
 hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                               const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, uint32_t count_image_columns,
-                               uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k, double alpha, uint32_t *n_img, double *planes,
-                               double *f_b, const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
+                               const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                               const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
+                               double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
+                               const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+	const bool guided = feat != nullptr;
+	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
 	if (table && n_blocks == 0) return hipSuccess; // a region without pixels: nothing would read the planes
 	const size_t N = (size_t)W * H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
@@ -249,24 +352,34 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
 	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
 	hipLaunchKernelGGL(dual_planes_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, n_a, n_b, N, planes);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
+	if (guided) { // the features' own count image, then their planes (which read the dual-validity mark dual_planes_kernel has just left)
+		if ((e = hipMemsetAsync(n_f_img, 0, N * sizeof(uint32_t), stream)) != hipSuccess) return e;
+		if (n_rects) {
+			hipLaunchKernelGGL(dual_feature_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_f, W, n_f_img);
+			if ((e = hipGetLastError()) != hipSuccess) return e;
+		}
+		hipLaunchKernelGGL(dual_feature_planes_kernel, dim3(blocks), dim3(256), 0, stream, planes, feat, feat_sq, n_f_img, N, feat_planes);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits, as for denoise_kernel)
-	const void *fn = table ? (tw == 32u ? reinterpret_cast<const void *>(&denoise_dual_kernel<32, true>) : reinterpret_cast<const void *>(&denoise_dual_kernel<24, true>))
-	                       : (tw == 32u ? reinterpret_cast<const void *>(&denoise_dual_kernel<32, false>) : reinterpret_cast<const void *>(&denoise_dual_kernel<24, false>));
+	const void *fn = table ? (tw == 32u ? dual_pass_fn<32, true>(guided) : dual_pass_fn<24, true>(guided)) : (tw == 32u ? dual_pass_fn<32, false>(guided) : dual_pass_fn<24, false>(guided));
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
 	const dim3 grid = table ? dim3(n_blocks) : dim3((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
 	const int ri = (int)radius, fi = (int)patch_radius;
 	const double k2 = k * k;
+	const DualGuide gd{feat_planes, k_f * k_f, tau};
+	const DualGuide *gp = guided ? &gd : nullptr;
 	const double *PA = planes, *PB = planes + 6u * N;
-	for (int pass = 0; pass < 2; pass++) { // f_A: weights from B applied to u_A, into out; f_B: weights from A applied to u_B, into f_b
+	for (int pass = 0; pass < 2; pass++) { // f_A: weights from B applied to u_A, into out; f_B: weights from A applied to u_B, into f_b (guided: the same w_f in both)
 		const double *Pw = pass == 0 ? PB : PA, *Uv = pass == 0 ? PA : PB;
 		double *fout = pass == 0 ? out : f_b;
-		if (table && tw == 32u) hipLaunchKernelGGL((denoise_dual_kernel<32, true>), grid, dim3(32 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
-		else if (table) hipLaunchKernelGGL((denoise_dual_kernel<24, true>), grid, dim3(24 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
-		else if (tw == 32u) hipLaunchKernelGGL((denoise_dual_kernel<32, false>), grid, dim3(32 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
-		else hipLaunchKernelGGL((denoise_dual_kernel<24, false>), grid, dim3(24 * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout);
-		if ((e = hipGetLastError()) != hipSuccess) return e;
+		if (table && tw == 32u) e = launch_dual_pass<32, true>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
+		else if (table) e = launch_dual_pass<24, true>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
+		else if (tw == 32u) e = launch_dual_pass<32, false>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
+		else e = launch_dual_pass<24, false>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
+		if (e != hipSuccess) return e;
 	}
 	if (table) hipLaunchKernelGGL(dual_combine_region_kernel, grid, dim3(tw * kDenoiseTile), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, table, tw, W, out, err);
 	else hipLaunchKernelGGL(dual_combine_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, N, out, err);

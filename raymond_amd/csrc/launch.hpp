@@ -129,11 +129,15 @@ struct alignas(16) DualBlock {
 // holds counts_a[i] and counts_b[i] samples, err (may be null) the per-pixel error estimate, W*H doubles.  Scratch: n_img 2 * W*H uint32, planes
 // 12 * W*H doubles, f_b 3 * W*H doubles.  rects and the counts are device memory; the tile shape and LDS are denoise_kernel's.  table null: every pixel
 // of out and err is written.  table not null (rmd_denoise_dual_region; device memory): n_blocks entries (x0, y0, x_end, y_end), one per workgroup of
-// denoise_tile_width(radius, patch_radius) x 16 pixels at (x0, y0); only the pixels before (x_end, y_end), inside the frame, are written
+// denoise_tile_width(radius, patch_radius) x 16 pixels at (x0, y0); only the pixels before (x_end, y_end), inside the frame, are written.
+// With the feature weight (rmd_denoise_dual_guided[_region]) when feat / feat_sq are given (W*H*7 doubles each, pixel-interleaved; rect i holds counts_f[i]
+// feature samples): n_f_img is W*H uint32 and feat_planes 14 * W*H doubles of further scratch, k_f and tau are checked by the caller.  Both null: exactly
+// the launches made without the feature — counts_f, k_f, tau, n_f_img and feat_planes are not read
 hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                               const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, uint32_t n_rects, uint32_t count_image_columns,
-                               uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius, double k, double alpha, uint32_t *n_img, double *planes,
-                               double *f_b, const DualBlock *table, uint32_t n_blocks, double *out, double *err);
+                               const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                               const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
+                               double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
+                               const DualBlock *table, uint32_t n_blocks, double *out, double *err);
 // out[i] = sqrt(the mean of err over rect i's pixels), +inf if one of them is NaN (denoise_dual.hip: tile_error_dual_kernel; rects and out are device memory)
 hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W, double *out);
 // rmd_render_features (features.hip): for each of the P.n_work wave tiles, the first-hit features of samples P.sample_begin .. + P.sample_count - 1

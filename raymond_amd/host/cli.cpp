@@ -11,6 +11,8 @@
 //                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
 //                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
 //                                                                       the image is rmd_denoise_dual's; T: tiles finish by rmd_tile_error_dual)
+//                                                                    [--denoise-dual-features 1]   (needs --denoise-dual 1: first-hit features guide the dual
+//                                                                      filter, rmd_denoise_dual_guided, with --denoise-feature-k / --denoise-feature-tau)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -58,7 +60,7 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 	if (st.denoise) {
 		handle.await(); // (its channel is drained: it only waits for the workers and rethrows a worker's error)
 		std::vector<Vector3> den = finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0})
-		                           : st.denoise_dual      ? denoise_dual_tiles(finished_tiles, st, 0)
+		                           : st.denoise_dual      ? denoise_dual_tiles(finished_tiles, st, 0, nullptr, scene)
 		                                                  : denoise_tiles(finished_tiles, st, 0, scene, feature_means);
 		if (finished_out) *finished_out = std::move(finished_tiles);
 		return den;
@@ -201,6 +203,7 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-k")) st.denoise_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-alpha")) st.denoise_alpha = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-dual")) st.denoise_dual = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--denoise-dual-features")) st.denoise_dual_features = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--adaptive-denoised")) st.adaptive_denoised_threshold = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--adaptive-min")) st.adaptive_min_samples = (size_t)std::strtoull(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;

@@ -400,10 +400,13 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 // adaptive_denoised_threshold > 0, after every even number of passes that leaves the live tiles below sample_count with at least
 // adaptive_min_samples: rmd_denoise_dual_region over the live tiles' pixels of the whole frame (finished tiles at the counts they finished with),
 // rmd_tile_error_dual over the live tiles, and the tiles at or below the threshold are finished.  Progress snapshots go out as they are made, the finished tiles at the end.
+// With denoise_dual_features the adaptive check needs the features: two feature buffers, into which every pass also adds the live tiles' first-hit
+// features of its samples [done, done + n) — a tile's features then hold count_a + count_b samples —, and the check is rmd_denoise_dual_guided_region.
 void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene scene, Settings st) {
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
 	double *fbs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
+	double *feat[2] = {nullptr, nullptr};                                    // adaptive with denoise_dual_features: the feature sums and sums of squares
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	try {
 		const auto t_setup = std::chrono::steady_clock::now();
@@ -414,6 +417,9 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
 		const bool adaptive = st.adaptive_denoised_threshold > 0.0;
 		for (int i = 0; i < (adaptive ? 6 : 4); i++) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fbs[i]), ctx, "rmd_framebuffer_alloc");
+		const bool guided = adaptive && st.denoise_dual_features; // (without the adaptive check nothing here would read the features: await() renders its own)
+		if (guided)
+			for (double *&d : feat) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
 		{
 			std::lock_guard<std::mutex> lock(sh->m);
 			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
@@ -470,6 +476,11 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 			std::memset(&rs, 0, sizeof(rs));
 			rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)done, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
 			check(rmd_render_tiles_moments(ctx, dscene, &cam, &rs, live.data(), (uint32_t)live.size(), fbs[2 * half], fbs[2 * half + 1]), ctx, "rmd_render_tiles_moments");
+			if (guided) {
+				rmd_settings fs = rs;
+				fs.flags = st.use_dof ? RMD_RENDER_DOF : 0u; // (as render_features_on)
+				check(rmd_render_features(ctx, dscene, &cam, &fs, live.data(), (uint32_t)live.size(), feat[0], feat[1]), ctx, "rmd_render_features");
+			}
 			done += n, j++, n_half[half] += n;
 			if (done >= st.sample_count) break;
 			std::vector<double> errors;
@@ -479,9 +490,18 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 				rects.insert(rects.end(), live.begin(), live.end());
 				ca.insert(ca.end(), live.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), live.size(), (uint32_t)n_half[1]);
 				// only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
-				check(rmd_denoise_dual_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(), (uint32_t)rects.size(), live.data(),
-				                              (uint32_t)live.size(), st.denoise_radius, st.denoise_patch, st.denoise_k, st.denoise_alpha, fbs[4], fbs[5]),
-				      ctx, "rmd_denoise_dual_region");
+				if (guided) {
+					std::vector<uint32_t> cf(ca);
+					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
+					check(rmd_denoise_dual_guided_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], feat[0], feat[1], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(),
+					                                     cf.data(), (uint32_t)rects.size(), live.data(), (uint32_t)live.size(), st.denoise_radius, st.denoise_patch,
+					                                     st.denoise_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fbs[4], fbs[5]),
+					      ctx, "rmd_denoise_dual_guided_region");
+				} else {
+					check(rmd_denoise_dual_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(), (uint32_t)rects.size(), live.data(),
+					                              (uint32_t)live.size(), st.denoise_radius, st.denoise_patch, st.denoise_k, st.denoise_alpha, fbs[4], fbs[5]),
+					      ctx, "rmd_denoise_dual_region");
+				}
 				errors.resize(live.size());
 				check(rmd_tile_error_dual(ctx, fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), errors.data()), ctx, "rmd_tile_error_dual");
 			}
@@ -525,6 +545,8 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 	}
 	for (double *fb : fbs)
 		if (fb) rmd_framebuffer_free(ctx, fb);
+	for (double *d : feat)
+		if (d) rmd_framebuffer_free(ctx, d);
 	rmd_scene_destroy(dscene);
 	rmd_context_destroy(ctx);
 	std::lock_guard<std::mutex> lock(sh->m);
@@ -553,6 +575,8 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)");
 	if (settings.denoise_dual && settings.denoise_features)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight");
+	if (settings.denoise_dual_features && !settings.denoise_dual)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)");
 	if (!(settings.adaptive_denoised_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_denoised_threshold > 0.0 && !settings.denoise_dual)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)");
@@ -564,6 +588,7 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 	h.settings = settings;
 	h.shared_ = std::make_shared<TaskHandle::Shared>();
 	if (settings.denoise_dual) {
+		if (settings.denoise_dual_features) h.scene_ = std::make_shared<const Scene>(scene);
 		h.shared_->alive = 1;
 		h.workers_.emplace_back(dual_worker_main, h.shared_, 0, scene, settings);
 		return h;
@@ -615,7 +640,7 @@ std::vector<Vector3> TaskHandle::await() {
 			}
 	}
 	lock.unlock();
-	if (!collected.empty()) out = settings.denoise_dual ? denoise_dual_tiles(collected, settings, 0) : denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
+	if (!collected.empty()) out = settings.denoise_dual ? denoise_dual_tiles(collected, settings, 0, nullptr, scene_.get()) : denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
 	return out;
 }
 
@@ -749,7 +774,8 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 	return out;
 }
 
-std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors) {
+std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors, const Scene *scene) {
+	if (settings.denoise_dual_features && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: settings.denoise_dual_features needs the scene");
 	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
 	std::vector<double> halves[4];
 	for (std::vector<double> &h : halves) h.assign(W * H * 3, 0.0);
@@ -769,13 +795,25 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 	std::vector<Vector3> out(W * H);
 	rmd_context *ctx = nullptr;
 	double *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // the four halves, the frame, the error image
+	double *fdev[2] = {nullptr, nullptr}; // settings.denoise_dual_features: the feature sums and sums of squares, each tile at count_a + count_b
 	try {
 		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
 		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
 		for (int i = 0; i < 4; i++) check(rmd_framebuffer_upload(ctx, halves[i].data(), dev[i], halves[i].size()), ctx, "rmd_framebuffer_upload");
-		check(rmd_denoise_dual(ctx, dev[0], dev[1], dev[2], dev[3], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(), (uint32_t)rects.size(),
-		                       settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, dev[4], tile_errors ? dev[5] : nullptr),
-		      ctx, "rmd_denoise_dual");
+		if (settings.denoise_dual_features) {
+			std::vector<uint32_t> counts_f(counts_a);
+			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
+			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
+			render_features_on(ctx, *scene, settings, rects, counts_f, fdev[0], fdev[1]);
+			check(rmd_denoise_dual_guided(ctx, dev[0], dev[1], dev[2], dev[3], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(),
+			                              counts_f.data(), (uint32_t)rects.size(), settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha,
+			                              settings.denoise_feature_k, settings.denoise_feature_tau, dev[4], tile_errors ? dev[5] : nullptr),
+			      ctx, "rmd_denoise_dual_guided");
+		} else {
+			check(rmd_denoise_dual(ctx, dev[0], dev[1], dev[2], dev[3], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(), (uint32_t)rects.size(),
+			                       settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, dev[4], tile_errors ? dev[5] : nullptr),
+			      ctx, "rmd_denoise_dual");
+		}
 		if (tile_errors) {
 			tile_errors->assign(rects.size(), 0.0);
 			check(rmd_tile_error_dual(ctx, dev[5], (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), tile_errors->data()), ctx, "rmd_tile_error_dual");
@@ -784,10 +822,14 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 	} catch (...) {
 		for (double *d : dev)
 			if (d) rmd_framebuffer_free(ctx, d);
+		for (double *d : fdev)
+			if (d) rmd_framebuffer_free(ctx, d);
 		rmd_context_destroy(ctx);
 		throw;
 	}
 	for (double *d : dev) rmd_framebuffer_free(ctx, d);
+	for (double *d : fdev)
+		if (d) rmd_framebuffer_free(ctx, d);
 	rmd_context_destroy(ctx);
 	return out;
 }

@@ -143,6 +143,9 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// from 0, adds its samples to half A when j is even and to half B when j is odd; TileFinished tiles carry both halves and await() returns
 	// rmd_denoise_dual's frame (raymond_hip.h).
 	bool denoise_dual = false;
+	// Feature weights in the dual-buffer filter (needs denoise_dual; false = off): the filter is rmd_denoise_dual_guided with the finished tiles' first-hit
+	// features at count_a + count_b samples per tile, k_f = denoise_feature_k and tau = denoise_feature_tau; the adaptive check is its region form.
+	bool denoise_dual_features = false;
 	// Adaptive sampling by the filtered frame's error (needs denoise_dual, excludes adaptive_threshold > 0; 0 = off): after every even number of
 	// passes that leaves live tiles with at least adaptive_min_samples samples, rmd_denoise_dual runs over the whole frame and a live tile whose
 	// rmd_tile_error_dual — an absolute RMS in linear radiance that reads low — is at most the threshold is finished at the samples it has.
@@ -216,7 +219,7 @@ class TaskHandle {
   private:
 	friend TaskHandle render_tiled(const Scene &, const Settings &);
 	TaskHandle() = default;
-	std::shared_ptr<const Scene> scene_; // settings.denoise_features: the scene whose features await() renders
+	std::shared_ptr<const Scene> scene_; // settings.denoise_features / denoise_dual_features: the scene whose features await() renders
 	std::shared_ptr<Shared> shared_;
 	std::vector<std::thread> workers_;
 	TileCallback callback_;
@@ -232,8 +235,10 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings);
 std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, const Scene *scene = nullptr,
                                    std::vector<double> *feature_means = nullptr);
 // Extension (settings.denoise_dual): the W*H means of rmd_denoise_dual on GPU `device` over the tiles' two halves (data_a .. count_b) with the
-// settings' parameters.  tile_errors (optional): receives rmd_tile_error_dual of every tile, in the tiles' order.
-std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, std::vector<double> *tile_errors = nullptr);
+// settings' parameters.  tile_errors (optional): receives rmd_tile_error_dual of every tile, in the tiles' order.  settings.denoise_dual_features: `scene`
+// (required then) is uploaded to that GPU, the tiles' first-hit features are rendered at count_a + count_b samples and the filter is rmd_denoise_dual_guided.
+std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, std::vector<double> *tile_errors = nullptr,
+                                        const Scene *scene = nullptr);
 // The W*H*7 first-hit feature sums (and, when asked for, sums of squares) of a frame whose rect i holds counts[i] samples, rendered on GPU `device`
 // with the settings' camera, seed and DOF flag: the AOVs (normal xyz, albedo rgb, depth) of raymond_hip.h's rmd_render_features.
 std::vector<double> render_features(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,

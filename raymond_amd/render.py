@@ -270,11 +270,13 @@ class ErrorImage(Framebuffer):
         raise NotImplementedError("error images have no tile-rect transfers")
 
 
-def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0, region=None):
+def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0, region=None,
+                 features=None, features_sq=None, counts_f=None, k_f=1.0, tau=1e-2):
     """rmd_denoise_dual: `out_framebuffer` = the cross-filtered means of the two sample halves `half_a` and `half_b`, each a (sums, sums of squares)
     pair of Framebuffers; rect i holds counts_a[i] and counts_b[i] samples per pixel in them.  `error_image` (an ErrorImage, optional) receives the
     per-pixel error estimate.  `region` (a list of rects, possibly empty): rmd_denoise_dual_region — only the pixels of those rects are written, with
-    the bytes the whole-frame call gives them; None is the whole-frame call."""
+    the bytes the whole-frame call gives them; None is the whole-frame call.  `features` / `features_sq` (FeatureBuffers; rect i holds counts_f[i]
+    feature samples per pixel): rmd_denoise_dual_guided[_region], the same with rmd_denoise_guided's feature weight; features=None makes the calls above."""
     counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
     counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
     if len(counts_a) != len(rects) or len(counts_b) != len(rects):
@@ -283,16 +285,30 @@ def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer
     head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, fb.width, fb.height, tile_array(rects),
             counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects))
     tail = (int(radius), int(patch_radius), float(k), float(alpha), out_framebuffer.ptr, None if error_image is None else error_image.ptr)
-    if region is None:
+    if features is not None or features_sq is not None:
+        counts_f = np.ascontiguousarray([] if counts_f is None else counts_f, dtype=np.uint32)
+        if len(counts_f) != len(rects):
+            raise ValueError("one feature sample count per rect")
+        head = head[:5] + (None if features is None else features.ptr, None if features_sq is None else features_sq.ptr) + head[5:10] + (
+            counts_f.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects))
+        tail = tail[:4] + (float(k_f), float(tau)) + tail[4:]
+        if region is None:
+            ctx.check(ctx.L.rmd_denoise_dual_guided(*head, *tail))
+        else:
+            region = list(region)
+            ctx.check(ctx.L.rmd_denoise_dual_guided_region(*head, tile_array(region), len(region), *tail))
+    elif region is None:
         ctx.check(ctx.L.rmd_denoise_dual(*head, *tail))
     else:
         region = list(region)
         ctx.check(ctx.L.rmd_denoise_dual_region(*head, tile_array(region), len(region), *tail))
 
 
-def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, region=None, out_init=None, err_init=None, **params):
+def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, region=None, out_init=None, err_init=None, features=None,
+                        features_sq=None, **params):
     """denoise_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate out.
-    `out_init` (H, W, 3) and `err_init` (H, W): what the two outputs hold before the call — what a pixel outside `region` still holds after it."""
+    `out_init` (H, W, 3) and `err_init` (H, W): what the two outputs hold before the call — what a pixel outside `region` still holds after it.
+    `features` / `features_sq`: (H, W, 7) feature sums and sums of squares for the guided forms (with counts_f, k_f, tau among the params)."""
     H, W = sums_a.shape[0], sums_a.shape[1]
     opened = []
     try:
@@ -303,7 +319,14 @@ def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts
         opened.append(ErrorImage(ctx, W, H))
         if err_init is not None:
             opened[-1].upload(err_init)
-        denoise_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5], region=region, **params)
+        fbufs = [None, None]
+        if features is not None:
+            for i, arr in enumerate((features, features_sq)):
+                opened.append(FeatureBuffer(ctx, W, H))
+                opened[-1].upload(arr)
+                fbufs[i] = opened[-1]
+        denoise_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5], region=region, features=fbufs[0],
+                     features_sq=fbufs[1], **params)
         return opened[4].download(), opened[5].download()
     finally:
         for b in opened:
@@ -358,7 +381,7 @@ class Message:  # src/trace.rs:62-66
 class TaskHandle:  # src/trace.rs:70-135
     def __init__(self, settings, messages, device=0, scene=None):
         self.settings = settings
-        self.scene = scene  # settings.denoise_features: await_() uploads it to `device` for the feature pass
+        self.scene = scene  # settings.denoise_features / denoise_dual_features: await_() uploads it to `device` for the feature pass
         self._messages = list(messages)
         self.callback = None
         self.device = device  # settings.denoise: the GPU await_() denoises on (render_tiled's first)
@@ -420,9 +443,13 @@ class TaskHandle:  # src/trace.rs:70-135
 
 
     def _await_dual(self):
-        """await_() with settings.denoise_dual: the finished tiles' two halves through rmd_denoise_dual on `device`."""
+        """await_() with settings.denoise_dual: the finished tiles' two halves through rmd_denoise_dual on `device`.  With settings.denoise_dual_features:
+        the finished tiles' first-hit features are rendered there at count_a + count_b samples per tile (finished_tile_features) and the filter is
+        rmd_denoise_dual_guided."""
         st = self.settings
         st.check_denoise()
+        if st.denoise_dual_features and self.scene is None:
+            raise ValueError("settings.denoise_dual_features: this TaskHandle was made without the scene whose features await_() has to render")
         cam = st.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         halves = [np.zeros(shape) for _ in range(4)]
@@ -438,8 +465,14 @@ class TaskHandle:  # src/trace.rs:70-135
             counts_a.append(t.count_a)
             counts_b.append(t.count_b)
         with Context(self.device) as ctx:
-            out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k,
-                                         alpha=st.denoise_alpha)
+            params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
+            if st.denoise_dual_features:
+                counts_f = [a + b for a, b in zip(counts_a, counts_b)]
+                feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
+                out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, features=feats, features_sq=feats_sq, counts_f=counts_f,
+                                             k_f=st.denoise_feature_k, tau=st.denoise_feature_tau, **params)
+            else:
+                out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, **params)
         return out
 
 
@@ -550,7 +583,12 @@ def _render_tiled_dual(scene, settings, devices):
 
     With settings.adaptive_denoised_threshold > 0: after every even number of passes that leaves live tiles below sample_count with at least
     adaptive_min_samples samples, rmd_denoise_dual_region filters the live tiles' pixels of the whole frame (finished tiles at the counts they
-    finished with: the bytes rmd_denoise_dual would give those pixels), rmd_tile_error_dual runs over the live tiles, and a live tile at or below the threshold is sent as TileFinished, with that error, and takes no further passes."""
+    finished with: the bytes rmd_denoise_dual would give those pixels), rmd_tile_error_dual runs over the live tiles, and a live tile at or below the threshold is sent as TileFinished, with that error, and takes no further passes.
+
+    With settings.denoise_dual_features the adaptive check needs the features: two feature buffers beside the four, into which rmd_render_features
+    adds, after each pass, the live tiles' first-hit features of the same samples [done, done + n), so a tile's features hold count_a + count_b
+    samples; the check is rmd_denoise_dual_guided_region with those counts.  (Without an adaptive threshold nothing in this loop would read them and
+    none are rendered.)  await_() renders the finished tiles' features itself (finished_tile_features) and returns rmd_denoise_dual_guided's frame."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     st = settings
@@ -571,6 +609,11 @@ def _render_tiled_dual(scene, settings, devices):
         if adaptive:
             out_fb, err_img = Framebuffer(ctx, W, H), ErrorImage(ctx, W, H)
             opened.extend([out_fb, err_img])
+        guided = adaptive and st.denoise_dual_features
+        guide = {}
+        if guided:
+            feat_fbs = [FeatureBuffer(ctx, W, H) for _ in range(2)]
+            opened.extend(feat_fbs)
         live = list(tiles)
         done_rects, done_a, done_b = [], [], []  # the finished tiles and the counts they finished with
         n_half = [0, 0]  # samples per pixel of a live tile in A and B
@@ -593,6 +636,8 @@ def _render_tiled_dual(scene, settings, devices):
             n = min(st.samples_per_iteration, st.sample_count - done)
             half = j & 1
             render_tiles(ctx, ds, cam, st, live, fbs[2 * half], done, n, sync=False, framebuffer_sq=fbs[2 * half + 1])
+            if guided:
+                render_features(ctx, ds, cam, st, live, feat_fbs[0], done, n, sync=False, features_sq=feat_fbs[1])
             ctx.synchronize()
             done, j = done + n, j + 1
             n_half[half] += n
@@ -600,8 +645,11 @@ def _render_tiled_dual(scene, settings, devices):
                 errors = [None] * len(live)
                 if adaptive and j % 2 == 0 and done >= st.adaptive_min_samples:
                     # only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
-                    denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, done_a + [n_half[0]] * len(live), done_b + [n_half[1]] * len(live),
-                                 out_fb, err_img, region=live, **params)
+                    all_a, all_b = done_a + [n_half[0]] * len(live), done_b + [n_half[1]] * len(live)
+                    if guided:
+                        guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
+                                     tau=st.denoise_feature_tau)
+                    denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide)
                     errors = tile_error_dual(ctx, err_img, live)
                 conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
                 finish([r for r, c in zip(live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
@@ -619,4 +667,4 @@ def _render_tiled_dual(scene, settings, devices):
                 o.close()
             except Exception:  # noqa: BLE001 (a failing close must not keep the others open, nor hide the body's own error)
                 pass
-    return TaskHandle(settings, messages, devices[0])
+    return TaskHandle(settings, messages, devices[0], scene if settings.denoise_dual_features else None)

@@ -246,7 +246,7 @@ class Settings:
                  worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
                  adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
-                 adaptive_min_samples=32):
+                 adaptive_min_samples=32, denoise_dual_features=False):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -289,6 +289,9 @@ class Settings:
         # radiance that reads low (raymond_hip.h) — is at most the threshold is finished at the samples it has.
         self.adaptive_denoised_threshold = float(adaptive_denoised_threshold)
         self.adaptive_min_samples = adaptive_min_samples
+        # Feature weights in the dual-buffer filter (False = off; needs denoise_dual): the filter is rmd_denoise_dual_guided, with the first-hit
+        # features at count_a + count_b samples per tile, k_f = denoise_feature_k and tau = denoise_feature_tau; the adaptive check is its region form.
+        self.denoise_dual_features = bool(denoise_dual_features)
         self.check_denoise()
 
     def check_adaptive(self):
@@ -322,6 +325,8 @@ class Settings:
             raise ValueError("denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)")
         if self.denoise_dual and self.denoise_features:
             raise ValueError("denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight")
+        if self.denoise_dual_features and not self.denoise_dual:
+            raise ValueError("denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)")
         if not self.adaptive_denoised_threshold >= 0.0:
             raise ValueError("adaptive_denoised_threshold must be >= 0 (0 = off)")
         if self.adaptive_denoised_threshold > 0.0 and not self.denoise_dual:
