@@ -63,7 +63,7 @@ enum {
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
-	                                 rmd_denoise_dual_guided_region) */
+	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -530,6 +530,58 @@ rmd_status rmd_denoise_dual_guided_region(rmd_context *ctx,
     const rmd_tile_rect *region, uint32_t n_region,
     uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau,
     double *out_dev, double *err_dev);
+/*
+ * PER-PIXEL CHOICE AMONG SEVERAL DUAL-BUFFER FILTERS by Stein's unbiased risk estimate (an addition within ABI 6, found by its symbol; after
+ * Rousselle, Manzi and Zwicker 2013).  Whole-frame.  Every candidate i < n_cands is one parameter set of
+ * rmd_denoise_dual (guided = 0: k, alpha; k_f and tau are not read) or of rmd_denoise_dual_guided (guided != 0: k, alpha, k_f, tau) at the
+ * call's radius and patch_radius.  Counts, u, v, validity, dual validity, the feature planes and feature validity are those calls', word for word.
+ *   Per candidate i.  f_A,i and f_B,i are exactly the two cross passes of that call.  The weights that filter half X are made from the OTHER half
+ *   (and the features), so f_X,i(p) is linear in u_X and  g_X,i(p) = d f_X,i(p) / d u_X(p) = w(p, p) / sum_q w(p, q):  the weight the pass gives the
+ *   offset (0, 0) — through the same operations as any other offset, the feature weight included; it is 1 whenever alpha >= 0 — divided by the pass's
+ *   own sum of weights, the denominator of f_X,i(p).
+ *   SURE of half X, with u, v that half's mean and variance of the mean, per channel c:
+ *       d_c = f_X,i,c - u_c;   t_c = ((d_c * d_c) - v_c) + ((2 * v_c) * g_X,i)
+ *       sure_X,i(p) = ((t_0 + t_1) + t_2) / 3
+ *   an unbiased estimate of E (f_X,i - truth)^2, the bias included (err of rmd_denoise_dual sees the variance alone); it may be negative.
+ *   SURE of the candidate:  sure_i(p) = ((n_A * sure_A,i) + (n_B * sure_B,i)) / (n_A + n_B), NaN at a pixel that is not dual-valid.
+ *   Selection.  E_i(p) = the mean of sure_i over the dual-valid pixels of the (2*sure_window + 1)^2 window around p that lie inside the frame:
+ *   0.0, then those pixels' values added in raster order (row by row, left to right), divided by their number.  win(p) = the lowest index i with
+ *   the smallest E_i(p): i replaces the best so far only if E_i < E_best, or E_best is NaN and E_i is not; all NaN: 0.
+ *   m_i(p) = (the dual-valid in-frame pixels q of the (2*select_window + 1)^2 window around p with win(q) = i) / (the dual-valid in-frame pixels of
+ *   that window): two integer counts, converted to double, one division — exact fractions that sum to 1 up to rounding, whatever the order.
+ *   Output, for a dual-valid p:  f_X(p)_c = m_0 * f_X,0,c, then + m_i * f_X,i,c for i = 1 .. n_cands - 1 in that order;
+ *       out and err   rmd_denoise_dual's operations on f_A and f_B, word for word
+ *       sure_dev[p]   m_0 * sure_0(p), then + m_i * sure_i(p) in index order
+ *       win_dev[p]    win(p)
+ *   any other p: out is the merged mean and err NaN as in rmd_denoise_dual, sure_dev[p] is NaN and win_dev[p] is 0xFFFFFFFF.
+ * So n_cands = 1 gives m_0 = 1 and rmd_denoise_dual's (rmd_denoise_dual_guided's) out and err bit for bit; a candidate listed a second time never
+ * wins (the first of equal minima does), its m is 0 and the outputs are those of the list without it.  sure_dev of one candidate alone is that
+ * filter's per-pixel SURE: its frame mean estimates the filter's mean squared error (within x0.8 - 1.3 of the true RMSE
+ * after the root, where err reads x0.2 - 0.55); per tile it is too noisy to rank tiles, which stays err's task.
+ * cands: a HOST array.  err_dev (W*H doubles), sure_dev (W*H doubles) and win_dev (W*H uint32) may each be NULL.
+ * Arguments, all checked before the device is touched, anything else RMD_ERR_INVALID_ARGUMENT: rmd_denoise_dual's rules for the sum buffers,
+ * out_dev, err_dev, width, height, the rects, rect_counts_a / _b, radius and patch_radius; cands non-NULL and 1 <= n_cands <=
+ * RMD_DENOISE_MAX_CANDIDATES; sure_window and select_window <= 5; every candidate's reserved = 0, its k and alpha under rmd_denoise_dual's
+ * rules, and for a guided one k_f and tau under rmd_denoise_dual_guided's; feat_dev and feat_sq_dev both given or both NULL, under
+ * rmd_denoise_dual_guided's aliasing rule; a guided candidate needs both, and rect_counts_f when n_rects > 0; sure_dev and win_dev overlap
+ * no other range.  Features given without a guided candidate are not read.  Synchronous, and reports an earlier device fault, like rmd_denoise_dual.
+ * Values a caller may start from: {k 0.45 unguided, k 1.0 guided with k_f 1.0 and tau 1e-2}, both windows 2.
+ */
+typedef struct rmd_denoise_candidate {
+	double k, alpha, k_f, tau;
+	uint32_t guided, reserved;
+} rmd_denoise_candidate;
+enum { RMD_DENOISE_MAX_CANDIDATES = 4 };
+rmd_status rmd_denoise_dual_select(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t radius, uint32_t patch_radius,
+    const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
+    double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev);
 /*
  * Per-tile error of the delivered frame from rmd_denoise_dual's err_dev (W*H doubles):
  *     out_err_host[r] = sqrt((sum of err_p over rect r's pixels) / the rect's pixel count)

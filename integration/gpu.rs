@@ -95,8 +95,28 @@ extern "C" {
                                       rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32,
                                       region: *const rmd_tile_rect, n_region: u32, radius: u32, patch_radius: u32, k: f64, alpha: f64, k_f: f64, tau: f64,
                                       out_dev: *mut f64, err_dev: *mut f64) -> i32;
+    // per-pixel choice among up to 4 parameter sets of the two calls above by Stein's unbiased risk estimate (cands: a HOST array; err_dev, sure_dev
+    // and win_dev may be null)
+    fn rmd_denoise_dual_select(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64, accum_sq_b_dev: *const f64,
+                               feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, rect_counts_a: *const u32,
+                               rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32, radius: u32, patch_radius: u32,
+                               cands: *const rmd_denoise_candidate, n_cands: u32, sure_window: u32, select_window: u32, out_dev: *mut f64, err_dev: *mut f64,
+                               sure_dev: *mut f64, win_dev: *mut u32) -> i32;
     fn rmd_tile_error_dual(ctx: *mut rmd_context, err_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, n_rects: u32,
                            out_err_host: *mut f64) -> i32;
+}
+
+/// One candidate of rmd_denoise_dual_select (include/raymond_hip.h: rmd_denoise_candidate); `reserved` is 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+#[allow(non_camel_case_types, dead_code)]
+pub struct rmd_denoise_candidate {
+    pub k: f64,
+    pub alpha: f64,
+    pub k_f: f64,
+    pub tau: f64,
+    pub guided: u32,
+    pub reserved: u32,
 }
 
 fn check(ctx: *const rmd_context, status: i32) {

@@ -116,6 +116,20 @@ class TileRect(C.Structure):
     ]
 
 
+class DenoiseCandidate(C.Structure):  # rmd_denoise_candidate
+    _fields_ = [
+        ("k", C.c_double),
+        ("alpha", C.c_double),
+        ("k_f", C.c_double),
+        ("tau", C.c_double),
+        ("guided", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+DENOISE_MAX_CANDIDATES = 4  # RMD_DENOISE_MAX_CANDIDATES
+
+
 class LaunchInfo(C.Structure):  # rmd_launch_info
     _fields_ = [
         ("passes", C.c_uint32),

@@ -1172,6 +1172,98 @@ rmd_status rmd_denoise_dual_guided_region(rmd_context *ctx, const double *accum_
 	                            rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, region, n_region, radius, patch_radius, k, alpha, k_f, tau, out_dev, err_dev);
 }
 
+static rmd_status denoise_dual_select_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
+                                           const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
+                                           const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, uint32_t radius, uint32_t patch_radius,
+                                           const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window, double *out_dev,
+                                           double *err_dev, double *sure_dev, uint32_t *win_dev) {
+	if (rmd_status s = bind(ctx)) return s;
+	// device scratch: [the twelve u / v planes: 12 * W*H doubles][per candidate f_A, f_B and SURE: 7 * W*H doubles each][g_A, g_B: 2 * W*H doubles]
+	// [with a guided candidate, the planar f and g: 14 * W*H doubles][both halves' per-pixel counts, the winners and (guided) the features' counts:
+	// 3 or 4 * W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts of A, of B and (guided) of the features: 4 bytes each]
+	bool guided = false;
+	for (uint32_t i = 0; i < n_cands; i++) guided = guided || cands[i].guided != 0u;
+	const size_t N = (size_t)width * height;
+	const size_t plane_bytes = N * 12u * sizeof(double), cand_bytes = N * 7u * sizeof(double) * n_cands, gain_bytes = N * 2u * sizeof(double);
+	const size_t fplane_bytes = guided ? N * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
+	const size_t img_bytes = ((guided ? 4u : 3u) * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
+	rmd::DeviceBuffer scratch;
+	RMD_HIP(ctx, scratch.alloc(plane_bytes + cand_bytes + gain_bytes + fplane_bytes + img_bytes + rect_bytes + (guided ? 3u : 2u) * count_bytes));
+	unsigned char *d = scratch.as<unsigned char>();
+	double *d_planes = scratch.as<double>();
+	double *d_cand = reinterpret_cast<double *>(d + plane_bytes);
+	double *d_gain = reinterpret_cast<double *>(d + plane_bytes + cand_bytes);
+	double *d_fplanes = guided ? reinterpret_cast<double *>(d + plane_bytes + cand_bytes + gain_bytes) : nullptr;
+	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + plane_bytes + cand_bytes + gain_bytes + fplane_bytes), *d_win = d_img + 2u * N;
+	uint32_t *d_fimg = guided ? d_img + 3u * N : nullptr;
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + plane_bytes + cand_bytes + gain_bytes + fplane_bytes + img_bytes);
+	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_rects) + rect_bytes), *d_counts_b = d_counts_a + n_rects;
+	uint32_t *d_counts_f = guided ? d_counts_b + n_rects : nullptr;
+	if (n_rects != 0) {
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		if (guided) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+	}
+	uint64_t largest = 0; // as denoise_dual_impl
+	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
+	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
+	RMD_HIP(ctx, rmd::launch_denoise_dual_select(ctx->stream, sa, qa, sb, qb, guided ? feat : nullptr, guided ? feat_sq : nullptr, d_rects, d_counts_a, d_counts_b,
+	                                             d_counts_f, n_rects, columns, width, height, radius, patch_radius, cands, n_cands, sure_window, select_window, d_img,
+	                                             d_planes, d_cand, d_gain, d_win, d_fimg, d_fplanes, out_dev, err_dev, sure_dev, win_dev));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx);
+}
+
+rmd_status rmd_denoise_dual_select(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t radius,
+                                   uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
+                                   double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev) {
+	const std::string name = "rmd_denoise_dual_select: ";
+	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
+	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
+	if (!cands || n_cands == 0 || n_cands > rmd::kDenoiseMaxCandidates) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "n_cands must be 1 .. 4, cands not NULL");
+	if (sure_window > rmd::kDenoiseMaxSelectWindow || select_window > rmd::kDenoiseMaxSelectWindow)
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "sure_window and select_window must be <= 5");
+	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
+	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
+	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
+	for (uint32_t i = 0; i < n_cands; i++) {
+		const rmd_denoise_candidate &c = cands[i];
+		const std::string who = name + "candidate " + std::to_string(i) + ": ";
+		if (c.reserved != 0u) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "reserved must be 0");
+		if (!(c.k > 0.0) || !std::isfinite(c.k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "k must be finite and > 0");
+		if (!(c.alpha >= 0.0) || !std::isfinite(c.alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "alpha must be finite and >= 0");
+		if (c.guided) {
+			if (!feat_dev) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "guided, but feat_dev and feat_sq_dev are NULL");
+			if (n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "guided, but rect_counts_f is NULL with n_rects > 0");
+			if (!(c.k_f > 0.0) || !std::isfinite(c.k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "k_f must be finite and > 0");
+			if (!(c.tau > 0.0) || !std::isfinite(c.tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "tau must be finite and > 0");
+		}
+	}
+	{ // no two ranges overlap: five of W*H*3 doubles; err_dev's and sure_dev's W*H doubles, win_dev's W*H words, the two of W*H*7 doubles, where given
+		const unsigned __int128 n = (unsigned __int128)width * height;
+		const void *ptr[10] = {accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, out_dev, err_dev, sure_dev, win_dev, feat_dev, feat_sq_dev};
+		const unsigned __int128 len[10] = {n * 24u, n * 24u, n * 24u, n * 24u, n * 24u, n * 8u, n * 8u, n * 4u, n * 8u * RMD_FEATURE_CHANNELS, n * 8u * RMD_FEATURE_CHANNELS};
+		for (int i = 0; i < 10; i++)
+			for (int j = i + 1; j < 10; j++) {
+				const unsigned __int128 a = (uintptr_t)ptr[i], b = (uintptr_t)ptr[j];
+				if (ptr[i] && ptr[j] && a < b + len[j] && b < a + len[i])
+					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, the feature buffers, out_dev, err_dev, sure_dev and win_dev must not alias");
+			}
+	}
+	return rmd::guarded(ctx, "rmd_denoise_dual_select", [&] {
+		const char *why = nullptr;
+		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
+		return denoise_dual_select_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
+		                                rect_counts_b, rect_counts_f, n_rects, radius, patch_radius, cands, n_cands, sure_window, select_window, out_dev, err_dev,
+		                                sure_dev, win_dev);
+	});
+}
+
 static rmd_status tile_error_dual_impl(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
                                        double *out_err_host) {
 	if (rmd_status s = bind(ctx)) return s;

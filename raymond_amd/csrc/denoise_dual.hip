@@ -27,6 +27,11 @@
 // NaN in its f of channel 0), and step 3 of each cross pass makes rmd_denoise_guided's w_f of the pixel pair and takes min(w, w_f): p's seven f, g
 // and denominators in registers, q's fourteen values per taken neighbour from the planes in global memory.  w_f is evaluated in BOTH passes
 // (DESIGN.md section 15); the LDS layout is unchanged.
+// SELECTION (rmd_denoise_dual_select): the whole-frame cross pass takes one more optional trailing argument, a DualGain, and then
+// also writes g(p) = w(p, p) / sum_q w(p, q), the derivative of f(p) by the value half's own u(p) — instantiations of their own again, so the eight
+// above keep their arguments and their instructions.  dual_sure_kernel makes a candidate's per-pixel SURE from the planes, its two f and the two g
+// images; dual_winner_kernel the windowed means of every candidate's SURE (dual_window_mean) and the index of the smallest; dual_blend_kernel the
+// weights m_i from the winners around the pixel, the blended f_A and f_B, and then dual_combine_pixel itself.
 // tile_error_dual_kernel   — one workgroup per rect: sqrt(sum err / pixels), +inf when an err of the rect is NaN.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
@@ -130,23 +135,37 @@ struct DualGuide {
 	const double *planes;
 	double kf2, tau;
 };
+// the selecting call's extra argument: the W*H image that receives g(p) = w(p, p) / sum_q w(p, q) at the pixels where fout is written
+struct DualGain {
+	double *g;
+};
+// the argument of type T among a kernel's trailing pack
+template <class T, class A, class... R>
+__device__ inline T dual_pick(A a, R... rest) {
+	if constexpr (__is_same(T, A)) return a;
+	else return dual_pick<T>(rest...);
+}
 
 // Pw: the weight half's six planes (u, then v); Uv: the value half's three u planes; fout: W*H*3 doubles, pixel-interleaved, written at dual-valid
 // pixels only (dual_combine_kernel gives the others their value).
 // table: REGION only (null otherwise), one entry per workgroup.
 // GUIDED is the presence of a DualGuide argument: denoise_dual_kernel<TW, REGION> (no such argument) keeps the signature and the code it had before the
-// feature weight existed, denoise_dual_kernel<TW, REGION, DualGuide> is the guided instantiation.
+// feature weight existed, denoise_dual_kernel<TW, REGION, DualGuide> is the guided instantiation.  GAIN is the presence of a DualGain argument (after the
+// DualGuide, if there is one): the weight the loop makes at offset (0, 0) is kept, and g = that weight / wsum is written beside fout.
 template <int TW, bool REGION, class... G>
 __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__restrict__ Pw, const double *__restrict__ Uv, const DualBlock *__restrict__ table, uint32_t W,
                                                                uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ fout, G... guide) {
-	constexpr bool GUIDED = sizeof...(G) != 0;
-	static_assert(sizeof...(G) <= 1, "at most one DualGuide");
+	constexpr bool GUIDED = (__is_same(G, DualGuide) || ...), GAIN = (__is_same(G, DualGain) || ...);
+	static_assert(sizeof...(G) == (GUIDED ? 1 : 0) + (GAIN ? 1 : 0), "at most one DualGuide, then at most one DualGain");
 	[[maybe_unused]] const double *fplanes = nullptr;
 	[[maybe_unused]] double kf2 = 0.0, tau = 0.0;
 	if constexpr (GUIDED) {
-		const DualGuide gd = (guide, ...);
+		const DualGuide gd = dual_pick<DualGuide>(guide...);
 		fplanes = gd.planes, kf2 = gd.kf2, tau = gd.tau;
 	}
+	[[maybe_unused]] double *gout = nullptr;
+	[[maybe_unused]] double wcentre = 0.0; // GAIN: w(p, p) — set for every p_ok pixel, whose own offset (0, 0) is always taken
+	if constexpr (GAIN) gout = dual_pick<DualGain>(guide...).g;
 	extern __shared__ double lds[];
 	constexpr int TH = (int)kDenoiseTile, NT = TW * TH;
 	const int R = r + f, AW = TW + 2 * R, AA = AW * (TH + 2 * R), PW = TW + 2 * f, PP = PW * (TH + 2 * f);
@@ -269,6 +288,9 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 					}
 					acc0 = acc0 + w * Uv[pixq], acc1 = acc1 + w * Uv[N + pixq], acc2 = acc2 + w * Uv[2 * N + pixq];
 					wsum = wsum + w;
+					if constexpr (GAIN) {
+						if (dx == 0 && dy == 0) wcentre = w;
+					}
 				}
 			}
 		}
@@ -277,6 +299,7 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 	if (p_ok) {
 		const size_t o = pixp * 3;
 		fout[o + 0] = acc0 / wsum, fout[o + 1] = acc1 / wsum, fout[o + 2] = acc2 / wsum;
+		if constexpr (GAIN) gout[pixp] = wcentre / wsum;
 	}
 }
 
@@ -332,15 +355,12 @@ static const void *dual_pass_fn(bool guided) {
 	return guided ? reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION, DualGuide>) : reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION>);
 }
 
-hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                               const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                               const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
-                               double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
-                               const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
-	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
-	const bool guided = feat != nullptr;
-	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
-	if (table && n_blocks == 0) return hipSuccess; // a region without pixels: nothing would read the planes
+// What every dual call makes first, once: both halves' count images and the twelve planes; with features also their count image and their fourteen planes
+// (which read the dual-validity mark dual_planes_kernel has just left)
+static hipError_t dual_preamble(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b, const double *feat,
+                                const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f,
+                                uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t *n_img, double *planes, uint32_t *n_f_img,
+                                double *feat_planes) {
 	const size_t N = (size_t)W * H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
 	hipError_t e = hipMemsetAsync(n_img, 0, 2u * N * sizeof(uint32_t), stream);
@@ -352,7 +372,7 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
 	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
 	hipLaunchKernelGGL(dual_planes_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, n_a, n_b, N, planes);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
-	if (guided) { // the features' own count image, then their planes (which read the dual-validity mark dual_planes_kernel has just left)
+	if (feat) {
 		if ((e = hipMemsetAsync(n_f_img, 0, N * sizeof(uint32_t), stream)) != hipSuccess) return e;
 		if (n_rects) {
 			hipLaunchKernelGGL(dual_feature_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_f, W, n_f_img);
@@ -361,6 +381,24 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
 		hipLaunchKernelGGL(dual_feature_planes_kernel, dim3(blocks), dim3(256), 0, stream, planes, feat, feat_sq, n_f_img, N, feat_planes);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
+	return hipSuccess;
+}
+
+hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                               const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                               const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
+                               double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
+                               const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
+	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+	const bool guided = feat != nullptr;
+	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	if (table && n_blocks == 0) return hipSuccess; // a region without pixels: nothing would read the planes
+	const size_t N = (size_t)W * H;
+	uint32_t *n_a = n_img, *n_b = n_img + N;
+	hipError_t e = dual_preamble(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, feat, feat_sq, rects, counts_a, counts_b, counts_f, n_rects, count_image_columns, W, H,
+	                             n_img, planes, n_f_img, feat_planes);
+	if (e != hipSuccess) return e;
+	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits, as for denoise_kernel)
@@ -383,6 +421,193 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
 	}
 	if (table) hipLaunchKernelGGL(dual_combine_region_kernel, grid, dim3(tw * kDenoiseTile), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, table, tw, W, out, err);
 	else hipLaunchKernelGGL(dual_combine_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, N, out, err);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- rmd_denoise_dual_select
+// One candidate's per-pixel SURE.  Half X with u, v its planes, f its cross pass's result and g its gain image: t_c = ((d*d) - v_c) + ((2*v_c) * g) with
+// d = f_c - u_c; sure_X = ((t_0 + t_1) + t_2) / 3.  sure = ((n_A * sure_A) + (n_B * sure_B)) / (n_A + n_B); NaN at a pixel that is not dual-valid.
+__global__ __launch_bounds__(256) void dual_sure_kernel(const double *__restrict__ planes, const double *__restrict__ fa, const double *__restrict__ fb,
+                                                        const double *__restrict__ ga, const double *__restrict__ gb, const uint32_t *__restrict__ n_a,
+                                                        const uint32_t *__restrict__ n_b, size_t N, double *__restrict__ sure) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const double ua0 = planes[i];
+	if (!(ua0 == ua0)) {
+		sure[i] = __builtin_nan("");
+		return;
+	}
+	double sx[2];
+#pragma unroll
+	for (int h = 0; h < 2; h++) {
+		const double *f = h ? fb : fa;
+		const double g = h ? gb[i] : ga[i];
+		double t = 0.0;
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			const double u = planes[(size_t)(6 * h + c) * N + i], v = planes[(size_t)(6 * h + 3 + c) * N + i];
+			const double d = f[i * 3 + c] - u;
+			const double tc = (d * d - v) + (2.0 * v) * g;
+			t = c == 0 ? tc : t + tc;
+		}
+		sx[h] = t / 3.0;
+	}
+	const double na = (double)n_a[i], nb = (double)n_b[i];
+	sure[i] = (na * sx[0] + nb * sx[1]) / (na + nb);
+}
+
+// The mean of `img` over the dual-valid pixels (planes[q] is no NaN) of the (2*win + 1)^2 window around (x, y) that lie inside the frame: 0.0, then every such
+// pixel's value added in raster order, divided by their number (0 / 0 = NaN where there is none).
+__device__ inline double dual_window_mean(const double *__restrict__ img, const double *__restrict__ planes, int64_t x, int64_t y, int64_t W, int64_t H, int win) {
+	double s = 0.0;
+	uint32_t cnt = 0u;
+	for (int64_t qy = y - win; qy <= y + win; qy++) {
+		if (qy < 0 || qy >= H) continue;
+		for (int64_t qx = x - win; qx <= x + win; qx++) {
+			if (qx < 0 || qx >= W) continue;
+			const size_t q = (size_t)qx + (size_t)qy * (size_t)W;
+			const double m = planes[q];
+			if (m == m) s = s + img[q], cnt++;
+		}
+	}
+	return s / (double)cnt;
+}
+
+// win[p] = the lowest index i with the smallest E_i(p), the window mean of candidate i's SURE (image i of `sure`, N doubles apart at stride `stride`);
+// a NaN E loses to any number; all NaN: 0.  0xFFFFFFFF at a pixel that is not dual-valid.
+__global__ __launch_bounds__(256) void dual_winner_kernel(const double *__restrict__ sure, size_t stride, uint32_t n_cands, const double *__restrict__ planes, uint32_t W,
+                                                          uint32_t H, int win_radius, uint32_t *__restrict__ win) {
+	const size_t N = (size_t)W * H, i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const double ua0 = planes[i];
+	if (!(ua0 == ua0)) {
+		win[i] = 0xFFFFFFFFu;
+		return;
+	}
+	const int64_t x = (int64_t)(i % W), y = (int64_t)(i / W);
+	uint32_t best = 0u;
+	double eb = dual_window_mean(sure, planes, x, y, W, H, win_radius);
+	for (uint32_t c = 1; c < n_cands; c++) {
+		const double e = dual_window_mean(sure + (size_t)c * stride, planes, x, y, W, H, win_radius);
+		if (e < eb || (eb != eb && e == e)) best = c, eb = e;
+	}
+	win[i] = best;
+}
+
+// Per pixel p.  Dual-valid: cnt_i = the dual-valid in-frame pixels q of the (2*sel + 1)^2 window with win[q] = i, total = all of them (p is one), m_i =
+// cnt_i / total; f_X = m_0 * f_X,0, then + m_i * f_X,i in index order, per channel; f_A goes to out and f_B to candidate 0's f_B image (only p's own
+// entries of either are read here, by this thread), and dual_combine_pixel makes out and err of them.  sure_out = the same sum over the SURE images.
+// Any other pixel: dual_combine_pixel's merged mean and NaN, sure_out NaN.  cand: candidate i's images at cand + i * stride — f_A (3N), f_B (3N), SURE (N).
+__global__ __launch_bounds__(256) void dual_blend_kernel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
+                                                         const uint32_t *__restrict__ n_b, const double *__restrict__ planes, double *cand, size_t stride,
+                                                         uint32_t n_cands, const uint32_t *__restrict__ win, uint32_t W, uint32_t H, int sel_radius, double *out,
+                                                         double *__restrict__ err, double *__restrict__ sure_out, uint32_t *__restrict__ win_out) {
+	const size_t N = (size_t)W * H, i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const double ua0 = planes[i];
+	if (ua0 == ua0) {
+		const int64_t x = (int64_t)(i % W), y = (int64_t)(i / W);
+		uint32_t cnt[kDenoiseMaxCandidates] = {0u, 0u, 0u, 0u}, total = 0u;
+		for (int64_t qy = y - sel_radius; qy <= y + sel_radius; qy++) {
+			if (qy < 0 || qy >= (int64_t)H) continue;
+			for (int64_t qx = x - sel_radius; qx <= x + sel_radius; qx++) {
+				if (qx < 0 || qx >= (int64_t)W) continue;
+				const uint32_t w = win[(size_t)qx + (size_t)qy * W];
+				if (w != 0xFFFFFFFFu) {
+					total++;
+#pragma unroll
+					for (uint32_t c = 0; c < kDenoiseMaxCandidates; c++) cnt[c] += w == c ? 1u : 0u;
+				}
+			}
+		}
+		double fa[3], fb[3], su = 0.0;
+#pragma unroll
+		for (uint32_t c = 0; c < kDenoiseMaxCandidates; c++) {
+			if (c < n_cands) {
+				const double m = (double)cnt[c] / (double)total;
+				const double *ca = cand + (size_t)c * stride, *cb = ca + 3u * N, *cs = ca + 6u * N;
+#pragma unroll
+				for (int ch = 0; ch < 3; ch++) {
+					const double pa = m * ca[i * 3 + ch], pb = m * cb[i * 3 + ch];
+					fa[ch] = c == 0 ? pa : fa[ch] + pa, fb[ch] = c == 0 ? pb : fb[ch] + pb;
+				}
+				const double ps = m * cs[i];
+				su = c == 0 ? ps : su + ps;
+			}
+		}
+#pragma unroll
+		for (int ch = 0; ch < 3; ch++) out[i * 3 + ch] = fa[ch], cand[3u * N + i * 3 + ch] = fb[ch];
+		if (sure_out) sure_out[i] = su;
+	} else if (sure_out) sure_out[i] = __builtin_nan("");
+	if (win_out) win_out[i] = win[i];
+	dual_combine_pixel(SA, SB, n_a, n_b, planes, cand + 3u * N, i, out, err);
+}
+
+// a whole-frame cross pass that also writes its gain image
+template <int TW>
+static hipError_t launch_dual_pass_gain(hipStream_t stream, dim3 grid, size_t lds, const double *Pw, const double *Uv, uint32_t W, uint32_t H, int r, int f, double k2,
+                                        double alpha, double *fout, const DualGuide *gd, DualGain gn) {
+	const DualBlock *none = nullptr;
+	if (gd) {
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&denoise_dual_kernel<TW, false, DualGuide, DualGain>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL((denoise_dual_kernel<TW, false, DualGuide, DualGain>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, none, W, H, r, f, k2, alpha, fout, *gd, gn);
+	} else {
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&denoise_dual_kernel<TW, false, DualGain>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL((denoise_dual_kernel<TW, false, DualGain>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, none, W, H, r, f, k2, alpha, fout, gn);
+	}
+	return hipGetLastError();
+}
+
+hipError_t launch_denoise_dual_select(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius,
+                                      uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
+                                      uint32_t *n_img, double *planes, double *cand_img, double *gain, uint32_t *win_img, uint32_t *n_f_img, double *feat_planes,
+                                      double *out, double *err, double *sure, uint32_t *win) {
+	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch || n_cands == 0 || n_cands > kDenoiseMaxCandidates || sure_window > kDenoiseMaxSelectWindow ||
+	    select_window > kDenoiseMaxSelectWindow)
+		return hipErrorInvalidValue;
+	bool any_guided = false;
+	for (uint32_t i = 0; i < n_cands; i++) any_guided = any_guided || cands[i].guided != 0u;
+	if (any_guided && (feat == nullptr || feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	const size_t N = (size_t)W * H;
+	uint32_t *n_a = n_img, *n_b = n_img + N;
+	// once per call, whatever the number of candidates: k_f and tau enter the feature weight through denominators the kernel makes itself
+	hipError_t e = dual_preamble(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, any_guided ? feat : nullptr, feat_sq, rects, counts_a, counts_b, counts_f, n_rects,
+	                             count_image_columns, W, H, n_img, planes, n_f_img, feat_planes);
+	if (e != hipSuccess) return e;
+	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
+	const uint32_t tw = denoise_tile_width(radius, patch_radius);
+	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
+	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration;
+	const dim3 grid((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
+	const int ri = (int)radius, fi = (int)patch_radius;
+	const double *PA = planes, *PB = planes + 6u * N;
+	const size_t stride = 7u * N; // a candidate's images: f_A (3N), f_B (3N), SURE (N)
+	double *g_a = gain, *g_b = gain + N;
+	for (uint32_t i = 0; i < n_cands; i++) {
+		const rmd_denoise_candidate &c = cands[i];
+		const double k2 = c.k * c.k;
+		const DualGuide gd{feat_planes, c.k_f * c.k_f, c.tau};
+		const DualGuide *gp = c.guided ? &gd : nullptr;
+		double *f_a = cand_img + (size_t)i * stride, *f_b = f_a + 3u * N, *s_i = f_a + 6u * N;
+		for (int pass = 0; pass < 2; pass++) { // launch_denoise_dual's two passes
+			const double *Pw = pass == 0 ? PB : PA, *Uv = pass == 0 ? PA : PB;
+			double *fout = pass == 0 ? f_a : f_b;
+			const DualGain gn{pass == 0 ? g_a : g_b};
+			e = tw == 32u ? launch_dual_pass_gain<32>(stream, grid, lds, Pw, Uv, W, H, ri, fi, k2, c.alpha, fout, gp, gn)
+			              : launch_dual_pass_gain<24>(stream, grid, lds, Pw, Uv, W, H, ri, fi, k2, c.alpha, fout, gp, gn);
+			if (e != hipSuccess) return e;
+		}
+		hipLaunchKernelGGL(dual_sure_kernel, dim3(blocks), dim3(256), 0, stream, planes, f_a, f_b, g_a, g_b, n_a, n_b, N, s_i);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
+	hipLaunchKernelGGL(dual_winner_kernel, dim3(blocks), dim3(256), 0, stream, cand_img + 6u * N, stride, n_cands, planes, W, H, (int)sure_window, win_img);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	hipLaunchKernelGGL(dual_blend_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_b, n_a, n_b, planes, cand_img, stride, n_cands, win_img, W, H, (int)select_window,
+	                   out, err, sure, win);
 	return hipGetLastError();
 }
 

@@ -107,6 +107,7 @@ hipError_t launch_tile_error(hipStream_t stream, const double *accum, const doub
 constexpr uint32_t kDenoiseTile = 16;
 constexpr double kDenoiseEps = 1e-10;
 constexpr uint32_t kDenoiseMaxRadius = 12, kDenoiseMaxPatch = 4;
+constexpr uint32_t kDenoiseMaxCandidates = (uint32_t)RMD_DENOISE_MAX_CANDIDATES, kDenoiseMaxSelectWindow = 5; // rmd_denoise_dual_select
 constexpr int kDenoiseFeat = (int)RMD_FEATURE_CHANNELS; // rmd_denoise_guided: feature channels per pixel
 // dynamic LDS of denoise_kernel<tile_width>: the apron's u and v (48 B a pixel) and the term image with its row sums
 size_t denoise_lds_bytes(uint32_t tile_width, uint32_t radius, uint32_t patch_radius);
@@ -138,6 +139,16 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
                                const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
                                double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
                                const DualBlock *table, uint32_t n_blocks, double *out, double *err);
+// rmd_denoise_dual_select (denoise_dual.hip): launch_denoise_dual's preamble once, then per candidate (a HOST array, checked by the caller) its two cross
+// passes with their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per
+// candidate (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read
+// only when a candidate is guided.  err, sure and win (W*H each) may be null.
+hipError_t launch_denoise_dual_select(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius,
+                                      uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
+                                      uint32_t *n_img, double *planes, double *cand_img, double *gain, uint32_t *win_img, uint32_t *n_f_img, double *feat_planes,
+                                      double *out, double *err, double *sure, uint32_t *win);
 // out[i] = sqrt(the mean of err over rect i's pixels), +inf if one of them is NaN (denoise_dual.hip: tile_error_dual_kernel; rects and out are device memory)
 hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W, double *out);
 // rmd_render_features (features.hip): for each of the P.n_work wave tiles, the first-hit features of samples P.sample_begin .. + P.sample_count - 1

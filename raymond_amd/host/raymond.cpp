@@ -577,6 +577,8 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight");
 	if (settings.denoise_dual_features && !settings.denoise_dual)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)");
+	if (settings.denoise_dual_select && !settings.denoise_dual)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_select needs denoise_dual (it selects rmd_denoise_dual_select)");
 	if (!(settings.adaptive_denoised_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_denoised_threshold > 0.0 && !settings.denoise_dual)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)");
@@ -588,7 +590,7 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 	h.settings = settings;
 	h.shared_ = std::make_shared<TaskHandle::Shared>();
 	if (settings.denoise_dual) {
-		if (settings.denoise_dual_features) h.scene_ = std::make_shared<const Scene>(scene);
+		if (settings.denoise_dual_features || settings.denoise_dual_select) h.scene_ = std::make_shared<const Scene>(scene);
 		h.shared_->alive = 1;
 		h.workers_.emplace_back(dual_worker_main, h.shared_, 0, scene, settings);
 		return h;
@@ -776,6 +778,7 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 
 std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors, const Scene *scene) {
 	if (settings.denoise_dual_features && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: settings.denoise_dual_features needs the scene");
+	if (settings.denoise_dual_select && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: settings.denoise_dual_select needs the scene");
 	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
 	std::vector<double> halves[4];
 	for (std::vector<double> &h : halves) h.assign(W * H * 3, 0.0);
@@ -800,7 +803,18 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
 		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
 		for (int i = 0; i < 4; i++) check(rmd_framebuffer_upload(ctx, halves[i].data(), dev[i], halves[i].size()), ctx, "rmd_framebuffer_upload");
-		if (settings.denoise_dual_features) {
+		if (settings.denoise_dual_select) {
+			std::vector<uint32_t> counts_f(counts_a);
+			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
+			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
+			render_features_on(ctx, *scene, settings, rects, counts_f, fdev[0], fdev[1]);
+			const rmd_denoise_candidate cands[2] = {{settings.denoise_k, settings.denoise_alpha, 0.0, 0.0, 0u, 0u},
+			                                        {1.0, settings.denoise_alpha, settings.denoise_feature_k, settings.denoise_feature_tau, 1u, 0u}};
+			check(rmd_denoise_dual_select(ctx, dev[0], dev[1], dev[2], dev[3], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(),
+			                              counts_f.data(), (uint32_t)rects.size(), settings.denoise_radius, settings.denoise_patch, cands, 2u, 2u, 2u, dev[4],
+			                              tile_errors ? dev[5] : nullptr, nullptr, nullptr),
+			      ctx, "rmd_denoise_dual_select");
+		} else if (settings.denoise_dual_features) {
 			std::vector<uint32_t> counts_f(counts_a);
 			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
 			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");

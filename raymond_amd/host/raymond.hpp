@@ -146,6 +146,10 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// Feature weights in the dual-buffer filter (needs denoise_dual; false = off): the filter is rmd_denoise_dual_guided with the finished tiles' first-hit
 	// features at count_a + count_b samples per tile, k_f = denoise_feature_k and tau = denoise_feature_tau; the adaptive check is its region form.
 	bool denoise_dual_features = false;
+	// Per-pixel choice among dual-buffer filters (needs denoise_dual; false = off): await() renders the finished tiles' features as denoise_dual_features
+	// does and returns rmd_denoise_dual_select's frame at two candidates — (k = denoise_k, unguided) and (k = 1.0, guided, denoise_feature_k,
+	// denoise_feature_tau), both at denoise_alpha — with both windows 2.  The adaptive check is untouched.
+	bool denoise_dual_select = false;
 	// Adaptive sampling by the filtered frame's error (needs denoise_dual, excludes adaptive_threshold > 0; 0 = off): after every even number of
 	// passes that leaves live tiles with at least adaptive_min_samples samples, rmd_denoise_dual runs over the whole frame and a live tile whose
 	// rmd_tile_error_dual — an absolute RMS in linear radiance that reads low — is at most the threshold is finished at the samples it has.
@@ -237,6 +241,7 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 // Extension (settings.denoise_dual): the W*H means of rmd_denoise_dual on GPU `device` over the tiles' two halves (data_a .. count_b) with the
 // settings' parameters.  tile_errors (optional): receives rmd_tile_error_dual of every tile, in the tiles' order.  settings.denoise_dual_features: `scene`
 // (required then) is uploaded to that GPU, the tiles' first-hit features are rendered at count_a + count_b samples and the filter is rmd_denoise_dual_guided.
+// settings.denoise_dual_select: the scene and the features likewise, and the frame is rmd_denoise_dual_select's at the setting's two candidates.
 std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device = 0, std::vector<double> *tile_errors = nullptr,
                                         const Scene *scene = nullptr);
 // The W*H*7 first-hit feature sums (and, when asked for, sums of squares) of a frame whose rect i holds counts[i] samples, rendered on GPU `device`

@@ -333,6 +333,92 @@ def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts
             b.close()
 
 
+class WinnerImage(ErrorImage):
+    """W*H uint32 in HBM: rmd_denoise_dual_select's per-pixel winners (the allocation is a framebuffer's; its first W*H words are used)."""
+
+    def download(self):
+        out = np.empty((self.n + 1) // 2, dtype=np.float64)  # (transfers count doubles)
+        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), out.size))
+        return out.view(np.uint32)[: self.n].reshape(self.height, self.width).copy()
+
+    def upload(self, words):
+        buf = np.zeros(2 * ((self.n + 1) // 2), dtype=np.uint32)
+        buf[: self.n] = np.asarray(words, dtype=np.uint32).reshape(-1)
+        arr = buf.view(np.float64)
+        self.ctx.check(self.ctx.L.rmd_framebuffer_upload(self.ctx.handle, arr.ctypes.data_as(C.c_void_p), self.ptr, arr.size))
+
+
+def candidate_array(candidates):
+    """An abi.DenoiseCandidate array from dicts with k and, optionally, alpha (1.0), guided (False), k_f (1.0), tau (1e-2) and reserved (0)."""
+    arr = (abi.DenoiseCandidate * max(1, len(candidates)))()
+    for i, c in enumerate(candidates):
+        arr[i] = abi.DenoiseCandidate(float(c["k"]), float(c.get("alpha", 1.0)), float(c.get("k_f", 1.0)), float(c.get("tau", 1e-2)), int(bool(c.get("guided", False))),
+                                      int(c.get("reserved", 0)))
+    return arr
+
+
+def denoise_dual_select(ctx, half_a, half_b, rects, counts_a, counts_b, candidates, out_framebuffer, error_image=None, sure_image=None, winner_image=None,
+                        radius=10, patch_radius=3, sure_window=2, select_window=2, features=None, features_sq=None, counts_f=None):
+    """rmd_denoise_dual_select: per pixel, the best of `candidates` (dicts, see candidate_array: parameter sets of denoise_dual, `guided` ones with the
+    feature weight) by Stein's unbiased risk estimate, blended over the winners around the pixel.  `error_image` and `sure_image` (ErrorImages) and
+    `winner_image` (a WinnerImage) are optional; `features`, `features_sq` and `counts_f` are needed by a guided candidate."""
+    counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
+    counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
+    if len(counts_a) != len(rects) or len(counts_b) != len(rects):
+        raise ValueError("one sample count per rect and half")
+    cf = None
+    if counts_f is not None:
+        counts_f = np.ascontiguousarray(counts_f, dtype=np.uint32)
+        if len(counts_f) != len(rects):
+            raise ValueError("one feature sample count per rect")
+        cf = counts_f.ctypes.data_as(C.POINTER(C.c_uint32))
+    candidates = list(candidates)
+    fb = half_a[0]
+    opt = lambda o: None if o is None else o.ptr  # noqa: E731
+    ctx.check(ctx.L.rmd_denoise_dual_select(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, opt(features), opt(features_sq), fb.width,
+                                            fb.height, tile_array(rects), counts_a.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), cf, len(rects), int(radius), int(patch_radius),
+                                            candidate_array(candidates), len(candidates), int(sure_window), int(select_window), out_framebuffer.ptr,
+                                            opt(error_image), opt(sure_image), opt(winner_image)))
+
+
+def denoise_dual_select_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, candidates, features=None, features_sq=None,
+                               want=("err", "sure", "win"), init=None, **params):
+    """denoise_dual_select() for host arrays: the two halves' (H, W, 3) sums and sums of squares in (and (H, W, 7) `features` / `features_sq` with counts_f
+    among the params for guided candidates); a dict out with "out" (H, W, 3) and those of "err" (H, W), "sure" (H, W) and "win" (H, W) uint32 named in
+    `want` — one left out is passed as NULL.  `init`: a dict of what the named outputs hold before the call."""
+    H, W = sums_a.shape[0], sums_a.shape[1]
+    init = init or {}
+    opened = []
+    try:
+        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, init.get("out")):
+            opened.append(Framebuffer(ctx, W, H))
+            if arr is not None:
+                opened[-1].upload(arr)
+        imgs = {}
+        for name in ("err", "sure", "win"):
+            if name in want:
+                imgs[name] = (WinnerImage if name == "win" else ErrorImage)(ctx, W, H)
+                opened.append(imgs[name])
+                if init.get(name) is not None:
+                    imgs[name].upload(init[name])
+        fbufs = [None, None]
+        if features is not None:
+            for i, arr in enumerate((features, features_sq)):
+                opened.append(FeatureBuffer(ctx, W, H))
+                opened[-1].upload(arr)
+                fbufs[i] = opened[-1]
+        denoise_dual_select(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, candidates, opened[4], imgs.get("err"),
+                            imgs.get("sure"), imgs.get("win"), features=fbufs[0], features_sq=fbufs[1], **params)
+        res = {"out": opened[4].download()}
+        for name, img in imgs.items():
+            res[name] = img.download()
+        return res
+    finally:
+        for b in opened:
+            b.close()
+
+
 def tile_error_dual(ctx, error_image, tiles):
     """rmd_tile_error_dual: per tile, the root mean square of `error_image` (rmd_denoise_dual's estimate) over its pixels; +inf for a tile with a
     pixel that is not dual-valid (float64 array)."""
@@ -445,11 +531,12 @@ class TaskHandle:  # src/trace.rs:70-135
     def _await_dual(self):
         """await_() with settings.denoise_dual: the finished tiles' two halves through rmd_denoise_dual on `device`.  With settings.denoise_dual_features:
         the finished tiles' first-hit features are rendered there at count_a + count_b samples per tile (finished_tile_features) and the filter is
-        rmd_denoise_dual_guided."""
+        rmd_denoise_dual_guided.  With settings.denoise_dual_select: the features are rendered the same way and the frame is
+        rmd_denoise_dual_select's at settings.select_candidates(), both windows 2."""
         st = self.settings
         st.check_denoise()
-        if st.denoise_dual_features and self.scene is None:
-            raise ValueError("settings.denoise_dual_features: this TaskHandle was made without the scene whose features await_() has to render")
+        if (st.denoise_dual_features or st.denoise_dual_select) and self.scene is None:
+            raise ValueError("settings.denoise_dual_features / denoise_dual_select: this TaskHandle was made without the scene whose features await_() has to render")
         cam = st.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         halves = [np.zeros(shape) for _ in range(4)]
@@ -466,7 +553,13 @@ class TaskHandle:  # src/trace.rs:70-135
             counts_b.append(t.count_b)
         with Context(self.device) as ctx:
             params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
-            if st.denoise_dual_features:
+            if st.denoise_dual_select:
+                counts_f = [a + b for a, b in zip(counts_a, counts_b)]
+                feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
+                out = denoise_dual_select_arrays(ctx, *halves, rects, counts_a, counts_b, st.select_candidates(), features=feats, features_sq=feats_sq,
+                                                 counts_f=counts_f, want=(), radius=st.denoise_radius, patch_radius=st.denoise_patch, sure_window=2,
+                                                 select_window=2)["out"]
+            elif st.denoise_dual_features:
                 counts_f = [a + b for a, b in zip(counts_a, counts_b)]
                 feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
                 out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, features=feats, features_sq=feats_sq, counts_f=counts_f,
@@ -667,4 +760,4 @@ def _render_tiled_dual(scene, settings, devices):
                 o.close()
             except Exception:  # noqa: BLE001 (a failing close must not keep the others open, nor hide the body's own error)
                 pass
-    return TaskHandle(settings, messages, devices[0], scene if settings.denoise_dual_features else None)
+    return TaskHandle(settings, messages, devices[0], scene if settings.denoise_dual_features or settings.denoise_dual_select else None)

@@ -246,7 +246,7 @@ class Settings:
                  worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
                  adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
-                 adaptive_min_samples=32, denoise_dual_features=False):
+                 adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -292,7 +292,16 @@ class Settings:
         # Feature weights in the dual-buffer filter (False = off; needs denoise_dual): the filter is rmd_denoise_dual_guided, with the first-hit
         # features at count_a + count_b samples per tile, k_f = denoise_feature_k and tau = denoise_feature_tau; the adaptive check is its region form.
         self.denoise_dual_features = bool(denoise_dual_features)
+        # Per-pixel choice among dual-buffer filters (False = off; needs denoise_dual): await_() renders the finished tiles' features as
+        # denoise_dual_features does and returns rmd_denoise_dual_select's frame at select_candidates() with both windows 2.  The adaptive check is untouched.
+        self.denoise_dual_select = bool(denoise_dual_select)
         self.check_denoise()
+
+    def select_candidates(self):
+        """The candidates of denoise_dual_select, as render.denoise_dual_select takes them: the unguided filter at denoise_k, and the guided one at k = 1.0
+        with denoise_feature_k and denoise_feature_tau."""
+        return [dict(k=self.denoise_k, alpha=self.denoise_alpha), dict(k=1.0, alpha=self.denoise_alpha, guided=True, k_f=self.denoise_feature_k,
+                                                                      tau=self.denoise_feature_tau)]
 
     def check_adaptive(self):
         """Raises ValueError for adaptive settings render_tiled cannot follow."""
@@ -327,6 +336,8 @@ class Settings:
             raise ValueError("denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight")
         if self.denoise_dual_features and not self.denoise_dual:
             raise ValueError("denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)")
+        if self.denoise_dual_select and not self.denoise_dual:
+            raise ValueError("denoise_dual_select needs denoise_dual (it selects rmd_denoise_dual_select)")
         if not self.adaptive_denoised_threshold >= 0.0:
             raise ValueError("adaptive_denoised_threshold must be >= 0 (0 = off)")
         if self.adaptive_denoised_threshold > 0.0 and not self.denoise_dual:
