@@ -63,7 +63,7 @@ enum {
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
-	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select) */
+	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select, rmd_denoise_atrous) */
 };
 
 /* ---- scene description (mirrors core/src/scene.rs:8-45, core/src/lib.rs:21-26) ---- */
@@ -420,6 +420,45 @@ rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, c
 rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
                               uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
                               uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev);
+/*
+ * A FAST filter for previews: the edge-avoiding a-trous wavelet filter of Dammertz, Sewtz, Hanika and Lensch ("Edge-Avoiding A-Trous Wavelet
+ * Transform for fast Global Illumination Filtering", 2010), its weights steered by the per-pixel variance and by the feature buffers, the
+ * variance carried from level to level as in the spatial part of SVGF (Schied et al. 2017).  An addition within ABI 6: RMD_ABI_VERSION stays 6,
+ * no struct changes, a caller finds the function by its symbol.  `levels` passes of 5 x 5 taps at steps 1, 2, 4, ... : 25 * levels taps per pixel
+ * against rmd_denoise's 441 neighbours of 49 patch terms each.
+ * S, Q, F, G, the rects, n_i, u, v, VALID, f, g, FEATURE-VALID, s_ij, eps, k^2 and k_f^2 are rmd_denoise_guided's, word for word; there is one
+ * count per rect, and it serves colour and features alike.
+ *     state   c^0 = u and v^0 = v: three channels each, per pixel
+ *     taps    H5 = {1/16, 1/4, 3/8, 1/4, 1/16};  h(i, j) = H5[i + 2] * H5[j + 2] for i, j in -2..2   (these products are exact in binary64)
+ * Level l = 0 .. levels - 1, step s = 2^l, for a valid p: the taps are q = p + s*(i, j), in raster order (j ascending, then i ascending).  A tap
+ * is taken if q lies inside the frame (not clamped) and q is valid; the centre tap is always taken, through the same operations as any other.
+ *     term_c  rmd_denoise's formula with (u, v) read as (c^l, v^l) of p and q
+ *     D       = ((term_0 + term_1) + term_2) / 3.0
+ *     w_c     = exp(-(D > 0 ? D : 0))                    — a NaN D gives w_c = 1, as the comparison leaves it
+ *     w       = w_f if feat_dev is given, p and q are both feature-valid and w_f < w_c, else w_c
+ *               Phi_j, D_f and w_f = exp(-D_f) exactly rmd_denoise_guided's, made from f and g, which no level changes
+ *     hw      = h(i, j) * w
+ *     from 0.0, over the taken taps in order:   A_c = A_c + hw * c^l_qc;   B_c = B_c + (hw * hw) * v^l_qc;   Wsum = Wsum + hw
+ *     c^{l+1}_pc = A_c / Wsum;    v^{l+1}_pc = B_c / (Wsum * Wsum)
+ * For a p that is not valid, c and v are never read by anyone.
+ *     out_pc  = c^levels_pc     for a valid p
+ *     out_pc  = S_pc / n_p      exactly as IEEE gives it, for any other p (a NaN stays NaN)
+ * out_dev holds MEANS, as rmd_denoise's.  So: levels = 0 gives S / n bit for bit; NULL features give the colour weight alone; all-zero features
+ * with counts >= 2 give w_f = 1 and so the unguided bytes; a pixel that is not valid is never a tap, so a NaN does not spread; a pixel's value does
+ * not depend on how the rects cut the frame.
+ * The propagated v steers the later levels and is NOT an error estimate: after level 0 the neighbours' noise is correlated, and sqrt(mean v)
+ * reads 4 - 5 times below the true error.  Because of that v is not returned.  There is no dual or region form.
+ * Arguments (all checked before the device is touched, anything else RMD_ERR_INVALID_ARGUMENT): rmd_denoise_guided's rules for the buffers, their
+ * aliasing (the three W*H*3-double ranges, the two W*H*7-double feature ranges), width, height, the rects, the counts, k and alpha, and for k_f
+ * and tau when features are given; feat_dev and feat_sq_dev are both given or both NULL (when NULL, k_f and tau are not read);
+ * levels <= RMD_ATROUS_MAX_LEVELS.  Synchronous, and reports an earlier device fault, like rmd_denoise.  Values a caller may start from:
+ * levels 5, k 3.0, alpha 1, k_f 1.0, tau 1e-2 (k = 0.45, rmd_denoise's, is useless here: a single pixel's distance has no patch to average
+ * over).
+ */
+#define RMD_ATROUS_MAX_LEVELS 8u
+rmd_status rmd_denoise_atrous(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                              uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                              uint32_t levels, double k, double alpha, double k_f, double tau, double *out_dev);
 /*
  * DUAL-BUFFER denoising (the cross filter of Rousselle, Knaus and Zwicker 2012, the paper rmd_denoise follows; an addition within ABI 6:
  * RMD_ABI_VERSION stays 6, no struct changes, a caller finds the functions by their symbols).  The samples are split into two disjoint sets A

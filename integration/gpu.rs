@@ -79,6 +79,10 @@ extern "C" {
     fn rmd_denoise_guided(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
                           width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, radius: u32,
                           patch_radius: u32, k: f64, alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64) -> i32;
+    // the fast filter for previews: `levels` (<= 8) edge-avoiding a-trous passes steered by the variance and, when given, by the feature buffers
+    fn rmd_denoise_atrous(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
+                          width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, levels: u32, k: f64,
+                          alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64) -> i32;
     fn rmd_denoise_dual(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64, accum_sq_b_dev: *const f64,
                         width: u32, height: u32, rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, n_rects: u32, radius: u32,
                         patch_radius: u32, k: f64, alpha: f64, out_dev: *mut f64, err_dev: *mut f64) -> i32;

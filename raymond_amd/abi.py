@@ -38,6 +38,7 @@ RMD_MAT_DIFFUSE, RMD_MAT_METAL, RMD_MAT_EMISSION = 0, 1, 2
 
 RMD_MAX_BOUNCE_LIMIT = 16
 RMD_FEATURE_CHANNELS = 7  # first-hit feature buffers: 0..2 normal xyz, 3..5 albedo rgb, 6 depth
+RMD_ATROUS_MAX_LEVELS = 8  # rmd_denoise_atrous: the most levels a call may ask for
 RMD_RENDER_DOF = 1  # rmd_settings.flags
 RMD_RENDER_TRACE_BLACK_PATHS = 2  # never end a zero-throughput path early
 RMD_RENDER_END_BLACK_PATHS = 4  # end them in scenes with grids too (flags 0: only where provably exact, i.e. scenes without grids)

@@ -1028,6 +1028,70 @@ rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const d
 	                       patch_radius, k, alpha, k_f, tau, out_dev);
 }
 
+// ---------------------------------------------------------------- the a-trous filter (denoise_atrous.hip)
+static rmd_status denoise_atrous_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                                      uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                                      uint32_t levels, double k, double alpha, double k_f, double tau, double *out_dev) {
+	if (rmd_status s = bind(ctx)) return s;
+	// device scratch: [c and v, two sets of six planes: 12 * W*H doubles][guided: the planar per-pixel f and g, 14 planes of W*H doubles]
+	// [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each, padded to 16 bytes]
+	const size_t n_px = (size_t)width * height;
+	const size_t cv_bytes = n_px * 12u * sizeof(double), plane_bytes = feat_dev ? n_px * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
+	const size_t img_bytes = (n_px * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = ((size_t)n_rects * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	rmd::DeviceBuffer scratch;
+	RMD_HIP(ctx, scratch.alloc(cv_bytes + plane_bytes + img_bytes + rect_bytes + count_bytes));
+	unsigned char *d = scratch.as<unsigned char>();
+	double *d_cv = scratch.as<double>();
+	double *d_planes = feat_dev ? reinterpret_cast<double *>(d + cv_bytes) : nullptr;
+	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + cv_bytes + plane_bytes);
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + cv_bytes + plane_bytes + img_bytes);
+	uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + cv_bytes + plane_bytes + img_bytes + rect_bytes);
+	if (n_rects != 0) {
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, (size_t)n_rects * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+	}
+	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
+	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
+	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
+	RMD_HIP(ctx, rmd::launch_denoise_atrous(ctx->stream, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, d_rects, d_counts, n_rects, columns, width, height, levels, k,
+	                                        alpha, k_f, tau, d_img, d_cv, d_planes, out_dev));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
+}
+
+rmd_status rmd_denoise_atrous(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                              uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                              uint32_t levels, double k, double alpha, double k_f, double tau, double *out_dev) {
+	const std::string name = "rmd_denoise_atrous: ";
+	if (!accum_dev || !accum_sq_dev || !out_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
+	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
+	{ // rmd_denoise_guided's aliasing rules
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
+		const unsigned __int128 s = (uintptr_t)accum_dev, q = (uintptr_t)accum_sq_dev, o = (uintptr_t)out_dev, f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
+		auto overlap = [&](unsigned __int128 a, unsigned __int128 na, unsigned __int128 b, unsigned __int128 nb) { return a < b + nb && b < a + na; };
+		if (overlap(s, bytes, q, bytes) || overlap(s, bytes, o, bytes) || overlap(q, bytes, o, bytes))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "accum_dev, accum_sq_dev and out_dev must not alias");
+		if (feat_dev && (overlap(f, fbytes, g, fbytes) || overlap(f, fbytes, o, bytes) || overlap(g, fbytes, o, bytes)))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev, feat_sq_dev and out_dev must not alias");
+	}
+	if (levels > rmd::kAtrousMaxLevels) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "levels must be <= 8");
+	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
+	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
+	if (feat_dev) {
+		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
+		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
+	}
+	return rmd::guarded(ctx, "rmd_denoise_atrous", [&] {
+		const char *why = nullptr;
+		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
+		return denoise_atrous_impl(ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, levels, k, alpha, k_f, tau,
+		                           out_dev);
+	});
+}
+
 // ---------------------------------------------------------------- dual-buffer denoising (denoise_dual.hip)
 // region null: rmd_denoise_dual, every pixel.  region not null: rmd_denoise_dual_region, the pixels of its n_region rects only.  feat / feat_sq not
 // null: the guided forms (counts_f: the features' own counts)

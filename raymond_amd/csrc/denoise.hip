@@ -235,11 +235,9 @@ size_t denoise_lds_bytes(uint32_t tile_width, uint32_t radius, uint32_t patch_ra
 }
 uint32_t denoise_tile_width(uint32_t radius, uint32_t patch_radius) { return denoise_lds_bytes(32u, radius, patch_radius) <= kLdsBudgetBytes ? 32u : 24u; }
 
-hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
+hipError_t launch_denoise_planes(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
                                  const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
-                                 double *out) {
-	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+                                 uint32_t *n_img, double *feat_planes) {
 	const bool guided = feat != nullptr;
 	if (guided && (feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
 	hipError_t e = hipMemsetAsync(n_img, 0, (size_t)W * H * sizeof(uint32_t), stream);
@@ -253,6 +251,17 @@ hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const 
 		hipLaunchKernelGGL(feature_planes_kernel, dim3((uint32_t)((N + 255u) / 256u)), dim3(256), 0, stream, accum, accum_sq, feat, feat_sq, n_img, N, feat_planes);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
+	return hipSuccess;
+}
+
+hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
+                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
+                                 uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
+                                 double *out) {
+	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
+	const bool guided = feat != nullptr;
+	hipError_t e = launch_denoise_planes(stream, accum, accum_sq, feat, feat_sq, rects, rect_counts, n_rects, count_image_columns, W, H, n_img, feat_planes);
+	if (e != hipSuccess) return e;
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits: 145,152 B at r = 12, f = 4)

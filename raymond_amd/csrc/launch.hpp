@@ -122,6 +122,18 @@ hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const 
                                  const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
                                  uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
                                  double *out);
+// The preamble of launch_denoise_guided on its own (denoise.hip), for the filters of other units: n_img = the per-pixel counts, and when feat / feat_sq
+// are given feat_planes = the 14 planar images of the per-pixel f and g (a pixel that is not feature-valid keeps a NaN in plane 0)
+hipError_t launch_denoise_planes(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
+                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
+                                 uint32_t *n_img, double *feat_planes);
+// rmd_denoise_atrous (denoise_atrous.hip): out = the frame after `levels` levels of the edge-avoiding a-trous filter (levels = 0: S / n).  n_img, rects,
+// rect_counts, count_image_columns, feat / feat_sq and feat_planes as launch_denoise_guided's; cv is 12 * W*H doubles of scratch, the two sets of six
+// planes (c and v) the levels alternate between.  levels, k, alpha, k_f and tau are checked by the caller
+constexpr uint32_t kAtrousMaxLevels = (uint32_t)RMD_ATROUS_MAX_LEVELS;
+hipError_t launch_denoise_atrous(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
+                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
+                                 uint32_t levels, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *cv, double *feat_planes, double *out);
 // One workgroup's share of rmd_denoise_dual_region: its tile's origin, and the far corner (exclusive) of the region rect the tile was cut from
 struct alignas(16) DualBlock {
 	uint32_t x0, y0, x_end, y_end;

@@ -7,6 +7,9 @@
 //                                                                     [--denoise-alpha A]]   (the image is rmd_denoise's, on GPU 0)
 //                                                                    [--denoise-features 1 [--denoise-feature-k K] [--denoise-feature-tau T]]
 //                                                                      (needs --denoise 1: first-hit features guide the filter, rmd_denoise_guided)
+//                                                                    [--denoise-atrous 1 [--denoise-atrous-levels N] [--denoise-atrous-k K]]
+//                                                                      (needs --denoise 1, not with --denoise-dual: the fast filter for previews,
+//                                                                       rmd_denoise_atrous, guided with --denoise-features 1)
 //                                                                    [--dump-features FILE]   (the W*H*7 feature means as raw f64: the AOVs)
 //                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
 //                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
@@ -212,6 +215,9 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-feature-k")) st.denoise_feature_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-feature-tau")) st.denoise_feature_tau = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-atrous")) st.denoise_atrous = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--denoise-atrous-levels")) st.denoise_atrous_levels = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
+				else if (!std::strcmp(argv[i], "--denoise-atrous-k")) st.denoise_atrous_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--dump-features")) dump_features = argv[i + 1];
 			}
 			Scene scene;

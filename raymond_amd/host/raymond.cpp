@@ -566,6 +566,12 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 	if (!(settings.denoise_feature_tau > 0.0) || !std::isfinite(settings.denoise_feature_tau))
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_feature_tau must be finite and > 0");
 	if (settings.denoise_features && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_features needs denoise");
+	if (settings.denoise_atrous_levels > RMD_ATROUS_MAX_LEVELS) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous_levels must be <= 8");
+	if (!(settings.denoise_atrous_k > 0.0) || !std::isfinite(settings.denoise_atrous_k))
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous_k must be finite and > 0");
+	if (settings.denoise_atrous && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous needs denoise");
+	if (settings.denoise_atrous && settings.denoise_dual)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous cannot be combined with denoise_dual: rmd_denoise_atrous has no dual form");
 	if (!(settings.adaptive_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_threshold > 0.0 && settings.samples_per_iteration == 0)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)");
@@ -755,11 +761,16 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 		}
 		check(rmd_framebuffer_upload(ctx, sums.data(), dev[0], sums.size()), ctx, "rmd_framebuffer_upload");
 		check(rmd_framebuffer_upload(ctx, sums_sq.data(), dev[1], sums_sq.size()), ctx, "rmd_framebuffer_upload");
-		// (fdev both null without denoise_features: exactly rmd_denoise)
-		check(rmd_denoise_guided(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
-		                         settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,
-		                         settings.denoise_feature_tau, dev[2]),
-		      ctx, "rmd_denoise_guided");
+		if (settings.denoise_atrous) // (fdev both null without denoise_features: the colour weight alone)
+			check(rmd_denoise_atrous(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+			                         settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
+			                         settings.denoise_feature_tau, dev[2]),
+			      ctx, "rmd_denoise_atrous");
+		else // (fdev both null without denoise_features: exactly rmd_denoise)
+			check(rmd_denoise_guided(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+			                         settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,
+			                         settings.denoise_feature_tau, dev[2]),
+			      ctx, "rmd_denoise_guided");
 		check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
 	} catch (...) {
 		for (double *d : dev)

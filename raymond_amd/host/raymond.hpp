@@ -139,6 +139,13 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// rmd_denoise_guided, k_f = denoise_feature_k, tau = denoise_feature_tau (both finite and > 0, or render_tiled throws).
 	bool denoise_features = false;
 	double denoise_feature_k = 1.0, denoise_feature_tau = 1e-2; // (the best of the sweep in DESIGN.md section 12)
+	// The fast filter for previews (needs denoise, not with denoise_dual; false = off): await() returns rmd_denoise_atrous's frame at
+	// denoise_atrous_levels (0..8) and k = denoise_atrous_k (finite and > 0) with denoise_alpha, guided by the first-hit features when
+	// denoise_features is on (denoise_feature_k, denoise_feature_tau).  denoise_radius, denoise_patch and denoise_k are then not used.  render_tiled
+	// throws for levels or k out of range whether or not the setting is on.
+	bool denoise_atrous = false;
+	uint32_t denoise_atrous_levels = 5;
+	double denoise_atrous_k = 3.0;
 	// Dual-buffer denoising (needs denoise and samples_per_iteration > 0, one GPU, not with denoise_features; false = off): pass j of a tile, counted
 	// from 0, adds its samples to half A when j is even and to half B when j is odd; TileFinished tiles carry both halves and await() returns
 	// rmd_denoise_dual's frame (raymond_hip.h).

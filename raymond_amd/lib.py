@@ -69,6 +69,11 @@ SIGNATURES = {
         [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
          C.c_double, C.c_double, _vp],
     ),
+    "rmd_denoise_atrous": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double,
+         C.c_double, _vp],
+    ),
     "rmd_denoise_dual": (
         C.c_int32,
         [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,

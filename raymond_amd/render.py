@@ -251,6 +251,39 @@ def denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **
                 b.close()
 
 
+def denoise_atrous(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuffer, levels=5, k=3.0, alpha=1.0, features=None, features_sq=None, k_f=1.0,
+                   tau=1e-2):
+    """rmd_denoise_atrous: `out_framebuffer` = the frame after `levels` levels of the edge-avoiding a-trous filter (the fast filter for previews), with
+    the feature weight of the FeatureBuffers `features` / `features_sq` when they are given.  The result holds means, not sums."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != len(rects):
+        raise ValueError("one sample count per rect")
+    ctx.check(ctx.L.rmd_denoise_atrous(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr,
+                                       None if features_sq is None else features_sq.ptr, framebuffer.width, framebuffer.height, tile_array(rects),
+                                       counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(levels), float(k), float(alpha), float(k_f), float(tau),
+                                       out_framebuffer.ptr))
+
+
+def denoise_atrous_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **params):
+    """denoise_atrous() for host arrays: (H, W, 3) sums and sums of squares and (H, W, 7) feature sums and sums of squares in (the latter two may
+    both be None), the (H, W, 3) filtered means out."""
+    H, W = sums.shape[0], sums.shape[1]
+    bufs = [Framebuffer(ctx, W, H) for _ in range(3)]
+    fbufs = [FeatureBuffer(ctx, W, H) for _ in range(2)] if feats is not None else [None, None]
+    try:
+        bufs[0].upload(sums)
+        bufs[1].upload(sums_sq)
+        if feats is not None:
+            fbufs[0].upload(feats)
+            fbufs[1].upload(feats_sq)
+        denoise_atrous(ctx, bufs[0], bufs[1], rects, counts, bufs[2], features=fbufs[0], features_sq=fbufs[1], **params)
+        return bufs[2].download()
+    finally:
+        for b in bufs + fbufs:
+            if b is not None:
+                b.close()
+
+
 class ErrorImage(Framebuffer):
     """W*H f64 in HBM: rmd_denoise_dual's per-pixel error estimate (the allocation is a framebuffer's; its first W*H doubles are used)."""
 
@@ -490,13 +523,16 @@ class TaskHandle:  # src/trace.rs:70-135
         With settings.denoise (an extension): the finished tiles' sums, sums of squares and sample counts are assembled and the frame comes
         back through rmd_denoise on `device` — means as well; a pixel that no finished tile covers has n = 0 and comes back as 0 / 0.  With
         settings.denoise_features as well: the scene is uploaded to `device`, the finished tiles' first-hit features are rendered there
-        (finished_tile_features) and the filter is rmd_denoise_guided."""
+        (finished_tile_features) and the filter is rmd_denoise_guided.  With settings.denoise_atrous the filter is rmd_denoise_atrous instead, at
+        denoise_atrous_levels and denoise_atrous_k, guided by the same features when denoise_features is on."""
         cam = self.settings.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         out = np.zeros(shape, dtype=np.float64)
         if self.settings.denoise and self.settings.denoise_dual:
             return self._await_dual()
         denoised = self.settings.denoise
+        if denoised and self.settings.denoise_atrous:
+            self.settings.check_denoise()
         if denoised and self.settings.denoise_features:
             self.settings.check_denoise()
             if self.scene is None:
@@ -519,7 +555,11 @@ class TaskHandle:  # src/trace.rs:70-135
             st = self.settings
             with Context(self.device) as ctx:
                 params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
-                if st.denoise_features:
+                if st.denoise_atrous:
+                    feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts) if st.denoise_features else (None, None)
+                    out = denoise_atrous_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, levels=st.denoise_atrous_levels, k=st.denoise_atrous_k,
+                                                alpha=st.denoise_alpha, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau)
+                elif st.denoise_features:
                     feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts)
                     out = denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
                                                 **params)

@@ -246,7 +246,8 @@ class Settings:
                  worker_count=None, seed=0x5EED0001, use_dof=False, trace_black_paths=False, end_black_paths=False, adaptive_threshold=0.0,
                  adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
-                 adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False):
+                 adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False, denoise_atrous=False,
+                 denoise_atrous_levels=5, denoise_atrous_k=3.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -295,6 +296,12 @@ class Settings:
         # Per-pixel choice among dual-buffer filters (False = off; needs denoise_dual): await_() renders the finished tiles' features as
         # denoise_dual_features does and returns rmd_denoise_dual_select's frame at select_candidates() with both windows 2.  The adaptive check is untouched.
         self.denoise_dual_select = bool(denoise_dual_select)
+        # The fast filter for previews (False = off; needs denoise, excludes denoise_dual): await_() returns rmd_denoise_atrous's frame at
+        # denoise_atrous_levels (0..8) and k = denoise_atrous_k with denoise_alpha — guided by the first-hit features when denoise_features is on,
+        # with denoise_feature_k and denoise_feature_tau.  denoise_radius, denoise_patch and denoise_k are then not used.
+        self.denoise_atrous = bool(denoise_atrous)
+        self.denoise_atrous_levels = denoise_atrous_levels
+        self.denoise_atrous_k = float(denoise_atrous_k)
         self.check_denoise()
 
     def select_candidates(self):
@@ -326,6 +333,15 @@ class Settings:
             raise ValueError("denoise_feature_k must be finite and > 0")
         if not (self.denoise_feature_tau > 0.0 and np.isfinite(self.denoise_feature_tau)):
             raise ValueError("denoise_feature_tau must be finite and > 0")
+        v = self.denoise_atrous_levels
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= abi.RMD_ATROUS_MAX_LEVELS:
+            raise ValueError("denoise_atrous_levels must be an integer in [0, %d]" % abi.RMD_ATROUS_MAX_LEVELS)
+        if not (self.denoise_atrous_k > 0.0 and np.isfinite(self.denoise_atrous_k)):
+            raise ValueError("denoise_atrous_k must be finite and > 0")
+        if self.denoise_atrous and not self.denoise:
+            raise ValueError("denoise_atrous needs denoise")
+        if self.denoise_atrous and self.denoise_dual:
+            raise ValueError("denoise_atrous cannot be combined with denoise_dual: rmd_denoise_atrous has no dual form")
         if self.denoise_features and not self.denoise:
             raise ValueError("denoise_features needs denoise")
         if self.denoise_dual and not self.denoise:
