@@ -62,6 +62,7 @@ enum {
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
+	                                 rmd_denoise_atrous_dual,
 	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
 	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select, rmd_denoise_atrous) */
 };
@@ -447,7 +448,7 @@ rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const d
  * with counts >= 2 give w_f = 1 and so the unguided bytes; a pixel that is not valid is never a tap, so a NaN does not spread; a pixel's value does
  * not depend on how the rects cut the frame.
  * The propagated v steers the later levels and is NOT an error estimate: after level 0 the neighbours' noise is correlated, and sqrt(mean v)
- * reads 4 - 5 times below the true error.  Because of that v is not returned.  There is no dual or region form.
+ * reads 4 - 5 times below the true error.  Because of that v is not returned.  There is no region form; the dual form is rmd_denoise_atrous_dual.
  * Arguments (all checked before the device is touched, anything else RMD_ERR_INVALID_ARGUMENT): rmd_denoise_guided's rules for the buffers, their
  * aliasing (the three W*H*3-double ranges, the two W*H*7-double feature ranges), width, height, the rects, the counts, k and alpha, and for k_f
  * and tau when features are given; feat_dev and feat_sq_dev are both given or both NULL (when NULL, k_f and tau are not read);
@@ -621,6 +622,44 @@ rmd_status rmd_denoise_dual_select(rmd_context *ctx,
     uint32_t radius, uint32_t patch_radius,
     const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
     double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev);
+/*
+ * rmd_denoise_atrous on TWO SAMPLE HALVES, each filtered with the weights of the other, with rmd_denoise_dual's error estimate: the fast filter in
+ * a form that can drive adaptive sampling (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes, found by its symbol).
+ * S_A, Q_A, S_B, Q_B, the rects, n_A, n_B, u_A, v_A, u_B, v_B, validity and DUAL-VALID are rmd_denoise_dual's, word for word.  F, G, rect_counts_f,
+ * n_F, f, g and FEATURE-VALID (dual-valid, n_F >= 2, fourteen finite values; the features carry their own count) are rmd_denoise_dual_guided's.
+ * s_ij, Phi_j, D_f and w_f = exp(-D_f) are rmd_denoise_guided's.  H5, h(i, j), the tap order (j ascending, then i ascending), "inside the frame, not
+ * clamped", term_c and D = ((term_0 + term_1) + term_2) / 3.0 are rmd_denoise_atrous's.
+ *     state   c_A^0 = u_A, v_A^0 = v_A, c_B^0 = u_B, v_B^0 = v_B
+ * Level l = 0 .. levels - 1, step 2^l, for a dual-valid p and a tap q that is taken (inside the frame and dual-valid; the centre tap is always
+ * taken, through the same operations as any other):
+ *     w_cB    = exp(-(D_B > 0 ? D_B : 0))                with D_B made from (c_B^l, v_B^l) of p and q
+ *     w_B     = w_f if feat_dev is given, p and q are both feature-valid and w_f < w_cB, else w_cB
+ *     hw_B    = h(i, j) * w_B
+ *     from 0.0, over the taken taps in order:   A_c = A_c + hw_B * c_A^l_qc;   B_c = B_c + (hw_B * hw_B) * v_A^l_qc;   Wsum = Wsum + hw_B
+ *     c_A^{l+1}_pc = A_c / Wsum;    v_A^{l+1}_pc = B_c / (Wsum * Wsum)
+ * and symmetrically w_A, made from (c_A^l, v_A^l), filters half B.  The same w_f enters both.
+ *     f_A = c_A^levels, f_B = c_B^levels; out and err are rmd_denoise_dual's operations on f_A and f_B, word for word
+ * A pixel that is not dual-valid takes the merged mean (S_A + S_B) / (n_A + n_B) and err = NaN, and is never a tap.
+ * So: levels = 0 gives f_A = u_A and f_B = u_B bit for bit, rmd_denoise_dual's radius-0 closed form.  With the two halves equal and rect_counts_f
+ * equal to their counts, f_A = f_B = rmd_denoise_atrous of either half bit for bit and err = 0; out is then f again when n is a power of two.
+ * NULL features give the colour weights alone (rect_counts_f, k_f and tau are then not read); all-zero features at counts >= 2 give the unguided
+ * bytes.  A pixel's value does not depend on how the rects cut the frame.
+ * err measures VARIANCE, not bias, and after level 0 the two halves' weights are no longer independent of the values they multiply: level l + 1
+ * makes w_B from c_B^{l+1}, which level l made under weights from half A.  It therefore reads LOW.  It ranks tiles; it is not a bound (DESIGN.md
+ * section 18).  There is no region form: a level's taps reach 2^(l+1) pixels, so the region's dilation at 5 levels covers most of a frame.
+ * Arguments (all checked before the device is touched, anything else RMD_ERR_INVALID_ARGUMENT): rmd_denoise_dual_guided's rules for the buffers,
+ * their aliasing, the rects, the three count arrays, k, alpha, k_f and tau; levels <= RMD_ATROUS_MAX_LEVELS; err_dev may be NULL.  Synchronous,
+ * and reports an earlier device fault, like rmd_denoise_dual.  Values a caller may start from: rmd_denoise_atrous's.
+ */
+rmd_status rmd_denoise_atrous_dual(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t levels, double k, double alpha, double k_f, double tau,
+    double *out_dev, double *err_dev);
 /*
  * Per-tile error of the delivered frame from rmd_denoise_dual's err_dev (W*H doubles):
  *     out_err_host[r] = sqrt((sum of err_p over rect r's pixels) / the rect's pixel count)

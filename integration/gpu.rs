@@ -106,6 +106,12 @@ extern "C" {
                                rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32, radius: u32, patch_radius: u32,
                                cands: *const rmd_denoise_candidate, n_cands: u32, sure_window: u32, select_window: u32, out_dev: *mut f64, err_dev: *mut f64,
                                sure_dev: *mut f64, win_dev: *mut u32) -> i32;
+    // the fast filter on the two halves, each under the other's weights, with rmd_denoise_dual's error estimate (feat_dev = feat_sq_dev = null: the
+    // colour weights alone; err_dev may be null): what the adaptive check calls with denoise_dual_atrous
+    fn rmd_denoise_atrous_dual(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64, accum_sq_b_dev: *const f64,
+                               feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, rect_counts_a: *const u32,
+                               rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32, levels: u32, k: f64, alpha: f64, k_f: f64, tau: f64,
+                               out_dev: *mut f64, err_dev: *mut f64) -> i32;
     fn rmd_tile_error_dual(ctx: *mut rmd_context, err_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, n_rects: u32,
                            out_err_host: *mut f64) -> i32;
 }

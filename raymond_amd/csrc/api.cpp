@@ -1236,6 +1236,85 @@ rmd_status rmd_denoise_dual_guided_region(rmd_context *ctx, const double *accum_
 	                            rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, region, n_region, radius, patch_radius, k, alpha, k_f, tau, out_dev, err_dev);
 }
 
+// ---------------------------------------------------------------- the a-trous filter on two halves (denoise_atrous_dual.hip)
+static rmd_status denoise_atrous_dual_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
+                                           const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
+                                           const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, uint32_t levels, double k, double alpha, double k_f,
+                                           double tau, double *out_dev, double *err_dev) {
+	if (rmd_status s = bind(ctx)) return s;
+	// device scratch: [the state, two sets of twelve planes: 24 * W*H doubles][guided: the planar per-pixel f and g, 14 * W*H doubles]
+	// [both halves' per-pixel counts and (guided) the features': 2 or 3 * W*H uint32, padded to 16 bytes][rects: 16 bytes each]
+	// [counts of A, of B and (guided) of the features: 4 bytes each]
+	const size_t N = (size_t)width * height;
+	const size_t state_bytes = N * 24u * sizeof(double), fplane_bytes = feat ? N * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
+	const size_t img_bytes = ((feat ? 3u : 2u) * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
+	rmd::DeviceBuffer scratch;
+	RMD_HIP(ctx, scratch.alloc(state_bytes + fplane_bytes + img_bytes + rect_bytes + (feat ? 3u : 2u) * count_bytes));
+	unsigned char *d = scratch.as<unsigned char>();
+	double *d_state = scratch.as<double>();
+	double *d_fplanes = feat ? reinterpret_cast<double *>(d + state_bytes) : nullptr;
+	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + state_bytes + fplane_bytes);
+	uint32_t *d_fimg = feat ? d_img + 2u * N : nullptr;
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + state_bytes + fplane_bytes + img_bytes);
+	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_rects) + rect_bytes), *d_counts_b = d_counts_a + n_rects;
+	uint32_t *d_counts_f = feat ? d_counts_b + n_rects : nullptr;
+	if (n_rects != 0) {
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		if (feat) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+	}
+	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
+	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
+	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
+	RMD_HIP(ctx, rmd::launch_denoise_atrous_dual(ctx->stream, sa, qa, sb, qb, feat, feat_sq, d_rects, d_counts_a, d_counts_b, d_counts_f, n_rects, columns, width, height,
+	                                             levels, k, alpha, k_f, tau, d_img, d_state, d_fimg, d_fplanes, out_dev, err_dev));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
+}
+
+rmd_status rmd_denoise_atrous_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t levels,
+                                   double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
+	const std::string name = "rmd_denoise_atrous_dual: ";
+	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
+	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
+	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
+	if (feat_dev && n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "rect_counts_f is NULL with n_rects > 0");
+	{ // rmd_denoise_dual_guided's aliasing rules: five ranges of W*H*3 doubles, err_dev's W*H, the two W*H*7-double feature ranges
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		const unsigned __int128 at[6] = {(uintptr_t)accum_a_dev, (uintptr_t)accum_sq_a_dev, (uintptr_t)accum_b_dev, (uintptr_t)accum_sq_b_dev, (uintptr_t)out_dev, (uintptr_t)err_dev};
+		const unsigned __int128 len[6] = {bytes, bytes, bytes, bytes, bytes, bytes / 3u};
+		for (int i = 0; i < (err_dev ? 6 : 5); i++)
+			for (int j = i + 1; j < (err_dev ? 6 : 5); j++)
+				if (at[i] < at[j] + len[j] && at[j] < at[i] + len[i])
+					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, out_dev and err_dev must not alias");
+		if (feat_dev) {
+			const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
+			const unsigned __int128 f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
+			bool bad = f < g + fbytes && g < f + fbytes;
+			for (int i = 0; i < (err_dev ? 6 : 5); i++) bad = bad || (f < at[i] + len[i] && at[i] < f + fbytes) || (g < at[i] + len[i] && at[i] < g + fbytes);
+			if (bad) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must not alias each other, the sum buffers, out_dev or err_dev");
+		}
+	}
+	if (levels > rmd::kAtrousMaxLevels) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "levels must be <= 8");
+	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
+	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
+	if (feat_dev) {
+		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
+		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
+	}
+	return rmd::guarded(ctx, "rmd_denoise_atrous_dual", [&] {
+		const char *why = nullptr;
+		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
+		return denoise_atrous_dual_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
+		                                rect_counts_b, rect_counts_f, n_rects, levels, k, alpha, k_f, tau, out_dev, err_dev);
+	});
+}
+
 static rmd_status denoise_dual_select_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
                                            const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
                                            const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, uint32_t radius, uint32_t patch_radius,

@@ -1,0 +1,201 @@
+// The edge-avoiding a-trous filter on two sample halves, each filtered with the weights of the other, and its per-pixel error estimate
+// (rmd_denoise_atrous_dual; include/raymond_hip.h states the definition, DESIGN.md section 18 the structure and its cost).  A translation unit of
+// its own: no other unit's code objects change.
+//
+// The state is denoise_dual.hip's twelve planes (launch_dual_planes: half h's c in planes 6h + c, its v in planes 6h + 3 + c, a NaN in plane 0 at a
+// pixel that is not dual-valid), twice: the levels alternate between the two sets.  The count images and the fourteen feature planes at the
+// features' own count are that unit's too.
+// atrous_dual_level_kernel<G, LAST> — one level of BOTH cross passes: one thread per pixel, 64 x 4 pixels per workgroup, the 25 taps at step s read
+//                                     straight from the planar images in global memory, no LDS, tap loops rolled (atrous_level_kernel's shape,
+//                                     denoise_atrous.hip).  Per taken tap the thread reads q's twelve state values once, makes the feature weight
+//                                     once (G: guided) and uses it in both passes, and makes two colour distances and two exp: w_B from
+//                                     (c_B, v_B) weighs half A's values, w_A from (c_A, v_A) half B's.  LAST = false writes the other set of
+//                                     twelve planes; LAST = true writes out_dev and err_dev (rmd_denoise_dual's combination of f_A and f_B), and
+//                                     the merged mean and NaN for a pixel that is not dual-valid.
+// atrous_dual_mean_kernel           — levels = 0: the same combination of u_A and u_B.
+// f64 throughout, built with -ffp-contract=off like the rest of the library.
+#include <hip/hip_runtime.h>
+
+#include "launch.hpp"
+
+namespace rmd {
+
+constexpr int kAtrousDualBlockW = 64, kAtrousDualBlockH = 4;
+
+// rmd_denoise's term_c (denoise.hip: denoise_term), restated as denoise_atrous.hip restates it
+__device__ inline double atrous_dual_term(double ua, double ub, double va, double vb, double k2, double alpha) {
+	const double du = ua - ub;
+	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
+}
+
+// H5 = {1/16, 1/4, 3/8, 1/4, 1/16} at i + 2, as selects (denoise_atrous.hip: atrous_h5)
+__device__ inline double atrous_dual_h5(int i) { return i == 0 ? 0.375 : (i == 1 || i == -1 ? 0.25 : 0.0625); }
+
+// rmd_denoise_dual's combination (denoise_dual.hip: dual_combine_pixel) of a dual-valid pixel's f_A = a and f_B = b
+__device__ inline void atrous_dual_combine(const double a[3], const double b[3], double na, double nb, size_t pix, double *__restrict__ out, double *__restrict__ err) {
+	const double nsum = na + nb;
+	double e = 0.0;
+#pragma unroll
+	for (int c = 0; c < 3; c++) {
+		out[pix * 3 + c] = (na * a[c] + nb * b[c]) / nsum;
+		const double h = (a[c] - b[c]) / 2.0;
+		e = c == 0 ? h * h : e + h * h;
+	}
+	if (err) err[pix] = e / 3.0;
+}
+
+// ... and of any other pixel: the merged mean as IEEE gives it, err = NaN
+__device__ inline void atrous_dual_merged(const double *__restrict__ SA, const double *__restrict__ SB, double na, double nb, size_t pix, double *__restrict__ out,
+                                          double *__restrict__ err) {
+	const double nsum = na + nb;
+#pragma unroll
+	for (int c = 0; c < 3; c++) out[pix * 3 + c] = (SA[pix * 3 + c] + SB[pix * 3 + c]) / nsum;
+	if (err) err[pix] = __builtin_nan("");
+}
+
+__global__ __launch_bounds__(256) void atrous_dual_mean_kernel(const double *__restrict__ planes, const double *__restrict__ SA, const double *__restrict__ SB,
+                                                               const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b, size_t N, double *__restrict__ out,
+                                                               double *__restrict__ err) {
+	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	const double na = (double)n_a[i], nb = (double)n_b[i];
+	const double a0 = planes[i];
+	if (a0 == a0) {
+		const double a[3] = {a0, planes[N + i], planes[2 * N + i]}, b[3] = {planes[6 * N + i], planes[7 * N + i], planes[8 * N + i]};
+		atrous_dual_combine(a, b, na, nb, i, out, err);
+	} else {
+		atrous_dual_merged(SA, SB, na, nb, i, out, err);
+	}
+}
+
+// in / next: twelve planes of N = W*H doubles (above).  planes (GUIDED): dual_feature_planes_kernel's 14 planes.  tiles_x: workgroups per row of
+// tiles (the grid is one-dimensional: a frame may be taller than 65,535 tiles)
+template <bool GUIDED, bool LAST>
+__global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_dual_level_kernel(
+    const double *__restrict__ in, double *__restrict__ next, const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
+    const uint32_t *__restrict__ n_b, uint32_t W, uint32_t H, uint32_t tiles_x, int64_t step, double k2, double alpha, const double *__restrict__ planes, double kf2,
+    double tau, double *__restrict__ out, double *__restrict__ err) {
+	const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
+	const int64_t x = (int64_t)bx * kAtrousDualBlockW + (threadIdx.x % kAtrousDualBlockW), y = (int64_t)by * kAtrousDualBlockH + (threadIdx.x / kAtrousDualBlockW);
+	if (x >= (int64_t)W || y >= (int64_t)H) return;
+	const size_t N = (size_t)W * H, pix = (size_t)x + (size_t)y * W;
+	const double ap0 = in[pix];
+	if (!(ap0 == ap0)) { // not dual-valid: never a tap, so only its mark is kept
+		if constexpr (LAST) atrous_dual_merged(SA, SB, (double)n_a[pix], (double)n_b[pix], pix, out, err);
+		else next[pix] = ap0;
+		return;
+	}
+	// p's state: half A's c and v, half B's c and v
+	const double ap1 = in[N + pix], ap2 = in[2 * N + pix], sp0 = in[3 * N + pix], sp1 = in[4 * N + pix], sp2 = in[5 * N + pix];
+	const double bp0 = in[6 * N + pix], bp1 = in[7 * N + pix], bp2 = in[8 * N + pix], tp0 = in[9 * N + pix], tp1 = in[10 * N + pix], tp2 = in[11 * N + pix];
+	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .), as atrous_level_kernel makes them
+	[[maybe_unused]] double fp[kDenoiseFeat], gp[kDenoiseFeat], den[kDenoiseFeat];
+	[[maybe_unused]] bool p_fok = false;
+	if constexpr (GUIDED) {
+#pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) {
+			fp[j] = planes[(size_t)j * N + pix], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pix];
+			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
+			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+		}
+		p_fok = fp[0] == fp[0];
+	}
+	// half A's sums under w_B (a, s, wsa), half B's under w_A (b, t, wsb)
+	double a0 = 0.0, a1 = 0.0, a2 = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, wsa = 0.0;
+	double b0 = 0.0, b1 = 0.0, b2 = 0.0, t0 = 0.0, t1 = 0.0, t2 = 0.0, wsb = 0.0;
+	for (int j = -2; j <= 2; j++) {
+		const int64_t qy = y + step * j;
+		if (qy < 0 || qy >= (int64_t)H) continue;
+		for (int i = -2; i <= 2; i++) {
+			const int64_t qx = x + step * i;
+			if (qx < 0 || qx >= (int64_t)W) continue;
+			const size_t q = (size_t)qx + (size_t)qy * W;
+			const double aq0 = in[q];
+			if (!(aq0 == aq0)) continue;
+			const double aq1 = in[N + q], aq2 = in[2 * N + q], sq0 = in[3 * N + q], sq1 = in[4 * N + q], sq2 = in[5 * N + q];
+			const double bq0 = in[6 * N + q], bq1 = in[7 * N + q], bq2 = in[8 * N + q], tq0 = in[9 * N + q], tq1 = in[10 * N + q], tq2 = in[11 * N + q];
+			const double DA = ((atrous_dual_term(ap0, aq0, sp0, sq0, k2, alpha) + atrous_dual_term(ap1, aq1, sp1, sq1, k2, alpha)) + atrous_dual_term(ap2, aq2, sp2, sq2, k2, alpha)) / 3.0;
+			const double DB = ((atrous_dual_term(bp0, bq0, tp0, tq0, k2, alpha) + atrous_dual_term(bp1, bq1, tp1, tq1, k2, alpha)) + atrous_dual_term(bp2, bq2, tp2, tq2, k2, alpha)) / 3.0;
+			double wA = exp(-(DA > 0.0 ? DA : 0.0)), wB = exp(-(DB > 0.0 ? DB : 0.0));
+			if constexpr (GUIDED) {
+				if (p_fok) {
+					const double fq0 = planes[q];
+					if (fq0 == fq0) { // q is feature-valid too
+						double Df = 0.0;
+#pragma unroll
+						for (int c = 0; c < kDenoiseFeat; c++) {
+							const double fq = c == 0 ? fq0 : planes[(size_t)c * N + q], gq = planes[(size_t)(kDenoiseFeat + c) * N + q];
+							const double df = fp[c] - fq;
+							const double phi = (df * df - (gp[c] + __builtin_fmin(gp[c], gq))) / den[c];
+							if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
+						}
+						const double wf = exp(-Df); // once, for both passes
+						if (wf < wA) wA = wf;
+						if (wf < wB) wB = wf;
+					}
+				}
+			}
+			const double h = atrous_dual_h5(i) * atrous_dual_h5(j);
+			const double hwB = h * wB, hwB2 = hwB * hwB, hwA = h * wA, hwA2 = hwA * hwA;
+			a0 = a0 + hwB * aq0, a1 = a1 + hwB * aq1, a2 = a2 + hwB * aq2;
+			s0 = s0 + hwB2 * sq0, s1 = s1 + hwB2 * sq1, s2 = s2 + hwB2 * sq2;
+			wsa = wsa + hwB;
+			b0 = b0 + hwA * bq0, b1 = b1 + hwA * bq1, b2 = b2 + hwA * bq2;
+			t0 = t0 + hwA2 * tq0, t1 = t1 + hwA2 * tq1, t2 = t2 + hwA2 * tq2;
+			wsb = wsb + hwA;
+		}
+	}
+	if constexpr (LAST) {
+		const double fa[3] = {a0 / wsa, a1 / wsa, a2 / wsa}, fb[3] = {b0 / wsb, b1 / wsb, b2 / wsb};
+		atrous_dual_combine(fa, fb, (double)n_a[pix], (double)n_b[pix], pix, out, err);
+	} else {
+		const double wa2 = wsa * wsa, wb2 = wsb * wsb;
+		next[pix] = a0 / wsa, next[N + pix] = a1 / wsa, next[2 * N + pix] = a2 / wsa;
+		next[3 * N + pix] = s0 / wa2, next[4 * N + pix] = s1 / wa2, next[5 * N + pix] = s2 / wa2;
+		next[6 * N + pix] = b0 / wsb, next[7 * N + pix] = b1 / wsb, next[8 * N + pix] = b2 / wsb;
+		next[9 * N + pix] = t0 / wb2, next[10 * N + pix] = t1 / wb2, next[11 * N + pix] = t2 / wb2;
+	}
+}
+
+hipError_t launch_denoise_atrous_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
+                                      double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes, double *out,
+                                      double *err) {
+	if (levels > kAtrousMaxLevels) return hipErrorInvalidValue;
+	const bool guided = feat != nullptr && levels != 0u;
+	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	const size_t N = (size_t)W * H;
+	const uint64_t blocks_1d = ((uint64_t)N + 255u) / 256u;
+	const uint32_t tiles_x = (W + kAtrousDualBlockW - 1u) / kAtrousDualBlockW;
+	const uint64_t tiles = (uint64_t)tiles_x * ((H + kAtrousDualBlockH - 1u) / kAtrousDualBlockH);
+	if (blocks_1d > 0x7FFFFFFFull || tiles > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+	hipError_t e = launch_dual_planes(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, guided ? feat : nullptr, guided ? feat_sq : nullptr, rects, counts_a, counts_b,
+	                                  counts_f, n_rects, count_image_columns, W, H, n_img, state, n_f_img, feat_planes);
+	if (e != hipSuccess) return e;
+	const uint32_t *n_a = n_img, *n_b = n_img + N;
+	if (levels == 0u) {
+		hipLaunchKernelGGL(atrous_dual_mean_kernel, dim3((uint32_t)blocks_1d), dim3(256), 0, stream, state, accum_a, accum_b, n_a, n_b, N, out, err);
+		return hipGetLastError();
+	}
+	const double k2 = k * k, kf2 = k_f * k_f;
+	const dim3 grid((uint32_t)tiles), block(kAtrousDualBlockW * kAtrousDualBlockH);
+	double *set[2] = {state, state + 12u * N};
+	for (uint32_t l = 0; l < levels; l++) {
+		const double *in = set[l & 1u];
+		double *next = set[(l + 1u) & 1u];
+		const int64_t step = (int64_t)1 << l;
+		const bool last = l + 1u == levels;
+		if (guided) {
+			if (last) hipLaunchKernelGGL((atrous_dual_level_kernel<true, true>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
+			else hipLaunchKernelGGL((atrous_dual_level_kernel<true, false>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
+		} else {
+			if (last) hipLaunchKernelGGL((atrous_dual_level_kernel<false, true>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
+			else hipLaunchKernelGGL((atrous_dual_level_kernel<false, false>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
+		}
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
+	return hipSuccess;
+}
+
+} // namespace rmd

@@ -384,6 +384,15 @@ static hipError_t dual_preamble(hipStream_t stream, const double *accum_a, const
 	return hipSuccess;
 }
 
+// dual_preamble for the filters of other units (denoise_atrous_dual.hip): host code only, the kernels above as they are
+hipError_t launch_dual_planes(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b, const double *feat,
+                              const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f,
+                              uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t *n_img, double *planes, uint32_t *n_f_img,
+                              double *feat_planes) {
+	return dual_preamble(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, feat, feat_sq, rects, counts_a, counts_b, counts_f, n_rects, count_image_columns, W, H, n_img,
+	                     planes, n_f_img, feat_planes);
+}
+
 hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
                                const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
                                const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,

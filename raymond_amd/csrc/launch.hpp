@@ -151,6 +151,21 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
                                const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
                                double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
                                const DualBlock *table, uint32_t n_blocks, double *out, double *err);
+// The preamble of launch_denoise_dual on its own (denoise_dual.hip), for the filters of other units: n_img = both halves' per-pixel counts (2 * W*H
+// uint32), planes = the twelve planar u / v images (half h's u in planes 6h + c, its v in 6h + 3 + c; a pixel that is not dual-valid keeps a NaN in
+// plane 0), and when feat / feat_sq are given n_f_img and feat_planes = the features' per-pixel counts and their 14 planar f and g at that count
+hipError_t launch_dual_planes(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b, const double *feat,
+                              const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f,
+                              uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t *n_img, double *planes, uint32_t *n_f_img,
+                              double *feat_planes);
+// rmd_denoise_atrous_dual (denoise_atrous_dual.hip): out / err (err may be null) = rmd_denoise_dual's combination of the two halves after `levels`
+// levels of the a-trous filter, each half under the other's weights.  Arguments as launch_denoise_dual's; state is 24 * W*H doubles of scratch, the two
+// sets of twelve planes the levels alternate between.  levels, k, alpha, k_f and tau are checked by the caller
+hipError_t launch_denoise_atrous_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
+                                      double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes, double *out,
+                                      double *err);
 // rmd_denoise_dual_select (denoise_dual.hip): launch_denoise_dual's preamble once, then per candidate (a HOST array, checked by the caller) its two cross
 // passes with their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per
 // candidate (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read

@@ -402,6 +402,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 // rmd_tile_error_dual over the live tiles, and the tiles at or below the threshold are finished.  Progress snapshots go out as they are made, the finished tiles at the end.
 // With denoise_dual_features the adaptive check needs the features: two feature buffers, into which every pass also adds the live tiles' first-hit
 // features of its samples [done, done + n) — a tile's features then hold count_a + count_b samples —, and the check is rmd_denoise_dual_guided_region.
+// With denoise_dual_atrous the check is rmd_denoise_atrous_dual on the whole frame, at the same rects, counts and feature buffers.
 void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene scene, Settings st) {
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
@@ -490,7 +491,14 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 				rects.insert(rects.end(), live.begin(), live.end());
 				ca.insert(ca.end(), live.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), live.size(), (uint32_t)n_half[1]);
 				// only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
-				if (guided) {
+				if (st.denoise_dual_atrous) { // the whole frame: rmd_denoise_atrous_dual has no region form (cf not read without the features)
+					std::vector<uint32_t> cf(ca);
+					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
+					check(rmd_denoise_atrous_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
+					                              rects.data(), ca.data(), cb.data(), cf.data(), (uint32_t)rects.size(), st.denoise_atrous_levels, st.denoise_atrous_k,
+					                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fbs[4], fbs[5]),
+					      ctx, "rmd_denoise_atrous_dual");
+				} else if (guided) {
 					std::vector<uint32_t> cf(ca);
 					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
 					check(rmd_denoise_dual_guided_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], feat[0], feat[1], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(),
@@ -585,6 +593,10 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)");
 	if (settings.denoise_dual_select && !settings.denoise_dual)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_select needs denoise_dual (it selects rmd_denoise_dual_select)");
+	if (settings.denoise_dual_atrous && !settings.denoise_dual)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_atrous needs denoise_dual (it selects rmd_denoise_atrous_dual)");
+	if (settings.denoise_dual_atrous && settings.denoise_dual_select)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_atrous cannot be combined with denoise_dual_select: the selection has no a-trous candidate");
 	if (!(settings.adaptive_denoised_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_denoised_threshold > 0.0 && !settings.denoise_dual)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)");
@@ -814,7 +826,18 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
 		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
 		for (int i = 0; i < 4; i++) check(rmd_framebuffer_upload(ctx, halves[i].data(), dev[i], halves[i].size()), ctx, "rmd_framebuffer_upload");
-		if (settings.denoise_dual_select) {
+		if (settings.denoise_dual_atrous) {
+			std::vector<uint32_t> counts_f(counts_a);
+			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
+			if (settings.denoise_dual_features) {
+				for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
+				render_features_on(ctx, *scene, settings, rects, counts_f, fdev[0], fdev[1]);
+			}
+			check(rmd_denoise_atrous_dual(ctx, dev[0], dev[1], dev[2], dev[3], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(),
+			                              counts_f.data(), (uint32_t)rects.size(), settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha,
+			                              settings.denoise_feature_k, settings.denoise_feature_tau, dev[4], tile_errors ? dev[5] : nullptr),
+			      ctx, "rmd_denoise_atrous_dual");
+		} else if (settings.denoise_dual_select) {
 			std::vector<uint32_t> counts_f(counts_a);
 			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
 			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");

@@ -366,6 +366,59 @@ def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts
             b.close()
 
 
+def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, levels=5, k=3.0, alpha=1.0, features=None,
+                        features_sq=None, counts_f=None, k_f=1.0, tau=1e-2):
+    """rmd_denoise_atrous_dual: `out_framebuffer` = the two sample halves `half_a` and `half_b` (as denoise_dual's) after `levels` levels of the
+    edge-avoiding a-trous filter, each half under the other's weights, combined as denoise_dual combines them; `error_image` (an ErrorImage,
+    optional) receives the per-pixel error estimate.  `features` / `features_sq` (FeatureBuffers; rect i holds counts_f[i] feature samples per
+    pixel) add the feature weight; without them counts_f, k_f and tau are not read."""
+    counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
+    counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
+    if len(counts_a) != len(rects) or len(counts_b) != len(rects):
+        raise ValueError("one sample count per rect and half")
+    p_f = None
+    if features is not None or features_sq is not None:
+        counts_f = np.ascontiguousarray([] if counts_f is None else counts_f, dtype=np.uint32)
+        if len(counts_f) != len(rects):
+            raise ValueError("one feature sample count per rect")
+        p_f = counts_f.ctypes.data_as(C.POINTER(C.c_uint32))
+    fb = half_a[0]
+    ctx.check(ctx.L.rmd_denoise_atrous_dual(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, None if features is None else features.ptr,
+                                            None if features_sq is None else features_sq.ptr, fb.width, fb.height, tile_array(rects),
+                                            counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), p_f, len(rects),
+                                            int(levels), float(k), float(alpha), float(k_f), float(tau), out_framebuffer.ptr,
+                                            None if error_image is None else error_image.ptr))
+
+
+def denoise_atrous_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, out_init=None, err_init=None, features=None,
+                               features_sq=None, want_err=True, **params):
+    """denoise_atrous_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate
+    out (None for the latter with want_err=False: the call is then made without an error image).  `out_init` / `err_init`: what the two outputs hold
+    before the call.  `features` / `features_sq`: (H, W, 7) feature sums and sums of squares (with counts_f, k_f, tau among the params)."""
+    H, W = sums_a.shape[0], sums_a.shape[1]
+    opened = []
+    try:
+        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, out_init):
+            opened.append(Framebuffer(ctx, W, H))
+            if arr is not None:
+                opened[-1].upload(arr)
+        opened.append(ErrorImage(ctx, W, H))
+        if err_init is not None:
+            opened[-1].upload(err_init)
+        fbufs = [None, None]
+        if features is not None:
+            for i, arr in enumerate((features, features_sq)):
+                opened.append(FeatureBuffer(ctx, W, H))
+                opened[-1].upload(arr)
+                fbufs[i] = opened[-1]
+        denoise_atrous_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5] if want_err else None,
+                            features=fbufs[0], features_sq=fbufs[1], **params)
+        return opened[4].download(), opened[5].download() if want_err else None
+    finally:
+        for b in opened:
+            b.close()
+
+
 class WinnerImage(ErrorImage):
     """W*H uint32 in HBM: rmd_denoise_dual_select's per-pixel winners (the allocation is a framebuffer's; its first W*H words are used)."""
 
@@ -572,7 +625,8 @@ class TaskHandle:  # src/trace.rs:70-135
         """await_() with settings.denoise_dual: the finished tiles' two halves through rmd_denoise_dual on `device`.  With settings.denoise_dual_features:
         the finished tiles' first-hit features are rendered there at count_a + count_b samples per tile (finished_tile_features) and the filter is
         rmd_denoise_dual_guided.  With settings.denoise_dual_select: the features are rendered the same way and the frame is
-        rmd_denoise_dual_select's at settings.select_candidates(), both windows 2."""
+        rmd_denoise_dual_select's at settings.select_candidates(), both windows 2.  With settings.denoise_dual_atrous the frame is
+        rmd_denoise_atrous_dual's at denoise_atrous_levels and denoise_atrous_k, guided by the same features when denoise_dual_features is on."""
         st = self.settings
         st.check_denoise()
         if (st.denoise_dual_features or st.denoise_dual_select) and self.scene is None:
@@ -593,7 +647,15 @@ class TaskHandle:  # src/trace.rs:70-135
             counts_b.append(t.count_b)
         with Context(self.device) as ctx:
             params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
-            if st.denoise_dual_select:
+            if st.denoise_dual_atrous:
+                guide = {}
+                if st.denoise_dual_features:
+                    counts_f = [a + b for a, b in zip(counts_a, counts_b)]
+                    feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
+                    guide = dict(features=feats, features_sq=feats_sq, counts_f=counts_f, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau)
+                out, _ = denoise_atrous_dual_arrays(ctx, *halves, rects, counts_a, counts_b, levels=st.denoise_atrous_levels, k=st.denoise_atrous_k,
+                                                    alpha=st.denoise_alpha, **guide)
+            elif st.denoise_dual_select:
                 counts_f = [a + b for a, b in zip(counts_a, counts_b)]
                 feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
                 out = denoise_dual_select_arrays(ctx, *halves, rects, counts_a, counts_b, st.select_candidates(), features=feats, features_sq=feats_sq,
@@ -721,7 +783,10 @@ def _render_tiled_dual(scene, settings, devices):
     With settings.denoise_dual_features the adaptive check needs the features: two feature buffers beside the four, into which rmd_render_features
     adds, after each pass, the live tiles' first-hit features of the same samples [done, done + n), so a tile's features hold count_a + count_b
     samples; the check is rmd_denoise_dual_guided_region with those counts.  (Without an adaptive threshold nothing in this loop would read them and
-    none are rendered.)  await_() renders the finished tiles' features itself (finished_tile_features) and returns rmd_denoise_dual_guided's frame."""
+    none are rendered.)  await_() renders the finished tiles' features itself (finished_tile_features) and returns rmd_denoise_dual_guided's frame.
+
+    With settings.denoise_dual_atrous the check is rmd_denoise_atrous_dual on the WHOLE frame instead (it has no region form), at the same rects and
+    counts, guided by the same feature buffers; rmd_tile_error_dual then runs over the live tiles as before."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     st = settings
@@ -782,7 +847,11 @@ def _render_tiled_dual(scene, settings, devices):
                     if guided:
                         guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
                                      tau=st.denoise_feature_tau)
-                    denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide)
+                    if st.denoise_dual_atrous:
+                        denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img,
+                                            levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide)
+                    else:
+                        denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide)
                     errors = tile_error_dual(ctx, err_img, live)
                 conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
                 finish([r for r, c in zip(live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
