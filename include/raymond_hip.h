@@ -62,7 +62,7 @@ enum {
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
-	                                 rmd_denoise_atrous_dual,
+	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
 	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
 	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select, rmd_denoise_atrous) */
 };
@@ -646,7 +646,8 @@ rmd_status rmd_denoise_dual_select(rmd_context *ctx,
  * bytes.  A pixel's value does not depend on how the rects cut the frame.
  * err measures VARIANCE, not bias, and after level 0 the two halves' weights are no longer independent of the values they multiply: level l + 1
  * makes w_B from c_B^{l+1}, which level l made under weights from half A.  It therefore reads LOW.  It ranks tiles; it is not a bound (DESIGN.md
- * section 18).  There is no region form: a level's taps reach 2^(l+1) pixels, so the region's dilation at 5 levels covers most of a frame.
+ * section 18).  The region form is rmd_denoise_atrous_dual_region: a level's taps reach two steps of 2^l pixels, so its cost follows the region dilated by
+ * 2 * (2^levels - 1) pixels rather than the region.
  * Arguments (all checked before the device is touched, anything else RMD_ERR_INVALID_ARGUMENT): rmd_denoise_dual_guided's rules for the buffers,
  * their aliasing, the rects, the three count arrays, k, alpha, k_f and tau; levels <= RMD_ATROUS_MAX_LEVELS; err_dev may be NULL.  Synchronous,
  * and reports an earlier device fault, like rmd_denoise_dual.  Values a caller may start from: rmd_denoise_atrous's.
@@ -658,6 +659,34 @@ rmd_status rmd_denoise_atrous_dual(rmd_context *ctx,
     uint32_t width, uint32_t height,
     const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
     const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t levels, double k, double alpha, double k_f, double tau,
+    double *out_dev, double *err_dev);
+/*
+ * rmd_denoise_atrous_dual for SOME PIXELS of the frame (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes, found by its symbol).
+ * Everything rmd_denoise_atrous_dual defines stays word for word.  rects and the three count arrays describe the WHOLE frame as there — taps come from
+ * anywhere in it.  `region` is a HOST array of n_region rects under rmd_denoise_dual_region's rules: inside the frame, no two overlapping, of any size
+ * and alignment; it need not coincide with `rects`.  Added:
+ *     for every pixel inside a rect of `region`, out_dev and err_dev receive exactly the bytes rmd_denoise_atrous_dual would write there
+ *     every other double of out_dev and err_dev is not written at all: whatever it held before the call it holds after
+ * (every sum order above is fixed per pixel, so a pixel's value does not depend on which other pixels are computed).  Calls over disjoint regions
+ * into the same buffers compose to rmd_denoise_atrous_dual's frame, in any order.  What is computed: the last level on the region; level l on the set
+ * level l + 1 is computed on, dilated by 2 * 2^(l+1) pixels each way (a tap of level l + 1 reaches two steps of 2^(l+1)) and clipped to the frame; u, v, f
+ * and g on level 0's set dilated by 2 — the region dilated by 2 * (2^levels - 1) in all.  No kernel but the memset and the painting of the count images
+ * runs over the whole frame, so the cost follows that dilated area: 14 pixels each way at 3 levels, 62 at 5.  The call's scratch
+ * memory is kept on the context and grown when a call needs more, not allocated per call; it is released with the context.
+ * levels = 0 is the closed form on the region's pixels.  NULL features and err_dev = NULL behave as in rmd_denoise_atrous_dual.  n_region = 0 (region may
+ * then be NULL), or a region without pixels, writes nothing and returns RMD_OK; the call still waits and still reports an earlier device fault.
+ * Arguments (all checked before the device is touched, anything else RMD_ERR_INVALID_ARGUMENT): rmd_denoise_atrous_dual's rules; region non-NULL when
+ * n_region > 0; every region rect inside the frame; no two region rects overlapping.  Synchronous, like rmd_denoise_atrous_dual.
+ */
+rmd_status rmd_denoise_atrous_dual_region(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    const rmd_tile_rect *region, uint32_t n_region,
     uint32_t levels, double k, double alpha, double k_f, double tau,
     double *out_dev, double *err_dev);
 /*

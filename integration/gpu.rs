@@ -112,6 +112,12 @@ extern "C" {
                                feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, rect_counts_a: *const u32,
                                rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32, levels: u32, k: f64, alpha: f64, k_f: f64, tau: f64,
                                out_dev: *mut f64, err_dev: *mut f64) -> i32;
+    // ... for the pixels of `region` only, with the whole-frame call's bytes: the check with denoise_dual_atrous_region
+    fn rmd_denoise_atrous_dual_region(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64,
+                                      accum_sq_b_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32,
+                                      rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32,
+                                      region: *const rmd_tile_rect, n_region: u32, levels: u32, k: f64, alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64,
+                                      err_dev: *mut f64) -> i32;
     fn rmd_tile_error_dual(ctx: *mut rmd_context, err_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, n_rects: u32,
                            out_err_host: *mut f64) -> i32;
 }

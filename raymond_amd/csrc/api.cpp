@@ -1274,14 +1274,125 @@ static rmd_status denoise_atrous_dual_impl(rmd_context *ctx, const double *sa, c
 	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
 }
 
-rmd_status rmd_denoise_atrous_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
-                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t levels,
-                                   double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	const std::string name = "rmd_denoise_atrous_dual: ";
+// rmd_denoise_atrous_dual_region.  The needed sets: the last level's output is needed on the region; level l's on R_l = R_{l+1}
+// dilated by 2 * 2^(l+1) pixels each way — a level-(l+1) tap reaches two steps of 2^(l+1) — clipped to the frame; the prologue's planes on R_0 dilated by 2.
+// Dilating a union of rects is dilating each, and clipping after every step is clipping once, so R_l is the region's rects each grown by
+// 2 * (2^levels - 2^(l+1)) and the prologue's set by 2 * (2^levels - 1).
+static rmd_status denoise_atrous_dual_region_impl(const char *what, rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb,
+                                                  const double *feat, const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                                  const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects,
+                                                  const rmd_tile_rect *region, uint32_t n_region, uint32_t levels, double k, double alpha, double k_f, double tau,
+                                                  double *out_dev, double *err_dev) {
+	if (rmd_status s = bind(ctx)) return s;
+	constexpr uint32_t bw = 64, bh = 4; // the kernels' workgroup (denoise_atrous_dual.hip: kAtrousDualBlockW x kAtrousDualBlockH)
+	// The region as the host cuts it: rects of one top and height that abut left to right are joined (they are disjoint, so the pixels are the same) — a
+	// row of live 32 x 32 tiles then fills the 64-wide blocks of the last level instead of half of each.  Rects without pixels are dropped.
+	std::vector<rmd_tile_rect> joined;
+	{
+		std::vector<uint32_t> order;
+		for (uint32_t i = 0; i < n_region; i++)
+			if (region[i].width != 0 && region[i].height != 0) order.push_back(i);
+		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+			const rmd_tile_rect &p = region[a], &q = region[b];
+			return p.top != q.top ? p.top < q.top : p.height != q.height ? p.height < q.height : p.left < q.left;
+		});
+		for (uint32_t i : order) {
+			const rmd_tile_rect &r = region[i];
+			if (!joined.empty() && joined.back().top == r.top && joined.back().height == r.height && joined.back().left + joined.back().width == r.left) joined.back().width += r.width;
+			else joined.push_back(r);
+		}
+	}
+	region = joined.data(), n_region = (uint32_t)joined.size();
+	// the block tables, one after another: [0] the prologue's, [1 + l] level l's
+	std::vector<rmd::DualBlock> table;
+	std::vector<uint32_t> first(levels + 1u), count(levels + 1u);
+	const uint64_t tiles_x = ((uint64_t)width + bw - 1u) / bw, tiles_y = ((uint64_t)height + bh - 1u) / bh;
+	bool too_many = false;
+	// the frame-aligned blocks that intersect the region's rects grown by `grow` pixels each way, each once, in raster order
+	auto aligned_blocks = [&](uint64_t grow) {
+		std::vector<uint8_t> hit(tiles_x * tiles_y, 0);
+		for (uint32_t i = 0; i < n_region; i++) {
+			const rmd_tile_rect &r = region[i];
+			if (r.width == 0 || r.height == 0) continue;
+			const uint64_t x0 = r.left > grow ? r.left - grow : 0u, y0 = r.top > grow ? r.top - grow : 0u; // (inclusive)
+			const uint64_t x1 = std::min<uint64_t>(width, (uint64_t)r.left + r.width + grow), y1 = std::min<uint64_t>(height, (uint64_t)r.top + r.height + grow); // (exclusive)
+			for (uint64_t by = y0 / bh; by <= (y1 - 1u) / bh; by++) std::fill(hit.begin() + by * tiles_x + x0 / bw, hit.begin() + by * tiles_x + (x1 - 1u) / bw + 1u, (uint8_t)1);
+		}
+		for (uint64_t by = 0; by < tiles_y; by++)
+			for (uint64_t bx = 0; bx < tiles_x; bx++)
+				if (hit[by * tiles_x + bx]) table.push_back(rmd::DualBlock{(uint32_t)(bx * bw), (uint32_t)(by * bh), width, height});
+	};
+	// the region's rects cut into blocks from their own corners, each entry with its rect's far corner
+	auto region_blocks = [&] {
+		for (uint32_t i = 0; i < n_region; i++) {
+			const rmd_tile_rect &r = region[i];
+			const uint64_t n = (((uint64_t)r.width + bw - 1u) / bw) * (((uint64_t)r.height + bh - 1u) / bh);
+			if (table.size() + n > 0x7fffffffu) return void(too_many = true);
+			for (uint32_t y = 0; y < r.height; y += bh)
+				for (uint32_t x = 0; x < r.width; x += bw) table.push_back(rmd::DualBlock{r.left + x, r.top + y, r.left + r.width, r.top + r.height});
+		}
+	};
+	if (tiles_x * tiles_y > 0x7fffffffu) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(what) + ": frame of more than 2^31 - 1 workgroups");
+	for (uint32_t t = 0; t <= levels && !too_many; t++) {
+		first[t] = (uint32_t)table.size();
+		if (t == levels) region_blocks(); // the last level; at levels = 0 the prologue and the closed form
+		else aligned_blocks(t == 0 ? 2u * ((1ull << levels) - 1u) : 2u * ((1ull << levels) - (1ull << t))); // (table t > 0 is level t - 1's: R_{t-1})
+		count[t] = (uint32_t)(table.size() - first[t]);
+		if (table.size() > 0x7fffffffu) too_many = true;
+	}
+	if (too_many) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(what) + ": region of more than 2^31 - 1 workgroups");
+	if (count[levels] == 0u) { // nothing to write: the call still waits and reports an earlier fault
+		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		return rmd::check_fault(ctx);
+	}
+	// device scratch, kept on the context and grown when a call needs more: rmd_denoise_atrous_dual's layout, then the tables —
+	// [the state, two sets of twelve planes: 24 * W*H doubles][guided: the planar per-pixel f and g, 14 * W*H doubles][both halves' per-pixel counts and
+	// (guided) the features': 2 or 3 * W*H uint32, padded to 16 bytes][the block tables: 16 bytes each][rects: 16 bytes each][counts of A, of B and (guided)
+	// of the features: 4 bytes each]
+	const size_t N = (size_t)width * height;
+	const size_t state_bytes = N * 24u * sizeof(double), fplane_bytes = feat ? N * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
+	const size_t img_bytes = ((feat ? 3u : 2u) * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
+	const size_t table_bytes = table.size() * sizeof(rmd::DualBlock);
+	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
+	rmd::DeviceBuffer &scratch = ctx->atrous_region_scratch;
+	RMD_HIP(ctx, scratch.grow(state_bytes + fplane_bytes + img_bytes + table_bytes + rect_bytes + (feat ? 3u : 2u) * count_bytes));
+	unsigned char *d = scratch.as<unsigned char>();
+	double *d_state = scratch.as<double>();
+	double *d_fplanes = feat ? reinterpret_cast<double *>(d + state_bytes) : nullptr;
+	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + state_bytes + fplane_bytes);
+	uint32_t *d_fimg = feat ? d_img + 2u * N : nullptr;
+	rmd::DualBlock *d_table = reinterpret_cast<rmd::DualBlock *>(d + state_bytes + fplane_bytes + img_bytes);
+	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(reinterpret_cast<unsigned char *>(d_table) + table_bytes);
+	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_rects) + rect_bytes), *d_counts_b = d_counts_a + n_rects;
+	uint32_t *d_counts_f = feat ? d_counts_b + n_rects : nullptr;
+	if (n_rects != 0) {
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+		if (feat) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
+	}
+	RMD_HIP(ctx, hipMemcpyAsync(d_table, table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
+	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
+	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
+	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
+	RMD_HIP(ctx, rmd::launch_denoise_atrous_dual_region(ctx->stream, sa, qa, sb, qb, feat, feat_sq, d_rects, d_counts_a, d_counts_b, d_counts_f, n_rects, columns, width, height,
+	                                                    levels, k, alpha, k_f, tau, d_img, d_state, d_fimg, d_fplanes, d_table, first.data(), count.data(), out_dev, err_dev));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the host arrays are read by the copies until here)
+	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
+}
+
+// rmd_denoise_atrous_dual and rmd_denoise_atrous_dual_region: one argument check (`what`: the entry point's name, for the messages; `regional`: the region
+// form, whose region may still be NULL when n_region is 0)
+static rmd_status denoise_atrous_dual_checked(const char *what, bool regional, rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev,
+                                              const double *accum_b_dev, const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width,
+                                              uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
+                                              const uint32_t *rect_counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t levels, double k,
+                                              double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
+	const std::string name = std::string(what) + ": ";
 	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
 	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
 		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
+	if (regional && n_region && !region) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region is NULL with n_region > 0");
 	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
 	if (feat_dev && n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "rect_counts_f is NULL with n_rects > 0");
 	{ // rmd_denoise_dual_guided's aliasing rules: five ranges of W*H*3 doubles, err_dev's W*H, the two W*H*7-double feature ranges
@@ -1307,12 +1418,33 @@ rmd_status rmd_denoise_atrous_dual(rmd_context *ctx, const double *accum_a_dev, 
 		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
 		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
 	}
-	return rmd::guarded(ctx, "rmd_denoise_atrous_dual", [&] {
+	return rmd::guarded(ctx, what, [&] {
 		const char *why = nullptr;
 		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
-		return denoise_atrous_dual_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
-		                                rect_counts_b, rect_counts_f, n_rects, levels, k, alpha, k_f, tau, out_dev, err_dev);
+		if (!regional)
+			return denoise_atrous_dual_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
+			                                rect_counts_b, rect_counts_f, n_rects, levels, k, alpha, k_f, tau, out_dev, err_dev);
+		if (!denoise_rects_ok(region, n_region, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region: " + why);
+		return denoise_atrous_dual_region_impl(what, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
+		                                       rect_counts_b, rect_counts_f, n_rects, region, n_region, levels, k, alpha, k_f, tau, out_dev, err_dev);
 	});
+}
+
+rmd_status rmd_denoise_atrous_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t levels,
+                                   double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
+	return denoise_atrous_dual_checked("rmd_denoise_atrous_dual", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height,
+	                                   rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, nullptr, 0u, levels, k, alpha, k_f, tau, out_dev, err_dev);
+}
+
+rmd_status rmd_denoise_atrous_dual_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                          const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                          const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
+                                          uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t levels, double k, double alpha, double k_f,
+                                          double tau, double *out_dev, double *err_dev) {
+	return denoise_atrous_dual_checked("rmd_denoise_atrous_dual_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width,
+	                                   height, rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, region, n_region, levels, k, alpha, k_f, tau, out_dev, err_dev);
 }
 
 static rmd_status denoise_dual_select_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,

@@ -13,6 +13,13 @@
 //                                     twelve planes; LAST = true writes out_dev and err_dev (rmd_denoise_dual's combination of f_A and f_B), and
 //                                     the merged mean and NaN for a pixel that is not dual-valid.
 // atrous_dual_mean_kernel           — levels = 0: the same combination of u_A and u_B.
+// REGION (rmd_denoise_atrous_dual_region): atrous_dual_level_kernel<G, LAST, true> takes one more trailing argument, a block
+//                                     table (launch.hpp: DualBlock), and workgroup b owns the 64 x 4 pixels at entry b's origin that lie before its far
+//                                     corner; nothing else differs, so a pixel's value is the whole-frame call's.  The whole-frame instantiations
+//                                     keep their arguments and their instructions.  atrous_dual_mean_region_kernel is the closed form and
+//                                     atrous_dual_planes_region_kernel<G> the prologue (denoise_dual.hip's dual_planes_kernel and
+//                                     dual_feature_planes_kernel, operation for operation, in one pass) over a block table's pixels.  The host
+//                                     makes one table per kernel from the needed sets (launch_denoise_atrous_dual_region).
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -68,16 +75,116 @@ __global__ __launch_bounds__(256) void atrous_dual_mean_kernel(const double *__r
 	}
 }
 
+// The region call's count images: dual_count_image_kernel and dual_feature_count_image_kernel of denoise_dual.hip in one pass (n_a, n_b and n_f are
+// zeroed by the caller; counts_f and n_f are null without the guide)
+__global__ __launch_bounds__(256) void atrous_dual_count_image_kernel(const rmd_tile_rect *__restrict__ rects, const uint32_t *__restrict__ counts_a,
+                                                                      const uint32_t *__restrict__ counts_b, const uint32_t *__restrict__ counts_f, uint32_t W,
+                                                                      uint32_t *__restrict__ n_a, uint32_t *__restrict__ n_b, uint32_t *__restrict__ n_f) {
+	const rmd_tile_rect r = rects[blockIdx.x];
+	const uint32_t na = counts_a[blockIdx.x], nb = counts_b[blockIdx.x], nf = counts_f ? counts_f[blockIdx.x] : 0u;
+	const uint64_t n_px = (uint64_t)r.width * r.height;
+	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
+		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
+		const size_t p = (size_t)(r.left + x) + (size_t)(r.top + y) * W;
+		n_a[p] = na, n_b[p] = nb;
+		if (n_f) n_f[p] = nf;
+	}
+}
+
+// ... over a block table's pixels: workgroup b owns the 64 x 4 pixels at entry b's origin that lie before its far corner
+__global__ __launch_bounds__(256) void atrous_dual_mean_region_kernel(const double *__restrict__ planes, const double *__restrict__ SA, const double *__restrict__ SB,
+                                                                      const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b,
+                                                                      const DualBlock *__restrict__ table, uint32_t W, size_t N, double *__restrict__ out,
+                                                                      double *__restrict__ err) {
+	const DualBlock e = table[blockIdx.x];
+	const uint32_t x = e.x0 + threadIdx.x % kAtrousDualBlockW, y = e.y0 + threadIdx.x / kAtrousDualBlockW; // (no wrap: the origin lies before the far corner)
+	if (x >= e.x_end || y >= e.y_end) return;
+	const size_t i = (size_t)x + (size_t)y * W;
+	const double na = (double)n_a[i], nb = (double)n_b[i];
+	const double a0 = planes[i];
+	if (a0 == a0) {
+		const double a[3] = {a0, planes[N + i], planes[2 * N + i]}, b[3] = {planes[6 * N + i], planes[7 * N + i], planes[8 * N + i]};
+		atrous_dual_combine(a, b, na, nb, i, out, err);
+	} else {
+		atrous_dual_merged(SA, SB, na, nb, i, out, err);
+	}
+}
+
+// The prologue over a block table's pixels: dual_planes_kernel's twelve planes and, GUIDED, dual_feature_planes_kernel's fourteen (denoise_dual.hip),
+// the same operations in the same order per pixel — a pixel's feature validity reads only its own dual validity, so one thread makes both.
+template <bool GUIDED>
+__global__ __launch_bounds__(256) void atrous_dual_planes_region_kernel(const double *__restrict__ SA, const double *__restrict__ QA, const double *__restrict__ SB,
+                                                                        const double *__restrict__ QB, const double *__restrict__ F, const double *__restrict__ G,
+                                                                        const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b,
+                                                                        const uint32_t *__restrict__ n_f, const DualBlock *__restrict__ table, uint32_t W, size_t N,
+                                                                        double *__restrict__ planes, double *__restrict__ fplanes) {
+	const DualBlock e = table[blockIdx.x];
+	const uint32_t x = e.x0 + threadIdx.x % kAtrousDualBlockW, y = e.y0 + threadIdx.x / kAtrousDualBlockW;
+	if (x >= e.x_end || y >= e.y_end) return;
+	const size_t i = (size_t)x + (size_t)y * W;
+	double u[2][3], v[2][3];
+	bool dual = true;
+#pragma unroll
+	for (int h = 0; h < 2; h++) {
+		const double *S = h ? SB : SA, *Q = h ? QB : QA;
+		const uint32_t n = h ? n_b[i] : n_a[i];
+		const double nd = (double)n;
+		dual = dual && n >= 2u;
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			const double s = S[i * 3 + c], q = Q[i * 3 + c];
+			dual = dual && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
+			u[h][c] = s / nd;
+			double t = (q - s * u[h][c]) / (nd - 1.0);
+			if (t < 0.0) t = 0.0;
+			v[h][c] = t / nd;
+		}
+	}
+#pragma unroll
+	for (int h = 0; h < 2; h++) {
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			planes[(size_t)(6 * h + c) * N + i] = (c == 0 && !dual) ? __builtin_nan("") : u[h][c];
+			planes[(size_t)(6 * h + 3 + c) * N + i] = v[h][c];
+		}
+	}
+	if constexpr (GUIDED) {
+		const uint32_t n = n_f[i];
+		const double nd = (double)n;
+		bool valid = dual && n >= 2u;
+		double fv[kDenoiseFeat], gv[kDenoiseFeat];
+#pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) {
+			const double s = F[i * kDenoiseFeat + j], q = G[i * kDenoiseFeat + j];
+			valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
+			fv[j] = s / nd;
+			double t = (q - s * fv[j]) / (nd - 1.0);
+			if (t < 0.0) t = 0.0;
+			gv[j] = t / nd;
+		}
+#pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) fplanes[(size_t)j * N + i] = (j == 0 && !valid) ? __builtin_nan("") : fv[j], fplanes[(size_t)(kDenoiseFeat + j) * N + i] = gv[j];
+	}
+}
+
+__device__ inline const DualBlock *atrous_dual_table(const DualBlock *t) { return t; }
+
 // in / next: twelve planes of N = W*H doubles (above).  planes (GUIDED): dual_feature_planes_kernel's 14 planes.  tiles_x: workgroups per row of
-// tiles (the grid is one-dimensional: a frame may be taller than 65,535 tiles)
-template <bool GUIDED, bool LAST>
+// tiles (the grid is one-dimensional: a frame may be taller than 65,535 tiles).  REGION: one more argument, the block table; workgroup b owns the pixels
+// at entry b's origin before its far corner (inside the frame), tiles_x is not read
+template <bool GUIDED, bool LAST, bool REGION = false, class... T>
 __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_dual_level_kernel(
     const double *__restrict__ in, double *__restrict__ next, const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
     const uint32_t *__restrict__ n_b, uint32_t W, uint32_t H, uint32_t tiles_x, int64_t step, double k2, double alpha, const double *__restrict__ planes, double kf2,
-    double tau, double *__restrict__ out, double *__restrict__ err) {
-	const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
-	const int64_t x = (int64_t)bx * kAtrousDualBlockW + (threadIdx.x % kAtrousDualBlockW), y = (int64_t)by * kAtrousDualBlockH + (threadIdx.x / kAtrousDualBlockW);
-	if (x >= (int64_t)W || y >= (int64_t)H) return;
+    double tau, double *__restrict__ out, double *__restrict__ err, T... table) {
+	static_assert(sizeof...(T) == (REGION ? 1 : 0), "the block table, with REGION only");
+	[[maybe_unused]] DualBlock e{};
+	if constexpr (REGION) e = atrous_dual_table(table...)[blockIdx.x];
+	// (REGION is a constant: each conditional below is one of its arms, and the whole-frame instantiations are compiled from the lines they always had)
+	const uint32_t bx = REGION ? 0u : blockIdx.x % tiles_x, by = REGION ? 0u : blockIdx.x / tiles_x;
+	const int64_t x = REGION ? (int64_t)e.x0 + (threadIdx.x % kAtrousDualBlockW) : (int64_t)bx * kAtrousDualBlockW + (threadIdx.x % kAtrousDualBlockW),
+	              y = REGION ? (int64_t)e.y0 + (threadIdx.x / kAtrousDualBlockW) : (int64_t)by * kAtrousDualBlockH + (threadIdx.x / kAtrousDualBlockW);
+	if (x >= (REGION ? (int64_t)e.x_end : (int64_t)W) || y >= (REGION ? (int64_t)e.y_end : (int64_t)H)) return;
 	const size_t N = (size_t)W * H, pix = (size_t)x + (size_t)y * W;
 	const double ap0 = in[pix];
 	if (!(ap0 == ap0)) { // not dual-valid: never a tap, so only its mark is kept
@@ -194,6 +301,63 @@ hipError_t launch_denoise_atrous_dual(hipStream_t stream, const double *accum_a,
 			else hipLaunchKernelGGL((atrous_dual_level_kernel<false, false>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
 		}
 		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
+	return hipSuccess;
+}
+
+// One level of the region call over `n_blocks` entries of `table`
+template <bool GUIDED, bool LAST>
+static hipError_t launch_atrous_dual_region_level(hipStream_t stream, const DualBlock *table, uint32_t n_blocks, const double *in, double *next, const double *SA,
+                                                  const double *SB, const uint32_t *n_a, const uint32_t *n_b, uint32_t W, uint32_t H, int64_t step, double k2, double alpha,
+                                                  const double *fplanes, double kf2, double tau, double *out, double *err) {
+	hipLaunchKernelGGL((atrous_dual_level_kernel<GUIDED, LAST, true, const DualBlock *>), dim3(n_blocks), dim3(kAtrousDualBlockW * kAtrousDualBlockH), 0, stream, in, next, SA,
+	                   SB, n_a, n_b, W, H, 0u, step, k2, alpha, fplanes, kf2, tau, out, err, table);
+	return hipGetLastError();
+}
+
+hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                                             const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                                             const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
+                                             double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes,
+                                             const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count, double *out, double *err) {
+	if (levels > kAtrousMaxLevels || table == nullptr || table_first == nullptr || table_count == nullptr) return hipErrorInvalidValue;
+	const bool guided = feat != nullptr && levels != 0u;
+	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	for (uint32_t i = 0; i <= levels; i++)
+		if (table_count[i] == 0u || table_count[i] > 0x7FFFFFFFu) return hipErrorInvalidConfiguration; // (a region with pixels needs every table; the caller returns before an empty one)
+	const size_t N = (size_t)W * H;
+	uint32_t *n_a = n_img, *n_b = n_img + N;
+	// the count images: the whole frame's, as dual_preamble makes them (a memset and the painting of the rects)
+	hipError_t e = hipMemsetAsync(n_img, 0, 2u * N * sizeof(uint32_t), stream);
+	if (e != hipSuccess) return e;
+	if (guided && (e = hipMemsetAsync(n_f_img, 0, N * sizeof(uint32_t), stream)) != hipSuccess) return e;
+	if (n_rects) {
+		hipLaunchKernelGGL(atrous_dual_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_a, counts_b, guided ? counts_f : nullptr, W, n_a,
+		                   n_b, guided ? n_f_img : nullptr);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
+	const dim3 block(kAtrousDualBlockW * kAtrousDualBlockH);
+	if (guided) hipLaunchKernelGGL(atrous_dual_planes_region_kernel<true>, dim3(table_count[0]), block, 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, feat, feat_sq, n_a, n_b, n_f_img, table + table_first[0], W, N, state, feat_planes);
+	else hipLaunchKernelGGL(atrous_dual_planes_region_kernel<false>, dim3(table_count[0]), block, 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, nullptr, nullptr, n_a, n_b, nullptr, table + table_first[0], W, N, state, nullptr);
+	if ((e = hipGetLastError()) != hipSuccess) return e;
+	if (levels == 0u) { // (table 0 is the region's own then)
+		hipLaunchKernelGGL(atrous_dual_mean_region_kernel, dim3(table_count[0]), block, 0, stream, state, accum_a, accum_b, n_a, n_b, table + table_first[0], W, N, out, err);
+		return hipGetLastError();
+	}
+	const double k2 = k * k, kf2 = k_f * k_f;
+	double *set[2] = {state, state + 12u * N};
+	for (uint32_t l = 0; l < levels; l++) {
+		const double *in = set[l & 1u];
+		double *next = set[(l + 1u) & 1u];
+		const int64_t step = (int64_t)1 << l;
+		const bool last = l + 1u == levels;
+		const DualBlock *t = table + table_first[l + 1u];
+		const uint32_t nb = table_count[l + 1u];
+		if (guided) e = last ? launch_atrous_dual_region_level<true, true>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err)
+			                 : launch_atrous_dual_region_level<true, false>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err);
+		else e = last ? launch_atrous_dual_region_level<false, true>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err)
+			          : launch_atrous_dual_region_level<false, false>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err);
+		if (e != hipSuccess) return e;
 	}
 	return hipSuccess;
 }

@@ -166,6 +166,16 @@ hipError_t launch_denoise_atrous_dual(hipStream_t stream, const double *accum_a,
                                       const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
                                       double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes, double *out,
                                       double *err);
+// rmd_denoise_atrous_dual_region (denoise_atrous_dual.hip): launch_denoise_atrous_dual for the pixels of a region, through levels + 1 block tables of
+// 64 x 4-pixel workgroups (entries table_first[i] .. + table_count[i] of `table`, device memory; the two index arrays are host memory): table 0 the
+// prologue's — the pixels whose planes are made —, table 1 + l level l's; the last level's (table 0 at levels = 0) is cut from the region's rects and
+// carries their far corners, so only the region's pixels of out and err are written.  Every table has at least one entry.  n_img, state, n_f_img and
+// feat_planes as launch_denoise_atrous_dual's; what they hold outside the tables' pixels is not defined
+hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
+                                             const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
+                                             const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
+                                             double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes,
+                                             const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count, double *out, double *err);
 // rmd_denoise_dual_select (denoise_dual.hip): launch_denoise_dual's preamble once, then per candidate (a HOST array, checked by the caller) its two cross
 // passes with their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per
 // candidate (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read

@@ -21,6 +21,8 @@
 //                                                                    [--denoise-dual-atrous 1]     (needs --denoise-dual 1, not with --denoise-dual-select: the fast filter
 //                                                                      on the two halves, rmd_denoise_atrous_dual, at --denoise-atrous-levels / --denoise-atrous-k,
 //                                                                      guided with --denoise-dual-features 1; the adaptive check calls it on the whole frame)
+//                                                                    [--denoise-dual-atrous-region 1] (needs --denoise-dual-atrous 1: the adaptive check calls
+//                                                                      rmd_denoise_atrous_dual_region over the live tiles instead; the same output)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -214,6 +216,7 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-dual-features")) st.denoise_dual_features = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-dual-select")) st.denoise_dual_select = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-dual-atrous")) st.denoise_dual_atrous = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--denoise-dual-atrous-region")) st.denoise_dual_atrous_region = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--adaptive-denoised")) st.adaptive_denoised_threshold = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--adaptive-min")) st.adaptive_min_samples = (size_t)std::strtoull(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;

@@ -402,7 +402,8 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 // rmd_tile_error_dual over the live tiles, and the tiles at or below the threshold are finished.  Progress snapshots go out as they are made, the finished tiles at the end.
 // With denoise_dual_features the adaptive check needs the features: two feature buffers, into which every pass also adds the live tiles' first-hit
 // features of its samples [done, done + n) — a tile's features then hold count_a + count_b samples —, and the check is rmd_denoise_dual_guided_region.
-// With denoise_dual_atrous the check is rmd_denoise_atrous_dual on the whole frame, at the same rects, counts and feature buffers.
+// With denoise_dual_atrous the check is rmd_denoise_atrous_dual on the whole frame, at the same rects, counts and feature buffers; with
+// denoise_dual_atrous_region it is rmd_denoise_atrous_dual_region over the live tiles, which gives the pixels read here the same bytes.
 void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene scene, Settings st) {
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
@@ -491,7 +492,15 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 				rects.insert(rects.end(), live.begin(), live.end());
 				ca.insert(ca.end(), live.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), live.size(), (uint32_t)n_half[1]);
 				// only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
-				if (st.denoise_dual_atrous) { // the whole frame: rmd_denoise_atrous_dual has no region form (cf not read without the features)
+				if (st.denoise_dual_atrous && st.denoise_dual_atrous_region) { // the live tiles' pixels, with the whole-frame call's bytes (cf not read without the features)
+					std::vector<uint32_t> cf(ca);
+					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
+					check(rmd_denoise_atrous_dual_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
+					                                     rects.data(), ca.data(), cb.data(), cf.data(), (uint32_t)rects.size(), live.data(), (uint32_t)live.size(),
+					                                     st.denoise_atrous_levels, st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fbs[4],
+					                                     fbs[5]),
+					      ctx, "rmd_denoise_atrous_dual_region");
+				} else if (st.denoise_dual_atrous) { // the whole frame; the region form is behind denoise_dual_atrous_region (cf not read without the features)
 					std::vector<uint32_t> cf(ca);
 					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
 					check(rmd_denoise_atrous_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
@@ -597,6 +606,9 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_atrous needs denoise_dual (it selects rmd_denoise_atrous_dual)");
 	if (settings.denoise_dual_atrous && settings.denoise_dual_select)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_atrous cannot be combined with denoise_dual_select: the selection has no a-trous candidate");
+	if (settings.denoise_dual_atrous_region && !settings.denoise_dual_atrous)
+		throw Error(RMD_ERR_INVALID_ARGUMENT,
+		            "render_tiled: denoise_dual_atrous_region needs denoise_dual_atrous (it selects rmd_denoise_atrous_dual_region for the adaptive check)");
 	if (!(settings.adaptive_denoised_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold must be >= 0 (0 = off)");
 	if (settings.adaptive_denoised_threshold > 0.0 && !settings.denoise_dual)
 		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)");

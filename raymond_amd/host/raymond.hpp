@@ -159,8 +159,11 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	bool denoise_dual_select = false;
 	// The fast filter in the dual-buffer loop (needs denoise_dual, not with denoise_dual_select; false = off): await() returns rmd_denoise_atrous_dual's
 	// frame at denoise_atrous_levels, denoise_atrous_k and denoise_alpha, guided when denoise_dual_features is on, and the adaptive check is that call on
-	// the whole frame (it has no region form).
+	// the whole frame.
 	bool denoise_dual_atrous = false;
+	// The region form in that check (needs denoise_dual_atrous; false = off): the check calls rmd_denoise_atrous_dual_region over the live tiles, which gives
+	// their pixels the whole-frame call's bytes at a cost that follows their dilated area.  No message and no output changes; await() is untouched.
+	bool denoise_dual_atrous_region = false;
 	// Adaptive sampling by the filtered frame's error (needs denoise_dual, excludes adaptive_threshold > 0; 0 = off): after every even number of
 	// passes that leaves live tiles with at least adaptive_min_samples samples, rmd_denoise_dual runs over the whole frame and a live tile whose
 	// rmd_tile_error_dual — an absolute RMS in linear radiance that reads low — is at most the threshold is finished at the samples it has.

@@ -367,11 +367,13 @@ def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts
 
 
 def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, levels=5, k=3.0, alpha=1.0, features=None,
-                        features_sq=None, counts_f=None, k_f=1.0, tau=1e-2):
+                        features_sq=None, counts_f=None, k_f=1.0, tau=1e-2, region=None):
     """rmd_denoise_atrous_dual: `out_framebuffer` = the two sample halves `half_a` and `half_b` (as denoise_dual's) after `levels` levels of the
     edge-avoiding a-trous filter, each half under the other's weights, combined as denoise_dual combines them; `error_image` (an ErrorImage,
     optional) receives the per-pixel error estimate.  `features` / `features_sq` (FeatureBuffers; rect i holds counts_f[i] feature samples per
-    pixel) add the feature weight; without them counts_f, k_f and tau are not read."""
+    pixel) add the feature weight; without them counts_f, k_f and tau are not read.  `region` (a list of rects, possibly empty):
+    rmd_denoise_atrous_dual_region — only the pixels of those rects are written, with the bytes the whole-frame call gives them; None is the whole-frame
+    call."""
     counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
     counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
     if len(counts_a) != len(rects) or len(counts_b) != len(rects):
@@ -383,18 +385,23 @@ def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_fram
             raise ValueError("one feature sample count per rect")
         p_f = counts_f.ctypes.data_as(C.POINTER(C.c_uint32))
     fb = half_a[0]
-    ctx.check(ctx.L.rmd_denoise_atrous_dual(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, None if features is None else features.ptr,
-                                            None if features_sq is None else features_sq.ptr, fb.width, fb.height, tile_array(rects),
-                                            counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), p_f, len(rects),
-                                            int(levels), float(k), float(alpha), float(k_f), float(tau), out_framebuffer.ptr,
-                                            None if error_image is None else error_image.ptr))
+    head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, None if features is None else features.ptr,
+            None if features_sq is None else features_sq.ptr, fb.width, fb.height, tile_array(rects), counts_a.ctypes.data_as(C.POINTER(C.c_uint32)),
+            counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), p_f, len(rects))
+    tail = (int(levels), float(k), float(alpha), float(k_f), float(tau), out_framebuffer.ptr, None if error_image is None else error_image.ptr)
+    if region is None:
+        ctx.check(ctx.L.rmd_denoise_atrous_dual(*head, *tail))
+    else:
+        region = list(region)
+        ctx.check(ctx.L.rmd_denoise_atrous_dual_region(*head, tile_array(region), len(region), *tail))
 
 
 def denoise_atrous_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, out_init=None, err_init=None, features=None,
-                               features_sq=None, want_err=True, **params):
+                               features_sq=None, want_err=True, region=None, **params):
     """denoise_atrous_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate
     out (None for the latter with want_err=False: the call is then made without an error image).  `out_init` / `err_init`: what the two outputs hold
-    before the call.  `features` / `features_sq`: (H, W, 7) feature sums and sums of squares (with counts_f, k_f, tau among the params)."""
+    before the call — what a pixel outside `region` still holds after it.  `features` / `features_sq`: (H, W, 7) feature sums and sums of squares (with
+    counts_f, k_f, tau among the params)."""
     H, W = sums_a.shape[0], sums_a.shape[1]
     opened = []
     try:
@@ -412,7 +419,7 @@ def denoise_atrous_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects,
                 opened[-1].upload(arr)
                 fbufs[i] = opened[-1]
         denoise_atrous_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5] if want_err else None,
-                            features=fbufs[0], features_sq=fbufs[1], **params)
+                            features=fbufs[0], features_sq=fbufs[1], region=region, **params)
         return opened[4].download(), opened[5].download() if want_err else None
     finally:
         for b in opened:
@@ -785,8 +792,9 @@ def _render_tiled_dual(scene, settings, devices):
     samples; the check is rmd_denoise_dual_guided_region with those counts.  (Without an adaptive threshold nothing in this loop would read them and
     none are rendered.)  await_() renders the finished tiles' features itself (finished_tile_features) and returns rmd_denoise_dual_guided's frame.
 
-    With settings.denoise_dual_atrous the check is rmd_denoise_atrous_dual on the WHOLE frame instead (it has no region form), at the same rects and
-    counts, guided by the same feature buffers; rmd_tile_error_dual then runs over the live tiles as before."""
+    With settings.denoise_dual_atrous the check is rmd_denoise_atrous_dual on the WHOLE frame instead, at the same rects and counts, guided by the same
+    feature buffers; rmd_tile_error_dual then runs over the live tiles as before.  With settings.denoise_dual_atrous_region the check passes
+    region=live — rmd_denoise_atrous_dual_region, the same bytes at the live tiles' pixels —; nothing else changes."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     st = settings
@@ -848,8 +856,9 @@ def _render_tiled_dual(scene, settings, devices):
                         guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
                                      tau=st.denoise_feature_tau)
                     if st.denoise_dual_atrous:
+                        where = dict(region=live) if st.denoise_dual_atrous_region else {}  # (off: exactly the call made before the region form existed)
                         denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img,
-                                            levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide)
+                                            levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **where)
                     else:
                         denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide)
                     errors = tile_error_dual(ctx, err_img, live)

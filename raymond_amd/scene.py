@@ -247,7 +247,7 @@ class Settings:
                  adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
                  adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False, denoise_atrous=False,
-                 denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False):
+                 denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -304,8 +304,11 @@ class Settings:
         self.denoise_atrous_k = float(denoise_atrous_k)
         # The fast filter in the dual-buffer loop (False = off; needs denoise_dual, excludes denoise_dual_select): await_() returns
         # rmd_denoise_atrous_dual's frame at denoise_atrous_levels, denoise_atrous_k and denoise_alpha — guided when denoise_dual_features is on, with
-        # denoise_feature_k and denoise_feature_tau — and the adaptive check is that call on the whole frame (it has no region form).
+        # denoise_feature_k and denoise_feature_tau — and the adaptive check is that call on the whole frame.
         self.denoise_dual_atrous = bool(denoise_dual_atrous)
+        # The region form in that check (False = off; needs denoise_dual_atrous): the check calls rmd_denoise_atrous_dual_region over the live tiles, which
+        # gives their pixels the whole-frame call's bytes at a cost that follows their dilated area.  No message and no output changes; await_() is untouched.
+        self.denoise_dual_atrous_region = bool(denoise_dual_atrous_region)
         self.check_denoise()
 
     def select_candidates(self):
@@ -362,6 +365,8 @@ class Settings:
             raise ValueError("denoise_dual_atrous needs denoise_dual (it selects rmd_denoise_atrous_dual)")
         if self.denoise_dual_atrous and self.denoise_dual_select:
             raise ValueError("denoise_dual_atrous cannot be combined with denoise_dual_select: the selection has no a-trous candidate")
+        if self.denoise_dual_atrous_region and not self.denoise_dual_atrous:
+            raise ValueError("denoise_dual_atrous_region needs denoise_dual_atrous (it selects rmd_denoise_atrous_dual_region for the adaptive check)")
         if not self.adaptive_denoised_threshold >= 0.0:
             raise ValueError("adaptive_denoised_threshold must be >= 0 (0 = off)")
         if self.adaptive_denoised_threshold > 0.0 and not self.denoise_dual:

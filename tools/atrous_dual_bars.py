@@ -9,6 +9,11 @@ defaults (5 levels, k 3.0, alpha 1, unguided).  Over three seeds, per scene:
   (b) Spearman's rank correlation over the 32 x 32 tiles between tile_error_dual of err and the tile's true RMS error
 and the bars the device test asserts: (a) the largest ratio plus twice the spread, (b) the smallest correlation minus twice the spread, the
 spread being largest minus smallest over the three seeds.
+
+    --levels 3 5      also, per seed, the dual frame's RMSE and the rank correlation at each of these level counts (one run of the restatement to the
+                      largest of them), under "by_levels" — the comparison DESIGN.md section 19 makes between 3 and 5 levels for the adaptive check.
+                      The bars stay those of 5 levels.
+    --ref-spp N, --seeds N   a smaller converged frame and fewer seeds than the bars' own 2,048 and 3
 """
 import argparse
 import json
@@ -77,15 +82,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_atrous_dual", "atrous_dual_bars.json"))
     ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--levels", type=int, nargs="*", default=[])
+    ap.add_argument("--ref-spp", type=int, default=REF_SPP)
+    ap.add_argument("--seeds", type=int, default=3)
     a = ap.parse_args()
     cam = scenes.camera(W, H)
     tiles = generate_tiles(W, H, (32, 32))
-    seeds = [scenes.SEED, scenes.SEED + 2, scenes.SEED + 3]  # (SEED + 1 is the converged frame's)
-    result = {"width": W, "height": H, "half_spp": HALF, "reference_spp": REF_SPP, "levels": 5, "k": 3.0, "alpha": 1.0, "seeds": seeds, "scenes": {}}
+    seeds = [scenes.SEED, scenes.SEED + 2, scenes.SEED + 3][: a.seeds]  # (SEED + 1 is the converged frame's)
+    result = {"width": W, "height": H, "half_spp": HALF, "reference_spp": a.ref_spp, "levels": 5, "k": 3.0, "alpha": 1.0, "seeds": seeds, "scenes": {}}
     for which, sc in (("spheres", scenes.reflective_spheres()), ("mesh", scenes.gold_dragon_standin(n=24))):
         osc = oracle_lib.OracleScene(sc, fast=True)
-        st_ref = Settings(cam, sample_count=REF_SPP, bounce_limit=5, seed=scenes.SEED + 1)
-        ref = osc.render_tiles(cam, st_ref, tiles, threads=a.threads) / float(REF_SPP)
+        st_ref = Settings(cam, sample_count=a.ref_spp, bounce_limit=5, seed=scenes.SEED + 1)
+        ref = osc.render_tiles(cam, st_ref, tiles, threads=a.threads) / float(a.ref_spp)
         rows = []
         for seed in seeds:
             S_a, Q_a = half_sums(osc, cam, seed, 0, a.threads)
@@ -97,6 +105,12 @@ def main():
                    "sqrt_mean_err_over_rmse": float(np.sqrt(err.mean())) / rmse(out, ref),
                    "spearman": spearman(denoise_dual_ref.tile_error_dual(err, tiles), tile_true_rms(out, ref, tiles))}
             row["ratio"] = row["rmse_dual"] / row["rmse_single"]
+            if a.levels:
+                halves, dual = adref.filtered_halves_all(S_a, Q_a, S_b, Q_b, n, n, a.levels)
+                row["by_levels"] = {}
+                for lv in sorted(set(a.levels)):
+                    o, e = denoise_dual_ref.combine(*halves[lv], S_a, S_b, n, n, dual)
+                    row["by_levels"][str(lv)] = {"rmse_dual": rmse(o, ref), "spearman": spearman(denoise_dual_ref.tile_error_dual(e, tiles), tile_true_rms(o, ref, tiles))}
             rows.append(row)
             print(which, json.dumps(row), flush=True)
         result["scenes"][which] = {"rows": rows, **bars([r["ratio"] for r in rows], [r["spearman"] for r in rows])}
