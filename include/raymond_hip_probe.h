@@ -102,6 +102,16 @@ rmd_status rmd_probe_launch_plan(uint32_t mode, uint32_t grid, size_t n, const u
 rmd_status rmd_probe_launch_sizes(uint32_t mode, uint32_t grid, uint64_t *out8);
 /* Host only: the LDS layout of an uploaded scene — objects in the table, grids, and words of the grids' occupancy masks. */
 rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total);
+/* Host only: the device scratch block a denoise entry point carves (raymond_amd/csrc/denoise_host.hpp: denoise_scratch_layout — the function the entry
+ * points themselves call).  form 0 = rmd_denoise[_guided], 1 = rmd_denoise_atrous, 2 = rmd_denoise_dual and its guided and region forms,
+ * 3 = rmd_denoise_atrous_dual, 4 = rmd_denoise_atrous_dual_region, 5 = rmd_denoise_dual_select, 6 = rmd_tile_error_dual; guided = 1: the call has
+ * features (form 5: a guided candidate); n_table: the entries of a region form's block tables (forms 2 and 4; ignored by the others).  Part p
+ * (RMD_PROBE_SCRATCH_PARTS of them, in ScratchPart's order) has out3[3 * p] = 1 when the form holds it, then its offset and its length in bytes;
+ * *total = the block's bytes. */
+#define RMD_PROBE_SCRATCH_FORMS 7u
+#define RMD_PROBE_SCRATCH_PARTS 14u
+rmd_status rmd_probe_denoise_scratch(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t n_cands, uint64_t n_table,
+                                     uint64_t *out3, uint64_t *total);
 rmd_status rmd_probe_pretest_pairs(rmd_context *ctx, size_t n, const double *sphere5, const double *pos9, const double *ray6, int32_t *pass,
                                    int32_t *hit, double *t);
 

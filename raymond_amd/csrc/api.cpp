@@ -1,5 +1,5 @@
 // C-ABI implementation (include/raymond_hip.h): contexts, scene upload, the render entry points,
-// framebuffer helpers and the resolve/tone-map epilogue.  Host code only; kernels are in kernels.hip.
+// framebuffer helpers and the resolve/tone-map epilogue (the denoise entry points: api_denoise.cpp).  Host code only; kernels are in kernels.hip.
 #define RMD_WITH_HIP 1
 #include <algorithm>
 #include <cmath>
@@ -12,14 +12,10 @@
 #include "internal.hpp"
 #include "launch.hpp"
 
+using rmd::bind;
+
 namespace {
 thread_local std::string tl_last_error;
-
-rmd_status bind(rmd_context *ctx) {
-	if (!ctx) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "null context");
-	RMD_HIP(ctx, hipSetDevice(ctx->device));
-	return RMD_OK;
-}
 
 rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, rmd_context **out) {
 	if (!out) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "rmd_context_create: null out pointer");
@@ -156,6 +152,12 @@ rmd_status fail_noexcept(rmd_context *ctx, rmd_status status, const char *what, 
 		}
 		return status;
 	}
+}
+
+rmd_status bind(rmd_context *ctx) {
+	if (!ctx) return fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "null context");
+	RMD_HIP(ctx, hipSetDevice(ctx->device));
+	return RMD_OK;
 }
 
 static_assert(RMD_MAX_BOUNCE_LIMIT_DEV == RMD_MAX_BOUNCE_LIMIT, "launch.hpp mirrors include/raymond_hip.h");
@@ -930,643 +932,6 @@ rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const doubl
 	});
 }
 
-static rmd_status denoise_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
-                               uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
-                               uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev) {
-	if (rmd_status s = bind(ctx)) return s;
-	// device scratch: [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each, padded to 16 bytes]
-	// [guided: the planar per-pixel f and g, 14 planes of W*H doubles]
-	const size_t img_bytes = ((size_t)width * height * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = ((size_t)n_rects * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t plane_bytes = feat_dev ? (size_t)width * height * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
-	rmd::DeviceBuffer scratch;
-	RMD_HIP(ctx, scratch.alloc(img_bytes + rect_bytes + count_bytes + plane_bytes));
-	unsigned char *d = scratch.as<unsigned char>();
-	uint32_t *d_img = scratch.as<uint32_t>();
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + img_bytes);
-	uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + img_bytes + rect_bytes);
-	double *d_planes = feat_dev ? reinterpret_cast<double *>(d + img_bytes + rect_bytes + count_bytes) : nullptr;
-	if (n_rects != 0) {
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, (size_t)n_rects * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-	}
-	uint64_t largest = 0; // pixels of the largest rect: the count image gives each rect a column of 256-thread workgroups that covers it, up to 1,024
-	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
-	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_guided(ctx->stream, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, d_rects, d_counts, n_rects, columns, width, height, radius,
-	                                        patch_radius, k, alpha, k_f, tau, d_img, d_planes, out_dev));
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
-}
-
-// Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
-// start before it ends.
-static bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height, const char **why) {
-	// (*why: the rule that was broken; the caller puts its own name in front)
-	std::vector<uint32_t> order;
-	for (uint32_t i = 0; i < n_rects; i++) {
-		const rmd_tile_rect &r = rects[i];
-		if ((uint64_t)r.left + r.width > width || (uint64_t)r.top + r.height > height) return *why = "tile rectangle outside the framebuffer", false;
-		if (r.width != 0 && r.height != 0) order.push_back(i);
-	}
-	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rects[a].left < rects[b].left; });
-	for (size_t i = 0; i < order.size(); i++) {
-		const rmd_tile_rect &a = rects[order[i]];
-		for (size_t j = i + 1; j < order.size() && rects[order[j]].left < (uint64_t)a.left + a.width; j++) {
-			const rmd_tile_rect &b = rects[order[j]];
-			if (b.top < (uint64_t)a.top + a.height && a.top < (uint64_t)b.top + b.height) return *why = "tile rectangles overlap", false;
-		}
-	}
-	return true;
-}
-
-// rmd_denoise and rmd_denoise_guided: one argument check, one launch path (`what`: the entry point's name, for the messages)
-static rmd_status denoise_checked(const char *what, rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev,
-                                  const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts,
-                                  uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev) {
-	const std::string name = std::string(what) + ": ";
-	if (!accum_dev || !accum_sq_dev || !out_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
-	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
-	{ // no two of the three W*H*3-double ranges overlap; nor do the two W*H*7-double feature ranges, each other or out_dev's
-		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
-		const unsigned __int128 s = (uintptr_t)accum_dev, q = (uintptr_t)accum_sq_dev, o = (uintptr_t)out_dev, f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
-		auto overlap = [&](unsigned __int128 a, unsigned __int128 na, unsigned __int128 b, unsigned __int128 nb) { return a < b + nb && b < a + na; };
-		if (overlap(s, bytes, q, bytes) || overlap(s, bytes, o, bytes) || overlap(q, bytes, o, bytes))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "accum_dev, accum_sq_dev and out_dev must not alias");
-		if (feat_dev && (overlap(f, fbytes, g, fbytes) || overlap(f, fbytes, o, bytes) || overlap(g, fbytes, o, bytes)))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev, feat_sq_dev and out_dev must not alias");
-	}
-	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
-	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
-	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
-	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
-	if (feat_dev) {
-		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
-		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
-	}
-	return rmd::guarded(ctx, what, [&] {
-		const char *why = nullptr;
-		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
-		return denoise_impl(ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k, alpha, k_f,
-		                    tau, out_dev);
-	});
-}
-
-rmd_status rmd_denoise(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                       const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha,
-                       double *out_dev) {
-	return denoise_checked("rmd_denoise", ctx, accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_sample_counts, n_rects, radius, patch_radius, k,
-	                       alpha, 0.0, 0.0, out_dev);
-}
-
-rmd_status rmd_denoise_guided(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
-                              uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
-                              uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev) {
-	return denoise_checked("rmd_denoise_guided", ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, radius,
-	                       patch_radius, k, alpha, k_f, tau, out_dev);
-}
-
-// ---------------------------------------------------------------- the a-trous filter (denoise_atrous.hip)
-static rmd_status denoise_atrous_impl(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
-                                      uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
-                                      uint32_t levels, double k, double alpha, double k_f, double tau, double *out_dev) {
-	if (rmd_status s = bind(ctx)) return s;
-	// device scratch: [c and v, two sets of six planes: 12 * W*H doubles][guided: the planar per-pixel f and g, 14 planes of W*H doubles]
-	// [per-pixel counts: W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts: 4 bytes each, padded to 16 bytes]
-	const size_t n_px = (size_t)width * height;
-	const size_t cv_bytes = n_px * 12u * sizeof(double), plane_bytes = feat_dev ? n_px * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
-	const size_t img_bytes = (n_px * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = ((size_t)n_rects * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	rmd::DeviceBuffer scratch;
-	RMD_HIP(ctx, scratch.alloc(cv_bytes + plane_bytes + img_bytes + rect_bytes + count_bytes));
-	unsigned char *d = scratch.as<unsigned char>();
-	double *d_cv = scratch.as<double>();
-	double *d_planes = feat_dev ? reinterpret_cast<double *>(d + cv_bytes) : nullptr;
-	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + cv_bytes + plane_bytes);
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + cv_bytes + plane_bytes + img_bytes);
-	uint32_t *d_counts = reinterpret_cast<uint32_t *>(d + cv_bytes + plane_bytes + img_bytes + rect_bytes);
-	if (n_rects != 0) {
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts, rect_sample_counts, (size_t)n_rects * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-	}
-	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
-	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
-	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_atrous(ctx->stream, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, d_rects, d_counts, n_rects, columns, width, height, levels, k,
-	                                        alpha, k_f, tau, d_img, d_cv, d_planes, out_dev));
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
-}
-
-rmd_status rmd_denoise_atrous(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
-                              uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
-                              uint32_t levels, double k, double alpha, double k_f, double tau, double *out_dev) {
-	const std::string name = "rmd_denoise_atrous: ";
-	if (!accum_dev || !accum_sq_dev || !out_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
-	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
-	{ // rmd_denoise_guided's aliasing rules
-		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
-		const unsigned __int128 s = (uintptr_t)accum_dev, q = (uintptr_t)accum_sq_dev, o = (uintptr_t)out_dev, f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
-		auto overlap = [&](unsigned __int128 a, unsigned __int128 na, unsigned __int128 b, unsigned __int128 nb) { return a < b + nb && b < a + na; };
-		if (overlap(s, bytes, q, bytes) || overlap(s, bytes, o, bytes) || overlap(q, bytes, o, bytes))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "accum_dev, accum_sq_dev and out_dev must not alias");
-		if (feat_dev && (overlap(f, fbytes, g, fbytes) || overlap(f, fbytes, o, bytes) || overlap(g, fbytes, o, bytes)))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev, feat_sq_dev and out_dev must not alias");
-	}
-	if (levels > rmd::kAtrousMaxLevels) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "levels must be <= 8");
-	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
-	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
-	if (feat_dev) {
-		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
-		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
-	}
-	return rmd::guarded(ctx, "rmd_denoise_atrous", [&] {
-		const char *why = nullptr;
-		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
-		return denoise_atrous_impl(ctx, accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects, levels, k, alpha, k_f, tau,
-		                           out_dev);
-	});
-}
-
-// ---------------------------------------------------------------- dual-buffer denoising (denoise_dual.hip)
-// region null: rmd_denoise_dual, every pixel.  region not null: rmd_denoise_dual_region, the pixels of its n_region rects only.  feat / feat_sq not
-// null: the guided forms (counts_f: the features' own counts)
-static rmd_status denoise_dual_impl(const char *what, rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
-                                    const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
-                                    const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region,
-                                    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	if (rmd_status s = bind(ctx)) return s;
-	// the block table: each region rect cut into tiles of the kernel's own shape from the rect's corner, row by row
-	std::vector<rmd::DualBlock> table;
-	if (region) {
-		const uint32_t tw = rmd::denoise_tile_width(radius, patch_radius), th = rmd::kDenoiseTile;
-		for (uint32_t i = 0; i < n_region; i++) {
-			const rmd_tile_rect &r = region[i];
-			for (uint32_t y = 0; y < r.height; y += th)
-				for (uint32_t x = 0; x < r.width; x += tw) table.push_back(rmd::DualBlock{r.left + x, r.top + y, r.left + r.width, r.top + r.height});
-		}
-		if (table.size() > 0x7fffffffu) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(what) + ": region of more than 2^31 - 1 workgroups");
-		if (table.empty()) { // nothing to write: the call still waits and reports an earlier fault
-			RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-			return rmd::check_fault(ctx);
-		}
-	}
-	// device scratch: [the twelve u / v planes: 12 * W*H doubles][f_B: 3 * W*H doubles][both halves' per-pixel counts: 2 * W*H uint32, padded to 16 bytes]
-	// [the block table: 16 bytes each][rects: 16 bytes each][counts of A, then of B: 4 bytes each]
-	// guided only, from the next 16-byte boundary: [the planar per-pixel f and g: 14 * W*H doubles][the features' per-pixel counts: W*H uint32, padded to
-	// 16 bytes][the features' counts: 4 bytes each]
-	const size_t N = (size_t)width * height;
-	const size_t plane_bytes = N * 12u * sizeof(double), fb_bytes = N * 3u * sizeof(double);
-	const size_t img_bytes = (2u * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t table_bytes = table.size() * sizeof(rmd::DualBlock);
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
-	const size_t plain_bytes = plane_bytes + fb_bytes + img_bytes + table_bytes + rect_bytes + 2u * count_bytes, base_bytes = (plain_bytes + 15u) & ~(size_t)15u;
-	const size_t fplane_bytes = N * 2u * RMD_FEATURE_CHANNELS * sizeof(double), fimg_bytes = (N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	rmd::DeviceBuffer scratch;
-	RMD_HIP(ctx, scratch.alloc(feat ? base_bytes + fplane_bytes + fimg_bytes + count_bytes : plain_bytes));
-	unsigned char *d = scratch.as<unsigned char>();
-	double *d_planes = scratch.as<double>();
-	double *d_fplanes = feat ? reinterpret_cast<double *>(d + base_bytes) : nullptr;
-	uint32_t *d_fimg = feat ? reinterpret_cast<uint32_t *>(d + base_bytes + fplane_bytes) : nullptr;
-	uint32_t *d_counts_f = feat ? reinterpret_cast<uint32_t *>(d + base_bytes + fplane_bytes + fimg_bytes) : nullptr;
-	double *d_fb = reinterpret_cast<double *>(d + plane_bytes);
-	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + plane_bytes + fb_bytes);
-	rmd::DualBlock *d_table = region ? reinterpret_cast<rmd::DualBlock *>(d + plane_bytes + fb_bytes + img_bytes) : nullptr;
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + plane_bytes + fb_bytes + img_bytes + table_bytes);
-	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(d + plane_bytes + fb_bytes + img_bytes + table_bytes + rect_bytes), *d_counts_b = d_counts_a + n_rects;
-	if (n_rects != 0) {
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		if (feat) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-	}
-	if (region) RMD_HIP(ctx, hipMemcpyAsync(d_table, table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
-	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
-	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
-	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, sa, qa, sb, qb, feat, feat_sq, d_rects, d_counts_a, d_counts_b, d_counts_f, n_rects, columns, width, height, radius,
-	                                      patch_radius, k, alpha, k_f, tau, d_img, d_planes, d_fb, d_fimg, d_fplanes, d_table, (uint32_t)table.size(), out_dev, err_dev));
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the table is read by the copy until here)
-	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
-}
-
-// rmd_denoise_dual, rmd_denoise_dual_region and their guided forms: one argument check, one launch path (`what`: the entry point's name, for the
-// messages; `regional`: a region form, whose region may still be NULL when n_region is 0; feat_dev / feat_sq_dev both NULL: no feature weight —
-// rect_counts_f, k_f and tau are then not read)
-static rmd_status denoise_dual_checked(const char *what, bool regional, rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev,
-                                       const double *accum_b_dev, const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width,
-                                       uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
-                                       const uint32_t *rect_counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius,
-                                       uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	const std::string name = std::string(what) + ": ";
-	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
-	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
-	if (regional && n_region && !region) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region is NULL with n_region > 0");
-	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
-	if (feat_dev && n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "rect_counts_f is NULL with n_rects > 0");
-	{ // no two of the six ranges overlap: five of W*H*3 doubles, err_dev's W*H
-		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		const unsigned __int128 at[6] = {(uintptr_t)accum_a_dev, (uintptr_t)accum_sq_a_dev, (uintptr_t)accum_b_dev, (uintptr_t)accum_sq_b_dev, (uintptr_t)out_dev, (uintptr_t)err_dev};
-		const unsigned __int128 len[6] = {bytes, bytes, bytes, bytes, bytes, bytes / 3u};
-		for (int i = 0; i < (err_dev ? 6 : 5); i++)
-			for (int j = i + 1; j < (err_dev ? 6 : 5); j++)
-				if (at[i] < at[j] + len[j] && at[j] < at[i] + len[i])
-					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, out_dev and err_dev must not alias");
-		if (feat_dev) { // nor do the two W*H*7-double feature ranges, each other or any of the six
-			const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
-			const unsigned __int128 f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
-			bool bad = f < g + fbytes && g < f + fbytes;
-			for (int i = 0; i < (err_dev ? 6 : 5); i++) bad = bad || (f < at[i] + len[i] && at[i] < f + fbytes) || (g < at[i] + len[i] && at[i] < g + fbytes);
-			if (bad) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must not alias each other, the sum buffers, out_dev or err_dev");
-		}
-	}
-	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
-	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
-	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
-	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
-	if (feat_dev) {
-		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
-		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
-	}
-	return rmd::guarded(ctx, what, [&] {
-		const char *why = nullptr;
-		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
-		if (regional && !denoise_rects_ok(region, n_region, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region: " + why);
-		const rmd_tile_rect none{0, 0, 0, 0}; // (an empty region may come as NULL: the launch path tells the two calls apart by the pointer)
-		return denoise_dual_impl(what, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
-		                         rect_counts_b, rect_counts_f, n_rects, regional ? (region ? region : &none) : nullptr, regional ? n_region : 0u, radius, patch_radius, k,
-		                         alpha, k_f, tau, out_dev, err_dev);
-	});
-}
-
-rmd_status rmd_denoise_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
-                            uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
-                            uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha, double *out_dev, double *err_dev) {
-	return denoise_dual_checked("rmd_denoise_dual", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, nullptr, nullptr, width, height, rects,
-	                            rect_counts_a, rect_counts_b, nullptr, n_rects, nullptr, 0u, radius, patch_radius, k, alpha, 0.0, 0.0, out_dev, err_dev);
-}
-
-rmd_status rmd_denoise_dual_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
-                                   uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
-                                   uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius, uint32_t patch_radius, double k, double alpha,
-                                   double *out_dev, double *err_dev) {
-	return denoise_dual_checked("rmd_denoise_dual_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, nullptr, nullptr, width, height, rects,
-	                            rect_counts_a, rect_counts_b, nullptr, n_rects, region, n_region, radius, patch_radius, k, alpha, 0.0, 0.0, out_dev, err_dev);
-}
-
-rmd_status rmd_denoise_dual_guided(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
-                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t radius,
-                                   uint32_t patch_radius, double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	return denoise_dual_checked("rmd_denoise_dual_guided", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects,
-	                            rect_counts_a, rect_counts_b, rect_counts_f, n_rects, nullptr, 0u, radius, patch_radius, k, alpha, k_f, tau, out_dev, err_dev);
-}
-
-rmd_status rmd_denoise_dual_guided_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
-                                          const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
-                                          const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
-                                          uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius, uint32_t patch_radius, double k,
-                                          double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	return denoise_dual_checked("rmd_denoise_dual_guided_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height,
-	                            rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, region, n_region, radius, patch_radius, k, alpha, k_f, tau, out_dev, err_dev);
-}
-
-// ---------------------------------------------------------------- the a-trous filter on two halves (denoise_atrous_dual.hip)
-static rmd_status denoise_atrous_dual_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
-                                           const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
-                                           const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, uint32_t levels, double k, double alpha, double k_f,
-                                           double tau, double *out_dev, double *err_dev) {
-	if (rmd_status s = bind(ctx)) return s;
-	// device scratch: [the state, two sets of twelve planes: 24 * W*H doubles][guided: the planar per-pixel f and g, 14 * W*H doubles]
-	// [both halves' per-pixel counts and (guided) the features': 2 or 3 * W*H uint32, padded to 16 bytes][rects: 16 bytes each]
-	// [counts of A, of B and (guided) of the features: 4 bytes each]
-	const size_t N = (size_t)width * height;
-	const size_t state_bytes = N * 24u * sizeof(double), fplane_bytes = feat ? N * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
-	const size_t img_bytes = ((feat ? 3u : 2u) * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
-	rmd::DeviceBuffer scratch;
-	RMD_HIP(ctx, scratch.alloc(state_bytes + fplane_bytes + img_bytes + rect_bytes + (feat ? 3u : 2u) * count_bytes));
-	unsigned char *d = scratch.as<unsigned char>();
-	double *d_state = scratch.as<double>();
-	double *d_fplanes = feat ? reinterpret_cast<double *>(d + state_bytes) : nullptr;
-	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + state_bytes + fplane_bytes);
-	uint32_t *d_fimg = feat ? d_img + 2u * N : nullptr;
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + state_bytes + fplane_bytes + img_bytes);
-	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_rects) + rect_bytes), *d_counts_b = d_counts_a + n_rects;
-	uint32_t *d_counts_f = feat ? d_counts_b + n_rects : nullptr;
-	if (n_rects != 0) {
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		if (feat) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-	}
-	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
-	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
-	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_atrous_dual(ctx->stream, sa, qa, sb, qb, feat, feat_sq, d_rects, d_counts_a, d_counts_b, d_counts_f, n_rects, columns, width, height,
-	                                             levels, k, alpha, k_f, tau, d_img, d_state, d_fimg, d_fplanes, out_dev, err_dev));
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
-}
-
-// rmd_denoise_atrous_dual_region.  The needed sets: the last level's output is needed on the region; level l's on R_l = R_{l+1}
-// dilated by 2 * 2^(l+1) pixels each way — a level-(l+1) tap reaches two steps of 2^(l+1) — clipped to the frame; the prologue's planes on R_0 dilated by 2.
-// Dilating a union of rects is dilating each, and clipping after every step is clipping once, so R_l is the region's rects each grown by
-// 2 * (2^levels - 2^(l+1)) and the prologue's set by 2 * (2^levels - 1).
-static rmd_status denoise_atrous_dual_region_impl(const char *what, rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb,
-                                                  const double *feat, const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                                                  const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects,
-                                                  const rmd_tile_rect *region, uint32_t n_region, uint32_t levels, double k, double alpha, double k_f, double tau,
-                                                  double *out_dev, double *err_dev) {
-	if (rmd_status s = bind(ctx)) return s;
-	constexpr uint32_t bw = 64, bh = 4; // the kernels' workgroup (denoise_atrous_dual.hip: kAtrousDualBlockW x kAtrousDualBlockH)
-	// The region as the host cuts it: rects of one top and height that abut left to right are joined (they are disjoint, so the pixels are the same) — a
-	// row of live 32 x 32 tiles then fills the 64-wide blocks of the last level instead of half of each.  Rects without pixels are dropped.
-	std::vector<rmd_tile_rect> joined;
-	{
-		std::vector<uint32_t> order;
-		for (uint32_t i = 0; i < n_region; i++)
-			if (region[i].width != 0 && region[i].height != 0) order.push_back(i);
-		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-			const rmd_tile_rect &p = region[a], &q = region[b];
-			return p.top != q.top ? p.top < q.top : p.height != q.height ? p.height < q.height : p.left < q.left;
-		});
-		for (uint32_t i : order) {
-			const rmd_tile_rect &r = region[i];
-			if (!joined.empty() && joined.back().top == r.top && joined.back().height == r.height && joined.back().left + joined.back().width == r.left) joined.back().width += r.width;
-			else joined.push_back(r);
-		}
-	}
-	region = joined.data(), n_region = (uint32_t)joined.size();
-	// the block tables, one after another: [0] the prologue's, [1 + l] level l's
-	std::vector<rmd::DualBlock> table;
-	std::vector<uint32_t> first(levels + 1u), count(levels + 1u);
-	const uint64_t tiles_x = ((uint64_t)width + bw - 1u) / bw, tiles_y = ((uint64_t)height + bh - 1u) / bh;
-	bool too_many = false;
-	// the frame-aligned blocks that intersect the region's rects grown by `grow` pixels each way, each once, in raster order
-	auto aligned_blocks = [&](uint64_t grow) {
-		std::vector<uint8_t> hit(tiles_x * tiles_y, 0);
-		for (uint32_t i = 0; i < n_region; i++) {
-			const rmd_tile_rect &r = region[i];
-			if (r.width == 0 || r.height == 0) continue;
-			const uint64_t x0 = r.left > grow ? r.left - grow : 0u, y0 = r.top > grow ? r.top - grow : 0u; // (inclusive)
-			const uint64_t x1 = std::min<uint64_t>(width, (uint64_t)r.left + r.width + grow), y1 = std::min<uint64_t>(height, (uint64_t)r.top + r.height + grow); // (exclusive)
-			for (uint64_t by = y0 / bh; by <= (y1 - 1u) / bh; by++) std::fill(hit.begin() + by * tiles_x + x0 / bw, hit.begin() + by * tiles_x + (x1 - 1u) / bw + 1u, (uint8_t)1);
-		}
-		for (uint64_t by = 0; by < tiles_y; by++)
-			for (uint64_t bx = 0; bx < tiles_x; bx++)
-				if (hit[by * tiles_x + bx]) table.push_back(rmd::DualBlock{(uint32_t)(bx * bw), (uint32_t)(by * bh), width, height});
-	};
-	// the region's rects cut into blocks from their own corners, each entry with its rect's far corner
-	auto region_blocks = [&] {
-		for (uint32_t i = 0; i < n_region; i++) {
-			const rmd_tile_rect &r = region[i];
-			const uint64_t n = (((uint64_t)r.width + bw - 1u) / bw) * (((uint64_t)r.height + bh - 1u) / bh);
-			if (table.size() + n > 0x7fffffffu) return void(too_many = true);
-			for (uint32_t y = 0; y < r.height; y += bh)
-				for (uint32_t x = 0; x < r.width; x += bw) table.push_back(rmd::DualBlock{r.left + x, r.top + y, r.left + r.width, r.top + r.height});
-		}
-	};
-	if (tiles_x * tiles_y > 0x7fffffffu) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(what) + ": frame of more than 2^31 - 1 workgroups");
-	for (uint32_t t = 0; t <= levels && !too_many; t++) {
-		first[t] = (uint32_t)table.size();
-		if (t == levels) region_blocks(); // the last level; at levels = 0 the prologue and the closed form
-		else aligned_blocks(t == 0 ? 2u * ((1ull << levels) - 1u) : 2u * ((1ull << levels) - (1ull << t))); // (table t > 0 is level t - 1's: R_{t-1})
-		count[t] = (uint32_t)(table.size() - first[t]);
-		if (table.size() > 0x7fffffffu) too_many = true;
-	}
-	if (too_many) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(what) + ": region of more than 2^31 - 1 workgroups");
-	if (count[levels] == 0u) { // nothing to write: the call still waits and reports an earlier fault
-		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-		return rmd::check_fault(ctx);
-	}
-	// device scratch, kept on the context and grown when a call needs more: rmd_denoise_atrous_dual's layout, then the tables —
-	// [the state, two sets of twelve planes: 24 * W*H doubles][guided: the planar per-pixel f and g, 14 * W*H doubles][both halves' per-pixel counts and
-	// (guided) the features': 2 or 3 * W*H uint32, padded to 16 bytes][the block tables: 16 bytes each][rects: 16 bytes each][counts of A, of B and (guided)
-	// of the features: 4 bytes each]
-	const size_t N = (size_t)width * height;
-	const size_t state_bytes = N * 24u * sizeof(double), fplane_bytes = feat ? N * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
-	const size_t img_bytes = ((feat ? 3u : 2u) * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t table_bytes = table.size() * sizeof(rmd::DualBlock);
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
-	rmd::DeviceBuffer &scratch = ctx->atrous_region_scratch;
-	RMD_HIP(ctx, scratch.grow(state_bytes + fplane_bytes + img_bytes + table_bytes + rect_bytes + (feat ? 3u : 2u) * count_bytes));
-	unsigned char *d = scratch.as<unsigned char>();
-	double *d_state = scratch.as<double>();
-	double *d_fplanes = feat ? reinterpret_cast<double *>(d + state_bytes) : nullptr;
-	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + state_bytes + fplane_bytes);
-	uint32_t *d_fimg = feat ? d_img + 2u * N : nullptr;
-	rmd::DualBlock *d_table = reinterpret_cast<rmd::DualBlock *>(d + state_bytes + fplane_bytes + img_bytes);
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(reinterpret_cast<unsigned char *>(d_table) + table_bytes);
-	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_rects) + rect_bytes), *d_counts_b = d_counts_a + n_rects;
-	uint32_t *d_counts_f = feat ? d_counts_b + n_rects : nullptr;
-	if (n_rects != 0) {
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		if (feat) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-	}
-	RMD_HIP(ctx, hipMemcpyAsync(d_table, table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream));
-	uint64_t largest = 0; // as denoise_impl: a column of 256-thread workgroups per rect that covers the largest, up to 1,024
-	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
-	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_atrous_dual_region(ctx->stream, sa, qa, sb, qb, feat, feat_sq, d_rects, d_counts_a, d_counts_b, d_counts_f, n_rects, columns, width, height,
-	                                                    levels, k, alpha, k_f, tau, d_img, d_state, d_fimg, d_fplanes, d_table, first.data(), count.data(), out_dev, err_dev));
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the host arrays are read by the copies until here)
-	return rmd::check_fault(ctx); // the sums came from launches this call has waited for
-}
-
-// rmd_denoise_atrous_dual and rmd_denoise_atrous_dual_region: one argument check (`what`: the entry point's name, for the messages; `regional`: the region
-// form, whose region may still be NULL when n_region is 0)
-static rmd_status denoise_atrous_dual_checked(const char *what, bool regional, rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev,
-                                              const double *accum_b_dev, const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width,
-                                              uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
-                                              const uint32_t *rect_counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t levels, double k,
-                                              double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	const std::string name = std::string(what) + ": ";
-	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
-	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
-	if (regional && n_region && !region) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region is NULL with n_region > 0");
-	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
-	if (feat_dev && n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "rect_counts_f is NULL with n_rects > 0");
-	{ // rmd_denoise_dual_guided's aliasing rules: five ranges of W*H*3 doubles, err_dev's W*H, the two W*H*7-double feature ranges
-		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		const unsigned __int128 at[6] = {(uintptr_t)accum_a_dev, (uintptr_t)accum_sq_a_dev, (uintptr_t)accum_b_dev, (uintptr_t)accum_sq_b_dev, (uintptr_t)out_dev, (uintptr_t)err_dev};
-		const unsigned __int128 len[6] = {bytes, bytes, bytes, bytes, bytes, bytes / 3u};
-		for (int i = 0; i < (err_dev ? 6 : 5); i++)
-			for (int j = i + 1; j < (err_dev ? 6 : 5); j++)
-				if (at[i] < at[j] + len[j] && at[j] < at[i] + len[i])
-					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, out_dev and err_dev must not alias");
-		if (feat_dev) {
-			const unsigned __int128 fbytes = (unsigned __int128)width * height * RMD_FEATURE_CHANNELS * sizeof(double);
-			const unsigned __int128 f = (uintptr_t)feat_dev, g = (uintptr_t)feat_sq_dev;
-			bool bad = f < g + fbytes && g < f + fbytes;
-			for (int i = 0; i < (err_dev ? 6 : 5); i++) bad = bad || (f < at[i] + len[i] && at[i] < f + fbytes) || (g < at[i] + len[i] && at[i] < g + fbytes);
-			if (bad) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must not alias each other, the sum buffers, out_dev or err_dev");
-		}
-	}
-	if (levels > rmd::kAtrousMaxLevels) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "levels must be <= 8");
-	if (!(k > 0.0) || !std::isfinite(k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k must be finite and > 0");
-	if (!(alpha >= 0.0) || !std::isfinite(alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "alpha must be finite and >= 0");
-	if (feat_dev) {
-		if (!(k_f > 0.0) || !std::isfinite(k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "k_f must be finite and > 0");
-		if (!(tau > 0.0) || !std::isfinite(tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "tau must be finite and > 0");
-	}
-	return rmd::guarded(ctx, what, [&] {
-		const char *why = nullptr;
-		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
-		if (!regional)
-			return denoise_atrous_dual_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
-			                                rect_counts_b, rect_counts_f, n_rects, levels, k, alpha, k_f, tau, out_dev, err_dev);
-		if (!denoise_rects_ok(region, n_region, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "region: " + why);
-		return denoise_atrous_dual_region_impl(what, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
-		                                       rect_counts_b, rect_counts_f, n_rects, region, n_region, levels, k, alpha, k_f, tau, out_dev, err_dev);
-	});
-}
-
-rmd_status rmd_denoise_atrous_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
-                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t levels,
-                                   double k, double alpha, double k_f, double tau, double *out_dev, double *err_dev) {
-	return denoise_atrous_dual_checked("rmd_denoise_atrous_dual", false, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height,
-	                                   rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, nullptr, 0u, levels, k, alpha, k_f, tau, out_dev, err_dev);
-}
-
-rmd_status rmd_denoise_atrous_dual_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
-                                          const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
-                                          const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
-                                          uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t levels, double k, double alpha, double k_f,
-                                          double tau, double *out_dev, double *err_dev) {
-	return denoise_atrous_dual_checked("rmd_denoise_atrous_dual_region", true, ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width,
-	                                   height, rects, rect_counts_a, rect_counts_b, rect_counts_f, n_rects, region, n_region, levels, k, alpha, k_f, tau, out_dev, err_dev);
-}
-
-static rmd_status denoise_dual_select_impl(rmd_context *ctx, const double *sa, const double *qa, const double *sb, const double *qb, const double *feat,
-                                           const double *feat_sq, uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *counts_a,
-                                           const uint32_t *counts_b, const uint32_t *counts_f, uint32_t n_rects, uint32_t radius, uint32_t patch_radius,
-                                           const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window, double *out_dev,
-                                           double *err_dev, double *sure_dev, uint32_t *win_dev) {
-	if (rmd_status s = bind(ctx)) return s;
-	// device scratch: [the twelve u / v planes: 12 * W*H doubles][per candidate f_A, f_B and SURE: 7 * W*H doubles each][g_A, g_B: 2 * W*H doubles]
-	// [with a guided candidate, the planar f and g: 14 * W*H doubles][both halves' per-pixel counts, the winners and (guided) the features' counts:
-	// 3 or 4 * W*H uint32, padded to 16 bytes][rects: 16 bytes each][counts of A, of B and (guided) of the features: 4 bytes each]
-	bool guided = false;
-	for (uint32_t i = 0; i < n_cands; i++) guided = guided || cands[i].guided != 0u;
-	const size_t N = (size_t)width * height;
-	const size_t plane_bytes = N * 12u * sizeof(double), cand_bytes = N * 7u * sizeof(double) * n_cands, gain_bytes = N * 2u * sizeof(double);
-	const size_t fplane_bytes = guided ? N * 2u * RMD_FEATURE_CHANNELS * sizeof(double) : 0u;
-	const size_t img_bytes = ((guided ? 4u : 3u) * N * sizeof(uint32_t) + 15u) & ~(size_t)15u;
-	const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect), count_bytes = (size_t)n_rects * sizeof(uint32_t);
-	rmd::DeviceBuffer scratch;
-	RMD_HIP(ctx, scratch.alloc(plane_bytes + cand_bytes + gain_bytes + fplane_bytes + img_bytes + rect_bytes + (guided ? 3u : 2u) * count_bytes));
-	unsigned char *d = scratch.as<unsigned char>();
-	double *d_planes = scratch.as<double>();
-	double *d_cand = reinterpret_cast<double *>(d + plane_bytes);
-	double *d_gain = reinterpret_cast<double *>(d + plane_bytes + cand_bytes);
-	double *d_fplanes = guided ? reinterpret_cast<double *>(d + plane_bytes + cand_bytes + gain_bytes) : nullptr;
-	uint32_t *d_img = reinterpret_cast<uint32_t *>(d + plane_bytes + cand_bytes + gain_bytes + fplane_bytes), *d_win = d_img + 2u * N;
-	uint32_t *d_fimg = guided ? d_img + 3u * N : nullptr;
-	rmd_tile_rect *d_rects = reinterpret_cast<rmd_tile_rect *>(d + plane_bytes + cand_bytes + gain_bytes + fplane_bytes + img_bytes);
-	uint32_t *d_counts_a = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(d_rects) + rect_bytes), *d_counts_b = d_counts_a + n_rects;
-	uint32_t *d_counts_f = guided ? d_counts_b + n_rects : nullptr;
-	if (n_rects != 0) {
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_a, counts_a, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, hipMemcpyAsync(d_counts_b, counts_b, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-		if (guided) RMD_HIP(ctx, hipMemcpyAsync(d_counts_f, counts_f, count_bytes, hipMemcpyHostToDevice, ctx->stream));
-	}
-	uint64_t largest = 0; // as denoise_dual_impl
-	for (uint32_t i = 0; i < n_rects; i++) largest = std::max<uint64_t>(largest, (uint64_t)rects[i].width * rects[i].height);
-	const uint32_t columns = (uint32_t)std::min<uint64_t>(1024u, std::max<uint64_t>(1u, (largest + 255u) / 256u));
-	RMD_HIP(ctx, rmd::launch_denoise_dual_select(ctx->stream, sa, qa, sb, qb, guided ? feat : nullptr, guided ? feat_sq : nullptr, d_rects, d_counts_a, d_counts_b,
-	                                             d_counts_f, n_rects, columns, width, height, radius, patch_radius, cands, n_cands, sure_window, select_window, d_img,
-	                                             d_planes, d_cand, d_gain, d_win, d_fimg, d_fplanes, out_dev, err_dev, sure_dev, win_dev));
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return rmd::check_fault(ctx);
-}
-
-rmd_status rmd_denoise_dual_select(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
-                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
-                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t radius,
-                                   uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
-                                   double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev) {
-	const std::string name = "rmd_denoise_dual_select: ";
-	if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_dev || width == 0 || height == 0 ||
-	    (n_rects && (!rects || !rect_counts_a || !rect_counts_b)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "bad argument");
-	if (!cands || n_cands == 0 || n_cands > rmd::kDenoiseMaxCandidates) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "n_cands must be 1 .. 4, cands not NULL");
-	if (sure_window > rmd::kDenoiseMaxSelectWindow || select_window > rmd::kDenoiseMaxSelectWindow)
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "sure_window and select_window must be <= 5");
-	if ((feat_dev == nullptr) != (feat_sq_dev == nullptr)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "feat_dev and feat_sq_dev must both be given or both be NULL");
-	if (radius > rmd::kDenoiseMaxRadius) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "radius must be <= 12");
-	if (patch_radius > rmd::kDenoiseMaxPatch) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "patch_radius must be <= 4");
-	for (uint32_t i = 0; i < n_cands; i++) {
-		const rmd_denoise_candidate &c = cands[i];
-		const std::string who = name + "candidate " + std::to_string(i) + ": ";
-		if (c.reserved != 0u) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "reserved must be 0");
-		if (!(c.k > 0.0) || !std::isfinite(c.k)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "k must be finite and > 0");
-		if (!(c.alpha >= 0.0) || !std::isfinite(c.alpha)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "alpha must be finite and >= 0");
-		if (c.guided) {
-			if (!feat_dev) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "guided, but feat_dev and feat_sq_dev are NULL");
-			if (n_rects && !rect_counts_f) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "guided, but rect_counts_f is NULL with n_rects > 0");
-			if (!(c.k_f > 0.0) || !std::isfinite(c.k_f)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "k_f must be finite and > 0");
-			if (!(c.tau > 0.0) || !std::isfinite(c.tau)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, who + "tau must be finite and > 0");
-		}
-	}
-	{ // no two ranges overlap: five of W*H*3 doubles; err_dev's and sure_dev's W*H doubles, win_dev's W*H words, the two of W*H*7 doubles, where given
-		const unsigned __int128 n = (unsigned __int128)width * height;
-		const void *ptr[10] = {accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, out_dev, err_dev, sure_dev, win_dev, feat_dev, feat_sq_dev};
-		const unsigned __int128 len[10] = {n * 24u, n * 24u, n * 24u, n * 24u, n * 24u, n * 8u, n * 8u, n * 4u, n * 8u * RMD_FEATURE_CHANNELS, n * 8u * RMD_FEATURE_CHANNELS};
-		for (int i = 0; i < 10; i++)
-			for (int j = i + 1; j < 10; j++) {
-				const unsigned __int128 a = (uintptr_t)ptr[i], b = (uintptr_t)ptr[j];
-				if (ptr[i] && ptr[j] && a < b + len[j] && b < a + len[i])
-					return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "the sum buffers, the feature buffers, out_dev, err_dev, sure_dev and win_dev must not alias");
-			}
-	}
-	return rmd::guarded(ctx, "rmd_denoise_dual_select", [&] {
-		const char *why = nullptr;
-		if (!denoise_rects_ok(rects, n_rects, width, height, &why)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + why);
-		return denoise_dual_select_impl(ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a,
-		                                rect_counts_b, rect_counts_f, n_rects, radius, patch_radius, cands, n_cands, sure_window, select_window, out_dev, err_dev,
-		                                sure_dev, win_dev);
-	});
-}
-
-static rmd_status tile_error_dual_impl(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
-                                       double *out_err_host) {
-	if (rmd_status s = bind(ctx)) return s;
-	rmd::DeviceBuffer d; // the device scratch (it outlives the wait below)
-	if (n_rects != 0) {
-		// device buffer: [rects: 16 bytes each][errors: 8 bytes each]
-		const size_t rect_bytes = (size_t)n_rects * sizeof(rmd_tile_rect);
-		RMD_HIP(ctx, d.alloc(rect_bytes + (size_t)n_rects * sizeof(double)));
-		rmd_tile_rect *d_rects = d.as<rmd_tile_rect>();
-		double *d_out = reinterpret_cast<double *>(d.as<unsigned char>() + rect_bytes);
-		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, ctx->stream));
-		RMD_HIP(ctx, rmd::launch_tile_error_dual(ctx->stream, err_dev, d_rects, n_rects, width, d_out));
-		RMD_HIP(ctx, hipMemcpyAsync(out_err_host, d_out, (size_t)n_rects * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-	}
-	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
-	return rmd::check_fault(ctx);
-}
-
-rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
-                               double *out_err_host) {
-	if (!err_dev || width == 0 || height == 0 || (n_rects && (!rects || !out_err_host)))
-		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error_dual: bad argument");
-	for (uint32_t i = 0; i < n_rects; i++)
-		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_tile_error_dual: tile rectangle outside the framebuffer");
-	return rmd::guarded(ctx, "rmd_tile_error_dual", [&] { return tile_error_dual_impl(ctx, err_dev, width, height, rects, n_rects, out_err_host); });
-}
-
 // ---------------------------------------------------------------- first-hit feature buffers (features.hip)
 rmd_status rmd_feature_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, double **out_dev) {
 	if (rmd_status s = bind(ctx)) return s;
@@ -1584,7 +949,7 @@ static rmd_status render_features_impl(rmd_context *ctx, const rmd_scene *scene,
 	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
 	{
 		const char *why = nullptr;
-		if (!denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
+		if (!rmd::denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
 			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string("rmd_render_features: ") + why);
 	}
 	if (rmd_status s = bind(ctx)) return s;

@@ -235,32 +235,30 @@ size_t denoise_lds_bytes(uint32_t tile_width, uint32_t radius, uint32_t patch_ra
 }
 uint32_t denoise_tile_width(uint32_t radius, uint32_t patch_radius) { return denoise_lds_bytes(32u, radius, patch_radius) <= kLdsBudgetBytes ? 32u : 24u; }
 
-hipError_t launch_denoise_planes(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
-                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t *n_img, double *feat_planes) {
-	const bool guided = feat != nullptr;
-	if (guided && (feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
-	hipError_t e = hipMemsetAsync(n_img, 0, (size_t)W * H * sizeof(uint32_t), stream);
+hipError_t launch_denoise_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *feat_planes) {
+	const bool guided = in.feat != nullptr;
+	if (guided && (in.feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
+	const size_t N = (size_t)in.W * in.H;
+	hipError_t e = hipMemsetAsync(n_img, 0, N * sizeof(uint32_t), stream);
 	if (e != hipSuccess) return e;
-	if (n_rects) { // a column of workgroups per rect, enough for the largest (a full-frame rect is one rect)
-		hipLaunchKernelGGL(count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, rect_counts, W, n_img);
+	if (in.n_rects) { // a column of workgroups per rect, enough for the largest (a full-frame rect is one rect)
+		hipLaunchKernelGGL(count_image_kernel, dim3(in.n_rects, in.count_image_columns), dim3(256), 0, stream, in.rects, in.counts_a, in.W, n_img);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
 	if (guided) {
-		const size_t N = (size_t)W * H;
-		hipLaunchKernelGGL(feature_planes_kernel, dim3((uint32_t)((N + 255u) / 256u)), dim3(256), 0, stream, accum, accum_sq, feat, feat_sq, n_img, N, feat_planes);
+		hipLaunchKernelGGL(feature_planes_kernel, dim3((uint32_t)((N + 255u) / 256u)), dim3(256), 0, stream, in.accum_a, in.accum_sq_a, in.feat, in.feat_sq, n_img, N, feat_planes);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
 	return hipSuccess;
 }
 
-hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
-                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
-                                 double *out) {
+hipError_t launch_denoise_guided(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img,
+                                 double *feat_planes, double *out) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
-	const bool guided = feat != nullptr;
-	hipError_t e = launch_denoise_planes(stream, accum, accum_sq, feat, feat_sq, rects, rect_counts, n_rects, count_image_columns, W, H, n_img, feat_planes);
+	const bool guided = in.feat != nullptr;
+	const double *accum = in.accum_a, *accum_sq = in.accum_sq_a;
+	const uint32_t W = in.W, H = in.H;
+	hipError_t e = launch_denoise_planes(stream, in, n_img, feat_planes);
 	if (e != hipSuccess) return e;
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
@@ -270,14 +268,14 @@ hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const 
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
 	const dim3 grid((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
 	const int ri = (int)radius, fi = (int)patch_radius;
-	const double k2 = k * k, kf2 = k_f * k_f;
+	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
 	if (guided) {
-		const DenoiseGuide gd{feat_planes, kf2, tau};
-		if (tw == 32u) hipLaunchKernelGGL((denoise_kernel<32, DenoiseGuide>), grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out, gd);
-		else hipLaunchKernelGGL((denoise_kernel<24, DenoiseGuide>), grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out, gd);
+		const DenoiseGuide gd{feat_planes, kf2, w.tau};
+		if (tw == 32u) hipLaunchKernelGGL((denoise_kernel<32, DenoiseGuide>), grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out, gd);
+		else hipLaunchKernelGGL((denoise_kernel<24, DenoiseGuide>), grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out, gd);
 	} else {
-		if (tw == 32u) hipLaunchKernelGGL(denoise_kernel<32>, grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out);
-		else hipLaunchKernelGGL(denoise_kernel<24>, grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, alpha, out);
+		if (tw == 32u) hipLaunchKernelGGL(denoise_kernel<32>, grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out);
+		else hipLaunchKernelGGL(denoise_kernel<24>, grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out);
 	}
 	return hipGetLastError();
 }

@@ -137,15 +137,18 @@ __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_ker
 	}
 }
 
-hipError_t launch_denoise_atrous(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
-                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t levels, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *cv, double *feat_planes, double *out) {
+hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *cv, double *feat_planes,
+                                 double *out) {
 	if (levels > kAtrousMaxLevels) return hipErrorInvalidValue;
-	const bool guided = feat != nullptr && levels != 0u;
-	if (feat != nullptr && (feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
-	hipError_t e = launch_denoise_planes(stream, accum, accum_sq, guided ? feat : nullptr, guided ? feat_sq : nullptr, rects, rect_counts, n_rects, count_image_columns, W,
-	                                     H, n_img, feat_planes);
+	const bool guided = in.feat != nullptr && levels != 0u;
+	if (in.feat != nullptr && (in.feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
+	DenoiseInput pre = in; // (levels = 0 reads no feature)
+	if (!guided) pre.feat = pre.feat_sq = nullptr;
+	hipError_t e = launch_denoise_planes(stream, pre, n_img, feat_planes);
 	if (e != hipSuccess) return e;
+	const double *accum = in.accum_a, *accum_sq = in.accum_sq_a;
+	const uint32_t W = in.W, H = in.H;
+	const double alpha = w.alpha, tau = w.tau;
 	const size_t N = (size_t)W * H;
 	const uint64_t blocks_1d = ((uint64_t)N + 255u) / 256u;
 	const uint32_t tiles_x = (W + kAtrousBlockW - 1u) / kAtrousBlockW;
@@ -157,7 +160,7 @@ hipError_t launch_denoise_atrous(hipStream_t stream, const double *accum, const 
 	}
 	hipLaunchKernelGGL(atrous_prologue_kernel, dim3((uint32_t)blocks_1d), dim3(256), 0, stream, accum, accum_sq, n_img, N, cv);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
-	const double k2 = k * k, kf2 = k_f * k_f;
+	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
 	const dim3 grid((uint32_t)tiles), block(kAtrousBlockW * kAtrousBlockH);
 	double *set[2] = {cv, cv + 6u * N};
 	for (uint32_t l = 0; l < levels; l++) {

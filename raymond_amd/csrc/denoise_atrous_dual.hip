@@ -264,28 +264,29 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 	}
 }
 
-hipError_t launch_denoise_atrous_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
-                                      double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes, double *out,
-                                      double *err) {
+hipError_t launch_denoise_atrous_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
+                                      uint32_t *n_f_img, double *feat_planes, double *out, double *err) {
 	if (levels > kAtrousMaxLevels) return hipErrorInvalidValue;
-	const bool guided = feat != nullptr && levels != 0u;
-	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	const bool guided = in.feat != nullptr && levels != 0u;
+	if (guided && (in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr))) return hipErrorInvalidValue;
+	const double *accum_a = in.accum_a, *accum_b = in.accum_b;
+	const uint32_t W = in.W, H = in.H;
+	const double alpha = w.alpha, tau = w.tau;
 	const size_t N = (size_t)W * H;
 	const uint64_t blocks_1d = ((uint64_t)N + 255u) / 256u;
 	const uint32_t tiles_x = (W + kAtrousDualBlockW - 1u) / kAtrousDualBlockW;
 	const uint64_t tiles = (uint64_t)tiles_x * ((H + kAtrousDualBlockH - 1u) / kAtrousDualBlockH);
 	if (blocks_1d > 0x7FFFFFFFull || tiles > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
-	hipError_t e = launch_dual_planes(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, guided ? feat : nullptr, guided ? feat_sq : nullptr, rects, counts_a, counts_b,
-	                                  counts_f, n_rects, count_image_columns, W, H, n_img, state, n_f_img, feat_planes);
+	DenoiseInput pre = in; // (levels = 0 reads no feature)
+	if (!guided) pre.feat = pre.feat_sq = nullptr;
+	hipError_t e = launch_dual_planes(stream, pre, n_img, state, n_f_img, feat_planes);
 	if (e != hipSuccess) return e;
 	const uint32_t *n_a = n_img, *n_b = n_img + N;
 	if (levels == 0u) {
 		hipLaunchKernelGGL(atrous_dual_mean_kernel, dim3((uint32_t)blocks_1d), dim3(256), 0, stream, state, accum_a, accum_b, n_a, n_b, N, out, err);
 		return hipGetLastError();
 	}
-	const double k2 = k * k, kf2 = k_f * k_f;
+	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
 	const dim3 grid((uint32_t)tiles), block(kAtrousDualBlockW * kAtrousDualBlockH);
 	double *set[2] = {state, state + 12u * N};
 	for (uint32_t l = 0; l < levels; l++) {
@@ -315,36 +316,37 @@ static hipError_t launch_atrous_dual_region_level(hipStream_t stream, const Dual
 	return hipGetLastError();
 }
 
-hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                                             const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                                             const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
-                                             double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes,
-                                             const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count, double *out, double *err) {
+hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
+                                             uint32_t *n_f_img, double *feat_planes, const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count,
+                                             double *out, double *err) {
 	if (levels > kAtrousMaxLevels || table == nullptr || table_first == nullptr || table_count == nullptr) return hipErrorInvalidValue;
-	const bool guided = feat != nullptr && levels != 0u;
-	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	const bool guided = in.feat != nullptr && levels != 0u;
+	if (guided && (in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr))) return hipErrorInvalidValue;
+	const double *accum_a = in.accum_a, *accum_sq_a = in.accum_sq_a, *accum_b = in.accum_b, *accum_sq_b = in.accum_sq_b;
+	const uint32_t W = in.W, H = in.H;
+	const double alpha = w.alpha, tau = w.tau;
 	for (uint32_t i = 0; i <= levels; i++)
 		if (table_count[i] == 0u || table_count[i] > 0x7FFFFFFFu) return hipErrorInvalidConfiguration; // (a region with pixels needs every table; the caller returns before an empty one)
 	const size_t N = (size_t)W * H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
-	// the count images: the whole frame's, as dual_preamble makes them (a memset and the painting of the rects)
+	// the count images: the whole frame's, as launch_dual_planes makes them (a memset and the painting of the rects)
 	hipError_t e = hipMemsetAsync(n_img, 0, 2u * N * sizeof(uint32_t), stream);
 	if (e != hipSuccess) return e;
 	if (guided && (e = hipMemsetAsync(n_f_img, 0, N * sizeof(uint32_t), stream)) != hipSuccess) return e;
-	if (n_rects) {
-		hipLaunchKernelGGL(atrous_dual_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_a, counts_b, guided ? counts_f : nullptr, W, n_a,
-		                   n_b, guided ? n_f_img : nullptr);
+	if (in.n_rects) {
+		hipLaunchKernelGGL(atrous_dual_count_image_kernel, dim3(in.n_rects, in.count_image_columns), dim3(256), 0, stream, in.rects, in.counts_a, in.counts_b,
+		                   guided ? in.counts_f : nullptr, W, n_a, n_b, guided ? n_f_img : nullptr);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
 	const dim3 block(kAtrousDualBlockW * kAtrousDualBlockH);
-	if (guided) hipLaunchKernelGGL(atrous_dual_planes_region_kernel<true>, dim3(table_count[0]), block, 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, feat, feat_sq, n_a, n_b, n_f_img, table + table_first[0], W, N, state, feat_planes);
+	if (guided) hipLaunchKernelGGL(atrous_dual_planes_region_kernel<true>, dim3(table_count[0]), block, 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, in.feat, in.feat_sq, n_a, n_b, n_f_img, table + table_first[0], W, N, state, feat_planes);
 	else hipLaunchKernelGGL(atrous_dual_planes_region_kernel<false>, dim3(table_count[0]), block, 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, nullptr, nullptr, n_a, n_b, nullptr, table + table_first[0], W, N, state, nullptr);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
 	if (levels == 0u) { // (table 0 is the region's own then)
 		hipLaunchKernelGGL(atrous_dual_mean_region_kernel, dim3(table_count[0]), block, 0, stream, state, accum_a, accum_b, n_a, n_b, table + table_first[0], W, N, out, err);
 		return hipGetLastError();
 	}
-	const double k2 = k * k, kf2 = k_f * k_f;
+	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
 	double *set[2] = {state, state + 12u * N};
 	for (uint32_t l = 0; l < levels; l++) {
 		const double *in = set[l & 1u];

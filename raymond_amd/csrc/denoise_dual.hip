@@ -355,57 +355,43 @@ static const void *dual_pass_fn(bool guided) {
 	return guided ? reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION, DualGuide>) : reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION>);
 }
 
-// What every dual call makes first, once: both halves' count images and the twelve planes; with features also their count image and their fourteen planes
-// (which read the dual-validity mark dual_planes_kernel has just left)
-static hipError_t dual_preamble(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b, const double *feat,
-                                const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f,
-                                uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t *n_img, double *planes, uint32_t *n_f_img,
-                                double *feat_planes) {
-	const size_t N = (size_t)W * H;
+// What every dual call makes first, once — also the filters of other units (denoise_atrous_dual.hip): both halves' count images and the twelve planes;
+// with features also their count image and their fourteen planes (which read the dual-validity mark dual_planes_kernel has just left)
+hipError_t launch_dual_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *planes, uint32_t *n_f_img, double *feat_planes) {
+	const size_t N = (size_t)in.W * in.H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
 	hipError_t e = hipMemsetAsync(n_img, 0, 2u * N * sizeof(uint32_t), stream);
 	if (e != hipSuccess) return e;
-	if (n_rects) {
-		hipLaunchKernelGGL(dual_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_a, counts_b, W, n_a, n_b);
+	if (in.n_rects) {
+		hipLaunchKernelGGL(dual_count_image_kernel, dim3(in.n_rects, in.count_image_columns), dim3(256), 0, stream, in.rects, in.counts_a, in.counts_b, in.W, n_a, n_b);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
 	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
-	hipLaunchKernelGGL(dual_planes_kernel, dim3(blocks), dim3(256), 0, stream, accum_a, accum_sq_a, accum_b, accum_sq_b, n_a, n_b, N, planes);
+	hipLaunchKernelGGL(dual_planes_kernel, dim3(blocks), dim3(256), 0, stream, in.accum_a, in.accum_sq_a, in.accum_b, in.accum_sq_b, n_a, n_b, N, planes);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
-	if (feat) {
+	if (in.feat) {
 		if ((e = hipMemsetAsync(n_f_img, 0, N * sizeof(uint32_t), stream)) != hipSuccess) return e;
-		if (n_rects) {
-			hipLaunchKernelGGL(dual_feature_count_image_kernel, dim3(n_rects, count_image_columns), dim3(256), 0, stream, rects, counts_f, W, n_f_img);
+		if (in.n_rects) {
+			hipLaunchKernelGGL(dual_feature_count_image_kernel, dim3(in.n_rects, in.count_image_columns), dim3(256), 0, stream, in.rects, in.counts_f, in.W, n_f_img);
 			if ((e = hipGetLastError()) != hipSuccess) return e;
 		}
-		hipLaunchKernelGGL(dual_feature_planes_kernel, dim3(blocks), dim3(256), 0, stream, planes, feat, feat_sq, n_f_img, N, feat_planes);
+		hipLaunchKernelGGL(dual_feature_planes_kernel, dim3(blocks), dim3(256), 0, stream, planes, in.feat, in.feat_sq, n_f_img, N, feat_planes);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 	}
 	return hipSuccess;
 }
 
-// dual_preamble for the filters of other units (denoise_atrous_dual.hip): host code only, the kernels above as they are
-hipError_t launch_dual_planes(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b, const double *feat,
-                              const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f,
-                              uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t *n_img, double *planes, uint32_t *n_f_img,
-                              double *feat_planes) {
-	return dual_preamble(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, feat, feat_sq, rects, counts_a, counts_b, counts_f, n_rects, count_image_columns, W, H, n_img,
-	                     planes, n_f_img, feat_planes);
-}
-
-hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                               const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                               const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
-                               double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
-                               const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
+hipError_t launch_denoise_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img, double *planes,
+                               double *f_b, uint32_t *n_f_img, double *feat_planes, const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
-	const bool guided = feat != nullptr;
-	if (guided && (feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	const bool guided = in.feat != nullptr;
+	if (guided && (in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr))) return hipErrorInvalidValue;
 	if (table && n_blocks == 0) return hipSuccess; // a region without pixels: nothing would read the planes
+	const double *accum_a = in.accum_a, *accum_b = in.accum_b;
+	const uint32_t W = in.W, H = in.H;
 	const size_t N = (size_t)W * H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
-	hipError_t e = dual_preamble(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, feat, feat_sq, rects, counts_a, counts_b, counts_f, n_rects, count_image_columns, W, H,
-	                             n_img, planes, n_f_img, feat_planes);
+	hipError_t e = launch_dual_planes(stream, in, n_img, planes, n_f_img, feat_planes);
 	if (e != hipSuccess) return e;
 	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
@@ -415,8 +401,8 @@ hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const 
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
 	const dim3 grid = table ? dim3(n_blocks) : dim3((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
 	const int ri = (int)radius, fi = (int)patch_radius;
-	const double k2 = k * k;
-	const DualGuide gd{feat_planes, k_f * k_f, tau};
+	const double k2 = w.k * w.k, alpha = w.alpha;
+	const DualGuide gd{feat_planes, w.k_f * w.k_f, w.tau};
 	const DualGuide *gp = guided ? &gd : nullptr;
 	const double *PA = planes, *PB = planes + 6u * N;
 	for (int pass = 0; pass < 2; pass++) { // f_A: weights from B applied to u_A, into out; f_B: weights from A applied to u_B, into f_b (guided: the same w_f in both)
@@ -569,23 +555,24 @@ static hipError_t launch_dual_pass_gain(hipStream_t stream, dim3 grid, size_t ld
 	return hipGetLastError();
 }
 
-hipError_t launch_denoise_dual_select(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius,
-                                      uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
-                                      uint32_t *n_img, double *planes, double *cand_img, double *gain, uint32_t *win_img, uint32_t *n_f_img, double *feat_planes,
-                                      double *out, double *err, double *sure, uint32_t *win) {
+hipError_t launch_denoise_dual_select(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t patch_radius, const rmd_denoise_candidate *cands,
+                                      uint32_t n_cands, uint32_t sure_window, uint32_t select_window, uint32_t *n_img, double *planes, double *cand_img, double *gain,
+                                      uint32_t *win_img, uint32_t *n_f_img, double *feat_planes, double *out, double *err, double *sure, uint32_t *win) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch || n_cands == 0 || n_cands > kDenoiseMaxCandidates || sure_window > kDenoiseMaxSelectWindow ||
 	    select_window > kDenoiseMaxSelectWindow)
 		return hipErrorInvalidValue;
 	bool any_guided = false;
 	for (uint32_t i = 0; i < n_cands; i++) any_guided = any_guided || cands[i].guided != 0u;
-	if (any_guided && (feat == nullptr || feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (n_rects && counts_f == nullptr))) return hipErrorInvalidValue;
+	if (any_guided && (in.feat == nullptr || in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr)))
+		return hipErrorInvalidValue;
+	const double *accum_a = in.accum_a, *accum_b = in.accum_b;
+	const uint32_t W = in.W, H = in.H;
 	const size_t N = (size_t)W * H;
 	uint32_t *n_a = n_img, *n_b = n_img + N;
 	// once per call, whatever the number of candidates: k_f and tau enter the feature weight through denominators the kernel makes itself
-	hipError_t e = dual_preamble(stream, accum_a, accum_sq_a, accum_b, accum_sq_b, any_guided ? feat : nullptr, feat_sq, rects, counts_a, counts_b, counts_f, n_rects,
-	                             count_image_columns, W, H, n_img, planes, n_f_img, feat_planes);
+	DenoiseInput pre = in;
+	if (!any_guided) pre.feat = nullptr;
+	hipError_t e = launch_dual_planes(stream, pre, n_img, planes, n_f_img, feat_planes);
 	if (e != hipSuccess) return e;
 	const uint32_t blocks = (uint32_t)((N + 255u) / 256u);
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);

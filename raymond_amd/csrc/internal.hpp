@@ -1,4 +1,4 @@
-// Library-internal declarations shared by api.cpp, probe.cpp, comm.cpp, grid_build.cpp and grid_build_gpu.hip.
+// Library-internal declarations shared by api.cpp, api_denoise.cpp, probe.cpp, comm.cpp, grid_build.cpp and grid_build_gpu.hip.
 #pragma once
 #include <stdint.h>
 
@@ -84,7 +84,7 @@ struct rmd_context {
 	rmd::DeviceBuffer queue_buf;      // the resident waves' path queues (render_kernel.hpp: render_wave_queued), allocated at the first launch that uses them
 	rmd::DeviceBuffer tile_done;      // split launches: finished waves per wave tile, a uint32 each (render_kernel.hpp)
 	rmd::DeviceBuffer debug_counters; // walk diagnostics (DIAG builds, RMD_DEBUG=8|16)
-	rmd::DeviceBuffer atrous_region_scratch; // rmd_denoise_atrous_dual_region's planes, count images and tables: grown when a call needs more, kept between calls
+	rmd::DeviceBuffer atrous_region_scratch; // rmd_denoise_atrous_dual_region's planes, count images and tables (api_denoise.cpp): grown when a call needs more, kept between calls
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound
 	// writes here; the host looks after every wait for the stream (api.cpp: check_fault) — a plain host load, no copy
 	uint32_t *h_fault = nullptr, *d_fault = nullptr;
@@ -239,6 +239,10 @@ rmd_status guarded(rmd_context *ctx, const char *what, F &&body) noexcept {
 	}
 }
 #ifdef RMD_WITH_HIP
+// What an entry point does with its context first (api.cpp): "null context", or the context's device made current.
+rmd_status bind(rmd_context *ctx);
+// Rects inside the frame and pairwise disjoint (api_denoise.cpp); *why: the rule that was broken, the caller puts its own name in front
+bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height, const char **why);
 // After a wait for the context's stream: RMD_ERR_DEVICE_FAULT (and the fault words cleared) when a wave of a launch reported one, else RMD_OK.
 rmd_status check_fault(rmd_context *ctx);
 RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/raymond_hip.h"
+#include "denoise_host.hpp"
 #include "device_types.hpp"
 
 // entries per lane in the list-mode path record: one per trace() depth, bounce_limit <= 16
@@ -113,79 +114,65 @@ constexpr int kDenoiseFeat = (int)RMD_FEATURE_CHANNELS; // rmd_denoise_guided: f
 size_t denoise_lds_bytes(uint32_t tile_width, uint32_t radius, uint32_t patch_radius);
 // 32 when that tile's LDS fits the budget (every (r, f) but r = 12 with f = 4: 168,192 B), else 24 (145,152 B there)
 uint32_t denoise_tile_width(uint32_t radius, uint32_t patch_radius);
-// out = the denoised means of the W x H frame (accum, accum_sq) whose rect i holds rect_counts[i] samples; n_img is W*H uint32 of scratch for the
-// per-pixel counts, count_image_columns the workgroups given to each rect.  rects and rect_counts are device memory; k and alpha are checked by
-// the caller.  With the feature weight (rmd_denoise_guided) when feat / feat_sq are given (W*H*7 doubles each, pixel-interleaved); both null = the
-// unguided kernel (rmd_denoise), feat_planes unused.  feat_planes is 14 * W*H doubles of scratch for the planar per-pixel f and g; k_f and tau are
-// checked by the caller
-hipError_t launch_denoise_guided(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
-                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *feat_planes,
-                                 double *out);
+// What every denoise launcher is given of the frame (host-only plain structs: no kernel takes one).  The W x H frame's sums — accum_a / accum_sq_a alone for
+// the single-buffer filters, both halves for the dual ones —, the features (W*H*7 doubles each, pixel-interleaved; both null: no feature weight, and then
+// counts_f, k_f, tau and the features' scratch are not read), and in device memory the rects with their counts: rect i holds counts_a[i] and counts_b[i]
+// samples and counts_f[i] feature samples.  count_image_columns: the workgroups given to each rect when the per-pixel counts are painted
+struct DenoiseInput {
+	const double *accum_a, *accum_sq_a, *accum_b, *accum_sq_b, *feat, *feat_sq;
+	const rmd_tile_rect *rects;
+	const uint32_t *counts_a, *counts_b, *counts_f;
+	uint32_t n_rects, count_image_columns, W, H;
+};
+// checked by the caller (api_denoise.cpp); k_f and tau are read only with features
+struct DenoiseWeights {
+	double k, alpha, k_f, tau;
+};
+// rmd_denoise / rmd_denoise_guided (denoise.hip): out = the denoised means.  Scratch: n_img W*H uint32 for the per-pixel counts; with features feat_planes,
+// 14 * W*H doubles for the planar per-pixel f and g
+hipError_t launch_denoise_guided(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img,
+                                 double *feat_planes, double *out);
 // The preamble of launch_denoise_guided on its own (denoise.hip), for the filters of other units: n_img = the per-pixel counts, and when feat / feat_sq
 // are given feat_planes = the 14 planar images of the per-pixel f and g (a pixel that is not feature-valid keeps a NaN in plane 0)
-hipError_t launch_denoise_planes(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
-                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t *n_img, double *feat_planes);
-// rmd_denoise_atrous (denoise_atrous.hip): out = the frame after `levels` levels of the edge-avoiding a-trous filter (levels = 0: S / n).  n_img, rects,
-// rect_counts, count_image_columns, feat / feat_sq and feat_planes as launch_denoise_guided's; cv is 12 * W*H doubles of scratch, the two sets of six
-// planes (c and v) the levels alternate between.  levels, k, alpha, k_f and tau are checked by the caller
+hipError_t launch_denoise_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *feat_planes);
+// rmd_denoise_atrous (denoise_atrous.hip): out = the frame after `levels` levels of the edge-avoiding a-trous filter (levels = 0: S / n).  n_img and
+// feat_planes as launch_denoise_guided's; cv is 12 * W*H doubles of scratch, the two sets of six planes (c and v) the levels alternate between.  levels is
+// checked by the caller
 constexpr uint32_t kAtrousMaxLevels = (uint32_t)RMD_ATROUS_MAX_LEVELS;
-hipError_t launch_denoise_atrous(hipStream_t stream, const double *accum, const double *accum_sq, const double *feat, const double *feat_sq,
-                                 const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H,
-                                 uint32_t levels, double k, double alpha, double k_f, double tau, uint32_t *n_img, double *cv, double *feat_planes, double *out);
-// One workgroup's share of rmd_denoise_dual_region: its tile's origin, and the far corner (exclusive) of the region rect the tile was cut from
-struct alignas(16) DualBlock {
-	uint32_t x0, y0, x_end, y_end;
-};
-// rmd_denoise_dual (denoise_dual.hip): out = the cross-filtered means of the two halves (accum_a, accum_sq_a) and (accum_b, accum_sq_b) whose rect i
-// holds counts_a[i] and counts_b[i] samples, err (may be null) the per-pixel error estimate, W*H doubles.  Scratch: n_img 2 * W*H uint32, planes
-// 12 * W*H doubles, f_b 3 * W*H doubles.  rects and the counts are device memory; the tile shape and LDS are denoise_kernel's.  table null: every pixel
+hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *cv, double *feat_planes,
+                                 double *out);
+// rmd_denoise_dual (denoise_dual.hip): out = the cross-filtered means of the two halves, err (may be null) the per-pixel error estimate, W*H doubles.
+// Scratch: n_img 2 * W*H uint32, planes 12 * W*H doubles, f_b 3 * W*H doubles; the tile shape and LDS are denoise_kernel's.  table null: every pixel
 // of out and err is written.  table not null (rmd_denoise_dual_region; device memory): n_blocks entries (x0, y0, x_end, y_end), one per workgroup of
 // denoise_tile_width(radius, patch_radius) x 16 pixels at (x0, y0); only the pixels before (x_end, y_end), inside the frame, are written.
-// With the feature weight (rmd_denoise_dual_guided[_region]) when feat / feat_sq are given (W*H*7 doubles each, pixel-interleaved; rect i holds counts_f[i]
-// feature samples): n_f_img is W*H uint32 and feat_planes 14 * W*H doubles of further scratch, k_f and tau are checked by the caller.  Both null: exactly
-// the launches made without the feature — counts_f, k_f, tau, n_f_img and feat_planes are not read
-hipError_t launch_denoise_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                               const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                               const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius, uint32_t patch_radius,
-                               double k, double alpha, double k_f, double tau, uint32_t *n_img, double *planes, double *f_b, uint32_t *n_f_img, double *feat_planes,
-                               const DualBlock *table, uint32_t n_blocks, double *out, double *err);
-// The preamble of launch_denoise_dual on its own (denoise_dual.hip), for the filters of other units: n_img = both halves' per-pixel counts (2 * W*H
-// uint32), planes = the twelve planar u / v images (half h's u in planes 6h + c, its v in 6h + 3 + c; a pixel that is not dual-valid keeps a NaN in
-// plane 0), and when feat / feat_sq are given n_f_img and feat_planes = the features' per-pixel counts and their 14 planar f and g at that count
-hipError_t launch_dual_planes(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b, const double *feat,
-                              const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b, const uint32_t *counts_f,
-                              uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t *n_img, double *planes, uint32_t *n_f_img,
-                              double *feat_planes);
+// With features (rmd_denoise_dual_guided[_region]): n_f_img is W*H uint32 and feat_planes 14 * W*H doubles of further scratch.  Without: exactly the
+// launches made without the feature
+hipError_t launch_denoise_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img, double *planes,
+                               double *f_b, uint32_t *n_f_img, double *feat_planes, const DualBlock *table, uint32_t n_blocks, double *out, double *err);
+// What every dual call makes first, once (denoise_dual.hip; also for the filters of other units): n_img = both halves' per-pixel counts (2 * W*H uint32),
+// planes = the twelve planar u / v images (half h's u in planes 6h + c, its v in 6h + 3 + c; a pixel that is not dual-valid keeps a NaN in plane 0), and
+// with features n_f_img and feat_planes = their per-pixel counts and their 14 planar f and g at that count (which read the dual-validity mark just left)
+hipError_t launch_dual_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *planes, uint32_t *n_f_img, double *feat_planes);
 // rmd_denoise_atrous_dual (denoise_atrous_dual.hip): out / err (err may be null) = rmd_denoise_dual's combination of the two halves after `levels`
-// levels of the a-trous filter, each half under the other's weights.  Arguments as launch_denoise_dual's; state is 24 * W*H doubles of scratch, the two
-// sets of twelve planes the levels alternate between.  levels, k, alpha, k_f and tau are checked by the caller
-hipError_t launch_denoise_atrous_dual(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
-                                      double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes, double *out,
-                                      double *err);
+// levels of the a-trous filter, each half under the other's weights.  n_img, n_f_img and feat_planes as launch_denoise_dual's; state is 24 * W*H doubles of
+// scratch, the two sets of twelve planes the levels alternate between.  levels is checked by the caller
+hipError_t launch_denoise_atrous_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
+                                      uint32_t *n_f_img, double *feat_planes, double *out, double *err);
 // rmd_denoise_atrous_dual_region (denoise_atrous_dual.hip): launch_denoise_atrous_dual for the pixels of a region, through levels + 1 block tables of
 // 64 x 4-pixel workgroups (entries table_first[i] .. + table_count[i] of `table`, device memory; the two index arrays are host memory): table 0 the
 // prologue's — the pixels whose planes are made —, table 1 + l level l's; the last level's (table 0 at levels = 0) is cut from the region's rects and
 // carries their far corners, so only the region's pixels of out and err are written.  Every table has at least one entry.  n_img, state, n_f_img and
 // feat_planes as launch_denoise_atrous_dual's; what they hold outside the tables' pixels is not defined
-hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                                             const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                                             const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t levels, double k,
-                                             double alpha, double k_f, double tau, uint32_t *n_img, double *state, uint32_t *n_f_img, double *feat_planes,
-                                             const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count, double *out, double *err);
-// rmd_denoise_dual_select (denoise_dual.hip): launch_denoise_dual's preamble once, then per candidate (a HOST array, checked by the caller) its two cross
-// passes with their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per
-// candidate (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read
-// only when a candidate is guided.  err, sure and win (W*H each) may be null.
-hipError_t launch_denoise_dual_select(hipStream_t stream, const double *accum_a, const double *accum_sq_a, const double *accum_b, const double *accum_sq_b,
-                                      const double *feat, const double *feat_sq, const rmd_tile_rect *rects, const uint32_t *counts_a, const uint32_t *counts_b,
-                                      const uint32_t *counts_f, uint32_t n_rects, uint32_t count_image_columns, uint32_t W, uint32_t H, uint32_t radius,
-                                      uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
-                                      uint32_t *n_img, double *planes, double *cand_img, double *gain, uint32_t *win_img, uint32_t *n_f_img, double *feat_planes,
-                                      double *out, double *err, double *sure, uint32_t *win);
+hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
+                                             uint32_t *n_f_img, double *feat_planes, const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count,
+                                             double *out, double *err);
+// rmd_denoise_dual_select (denoise_dual.hip): launch_dual_planes once, then per candidate (a HOST array, checked by the caller) its two cross passes with
+// their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per candidate
+// (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read only when
+// a candidate is guided.  err, sure and win (W*H each) may be null.
+hipError_t launch_denoise_dual_select(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t patch_radius, const rmd_denoise_candidate *cands,
+                                      uint32_t n_cands, uint32_t sure_window, uint32_t select_window, uint32_t *n_img, double *planes, double *cand_img, double *gain,
+                                      uint32_t *win_img, uint32_t *n_f_img, double *feat_planes, double *out, double *err, double *sure, uint32_t *win);
 // out[i] = sqrt(the mean of err over rect i's pixels), +inf if one of them is NaN (denoise_dual.hip: tile_error_dual_kernel; rects and out are device memory)
 hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W, double *out);
 // rmd_render_features (features.hip): for each of the P.n_work wave tiles, the first-hit features of samples P.sample_begin .. + P.sample_count - 1

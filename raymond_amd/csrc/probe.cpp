@@ -291,6 +291,16 @@ rmd_status rmd_probe_launch_sizes(uint32_t mode, uint32_t grid, uint64_t *out8) 
 	return RMD_OK;
 }
 
+static_assert(RMD_PROBE_SCRATCH_FORMS == rmd::kScratchForms && RMD_PROBE_SCRATCH_PARTS == rmd::kScratchParts, "include/raymond_hip_probe.h mirrors denoise_host.hpp");
+rmd_status rmd_probe_denoise_scratch(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t n_cands, uint64_t n_table,
+                                     uint64_t *out3, uint64_t *total) {
+	if (form >= rmd::kScratchForms || guided > 1u || !out3 || !total) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	const rmd::ScratchLayout L = rmd::denoise_scratch_layout((rmd::ScratchForm)form, width, height, n_rects, guided != 0u, n_cands, (size_t)n_table);
+	for (uint32_t p = 0; p < rmd::kScratchParts; p++) out3[3 * p] = L.used[p], out3[3 * p + 1] = L.offset[p], out3[3 * p + 2] = L.bytes[p];
+	*total = L.total;
+	return RMD_OK;
+}
+
 rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total) {
 	if (!scene || !n_objects || !n_grids || !mask_words_total) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
 	*n_objects = scene->n_objects, *n_grids = scene->n_grids, *mask_words_total = scene->mask_words_total;

@@ -37,6 +37,7 @@ _SIGS = {
     "rmd_probe_launch_plan": [C.c_uint32, C.c_uint32, _sz, _vp, _vp],
     "rmd_probe_launch_sizes": [C.c_uint32, C.c_uint32, _vp],
     "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
+    "rmd_probe_denoise_scratch": [C.c_uint32] * 6 + [C.c_uint64, _vp, _P(C.c_uint64)],
 }
 PATH_STRIDE = 17
 _ready = False
@@ -255,3 +256,20 @@ def scene_layout(dscene):
     n, g, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
     _host_check(L.rmd_probe_scene_layout(dscene.handle, C.byref(n), C.byref(g), C.byref(m)), "rmd_probe_scene_layout")
     return n.value, g.value, m.value
+
+
+# rmd_probe_denoise_scratch: the forms, and the parts in the order of denoise_host.hpp's ScratchPart
+SCRATCH_FORMS = ("single", "atrous", "dual", "atrous_dual", "atrous_dual_region", "dual_select", "tile_error")
+SCRATCH_PARTS = ("planes", "f_b", "cand_img", "gain", "feat_planes", "n_img", "win_img", "n_f_img", "table", "rects", "counts_a", "counts_b", "counts_f",
+                 "tile_errors")
+
+
+def denoise_scratch(form, width, height, n_rects, guided=False, n_cands=0, n_table=0):
+    """Host only: the scratch block of a denoise call -> ({part: (offset, bytes)} of the parts the form holds, total bytes).
+    api: rmd_probe_denoise_scratch."""
+    L = _L()
+    out = np.zeros((len(SCRATCH_PARTS), 3), dtype=np.uint64)
+    total = C.c_uint64()
+    _host_check(L.rmd_probe_denoise_scratch(SCRATCH_FORMS.index(form), width, height, n_rects, int(guided), n_cands, n_table, _p(out), C.byref(total)),
+                "rmd_probe_denoise_scratch")
+    return {name: (int(o), int(b)) for name, (used, o, b) in zip(SCRATCH_PARTS, out) if used}, total.value
