@@ -1,5 +1,6 @@
 // Variance-guided non-local means over a rendered frame (rmd_denoise; include/raymond_hip.h states the definition, DESIGN.md section 11 the
-// structure and its cost).  A translation unit of its own: the render kernels' code objects do not change.
+// structure and its cost).  A translation unit of its own: the render kernels' code objects do not change.  The per-pixel arithmetic — the term, the
+// moments, the feature weight's pieces — is denoise_device.hpp's, shared with the other three denoise units.
 //
 // count_image_kernel — the rects' sample counts expanded into one count per pixel (0 where no rect lies): a column of workgroups per rect.
 // denoise_kernel<TW> — one TW x 16 output tile per workgroup of TW * 16 threads, one output pixel per thread.  TW = 32 (8 waves: two per SIMD,
@@ -19,7 +20,7 @@
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
-#include "launch.hpp"
+#include "denoise_device.hpp"
 
 namespace rmd {
 
@@ -28,41 +29,18 @@ __global__ __launch_bounds__(256) void count_image_kernel(const rmd_tile_rect *_
 	const rmd_tile_rect r = rects[blockIdx.x];
 	const uint32_t n = counts[blockIdx.x];
 	const uint64_t n_px = (uint64_t)r.width * r.height;
-	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
-		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
-		n_img[(size_t)(r.left + x) + (size_t)(r.top + y) * W] = n;
-	}
+	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) n_img[rect_pixel(r, i, W)] = n;
 }
 
-__device__ inline double denoise_term(double ua, double ub, double va, double vb, double k2, double alpha) {
-	const double du = ua - ub;
-	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
-}
-
-// Per pixel: f_j = F_j / n, g_j = max(0, (G_j - F_j*f_j) / (n - 1)) / n (as u and v), into planes j and 7 + j of `planes` (N = W*H doubles each).
-// A pixel that is not FEATURE-VALID (valid, and its fourteen F and G values finite) gets a NaN in plane 0.
+// Per pixel: feature_planes_pixel's fourteen planes (N = W*H doubles each), seeded with the pixel's own validity: n >= 2 and finite S, Q.
 __global__ __launch_bounds__(256) void feature_planes_kernel(const double *__restrict__ S, const double *__restrict__ Q, const double *__restrict__ F,
                                                              const double *__restrict__ G, const uint32_t *__restrict__ n_img, size_t N,
                                                              double *__restrict__ planes) {
 	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
 	if (i >= N) return;
 	const uint32_t n = n_img[i];
-	const double nd = (double)n;
-	bool valid = n >= 2u;
-#pragma unroll
-	for (int c = 0; c < 3; c++) valid = valid && __builtin_fabs(S[i * 3 + c]) < __builtin_inf() && __builtin_fabs(Q[i * 3 + c]) < __builtin_inf();
-	double fv[kDenoiseFeat], gv[kDenoiseFeat];
-#pragma unroll
-	for (int j = 0; j < kDenoiseFeat; j++) {
-		const double s = F[i * kDenoiseFeat + j], q = G[i * kDenoiseFeat + j];
-		valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-		fv[j] = s / nd;
-		double t = (q - s * fv[j]) / (nd - 1.0);
-		if (t < 0.0) t = 0.0;
-		gv[j] = t / nd;
-	}
-#pragma unroll
-	for (int j = 0; j < kDenoiseFeat; j++) planes[(size_t)j * N + i] = (j == 0 && !valid) ? __builtin_nan("") : fv[j], planes[(size_t)(kDenoiseFeat + j) * N + i] = gv[j];
+	double u[3], v[3];
+	feature_planes_pixel(F, G, i, n, moments_pixel(S, Q, i, n, u, v), N, planes);
 }
 
 // the guided kernel's extra arguments: the planar f and g images, k_f^2 and tau
@@ -103,11 +81,8 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 #pragma unroll
 		for (int c = 0; c < 3; c++) {
 			const double s = S[pix * 3 + c], q = Q[pix * 3 + c];
-			valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-			u[c] = s / nd;
-			double t = (q - s * u[c]) / (nd - 1.0);
-			if (t < 0.0) t = 0.0;
-			v[c] = t / nd;
+			valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf(); // denoise_finite of both, written out: through the call this kernel's instructions change
+			denoise_moments(s, q, nd, u[c], v[c]);
 		}
 		U[i] = valid ? u[0] : __builtin_nan(""), U[AA + i] = u[1], U[2 * AA + i] = u[2];
 		V[i] = v[0], V[AA + i] = v[1], V[2 * AA + i] = v[2];
@@ -138,7 +113,7 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 	const int dx_lo = (int)max((int64_t)-r, -gx), dx_hi = (int)min((int64_t)r, (int64_t)W - 1 - gx);
 	const int dy_lo = (int)max((int64_t)-r, -gy), dy_hi = (int)min((int64_t)r, (int64_t)H - 1 - gy);
 	double acc0 = -0.0, acc1 = -0.0, acc2 = -0.0, wsum = -0.0; // -0.0 + x == x for every x, so r = 0 gives S / n bit for bit
-	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .): eps + k_f^2 * max(tau * s_pj, g_pj), s = 1 but for the depth
+	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .)
 	[[maybe_unused]] double fp[kDenoiseFeat], gp[kDenoiseFeat], den[kDenoiseFeat];
 	[[maybe_unused]] bool p_fok = false;
 	[[maybe_unused]] const size_t N = (size_t)W * H;
@@ -147,8 +122,7 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 #pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = planes[(size_t)j * N + pixp], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pixp];
-			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
-			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = p_ok && fp[0] == fp[0];
 	}
@@ -202,8 +176,7 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 #pragma unroll
 								for (int j = 0; j < kDenoiseFeat; j++) {
 									const double fq = j == 0 ? fq0 : planes[(size_t)j * N + pixq], gq = planes[(size_t)(kDenoiseFeat + j) * N + pixq];
-									const double df = fp[j] - fq;
-									const double phi = (df * df - (gp[j] + __builtin_fmin(gp[j], gq))) / den[j];
+									const double phi = feature_phi(fp[j], gp[j], den[j], fq, gq);
 									if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
 								}
 								const double wf = exp(-Df);

@@ -11,41 +11,21 @@
 //                                 LAST = false writes c^{l+1}, v^{l+1} into the other set of six planes; LAST = true writes the interleaved
 //                                 out_dev, and S / n for a pixel that is not valid.
 // atrous_mean_kernel            — levels = 0: out = S / n for every pixel.
-// The count image and the 14 feature planes are denoise.hip's.  f64 throughout, built with -ffp-contract=off like the rest of the library.
+// The count image and the 14 feature planes are denoise.hip's, the per-pixel arithmetic denoise_device.hpp's.  f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
-#include "launch.hpp"
+#include "denoise_device.hpp"
 
 namespace rmd {
 
 constexpr int kAtrousBlockW = 64, kAtrousBlockH = 4;
 
-// rmd_denoise's term_c (denoise.hip: denoise_term), restated: that unit's code object stays as it was
-__device__ inline double atrous_term(double ua, double ub, double va, double vb, double k2, double alpha) {
-	const double du = ua - ub;
-	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
-}
-
-// H5 = {1/16, 1/4, 3/8, 1/4, 1/16} at i + 2, as selects: a table indexed by the loop counters would live in memory
-__device__ inline double atrous_h5(int i) { return i == 0 ? 0.375 : (i == 1 || i == -1 ? 0.25 : 0.0625); }
-
 __global__ __launch_bounds__(256) void atrous_prologue_kernel(const double *__restrict__ S, const double *__restrict__ Q, const uint32_t *__restrict__ n_img,
                                                               size_t N, double *__restrict__ cv) {
 	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
 	if (i >= N) return;
-	const uint32_t n = n_img[i];
-	const double nd = (double)n;
-	bool valid = n >= 2u;
 	double u[3], v[3];
-#pragma unroll
-	for (int c = 0; c < 3; c++) {
-		const double s = S[i * 3 + c], q = Q[i * 3 + c];
-		valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-		u[c] = s / nd;
-		double t = (q - s * u[c]) / (nd - 1.0);
-		if (t < 0.0) t = 0.0;
-		v[c] = t / nd;
-	}
+	const bool valid = moments_pixel(S, Q, i, n_img[i], u, v);
 	cv[i] = valid ? u[0] : __builtin_nan(""), cv[N + i] = u[1], cv[2 * N + i] = u[2];
 	cv[3 * N + i] = v[0], cv[4 * N + i] = v[1], cv[5 * N + i] = v[2];
 }
@@ -87,8 +67,7 @@ __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_ker
 #pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = planes[(size_t)j * N + pix], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pix];
-			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
-			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = fp[0] == fp[0];
 	}
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_ker
 			const double cq0 = in[q];
 			if (!(cq0 == cq0)) continue;
 			const double cq1 = in[N + q], cq2 = in[2 * N + q], vq0 = in[3 * N + q], vq1 = in[4 * N + q], vq2 = in[5 * N + q];
-			const double D = ((atrous_term(cp0, cq0, vp0, vq0, k2, alpha) + atrous_term(cp1, cq1, vp1, vq1, k2, alpha)) + atrous_term(cp2, cq2, vp2, vq2, k2, alpha)) / 3.0;
+			const double D = ((denoise_term(cp0, cq0, vp0, vq0, k2, alpha) + denoise_term(cp1, cq1, vp1, vq1, k2, alpha)) + denoise_term(cp2, cq2, vp2, vq2, k2, alpha)) / 3.0;
 			double w = exp(-(D > 0.0 ? D : 0.0));
 			if constexpr (GUIDED) {
 				if (p_fok) {
@@ -113,8 +92,7 @@ __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_ker
 #pragma unroll
 						for (int c = 0; c < kDenoiseFeat; c++) {
 							const double fq = c == 0 ? fq0 : planes[(size_t)c * N + q], gq = planes[(size_t)(kDenoiseFeat + c) * N + q];
-							const double df = fp[c] - fq;
-							const double phi = (df * df - (gp[c] + __builtin_fmin(gp[c], gq))) / den[c];
+							const double phi = feature_phi(fp[c], gp[c], den[c], fq, gq);
 							if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
 						}
 						const double wf = exp(-Df);

@@ -17,62 +17,38 @@
 //                                     table (launch.hpp: DualBlock), and workgroup b owns the 64 x 4 pixels at entry b's origin that lie before its far
 //                                     corner; nothing else differs, so a pixel's value is the whole-frame call's.  The whole-frame instantiations
 //                                     keep their arguments and their instructions.  atrous_dual_mean_region_kernel is the closed form and
-//                                     atrous_dual_planes_region_kernel<G> the prologue (denoise_dual.hip's dual_planes_kernel and
-//                                     dual_feature_planes_kernel, operation for operation, in one pass) over a block table's pixels.  The host
-//                                     makes one table per kernel from the needed sets (launch_denoise_atrous_dual_region).
+//                                     atrous_dual_planes_region_kernel<G> the prologue (the pixel functions of denoise_dual.hip's dual_planes_kernel
+//                                     and dual_feature_planes_kernel, in one pass) over a block table's pixels.  The host makes one table per
+//                                     kernel from the needed sets (launch_denoise_atrous_dual_region).
+// The per-pixel arithmetic and rmd_denoise_dual's combination are denoise_device.hpp's.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
-#include "launch.hpp"
+#include "denoise_device.hpp"
 
 namespace rmd {
 
 constexpr int kAtrousDualBlockW = 64, kAtrousDualBlockH = 4;
 
-// rmd_denoise's term_c (denoise.hip: denoise_term), restated as denoise_atrous.hip restates it
-__device__ inline double atrous_dual_term(double ua, double ub, double va, double vb, double k2, double alpha) {
-	const double du = ua - ub;
-	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
-}
-
-// H5 = {1/16, 1/4, 3/8, 1/4, 1/16} at i + 2, as selects (denoise_atrous.hip: atrous_h5)
-__device__ inline double atrous_dual_h5(int i) { return i == 0 ? 0.375 : (i == 1 || i == -1 ? 0.25 : 0.0625); }
-
-// rmd_denoise_dual's combination (denoise_dual.hip: dual_combine_pixel) of a dual-valid pixel's f_A = a and f_B = b
-__device__ inline void atrous_dual_combine(const double a[3], const double b[3], double na, double nb, size_t pix, double *__restrict__ out, double *__restrict__ err) {
-	const double nsum = na + nb;
-	double e = 0.0;
-#pragma unroll
-	for (int c = 0; c < 3; c++) {
-		out[pix * 3 + c] = (na * a[c] + nb * b[c]) / nsum;
-		const double h = (a[c] - b[c]) / 2.0;
-		e = c == 0 ? h * h : e + h * h;
+// levels = 0 at pixel i: the combination of u_A and u_B, the merged mean at a pixel that is not dual-valid
+__device__ inline void atrous_dual_mean_pixel(const double *__restrict__ planes, const double *__restrict__ SA, const double *__restrict__ SB,
+                                              const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b, size_t i, size_t N, double *__restrict__ out,
+                                              double *__restrict__ err) {
+	const double na = (double)n_a[i], nb = (double)n_b[i];
+	const double a0 = planes[i];
+	if (a0 == a0) {
+		const double a[3] = {a0, planes[N + i], planes[2 * N + i]}, b[3] = {planes[6 * N + i], planes[7 * N + i], planes[8 * N + i]};
+		dual_combine(a, b, na, nb, i, out, err);
+	} else {
+		dual_merged(SA, SB, na, nb, i, out, err);
 	}
-	if (err) err[pix] = e / 3.0;
-}
-
-// ... and of any other pixel: the merged mean as IEEE gives it, err = NaN
-__device__ inline void atrous_dual_merged(const double *__restrict__ SA, const double *__restrict__ SB, double na, double nb, size_t pix, double *__restrict__ out,
-                                          double *__restrict__ err) {
-	const double nsum = na + nb;
-#pragma unroll
-	for (int c = 0; c < 3; c++) out[pix * 3 + c] = (SA[pix * 3 + c] + SB[pix * 3 + c]) / nsum;
-	if (err) err[pix] = __builtin_nan("");
 }
 
 __global__ __launch_bounds__(256) void atrous_dual_mean_kernel(const double *__restrict__ planes, const double *__restrict__ SA, const double *__restrict__ SB,
                                                                const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b, size_t N, double *__restrict__ out,
                                                                double *__restrict__ err) {
 	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-	if (i >= N) return;
-	const double na = (double)n_a[i], nb = (double)n_b[i];
-	const double a0 = planes[i];
-	if (a0 == a0) {
-		const double a[3] = {a0, planes[N + i], planes[2 * N + i]}, b[3] = {planes[6 * N + i], planes[7 * N + i], planes[8 * N + i]};
-		atrous_dual_combine(a, b, na, nb, i, out, err);
-	} else {
-		atrous_dual_merged(SA, SB, na, nb, i, out, err);
-	}
+	if (i < N) atrous_dual_mean_pixel(planes, SA, SB, n_a, n_b, i, N, out, err);
 }
 
 // The region call's count images: dual_count_image_kernel and dual_feature_count_image_kernel of denoise_dual.hip in one pass (n_a, n_b and n_f are
@@ -84,8 +60,7 @@ __global__ __launch_bounds__(256) void atrous_dual_count_image_kernel(const rmd_
 	const uint32_t na = counts_a[blockIdx.x], nb = counts_b[blockIdx.x], nf = counts_f ? counts_f[blockIdx.x] : 0u;
 	const uint64_t n_px = (uint64_t)r.width * r.height;
 	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
-		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
-		const size_t p = (size_t)(r.left + x) + (size_t)(r.top + y) * W;
+		const size_t p = rect_pixel(r, i, W);
 		n_a[p] = na, n_b[p] = nb;
 		if (n_f) n_f[p] = nf;
 	}
@@ -98,20 +73,11 @@ __global__ __launch_bounds__(256) void atrous_dual_mean_region_kernel(const doub
                                                                       double *__restrict__ err) {
 	const DualBlock e = table[blockIdx.x];
 	const uint32_t x = e.x0 + threadIdx.x % kAtrousDualBlockW, y = e.y0 + threadIdx.x / kAtrousDualBlockW; // (no wrap: the origin lies before the far corner)
-	if (x >= e.x_end || y >= e.y_end) return;
-	const size_t i = (size_t)x + (size_t)y * W;
-	const double na = (double)n_a[i], nb = (double)n_b[i];
-	const double a0 = planes[i];
-	if (a0 == a0) {
-		const double a[3] = {a0, planes[N + i], planes[2 * N + i]}, b[3] = {planes[6 * N + i], planes[7 * N + i], planes[8 * N + i]};
-		atrous_dual_combine(a, b, na, nb, i, out, err);
-	} else {
-		atrous_dual_merged(SA, SB, na, nb, i, out, err);
-	}
+	if (x < e.x_end && y < e.y_end) atrous_dual_mean_pixel(planes, SA, SB, n_a, n_b, (size_t)x + (size_t)y * W, N, out, err);
 }
 
-// The prologue over a block table's pixels: dual_planes_kernel's twelve planes and, GUIDED, dual_feature_planes_kernel's fourteen (denoise_dual.hip),
-// the same operations in the same order per pixel — a pixel's feature validity reads only its own dual validity, so one thread makes both.
+// The prologue over a block table's pixels: dual_planes_kernel's twelve planes and, GUIDED, dual_feature_planes_kernel's fourteen (denoise_dual.hip) —
+// a pixel's feature validity reads only its own dual validity, so one thread makes both.
 template <bool GUIDED>
 __global__ __launch_bounds__(256) void atrous_dual_planes_region_kernel(const double *__restrict__ SA, const double *__restrict__ QA, const double *__restrict__ SB,
                                                                         const double *__restrict__ QB, const double *__restrict__ F, const double *__restrict__ G,
@@ -122,49 +88,8 @@ __global__ __launch_bounds__(256) void atrous_dual_planes_region_kernel(const do
 	const uint32_t x = e.x0 + threadIdx.x % kAtrousDualBlockW, y = e.y0 + threadIdx.x / kAtrousDualBlockW;
 	if (x >= e.x_end || y >= e.y_end) return;
 	const size_t i = (size_t)x + (size_t)y * W;
-	double u[2][3], v[2][3];
-	bool dual = true;
-#pragma unroll
-	for (int h = 0; h < 2; h++) {
-		const double *S = h ? SB : SA, *Q = h ? QB : QA;
-		const uint32_t n = h ? n_b[i] : n_a[i];
-		const double nd = (double)n;
-		dual = dual && n >= 2u;
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			const double s = S[i * 3 + c], q = Q[i * 3 + c];
-			dual = dual && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-			u[h][c] = s / nd;
-			double t = (q - s * u[h][c]) / (nd - 1.0);
-			if (t < 0.0) t = 0.0;
-			v[h][c] = t / nd;
-		}
-	}
-#pragma unroll
-	for (int h = 0; h < 2; h++) {
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			planes[(size_t)(6 * h + c) * N + i] = (c == 0 && !dual) ? __builtin_nan("") : u[h][c];
-			planes[(size_t)(6 * h + 3 + c) * N + i] = v[h][c];
-		}
-	}
-	if constexpr (GUIDED) {
-		const uint32_t n = n_f[i];
-		const double nd = (double)n;
-		bool valid = dual && n >= 2u;
-		double fv[kDenoiseFeat], gv[kDenoiseFeat];
-#pragma unroll
-		for (int j = 0; j < kDenoiseFeat; j++) {
-			const double s = F[i * kDenoiseFeat + j], q = G[i * kDenoiseFeat + j];
-			valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-			fv[j] = s / nd;
-			double t = (q - s * fv[j]) / (nd - 1.0);
-			if (t < 0.0) t = 0.0;
-			gv[j] = t / nd;
-		}
-#pragma unroll
-		for (int j = 0; j < kDenoiseFeat; j++) fplanes[(size_t)j * N + i] = (j == 0 && !valid) ? __builtin_nan("") : fv[j], fplanes[(size_t)(kDenoiseFeat + j) * N + i] = gv[j];
-	}
+	const bool dual = dual_planes_pixel(SA, QA, SB, QB, n_a[i], n_b[i], i, N, planes);
+	if constexpr (GUIDED) feature_planes_pixel(F, G, i, n_f[i], dual, N, fplanes);
 }
 
 __device__ inline const DualBlock *atrous_dual_table(const DualBlock *t) { return t; }
@@ -188,7 +113,7 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 	const size_t N = (size_t)W * H, pix = (size_t)x + (size_t)y * W;
 	const double ap0 = in[pix];
 	if (!(ap0 == ap0)) { // not dual-valid: never a tap, so only its mark is kept
-		if constexpr (LAST) atrous_dual_merged(SA, SB, (double)n_a[pix], (double)n_b[pix], pix, out, err);
+		if constexpr (LAST) dual_merged(SA, SB, (double)n_a[pix], (double)n_b[pix], pix, out, err);
 		else next[pix] = ap0;
 		return;
 	}
@@ -202,8 +127,7 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 #pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = planes[(size_t)j * N + pix], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pix];
-			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
-			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = fp[0] == fp[0];
 	}
@@ -221,8 +145,8 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 			if (!(aq0 == aq0)) continue;
 			const double aq1 = in[N + q], aq2 = in[2 * N + q], sq0 = in[3 * N + q], sq1 = in[4 * N + q], sq2 = in[5 * N + q];
 			const double bq0 = in[6 * N + q], bq1 = in[7 * N + q], bq2 = in[8 * N + q], tq0 = in[9 * N + q], tq1 = in[10 * N + q], tq2 = in[11 * N + q];
-			const double DA = ((atrous_dual_term(ap0, aq0, sp0, sq0, k2, alpha) + atrous_dual_term(ap1, aq1, sp1, sq1, k2, alpha)) + atrous_dual_term(ap2, aq2, sp2, sq2, k2, alpha)) / 3.0;
-			const double DB = ((atrous_dual_term(bp0, bq0, tp0, tq0, k2, alpha) + atrous_dual_term(bp1, bq1, tp1, tq1, k2, alpha)) + atrous_dual_term(bp2, bq2, tp2, tq2, k2, alpha)) / 3.0;
+			const double DA = ((denoise_term(ap0, aq0, sp0, sq0, k2, alpha) + denoise_term(ap1, aq1, sp1, sq1, k2, alpha)) + denoise_term(ap2, aq2, sp2, sq2, k2, alpha)) / 3.0;
+			const double DB = ((denoise_term(bp0, bq0, tp0, tq0, k2, alpha) + denoise_term(bp1, bq1, tp1, tq1, k2, alpha)) + denoise_term(bp2, bq2, tp2, tq2, k2, alpha)) / 3.0;
 			double wA = exp(-(DA > 0.0 ? DA : 0.0)), wB = exp(-(DB > 0.0 ? DB : 0.0));
 			if constexpr (GUIDED) {
 				if (p_fok) {
@@ -232,8 +156,7 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 #pragma unroll
 						for (int c = 0; c < kDenoiseFeat; c++) {
 							const double fq = c == 0 ? fq0 : planes[(size_t)c * N + q], gq = planes[(size_t)(kDenoiseFeat + c) * N + q];
-							const double df = fp[c] - fq;
-							const double phi = (df * df - (gp[c] + __builtin_fmin(gp[c], gq))) / den[c];
+							const double phi = feature_phi(fp[c], gp[c], den[c], fq, gq);
 							if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
 						}
 						const double wf = exp(-Df); // once, for both passes
@@ -242,7 +165,7 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 					}
 				}
 			}
-			const double h = atrous_dual_h5(i) * atrous_dual_h5(j);
+			const double h = atrous_h5(i) * atrous_h5(j);
 			const double hwB = h * wB, hwB2 = hwB * hwB, hwA = h * wA, hwA2 = hwA * hwA;
 			a0 = a0 + hwB * aq0, a1 = a1 + hwB * aq1, a2 = a2 + hwB * aq2;
 			s0 = s0 + hwB2 * sq0, s1 = s1 + hwB2 * sq1, s2 = s2 + hwB2 * sq2;
@@ -254,7 +177,7 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 	}
 	if constexpr (LAST) {
 		const double fa[3] = {a0 / wsa, a1 / wsa, a2 / wsa}, fb[3] = {b0 / wsb, b1 / wsb, b2 / wsb};
-		atrous_dual_combine(fa, fb, (double)n_a[pix], (double)n_b[pix], pix, out, err);
+		dual_combine(fa, fb, (double)n_a[pix], (double)n_b[pix], pix, out, err);
 	} else {
 		const double wa2 = wsa * wsa, wb2 = wsb * wsb;
 		next[pix] = a0 / wsa, next[N + pix] = a1 / wsa, next[2 * N + pix] = a2 / wsa;

@@ -2,7 +2,7 @@
 // the definition, DESIGN.md section 13 the structure and its cost).  A translation unit of its own: the code objects of denoise.hip and of the
 // render kernels do not change.
 //
-// dual_planes_kernel       — per pixel, both halves' u and v (exactly denoise_kernel's staging arithmetic) into twelve planar images of W*H
+// dual_planes_kernel       — per pixel, both halves' u and v (denoise_device.hpp: dual_planes_pixel, denoise_kernel's staging arithmetic) into twelve planar images of W*H
 //                            doubles: half h's u in planes 6h + c, its v in planes 6h + 3 + c.  A pixel that is not DUAL-VALID keeps a NaN in
 //                            the u of channel 0 of BOTH halves, so one test reads "valid" as dual-valid everywhere.
 // denoise_dual_kernel<TW>  — one cross pass: the weights from the six planes of the WEIGHT half, staged into LDS as denoise_kernel stages its
@@ -36,15 +36,9 @@
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
-#include "launch.hpp"
+#include "denoise_device.hpp"
 
 namespace rmd {
-
-// rmd_denoise's term, word for word (denoise.hip: denoise_term — restated here so that that translation unit stays as it is)
-__device__ inline double dual_term(double ua, double ub, double va, double vb, double k2, double alpha) {
-	const double du = ua - ub;
-	return (du * du - alpha * (va + __builtin_fmin(va, vb))) / (kDenoiseEps + k2 * (va + vb));
-}
 
 // (count_image_kernel of denoise.hip, for two count arrays at once: n_a and n_b are zeroed by the caller)
 __global__ __launch_bounds__(256) void dual_count_image_kernel(const rmd_tile_rect *__restrict__ rects, const uint32_t *__restrict__ counts_a,
@@ -54,8 +48,7 @@ __global__ __launch_bounds__(256) void dual_count_image_kernel(const rmd_tile_re
 	const uint32_t na = counts_a[blockIdx.x], nb = counts_b[blockIdx.x];
 	const uint64_t n_px = (uint64_t)r.width * r.height;
 	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
-		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
-		const size_t p = (size_t)(r.left + x) + (size_t)(r.top + y) * W;
+		const size_t p = rect_pixel(r, i, W);
 		n_a[p] = na, n_b[p] = nb;
 	}
 }
@@ -64,33 +57,7 @@ __global__ __launch_bounds__(256) void dual_planes_kernel(const double *__restri
                                                           const double *__restrict__ QB, const uint32_t *__restrict__ n_a, const uint32_t *__restrict__ n_b,
                                                           size_t N, double *__restrict__ planes) {
 	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
-	if (i >= N) return;
-	double u[2][3], v[2][3];
-	bool dual = true;
-#pragma unroll
-	for (int h = 0; h < 2; h++) {
-		const double *S = h ? SB : SA, *Q = h ? QB : QA;
-		const uint32_t n = h ? n_b[i] : n_a[i];
-		const double nd = (double)n;
-		dual = dual && n >= 2u;
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			const double s = S[i * 3 + c], q = Q[i * 3 + c];
-			dual = dual && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-			u[h][c] = s / nd;
-			double t = (q - s * u[h][c]) / (nd - 1.0);
-			if (t < 0.0) t = 0.0;
-			v[h][c] = t / nd;
-		}
-	}
-#pragma unroll
-	for (int h = 0; h < 2; h++) {
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			planes[(size_t)(6 * h + c) * N + i] = (c == 0 && !dual) ? __builtin_nan("") : u[h][c];
-			planes[(size_t)(6 * h + 3 + c) * N + i] = v[h][c];
-		}
-	}
+	if (i < N) dual_planes_pixel(SA, QA, SB, QB, n_a[i], n_b[i], i, N, planes);
 }
 
 // (count_image_kernel of denoise.hip for the features' own counts: n_f is zeroed by the caller)
@@ -99,38 +66,19 @@ __global__ __launch_bounds__(256) void dual_feature_count_image_kernel(const rmd
 	const rmd_tile_rect r = rects[blockIdx.x];
 	const uint32_t nf = counts_f[blockIdx.x];
 	const uint64_t n_px = (uint64_t)r.width * r.height;
-	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) {
-		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
-		n_f[(size_t)(r.left + x) + (size_t)(r.top + y) * W] = nf;
-	}
+	for (uint64_t i = (uint64_t)blockIdx.y * 256u + threadIdx.x; i < n_px; i += (uint64_t)gridDim.y * 256u) n_f[rect_pixel(r, i, W)] = nf;
 }
 
-// feature_planes_kernel of denoise.hip at the features' own count n_F: f_j = F_j / n_F, g_j = max(0, (G_j - F_j*f_j) / (n_F - 1)) / n_F into planes j
-// and 7 + j of `fplanes`.  A pixel that is not FEATURE-VALID (dual-valid: planes[i], dual_planes_kernel's mark, is no NaN; n_F >= 2; its fourteen F and G
-// values finite) gets a NaN in plane 0.
+// feature_planes_pixel at the features' own count n_F, seeded with the dual-validity: planes[i], dual_planes_kernel's mark, is no NaN
 __global__ __launch_bounds__(256) void dual_feature_planes_kernel(const double *__restrict__ planes, const double *__restrict__ F, const double *__restrict__ G,
                                                                   const uint32_t *__restrict__ n_f, size_t N, double *__restrict__ fplanes) {
 	const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
 	if (i >= N) return;
-	const uint32_t n = n_f[i];
-	const double nd = (double)n;
 	const double ua0 = planes[i];
-	bool valid = ua0 == ua0 && n >= 2u;
-	double fv[kDenoiseFeat], gv[kDenoiseFeat];
-#pragma unroll
-	for (int j = 0; j < kDenoiseFeat; j++) {
-		const double s = F[i * kDenoiseFeat + j], q = G[i * kDenoiseFeat + j];
-		valid = valid && __builtin_fabs(s) < __builtin_inf() && __builtin_fabs(q) < __builtin_inf();
-		fv[j] = s / nd;
-		double t = (q - s * fv[j]) / (nd - 1.0);
-		if (t < 0.0) t = 0.0;
-		gv[j] = t / nd;
-	}
-#pragma unroll
-	for (int j = 0; j < kDenoiseFeat; j++) fplanes[(size_t)j * N + i] = (j == 0 && !valid) ? __builtin_nan("") : fv[j], fplanes[(size_t)(kDenoiseFeat + j) * N + i] = gv[j];
+	feature_planes_pixel(F, G, i, n_f[i], ua0 == ua0, N, fplanes);
 }
 
-// the guided kernel's extra arguments: the planar f and g images, k_f^2 and tau (denoise.hip: DenoiseGuide, restated as dual_term is)
+// the guided kernel's extra arguments: the planar f and g images, k_f^2 and tau (denoise.hip's DenoiseGuide; a type of its own, which the kernels' names carry)
 struct DualGuide {
 	const double *planes;
 	double kf2, tau;
@@ -216,15 +164,14 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 	const int dy_lo = (int)max((int64_t)-r, -gy), dy_hi = (int)min((int64_t)r, (int64_t)H - 1 - gy);
 	const size_t pixp = inside ? (size_t)gx + (size_t)gy * W : 0;
 	double acc0 = -0.0, acc1 = -0.0, acc2 = -0.0, wsum = -0.0; // -0.0 + x == x for every x, so r = 0 gives the value half's u bit for bit
-	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .): eps + k_f^2 * max(tau * s_pj, g_pj), s = 1 but for the depth
+	// GUIDED: this pixel's features, their variances and the denominators of Phi_j(p, .)
 	[[maybe_unused]] double fp[kDenoiseFeat], gp[kDenoiseFeat], den[kDenoiseFeat];
 	[[maybe_unused]] bool p_fok = false;
 	if constexpr (GUIDED) {
 #pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = fplanes[(size_t)j * N + pixp], gp[j] = fplanes[(size_t)(kDenoiseFeat + j) * N + pixp];
-			const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp[j] * fp[j]);
-			den[j] = kDenoiseEps + kf2 * (a > gp[j] ? a : gp[j]);
+			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = p_ok && fp[0] == fp[0];
 	}
@@ -241,9 +188,9 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 					double t = 0.0;
 					uint32_t taken = 0u;
 					if (oka[s] && ub0 == ub0) {
-						t = dual_term(ua[s][0], ub0, va[s][0], V[ib], k2, alpha);
-						t = t + dual_term(ua[s][1], U[AA + ib], va[s][1], V[AA + ib], k2, alpha);
-						t = t + dual_term(ua[s][2], U[2 * AA + ib], va[s][2], V[2 * AA + ib], k2, alpha);
+						t = denoise_term(ua[s][0], ub0, va[s][0], V[ib], k2, alpha);
+						t = t + denoise_term(ua[s][1], U[AA + ib], va[s][1], V[AA + ib], k2, alpha);
+						t = t + denoise_term(ua[s][2], U[2 * AA + ib], va[s][2], V[2 * AA + ib], k2, alpha);
 						taken = 1u;
 					}
 					T[j] = t, Tc[j] = taken;
@@ -277,8 +224,7 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 #pragma unroll
 								for (int j = 0; j < kDenoiseFeat; j++) {
 									const double fq = j == 0 ? fq0 : fplanes[(size_t)j * N + pixq], gq = fplanes[(size_t)(kDenoiseFeat + j) * N + pixq];
-									const double df = fp[j] - fq;
-									const double phi = (df * df - (gp[j] + __builtin_fmin(gp[j], gq))) / den[j];
+									const double phi = feature_phi(fp[j], gp[j], den[j], fq, gq);
 									if (phi > Df) Df = phi; // (a NaN is skipped by the comparison)
 								}
 								const double wf = exp(-Df);
@@ -303,29 +249,17 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 	}
 }
 
-// fa = out (in place), fb: the two cross passes' results.  Dual-valid p: out = (n_A*f_A + n_B*f_B) / (n_A + n_B) — the two products, their sum, one
-// division —, err = (h_0^2 + h_1^2 + h_2^2) / 3 with h_c = (f_Ac - f_Bc) / 2, summed in channel order.  Any other p: the merged mean as IEEE gives it
-// and err = NaN.  err may be null.
+// fa = out (read before it is written, in place), fb: the two cross passes' results.  Dual-valid p: dual_combine of them; any other p: dual_merged.  err may be null.
 __device__ inline void dual_combine_pixel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
                                           const uint32_t *__restrict__ n_b, const double *__restrict__ planes, const double *__restrict__ fb, size_t i, double *out,
                                           double *__restrict__ err) {
 	const double na = (double)n_a[i], nb = (double)n_b[i];
-	const double nsum = na + nb;
 	const double ua0 = planes[i];
 	if (ua0 == ua0) {
-		double e = 0.0;
-#pragma unroll
-		for (int c = 0; c < 3; c++) {
-			const double a = out[i * 3 + c], b = fb[i * 3 + c];
-			out[i * 3 + c] = (na * a + nb * b) / nsum;
-			const double h = (a - b) / 2.0;
-			e = c == 0 ? h * h : e + h * h;
-		}
-		if (err) err[i] = e / 3.0;
+		const double a[3] = {out[i * 3 + 0], out[i * 3 + 1], out[i * 3 + 2]}, b[3] = {fb[i * 3 + 0], fb[i * 3 + 1], fb[i * 3 + 2]};
+		dual_combine(a, b, na, nb, i, out, err);
 	} else {
-#pragma unroll
-		for (int c = 0; c < 3; c++) out[i * 3 + c] = (SA[i * 3 + c] + SB[i * 3 + c]) / nsum;
-		if (err) err[i] = __builtin_nan("");
+		dual_merged(SA, SB, na, nb, i, out, err);
 	}
 }
 __global__ __launch_bounds__(256) void dual_combine_kernel(const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
@@ -617,8 +551,7 @@ __global__ __launch_bounds__(256) void tile_error_dual_kernel(const double *__re
 	double s = 0.0;
 	uint32_t bad = 0u;
 	for (uint64_t i = threadIdx.x; i < n_px; i += 256u) {
-		const uint32_t x = (uint32_t)(i % r.width), y = (uint32_t)(i / r.width);
-		const double e = err[(size_t)(r.left + x) + (size_t)(r.top + y) * W];
+		const double e = err[rect_pixel(r, i, W)];
 		if (e == e) s = s + e;
 		else bad = 1u;
 	}
