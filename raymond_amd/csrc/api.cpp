@@ -707,8 +707,8 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, settings);
 	P.n_work = ctx->n_wave_tiles;
 	if (P.debug_flags & 24u) {
-		RMD_HIP(ctx, ctx->debug_counters.grow(40 * sizeof(unsigned long long)));
-		RMD_HIP(ctx, hipMemsetAsync(ctx->debug_counters.as<void>(), 0, 40 * sizeof(unsigned long long), ctx->stream));
+		RMD_HIP(ctx, ctx->debug_counters.grow(48 * sizeof(unsigned long long)));
+		RMD_HIP(ctx, hipMemsetAsync(ctx->debug_counters.as<void>(), 0, 48 * sizeof(unsigned long long), ctx->stream));
 		P.debug_counters = ctx->debug_counters.as<unsigned long long>();
 	}
 	bool buffered = false;
@@ -819,7 +819,7 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	RMD_HIP(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
 	ctx->timed = true;
 	if (P.debug_flags & 24u) {
-		unsigned long long h[40];
+		unsigned long long h[48];
 		RMD_HIP(ctx, hipMemcpyAsync(h, ctx->debug_counters.as<void>(), sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
 		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		if ((P.debug_flags & 16u) && ctx->last_launch.queued) {
@@ -840,6 +840,9 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		if ((P.debug_flags & 16u) == 0u && (P.debug_flags & 512u))
 			std::fprintf(stderr, "[rmd debug] primary candidates: lanes checked=%llu sphere turns left out=%llu trips with two axis pairs left out=%llu | cleared spheres that register a hit (must be 0)=%llu closest hits that differ from the full visit's (must be 0)=%llu\n",
 			             h[32], h[35], h[36], h[33], h[34]);
+		if ((P.debug_flags & 16u) == 0u && ctx->last_launch.buffered && scene->n_grids == 0u) // (the role-sorted spheres kernel: render_wave_sorted)
+			std::fprintf(stderr, "[rmd debug] lobe trips: diffuse trips=%llu diffuse hits shaded=%llu ggx trips=%llu ggx hits shaded=%llu | hits parked: diffuse=%llu ggx=%llu\n", h[37], h[38], h[39],
+			             h[40], h[41], h[42]);
 		if ((P.debug_flags & 16u) == 0u && ctx->last_launch.queued)
 			std::fprintf(stderr, "[rmd debug] path queues: rays pushed=%llu (of them walks put aside=%llu) rays held in their lanes=%llu hits pushed=%llu hits held in their lanes=%llu\n", h[19], h[22], h[23], h[20], h[21]);
 	}

@@ -528,6 +528,14 @@ RMD_DEV V3 sel(bool c, V3 a, V3 b) { return mk(c ? a.x : b.x, c ? a.y : b.y, c ?
 // Must be called in wave-uniform control flow; a lane with neither flag set is left untouched.
 // A register (pair) the compiler may fill with anything: the value of a variable in the lanes that never use it.
 #define RMD_UNDEF(v) asm volatile("" : "=v"(v));
+// Which lobe a hit's bounce samples (src/trace.rs:260-264): r, the 22-bit uniform of the path's PREVIOUS block, against prob_d = lerp(0.5, 0, metal).
+// ONE definition for next_ray's branch and for the role-sorted spheres kernel, which decides the lobe when it parks a hit (render_kernel.hpp:
+// render_wave_sorted) and shades it with shade_lobe<> below: the decision at the park and the branch at the shading cannot disagree.
+RMD_DEV double lobe_uniform(uint32_t lobe_bits) { return (double)lobe_bits * (1.0 / 4194304.0); }
+RMD_DEV bool bounce_is_diffuse(double r, double metal, double &prob_d) {
+	prob_d = lerp(0.5, 0.0, metal); // :263
+	return r < prob_d;              // :264
+}
 struct NextRayShadeIn {
 	V3 normal, frag, color;
 	double roughness, metal;
@@ -539,7 +547,7 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 	// select where the branches meet — RMD_UNDEF)
 	double u_first, u_second;
 	RMD_UNDEF(u_first) RMD_UNDEF(u_second)
-	const double r = (double)rng.lobe_bits * (1.0 / 4194304.0); // shade only (:260): the 22-bit uniform of the path's previous block
+	const double r = lobe_uniform(rng.lobe_bits); // shade only (:260): the 22-bit uniform of the path's previous block
 	if (gen) {
 		uint32_t w0, w1, w2, w3;
 		philox4x32_10(rng.pixel, rng.sample, rng.block, 0u, P.key0, P.key1, w0, w1, w2, w3);
@@ -558,8 +566,7 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 		view = normalize(cam_pos - in.frag); // :256
 		f0 = mk(lerp(0.04, in.color.x, in.metal), lerp(0.04, in.color.y, in.metal), lerp(0.04, in.color.z, in.metal)); // :257-258
 		const double r1 = u_first, r2 = u_second; // :397-398 or :287-288
-		prob_d = lerp(0.5, 0.0, in.metal);         // :263
-		diffuse = r < prob_d;                      // :264
+		diffuse = bounce_is_diffuse(r, in.metal, prob_d); // :263-264
 		double phi, st, ct, sp, cp;
 		V3 axis;
 		// both samplers begin with a square root — sqrt(r1) (:399) or sqrt(r2 / (1 - r2)) (:289): one sequence for the lanes of either kind
@@ -653,6 +660,77 @@ RMD_DEV void next_ray(const RenderParams &P, bool do_shade, bool do_prim, const 
 RMD_DEV void shade(const RenderParams &P, V3 normal, V3 frag, V3 color, double roughness, double metal, V3 cam_pos, Rng &rng, V3 &ro, V3 &rd, V3 &T) {
 	NextRayShadeIn in{normal, frag, color, roughness, metal};
 	next_ray(P, true, false, in, cam_pos, 0u, 0u, rng, ro, rd, T);
+}
+
+// The shading half for a wave whose lanes ALL sample the same lobe (render_wave_sorted's shading trips): next_ray's SHADE stream with the lobe a
+// compile-time argument.  Per lane the operations and their order are exactly next_ray's for that lobe — the diffuse instantiation holds no
+// division, no polar sin / cos, no mirror direction and no D / G terms, the GGX one no hemisphere pair — and there is no `diffuse ? :` select and
+// no join of two arms.  The caller guarantees DIFFUSE == bounce_is_diffuse(lobe_uniform(rng.lobe_bits), metal, .) for every lane whose result it keeps.
+template <bool DIFFUSE>
+RMD_DEV void shade_lobe(const RenderParams &P, V3 normal, V3 frag, V3 color, double roughness, double metal, V3 cam_pos, Rng &rng, V3 &ro, V3 &rd, V3 &T) {
+	uint32_t w0, w1, w2, w3;
+	philox4x32_10(rng.pixel, rng.sample, rng.block, 0u, P.key0, P.key1, w0, w1, w2, w3);
+	rng.block++;
+	const double r1 = Rng::to_unit(w0, w1), r2 = Rng::to_unit(w2, w3); // :397-398 or :287-288
+	rng.lobe_bits = Rng::spare22(w0, w2); // for the next shaded depth
+	// ---- first half: the direction (next_ray: "SHADE, first half")
+	const V3 view = normalize(cam_pos - frag); // :256
+	const V3 f0 = mk(lerp(0.04, color.x, metal), lerp(0.04, color.y, metal), lerp(0.04, color.z, metal)); // :257-258
+	const double prob_d = lerp(0.5, 0.0, metal); // :263
+	double phi, st, ct, sp, cp, pdf_d = 0.0;
+	V3 axis;
+	if constexpr (DIFFUSE) {
+		// uniform_sample_hemisphere (:396-406), frame around the normal (:261-262)
+		const double root = sqrt64(r1);
+		hemisphere_sincos(root, st, ct);
+		phi = 2.0 * kPi * r2;
+		pdf_d = root;
+		axis = normal;
+	} else {
+		// importance_sample_ggx (:286-296), frame around the mirror direction (:285)
+		const double root = sqrt64(div_lean(r2, 1.0 - r2));
+		const double a = roughness * roughness;
+		phi = 2.0 * kPi * r1;
+		sincos_cw(a * root, st, ct);
+		axis = normalize(-view - 2.0 * (-dot(view, normal) * normal));
+	}
+	sincos_cw(phi, sp, cp);
+	const V3 local = mk(st * cp, ct, st * sp);
+	V3 tg, bt;
+	onb(axis, tg, bt);
+	const V3 sw = normalize(mat3_mul(tg, axis, bt, local)); // :266 / :295
+	// ---- second half: the bounce's weight (:275-282 / :301-318: next_ray's derivation) and the bounce ray
+	const double n_dot_sw = dot(normal, sw);
+	const V3 halfway = normalize_for_weight(sw + view);
+	const double h_dot_v = dot(halfway, view);
+	const double fc = DIFFUSE ? fmax(h_dot_v, 0.0) : h_dot_v; // :277 clamps, :309 does not
+	const V3 F = f0 + (mk(1.0, 1.0, 1.0) - f0) * pow5(1.0 - fc); // fresnel_schlick :384-386
+	V3 vec;
+	double N, Dn;
+	if constexpr (DIFFUSE) {
+		const V3 diffuse_part = (mk(1.0, 1.0, 1.0) - F) * (1.0 - metal); // :279-280
+		vec = hadamard(diffuse_part, color);
+		N = fmax(n_dot_sw, 0.0); // :275
+		Dn = prob_d * pdf_d;     // :282
+	} else {
+		const double a2 = roughness * roughness;
+		const double ndh = dot(normal, halfway);
+		const double den = (ndh * ndh) * (a2 - 1.0) + 1.0;
+		const double Dd = fmax(kPi * den * den, 1e-7); // :367-368
+		const double k = (roughness * roughness) / 8.0; // :374
+		const double n_dot_v = dot(normal, view);
+		const double g1n = fmax(n_dot_v, 0.0), g2n = fmax(n_dot_sw, 0.0); // :373
+		const double g1d = g1n * (1.0 - k) + k, g2d = g2n * (1.0 - k) + k; // :375-377
+		const double denominator = 4.0 * n_dot_v * n_dot_sw + 0.001;       // :312
+		const double hv4 = 4.0 * h_dot_v;
+		vec = F;
+		N = (((a2 * g1n) * g2n) * n_dot_sw) * hv4; // cos_theta = n.l unclamped (:306)
+		Dn = (((g1d * g2d) * denominator) * (1.0 - prob_d)) * (a2 * ndh + 0.0001 * (Dd * hv4));
+	}
+	const V3 wgt = vec * (N * fast_rcp(Dn));
+	T = hadamard(T, wgt);
+	ro = frag + normal * (DIFFUSE ? scalar_const(0.00001) : scalar_const(0.0001)); // :269 / :300
+	rd = sw;
 }
 
 // ---------------------------------------------------------------- ray generation (src/trace.rs:322-360)

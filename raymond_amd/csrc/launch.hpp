@@ -65,11 +65,11 @@ constexpr uint32_t kGridWavesPerWg = 4;
 // waves of a persistent workgroup (one per CU: all 16 wave slots that 128 registers per lane leave)
 constexpr uint32_t kPersistWavesPerWg = 16;
 constexpr uint32_t kGridPersistWavesPerWg = 16; // ... of the grid instantiation
-// the spheres kernel's split launches (render_kernel.hpp: render_wave_sorted): path slots of a wave's pool and waves of a persistent workgroup —
-// 16 pools of 112 slots (86 bytes each) and the object table fit the CU's 160 KB
-constexpr uint32_t kSortSlots = 120;
+// the spheres kernel's split launches (render_kernel.hpp: render_wave_sorted): entries of a wave's two hit stacks together and waves of a
+// persistent workgroup — 16 areas of 168 entries (60 bytes each: an entry holds no normal) and the object table fit the CU's 160 KB
+constexpr uint32_t kSortSlots = 168;
 constexpr uint32_t kSortedWavesPerWg = 16; // waves of one persistent workgroup (one per CU)
-constexpr size_t kSortPoolBytes = 84u * kSortSlots; // per-wave LDS (sizeof(HitStack): 9 doubles + 3 words an entry)
+constexpr size_t kSortPoolBytes = 60u * kSortSlots; // per-wave LDS (sizeof(HitStack): 6 doubles + 3 words an entry)
 // every wave's LDS area ends with 16 bytes of bookkeeping (render_kernel.hpp: word 0 = 1 + the work item a persistent wave drew last)
 constexpr size_t kWaveHeadBytes = 16u;
 // the form a render launch was made in (render_kernel.hpp: launch_render) -> rmd_launch_info

@@ -6,6 +6,7 @@
 #include "device_core.hpp"
 #include "grid_walk.hpp"
 #include "launch.hpp"
+#include "lobe_trips.hpp"
 #include "primary_candidates.hpp"
 #include "scene_split.hpp"
 
@@ -669,19 +670,27 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 //       classification;
 //   SI  the top 64 hits of the stack: shading (:256-319) -> bounce ray, intersection, classification.
 // Classification (:242-252 and the rules of DESIGN.md section 3) ends a path — its sample goes to the per-sample buffer — or parks the hit
-// (hit point, normal, throughput, RNG state: 9 doubles + 3 words) on the stack.  A path's arithmetic is the same functions in the same order
+// (hit point, throughput, RNG state: 6 doubles + 3 words) on the stack.  A path's arithmetic is the same functions in the same order
 // as in render_wave(): every sample has the same bits; which lane and which trip compute it changes nothing (the RNG is keyed by pixel and
-// sample, the samples are added in order afterwards).  A generation trip runs while the stack has room for the 64 hits it may park, so a
-// shading trip finds more than kSortSlots - 64 hits (57 .. 64 lanes at 120 entries) until the item runs out of pairs; the remaining hits are
-// then shaded in ever smaller trips.
+// sample, the samples are added in order afterwards).
+// A shading trip is LOBE-UNIFORM: which lobe a hit's next bounce samples is known when the hit is parked (device_core.hpp: bounce_is_diffuse, from
+// the path's last block and the object's metalness), the stack is two stacks — diffuse hits from entry 0 upward, GGX hits from the last entry
+// downward — and a shading trip pops one of them and runs shade_lobe<> for that lobe alone: no GGX division, polar sin / cos, mirror direction
+// and D / G terms in a diffuse trip, no hemisphere pair in a GGX trip, no selects where the two arms met.  The rule (lobe_trips.hpp): a generation
+// trip while the item has pairs and both stacks together leave room for the 64 hits it may park, else a shading trip of the fuller stack, until
+// the item runs out of pairs; the remaining hits are then shaded in ever smaller trips.
 constexpr int kSortObjPrio = 1; // s_setprio level of the closest-hit loop over the objects in the role-sorted spheres kernel
 // The wave's parked hits: a dense STACK in LDS (round 5; round 4 kept a path in a fixed slot of a pool and two lists of slot numbers).  A hit is
 // pushed where the stack ends — the lanes of a trip that park write to consecutive entries — and a shading trip pops the top 64, lane i entry
 // n_hit - 64 + i: every access of a trip is 64 consecutive 8-byte (or 4-byte) words, the one pattern the LDS serves without a bank conflict
 // (53 % of the LDS-active cycles of round 4's pool were conflicts: a trip's slot numbers were arbitrary), there are no slot lists to read and
 // write, and a lane that starts a sample needs no slot at all.
+// An entry holds no surface normal: it is a function of what the entry holds anyway — the object's own for a plane, normalize(frag - origin) for a
+// sphere — and is made again by the trip that shades the hit, from the same stored values by the same function.  Without its 24 bytes an entry is
+// 60 bytes and 168 of them fit the LDS that 120 took: room for two stacks that each fill a trip (tools/lobe_trip_model.py: at 120 entries
+// lobe-uniform trips run at 50 lanes and lose).
 struct alignas(16) HitStack {
-	double frag[3][kSortSlots], normal[3][kSortSlots], T[3][kSortSlots]; // the parked hit: point, surface normal; the path's throughput
+	double frag[3][kSortSlots], T[3][kSortSlots]; // the parked hit's point; the path's throughput
 	uint32_t state[kSortSlots];     // object (16 bits) | next RNG block (16)
 	uint32_t lobe_bits[kSortSlots]; // the 22 spare bits of the path's last block | depth << 24
 	uint32_t item[kSortSlots];      // the path's (pixel, sample) pair: its number in the work item's pool
@@ -750,9 +759,9 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 	uint32_t *item_sets = reinterpret_cast<uint32_t *>(wave_lds + sizeof(HitStack)) + 1; // [0]: axis pairs, [1], [2]: visit mask (word 0 of the head is the work loop's)
 	item_candidates(kernarg_params, tile, objs, lobjs, item_sets);
 
-	uint32_t n_hit = 0, next_item = 0; // wave-uniform: entries on the stack, pairs handed out
+	uint32_t n_d = 0, n_g = 0, next_item = 0; // wave-uniform: entries on the diffuse and on the GGX stack, pairs handed out
 	// the trip loop's bound (report_fault): every trip hands out 64 pairs or advances at least one path by a segment
-	unsigned long long trips_left = (unsigned long long)pool_items * kTripBoundPerPair + 64ull;
+	unsigned long long trips_left = lobe_trip_bound(pool_items, kTripBoundPerPair);
 #if RMD_DIAG
 	if (P.debug_flags & 32u) trips_left = 1ull; // tests/test_gpu_faults.py: forces the bound
 #endif
@@ -766,23 +775,24 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		RenderParams Pt;
 		__builtin_memcpy(&Pt, w, sizeof(Pt));
 
-		// Which kind of trip.  A generation trip (64 new samples) needs room for the 64 hits it may park: it runs while the item has pairs and
-		// the stack holds at most kSortSlots - 64 hits; else the top min(n_hit, 64) hits are shaded — more than kSortSlots - 64 of them (57 .. 64
-		// lanes at 120 entries) unless the item has run out of pairs, when what is left is shaded in ever smaller trips.  (The other way round —
-		// shading trips only when 64 hits wait, generation trips of min(64, kSortSlots - n_hit) pairs — measured 0.4 % slower on C2, 0.8 % with
-		// every path traced.)
+		// Which kind of trip (lobe_trips.hpp: lobe_trip_rule).  A generation trip (64 new samples) needs room for the 64 hits it may park, whatever
+		// their lobes: it runs while the item has pairs and n_d + n_g <= kSortSlots - 64; else the fuller of the two stacks is shaded, its top
+		// min(n, 64) hits — unless the item has run out of pairs, when what is left is shaded in ever smaller trips.  (With ONE stack the other way
+		// round — shading trips only when 64 hits wait, generation trips of min(64, kSortSlots - n_hit) pairs — measured 0.4 % slower on C2,
+		// 0.8 % with every path traced.)
 		// Every trip makes progress, for every stack size the static_assert admits: a generation trip hands out 64 pairs — next_item grows; a
-		// shading trip runs when no pair is left (n_hit > 0 then, else the loop has ended) or n_hit > kSortSlots - 64 >= 8, so at least one path
-		// advances by a segment, and a path has at most bounce_limit of them.  There is no state in which a trip runs with no lane —
-		// unlike a pool with THREE lists, where all three can be short of a full trip while the empty list holds nothing
-		// (tools/experiments/README.md: the run that was killed for silence in round 4).
+		// shading trip runs when no pair is left (n_d + n_g > 0 then, else the loop has ended) or n_d + n_g > kSortSlots - 64 >= 8, so the fuller
+		// stack holds at least one hit and at least one path advances by a segment, and a path has at most bounce_limit of them.  There is no
+		// state in which a trip runs with no lane — unlike a pool with THREE lists, where all three can be short of a full trip while the empty
+		// list holds nothing (tools/experiments/README.md: the run that was killed for silence in round 4).  The stacks never meet: a generation
+		// trip parks at most 64 hits into at least 64 free entries, a shading trip parks at most as many as it has popped.
 		if (RMD_UNLIKELY(trips_left-- == 0ull)) { // (never reached: see above) — the wave reports, drops what it holds and leaves through the loop's own exit
 			report_fault(Pt, kFaultSortedTripLoop, work_item);
-			n_hit = 0u, next_item = pool_items;
+			n_d = 0u, n_g = 0u, next_item = pool_items;
 		}
-		const bool items_left = next_item < pool_items;
-		if (n_hit == 0u && !items_left) break;
-		const bool shade_trip = !items_left || n_hit > kSortSlots - 64u;
+		const LobeTrip trip = lobe_trip_rule(n_d, n_g, next_item < pool_items, kSortSlots);
+		if (trip.kind == kTripDone) break;
+		const bool shade_trip = trip.kind != kTripGenerate;
 		bool active;
 		uint32_t item = 0, depth = 1;
 		Rng rng;
@@ -795,26 +805,36 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		unsigned long long turns = Pt.visit_mask; // the object loop's turns and the axis pairs of this trip: the launch's, or (GI) the item's own
 		uint32_t pairs = Pt.axis_pairs;
 		if (shade_trip) {
-			// ---------------- SI: the top (up to) 64 parked hits, lane i the entry n_hit - n + i
-			const uint32_t n = n_hit < 64u ? n_hit : 64u;
+			// ---------------- SI: the top (up to) 64 hits of one lobe's stack, lane i the entry first + i
+			const bool lobe_d = trip.kind == kTripShadeDiffuse;
+			const uint32_t n = trip.lanes;
 			active = lane < n;
-			const uint32_t e = active ? n_hit - n + lane : 0u;
-			n_hit -= n;
+			const uint32_t e = lobe_pop_first(lobe_d, n_d, n_g, n, kSortSlots) + (active ? lane : 0u);
+			if (lobe_d) n_d -= n;
+			else n_g -= n;
+#if RMD_DIAG
+			if ((Pt.debug_flags & 8u) && Pt.debug_counters && lane == 0u) // RMD_DEBUG bit 8: [37] / [39] shading trips, [38] / [40] shaded hits — diffuse / GGX
+				atomicAdd(&Pt.debug_counters[lobe_d ? 37 : 39], 1ull), atomicAdd(&Pt.debug_counters[lobe_d ? 38 : 40], (unsigned long long)n);
+#endif
 			const uint32_t st = stack.state[e];
 			item = stack.item[e];
 			const uint32_t lb = stack.lobe_bits[e];
 			rng.block = st >> 16, rng.lobe_bits = lb & 0x3FFFFFu;
 			depth = lb >> 24;
-			const DevObject &o = lobjs[active ? (st & 0xFFFFu) : 0u];
+			const DevObject &o = lobjs[st & 0xFFFFu]; // (a lane beyond the trip's n holds the trip's first entry)
 			T = mk(stack.T[0][e], stack.T[1][e], stack.T[2][e]);
-			const V3 normal = mk(stack.normal[0][e], stack.normal[1][e], stack.normal[2][e]);
 			const V3 frag = mk(stack.frag[0][e], stack.frag[1][e], stack.frag[2][e]);
+			// the surface normal, from the stored hit point and object: the operations classification ran before it parked their result
+			V3 normal;
+			if (o.geometry_kind == 0u) normal = ld3(o.normal); // plane.rs:28-32
+			else normal = normalize(frag - ld3(o.origin));      // sphere.rs:31-35
 			const uint32_t x = tile.x0 + (item & 7u), y = tile.y0 + ((item >> 3) & 7u);
 			rng.pixel = y * Pt.W + x, rng.sample = Pt.sample_begin + pool_first + (item >> 6);
-			{ // every lane shades — a lane beyond the trip's n the stack's entry 0, a hit of this work item like any other; what it computes is never
+			{ // every lane shades — a lane beyond the trip's n the trip's first entry, a hit of this lobe like any other; what it computes is never
 			  // stored (`active` gates everything below).  Shading under `if (active)` made ro, rd and T values that are assigned inside a divergent
-			  // branch: nine 64-bit copies of the other lanes' undefined values per trip.
-				shade(Pt, normal, frag, ld3(o.color), o.roughness, o.metalness, cam_pos, rng, ro, rd, T);
+			  // branch: nine 64-bit copies of the other lanes' undefined values per trip.  The branch on the lobe is wave-uniform.
+				if (lobe_d) shade_lobe<true>(Pt, normal, frag, ld3(o.color), o.roughness, o.metalness, cam_pos, rng, ro, rd, T);
+				else shade_lobe<false>(Pt, normal, frag, ld3(o.color), o.roughness, o.metalness, cam_pos, rng, ro, rd, T);
 				depth++;
 				// (see render_wave: a path whose throughput is exactly zero is ended unless the caller traces such paths on)
 				const bool black = Pt.end_black_paths != 0u && T.x == 0.0 && T.y == 0.0 && T.z == 0.0;
@@ -873,8 +893,9 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 #endif
 		// ---------------- classification (the rules of render_wave's phase C)
 		bool terminal = failed, park = false, emitted = false;
-		V3 frag, normal;
-		RMD_UNDEF3(frag) RMD_UNDEF3(normal)
+		bool park_d = false; // the parked hit's next bounce samples the diffuse lobe: the stack it goes onto
+		V3 frag;
+		RMD_UNDEF3(frag)
 		if (want) {
 			if (oi < 0) {
 				terminal = true; // :242 miss -> radiance 0
@@ -885,13 +906,20 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 					emitted = true; // :250-252 Emission
 					terminal = true;
 				} else {
-					if (o.geometry_kind == 0u) normal = ld3(o.normal);       // plane.rs:28-32
-					else normal = normalize(frag - ld3(o.origin));            // sphere.rs:31-35
-					const double probe_sum = ((normal.x + normal.y) + normal.z) + ((frag.x + frag.y) + frag.z);
-					const bool finite_inputs = __builtin_fabs(probe_sum) < __builtin_inf();
 					const bool black_bounce = Pt.end_black_paths != 0u && (o.flags & kObjBlackDiffuse) != 0u && rng.lobe_bits < (1u << 21);
-					if (((depth == Pt.bounce_limit && Pt.shade_last_depth == 0u) || black_bounce) && finite_inputs) terminal = true; // L = 0
-					else park = true;
+					park = true;
+					// The surface normal is read here only by finite_inputs, and that decides only for a hit one of the two rules would end: it is made
+					// under that condition.  A hit that is parked regardless is parked without it (the trip that shades it makes it).
+					if ((depth == Pt.bounce_limit && Pt.shade_last_depth == 0u) || black_bounce) {
+						V3 normal;
+						if (o.geometry_kind == 0u) normal = ld3(o.normal); // plane.rs:28-32
+						else normal = normalize(frag - ld3(o.origin));      // sphere.rs:31-35
+						const double probe_sum = ((normal.x + normal.y) + normal.z) + ((frag.x + frag.y) + frag.z);
+						const bool finite_inputs = __builtin_fabs(probe_sum) < __builtin_inf();
+						if (finite_inputs) terminal = true, park = false; // L = 0
+					}
+					double prob_d; // the branch shade_lobe<> will be chosen by, on the values the entry stores
+					park_d = bounce_is_diffuse(lobe_uniform(rng.lobe_bits), o.metalness, prob_d);
 				}
 			}
 		}
@@ -902,18 +930,24 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			RMD_GLOBAL double *dst = (RMD_GLOBAL double *)Pt.sample_buf + (((size_t)wt * Pt.sample_count + pool_first + (item >> 6)) * 64u + (item & 63u)) * kSampleStride;
 			store_sample(dst, L);
 		}
-		// the hits that go on: pushed onto the stack, consecutive entries for the lanes that park
+		// the hits that go on: pushed onto their lobe's stack — the lanes that park a diffuse hit write consecutive entries upward from n_d, those
+		// that park a GGX hit consecutive entries downward from kSortSlots - 1 - n_g, each by its rank among the lanes of its own kind
 		{
-			const unsigned long long pm = __ballot(park);
-			const uint32_t e = n_hit + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
+			const unsigned long long pm_d = __ballot(park && park_d), pm_g = __ballot(park && !park_d);
+			const uint32_t rank_d = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm_d >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm_d, 0u));
+			const uint32_t rank_g = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm_g >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm_g, 0u));
+			const uint32_t e = lobe_push_entry(park_d, n_d, n_g, park_d ? rank_d : rank_g, kSortSlots);
 			if (park) {
 				stack.frag[0][e] = frag.x, stack.frag[1][e] = frag.y, stack.frag[2][e] = frag.z;
-				stack.normal[0][e] = normal.x, stack.normal[1][e] = normal.y, stack.normal[2][e] = normal.z;
 				stack.T[0][e] = T.x, stack.T[1][e] = T.y, stack.T[2][e] = T.z;
 				stack.state[e] = (uint32_t)oi | (rng.block << 16); // (fewer than 2^16 objects fit the LDS; a lens loop runs at most 4096 rounds)
 				stack.lobe_bits[e] = rng.lobe_bits | (depth << 24), stack.item[e] = item;
 			}
-			n_hit += (uint32_t)__popcll(pm);
+			n_d += (uint32_t)__popcll(pm_d), n_g += (uint32_t)__popcll(pm_g);
+#if RMD_DIAG
+			if ((Pt.debug_flags & 8u) && Pt.debug_counters && lane == 0u) // [41] / [42]: hits parked — diffuse / GGX (each is shaded once: [38] / [40])
+				atomicAdd(&Pt.debug_counters[41], (unsigned long long)__popcll(pm_d)), atomicAdd(&Pt.debug_counters[42], (unsigned long long)__popcll(pm_g));
+#endif
 			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 			__builtin_amdgcn_wave_barrier();
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
