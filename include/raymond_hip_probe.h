@@ -100,6 +100,17 @@ rmd_status rmd_probe_launch_plan(uint32_t mode, uint32_t grid, size_t n, const u
  * instantiation's unqueued kernels, the queued wave's area, waves of its persistent workgroup, waves of a one-wave-per-item workgroup of a scene with
  * grids, the spheres kernel's per-wave pool bytes (admission), the grids' mask budget bytes. */
 rmd_status rmd_probe_launch_sizes(uint32_t mode, uint32_t grid, uint64_t *out8);
+/* Host only (no device needed): the two-part work list of the role-sorted spheres kernel's split launches (raymond_amd/csrc/work_list.hpp; api.cpp:
+ * plan_work_list).  Per entry in4 = wave slots, wave tiles, samples of the pass, the uniform rule's items per wave tile; out3 = n_whole (the wave tiles
+ * that are one item each, first in the list), n_tail (the others) and k_tail (items per tail tile).  With ctx not null the plan is the one that
+ * context — its wave slots, its tunables, a scene without grids — gives a pass of a render of that many wave tiles and samples: in4's first word is
+ * then the samples of the pass asked about (0 = the render is one pass) and its last word is ignored.  tests/test_work_list.py walks the plans. */
+rmd_status rmd_probe_work_plan(const rmd_context *ctx, size_t n, const uint32_t *in4, uint32_t *out3);
+/* Host only: items first .. first + n - 1 of the list (n_tiles, n_whole, k_tail) of a pass of sample_count samples, by the mapping the kernel itself
+ * evaluates (work_list.hpp: work_list_item): out5 = wave tile (n_tiles past the end of the list), first sample, sample count, parts of this tile,
+ * 1 for a whole item; *n_items = the items of the list. */
+rmd_status rmd_probe_work_items(uint32_t n_tiles, uint32_t n_whole, uint32_t k_tail, uint32_t sample_count, uint32_t first, size_t n, uint32_t *out5,
+                                uint32_t *n_items);
 /* Host only: the LDS layout of an uploaded scene — objects in the table, grids, and words of the grids' occupancy masks. */
 rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total);
 /* Host only: the device scratch block a denoise entry point carves (raymond_amd/csrc/denoise_host.hpp: denoise_scratch_layout — the function the entry

@@ -61,7 +61,14 @@ rmd_status context_create(int32_t device, hipStream_t stream, bool own_stream, r
 		const char *form = std::getenv("RMD_LAUNCH_FORM");
 		ctx->tunable[RMD_TUNE_LAUNCH_FORM] = !form ? 0 : (std::strcmp(form, "per-item") == 0 || std::strcmp(form, "1") == 0) ? 1 : (std::strcmp(form, "persistent") == 0 || std::strcmp(form, "2") == 0) ? 2 : 0;
 #if RMD_DIAG
-		ctx->debug_flags = (uint32_t)env_int("RMD_DEBUG"); // DIAG builds only: 1 | 2 are timing ablations that change results, 8 | 16 count events, 256 fails the path queues' allocation
+		ctx->debug_flags = (uint32_t)env_int("RMD_DEBUG"); // DIAG builds only: 1 | 2 are timing ablations that change results, 8 | 16 count events, 256 fails the path queues' allocation, 1024 makes the work list's tail 4 wave tiles
+#endif
+#if RMD_WORK_LIST_SWEEP
+		// sweep builds only (tools/work_list_sweep.py): RMD_WORK_LIST = "<tail tiles per wave slot, in halves>,<parts of a tail tile>"; 0 halves = no whole items
+		if (const char *v = std::getenv("RMD_WORK_LIST")) {
+			unsigned a = 0, b = 0;
+			if (std::sscanf(v, "%u,%u", &a, &b) == 2 && b >= 1u) ctx->tail_x2 = a, ctx->tail_parts = b;
+		}
 #endif
 	}
 	if (hipEventCreate(&ctx->ev_start) != hipSuccess || hipEventCreate(&ctx->ev_stop) != hipSuccess)
@@ -655,7 +662,8 @@ rmd_status rmd_framebuffer_upload(rmd_context *ctx, const double *host, double *
 // scratch buffer, added to the pixels in sample order afterwards (by the wave that finishes a tile last, or by sum_kernel) — bit-identical
 // to the unsplit launch (tests/test_gpu_parity.py::test_sample_split_is_bit_exact).  It buys enough items to level the launch over 256 CUs
 // when wave tiles are few (an N-way shard) or very uneven (a mesh), and lanes that draw (pixel, sample) pairs from the item's pool instead
-// of idling until the tile's longest pixel is done.  RMD_TUNE_SAMPLE_SPLIT forces K.
+// of idling until the tile's longest pixel is done.  RMD_TUNE_SAMPLE_SPLIT forces K.  In automatic mode the persistent launches of the spheres kernel
+// split only the END of their list this way and run the tiles before it as one item each (plan_work_list below): K is then the tail's.
 // `buffered` (out): whether the launch runs the tiles-buffered instantiation.  A split launch (K > 1) always does; a launch too short to split
 // does too — as ONE item per wave tile — in scenes with grids (the direct instantiation of the mesh kernel is the slower one at any size: C3 at
 // 4 spp 5.6 ms direct, 4.5 ms as two items of 2 samples; progressive passes of a host scheduler are such launches) and, from kSortedMinSamples
@@ -691,6 +699,63 @@ static uint32_t choose_split(const rmd_context *ctx, bool has_grid, uint32_t n_w
 	if (buffered) *buffered = k > 1u || may_buffer_unsplit;
 	return k;
 }
+
+extern "C++" {
+namespace rmd {
+// The spheres kernel's work list (work_list.hpp): which wave tiles run as ONE item.  What an item costs beside its samples — a drain of its last <= 168
+// parked hits in ever smaller trips, the tile's candidate set (about 1,270 instructions), an agent-scope release that writes back the XCD's L2, an
+// atomic, and a wave that issues nothing meanwhile — buys an even END of the launch and nothing before it.  So the tail of the list alone is split:
+//   n_tail   = tail_x2 / 2 wave tiles per wave slot (kTailTilesPerSlotX2: c = 2.5), the LAST tiles of the list; a list with no more tiles than that (an
+//              8-way tile share, a small frame) is all tail and the launch is the uniform split it always was;
+//   k_tail   = the uniform rule's k (k_uniform: choose_split), or tail_parts (kTailParts = 4) where that is more and every part keeps min_samples samples;
+//   n_whole  = the other tiles, first in the list, all samples of the pass each.
+// Why 2.5: a whole item cannot be divided, so the one that starts LAST must end before the tail does — the tail has to last as long as the list's
+// longest tile takes, and on C2 a tile through the spheres takes about 2.5 times the mean tile.  A shorter tail works only while the long tiles
+// happen to lie early in the list.  Measured with tools/work_list_sweep.py, C2 at 500 spp, kernel ms, c = 0 (uniform) / 1 / 1.5 / 2 / 2.5 / 3 —
+//   full frame (7.9 tiles a slot)   40.6 / 39.7 / 39.1 .. 39.6 / 39.1 .. 39.4 / 39.0 .. 39.1 / 39.2 .. 39.5   (k_tail 3 .. 5 alike, 6 and 7 up to 1.5 ms slower)
+//   2-way share (4.0)               23.1 / 23.1 / 23.3 / 21.0 / 21.3 / 21.9        3-way (2.6)  15.5 / 16.9 / 16.4 / 14.5 / 15.0 / all tail
+//   4-way share (2.0)               11.6 / 13.7 / 11.0 / all tail from 2 on        8-way: all tail at every c; at 200 spp 19.0 / - / 16.3 / 16.7 / 16.9 / 17.0
+// — at c = 1 and 1.5 the shares whose long tiles start late (2-, 3-, 4-way) are no faster or up to 18 % SLOWER than the uniform split; from 2 on none is.
+// Whole items are planned only for passes of at most kWholeMaxSamples = 2^20 samples (a whole item's pool indices, sample_count x 64 < 2^26, and its
+// trip bound keep six bits of room in their 32-bit fields).  n_tail_forced (DIAG builds: RMD_DEBUG bit 1024): a tail of that many tiles whatever the slots.
+WorkPlan plan_work_list(uint32_t wave_slots, uint32_t n_tiles, uint32_t sample_count, uint32_t k_uniform, uint32_t min_samples, uint32_t tail_x2, uint32_t tail_parts,
+                        uint32_t n_tail_forced) {
+	WorkPlan w{0u, n_tiles, k_uniform < 1u ? 1u : k_uniform};
+	if (tail_x2 == 0u || sample_count > kWholeMaxSamples) return w;
+	const uint64_t n_tail = n_tail_forced ? (uint64_t)n_tail_forced : ((uint64_t)tail_x2 * wave_slots + 1u) / 2u;
+	if ((uint64_t)n_tiles <= n_tail) return w; // few tiles: everything is tail
+	uint32_t k = tail_parts > 64u ? 64u : tail_parts;
+	if (min_samples < 1u) min_samples = 1u;
+	if (k > sample_count / min_samples) k = sample_count / min_samples;
+	if (k < w.k_tail) k = w.k_tail;
+	if ((uint64_t)(n_tiles - n_tail) + n_tail * k > 0x7FFFFFFFull) return w; // work items are indexed in 32 bits (never: n_tail * 64 < 2^31 - n_tiles for any device)
+	w.n_whole = n_tiles - (uint32_t)n_tail, w.n_tail = (uint32_t)n_tail, w.k_tail = k;
+	return w;
+}
+// One pass's list: the uniform split of choose_split, and for a buffered persistent pass of a scene without grids in automatic mode the two-part
+// list.  A forced RMD_TUNE_SAMPLE_SPLIT, the one-wave-per-item form and every scene with grids keep the uniform split (n_whole = 0).
+static WorkPlan pass_work_plan(const rmd_context *ctx, bool has_grid, bool split_launch, bool buffered, bool persistent, uint32_t n_tiles, uint32_t sample_count,
+                               bool *persistent_pass) {
+	WorkPlan w{0u, n_tiles, split_launch ? choose_split(ctx, has_grid, n_tiles, sample_count) : 1u};
+	// (a launch with fewer work items than the device has wave slots spreads better as one wave per item)
+	*persistent_pass = persistent && ((uint64_t)n_tiles * w.k_tail >= ctx->wave_slots || ctx->tunable[RMD_TUNE_LAUNCH_FORM] == 2);
+	if (!buffered || has_grid || !*persistent_pass || ctx->tunable[RMD_TUNE_SAMPLE_SPLIT] > 0) return w;
+	uint32_t min_samples = kTailMinSamples, forced_tail = 0u;
+	if (ctx->tunable[RMD_TUNE_SPLIT_MIN_SAMPLES] > 0) min_samples = (uint32_t)std::min<int64_t>(ctx->tunable[RMD_TUNE_SPLIT_MIN_SAMPLES], 1 << 20);
+#if RMD_DIAG
+	if (ctx->debug_flags & 1024u) forced_tail = 4u; // both kinds of item in a frame of a few dozen wave tiles (tests/test_gpu_whole_tile_items.py)
+#endif
+	return plan_work_list(ctx->wave_slots, n_tiles, sample_count, w.k_tail, min_samples, ctx->tail_x2, ctx->tail_parts, forced_tail);
+}
+// the list this context gives a pass of pass_samples samples of a render of n_tiles wave tiles and sample_count samples, provided the scratch for the
+// render's passes can be had (probe.cpp: rmd_probe_work_plan) — the render decides whether it is buffered, the pass its own list
+WorkPlan context_work_plan(const rmd_context *ctx, bool has_grid, uint32_t n_tiles, uint32_t sample_count, uint32_t pass_samples) {
+	bool buffered = false, persistent_pass = false;
+	const uint32_t split = choose_split(ctx, has_grid, n_tiles, sample_count, &buffered);
+	return pass_work_plan(ctx, has_grid, split > 1u, buffered, ctx->tunable[RMD_TUNE_LAUNCH_FORM] != 1, n_tiles, pass_samples, &persistent_pass);
+}
+} // namespace rmd
+} // extern "C++"
 
 static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
                                           const rmd_tile_rect *tiles, uint32_t n_tiles, double *accum_dev, double *accum_sq_dev) {
@@ -765,7 +830,9 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		rmd::RenderParams Q = P;
 		Q.sample_begin = settings->sample_begin + (uint32_t)done;
 		Q.sample_count = settings->sample_count - done < per_pass ? (uint32_t)(settings->sample_count - done) : per_pass;
-		Q.split_k = split > 1u ? choose_split(ctx, scene->n_grids != 0, P.n_work, Q.sample_count) : 1u;
+		bool persistent_pass = false;
+		const rmd::WorkPlan list = rmd::pass_work_plan(ctx, scene->n_grids != 0, split > 1u, buffered, persistent, P.n_work, Q.sample_count, &persistent_pass);
+		Q.split_k = list.k_tail, Q.n_whole = list.n_whole;
 		Q.sample_magic = Q.sample_count > 1u ? ~0ull / Q.sample_count + 1ull : 0ull; // floor(2^64 / d) + 1 for d >= 2 (2^64 - 1 and 2^64 have the same quotient unless d divides 2^64: then + 1 overshoots by one and is still exact for dividends below 2^32)
 		Q.buffered = buffered ? 1u : 0u;
 		{ // split launches of grid scenes chain their work items (launch.hpp: kChainMaxSamples; RMD_TUNE_CHAIN_ITEMS: 1 = never, 2 = always)
@@ -773,8 +840,6 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 			Q.chain_items = (buffered && scene->n_grids != 0u && (force == 2 || (force == 0 && Q.sample_count <= rmd::kChainMaxSamples))) ? 1u : 0u;
 		}
 		Q.sample_buf = ctx->sample_buf.as<double>();
-		// (a launch with fewer work items than the device has wave slots spreads better as one wave per item)
-		const bool persistent_pass = persistent && ((uint64_t)P.n_work * Q.split_k >= ctx->wave_slots || ctx->tunable[RMD_TUNE_LAUNCH_FORM] == 2);
 		if (persistent_pass) {
 			RMD_HIP(ctx, hipMemsetAsync(ctx->work_counter.as<void>(), 0, sizeof(uint32_t), ctx->stream));
 			Q.work_counter = ctx->work_counter.as<uint32_t>();

@@ -130,7 +130,8 @@ struct RenderParams {
 	                                    // tile's primary rays can hit (primary_candidates.hpp has the conditions and the argument; api.cpp: make_params sets it)
 	uint32_t buffered;                  // 1: the tiles-buffered instantiation (pooled (pixel, sample) hand-out, per-sample scratch, ordered sum) — also with split_k = 1
 	uint32_t axis_pairs;                // three 10-bit fields, one per axis k: index + 1 of the later plane of THE pair of opposite planes with normals +-e_k that is
-	uint32_t _pad2;                     //   tested ahead of the object loop (kObjAxisPair), 0 = none
+	uint32_t n_whole;                   //   tested ahead of the object loop (kObjAxisPair), 0 = none.  n_whole: the role-sorted spheres kernel's two-part work list
+	                                    //   (work_list.hpp) — wave tiles 0 .. n_whole - 1 are one item each, the others split_k items each; 0 = the uniform split
 	uint32_t *fault;                    // the context's fault words (host memory mapped into the device's address space; kFault*): a wave whose loop runs past
 	                                    // its bound reports here, poisons work_counter so that the launch drains, and leaves (render_kernel.hpp: report_fault)
 	unsigned char *queue_buf;           // split launches of grid scenes in the persistent form (render_kernel.hpp: render_wave_queued): the waves' path queues in

@@ -19,6 +19,7 @@
 
 #include "device_types.hpp"
 #include "primary_candidates.hpp"
+#include "work_list.hpp"
 
 // The one mapping of a failed HIP call to a status: returns from the calling function with the call's text and HIP's own.
 #define RMD_HIP(ctx, call)                                                                                      \
@@ -103,6 +104,7 @@ struct rmd_context {
 	// context is created; none of them changes a result.
 	int64_t tunable[RMD_TUNE_COUNT] = {};
 	uint32_t debug_flags = 0; // RMD_DEBUG, honoured by DIAG builds only
+	uint32_t tail_x2 = rmd::kTailTilesPerSlotX2, tail_parts = rmd::kTailParts; // the spheres kernel's work list (api.cpp: plan_work_list); only a sweep build changes them
 	rmd_launch_info last_launch = {}; // rmd_last_launch_info
 	// Waits for both streams, then destroys them, the events and the fault words; the buffers above are freed after that (api.cpp).
 	~rmd_context();
@@ -247,6 +249,10 @@ bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t wid
 rmd_status check_fault(rmd_context *ctx);
 RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st);
 bool primary_cull_allowed(const RenderParams &P);
+// The role-sorted spheres kernel's two-part work list (api.cpp, beside choose_split; work_list.hpp has the mapping the kernel shares)
+WorkPlan plan_work_list(uint32_t wave_slots, uint32_t n_tiles, uint32_t sample_count, uint32_t k_uniform, uint32_t min_samples = kTailMinSamples,
+                        uint32_t tail_x2 = kTailTilesPerSlotX2, uint32_t tail_parts = kTailParts, uint32_t n_tail_forced = 0u);
+WorkPlan context_work_plan(const rmd_context *ctx, bool has_grid, uint32_t n_tiles, uint32_t sample_count, uint32_t pass_samples);
 // The host half of rmd_scene_create (api.cpp), also for the host-only probe of the primary rays' candidate sets (probe.cpp)
 struct SceneObjects {
 	std::vector<DevObject> objs;

@@ -199,7 +199,7 @@ hipError_t launch_render_tiles(hipStream_t stream, const RenderParams &P, const 
                                const WaveTile *wave_tiles, double *accum, uint32_t n_cus, LaunchShape *shape, double *accum_sq) {
 	if (P.n_work == 0) return hipSuccess;
 	const bool buffered = P.buffered != 0u;
-	const uint32_t n_waves = P.n_work * (buffered ? P.split_k : 1u);
+	const uint32_t n_waves = buffered ? work_list_items(P.n_work, P.n_whole, P.split_k) : P.n_work;
 	hipError_t e;
 	if (P.n_grids) e = buffered ? launch_render<kModeTilesBuffered, true>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape)
 	                            : launch_render<kModeTiles, true>(stream, P, objs, grids, wave_tiles, n_waves, accum, nullptr, nullptr, n_cus, shape, accum_sq);

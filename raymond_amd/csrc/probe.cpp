@@ -285,6 +285,28 @@ rmd_status rmd_probe_launch_plan(uint32_t mode, uint32_t grid, size_t n, const u
 	return RMD_OK;
 }
 
+rmd_status rmd_probe_work_plan(const rmd_context *ctx, size_t n, const uint32_t *in4, uint32_t *out3) {
+	if (n != 0 && (!in4 || !out3)) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	for (size_t i = 0; i < n; i++) {
+		const uint32_t *a = in4 + i * 4;
+		const rmd::WorkPlan w = ctx ? rmd::context_work_plan(ctx, false, a[1], a[2], a[0] ? a[0] : a[2]) : rmd::plan_work_list(a[0], a[1], a[2], a[3]);
+		out3[i * 3] = w.n_whole, out3[i * 3 + 1] = w.n_tail, out3[i * 3 + 2] = w.k_tail;
+	}
+	return RMD_OK;
+}
+
+rmd_status rmd_probe_work_items(uint32_t n_tiles, uint32_t n_whole, uint32_t k_tail, uint32_t sample_count, uint32_t first, size_t n, uint32_t *out5,
+                                uint32_t *n_items) {
+	if (n_whole > n_tiles || k_tail == 0u || !n_items || (n != 0 && !out5)) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	*n_items = rmd::work_list_items(n_tiles, n_whole, k_tail);
+	for (size_t i = 0; i < n; i++) {
+		const rmd::WorkItem w = rmd::work_list_item(first + (uint32_t)i, n_tiles, n_whole, k_tail, sample_count);
+		uint32_t *o = out5 + i * 5;
+		o[0] = w.tile, o[1] = w.first, o[2] = w.count, o[3] = w.parts, o[4] = w.whole;
+	}
+	return RMD_OK;
+}
+
 rmd_status rmd_probe_launch_sizes(uint32_t mode, uint32_t grid, uint64_t *out8) {
 	if (mode > 2u || grid > 1u || !out8) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
 	rmd::render_lds_sizes((int)mode, grid != 0u, out8);

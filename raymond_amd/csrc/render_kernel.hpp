@@ -9,6 +9,7 @@
 #include "lobe_trips.hpp"
 #include "primary_candidates.hpp"
 #include "scene_split.hpp"
+#include "work_list.hpp"
 
 namespace rmd {
 
@@ -158,15 +159,31 @@ RMD_DEV void store_sample(RMD_GLOBAL double *dst, V3 L) { dst[0] = L.x, dst[1] =
 // the reads (bandwidth) overlap the other waves' arithmetic; as a kernel of its own the sum cost 5.5 ms per 1080p / 500 spp frame.  Release: an
 // agent-scope fence writes this wave's sample stores back before its count; acquire: the last wave invalidates its caches before it reads.
 // MOM (rmd_render_tiles_moments): the same pass adds each sample's square to out_sq from the values it has loaded anyway.
+// `whole` (work_list.hpp: a whole item — the wave has computed ALL samples of its tile): no agent-scope release and no count.  The wave waits for
+// its own stores and adds what it stored; a release / acquire pair at wavefront scope (the stack push's pattern) is the whole protocol, because
+//   - the sectors of this tile are written by this wave alone in this launch (no other item names the tile), and read once, by this wave;
+//   - the CU's L1 is write-through: once the stores have been acknowledged (vmcnt = 0) the samples are in the XCD's L2, which the loads below
+//     reach from the same CU, so neither side depends on another cache;
+//   - no line of that region can be resident in the L1 from before the stores: nothing of this launch has read it, a tile's region is a whole
+//     number of lines of its own (sample_count x 2 KiB from a 2 KiB boundary), and a launch starts with its L1 invalidated.
+// What an item costs at its end is then the loop below — no write-back of the L2's dirty lines, no wait for one.
 template <bool MOM = false>
-RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, uint32_t wt, uint32_t lane, double *__restrict__ out, double *__restrict__ out_sq = nullptr) {
+RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, uint32_t wt, uint32_t parts, bool whole, uint32_t lane, double *__restrict__ out,
+                                 double *__restrict__ out_sq = nullptr) {
 	if (P.tile_done == nullptr || wt >= P.n_work) return;
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // this wave's samples leave the XCD's L2 before its count is seen
-	uint32_t before = 0;
-	if (lane == 0u) before = __hip_atomic_fetch_add(P.tile_done + wt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	before = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
-	if (before + 1u != P.split_k) return;
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	if (whole) {
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+		__builtin_amdgcn_s_waitcnt(0); // every counter at zero: the wave's sample stores have been acknowledged
+		__builtin_amdgcn_wave_barrier();
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+	} else {
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); // this wave's samples leave the XCD's L2 before its count is seen
+		uint32_t before = 0;
+		if (lane == 0u) before = __hip_atomic_fetch_add(P.tile_done + wt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		before = (uint32_t)__builtin_amdgcn_readfirstlane((int)before);
+		if (before + 1u != parts) return;
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+	}
 	const uint32_t lx = lane & 7u, ly = lane >> 3;
 	if (lx < tile.w && ly < tile.h) {
 		const size_t pix = ((size_t)(tile.x0 + lx) + (size_t)(tile.y0 + ly) * P.W) * 3;
@@ -649,7 +666,7 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 	}
 #endif
 #undef RMD_TSTAMP
-	if constexpr (to_buffer && !GRID) finish_sample_range(P, tile, wt, lane, out); // (mesh scenes keep sum_kernel: api.cpp)
+	if constexpr (to_buffer && !GRID) finish_sample_range(P, tile, wt, P.split_k, false, lane, out); // (mesh scenes keep sum_kernel: api.cpp)
 	if (writes && !to_buffer && !acc_in_memory) {
 		out[out_index + 0] = acc.x;
 		out[out_index + 1] = acc.y;
@@ -745,13 +762,12 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 	const uint32_t lane = threadIdx.x & 63u;
 	HitStack &stack = *reinterpret_cast<HitStack *>(wave_lds);
 	WalkScratch *no_scratch = nullptr; // (scene_intersect_wave<false> never touches it)
-	const uint32_t wt = work_item / P.split_k, part = work_item % P.split_k;
+	// the item's wave tile and samples (work_list.hpp): a whole item — all samples of its tile, pool_first = 0 — or one of a tail tile's split_k parts
+	const WorkItem wi = work_list_item(work_item, P.n_work, P.n_whole, P.split_k, P.sample_count);
+	const uint32_t wt = wi.tile;
 	const bool have = wt < P.n_work;
 	const WaveTile tile = reinterpret_cast<const WaveTile *>(work)[have ? wt : 0];
-	const uint32_t per_part = (P.sample_count + P.split_k - 1u) / P.split_k;
-	const uint32_t s_lo = part * per_part < P.sample_count ? part * per_part : P.sample_count;
-	const uint32_t s_hi = s_lo + per_part < P.sample_count ? s_lo + per_part : P.sample_count;
-	const uint32_t pool_first = s_lo, pool_items = have ? (s_hi - s_lo) * 64u : 0u;
+	const uint32_t pool_first = wi.first, pool_items = wi.count * 64u; // (whole items: < 2^26, work_list.hpp: kWholeMaxSamples)
 	if (P.bounce_limit == 0u) return; // (such launches are not made: api.cpp)
 	const V3 cam_pos = ld3(P.cam_pos);
 
@@ -953,7 +969,8 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		}
 	}
-	finish_sample_range<MOM>(P, tile, wt, lane, out, out_sq);
+	// (whether the item is a whole one is asked of the launch parameters again, not carried across the trip loop: work_list_item's `whole` and `parts`)
+	finish_sample_range<MOM>(P, tile, wt, P.split_k, work_item < P.n_whole, lane, out, out_sq);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1478,7 +1495,8 @@ RMD_DEV void render_kernel_body(const RenderParams &P, const DevObject *__restri
 	const uint32_t *lds_masks = P.mask_words_total ? lmasks : nullptr;
 	if constexpr (PERSIST) {
 		static_assert(MODE != kModeList, "list launches are not persistent");
-		const uint32_t n_items = P.n_work * (MODE == kModeTilesBuffered ? P.split_k : 1u);
+		// (the role-sorted spheres kernel's list may have two parts: work_list.hpp; the other instantiations are compiled as they were)
+		const uint32_t n_items = kSortedTrips<MODE, GRID> ? work_list_items(P.n_work, P.n_whole, P.split_k) : P.n_work * (MODE == kModeTilesBuffered ? P.split_k : 1u);
 		// The work loop's bound.  The counter only grows, so every draw of a wave is larger than its last one and the draws that pass the test
 		// below are fewer than n_items: the loop ends by itself.  What is checked is the premise — a draw that is NOT larger than the wave's last
 		// (the counter was overwritten: items would be rendered twice, for ever) is a fault.  The last draw + 1 lives in the wave's LDS head,

@@ -36,6 +36,8 @@ _SIGS = {
     "rmd_probe_primary_candidates": [_P(abi.Camera), _P(abi.Settings), _P(abi.Object), C.c_uint32, C.c_uint32, C.c_int64, _sz, _vp, _vp, _vp],
     "rmd_probe_launch_plan": [C.c_uint32, C.c_uint32, _sz, _vp, _vp],
     "rmd_probe_launch_sizes": [C.c_uint32, C.c_uint32, _vp],
+    "rmd_probe_work_plan": [_vp, _sz, _vp, _vp],
+    "rmd_probe_work_items": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _vp, _P(C.c_uint32)],
     "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
     "rmd_probe_denoise_scratch": [C.c_uint32] * 6 + [C.c_uint64, _vp, _P(C.c_uint64)],
 }
@@ -248,6 +250,34 @@ def launch_sizes(mode, grid):
     out = np.zeros(8, dtype=np.uint64)
     _host_check(L.rmd_probe_launch_sizes(mode, int(grid), _p(out)), "rmd_probe_launch_sizes")
     return {k: int(v) for k, v in zip(SIZE_FIELDS, out)}
+
+
+def work_plan(wave_slots, n_tiles, sample_count, k_uniform, ctx=None, pass_samples=0):
+    """Host only: the two-part work list of the spheres kernel's split launches -> (n_whole, n_tail, k_tail) int64 arrays; the inputs broadcast
+    against each other.  With a render.Context the plan is the one that context gives a pass of pass_samples samples (0: the only pass) of a render
+    of n_tiles wave tiles and sample_count samples of a scene without grids (wave_slots and k_uniform are ignored).  api: rmd_probe_work_plan."""
+    L = _L()
+    if ctx is not None:
+        wave_slots = pass_samples
+    cols = np.broadcast_arrays(*(np.asarray(a, dtype=np.int64) for a in (wave_slots, n_tiles, sample_count, k_uniform)))
+    inp = np.ascontiguousarray(np.stack([c.ravel() for c in cols], axis=1).astype(np.uint32))
+    out = np.zeros((inp.shape[0], 3), dtype=np.uint32)
+    _host_check(L.rmd_probe_work_plan(ctx.handle if ctx is not None else None, inp.shape[0], _p(inp), _p(out)), "rmd_probe_work_plan")
+    return tuple(out[:, i].astype(np.int64).reshape(cols[0].shape) for i in range(3))
+
+
+WORK_ITEM_FIELDS = ("tile", "first", "count", "parts", "whole")
+
+
+def work_items(n_tiles, n_whole, k_tail, sample_count, extra=0):
+    """Host only: every item of the list, and `extra` numbers past its end, by the mapping the kernel evaluates -> (int64 array [items + extra, 5]
+    in the order of WORK_ITEM_FIELDS, the number of items).  api: rmd_probe_work_items."""
+    L = _L()
+    n_items = C.c_uint32()
+    _host_check(L.rmd_probe_work_items(n_tiles, n_whole, k_tail, sample_count, 0, 0, None, C.byref(n_items)), "rmd_probe_work_items")
+    out = np.zeros((n_items.value + extra, 5), dtype=np.uint32)
+    _host_check(L.rmd_probe_work_items(n_tiles, n_whole, k_tail, sample_count, 0, out.shape[0], _p(out), C.byref(n_items)), "rmd_probe_work_items")
+    return out.astype(np.int64), n_items.value
 
 
 def scene_layout(dscene):
