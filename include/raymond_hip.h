@@ -60,6 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
+	                                 rmd_resolve_tonemap_tiles,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
@@ -734,6 +735,20 @@ rmd_status rmd_last_launch_info(const rmd_context *ctx, rmd_launch_info *out);
  * the device evaluates every pixel and the few whose value lies within 1e-7 of a truncation boundary are recomputed on the host. */
 rmd_status rmd_resolve_tonemap(rmd_context *ctx, const double *accum_dev, uint32_t width, uint32_t height,
                                uint32_t sample_count, double exposure, double gamma, uint8_t *out_rgb8_host);
+/* The same stage over tile rectangles, each at its own sample count, into a PACKED host buffer of bytes: rect j's pixels row-major, width_j *
+ * height_j * 3 bytes, one rect after the other in the order of `rects` — rmd_framebuffer_download_tiles's layout in bytes.  What a render loop needs
+ * to show the frame while it renders: live tiles at the current count, tiles that finished early at theirs, one tile's 8-bit pixels without the frame's.
+ * For a pixel of rect j and channel c: s = accum_dev's sum — plus accum2_dev's, in one rounded addition, when accum2_dev is not NULL (a dual-buffer
+ * render's two halves; the count is then n_A + n_B) —, p = s / (double)rect_sample_counts[j], and the byte is rmd_resolve_tonemap's, with the same
+ * contract: byte for byte what the host's libm gives.  A count of 0 is allowed (zero sums: 0 / 0, a black pixel).  Rects may have any size and
+ * alignment inside the width x height frame and may overlap; a rect without pixels contributes no bytes; n_rects = 0 writes nothing and returns RMD_OK.
+ * RMD_ERR_INVALID_ARGUMENT, checked before the device is touched and with the output untouched: accum_dev NULL, width or height 0, rects or
+ * rect_sample_counts NULL with n_rects > 0, out NULL while the rects hold pixels, a rect outside the frame, accum2_dev overlapping accum_dev.
+ * RMD_ERR_UNSUPPORTED: more than 2^32 - 1 packed pixels.  Synchronous; reports an earlier device fault like rmd_resolve_tonemap.  The cost follows
+ * the packed pixels, whatever the number and shape of the rects; the call's device scratch stays on the context and grows on demand. */
+rmd_status rmd_resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
+                                     const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, double exposure, double gamma,
+                                     uint8_t *out_rgb8_host_packed);
 
 /* ---- multi-GPU (no reference counterpart; the reference has no collectives) ---- */
 #define RMD_COMM_ID_BYTES 128

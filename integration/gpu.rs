@@ -120,6 +120,10 @@ extern "C" {
                                       err_dev: *mut f64) -> i32;
     fn rmd_tile_error_dual(ctx: *mut rmd_context, err_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, n_rects: u32,
                            out_err_host: *mut f64) -> i32;
+    // the output stage over tile rects, rect i at rect_sample_counts[i], into packed bytes in rmd_framebuffer_download_tiles's layout (accum2_dev: null, or
+    // a dual-buffer render's other half): what a FramePreview of the C++ mirror (raymond_amd/host: settings.preview_every) is made with
+    fn rmd_resolve_tonemap_tiles(ctx: *mut rmd_context, accum_dev: *const f64, accum2_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                                 rect_sample_counts: *const u32, n_rects: u32, exposure: f64, gamma: f64, out_rgb8_host_packed: *mut u8) -> i32;
 }
 
 /// One candidate of rmd_denoise_dual_select (include/raymond_hip.h: rmd_denoise_candidate); `reserved` is 0

@@ -11,6 +11,7 @@
 
 #include "internal.hpp"
 #include "launch.hpp"
+#include "resolve_tiles_host.hpp"
 
 using rmd::bind;
 
@@ -1241,6 +1242,102 @@ static rmd_status resolve_tonemap_impl(rmd_context *ctx, const double *accum_dev
 rmd_status rmd_resolve_tonemap(rmd_context *ctx, const double *accum_dev, uint32_t width, uint32_t height, uint32_t sample_count,
                                double exposure, double gamma, uint8_t *out_rgb8_host) {
 	return rmd::guarded(ctx, "rmd_resolve_tonemap", [&] { return resolve_tonemap_impl(ctx, accum_dev, width, height, sample_count, exposure, gamma, out_rgb8_host); });
+}
+
+// The same stage over tile rectangles, each at its own sample count, into rmd_framebuffer_download_tiles's layout (resolve_tiles.hip; the table and
+// the way back from a flagged packed pixel: resolve_tiles_host.hpp).  Scratch on the context: [rgb8: 3 P bytes, padded to 16][flag count: 16 bytes]
+// [flagged packed pixels: P words, padded to 16][runs].
+static rmd_status resolve_tonemap_tiles_impl(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
+                                             const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, double exposure, double gamma,
+                                             uint8_t *out) {
+	const char *name = "rmd_resolve_tonemap_tiles: ";
+	if (rmd_status s = bind(ctx)) return s;
+	if (!accum_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "bad argument");
+	const size_t frame_doubles = (size_t)width * height * 3;
+	const uintptr_t lo1 = reinterpret_cast<uintptr_t>(accum_dev), lo2 = reinterpret_cast<uintptr_t>(accum2_dev), frame_bytes = frame_doubles * sizeof(double);
+	if (accum2_dev && lo2 < lo1 + frame_bytes && lo1 < lo2 + frame_bytes)
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "accum2_dev overlaps accum_dev");
+	std::vector<uint64_t> first;
+	if (!rmd::resolve_first_pixels(rects, n_rects, width, height, first))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "tile rectangle outside the framebuffer");
+	const uint64_t n_pixels = first[n_rects];
+	if (n_pixels > 0xFFFFFFFFull) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, std::string(name) + "more than 2^32-1 packed pixels");
+	if (n_pixels == 0) return RMD_OK;
+	if (!out) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "null output for rects that hold pixels");
+	const std::vector<rmd::ResolveRun> runs = rmd::resolve_runs(rects, rect_sample_counts, n_rects, first);
+	if (runs.size() > 0x7FFFFFFFull) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, std::string(name) + "more than 2^31-1 workgroups");
+	const size_t rgb_bytes = ((size_t)n_pixels * 3 + 15) & ~(size_t)15, list_bytes = ((size_t)n_pixels * 4 + 15) & ~(size_t)15;
+	const size_t table_bytes = runs.size() * sizeof(rmd::ResolveRun);
+	// The stream is waited for before anything is enqueued (the call waits for the frame's renders in any case): the table's upload and the downloads
+	// below, which may go to pageable memory, are then made on an idle stream, as rmd_resolve_tonemap's are by every caller here
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	RMD_HIP(ctx, ctx->resolve_tiles_scratch.grow(rgb_bytes + 16 + list_bytes + table_bytes));
+	ctx->resolve_tiles_table.assign(reinterpret_cast<const unsigned char *>(runs.data()), reinterpret_cast<const unsigned char *>(runs.data()) + table_bytes);
+	uint8_t *d = ctx->resolve_tiles_scratch.as<uint8_t>();
+	uint32_t *d_count = reinterpret_cast<uint32_t *>(d + rgb_bytes), *d_list = reinterpret_cast<uint32_t *>(d + rgb_bytes + 16);
+	rmd::ResolveRun *d_runs = reinterpret_cast<rmd::ResolveRun *>(d + rgb_bytes + 16 + list_bytes);
+	const double inv_gamma = 1.0 / gamma;
+	uint32_t n_flagged = 0;
+	std::vector<uint32_t> list;
+	std::vector<double> px, px2;
+	hipError_t e = hipMemsetAsync(d_count, 0, 4, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_runs, ctx->resolve_tiles_table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = rmd::launch_resolve_tiles(ctx->stream, accum_dev, accum2_dev, width, d_runs, (uint32_t)runs.size(), exposure, inv_gamma, d, d_list, d_count);
+	if (e == hipSuccess) e = hipMemcpyAsync(out, d, (size_t)n_pixels * 3, hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(&n_flagged, d_count, 4, hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e == hipSuccess && n_flagged != 0) {
+		// as rmd_resolve_tonemap: the pixels whose byte an ulp of exp / pow could decide, recomputed with the host libm
+		list.resize(n_flagged);
+		e = hipMemcpy(list.data(), d_list, (size_t)n_flagged * 4, hipMemcpyDeviceToHost);
+		const bool whole = n_flagged > 1024u; // many: one download of the sums instead of a copy per pixel
+		if (e == hipSuccess && whole) {
+			px.resize(frame_doubles);
+			e = hipMemcpy(px.data(), accum_dev, frame_doubles * sizeof(double), hipMemcpyDeviceToHost);
+			if (e == hipSuccess && accum2_dev) {
+				px2.resize(frame_doubles);
+				e = hipMemcpy(px2.data(), accum2_dev, frame_doubles * sizeof(double), hipMemcpyDeviceToHost);
+			}
+		}
+		for (uint32_t k = 0; k < n_flagged && e == hipSuccess; k++) {
+			const uint64_t q = list[k];
+			const rmd::ResolvePixel at = rmd::resolve_locate(rects, n_rects, first, q);
+			const size_t i = ((size_t)at.x + (size_t)at.y * width) * 3;
+			double a[3], b[3] = {0.0, 0.0, 0.0};
+			if (whole) {
+				for (int c = 0; c < 3; c++) a[c] = px[i + c];
+				if (accum2_dev)
+					for (int c = 0; c < 3; c++) b[c] = px2[i + c];
+			} else {
+				e = hipMemcpy(a, accum_dev + i, sizeof(a), hipMemcpyDeviceToHost);
+				if (e == hipSuccess && accum2_dev) e = hipMemcpy(b, accum2_dev + i, sizeof(b), hipMemcpyDeviceToHost);
+			}
+			if (e != hipSuccess) break;
+			const double sc = (double)rect_sample_counts[at.rect];
+			double v[3];
+			bool ok = true;
+			for (int c = 0; c < 3; c++) {
+				const double s = accum2_dev ? a[c] + b[c] : a[c];
+				const double p = s / sc; // src/trace.rs:95
+				double tm = 1.0 - std::exp(p * -1.0 * exposure); // cli_old/src/main.rs:165
+				tm = std::pow(tm, inv_gamma);                    // :166
+				v[c] = tm * 255.0;
+				ok = ok && (v[c] > -1.0 && v[c] < 256.0); // :176 cast::<u8>()
+			}
+			for (int c = 0; c < 3; c++) out[q * 3 + c] = ok ? (uint8_t)v[c] : (uint8_t)0;
+		}
+	}
+	RMD_HIP(ctx, e);
+	return rmd::check_fault(ctx);
+}
+rmd_status rmd_resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
+                                     const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, double exposure, double gamma,
+                                     uint8_t *out_rgb8_host_packed) {
+	return rmd::guarded(ctx, "rmd_resolve_tonemap_tiles", [&] {
+		return resolve_tonemap_tiles_impl(ctx, accum_dev, accum2_dev, width, height, rects, rect_sample_counts, n_rects, exposure, gamma, out_rgb8_host_packed);
+	});
 }
 
 } // extern "C"

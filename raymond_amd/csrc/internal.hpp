@@ -86,6 +86,8 @@ struct rmd_context {
 	rmd::DeviceBuffer tile_done;      // split launches: finished waves per wave tile, a uint32 each (render_kernel.hpp)
 	rmd::DeviceBuffer debug_counters; // walk diagnostics (DIAG builds, RMD_DEBUG=8|16)
 	rmd::DeviceBuffer atrous_region_scratch; // rmd_denoise_atrous_dual_region's planes, count images and tables (api_denoise.cpp): grown when a call needs more, kept between calls
+	rmd::DeviceBuffer resolve_tiles_scratch; // rmd_resolve_tonemap_tiles's packed bytes, flag count, flag list and run table (api.cpp): grown when a call needs more, kept between calls
+	std::vector<unsigned char> resolve_tiles_table; // ... and the host copy of the table, alive until its upload has completed
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound
 	// writes here; the host looks after every wait for the stream (api.cpp: check_fault) — a plain host load, no copy
 	uint32_t *h_fault = nullptr, *d_fault = nullptr;

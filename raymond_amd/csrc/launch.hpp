@@ -190,6 +190,11 @@ hipError_t launch_sum(hipStream_t stream, const RenderParams &P, const WaveTile 
 constexpr double kTonemapGuard = 1e-7;
 hipError_t launch_tonemap(hipStream_t stream, const double *accum, uint8_t *rgb8, size_t n_pixels, double sample_count,
                           double exposure, double inv_gamma, uint32_t *flagged, uint32_t *n_flagged);
+// rmd_resolve_tonemap_tiles (resolve_tiles.hip): one workgroup per run of the table (resolve_tiles_host.hpp; device memory); rgb8: 3 bytes per packed
+// pixel, padded to 4, at a 4-byte boundary; flagged: one word per packed pixel, n_flagged: one zeroed word; accum2 may be null
+struct ResolveRun;
+hipError_t launch_resolve_tiles(hipStream_t stream, const double *accum, const double *accum2, uint32_t W, const ResolveRun *runs, uint32_t n_runs,
+                                double exposure, double inv_gamma, uint8_t *rgb8, uint32_t *flagged, uint32_t *n_flagged);
 hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in, int in_stride, double *out, int out_stride,
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,

@@ -23,12 +23,17 @@
 //                                                                      guided with --denoise-dual-features 1; the adaptive check calls it on the whole frame)
 //                                                                    [--denoise-dual-atrous-region 1] (needs --denoise-dual-atrous 1: the adaptive check calls
 //                                                                      rmd_denoise_atrous_dual_region over the live tiles instead; the same output)
+//                                                                    [--preview-every N --preview-prefix PATH [--preview-denoise 1] [--preview-exposure E]
+//                                                                     [--preview-gamma G]]   (needs --spi, one GPU: after every N-th pass that leaves the
+//                                                                      render unfinished the frame so far, tone-mapped on the GPU, is written to
+//                                                                      PATH_0001.ppm, PATH_0002.ppm, ...; --preview-denoise 1: the fast filter's frame)
+//                                                                    [--progress-tiles 0]   (no TileProgressed snapshot is made or downloaded)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
 //   raymond_cli project in.json dump|json Project::load (core/src/project.rs): flattened scene, or the re-serialised JSON
 //   raymond_cli tilemsg W H               a TileFinished message in the wire form of server/src/protocol.rs
-//   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1]
+//   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
 //                                         what a drop-in caller gets: one JSON line with the wall time of render_tiled -> last TileFinished
 //   (render also accepts `project:in.json` as its scene)
 #include <chrono>
@@ -46,19 +51,28 @@ using namespace raymond;
 // A consumer of a progressive render: every message through poll() (src/trace.rs:115-117) as it arrives — TileProgressed snapshots are counted,
 // TileFinished tiles are assembled into the image as await() would (:93-99).  (await() itself stops collecting at the first message that is not
 // TileFinished, :101-103: with snapshots of several workers in the channel it is only safe once they have been drained.)  With st.denoise the
-// finished tiles go through denoise_tiles on GPU 0 once the workers have left, as await() would.
+// finished tiles go through denoise_tiles on GPU 0 once the workers have left, as await() would.  FramePreview messages are written as
+// <preview_prefix>_0001.ppm, _0002.ppm, ... in the order they arrive (dropped without a prefix).
 static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size_t &progressed, double *last_finished_s = nullptr,
                                     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), const Scene *scene = nullptr,
-                                    std::vector<double> *feature_means = nullptr, std::vector<Tile> *finished_out = nullptr) {
+                                    std::vector<double> *feature_means = nullptr, std::vector<Tile> *finished_out = nullptr, const std::string &preview_prefix = "",
+                                    size_t *previews_out = nullptr) {
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	const size_t n_tiles = generate_tiles(W, H, st.tile_size).size();
 	std::vector<Tile> finished_tiles; // (zero-copy views of the download's block: taking them is cheap; the image is assembled afterwards)
 	finished_tiles.reserve(n_tiles);
+	size_t previews = 0;
 	for (;;) {
 		const bool done = handle.finished(); // read BEFORE the channel is drained: nothing is sent after the last worker has left
 		while (std::optional<Message> m = handle.poll()) {
 			if (m->kind == Message::TileProgressed) {
 				progressed++;
+				continue;
+			}
+			if (m->kind == Message::FramePreview) {
+				char number[32];
+				std::snprintf(number, sizeof(number), "_%04zu.ppm", ++previews);
+				if (!preview_prefix.empty()) write_ppm(preview_prefix + number, m->preview->rgb8, m->preview->width, m->preview->height);
 				continue;
 			}
 			finished_tiles.push_back(std::move(m->tile));
@@ -67,6 +81,7 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 		if (done || finished_tiles.size() == n_tiles) break;
 		std::this_thread::sleep_for(std::chrono::microseconds(100));
 	}
+	if (previews_out) *previews_out = previews;
 	if (st.denoise) {
 		handle.await(); // (its channel is drained: it only waits for the workers and rethrows a worker's error)
 		std::vector<Vector3> den = finished_tiles.empty() ? std::vector<Vector3>(W * H, Vector3{0, 0, 0})
@@ -155,15 +170,18 @@ int main(int argc, char **argv) {
 			st.tile_size = {32, 32};
 			for (int i = 8; i + 1 < argc; i += 2)
 				if (!std::strcmp(argv[i], "--end-black-paths")) st.end_black_paths = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--preview-every")) st.preview_every = (size_t)std::strtoull(argv[i + 1], nullptr, 10);
+				else if (!std::strcmp(argv[i], "--preview-denoise")) st.preview_denoise = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--progress-tiles")) st.progress_tiles = std::atoi(argv[i + 1]) != 0;
 			Scene scene = what == "spheres" ? reflective_spheres() : gold_dragon_standin(what.size() > 7 ? std::atoi(what.c_str() + 7) : 91);
 			{
 				Settings warm = st;
-				warm.camera_settings.backbuffer_width = warm.camera_settings.backbuffer_height = 64, warm.sample_count = 1, warm.samples_per_iteration = 0;
+				warm.camera_settings.backbuffer_width = warm.camera_settings.backbuffer_height = 64, warm.sample_count = 1, warm.samples_per_iteration = 0, warm.preview_every = 0, warm.preview_denoise = false;
 				render_tiled(reflective_spheres(), warm).await();
 			}
 			const int reps = 3;
 			double best = 1e30, best_setup = 0.0, best_await = 0.0;
-			size_t progressed = 0, finished_tiles = 0;
+			size_t progressed = 0, finished_tiles = 0, previews = 0;
 			double checksum = 0.0;
 			for (int rep = 0; rep < reps; rep++) {
 				progressed = 0;
@@ -172,7 +190,7 @@ int main(int argc, char **argv) {
 				// wall: call -> the last TileFinished message has ARRIVED at the consumer (every message taken through poll() as it comes); then the
 				// image is assembled as await() would (:93-99) and the workers' teardown is waited for
 				double secs = 0.0;
-				std::vector<Vector3> image = consume(handle, st, progressed, &secs, t0);
+				std::vector<Vector3> image = consume(handle, st, progressed, &secs, t0, nullptr, nullptr, nullptr, "", &previews);
 				const double secs_await = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 				if (secs < best) best = secs, best_setup = handle.setup_seconds(), best_await = secs_await;
 				checksum = 0.0;
@@ -184,14 +202,15 @@ int main(int argc, char **argv) {
 			const double n = (double)st.camera_settings.backbuffer_width * st.camera_settings.backbuffer_height * st.sample_count;
 			std::printf("{\"scene\": \"%s\", \"width\": %zu, \"height\": %zu, \"spp\": %zu, \"bounces\": %zu, \"samples_per_iteration\": %zu, \"wall_ms\": %.3f, "
 			            "\"setup_ms\": %.3f, \"image_assembled_ms\": %.3f, \"msamples_per_s\": %.2f, \"msamples_per_s_after_setup\": %.2f, \"tile_progressed_messages\": %zu, \"tiles\": %zu, "
-			            "\"mean_radiance_sum\": %.17g, \"runs\": %d}\n",
+			            "\"mean_radiance_sum\": %.17g, \"runs\": %d%s}\n",
 			            what.c_str(), st.camera_settings.backbuffer_width, st.camera_settings.backbuffer_height, st.sample_count, st.bounce_limit, st.samples_per_iteration,
-			            best * 1e3, best_setup * 1e3, best_await * 1e3, n / best / 1e6, n / (best - best_setup) / 1e6, progressed, finished_tiles, checksum, reps);
+			            best * 1e3, best_setup * 1e3, best_await * 1e3, n / best / 1e6, n / (best - best_setup) / 1e6, progressed, finished_tiles, checksum, reps,
+			            st.preview_every ? (", \"frame_previews\": " + std::to_string(previews)).c_str() : ""); // (a run without previews prints the line it always printed)
 			return 0;
 		}
 		if (argc >= 8 && !std::strcmp(argv[1], "render")) {
 			const auto t0 = std::chrono::steady_clock::now(); // cli_old/src/main.rs:36
-			std::string what = argv[2], raw, dump_features;
+			std::string what = argv[2], raw, dump_features, preview_prefix;
 			Settings st;
 			st.camera_settings.backbuffer_width = std::atoi(argv[3]);
 			st.camera_settings.backbuffer_height = std::atoi(argv[4]);
@@ -226,6 +245,12 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-atrous-levels")) st.denoise_atrous_levels = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--denoise-atrous-k")) st.denoise_atrous_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--dump-features")) dump_features = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--preview-every")) st.preview_every = (size_t)std::strtoull(argv[i + 1], nullptr, 10); // (render_tiled refuses it without --spi)
+				else if (!std::strcmp(argv[i], "--preview-prefix")) preview_prefix = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--preview-denoise")) st.preview_denoise = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--preview-exposure")) st.preview_exposure = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--preview-gamma")) st.preview_gamma = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--progress-tiles")) st.progress_tiles = std::atoi(argv[i + 1]) != 0;
 			}
 			Scene scene;
 			if (what == "spheres") scene = reflective_spheres();
@@ -239,7 +264,7 @@ int main(int argc, char **argv) {
 			std::vector<double> feature_means;
 			std::vector<Tile> finished;
 			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty();
-			std::vector<Vector3> image = by_consume ? consume(handle, st, progressed, nullptr, t0, &scene, dump_features.empty() ? nullptr : &feature_means, &finished)
+			std::vector<Vector3> image = by_consume ? consume(handle, st, progressed, nullptr, t0, &scene, dump_features.empty() ? nullptr : &feature_means, &finished, preview_prefix)
 			                                        : handle.await();
 			const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 			if (!dump_features.empty()) {

@@ -257,6 +257,7 @@ Scene Project::build_scene() const { // project.rs:38-57
 }
 
 std::string message_to_json(const Message &message) {
+	if (message.kind == Message::FramePreview) throw Error(RMD_ERR_INVALID_ARGUMENT, "message_to_json: a FramePreview has no wire form in server/src/protocol.rs");
 	const Tile &t = message.tile;
 	std::string out = std::string("{\"type\":\"") + (message.kind == Message::TileFinished ? "TileFinished" : "TileProgressed") + "\",\"data\":{";
 	out += "\"sample_count\":" + std::to_string(t.sample_count) + ",\"width\":" + std::to_string(t.width) + ",\"height\":" + std::to_string(t.height) +

@@ -180,6 +180,36 @@ struct BlockPool : std::enable_shared_from_this<BlockPool> {
 	}
 };
 
+void scatter_packed(const std::vector<rmd_tile_rect> &rects, const uint8_t *packed, size_t packed_bytes, size_t width, size_t height, std::vector<uint8_t> &frame) {
+	frame.resize(width * height * 3, 0);
+	size_t at = 0;
+	for (const rmd_tile_rect &r : rects) {
+		const size_t row = (size_t)r.width * 3;
+		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height || at + row * r.height > packed_bytes)
+			throw Error(RMD_ERR_INVALID_ARGUMENT, "scatter_tiles: a rect outside the frame, or fewer packed bytes than the rects hold");
+		for (size_t y = 0; y < r.height; y++, at += row) std::memcpy(frame.data() + ((size_t)r.left + ((size_t)r.top + y) * width) * 3, packed + at, row);
+	}
+}
+
+// One FramePreview message: the rects of `fb` (plus `fb2`'s sums when it is not null), each at its count, resolved and tone-mapped on the GPU and scattered
+// into a frame
+Message preview_message(rmd_context *ctx, const double *fb, const double *fb2, size_t W, size_t H, const std::vector<rmd_tile_rect> &rects,
+                        const std::vector<uint32_t> &counts, const Settings &st, size_t pass_index, size_t sample_count) {
+	auto pv = std::make_shared<Preview>();
+	pv->width = W, pv->height = H, pv->pass_index = pass_index, pv->sample_count = sample_count;
+	// the packed bytes arrive in a page-locked block of the pool the tile downloads use, as those do
+	size_t pixels = 0;
+	for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
+	std::shared_ptr<void> block = BlockPool::shared()->get(ctx, std::max<size_t>(pixels * 3, 1));
+	check(rmd_resolve_tonemap_tiles(ctx, fb, fb2, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.preview_exposure, st.preview_gamma,
+	                                static_cast<uint8_t *>(block.get())),
+	      ctx, "rmd_resolve_tonemap_tiles");
+	scatter_packed(rects, static_cast<const uint8_t *>(block.get()), pixels * 3, W, H, pv->rgb8);
+	Message m;
+	m.kind = Message::FramePreview, m.preview = std::move(pv);
+	return m;
+}
+
 // One worker = one GPU.  Pops a batch of tiles, adds `step` samples to each with ONE rmd_render_tiles call per sample count, then reports them
 // finished or re-queues them (src/trace.rs:188-221).  The tiles' sums stay in this GPU's framebuffer; only what a message carries is downloaded,
 // on the copy stream, while the next batch renders (the messages of batch k are sent while batch k + 1 runs).
@@ -187,6 +217,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 	rmd_context *ctx = nullptr;
 	rmd_scene *dscene = nullptr;
 	double *fb = nullptr, *fb_sq = nullptr; // fb_sq: the sums of squares of an adaptive or denoised render
+	double *fb_preview = nullptr;           // settings.preview_denoise: the filtered means of a preview
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	// a batch whose download is on its way: the tiles that become messages, in message order
 	struct Pending {
@@ -213,8 +244,14 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 		flatten(scene, objs, grids);
 		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
 		check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb), ctx, "rmd_framebuffer_alloc"); // zeroed: a fresh tile's sums
-		const bool adaptive = st.adaptive_threshold > 0.0, moments = adaptive || st.denoise;
+		// previews (one worker: render_tiled): every loop below is then one pass over all live tiles, which all hold the same count
+		const bool preview = st.preview_every > 0, preview_filtered = preview && st.preview_denoise;
+		const bool adaptive = st.adaptive_threshold > 0.0, moments = adaptive || st.denoise || preview_filtered;
 		if (moments) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_sq), ctx, "rmd_framebuffer_alloc");
+		if (preview_filtered) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_preview), ctx, "rmd_framebuffer_alloc");
+		std::vector<rmd_tile_rect> early_rects; // previews: the tiles that finished early and the counts they finished with
+		std::vector<uint32_t> early_counts;
+		size_t passes = 0;
 		{
 			std::lock_guard<std::mutex> lock(sh->m);
 			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
@@ -248,6 +285,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 				sh->in_flight += mine.size();
 			}
 			if (mine.empty()) break;
+			passes++;
 			// tiles that arrive with their sums in RAM (another GPU rendered their earlier passes): into this GPU's framebuffer
 			{
 				std::vector<rmd_tile_rect> rects;
@@ -313,7 +351,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 			for (size_t i = 0; i < mine.size(); i++) {
 				Tile &t = mine[i];
 				const bool finished = is_finished(i);
-				const bool progressed = !finished && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
+				const bool progressed = !finished && st.progress_tiles && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
 				if (finished || progressed || workers > 1) {
 					want.push_back(i);
 					rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
@@ -347,7 +385,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 			for (size_t i = 0; i < mine.size(); i++) {
 				Tile &t = mine[i];
 				const bool finished = is_finished(i);
-				const bool progressed = !finished && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
+				const bool progressed = !finished && st.progress_tiles && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
 				if (finished) {
 					t.resident = -1;
 					next.messages.push_back(Message{Message::TileFinished, std::move(t)});
@@ -371,6 +409,31 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 					resident_requeue.push_back(std::move(t));
 				}
 			}
+			if (preview) {
+				// behind this pass's messages: the whole frame, the tiles that go on at this pass's count, those that finished early at their own
+				const size_t done = resident_requeue.empty() ? st.sample_count : resident_requeue.front().sample_count;
+				std::vector<rmd_tile_rect> live_rects;
+				for (const Message &m : next.messages)
+					if (m.kind == Message::TileFinished && m.tile.sample_count < st.sample_count) {
+						early_rects.push_back(rmd_tile_rect{(uint32_t)m.tile.left, (uint32_t)m.tile.top, (uint32_t)m.tile.width, (uint32_t)m.tile.height});
+						early_counts.push_back((uint32_t)m.tile.sample_count);
+					}
+				for (const Tile &t : resident_requeue) live_rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+				if (!live_rects.empty() && passes % st.preview_every == 0) {
+					std::vector<rmd_tile_rect> rects(early_rects);
+					std::vector<uint32_t> counts(early_counts);
+					rects.insert(rects.end(), live_rects.begin(), live_rects.end());
+					counts.insert(counts.end(), live_rects.size(), (uint32_t)done);
+					const double *src = fb;
+					if (preview_filtered) {
+						check(rmd_denoise_atrous(ctx, fb, fb_sq, nullptr, nullptr, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+						                         st.denoise_atrous_levels, st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fb_preview),
+						      ctx, "rmd_denoise_atrous");
+						src = fb_preview, counts.assign(rects.size(), 1u); // (means)
+					}
+					next.messages.push_back(preview_message(ctx, src, nullptr, W, H, rects, counts, st, passes, done));
+				}
+			}
 			{
 				std::lock_guard<std::mutex> lock(sh->m);
 				sh->in_flight -= resident_requeue.size();
@@ -388,6 +451,7 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 	}
 	if (fb) rmd_framebuffer_free(ctx, fb);
 	if (fb_sq) rmd_framebuffer_free(ctx, fb_sq);
+	if (fb_preview) rmd_framebuffer_free(ctx, fb_preview);
 	rmd_scene_destroy(dscene);
 	rmd_context_destroy(ctx);
 	std::lock_guard<std::mutex> lock(sh->m);
@@ -409,6 +473,7 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 	rmd_scene *dscene = nullptr;
 	double *fbs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
 	double *feat[2] = {nullptr, nullptr};                                    // adaptive with denoise_dual_features: the feature sums and sums of squares
+	double *fb_preview = nullptr;                                            // settings.preview_denoise: the filtered means of a preview
 	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
 	try {
 		const auto t_setup = std::chrono::steady_clock::now();
@@ -422,6 +487,7 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 		const bool guided = adaptive && st.denoise_dual_features; // (without the adaptive check nothing here would read the features: await() renders its own)
 		if (guided)
 			for (double *&d : feat) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
+		if (st.preview_every > 0 && st.preview_denoise) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_preview), ctx, "rmd_framebuffer_alloc");
 		{
 			std::lock_guard<std::mutex> lock(sh->m);
 			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
@@ -531,10 +597,11 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 			}
 			finish(converged, converged_err);
 			// progress snapshots of the tiles that go on: the two halves' sums added
-			std::vector<Vector3> pa = download(fbs[0], still), pb = download(fbs[2], still);
+			std::vector<Vector3> pa, pb;
+			if (st.progress_tiles) pa = download(fbs[0], still), pb = download(fbs[2], still);
 			std::vector<Message> snapshots;
 			size_t at = 0;
-			for (size_t k = 0; k < still.size(); k++) {
+			for (size_t k = 0; st.progress_tiles && k < still.size(); k++) {
 				const rmd_tile_rect &r = still[k];
 				const size_t px = (size_t)r.width * r.height;
 				Tile t;
@@ -545,6 +612,24 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 					for (int c = 0; c < 3; c++) t.data[p][c] = pa[at + p][c] + pb[at + p][c];
 				at += px;
 				snapshots.push_back(Message{Message::TileProgressed, std::move(t)});
+			}
+			if (!still.empty() && st.preview_every > 0 && j % st.preview_every == 0) {
+				// the whole frame: finished tiles at the counts they finished with, live ones at n_A + n_B, the two halves' sums added on the device
+				std::vector<rmd_tile_rect> rects(done_rects);
+				std::vector<uint32_t> ca(done_a), cb(done_b);
+				rects.insert(rects.end(), still.begin(), still.end());
+				ca.insert(ca.end(), still.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), still.size(), (uint32_t)n_half[1]);
+				std::vector<uint32_t> both(ca);
+				for (size_t i = 0; i < both.size(); i++) both[i] += cb[i];
+				if (fb_preview) {
+					check(rmd_denoise_atrous_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
+					                              rects.data(), ca.data(), cb.data(), both.data(), (uint32_t)rects.size(), st.denoise_atrous_levels, st.denoise_atrous_k,
+					                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fb_preview, nullptr),
+					      ctx, "rmd_denoise_atrous_dual");
+					snapshots.push_back(preview_message(ctx, fb_preview, nullptr, W, H, rects, std::vector<uint32_t>(rects.size(), 1u), st, j, done)); // (means)
+				} else {
+					snapshots.push_back(preview_message(ctx, fbs[0], fbs[2], W, H, rects, both, st, j, done));
+				}
 			}
 			{
 				std::lock_guard<std::mutex> lock(sh->m);
@@ -564,6 +649,7 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 		if (fb) rmd_framebuffer_free(ctx, fb);
 	for (double *d : feat)
 		if (d) rmd_framebuffer_free(ctx, d);
+	if (fb_preview) rmd_framebuffer_free(ctx, fb_preview);
 	rmd_scene_destroy(dscene);
 	rmd_context_destroy(ctx);
 	std::lock_guard<std::mutex> lock(sh->m);
@@ -573,7 +659,20 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 
 } // namespace
 
+std::string check_preview(const Settings &st) {
+	if (st.preview_every > 0 && st.samples_per_iteration == 0) return "preview_every > 0 needs samples_per_iteration > 0 (a preview is made between passes)";
+	if (!(st.preview_exposure > 0.0) || !std::isfinite(st.preview_exposure)) return "preview_exposure must be finite and > 0";
+	if (!(st.preview_gamma > 0.0) || !std::isfinite(st.preview_gamma)) return "preview_gamma must be finite and > 0";
+	if (st.preview_denoise && st.preview_every == 0) return "preview_denoise needs preview_every > 0 (it selects the filter of the previews)";
+	if (st.preview_denoise && st.worker_count > 1)
+		return "preview_denoise renders on one device: the filter's window crosses the tiles that several devices would own";
+	if (st.preview_every > 0 && st.worker_count > 1)
+		return "preview_every > 0 needs worker_count == 1 here: a tile moves from GPU to GPU between passes, so no GPU holds a frame's share";
+	return "";
+}
+
 TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
+	if (const std::string why = check_preview(settings); !why.empty()) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: " + why);
 	if (settings.denoise_radius > 12 || settings.denoise_patch > 4) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_radius must be <= 12, denoise_patch <= 4");
 	if (!(settings.denoise_k > 0.0) || !std::isfinite(settings.denoise_k)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_k must be finite and > 0");
 	if (!(settings.denoise_alpha >= 0.0) || !std::isfinite(settings.denoise_alpha))
@@ -917,15 +1016,33 @@ void TaskHandle::async_await() {
 		std::optional<Message> m;
 		{
 			std::lock_guard<std::mutex> lock(shared_->m);
-			if (shared_->channel.empty() || shared_->channel.front().kind != Message::TileProgressed) return;
+			if (shared_->channel.empty() || shared_->channel.front().kind == Message::TileFinished) return;
 			m = std::move(shared_->channel.front());
 			shared_->channel.pop_front();
 		}
-		if (callback_) callback_(m->tile);
+		if (m->kind == Message::FramePreview) {
+			if (preview_callback_) preview_callback_(*m->preview);
+		} else if (callback_) callback_(m->tile);
 	}
 }
 
 // ---------------------------------------------------------------- output stage (cli_old/src/main.rs:155-197)
+std::vector<uint8_t> resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, size_t width, size_t height,
+                                           const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double exposure, double gamma) {
+	if (counts.size() != rects.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "resolve_tonemap_tiles: one sample count per rect");
+	size_t pixels = 0;
+	for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
+	std::vector<uint8_t> packed(pixels * 3);
+	check(rmd_resolve_tonemap_tiles(ctx, accum_dev, accum2_dev, (uint32_t)width, (uint32_t)height, rects.data(), counts.data(), (uint32_t)rects.size(), exposure, gamma,
+	                                packed.data()),
+	      ctx, "rmd_resolve_tonemap_tiles");
+	return packed;
+}
+
+void scatter_tiles(const std::vector<rmd_tile_rect> &rects, const std::vector<uint8_t> &packed, size_t width, size_t height, std::vector<uint8_t> &frame) {
+	scatter_packed(rects, packed.data(), packed.size(), width, height, frame);
+}
+
 std::vector<uint8_t> tone_map(const std::vector<Vector3> &image, double exposure, double gamma) {
 	std::vector<uint8_t> out(image.size() * 3, 0);
 	for (size_t i = 0; i < image.size(); i++) {

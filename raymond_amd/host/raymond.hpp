@@ -169,7 +169,23 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// rmd_tile_error_dual — an absolute RMS in linear radiance that reads low — is at most the threshold is finished at the samples it has.
 	double adaptive_denoised_threshold = 0.0;
 	size_t adaptive_min_samples = 32;
+	// Frame previews during a progressive render (needs samples_per_iteration > 0; 0 = off): after every preview_every-th pass that leaves the render
+	// unfinished — the passes after which TileProgressed is sent — one Message::FramePreview follows that pass's TileProgressed messages: the whole frame
+	// as W*H*3 bytes, every tile resolved and tone-mapped on the GPU at its own sample count (rmd_resolve_tonemap_tiles) with preview_exposure and
+	// preview_gamma (both finite and > 0).  In this mirror a tile may move from GPU to GPU between passes, so no GPU holds a frame's share: previews
+	// need worker_count == 1, and render_tiled throws otherwise.
+	size_t preview_every = 0;
+	double preview_exposure = 1.0, preview_gamma = 2.2;
+	// The preview is the fast filter's frame instead of the raw means (needs preview_every; false = off), at denoise_atrous_levels, denoise_atrous_k and
+	// denoise_alpha: rmd_denoise_atrous on the sums and sums of squares — the passes then render with second moments, as they do for denoise —, in the
+	// dual-buffer loop rmd_denoise_atrous_dual, guided by the feature buffers when the loop already keeps them.  Its means are resolved at count 1.
+	bool preview_denoise = false;
+	// false: no TileProgressed message is made and nothing is downloaded for one; an adaptive render's TileFinished messages stay.
+	bool progress_tiles = true;
 };
+// What render_tiled refuses in the preview settings (it throws this text as a raymond::Error); empty: nothing.  One policy with raymond_amd/scene.py's
+// Settings.check_preview.
+std::string check_preview(const Settings &settings);
 
 // core/src/tile.rs:13 `data: Vec<Vector3>` — the running sums of a tile, width * height of them, row-major.  Here a VIEW: the tiles of one
 // message batch (a progressive pass's TileProgressed snapshots, or the TileFinished tiles) share the one page-locked block their pixels were
@@ -212,9 +228,16 @@ struct Tile { // core/src/tile.rs:7-14
 	size_t count_a = 0, count_b = 0;
 	double error = -1.0; // dual-buffer adaptive renders: the tile's rmd_tile_error_dual when it was last checked; -1: never
 };
+// An extension (settings.preview_every): the frame after pass `pass_index` (counted from 1), row-major RGB bytes; sample_count: the samples per pixel
+// of a tile that is still live (tiles that finished early are in the frame at the count they finished with)
+struct Preview {
+	std::vector<uint8_t> rgb8;
+	size_t width = 0, height = 0, pass_index = 0, sample_count = 0;
+};
 struct Message { // src/trace.rs:62-66
-	enum Kind { TileFinished, TileProgressed } kind;
+	enum Kind { TileFinished, TileProgressed, FramePreview } kind; // FramePreview: `preview` is set and `tile` is empty
 	Tile tile;
+	std::shared_ptr<const Preview> preview = nullptr;
 };
 
 // src/trace.rs:70-135
@@ -223,11 +246,13 @@ class TaskHandle {
 	using TileCallback = std::function<void(const Tile &)>;
 	Settings settings;
 	void set_callback(TileCallback cb) { callback_ = std::move(cb); }
+	using PreviewCallback = std::function<void(const Preview &)>;
+	void set_preview_callback(PreviewCallback cb) { preview_callback_ = std::move(cb); }
 	// Blocks until every worker is done, then assembles W*H radiance values (tile sums / sample_count), row-major (:82-113).  settings.denoise: the
 	// collected tiles go through denoise_tiles (settings.denoise_dual: denoise_dual_tiles) on GPU 0 instead (none collected: the zero frame, as without it)
 	std::vector<Vector3> await();
 	std::optional<Message> poll();        // :115-117
-	void async_await();                   // :119-134: drains leading TileProgressed messages into the callback
+	void async_await();                   // :119-134: drains leading TileProgressed messages into the callback (and FramePreview ones into the preview callback)
 	bool finished() const;                // extension: alive_thread_count == 0 (what await() polls for, :89)
 	double setup_seconds() const;         // extension (measurement): the longest a worker took to get ready — context, scene upload, framebuffer
 	~TaskHandle();
@@ -241,6 +266,7 @@ class TaskHandle {
 	std::shared_ptr<Shared> shared_;
 	std::vector<std::thread> workers_;
 	TileCallback callback_;
+	PreviewCallback preview_callback_;
 };
 
 // src/trace.rs:137-230
@@ -262,6 +288,13 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 // with the settings' camera, seed and DOF flag: the AOVs (normal xyz, albedo rgb, depth) of raymond_hip.h's rmd_render_features.
 std::vector<double> render_features(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
                                     int device = 0, std::vector<double> *sums_sq = nullptr);
+
+// rmd_resolve_tonemap_tiles on `ctx`: the rects of the width x height device framebuffer `accum_dev`, rect i at counts[i] samples per pixel, tone-mapped
+// into packed bytes — rect after rect, each row-major, 3 bytes per pixel.  accum2_dev (or null): a dual-buffer render's other half, added first.
+std::vector<uint8_t> resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, size_t width, size_t height,
+                                           const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double exposure = 1.0, double gamma = 2.2);
+// ... and those packed bytes written into a width x height x 3 frame at their rects (later rects overwrite earlier ones where they overlap)
+void scatter_tiles(const std::vector<rmd_tile_rect> &rects, const std::vector<uint8_t> &packed, size_t width, size_t height, std::vector<uint8_t> &frame);
 
 // Tile generation of render_tiled (:142-173): column-major, edge tiles clamped
 std::vector<rmd_tile_rect> generate_tiles(size_t width, size_t height, std::pair<size_t, size_t> tile_size);
@@ -288,6 +321,7 @@ struct Project {
 	Scene build_scene() const; // project.rs:38-57: meshes through Mesh::load_ply + AccGrid::build_from_mesh
 };
 // server/src/protocol.rs:9-14: {"type":"TileProgressed"|"TileFinished","data":{sample_count,width,height,left,top,data:[V..]}}
+// (a FramePreview has no wire form there: raymond::Error)
 std::string message_to_json(const Message &message);
 
 // Benchmark inputs, identical to raymond_amd/scenes.py

@@ -531,6 +531,46 @@ def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
     return out
 
 
+def resolve_tonemap_tiles(ctx, framebuffer, rects, counts, exposure=1.0, gamma=2.2, second=None):
+    """rmd_resolve_tonemap_tiles: resolve_tonemap over the tile rects (left, top, width, height), rect i at counts[i] samples per pixel -> one
+    (h, w, 3) uint8 array per rect (views of one packed block, in download_tiles's order).  `second` (a Framebuffer): a dual-buffer render's other
+    half, whose sums are added to `framebuffer`'s before the division; counts then hold both halves' samples."""
+    rects = list(rects)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != len(rects):
+        raise ValueError("one sample count per rect")
+    n = sum(w * h for (_, _, w, h) in rects)
+    out = np.empty(n * 3, dtype=np.uint8)
+    ctx.check(ctx.L.rmd_resolve_tonemap_tiles(ctx.handle, framebuffer.ptr, None if second is None else second.ptr, framebuffer.width, framebuffer.height,
+                                              tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), float(exposure), float(gamma),
+                                              out.ctypes.data_as(C.c_void_p)))
+    views, at = [], 0
+    for (_, _, w, h) in rects:
+        views.append(out[at : at + w * h * 3].reshape(h, w, 3))
+        at += w * h * 3
+    return views
+
+
+def scatter_tiles(rects, tiles, width=None, height=None, out=None):
+    """The per-rect arrays `tiles` ((h, w, c) each, as resolve_tonemap_tiles or download_tiles return them) written into a (height, width, c) frame at
+    their rects: `out` when given, else a new zeroed frame of the tiles' dtype.  Later rects overwrite earlier ones where they overlap."""
+    rects = list(rects)
+    if len(rects) != len(tiles):
+        raise ValueError("one array per rect")
+    if out is None:
+        if width is None or height is None:
+            raise ValueError("scatter_tiles needs a frame: out, or width and height")
+        first = np.asarray(tiles[0]) if len(tiles) else np.empty((0, 0, 3), dtype=np.uint8)
+        out = np.zeros((height, width, first.shape[2] if first.ndim == 3 else 3), dtype=first.dtype)
+    H, W = out.shape[0], out.shape[1]
+    for (l, t, w, h), data in zip(rects, tiles):
+        if l < 0 or t < 0 or w < 0 or h < 0 or l + w > W or t + h > H:
+            raise ValueError("rect (%d, %d, %d, %d) outside the %d x %d frame" % (l, t, w, h, W, H))
+        if w and h:
+            out[t : t + h, l : l + w] = np.asarray(data).reshape(h, w, -1)
+    return out
+
+
 # ---------------------------------------------------------------- the reference-shaped API
 class Tile:  # core/src/tile.rs:7-14
     def __init__(self, left, top, width, height, sample_count, data, error=None, data_sq=None):
@@ -556,6 +596,14 @@ class Message:  # src/trace.rs:62-66
     def TileProgressed(tile):
         return Message("TileProgressed", tile)
 
+    @staticmethod
+    def FramePreview(frame, pass_index, sample_count):
+        """An extension (settings.preview_every): `frame` — the whole (H, W, 3) uint8 frame after pass `pass_index` (counted from 1), every tile
+        tone-mapped at its own sample count; `sample_count`: the samples per pixel of a tile that is still live.  `tile` is None."""
+        m = Message("FramePreview", None)
+        m.frame, m.pass_index, m.sample_count = frame, pass_index, sample_count
+        return m
+
 
 class TaskHandle:  # src/trace.rs:70-135
     def __init__(self, settings, messages, device=0, scene=None):
@@ -563,6 +611,7 @@ class TaskHandle:  # src/trace.rs:70-135
         self.scene = scene  # settings.denoise_features / denoise_dual_features: await_() uploads it to `device` for the feature pass
         self._messages = list(messages)
         self.callback = None
+        self.preview_callback = None
         self.device = device  # settings.denoise: the GPU await_() denoises on (render_tiled's first)
 
     def set_callback(self, callback):
@@ -571,10 +620,17 @@ class TaskHandle:  # src/trace.rs:70-135
     def poll(self):
         return self._messages.pop(0) if self._messages else None
 
+    def set_preview_callback(self, callback):
+        """`callback(message)` for every Message.FramePreview that async_await meets."""
+        self.preview_callback = callback
+
     def async_await(self):
-        while self._messages and self._messages[0].kind == "TileProgressed":
+        while self._messages and self._messages[0].kind in ("TileProgressed", "FramePreview"):
             m = self._messages.pop(0)
-            if self.callback:
+            if m.kind == "FramePreview":
+                if self.preview_callback:
+                    self.preview_callback(m)
+            elif self.callback:
                 self.callback(m.tile)
 
     def await_(self):
@@ -715,13 +771,21 @@ def render_tiled(scene, settings, devices=(0,)):
     Denoised (settings.denoise, an extension): the passes render with second moments, every TileFinished tile carries them as `data_sq`, and
     TaskHandle.await_() denoises the assembled frame on the first of `devices`.
 
+    Previews (settings.preview_every > 0, an extension): after every preview_every-th pass that leaves live tiles below sample_count, one
+    Message.FramePreview follows that pass's TileProgressed messages — each device resolves and tone-maps the tiles of its share with
+    rmd_resolve_tonemap_tiles, live ones at the current count and those that finished early at theirs, and the packed tiles are scattered into one
+    (H, W, 3) uint8 frame here.  With settings.preview_denoise the frame is rmd_denoise_atrous's (one device; the passes then render with second
+    moments).  With settings.progress_tiles = False no TileProgressed message is made and only converged tiles' pixels are downloaded.
+
     Dual-buffer (settings.denoise_dual, an extension): _render_tiled_dual."""
     settings.check_adaptive()
     settings.check_denoise()
+    settings.check_preview(len(devices))
     if settings.denoise_dual:
         return _render_tiled_dual(scene, settings, devices)
     adaptive = settings.adaptive_threshold > 0.0
-    moments = adaptive or settings.denoise
+    preview_filtered = settings.preview_every > 0 and settings.preview_denoise
+    moments = adaptive or settings.denoise or preview_filtered
     cam = settings.camera_settings
     W, H = cam.backbuffer_width, cam.backbuffer_height
     tiles = generate_tiles(W, H, settings.tile_size)
@@ -729,11 +793,13 @@ def render_tiled(scene, settings, devices=(0,)):
     for d in devices:
         ctx = Context(d)
         workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H), Framebuffer(ctx, W, H) if moments else None))
+    filtered_fb = Framebuffer(workers[0][0], W, H) if preview_filtered else None  # (one device: check_preview)
     shares = [tiles[i :: len(workers)] for i in range(len(workers))]  # adaptive: the tiles of a share that are still live
+    early = [[] for _ in workers]  # previews: per worker, the (rect, sample count) of the tiles that finished early
     step = settings.samples_per_iteration if settings.samples_per_iteration else settings.sample_count
     messages = []
     finished = []
-    done = 0
+    done = passes = 0
     try:
         while done < settings.sample_count:
             n = min(step, settings.sample_count - done)
@@ -743,10 +809,21 @@ def render_tiled(scene, settings, devices=(0,)):
             for ctx, _, _, _ in workers:
                 ctx.synchronize()
             done += n
+            passes += 1
             if done < settings.sample_count and settings.samples_per_iteration:
                 for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
                     share = shares[i]
                     errors = tile_error(ctx, fb, fb_sq, done, settings.adaptive_floor, share) if adaptive and share else [None] * len(share)
+                    if not settings.progress_tiles:  # no snapshots: only the converged tiles' pixels come to the host
+                        is_conv = [adaptive and e <= settings.adaptive_threshold for e in errors]
+                        conv = [r for r, c in zip(share, is_conv) if c]
+                        data = fb.download_tiles(conv) if conv else []
+                        data_sq = fb_sq.download_tiles(conv) if conv and settings.denoise else [None] * len(conv)
+                        for (l, t, w, h), e, d, d_sq in zip(conv, [e for e, c in zip(errors, is_conv) if c], data, data_sq):
+                            finished.append(Message.TileFinished(Tile(l, t, w, h, done, d.copy(), float(e), None if d_sq is None else d_sq.copy())))
+                            early[i].append(((l, t, w, h), done))
+                        shares[i] = [r for r, c in zip(share, is_conv) if not c]
+                        continue
                     img = fb.download()
                     img_sq = fb_sq.download() if settings.denoise else None
                     live = []
@@ -756,18 +833,36 @@ def render_tiled(scene, settings, devices=(0,)):
                             if img_sq is not None:
                                 tile.data_sq = img_sq[t : t + h, l : l + w].copy()
                             finished.append(Message.TileFinished(tile))  # converged: finished at the samples it has
+                            early[i].append(((l, t, w, h), done))
                         else:
                             messages.append(Message.TileProgressed(tile))
                             live.append((l, t, w, h))
                     shares[i] = live
+                if settings.preview_every and passes % settings.preview_every == 0 and any(shares):  # (no live tile: the render is finished)
+                    # every device resolves the tiles of its share — live ones at `done`, those that finished early at their own counts — and the
+                    # packed 8-bit tiles are scattered into one frame here
+                    frame = np.zeros((H, W, 3), dtype=np.uint8)
+                    for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
+                        rects = [r for r, _ in early[i]] + shares[i]
+                        counts = [c for _, c in early[i]] + [done] * len(shares[i])
+                        if not rects:
+                            continue
+                        if preview_filtered:
+                            denoise_atrous(ctx, fb, fb_sq, rects, counts, filtered_fb, levels=settings.denoise_atrous_levels, k=settings.denoise_atrous_k,
+                                           alpha=settings.denoise_alpha)
+                            fb, counts = filtered_fb, [1] * len(rects)  # (means)
+                        scatter_tiles(rects, resolve_tonemap_tiles(ctx, fb, rects, counts, settings.preview_exposure, settings.preview_gamma), out=frame)
+                    messages.append(Message.FramePreview(frame, passes, done))
         for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
             img = fb.download()
             img_sq = fb_sq.download() if settings.denoise else None
             for (l, t, w, h) in share:
                 sq = None if img_sq is None else img_sq[t : t + h, l : l + w].copy()
                 finished.append(Message.TileFinished(Tile(l, t, w, h, settings.sample_count, img[t : t + h, l : l + w].copy(), data_sq=sq)))
-        messages = messages + finished  # progress snapshots first, then the finished tiles
+        messages = messages + finished  # progress snapshots (and previews) first, then the finished tiles
     finally:
+        if filtered_fb is not None:
+            filtered_fb.close()
         for ctx, ds, fb, fb_sq in workers:
             fb.close()
             if fb_sq is not None:
@@ -794,7 +889,11 @@ def _render_tiled_dual(scene, settings, devices):
 
     With settings.denoise_dual_atrous the check is rmd_denoise_atrous_dual on the WHOLE frame instead, at the same rects and counts, guided by the same
     feature buffers; rmd_tile_error_dual then runs over the live tiles as before.  With settings.denoise_dual_atrous_region the check passes
-    region=live — rmd_denoise_atrous_dual_region, the same bytes at the live tiles' pixels —; nothing else changes."""
+    region=live — rmd_denoise_atrous_dual_region, the same bytes at the live tiles' pixels —; nothing else changes.
+
+    With settings.preview_every > 0 a Message.FramePreview follows the snapshots of every preview_every-th pass that leaves live tiles: the two halves'
+    sums added on the device (rmd_resolve_tonemap_tiles with the other half as its second buffer) at n_A + n_B, finished tiles at the counts they
+    finished with; with settings.preview_denoise, rmd_denoise_atrous_dual's frame at those counts, guided when this loop keeps the feature buffers."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     st = settings
@@ -820,6 +919,10 @@ def _render_tiled_dual(scene, settings, devices):
         if guided:
             feat_fbs = [FeatureBuffer(ctx, W, H) for _ in range(2)]
             opened.extend(feat_fbs)
+        preview_fb = None
+        if st.preview_every and st.preview_denoise:
+            preview_fb = Framebuffer(ctx, W, H)
+            opened.append(preview_fb)
         live = list(tiles)
         done_rects, done_a, done_b = [], [], []  # the finished tiles and the counts they finished with
         n_half = [0, 0]  # samples per pixel of a live tile in A and B
@@ -865,10 +968,24 @@ def _render_tiled_dual(scene, settings, devices):
                 conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
                 finish([r for r, c in zip(live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
                 still = [r for r, c in zip(live, conv) if not c]
-                if still:  # progress snapshots: the two halves' sums added
+                if still and st.progress_tiles:  # progress snapshots: the two halves' sums added
                     pa, pb = fbs[0].download_tiles(still), fbs[2].download_tiles(still)
                     for (l, t, w, h), e, a, b in zip(still, [e for e, c in zip(errors, conv) if not c], pa, pb):
                         messages.append(Message.TileProgressed(Tile(l, t, w, h, done, a + b, None if e is None else float(e))))
+                if still and st.preview_every and j % st.preview_every == 0:
+                    # the whole frame: finished tiles at the counts they finished with, live ones at n_A + n_B, the two halves' sums added on the device
+                    rects = done_rects + still
+                    all_a, all_b = done_a + [n_half[0]] * len(still), done_b + [n_half[1]] * len(still)
+                    if preview_fb is None:
+                        packed = resolve_tonemap_tiles(ctx, fbs[0], rects, [a + b for a, b in zip(all_a, all_b)], st.preview_exposure, st.preview_gamma, second=fbs[2])
+                    else:
+                        if guided:
+                            guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
+                                         tau=st.denoise_feature_tau)
+                        denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), rects, all_a, all_b, preview_fb, None, levels=st.denoise_atrous_levels,
+                                            k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide)
+                        packed = resolve_tonemap_tiles(ctx, preview_fb, rects, [1] * len(rects), st.preview_exposure, st.preview_gamma)  # (means)
+                    messages.append(Message.FramePreview(scatter_tiles(rects, packed, W, H), j, done))
                 live = still
         finish(live)
         messages = messages + finished  # progress snapshots first, then the finished tiles

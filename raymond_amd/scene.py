@@ -247,7 +247,8 @@ class Settings:
                  adaptive_floor=1e-3, denoise=False, denoise_radius=10, denoise_patch=3, denoise_k=0.45, denoise_alpha=1.0,
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
                  adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False, denoise_atrous=False,
-                 denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False):
+                 denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False, preview_every=0,
+                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -310,6 +311,22 @@ class Settings:
         # gives their pixels the whole-frame call's bytes at a cost that follows their dilated area.  No message and no output changes; await_() is untouched.
         self.denoise_dual_atrous_region = bool(denoise_dual_atrous_region)
         self.check_denoise()
+        # Frame previews during a progressive render (an extension; 0 = off): after every preview_every-th pass that leaves the render unfinished — the
+        # passes after which TileProgressed is sent — one Message.FramePreview follows that pass's TileProgressed messages: the whole frame as (H, W, 3)
+        # uint8, every tile resolved and tone-mapped on its device at its own sample count (rmd_resolve_tonemap_tiles) with preview_exposure and
+        # preview_gamma.  Needs samples_per_iteration > 0.
+        self.preview_every = preview_every
+        self.preview_exposure = float(preview_exposure)
+        self.preview_gamma = float(preview_gamma)
+        # The preview is the fast filter's frame instead of the raw means (False = off; needs preview_every, one device only), at denoise_atrous_levels,
+        # denoise_atrous_k and denoise_alpha: rmd_denoise_atrous on the sums and sums of squares — the passes then render with second moments, as they do
+        # for denoise —, in the dual-buffer loop rmd_denoise_atrous_dual, guided by the feature buffers when the loop already keeps them (a half without
+        # samples, after a first pass, leaves that filter nothing to cross-weight with).  Its means are resolved at count 1.
+        self.preview_denoise = bool(preview_denoise)
+        # False: no TileProgressed message is made and nothing is downloaded for one; an adaptive render's TileFinished messages stay, the data of
+        # converged tiles coming through download_tiles of those tiles only.
+        self.progress_tiles = bool(progress_tiles)
+        self.check_preview()
 
     def select_candidates(self):
         """The candidates of denoise_dual_select, as render.denoise_dual_select takes them: the unguided filter at denoise_k, and the guided one at k = 1.0
@@ -376,6 +393,22 @@ class Settings:
         v = self.adaptive_min_samples
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
             raise ValueError("adaptive_min_samples must be an integer >= 0")
+
+    def check_preview(self, n_devices=1):
+        """Raises ValueError for preview settings render_tiled cannot follow on `n_devices` devices."""
+        v = self.preview_every
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("preview_every must be an integer >= 0 (0 = off)")
+        if self.preview_every > 0 and self.samples_per_iteration == 0:
+            raise ValueError("preview_every > 0 needs samples_per_iteration > 0 (a preview is made between passes)")
+        if not (self.preview_exposure > 0.0 and np.isfinite(self.preview_exposure)):
+            raise ValueError("preview_exposure must be finite and > 0")
+        if not (self.preview_gamma > 0.0 and np.isfinite(self.preview_gamma)):
+            raise ValueError("preview_gamma must be finite and > 0")
+        if self.preview_denoise and self.preview_every == 0:
+            raise ValueError("preview_denoise needs preview_every > 0 (it selects the filter of the previews)")
+        if self.preview_denoise and n_devices != 1:
+            raise ValueError("preview_denoise renders on one device: the filter's window crosses the tiles that several devices would own")
 
     def pod(self, sample_begin=0, sample_count=None):
         s = abi.Settings()
