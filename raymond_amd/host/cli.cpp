@@ -92,13 +92,7 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 	}
 	if (finished_out) *finished_out = finished_tiles; // (views: cheap)
 	std::vector<Vector3> image(W * H, Vector3{0, 0, 0});
-	for (const Tile &t : finished_tiles)
-		for (size_t y = 0; y < t.height; y++)
-			for (size_t x = 0; x < t.width; x++) {
-				Vector3 v = t.data[x + y * t.width];
-				for (double &c : v) c /= (double)t.sample_count; // :95
-				image[x + t.left + (y + t.top) * W] = v;
-			}
+	for (const Tile &t : finished_tiles) place_tile(t, t.data, W, image, (double)t.sample_count); // :95
 	handle.await(); // waits for the workers to leave (they free their device memory after their last message); rethrows a worker's error
 	return image;
 }
@@ -272,16 +266,11 @@ int main(int argc, char **argv) {
 					std::vector<rmd_tile_rect> rects;
 					std::vector<uint32_t> counts;
 					for (const Tile &t : finished) {
-						rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+						rects.push_back(rect_of(t));
 						counts.push_back((uint32_t)t.sample_count);
 					}
 					feature_means = render_features(scene, st, rects, counts, 0);
-					std::vector<double> n_img(W * H, 0.0);
-					for (size_t i = 0; i < rects.size(); i++)
-						for (size_t y = rects[i].top; y < (size_t)rects[i].top + rects[i].height; y++)
-							for (size_t x = rects[i].left; x < (size_t)rects[i].left + rects[i].width; x++) n_img[x + y * W] = (double)counts[i];
-					for (size_t p = 0; p < W * H; p++)
-						for (size_t j = 0; j < RMD_FEATURE_CHANNELS; j++) feature_means[p * RMD_FEATURE_CHANNELS + j] /= n_img[p];
+					divide_by_counts(feature_means, W, H, RMD_FEATURE_CHANNELS, rects, counts);
 				}
 				std::ofstream f(dump_features, std::ios::binary);
 				f.write(reinterpret_cast<const char *>(feature_means.data()), (std::streamsize)(feature_means.size() * 8));

@@ -12,6 +12,7 @@
 #include <map>
 #include <sstream>
 #include <tuple>
+#include <utility>
 
 namespace raymond {
 
@@ -105,6 +106,26 @@ std::vector<rmd_tile_rect> generate_tiles(size_t width, size_t height, std::pair
 	return tiles;
 }
 
+rmd_tile_rect rect_of(const Tile &t) { return rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height}; }
+
+void place_tile(const Tile &t, const TileData &data, size_t width, std::vector<Vector3> &frame, double divisor) {
+	for (size_t y = 0; y < t.height; y++)
+		for (size_t x = 0; x < t.width; x++) {
+			Vector3 s = data[x + y * t.width];
+			for (double &c : s) c /= divisor; // :95 (x / 1.0 is x: without a divisor the sums arrive as they are)
+			frame[x + t.left + (y + t.top) * width] = s;
+		}
+}
+
+void divide_by_counts(std::vector<double> &sums, size_t width, size_t height, size_t channels, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts) {
+	std::vector<double> n_img(width * height, 0.0);
+	for (size_t i = 0; i < rects.size(); i++)
+		for (size_t y = rects[i].top; y < (size_t)rects[i].top + rects[i].height; y++)
+			for (size_t x = rects[i].left; x < (size_t)rects[i].left + rects[i].width; x++) n_img[x + y * width] = (double)counts[i];
+	for (size_t p = 0; p < width * height; p++)
+		for (size_t j = 0; j < channels; j++) sums[p * channels + j] /= n_img[p];
+}
+
 struct TaskHandle::Shared {
 	std::mutex m;
 	std::condition_variable cv;
@@ -144,6 +165,96 @@ void flatten(const Scene &scene, std::vector<rmd_object> &objs, std::vector<rmd_
 		for (int a = 0; a < 5; a++) r.material.emission_aux[a] = o.material.aux[a];
 		objs.push_back(r);
 	}
+}
+
+// ---------------------------------------------------------------- owners of what the C-ABI hands out
+// Move-only, freed by their destructors.  Whoever holds several declares them context, scene, frames: they then go frames first, the context last.
+class Context {
+  public:
+	explicit Context(int device) { check(rmd_context_create(device, &p_), nullptr, "rmd_context_create"); }
+	~Context() { rmd_context_destroy(p_); }
+	Context(Context &&o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+	Context &operator=(Context &&) = delete;
+	operator rmd_context *() const { return p_; }
+
+  private:
+	rmd_context *p_ = nullptr;
+};
+
+class DeviceScene { // a Scene flattened and uploaded to a context's GPU
+  public:
+	DeviceScene(rmd_context *ctx, const Scene &scene) {
+		std::vector<rmd_object> objs;
+		std::vector<rmd_grid_desc> grids;
+		flatten(scene, objs, grids);
+		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &p_), ctx, "rmd_scene_create");
+	}
+	~DeviceScene() { rmd_scene_destroy(p_); }
+	DeviceScene(DeviceScene &&o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+	DeviceScene &operator=(DeviceScene &&) = delete;
+	operator rmd_scene *() const { return p_; }
+
+  private:
+	rmd_scene *p_ = nullptr;
+};
+
+class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, or the features' RMD_FEATURE_CHANNELS; empty (a null pointer) until one is moved in
+  public:
+	enum Kind { Colour, Features };
+	Frame() = default;
+	Frame(rmd_context *ctx, size_t W, size_t H, Kind kind = Colour) : ctx_(ctx) {
+		if (kind == Features) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_feature_buffer_alloc");
+		else check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_framebuffer_alloc");
+	}
+	~Frame() {
+		if (p_) rmd_framebuffer_free(ctx_, p_);
+	}
+	Frame(Frame &&o) noexcept : ctx_(o.ctx_), p_(std::exchange(o.p_, nullptr)) {}
+	Frame &operator=(Frame &&o) noexcept {
+		std::swap(ctx_, o.ctx_), std::swap(p_, o.p_);
+		return *this;
+	}
+	operator double *() const { return p_; }
+
+  private:
+	rmd_context *ctx_ = nullptr;
+	double *p_ = nullptr;
+};
+
+// ---------------------------------------------------------------- the C-ABI's PODs from a Settings, and the small sums
+rmd_camera camera_pod(const Settings &st) {
+	rmd_camera cam;
+	std::memset(&cam, 0, sizeof(cam));
+	cam.backbuffer_width = (uint32_t)st.camera_settings.backbuffer_width, cam.backbuffer_height = (uint32_t)st.camera_settings.backbuffer_height;
+	cam.fov_vert = st.camera_settings.fov_vert;
+	for (int a = 0; a < 3; a++) cam.position[a] = st.camera_settings.transform.position[a];
+	cam.focal_length = st.camera_settings.focal_length, cam.aperture_radius = st.camera_settings.aperture_radius;
+	return cam;
+}
+uint32_t feature_flags(const Settings &st) { return st.use_dof ? RMD_RENDER_DOF : 0u; } // what rmd_render_features takes: the DOF flag alone
+uint32_t render_flags(const Settings &st) { // 0 = the reference's loop: pinhole (:199), every sample identical
+	return feature_flags(st) | (st.end_black_paths ? RMD_RENDER_END_BLACK_PATHS : 0u);
+}
+rmd_settings settings_pod(const Settings &st, size_t begin, size_t n, uint32_t flags) { // samples [begin, begin + n)
+	rmd_settings rs;
+	std::memset(&rs, 0, sizeof(rs));
+	rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)begin, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
+	return rs;
+}
+size_t pixels_of(const std::vector<rmd_tile_rect> &rects) {
+	size_t pixels = 0;
+	for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
+	return pixels;
+}
+std::vector<uint32_t> sum_counts(const std::vector<uint32_t> &a, const std::vector<uint32_t> &b) {
+	std::vector<uint32_t> both(a);
+	for (size_t i = 0; i < both.size(); i++) both[i] += b[i];
+	return both;
+}
+std::vector<rmd_tile_rect> rects_of(const std::vector<Tile> &tiles, const std::vector<size_t> &which) {
+	std::vector<rmd_tile_rect> rects;
+	for (size_t i : which) rects.push_back(rect_of(tiles[i]));
+	return rects;
 }
 
 // Page-locked blocks for the downloads, recycled: a block goes back to the pool when the last tile (message) that views it is dropped.
@@ -198,8 +309,7 @@ Message preview_message(rmd_context *ctx, const double *fb, const double *fb2, s
 	auto pv = std::make_shared<Preview>();
 	pv->width = W, pv->height = H, pv->pass_index = pass_index, pv->sample_count = sample_count;
 	// the packed bytes arrive in a page-locked block of the pool the tile downloads use, as those do
-	size_t pixels = 0;
-	for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
+	const size_t pixels = pixels_of(rects);
 	std::shared_ptr<void> block = BlockPool::shared()->get(ctx, std::max<size_t>(pixels * 3, 1));
 	check(rmd_resolve_tonemap_tiles(ctx, fb, fb2, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.preview_exposure, st.preview_gamma,
 	                                static_cast<uint8_t *>(block.get())),
@@ -210,15 +320,86 @@ Message preview_message(rmd_context *ctx, const double *fb, const double *fb2, s
 	return m;
 }
 
+// The dual-buffer filter that `st` selects, as its one C-ABI call: over the two halves half[0..3] = S_A, Q_A, S_B, Q_B of a W x H frame whose rect i holds
+// counts_a[i] + counts_b[i] samples, into `out` and — where it is not null — the error image `err`.  feat / feat_sq: the feature sums and sums of squares
+// at those counts added, or nulls.  region (n_region rects), or null: the caller reads only those pixels of `out` and `err` — the adaptive check of the
+// dual loop, whose region is its live tiles; the forms that have a region form then write those pixels alone, with the whole-frame call's bytes.
+//   denoise_dual_atrous:   rmd_denoise_atrous_dual, guided where the features are given; its region form only with denoise_dual_atrous_region
+//   denoise_dual_select:   rmd_denoise_dual_select at the setting's two candidates (it needs the features)
+//   the features given:    rmd_denoise_dual_guided[_region]
+//   otherwise:             rmd_denoise_dual[_region]
+// Two things that a reader may take for oversights and that every caller's bytes depend on: a call with a region never selects — rmd_denoise_dual_select
+// has no region form, and a select render's adaptive check is the plain or the guided region form —; and the unguided call with a region is
+// rmd_denoise_dual_region where the one without is rmd_denoise_dual.
+void denoise_dual_frame(rmd_context *ctx, const Settings &st, size_t W, size_t H, const Frame *half, const double *feat, const double *feat_sq,
+                        const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts_a, const std::vector<uint32_t> &counts_b, const rmd_tile_rect *region,
+                        size_t n_region, double *out, double *err) {
+	const uint32_t w = (uint32_t)W, h = (uint32_t)H, n = (uint32_t)rects.size(), nr = (uint32_t)n_region;
+	const std::vector<uint32_t> counts_f = sum_counts(counts_a, counts_b); // (not read without the features)
+	const uint32_t *ca = counts_a.data(), *cb = counts_b.data(), *cf = counts_f.data();
+	if (st.denoise_dual_atrous && region && st.denoise_dual_atrous_region) {
+		check(rmd_denoise_atrous_dual_region(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, region, nr, st.denoise_atrous_levels,
+		                                     st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
+		      ctx, "rmd_denoise_atrous_dual_region");
+	} else if (st.denoise_dual_atrous) {
+		check(rmd_denoise_atrous_dual(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_atrous_levels, st.denoise_atrous_k,
+		                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
+		      ctx, "rmd_denoise_atrous_dual");
+	} else if (st.denoise_dual_select && !region) {
+		const rmd_denoise_candidate cands[2] = {{st.denoise_k, st.denoise_alpha, 0.0, 0.0, 0u, 0u}, {1.0, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, 1u, 0u}};
+		check(rmd_denoise_dual_select(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_radius, st.denoise_patch, cands, 2u,
+		                              2u, 2u, out, err, nullptr, nullptr),
+		      ctx, "rmd_denoise_dual_select");
+	} else if (feat && region) {
+		check(rmd_denoise_dual_guided_region(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, region, nr, st.denoise_radius,
+		                                     st.denoise_patch, st.denoise_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
+		      ctx, "rmd_denoise_dual_guided_region");
+	} else if (feat) {
+		check(rmd_denoise_dual_guided(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_radius, st.denoise_patch, st.denoise_k,
+		                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
+		      ctx, "rmd_denoise_dual_guided");
+	} else if (region) {
+		check(rmd_denoise_dual_region(ctx, half[0], half[1], half[2], half[3], w, h, rects.data(), ca, cb, n, region, nr, st.denoise_radius, st.denoise_patch, st.denoise_k,
+		                              st.denoise_alpha, out, err),
+		      ctx, "rmd_denoise_dual_region");
+	} else {
+		check(rmd_denoise_dual(ctx, half[0], half[1], half[2], half[3], w, h, rects.data(), ca, cb, n, st.denoise_radius, st.denoise_patch, st.denoise_k, st.denoise_alpha, out,
+		                       err),
+		      ctx, "rmd_denoise_dual");
+	}
+}
+
+// What both kinds of worker hold while they run: their GPU's context, the scene on it, and what every launch takes.  The frames are the derived
+// structs' members, so they are freed first, then the scene, then the context.
+struct Worker {
+	TaskHandle::Shared &sh;
+	const Settings st;
+	const size_t W, H;
+	Context ctx;
+	DeviceScene dscene;
+	const rmd_camera cam;
+	const uint32_t flags;
+	Worker(TaskHandle::Shared &sh, int device, const Scene &scene, const Settings &st)
+	    : sh(sh), st(st), W(st.camera_settings.backbuffer_width), H(st.camera_settings.backbuffer_height), ctx(device), dscene(ctx, scene), cam(camera_pod(st)),
+	      flags(render_flags(st)) {}
+	Frame frame(bool wanted = true, Frame::Kind kind = Frame::Colour) { return wanted ? Frame(ctx, W, H, kind) : Frame(); } // zeroed: a fresh tile's sums
+};
+
 // One worker = one GPU.  Pops a batch of tiles, adds `step` samples to each with ONE rmd_render_tiles call per sample count, then reports them
 // finished or re-queues them (src/trace.rs:188-221).  The tiles' sums stay in this GPU's framebuffer; only what a message carries is downloaded,
 // on the copy stream, while the next batch renders (the messages of batch k are sent while batch k + 1 runs).
-void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, size_t workers, Scene scene, Settings st, size_t batch) {
-	rmd_context *ctx = nullptr;
-	rmd_scene *dscene = nullptr;
-	double *fb = nullptr, *fb_sq = nullptr; // fb_sq: the sums of squares of an adaptive or denoised render
-	double *fb_preview = nullptr;           // settings.preview_denoise: the filtered means of a preview
-	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
+struct TileWorker : Worker {
+	const int me;
+	const size_t workers, batch;
+	// previews (one worker: render_tiled): every batch is then one pass over all live tiles, which all hold the same count
+	const bool preview, preview_filtered, adaptive, moments;
+	const size_t step;
+	Frame fb, fb_sq;    // fb_sq: the sums of squares of an adaptive or denoised render
+	Frame fb_preview;   // settings.preview_denoise: the filtered means of a preview
+	std::shared_ptr<BlockPool> pool = BlockPool::shared(); // process-wide: page-locking 50 MB costs about as much as moving them
+	std::vector<rmd_tile_rect> early_rects; // previews: the tiles that finished early and the counts they finished with
+	std::vector<uint32_t> early_counts;
+	size_t passes = 0;
 	// a batch whose download is on its way: the tiles that become messages, in message order
 	struct Pending {
 		std::vector<Message> messages;
@@ -226,238 +407,217 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 		size_t taken = 0;          // tiles of the batch that were neither finished nor re-queued at once (they leave `in_flight` now)
 	};
 	std::optional<Pending> pending;
-	auto flush = [&]() { // the previous batch's download has to arrive before its messages can be sent
-		if (!pending) return;
-		check(rmd_context_wait_transfers(ctx), ctx, "rmd_context_wait_transfers");
-		std::lock_guard<std::mutex> lock(sh->m);
-		for (Message &m : pending->messages) sh->channel.push_back(std::move(m));
-		for (Tile &t : pending->requeue) sh->queue.push_back(std::move(t));
-		sh->in_flight -= pending->taken;
-		pending.reset();
-		sh->cv.notify_all();
+	struct Fate {
+		bool finished, progressed; // the tile is done (:211-212); it goes on and this pass sends a snapshot of it (:217-219)
 	};
-	try {
-		const auto t_setup = std::chrono::steady_clock::now();
-		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
-		std::vector<rmd_object> objs;
-		std::vector<rmd_grid_desc> grids;
-		flatten(scene, objs, grids);
-		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
-		check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb), ctx, "rmd_framebuffer_alloc"); // zeroed: a fresh tile's sums
-		// previews (one worker: render_tiled): every loop below is then one pass over all live tiles, which all hold the same count
-		const bool preview = st.preview_every > 0, preview_filtered = preview && st.preview_denoise;
-		const bool adaptive = st.adaptive_threshold > 0.0, moments = adaptive || st.denoise || preview_filtered;
-		if (moments) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_sq), ctx, "rmd_framebuffer_alloc");
-		if (preview_filtered) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_preview), ctx, "rmd_framebuffer_alloc");
-		std::vector<rmd_tile_rect> early_rects; // previews: the tiles that finished early and the counts they finished with
-		std::vector<uint32_t> early_counts;
-		size_t passes = 0;
-		{
-			std::lock_guard<std::mutex> lock(sh->m);
-			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
-		}
-		rmd_camera cam;
-		std::memset(&cam, 0, sizeof(cam));
-		cam.backbuffer_width = (uint32_t)W, cam.backbuffer_height = (uint32_t)H, cam.fov_vert = st.camera_settings.fov_vert;
-		for (int a = 0; a < 3; a++) cam.position[a] = st.camera_settings.transform.position[a];
-		cam.focal_length = st.camera_settings.focal_length, cam.aperture_radius = st.camera_settings.aperture_radius;
-		const uint32_t flags = (st.use_dof ? RMD_RENDER_DOF : 0u) | (st.end_black_paths ? RMD_RENDER_END_BLACK_PATHS : 0u); // 0 = the reference's loop: pinhole (:199), every sample identical
-		const size_t step = st.samples_per_iteration ? st.samples_per_iteration : st.sample_count;
-		std::shared_ptr<BlockPool> pool = BlockPool::shared(); // process-wide: page-locking 50 MB costs about as much as moving them
+
+	TileWorker(TaskHandle::Shared &sh, int device, int me, size_t workers, const Scene &scene, const Settings &st, size_t batch)
+	    : Worker(sh, device, scene, st), me(me), workers(workers), batch(batch), preview(st.preview_every > 0), preview_filtered(preview && st.preview_denoise),
+	      adaptive(st.adaptive_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered),
+	      step(st.samples_per_iteration ? st.samples_per_iteration : st.sample_count), fb(frame()), fb_sq(frame(moments)), fb_preview(frame(preview_filtered)) {}
+
+	void run() {
 		for (;;) {
-			std::vector<Tile> mine;
-			{
-				// try_pop (:189).  The reference's worker leaves as soon as the queue is empty (:191-194); with one GPU call
-				// per batch a queue that is only momentarily empty — the other workers hold every tile and will re-queue them
-				// for the next progressive pass — would collapse the pool to one GPU, so a worker leaves only when no tile is
-				// queued AND none is in flight.
-				std::unique_lock<std::mutex> lock(sh->m);
-				if (sh->queue.empty() && pending) { // nothing to start: send what is pending (it may re-queue tiles or end the render)
-					lock.unlock();
-					flush();
-					lock.lock();
-				}
-				sh->cv.wait(lock, [&] { return !sh->queue.empty() || sh->in_flight == 0 || !sh->error.empty(); });
-				while (sh->error.empty() && !sh->queue.empty() && mine.size() < batch) {
-					mine.push_back(std::move(sh->queue.front()));
-					sh->queue.pop_front();
-				}
-				sh->in_flight += mine.size();
-			}
+			std::vector<Tile> mine = take_batch();
 			if (mine.empty()) break;
 			passes++;
-			// tiles that arrive with their sums in RAM (another GPU rendered their earlier passes): into this GPU's framebuffer
-			{
-				std::vector<rmd_tile_rect> rects;
-				std::vector<double> packed, packed_sq;
-				for (Tile &t : mine)
-					if (t.resident != me && t.sample_count != 0) {
-						rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
-						const double *src = reinterpret_cast<const double *>(t.data.data());
-						packed.insert(packed.end(), src, src + t.data.size() * 3);
-						if (moments) {
-							const double *sq = reinterpret_cast<const double *>(t.data_sq.data());
-							packed_sq.insert(packed_sq.end(), sq, sq + t.data_sq.size() * 3);
-						}
-					}
-				if (!rects.empty()) check(rmd_framebuffer_upload_tiles(ctx, packed.data(), fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
-				if (!rects.empty() && moments)
-					check(rmd_framebuffer_upload_tiles(ctx, packed_sq.data(), fb_sq, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
-			}
-			// tiles of one batch may be at different sample counts: one launch per count (enqueued, not waited for)
-			std::map<size_t, std::vector<size_t>> by_count;
-			for (size_t i = 0; i < mine.size(); i++) by_count[mine[i].sample_count].push_back(i);
-			for (auto &grp : by_count) {
-				const size_t begin = grp.first, n = std::min(step, st.sample_count - begin);
-				std::vector<rmd_tile_rect> rects;
-				for (size_t i : grp.second) rects.push_back(rmd_tile_rect{(uint32_t)mine[i].left, (uint32_t)mine[i].top, (uint32_t)mine[i].width, (uint32_t)mine[i].height});
-				rmd_settings rs;
-				std::memset(&rs, 0, sizeof(rs));
-				rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)begin, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
-				if (moments) check(rmd_render_tiles_moments_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb, fb_sq), ctx, "rmd_render_tiles_moments");
-				else check(rmd_render_tiles_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb), ctx, "rmd_render_tiles");
-				for (size_t i : grp.second) mine[i].sample_count += n, mine[i].resident = me, mine[i].data = TileData(), mine[i].data_sq = TileData(); // :207 — the sums are on this GPU now
-			}
-			// the previous batch's messages go out while this batch renders
-			flush();
-			// adaptive: the error of every tile this pass has left below sample_count, one rmd_tile_error per sample count (it waits for the pass); a
-			// tile at or below the threshold is finished at the samples it has
-			std::vector<bool> converged(mine.size(), false);
-			if (adaptive) {
-				std::map<size_t, std::vector<size_t>> live;
-				for (size_t i = 0; i < mine.size(); i++)
-					if (mine[i].sample_count < st.sample_count) live[mine[i].sample_count].push_back(i);
-				for (auto &grp : live) {
-					std::vector<rmd_tile_rect> rects;
-					for (size_t i : grp.second) rects.push_back(rmd_tile_rect{(uint32_t)mine[i].left, (uint32_t)mine[i].top, (uint32_t)mine[i].width, (uint32_t)mine[i].height});
-					std::vector<double> err(rects.size());
-					check(rmd_tile_error(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, (uint32_t)grp.first, st.adaptive_floor, rects.data(), (uint32_t)rects.size(), err.data()), ctx,
-					      "rmd_tile_error");
-					for (size_t k = 0; k < err.size(); k++) converged[grp.second[k]] = err[k] <= st.adaptive_threshold;
-				}
-			}
-			auto is_finished = [&](size_t i) { return mine[i].sample_count == st.sample_count || converged[i]; };
-			// what of this batch has to come to the host: finished tiles (:211-212), progress snapshots (:217-219), and — with several GPUs — every
-			// tile that goes back to the shared queue (another GPU may take it next)
+			upload_arrivals(mine);
+			launch(mine);
+			flush(); // the previous batch's messages go out while this batch renders
+			const std::vector<Fate> fate = decide(mine);
+			start_downloads(mine, fate);
 			Pending next;
-			std::vector<rmd_tile_rect> rects;
-			std::vector<size_t> want;
 			std::vector<Tile> resident_requeue;
-			size_t pixels = 0;
-			// the sums of squares: of the tiles that go back to the shared queue (adaptive or denoised, several GPUs) and of the finished tiles (denoised)
-			std::vector<rmd_tile_rect> rects_sq;
-			std::vector<size_t> want_sq;
-			size_t pixels_sq = 0;
-			for (size_t i = 0; i < mine.size(); i++) {
-				Tile &t = mine[i];
-				const bool finished = is_finished(i);
-				const bool progressed = !finished && st.progress_tiles && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
-				if (finished || progressed || workers > 1) {
-					want.push_back(i);
-					rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
-					pixels += t.width * t.height;
-				}
-				if ((moments && !finished && workers > 1) || (st.denoise && finished)) {
-					want_sq.push_back(i);
-					rects_sq.push_back(rects.back());
-					pixels_sq += t.width * t.height;
-				}
-			}
-			if (!want.empty()) {
-				std::shared_ptr<void> block = pool->get(ctx, pixels * 24);
-				check(rmd_framebuffer_download_tiles_async(ctx, fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), static_cast<double *>(block.get())), ctx, "rmd_framebuffer_download_tiles");
-				Vector3 *p = static_cast<Vector3 *>(block.get());
-				for (size_t i : want) {
-					mine[i].data = TileData(block, p, mine[i].width * mine[i].height);
-					p += mine[i].width * mine[i].height;
-				}
-			}
-			if (!want_sq.empty()) {
-				std::shared_ptr<void> block = pool->get(ctx, pixels_sq * 24);
-				check(rmd_framebuffer_download_tiles_async(ctx, fb_sq, (uint32_t)W, (uint32_t)H, rects_sq.data(), (uint32_t)rects_sq.size(), static_cast<double *>(block.get())), ctx,
-				      "rmd_framebuffer_download_tiles");
-				Vector3 *p = static_cast<Vector3 *>(block.get());
-				for (size_t i : want_sq) {
-					mine[i].data_sq = TileData(block, p, mine[i].width * mine[i].height);
-					p += mine[i].width * mine[i].height;
-				}
-			}
-			for (size_t i = 0; i < mine.size(); i++) {
-				Tile &t = mine[i];
-				const bool finished = is_finished(i);
-				const bool progressed = !finished && st.progress_tiles && st.samples_per_iteration != 0 && t.sample_count % st.samples_per_iteration == 0;
-				if (finished) {
-					t.resident = -1;
-					next.messages.push_back(Message{Message::TileFinished, std::move(t)});
-					next.taken++;
-				} else if (workers > 1) { // back to the shared queue with its sums in RAM, once they have arrived
-					t.resident = -1;
-					if (progressed) {
-						Tile snapshot = t;
-						snapshot.data_sq = TileData(); // (the sums of squares stay with the scheduler)
-						next.messages.push_back(Message{Message::TileProgressed, std::move(snapshot)});
-					}
-					next.requeue.push_back(std::move(t));
-					next.taken++;
-				} else { // one GPU: the tile goes back to the queue at once, sums resident; its snapshot follows when it has arrived
-					if (progressed) {
-						Tile snapshot = t;
-						snapshot.resident = -1;
-						next.messages.push_back(Message{Message::TileProgressed, std::move(snapshot)});
-					}
-					t.data = TileData();
-					resident_requeue.push_back(std::move(t));
-				}
-			}
-			if (preview) {
-				// behind this pass's messages: the whole frame, the tiles that go on at this pass's count, those that finished early at their own
-				const size_t done = resident_requeue.empty() ? st.sample_count : resident_requeue.front().sample_count;
-				std::vector<rmd_tile_rect> live_rects;
-				for (const Message &m : next.messages)
-					if (m.kind == Message::TileFinished && m.tile.sample_count < st.sample_count) {
-						early_rects.push_back(rmd_tile_rect{(uint32_t)m.tile.left, (uint32_t)m.tile.top, (uint32_t)m.tile.width, (uint32_t)m.tile.height});
-						early_counts.push_back((uint32_t)m.tile.sample_count);
-					}
-				for (const Tile &t : resident_requeue) live_rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
-				if (!live_rects.empty() && passes % st.preview_every == 0) {
-					std::vector<rmd_tile_rect> rects(early_rects);
-					std::vector<uint32_t> counts(early_counts);
-					rects.insert(rects.end(), live_rects.begin(), live_rects.end());
-					counts.insert(counts.end(), live_rects.size(), (uint32_t)done);
-					const double *src = fb;
-					if (preview_filtered) {
-						check(rmd_denoise_atrous(ctx, fb, fb_sq, nullptr, nullptr, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
-						                         st.denoise_atrous_levels, st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fb_preview),
-						      ctx, "rmd_denoise_atrous");
-						src = fb_preview, counts.assign(rects.size(), 1u); // (means)
-					}
-					next.messages.push_back(preview_message(ctx, src, nullptr, W, H, rects, counts, st, passes, done));
-				}
-			}
-			{
-				std::lock_guard<std::mutex> lock(sh->m);
-				sh->in_flight -= resident_requeue.size();
-				for (Tile &t : resident_requeue) sh->queue.push_back(std::move(t));
-				sh->cv.notify_all();
-			}
-			pending = std::move(next);
+			sort_batch(mine, fate, next, resident_requeue);
+			if (preview) add_preview(next, resident_requeue);
+			publish(resident_requeue, std::move(next));
 		}
 		flush();
 		check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize"); // a device fault of the last launch surfaces here at the latest
-	} catch (const std::exception &e) {
-		std::lock_guard<std::mutex> lock(sh->m);
-		if (sh->error.empty()) sh->error = e.what(); // the waiting workers see it and leave
-		sh->cv.notify_all();
 	}
-	if (fb) rmd_framebuffer_free(ctx, fb);
-	if (fb_sq) rmd_framebuffer_free(ctx, fb_sq);
-	if (fb_preview) rmd_framebuffer_free(ctx, fb_preview);
-	rmd_scene_destroy(dscene);
-	rmd_context_destroy(ctx);
-	std::lock_guard<std::mutex> lock(sh->m);
-	sh->alive--; // :192
-	sh->cv.notify_all();
-}
+
+	void flush() { // the previous batch's download has to arrive before its messages can be sent
+		if (!pending) return;
+		check(rmd_context_wait_transfers(ctx), ctx, "rmd_context_wait_transfers");
+		std::lock_guard<std::mutex> lock(sh.m);
+		for (Message &m : pending->messages) sh.channel.push_back(std::move(m));
+		for (Tile &t : pending->requeue) sh.queue.push_back(std::move(t));
+		sh.in_flight -= pending->taken;
+		pending.reset();
+		sh.cv.notify_all();
+	}
+
+	std::vector<Tile> take_batch() {
+		// try_pop (:189).  The reference's worker leaves as soon as the queue is empty (:191-194); with one GPU call
+		// per batch a queue that is only momentarily empty — the other workers hold every tile and will re-queue them
+		// for the next progressive pass — would collapse the pool to one GPU, so a worker leaves only when no tile is
+		// queued AND none is in flight.
+		std::vector<Tile> mine;
+		std::unique_lock<std::mutex> lock(sh.m);
+		if (sh.queue.empty() && pending) { // nothing to start: send what is pending (it may re-queue tiles or end the render)
+			lock.unlock();
+			flush();
+			lock.lock();
+		}
+		sh.cv.wait(lock, [&] { return !sh.queue.empty() || sh.in_flight == 0 || !sh.error.empty(); });
+		while (sh.error.empty() && !sh.queue.empty() && mine.size() < batch) {
+			mine.push_back(std::move(sh.queue.front()));
+			sh.queue.pop_front();
+		}
+		sh.in_flight += mine.size();
+		return mine;
+	}
+
+	// tiles that arrive with their sums in RAM (another GPU rendered their earlier passes): into this GPU's framebuffer
+	void upload_arrivals(const std::vector<Tile> &mine) {
+		std::vector<rmd_tile_rect> rects;
+		std::vector<double> packed, packed_sq;
+		for (const Tile &t : mine)
+			if (t.resident != me && t.sample_count != 0) {
+				rects.push_back(rect_of(t));
+				const double *src = reinterpret_cast<const double *>(t.data.data());
+				packed.insert(packed.end(), src, src + t.data.size() * 3);
+				if (moments) {
+					const double *sq = reinterpret_cast<const double *>(t.data_sq.data());
+					packed_sq.insert(packed_sq.end(), sq, sq + t.data_sq.size() * 3);
+				}
+			}
+		if (!rects.empty()) check(rmd_framebuffer_upload_tiles(ctx, packed.data(), fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
+		if (!rects.empty() && moments)
+			check(rmd_framebuffer_upload_tiles(ctx, packed_sq.data(), fb_sq, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size()), ctx, "rmd_framebuffer_upload_tiles");
+	}
+
+	// tiles of one batch may be at different sample counts: one launch per count (enqueued, not waited for)
+	void launch(std::vector<Tile> &mine) {
+		std::map<size_t, std::vector<size_t>> by_count;
+		for (size_t i = 0; i < mine.size(); i++) by_count[mine[i].sample_count].push_back(i);
+		for (auto &grp : by_count) {
+			const size_t begin = grp.first, n = std::min(step, st.sample_count - begin);
+			const std::vector<rmd_tile_rect> rects = rects_of(mine, grp.second);
+			const rmd_settings rs = settings_pod(st, begin, n, flags);
+			if (moments) check(rmd_render_tiles_moments_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb, fb_sq), ctx, "rmd_render_tiles_moments");
+			else check(rmd_render_tiles_async(ctx, dscene, &cam, &rs, rects.data(), (uint32_t)rects.size(), fb), ctx, "rmd_render_tiles");
+			for (size_t i : grp.second) mine[i].sample_count += n, mine[i].resident = me, mine[i].data = TileData(), mine[i].data_sq = TileData(); // :207 — the sums are on this GPU now
+		}
+	}
+
+	// adaptive: the error of every tile this pass has left below sample_count, one rmd_tile_error per sample count (it waits for the pass); a
+	// tile at or below the threshold is finished at the samples it has
+	std::vector<bool> converged_tiles(const std::vector<Tile> &mine) {
+		std::vector<bool> converged(mine.size(), false);
+		if (!adaptive) return converged;
+		std::map<size_t, std::vector<size_t>> live;
+		for (size_t i = 0; i < mine.size(); i++)
+			if (mine[i].sample_count < st.sample_count) live[mine[i].sample_count].push_back(i);
+		for (auto &grp : live) {
+			const std::vector<rmd_tile_rect> rects = rects_of(mine, grp.second);
+			std::vector<double> err(rects.size());
+			check(rmd_tile_error(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, (uint32_t)grp.first, st.adaptive_floor, rects.data(), (uint32_t)rects.size(), err.data()), ctx,
+			      "rmd_tile_error");
+			for (size_t k = 0; k < err.size(); k++) converged[grp.second[k]] = err[k] <= st.adaptive_threshold;
+		}
+		return converged;
+	}
+
+	std::vector<Fate> decide(const std::vector<Tile> &mine) {
+		const std::vector<bool> converged = converged_tiles(mine);
+		std::vector<Fate> fate(mine.size());
+		for (size_t i = 0; i < mine.size(); i++) {
+			const bool finished = mine[i].sample_count == st.sample_count || converged[i];
+			fate[i] = Fate{finished, !finished && st.progress_tiles && st.samples_per_iteration != 0 && mine[i].sample_count % st.samples_per_iteration == 0};
+		}
+		return fate;
+	}
+
+	// the tiles `want` of `from`, enqueued on the copy stream into one block of the pool; `field` of each of them becomes its view of that block
+	void download(const Frame &from, std::vector<Tile> &mine, const std::vector<size_t> &want, TileData Tile::*field) {
+		if (want.empty()) return;
+		const std::vector<rmd_tile_rect> rects = rects_of(mine, want);
+		std::shared_ptr<void> block = pool->get(ctx, pixels_of(rects) * 24);
+		check(rmd_framebuffer_download_tiles_async(ctx, from, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), static_cast<double *>(block.get())), ctx,
+		      "rmd_framebuffer_download_tiles");
+		Vector3 *p = static_cast<Vector3 *>(block.get());
+		for (size_t i : want) {
+			mine[i].*field = TileData(block, p, mine[i].width * mine[i].height);
+			p += mine[i].width * mine[i].height;
+		}
+	}
+
+	// what of this batch has to come to the host: finished tiles (:211-212), progress snapshots (:217-219), and — with several GPUs — every
+	// tile that goes back to the shared queue (another GPU may take it next)
+	void start_downloads(std::vector<Tile> &mine, const std::vector<Fate> &fate) {
+		std::vector<size_t> want;
+		// the sums of squares: of the tiles that go back to the shared queue (adaptive or denoised, several GPUs) and of the finished tiles (denoised)
+		std::vector<size_t> want_sq;
+		for (size_t i = 0; i < mine.size(); i++) {
+			if (fate[i].finished || fate[i].progressed || workers > 1) want.push_back(i);
+			if ((moments && !fate[i].finished && workers > 1) || (st.denoise && fate[i].finished)) want_sq.push_back(i);
+		}
+		download(fb, mine, want, &Tile::data);
+		download(fb_sq, mine, want_sq, &Tile::data_sq);
+	}
+
+	void sort_batch(std::vector<Tile> &mine, const std::vector<Fate> &fate, Pending &next, std::vector<Tile> &resident_requeue) {
+		for (size_t i = 0; i < mine.size(); i++) {
+			Tile &t = mine[i];
+			if (fate[i].finished) {
+				t.resident = -1;
+				next.messages.push_back(Message{Message::TileFinished, std::move(t)});
+				next.taken++;
+			} else if (workers > 1) { // back to the shared queue with its sums in RAM, once they have arrived
+				t.resident = -1;
+				if (fate[i].progressed) {
+					Tile snapshot = t;
+					snapshot.data_sq = TileData(); // (the sums of squares stay with the scheduler)
+					next.messages.push_back(Message{Message::TileProgressed, std::move(snapshot)});
+				}
+				next.requeue.push_back(std::move(t));
+				next.taken++;
+			} else { // one GPU: the tile goes back to the queue at once, sums resident; its snapshot follows when it has arrived
+				if (fate[i].progressed) {
+					Tile snapshot = t;
+					snapshot.resident = -1;
+					next.messages.push_back(Message{Message::TileProgressed, std::move(snapshot)});
+				}
+				t.data = TileData();
+				resident_requeue.push_back(std::move(t));
+			}
+		}
+	}
+
+	// behind this pass's messages: the whole frame, the tiles that go on at this pass's count, those that finished early at their own
+	void add_preview(Pending &next, const std::vector<Tile> &resident_requeue) {
+		const size_t done = resident_requeue.empty() ? st.sample_count : resident_requeue.front().sample_count;
+		for (const Message &m : next.messages)
+			if (m.kind == Message::TileFinished && m.tile.sample_count < st.sample_count) {
+				early_rects.push_back(rect_of(m.tile));
+				early_counts.push_back((uint32_t)m.tile.sample_count);
+			}
+		if (resident_requeue.empty() || passes % st.preview_every != 0) return;
+		std::vector<rmd_tile_rect> rects(early_rects);
+		std::vector<uint32_t> counts(early_counts);
+		for (const Tile &t : resident_requeue) rects.push_back(rect_of(t));
+		counts.insert(counts.end(), resident_requeue.size(), (uint32_t)done);
+		const double *src = fb;
+		if (preview_filtered) {
+			check(rmd_denoise_atrous(ctx, fb, fb_sq, nullptr, nullptr, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.denoise_atrous_levels,
+			                         st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fb_preview),
+			      ctx, "rmd_denoise_atrous");
+			src = fb_preview, counts.assign(rects.size(), 1u); // (means)
+		}
+		next.messages.push_back(preview_message(ctx, src, nullptr, W, H, rects, counts, st, passes, done));
+	}
+
+	void publish(std::vector<Tile> &resident_requeue, Pending &&next) {
+		{
+			std::lock_guard<std::mutex> lock(sh.m);
+			sh.in_flight -= resident_requeue.size();
+			for (Tile &t : resident_requeue) sh.queue.push_back(std::move(t));
+			sh.cv.notify_all();
+		}
+		pending = std::move(next);
+	}
+};
 
 // settings.denoise_dual: the one worker of a dual-buffer render, a plain loop over passes (every live tile takes every pass).  Four framebuffers:
 // pass j, counted from 0, adds its samples to half A (fbs 0, 1) when j is even and to half B (fbs 2, 3) when j is odd.  With
@@ -468,126 +628,32 @@ void worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, int me, siz
 // features of its samples [done, done + n) — a tile's features then hold count_a + count_b samples —, and the check is rmd_denoise_dual_guided_region.
 // With denoise_dual_atrous the check is rmd_denoise_atrous_dual on the whole frame, at the same rects, counts and feature buffers; with
 // denoise_dual_atrous_region it is rmd_denoise_atrous_dual_region over the live tiles, which gives the pixels read here the same bytes.
-void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene scene, Settings st) {
-	rmd_context *ctx = nullptr;
-	rmd_scene *dscene = nullptr;
-	double *fbs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
-	double *feat[2] = {nullptr, nullptr};                                    // adaptive with denoise_dual_features: the feature sums and sums of squares
-	double *fb_preview = nullptr;                                            // settings.preview_denoise: the filtered means of a preview
-	const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
-	try {
-		const auto t_setup = std::chrono::steady_clock::now();
-		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
-		std::vector<rmd_object> objs;
-		std::vector<rmd_grid_desc> grids;
-		flatten(scene, objs, grids);
-		check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
-		const bool adaptive = st.adaptive_denoised_threshold > 0.0;
-		for (int i = 0; i < (adaptive ? 6 : 4); i++) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fbs[i]), ctx, "rmd_framebuffer_alloc");
-		const bool guided = adaptive && st.denoise_dual_features; // (without the adaptive check nothing here would read the features: await() renders its own)
-		if (guided)
-			for (double *&d : feat) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
-		if (st.preview_every > 0 && st.preview_denoise) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &fb_preview), ctx, "rmd_framebuffer_alloc");
-		{
-			std::lock_guard<std::mutex> lock(sh->m);
-			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
-		}
-		rmd_camera cam;
-		std::memset(&cam, 0, sizeof(cam));
-		cam.backbuffer_width = (uint32_t)W, cam.backbuffer_height = (uint32_t)H, cam.fov_vert = st.camera_settings.fov_vert;
-		for (int a = 0; a < 3; a++) cam.position[a] = st.camera_settings.transform.position[a];
-		cam.focal_length = st.camera_settings.focal_length, cam.aperture_radius = st.camera_settings.aperture_radius;
-		const uint32_t flags = (st.use_dof ? RMD_RENDER_DOF : 0u) | (st.end_black_paths ? RMD_RENDER_END_BLACK_PATHS : 0u);
-		std::vector<rmd_tile_rect> live = generate_tiles(W, H, st.tile_size);
-		std::vector<rmd_tile_rect> done_rects;
-		std::vector<uint32_t> done_a, done_b;
-		std::vector<Message> finished;
-		size_t n_half[2] = {0, 0}, done = 0, j = 0;
-		// the rects' pixels of one framebuffer, tile after tile in Tile.data layout
-		auto download = [&](double *fb, const std::vector<rmd_tile_rect> &rects) {
-			size_t pixels = 0;
-			for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
-			std::vector<Vector3> packed(pixels);
-			if (pixels)
-				check(rmd_framebuffer_download_tiles(ctx, fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), reinterpret_cast<double *>(packed.data())), ctx,
-				      "rmd_framebuffer_download_tiles");
-			return packed;
-		};
-		auto finish = [&](const std::vector<rmd_tile_rect> &rects, const std::vector<double> &errors) {
-			if (rects.empty()) return;
-			std::vector<Vector3> packed[4];
-			for (int i = 0; i < 4; i++) packed[i] = download(fbs[i], rects);
-			size_t at = 0;
-			for (size_t k = 0; k < rects.size(); k++) {
-				const rmd_tile_rect &r = rects[k];
-				const size_t n = (size_t)r.width * r.height;
-				Tile t;
-				t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height;
-				t.count_a = n_half[0], t.count_b = n_half[1], t.sample_count = n_half[0] + n_half[1];
-				if (!errors.empty()) t.error = errors[k];
-				TileData *half[4] = {&t.data_a, &t.data_sq_a, &t.data_b, &t.data_sq_b};
-				for (int i = 0; i < 4; i++) {
-					*half[i] = TileData(n);
-					std::copy(packed[i].begin() + (long)at, packed[i].begin() + (long)(at + n), half[i]->data());
-				}
-				t.data = TileData(n), t.data_sq = TileData(n);
-				for (size_t p = 0; p < n; p++)
-					for (int c = 0; c < 3; c++) t.data[p][c] = t.data_a[p][c] + t.data_b[p][c], t.data_sq[p][c] = t.data_sq_a[p][c] + t.data_sq_b[p][c];
-				at += n;
-				finished.push_back(Message{Message::TileFinished, std::move(t)});
-				done_rects.push_back(r), done_a.push_back((uint32_t)n_half[0]), done_b.push_back((uint32_t)n_half[1]);
-			}
-		};
+struct DualWorker : Worker {
+	const bool adaptive;
+	const bool guided; // (without the adaptive check nothing here would read the features: await() renders its own)
+	Frame fbs[6];      // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
+	Frame feat[2];     // guided: the feature sums and sums of squares
+	Frame fb_preview;  // settings.preview_denoise: the filtered means of a preview
+	Settings preview_st; // ... which are always the fast filter's, whichever filter the settings select for the frame: `st` with denoise_dual_atrous on
+	std::vector<rmd_tile_rect> live, done_rects;
+	std::vector<uint32_t> done_a, done_b;
+	std::vector<Message> finished;
+	size_t n_half[2] = {0, 0}, done = 0, j = 0;
+
+	DualWorker(TaskHandle::Shared &sh, int device, const Scene &scene, const Settings &st)
+	    : Worker(sh, device, scene, st), adaptive(st.adaptive_denoised_threshold > 0.0), guided(adaptive && st.denoise_dual_features), preview_st(st),
+	      live(generate_tiles(W, H, st.tile_size)) {
+		for (int i = 0; i < (adaptive ? 6 : 4); i++) fbs[i] = frame();
+		for (Frame &f : feat) f = frame(guided, Frame::Features);
+		fb_preview = frame(st.preview_every > 0 && st.preview_denoise);
+		preview_st.denoise_dual_atrous = true;
+	}
+
+	void run() {
 		while (done < st.sample_count && !live.empty()) {
-			const size_t n = std::min(st.samples_per_iteration, st.sample_count - done), half = j & 1;
-			rmd_settings rs;
-			std::memset(&rs, 0, sizeof(rs));
-			rs.bounce_limit = (uint32_t)st.bounce_limit, rs.sample_begin = (uint32_t)done, rs.sample_count = (uint32_t)n, rs.seed = st.seed, rs.flags = flags;
-			check(rmd_render_tiles_moments(ctx, dscene, &cam, &rs, live.data(), (uint32_t)live.size(), fbs[2 * half], fbs[2 * half + 1]), ctx, "rmd_render_tiles_moments");
-			if (guided) {
-				rmd_settings fs = rs;
-				fs.flags = st.use_dof ? RMD_RENDER_DOF : 0u; // (as render_features_on)
-				check(rmd_render_features(ctx, dscene, &cam, &fs, live.data(), (uint32_t)live.size(), feat[0], feat[1]), ctx, "rmd_render_features");
-			}
-			done += n, j++, n_half[half] += n;
+			render_pass();
 			if (done >= st.sample_count) break;
-			std::vector<double> errors;
-			if (adaptive && j % 2 == 0 && done >= st.adaptive_min_samples) {
-				std::vector<rmd_tile_rect> rects(done_rects);
-				std::vector<uint32_t> ca(done_a), cb(done_b);
-				rects.insert(rects.end(), live.begin(), live.end());
-				ca.insert(ca.end(), live.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), live.size(), (uint32_t)n_half[1]);
-				// only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
-				if (st.denoise_dual_atrous && st.denoise_dual_atrous_region) { // the live tiles' pixels, with the whole-frame call's bytes (cf not read without the features)
-					std::vector<uint32_t> cf(ca);
-					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
-					check(rmd_denoise_atrous_dual_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
-					                                     rects.data(), ca.data(), cb.data(), cf.data(), (uint32_t)rects.size(), live.data(), (uint32_t)live.size(),
-					                                     st.denoise_atrous_levels, st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fbs[4],
-					                                     fbs[5]),
-					      ctx, "rmd_denoise_atrous_dual_region");
-				} else if (st.denoise_dual_atrous) { // the whole frame; the region form is behind denoise_dual_atrous_region (cf not read without the features)
-					std::vector<uint32_t> cf(ca);
-					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
-					check(rmd_denoise_atrous_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
-					                              rects.data(), ca.data(), cb.data(), cf.data(), (uint32_t)rects.size(), st.denoise_atrous_levels, st.denoise_atrous_k,
-					                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fbs[4], fbs[5]),
-					      ctx, "rmd_denoise_atrous_dual");
-				} else if (guided) {
-					std::vector<uint32_t> cf(ca);
-					for (size_t i = 0; i < cf.size(); i++) cf[i] += cb[i];
-					check(rmd_denoise_dual_guided_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], feat[0], feat[1], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(),
-					                                     cf.data(), (uint32_t)rects.size(), live.data(), (uint32_t)live.size(), st.denoise_radius, st.denoise_patch,
-					                                     st.denoise_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fbs[4], fbs[5]),
-					      ctx, "rmd_denoise_dual_guided_region");
-				} else {
-					check(rmd_denoise_dual_region(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, rects.data(), ca.data(), cb.data(), (uint32_t)rects.size(), live.data(),
-					                              (uint32_t)live.size(), st.denoise_radius, st.denoise_patch, st.denoise_k, st.denoise_alpha, fbs[4], fbs[5]),
-					      ctx, "rmd_denoise_dual_region");
-				}
-				errors.resize(live.size());
-				check(rmd_tile_error_dual(ctx, fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), errors.data()), ctx, "rmd_tile_error_dual");
-			}
+			const std::vector<double> errors = adaptive_check(); // (empty: this pass is not followed by a check)
 			std::vector<rmd_tile_rect> converged, still;
 			std::vector<double> converged_err, still_err;
 			for (size_t k = 0; k < live.size(); k++) {
@@ -596,64 +662,141 @@ void dual_worker_main(std::shared_ptr<TaskHandle::Shared> sh, int device, Scene 
 				if (!errors.empty()) (conv ? converged_err : still_err).push_back(errors[k]);
 			}
 			finish(converged, converged_err);
-			// progress snapshots of the tiles that go on: the two halves' sums added
-			std::vector<Vector3> pa, pb;
-			if (st.progress_tiles) pa = download(fbs[0], still), pb = download(fbs[2], still);
-			std::vector<Message> snapshots;
-			size_t at = 0;
-			for (size_t k = 0; st.progress_tiles && k < still.size(); k++) {
-				const rmd_tile_rect &r = still[k];
-				const size_t px = (size_t)r.width * r.height;
-				Tile t;
-				t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height, t.sample_count = done;
-				if (!still_err.empty()) t.error = still_err[k];
-				t.data = TileData(px);
-				for (size_t p = 0; p < px; p++)
-					for (int c = 0; c < 3; c++) t.data[p][c] = pa[at + p][c] + pb[at + p][c];
-				at += px;
-				snapshots.push_back(Message{Message::TileProgressed, std::move(t)});
-			}
-			if (!still.empty() && st.preview_every > 0 && j % st.preview_every == 0) {
-				// the whole frame: finished tiles at the counts they finished with, live ones at n_A + n_B, the two halves' sums added on the device
-				std::vector<rmd_tile_rect> rects(done_rects);
-				std::vector<uint32_t> ca(done_a), cb(done_b);
-				rects.insert(rects.end(), still.begin(), still.end());
-				ca.insert(ca.end(), still.size(), (uint32_t)n_half[0]), cb.insert(cb.end(), still.size(), (uint32_t)n_half[1]);
-				std::vector<uint32_t> both(ca);
-				for (size_t i = 0; i < both.size(); i++) both[i] += cb[i];
-				if (fb_preview) {
-					check(rmd_denoise_atrous_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], guided ? feat[0] : nullptr, guided ? feat[1] : nullptr, (uint32_t)W, (uint32_t)H,
-					                              rects.data(), ca.data(), cb.data(), both.data(), (uint32_t)rects.size(), st.denoise_atrous_levels, st.denoise_atrous_k,
-					                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, fb_preview, nullptr),
-					      ctx, "rmd_denoise_atrous_dual");
-					snapshots.push_back(preview_message(ctx, fb_preview, nullptr, W, H, rects, std::vector<uint32_t>(rects.size(), 1u), st, j, done)); // (means)
-				} else {
-					snapshots.push_back(preview_message(ctx, fbs[0], fbs[2], W, H, rects, both, st, j, done));
-				}
-			}
-			{
-				std::lock_guard<std::mutex> lock(sh->m);
-				for (Message &m : snapshots) sh->channel.push_back(std::move(m));
-				sh->cv.notify_all();
-			}
+			std::vector<Message> out = snapshots(still, still_err);
+			if (!still.empty() && st.preview_every > 0 && j % st.preview_every == 0) out.push_back(preview(still));
+			send(out);
 			live = std::move(still);
 		}
 		finish(live, {});
-		std::lock_guard<std::mutex> lock(sh->m);
-		for (Message &m : finished) sh->channel.push_back(std::move(m));
+		send(finished);
+	}
+
+	void send(std::vector<Message> &messages) {
+		std::lock_guard<std::mutex> lock(sh.m);
+		for (Message &m : messages) sh.channel.push_back(std::move(m));
+		sh.cv.notify_all();
+	}
+
+	void render_pass() {
+		const size_t n = std::min(st.samples_per_iteration, st.sample_count - done), half = j & 1;
+		const rmd_settings rs = settings_pod(st, done, n, flags);
+		check(rmd_render_tiles_moments(ctx, dscene, &cam, &rs, live.data(), (uint32_t)live.size(), fbs[2 * half], fbs[2 * half + 1]), ctx, "rmd_render_tiles_moments");
+		if (guided) {
+			const rmd_settings fs = settings_pod(st, done, n, feature_flags(st));
+			check(rmd_render_features(ctx, dscene, &cam, &fs, live.data(), (uint32_t)live.size(), feat[0], feat[1]), ctx, "rmd_render_features");
+		}
+		done += n, j++, n_half[half] += n;
+	}
+
+	// the whole frame: finished tiles at the counts they finished with, `tiles` — the live ones — at n_A and n_B
+	struct FrameCounts {
+		std::vector<rmd_tile_rect> rects;
+		std::vector<uint32_t> a, b;
+	};
+	FrameCounts whole_frame(const std::vector<rmd_tile_rect> &tiles) const {
+		FrameCounts f{done_rects, done_a, done_b};
+		f.rects.insert(f.rects.end(), tiles.begin(), tiles.end());
+		f.a.insert(f.a.end(), tiles.size(), (uint32_t)n_half[0]), f.b.insert(f.b.end(), tiles.size(), (uint32_t)n_half[1]);
+		return f;
+	}
+
+	// the live tiles' rmd_tile_error_dual after the filter the settings select; only the live tiles' filtered pixels are read, so they are the filter's region
+	std::vector<double> adaptive_check() {
+		std::vector<double> errors;
+		if (!(adaptive && j % 2 == 0 && done >= st.adaptive_min_samples)) return errors;
+		const FrameCounts f = whole_frame(live);
+		denoise_dual_frame(ctx, st, W, H, fbs, feat[0], feat[1], f.rects, f.a, f.b, live.data(), live.size(), fbs[4], fbs[5]);
+		errors.resize(live.size());
+		check(rmd_tile_error_dual(ctx, fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), errors.data()), ctx, "rmd_tile_error_dual");
+		return errors;
+	}
+
+	// the rects' pixels of one framebuffer, tile after tile in Tile.data layout
+	std::vector<Vector3> download(const Frame &fb, const std::vector<rmd_tile_rect> &rects) {
+		const size_t pixels = pixels_of(rects);
+		std::vector<Vector3> packed(pixels);
+		if (pixels)
+			check(rmd_framebuffer_download_tiles(ctx, fb, (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), reinterpret_cast<double *>(packed.data())), ctx,
+			      "rmd_framebuffer_download_tiles");
+		return packed;
+	}
+
+	// the TileFinished messages of `rects` (kept for the end) with both halves; they are in every later check and preview at these counts
+	void finish(const std::vector<rmd_tile_rect> &rects, const std::vector<double> &errors) {
+		if (rects.empty()) return;
+		std::vector<Vector3> packed[4];
+		for (int i = 0; i < 4; i++) packed[i] = download(fbs[i], rects);
+		size_t at = 0;
+		for (size_t k = 0; k < rects.size(); k++) {
+			const rmd_tile_rect &r = rects[k];
+			const size_t n = (size_t)r.width * r.height;
+			Tile t;
+			t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height;
+			t.count_a = n_half[0], t.count_b = n_half[1], t.sample_count = n_half[0] + n_half[1];
+			if (!errors.empty()) t.error = errors[k];
+			TileData *half[4] = {&t.data_a, &t.data_sq_a, &t.data_b, &t.data_sq_b};
+			for (int i = 0; i < 4; i++) {
+				*half[i] = TileData(n);
+				std::copy(packed[i].begin() + (long)at, packed[i].begin() + (long)(at + n), half[i]->data());
+			}
+			t.data = TileData(n), t.data_sq = TileData(n);
+			for (size_t p = 0; p < n; p++)
+				for (int c = 0; c < 3; c++) t.data[p][c] = t.data_a[p][c] + t.data_b[p][c], t.data_sq[p][c] = t.data_sq_a[p][c] + t.data_sq_b[p][c];
+			at += n;
+			finished.push_back(Message{Message::TileFinished, std::move(t)});
+			done_rects.push_back(r), done_a.push_back((uint32_t)n_half[0]), done_b.push_back((uint32_t)n_half[1]);
+		}
+	}
+
+	// progress snapshots of the tiles that go on: the two halves' sums added
+	std::vector<Message> snapshots(const std::vector<rmd_tile_rect> &still, const std::vector<double> &still_err) {
+		std::vector<Message> out;
+		if (!st.progress_tiles) return out;
+		const std::vector<Vector3> pa = download(fbs[0], still), pb = download(fbs[2], still);
+		size_t at = 0;
+		for (size_t k = 0; k < still.size(); k++) {
+			const rmd_tile_rect &r = still[k];
+			const size_t px = (size_t)r.width * r.height;
+			Tile t;
+			t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height, t.sample_count = done;
+			if (!still_err.empty()) t.error = still_err[k];
+			t.data = TileData(px);
+			for (size_t p = 0; p < px; p++)
+				for (int c = 0; c < 3; c++) t.data[p][c] = pa[at + p][c] + pb[at + p][c];
+			at += px;
+			out.push_back(Message{Message::TileProgressed, std::move(t)});
+		}
+		return out;
+	}
+
+	// the whole frame, the two halves' sums added on the device — or, with preview_denoise, the fast filter's means of them, guided when the loop keeps the features
+	Message preview(const std::vector<rmd_tile_rect> &still) {
+		const FrameCounts f = whole_frame(still);
+		if (!fb_preview) return preview_message(ctx, fbs[0], fbs[2], W, H, f.rects, sum_counts(f.a, f.b), st, j, done);
+		denoise_dual_frame(ctx, preview_st, W, H, fbs, feat[0], feat[1], f.rects, f.a, f.b, nullptr, 0, fb_preview, nullptr);
+		return preview_message(ctx, fb_preview, nullptr, W, H, f.rects, std::vector<uint32_t>(f.rects.size(), 1u), st, j, done); // (means)
+	}
+};
+
+// What the two kinds of worker share: make the worker — context, scene, frames — and record how long that took, run it, and whatever happened
+// publish the error and leave.  The worker, and with it its device memory, is gone BEFORE alive-- is published: await() takes alive == 0 for
+// "torn down", and a consumer of the channel for "the workers free their device memory after their last message".
+template <class W, class... Args> void worker_main(std::shared_ptr<TaskHandle::Shared> sh, const Args &...args) {
+	try {
+		const auto t_setup = std::chrono::steady_clock::now();
+		W worker(*sh, args...);
+		{
+			std::lock_guard<std::mutex> lock(sh->m);
+			sh->setup_s = std::max(sh->setup_s, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup).count());
+		}
+		worker.run();
 	} catch (const std::exception &e) {
 		std::lock_guard<std::mutex> lock(sh->m);
-		if (sh->error.empty()) sh->error = e.what();
+		if (sh->error.empty()) sh->error = e.what(); // the waiting workers see it and leave
+		sh->cv.notify_all();
 	}
-	for (double *fb : fbs)
-		if (fb) rmd_framebuffer_free(ctx, fb);
-	for (double *d : feat)
-		if (d) rmd_framebuffer_free(ctx, d);
-	if (fb_preview) rmd_framebuffer_free(ctx, fb_preview);
-	rmd_scene_destroy(dscene);
-	rmd_context_destroy(ctx);
 	std::lock_guard<std::mutex> lock(sh->m);
-	sh->alive--;
+	sh->alive--; // :192
 	sh->cv.notify_all();
 }
 
@@ -671,57 +814,51 @@ std::string check_preview(const Settings &st) {
 	return "";
 }
 
+namespace {
+// What render_tiled refuses in a Settings: the first failing check's text, or nothing.  The order is part of what a caller sees.
+std::string check_settings(const Settings &st) {
+	auto positive = [](double v) { return v > 0.0 && std::isfinite(v); };
+	if (const std::string why = check_preview(st); !why.empty()) return why;
+	if (st.denoise_radius > 12 || st.denoise_patch > 4) return "denoise_radius must be <= 12, denoise_patch <= 4";
+	if (!positive(st.denoise_k)) return "denoise_k must be finite and > 0";
+	if (!(st.denoise_alpha >= 0.0) || !std::isfinite(st.denoise_alpha)) return "denoise_alpha must be finite and >= 0";
+	if (!positive(st.denoise_feature_k)) return "denoise_feature_k must be finite and > 0";
+	if (!positive(st.denoise_feature_tau)) return "denoise_feature_tau must be finite and > 0";
+	if (st.denoise_features && !st.denoise) return "denoise_features needs denoise";
+	if (st.denoise_atrous_levels > RMD_ATROUS_MAX_LEVELS) return "denoise_atrous_levels must be <= 8";
+	if (!positive(st.denoise_atrous_k)) return "denoise_atrous_k must be finite and > 0";
+	if (st.denoise_atrous && !st.denoise) return "denoise_atrous needs denoise";
+	if (st.denoise_atrous && st.denoise_dual) return "denoise_atrous cannot be combined with denoise_dual: rmd_denoise_atrous has no dual form";
+	if (!(st.adaptive_threshold >= 0.0)) return "adaptive_threshold must be >= 0 (0 = off)";
+	if (st.adaptive_threshold > 0.0 && st.samples_per_iteration == 0) return "adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)";
+	if (!positive(st.adaptive_floor)) return "adaptive_floor must be finite and > 0";
+	if (st.denoise_dual && !st.denoise) return "denoise_dual needs denoise";
+	if (st.denoise_dual && st.samples_per_iteration == 0) return "denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)";
+	if (st.denoise_dual && st.denoise_features) return "denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight";
+	if (st.denoise_dual_features && !st.denoise_dual) return "denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)";
+	if (st.denoise_dual_select && !st.denoise_dual) return "denoise_dual_select needs denoise_dual (it selects rmd_denoise_dual_select)";
+	if (st.denoise_dual_atrous && !st.denoise_dual) return "denoise_dual_atrous needs denoise_dual (it selects rmd_denoise_atrous_dual)";
+	if (st.denoise_dual_atrous && st.denoise_dual_select) return "denoise_dual_atrous cannot be combined with denoise_dual_select: the selection has no a-trous candidate";
+	if (st.denoise_dual_atrous_region && !st.denoise_dual_atrous)
+		return "denoise_dual_atrous_region needs denoise_dual_atrous (it selects rmd_denoise_atrous_dual_region for the adaptive check)";
+	if (!(st.adaptive_denoised_threshold >= 0.0)) return "adaptive_denoised_threshold must be >= 0 (0 = off)";
+	if (st.adaptive_denoised_threshold > 0.0 && !st.denoise_dual) return "adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)";
+	if (st.adaptive_denoised_threshold > 0.0 && st.adaptive_threshold > 0.0) return "adaptive_denoised_threshold and adaptive_threshold are mutually exclusive";
+	if (st.denoise_dual && st.worker_count > 1) return "denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own";
+	return "";
+}
+} // namespace
+
 TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
-	if (const std::string why = check_preview(settings); !why.empty()) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: " + why);
-	if (settings.denoise_radius > 12 || settings.denoise_patch > 4) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_radius must be <= 12, denoise_patch <= 4");
-	if (!(settings.denoise_k > 0.0) || !std::isfinite(settings.denoise_k)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_k must be finite and > 0");
-	if (!(settings.denoise_alpha >= 0.0) || !std::isfinite(settings.denoise_alpha))
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_alpha must be finite and >= 0");
-	if (!(settings.denoise_feature_k > 0.0) || !std::isfinite(settings.denoise_feature_k))
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_feature_k must be finite and > 0");
-	if (!(settings.denoise_feature_tau > 0.0) || !std::isfinite(settings.denoise_feature_tau))
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_feature_tau must be finite and > 0");
-	if (settings.denoise_features && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_features needs denoise");
-	if (settings.denoise_atrous_levels > RMD_ATROUS_MAX_LEVELS) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous_levels must be <= 8");
-	if (!(settings.denoise_atrous_k > 0.0) || !std::isfinite(settings.denoise_atrous_k))
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous_k must be finite and > 0");
-	if (settings.denoise_atrous && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous needs denoise");
-	if (settings.denoise_atrous && settings.denoise_dual)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_atrous cannot be combined with denoise_dual: rmd_denoise_atrous has no dual form");
-	if (!(settings.adaptive_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold must be >= 0 (0 = off)");
-	if (settings.adaptive_threshold > 0.0 && settings.samples_per_iteration == 0)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)");
-	if (!(settings.adaptive_floor > 0.0) || !std::isfinite(settings.adaptive_floor)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_floor must be finite and > 0");
-	if (settings.denoise_dual && !settings.denoise) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual needs denoise");
-	if (settings.denoise_dual && settings.samples_per_iteration == 0)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)");
-	if (settings.denoise_dual && settings.denoise_features)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight");
-	if (settings.denoise_dual_features && !settings.denoise_dual)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_features needs denoise_dual (it selects rmd_denoise_dual_guided)");
-	if (settings.denoise_dual_select && !settings.denoise_dual)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_select needs denoise_dual (it selects rmd_denoise_dual_select)");
-	if (settings.denoise_dual_atrous && !settings.denoise_dual)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_atrous needs denoise_dual (it selects rmd_denoise_atrous_dual)");
-	if (settings.denoise_dual_atrous && settings.denoise_dual_select)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual_atrous cannot be combined with denoise_dual_select: the selection has no a-trous candidate");
-	if (settings.denoise_dual_atrous_region && !settings.denoise_dual_atrous)
-		throw Error(RMD_ERR_INVALID_ARGUMENT,
-		            "render_tiled: denoise_dual_atrous_region needs denoise_dual_atrous (it selects rmd_denoise_atrous_dual_region for the adaptive check)");
-	if (!(settings.adaptive_denoised_threshold >= 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold must be >= 0 (0 = off)");
-	if (settings.adaptive_denoised_threshold > 0.0 && !settings.denoise_dual)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)");
-	if (settings.adaptive_denoised_threshold > 0.0 && settings.adaptive_threshold > 0.0)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: adaptive_denoised_threshold and adaptive_threshold are mutually exclusive");
-	if (settings.denoise_dual && settings.worker_count > 1)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own");
+	if (const std::string why = check_settings(settings); !why.empty()) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_tiled: " + why);
 	TaskHandle h;
 	h.settings = settings;
 	h.shared_ = std::make_shared<TaskHandle::Shared>();
+	const std::shared_ptr<TaskHandle::Shared> sh = h.shared_;
 	if (settings.denoise_dual) {
 		if (settings.denoise_dual_features || settings.denoise_dual_select) h.scene_ = std::make_shared<const Scene>(scene);
-		h.shared_->alive = 1;
-		h.workers_.emplace_back(dual_worker_main, h.shared_, 0, scene, settings);
+		sh->alive = 1;
+		h.workers_.emplace_back([sh, scene, settings] { worker_main<DualWorker>(sh, 0, scene, settings); });
 		return h;
 	}
 	if (settings.denoise_features) h.scene_ = std::make_shared<const Scene>(scene);
@@ -730,15 +867,15 @@ TaskHandle render_tiled(const Scene &scene, const Settings &settings) {
 		Tile t;
 		t.left = r.left, t.top = r.top, t.width = r.width, t.height = r.height;
 		// (no data: a fresh tile's sums are the zeros of its worker's device framebuffer)
-		h.shared_->queue.push_back(std::move(t));
+		sh->queue.push_back(std::move(t));
 	}
 	const size_t workers = std::max<size_t>(1, settings.worker_count);
-	const size_t batch = std::max<size_t>(1, (h.shared_->queue.size() + workers * 4 - 1) / (workers * 4));
-	h.shared_->alive = workers;
+	const size_t batch = workers == 1 ? sh->queue.size() : std::max<size_t>(1, (sh->queue.size() + workers * 4 - 1) / (workers * 4));
+	sh->alive = workers;
 	// worker w drives GPU w; RAYMOND_REHEARSE_ON_DEVICE0=1 (tests on a one-GPU box) gives every worker its own context on GPU 0
 	const bool rehearse = std::getenv("RAYMOND_REHEARSE_ON_DEVICE0") != nullptr;
 	for (size_t w = 0; w < workers; w++)
-		h.workers_.emplace_back(worker_main, h.shared_, rehearse ? 0 : (int)w, (int)w, workers, scene, settings, workers == 1 ? h.shared_->queue.size() : batch);
+		h.workers_.emplace_back([=] { worker_main<TileWorker>(sh, rehearse ? 0 : (int)w, (int)w, workers, scene, settings, batch); });
 	return h;
 }
 
@@ -758,17 +895,8 @@ std::vector<Vector3> TaskHandle::await() {
 		Message m = std::move(shared_->channel.front());
 		shared_->channel.pop_front();
 		if (m.kind != Message::TileFinished) break; // :101-103
-		if (settings.denoise) {
-			collected.push_back(std::move(m.tile));
-			continue;
-		}
-		const Tile &t = m.tile;
-		for (size_t y = 0; y < t.height; y++)
-			for (size_t x = 0; x < t.width; x++) {
-				Vector3 s = t.data[x + y * t.width];
-				for (double &c : s) c /= (double)t.sample_count; // :95
-				out[x + t.left + (y + t.top) * cam.backbuffer_width] = s;
-			}
+		if (settings.denoise) collected.push_back(std::move(m.tile));
+		else place_tile(m.tile, m.tile.data, cam.backbuffer_width, out, (double)m.tile.sample_count);
 	}
 	lock.unlock();
 	if (!collected.empty()) out = settings.denoise_dual ? denoise_dual_tiles(collected, settings, 0, nullptr, scene_.get()) : denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
@@ -776,45 +904,23 @@ std::vector<Vector3> TaskHandle::await() {
 }
 
 namespace {
-rmd_camera camera_pod(const Settings &st) {
-	rmd_camera cam;
-	std::memset(&cam, 0, sizeof(cam));
-	cam.backbuffer_width = (uint32_t)st.camera_settings.backbuffer_width, cam.backbuffer_height = (uint32_t)st.camera_settings.backbuffer_height;
-	cam.fov_vert = st.camera_settings.fov_vert;
-	for (int a = 0; a < 3; a++) cam.position[a] = st.camera_settings.transform.position[a];
-	cam.focal_length = st.camera_settings.focal_length, cam.aperture_radius = st.camera_settings.aperture_radius;
-	return cam;
-}
 // the feature sums of the rects, each at its own count, into feat / feat_sq (zeroed device buffers of ctx): one call per distinct sample count
 void render_features_on(rmd_context *ctx, const Scene &scene, const Settings &st, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
                         double *feat, double *feat_sq) {
-	rmd_scene *dscene = nullptr;
-	std::vector<rmd_object> objs;
-	std::vector<rmd_grid_desc> grids;
-	flatten(scene, objs, grids);
-	check(rmd_scene_create(ctx, objs.data(), (uint32_t)objs.size(), grids.data(), (uint32_t)grids.size(), &dscene), ctx, "rmd_scene_create");
-	try {
-		const rmd_camera cam = camera_pod(st);
-		std::vector<uint32_t> distinct(counts);
-		std::sort(distinct.begin(), distinct.end());
-		distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-		for (uint32_t n : distinct) {
-			if (n == 0) continue;
-			std::vector<rmd_tile_rect> share;
-			for (size_t i = 0; i < rects.size(); i++)
-				if (counts[i] == n) share.push_back(rects[i]);
-			rmd_settings s;
-			std::memset(&s, 0, sizeof(s));
-			s.bounce_limit = (uint32_t)st.bounce_limit, s.sample_begin = 0, s.sample_count = n, s.seed = st.seed;
-			s.flags = st.use_dof ? RMD_RENDER_DOF : 0u;
-			check(rmd_render_features_async(ctx, dscene, &cam, &s, share.data(), (uint32_t)share.size(), feat, feat_sq), ctx, "rmd_render_features");
-		}
-		check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize");
-	} catch (...) {
-		rmd_scene_destroy(dscene);
-		throw;
+	const DeviceScene dscene(ctx, scene);
+	const rmd_camera cam = camera_pod(st);
+	std::vector<uint32_t> distinct(counts);
+	std::sort(distinct.begin(), distinct.end());
+	distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+	for (uint32_t n : distinct) {
+		if (n == 0) continue;
+		std::vector<rmd_tile_rect> share;
+		for (size_t i = 0; i < rects.size(); i++)
+			if (counts[i] == n) share.push_back(rects[i]);
+		const rmd_settings s = settings_pod(st, 0, n, feature_flags(st));
+		check(rmd_render_features_async(ctx, dscene, &cam, &s, share.data(), (uint32_t)share.size(), feat, feat_sq), ctx, "rmd_render_features");
 	}
-	rmd_scene_destroy(dscene);
+	check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize");
 }
 } // namespace
 
@@ -824,89 +930,53 @@ std::vector<double> render_features(const Scene &scene, const Settings &settings
 	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
 	std::vector<double> out(W * H * RMD_FEATURE_CHANNELS);
 	if (sums_sq) sums_sq->assign(out.size(), 0.0);
-	rmd_context *ctx = nullptr;
-	double *dev[2] = {nullptr, nullptr};
-	try {
-		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
-		for (double *&d : dev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
-		render_features_on(ctx, scene, settings, rects, counts, dev[0], sums_sq ? dev[1] : nullptr);
-		check(rmd_framebuffer_download(ctx, dev[0], out.data(), out.size()), ctx, "rmd_framebuffer_download");
-		if (sums_sq) check(rmd_framebuffer_download(ctx, dev[1], sums_sq->data(), sums_sq->size()), ctx, "rmd_framebuffer_download");
-	} catch (...) {
-		for (double *d : dev)
-			if (d) rmd_framebuffer_free(ctx, d);
-		rmd_context_destroy(ctx);
-		throw;
-	}
-	for (double *d : dev) rmd_framebuffer_free(ctx, d);
-	rmd_context_destroy(ctx);
+	const Context ctx(device);
+	const Frame dev[2] = {Frame(ctx, W, H, Frame::Features), Frame(ctx, W, H, Frame::Features)};
+	render_features_on(ctx, scene, settings, rects, counts, dev[0], sums_sq ? (double *)dev[1] : nullptr);
+	check(rmd_framebuffer_download(ctx, dev[0], out.data(), out.size()), ctx, "rmd_framebuffer_download");
+	if (sums_sq) check(rmd_framebuffer_download(ctx, dev[1], sums_sq->data(), sums_sq->size()), ctx, "rmd_framebuffer_download");
 	return out;
 }
 
 std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, const Scene *scene, std::vector<double> *feature_means) {
 	if (settings.denoise_features && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_tiles: settings.denoise_features needs the scene");
 	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
-	std::vector<double> sums(W * H * 3, 0.0), sums_sq(W * H * 3, 0.0);
+	std::vector<Vector3> sums(W * H), sums_sq(W * H);
 	std::vector<rmd_tile_rect> rects;
 	std::vector<uint32_t> counts;
 	for (const Tile &t : tiles) {
 		if (t.data.size() != t.width * t.height || t.data_sq.size() != t.width * t.height)
 			throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_tiles: a tile without its sums and sums of squares");
-		for (size_t y = 0; y < t.height; y++)
-			for (size_t x = 0; x < t.width; x++)
-				for (int c = 0; c < 3; c++) {
-					const size_t at = (x + t.left + (y + t.top) * W) * 3 + c;
-					sums[at] = t.data[x + y * t.width][c], sums_sq[at] = t.data_sq[x + y * t.width][c];
-				}
-		rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+		place_tile(t, t.data, W, sums), place_tile(t, t.data_sq, W, sums_sq);
+		rects.push_back(rect_of(t));
 		counts.push_back((uint32_t)t.sample_count);
 	}
 	std::vector<Vector3> out(W * H);
-	rmd_context *ctx = nullptr;
-	double *dev[3] = {nullptr, nullptr, nullptr};
-	double *fdev[2] = {nullptr, nullptr}; // settings.denoise_features: the feature sums and sums of squares
-	try {
-		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
-		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
-		if (settings.denoise_features) {
-			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
-			render_features_on(ctx, *scene, settings, rects, counts, fdev[0], fdev[1]);
-			if (feature_means) {
-				feature_means->assign(W * H * RMD_FEATURE_CHANNELS, 0.0);
-				check(rmd_framebuffer_download(ctx, fdev[0], feature_means->data(), feature_means->size()), ctx, "rmd_framebuffer_download");
-				std::vector<double> n_img(W * H, 0.0);
-				for (size_t i = 0; i < rects.size(); i++)
-					for (size_t y = rects[i].top; y < (size_t)rects[i].top + rects[i].height; y++)
-						for (size_t x = rects[i].left; x < (size_t)rects[i].left + rects[i].width; x++) n_img[x + y * W] = (double)counts[i];
-				for (size_t p = 0; p < W * H; p++)
-					for (size_t j = 0; j < RMD_FEATURE_CHANNELS; j++) (*feature_means)[p * RMD_FEATURE_CHANNELS + j] /= n_img[p];
-			}
+	const Context ctx(device);
+	const Frame dev[3] = {Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H)};
+	Frame fdev[2]; // settings.denoise_features: the feature sums and sums of squares
+	if (settings.denoise_features) {
+		for (Frame &f : fdev) f = Frame(ctx, W, H, Frame::Features);
+		render_features_on(ctx, *scene, settings, rects, counts, fdev[0], fdev[1]);
+		if (feature_means) {
+			feature_means->assign(W * H * RMD_FEATURE_CHANNELS, 0.0);
+			check(rmd_framebuffer_download(ctx, fdev[0], feature_means->data(), feature_means->size()), ctx, "rmd_framebuffer_download");
+			divide_by_counts(*feature_means, W, H, RMD_FEATURE_CHANNELS, rects, counts);
 		}
-		check(rmd_framebuffer_upload(ctx, sums.data(), dev[0], sums.size()), ctx, "rmd_framebuffer_upload");
-		check(rmd_framebuffer_upload(ctx, sums_sq.data(), dev[1], sums_sq.size()), ctx, "rmd_framebuffer_upload");
-		if (settings.denoise_atrous) // (fdev both null without denoise_features: the colour weight alone)
-			check(rmd_denoise_atrous(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
-			                         settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
-			                         settings.denoise_feature_tau, dev[2]),
-			      ctx, "rmd_denoise_atrous");
-		else // (fdev both null without denoise_features: exactly rmd_denoise)
-			check(rmd_denoise_guided(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
-			                         settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,
-			                         settings.denoise_feature_tau, dev[2]),
-			      ctx, "rmd_denoise_guided");
-		check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
-	} catch (...) {
-		for (double *d : dev)
-			if (d) rmd_framebuffer_free(ctx, d);
-		for (double *d : fdev)
-			if (d) rmd_framebuffer_free(ctx, d);
-		rmd_context_destroy(ctx);
-		throw;
 	}
-	for (double *d : dev) rmd_framebuffer_free(ctx, d);
-	for (double *d : fdev)
-		if (d) rmd_framebuffer_free(ctx, d);
-	rmd_context_destroy(ctx);
+	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums.data()), dev[0], W * H * 3), ctx, "rmd_framebuffer_upload");
+	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums_sq.data()), dev[1], W * H * 3), ctx, "rmd_framebuffer_upload");
+	if (settings.denoise_atrous) // (fdev both null without denoise_features: the colour weight alone)
+		check(rmd_denoise_atrous(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+		                         settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
+		                         settings.denoise_feature_tau, dev[2]),
+		      ctx, "rmd_denoise_atrous");
+	else // (fdev both null without denoise_features: exactly rmd_denoise)
+		check(rmd_denoise_guided(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+		                         settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,
+		                         settings.denoise_feature_tau, dev[2]),
+		      ctx, "rmd_denoise_guided");
+	check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
 	return out;
 }
 
@@ -914,82 +984,34 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 	if (settings.denoise_dual_features && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: settings.denoise_dual_features needs the scene");
 	if (settings.denoise_dual_select && !scene) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: settings.denoise_dual_select needs the scene");
 	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
-	std::vector<double> halves[4];
-	for (std::vector<double> &h : halves) h.assign(W * H * 3, 0.0);
+	std::vector<Vector3> halves[4];
+	for (std::vector<Vector3> &h : halves) h.resize(W * H);
 	std::vector<rmd_tile_rect> rects;
 	std::vector<uint32_t> counts_a, counts_b;
 	for (const Tile &t : tiles) {
 		const TileData *src[4] = {&t.data_a, &t.data_sq_a, &t.data_b, &t.data_sq_b};
 		for (int i = 0; i < 4; i++) {
 			if (src[i]->size() != t.width * t.height) throw Error(RMD_ERR_INVALID_ARGUMENT, "denoise_dual_tiles: a tile without its two halves' sums and sums of squares");
-			for (size_t y = 0; y < t.height; y++)
-				for (size_t x = 0; x < t.width; x++)
-					for (int c = 0; c < 3; c++) halves[i][(x + t.left + (y + t.top) * W) * 3 + c] = (*src[i])[x + y * t.width][c];
+			place_tile(t, *src[i], W, halves[i]);
 		}
-		rects.push_back(rmd_tile_rect{(uint32_t)t.left, (uint32_t)t.top, (uint32_t)t.width, (uint32_t)t.height});
+		rects.push_back(rect_of(t));
 		counts_a.push_back((uint32_t)t.count_a), counts_b.push_back((uint32_t)t.count_b);
 	}
 	std::vector<Vector3> out(W * H);
-	rmd_context *ctx = nullptr;
-	double *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // the four halves, the frame, the error image
-	double *fdev[2] = {nullptr, nullptr}; // settings.denoise_dual_features: the feature sums and sums of squares, each tile at count_a + count_b
-	try {
-		check(rmd_context_create(device, &ctx), nullptr, "rmd_context_create");
-		for (double *&d : dev) check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_framebuffer_alloc");
-		for (int i = 0; i < 4; i++) check(rmd_framebuffer_upload(ctx, halves[i].data(), dev[i], halves[i].size()), ctx, "rmd_framebuffer_upload");
-		if (settings.denoise_dual_atrous) {
-			std::vector<uint32_t> counts_f(counts_a);
-			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
-			if (settings.denoise_dual_features) {
-				for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
-				render_features_on(ctx, *scene, settings, rects, counts_f, fdev[0], fdev[1]);
-			}
-			check(rmd_denoise_atrous_dual(ctx, dev[0], dev[1], dev[2], dev[3], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(),
-			                              counts_f.data(), (uint32_t)rects.size(), settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha,
-			                              settings.denoise_feature_k, settings.denoise_feature_tau, dev[4], tile_errors ? dev[5] : nullptr),
-			      ctx, "rmd_denoise_atrous_dual");
-		} else if (settings.denoise_dual_select) {
-			std::vector<uint32_t> counts_f(counts_a);
-			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
-			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
-			render_features_on(ctx, *scene, settings, rects, counts_f, fdev[0], fdev[1]);
-			const rmd_denoise_candidate cands[2] = {{settings.denoise_k, settings.denoise_alpha, 0.0, 0.0, 0u, 0u},
-			                                        {1.0, settings.denoise_alpha, settings.denoise_feature_k, settings.denoise_feature_tau, 1u, 0u}};
-			check(rmd_denoise_dual_select(ctx, dev[0], dev[1], dev[2], dev[3], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(),
-			                              counts_f.data(), (uint32_t)rects.size(), settings.denoise_radius, settings.denoise_patch, cands, 2u, 2u, 2u, dev[4],
-			                              tile_errors ? dev[5] : nullptr, nullptr, nullptr),
-			      ctx, "rmd_denoise_dual_select");
-		} else if (settings.denoise_dual_features) {
-			std::vector<uint32_t> counts_f(counts_a);
-			for (size_t i = 0; i < counts_f.size(); i++) counts_f[i] += counts_b[i];
-			for (double *&d : fdev) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &d), ctx, "rmd_feature_buffer_alloc");
-			render_features_on(ctx, *scene, settings, rects, counts_f, fdev[0], fdev[1]);
-			check(rmd_denoise_dual_guided(ctx, dev[0], dev[1], dev[2], dev[3], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(),
-			                              counts_f.data(), (uint32_t)rects.size(), settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha,
-			                              settings.denoise_feature_k, settings.denoise_feature_tau, dev[4], tile_errors ? dev[5] : nullptr),
-			      ctx, "rmd_denoise_dual_guided");
-		} else {
-			check(rmd_denoise_dual(ctx, dev[0], dev[1], dev[2], dev[3], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(), (uint32_t)rects.size(),
-			                       settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, dev[4], tile_errors ? dev[5] : nullptr),
-			      ctx, "rmd_denoise_dual");
-		}
-		if (tile_errors) {
-			tile_errors->assign(rects.size(), 0.0);
-			check(rmd_tile_error_dual(ctx, dev[5], (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), tile_errors->data()), ctx, "rmd_tile_error_dual");
-		}
-		check(rmd_framebuffer_download(ctx, dev[4], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
-	} catch (...) {
-		for (double *d : dev)
-			if (d) rmd_framebuffer_free(ctx, d);
-		for (double *d : fdev)
-			if (d) rmd_framebuffer_free(ctx, d);
-		rmd_context_destroy(ctx);
-		throw;
+	const Context ctx(device);
+	const Frame dev[6] = {Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H)}; // the four halves, the frame, the error image
+	for (int i = 0; i < 4; i++) check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(halves[i].data()), dev[i], W * H * 3), ctx, "rmd_framebuffer_upload");
+	Frame fdev[2]; // the feature sums and sums of squares, each tile at count_a + count_b: for the guided filter, the selecting one, and the fast one when it is guided
+	if (settings.denoise_dual_features || (settings.denoise_dual_select && !settings.denoise_dual_atrous)) {
+		for (Frame &f : fdev) f = Frame(ctx, W, H, Frame::Features);
+		render_features_on(ctx, *scene, settings, rects, sum_counts(counts_a, counts_b), fdev[0], fdev[1]);
 	}
-	for (double *d : dev) rmd_framebuffer_free(ctx, d);
-	for (double *d : fdev)
-		if (d) rmd_framebuffer_free(ctx, d);
-	rmd_context_destroy(ctx);
+	denoise_dual_frame(ctx, settings, W, H, dev, fdev[0], fdev[1], rects, counts_a, counts_b, nullptr, 0, dev[4], tile_errors ? (double *)dev[5] : nullptr);
+	if (tile_errors) {
+		tile_errors->assign(rects.size(), 0.0);
+		check(rmd_tile_error_dual(ctx, dev[5], (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), tile_errors->data()), ctx, "rmd_tile_error_dual");
+	}
+	check(rmd_framebuffer_download(ctx, dev[4], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
 	return out;
 }
 
@@ -1030,9 +1052,7 @@ void TaskHandle::async_await() {
 std::vector<uint8_t> resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, size_t width, size_t height,
                                            const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double exposure, double gamma) {
 	if (counts.size() != rects.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "resolve_tonemap_tiles: one sample count per rect");
-	size_t pixels = 0;
-	for (const rmd_tile_rect &r : rects) pixels += (size_t)r.width * r.height;
-	std::vector<uint8_t> packed(pixels * 3);
+	std::vector<uint8_t> packed(pixels_of(rects) * 3);
 	check(rmd_resolve_tonemap_tiles(ctx, accum_dev, accum2_dev, (uint32_t)width, (uint32_t)height, rects.data(), counts.data(), (uint32_t)rects.size(), exposure, gamma,
 	                                packed.data()),
 	      ctx, "rmd_resolve_tonemap_tiles");

@@ -298,6 +298,13 @@ void scatter_tiles(const std::vector<rmd_tile_rect> &rects, const std::vector<ui
 
 // Tile generation of render_tiled (:142-173): column-major, edge tiles clamped
 std::vector<rmd_tile_rect> generate_tiles(size_t width, size_t height, std::pair<size_t, size_t> tile_size);
+// A tile's place in the frame, as the C-ABI takes it
+rmd_tile_rect rect_of(const Tile &tile);
+// Frame assembly (:93-99): `data` — one of the tile's TileData, width * height of them — written into the row-major frame `width` pixels wide at the
+// tile's rect, every value divided by `divisor` (await(): the tile's sample_count)
+void place_tile(const Tile &tile, const TileData &data, size_t width, std::vector<Vector3> &frame, double divisor = 1.0);
+// width * height * channels sums divided by the count of the rect their pixel lies in (rect i holds counts[i] samples; 0 / 0 where no rect lies)
+void divide_by_counts(std::vector<double> &sums, size_t width, size_t height, size_t channels, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts);
 
 // cli_old/src/main.rs:155-181 on the host: c = (1 - exp(-p * exposure))^(1/gamma); u8 = trunc(c * 255)
 std::vector<uint8_t> tone_map(const std::vector<Vector3> &image, double exposure = 1.0, double gamma = 2.2);

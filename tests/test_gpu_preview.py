@@ -278,5 +278,17 @@ def test_cli_writes_the_python_previews(cli, tmp_path, long_preview_run):
     assert names == ["dual_0001.ppm"]
     (p,) = previews(run(settings(preview_every=2, denoise=True, denoise_dual=True)))
     assert np.array_equal(read_ppm("%s_0001.ppm" % prefix), p.frame)
+    # the dual loop's filtered preview: rmd_denoise_atrous_dual on the two halves ...
+    names, prefix = render_cli("dualden", SPP, "--denoise", 1, "--denoise-dual", 1, "--preview-denoise", 1)
+    assert names == ["dualden_0001.ppm"]
+    (p,) = previews(run(settings(preview_every=2, denoise=True, denoise_dual=True, preview_denoise=True)))
+    assert np.array_equal(read_ppm("%s_0001.ppm" % prefix), p.frame)
+    # ... and guided: a threshold no tile reaches makes the loop keep the feature buffers, which the preview's filter then reads
+    names, prefix = render_cli("dualguided", SPP, "--denoise", 1, "--denoise-dual", 1, "--preview-denoise", 1, "--denoise-dual-features", 1, "--adaptive-denoised", "1e-9",
+                               "--adaptive-min", 2)
+    assert names == ["dualguided_0001.ppm"]
+    (p,) = previews(run(settings(preview_every=2, denoise=True, denoise_dual=True, preview_denoise=True, denoise_dual_features=True, adaptive_denoised_threshold=1e-9,
+                                 adaptive_min_samples=2)))
+    assert np.array_equal(read_ppm("%s_0001.ppm" % prefix), p.frame)
     r = subprocess.run([cli, "render", "spheres", str(W), str(H), str(SPP), str(BOUNCES), str(tmp_path / "x.ppm"), "--preview-every", "2"], capture_output=True, text=True)
     assert r.returncode == 1 and "preview_every > 0 needs samples_per_iteration > 0" in r.stderr  # the settings' rule, in the C++ mirror's words too
