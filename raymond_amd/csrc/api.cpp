@@ -201,6 +201,21 @@ bool primary_cull_allowed(const RenderParams &P) {
 	return P.use_dof == 0u && cull_camera_ok(c);
 }
 
+// Does the camera lie ON a plane of the scene?  A primary ray that faces such a plane hits it at t = 0 (plane.rs:11-24: t >= 0 counts), the hit
+// point IS the camera position, and the view direction normalize(camera - hit) (src/trace.rs:257) is NaN: a non-finite weight from finite inputs,
+// in a scene of regular parameters.  The reference's sample is then NaN unless the plane emits, so the two rules that end a path with L = 0 — a hit
+// at the bounce limit, a diffuse bounce off a black surface — do not hold for such a launch (make_params).  "On": the numerator dot(o - cam, -n) of
+// the plane test is zero, or so small (1e-9 of the sum of its terms' magnitudes: a distance no frame shows) that cam + t rd may round to cam.
+static bool camera_on_a_plane(const rmd_scene *scene, const rmd_camera *cam) {
+	for (size_t i = 0; i + 6 <= scene->planes.size(); i += 6) {
+		const double *o = &scene->planes[i], *n = o + 3;
+		double num = 0.0, scale = 0.0;
+		for (int a = 0; a < 3; a++) num += (o[a] - cam->position[a]) * -n[a], scale += (std::fabs(o[a]) + std::fabs(cam->position[a])) * std::fabs(n[a]);
+		if (!(std::fabs(num) > 1e-9 * scale)) return true; // (a NaN too)
+	}
+	return false;
+}
+
 // generate_primary_ray's loop-invariant terms (src/trace.rs:323-330), evaluated with the host libm
 RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st) {
 	const double PI = 3.14159265358979323846;
@@ -226,8 +241,10 @@ RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const r
 	// (its one NaN source, the interpolated normal of a mesh hit, does not exist there); END opts in for scenes with grids, TRACE never ends
 	// — AND whose parameters are all inside the class for which that is proved (rmd_scene::regular: an Emission of (inf, 0, 0), a NaN colour, a
 	// material of roughness 0 or a sphere of radius 0 make non-finite radiance reachable without a mesh; such a scene is traced like one with a grid)
-	P.end_black_paths = (st->flags & RMD_RENDER_TRACE_BLACK_PATHS) ? 0u : ((st->flags & RMD_RENDER_END_BLACK_PATHS) || !scene || (scene->n_grids == 0u && scene->regular)) ? 1u : 0u;
-	P.shade_last_depth = (scene && !scene->regular) ? 1u : 0u;
+	// — AND whose camera does not lie on one of its planes (camera_on_a_plane: the view direction of a hit at t = 0 is NaN)
+	const bool on_plane = scene && camera_on_a_plane(scene, cam);
+	P.end_black_paths = (st->flags & RMD_RENDER_TRACE_BLACK_PATHS) ? 0u : ((st->flags & RMD_RENDER_END_BLACK_PATHS) || !scene || (scene->n_grids == 0u && scene->regular && !on_plane)) ? 1u : 0u;
+	P.shade_last_depth = (scene && (!scene->regular || on_plane)) ? 1u : 0u;
 	P.axis_pairs = scene ? scene->axis_pairs : 0u;
 	P.visit_mask = scene ? scene->visit_mask : ~0ull, P.grid_mask = scene ? scene->grid_mask : ~0ull;
 	P.primary_cull = (scene && scene->primary_cull && rmd::primary_cull_allowed(P)) ? 1u : 0u;
@@ -507,6 +524,8 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 	std::memset(&walls_block, 0, sizeof(walls_block));
 	std::memcpy(&walls_block, derived.walls, sizeof(derived.walls));
 	sc->visit_mask = derived.visit_mask, sc->grid_mask = derived.grid_mask;
+	for (uint32_t i = 0; i < n_objects; i++)
+		if (objects[i].geometry_kind == RMD_GEOM_PLANE) sc->planes.insert(sc->planes.end(), objects[i].origin, objects[i].origin + 3), sc->planes.insert(sc->planes.end(), objects[i].normal, objects[i].normal + 3);
 	// the generation trips' own candidate sets (primary_candidates.hpp): a regular scene without a grid, unless RMD_TUNE_AXIS_PAIRS says 1 or 2
 	sc->primary_cull = regular && n_grids == 0u && ctx->tunable[RMD_TUNE_AXIS_PAIRS] == 0;
 	for (uint32_t i = 0; i < n_objects; i++) sc->n_grid_objects += objects[i].geometry_kind == RMD_GEOM_GRID ? 1u : 0u;

@@ -122,6 +122,7 @@ struct rmd_scene {
 	uint32_t walk_steps_bound = 0; // RenderParams::walk_steps_bound
 	bool primary_cull = false; // the scene's half of RenderParams::primary_cull: regular, no grid, RMD_TUNE_AXIS_PAIRS = 0 when it was created
 	bool regular = true; // every parameter the kernel reads is finite and inside the class for which ending zero-throughput paths is exact (api.cpp: rmd_scene_create)
+	std::vector<double> planes; // origin and normal of every plane object, six numbers each: make_params asks whether the camera lies ON one
 	rmd::DevObject *d_objects = nullptr;
 	rmd::DevGrid *d_grids = nullptr;
 	std::vector<rmd::DeviceBuffer> owned; // every device allocation of this scene

@@ -156,7 +156,9 @@ def same_f64(a, b):
     return np.float64(a).tobytes() == np.float64(b).tobytes() or (a != a and b != b)
 
 
-def hold_oracle_to_second_reading(oracle, scene, settings, pixels, samples_per_pixel, want_depths, want_object=0):
+def hold_oracle_to_second_reading(oracle, scene, settings, pixels, samples_per_pixel, want_depths, want_object=0, min_nonzero=None, vertices_every=97):
+    """min_nonzero: how many samples must carry radiance (default: more than a twentieth; -1 for a scene that is black by construction);
+    vertices_every: the vertex sequences are compared on every so-manyth sample (1: on all of them)."""
     cam = settings.camera_settings
     osc = oracle.OracleScene(scene)
     sc, c = second_reading_scene(scene, cam)
@@ -174,10 +176,10 @@ def hold_oracle_to_second_reading(oracle, scene, settings, pixels, samples_per_p
         depths[len(path)] = depths.get(len(path), 0) + 1
         nonzero += any(v != 0.0 for v in rgb)
         through_object += any(o == want_object for o, _ in path)
-        if i % 97 == 0:  # the vertices as well, on a subset
+        if i % vertices_every == 0:  # the vertices as well, on a subset
             _, po, ps = osc.trace_sample_path(cam, settings, int(xy[i, 0]), int(xy[i, 1]), int(smp[i]))
             assert [p[0] for p in path] == po.tolist()[: len(path)], (i, path, po)
-    assert nonzero > len(smp) // 20 and through_object > len(smp) // 20
+    assert nonzero > (len(smp) // 20 if min_nonzero is None else min_nonzero) and through_object > len(smp) // 20
     for d in want_depths:
         assert depths.get(d, 0) > 0, depths
     return depths
