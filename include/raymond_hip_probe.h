@@ -113,6 +113,11 @@ rmd_status rmd_probe_work_items(uint32_t n_tiles, uint32_t n_whole, uint32_t k_t
                                 uint32_t *n_items);
 /* Host only: the LDS layout of an uploaded scene — objects in the table, grids, and words of the grids' occupancy masks. */
 rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total);
+/* Host code only (no kernel runs; the grids' records are copied back from the scene's device): what rmd_scene_create decided once for an uploaded
+ * scene and every launch of it reads — out8 = n_grid_objects, regular, walk_steps_bound, axis_pairs, visit_mask, grid_mask, n_grids, 0 — and, for the
+ * first n of its grids, shift_bits2 = mask_shift and mask_bits per grid.  tests/test_gpu_mesh_scenes.py asserts from it that a class of
+ * tests/mesh_scenes.py reaches the state it names. */
+rmd_status rmd_probe_scene_plan(const rmd_scene *scene, uint64_t *out8, size_t n, uint32_t *shift_bits2);
 /* Host only: the device scratch block a denoise entry point carves (raymond_amd/csrc/denoise_host.hpp: denoise_scratch_layout — the function the entry
  * points themselves call).  form 0 = rmd_denoise[_guided], 1 = rmd_denoise_atrous, 2 = rmd_denoise_dual and its guided and region forms,
  * 3 = rmd_denoise_atrous_dual, 4 = rmd_denoise_atrous_dual_region, 5 = rmd_denoise_dual_select, 6 = rmd_tile_error_dual; guided = 1: the call has

@@ -329,6 +329,20 @@ rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, u
 	return RMD_OK;
 }
 
+rmd_status rmd_probe_scene_plan(const rmd_scene *scene, uint64_t *out8, size_t n, uint32_t *shift_bits2) {
+	if (!scene || !scene->ctx || !out8 || (n && !shift_bits2) || n > scene->n_grids) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	rmd_context *ctx = scene->ctx;
+	out8[0] = scene->n_grid_objects, out8[1] = scene->regular ? 1u : 0u, out8[2] = scene->walk_steps_bound, out8[3] = scene->axis_pairs;
+	out8[4] = scene->visit_mask, out8[5] = scene->grid_mask, out8[6] = scene->n_grids, out8[7] = 0u;
+	if (n == 0) return RMD_OK;
+	std::vector<rmd::DevGrid> grids(n);
+	RMD_HIP(ctx, hipSetDevice(ctx->device));
+	RMD_HIP(ctx, hipMemcpyAsync(grids.data(), scene->d_grids, n * sizeof(rmd::DevGrid), hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	for (size_t g = 0; g < n; g++) shift_bits2[2 * g] = grids[g].mask_shift, shift_bits2[2 * g + 1] = grids[g].mask_bits;
+	return RMD_OK;
+}
+
 rmd_status rmd_probe_pretest_pairs(rmd_context *ctx, size_t n, const double *sphere5, const double *pos9, const double *ray6, int32_t *pass, int32_t *hit,
                                    double *t) {
 	if (n != 0 && (!sphere5 || !pos9 || !ray6 || !pass || !hit || !t)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");

@@ -39,6 +39,7 @@ _SIGS = {
     "rmd_probe_work_plan": [_vp, _sz, _vp, _vp],
     "rmd_probe_work_items": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _vp, _P(C.c_uint32)],
     "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
+    "rmd_probe_scene_plan": [_vp, _vp, _sz, _vp],
     "rmd_probe_denoise_scratch": [C.c_uint32] * 6 + [C.c_uint64, _vp, _P(C.c_uint64)],
 }
 PATH_STRIDE = 17
@@ -286,6 +287,23 @@ def scene_layout(dscene):
     n, g, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
     _host_check(L.rmd_probe_scene_layout(dscene.handle, C.byref(n), C.byref(g), C.byref(m)), "rmd_probe_scene_layout")
     return n.value, g.value, m.value
+
+
+SCENE_PLAN_FIELDS = ("n_grid_objects", "regular", "walk_steps_bound", "axis_pairs", "visit_mask", "grid_mask", "n_grids")
+
+
+def scene_plan(dscene):
+    """What rmd_scene_create decided once for an uploaded scene -> dict keyed by SCENE_PLAN_FIELDS, plus "mask_shift" and "mask_bits": one int per
+    grid.  api: rmd_probe_scene_plan."""
+    L = _L()
+    out = np.zeros(8, dtype=np.uint64)
+    _host_check(L.rmd_probe_scene_plan(dscene.handle, _p(out), 0, None), "rmd_probe_scene_plan")
+    n = int(out[6])
+    per_grid = np.zeros((max(n, 1), 2), dtype=np.uint32)
+    _host_check(L.rmd_probe_scene_plan(dscene.handle, _p(out), n, _p(per_grid)), "rmd_probe_scene_plan")
+    plan = {k: int(v) for k, v in zip(SCENE_PLAN_FIELDS, out)}
+    plan["mask_shift"], plan["mask_bits"] = [int(v) for v in per_grid[:n, 0]], [int(v) for v in per_grid[:n, 1]]
+    return plan
 
 
 # rmd_probe_denoise_scratch: the forms, and the parts in the order of denoise_host.hpp's ScratchPart

@@ -35,7 +35,8 @@ def test_every_declared_symbol_is_exported(product_lib):
     assert set(lib.SIGNATURES) <= exported
     assert not [n for n in exported if n.startswith("rmd_probe_")]
     probes = declared_functions("raymond_hip_probe.h")
-    assert len(probes) >= 18 and all(n.startswith("rmd_probe_") for n in probes)
+    assert len(probes) >= 19 and all(n.startswith("rmd_probe_") for n in probes)
+    assert "rmd_probe_scene_layout" in probes and "rmd_probe_scene_plan" in probes  # (the host-only readings of an uploaded scene)
     probe_exported, _ = exported_functions(probe.PROBE_LIB_PATH)
     assert not [n for n in probes if n not in probe_exported] and set(probe._SIGS) <= probe_exported
     # the boundary is plain C: no C++-mangled rmd entry points, no torch types anywhere near it

@@ -561,8 +561,12 @@ def test_black_path_modes_change_no_finite_sample(gpu_ctx, oracle, small_mesh_sc
     traced-on frame is non-finite."""
     frames, st, tiles = _render_modes(gpu_ctx, scenes.reflective_spheres(), 203, 117, 24, 5, 41, ("default", "trace"))
     assert same_bits(frames["default"], frames["trace"]).all() and np.isfinite(frames["default"]).all()
+    from test_gpu_fullsize import account_for_off_pixels
+
     ref = oracle.OracleScene(scenes.reflective_spheres()).render_tiles(st.camera_settings, st, tiles, threads=4)
-    assert rel_close(frames["default"], ref, 1e-9).all(axis=2).mean() >= 0.995
+    ok = rel_close(frames["default"], ref, 1e-9).all(axis=2)
+    st0 = Settings(scenes.camera(203, 117), sample_count=24, bounce_limit=5, seed=41)  # (flags 0: the frame that is compared)
+    account_for_off_pixels(gpu_ctx, oracle, scenes.reflective_spheres(), st0, st0.camera_settings, 24, frames["default"], ref, ok, "black path modes, spheres")
     assert (frames["default"] == 0.0).all(axis=2).mean() < 0.5  # (the frame itself is not black)
 
     frames, st, tiles = _render_modes(gpu_ctx, small_mesh_scene, 160, 96, 12, 8, 41, ("default", "trace", "end"))
@@ -571,7 +575,9 @@ def test_black_path_modes_change_no_finite_sample(gpu_ctx, oracle, small_mesh_sc
     assert np.isfinite(frames["default"][~same]).all(axis=1).sum() == 0, "a finite pixel changed"
     assert same.mean() > 0.9999
     ref = oracle.OracleScene(small_mesh_scene).render_tiles(st.camera_settings, st, tiles, threads=4)
-    assert rel_close(frames["default"], ref, 1e-9).all(axis=2).mean() >= 0.995
+    ok = rel_close(frames["default"], ref, 1e-9).all(axis=2)
+    st0 = Settings(scenes.camera(160, 96), sample_count=12, bounce_limit=8, seed=41)
+    account_for_off_pixels(gpu_ctx, oracle, small_mesh_scene, st0, st0.camera_settings, 12, frames["default"], ref, ok, "black path modes, mesh")
 
 
 def test_contradictory_or_unknown_flags_are_refused(gpu_ctx):
@@ -1216,7 +1222,10 @@ def test_chained_work_items_do_not_change_the_image(gpu_ctx, small_mesh_scene, o
         for name, img in frames.items():
             assert same_bits(img, frames["direct"]).all(), (spp, name)
         ref = oracle.OracleScene(small_mesh_scene).render_tiles(st.camera_settings, st, tiles, threads=8)
-        assert rel_close(frames["chained"], ref, 1e-9).all(axis=2).mean() >= 0.995
+        from test_gpu_fullsize import account_for_off_pixels
+
+        ok = rel_close(frames["chained"], ref, 1e-9).all(axis=2)
+        account_for_off_pixels(gpu_ctx, oracle, small_mesh_scene, st, st.camera_settings, spp, frames["chained"], ref, ok, "chained work items spp=%d dof=%s bounces=%d" % (spp, dof, bounces))
     fb.close(), ds.close()
 
 
@@ -1278,7 +1287,11 @@ def test_path_queues_do_not_change_the_image(gpu_ctx, small_mesh_scene, oracle):
             assert same_bits(img, frames["direct"]).all(), (spp, dof, end_black, name)
         ref = oracle.OracleScene(sc).render_tiles(st.camera_settings, st, tiles, threads=8)
         if not end_black:  # (the oracle traces every path: flags 0)
-            assert rel_close(frames["queued"], ref, 1e-9).all(axis=2).mean() >= 0.995
+            from test_gpu_fullsize import account_for_off_pixels
+
+            ok = rel_close(frames["queued"], ref, 1e-9).all(axis=2)
+            account_for_off_pixels(gpu_ctx, oracle, sc, st, st.camera_settings, spp, frames["queued"], ref, ok,
+                                   "path queues %s spp=%d dof=%s bounces=%d mask budget %d" % ("two grids" if sc is two else "one grid", spp, dof, bounces, mask_budget))
         fb.close(), ds.close()
 
 
