@@ -65,6 +65,8 @@ enum {
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
 	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
+	                                 rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope,
+	                                 rmd_denoise_dual_guided_slope_region, rmd_denoise_dual_select_slope,
 	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select, rmd_denoise_atrous) */
 };
 
@@ -414,7 +416,8 @@ rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, c
  *     w(p, q) = w_f if p and q are both feature-valid and w_f < w_c, else w_c
  * and out is the w-weighted mean as before.  So w(p, p) = 1, a pixel whose mesh normal is NaN is filtered by colour alone, a miss never mixes
  * with a hit (Phi_6 = t^2 / eps), and two misses do.  The gradient term of the 2013 paper and its second filtering pass are left out on
- * purpose.  feat_dev = feat_sq_dev = NULL is exactly rmd_denoise (k_f and tau are then not read), and rmd_denoise is that call.  Beyond
+ * purpose (of this call: rmd_denoise_guided_slope, further down, adds a form of the gradient term).  feat_dev = feat_sq_dev = NULL is
+ * exactly rmd_denoise (k_f and tau are then not read), and rmd_denoise is that call.  Beyond
  * rmd_denoise's rules: one of the two NULL and the other not, k_f or tau not finite or not > 0, the two W*H*7-double feature ranges overlapping
  * each other or out_dev's range: RMD_ERR_INVALID_ARGUMENT before the device is touched.  Values a caller may start from: k_f 1.0, tau 1e-2 (the
  * best of the sweep in DESIGN.md section 12; the paper's 0.6 and 1e-3 filter less and measured worse on the two test scenes).  Synchronous, like rmd_denoise.
@@ -622,6 +625,72 @@ rmd_status rmd_denoise_dual_select(rmd_context *ctx,
     const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
     uint32_t radius, uint32_t patch_radius,
     const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
+    double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev);
+/*
+ * The guided non-local-means filters with a FEATURE-SLOPE TERM (additions within ABI 6: RMD_ABI_VERSION stays 6, no struct changes, found by their
+ * symbols).  A tight feature weight reads the change of a feature along a CURVED surface — a sphere's normal differs from pixel to pixel — as an edge
+ * and takes away neighbours the pixel needs (DESIGN.md sections 12 and 21).  The 2013 paper answers with the feature's gradient in the denominator of
+ * Phi_j; here it is the feature's own local slope, estimated so that a step does not count, times a scale in pixels (the scale is not the paper's).
+ * `slope`: a double, finite and >= 0 — the number of pixels of a feature's local slope that is not an edge.  Everything of the call without the
+ * suffix stays word for word.  Added, for a FEATURE-VALID pixel p = (x, y) and channel j, with f the call's own feature means:
+ *     a_l = f_pj - f_(x-1,y)j      present if x >= 1 and (x-1, y) is feature-valid
+ *     a_r = f_(x+1,y)j - f_pj      present if x + 1 < W and (x+1, y) is feature-valid
+ *     a_u = f_pj - f_(x,y-1)j,  a_d = f_(x,y+1)j - f_pj      likewise for the rows y - 1 and y + 1 (y + 1 < H)
+ *     h_j  = (a_l*a_l < a_r*a_r ? a_l*a_l : a_r*a_r)  if both are present, else 0.0          — the two-sided minimum: a slope that continues on both
+ *     v_j  = the same from a_u and a_d                                                         sides counts, a step, which has a flat side, does not
+ *     m_pj = (slope * slope) * (h_j + v_j)
+ *     t    = max(tau * s_pj, g_pj)         exactly the comparison of rmd_denoise_guided (a > g ? a : g)
+ *     if m_pj > t then t = m_pj            (a NaN m is skipped by the comparison)
+ *     the denominator of Phi_j(p, .) = eps + k_f^2 * t
+ * Phi_j's numerator, D_f, w_f, w and every sum order are unchanged.  FEATURE-VALID is each call's own: rmd_denoise_guided's for
+ * rmd_denoise_guided_slope; rmd_denoise_dual_guided's (dual-valid, n_F >= 2, fourteen finite values) for the dual calls.  So:
+ *     slope = 0 gives the bytes of the call without the suffix, launches nothing more and takes no more scratch;
+ *     features that are constant on one side of every pixel, on each axis, give those bytes at any slope (a step edge stays an edge, and
+ *     "a miss never mixes with a hit" holds for every miss that has another miss beside it: its depth then has a flat side);
+ *     a pixel on the frame's border, or beside a pixel that is not feature-valid, has no slope on that axis;
+ *     the slope only raises a denominator: w_f rises towards w_c, never above it.
+ * rmd_denoise_guided_slope             = rmd_denoise_guided with `slope` after tau
+ * rmd_denoise_dual_guided_slope        = rmd_denoise_dual_guided with `slope` after tau; the same m enters both passes
+ * rmd_denoise_dual_guided_slope_region = rmd_denoise_dual_guided_region likewise: for every pixel of the region, byte for byte what
+ *                                        rmd_denoise_dual_guided_slope writes there; nothing else is written (the slopes are made over the whole frame)
+ * rmd_denoise_dual_select_slope        = rmd_denoise_dual_select with cand_slopes after cands: a HOST array of n_cands doubles, candidate i's slope, read
+ *                                        for guided candidates only; NULL = every slope 0 = rmd_denoise_dual_select exactly
+ * feat_dev = feat_sq_dev = NULL behaves as in the call without the suffix, and `slope` is then not read.  With features, a slope (of a guided
+ * candidate: cand_slopes[i]) that is not finite or is negative is RMD_ERR_INVALID_ARGUMENT before the device is touched, after the checks of k_f
+ * and tau; every other rule, and its order, is that of the call without the suffix.  Synchronous, and they report an earlier device fault, like those.
+ * The a-trous filters have no slope form.  Values a caller may start from: slope 3 at k_f 1.0, tau 1e-2.
+ */
+rmd_status rmd_denoise_guided_slope(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                                    uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                                    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double slope, double *out_dev);
+rmd_status rmd_denoise_dual_guided_slope(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double slope,
+    double *out_dev, double *err_dev);
+rmd_status rmd_denoise_dual_guided_slope_region(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    const rmd_tile_rect *region, uint32_t n_region,
+    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double slope,
+    double *out_dev, double *err_dev);
+rmd_status rmd_denoise_dual_select_slope(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t radius, uint32_t patch_radius,
+    const rmd_denoise_candidate *cands, const double *cand_slopes, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
     double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev);
 /*
  * rmd_denoise_atrous on TWO SAMPLE HALVES, each filtered with the weights of the other, with rmd_denoise_dual's error estimate: the fast filter in

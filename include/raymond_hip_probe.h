@@ -123,11 +123,20 @@ rmd_status rmd_probe_scene_plan(const rmd_scene *scene, uint64_t *out8, size_t n
  * 3 = rmd_denoise_atrous_dual, 4 = rmd_denoise_atrous_dual_region, 5 = rmd_denoise_dual_select, 6 = rmd_tile_error_dual; guided = 1: the call has
  * features (form 5: a guided candidate); n_table: the entries of a region form's block tables (forms 2 and 4; ignored by the others).  Part p
  * (RMD_PROBE_SCRATCH_PARTS of them, in ScratchPart's order) has out3[3 * p] = 1 when the form holds it, then its offset and its length in bytes;
+ * out3 therefore holds 3 * RMD_PROBE_SCRATCH_PARTS words — 45 since the slope planes became the fifteenth part (42 before: a caller sizes out3 by the constant);
  * *total = the block's bytes. */
 #define RMD_PROBE_SCRATCH_FORMS 7u
-#define RMD_PROBE_SCRATCH_PARTS 14u
+#define RMD_PROBE_SCRATCH_PARTS 15u
 rmd_status rmd_probe_denoise_scratch(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t n_cands, uint64_t n_table,
                                      uint64_t *out3, uint64_t *total);
+/* ... of a _slope call (rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope[_region], rmd_denoise_dual_select_slope): sloped = 1 when a slope the call
+ * reads is > 0 — the forms 0, 2 and 5 with features then hold the seven slope planes, behind the feature planes; sloped = 0 is rmd_probe_denoise_scratch. */
+rmd_status rmd_probe_denoise_scratch_slope(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t sloped, uint32_t n_cands,
+                                           uint64_t n_table, uint64_t *out3, uint64_t *total);
+/* The slope floors of the _slope denoise calls as the device makes them (raymond_amd/csrc/denoise.hip: feature_slope_kernel, through the launcher the entry
+ * points call): fplanes7 = the seven planar per-pixel feature means f (W*H doubles each, HOST memory; a NaN in plane 0 marks a pixel that is not
+ * feature-valid), mplanes7 = the seven planes m_j = (slope * slope) * (h_j + v_j) of include/raymond_hip.h, zeros at a pixel that is not feature-valid. */
+rmd_status rmd_probe_feature_slope(rmd_context *ctx, const double *fplanes7, uint32_t width, uint32_t height, double slope, double *mplanes7);
 rmd_status rmd_probe_pretest_pairs(rmd_context *ctx, size_t n, const double *sphere5, const double *pos9, const double *ray6, int32_t *pass,
                                    int32_t *hit, double *t);
 

@@ -106,6 +106,27 @@ extern "C" {
                                rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32, radius: u32, patch_radius: u32,
                                cands: *const rmd_denoise_candidate, n_cands: u32, sure_window: u32, select_window: u32, out_dev: *mut f64, err_dev: *mut f64,
                                sure_dev: *mut f64, win_dev: *mut u32) -> i32;
+    // the guided non-local-means filters with the feature-slope term: `slope` (finite, >= 0; 0 = the call without the suffix, bit for bit) is the pixels of
+    // a feature's local slope that are not an edge — a curved mirror's normals no longer cost a pixel its neighbours; 3 is the value to start from.
+    // rmd_denoise_dual_select_slope: cand_slopes is a HOST array of n_cands f64, read for guided candidates only (null: all 0)
+    fn rmd_denoise_guided_slope(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
+                                width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, radius: u32, patch_radius: u32,
+                                k: f64, alpha: f64, k_f: f64, tau: f64, slope: f64, out_dev: *mut f64) -> i32;
+    fn rmd_denoise_dual_guided_slope(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64,
+                                     accum_sq_b_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32,
+                                     rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32,
+                                     radius: u32, patch_radius: u32, k: f64, alpha: f64, k_f: f64, tau: f64, slope: f64, out_dev: *mut f64,
+                                     err_dev: *mut f64) -> i32;
+    fn rmd_denoise_dual_guided_slope_region(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64,
+                                            accum_sq_b_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32,
+                                            rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32,
+                                            n_rects: u32, region: *const rmd_tile_rect, n_region: u32, radius: u32, patch_radius: u32, k: f64, alpha: f64,
+                                            k_f: f64, tau: f64, slope: f64, out_dev: *mut f64, err_dev: *mut f64) -> i32;
+    fn rmd_denoise_dual_select_slope(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64,
+                                     accum_sq_b_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32,
+                                     rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32,
+                                     radius: u32, patch_radius: u32, cands: *const rmd_denoise_candidate, cand_slopes: *const f64, n_cands: u32,
+                                     sure_window: u32, select_window: u32, out_dev: *mut f64, err_dev: *mut f64, sure_dev: *mut f64, win_dev: *mut u32) -> i32;
     // the fast filter on the two halves, each under the other's weights, with rmd_denoise_dual's error estimate (feat_dev = feat_sq_dev = null: the
     // colour weights alone; err_dev may be null): what the adaptive check calls with denoise_dual_atrous
     fn rmd_denoise_atrous_dual(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64, accum_sq_b_dev: *const f64,

@@ -67,6 +67,9 @@ rmd_status check_feature_weights(rmd_context *ctx, const std::string &name, doub
 	if (!(tau > 0.0) || !std::isfinite(tau)) return fail(ctx, kInvalid, name + "tau must be finite and > 0");
 	return RMD_OK;
 }
+rmd_status check_slope(rmd_context *ctx, const std::string &name, double slope) { // (the _slope calls; the others pass 0)
+	return !(slope >= 0.0) || !std::isfinite(slope) ? fail(ctx, kInvalid, name + "slope must be finite and >= 0") : RMD_OK;
+}
 rmd_status check_rects(rmd_context *ctx, const std::string &name, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height) {
 	const char *why = nullptr;
 	return rmd::denoise_rects_ok(rects, n_rects, width, height, &why) ? RMD_OK : fail(ctx, kInvalid, name + why);
@@ -141,7 +144,7 @@ rmd_status finish(rmd_context *ctx) {
 }
 
 // ---------------------------------------------------------------- the single-buffer filters (denoise.hip, denoise_atrous.hip)
-// rmd_denoise and rmd_denoise_guided (levels null), rmd_denoise_atrous (levels given; radius and patch_radius unused).  `what`: the entry point's name
+// rmd_denoise and rmd_denoise_guided[_slope] (levels null), rmd_denoise_atrous (levels given; radius and patch_radius unused).  `what`: the entry point's name
 rmd_status denoise_single(const char *what, rmd_context *ctx, DenoiseInput in, const uint32_t *levels, uint32_t radius, uint32_t patch_radius, const DenoiseWeights &w,
                           double *out_dev) {
 	const std::string name = std::string(what) + ": ";
@@ -154,18 +157,21 @@ rmd_status denoise_single(const char *what, rmd_context *ctx, DenoiseInput in, c
 	if (any_overlap({{in.feat, fbytes}, {in.feat_sq, fbytes}, {out_dev, bytes}})) return fail(ctx, kInvalid, name + "feat_dev, feat_sq_dev and out_dev must not alias");
 	if (rmd_status s = levels ? check_levels(ctx, name, *levels) : check_window(ctx, name, radius, patch_radius)) return s;
 	if (rmd_status s = check_weights(ctx, name, w.k, w.alpha)) return s;
-	if (guided)
+	if (guided) {
 		if (rmd_status s = check_feature_weights(ctx, name, w.k_f, w.tau)) return s;
+		if (rmd_status s = check_slope(ctx, name, w.slope)) return s;
+	}
+	const bool sloped = guided && !levels && w.slope > 0.0;
 	return rmd::guarded(ctx, what, [&] {
 		if (rmd_status s = check_rects(ctx, name, in.rects, in.n_rects, in.W, in.H)) return s;
 		if (rmd_status s = rmd::bind(ctx)) return s;
 		Scratch sc;
-		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(levels ? rmd::kScratchAtrous : rmd::kScratchSingle, in.W, in.H, in.n_rects, guided, 0u, 0u))) return s;
+		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(levels ? rmd::kScratchAtrous : rmd::kScratchSingle, in.W, in.H, in.n_rects, guided, 0u, 0u, sloped))) return s;
 		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
 		uint32_t *n_img = sc.part<uint32_t>(rmd::kPartCountImg);
 		double *feat_planes = sc.part<double>(rmd::kPartFeatPlanes);
 		if (levels) RMD_HIP(ctx, rmd::launch_denoise_atrous(ctx->stream, in, w, *levels, n_img, sc.part<double>(rmd::kPartPlanes), feat_planes, out_dev));
-		else RMD_HIP(ctx, rmd::launch_denoise_guided(ctx->stream, in, w, radius, patch_radius, n_img, feat_planes, out_dev));
+		else RMD_HIP(ctx, rmd::launch_denoise_guided(ctx->stream, in, w, radius, patch_radius, n_img, feat_planes, sc.part<double>(rmd::kPartSlopePlanes), out_dev));
 		return finish(ctx);
 	});
 }
@@ -173,7 +179,7 @@ rmd_status denoise_single(const char *what, rmd_context *ctx, DenoiseInput in, c
 // ---------------------------------------------------------------- the dual-buffer filters (denoise_dual.hip, denoise_atrous_dual.hip)
 // rmd_denoise_dual and its guided and region forms (levels null), rmd_denoise_atrous_dual and its region form (levels given; radius and patch_radius
 // unused).  `regional`: a region form, which writes the pixels of its n_region rects only; its region may still be NULL when n_region is 0.  Without
-// features rect_counts_f, k_f and tau are not read
+// features rect_counts_f, k_f, tau and the slope (the _slope calls: w.slope, 0 in every other) are not read
 rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, DenoiseInput in, const rmd_tile_rect *region, uint32_t n_region, const uint32_t *levels,
                         uint32_t radius, uint32_t patch_radius, const DenoiseWeights &w, double *out_dev, double *err_dev) {
 	const std::string name = std::string(what) + ": ";
@@ -190,8 +196,11 @@ rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, Denoi
 		return fail(ctx, kInvalid, name + "feat_dev and feat_sq_dev must not alias each other, the sum buffers, out_dev or err_dev");
 	if (rmd_status s = levels ? check_levels(ctx, name, *levels) : check_window(ctx, name, radius, patch_radius)) return s;
 	if (rmd_status s = check_weights(ctx, name, w.k, w.alpha)) return s;
-	if (guided)
+	if (guided) {
 		if (rmd_status s = check_feature_weights(ctx, name, w.k_f, w.tau)) return s;
+		if (rmd_status s = check_slope(ctx, name, w.slope)) return s;
+	}
+	const bool sloped = guided && !levels && w.slope > 0.0;
 	return rmd::guarded(ctx, what, [&] {
 		if (rmd_status s = check_rects(ctx, name, in.rects, in.n_rects, in.W, in.H)) return s;
 		if (regional)
@@ -212,7 +221,7 @@ rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, Denoi
 		const std::vector<rmd::DualBlock> &blocks = levels ? tables.table : table;
 		const rmd::ScratchForm form = !levels ? rmd::kScratchDual : regional ? rmd::kScratchAtrousDualRegion : rmd::kScratchAtrousDual;
 		Scratch sc; // (only the a-trous region form keeps its block between calls)
-		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(form, in.W, in.H, in.n_rects, guided, 0u, blocks.size()),
+		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(form, in.W, in.H, in.n_rects, guided, 0u, blocks.size(), sloped),
 		                            form == rmd::kScratchAtrousDualRegion ? &ctx->atrous_region_scratch : nullptr))
 			return s;
 		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
@@ -221,12 +230,65 @@ rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, Denoi
 		uint32_t *n_img = sc.part<uint32_t>(rmd::kPartCountImg), *n_f_img = sc.part<uint32_t>(rmd::kPartFeatCountImg);
 		double *planes = sc.part<double>(rmd::kPartPlanes), *feat_planes = sc.part<double>(rmd::kPartFeatPlanes);
 		if (!levels)
-			RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, in, w, radius, patch_radius, n_img, planes, sc.part<double>(rmd::kPartFb), n_f_img, feat_planes, d_table,
-			                                      (uint32_t)table.size(), out_dev, err_dev));
+			RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, in, w, radius, patch_radius, n_img, planes, sc.part<double>(rmd::kPartFb), n_f_img, feat_planes,
+			                                      sc.part<double>(rmd::kPartSlopePlanes), d_table, (uint32_t)table.size(), out_dev, err_dev));
 		else if (regional)
 			RMD_HIP(ctx, rmd::launch_denoise_atrous_dual_region(ctx->stream, in, w, *levels, n_img, planes, n_f_img, feat_planes, d_table, tables.first.data(),
 			                                                    tables.count.data(), out_dev, err_dev));
 		else RMD_HIP(ctx, rmd::launch_denoise_atrous_dual(ctx->stream, in, w, *levels, n_img, planes, n_f_img, feat_planes, out_dev, err_dev));
+		return finish(ctx);
+	});
+}
+
+// ---------------------------------------------------------------- the selecting filter (denoise_dual.hip)
+// rmd_denoise_dual_select and rmd_denoise_dual_select_slope (denoise_dual.hip): the window is checked before the candidates, aliasing last.  cand_slopes: the
+// _slope call's host array (null: every slope 0, and then exactly the launches and the scratch of rmd_denoise_dual_select), read for guided candidates only
+rmd_status denoise_dual_select(const char *what, rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                                   const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                   const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t radius,
+                                   uint32_t patch_radius, const rmd_denoise_candidate *cands, const double *cand_slopes, uint32_t n_cands, uint32_t sure_window,
+                                   uint32_t select_window, double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev) {
+	const std::string name = std::string(what) + ": ";
+	DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
+	                                   rect_counts_f, n_rects);
+	if (rmd_status s = check_frame(ctx, name, in, true, out_dev)) return s;
+	if (!cands || n_cands == 0 || n_cands > rmd::kDenoiseMaxCandidates) return fail(ctx, kInvalid, name + "n_cands must be 1 .. 4, cands not NULL");
+	if (sure_window > rmd::kDenoiseMaxSelectWindow || select_window > rmd::kDenoiseMaxSelectWindow) return fail(ctx, kInvalid, name + "sure_window and select_window must be <= 5");
+	if (rmd_status s = check_features(ctx, name, in, false)) return s;
+	if (rmd_status s = check_window(ctx, name, radius, patch_radius)) return s;
+	bool guided = false; // a guided candidate: only then are the features read
+	bool sloped = false; // ... with a slope > 0: only then are the slope planes made
+	for (uint32_t i = 0; i < n_cands; i++) {
+		const rmd_denoise_candidate &c = cands[i];
+		const std::string who = name + "candidate " + std::to_string(i) + ": ";
+		if (c.reserved != 0u) return fail(ctx, kInvalid, who + "reserved must be 0");
+		if (rmd_status s = check_weights(ctx, who, c.k, c.alpha)) return s;
+		if (!c.guided) continue;
+		guided = true;
+		if (!feat_dev) return fail(ctx, kInvalid, who + "guided, but feat_dev and feat_sq_dev are NULL");
+		if (n_rects && !rect_counts_f) return fail(ctx, kInvalid, who + "guided, but rect_counts_f is NULL with n_rects > 0");
+		if (rmd_status s = check_feature_weights(ctx, who, c.k_f, c.tau)) return s;
+		if (cand_slopes) {
+			if (rmd_status s = check_slope(ctx, who, cand_slopes[i])) return s;
+			sloped = sloped || cand_slopes[i] > 0.0;
+		}
+	}
+	// no two ranges overlap: five of W*H*3 doubles; err_dev's and sure_dev's W*H doubles, win_dev's W*H words, the two of W*H*7 doubles, where given
+	const unsigned __int128 n = (unsigned __int128)width * height;
+	if (any_overlap({{accum_a_dev, n * 24u}, {accum_sq_a_dev, n * 24u}, {accum_b_dev, n * 24u}, {accum_sq_b_dev, n * 24u}, {out_dev, n * 24u}, {err_dev, n * 8u}, {sure_dev, n * 8u},
+	                 {win_dev, n * 4u}, {feat_dev, n * 8u * RMD_FEATURE_CHANNELS}, {feat_sq_dev, n * 8u * RMD_FEATURE_CHANNELS}}))
+		return fail(ctx, kInvalid, name + "the sum buffers, the feature buffers, out_dev, err_dev, sure_dev and win_dev must not alias");
+	return rmd::guarded(ctx, what, [&] {
+		if (rmd_status s = check_rects(ctx, name, rects, n_rects, width, height)) return s;
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		if (!guided) in.feat = in.feat_sq = nullptr;
+		Scratch sc;
+		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(rmd::kScratchDualSelect, width, height, n_rects, guided, n_cands, 0u, sloped))) return s;
+		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
+		RMD_HIP(ctx, rmd::launch_denoise_dual_select(ctx->stream, in, radius, patch_radius, cands, sloped ? cand_slopes : nullptr, n_cands, sure_window, select_window,
+		                                             sc.part<uint32_t>(rmd::kPartCountImg), sc.part<double>(rmd::kPartPlanes), sc.part<double>(rmd::kPartCand),
+		                                             sc.part<double>(rmd::kPartGain), sc.part<uint32_t>(rmd::kPartWinImg), sc.part<uint32_t>(rmd::kPartFeatCountImg),
+		                                             sc.part<double>(rmd::kPartFeatPlanes), sc.part<double>(rmd::kPartSlopePlanes), out_dev, err_dev, sure_dev, win_dev));
 		return finish(ctx);
 	});
 }
@@ -310,50 +372,52 @@ rmd_status rmd_denoise_atrous_dual_region(rmd_context *ctx, const double *accum_
 	return denoise_dual("rmd_denoise_atrous_dual_region", true, ctx, in, region, n_region, &levels, 0u, 0u, {k, alpha, k_f, tau}, out_dev, err_dev);
 }
 
-// rmd_denoise_dual_select (denoise_dual.hip): the window is checked before the candidates, aliasing last
 rmd_status rmd_denoise_dual_select(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
                                    const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
                                    const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects, uint32_t radius,
                                    uint32_t patch_radius, const rmd_denoise_candidate *cands, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
                                    double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev) {
-	const std::string name = "rmd_denoise_dual_select: ";
-	DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
+	return denoise_dual_select("rmd_denoise_dual_select", ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects,
+	                           rect_counts_a, rect_counts_b, rect_counts_f, n_rects, radius, patch_radius, cands, nullptr, n_cands, sure_window, select_window, out_dev, err_dev,
+	                           sure_dev, win_dev);
+}
+
+rmd_status rmd_denoise_dual_select_slope(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                         const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                         const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
+                                         uint32_t n_rects, uint32_t radius, uint32_t patch_radius, const rmd_denoise_candidate *cands, const double *cand_slopes,
+                                         uint32_t n_cands, uint32_t sure_window, uint32_t select_window, double *out_dev, double *err_dev, double *sure_dev,
+                                         uint32_t *win_dev) {
+	return denoise_dual_select("rmd_denoise_dual_select_slope", ctx, accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects,
+	                           rect_counts_a, rect_counts_b, rect_counts_f, n_rects, radius, patch_radius, cands, cand_slopes, n_cands, sure_window, select_window, out_dev,
+	                           err_dev, sure_dev, win_dev);
+}
+
+rmd_status rmd_denoise_guided_slope(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                                    uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                                    uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double slope, double *out_dev) {
+	const DenoiseInput in = single_input(accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects);
+	return denoise_single("rmd_denoise_guided_slope", ctx, in, nullptr, radius, patch_radius, {k, alpha, k_f, tau, slope}, out_dev);
+}
+
+rmd_status rmd_denoise_dual_guided_slope(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                         const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                         const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
+                                         uint32_t n_rects, uint32_t radius, uint32_t patch_radius, double k, double alpha, double k_f, double tau, double slope,
+                                         double *out_dev, double *err_dev) {
+	const DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
 	                                   rect_counts_f, n_rects);
-	if (rmd_status s = check_frame(ctx, name, in, true, out_dev)) return s;
-	if (!cands || n_cands == 0 || n_cands > rmd::kDenoiseMaxCandidates) return fail(ctx, kInvalid, name + "n_cands must be 1 .. 4, cands not NULL");
-	if (sure_window > rmd::kDenoiseMaxSelectWindow || select_window > rmd::kDenoiseMaxSelectWindow) return fail(ctx, kInvalid, name + "sure_window and select_window must be <= 5");
-	if (rmd_status s = check_features(ctx, name, in, false)) return s;
-	if (rmd_status s = check_window(ctx, name, radius, patch_radius)) return s;
-	bool guided = false; // a guided candidate: only then are the features read
-	for (uint32_t i = 0; i < n_cands; i++) {
-		const rmd_denoise_candidate &c = cands[i];
-		const std::string who = name + "candidate " + std::to_string(i) + ": ";
-		if (c.reserved != 0u) return fail(ctx, kInvalid, who + "reserved must be 0");
-		if (rmd_status s = check_weights(ctx, who, c.k, c.alpha)) return s;
-		if (!c.guided) continue;
-		guided = true;
-		if (!feat_dev) return fail(ctx, kInvalid, who + "guided, but feat_dev and feat_sq_dev are NULL");
-		if (n_rects && !rect_counts_f) return fail(ctx, kInvalid, who + "guided, but rect_counts_f is NULL with n_rects > 0");
-		if (rmd_status s = check_feature_weights(ctx, who, c.k_f, c.tau)) return s;
-	}
-	// no two ranges overlap: five of W*H*3 doubles; err_dev's and sure_dev's W*H doubles, win_dev's W*H words, the two of W*H*7 doubles, where given
-	const unsigned __int128 n = (unsigned __int128)width * height;
-	if (any_overlap({{accum_a_dev, n * 24u}, {accum_sq_a_dev, n * 24u}, {accum_b_dev, n * 24u}, {accum_sq_b_dev, n * 24u}, {out_dev, n * 24u}, {err_dev, n * 8u}, {sure_dev, n * 8u},
-	                 {win_dev, n * 4u}, {feat_dev, n * 8u * RMD_FEATURE_CHANNELS}, {feat_sq_dev, n * 8u * RMD_FEATURE_CHANNELS}}))
-		return fail(ctx, kInvalid, name + "the sum buffers, the feature buffers, out_dev, err_dev, sure_dev and win_dev must not alias");
-	return rmd::guarded(ctx, "rmd_denoise_dual_select", [&] {
-		if (rmd_status s = check_rects(ctx, name, rects, n_rects, width, height)) return s;
-		if (rmd_status s = rmd::bind(ctx)) return s;
-		if (!guided) in.feat = in.feat_sq = nullptr;
-		Scratch sc;
-		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(rmd::kScratchDualSelect, width, height, n_rects, guided, n_cands, 0u))) return s;
-		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
-		RMD_HIP(ctx, rmd::launch_denoise_dual_select(ctx->stream, in, radius, patch_radius, cands, n_cands, sure_window, select_window, sc.part<uint32_t>(rmd::kPartCountImg),
-		                                             sc.part<double>(rmd::kPartPlanes), sc.part<double>(rmd::kPartCand), sc.part<double>(rmd::kPartGain),
-		                                             sc.part<uint32_t>(rmd::kPartWinImg), sc.part<uint32_t>(rmd::kPartFeatCountImg), sc.part<double>(rmd::kPartFeatPlanes),
-		                                             out_dev, err_dev, sure_dev, win_dev));
-		return finish(ctx);
-	});
+	return denoise_dual("rmd_denoise_dual_guided_slope", false, ctx, in, nullptr, 0u, nullptr, radius, patch_radius, {k, alpha, k_f, tau, slope}, out_dev, err_dev);
+}
+
+rmd_status rmd_denoise_dual_guided_slope_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                                const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                                const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
+                                                const uint32_t *rect_counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t radius,
+                                                uint32_t patch_radius, double k, double alpha, double k_f, double tau, double slope, double *out_dev, double *err_dev) {
+	const DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
+	                                   rect_counts_f, n_rects);
+	return denoise_dual("rmd_denoise_dual_guided_slope_region", true, ctx, in, region, n_region, nullptr, radius, patch_radius, {k, alpha, k_f, tau, slope}, out_dev, err_dev);
 }
 
 rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,

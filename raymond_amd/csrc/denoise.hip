@@ -17,6 +17,9 @@
 // q's f and g are read per offset straight from planar images in global memory (feature_planes_kernel writes them: 14 planes of W*H doubles, a
 // pixel that is not feature-valid keeps a NaN in its f of channel 0) — neighbouring lanes read neighbouring doubles and consecutive offsets shift
 // by one pixel, so these are cache hits; f64 planes for the apron do not fit in LDS beside the colour planes.
+// SLOPE (rmd_denoise_guided_slope at slope > 0): feature_slope_kernel makes seven more planes, the slope floors m of the seven f
+// planes, and denoise_kernel<TW, DenoiseSlope> — instantiations of their own again — reads p's seven m once, where the denominators are made.  At slope 0
+// neither is launched.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -43,13 +46,33 @@ __global__ __launch_bounds__(256) void feature_planes_kernel(const double *__res
 	feature_planes_pixel(F, G, i, n, moments_pixel(S, Q, i, n, u, v), N, planes);
 }
 
+// The slope floors of rmd_denoise_guided_slope and of the dual _slope calls (denoise_dual.hip's launchers call launch_feature_slope too): feature_slope_pixel's
+// seven planes m from the seven planar f that feature_planes_kernel / dual_feature_planes_kernel have written.  Whole-frame in every form.  Consecutive
+// lanes hold consecutive pixels of a row, so each of the five reads per channel is coalesced
+__global__ __launch_bounds__(256) void feature_slope_kernel(const double *__restrict__ fplanes, uint32_t W, uint32_t H, double s2, double *__restrict__ mplanes) {
+	const size_t N = (size_t)W * H, i = (size_t)blockIdx.x * 256u + threadIdx.x;
+	if (i >= N) return;
+	feature_slope_pixel(fplanes, i, (uint32_t)(i % W), (uint32_t)(i / W), W, H, N, s2, mplanes);
+}
+hipError_t launch_feature_slope(hipStream_t stream, const double *feat_planes, uint32_t W, uint32_t H, double slope, double *slope_planes) {
+	if (feat_planes == nullptr || slope_planes == nullptr) return hipErrorInvalidValue;
+	const size_t N = (size_t)W * H;
+	hipLaunchKernelGGL(feature_slope_kernel, dim3((uint32_t)((N + 255u) / 256u)), dim3(256), 0, stream, feat_planes, W, H, slope * slope, slope_planes);
+	return hipGetLastError();
+}
+
 // the guided kernel's extra arguments: the planar f and g images, k_f^2 and tau
 struct DenoiseGuide {
 	const double *planes;
 	double kf2, tau;
 };
+// ... and with the slope floors (rmd_denoise_guided_slope at slope > 0): feature_slope_kernel's seven planes m
+struct DenoiseSlope : DenoiseGuide {
+	const double *m;
+};
 // GUIDED is the presence of a DenoiseGuide argument: denoise_kernel<TW> (no such argument) keeps the signature and the code it had before the
-// guided filter existed, denoise_kernel<TW, DenoiseGuide> is the guided instantiation.
+// guided filter existed, denoise_kernel<TW, DenoiseGuide> is the guided instantiation.  SLOPE: the argument is a DenoiseSlope — an instantiation of its
+// own again (denoise_kernel<TW, DenoiseSlope>), which reads p's seven m once, where den is made; the per-pair loop is the guided one's.
 template <int TW, class... G>
 __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restrict__ S, const double *__restrict__ Q, const uint32_t *__restrict__ n_img,
                                                           uint32_t W, uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ out, G... guide) {
@@ -57,9 +80,12 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 	static_assert(sizeof...(G) <= 1, "at most one DenoiseGuide");
 	[[maybe_unused]] const double *planes = nullptr;
 	[[maybe_unused]] double kf2 = 0.0, tau = 0.0;
+	constexpr bool SLOPE = (__is_same(G, DenoiseSlope) || ...);
+	[[maybe_unused]] const double *mplanes = nullptr;
 	if constexpr (GUIDED) {
 		const DenoiseGuide gd = (guide, ...);
 		planes = gd.planes, kf2 = gd.kf2, tau = gd.tau;
+		if constexpr (SLOPE) mplanes = (guide, ...).m;
 	}
 	extern __shared__ double lds[];
 	constexpr int TH = (int)kDenoiseTile, NT = TW * TH;
@@ -122,7 +148,8 @@ __global__ __launch_bounds__(TW * 16) void denoise_kernel(const double *__restri
 #pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = planes[(size_t)j * N + pixp], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pixp];
-			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
+			if constexpr (SLOPE) den[j] = feature_den(fp[j], gp[j], j, kf2, tau, mplanes[(size_t)j * N + pixp]);
+			else den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = p_ok && fp[0] == fp[0];
 	}
@@ -226,9 +253,10 @@ hipError_t launch_denoise_planes(hipStream_t stream, const DenoiseInput &in, uin
 }
 
 hipError_t launch_denoise_guided(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img,
-                                 double *feat_planes, double *out) {
+                                 double *feat_planes, double *slope_planes, double *out) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
-	const bool guided = in.feat != nullptr;
+	const bool guided = in.feat != nullptr, sloped = guided && w.slope > 0.0;
+	if (sloped && slope_planes == nullptr) return hipErrorInvalidValue;
 	const double *accum = in.accum_a, *accum_sq = in.accum_sq_a;
 	const uint32_t W = in.W, H = in.H;
 	hipError_t e = launch_denoise_planes(stream, in, n_img, feat_planes);
@@ -236,13 +264,20 @@ hipError_t launch_denoise_guided(hipStream_t stream, const DenoiseInput &in, con
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits: 145,152 B at r = 12, f = 4)
-	const void *fn = guided ? (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32, DenoiseGuide>) : reinterpret_cast<const void *>(&denoise_kernel<24, DenoiseGuide>))
-	                        : (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32>) : reinterpret_cast<const void *>(&denoise_kernel<24>));
+	if (sloped && (e = launch_feature_slope(stream, feat_planes, W, H, w.slope, slope_planes)) != hipSuccess) return e;
+	const void *fn = sloped ? (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32, DenoiseSlope>) : reinterpret_cast<const void *>(&denoise_kernel<24, DenoiseSlope>))
+	                 : guided ? (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32, DenoiseGuide>) : reinterpret_cast<const void *>(&denoise_kernel<24, DenoiseGuide>))
+	                          : (tw == 32u ? reinterpret_cast<const void *>(&denoise_kernel<32>) : reinterpret_cast<const void *>(&denoise_kernel<24>));
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
 	const dim3 grid((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
 	const int ri = (int)radius, fi = (int)patch_radius;
 	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
-	if (guided) {
+	if (sloped) {
+		DenoiseSlope gs;
+		gs.planes = feat_planes, gs.kf2 = kf2, gs.tau = w.tau, gs.m = slope_planes;
+		if (tw == 32u) hipLaunchKernelGGL((denoise_kernel<32, DenoiseSlope>), grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out, gs);
+		else hipLaunchKernelGGL((denoise_kernel<24, DenoiseSlope>), grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out, gs);
+	} else if (guided) {
 		const DenoiseGuide gd{feat_planes, kf2, w.tau};
 		if (tw == 32u) hipLaunchKernelGGL((denoise_kernel<32, DenoiseGuide>), grid, dim3(32 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out, gd);
 		else hipLaunchKernelGGL((denoise_kernel<24, DenoiseGuide>), grid, dim3(24 * kDenoiseTile), lds, stream, accum, accum_sq, n_img, W, H, ri, fi, k2, w.alpha, out, gd);

@@ -29,10 +29,53 @@ __device__ inline void denoise_moments(double s, double q, double nd, double &u,
 // ... and the finiteness a valid pixel needs of every s and q
 __device__ inline bool denoise_finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }
 
-// The denominator of Phi_j(p, .): eps + k_f^2 * max(tau * s_pj, g_pj), s = 1 but for the depth (the last channel), where it is f_pj^2
-__device__ inline double feature_den(double fp, double gp, int j, double kf2, double tau) {
+// max(tau * s_pj, g_pj), s = 1 but for the depth (the last channel), where it is f_pj^2
+__device__ inline double feature_scale(double fp, double gp, int j, double tau) {
 	const double a = tau * (j < kDenoiseFeat - 1 ? 1.0 : fp * fp);
-	return kDenoiseEps + kf2 * (a > gp ? a : gp);
+	return a > gp ? a : gp;
+}
+// The denominator of Phi_j(p, .): eps + k_f^2 * max(tau * s_pj, g_pj)
+__device__ inline double feature_den(double fp, double gp, int j, double kf2, double tau) { return kDenoiseEps + kf2 * feature_scale(fp, gp, j, tau); }
+// ... and with the slope's floor m_pj under it (the _slope calls): m replaces the maximum where it is larger (a NaN m is skipped by the comparison)
+__device__ inline double feature_den(double fp, double gp, int j, double kf2, double tau, double m) {
+	double t = feature_scale(fp, gp, j, tau);
+	if (m > t) t = m;
+	return kDenoiseEps + kf2 * t;
+}
+// One axis' share of a feature's local slope at a pixel with the value f: with a_l = f - f_l and a_r = f_r - f, the smaller of a_l*a_l and a_r*a_r when
+// both neighbours are present, else 0.0 — a slope that continues on both sides counts, a step (which has a flat side) does not
+__device__ inline double feature_slope_axis(double f, double fl, bool has_l, double fr, bool has_r) {
+	if (!(has_l && has_r)) return 0.0;
+	const double al = f - fl, ar = fr - f;
+	const double l2 = al * al, r2 = ar * ar;
+	return l2 < r2 ? l2 : r2;
+}
+// Pixel i = (x, y)'s seven slope floors m_j = s2 * (h_j + v_j), s2 = slope * slope, from the seven planar f (fplanes: feature_planes_pixel's, N doubles each;
+// a NaN in plane 0 marks a pixel that is not FEATURE-VALID) into mplanes.  A neighbour is present if it lies inside the frame and is feature-valid; a pixel
+// that is not feature-valid itself gets seven zeros (nothing reads them: it has no feature weight)
+__device__ inline void feature_slope_pixel(const double *__restrict__ fplanes, size_t i, uint32_t x, uint32_t y, uint32_t W, uint32_t H, size_t N, double s2,
+                                           double *__restrict__ mplanes) {
+	const double f0 = fplanes[i];
+	const bool ok = f0 == f0;
+	bool has_l = false, has_r = false, has_u = false, has_d = false;
+	if (ok) {
+		if (x >= 1u) has_l = fplanes[i - 1] == fplanes[i - 1];
+		if (x + 1u < W) has_r = fplanes[i + 1] == fplanes[i + 1];
+		if (y >= 1u) has_u = fplanes[i - W] == fplanes[i - W];
+		if (y + 1u < H) has_d = fplanes[i + W] == fplanes[i + W];
+	}
+#pragma unroll
+	for (int j = 0; j < kDenoiseFeat; j++) {
+		const double *fj = fplanes + (size_t)j * N;
+		double m = 0.0;
+		if (ok) {
+			const double f = j == 0 ? f0 : fj[i];
+			const double h = feature_slope_axis(f, has_l ? fj[i - 1] : 0.0, has_l, has_r ? fj[i + 1] : 0.0, has_r);
+			const double v = feature_slope_axis(f, has_u ? fj[i - W] : 0.0, has_u, has_d ? fj[i + W] : 0.0, has_d);
+			m = s2 * (h + v);
+		}
+		mplanes[(size_t)j * N + i] = m;
+	}
 }
 // Phi_j(p, q) (a NaN loses the caller's `phi > Df`)
 __device__ inline double feature_phi(double fp, double gp, double den, double fq, double gq) {

@@ -27,6 +27,9 @@
 // NaN in its f of channel 0), and step 3 of each cross pass makes rmd_denoise_guided's w_f of the pixel pair and takes min(w, w_f): p's seven f, g
 // and denominators in registers, q's fourteen values per taken neighbour from the planes in global memory.  w_f is evaluated in BOTH passes
 // (DESIGN.md section 15); the LDS layout is unchanged.
+// SLOPE (the dual _slope calls at slope > 0): one more optional argument after the DualGuide, a DualSlope — the seven planes m that
+// denoise.hip's feature_slope_kernel makes of the f planes, over the whole frame in the region form too; the pass reads p's seven m once, where the
+// denominators are made.  Instantiations of their own once more: the twelve without it keep their arguments and their instructions.
 // SELECTION (rmd_denoise_dual_select): the whole-frame cross pass takes one more optional trailing argument, a DualGain, and then
 // also writes g(p) = w(p, p) / sum_q w(p, q), the derivative of f(p) by the value half's own u(p) — instantiations of their own again, so the eight
 // above keep their arguments and their instructions.  dual_sure_kernel makes a candidate's per-pixel SURE from the planes, its two f and the two g
@@ -83,6 +86,10 @@ struct DualGuide {
 	const double *planes;
 	double kf2, tau;
 };
+// the _slope calls' extra argument at slope > 0 (after the DualGuide): feature_slope_kernel's seven planes m (denoise.hip)
+struct DualSlope {
+	const double *m;
+};
 // the selecting call's extra argument: the W*H image that receives g(p) = w(p, p) / sum_q w(p, q) at the pixels where fout is written
 struct DualGain {
 	double *g;
@@ -103,14 +110,16 @@ __device__ inline T dual_pick(A a, R... rest) {
 template <int TW, bool REGION, class... G>
 __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__restrict__ Pw, const double *__restrict__ Uv, const DualBlock *__restrict__ table, uint32_t W,
                                                                uint32_t H, int r, int f, double k2, double alpha, double *__restrict__ fout, G... guide) {
-	constexpr bool GUIDED = (__is_same(G, DualGuide) || ...), GAIN = (__is_same(G, DualGain) || ...);
-	static_assert(sizeof...(G) == (GUIDED ? 1 : 0) + (GAIN ? 1 : 0), "at most one DualGuide, then at most one DualGain");
+	constexpr bool GUIDED = (__is_same(G, DualGuide) || ...), GAIN = (__is_same(G, DualGain) || ...), SLOPE = (__is_same(G, DualSlope) || ...);
+	static_assert(sizeof...(G) == (GUIDED ? 1 : 0) + (SLOPE ? 1 : 0) + (GAIN ? 1 : 0) && (GUIDED || !SLOPE), "at most one DualGuide, with it at most one DualSlope, then at most one DualGain");
 	[[maybe_unused]] const double *fplanes = nullptr;
 	[[maybe_unused]] double kf2 = 0.0, tau = 0.0;
 	if constexpr (GUIDED) {
 		const DualGuide gd = dual_pick<DualGuide>(guide...);
 		fplanes = gd.planes, kf2 = gd.kf2, tau = gd.tau;
 	}
+	[[maybe_unused]] const double *mplanes = nullptr; // SLOPE: p's seven m are read once, where den is made; the per-pair loop is the guided one's
+	if constexpr (SLOPE) mplanes = dual_pick<DualSlope>(guide...).m;
 	[[maybe_unused]] double *gout = nullptr;
 	[[maybe_unused]] double wcentre = 0.0; // GAIN: w(p, p) — set for every p_ok pixel, whose own offset (0, 0) is always taken
 	if constexpr (GAIN) gout = dual_pick<DualGain>(guide...).g;
@@ -171,7 +180,8 @@ __global__ __launch_bounds__(TW * 16) void denoise_dual_kernel(const double *__r
 #pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = fplanes[(size_t)j * N + pixp], gp[j] = fplanes[(size_t)(kDenoiseFeat + j) * N + pixp];
-			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
+			if constexpr (SLOPE) den[j] = feature_den(fp[j], gp[j], j, kf2, tau, mplanes[(size_t)j * N + pixp]);
+			else den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = p_ok && fp[0] == fp[0];
 	}
@@ -279,14 +289,16 @@ __global__ __launch_bounds__(512) void dual_combine_region_kernel(const double *
 
 template <int TW, bool REGION>
 static hipError_t launch_dual_pass(hipStream_t stream, dim3 grid, size_t lds, const double *Pw, const double *Uv, const DualBlock *table, uint32_t W, uint32_t H, int r,
-                                   int f, double k2, double alpha, double *fout, const DualGuide *gd) {
-	if (gd) hipLaunchKernelGGL((denoise_dual_kernel<TW, REGION, DualGuide>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, r, f, k2, alpha, fout, *gd);
+                                   int f, double k2, double alpha, double *fout, const DualGuide *gd, const DualSlope *gs) {
+	if (gd && gs) hipLaunchKernelGGL((denoise_dual_kernel<TW, REGION, DualGuide, DualSlope>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, r, f, k2, alpha, fout, *gd, *gs);
+	else if (gd) hipLaunchKernelGGL((denoise_dual_kernel<TW, REGION, DualGuide>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, r, f, k2, alpha, fout, *gd);
 	else hipLaunchKernelGGL((denoise_dual_kernel<TW, REGION>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, table, W, H, r, f, k2, alpha, fout);
 	return hipGetLastError();
 }
 template <int TW, bool REGION>
-static const void *dual_pass_fn(bool guided) {
-	return guided ? reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION, DualGuide>) : reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION>);
+static const void *dual_pass_fn(bool guided, bool sloped) {
+	return sloped ? reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION, DualGuide, DualSlope>)
+	     : guided ? reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION, DualGuide>) : reinterpret_cast<const void *>(&denoise_dual_kernel<TW, REGION>);
 }
 
 // What every dual call makes first, once — also the filters of other units (denoise_atrous_dual.hip): both halves' count images and the twelve planes;
@@ -316,10 +328,12 @@ hipError_t launch_dual_planes(hipStream_t stream, const DenoiseInput &in, uint32
 }
 
 hipError_t launch_denoise_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img, double *planes,
-                               double *f_b, uint32_t *n_f_img, double *feat_planes, const DualBlock *table, uint32_t n_blocks, double *out, double *err) {
+                               double *f_b, uint32_t *n_f_img, double *feat_planes, double *slope_planes, const DualBlock *table, uint32_t n_blocks, double *out,
+                               double *err) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch) return hipErrorInvalidValue;
-	const bool guided = in.feat != nullptr;
+	const bool guided = in.feat != nullptr, sloped = guided && w.slope > 0.0;
 	if (guided && (in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr))) return hipErrorInvalidValue;
+	if (sloped && slope_planes == nullptr) return hipErrorInvalidValue;
 	if (table && n_blocks == 0) return hipSuccess; // a region without pixels: nothing would read the planes
 	const double *accum_a = in.accum_a, *accum_b = in.accum_b;
 	const uint32_t W = in.W, H = in.H;
@@ -331,21 +345,25 @@ hipError_t launch_denoise_dual(hipStream_t stream, const DenoiseInput &in, const
 	const uint32_t tw = denoise_tile_width(radius, patch_radius);
 	const size_t lds = denoise_lds_bytes(tw, radius, patch_radius);
 	if (lds > kLdsBudgetBytes) return hipErrorInvalidConfiguration; // (never within the limits, as for denoise_kernel)
-	const void *fn = table ? (tw == 32u ? dual_pass_fn<32, true>(guided) : dual_pass_fn<24, true>(guided)) : (tw == 32u ? dual_pass_fn<32, false>(guided) : dual_pass_fn<24, false>(guided));
+	if (sloped && (e = launch_feature_slope(stream, feat_planes, W, H, w.slope, slope_planes)) != hipSuccess) return e; // (whole-frame in the region form too, as the planes are)
+	const void *fn = table ? (tw == 32u ? dual_pass_fn<32, true>(guided, sloped) : dual_pass_fn<24, true>(guided, sloped))
+	                       : (tw == 32u ? dual_pass_fn<32, false>(guided, sloped) : dual_pass_fn<24, false>(guided, sloped));
 	if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
 	const dim3 grid = table ? dim3(n_blocks) : dim3((W + tw - 1u) / tw, (H + kDenoiseTile - 1u) / kDenoiseTile);
 	const int ri = (int)radius, fi = (int)patch_radius;
 	const double k2 = w.k * w.k, alpha = w.alpha;
 	const DualGuide gd{feat_planes, w.k_f * w.k_f, w.tau};
 	const DualGuide *gp = guided ? &gd : nullptr;
+	const DualSlope gs{slope_planes};
+	const DualSlope *sp = sloped ? &gs : nullptr;
 	const double *PA = planes, *PB = planes + 6u * N;
 	for (int pass = 0; pass < 2; pass++) { // f_A: weights from B applied to u_A, into out; f_B: weights from A applied to u_B, into f_b (guided: the same w_f in both)
 		const double *Pw = pass == 0 ? PB : PA, *Uv = pass == 0 ? PA : PB;
 		double *fout = pass == 0 ? out : f_b;
-		if (table && tw == 32u) e = launch_dual_pass<32, true>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
-		else if (table) e = launch_dual_pass<24, true>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
-		else if (tw == 32u) e = launch_dual_pass<32, false>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
-		else e = launch_dual_pass<24, false>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp);
+		if (table && tw == 32u) e = launch_dual_pass<32, true>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp, sp);
+		else if (table) e = launch_dual_pass<24, true>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp, sp);
+		else if (tw == 32u) e = launch_dual_pass<32, false>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp, sp);
+		else e = launch_dual_pass<24, false>(stream, grid, lds, Pw, Uv, table, W, H, ri, fi, k2, alpha, fout, gp, sp);
 		if (e != hipSuccess) return e;
 	}
 	if (table) hipLaunchKernelGGL(dual_combine_region_kernel, grid, dim3(tw * kDenoiseTile), 0, stream, accum_a, accum_b, n_a, n_b, planes, f_b, table, tw, W, out, err);
@@ -475,9 +493,13 @@ __global__ __launch_bounds__(256) void dual_blend_kernel(const double *__restric
 // a whole-frame cross pass that also writes its gain image
 template <int TW>
 static hipError_t launch_dual_pass_gain(hipStream_t stream, dim3 grid, size_t lds, const double *Pw, const double *Uv, uint32_t W, uint32_t H, int r, int f, double k2,
-                                        double alpha, double *fout, const DualGuide *gd, DualGain gn) {
+                                        double alpha, double *fout, const DualGuide *gd, const DualSlope *gs, DualGain gn) {
 	const DualBlock *none = nullptr;
-	if (gd) {
+	if (gd && gs) {
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&denoise_dual_kernel<TW, false, DualGuide, DualSlope, DualGain>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+		hipLaunchKernelGGL((denoise_dual_kernel<TW, false, DualGuide, DualSlope, DualGain>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, none, W, H, r, f, k2, alpha, fout, *gd, *gs, gn);
+	} else if (gd) {
 		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&denoise_dual_kernel<TW, false, DualGuide, DualGain>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 		if (e != hipSuccess) return e;
 		hipLaunchKernelGGL((denoise_dual_kernel<TW, false, DualGuide, DualGain>), grid, dim3(TW * kDenoiseTile), lds, stream, Pw, Uv, none, W, H, r, f, k2, alpha, fout, *gd, gn);
@@ -490,8 +512,9 @@ static hipError_t launch_dual_pass_gain(hipStream_t stream, dim3 grid, size_t ld
 }
 
 hipError_t launch_denoise_dual_select(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t patch_radius, const rmd_denoise_candidate *cands,
-                                      uint32_t n_cands, uint32_t sure_window, uint32_t select_window, uint32_t *n_img, double *planes, double *cand_img, double *gain,
-                                      uint32_t *win_img, uint32_t *n_f_img, double *feat_planes, double *out, double *err, double *sure, uint32_t *win) {
+                                      const double *cand_slopes, uint32_t n_cands, uint32_t sure_window, uint32_t select_window, uint32_t *n_img, double *planes,
+                                      double *cand_img, double *gain, uint32_t *win_img, uint32_t *n_f_img, double *feat_planes, double *slope_planes, double *out,
+                                      double *err, double *sure, uint32_t *win) {
 	if (radius > kDenoiseMaxRadius || patch_radius > kDenoiseMaxPatch || n_cands == 0 || n_cands > kDenoiseMaxCandidates || sure_window > kDenoiseMaxSelectWindow ||
 	    select_window > kDenoiseMaxSelectWindow)
 		return hipErrorInvalidValue;
@@ -517,18 +540,27 @@ hipError_t launch_denoise_dual_select(hipStream_t stream, const DenoiseInput &in
 	const double *PA = planes, *PB = planes + 6u * N;
 	const size_t stride = 7u * N; // a candidate's images: f_A (3N), f_B (3N), SURE (N)
 	double *g_a = gain, *g_b = gain + N;
+	double made_slope = 0.0; // the slope the one set of slope planes holds (0: none yet): remade when a guided candidate's differs
 	for (uint32_t i = 0; i < n_cands; i++) {
 		const rmd_denoise_candidate &c = cands[i];
 		const double k2 = c.k * c.k;
 		const DualGuide gd{feat_planes, c.k_f * c.k_f, c.tau};
 		const DualGuide *gp = c.guided ? &gd : nullptr;
+		const double slope = c.guided && cand_slopes ? cand_slopes[i] : 0.0;
+		const DualSlope gs{slope_planes};
+		const DualSlope *sp = slope > 0.0 ? &gs : nullptr;
+		if (sp && slope != made_slope) { // (stream order: the passes of the candidate before have read the planes by then)
+			if (slope_planes == nullptr) return hipErrorInvalidValue;
+			if ((e = launch_feature_slope(stream, feat_planes, W, H, slope, slope_planes)) != hipSuccess) return e;
+			made_slope = slope;
+		}
 		double *f_a = cand_img + (size_t)i * stride, *f_b = f_a + 3u * N, *s_i = f_a + 6u * N;
 		for (int pass = 0; pass < 2; pass++) { // launch_denoise_dual's two passes
 			const double *Pw = pass == 0 ? PB : PA, *Uv = pass == 0 ? PA : PB;
 			double *fout = pass == 0 ? f_a : f_b;
 			const DualGain gn{pass == 0 ? g_a : g_b};
-			e = tw == 32u ? launch_dual_pass_gain<32>(stream, grid, lds, Pw, Uv, W, H, ri, fi, k2, c.alpha, fout, gp, gn)
-			              : launch_dual_pass_gain<24>(stream, grid, lds, Pw, Uv, W, H, ri, fi, k2, c.alpha, fout, gp, gn);
+			e = tw == 32u ? launch_dual_pass_gain<32>(stream, grid, lds, Pw, Uv, W, H, ri, fi, k2, c.alpha, fout, gp, sp, gn)
+			              : launch_dual_pass_gain<24>(stream, grid, lds, Pw, Uv, W, H, ri, fi, k2, c.alpha, fout, gp, sp, gn);
 			if (e != hipSuccess) return e;
 		}
 		hipLaunchKernelGGL(dual_sure_kernel, dim3(blocks), dim3(256), 0, stream, planes, f_a, f_b, g_a, g_b, n_a, n_b, N, s_i);

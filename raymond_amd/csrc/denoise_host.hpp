@@ -45,6 +45,7 @@ enum ScratchPart {
 	kPartCountsB,
 	kPartCountsF,
 	kPartTileErrors,  // rmd_tile_error_dual's result, n_rects doubles
+	kPartSlopePlanes, // slope_planes, 7 * W*H doubles (the _slope calls with a slope > 0; the block holds it right behind feat_planes)
 	kScratchParts
 };
 struct ScratchLayout {
@@ -54,8 +55,10 @@ struct ScratchLayout {
 };
 // The block of one call.  Every part starts on a 16-byte boundary.  `guided`: the call has features (rmd_denoise_dual_select: a guided candidate);
 // n_table: the entries of the region forms' block tables (rmd_denoise_dual[_guided]_region, rmd_denoise_atrous_dual_region), 0 for a whole-frame call;
-// the other forms take no table and ignore it
-inline ScratchLayout denoise_scratch_layout(ScratchForm form, uint32_t W, uint32_t H, uint32_t n_rects, bool guided, uint32_t n_cands, size_t n_table) {
+// the other forms take no table and ignore it; `sloped`: a guided non-local-means call (single, dual, dual_select) some slope of which is > 0 — without it every
+// block is what it was before the slope existed
+inline ScratchLayout denoise_scratch_layout(ScratchForm form, uint32_t W, uint32_t H, uint32_t n_rects, bool guided, uint32_t n_cands, size_t n_table,
+                                            bool sloped = false) {
 	ScratchLayout L;
 	const size_t N = (size_t)W * H, f64 = sizeof(double), u32 = sizeof(uint32_t);
 	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count, bool wanted = true) {
@@ -76,6 +79,7 @@ inline ScratchLayout denoise_scratch_layout(ScratchForm form, uint32_t W, uint32
 	if (form != kScratchTileError) {
 		part(kPartCountImg, u32, dual ? 2u * N : N);
 		part(kPartFeatPlanes, f64, 2u * RMD_FEATURE_CHANNELS * N, guided);
+		part(kPartSlopePlanes, f64, RMD_FEATURE_CHANNELS * N, guided && sloped && (form == kScratchSingle || form == kScratchDual || form == kScratchDualSelect));
 		part(kPartFeatCountImg, u32, N, guided && dual);
 		part(kPartTable, sizeof(DualBlock), n_table, n_table != 0u && (form == kScratchDual || form == kScratchAtrousDualRegion)); // (the region launchers alone)
 	}

@@ -124,14 +124,19 @@ struct DenoiseInput {
 	const uint32_t *counts_a, *counts_b, *counts_f;
 	uint32_t n_rects, count_image_columns, W, H;
 };
-// checked by the caller (api_denoise.cpp); k_f and tau are read only with features
+// checked by the caller (api_denoise.cpp); k_f, tau and slope are read only with features.  slope (the _slope calls; 0 everywhere else): the non-local-means
+// launchers alone read it, and at 0 they launch and read exactly what they did without it
 struct DenoiseWeights {
 	double k, alpha, k_f, tau;
+	double slope = 0.0;
 };
-// rmd_denoise / rmd_denoise_guided (denoise.hip): out = the denoised means.  Scratch: n_img W*H uint32 for the per-pixel counts; with features feat_planes,
-// 14 * W*H doubles for the planar per-pixel f and g
+// The slope floors (denoise.hip: feature_slope_kernel): slope_planes = the seven planes m_j = (slope * slope) * (h_j + v_j), W*H doubles each, from the 14
+// planes feat_planes that launch_denoise_planes / launch_dual_planes have made on the same stream.  Always the whole frame
+hipError_t launch_feature_slope(hipStream_t stream, const double *feat_planes, uint32_t W, uint32_t H, double slope, double *slope_planes);
+// rmd_denoise / rmd_denoise_guided[_slope] (denoise.hip): out = the denoised means.  Scratch: n_img W*H uint32 for the per-pixel counts; with features
+// feat_planes, 14 * W*H doubles for the planar per-pixel f and g; with features and w.slope > 0 slope_planes, 7 * W*H doubles (else not read, may be null)
 hipError_t launch_denoise_guided(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img,
-                                 double *feat_planes, double *out);
+                                 double *feat_planes, double *slope_planes, double *out);
 // The preamble of launch_denoise_guided on its own (denoise.hip), for the filters of other units: n_img = the per-pixel counts, and when feat / feat_sq
 // are given feat_planes = the 14 planar images of the per-pixel f and g (a pixel that is not feature-valid keeps a NaN in plane 0)
 hipError_t launch_denoise_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *feat_planes);
@@ -146,9 +151,11 @@ hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, con
 // of out and err is written.  table not null (rmd_denoise_dual_region; device memory): n_blocks entries (x0, y0, x_end, y_end), one per workgroup of
 // denoise_tile_width(radius, patch_radius) x 16 pixels at (x0, y0); only the pixels before (x_end, y_end), inside the frame, are written.
 // With features (rmd_denoise_dual_guided[_region]): n_f_img is W*H uint32 and feat_planes 14 * W*H doubles of further scratch.  Without: exactly the
-// launches made without the feature
+// launches made without the feature.  With features and w.slope > 0 (the _slope calls): slope_planes is 7 * W*H doubles more, made over the whole frame in
+// the region form too; else it is not read and may be null
 hipError_t launch_denoise_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t radius, uint32_t patch_radius, uint32_t *n_img, double *planes,
-                               double *f_b, uint32_t *n_f_img, double *feat_planes, const DualBlock *table, uint32_t n_blocks, double *out, double *err);
+                               double *f_b, uint32_t *n_f_img, double *feat_planes, double *slope_planes, const DualBlock *table, uint32_t n_blocks, double *out,
+                               double *err);
 // What every dual call makes first, once (denoise_dual.hip; also for the filters of other units): n_img = both halves' per-pixel counts (2 * W*H uint32),
 // planes = the twelve planar u / v images (half h's u in planes 6h + c, its v in 6h + 3 + c; a pixel that is not dual-valid keeps a NaN in plane 0), and
 // with features n_f_img and feat_planes = their per-pixel counts and their 14 planar f and g at that count (which read the dual-validity mark just left)
@@ -169,10 +176,13 @@ hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseIn
 // rmd_denoise_dual_select (denoise_dual.hip): launch_dual_planes once, then per candidate (a HOST array, checked by the caller) its two cross passes with
 // their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per candidate
 // (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read only when
-// a candidate is guided.  err, sure and win (W*H each) may be null.
+// a candidate is guided.  err, sure and win (W*H each) may be null.  cand_slopes (rmd_denoise_dual_select_slope; a HOST array of n_cands, or null = all 0):
+// a guided candidate's slope; slope_planes, 7 * W*H doubles, is one set for all of them, remade whenever the next guided candidate's slope > 0 differs from
+// the one it holds, and not read (may be null) when none is > 0
 hipError_t launch_denoise_dual_select(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t patch_radius, const rmd_denoise_candidate *cands,
-                                      uint32_t n_cands, uint32_t sure_window, uint32_t select_window, uint32_t *n_img, double *planes, double *cand_img, double *gain,
-                                      uint32_t *win_img, uint32_t *n_f_img, double *feat_planes, double *out, double *err, double *sure, uint32_t *win);
+                                      const double *cand_slopes, uint32_t n_cands, uint32_t sure_window, uint32_t select_window, uint32_t *n_img, double *planes,
+                                      double *cand_img, double *gain, uint32_t *win_img, uint32_t *n_f_img, double *feat_planes, double *slope_planes, double *out,
+                                      double *err, double *sure, uint32_t *win);
 // out[i] = sqrt(the mean of err over rect i's pixels), +inf if one of them is NaN (denoise_dual.hip: tile_error_dual_kernel; rects and out are device memory)
 hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W, double *out);
 // rmd_render_features (features.hip): for each of the P.n_work wave tiles, the first-hit features of samples P.sample_begin .. + P.sample_count - 1

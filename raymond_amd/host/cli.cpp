@@ -7,6 +7,9 @@
 //                                                                     [--denoise-alpha A]]   (the image is rmd_denoise's, on GPU 0)
 //                                                                    [--denoise-features 1 [--denoise-feature-k K] [--denoise-feature-tau T]]
 //                                                                      (needs --denoise 1: first-hit features guide the filter, rmd_denoise_guided)
+//                                                                    [--denoise-feature-slope G]   (needs a guided non-local-means filter — --denoise-features,
+//                                                                      --denoise-dual-features or --denoise-dual-select —, not with the a-trous ones: the
+//                                                                      feature-slope term at G pixels, the _slope calls; 3 is the value to start from)
 //                                                                    [--denoise-atrous 1 [--denoise-atrous-levels N] [--denoise-atrous-k K]]
 //                                                                      (needs --denoise 1, not with --denoise-dual: the fast filter for previews,
 //                                                                       rmd_denoise_atrous, guided with --denoise-features 1)
@@ -235,6 +238,7 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-feature-k")) st.denoise_feature_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-feature-tau")) st.denoise_feature_tau = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-feature-slope")) st.denoise_feature_slope = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-atrous")) st.denoise_atrous = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-atrous-levels")) st.denoise_atrous_levels = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--denoise-atrous-k")) st.denoise_atrous_k = std::atof(argv[i + 1]);

@@ -328,6 +328,7 @@ Message preview_message(rmd_context *ctx, const double *fb, const double *fb2, s
 //   denoise_dual_select:   rmd_denoise_dual_select at the setting's two candidates (it needs the features)
 //   the features given:    rmd_denoise_dual_guided[_region]
 //   otherwise:             rmd_denoise_dual[_region]
+// With denoise_feature_slope > 0 the second and the third are their _slope calls (the guided candidate's slope; the setting excludes the first).
 // Two things that a reader may take for oversights and that every caller's bytes depend on: a call with a region never selects — rmd_denoise_dual_select
 // has no region form, and a select render's adaptive check is the plain or the guided region form —; and the unguided call with a region is
 // rmd_denoise_dual_region where the one without is rmd_denoise_dual.
@@ -345,11 +346,26 @@ void denoise_dual_frame(rmd_context *ctx, const Settings &st, size_t W, size_t H
 		check(rmd_denoise_atrous_dual(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_atrous_levels, st.denoise_atrous_k,
 		                              st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
 		      ctx, "rmd_denoise_atrous_dual");
+	} else if (st.denoise_dual_select && !region && st.denoise_feature_slope > 0.0) {
+		const rmd_denoise_candidate cands[2] = {{st.denoise_k, st.denoise_alpha, 0.0, 0.0, 0u, 0u}, {1.0, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, 1u, 0u}};
+		const double slopes[2] = {0.0, st.denoise_feature_slope}; // (the guided candidate's)
+		check(rmd_denoise_dual_select_slope(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_radius, st.denoise_patch, cands,
+		                                    slopes, 2u, 2u, 2u, out, err, nullptr, nullptr),
+		      ctx, "rmd_denoise_dual_select_slope");
 	} else if (st.denoise_dual_select && !region) {
 		const rmd_denoise_candidate cands[2] = {{st.denoise_k, st.denoise_alpha, 0.0, 0.0, 0u, 0u}, {1.0, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, 1u, 0u}};
 		check(rmd_denoise_dual_select(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_radius, st.denoise_patch, cands, 2u,
 		                              2u, 2u, out, err, nullptr, nullptr),
 		      ctx, "rmd_denoise_dual_select");
+	} else if (feat && region && st.denoise_feature_slope > 0.0) {
+		check(rmd_denoise_dual_guided_slope_region(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, region, nr, st.denoise_radius,
+		                                           st.denoise_patch, st.denoise_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, st.denoise_feature_slope, out,
+		                                           err),
+		      ctx, "rmd_denoise_dual_guided_slope_region");
+	} else if (feat && st.denoise_feature_slope > 0.0) {
+		check(rmd_denoise_dual_guided_slope(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_radius, st.denoise_patch,
+		                                    st.denoise_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, st.denoise_feature_slope, out, err),
+		      ctx, "rmd_denoise_dual_guided_slope");
 	} else if (feat && region) {
 		check(rmd_denoise_dual_guided_region(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, region, nr, st.denoise_radius,
 		                                     st.denoise_patch, st.denoise_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
@@ -845,6 +861,11 @@ std::string check_settings(const Settings &st) {
 	if (st.adaptive_denoised_threshold > 0.0 && !st.denoise_dual) return "adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)";
 	if (st.adaptive_denoised_threshold > 0.0 && st.adaptive_threshold > 0.0) return "adaptive_denoised_threshold and adaptive_threshold are mutually exclusive";
 	if (st.denoise_dual && st.worker_count > 1) return "denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own";
+	if (!(st.denoise_feature_slope >= 0.0) || !std::isfinite(st.denoise_feature_slope)) return "denoise_feature_slope must be finite and >= 0 (0 = off)";
+	if (st.denoise_feature_slope > 0.0 && (st.denoise_atrous || st.denoise_dual_atrous))
+		return "denoise_feature_slope cannot be combined with denoise_atrous / denoise_dual_atrous: the a-trous filters have no slope term";
+	if (st.denoise_feature_slope > 0.0 && !(st.denoise_features || st.denoise_dual_features || st.denoise_dual_select))
+		return "denoise_feature_slope > 0 needs a guided non-local-means filter (denoise_features, denoise_dual_features or denoise_dual_select)";
 	return "";
 }
 } // namespace
@@ -971,6 +992,11 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 		                         settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
 		                         settings.denoise_feature_tau, dev[2]),
 		      ctx, "rmd_denoise_atrous");
+	else if (settings.denoise_features && settings.denoise_feature_slope > 0.0)
+		check(rmd_denoise_guided_slope(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+		                               settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,
+		                               settings.denoise_feature_tau, settings.denoise_feature_slope, dev[2]),
+		      ctx, "rmd_denoise_guided_slope");
 	else // (fdev both null without denoise_features: exactly rmd_denoise)
 		check(rmd_denoise_guided(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
 		                         settings.denoise_radius, settings.denoise_patch, settings.denoise_k, settings.denoise_alpha, settings.denoise_feature_k,

@@ -139,6 +139,11 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// rmd_denoise_guided, k_f = denoise_feature_k, tau = denoise_feature_tau (both finite and > 0, or render_tiled throws).
 	bool denoise_features = false;
 	double denoise_feature_k = 1.0, denoise_feature_tau = 1e-2; // (the best of the sweep in DESIGN.md section 12)
+	// The feature-slope term of the guided non-local-means filters (0 = off: no frame, message or launch changes): the pixels of a feature's local slope
+	// that are not an edge (raymond_hip.h: rmd_denoise_guided_slope; 3 is the value to start from).  When set, whichever of denoise_features,
+	// denoise_dual_features (await() and the adaptive check's region call) and denoise_dual_select's guided candidate is on makes its _slope call with it.
+	// render_tiled throws if it is not finite or negative, if it is > 0 with none of the three on, or with denoise_atrous / denoise_dual_atrous.
+	double denoise_feature_slope = 0.0;
 	// The fast filter for previews (needs denoise, not with denoise_dual; false = off): await() returns rmd_denoise_atrous's frame at
 	// denoise_atrous_levels (0..8) and k = denoise_atrous_k (finite and > 0) with denoise_alpha, guided by the first-hit features when
 	// denoise_features is on (denoise_feature_k, denoise_feature_tau).  denoise_radius, denoise_patch and denoise_k are then not used.  render_tiled

@@ -99,6 +99,27 @@ SIGNATURES = {
         [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32,
          C.c_uint32, _P(abi.DenoiseCandidate), C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp],
     ),
+    # the _slope calls: `slope` after tau; rmd_denoise_dual_select_slope: cand_slopes (a host array of n_cands doubles, or NULL) after cands
+    "rmd_denoise_guided_slope": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
+         C.c_double, C.c_double, C.c_double, _vp],
+    ),
+    "rmd_denoise_dual_guided_slope": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32,
+         C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp],
+    ),
+    "rmd_denoise_dual_guided_slope_region": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32,
+         _P(abi.TileRect), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp],
+    ),
+    "rmd_denoise_dual_select_slope": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32,
+         C.c_uint32, _P(abi.DenoiseCandidate), _P(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp],
+    ),
     "rmd_denoise_atrous_dual": (
         C.c_int32,
         [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32,

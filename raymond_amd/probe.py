@@ -41,6 +41,8 @@ _SIGS = {
     "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
     "rmd_probe_scene_plan": [_vp, _vp, _sz, _vp],
     "rmd_probe_denoise_scratch": [C.c_uint32] * 6 + [C.c_uint64, _vp, _P(C.c_uint64)],
+    "rmd_probe_feature_slope": [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp],
+    "rmd_probe_denoise_scratch_slope": [C.c_uint32] * 7 + [C.c_uint64, _vp, _P(C.c_uint64)],
 }
 PATH_STRIDE = 17
 _ready = False
@@ -306,18 +308,34 @@ def scene_plan(dscene):
     return plan
 
 
+def feature_slope(ctx, f, fvalid, slope):
+    """The device's slope floors of (H, W, 7) feature means `f` with the (H, W) feature-validity mask -> m (H, W, 7).  api: rmd_probe_feature_slope."""
+    L = _L()
+    H, W = fvalid.shape
+    planes = np.ascontiguousarray(np.moveaxis(np.asarray(f, dtype=np.float64), -1, 0)).copy()
+    planes[0][~np.asarray(fvalid, dtype=bool)] = np.nan  # the mark feature_planes_pixel leaves
+    out = np.zeros_like(planes)
+    ctx.check(L.rmd_probe_feature_slope(ctx.handle, _p(planes), W, H, float(slope), _p(out)))
+    return np.moveaxis(out, 0, -1).copy()
+
+
 # rmd_probe_denoise_scratch: the forms, and the parts in the order of denoise_host.hpp's ScratchPart
 SCRATCH_FORMS = ("single", "atrous", "dual", "atrous_dual", "atrous_dual_region", "dual_select", "tile_error")
 SCRATCH_PARTS = ("planes", "f_b", "cand_img", "gain", "feat_planes", "n_img", "win_img", "n_f_img", "table", "rects", "counts_a", "counts_b", "counts_f",
-                 "tile_errors")
+                 "tile_errors", "slope_planes")
 
 
-def denoise_scratch(form, width, height, n_rects, guided=False, n_cands=0, n_table=0):
-    """Host only: the scratch block of a denoise call -> ({part: (offset, bytes)} of the parts the form holds, total bytes).
-    api: rmd_probe_denoise_scratch."""
+def denoise_scratch(form, width, height, n_rects, guided=False, n_cands=0, n_table=0, sloped=None):
+    """Host only: the scratch block of a denoise call -> ({part: (offset, bytes)} of the parts the form holds, total bytes).  sloped (None: the call
+    has no slope argument): a _slope call, and whether a slope it reads is > 0.
+    api: rmd_probe_denoise_scratch, rmd_probe_denoise_scratch_slope."""
     L = _L()
     out = np.zeros((len(SCRATCH_PARTS), 3), dtype=np.uint64)
     total = C.c_uint64()
-    _host_check(L.rmd_probe_denoise_scratch(SCRATCH_FORMS.index(form), width, height, n_rects, int(guided), n_cands, n_table, _p(out), C.byref(total)),
-                "rmd_probe_denoise_scratch")
+    if sloped is None:
+        _host_check(L.rmd_probe_denoise_scratch(SCRATCH_FORMS.index(form), width, height, n_rects, int(guided), n_cands, n_table, _p(out), C.byref(total)),
+                    "rmd_probe_denoise_scratch")
+    else:
+        _host_check(L.rmd_probe_denoise_scratch_slope(SCRATCH_FORMS.index(form), width, height, n_rects, int(guided), int(sloped), n_cands, n_table, _p(out),
+                                                      C.byref(total)), "rmd_probe_denoise_scratch_slope")
     return {name: (int(o), int(b)) for name, (used, o, b) in zip(SCRATCH_PARTS, out) if used}, total.value

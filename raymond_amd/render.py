@@ -220,15 +220,20 @@ def denoise_arrays(ctx, sums, sums_sq, rects, counts, **params):
 
 
 def denoise_guided(ctx, framebuffer, framebuffer_sq, features, features_sq, rects, counts, out_framebuffer, radius=10, patch_radius=3, k=0.45, alpha=1.0,
-                   k_f=1.0, tau=1e-2):
-    """rmd_denoise_guided: denoise() with the feature weight of the FeatureBuffers `features` / `features_sq` (both None: exactly denoise())."""
+                   k_f=1.0, tau=1e-2, slope=None):
+    """rmd_denoise_guided: denoise() with the feature weight of the FeatureBuffers `features` / `features_sq` (both None: exactly denoise()).
+    `slope` (a number; None: the call above): rmd_denoise_guided_slope, the same with the feature-slope term at that many pixels (0: the same bytes);
+    without features it is passed and not read, as the header states."""
     counts = np.ascontiguousarray(counts, dtype=np.uint32)
     if len(counts) != len(rects):
         raise ValueError("one sample count per rect")
-    ctx.check(ctx.L.rmd_denoise_guided(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr,
-                                       None if features_sq is None else features_sq.ptr, framebuffer.width, framebuffer.height, tile_array(rects),
-                                       counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius), int(patch_radius), float(k), float(alpha),
-                                       float(k_f), float(tau), out_framebuffer.ptr))
+    head = (ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr, None if features_sq is None else features_sq.ptr,
+            framebuffer.width, framebuffer.height, tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius), int(patch_radius),
+            float(k), float(alpha), float(k_f), float(tau))
+    if slope is None:
+        ctx.check(ctx.L.rmd_denoise_guided(*head, out_framebuffer.ptr))
+    else:
+        ctx.check(ctx.L.rmd_denoise_guided_slope(*head, float(slope), out_framebuffer.ptr))
 
 
 def denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **params):
@@ -304,12 +309,14 @@ class ErrorImage(Framebuffer):
 
 
 def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0, region=None,
-                 features=None, features_sq=None, counts_f=None, k_f=1.0, tau=1e-2):
+                 features=None, features_sq=None, counts_f=None, k_f=1.0, tau=1e-2, slope=None):
     """rmd_denoise_dual: `out_framebuffer` = the cross-filtered means of the two sample halves `half_a` and `half_b`, each a (sums, sums of squares)
     pair of Framebuffers; rect i holds counts_a[i] and counts_b[i] samples per pixel in them.  `error_image` (an ErrorImage, optional) receives the
     per-pixel error estimate.  `region` (a list of rects, possibly empty): rmd_denoise_dual_region — only the pixels of those rects are written, with
     the bytes the whole-frame call gives them; None is the whole-frame call.  `features` / `features_sq` (FeatureBuffers; rect i holds counts_f[i]
-    feature samples per pixel): rmd_denoise_dual_guided[_region], the same with rmd_denoise_guided's feature weight; features=None makes the calls above."""
+    feature samples per pixel): rmd_denoise_dual_guided[_region], the same with rmd_denoise_guided's feature weight; features=None makes the calls above.
+    `slope` (a number; None: the calls above): rmd_denoise_dual_guided_slope[_region], the same with the feature-slope term.  Without features the slope
+    is not read, as in the C calls and in denoise_guided: the unguided calls above are made."""
     counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
     counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
     if len(counts_a) != len(rects) or len(counts_b) != len(rects):
@@ -324,12 +331,14 @@ def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer
             raise ValueError("one feature sample count per rect")
         head = head[:5] + (None if features is None else features.ptr, None if features_sq is None else features_sq.ptr) + head[5:10] + (
             counts_f.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects))
-        tail = tail[:4] + (float(k_f), float(tau)) + tail[4:]
+        tail = tail[:4] + (float(k_f), float(tau)) + (() if slope is None else (float(slope),)) + tail[4:]
+        whole, regional = ((ctx.L.rmd_denoise_dual_guided, ctx.L.rmd_denoise_dual_guided_region) if slope is None else
+                           (ctx.L.rmd_denoise_dual_guided_slope, ctx.L.rmd_denoise_dual_guided_slope_region))
         if region is None:
-            ctx.check(ctx.L.rmd_denoise_dual_guided(*head, *tail))
+            ctx.check(whole(*head, *tail))
         else:
             region = list(region)
-            ctx.check(ctx.L.rmd_denoise_dual_guided_region(*head, tile_array(region), len(region), *tail))
+            ctx.check(regional(*head, tile_array(region), len(region), *tail))
     elif region is None:
         ctx.check(ctx.L.rmd_denoise_dual(*head, *tail))
     else:
@@ -454,7 +463,8 @@ def denoise_dual_select(ctx, half_a, half_b, rects, counts_a, counts_b, candidat
                         radius=10, patch_radius=3, sure_window=2, select_window=2, features=None, features_sq=None, counts_f=None):
     """rmd_denoise_dual_select: per pixel, the best of `candidates` (dicts, see candidate_array: parameter sets of denoise_dual, `guided` ones with the
     feature weight) by Stein's unbiased risk estimate, blended over the winners around the pixel.  `error_image` and `sure_image` (ErrorImages) and
-    `winner_image` (a WinnerImage) are optional; `features`, `features_sq` and `counts_f` are needed by a guided candidate."""
+    `winner_image` (a WinnerImage) are optional; `features`, `features_sq` and `counts_f` are needed by a guided candidate.  A candidate with a `slope`
+    key makes the call rmd_denoise_dual_select_slope, with that candidate's slope (0.0 for one without the key)."""
     counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
     counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
     if len(counts_a) != len(rects) or len(counts_b) != len(rects):
@@ -468,11 +478,15 @@ def denoise_dual_select(ctx, half_a, half_b, rects, counts_a, counts_b, candidat
     candidates = list(candidates)
     fb = half_a[0]
     opt = lambda o: None if o is None else o.ptr  # noqa: E731
-    ctx.check(ctx.L.rmd_denoise_dual_select(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, opt(features), opt(features_sq), fb.width,
-                                            fb.height, tile_array(rects), counts_a.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                            counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), cf, len(rects), int(radius), int(patch_radius),
-                                            candidate_array(candidates), len(candidates), int(sure_window), int(select_window), out_framebuffer.ptr,
-                                            opt(error_image), opt(sure_image), opt(winner_image)))
+    head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, opt(features), opt(features_sq), fb.width, fb.height, tile_array(rects),
+            counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), cf, len(rects), int(radius), int(patch_radius),
+            candidate_array(candidates))
+    tail = (len(candidates), int(sure_window), int(select_window), out_framebuffer.ptr, opt(error_image), opt(sure_image), opt(winner_image))
+    if any("slope" in c for c in candidates):
+        slopes = (C.c_double * len(candidates))(*[float(c.get("slope", 0.0)) for c in candidates])
+        ctx.check(ctx.L.rmd_denoise_dual_select_slope(*head, slopes, *tail))
+    else:
+        ctx.check(ctx.L.rmd_denoise_dual_select(*head, *tail))
 
 
 def denoise_dual_select_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, candidates, features=None, features_sq=None,
@@ -678,7 +692,7 @@ class TaskHandle:  # src/trace.rs:70-135
                 elif st.denoise_features:
                     feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts)
                     out = denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
-                                                **params)
+                                                **st.slope_keyword(), **params)
                 else:
                     out = denoise_arrays(ctx, sums, sums_sq, rects, counts, **params)
         return out
@@ -728,7 +742,7 @@ class TaskHandle:  # src/trace.rs:70-135
                 counts_f = [a + b for a, b in zip(counts_a, counts_b)]
                 feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
                 out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, features=feats, features_sq=feats_sq, counts_f=counts_f,
-                                             k_f=st.denoise_feature_k, tau=st.denoise_feature_tau, **params)
+                                             k_f=st.denoise_feature_k, tau=st.denoise_feature_tau, **st.slope_keyword(), **params)
             else:
                 out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, **params)
         return out
@@ -963,7 +977,8 @@ def _render_tiled_dual(scene, settings, devices):
                         denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img,
                                             levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **where)
                     else:
-                        denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide)
+                        slope = st.slope_keyword() if guided else {}  # (set: the check is rmd_denoise_dual_guided_slope_region)
+                        denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide, **slope)
                     errors = tile_error_dual(ctx, err_img, live)
                 conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
                 finish([r for r, c in zip(live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have

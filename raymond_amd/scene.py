@@ -248,7 +248,7 @@ class Settings:
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
                  adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False, denoise_atrous=False,
                  denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False, preview_every=0,
-                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True):
+                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, denoise_feature_slope=0.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -282,6 +282,11 @@ class Settings:
         self.denoise_features = bool(denoise_features)
         self.denoise_feature_k = float(denoise_feature_k)
         self.denoise_feature_tau = float(denoise_feature_tau)
+        # The feature-slope term of the guided non-local-means filters (0.0 = off: no frame, message or launch changes): the number of pixels of a
+        # feature's local slope that is not an edge (raymond_hip.h: rmd_denoise_guided_slope; DESIGN.md section 21 — 3 is the value to start from).  When
+        # set, whichever of denoise_features, denoise_dual_features (await_() and the adaptive check's region call) and denoise_dual_select's guided
+        # candidate is on makes its _slope call with it.  Needs one of them, excludes the a-trous filters.
+        self.denoise_feature_slope = float(denoise_feature_slope)
         # Dual-buffer denoising (an extension of the extension; False = off): a tile's passes go alternately into two half buffers A (even passes,
         # counted from 0) and B (odd ones), and await_() returns rmd_denoise_dual's frame: each half filtered with the other's weights.  Needs
         # denoise and samples_per_iteration > 0; one device only.
@@ -332,7 +337,11 @@ class Settings:
         """The candidates of denoise_dual_select, as render.denoise_dual_select takes them: the unguided filter at denoise_k, and the guided one at k = 1.0
         with denoise_feature_k and denoise_feature_tau."""
         return [dict(k=self.denoise_k, alpha=self.denoise_alpha), dict(k=1.0, alpha=self.denoise_alpha, guided=True, k_f=self.denoise_feature_k,
-                                                                      tau=self.denoise_feature_tau)]
+                                                                      tau=self.denoise_feature_tau, **self.slope_keyword())]
+
+    def slope_keyword(self):
+        """{} while denoise_feature_slope is off — the calls made are then those made before it existed —, else dict(slope=denoise_feature_slope)."""
+        return dict(slope=self.denoise_feature_slope) if self.denoise_feature_slope > 0.0 else {}
 
     def check_adaptive(self):
         """Raises ValueError for adaptive settings render_tiled cannot follow."""
@@ -357,6 +366,12 @@ class Settings:
             raise ValueError("denoise_feature_k must be finite and > 0")
         if not (self.denoise_feature_tau > 0.0 and np.isfinite(self.denoise_feature_tau)):
             raise ValueError("denoise_feature_tau must be finite and > 0")
+        if not (self.denoise_feature_slope >= 0.0 and np.isfinite(self.denoise_feature_slope)):
+            raise ValueError("denoise_feature_slope must be finite and >= 0 (0 = off)")
+        if self.denoise_feature_slope > 0.0 and (self.denoise_atrous or self.denoise_dual_atrous):
+            raise ValueError("denoise_feature_slope cannot be combined with denoise_atrous / denoise_dual_atrous: the a-trous filters have no slope term")
+        if self.denoise_feature_slope > 0.0 and not (self.denoise_features or self.denoise_dual_features or self.denoise_dual_select):
+            raise ValueError("denoise_feature_slope > 0 needs a guided non-local-means filter (denoise_features, denoise_dual_features or denoise_dual_select)")
         v = self.denoise_atrous_levels
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= abi.RMD_ATROUS_MAX_LEVELS:
             raise ValueError("denoise_atrous_levels must be an integer in [0, %d]" % abi.RMD_ATROUS_MAX_LEVELS)

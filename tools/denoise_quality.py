@@ -3,6 +3,7 @@
 
     python tools/denoise_quality.py [--out profiles/r08_denoise/denoise_quality.json] [--ref-spp 2048]
     python tools/denoise_quality.py --guided [--out profiles/r09_features/denoise_quality.json]
+    python tools/denoise_quality.py --slope [--out profiles/r20_slope/slope_quality.json]
 
 For ReflectiveSpheres and the small GoldDragon stand-in (n = 24) at 256x144: frames of 16, 64 and 256 spp with moments are denoised, and the
 RMSE of the noisy and of the denoised frame against a --ref-spp frame of another seed is reported with its ratio, first at the default
@@ -12,6 +13,10 @@ parameters (r 10, f 3, k 0.45, alpha 1), then over a small sweep of k, alpha, r 
 --guided: rmd_denoise_guided against rmd_denoise on the same sums instead.  At 16 and 64 spp, k_f in {0.3, 0.6, 1.0} x tau in {1e-4, 1e-3, 1e-2}
 x k in {0.45, 0.6}: whole-frame RMSE, and RMSE over the pixels within 2 px of a change of first-hit object (found from the converged albedo and
 depth means), guided and unguided at the SAME k; and the converged-frame check of the guided filter for every (k_f, tau) at k = 0.45.
+
+--slope: rmd_denoise_guided_slope.  At 16 and 64 spp, slope in {0, 1, 2, 3, 5, 8} x k in {0.45, 0.6} x (k_f, tau) in {(1.0, 1e-2), (0.6, 1e-3)}: whole-frame
+and edge-pixel RMSE, beside the unguided filter's at the same k; and the converged-frame check at the values the header recommends (k 0.45, k_f 1.0,
+tau 1e-2) for every slope.
 """
 import argparse
 import json
@@ -116,14 +121,62 @@ def guided_main(a):
             json.dump(out, f, indent=1)
 
 
+SLOPES = (0.0, 1.0, 2.0, 3.0, 5.0, 8.0)
+SLOPE_GUIDES = ((1.0, 1e-2), (0.6, 1e-3))
+
+
+def slope_main(a):
+    W, H = 256, 144
+    out = {"width": W, "height": H, "ref_spp": a.ref_spp, "unguided_default": DEFAULT, "slopes": SLOPES, "scenes": {}}
+    rect = [(0, 0, W, H)]
+    with render.Context(0) as ctx:
+        for name, scene in (("reflective_spheres", scenes.reflective_spheres()), ("gold_dragon_standin_n24", scenes.gold_dragon_standin(n=24))):
+            ds = render.DeviceScene(ctx, scene)
+            try:
+                S_ref, Q_ref = moments(ctx, ds, W, H, a.ref_spp, seed=0x1234567)
+                S_ref2, _ = moments(ctx, ds, W, H, a.ref_spp, seed=0x7654321)
+                F_ref, G_ref = feature_sums(ctx, ds, W, H, a.ref_spp, 0x1234567)
+                ref, ref2 = S_ref / a.ref_spp, S_ref2 / a.ref_spp
+                edge = edge_mask(F_ref / a.ref_spp)
+                rec = {"edge_pixel_fraction": float(edge.mean()), "sweep": [], "converged": []}
+                own = rmse(ref, ref2)
+                for slope in SLOPES:  # at the recommended k, k_f and tau
+                    den = render.denoise_guided_arrays(ctx, S_ref, Q_ref, F_ref, G_ref, rect, [a.ref_spp], k_f=1.0, tau=1e-2, slope=slope, **DEFAULT)
+                    rec["converged"].append({"slope": slope, "ratio": rmse(den, ref2) / own})
+                for spp in (16, 64):
+                    S, Q = moments(ctx, ds, W, H, spp, seed=scenes.SEED)
+                    F, G = feature_sums(ctx, ds, W, H, spp, scenes.SEED)
+                    for k in (0.45, 0.6):
+                        p = dict(DEFAULT, k=k)
+                        un = render.denoise_arrays(ctx, S, Q, rect, [spp], **p)
+                        for kf, tau in SLOPE_GUIDES:
+                            row = {"spp": spp, "k": k, "k_f": kf, "tau": tau, "unguided": {"rmse": rmse(un, ref), "rmse_edge": rmse(un[edge], ref[edge])}, "slopes": []}
+                            for slope in SLOPES:
+                                gd = render.denoise_guided_arrays(ctx, S, Q, F, G, rect, [spp], k_f=kf, tau=tau, slope=slope, **p)
+                                row["slopes"].append({"slope": slope, "rmse": rmse(gd, ref), "rmse_edge": rmse(gd[edge], ref[edge])})
+                            rec["sweep"].append(row)
+                            print(name, json.dumps(row), flush=True)
+                out["scenes"][name] = rec
+                print(name, json.dumps(rec["converged"]), flush=True)
+            finally:
+                ds.close()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--ref-spp", type=int, default=2048)
     ap.add_argument("--guided", action="store_true")
+    ap.add_argument("--slope", action="store_true")
     a = ap.parse_args()
     if a.guided:
         return guided_main(a)
+    if a.slope:
+        return slope_main(a)
     W, H = 256, 144
     out = {"width": W, "height": H, "ref_spp": a.ref_spp, "default": DEFAULT, "scenes": {}}
     with render.Context(0) as ctx:
