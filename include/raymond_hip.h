@@ -67,6 +67,8 @@ enum {
 	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
 	                                 rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope,
 	                                 rmd_denoise_dual_guided_slope_region, rmd_denoise_dual_select_slope,
+	                                 rmd_denoise_atrous_slope, rmd_denoise_atrous_dual_slope,
+	                                 rmd_denoise_atrous_dual_slope_region,
 	                                 rmd_denoise_dual_guided_region, rmd_denoise_dual_select, rmd_denoise_atrous) */
 };
 
@@ -658,7 +660,7 @@ rmd_status rmd_denoise_dual_select(rmd_context *ctx,
  * feat_dev = feat_sq_dev = NULL behaves as in the call without the suffix, and `slope` is then not read.  With features, a slope (of a guided
  * candidate: cand_slopes[i]) that is not finite or is negative is RMD_ERR_INVALID_ARGUMENT before the device is touched, after the checks of k_f
  * and tau; every other rule, and its order, is that of the call without the suffix.  Synchronous, and they report an earlier device fault, like those.
- * The a-trous filters have no slope form.  Values a caller may start from: slope 3 at k_f 1.0, tau 1e-2.
+ * The a-trous filters have their own _slope forms, right below.  Values a caller may start from: slope 3 at k_f 1.0, tau 1e-2.
  */
 rmd_status rmd_denoise_guided_slope(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
                                     uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
@@ -692,6 +694,58 @@ rmd_status rmd_denoise_dual_select_slope(rmd_context *ctx,
     uint32_t radius, uint32_t patch_radius,
     const rmd_denoise_candidate *cands, const double *cand_slopes, uint32_t n_cands, uint32_t sure_window, uint32_t select_window,
     double *out_dev, double *err_dev, double *sure_dev, uint32_t *win_dev);
+/*
+ * The guided A-TROUS filters with the same FEATURE-SLOPE TERM (additions within ABI 6: RMD_ABI_VERSION stays 6, no struct changes, found by their
+ * symbols).  rmd_denoise_atrous, rmd_denoise_atrous_dual and rmd_denoise_atrous_dual_region (their definitions stand with their declarations) use
+ * rmd_denoise_guided's Phi_j word for word, and a level-l tap lies up to 2 * 2^l pixels away: on a curved mirror every level but the first loses all
+ * its taps to the normal term.  Each _slope call is the call without the suffix with `double slope` after tau; everything of
+ * that call stays word for word.  Added, for a FEATURE-VALID pixel p and channel j, with f the call's own feature means:
+ *     m_pj = (slope * slope) * (h_j + v_j)    exactly the m_pj above: per axis the two-sided minimum of the squared differences to the two neighbours at
+ *                                             ONE pixel's distance, whatever the level; a neighbour is present if it is inside the frame and feature-valid
+ *     t    = max(tau * s_pj, g_pj)            exactly the comparison of the call without the suffix (a > g ? a : g)
+ *     if m_pj > t then t = m_pj               (a NaN m is skipped by the comparison)
+ *     the denominator of Phi_j(p, .) = eps + k_f^2 * t
+ * FEATURE-VALID is each call's own: rmd_denoise_atrous's for rmd_denoise_atrous_slope; the dual calls' (dual-valid, n_F >= 2, fourteen finite values)
+ * for the other two.  The SAME m serves EVERY LEVEL and, in the dual calls, BOTH HALVES: the features do not change from level to level, so m is made
+ * once.  It is deliberately NOT scaled by the level's step 2^l: `slope` is a distance in pixels, and a term that grew with the step would forgive every
+ * curved surface at every level and undo the feature weight.  On a curved surface the unscaled term leaves the first one or two levels open and closes
+ * the later ones; a larger slope opens more levels.  So, all bit for bit:
+ *     slope = 0 gives the bytes of the call without the suffix, launches nothing more and takes no more scratch;
+ *     feat_dev = feat_sq_dev = NULL behaves as in the call without the suffix, and `slope` is then not read (a NaN is accepted);
+ *     features that are constant on one side of every pixel, on each axis, give the slope-0 bytes at any slope;
+ *     features that are zero everywhere, at counts >= 2, give the bytes of the call without features;
+ *     levels = 0 is the closed form of the call without the suffix (no feature and no slope is read);
+ *     equal halves with rect_counts_f equal to their counts give rmd_denoise_atrous_slope's bytes and err = 0;
+ *     rmd_denoise_atrous_dual_slope_region writes, for every pixel of the region, the bytes rmd_denoise_atrous_dual_slope writes there, and nothing else;
+ *     calls over disjoint regions compose, and a pixel's value does not depend on how the rects cut the frame.
+ * The region form makes m on the pixels its levels are computed on only (level 0's needed set), from the f it has made one pixel further out; a
+ * neighbour's presence is still "inside the FRAME and feature-valid".  Its scratch stays on the context.
+ * With features, a slope that is not finite or is negative is RMD_ERR_INVALID_ARGUMENT ("NAME: slope must be finite and >= 0") before the device is
+ * touched, after the checks of k_f and tau; every other rule, its order and its text are those of the call without the suffix, with the name alone
+ * differing.  Synchronous, and they report an earlier device fault, like those.  A value a caller may start from: slope 3 at k_f 1.0, tau 1e-2.
+ */
+rmd_status rmd_denoise_atrous_slope(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                                    uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                                    uint32_t levels, double k, double alpha, double k_f, double tau, double slope, double *out_dev);
+rmd_status rmd_denoise_atrous_dual_slope(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    uint32_t levels, double k, double alpha, double k_f, double tau, double slope,
+    double *out_dev, double *err_dev);
+rmd_status rmd_denoise_atrous_dual_slope_region(rmd_context *ctx,
+    const double *accum_a_dev, const double *accum_sq_a_dev,
+    const double *accum_b_dev, const double *accum_sq_b_dev,
+    const double *feat_dev, const double *feat_sq_dev,
+    uint32_t width, uint32_t height,
+    const rmd_tile_rect *rects, const uint32_t *rect_counts_a,
+    const uint32_t *rect_counts_b, const uint32_t *rect_counts_f, uint32_t n_rects,
+    const rmd_tile_rect *region, uint32_t n_region,
+    uint32_t levels, double k, double alpha, double k_f, double tau, double slope,
+    double *out_dev, double *err_dev);
 /*
  * rmd_denoise_atrous on TWO SAMPLE HALVES, each filtered with the weights of the other, with rmd_denoise_dual's error estimate: the fast filter in
  * a form that can drive adaptive sampling (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes, found by its symbol).

@@ -130,13 +130,19 @@ rmd_status rmd_probe_scene_plan(const rmd_scene *scene, uint64_t *out8, size_t n
 rmd_status rmd_probe_denoise_scratch(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t n_cands, uint64_t n_table,
                                      uint64_t *out3, uint64_t *total);
 /* ... of a _slope call (rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope[_region], rmd_denoise_dual_select_slope): sloped = 1 when a slope the call
- * reads is > 0 — the forms 0, 2 and 5 with features then hold the seven slope planes, behind the feature planes; sloped = 0 is rmd_probe_denoise_scratch. */
+ * reads is > 0 — the forms 0, 2 and 5 with features then hold the seven slope planes, behind the feature planes; sloped = 0 is rmd_probe_denoise_scratch.
+ * sloped = 2: an a-trous _slope call (rmd_denoise_atrous_slope, rmd_denoise_atrous_dual_slope[_region]) whose slope is > 0 — the forms 1, 3 and 4 with
+ * features then hold the seven slope planes behind every other part, each of which keeps its offset.  (A value of its own: 1 leaves the a-trous forms alone.) */
 rmd_status rmd_probe_denoise_scratch_slope(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t sloped, uint32_t n_cands,
                                            uint64_t n_table, uint64_t *out3, uint64_t *total);
 /* The slope floors of the _slope denoise calls as the device makes them (raymond_amd/csrc/denoise.hip: feature_slope_kernel, through the launcher the entry
  * points call): fplanes7 = the seven planar per-pixel feature means f (W*H doubles each, HOST memory; a NaN in plane 0 marks a pixel that is not
  * feature-valid), mplanes7 = the seven planes m_j = (slope * slope) * (h_j + v_j) of include/raymond_hip.h, zeros at a pixel that is not feature-valid. */
 rmd_status rmd_probe_feature_slope(rmd_context *ctx, const double *fplanes7, uint32_t width, uint32_t height, double slope, double *mplanes7);
+/* The seven slope planes that this context's last rmd_denoise_atrous_dual_slope_region call with features, levels > 0 and slope > 0 left in the scratch it keeps
+ * on the context, copied to mplanes7 (7 * W*H doubles, HOST memory; width and height must be that call's).  Only level 0's needed set is defined: the region's
+ * rects grown by 2 * (2^levels - 2) pixels, clipped to the frame.  RMD_ERR_INVALID_ARGUMENT when no such call was made. */
+rmd_status rmd_probe_atrous_region_slope_planes(rmd_context *ctx, uint32_t width, uint32_t height, double *mplanes7);
 rmd_status rmd_probe_pretest_pairs(rmd_context *ctx, size_t n, const double *sphere5, const double *pos9, const double *ray6, int32_t *pass,
                                    int32_t *hit, double *t);
 

@@ -139,6 +139,20 @@ extern "C" {
                                       rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32,
                                       region: *const rmd_tile_rect, n_region: u32, levels: u32, k: f64, alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64,
                                       err_dev: *mut f64) -> i32;
+    // the guided a-trous filters with the feature-slope term: the calls without the suffix with `slope` (finite, >= 0; 0 = that call, bit for bit) after tau —
+    // the same floor at every level and for both halves, not scaled by the level's step; 3 is the value to start from
+    fn rmd_denoise_atrous_slope(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
+                                width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, levels: u32,
+                                k: f64, alpha: f64, k_f: f64, tau: f64, slope: f64, out_dev: *mut f64) -> i32;
+    fn rmd_denoise_atrous_dual_slope(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64,
+                                     accum_sq_b_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32,
+                                     rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32, n_rects: u32,
+                                     levels: u32, k: f64, alpha: f64, k_f: f64, tau: f64, slope: f64, out_dev: *mut f64, err_dev: *mut f64) -> i32;
+    fn rmd_denoise_atrous_dual_slope_region(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64,
+                                            accum_sq_b_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64, width: u32, height: u32,
+                                            rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, rect_counts_f: *const u32,
+                                            n_rects: u32, region: *const rmd_tile_rect, n_region: u32, levels: u32, k: f64, alpha: f64, k_f: f64, tau: f64,
+                                            slope: f64, out_dev: *mut f64, err_dev: *mut f64) -> i32;
     fn rmd_tile_error_dual(ctx: *mut rmd_context, err_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect, n_rects: u32,
                            out_err_host: *mut f64) -> i32;
     // the output stage over tile rects, rect i at rect_sample_counts[i], into packed bytes in rmd_framebuffer_download_tiles's layout (accum2_dev: null, or

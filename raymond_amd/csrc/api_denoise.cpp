@@ -144,7 +144,7 @@ rmd_status finish(rmd_context *ctx) {
 }
 
 // ---------------------------------------------------------------- the single-buffer filters (denoise.hip, denoise_atrous.hip)
-// rmd_denoise and rmd_denoise_guided[_slope] (levels null), rmd_denoise_atrous (levels given; radius and patch_radius unused).  `what`: the entry point's name
+// rmd_denoise and rmd_denoise_guided[_slope] (levels null), rmd_denoise_atrous[_slope] (levels given; radius and patch_radius unused).  `what`: the entry point's name
 rmd_status denoise_single(const char *what, rmd_context *ctx, DenoiseInput in, const uint32_t *levels, uint32_t radius, uint32_t patch_radius, const DenoiseWeights &w,
                           double *out_dev) {
 	const std::string name = std::string(what) + ": ";
@@ -161,23 +161,23 @@ rmd_status denoise_single(const char *what, rmd_context *ctx, DenoiseInput in, c
 		if (rmd_status s = check_feature_weights(ctx, name, w.k_f, w.tau)) return s;
 		if (rmd_status s = check_slope(ctx, name, w.slope)) return s;
 	}
-	const bool sloped = guided && !levels && w.slope > 0.0;
+	const bool sloped = guided && w.slope > 0.0;
 	return rmd::guarded(ctx, what, [&] {
 		if (rmd_status s = check_rects(ctx, name, in.rects, in.n_rects, in.W, in.H)) return s;
 		if (rmd_status s = rmd::bind(ctx)) return s;
 		Scratch sc;
-		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(levels ? rmd::kScratchAtrous : rmd::kScratchSingle, in.W, in.H, in.n_rects, guided, 0u, 0u, sloped))) return s;
+		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(levels ? rmd::kScratchAtrous : rmd::kScratchSingle, in.W, in.H, in.n_rects, guided, 0u, 0u, sloped && !levels, sloped && levels))) return s;
 		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
 		uint32_t *n_img = sc.part<uint32_t>(rmd::kPartCountImg);
 		double *feat_planes = sc.part<double>(rmd::kPartFeatPlanes);
-		if (levels) RMD_HIP(ctx, rmd::launch_denoise_atrous(ctx->stream, in, w, *levels, n_img, sc.part<double>(rmd::kPartPlanes), feat_planes, out_dev));
+		if (levels) RMD_HIP(ctx, rmd::launch_denoise_atrous(ctx->stream, in, w, *levels, n_img, sc.part<double>(rmd::kPartPlanes), feat_planes, sc.part<double>(rmd::kPartSlopePlanes), out_dev));
 		else RMD_HIP(ctx, rmd::launch_denoise_guided(ctx->stream, in, w, radius, patch_radius, n_img, feat_planes, sc.part<double>(rmd::kPartSlopePlanes), out_dev));
 		return finish(ctx);
 	});
 }
 
 // ---------------------------------------------------------------- the dual-buffer filters (denoise_dual.hip, denoise_atrous_dual.hip)
-// rmd_denoise_dual and its guided and region forms (levels null), rmd_denoise_atrous_dual and its region form (levels given; radius and patch_radius
+// rmd_denoise_dual and its guided and region forms (levels null), rmd_denoise_atrous_dual[_slope] and their region forms (levels given; radius and patch_radius
 // unused).  `regional`: a region form, which writes the pixels of its n_region rects only; its region may still be NULL when n_region is 0.  Without
 // features rect_counts_f, k_f, tau and the slope (the _slope calls: w.slope, 0 in every other) are not read
 rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, DenoiseInput in, const rmd_tile_rect *region, uint32_t n_region, const uint32_t *levels,
@@ -200,7 +200,7 @@ rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, Denoi
 		if (rmd_status s = check_feature_weights(ctx, name, w.k_f, w.tau)) return s;
 		if (rmd_status s = check_slope(ctx, name, w.slope)) return s;
 	}
-	const bool sloped = guided && !levels && w.slope > 0.0;
+	const bool sloped = guided && w.slope > 0.0;
 	return rmd::guarded(ctx, what, [&] {
 		if (rmd_status s = check_rects(ctx, name, in.rects, in.n_rects, in.W, in.H)) return s;
 		if (regional)
@@ -221,21 +221,22 @@ rmd_status denoise_dual(const char *what, bool regional, rmd_context *ctx, Denoi
 		const std::vector<rmd::DualBlock> &blocks = levels ? tables.table : table;
 		const rmd::ScratchForm form = !levels ? rmd::kScratchDual : regional ? rmd::kScratchAtrousDualRegion : rmd::kScratchAtrousDual;
 		Scratch sc; // (only the a-trous region form keeps its block between calls)
-		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(form, in.W, in.H, in.n_rects, guided, 0u, blocks.size(), sloped),
+		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(form, in.W, in.H, in.n_rects, guided, 0u, blocks.size(), sloped && !levels, sloped && levels),
 		                            form == rmd::kScratchAtrousDualRegion ? &ctx->atrous_region_scratch : nullptr))
 			return s;
 		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
 		rmd::DualBlock *d_table = sc.part<rmd::DualBlock>(rmd::kPartTable);
 		if (d_table) RMD_HIP(ctx, hipMemcpyAsync(d_table, blocks.data(), blocks.size() * sizeof(rmd::DualBlock), hipMemcpyHostToDevice, ctx->stream));
 		uint32_t *n_img = sc.part<uint32_t>(rmd::kPartCountImg), *n_f_img = sc.part<uint32_t>(rmd::kPartFeatCountImg);
-		double *planes = sc.part<double>(rmd::kPartPlanes), *feat_planes = sc.part<double>(rmd::kPartFeatPlanes);
+		double *planes = sc.part<double>(rmd::kPartPlanes), *feat_planes = sc.part<double>(rmd::kPartFeatPlanes), *slope_planes = sc.part<double>(rmd::kPartSlopePlanes);
 		if (!levels)
-			RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, in, w, radius, patch_radius, n_img, planes, sc.part<double>(rmd::kPartFb), n_f_img, feat_planes,
-			                                      sc.part<double>(rmd::kPartSlopePlanes), d_table, (uint32_t)table.size(), out_dev, err_dev));
-		else if (regional)
-			RMD_HIP(ctx, rmd::launch_denoise_atrous_dual_region(ctx->stream, in, w, *levels, n_img, planes, n_f_img, feat_planes, d_table, tables.first.data(),
+			RMD_HIP(ctx, rmd::launch_denoise_dual(ctx->stream, in, w, radius, patch_radius, n_img, planes, sc.part<double>(rmd::kPartFb), n_f_img, feat_planes, slope_planes,
+			                                      d_table, (uint32_t)table.size(), out_dev, err_dev));
+		else if (regional) {
+			if (slope_planes && *levels != 0u) ctx->atrous_region_slope_offset = sc.layout.offset[rmd::kPartSlopePlanes], ctx->atrous_region_slope_pixels = (size_t)in.W * in.H;
+			RMD_HIP(ctx, rmd::launch_denoise_atrous_dual_region(ctx->stream, in, w, *levels, n_img, planes, n_f_img, feat_planes, slope_planes, d_table, tables.first.data(),
 			                                                    tables.count.data(), out_dev, err_dev));
-		else RMD_HIP(ctx, rmd::launch_denoise_atrous_dual(ctx->stream, in, w, *levels, n_img, planes, n_f_img, feat_planes, out_dev, err_dev));
+		} else RMD_HIP(ctx, rmd::launch_denoise_atrous_dual(ctx->stream, in, w, *levels, n_img, planes, n_f_img, feat_planes, slope_planes, out_dev, err_dev));
 		return finish(ctx);
 	});
 }
@@ -418,6 +419,33 @@ rmd_status rmd_denoise_dual_guided_slope_region(rmd_context *ctx, const double *
 	const DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
 	                                   rect_counts_f, n_rects);
 	return denoise_dual("rmd_denoise_dual_guided_slope_region", true, ctx, in, region, n_region, nullptr, radius, patch_radius, {k, alpha, k_f, tau, slope}, out_dev, err_dev);
+}
+
+rmd_status rmd_denoise_atrous_slope(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, const double *feat_dev, const double *feat_sq_dev,
+                                    uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                                    uint32_t levels, double k, double alpha, double k_f, double tau, double slope, double *out_dev) {
+	const DenoiseInput in = single_input(accum_dev, accum_sq_dev, feat_dev, feat_sq_dev, width, height, rects, rect_sample_counts, n_rects);
+	return denoise_single("rmd_denoise_atrous_slope", ctx, in, &levels, 0u, 0u, {k, alpha, k_f, tau, slope}, out_dev);
+}
+
+rmd_status rmd_denoise_atrous_dual_slope(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                         const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                         const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, const uint32_t *rect_counts_f,
+                                         uint32_t n_rects, uint32_t levels, double k, double alpha, double k_f, double tau, double slope, double *out_dev,
+                                         double *err_dev) {
+	const DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
+	                                   rect_counts_f, n_rects);
+	return denoise_dual("rmd_denoise_atrous_dual_slope", false, ctx, in, nullptr, 0u, &levels, 0u, 0u, {k, alpha, k_f, tau, slope}, out_dev, err_dev);
+}
+
+rmd_status rmd_denoise_atrous_dual_slope_region(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev,
+                                                const double *accum_sq_b_dev, const double *feat_dev, const double *feat_sq_dev, uint32_t width, uint32_t height,
+                                                const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
+                                                const uint32_t *rect_counts_f, uint32_t n_rects, const rmd_tile_rect *region, uint32_t n_region, uint32_t levels,
+                                                double k, double alpha, double k_f, double tau, double slope, double *out_dev, double *err_dev) {
+	const DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
+	                                   rect_counts_f, n_rects);
+	return denoise_dual("rmd_denoise_atrous_dual_slope_region", true, ctx, in, region, n_region, &levels, 0u, 0u, {k, alpha, k_f, tau, slope}, out_dev, err_dev);
 }
 
 rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,

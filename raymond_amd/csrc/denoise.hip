@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void feature_planes_kernel(const double *__res
 	feature_planes_pixel(F, G, i, n, moments_pixel(S, Q, i, n, u, v), N, planes);
 }
 
-// The slope floors of rmd_denoise_guided_slope and of the dual _slope calls (denoise_dual.hip's launchers call launch_feature_slope too): feature_slope_pixel's
+// The slope floors of rmd_denoise_guided_slope and of the dual _slope calls (denoise_dual.hip's launchers and the whole-frame a-trous ones call launch_feature_slope too): feature_slope_pixel's
 // seven planes m from the seven planar f that feature_planes_kernel / dual_feature_planes_kernel have written.  Whole-frame in every form.  Consecutive
 // lanes hold consecutive pixels of a row, so each of the five reads per channel is coalesced
 __global__ __launch_bounds__(256) void feature_slope_kernel(const double *__restrict__ fplanes, uint32_t W, uint32_t H, double s2, double *__restrict__ mplanes) {

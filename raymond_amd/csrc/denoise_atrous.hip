@@ -11,6 +11,10 @@
 //                                 LAST = false writes c^{l+1}, v^{l+1} into the other set of six planes; LAST = true writes the interleaved
 //                                 out_dev, and S / n for a pixel that is not valid.
 // atrous_mean_kernel            — levels = 0: out = S / n for every pixel.
+// SLOPE (rmd_denoise_atrous_slope at slope > 0): atrous_level_kernel<true, LAST, const double *> takes one more trailing argument, the
+//                                 seven planes m that denoise.hip's feature_slope_kernel makes of the f planes (launch_feature_slope), and reads p's
+//                                 seven m once, where the denominators are made: the same m at every level.  The instantiations without it keep their
+//                                 arguments and their instructions.
 // The count image and the 14 feature planes are denoise.hip's, the per-pixel arithmetic denoise_device.hpp's.  f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -39,12 +43,15 @@ __global__ __launch_bounds__(256) void atrous_mean_kernel(const double *__restri
 
 // in / next: six planes of N = W*H doubles, c of channel 0..2 then v of channel 0..2.  planes (GUIDED): feature_planes_kernel's 14 planes.
 // tiles_x: workgroups per row of tiles (the grid is one-dimensional: a frame may be taller than 65,535 tiles)
-template <bool GUIDED, bool LAST>
+// m (GUIDED only, at most one): feature_slope_kernel's seven planes, the floors under the denominators
+__device__ inline const double *atrous_slope_planes(const double *m) { return m; }
+template <bool GUIDED, bool LAST, class... M>
 __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_kernel(const double *__restrict__ in, double *__restrict__ next,
                                                                                     const double *__restrict__ S, const uint32_t *__restrict__ n_img, uint32_t W,
                                                                                     uint32_t H, uint32_t tiles_x, int64_t step, double k2, double alpha,
                                                                                     const double *__restrict__ planes, double kf2, double tau,
-                                                                                    double *__restrict__ out) {
+                                                                                    double *__restrict__ out, M... m) {
+	static_assert(sizeof...(M) <= (GUIDED ? 1 : 0), "the slope planes, with GUIDED only");
 	const uint32_t bx = blockIdx.x % tiles_x, by = blockIdx.x / tiles_x;
 	const int64_t x = (int64_t)bx * kAtrousBlockW + (threadIdx.x % kAtrousBlockW), y = (int64_t)by * kAtrousBlockH + (threadIdx.x / kAtrousBlockW);
 	if (x >= (int64_t)W || y >= (int64_t)H) return;
@@ -65,9 +72,14 @@ __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_ker
 	[[maybe_unused]] bool p_fok = false;
 	if constexpr (GUIDED) {
 #pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) { // the slope form: the seven floors first, into den's registers (atrous_dual_level_kernel's order)
+			if constexpr (sizeof...(M) != 0) den[j] = atrous_slope_planes(m...)[(size_t)j * N + pix];
+		}
+#pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = planes[(size_t)j * N + pix], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pix];
-			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
+			if constexpr (sizeof...(M) != 0) den[j] = feature_den(fp[j], gp[j], j, kf2, tau, den[j]);
+			else den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = fp[0] == fp[0];
 	}
@@ -116,10 +128,11 @@ __global__ __launch_bounds__(kAtrousBlockW *kAtrousBlockH) void atrous_level_ker
 }
 
 hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *cv, double *feat_planes,
-                                 double *out) {
+                                 double *slope_planes, double *out) {
 	if (levels > kAtrousMaxLevels) return hipErrorInvalidValue;
-	const bool guided = in.feat != nullptr && levels != 0u;
+	const bool guided = in.feat != nullptr && levels != 0u, sloped = guided && w.slope > 0.0;
 	if (in.feat != nullptr && (in.feat_sq == nullptr || feat_planes == nullptr)) return hipErrorInvalidValue;
+	if (sloped && slope_planes == nullptr) return hipErrorInvalidValue;
 	DenoiseInput pre = in; // (levels = 0 reads no feature)
 	if (!guided) pre.feat = pre.feat_sq = nullptr;
 	hipError_t e = launch_denoise_planes(stream, pre, n_img, feat_planes);
@@ -138,6 +151,8 @@ hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, con
 	}
 	hipLaunchKernelGGL(atrous_prologue_kernel, dim3((uint32_t)blocks_1d), dim3(256), 0, stream, accum, accum_sq, n_img, N, cv);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
+	if (sloped && (e = launch_feature_slope(stream, feat_planes, W, H, w.slope, slope_planes)) != hipSuccess) return e; // (once: the features are every level's)
+	const double *m = slope_planes;
 	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
 	const dim3 grid((uint32_t)tiles), block(kAtrousBlockW * kAtrousBlockH);
 	double *set[2] = {cv, cv + 6u * N};
@@ -146,7 +161,10 @@ hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, con
 		double *next = set[(l + 1u) & 1u];
 		const int64_t step = (int64_t)1 << l;
 		const bool last = l + 1u == levels;
-		if (guided) {
+		if (sloped) {
+			if (last) hipLaunchKernelGGL((atrous_level_kernel<true, true, const double *>), grid, block, 0, stream, in, next, accum, n_img, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, m);
+			else hipLaunchKernelGGL((atrous_level_kernel<true, false, const double *>), grid, block, 0, stream, in, next, accum, n_img, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, m);
+		} else if (guided) {
 			if (last) hipLaunchKernelGGL((atrous_level_kernel<true, true>), grid, block, 0, stream, in, next, accum, n_img, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out);
 			else hipLaunchKernelGGL((atrous_level_kernel<true, false>), grid, block, 0, stream, in, next, accum, n_img, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out);
 		} else {

@@ -20,6 +20,12 @@
 //                                     atrous_dual_planes_region_kernel<G> the prologue (the pixel functions of denoise_dual.hip's dual_planes_kernel
 //                                     and dual_feature_planes_kernel, in one pass) over a block table's pixels.  The host makes one table per
 //                                     kernel from the needed sets (launch_denoise_atrous_dual_region).
+// SLOPE (rmd_denoise_atrous_dual_slope[_region] at slope > 0): one more trailing argument, last, the seven planes m of the f planes'
+//                                     slope floors; the kernel reads p's seven m once, where the denominators are made, and the same m serves every
+//                                     level and both passes.  The whole-frame call makes them with denoise.hip's feature_slope_kernel
+//                                     (launch_feature_slope); the region call with atrous_dual_slope_region_kernel, the same pixel function over level
+//                                     0's block table — every level's pixels lie in it, and the prologue's table holds their neighbours' f.  The
+//                                     instantiations without the argument keep their arguments and their instructions.
 // The per-pixel arithmetic and rmd_denoise_dual's combination are denoise_device.hpp's.
 // f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
@@ -92,17 +98,31 @@ __global__ __launch_bounds__(256) void atrous_dual_planes_region_kernel(const do
 	if constexpr (GUIDED) feature_planes_pixel(F, G, i, n_f[i], dual, N, fplanes);
 }
 
+// The slope floors over a block table's pixels (the region _slope call: level 0's table): feature_slope_pixel with the FRAME's width and height, so a
+// neighbour is present exactly when the whole-frame call finds it so — inside the frame and feature-valid, whatever the table holds
+__global__ __launch_bounds__(256) void atrous_dual_slope_region_kernel(const double *__restrict__ fplanes, const DualBlock *__restrict__ table, uint32_t W, uint32_t H,
+                                                                       size_t N, double s2, double *__restrict__ mplanes) {
+	const DualBlock e = table[blockIdx.x];
+	const uint32_t x = e.x0 + threadIdx.x % kAtrousDualBlockW, y = e.y0 + threadIdx.x / kAtrousDualBlockW;
+	if (x < e.x_end && y < e.y_end) feature_slope_pixel(fplanes, (size_t)x + (size_t)y * W, x, y, W, H, N, s2, mplanes);
+}
+
+// the trailing arguments: the block table (REGION), then the slope planes (SLOPE)
 __device__ inline const DualBlock *atrous_dual_table(const DualBlock *t) { return t; }
+__device__ inline const DualBlock *atrous_dual_table(const DualBlock *t, const double *) { return t; }
+__device__ inline const double *atrous_dual_slope(const double *m) { return m; }
+__device__ inline const double *atrous_dual_slope(const DualBlock *, const double *m) { return m; }
 
 // in / next: twelve planes of N = W*H doubles (above).  planes (GUIDED): dual_feature_planes_kernel's 14 planes.  tiles_x: workgroups per row of
 // tiles (the grid is one-dimensional: a frame may be taller than 65,535 tiles).  REGION: one more argument, the block table; workgroup b owns the pixels
-// at entry b's origin before its far corner (inside the frame), tiles_x is not read
+// at entry b's origin before its far corner (inside the frame), tiles_x is not read.  SLOPE (GUIDED only): one more argument after that, the seven slope planes
 template <bool GUIDED, bool LAST, bool REGION = false, class... T>
 __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_dual_level_kernel(
     const double *__restrict__ in, double *__restrict__ next, const double *__restrict__ SA, const double *__restrict__ SB, const uint32_t *__restrict__ n_a,
     const uint32_t *__restrict__ n_b, uint32_t W, uint32_t H, uint32_t tiles_x, int64_t step, double k2, double alpha, const double *__restrict__ planes, double kf2,
     double tau, double *__restrict__ out, double *__restrict__ err, T... table) {
-	static_assert(sizeof...(T) == (REGION ? 1 : 0), "the block table, with REGION only");
+	static_assert(sizeof...(T) == (REGION ? 1 : 0) || (GUIDED && sizeof...(T) == (REGION ? 2 : 1)), "the block table, with REGION only, then the slope planes, with GUIDED only");
+	constexpr bool SLOPE = sizeof...(T) == (REGION ? 2 : 1);
 	[[maybe_unused]] DualBlock e{};
 	if constexpr (REGION) e = atrous_dual_table(table...)[blockIdx.x];
 	// (REGION is a constant: each conditional below is one of its arms, and the whole-frame instantiations are compiled from the lines they always had)
@@ -125,9 +145,14 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 	[[maybe_unused]] bool p_fok = false;
 	if constexpr (GUIDED) {
 #pragma unroll
+		for (int j = 0; j < kDenoiseFeat; j++) { // SLOPE: the seven floors first, into den's registers — read beside f and g they cost two VGPRs and a wave per SIMD
+			if constexpr (SLOPE) den[j] = atrous_dual_slope(table...)[(size_t)j * N + pix];
+		}
+#pragma unroll
 		for (int j = 0; j < kDenoiseFeat; j++) {
 			fp[j] = planes[(size_t)j * N + pix], gp[j] = planes[(size_t)(kDenoiseFeat + j) * N + pix];
-			den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
+			if constexpr (SLOPE) den[j] = feature_den(fp[j], gp[j], j, kf2, tau, den[j]);
+			else den[j] = feature_den(fp[j], gp[j], j, kf2, tau);
 		}
 		p_fok = fp[0] == fp[0];
 	}
@@ -188,10 +213,11 @@ __global__ __launch_bounds__(kAtrousDualBlockW *kAtrousDualBlockH) void atrous_d
 }
 
 hipError_t launch_denoise_atrous_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
-                                      uint32_t *n_f_img, double *feat_planes, double *out, double *err) {
+                                      uint32_t *n_f_img, double *feat_planes, double *slope_planes, double *out, double *err) {
 	if (levels > kAtrousMaxLevels) return hipErrorInvalidValue;
-	const bool guided = in.feat != nullptr && levels != 0u;
+	const bool guided = in.feat != nullptr && levels != 0u, sloped = guided && w.slope > 0.0;
 	if (guided && (in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr))) return hipErrorInvalidValue;
+	if (sloped && slope_planes == nullptr) return hipErrorInvalidValue;
 	const double *accum_a = in.accum_a, *accum_b = in.accum_b;
 	const uint32_t W = in.W, H = in.H;
 	const double alpha = w.alpha, tau = w.tau;
@@ -211,13 +237,18 @@ hipError_t launch_denoise_atrous_dual(hipStream_t stream, const DenoiseInput &in
 	}
 	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
 	const dim3 grid((uint32_t)tiles), block(kAtrousDualBlockW * kAtrousDualBlockH);
+	if (sloped && (e = launch_feature_slope(stream, feat_planes, W, H, w.slope, slope_planes)) != hipSuccess) return e; // (once: the features are every level's)
+	const double *m = slope_planes;
 	double *set[2] = {state, state + 12u * N};
 	for (uint32_t l = 0; l < levels; l++) {
 		const double *in = set[l & 1u];
 		double *next = set[(l + 1u) & 1u];
 		const int64_t step = (int64_t)1 << l;
 		const bool last = l + 1u == levels;
-		if (guided) {
+		if (sloped) {
+			if (last) hipLaunchKernelGGL((atrous_dual_level_kernel<true, true, false, const double *>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err, m);
+			else hipLaunchKernelGGL((atrous_dual_level_kernel<true, false, false, const double *>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err, m);
+		} else if (guided) {
 			if (last) hipLaunchKernelGGL((atrous_dual_level_kernel<true, true>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
 			else hipLaunchKernelGGL((atrous_dual_level_kernel<true, false>), grid, block, 0, stream, in, next, accum_a, accum_b, n_a, n_b, W, H, tiles_x, step, k2, alpha, feat_planes, kf2, tau, out, err);
 		} else {
@@ -229,22 +260,26 @@ hipError_t launch_denoise_atrous_dual(hipStream_t stream, const DenoiseInput &in
 	return hipSuccess;
 }
 
-// One level of the region call over `n_blocks` entries of `table`
-template <bool GUIDED, bool LAST>
+// One level of the region call over `n_blocks` entries of `table`; m (at most one, GUIDED only): the slope planes
+template <bool GUIDED, bool LAST, class... M>
 static hipError_t launch_atrous_dual_region_level(hipStream_t stream, const DualBlock *table, uint32_t n_blocks, const double *in, double *next, const double *SA,
                                                   const double *SB, const uint32_t *n_a, const uint32_t *n_b, uint32_t W, uint32_t H, int64_t step, double k2, double alpha,
-                                                  const double *fplanes, double kf2, double tau, double *out, double *err) {
-	hipLaunchKernelGGL((atrous_dual_level_kernel<GUIDED, LAST, true, const DualBlock *>), dim3(n_blocks), dim3(kAtrousDualBlockW * kAtrousDualBlockH), 0, stream, in, next, SA,
+                                                  const double *fplanes, double kf2, double tau, double *out, double *err, M... m) {
+	if constexpr (sizeof...(M) != 0)
+		hipLaunchKernelGGL((atrous_dual_level_kernel<GUIDED, LAST, true, const DualBlock *, const double *>), dim3(n_blocks), dim3(kAtrousDualBlockW * kAtrousDualBlockH), 0, stream,
+		                   in, next, SA, SB, n_a, n_b, W, H, 0u, step, k2, alpha, fplanes, kf2, tau, out, err, table, m...);
+	else hipLaunchKernelGGL((atrous_dual_level_kernel<GUIDED, LAST, true, const DualBlock *>), dim3(n_blocks), dim3(kAtrousDualBlockW * kAtrousDualBlockH), 0, stream, in, next, SA,
 	                   SB, n_a, n_b, W, H, 0u, step, k2, alpha, fplanes, kf2, tau, out, err, table);
 	return hipGetLastError();
 }
 
 hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
-                                             uint32_t *n_f_img, double *feat_planes, const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count,
-                                             double *out, double *err) {
+                                             uint32_t *n_f_img, double *feat_planes, double *slope_planes, const DualBlock *table, const uint32_t *table_first,
+                                             const uint32_t *table_count, double *out, double *err) {
 	if (levels > kAtrousMaxLevels || table == nullptr || table_first == nullptr || table_count == nullptr) return hipErrorInvalidValue;
-	const bool guided = in.feat != nullptr && levels != 0u;
+	const bool guided = in.feat != nullptr && levels != 0u, sloped = guided && w.slope > 0.0;
 	if (guided && (in.feat_sq == nullptr || n_f_img == nullptr || feat_planes == nullptr || (in.n_rects && in.counts_f == nullptr))) return hipErrorInvalidValue;
+	if (sloped && slope_planes == nullptr) return hipErrorInvalidValue;
 	const double *accum_a = in.accum_a, *accum_sq_a = in.accum_sq_a, *accum_b = in.accum_b, *accum_sq_b = in.accum_sq_b;
 	const uint32_t W = in.W, H = in.H;
 	const double alpha = w.alpha, tau = w.tau;
@@ -270,6 +305,11 @@ hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseIn
 		return hipGetLastError();
 	}
 	const double k2 = w.k * w.k, kf2 = w.k_f * w.k_f;
+	const double *m = slope_planes;
+	if (sloped) { // on level 0's table: every later level's pixels lie in it, and table 0, made above, reaches two pixels further
+		hipLaunchKernelGGL(atrous_dual_slope_region_kernel, dim3(table_count[1]), block, 0, stream, feat_planes, table + table_first[1], W, H, N, w.slope * w.slope, slope_planes);
+		if ((e = hipGetLastError()) != hipSuccess) return e;
+	}
 	double *set[2] = {state, state + 12u * N};
 	for (uint32_t l = 0; l < levels; l++) {
 		const double *in = set[l & 1u];
@@ -278,7 +318,9 @@ hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseIn
 		const bool last = l + 1u == levels;
 		const DualBlock *t = table + table_first[l + 1u];
 		const uint32_t nb = table_count[l + 1u];
-		if (guided) e = last ? launch_atrous_dual_region_level<true, true>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err)
+		if (sloped) e = last ? launch_atrous_dual_region_level<true, true>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err, m)
+			                 : launch_atrous_dual_region_level<true, false>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err, m);
+		else if (guided) e = last ? launch_atrous_dual_region_level<true, true>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err)
 			                 : launch_atrous_dual_region_level<true, false>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err);
 		else e = last ? launch_atrous_dual_region_level<false, true>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err)
 			          : launch_atrous_dual_region_level<false, false>(stream, t, nb, in, next, accum_a, accum_b, n_a, n_b, W, H, step, k2, alpha, feat_planes, kf2, tau, out, err);

@@ -45,7 +45,7 @@ enum ScratchPart {
 	kPartCountsB,
 	kPartCountsF,
 	kPartTileErrors,  // rmd_tile_error_dual's result, n_rects doubles
-	kPartSlopePlanes, // slope_planes, 7 * W*H doubles (the _slope calls with a slope > 0; the block holds it right behind feat_planes)
+	kPartSlopePlanes, // slope_planes, 7 * W*H doubles (the _slope calls with a slope > 0; the non-local-means blocks hold it right behind feat_planes, the a-trous blocks last)
 	kScratchParts
 };
 struct ScratchLayout {
@@ -55,10 +55,12 @@ struct ScratchLayout {
 };
 // The block of one call.  Every part starts on a 16-byte boundary.  `guided`: the call has features (rmd_denoise_dual_select: a guided candidate);
 // n_table: the entries of the region forms' block tables (rmd_denoise_dual[_guided]_region, rmd_denoise_atrous_dual_region), 0 for a whole-frame call;
-// the other forms take no table and ignore it; `sloped`: a guided non-local-means call (single, dual, dual_select) some slope of which is > 0 — without it every
-// block is what it was before the slope existed
+// the other forms take no table and ignore it; `sloped`: a guided non-local-means _slope call (single, dual, dual_select) some slope of which is > 0;
+// `atrous_sloped`: a guided a-trous _slope call (atrous, atrous_dual, atrous_dual_region) whose slope is > 0 — without them every block is what it was before the
+// slope existed.  The non-local-means blocks hold the slope planes right behind the feature planes, the a-trous blocks behind everything else: every other
+// part of theirs keeps its offset.  (Two flags: `sloped` is pinned to change nothing on the a-trous forms.)
 inline ScratchLayout denoise_scratch_layout(ScratchForm form, uint32_t W, uint32_t H, uint32_t n_rects, bool guided, uint32_t n_cands, size_t n_table,
-                                            bool sloped = false) {
+                                            bool sloped = false, bool atrous_sloped = false) {
 	ScratchLayout L;
 	const size_t N = (size_t)W * H, f64 = sizeof(double), u32 = sizeof(uint32_t);
 	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count, bool wanted = true) {
@@ -88,6 +90,7 @@ inline ScratchLayout denoise_scratch_layout(ScratchForm form, uint32_t W, uint32
 	part(kPartCountsB, u32, n_rects, dual);
 	part(kPartCountsF, u32, n_rects, guided && dual);
 	part(kPartTileErrors, f64, n_rects, form == kScratchTileError);
+	part(kPartSlopePlanes, f64, RMD_FEATURE_CHANNELS * N, guided && atrous_sloped && (form == kScratchAtrous || form == kScratchAtrousDual || form == kScratchAtrousDualRegion));
 	return L;
 }
 

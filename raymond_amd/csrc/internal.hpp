@@ -86,6 +86,7 @@ struct rmd_context {
 	rmd::DeviceBuffer tile_done;      // split launches: finished waves per wave tile, a uint32 each (render_kernel.hpp)
 	rmd::DeviceBuffer debug_counters; // walk diagnostics (DIAG builds, RMD_DEBUG=8|16)
 	rmd::DeviceBuffer atrous_region_scratch; // rmd_denoise_atrous_dual_region's planes, count images and tables (api_denoise.cpp): grown when a call needs more, kept between calls
+	size_t atrous_region_slope_offset = 0, atrous_region_slope_pixels = 0; // the last sloped region call's slope planes in that block and its W*H (0: none yet), for rmd_probe_atrous_region_slope_planes
 	rmd::DeviceBuffer resolve_tiles_scratch; // rmd_resolve_tonemap_tiles's packed bytes, flag count, flag list and run table (api.cpp): grown when a call needs more, kept between calls
 	std::vector<unsigned char> resolve_tiles_table; // ... and the host copy of the table, alive until its upload has completed
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound

@@ -124,14 +124,15 @@ struct DenoiseInput {
 	const uint32_t *counts_a, *counts_b, *counts_f;
 	uint32_t n_rects, count_image_columns, W, H;
 };
-// checked by the caller (api_denoise.cpp); k_f, tau and slope are read only with features.  slope (the _slope calls; 0 everywhere else): the non-local-means
-// launchers alone read it, and at 0 they launch and read exactly what they did without it
+// checked by the caller (api_denoise.cpp); k_f, tau and slope are read only with features.  slope (the _slope calls; 0 everywhere else): at 0 every
+// launcher launches and reads exactly what it did without it
 struct DenoiseWeights {
 	double k, alpha, k_f, tau;
 	double slope = 0.0;
 };
 // The slope floors (denoise.hip: feature_slope_kernel): slope_planes = the seven planes m_j = (slope * slope) * (h_j + v_j), W*H doubles each, from the 14
-// planes feat_planes that launch_denoise_planes / launch_dual_planes have made on the same stream.  Always the whole frame
+// planes feat_planes that launch_denoise_planes / launch_dual_planes have made on the same stream.  Always the whole frame (the non-local-means launchers and
+// the whole-frame a-trous ones call it; rmd_denoise_atrous_dual_slope_region makes its floors over its own block table)
 hipError_t launch_feature_slope(hipStream_t stream, const double *feat_planes, uint32_t W, uint32_t H, double slope, double *slope_planes);
 // rmd_denoise / rmd_denoise_guided[_slope] (denoise.hip): out = the denoised means.  Scratch: n_img W*H uint32 for the per-pixel counts; with features
 // feat_planes, 14 * W*H doubles for the planar per-pixel f and g; with features and w.slope > 0 slope_planes, 7 * W*H doubles (else not read, may be null)
@@ -142,10 +143,11 @@ hipError_t launch_denoise_guided(hipStream_t stream, const DenoiseInput &in, con
 hipError_t launch_denoise_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *feat_planes);
 // rmd_denoise_atrous (denoise_atrous.hip): out = the frame after `levels` levels of the edge-avoiding a-trous filter (levels = 0: S / n).  n_img and
 // feat_planes as launch_denoise_guided's; cv is 12 * W*H doubles of scratch, the two sets of six planes (c and v) the levels alternate between.  levels is
-// checked by the caller
+// checked by the caller.  With features, levels > 0 and w.slope > 0 (rmd_denoise_atrous_slope): slope_planes is 7 * W*H doubles more, made once by
+// launch_feature_slope and read by every level; else it is not read and may be null
 constexpr uint32_t kAtrousMaxLevels = (uint32_t)RMD_ATROUS_MAX_LEVELS;
 hipError_t launch_denoise_atrous(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *cv, double *feat_planes,
-                                 double *out);
+                                 double *slope_planes, double *out);
 // rmd_denoise_dual (denoise_dual.hip): out = the cross-filtered means of the two halves, err (may be null) the per-pixel error estimate, W*H doubles.
 // Scratch: n_img 2 * W*H uint32, planes 12 * W*H doubles, f_b 3 * W*H doubles; the tile shape and LDS are denoise_kernel's.  table null: every pixel
 // of out and err is written.  table not null (rmd_denoise_dual_region; device memory): n_blocks entries (x0, y0, x_end, y_end), one per workgroup of
@@ -162,17 +164,19 @@ hipError_t launch_denoise_dual(hipStream_t stream, const DenoiseInput &in, const
 hipError_t launch_dual_planes(hipStream_t stream, const DenoiseInput &in, uint32_t *n_img, double *planes, uint32_t *n_f_img, double *feat_planes);
 // rmd_denoise_atrous_dual (denoise_atrous_dual.hip): out / err (err may be null) = rmd_denoise_dual's combination of the two halves after `levels`
 // levels of the a-trous filter, each half under the other's weights.  n_img, n_f_img and feat_planes as launch_denoise_dual's; state is 24 * W*H doubles of
-// scratch, the two sets of twelve planes the levels alternate between.  levels is checked by the caller
+// scratch, the two sets of twelve planes the levels alternate between.  levels is checked by the caller.  slope_planes as launch_denoise_atrous's
+// (rmd_denoise_atrous_dual_slope): one set of floors for every level and both halves
 hipError_t launch_denoise_atrous_dual(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
-                                      uint32_t *n_f_img, double *feat_planes, double *out, double *err);
+                                      uint32_t *n_f_img, double *feat_planes, double *slope_planes, double *out, double *err);
 // rmd_denoise_atrous_dual_region (denoise_atrous_dual.hip): launch_denoise_atrous_dual for the pixels of a region, through levels + 1 block tables of
 // 64 x 4-pixel workgroups (entries table_first[i] .. + table_count[i] of `table`, device memory; the two index arrays are host memory): table 0 the
 // prologue's — the pixels whose planes are made —, table 1 + l level l's; the last level's (table 0 at levels = 0) is cut from the region's rects and
 // carries their far corners, so only the region's pixels of out and err are written.  Every table has at least one entry.  n_img, state, n_f_img and
-// feat_planes as launch_denoise_atrous_dual's; what they hold outside the tables' pixels is not defined
+// feat_planes as launch_denoise_atrous_dual's; what they hold outside the tables' pixels is not defined.  slope_planes (rmd_denoise_atrous_dual_slope_region at
+// slope > 0, else not read): 7 * W*H doubles, made on table 1's pixels only — level 0's, which hold every later level's — from the f planes of table 0
 hipError_t launch_denoise_atrous_dual_region(hipStream_t stream, const DenoiseInput &in, const DenoiseWeights &w, uint32_t levels, uint32_t *n_img, double *state,
-                                             uint32_t *n_f_img, double *feat_planes, const DualBlock *table, const uint32_t *table_first, const uint32_t *table_count,
-                                             double *out, double *err);
+                                             uint32_t *n_f_img, double *feat_planes, double *slope_planes, const DualBlock *table, const uint32_t *table_first,
+                                             const uint32_t *table_count, double *out, double *err);
 // rmd_denoise_dual_select (denoise_dual.hip): launch_dual_planes once, then per candidate (a HOST array, checked by the caller) its two cross passes with
 // their gain images and its SURE image, then the winners and the blend.  Scratch: n_img and planes as above; cand_img 7 * W*H doubles per candidate
 // (f_A 3, f_B 3, SURE 1); gain 2 * W*H doubles (g_A, g_B, reused by every candidate); win_img W*H uint32; n_f_img and feat_planes as above, read only when

@@ -324,8 +324,8 @@ rmd_status rmd_probe_denoise_scratch(uint32_t form, uint32_t width, uint32_t hei
 }
 rmd_status rmd_probe_denoise_scratch_slope(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t sloped, uint32_t n_cands,
                                            uint64_t n_table, uint64_t *out3, uint64_t *total) {
-	if (form >= rmd::kScratchForms || guided > 1u || sloped > 1u || !out3 || !total) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
-	const rmd::ScratchLayout L = rmd::denoise_scratch_layout((rmd::ScratchForm)form, width, height, n_rects, guided != 0u, n_cands, (size_t)n_table, sloped != 0u);
+	if (form >= rmd::kScratchForms || guided > 1u || sloped > 2u || !out3 || !total) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	const rmd::ScratchLayout L = rmd::denoise_scratch_layout((rmd::ScratchForm)form, width, height, n_rects, guided != 0u, n_cands, (size_t)n_table, sloped == 1u, sloped == 2u);
 	for (uint32_t p = 0; p < rmd::kScratchParts; p++) out3[3 * p] = L.used[p], out3[3 * p + 1] = L.offset[p], out3[3 * p + 2] = L.bytes[p];
 	*total = L.total;
 	return RMD_OK;
@@ -341,6 +341,16 @@ rmd_status rmd_probe_feature_slope(rmd_context *ctx, const double *fplanes7, uin
 	RMD_HIP(ctx, hipMemcpyAsync(df.as<void>(), fplanes7, bytes, hipMemcpyHostToDevice, ctx->stream));
 	RMD_HIP(ctx, rmd::launch_feature_slope(ctx->stream, df.as<double>(), width, height, slope, dm.as<double>()));
 	RMD_HIP(ctx, hipMemcpyAsync(mplanes7, dm.as<void>(), bytes, hipMemcpyDeviceToHost, ctx->stream));
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	return RMD_OK;
+}
+
+rmd_status rmd_probe_atrous_region_slope_planes(rmd_context *ctx, uint32_t width, uint32_t height, double *mplanes7) {
+	if (!ctx || !mplanes7 || ctx->atrous_region_slope_pixels == 0u || (size_t)width * height != ctx->atrous_region_slope_pixels)
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	RMD_HIP(ctx, hipSetDevice(ctx->device));
+	const size_t bytes = ctx->atrous_region_slope_pixels * RMD_FEATURE_CHANNELS * sizeof(double);
+	RMD_HIP(ctx, hipMemcpyAsync(mplanes7, ctx->atrous_region_scratch.as<unsigned char>() + ctx->atrous_region_slope_offset, bytes, hipMemcpyDeviceToHost, ctx->stream));
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 	return RMD_OK;
 }

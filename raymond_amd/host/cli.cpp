@@ -13,6 +13,9 @@
 //                                                                    [--denoise-atrous 1 [--denoise-atrous-levels N] [--denoise-atrous-k K]]
 //                                                                      (needs --denoise 1, not with --denoise-dual: the fast filter for previews,
 //                                                                       rmd_denoise_atrous, guided with --denoise-features 1)
+//                                                                    [--denoise-atrous-slope G]   (needs a guided a-trous filter — --denoise-atrous 1 with --denoise-features 1,
+//                                                                      or --denoise-dual-atrous 1 with --denoise-dual-features 1: the feature-slope term at G
+//                                                                      pixels in rmd_denoise_atrous_slope / rmd_denoise_atrous_dual_slope[_region]; 3 to start from)
 //                                                                    [--dump-features FILE]   (the W*H*7 feature means as raw f64: the AOVs)
 //                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
 //                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
@@ -239,6 +242,7 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-feature-k")) st.denoise_feature_k = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-feature-tau")) st.denoise_feature_tau = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-feature-slope")) st.denoise_feature_slope = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--denoise-atrous-slope")) st.denoise_atrous_slope = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--denoise-atrous")) st.denoise_atrous = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-atrous-levels")) st.denoise_atrous_levels = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--denoise-atrous-k")) st.denoise_atrous_k = std::atof(argv[i + 1]);

@@ -329,6 +329,7 @@ Message preview_message(rmd_context *ctx, const double *fb, const double *fb2, s
 //   the features given:    rmd_denoise_dual_guided[_region]
 //   otherwise:             rmd_denoise_dual[_region]
 // With denoise_feature_slope > 0 the second and the third are their _slope calls (the guided candidate's slope; the setting excludes the first).
+// With denoise_atrous_slope > 0 and the features given the first is rmd_denoise_atrous_dual_slope[_region].
 // Two things that a reader may take for oversights and that every caller's bytes depend on: a call with a region never selects — rmd_denoise_dual_select
 // has no region form, and a select render's adaptive check is the plain or the guided region form —; and the unguided call with a region is
 // rmd_denoise_dual_region where the one without is rmd_denoise_dual.
@@ -338,7 +339,15 @@ void denoise_dual_frame(rmd_context *ctx, const Settings &st, size_t W, size_t H
 	const uint32_t w = (uint32_t)W, h = (uint32_t)H, n = (uint32_t)rects.size(), nr = (uint32_t)n_region;
 	const std::vector<uint32_t> counts_f = sum_counts(counts_a, counts_b); // (not read without the features)
 	const uint32_t *ca = counts_a.data(), *cb = counts_b.data(), *cf = counts_f.data();
-	if (st.denoise_dual_atrous && region && st.denoise_dual_atrous_region) {
+	if (st.denoise_dual_atrous && feat && st.denoise_atrous_slope > 0.0 && region && st.denoise_dual_atrous_region) {
+		check(rmd_denoise_atrous_dual_slope_region(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, region, nr, st.denoise_atrous_levels,
+		                                           st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, st.denoise_atrous_slope, out, err),
+		      ctx, "rmd_denoise_atrous_dual_slope_region");
+	} else if (st.denoise_dual_atrous && feat && st.denoise_atrous_slope > 0.0) {
+		check(rmd_denoise_atrous_dual_slope(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, st.denoise_atrous_levels, st.denoise_atrous_k,
+		                                    st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, st.denoise_atrous_slope, out, err),
+		      ctx, "rmd_denoise_atrous_dual_slope");
+	} else if (st.denoise_dual_atrous && region && st.denoise_dual_atrous_region) {
 		check(rmd_denoise_atrous_dual_region(ctx, half[0], half[1], half[2], half[3], feat, feat_sq, w, h, rects.data(), ca, cb, cf, n, region, nr, st.denoise_atrous_levels,
 		                                     st.denoise_atrous_k, st.denoise_alpha, st.denoise_feature_k, st.denoise_feature_tau, out, err),
 		      ctx, "rmd_denoise_atrous_dual_region");
@@ -866,6 +875,9 @@ std::string check_settings(const Settings &st) {
 		return "denoise_feature_slope cannot be combined with denoise_atrous / denoise_dual_atrous: the a-trous filters have no slope term";
 	if (st.denoise_feature_slope > 0.0 && !(st.denoise_features || st.denoise_dual_features || st.denoise_dual_select))
 		return "denoise_feature_slope > 0 needs a guided non-local-means filter (denoise_features, denoise_dual_features or denoise_dual_select)";
+	if (!(st.denoise_atrous_slope >= 0.0) || !std::isfinite(st.denoise_atrous_slope)) return "denoise_atrous_slope must be finite and >= 0 (0 = off)";
+	if (st.denoise_atrous_slope > 0.0 && !((st.denoise_atrous && st.denoise_features) || (st.denoise_dual_atrous && st.denoise_dual_features)))
+		return "denoise_atrous_slope > 0 needs a guided a-trous filter (denoise_atrous with denoise_features, or denoise_dual_atrous with denoise_dual_features)";
 	return "";
 }
 } // namespace
@@ -987,7 +999,12 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 	}
 	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums.data()), dev[0], W * H * 3), ctx, "rmd_framebuffer_upload");
 	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums_sq.data()), dev[1], W * H * 3), ctx, "rmd_framebuffer_upload");
-	if (settings.denoise_atrous) // (fdev both null without denoise_features: the colour weight alone)
+	if (settings.denoise_atrous && settings.denoise_features && settings.denoise_atrous_slope > 0.0)
+		check(rmd_denoise_atrous_slope(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
+		                               settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
+		                               settings.denoise_feature_tau, settings.denoise_atrous_slope, dev[2]),
+		      ctx, "rmd_denoise_atrous_slope");
+	else if (settings.denoise_atrous) // (fdev both null without denoise_features: the colour weight alone)
 		check(rmd_denoise_atrous(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
 		                         settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
 		                         settings.denoise_feature_tau, dev[2]),

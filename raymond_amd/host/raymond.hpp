@@ -144,6 +144,11 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// denoise_dual_features (await() and the adaptive check's region call) and denoise_dual_select's guided candidate is on makes its _slope call with it.
 	// render_tiled throws if it is not finite or negative, if it is > 0 with none of the three on, or with denoise_atrous / denoise_dual_atrous.
 	double denoise_feature_slope = 0.0;
+	// The same term in the guided a-trous filters (0 = off: no frame, message or launch changes; raymond_hip.h: rmd_denoise_atrous_slope; 3 is the value to
+	// start from).  When set, every call of a guided a-trous filter is its _slope call with it: await() with denoise_atrous + denoise_features or
+	// denoise_dual_atrous + denoise_dual_features, the adaptive check (its region form with denoise_dual_atrous_region) and a filtered FramePreview when it is
+	// guided.  render_tiled throws if it is not finite or negative, or if it is > 0 with neither of the two pairs on.
+	double denoise_atrous_slope = 0.0;
 	// The fast filter for previews (needs denoise, not with denoise_dual; false = off): await() returns rmd_denoise_atrous's frame at
 	// denoise_atrous_levels (0..8) and k = denoise_atrous_k (finite and > 0) with denoise_alpha, guided by the first-hit features when
 	// denoise_features is on (denoise_feature_k, denoise_feature_tau).  denoise_radius, denoise_patch and denoise_k are then not used.  render_tiled

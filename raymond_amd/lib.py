@@ -130,6 +130,22 @@ SIGNATURES = {
         [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32,
          _P(abi.TileRect), C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp],
     ),
+    # the a-trous _slope calls: `slope` after tau
+    "rmd_denoise_atrous_slope": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double,
+         C.c_double, C.c_double, _vp],
+    ),
+    "rmd_denoise_atrous_dual_slope": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32,
+         C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp],
+    ),
+    "rmd_denoise_atrous_dual_slope_region": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32,
+         _P(abi.TileRect), C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp],
+    ),
     "rmd_tile_error_dual": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), C.c_uint32, _vp]),
     "rmd_feature_buffer_alloc": (C.c_int32, [_vp, C.c_uint32, C.c_uint32, _P(_vp)]),
     "rmd_render_features": (

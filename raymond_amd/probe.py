@@ -42,6 +42,7 @@ _SIGS = {
     "rmd_probe_scene_plan": [_vp, _vp, _sz, _vp],
     "rmd_probe_denoise_scratch": [C.c_uint32] * 6 + [C.c_uint64, _vp, _P(C.c_uint64)],
     "rmd_probe_feature_slope": [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp],
+    "rmd_probe_atrous_region_slope_planes": [_vp, C.c_uint32, C.c_uint32, _vp],
     "rmd_probe_denoise_scratch_slope": [C.c_uint32] * 7 + [C.c_uint64, _vp, _P(C.c_uint64)],
 }
 PATH_STRIDE = 17
@@ -319,16 +320,28 @@ def feature_slope(ctx, f, fvalid, slope):
     return np.moveaxis(out, 0, -1).copy()
 
 
+def atrous_region_slope_planes(ctx, width, height):
+    """The slope planes the context's last sloped rmd_denoise_atrous_dual_slope_region call left in its scratch -> m (H, W, 7); defined on level 0's needed
+    set only.  api: rmd_probe_atrous_region_slope_planes."""
+    out = np.zeros((7, height, width), dtype=np.float64)
+    ctx.check(_L().rmd_probe_atrous_region_slope_planes(ctx.handle, width, height, _p(out)))
+    return np.moveaxis(out, 0, -1).copy()
+
+
 # rmd_probe_denoise_scratch: the forms, and the parts in the order of denoise_host.hpp's ScratchPart
 SCRATCH_FORMS = ("single", "atrous", "dual", "atrous_dual", "atrous_dual_region", "dual_select", "tile_error")
 SCRATCH_PARTS = ("planes", "f_b", "cand_img", "gain", "feat_planes", "n_img", "win_img", "n_f_img", "table", "rects", "counts_a", "counts_b", "counts_f",
                  "tile_errors", "slope_planes")
 
 
-def denoise_scratch(form, width, height, n_rects, guided=False, n_cands=0, n_table=0, sloped=None):
+def denoise_scratch(form, width, height, n_rects, guided=False, n_cands=0, n_table=0, sloped=None, atrous_sloped=None):
     """Host only: the scratch block of a denoise call -> ({part: (offset, bytes)} of the parts the form holds, total bytes).  sloped (None: the call
-    has no slope argument): a _slope call, and whether a slope it reads is > 0.
+    has no slope argument): a non-local-means _slope call, and whether a slope it reads is > 0.  atrous_sloped (None likewise): an a-trous _slope call
+    (rmd_denoise_atrous_slope, rmd_denoise_atrous_dual_slope[_region]), and whether its slope is > 0.
     api: rmd_probe_denoise_scratch, rmd_probe_denoise_scratch_slope."""
+    if atrous_sloped is not None:
+        assert sloped is None, "one call has one slope"
+        sloped = 2 if atrous_sloped else 0
     L = _L()
     out = np.zeros((len(SCRATCH_PARTS), 3), dtype=np.uint64)
     total = C.c_uint64()

@@ -257,16 +257,20 @@ def denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **
 
 
 def denoise_atrous(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuffer, levels=5, k=3.0, alpha=1.0, features=None, features_sq=None, k_f=1.0,
-                   tau=1e-2):
+                   tau=1e-2, slope=None):
     """rmd_denoise_atrous: `out_framebuffer` = the frame after `levels` levels of the edge-avoiding a-trous filter (the fast filter for previews), with
-    the feature weight of the FeatureBuffers `features` / `features_sq` when they are given.  The result holds means, not sums."""
+    the feature weight of the FeatureBuffers `features` / `features_sq` when they are given.  The result holds means, not sums.
+    `slope` (a number; None: the call above): rmd_denoise_atrous_slope, the same with the feature-slope term at that many pixels (0: the same bytes)."""
     counts = np.ascontiguousarray(counts, dtype=np.uint32)
     if len(counts) != len(rects):
         raise ValueError("one sample count per rect")
-    ctx.check(ctx.L.rmd_denoise_atrous(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr,
-                                       None if features_sq is None else features_sq.ptr, framebuffer.width, framebuffer.height, tile_array(rects),
-                                       counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(levels), float(k), float(alpha), float(k_f), float(tau),
-                                       out_framebuffer.ptr))
+    head = (ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr, None if features_sq is None else features_sq.ptr,
+            framebuffer.width, framebuffer.height, tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(levels), float(k),
+            float(alpha), float(k_f), float(tau))
+    if slope is None:
+        ctx.check(ctx.L.rmd_denoise_atrous(*head, out_framebuffer.ptr))
+    else:
+        ctx.check(ctx.L.rmd_denoise_atrous_slope(*head, float(slope), out_framebuffer.ptr))
 
 
 def denoise_atrous_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **params):
@@ -376,13 +380,13 @@ def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts
 
 
 def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, levels=5, k=3.0, alpha=1.0, features=None,
-                        features_sq=None, counts_f=None, k_f=1.0, tau=1e-2, region=None):
+                        features_sq=None, counts_f=None, k_f=1.0, tau=1e-2, region=None, slope=None):
     """rmd_denoise_atrous_dual: `out_framebuffer` = the two sample halves `half_a` and `half_b` (as denoise_dual's) after `levels` levels of the
     edge-avoiding a-trous filter, each half under the other's weights, combined as denoise_dual combines them; `error_image` (an ErrorImage,
     optional) receives the per-pixel error estimate.  `features` / `features_sq` (FeatureBuffers; rect i holds counts_f[i] feature samples per
     pixel) add the feature weight; without them counts_f, k_f and tau are not read.  `region` (a list of rects, possibly empty):
     rmd_denoise_atrous_dual_region — only the pixels of those rects are written, with the bytes the whole-frame call gives them; None is the whole-frame
-    call."""
+    call.  `slope` (a number; None: the calls above): rmd_denoise_atrous_dual_slope[_region], the same with the feature-slope term."""
     counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
     counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
     if len(counts_a) != len(rects) or len(counts_b) != len(rects):
@@ -397,12 +401,15 @@ def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_fram
     head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, None if features is None else features.ptr,
             None if features_sq is None else features_sq.ptr, fb.width, fb.height, tile_array(rects), counts_a.ctypes.data_as(C.POINTER(C.c_uint32)),
             counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), p_f, len(rects))
-    tail = (int(levels), float(k), float(alpha), float(k_f), float(tau), out_framebuffer.ptr, None if error_image is None else error_image.ptr)
+    tail = ((int(levels), float(k), float(alpha), float(k_f), float(tau)) + (() if slope is None else (float(slope),)) +
+            (out_framebuffer.ptr, None if error_image is None else error_image.ptr))
+    whole, regional = ((ctx.L.rmd_denoise_atrous_dual, ctx.L.rmd_denoise_atrous_dual_region) if slope is None else
+                       (ctx.L.rmd_denoise_atrous_dual_slope, ctx.L.rmd_denoise_atrous_dual_slope_region))
     if region is None:
-        ctx.check(ctx.L.rmd_denoise_atrous_dual(*head, *tail))
+        ctx.check(whole(*head, *tail))
     else:
         region = list(region)
-        ctx.check(ctx.L.rmd_denoise_atrous_dual_region(*head, tile_array(region), len(region), *tail))
+        ctx.check(regional(*head, tile_array(region), len(region), *tail))
 
 
 def denoise_atrous_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, out_init=None, err_init=None, features=None,
@@ -688,7 +695,7 @@ class TaskHandle:  # src/trace.rs:70-135
                 if st.denoise_atrous:
                     feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts) if st.denoise_features else (None, None)
                     out = denoise_atrous_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, levels=st.denoise_atrous_levels, k=st.denoise_atrous_k,
-                                                alpha=st.denoise_alpha, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau)
+                                                alpha=st.denoise_alpha, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau, **st.atrous_slope_keyword())
                 elif st.denoise_features:
                     feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts)
                     out = denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
@@ -729,7 +736,8 @@ class TaskHandle:  # src/trace.rs:70-135
                 if st.denoise_dual_features:
                     counts_f = [a + b for a, b in zip(counts_a, counts_b)]
                     feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
-                    guide = dict(features=feats, features_sq=feats_sq, counts_f=counts_f, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau)
+                    guide = dict(features=feats, features_sq=feats_sq, counts_f=counts_f, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
+                                 **st.atrous_slope_keyword())
                 out, _ = denoise_atrous_dual_arrays(ctx, *halves, rects, counts_a, counts_b, levels=st.denoise_atrous_levels, k=st.denoise_atrous_k,
                                                     alpha=st.denoise_alpha, **guide)
             elif st.denoise_dual_select:
@@ -974,8 +982,9 @@ def _render_tiled_dual(scene, settings, devices):
                                      tau=st.denoise_feature_tau)
                     if st.denoise_dual_atrous:
                         where = dict(region=live) if st.denoise_dual_atrous_region else {}  # (off: exactly the call made before the region form existed)
+                        slope = st.atrous_slope_keyword() if guided else {}  # (set: the check is rmd_denoise_atrous_dual_slope[_region])
                         denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img,
-                                            levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **where)
+                                            levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **where, **slope)
                     else:
                         slope = st.slope_keyword() if guided else {}  # (set: the check is rmd_denoise_dual_guided_slope_region)
                         denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide, **slope)
@@ -997,8 +1006,9 @@ def _render_tiled_dual(scene, settings, devices):
                         if guided:
                             guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
                                          tau=st.denoise_feature_tau)
+                        slope = st.atrous_slope_keyword() if guided else {}  # (set: the preview is rmd_denoise_atrous_dual_slope's)
                         denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), rects, all_a, all_b, preview_fb, None, levels=st.denoise_atrous_levels,
-                                            k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide)
+                                            k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **slope)
                         packed = resolve_tonemap_tiles(ctx, preview_fb, rects, [1] * len(rects), st.preview_exposure, st.preview_gamma)  # (means)
                     messages.append(Message.FramePreview(scatter_tiles(rects, packed, W, H), j, done))
                 live = still

@@ -248,7 +248,8 @@ class Settings:
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
                  adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False, denoise_atrous=False,
                  denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False, preview_every=0,
-                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, denoise_feature_slope=0.0):
+                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, denoise_feature_slope=0.0,
+                 denoise_atrous_slope=0.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -285,8 +286,14 @@ class Settings:
         # The feature-slope term of the guided non-local-means filters (0.0 = off: no frame, message or launch changes): the number of pixels of a
         # feature's local slope that is not an edge (raymond_hip.h: rmd_denoise_guided_slope; DESIGN.md section 21 — 3 is the value to start from).  When
         # set, whichever of denoise_features, denoise_dual_features (await_() and the adaptive check's region call) and denoise_dual_select's guided
-        # candidate is on makes its _slope call with it.  Needs one of them, excludes the a-trous filters.
+        # candidate is on makes its _slope call with it.  Needs one of them; the a-trous filters take the term through denoise_atrous_slope, a setting of
+        # its own, and are refused here.
         self.denoise_feature_slope = float(denoise_feature_slope)
+        # The same term in the guided a-trous filters (0.0 = off: no frame, message or launch changes; raymond_hip.h: rmd_denoise_atrous_slope; DESIGN.md
+        # section 22 — 3 is the value to start from).  When set, every call of a guided a-trous filter is its _slope call with it: await_() with denoise_atrous
+        # + denoise_features or denoise_dual_atrous + denoise_dual_features, the adaptive check (its region form with denoise_dual_atrous_region) and a
+        # filtered FramePreview when it is guided.  Needs one of those two pairs.
+        self.denoise_atrous_slope = float(denoise_atrous_slope)
         # Dual-buffer denoising (an extension of the extension; False = off): a tile's passes go alternately into two half buffers A (even passes,
         # counted from 0) and B (odd ones), and await_() returns rmd_denoise_dual's frame: each half filtered with the other's weights.  Needs
         # denoise and samples_per_iteration > 0; one device only.
@@ -343,6 +350,10 @@ class Settings:
         """{} while denoise_feature_slope is off — the calls made are then those made before it existed —, else dict(slope=denoise_feature_slope)."""
         return dict(slope=self.denoise_feature_slope) if self.denoise_feature_slope > 0.0 else {}
 
+    def atrous_slope_keyword(self):
+        """{} while denoise_atrous_slope is off — the calls made are then those made before it existed —, else dict(slope=denoise_atrous_slope)."""
+        return dict(slope=self.denoise_atrous_slope) if self.denoise_atrous_slope > 0.0 else {}
+
     def check_adaptive(self):
         """Raises ValueError for adaptive settings render_tiled cannot follow."""
         if not self.adaptive_threshold >= 0.0:
@@ -372,6 +383,11 @@ class Settings:
             raise ValueError("denoise_feature_slope cannot be combined with denoise_atrous / denoise_dual_atrous: the a-trous filters have no slope term")
         if self.denoise_feature_slope > 0.0 and not (self.denoise_features or self.denoise_dual_features or self.denoise_dual_select):
             raise ValueError("denoise_feature_slope > 0 needs a guided non-local-means filter (denoise_features, denoise_dual_features or denoise_dual_select)")
+        if not (self.denoise_atrous_slope >= 0.0 and np.isfinite(self.denoise_atrous_slope)):
+            raise ValueError("denoise_atrous_slope must be finite and >= 0 (0 = off)")
+        if self.denoise_atrous_slope > 0.0 and not ((self.denoise_atrous and self.denoise_features) or (self.denoise_dual_atrous and self.denoise_dual_features)):
+            raise ValueError("denoise_atrous_slope > 0 needs a guided a-trous filter (denoise_atrous with denoise_features, or denoise_dual_atrous with "
+                             "denoise_dual_features)")
         v = self.denoise_atrous_levels
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= abi.RMD_ATROUS_MAX_LEVELS:
             raise ValueError("denoise_atrous_levels must be an integer in [0, %d]" % abi.RMD_ATROUS_MAX_LEVELS)
