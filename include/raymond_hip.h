@@ -60,7 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_resolve_tonemap_tiles,
+	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
@@ -872,6 +872,41 @@ rmd_status rmd_resolve_tonemap(rmd_context *ctx, const double *accum_dev, uint32
 rmd_status rmd_resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
                                      const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, double exposure, double gamma,
                                      uint8_t *out_rgb8_host_packed);
+
+/* ---- automatic exposure: the luminance histogram of a frame and the exposure it asks for (no reference counterpart; the reference's exposure is 1) ---- */
+#define RMD_LUMA_BINS 256u
+/* Counts of pixels by luminance Y, binned by Y's IEEE binary64 bits alone: with E the unbiased exponent and M the top two mantissa bits, a Y with
+ * -32 <= E < 32 is counted in bins[(E + 32) * 4 + M] — bin i holds [2^e (1 + m / 4), 2^e (1 + (m + 1) / 4)) with e = i / 4 - 32, m = i % 4: four bins an
+ * octave over 2^-32 .. 2^32 — and every other Y in one of the five side counters.  No logarithm is taken anywhere, so every counter is an exact integer
+ * that a host can restate.  sizeof = 262 * 8. */
+typedef struct rmd_luma_histogram {
+	uint64_t bins[RMD_LUMA_BINS];
+	uint64_t below, above;               /* positive finite Y under 2^-32 (denormals included) / at or over 2^32 */
+	uint64_t zero, negative, not_finite; /* Y == +-0 / Y < 0 / NaN or +-inf */
+	uint64_t pixels;                     /* all packed pixels = the sum of every counter above */
+} rmd_luma_histogram;
+/* The luminance histogram of the pixels rmd_resolve_tonemap_tiles would resolve: the same buffers, rects, counts and optional second buffer, and the
+ * same rules.  For a packed pixel of rect j and channel c: s_c = accum_dev's sum — plus accum2_dev's, in one rounded addition, when accum2_dev is not
+ * NULL —, p_c = s_c / (double)rect_sample_counts[j], and Y = (0.2126 * p_0 + 0.7152 * p_1) + 0.0722 * p_2: each product rounded, then the two additions
+ * as bracketed, no fused multiply-add.  A buffer of means (a denoised frame) goes through with counts of 1.  A count of 0 is allowed (zero sums: 0 / 0,
+ * counted in not_finite).  Rects may have any size and alignment inside the width x height frame and may overlap (a pixel two rects cover is counted
+ * twice); a rect without pixels counts nothing; n_rects = 0 writes an all-zero histogram and returns RMD_OK.  Histograms of disjoint rect lists — several
+ * devices, each over its own tiles — add field by field to the histogram of the lists together, exactly and in any order.
+ * RMD_ERR_INVALID_ARGUMENT, checked before the device is touched and with the output untouched, in this order: accum_dev NULL, width or height 0, rects or
+ * rect_sample_counts NULL with n_rects > 0; accum2_dev overlapping accum_dev; a rect outside the frame; (RMD_ERR_UNSUPPORTED: more than 2^32 - 1 packed
+ * pixels;) out_host NULL; and only then a NULL context.  Synchronous; reports an earlier device fault like rmd_resolve_tonemap_tiles.  The cost follows
+ * the packed pixels, whatever the number and shape of the rects; the call's device scratch (261 counters and the workgroup table) stays on the context and
+ * grows on demand. */
+rmd_status rmd_luminance_histogram_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
+                                         const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, rmd_luma_histogram *out_host);
+/* The exposure that puts the histogram's `percentile` of luminance at `target` before gamma: 1 - exp(-Y_p * exposure) = target.  A host function: no
+ * context, no device.  N = below + the sum of bins + above (zero, negative and not_finite take no part); N == 0 gives 1.0.  Otherwise
+ * r = (uint64_t)ceil(percentile * (double)N) clamped to [1, N]; `below`, bins 0 .. 255 and `above` are accumulated in this order up to the first
+ * cumulative count >= r, and Y_p is 2^-32 when that is `below`, the bin's upper edge ldexp(1.0 + (M + 1) * 0.25, E) when it is a bin, 2^32 when it is
+ * `above`; *out_exposure = -log1p(-target) / Y_p with the host's libm.  Values to start from: percentile 0.99, target 0.8.
+ * RMD_ERR_INVALID_ARGUMENT (text through rmd_last_error(NULL)): h or out_exposure NULL; percentile not finite or outside (0, 1]; target not finite or
+ * outside (0, 1). */
+rmd_status rmd_exposure_from_histogram(const rmd_luma_histogram *h, double percentile, double target, double *out_exposure);
 
 /* ---- multi-GPU (no reference counterpart; the reference has no collectives) ---- */
 #define RMD_COMM_ID_BYTES 128

@@ -159,6 +159,11 @@ extern "C" {
     // a dual-buffer render's other half): what a FramePreview of the C++ mirror (raymond_amd/host: settings.preview_every) is made with
     fn rmd_resolve_tonemap_tiles(ctx: *mut rmd_context, accum_dev: *const f64, accum2_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                                  rect_sample_counts: *const u32, n_rects: u32, exposure: f64, gamma: f64, out_rgb8_host_packed: *mut u8) -> i32;
+    // the luminance histogram of the pixels that call would resolve, and the exposure a percentile of it asks for (settings.preview_auto_exposure of the
+    // C++ mirror); rmd_luma_histogram: include/raymond_hip.h, 262 u64
+    fn rmd_luminance_histogram_tiles(ctx: *mut rmd_context, accum_dev: *const f64, accum2_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                                     rect_sample_counts: *const u32, n_rects: u32, out_host: *mut rmd_luma_histogram) -> i32;
+    fn rmd_exposure_from_histogram(h: *const rmd_luma_histogram, percentile: f64, target: f64, out_exposure: *mut f64) -> i32;
 }
 
 /// One candidate of rmd_denoise_dual_select (include/raymond_hip.h: rmd_denoise_candidate); `reserved` is 0
@@ -172,6 +177,20 @@ pub struct rmd_denoise_candidate {
     pub tau: f64,
     pub guided: u32,
     pub reserved: u32,
+}
+
+/// rmd_luminance_histogram_tiles's counters (include/raymond_hip.h: rmd_luma_histogram): 256 bins, four an octave over 2^-32 .. 2^32, and the side counters
+#[repr(C)]
+#[derive(Clone, Copy)]
+#[allow(non_camel_case_types, dead_code)]
+pub struct rmd_luma_histogram {
+    pub bins: [u64; 256],
+    pub below: u64,
+    pub above: u64,
+    pub zero: u64,
+    pub negative: u64,
+    pub not_finite: u64,
+    pub pixels: u64,
 }
 
 fn check(ctx: *const rmd_context, status: i32) {

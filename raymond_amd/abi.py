@@ -130,6 +130,20 @@ class DenoiseCandidate(C.Structure):  # rmd_denoise_candidate
 
 DENOISE_MAX_CANDIDATES = 4  # RMD_DENOISE_MAX_CANDIDATES
 
+RMD_LUMA_BINS = 256  # rmd_luma_histogram: four bins an octave over 2^-32 .. 2^32
+
+
+class LumaHistogram(C.Structure):  # rmd_luma_histogram
+    _fields_ = [
+        ("bins", C.c_uint64 * RMD_LUMA_BINS),
+        ("below", C.c_uint64),
+        ("above", C.c_uint64),
+        ("zero", C.c_uint64),
+        ("negative", C.c_uint64),
+        ("not_finite", C.c_uint64),
+        ("pixels", C.c_uint64),
+    ]
+
 
 class LaunchInfo(C.Structure):  # rmd_launch_info
     _fields_ = [

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -11,6 +12,7 @@
 
 #include "internal.hpp"
 #include "launch.hpp"
+#include "luma_bins.hpp"
 #include "resolve_tiles_host.hpp"
 
 using rmd::bind;
@@ -1356,6 +1358,94 @@ rmd_status rmd_resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, 
                                      uint8_t *out_rgb8_host_packed) {
 	return rmd::guarded(ctx, "rmd_resolve_tonemap_tiles", [&] {
 		return resolve_tonemap_tiles_impl(ctx, accum_dev, accum2_dev, width, height, rects, rect_sample_counts, n_rects, exposure, gamma, out_rgb8_host_packed);
+	});
+}
+
+// The luminance histogram of the same rects (luma_histogram.hip; luma_bins.hpp: the luminance and the counter of a pixel).  The argument rules are
+// rmd_resolve_tonemap_tiles's, in its order, and all of them come before the context is looked at.  Scratch on the context: [261 counters, padded to
+// 16 bytes][runs].
+static_assert(sizeof(rmd_luma_histogram) == (rmd::kLumaCounters + 1) * sizeof(uint64_t) && RMD_LUMA_BINS == rmd::kLumaBins, "luma_bins.hpp mirrors include/raymond_hip.h");
+static_assert(offsetof(rmd_luma_histogram, below) == rmd::kLumaBelow * 8 && offsetof(rmd_luma_histogram, above) == rmd::kLumaAbove * 8 &&
+              offsetof(rmd_luma_histogram, zero) == rmd::kLumaZero * 8 && offsetof(rmd_luma_histogram, negative) == rmd::kLumaNegative * 8 &&
+              offsetof(rmd_luma_histogram, not_finite) == rmd::kLumaNotFinite * 8 && offsetof(rmd_luma_histogram, pixels) == rmd::kLumaCounters * 8,
+              "the device's counters are the struct's fields in order");
+static rmd_status luminance_histogram_tiles_impl(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
+                                                 const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, rmd_luma_histogram *out) {
+	const char *name = "rmd_luminance_histogram_tiles: ";
+	if (!accum_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts)))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "bad argument");
+	const size_t frame_doubles = (size_t)width * height * 3;
+	const uintptr_t lo1 = reinterpret_cast<uintptr_t>(accum_dev), lo2 = reinterpret_cast<uintptr_t>(accum2_dev), frame_bytes = frame_doubles * sizeof(double);
+	if (accum2_dev && lo2 < lo1 + frame_bytes && lo1 < lo2 + frame_bytes)
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "accum2_dev overlaps accum_dev");
+	std::vector<uint64_t> first;
+	if (!rmd::resolve_first_pixels(rects, n_rects, width, height, first))
+		return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "tile rectangle outside the framebuffer");
+	const uint64_t n_pixels = first[n_rects];
+	if (n_pixels > 0xFFFFFFFFull) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, std::string(name) + "more than 2^32-1 packed pixels");
+	if (!out) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "null out_host");
+	if (rmd_status s = bind(ctx)) return s;
+	std::memset(out, 0, sizeof(*out));
+	if (n_pixels == 0) return RMD_OK;
+	const std::vector<rmd::ResolveRun> runs = rmd::resolve_runs(rects, rect_sample_counts, n_rects, first);
+	if (runs.size() > 0x7FFFFFFFull) return rmd::fail(ctx, RMD_ERR_UNSUPPORTED, std::string(name) + "more than 2^31-1 workgroups");
+	const size_t counter_bytes = ((size_t)rmd::kLumaCounters * sizeof(uint64_t) + 15) & ~(size_t)15, table_bytes = runs.size() * sizeof(rmd::ResolveRun);
+	// as rmd_resolve_tonemap_tiles: the stream is waited for first, so that the table's upload and the counters' download are made on an idle stream
+	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+	RMD_HIP(ctx, ctx->luma_scratch.grow(counter_bytes + table_bytes));
+	ctx->luma_table.assign(reinterpret_cast<const unsigned char *>(runs.data()), reinterpret_cast<const unsigned char *>(runs.data()) + table_bytes);
+	uint8_t *d = ctx->luma_scratch.as<uint8_t>();
+	uint64_t *d_counters = reinterpret_cast<uint64_t *>(d);
+	rmd::ResolveRun *d_runs = reinterpret_cast<rmd::ResolveRun *>(d + counter_bytes);
+	uint64_t counters[rmd::kLumaCounters];
+	hipError_t e = hipMemsetAsync(d_counters, 0, counter_bytes, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(d_runs, ctx->luma_table.data(), table_bytes, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess) e = rmd::launch_luma_histogram(ctx->stream, accum_dev, accum2_dev, width, d_runs, (uint32_t)runs.size(), d_counters);
+	if (e == hipSuccess) e = hipMemcpyAsync(counters, d_counters, sizeof(counters), hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	RMD_HIP(ctx, e);
+	std::memcpy(out, counters, sizeof(counters)); // (the fields in order: the static_asserts above)
+	for (uint32_t i = 0; i < rmd::kLumaCounters; i++) out->pixels += counters[i];
+	return rmd::check_fault(ctx);
+}
+rmd_status rmd_luminance_histogram_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, uint32_t width, uint32_t height,
+                                         const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects, rmd_luma_histogram *out_host) {
+	return rmd::guarded(ctx, "rmd_luminance_histogram_tiles", [&] {
+		return luminance_histogram_tiles_impl(ctx, accum_dev, accum2_dev, width, height, rects, rect_sample_counts, n_rects, out_host);
+	});
+}
+
+// The exposure that puts a percentile of a histogram's luminance at `target` before gamma: host arithmetic only, no context, no device.
+rmd_status rmd_exposure_from_histogram(const rmd_luma_histogram *h, double percentile, double target, double *out_exposure) {
+	return rmd::guarded(nullptr, "rmd_exposure_from_histogram", [&]() -> rmd_status {
+		const char *name = "rmd_exposure_from_histogram: ";
+		if (!h || !out_exposure) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "null pointer");
+		if (!(percentile > 0.0 && percentile <= 1.0)) // (a NaN fails both)
+			return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "percentile must be finite and in (0, 1]");
+		if (!(target > 0.0 && target < 1.0)) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "target must be finite and in (0, 1)");
+		uint64_t n = h->below + h->above;
+		for (uint32_t i = 0; i < RMD_LUMA_BINS; i++) n += h->bins[i];
+		if (n == 0) {
+			*out_exposure = 1.0;
+			return RMD_OK;
+		}
+		const double want = std::ceil(percentile * (double)n);
+		uint64_t rank = want >= 18446744073709551616.0 ? n : (uint64_t)want; // (2^64: (double)n may have rounded up to it)
+		rank = std::min(std::max<uint64_t>(rank, 1), n);
+		double y = 0x1p-32; // the walk stops in `below`
+		uint64_t seen = h->below;
+		if (seen < rank) {
+			y = 0x1p32; // ... or in `above`, when no bin reaches the rank
+			for (uint32_t i = 0; i < RMD_LUMA_BINS; i++) {
+				seen += h->bins[i];
+				if (seen >= rank) {
+					y = std::ldexp(1.0 + (double)(i % 4u + 1u) * 0.25, (int)(i / 4u) + rmd::kLumaMinExponent); // the bin's upper edge
+					break;
+				}
+			}
+		}
+		*out_exposure = -std::log1p(-target) / y;
+		return RMD_OK;
 	});
 }
 

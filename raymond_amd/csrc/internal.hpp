@@ -89,6 +89,8 @@ struct rmd_context {
 	size_t atrous_region_slope_offset = 0, atrous_region_slope_pixels = 0; // the last sloped region call's slope planes in that block and its W*H (0: none yet), for rmd_probe_atrous_region_slope_planes
 	rmd::DeviceBuffer resolve_tiles_scratch; // rmd_resolve_tonemap_tiles's packed bytes, flag count, flag list and run table (api.cpp): grown when a call needs more, kept between calls
 	std::vector<unsigned char> resolve_tiles_table; // ... and the host copy of the table, alive until its upload has completed
+	rmd::DeviceBuffer luma_scratch; // rmd_luminance_histogram_tiles's 261 counters and run table (api.cpp): grown when a call needs more, kept between calls
+	std::vector<unsigned char> luma_table; // ... and the host copy of the table, alive until its upload has completed
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound
 	// writes here; the host looks after every wait for the stream (api.cpp: check_fault) — a plain host load, no copy
 	uint32_t *h_fault = nullptr, *d_fault = nullptr;

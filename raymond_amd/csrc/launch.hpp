@@ -209,6 +209,10 @@ hipError_t launch_tonemap(hipStream_t stream, const double *accum, uint8_t *rgb8
 struct ResolveRun;
 hipError_t launch_resolve_tiles(hipStream_t stream, const double *accum, const double *accum2, uint32_t W, const ResolveRun *runs, uint32_t n_runs,
                                 double exposure, double inv_gamma, uint8_t *rgb8, uint32_t *flagged, uint32_t *n_flagged);
+// rmd_luminance_histogram_tiles (luma_histogram.hip): one workgroup per run of the same table; counters: luma_bins.hpp's kLumaCounters uint64, zeroed by
+// the caller, to which the workgroups add; accum2 may be null
+hipError_t launch_luma_histogram(hipStream_t stream, const double *accum, const double *accum2, uint32_t W, const ResolveRun *runs, uint32_t n_runs,
+                                 uint64_t *counters);
 hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in, int in_stride, double *out, int out_stride,
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,

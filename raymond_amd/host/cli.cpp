@@ -34,11 +34,18 @@
 //                                                                      render unfinished the frame so far, tone-mapped on the GPU, is written to
 //                                                                      PATH_0001.ppm, PATH_0002.ppm, ...; --preview-denoise 1: the fast filter's frame)
 //                                                                    [--progress-tiles 0]   (no TileProgressed snapshot is made or downloaded)
+//                                                                    [--auto-exposure 1 [--auto-exposure-percentile P] [--auto-exposure-target T]]
+//                                                                      (the exposure that puts the P-th part of the luminance histogram, 0.99, at T, 0.8,
+//                                                                       before gamma — rmd_exposure_from_histogram —: for every preview from
+//                                                                       rmd_luminance_histogram_tiles on what it resolves, in place of --preview-exposure, and
+//                                                                       for out.ppm from the final frame's histogram, made on the host; --raw is untouched)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
 //   raymond_cli project in.json dump|json Project::load (core/src/project.rs): flattened scene, or the re-serialised JSON
 //   raymond_cli tilemsg W H               a TileFinished message in the wire form of server/src/protocol.rs
+//   raymond_cli lumahist in.f64 [P T]     the luminance histogram of a --raw frame, made on the host (raymond::luminance_histogram): one line of its 262
+//                                         counters in rmd_luma_histogram's order, one with rmd_exposure_from_histogram's exposure at P (0.99) and T (0.8)
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
 //                                         what a drop-in caller gets: one JSON line with the wall time of render_tiled -> last TileFinished
 //   (render also accepts `project:in.json` as its scene)
@@ -153,6 +160,22 @@ int main(int argc, char **argv) {
 			std::printf("%s\n", message_to_json(msg).c_str());
 			return 0;
 		}
+		if (argc >= 3 && !std::strcmp(argv[1], "lumahist")) {
+			std::ifstream f(argv[2], std::ios::binary | std::ios::ate);
+			if (!f) throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2]);
+			std::vector<Vector3> image((size_t)f.tellg() / sizeof(Vector3));
+			f.seekg(0);
+			f.read(reinterpret_cast<char *>(image.data()), (std::streamsize)(image.size() * sizeof(Vector3)));
+			const rmd_luma_histogram h = luminance_histogram(image);
+			for (uint32_t i = 0; i < RMD_LUMA_BINS; i++) std::printf("%llu ", (unsigned long long)h.bins[i]);
+			std::printf("%llu %llu %llu %llu %llu %llu\n", (unsigned long long)h.below, (unsigned long long)h.above, (unsigned long long)h.zero,
+			            (unsigned long long)h.negative, (unsigned long long)h.not_finite, (unsigned long long)h.pixels);
+			double exposure = 0.0;
+			if (rmd_exposure_from_histogram(&h, argc > 3 ? std::atof(argv[3]) : 0.99, argc > 4 ? std::atof(argv[4]) : 0.8, &exposure) != RMD_OK)
+				throw Error(RMD_ERR_INVALID_ARGUMENT, rmd_last_error(nullptr));
+			std::printf("%.17g\n", exposure);
+			return 0;
+		}
 		if (argc >= 6 && !std::strcmp(argv[1], "tiles")) {
 			for (const rmd_tile_rect &t : generate_tiles(std::atoi(argv[2]), std::atoi(argv[3]), {std::atoi(argv[4]), std::atoi(argv[5])}))
 				std::printf("%u %u %u %u\n", t.left, t.top, t.width, t.height);
@@ -211,6 +234,7 @@ int main(int argc, char **argv) {
 		if (argc >= 8 && !std::strcmp(argv[1], "render")) {
 			const auto t0 = std::chrono::steady_clock::now(); // cli_old/src/main.rs:36
 			std::string what = argv[2], raw, dump_features, preview_prefix;
+			bool auto_exposure = false;
 			Settings st;
 			st.camera_settings.backbuffer_width = std::atoi(argv[3]);
 			st.camera_settings.backbuffer_height = std::atoi(argv[4]);
@@ -253,7 +277,11 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--preview-exposure")) st.preview_exposure = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--preview-gamma")) st.preview_gamma = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--progress-tiles")) st.progress_tiles = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--auto-exposure")) auto_exposure = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--auto-exposure-percentile")) st.auto_exposure_percentile = std::atof(argv[i + 1]); // (render_tiled checks them)
+				else if (!std::strcmp(argv[i], "--auto-exposure-target")) st.auto_exposure_target = std::atof(argv[i + 1]);
 			}
+			st.preview_auto_exposure = auto_exposure && st.preview_every > 0; // (a render without previews: the final frame alone)
 			Scene scene;
 			if (what == "spheres") scene = reflective_spheres();
 			else if (what.rfind("dragon", 0) == 0) scene = gold_dragon_standin(what.size() > 7 ? std::atoi(what.c_str() + 7) : 91);
@@ -283,7 +311,14 @@ int main(int argc, char **argv) {
 				std::ofstream f(dump_features, std::ios::binary);
 				f.write(reinterpret_cast<const char *>(feature_means.data()), (std::streamsize)(feature_means.size() * 8));
 			}
-			write_ppm(argv[7], tone_map(image), W, H); // :161-197
+			double exposure = 1.0; // :165
+			if (auto_exposure) { // the final frame is on the host already: its histogram is made here, with the lines the device's kernel is built from
+				const rmd_luma_histogram hist = luminance_histogram(image);
+				if (rmd_exposure_from_histogram(&hist, st.auto_exposure_percentile, st.auto_exposure_target, &exposure) != RMD_OK)
+					throw Error(RMD_ERR_INVALID_ARGUMENT, rmd_last_error(nullptr));
+				std::printf("auto exposure: %.17g\n", exposure);
+			}
+			write_ppm(argv[7], tone_map(image, exposure), W, H); // :161-197
 			if (!raw.empty()) {
 				std::ofstream f(raw, std::ios::binary);
 				f.write(reinterpret_cast<const char *>(image.data()), (std::streamsize)(image.size() * 24));

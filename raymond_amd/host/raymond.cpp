@@ -2,9 +2,12 @@
 // rmd_render_tiles; nothing here evaluates a ray.
 #include "raymond.hpp"
 
+#include "../csrc/luma_bins.hpp"
+
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -311,7 +314,15 @@ Message preview_message(rmd_context *ctx, const double *fb, const double *fb2, s
 	// the packed bytes arrive in a page-locked block of the pool the tile downloads use, as those do
 	const size_t pixels = pixels_of(rects);
 	std::shared_ptr<void> block = BlockPool::shared()->get(ctx, std::max<size_t>(pixels * 3, 1));
-	check(rmd_resolve_tonemap_tiles(ctx, fb, fb2, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.preview_exposure, st.preview_gamma,
+	double exposure = st.preview_exposure;
+	if (st.preview_auto_exposure) { // the histogram of exactly what the resolve call below takes
+		rmd_luma_histogram hist;
+		check(rmd_luminance_histogram_tiles(ctx, fb, fb2, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), &hist), ctx,
+		      "rmd_luminance_histogram_tiles");
+		check(rmd_exposure_from_histogram(&hist, st.auto_exposure_percentile, st.auto_exposure_target, &exposure), nullptr, "rmd_exposure_from_histogram");
+		pv->exposure = exposure;
+	}
+	check(rmd_resolve_tonemap_tiles(ctx, fb, fb2, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), exposure, st.preview_gamma,
 	                                static_cast<uint8_t *>(block.get())),
 	      ctx, "rmd_resolve_tonemap_tiles");
 	scatter_packed(rects, static_cast<const uint8_t *>(block.get()), pixels * 3, W, H, pv->rgb8);
@@ -836,6 +847,9 @@ std::string check_preview(const Settings &st) {
 		return "preview_denoise renders on one device: the filter's window crosses the tiles that several devices would own";
 	if (st.preview_every > 0 && st.worker_count > 1)
 		return "preview_every > 0 needs worker_count == 1 here: a tile moves from GPU to GPU between passes, so no GPU holds a frame's share";
+	if (st.preview_auto_exposure && st.preview_every == 0) return "preview_auto_exposure needs preview_every > 0 (it sets the exposure of the previews)";
+	if (!(st.auto_exposure_percentile > 0.0 && st.auto_exposure_percentile <= 1.0)) return "auto_exposure_percentile must be finite and in (0, 1]";
+	if (!(st.auto_exposure_target > 0.0 && st.auto_exposure_target < 1.0)) return "auto_exposure_target must be finite and in (0, 1)";
 	return "";
 }
 
@@ -1104,6 +1118,18 @@ std::vector<uint8_t> resolve_tonemap_tiles(rmd_context *ctx, const double *accum
 
 void scatter_tiles(const std::vector<rmd_tile_rect> &rects, const std::vector<uint8_t> &packed, size_t width, size_t height, std::vector<uint8_t> &frame) {
 	scatter_packed(rects, packed.data(), packed.size(), width, height, frame);
+}
+
+rmd_luma_histogram luminance_histogram(const std::vector<Vector3> &image) {
+	static_assert(sizeof(rmd_luma_histogram) == (rmd::kLumaCounters + 1) * 8 && offsetof(rmd_luma_histogram, below) == rmd::kLumaBelow * 8 &&
+	              offsetof(rmd_luma_histogram, not_finite) == rmd::kLumaNotFinite * 8 && offsetof(rmd_luma_histogram, pixels) == rmd::kLumaCounters * 8,
+	              "luma_bins.hpp's counters are the struct's fields in order");
+	uint64_t counters[rmd::kLumaCounters + 1] = {};
+	for (const Vector3 &p : image) counters[rmd::luma_counter(rmd::luma_bits(rmd::luma_of(p[0], p[1], p[2])))]++; // (means: a count of 1)
+	counters[rmd::kLumaCounters] = image.size();
+	rmd_luma_histogram h;
+	std::memcpy(&h, counters, sizeof(h));
+	return h;
 }
 
 std::vector<uint8_t> tone_map(const std::vector<Vector3> &image, double exposure, double gamma) {

@@ -192,6 +192,12 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	bool preview_denoise = false;
 	// false: no TileProgressed message is made and nothing is downloaded for one; an adaptive render's TileFinished messages stay.
 	bool progress_tiles = true;
+	// Automatic exposure for the previews (needs preview_every; false = off): every preview first takes the luminance histogram of exactly the buffers, rects
+	// and counts its rmd_resolve_tonemap_tiles call is about to use (rmd_luminance_histogram_tiles), and the exposure that puts the
+	// auto_exposure_percentile (finite, in (0, 1]) of luminance at auto_exposure_target (finite, in (0, 1)) before gamma — rmd_exposure_from_histogram —
+	// replaces preview_exposure in that call; Preview::exposure carries it.  0.99 and 0.8 are values to start from.
+	bool preview_auto_exposure = false;
+	double auto_exposure_percentile = 0.99, auto_exposure_target = 0.8;
 };
 // What render_tiled refuses in the preview settings (it throws this text as a raymond::Error); empty: nothing.  One policy with raymond_amd/scene.py's
 // Settings.check_preview.
@@ -243,6 +249,7 @@ struct Tile { // core/src/tile.rs:7-14
 struct Preview {
 	std::vector<uint8_t> rgb8;
 	size_t width = 0, height = 0, pass_index = 0, sample_count = 0;
+	std::optional<double> exposure; // settings.preview_auto_exposure: the exposure the frame's histogram asked for and was tone-mapped with; unset when it is off
 };
 struct Message { // src/trace.rs:62-66
 	enum Kind { TileFinished, TileProgressed, FramePreview } kind; // FramePreview: `preview` is set and `tile` is empty
@@ -315,6 +322,11 @@ rmd_tile_rect rect_of(const Tile &tile);
 void place_tile(const Tile &tile, const TileData &data, size_t width, std::vector<Vector3> &frame, double divisor = 1.0);
 // width * height * channels sums divided by the count of the rect their pixel lies in (rect i holds counts[i] samples; 0 / 0 where no rect lies)
 void divide_by_counts(std::vector<double> &sums, size_t width, size_t height, size_t channels, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts);
+
+// The luminance histogram of a host image of radiance means: rmd_luminance_histogram_tiles's counters (the same luminance and binning, read from the
+// header the kernel is built from) with every pixel at a count of 1 — what the final frame's automatic exposure is made from
+// (rmd_exposure_from_histogram; raymond_cli --auto-exposure 1)
+rmd_luma_histogram luminance_histogram(const std::vector<Vector3> &image);
 
 // cli_old/src/main.rs:155-181 on the host: c = (1 - exp(-p * exposure))^(1/gamma); u8 = trunc(c * 255)
 std::vector<uint8_t> tone_map(const std::vector<Vector3> &image, double exposure = 1.0, double gamma = 2.2);

@@ -592,6 +592,65 @@ def scatter_tiles(rects, tiles, width=None, height=None, out=None):
     return out
 
 
+class LumaHistogram:
+    """rmd_luma_histogram as numpy counters: `bins` (256 uint64: bin i holds the luminances in [2^e (1 + m / 4), 2^e (1 + (m + 1) / 4)), e = i // 4 - 32,
+    m = i % 4) and the integers `below`, `above`, `zero`, `negative`, `not_finite`, `pixels`."""
+
+    SIDE = ("below", "above", "zero", "negative", "not_finite", "pixels")
+
+    def __init__(self, bins=None, below=0, above=0, zero=0, negative=0, not_finite=0, pixels=0):
+        self.bins = np.zeros(abi.RMD_LUMA_BINS, dtype=np.uint64) if bins is None else np.array(bins, dtype=np.uint64)
+        if self.bins.shape != (abi.RMD_LUMA_BINS,):
+            raise ValueError("a luminance histogram has %d bins" % abi.RMD_LUMA_BINS)
+        self.below, self.above, self.zero, self.negative, self.not_finite, self.pixels = (int(v) for v in (below, above, zero, negative, not_finite, pixels))
+
+    @staticmethod
+    def from_struct(s):
+        return LumaHistogram(np.ctypeslib.as_array(s.bins).copy(), s.below, s.above, s.zero, s.negative, s.not_finite, s.pixels)
+
+    def to_struct(self):
+        s = abi.LumaHistogram()
+        s.bins[:] = [int(v) for v in self.bins]
+        s.below, s.above, s.zero, s.negative, s.not_finite, s.pixels = self.below, self.above, self.zero, self.negative, self.not_finite, self.pixels
+        return s
+
+    def counters(self):
+        """All 262 integers in the struct's order, as one uint64 array."""
+        return np.concatenate([self.bins, np.array([getattr(self, n) for n in self.SIDE], dtype=np.uint64)])
+
+    def __eq__(self, other):
+        return isinstance(other, LumaHistogram) and np.array_equal(self.counters(), other.counters())
+
+    def __repr__(self):
+        nz = np.flatnonzero(self.bins)
+        return "LumaHistogram(%s, bins %s)" % (", ".join("%s=%d" % (n, getattr(self, n)) for n in self.SIDE), {int(i): int(self.bins[i]) for i in nz})
+
+
+def luminance_histogram(ctx, framebuffer, rects, counts, second=None):
+    """rmd_luminance_histogram_tiles: the luminance histogram of the pixels resolve_tonemap_tiles would resolve with the same arguments -> LumaHistogram."""
+    rects = list(rects)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != len(rects):
+        raise ValueError("one sample count per rect")
+    out = abi.LumaHistogram()
+    ctx.check(ctx.L.rmd_luminance_histogram_tiles(ctx.handle, framebuffer.ptr, None if second is None else second.ptr, framebuffer.width, framebuffer.height,
+                                                  tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), C.byref(out)))
+    return LumaHistogram.from_struct(out)
+
+
+def add_histograms(a, b):
+    """The histogram of two rect lists together from the histograms of each (several devices, each over its own tiles): every counter added — integers,
+    so exact in any order."""
+    return LumaHistogram(a.bins + b.bins, *(getattr(a, n) + getattr(b, n) for n in LumaHistogram.SIDE))
+
+
+def exposure_from_histogram(hist, percentile=0.99, target=0.8):
+    """rmd_exposure_from_histogram: the exposure that puts the histogram's `percentile` of luminance at `target` before gamma (a host function)."""
+    out = C.c_double()
+    _lib.check(_lib.load().rmd_exposure_from_histogram(C.byref(hist.to_struct()), float(percentile), float(target), C.byref(out)))
+    return out.value
+
+
 # ---------------------------------------------------------------- the reference-shaped API
 class Tile:  # core/src/tile.rs:7-14
     def __init__(self, left, top, width, height, sample_count, data, error=None, data_sq=None):
@@ -618,11 +677,12 @@ class Message:  # src/trace.rs:62-66
         return Message("TileProgressed", tile)
 
     @staticmethod
-    def FramePreview(frame, pass_index, sample_count):
+    def FramePreview(frame, pass_index, sample_count, exposure=None):
         """An extension (settings.preview_every): `frame` — the whole (H, W, 3) uint8 frame after pass `pass_index` (counted from 1), every tile
-        tone-mapped at its own sample count; `sample_count`: the samples per pixel of a tile that is still live.  `tile` is None."""
+        tone-mapped at its own sample count; `sample_count`: the samples per pixel of a tile that is still live.  `tile` is None.  `exposure`: with
+        settings.preview_auto_exposure the exposure this frame's histogram asked for and was tone-mapped with; None when the setting is off."""
         m = Message("FramePreview", None)
-        m.frame, m.pass_index, m.sample_count = frame, pass_index, sample_count
+        m.frame, m.pass_index, m.sample_count, m.exposure = frame, pass_index, sample_count, exposure
         return m
 
 
@@ -797,7 +857,10 @@ def render_tiled(scene, settings, devices=(0,)):
     Message.FramePreview follows that pass's TileProgressed messages — each device resolves and tone-maps the tiles of its share with
     rmd_resolve_tonemap_tiles, live ones at the current count and those that finished early at theirs, and the packed tiles are scattered into one
     (H, W, 3) uint8 frame here.  With settings.preview_denoise the frame is rmd_denoise_atrous's (one device; the passes then render with second
-    moments).  With settings.progress_tiles = False no TileProgressed message is made and only converged tiles' pixels are downloaded.
+    moments).  With settings.progress_tiles = False no TileProgressed message is made and only converged tiles' pixels are downloaded.  With
+    settings.preview_auto_exposure every device first histograms the buffers, rects and counts its resolve call is about to use
+    (rmd_luminance_histogram_tiles), the devices' histograms are added and the exposure of the sum (rmd_exposure_from_histogram at
+    auto_exposure_percentile and auto_exposure_target) replaces preview_exposure in that preview, which carries it as `exposure`.
 
     Dual-buffer (settings.denoise_dual, an extension): _render_tiled_dual."""
     settings.check_adaptive()
@@ -864,6 +927,7 @@ def render_tiled(scene, settings, devices=(0,)):
                     # every device resolves the tiles of its share — live ones at `done`, those that finished early at their own counts — and the
                     # packed 8-bit tiles are scattered into one frame here
                     frame = np.zeros((H, W, 3), dtype=np.uint8)
+                    calls = []  # per device with tiles: what its resolve call takes
                     for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
                         rects = [r for r, _ in early[i]] + shares[i]
                         counts = [c for _, c in early[i]] + [done] * len(shares[i])
@@ -873,8 +937,17 @@ def render_tiled(scene, settings, devices=(0,)):
                             denoise_atrous(ctx, fb, fb_sq, rects, counts, filtered_fb, levels=settings.denoise_atrous_levels, k=settings.denoise_atrous_k,
                                            alpha=settings.denoise_alpha)
                             fb, counts = filtered_fb, [1] * len(rects)  # (means)
-                        scatter_tiles(rects, resolve_tonemap_tiles(ctx, fb, rects, counts, settings.preview_exposure, settings.preview_gamma), out=frame)
-                    messages.append(Message.FramePreview(frame, passes, done))
+                        calls.append((ctx, fb, rects, counts))
+                    exposure = None
+                    if settings.preview_auto_exposure:  # one exposure for the frame: the devices' histograms added
+                        hist = LumaHistogram()
+                        for ctx, fb, rects, counts in calls:
+                            hist = add_histograms(hist, luminance_histogram(ctx, fb, rects, counts))
+                        exposure = exposure_from_histogram(hist, settings.auto_exposure_percentile, settings.auto_exposure_target)
+                    for ctx, fb, rects, counts in calls:
+                        scatter_tiles(rects, resolve_tonemap_tiles(ctx, fb, rects, counts, settings.preview_exposure if exposure is None else exposure,
+                                                                   settings.preview_gamma), out=frame)
+                    messages.append(Message.FramePreview(frame, passes, done, exposure))
         for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
             img = fb.download()
             img_sq = fb_sq.download() if settings.denoise else None
@@ -915,7 +988,8 @@ def _render_tiled_dual(scene, settings, devices):
 
     With settings.preview_every > 0 a Message.FramePreview follows the snapshots of every preview_every-th pass that leaves live tiles: the two halves'
     sums added on the device (rmd_resolve_tonemap_tiles with the other half as its second buffer) at n_A + n_B, finished tiles at the counts they
-    finished with; with settings.preview_denoise, rmd_denoise_atrous_dual's frame at those counts, guided when this loop keeps the feature buffers."""
+    finished with; with settings.preview_denoise, rmd_denoise_atrous_dual's frame at those counts, guided when this loop keeps the feature buffers.  With
+    settings.preview_auto_exposure the exposure comes from rmd_luminance_histogram_tiles on what that resolve call takes, as in render_tiled."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     st = settings
@@ -1001,7 +1075,7 @@ def _render_tiled_dual(scene, settings, devices):
                     rects = done_rects + still
                     all_a, all_b = done_a + [n_half[0]] * len(still), done_b + [n_half[1]] * len(still)
                     if preview_fb is None:
-                        packed = resolve_tonemap_tiles(ctx, fbs[0], rects, [a + b for a, b in zip(all_a, all_b)], st.preview_exposure, st.preview_gamma, second=fbs[2])
+                        src, src_counts, second = fbs[0], [a + b for a, b in zip(all_a, all_b)], fbs[2]
                     else:
                         if guided:
                             guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
@@ -1009,8 +1083,14 @@ def _render_tiled_dual(scene, settings, devices):
                         slope = st.atrous_slope_keyword() if guided else {}  # (set: the preview is rmd_denoise_atrous_dual_slope's)
                         denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), rects, all_a, all_b, preview_fb, None, levels=st.denoise_atrous_levels,
                                             k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **slope)
-                        packed = resolve_tonemap_tiles(ctx, preview_fb, rects, [1] * len(rects), st.preview_exposure, st.preview_gamma)  # (means)
-                    messages.append(Message.FramePreview(scatter_tiles(rects, packed, W, H), j, done))
+                        src, src_counts, second = preview_fb, [1] * len(rects), None  # (means)
+                    exposure = None
+                    if st.preview_auto_exposure:
+                        exposure = exposure_from_histogram(luminance_histogram(ctx, src, rects, src_counts, second=second), st.auto_exposure_percentile,
+                                                           st.auto_exposure_target)
+                    packed = resolve_tonemap_tiles(ctx, src, rects, src_counts, st.preview_exposure if exposure is None else exposure, st.preview_gamma,
+                                                   second=second)
+                    messages.append(Message.FramePreview(scatter_tiles(rects, packed, W, H), j, done, exposure))
                 live = still
         finish(live)
         messages = messages + finished  # progress snapshots first, then the finished tiles

@@ -248,7 +248,8 @@ class Settings:
                  denoise_features=False, denoise_feature_k=1.0, denoise_feature_tau=1e-2, denoise_dual=False, adaptive_denoised_threshold=0.0,
                  adaptive_min_samples=32, denoise_dual_features=False, denoise_dual_select=False, denoise_atrous=False,
                  denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False, preview_every=0,
-                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, denoise_feature_slope=0.0,
+                 preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, preview_auto_exposure=False,
+                 auto_exposure_percentile=0.99, auto_exposure_target=0.8, denoise_feature_slope=0.0,
                  denoise_atrous_slope=0.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
@@ -338,6 +339,13 @@ class Settings:
         # False: no TileProgressed message is made and nothing is downloaded for one; an adaptive render's TileFinished messages stay, the data of
         # converged tiles coming through download_tiles of those tiles only.
         self.progress_tiles = bool(progress_tiles)
+        # Automatic exposure for the previews (False = off; needs preview_every): every preview first takes the luminance histogram of exactly the buffers,
+        # rects and counts its rmd_resolve_tonemap_tiles call is about to use (rmd_luminance_histogram_tiles; several devices' histograms are added), and
+        # the exposure that puts the auto_exposure_percentile of luminance at auto_exposure_target before gamma (rmd_exposure_from_histogram) replaces
+        # preview_exposure in that call.  The message carries it as Message.FramePreview's `exposure`.  0.99 and 0.8 are values to start from.
+        self.preview_auto_exposure = bool(preview_auto_exposure)
+        self.auto_exposure_percentile = float(auto_exposure_percentile)
+        self.auto_exposure_target = float(auto_exposure_target)
         self.check_preview()
 
     def select_candidates(self):
@@ -440,6 +448,12 @@ class Settings:
             raise ValueError("preview_denoise needs preview_every > 0 (it selects the filter of the previews)")
         if self.preview_denoise and n_devices != 1:
             raise ValueError("preview_denoise renders on one device: the filter's window crosses the tiles that several devices would own")
+        if self.preview_auto_exposure and self.preview_every == 0:
+            raise ValueError("preview_auto_exposure needs preview_every > 0 (it sets the exposure of the previews)")
+        if not (0.0 < self.auto_exposure_percentile <= 1.0):  # (rmd_exposure_from_histogram's rules; a NaN fails both)
+            raise ValueError("auto_exposure_percentile must be finite and in (0, 1]")
+        if not (0.0 < self.auto_exposure_target < 1.0):
+            raise ValueError("auto_exposure_target must be finite and in (0, 1)")
 
     def pod(self, sample_begin=0, sample_count=None):
         s = abi.Settings()
