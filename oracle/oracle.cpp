@@ -781,19 +781,22 @@ V3 trace(const Ray &ray, TraceContext &ctx, Rng &rng, uint32_t depth) {
 	}
 }
 
+/* The primary ray of one sample, from the sample's own stream: the thin lens where it is asked for and the aperture is open, else the pinhole
+ * ray (render_tiled itself only ever calls the pinhole generator, :199).  `ok` false where the reference's unwrap() would panic. */
+Ray sample_primary_ray(uint32_t x, uint32_t y, const rmd_camera &cam, bool use_dof, Rng &rng, bool &ok) {
+	ok = true;
+	if (use_dof && cam.aperture_radius > 0.0) return generate_primary_ray_with_dof(x, y, cam, rng, ok);
+	return generate_primary_ray(x, y, cam, rng);
+}
+
 /* src/trace.rs:199-200 for one (pixel, sample) */
 V3 sample_pixel(const Scene &scene, const rmd_camera &cam, const rmd_settings &st, uint32_t x, uint32_t y, uint32_t s,
                 int32_t *path_obj = nullptr, uint32_t *path_sub = nullptr, int32_t *path_len = nullptr) {
 	ORC_COUNT(K_SAMPLES, 1);
 	Rng rng(st.seed, y * cam.backbuffer_width + x, s);
-	Ray primary;
-	if ((st.flags & RMD_RENDER_DOF) && cam.aperture_radius > 0.0) { /* render_tiled itself only ever calls the pinhole generator (:199) */
-		bool ok = true;
-		primary = generate_primary_ray_with_dof(x, y, cam, rng, ok);
-		if (!ok) return v3(0.0, 0.0, 0.0);
-	} else {
-		primary = generate_primary_ray(x, y, cam, rng);
-	}
+	bool ok = true;
+	Ray primary = sample_primary_ray(x, y, cam, (st.flags & RMD_RENDER_DOF) != 0u, rng, ok);
+	if (!ok) return v3(0.0, 0.0, 0.0);
 	TraceContext ctx{&scene, &cam, st.bounce_limit, path_obj, path_sub, 0};
 	V3 out = trace(primary, ctx, rng, mut(MUT_Q14_ONE_MORE_SEGMENT) ? 0 : 1);
 	if (path_len) *path_len = ctx.path_len;
@@ -1100,6 +1103,19 @@ void orc_grid_intersect(const orc_scene *s, uint32_t g, size_t n, const double *
 	for (size_t i = 0; i < n; i++) {
 		Hit h = grid_intersects(*s->scene.grids[g], ray_from(ray6 + 6 * i));
 		hit[i] = h.some, t[i] = h.distance, tri[i] = (uint32_t)h.subobject_index;
+	}
+}
+
+void orc_sample_primary_rays(const rmd_camera *cam, uint64_t seed, int32_t use_dof, size_t n, const uint32_t *xy2,
+                             const uint32_t *sample, double *ray6, int32_t *ok) {
+	for (size_t i = 0; i < n; i++) {
+		const uint32_t x = xy2[2 * i], y = xy2[2 * i + 1];
+		Rng rng(seed, y * cam->backbuffer_width + x, sample[i]); /* sample_pixel's stream */
+		bool good = true;
+		Ray r = sample_primary_ray(x, y, *cam, use_dof != 0, rng, good);
+		if (!good) r = Ray{v3(0.0, 0.0, 0.0), v3(0.0, 0.0, 0.0)};
+		v3_store(ray6 + 6 * i, r.origin), v3_store(ray6 + 6 * i + 3, r.direction);
+		ok[i] = good ? 1 : 0;
 	}
 }
 

@@ -97,6 +97,11 @@ void orc_grid_intersect(const orc_scene *s, uint32_t g, size_t n, const double *
  * RMD_MAX_BOUNCE_LIMIT+1 entries of (object index or -1, triangle index) per depth reached; returns depth count. */
 int32_t orc_trace_sample(const orc_scene *s, const rmd_camera *cam, const rmd_settings *st, uint32_t x, uint32_t y,
                          uint32_t sample, double rgb[3], int32_t *path_obj, uint32_t *path_sub);
+/* The primary ray of each (xy[2i], xy[2i+1], sample[i]) exactly as orc_trace_sample takes it: the sample's own stream Rng(seed, y*W + x, sample),
+ * generate_primary_ray, or generate_primary_ray_with_dof where use_dof != 0 and cam->aperture_radius > 0 (what RMD_RENDER_DOF selects there).
+ * ok[i] = 0 where the reference's unwrap() of the focal-plane hit would panic (the sample is then (0, 0, 0) with an empty path; ray6 is six zeros). */
+void orc_sample_primary_rays(const rmd_camera *cam, uint64_t seed, int32_t use_dof, size_t n, const uint32_t *xy2,
+                             const uint32_t *sample, double *ray6, int32_t *ok);
 /* Batched: rgb_out[3*i] for (xy[2i], xy[2i+1], sample[i]). */
 void orc_trace_samples(const orc_scene *s, const rmd_camera *cam, const rmd_settings *st, size_t n,
                        const uint32_t *xy2, const uint32_t *sample, double *rgb_out);

@@ -43,6 +43,7 @@ _SIGS = {
     "orc_scene_intersect": (None, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "orc_grid_intersect": (None, [_vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp]),
     "orc_trace_sample": (C.c_int32, [_vp, _P(abi.Camera), _P(abi.Settings), C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "orc_sample_primary_rays": (None, [_P(abi.Camera), C.c_uint64, C.c_int32, _sz, _vp, _vp, _vp, _vp]),
     "orc_trace_samples": (None, [_vp, _P(abi.Camera), _P(abi.Settings), _sz, _vp, _vp, _vp]),
     "orc_render_tiles": (None, [_vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, _vp, C.c_uint32]),
     "orc_mesh_load_ply": (C.c_int32, [C.c_char_p, _P(_vp)]),
@@ -226,6 +227,18 @@ def block_uniforms(seed, pixel, sample, block):
         lib.orc_block_uniforms(seed, int(p), int(s), int(b), ptr(row))
         out[i] = row
     return out
+
+
+def sample_primary_rays(cam, seed, use_dof, xy, samples):
+    """-> rays (n, 6), ok (n,) int32: the primary ray of each (x, y, sample) as orc_trace_sample takes it, the thin lens included; ok == 0 where
+    the reference would panic (the ray is then six zeros)"""
+    xy = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+    samples = np.ascontiguousarray(samples, dtype=np.uint32)
+    assert samples.shape == (xy.shape[0],)
+    rays, ok = np.zeros((xy.shape[0], 6)), np.zeros(xy.shape[0], dtype=np.int32)
+    c = cam.pod()
+    load().orc_sample_primary_rays(C.byref(c), int(seed), int(bool(use_dof)), xy.shape[0], ptr(xy), ptr(samples), ptr(rays), ptr(ok))
+    return rays, ok
 
 
 def counters():
