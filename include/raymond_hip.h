@@ -60,7 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles,
+	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
@@ -907,6 +907,43 @@ rmd_status rmd_luminance_histogram_tiles(rmd_context *ctx, const double *accum_d
  * RMD_ERR_INVALID_ARGUMENT (text through rmd_last_error(NULL)): h or out_exposure NULL; percentile not finite or outside (0, 1]; target not finite or
  * outside (0, 1). */
 rmd_status rmd_exposure_from_histogram(const rmd_luma_histogram *h, double percentile, double target, double *out_exposure);
+/*
+ * FIREFLY REJECTION from the moments, the stage in front of the filters and of rmd_tile_error (an addition within ABI 6: RMD_ABI_VERSION stays 6, no
+ * struct changes, found by its symbol).  A pixel far brighter than all but `rank` of its neighbours — measured in the NEIGHBOUR's standard error,
+ * never its own: a firefly's own variance is what hides it from the variance-guided filters — takes a neighbour's sums.
+ * S = accum_dev, Q = accum_sq_dev, rects and rect_sample_counts mean what they mean in rmd_denoise: n_i is the count of the rect that covers pixel i, 0 if
+ * no rect covers it;
+ *     u_ic = S_ic / n_i;   v_ic = max(0, (Q_ic - S_ic*u_ic) / (n_i - 1)) / n_i;   pixel i is VALID if n_i >= 2 and its six sums are finite
+ *     Y_i = (0.2126 * u_i0 + 0.7152 * u_i1) + 0.0722 * u_i2           (rmd_luminance_histogram_tiles's luminance)
+ *     V_i = (A0 * v_i0 + A1 * v_i1) + A2 * v_i2                       A_c = the binary64 product of the weight with itself
+ * every product rounded, the additions as bracketed, nothing fused.
+ * The OTHERS of a valid p are the pixels q = p + d with |d_x|, |d_y| <= radius and d != 0 that are inside the frame (not clamped) and valid, ordered by Y
+ * descending, ties by the raster order of d (d_y ascending, then d_x ascending).  The DONOR q* is the element at 0-based index `rank`; a p with fewer than
+ * rank + 1 others is unchanged.  With
+ *     e = (Y_p - ratio * Y_q*) - floor
+ * p is a SPIKE if e > 0 and e * e > (k * k) * V_q*.  No square root is taken; a NaN or an infinity in V decides by the IEEE comparisons, so a NaN makes no
+ * spike.  Only the donor's variance enters.
+ * Output (out_accum_dev = S', out_accum_sq_dev = Q'): a pixel that is not a spike — one that is not valid or that no rect covers included — is a bit copy
+ * of its six input values; a spike with n_p == n_q* is a bit copy of the donor's six values; a spike with another count gets
+ *     S'_pc = (S_q*c / n_q*) * n_p,   Q'_pc = (Q_q*c / n_q*) * n_p       (the donor's per-sample moments at p's own count)
+ * Every decision reads the INPUT only: a replaced pixel is never a donor's stand-in, and nothing cascades.  replaced_host (a HOST array of n_rects words,
+ * may be NULL): replaced_host[j] = the number of spikes in rect j, an exact integer.  Both outputs keep the rects' counts: rmd_tile_error, every
+ * rmd_denoise*, rmd_resolve_tonemap[_tiles] and rmd_luminance_histogram_tiles take them in place of S and Q unchanged.
+ * What the rank means, three consequences:
+ *   - `rank` is how many brighter others a pixel may have and still be a spike;
+ *   - a run of m bright pixels inside one window survives only if rank < m - 1 (a one-pixel-wide line survives radius 2 with rank 2 — five of it in a
+ *     window — and is erased at radius 1 with rank 2);
+ *   - the call removes energy, so it is BIASED: the frame's mean goes down by what the spikes held above their donors.
+ * RMD_ERR_INVALID_ARGUMENT, all checked before the device is touched, in this order: rmd_denoise's frame and rect rules (width, height > 0; rects and
+ * rect_sample_counts non-NULL when n_rects > 0; every rect inside the frame, no two overlapping); 1 <= radius <= 3; rank <= (2 * radius + 1)^2 - 2; k finite
+ * and >= 0, ratio finite and >= 1, floor finite and >= 0; the four buffers non-NULL and no two of the four W*H*3-double ranges overlapping; and only then a
+ * NULL context.  Synchronous, like rmd_denoise; the call's device scratch (two W*H-word images, the rects and the counters) stays on the context and grows
+ * on demand.  Values to start from (not tuned): radius 2, rank 2, k 6, ratio 2, floor 0.
+ */
+rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                       const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
+                       uint32_t radius, uint32_t rank, double k, double ratio, double floor,
+                       double *out_accum_dev, double *out_accum_sq_dev, uint32_t *replaced_host /* n_rects, may be NULL */);
 
 /* ---- multi-GPU (no reference counterpart; the reference has no collectives) ---- */
 #define RMD_COMM_ID_BYTES 128

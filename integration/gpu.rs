@@ -164,6 +164,11 @@ extern "C" {
     fn rmd_luminance_histogram_tiles(ctx: *mut rmd_context, accum_dev: *const f64, accum2_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                                      rect_sample_counts: *const u32, n_rects: u32, out_host: *mut rmd_luma_histogram) -> i32;
     fn rmd_exposure_from_histogram(h: *const rmd_luma_histogram, percentile: f64, target: f64, out_exposure: *mut f64) -> i32;
+    // firefly rejection from the moments, in front of the filters and of rmd_tile_error (settings.despike of the C++ mirror): out_accum_dev / out_accum_sq_dev
+    // take the place of the raw sums in every other call, at the same rects and counts; replaced_host (n_rects u32) may be null
+    fn rmd_despike(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                   rect_sample_counts: *const u32, n_rects: u32, radius: u32, rank: u32, k: f64, ratio: f64, floor: f64, out_accum_dev: *mut f64,
+                   out_accum_sq_dev: *mut f64, replaced_host: *mut u32) -> i32;
 }
 
 /// One candidate of rmd_denoise_dual_select (include/raymond_hip.h: rmd_denoise_candidate); `reserved` is 0

@@ -132,6 +132,8 @@ DENOISE_MAX_CANDIDATES = 4  # RMD_DENOISE_MAX_CANDIDATES
 
 RMD_LUMA_BINS = 256  # rmd_luma_histogram: four bins an octave over 2^-32 .. 2^32
 
+DESPIKE_MAX_RADIUS = 3  # rmd_despike: 1 <= radius <= 3, rank <= (2 * radius + 1)^2 - 2
+
 
 class LumaHistogram(C.Structure):  # rmd_luma_histogram
     _fields_ = [

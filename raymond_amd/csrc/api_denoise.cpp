@@ -4,6 +4,7 @@
 #define RMD_WITH_HIP 1
 #include <initializer_list>
 
+#include "despike_rule.hpp"
 #include "internal.hpp"
 #include "launch.hpp"
 
@@ -446,6 +447,36 @@ rmd_status rmd_denoise_atrous_dual_slope_region(rmd_context *ctx, const double *
 	const DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, feat_dev, feat_sq_dev, width, height, rects, rect_counts_a, rect_counts_b,
 	                                   rect_counts_f, n_rects);
 	return denoise_dual("rmd_denoise_atrous_dual_slope_region", true, ctx, in, region, n_region, &levels, 0u, 0u, {k, alpha, k_f, tau, slope}, out_dev, err_dev);
+}
+
+// rmd_despike (despike.hip).  Its refusals in the header's order: the frame and the rects first, the buffers after the parameters, the context last
+rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                       const uint32_t *rect_sample_counts, uint32_t n_rects, uint32_t radius, uint32_t rank, double k, double ratio, double floor,
+                       double *out_accum_dev, double *out_accum_sq_dev, uint32_t *replaced_host) {
+	const std::string name = "rmd_despike: ";
+	return rmd::guarded(ctx, "rmd_despike", [&] {
+		if (width == 0 || height == 0 || (n_rects && (!rects || !rect_sample_counts))) return fail(ctx, kInvalid, name + "bad argument");
+		if (rmd_status s = check_rects(ctx, name, rects, n_rects, width, height)) return s;
+		if (radius < 1u || radius > rmd::kDespikeMaxRadius) return fail(ctx, kInvalid, name + "radius must be 1 .. 3");
+		if (rank > (2u * radius + 1u) * (2u * radius + 1u) - 2u) return fail(ctx, kInvalid, name + "rank must be <= (2 * radius + 1)^2 - 2");
+		if (!(k >= 0.0) || !std::isfinite(k)) return fail(ctx, kInvalid, name + "k must be finite and >= 0");
+		if (!(ratio >= 1.0) || !std::isfinite(ratio)) return fail(ctx, kInvalid, name + "ratio must be finite and >= 1");
+		if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(ctx, kInvalid, name + "floor must be finite and >= 0");
+		if (!accum_dev || !accum_sq_dev || !out_accum_dev || !out_accum_sq_dev) return fail(ctx, kInvalid, name + "the four sum buffers must not be NULL");
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		if (any_overlap({{accum_dev, bytes}, {accum_sq_dev, bytes}, {out_accum_dev, bytes}, {out_accum_sq_dev, bytes}}))
+			return fail(ctx, kInvalid, name + "accum_dev, accum_sq_dev, out_accum_dev and out_accum_sq_dev must not alias");
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		DenoiseInput in = single_input(accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_sample_counts, n_rects);
+		Scratch sc; // (the context's block: kept between calls)
+		if (rmd_status s = sc.carve(ctx, rmd::despike_scratch_layout(width, height, n_rects), &ctx->despike_scratch)) return s;
+		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
+		uint32_t *d_replaced = replaced_host && n_rects ? sc.part<uint32_t>(rmd::kPartTileErrors) : nullptr;
+		RMD_HIP(ctx, rmd::launch_despike(ctx->stream, in, radius, rank, k, ratio, floor, sc.part<uint32_t>(rmd::kPartCountImg), sc.part<uint32_t>(rmd::kPartWinImg),
+		                                 out_accum_dev, out_accum_sq_dev, d_replaced));
+		if (d_replaced) RMD_HIP(ctx, hipMemcpyAsync(replaced_host, d_replaced, (size_t)n_rects * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		return finish(ctx);
+	});
 }
 
 rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,

@@ -94,6 +94,21 @@ inline ScratchLayout denoise_scratch_layout(ScratchForm form, uint32_t W, uint32
 	return L;
 }
 
+// rmd_despike's block, in the parts' existing names: kPartCountImg the per-pixel counts, kPartWinImg the per-pixel rect index (W*H uint32 each),
+// kPartRects and kPartCountsA the rects and their counts, kPartTileErrors the per-rect spike counters (n_rects uint32).  Not one of the forms above: no
+// filter's block changes, and the probe of those layouts does not list it
+inline ScratchLayout despike_scratch_layout(uint32_t W, uint32_t H, uint32_t n_rects) {
+	ScratchLayout L;
+	const size_t N = (size_t)W * H, u32 = sizeof(uint32_t);
+	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
+		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
+		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
+	};
+	part(kPartCountImg, u32, N), part(kPartWinImg, u32, N);
+	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, u32, n_rects), part(kPartTileErrors, u32, n_rects);
+	return L;
+}
+
 // ---------------------------------------------------------------- the block tables of the region forms
 // rmd_denoise_dual_region: each region rect cut into tiles of the kernel's own shape (tw x th) from the rect's corner, row by row
 inline std::vector<DualBlock> dual_region_table(const rmd_tile_rect *region, uint32_t n_region, uint32_t tw, uint32_t th) {

@@ -213,6 +213,12 @@ hipError_t launch_resolve_tiles(hipStream_t stream, const double *accum, const d
 // the caller, to which the workgroups add; accum2 may be null
 hipError_t launch_luma_histogram(hipStream_t stream, const double *accum, const double *accum2, uint32_t W, const ResolveRun *runs, uint32_t n_runs,
                                  uint64_t *counters);
+// rmd_despike (despike.hip): out_accum / out_accum_sq = the frame's sums with every spike replaced by its donor (despike_rule.hpp has the rule); only
+// in.accum_a / in.accum_sq_a, the rects and counts_a are read.  Scratch: n_img W*H uint32 for the per-pixel counts, rect_img W*H uint32 for the per-pixel
+// rect index, `replaced` in.n_rects uint32 to which the workgroups add each rect's spikes (zeroed here).  replaced null: nothing is counted and rect_img is
+// not read (may be null).  radius is 1 .. 3; the other arguments are checked by the caller
+hipError_t launch_despike(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t rank, double k, double ratio, double floor, uint32_t *n_img,
+                          uint32_t *rect_img, double *out_accum, double *out_accum_sq, uint32_t *replaced);
 hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in, int in_stride, double *out, int out_stride,
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,

@@ -39,6 +39,10 @@
 //                                                                       before gamma — rmd_exposure_from_histogram —: for every preview from
 //                                                                       rmd_luminance_histogram_tiles on what it resolves, in place of --preview-exposure, and
 //                                                                       for out.ppm from the final frame's histogram, made on the host; --raw is untouched)
+//                                                                    [--despike 1 [--despike-radius R] [--despike-rank N] [--despike-k K] [--despike-ratio Q]
+//                                                                     [--despike-floor F]]   (firefly rejection, rmd_despike at 2, 2, 6, 2, 0, in front of
+//                                                                      the plain divide or of whichever --denoise filter is on, and of the --adaptive check;
+//                                                                      not with --denoise-dual)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -46,6 +50,10 @@
 //   raymond_cli tilemsg W H               a TileFinished message in the wire form of server/src/protocol.rs
 //   raymond_cli lumahist in.f64 [P T]     the luminance histogram of a --raw frame, made on the host (raymond::luminance_histogram): one line of its 262
 //                                         counters in rmd_luma_histogram's order, one with rmd_exposure_from_histogram's exposure at P (0.99) and T (0.8)
+//   raymond_cli despike S.f64 Q.f64 W H rects.txt R N K Q F outS.f64 outQ.f64
+//                                         rmd_despike made on the host (raymond::despike_host, from the header the kernel is built from) over raw W*H*3 f64
+//                                         sums and sums of squares; rects.txt: one "left top width height count" per line; K, Q and F are read as C99
+//                                         hexadecimal or decimal doubles; prints one line of the spikes per rect
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
 //                                         what a drop-in caller gets: one JSON line with the wall time of render_tiled -> last TileFinished
 //   (render also accepts `project:in.json` as its scene)
@@ -104,6 +112,10 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 		return den;
 	}
 	if (finished_out) *finished_out = finished_tiles; // (views: cheap)
+	if (st.despike && !finished_tiles.empty()) { // await()'s plain path with the setting on: the divide of the despiked sums
+		handle.await();
+		return despike_tiles(finished_tiles, st, 0);
+	}
 	std::vector<Vector3> image(W * H, Vector3{0, 0, 0});
 	for (const Tile &t : finished_tiles) place_tile(t, t.data, W, image, (double)t.sample_count); // :95
 	handle.await(); // waits for the workers to leave (they free their device memory after their last message); rethrows a worker's error
@@ -174,6 +186,34 @@ int main(int argc, char **argv) {
 			if (rmd_exposure_from_histogram(&h, argc > 3 ? std::atof(argv[3]) : 0.99, argc > 4 ? std::atof(argv[4]) : 0.8, &exposure) != RMD_OK)
 				throw Error(RMD_ERR_INVALID_ARGUMENT, rmd_last_error(nullptr));
 			std::printf("%.17g\n", exposure);
+			return 0;
+		}
+		if (argc >= 14 && !std::strcmp(argv[1], "despike")) {
+			const size_t W = (size_t)std::atoll(argv[4]), H = (size_t)std::atoll(argv[5]);
+			std::vector<Vector3> sums(W * H), sums_sq(W * H), out, out_sq;
+			for (int i = 0; i < 2; i++) {
+				std::ifstream f(argv[2 + i], std::ios::binary);
+				std::vector<Vector3> &dst = i ? sums_sq : sums;
+				if (!f || !f.read(reinterpret_cast<char *>(dst.data()), (std::streamsize)(dst.size() * sizeof(Vector3))))
+					throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2 + i]);
+			}
+			std::vector<rmd_tile_rect> rects;
+			std::vector<uint32_t> counts;
+			std::ifstream rf(argv[6]);
+			for (rmd_tile_rect r; rf >> r.left >> r.top >> r.width >> r.height;) {
+				uint32_t n = 0;
+				rf >> n;
+				rects.push_back(r), counts.push_back(n);
+			}
+			const std::vector<uint32_t> replaced = despike_host(sums, sums_sq, W, H, rects, counts, (uint32_t)std::atoi(argv[7]), (uint32_t)std::atoi(argv[8]), std::strtod(argv[9], nullptr),
+			                                                    std::strtod(argv[10], nullptr), std::strtod(argv[11], nullptr), out, out_sq);
+			for (int i = 0; i < 2; i++) {
+				std::ofstream f(argv[12 + i], std::ios::binary);
+				const std::vector<Vector3> &src = i ? out_sq : out;
+				f.write(reinterpret_cast<const char *>(src.data()), (std::streamsize)(src.size() * sizeof(Vector3)));
+			}
+			for (uint32_t n : replaced) std::printf("%u ", n);
+			std::printf("\n");
 			return 0;
 		}
 		if (argc >= 6 && !std::strcmp(argv[1], "tiles")) {
@@ -280,6 +320,12 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--auto-exposure")) auto_exposure = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--auto-exposure-percentile")) st.auto_exposure_percentile = std::atof(argv[i + 1]); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--auto-exposure-target")) st.auto_exposure_target = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--despike")) st.despike = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--despike-radius")) st.despike_radius = (uint32_t)std::atoi(argv[i + 1]); // (render_tiled checks them)
+				else if (!std::strcmp(argv[i], "--despike-rank")) st.despike_rank = (uint32_t)std::atoi(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--despike-k")) st.despike_k = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--despike-ratio")) st.despike_ratio = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--despike-floor")) st.despike_floor = std::atof(argv[i + 1]);
 			}
 			st.preview_auto_exposure = auto_exposure && st.preview_every > 0; // (a render without previews: the final frame alone)
 			Scene scene;

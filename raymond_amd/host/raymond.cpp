@@ -2,6 +2,7 @@
 // rmd_render_tiles; nothing here evaluates a ray.
 #include "raymond.hpp"
 
+#include "../csrc/despike_rule.hpp"
 #include "../csrc/luma_bins.hpp"
 
 #include <algorithm>
@@ -429,9 +430,13 @@ struct TileWorker : Worker {
 	const size_t workers, batch;
 	// previews (one worker: render_tiled): every batch is then one pass over all live tiles, which all hold the same count
 	const bool preview, preview_filtered, adaptive, moments;
+	const bool despike_check; // settings.despike in an adaptive render (one worker: check_settings): the check reads despiked copies of the sums
 	const size_t step;
-	Frame fb, fb_sq;    // fb_sq: the sums of squares of an adaptive or denoised render
+	Frame fb, fb_sq;    // fb_sq: the sums of squares of an adaptive, denoised or despiked render
 	Frame fb_preview;   // settings.preview_denoise: the filtered means of a preview
+	Frame fb_spare, fb_spare_sq; // despike_check: rmd_despike's outputs, which rmd_tile_error reads; fb and fb_sq stay raw
+	std::vector<rmd_tile_rect> converged_rects; // despike_check: the tiles that finished early and the counts they finished with
+	std::vector<uint32_t> converged_counts;
 	std::shared_ptr<BlockPool> pool = BlockPool::shared(); // process-wide: page-locking 50 MB costs about as much as moving them
 	std::vector<rmd_tile_rect> early_rects; // previews: the tiles that finished early and the counts they finished with
 	std::vector<uint32_t> early_counts;
@@ -449,8 +454,9 @@ struct TileWorker : Worker {
 
 	TileWorker(TaskHandle::Shared &sh, int device, int me, size_t workers, const Scene &scene, const Settings &st, size_t batch)
 	    : Worker(sh, device, scene, st), me(me), workers(workers), batch(batch), preview(st.preview_every > 0), preview_filtered(preview && st.preview_denoise),
-	      adaptive(st.adaptive_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered),
-	      step(st.samples_per_iteration ? st.samples_per_iteration : st.sample_count), fb(frame()), fb_sq(frame(moments)), fb_preview(frame(preview_filtered)) {}
+	      adaptive(st.adaptive_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered || st.despike), despike_check(st.despike && adaptive),
+	      step(st.samples_per_iteration ? st.samples_per_iteration : st.sample_count), fb(frame()), fb_sq(frame(moments)), fb_preview(frame(preview_filtered)),
+	      fb_spare(frame(despike_check)), fb_spare_sq(frame(despike_check)) {}
 
 	void run() {
 		for (;;) {
@@ -545,13 +551,27 @@ struct TileWorker : Worker {
 		std::map<size_t, std::vector<size_t>> live;
 		for (size_t i = 0; i < mine.size(); i++)
 			if (mine[i].sample_count < st.sample_count) live[mine[i].sample_count].push_back(i);
+		const double *s = fb, *s_sq = fb_sq;
+		if (despike_check && !live.empty()) {
+			// one worker: the batch is every tile that has not finished.  All tiles at their current counts go through rmd_despike into the spare buffers
+			std::vector<rmd_tile_rect> rects(converged_rects);
+			std::vector<uint32_t> counts(converged_counts);
+			for (const Tile &t : mine) rects.push_back(rect_of(t)), counts.push_back((uint32_t)t.sample_count);
+			check(rmd_despike(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.despike_radius, st.despike_rank, st.despike_k,
+			                  st.despike_ratio, st.despike_floor, fb_spare, fb_spare_sq, nullptr),
+			      ctx, "rmd_despike");
+			s = fb_spare, s_sq = fb_spare_sq;
+		}
 		for (auto &grp : live) {
 			const std::vector<rmd_tile_rect> rects = rects_of(mine, grp.second);
 			std::vector<double> err(rects.size());
-			check(rmd_tile_error(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, (uint32_t)grp.first, st.adaptive_floor, rects.data(), (uint32_t)rects.size(), err.data()), ctx,
+			check(rmd_tile_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, (uint32_t)grp.first, st.adaptive_floor, rects.data(), (uint32_t)rects.size(), err.data()), ctx,
 			      "rmd_tile_error");
 			for (size_t k = 0; k < err.size(); k++) converged[grp.second[k]] = err[k] <= st.adaptive_threshold;
 		}
+		if (despike_check)
+			for (size_t i = 0; i < mine.size(); i++)
+				if (converged[i]) converged_rects.push_back(rect_of(mine[i])), converged_counts.push_back((uint32_t)mine[i].sample_count);
 		return converged;
 	}
 
@@ -587,7 +607,7 @@ struct TileWorker : Worker {
 		std::vector<size_t> want_sq;
 		for (size_t i = 0; i < mine.size(); i++) {
 			if (fate[i].finished || fate[i].progressed || workers > 1) want.push_back(i);
-			if ((moments && !fate[i].finished && workers > 1) || (st.denoise && fate[i].finished)) want_sq.push_back(i);
+			if ((moments && !fate[i].finished && workers > 1) || ((st.denoise || st.despike) && fate[i].finished)) want_sq.push_back(i);
 		}
 		download(fb, mine, want, &Tile::data);
 		download(fb_sq, mine, want_sq, &Tile::data_sq);
@@ -892,6 +912,14 @@ std::string check_settings(const Settings &st) {
 	if (!(st.denoise_atrous_slope >= 0.0) || !std::isfinite(st.denoise_atrous_slope)) return "denoise_atrous_slope must be finite and >= 0 (0 = off)";
 	if (st.denoise_atrous_slope > 0.0 && !((st.denoise_atrous && st.denoise_features) || (st.denoise_dual_atrous && st.denoise_dual_features)))
 		return "denoise_atrous_slope > 0 needs a guided a-trous filter (denoise_atrous with denoise_features, or denoise_dual_atrous with denoise_dual_features)";
+	if (st.despike_radius < 1 || st.despike_radius > rmd::kDespikeMaxRadius) return "despike_radius must be in [1, 3]";
+	if (st.despike_rank > (2 * st.despike_radius + 1) * (2 * st.despike_radius + 1) - 2) return "despike_rank must be in [0, (2 * despike_radius + 1)^2 - 2]";
+	if (!(st.despike_k >= 0.0) || !std::isfinite(st.despike_k)) return "despike_k must be finite and >= 0";
+	if (!(st.despike_ratio >= 1.0) || !std::isfinite(st.despike_ratio)) return "despike_ratio must be finite and >= 1";
+	if (!(st.despike_floor >= 0.0) || !std::isfinite(st.despike_floor)) return "despike_floor must be finite and >= 0";
+	if (st.despike && st.denoise_dual) return "despike cannot be combined with denoise_dual: the halves are not yet despiked";
+	if (st.despike && st.adaptive_threshold > 0.0 && st.worker_count > 1)
+		return "despike with adaptive_threshold renders on one device: the window crosses the tiles that several devices would own";
 	return "";
 }
 } // namespace
@@ -942,11 +970,12 @@ std::vector<Vector3> TaskHandle::await() {
 		Message m = std::move(shared_->channel.front());
 		shared_->channel.pop_front();
 		if (m.kind != Message::TileFinished) break; // :101-103
-		if (settings.denoise) collected.push_back(std::move(m.tile));
+		if (settings.denoise || settings.despike) collected.push_back(std::move(m.tile));
 		else place_tile(m.tile, m.tile.data, cam.backbuffer_width, out, (double)m.tile.sample_count);
 	}
 	lock.unlock();
-	if (!collected.empty()) out = settings.denoise_dual ? denoise_dual_tiles(collected, settings, 0, nullptr, scene_.get()) : denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
+	if (!collected.empty() && !settings.denoise) out = despike_tiles(collected, settings, 0); // (settings.despike alone: the plain divide of the despiked sums)
+	else if (!collected.empty()) out = settings.denoise_dual ? denoise_dual_tiles(collected, settings, 0, nullptr, scene_.get()) : denoise_tiles(collected, settings, 0, scene_.get()); // render_tiled's first GPU
 	return out;
 }
 
@@ -1000,7 +1029,7 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 	}
 	std::vector<Vector3> out(W * H);
 	const Context ctx(device);
-	const Frame dev[3] = {Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H)};
+	Frame dev[3] = {Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H)};
 	Frame fdev[2]; // settings.denoise_features: the feature sums and sums of squares
 	if (settings.denoise_features) {
 		for (Frame &f : fdev) f = Frame(ctx, W, H, Frame::Features);
@@ -1013,6 +1042,13 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 	}
 	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums.data()), dev[0], W * H * 3), ctx, "rmd_framebuffer_upload");
 	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums_sq.data()), dev[1], W * H * 3), ctx, "rmd_framebuffer_upload");
+	if (settings.despike) { // before anything else: every filter below takes the despiked sums in place of the raw ones
+		Frame clean[2] = {Frame(ctx, W, H), Frame(ctx, W, H)};
+		check(rmd_despike(ctx, dev[0], dev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), settings.despike_radius, settings.despike_rank,
+		                  settings.despike_k, settings.despike_ratio, settings.despike_floor, clean[0], clean[1], nullptr),
+		      ctx, "rmd_despike");
+		dev[0] = std::move(clean[0]), dev[1] = std::move(clean[1]);
+	}
 	if (settings.denoise_atrous && settings.denoise_features && settings.denoise_atrous_slope > 0.0)
 		check(rmd_denoise_atrous_slope(ctx, dev[0], dev[1], fdev[0], fdev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(),
 		                               settings.denoise_atrous_levels, settings.denoise_atrous_k, settings.denoise_alpha, settings.denoise_feature_k,
@@ -1035,6 +1071,76 @@ std::vector<Vector3> denoise_tiles(const std::vector<Tile> &tiles, const Setting
 		      ctx, "rmd_denoise_guided");
 	check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(out.data()), W * H * 3), ctx, "rmd_framebuffer_download");
 	return out;
+}
+
+std::vector<Vector3> despike_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device) {
+	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
+	std::vector<Vector3> sums(W * H), sums_sq(W * H);
+	std::vector<rmd_tile_rect> rects;
+	std::vector<uint32_t> counts;
+	for (const Tile &t : tiles) {
+		if (t.data.size() != t.width * t.height || t.data_sq.size() != t.width * t.height)
+			throw Error(RMD_ERR_INVALID_ARGUMENT, "despike_tiles: a tile without its sums and sums of squares");
+		place_tile(t, t.data, W, sums), place_tile(t, t.data_sq, W, sums_sq);
+		rects.push_back(rect_of(t));
+		counts.push_back((uint32_t)t.sample_count);
+	}
+	const Context ctx(device);
+	const Frame dev[4] = {Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H), Frame(ctx, W, H)};
+	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums.data()), dev[0], W * H * 3), ctx, "rmd_framebuffer_upload");
+	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(sums_sq.data()), dev[1], W * H * 3), ctx, "rmd_framebuffer_upload");
+	check(rmd_despike(ctx, dev[0], dev[1], (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), settings.despike_radius, settings.despike_rank,
+	                  settings.despike_k, settings.despike_ratio, settings.despike_floor, dev[2], dev[3], nullptr),
+	      ctx, "rmd_despike");
+	check(rmd_framebuffer_download(ctx, dev[2], reinterpret_cast<double *>(sums.data()), W * H * 3), ctx, "rmd_framebuffer_download");
+	// the plain divide (:93-99): every tile's pixels by its own count; a pixel no finished tile covers stays 0
+	std::vector<Vector3> out(W * H, Vector3{0, 0, 0});
+	for (const Tile &t : tiles)
+		for (size_t y = 0; y < t.height; y++)
+			for (size_t x = 0; x < t.width; x++) {
+				const size_t at = (t.top + y) * W + t.left + x;
+				for (int c = 0; c < 3; c++) out[at][c] = sums[at][c] / (double)t.sample_count;
+			}
+	return out;
+}
+
+std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height, const std::vector<rmd_tile_rect> &rects,
+                                   const std::vector<uint32_t> &counts, uint32_t radius, uint32_t rank, double k, double ratio, double floor,
+                                   std::vector<Vector3> &out_sums, std::vector<Vector3> &out_sums_sq) {
+	if (sums.size() != width * height || sums_sq.size() != width * height || rects.size() != counts.size() || radius < 1 || radius > rmd::kDespikeMaxRadius)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "despike_host: bad argument");
+	const size_t r = radius, AW = width + 2 * r, AH = height + 2 * r;
+	std::vector<uint32_t> n(width * height, 0u), rect_of_pixel(width * height, 0u), replaced(rects.size(), 0u);
+	for (size_t j = 0; j < rects.size(); j++)
+		for (size_t y = rects[j].top; y < (size_t)rects[j].top + rects[j].height; y++)
+			for (size_t x = rects[j].left; x < (size_t)rects[j].left + rects[j].width; x++) n[y * width + x] = counts[j], rect_of_pixel[y * width + x] = (uint32_t)j;
+	// the kernel's apron, for the whole frame at once: Y and V, a NaN Y where there is no other
+	std::vector<double> Y(AW * AH, std::nan("")), V(AW * AH, 0.0);
+	for (size_t y = 0; y < height; y++)
+		for (size_t x = 0; x < width; x++) {
+			double yy, vv;
+			if (rmd::despike_pixel(sums[y * width + x].data(), sums_sq[y * width + x].data(), n[y * width + x], yy, vv)) Y[(y + r) * AW + x + r] = yy, V[(y + r) * AW + x + r] = vv;
+		}
+	out_sums = sums, out_sums_sq = sums_sq;
+	const int side = 2 * (int)radius + 1;
+	for (size_t y = 0; y < height; y++)
+		for (size_t x = 0; x < width; x++) {
+			const size_t centre = (y + r) * AW + x + r, p = y * width + x;
+			const double yp = Y[centre];
+			const double *win = Y.data() + (centre - r * AW - r);
+			if (!(yp == yp) || rmd::despike_settled(rmd::despike_at_or_above(win, (uint32_t)AW, radius, yp), rank, yp)) continue;
+			const int donor = rmd::despike_donor(win, (uint32_t)AW, radius, rank);
+			if (donor < 0) continue;
+			const int dy = donor / side - (int)radius, dx = donor % side - (int)radius;
+			const size_t at = (size_t)((int64_t)centre + dy * (int64_t)AW + dx), q = (size_t)((int64_t)p + dy * (int64_t)width + dx);
+			if (!rmd::despike_is_spike(yp, Y[at], V[at], k, ratio, floor)) continue;
+			replaced[rect_of_pixel[p]]++;
+			for (int c = 0; c < 3; c++) {
+				out_sums[p][c] = n[p] == n[q] ? sums[q][c] : rmd::despike_scaled(sums[q][c], n[q], n[p]);
+				out_sums_sq[p][c] = n[p] == n[q] ? sums_sq[q][c] : rmd::despike_scaled(sums_sq[q][c], n[q], n[p]);
+			}
+		}
+	return replaced;
 }
 
 std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors, const Scene *scene) {

@@ -198,6 +198,16 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// replaces preview_exposure in that call; Preview::exposure carries it.  0.99 and 0.8 are values to start from.
 	bool preview_auto_exposure = false;
 	double auto_exposure_percentile = 0.99, auto_exposure_target = 0.8;
+	// Firefly rejection in front of everything that reads the moments (false = off: no buffer, launch or copy is added).  await() despikes the assembled
+	// sums and sums of squares on its GPU (raymond_hip.h: rmd_despike at despike_radius 1..3, despike_rank <= (2 * radius + 1)^2 - 2, despike_k finite and
+	// >= 0, despike_ratio finite and >= 1, despike_floor finite and >= 0) before the plain divide, denoise, denoise_features or denoise_atrous; the passes then
+	// render with second moments, as for denoise.  The adaptive_threshold check despikes all tiles at their current counts into two spare buffers and runs
+	// rmd_tile_error on those (worker_count == 1 only); the sums the passes add to, every message's data and the previews stay the raw sums.  render_tiled
+	// throws for values out of range whether or not the setting is on, with denoise_dual (the halves are not yet despiked) and with adaptive_threshold on
+	// several workers.  2, 2, 6, 2 and 0 are values to start from.
+	bool despike = false;
+	uint32_t despike_radius = 2, despike_rank = 2;
+	double despike_k = 6.0, despike_ratio = 2.0, despike_floor = 0.0;
 };
 // What render_tiled refuses in the preview settings (it throws this text as a raymond::Error); empty: nothing.  One policy with raymond_amd/scene.py's
 // Settings.check_preview.
@@ -327,6 +337,16 @@ void divide_by_counts(std::vector<double> &sums, size_t width, size_t height, si
 // header the kernel is built from) with every pixel at a count of 1 — what the final frame's automatic exposure is made from
 // (rmd_exposure_from_histogram; raymond_cli --auto-exposure 1)
 rmd_luma_histogram luminance_histogram(const std::vector<Vector3> &image);
+
+// rmd_despike on the host, from the header the kernel is built from (raymond_amd/csrc/despike_rule.hpp): width * height sums and sums of squares in, the
+// despiked ones out (out_sums / out_sums_sq are resized), the spikes per rect returned.  No argument is checked beyond the sizes; rects are inside the
+// frame and disjoint.  What raymond_cli despike runs, and what holds the header to the numpy restatement without a GPU
+std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height, const std::vector<rmd_tile_rect> &rects,
+                                   const std::vector<uint32_t> &counts, uint32_t radius, uint32_t rank, double k, double ratio, double floor,
+                                   std::vector<Vector3> &out_sums, std::vector<Vector3> &out_sums_sq);
+// await() with settings.despike alone: the finished tiles' sums and sums of squares assembled, despiked on `device` (rmd_despike) and divided by each
+// tile's count
+std::vector<Vector3> despike_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device);
 
 // cli_old/src/main.rs:155-181 on the host: c = (1 - exp(-p * exposure))^(1/gamma); u8 = trunc(c * 255)
 std::vector<uint8_t> tone_map(const std::vector<Vector3> &image, double exposure = 1.0, double gamma = 2.2);

@@ -194,6 +194,48 @@ def tile_error(ctx, framebuffer, framebuffer_sq, sample_count, floor, tiles):
     return out[: len(tiles)]
 
 
+def despike(ctx, framebuffer, framebuffer_sq, rects, counts, radius=2, rank=2, k=6.0, ratio=2.0, floor=0.0, out=None, want_replaced=True):
+    """rmd_despike: firefly rejection from the moments.  A pixel whose luminance stands more than `k` standard errors of its DONOR — the other of its
+    (2 * radius + 1)^2 window at 0-based index `rank` by luminance — above `ratio` times the donor's plus `floor` takes the donor's sums, at its own count.
+    Returns (Framebuffer S', Framebuffer Q', replaced): the two new sum buffers (the caller closes them), which every call takes in place of the inputs
+    with the same rects and counts, and the number of pixels replaced in each rect (uint32 array).  `out`: a (Framebuffer, Framebuffer) pair to write into
+    instead of two new ones.  want_replaced=False passes NULL for the counts and returns None for them."""
+    rects = list(rects)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if len(counts) != len(rects):
+        raise ValueError("one sample count per rect")
+    W, H = framebuffer.width, framebuffer.height
+    made = []
+    try:
+        if out is None:
+            made.append(Framebuffer(ctx, W, H))
+            made.append(Framebuffer(ctx, W, H))
+            out = tuple(made)
+        replaced = np.zeros(max(1, len(rects)), dtype=np.uint32) if want_replaced else None
+        ctx.check(ctx.L.rmd_despike(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, W, H, tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                    len(rects), int(radius), int(rank), float(k), float(ratio), float(floor), out[0].ptr, out[1].ptr,
+                                    None if replaced is None else replaced.ctypes.data_as(C.POINTER(C.c_uint32))))
+    except Exception:
+        for b in made:
+            b.close()
+        raise
+    return out[0], out[1], None if replaced is None else replaced[: len(rects)]
+
+
+def despike_arrays(ctx, sums, sums_sq, rects, counts, **params):
+    """despike() for host arrays: (H, W, 3) sums and sums of squares in; the (H, W, 3) despiked sums, sums of squares and the per-rect replaced counts out."""
+    H, W = sums.shape[0], sums.shape[1]
+    bufs = [Framebuffer(ctx, W, H) for _ in range(4)]
+    try:
+        bufs[0].upload(sums)
+        bufs[1].upload(sums_sq)
+        _, _, replaced = despike(ctx, bufs[0], bufs[1], rects, counts, out=(bufs[2], bufs[3]), **params)
+        return bufs[2].download(), bufs[3].download(), replaced
+    finally:
+        for b in bufs:
+            b.close()
+
+
 def denoise(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuffer, radius=10, patch_radius=3, k=0.45, alpha=1.0):
     """rmd_denoise: `out_framebuffer` = the variance-guided non-local means of the frame whose sums are `framebuffer` and sums of squares
     `framebuffer_sq`; rect i of `rects` (left, top, width, height) holds counts[i] samples per pixel.  The result holds means, not sums."""
@@ -721,7 +763,9 @@ class TaskHandle:  # src/trace.rs:70-135
         back through rmd_denoise on `device` — means as well; a pixel that no finished tile covers has n = 0 and comes back as 0 / 0.  With
         settings.denoise_features as well: the scene is uploaded to `device`, the finished tiles' first-hit features are rendered there
         (finished_tile_features) and the filter is rmd_denoise_guided.  With settings.denoise_atrous the filter is rmd_denoise_atrous instead, at
-        denoise_atrous_levels and denoise_atrous_k, guided by the same features when denoise_features is on."""
+        denoise_atrous_levels and denoise_atrous_k, guided by the same features when denoise_features is on.
+        With settings.despike: the assembled sums and sums of squares first go through rmd_despike on `device`, and the plain divide or whichever filter
+        is on takes its outputs in their place."""
         cam = self.settings.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         out = np.zeros(shape, dtype=np.float64)
@@ -734,23 +778,33 @@ class TaskHandle:  # src/trace.rs:70-135
             self.settings.check_denoise()
             if self.scene is None:
                 raise ValueError("settings.denoise_features: this TaskHandle was made without the scene whose features await_() has to render")
-        if denoised:
+        despiked = self.settings.despike
+        if despiked:
+            self.settings.check_despike()
+        if denoised or despiked:
             sums, sums_sq, rects, counts = np.zeros(shape), np.zeros(shape), [], []
         while self._messages:
             m = self._messages.pop(0)
             if m.kind != "TileFinished":
                 break  # the reference stops collecting at the first non-TileFinished message (:101-103)
             t = m.tile
-            if denoised:
+            if denoised or despiked:
                 sums[t.top : t.top + t.height, t.left : t.left + t.width] = t.data
                 sums_sq[t.top : t.top + t.height, t.left : t.left + t.width] = t.data_sq
                 rects.append((t.left, t.top, t.width, t.height))
                 counts.append(t.sample_count)
             else:
                 out[t.top : t.top + t.height, t.left : t.left + t.width] = t.data / float(t.sample_count)
+        if despiked and not denoised:  # the plain divide, of the despiked sums
+            with Context(self.device) as ctx:
+                sums, _, _ = despike_arrays(ctx, sums, sums_sq, rects, counts, want_replaced=False, **self.settings.despike_keywords())
+            for (l, t, w, h), n in zip(rects, counts):
+                out[t : t + h, l : l + w] = sums[t : t + h, l : l + w] / float(n)
         if denoised:
             st = self.settings
             with Context(self.device) as ctx:
+                if despiked:  # before anything else: every filter below takes the despiked sums in place of the raw ones
+                    sums, sums_sq, _ = despike_arrays(ctx, sums, sums_sq, rects, counts, want_replaced=False, **st.despike_keywords())
                 params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
                 if st.denoise_atrous:
                     feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts) if st.denoise_features else (None, None)
@@ -862,15 +916,22 @@ def render_tiled(scene, settings, devices=(0,)):
     (rmd_luminance_histogram_tiles), the devices' histograms are added and the exposure of the sum (rmd_exposure_from_histogram at
     auto_exposure_percentile and auto_exposure_target) replaces preview_exposure in that preview, which carries it as `exposure`.
 
+    Despiked (settings.despike, an extension): the passes render with second moments and every TileFinished tile carries them, as for denoise;
+    TaskHandle.await_() despikes the assembled frame (rmd_despike) before its divide or filter.  With adaptive_threshold the check calls rmd_despike over
+    all tiles — live ones at the current count, those that finished early at theirs — into two spare buffers and rmd_tile_error reads those; the buffers the
+    passes add to, every message's data and the previews stay the raw sums.
+
     Dual-buffer (settings.denoise_dual, an extension): _render_tiled_dual."""
     settings.check_adaptive()
     settings.check_denoise()
     settings.check_preview(len(devices))
+    settings.check_despike(len(devices))
     if settings.denoise_dual:
         return _render_tiled_dual(scene, settings, devices)
     adaptive = settings.adaptive_threshold > 0.0
     preview_filtered = settings.preview_every > 0 and settings.preview_denoise
-    moments = adaptive or settings.denoise or preview_filtered
+    moments = adaptive or settings.denoise or preview_filtered or settings.despike
+    with_sq = settings.denoise or settings.despike  # the finished tiles carry their sums of squares: await_() reads them
     cam = settings.camera_settings
     W, H = cam.backbuffer_width, cam.backbuffer_height
     tiles = generate_tiles(W, H, settings.tile_size)
@@ -879,6 +940,8 @@ def render_tiled(scene, settings, devices=(0,)):
         ctx = Context(d)
         workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H), Framebuffer(ctx, W, H) if moments else None))
     filtered_fb = Framebuffer(workers[0][0], W, H) if preview_filtered else None  # (one device: check_preview)
+    # despike with the adaptive check: two spare buffers for the despiked sums the check reads (one device: check_despike); the passes' own stay raw
+    spare = (Framebuffer(workers[0][0], W, H), Framebuffer(workers[0][0], W, H)) if settings.despike and adaptive else None
     shares = [tiles[i :: len(workers)] for i in range(len(workers))]  # adaptive: the tiles of a share that are still live
     early = [[] for _ in workers]  # previews: per worker, the (rect, sample count) of the tiles that finished early
     step = settings.samples_per_iteration if settings.samples_per_iteration else settings.sample_count
@@ -898,19 +961,24 @@ def render_tiled(scene, settings, devices=(0,)):
             if done < settings.sample_count and settings.samples_per_iteration:
                 for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
                     share = shares[i]
-                    errors = tile_error(ctx, fb, fb_sq, done, settings.adaptive_floor, share) if adaptive and share else [None] * len(share)
+                    if adaptive and share and spare is not None:  # all tiles at their current counts; the error of the live ones on the despiked sums
+                        despike(ctx, fb, fb_sq, [r for r, _ in early[i]] + share, [c for _, c in early[i]] + [done] * len(share), out=spare,
+                                want_replaced=False, **settings.despike_keywords())
+                        errors = tile_error(ctx, spare[0], spare[1], done, settings.adaptive_floor, share)
+                    else:
+                        errors = tile_error(ctx, fb, fb_sq, done, settings.adaptive_floor, share) if adaptive and share else [None] * len(share)
                     if not settings.progress_tiles:  # no snapshots: only the converged tiles' pixels come to the host
                         is_conv = [adaptive and e <= settings.adaptive_threshold for e in errors]
                         conv = [r for r, c in zip(share, is_conv) if c]
                         data = fb.download_tiles(conv) if conv else []
-                        data_sq = fb_sq.download_tiles(conv) if conv and settings.denoise else [None] * len(conv)
+                        data_sq = fb_sq.download_tiles(conv) if conv and with_sq else [None] * len(conv)
                         for (l, t, w, h), e, d, d_sq in zip(conv, [e for e, c in zip(errors, is_conv) if c], data, data_sq):
                             finished.append(Message.TileFinished(Tile(l, t, w, h, done, d.copy(), float(e), None if d_sq is None else d_sq.copy())))
                             early[i].append(((l, t, w, h), done))
                         shares[i] = [r for r, c in zip(share, is_conv) if not c]
                         continue
                     img = fb.download()
-                    img_sq = fb_sq.download() if settings.denoise else None
+                    img_sq = fb_sq.download() if with_sq else None
                     live = []
                     for (l, t, w, h), e in zip(share, errors):
                         tile = Tile(l, t, w, h, done, img[t : t + h, l : l + w].copy(), None if e is None else float(e))
@@ -950,7 +1018,7 @@ def render_tiled(scene, settings, devices=(0,)):
                     messages.append(Message.FramePreview(frame, passes, done, exposure))
         for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
             img = fb.download()
-            img_sq = fb_sq.download() if settings.denoise else None
+            img_sq = fb_sq.download() if with_sq else None
             for (l, t, w, h) in share:
                 sq = None if img_sq is None else img_sq[t : t + h, l : l + w].copy()
                 finished.append(Message.TileFinished(Tile(l, t, w, h, settings.sample_count, img[t : t + h, l : l + w].copy(), data_sq=sq)))
@@ -958,6 +1026,8 @@ def render_tiled(scene, settings, devices=(0,)):
     finally:
         if filtered_fb is not None:
             filtered_fb.close()
+        for b in spare or ():
+            b.close()
         for ctx, ds, fb, fb_sq in workers:
             fb.close()
             if fb_sq is not None:

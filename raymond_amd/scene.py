@@ -250,7 +250,7 @@ class Settings:
                  denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False, preview_every=0,
                  preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, preview_auto_exposure=False,
                  auto_exposure_percentile=0.99, auto_exposure_target=0.8, denoise_feature_slope=0.0,
-                 denoise_atrous_slope=0.0):
+                 denoise_atrous_slope=0.0, despike=False, despike_radius=2, despike_rank=2, despike_k=6.0, despike_ratio=2.0, despike_floor=0.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -347,6 +347,42 @@ class Settings:
         self.auto_exposure_percentile = float(auto_exposure_percentile)
         self.auto_exposure_target = float(auto_exposure_target)
         self.check_preview()
+        # Firefly rejection in front of everything that reads the moments (an extension; False = off: no buffer, launch or copy is added).  await_()
+        # despikes the assembled sums and sums of squares on the first device (raymond_hip.h: rmd_despike, at despike_radius, despike_rank, despike_k,
+        # despike_ratio and despike_floor) before the plain divide, denoise, denoise_features or denoise_atrous; render_tiled then renders with second
+        # moments, as for denoise.  The adaptive_threshold check despikes all tiles at their current counts into two spare buffers and runs rmd_tile_error on
+        # those (one device only); the sums the passes add to, the TileFinished / TileProgressed data and the previews stay the raw sums.  Refused with
+        # denoise_dual: the halves are not yet despiked.  2, 2, 6, 2 and 0 are values to start from.
+        self.despike = bool(despike)
+        self.despike_radius = despike_radius
+        self.despike_rank = despike_rank
+        self.despike_k = float(despike_k)
+        self.despike_ratio = float(despike_ratio)
+        self.despike_floor = float(despike_floor)
+        self.check_despike()
+
+    def despike_keywords(self):
+        """render.despike's parameters from the settings."""
+        return dict(radius=self.despike_radius, rank=self.despike_rank, k=self.despike_k, ratio=self.despike_ratio, floor=self.despike_floor)
+
+    def check_despike(self, n_devices=1):
+        """Raises ValueError for despike settings rmd_despike refuses (checked whether or not despike is on) or render_tiled cannot follow on `n_devices`."""
+        v = self.despike_radius
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= abi.DESPIKE_MAX_RADIUS:
+            raise ValueError("despike_radius must be an integer in [1, %d]" % abi.DESPIKE_MAX_RADIUS)
+        v = self.despike_rank
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= (2 * self.despike_radius + 1) ** 2 - 2:
+            raise ValueError("despike_rank must be an integer in [0, (2 * despike_radius + 1)^2 - 2]")
+        if not (self.despike_k >= 0.0 and np.isfinite(self.despike_k)):
+            raise ValueError("despike_k must be finite and >= 0")
+        if not (self.despike_ratio >= 1.0 and np.isfinite(self.despike_ratio)):
+            raise ValueError("despike_ratio must be finite and >= 1")
+        if not (self.despike_floor >= 0.0 and np.isfinite(self.despike_floor)):
+            raise ValueError("despike_floor must be finite and >= 0")
+        if self.despike and self.denoise_dual:
+            raise ValueError("despike cannot be combined with denoise_dual: the halves are not yet despiked")
+        if self.despike and self.adaptive_threshold > 0.0 and n_devices != 1:
+            raise ValueError("despike with adaptive_threshold renders on one device: the window crosses the tiles that several devices would own")
 
     def select_candidates(self):
         """The candidates of denoise_dual_select, as render.denoise_dual_select takes them: the unguided filter at denoise_k, and the guided one at k = 1.0
