@@ -1,13 +1,21 @@
-"""Host-side mirror of the reference's render API over the C-ABI.
+"""The Python binding of the C-ABI (include/raymond_hip.h), and the reference-shaped render API on top of it.
 
-`render_tiled(scene, settings) -> TaskHandle` keeps the reference's shape (src/trace.rs:137-230,
-TaskHandle :70-135): the framebuffer is split into tiles in the reference's column-major order
-(:142-173), tiles are handed to workers, finished tiles come back as `Message.TileFinished` and
-`TaskHandle.await_()` assembles the W*H image divided by the sample count (:82-113).  The one
-difference is what a worker is: a GPU context that runs rmd_render_tiles over its share of the
-tiles (the per-pixel body :197-205 for ALL pixels of those tiles at once) instead of an OS thread
-looping over pixels.
+Bottom up:
+  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, ErrorImage, WinnerImage —, each a context manager;
+  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], despike, the denoise family (every rmd_denoise* call is laid out
+    by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
+  * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
+  * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
+    into tiles in the reference's column-major order (:142-173), tiles are handed to workers, finished tiles come back as `Message.TileFinished` and
+    `TaskHandle.await_()` assembles the W*H image divided by the sample count (:82-113).  The one difference is what a worker is: a GPU context that
+    runs rmd_render_tiles over its share of the tiles (the per-pixel body :197-205 for ALL pixels of those tiles at once) instead of an OS thread
+    looping over pixels.  The extensions — adaptive sampling, denoising, the dual-buffer loop, previews, despiking — are steps of the two loops
+    (_TiledLoop, _DualLoop), named as the C++ mirror names them; which filter runs for which Settings is decided by Settings.nlm_keywords /
+    atrous_keywords / guide_keywords and _guide, nowhere else.
+
+tests/binding_trace.py pins which C call every function here makes, with which arguments in which order, against a recording stand-in for the library.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -17,7 +25,21 @@ from . import lib as _lib
 from .scene import generate_tiles, tile_array
 
 
-class Context:
+class _Scoped:
+    """`with` for the device objects: close() on the way out.  A failing close is dropped, so that inside an ExitStack it neither keeps the objects
+    opened before it open nor takes the place of the body's own error."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+class Context(_Scoped):
     """rmd_context: one per GPU."""
 
     def __init__(self, device=0, stream=None):
@@ -33,12 +55,6 @@ class Context:
         if self.handle:
             self.L.rmd_context_destroy(self.handle)
             self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def check(self, status):
         _lib.check(status, self.handle)
@@ -62,7 +78,8 @@ class Context:
         self.check(self.L.rmd_context_synchronize(self.handle))
 
     def last_launch_info(self):
-        """rmd_last_launch_info: how the most recent render was launched (passes, split_k, persistent, end_black_paths, has_grid)."""
+        """rmd_last_launch_info: how the most recent render was launched, as an abi.LaunchInfo (passes, split_k, persistent, end_black_paths, has_grid,
+        waves_per_workgroup, buffered, chained, queued)."""
         info = abi.LaunchInfo()
         self.check(self.L.rmd_last_launch_info(self.handle, C.byref(info)))
         return info
@@ -73,7 +90,7 @@ class Context:
         return ms.value
 
 
-class DeviceScene:
+class DeviceScene(_Scoped):
     """rmd_scene: the Scene resident in one GPU's HBM."""
 
     def __init__(self, ctx, scene):
@@ -88,26 +105,53 @@ class DeviceScene:
             self.handle = C.c_void_p()
 
 
-class Framebuffer:
-    """W*H*3 f64 accumulation buffer in HBM (library-allocated, or wrapping a caller's device pointer)."""
+def _ptr(buffer):
+    return None if buffer is None else buffer.ptr
+
+
+def _tile_views(packed, rects, channels=3):
+    """One (h, w, channels) view per rect of a block that holds the rects' pixels packed, tile after tile."""
+    views, at = [], 0
+    for (_, _, w, h) in rects:
+        views.append(packed[at : at + w * h * channels].reshape(h, w, channels))
+        at += w * h * channels
+    return views
+
+
+def _no_tile_transfers(what):
+    def refuse(self, *args):
+        raise NotImplementedError("%s have no tile-rect transfers" % what)
+
+    return refuse
+
+
+class Framebuffer(_Scoped):
+    """W*H*3 f64 accumulation buffer in HBM (library-allocated, or wrapping a caller's device pointer).  Its kinds below differ in `shape`, what
+    download() returns, and in the call that allocates them."""
+
+    ALLOC = "rmd_framebuffer_alloc"
 
     def __init__(self, ctx, width, height, device_ptr=None):
         self.ctx, self.width, self.height = ctx, width, height
-        self.n = width * height * 3
+        self.shape = self._shape()
+        self.n = int(np.prod(self.shape))
         self.owned = device_ptr is None
         if self.owned:
             p = C.c_void_p()
-            ctx.check(ctx.L.rmd_framebuffer_alloc(ctx.handle, width, height, C.byref(p)))
+            ctx.check(getattr(ctx.L, self.ALLOC)(ctx.handle, width, height, C.byref(p)))
             self.ptr = p
         else:
             self.ptr = C.c_void_p(device_ptr)
+
+    def _shape(self):
+        return (self.height, self.width, 3)
 
     def zero(self):
         self.ctx.check(self.ctx.L.rmd_framebuffer_zero(self.ctx.handle, self.ptr, self.n))
 
     def download(self):
-        out = np.empty((self.height, self.width, 3), dtype=np.float64)
-        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
+        out = np.empty(self.shape, dtype=np.float64)
+        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
     def upload(self, arr):
@@ -122,11 +166,7 @@ class Framebuffer:
         n = sum(w * h for (_, _, w, h) in tiles)
         out = np.empty(n * 3, dtype=np.float64)
         self.ctx.check(self.ctx.L.rmd_framebuffer_download_tiles(self.ctx.handle, self.ptr, self.width, self.height, arr, len(tiles), out.ctypes.data_as(C.c_void_p)))
-        views, at = [], 0
-        for (_, _, w, h) in tiles:
-            views.append(out[at : at + w * h * 3].reshape(h, w, 3))
-            at += w * h * 3
-        return views
+        return _tile_views(out, tiles)
 
     def upload_tiles(self, tiles, datas):
         """rmd_framebuffer_upload_tiles: the inverse (datas: one (height, width, 3) array per tile)."""
@@ -142,48 +182,38 @@ class Framebuffer:
 class FeatureBuffer(Framebuffer):
     """W*H*7 f64 first-hit feature sums in HBM (rmd_feature_buffer_alloc): per pixel normal xyz, albedo rgb, depth."""
 
+    ALLOC = "rmd_feature_buffer_alloc"
+    download_tiles = upload_tiles = _no_tile_transfers("feature buffers")
+
     def __init__(self, ctx, width, height):
-        self.ctx, self.width, self.height = ctx, width, height
-        self.n = width * height * abi.RMD_FEATURE_CHANNELS
-        self.owned = True
-        p = C.c_void_p()
-        ctx.check(ctx.L.rmd_feature_buffer_alloc(ctx.handle, width, height, C.byref(p)))
-        self.ptr = p
+        Framebuffer.__init__(self, ctx, width, height)
 
-    def download(self):
-        out = np.empty((self.height, self.width, abi.RMD_FEATURE_CHANNELS), dtype=np.float64)
-        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
-        return out
+    def _shape(self):
+        return (self.height, self.width, abi.RMD_FEATURE_CHANNELS)
 
-    def download_tiles(self, tiles):
-        raise NotImplementedError("feature buffers have no tile-rect transfers")
 
-    def upload_tiles(self, tiles, datas):
-        raise NotImplementedError("feature buffers have no tile-rect transfers")
+def _render_call(ctx, stem, sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, *buffers):
+    """rmd_render_*[_async]: `stem` or its _async form over `tiles` — a list of rects, or a ready (abi.TileRect array, n) pair."""
+    cam = camera_settings.pod()
+    st = settings.pod(sample_begin, sample_count)
+    arr, n = tiles if isinstance(tiles, tuple) and len(tiles) == 2 and hasattr(tiles[0], "_length_") else (tile_array(tiles), len(tiles))
+    fn = getattr(ctx.L, stem if sync else stem + "_async")
+    ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr, n, *buffers))
 
 
 def render_features(ctx, dscene, camera_settings, settings, tiles, features, sample_begin=0, sample_count=None, sync=True, features_sq=None):
     """rmd_render_features[_async]: add the first-hit features (normal, albedo, depth) of `sample_count` samples per pixel of `tiles` into the
     FeatureBuffer `features`, and their squares into `features_sq` when given."""
-    cam = camera_settings.pod()
-    st = settings.pod(sample_begin, sample_count)
-    arr = tiles if isinstance(tiles, tuple) and len(tiles) == 2 and hasattr(tiles[0], "_length_") else (tile_array(tiles), len(tiles))
-    fn = ctx.L.rmd_render_features if sync else ctx.L.rmd_render_features_async
-    ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], features.ptr, None if features_sq is None else features_sq.ptr))
+    _render_call(ctx, "rmd_render_features", sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, features.ptr, _ptr(features_sq))
 
 
 def render_tiles(ctx, dscene, camera_settings, settings, tiles, framebuffer, sample_begin=0, sample_count=None, sync=True, framebuffer_sq=None):
     """rmd_render_tiles[_async]: add `sample_count` samples per pixel of `tiles` into `framebuffer`.  With `framebuffer_sq`:
     rmd_render_tiles_moments[_async], which also adds every sample's square to it."""
-    cam = camera_settings.pod()
-    st = settings.pod(sample_begin, sample_count)
-    arr = tiles if isinstance(tiles, tuple) and len(tiles) == 2 and hasattr(tiles[0], "_length_") else (tile_array(tiles), len(tiles))
     if framebuffer_sq is None:
-        fn = ctx.L.rmd_render_tiles if sync else ctx.L.rmd_render_tiles_async
-        ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], framebuffer.ptr))
+        _render_call(ctx, "rmd_render_tiles", sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, framebuffer.ptr)
     else:
-        fn = ctx.L.rmd_render_tiles_moments if sync else ctx.L.rmd_render_tiles_moments_async
-        ctx.check(fn(ctx.handle, dscene.handle, C.byref(cam), C.byref(st), arr[0], arr[1], framebuffer.ptr, framebuffer_sq.ptr))
+        _render_call(ctx, "rmd_render_tiles_moments", sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, framebuffer.ptr, framebuffer_sq.ptr)
 
 
 def tile_error(ctx, framebuffer, framebuffer_sq, sample_count, floor, tiles):
@@ -194,6 +224,18 @@ def tile_error(ctx, framebuffer, framebuffer_sq, sample_count, floor, tiles):
     return out[: len(tiles)]
 
 
+def _counts(rects, *counts, what="one sample count per rect"):
+    """Each of `counts` as a uint32 array, one per rect."""
+    arrays = [np.ascontiguousarray(c, dtype=np.uint32) for c in counts]
+    if any(len(a) != len(rects) for a in arrays):
+        raise ValueError(what)
+    return arrays
+
+
+def _u32(array):
+    return None if array is None else array.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
 def despike(ctx, framebuffer, framebuffer_sq, rects, counts, radius=2, rank=2, k=6.0, ratio=2.0, floor=0.0, out=None, want_replaced=True):
     """rmd_despike: firefly rejection from the moments.  A pixel whose luminance stands more than `k` standard errors of its DONOR — the other of its
     (2 * radius + 1)^2 window at 0-based index `rank` by luminance — above `ratio` times the donor's plus `floor` takes the donor's sums, at its own count.
@@ -201,64 +243,76 @@ def despike(ctx, framebuffer, framebuffer_sq, rects, counts, radius=2, rank=2, k
     with the same rects and counts, and the number of pixels replaced in each rect (uint32 array).  `out`: a (Framebuffer, Framebuffer) pair to write into
     instead of two new ones.  want_replaced=False passes NULL for the counts and returns None for them."""
     rects = list(rects)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if len(counts) != len(rects):
-        raise ValueError("one sample count per rect")
+    (counts,) = _counts(rects, counts)
     W, H = framebuffer.width, framebuffer.height
-    made = []
-    try:
+    with contextlib.ExitStack() as made:
         if out is None:
-            made.append(Framebuffer(ctx, W, H))
-            made.append(Framebuffer(ctx, W, H))
-            out = tuple(made)
+            out = (made.enter_context(Framebuffer(ctx, W, H)), made.enter_context(Framebuffer(ctx, W, H)))
         replaced = np.zeros(max(1, len(rects)), dtype=np.uint32) if want_replaced else None
-        ctx.check(ctx.L.rmd_despike(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, W, H, tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                    len(rects), int(radius), int(rank), float(k), float(ratio), float(floor), out[0].ptr, out[1].ptr,
-                                    None if replaced is None else replaced.ctypes.data_as(C.POINTER(C.c_uint32))))
-    except Exception:
-        for b in made:
-            b.close()
-        raise
+        ctx.check(ctx.L.rmd_despike(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, W, H, tile_array(rects), _u32(counts), len(rects), int(radius), int(rank),
+                                    float(k), float(ratio), float(floor), out[0].ptr, out[1].ptr, _u32(replaced)))
+        made.pop_all()  # (the call went through: the new buffers are the caller's)
     return out[0], out[1], None if replaced is None else replaced[: len(rects)]
+
+
+def _staged(stack, ctx, like, *buffers):
+    """One device buffer per (kind, host array or None) of `buffers`, of the frame size of the (H, W, ..) array `like`: all allocated, then every array
+    that is given uploaded to its buffer.  `stack` (an ExitStack) closes them."""
+    H, W = like.shape[0], like.shape[1]
+    made = [stack.enter_context(kind(ctx, W, H)) for kind, _ in buffers]
+    for buf, (_, arr) in zip(made, buffers):
+        if arr is not None:
+            buf.upload(arr)
+    return made
 
 
 def despike_arrays(ctx, sums, sums_sq, rects, counts, **params):
     """despike() for host arrays: (H, W, 3) sums and sums of squares in; the (H, W, 3) despiked sums, sums of squares and the per-rect replaced counts out."""
-    H, W = sums.shape[0], sums.shape[1]
-    bufs = [Framebuffer(ctx, W, H) for _ in range(4)]
-    try:
-        bufs[0].upload(sums)
-        bufs[1].upload(sums_sq)
-        _, _, replaced = despike(ctx, bufs[0], bufs[1], rects, counts, out=(bufs[2], bufs[3]), **params)
-        return bufs[2].download(), bufs[3].download(), replaced
-    finally:
-        for b in bufs:
-            b.close()
+    with contextlib.ExitStack() as stack:
+        s, q, s_out, q_out = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq), (Framebuffer, None), (Framebuffer, None))
+        _, _, replaced = despike(ctx, s, q, rects, counts, out=(s_out, q_out), **params)
+        return s_out.download(), q_out.download(), replaced
+
+
+_GUIDED = {"rmd_denoise": "rmd_denoise_guided", "rmd_denoise_dual": "rmd_denoise_dual_guided"}  # the stems whose name says that the features are there
+
+
+def _denoise_call(ctx, stem, sums, rects, counts, params, outputs, features=None, region=None, slope=None, after_slope=()):
+    """One call of the rmd_denoise family.  Every one of its entry points is laid out as
+
+        ctx | sum buffers | [feature buffers] | W, H | rects | counts.. | n_rects | [region rects, n] | parameters [slope] [..] | outputs
+
+    and is named by the groups it has: `stem`, _guided where a stem's features are optional in the header (`features` is the pair of FeatureBuffers, either
+    of which may be None; features=None leaves the group out), _slope for `slope` and _region for `region` (a list of rects, possibly empty).  `sums` and
+    `outputs` are device buffers (an output may be None), `counts` uint32 arrays (the feature counts may be None), `params` and `after_slope` ready C
+    scalars and arrays.  lib.SIGNATURES holds the header's own argument types, so a group out of place does not get past ctypes."""
+    name = (stem if features is None else _GUIDED.get(stem, stem)) + ("" if slope is None else "_slope") + ("" if region is None else "_region")
+    args = [ctx.handle] + [b.ptr for b in sums] + ([] if features is None else [_ptr(b) for b in features])
+    args += [sums[0].width, sums[0].height, tile_array(rects)] + [_u32(c) for c in counts] + [len(rects)]
+    if region is not None:
+        region = list(region)
+        args += [tile_array(region), len(region)]
+    args += list(params) + ([] if slope is None else [slope]) + list(after_slope) + [_ptr(o) for o in outputs]
+    ctx.check(getattr(ctx.L, name)(*args))
+
+
+def _slope(slope):
+    return None if slope is None else float(slope)
 
 
 def denoise(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuffer, radius=10, patch_radius=3, k=0.45, alpha=1.0):
     """rmd_denoise: `out_framebuffer` = the variance-guided non-local means of the frame whose sums are `framebuffer` and sums of squares
     `framebuffer_sq`; rect i of `rects` (left, top, width, height) holds counts[i] samples per pixel.  The result holds means, not sums."""
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if len(counts) != len(rects):
-        raise ValueError("one sample count per rect")
-    ctx.check(ctx.L.rmd_denoise(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(rects),
-                                counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius), int(patch_radius), float(k), float(alpha),
-                                out_framebuffer.ptr))
+    _denoise_call(ctx, "rmd_denoise", (framebuffer, framebuffer_sq), rects, _counts(rects, counts), (int(radius), int(patch_radius), float(k), float(alpha)),
+                  (out_framebuffer,))
 
 
 def denoise_arrays(ctx, sums, sums_sq, rects, counts, **params):
     """denoise() for host arrays: (H, W, 3) sums and sums of squares in, the (H, W, 3) denoised means out."""
-    H, W = sums.shape[0], sums.shape[1]
-    bufs = [Framebuffer(ctx, W, H) for _ in range(3)]
-    try:
-        bufs[0].upload(sums)
-        bufs[1].upload(sums_sq)
-        denoise(ctx, bufs[0], bufs[1], rects, counts, bufs[2], **params)
-        return bufs[2].download()
-    finally:
-        for b in bufs:
-            b.close()
+    with contextlib.ExitStack() as stack:
+        s, q, out = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq), (Framebuffer, None))
+        denoise(ctx, s, q, rects, counts, out, **params)
+        return out.download()
 
 
 def denoise_guided(ctx, framebuffer, framebuffer_sq, features, features_sq, rects, counts, out_framebuffer, radius=10, patch_radius=3, k=0.45, alpha=1.0,
@@ -266,36 +320,25 @@ def denoise_guided(ctx, framebuffer, framebuffer_sq, features, features_sq, rect
     """rmd_denoise_guided: denoise() with the feature weight of the FeatureBuffers `features` / `features_sq` (both None: exactly denoise()).
     `slope` (a number; None: the call above): rmd_denoise_guided_slope, the same with the feature-slope term at that many pixels (0: the same bytes);
     without features it is passed and not read, as the header states."""
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if len(counts) != len(rects):
-        raise ValueError("one sample count per rect")
-    head = (ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr, None if features_sq is None else features_sq.ptr,
-            framebuffer.width, framebuffer.height, tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(radius), int(patch_radius),
-            float(k), float(alpha), float(k_f), float(tau))
-    if slope is None:
-        ctx.check(ctx.L.rmd_denoise_guided(*head, out_framebuffer.ptr))
-    else:
-        ctx.check(ctx.L.rmd_denoise_guided_slope(*head, float(slope), out_framebuffer.ptr))
+    _denoise_call(ctx, "rmd_denoise", (framebuffer, framebuffer_sq), rects, _counts(rects, counts),
+                  (int(radius), int(patch_radius), float(k), float(alpha), float(k_f), float(tau)), (out_framebuffer,), features=(features, features_sq),
+                  slope=_slope(slope))
+
+
+def _staged_guided(stack, ctx, sums, sums_sq, feats, feats_sq):
+    """denoise_guided_arrays' and denoise_atrous_arrays' buffers: sums, sums of squares, the output, then the features; all allocated before any upload."""
+    features = [(FeatureBuffer, feats), (FeatureBuffer, feats_sq)] if feats is not None else []
+    made = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq), (Framebuffer, None), *features)
+    return made + [None] * (5 - len(made))
 
 
 def denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **params):
     """denoise_guided() for host arrays: (H, W, 3) sums and sums of squares and (H, W, 7) feature sums and sums of squares in (the latter two may
     both be None), the (H, W, 3) denoised means out."""
-    H, W = sums.shape[0], sums.shape[1]
-    bufs = [Framebuffer(ctx, W, H) for _ in range(3)]
-    fbufs = [FeatureBuffer(ctx, W, H) for _ in range(2)] if feats is not None else [None, None]
-    try:
-        bufs[0].upload(sums)
-        bufs[1].upload(sums_sq)
-        if feats is not None:
-            fbufs[0].upload(feats)
-            fbufs[1].upload(feats_sq)
-        denoise_guided(ctx, bufs[0], bufs[1], fbufs[0], fbufs[1], rects, counts, bufs[2], **params)
-        return bufs[2].download()
-    finally:
-        for b in bufs + fbufs:
-            if b is not None:
-                b.close()
+    with contextlib.ExitStack() as stack:
+        s, q, out, f, f_sq = _staged_guided(stack, ctx, sums, sums_sq, feats, feats_sq)
+        denoise_guided(ctx, s, q, f, f_sq, rects, counts, out, **params)
+        return out.download()
 
 
 def denoise_atrous(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuffer, levels=5, k=3.0, alpha=1.0, features=None, features_sq=None, k_f=1.0,
@@ -303,55 +346,37 @@ def denoise_atrous(ctx, framebuffer, framebuffer_sq, rects, counts, out_framebuf
     """rmd_denoise_atrous: `out_framebuffer` = the frame after `levels` levels of the edge-avoiding a-trous filter (the fast filter for previews), with
     the feature weight of the FeatureBuffers `features` / `features_sq` when they are given.  The result holds means, not sums.
     `slope` (a number; None: the call above): rmd_denoise_atrous_slope, the same with the feature-slope term at that many pixels (0: the same bytes)."""
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if len(counts) != len(rects):
-        raise ValueError("one sample count per rect")
-    head = (ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, None if features is None else features.ptr, None if features_sq is None else features_sq.ptr,
-            framebuffer.width, framebuffer.height, tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), int(levels), float(k),
-            float(alpha), float(k_f), float(tau))
-    if slope is None:
-        ctx.check(ctx.L.rmd_denoise_atrous(*head, out_framebuffer.ptr))
-    else:
-        ctx.check(ctx.L.rmd_denoise_atrous_slope(*head, float(slope), out_framebuffer.ptr))
+    _denoise_call(ctx, "rmd_denoise_atrous", (framebuffer, framebuffer_sq), rects, _counts(rects, counts),
+                  (int(levels), float(k), float(alpha), float(k_f), float(tau)), (out_framebuffer,), features=(features, features_sq), slope=_slope(slope))
 
 
 def denoise_atrous_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, **params):
     """denoise_atrous() for host arrays: (H, W, 3) sums and sums of squares and (H, W, 7) feature sums and sums of squares in (the latter two may
     both be None), the (H, W, 3) filtered means out."""
-    H, W = sums.shape[0], sums.shape[1]
-    bufs = [Framebuffer(ctx, W, H) for _ in range(3)]
-    fbufs = [FeatureBuffer(ctx, W, H) for _ in range(2)] if feats is not None else [None, None]
-    try:
-        bufs[0].upload(sums)
-        bufs[1].upload(sums_sq)
-        if feats is not None:
-            fbufs[0].upload(feats)
-            fbufs[1].upload(feats_sq)
-        denoise_atrous(ctx, bufs[0], bufs[1], rects, counts, bufs[2], features=fbufs[0], features_sq=fbufs[1], **params)
-        return bufs[2].download()
-    finally:
-        for b in bufs + fbufs:
-            if b is not None:
-                b.close()
+    with contextlib.ExitStack() as stack:
+        s, q, out, f, f_sq = _staged_guided(stack, ctx, sums, sums_sq, feats, feats_sq)
+        denoise_atrous(ctx, s, q, rects, counts, out, features=f, features_sq=f_sq, **params)
+        return out.download()
 
 
 class ErrorImage(Framebuffer):
     """W*H f64 in HBM: rmd_denoise_dual's per-pixel error estimate (the allocation is a framebuffer's; its first W*H doubles are used)."""
 
+    download_tiles = upload_tiles = _no_tile_transfers("error images")
+
     def __init__(self, ctx, width, height):
         Framebuffer.__init__(self, ctx, width, height)
-        self.n = width * height
 
-    def download(self):
-        out = np.empty((self.height, self.width), dtype=np.float64)
-        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
-        return out
+    def _shape(self):
+        return (self.height, self.width)
 
-    def download_tiles(self, tiles):
-        raise NotImplementedError("error images have no tile-rect transfers")
 
-    def upload_tiles(self, tiles, datas):
-        raise NotImplementedError("error images have no tile-rect transfers")
+def _dual_counts(rects, counts_a, counts_b):
+    return _counts(rects, counts_a, counts_b, what="one sample count per rect and half")
+
+
+def _feature_counts(rects, counts_f):
+    return _counts(rects, [] if counts_f is None else counts_f, what="one feature sample count per rect")
 
 
 def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, radius=10, patch_radius=3, k=0.45, alpha=1.0, region=None,
@@ -363,33 +388,27 @@ def denoise_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer
     feature samples per pixel): rmd_denoise_dual_guided[_region], the same with rmd_denoise_guided's feature weight; features=None makes the calls above.
     `slope` (a number; None: the calls above): rmd_denoise_dual_guided_slope[_region], the same with the feature-slope term.  Without features the slope
     is not read, as in the C calls and in denoise_guided: the unguided calls above are made."""
-    counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
-    counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
-    if len(counts_a) != len(rects) or len(counts_b) != len(rects):
-        raise ValueError("one sample count per rect and half")
-    fb = half_a[0]
-    head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, fb.width, fb.height, tile_array(rects),
-            counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects))
-    tail = (int(radius), int(patch_radius), float(k), float(alpha), out_framebuffer.ptr, None if error_image is None else error_image.ptr)
-    if features is not None or features_sq is not None:
-        counts_f = np.ascontiguousarray([] if counts_f is None else counts_f, dtype=np.uint32)
-        if len(counts_f) != len(rects):
-            raise ValueError("one feature sample count per rect")
-        head = head[:5] + (None if features is None else features.ptr, None if features_sq is None else features_sq.ptr) + head[5:10] + (
-            counts_f.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects))
-        tail = tail[:4] + (float(k_f), float(tau)) + (() if slope is None else (float(slope),)) + tail[4:]
-        whole, regional = ((ctx.L.rmd_denoise_dual_guided, ctx.L.rmd_denoise_dual_guided_region) if slope is None else
-                           (ctx.L.rmd_denoise_dual_guided_slope, ctx.L.rmd_denoise_dual_guided_slope_region))
-        if region is None:
-            ctx.check(whole(*head, *tail))
-        else:
-            region = list(region)
-            ctx.check(regional(*head, tile_array(region), len(region), *tail))
-    elif region is None:
-        ctx.check(ctx.L.rmd_denoise_dual(*head, *tail))
+    counts = _dual_counts(rects, counts_a, counts_b)
+    params = (int(radius), int(patch_radius), float(k), float(alpha))
+    halves = (half_a[0], half_a[1], half_b[0], half_b[1])
+    if features is None and features_sq is None:
+        _denoise_call(ctx, "rmd_denoise_dual", halves, rects, counts, params, (out_framebuffer, error_image), region=region)
     else:
-        region = list(region)
-        ctx.check(ctx.L.rmd_denoise_dual_region(*head, tile_array(region), len(region), *tail))
+        _denoise_call(ctx, "rmd_denoise_dual", halves, rects, counts + _feature_counts(rects, counts_f), params + (float(k_f), float(tau)),
+                      (out_framebuffer, error_image), features=(features, features_sq), region=region, slope=_slope(slope))
+
+
+def _staged_dual(stack, ctx, halves, out_init, images, features, features_sq):
+    """The dual helpers' buffers, each allocated and filled before the next: the two halves' sums and sums of squares and the output frame (`out_init`:
+    what it holds before the call, or None), one image per (kind, what it holds before the call or None) of `images`, and the two feature buffers when
+    `features` is given -> half A, half B, the output, the images, (features, features_sq)."""
+    def one(kind, arr):
+        return _staged(stack, ctx, halves[0], (kind, arr))[0]
+
+    fbs = [one(Framebuffer, arr) for arr in (*halves, out_init)]
+    imgs = [one(kind, arr) for kind, arr in images]
+    feats = [one(FeatureBuffer, arr) for arr in (features, features_sq)] if features is not None else [None, None]
+    return (fbs[0], fbs[1]), (fbs[2], fbs[3]), fbs[4], imgs, feats
 
 
 def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, region=None, out_init=None, err_init=None, features=None,
@@ -397,28 +416,10 @@ def denoise_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts
     """denoise_dual() for host arrays: the two halves' (H, W, 3) sums and sums of squares in; the (H, W, 3) means and the (H, W) error estimate out.
     `out_init` (H, W, 3) and `err_init` (H, W): what the two outputs hold before the call — what a pixel outside `region` still holds after it.
     `features` / `features_sq`: (H, W, 7) feature sums and sums of squares for the guided forms (with counts_f, k_f, tau among the params)."""
-    H, W = sums_a.shape[0], sums_a.shape[1]
-    opened = []
-    try:
-        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, out_init):
-            opened.append(Framebuffer(ctx, W, H))
-            if arr is not None:
-                opened[-1].upload(arr)
-        opened.append(ErrorImage(ctx, W, H))
-        if err_init is not None:
-            opened[-1].upload(err_init)
-        fbufs = [None, None]
-        if features is not None:
-            for i, arr in enumerate((features, features_sq)):
-                opened.append(FeatureBuffer(ctx, W, H))
-                opened[-1].upload(arr)
-                fbufs[i] = opened[-1]
-        denoise_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5], region=region, features=fbufs[0],
-                     features_sq=fbufs[1], **params)
-        return opened[4].download(), opened[5].download()
-    finally:
-        for b in opened:
-            b.close()
+    with contextlib.ExitStack() as stack:
+        a, b, out, (err,), (f, f_sq) = _staged_dual(stack, ctx, (sums_a, sums_sq_a, sums_b, sums_sq_b), out_init, [(ErrorImage, err_init)], features, features_sq)
+        denoise_dual(ctx, a, b, rects, counts_a, counts_b, out, err, region=region, features=f, features_sq=f_sq, **params)
+        return out.download(), err.download()
 
 
 def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_framebuffer, error_image=None, levels=5, k=3.0, alpha=1.0, features=None,
@@ -429,29 +430,11 @@ def denoise_atrous_dual(ctx, half_a, half_b, rects, counts_a, counts_b, out_fram
     pixel) add the feature weight; without them counts_f, k_f and tau are not read.  `region` (a list of rects, possibly empty):
     rmd_denoise_atrous_dual_region — only the pixels of those rects are written, with the bytes the whole-frame call gives them; None is the whole-frame
     call.  `slope` (a number; None: the calls above): rmd_denoise_atrous_dual_slope[_region], the same with the feature-slope term."""
-    counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
-    counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
-    if len(counts_a) != len(rects) or len(counts_b) != len(rects):
-        raise ValueError("one sample count per rect and half")
-    p_f = None
-    if features is not None or features_sq is not None:
-        counts_f = np.ascontiguousarray([] if counts_f is None else counts_f, dtype=np.uint32)
-        if len(counts_f) != len(rects):
-            raise ValueError("one feature sample count per rect")
-        p_f = counts_f.ctypes.data_as(C.POINTER(C.c_uint32))
-    fb = half_a[0]
-    head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, None if features is None else features.ptr,
-            None if features_sq is None else features_sq.ptr, fb.width, fb.height, tile_array(rects), counts_a.ctypes.data_as(C.POINTER(C.c_uint32)),
-            counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), p_f, len(rects))
-    tail = ((int(levels), float(k), float(alpha), float(k_f), float(tau)) + (() if slope is None else (float(slope),)) +
-            (out_framebuffer.ptr, None if error_image is None else error_image.ptr))
-    whole, regional = ((ctx.L.rmd_denoise_atrous_dual, ctx.L.rmd_denoise_atrous_dual_region) if slope is None else
-                       (ctx.L.rmd_denoise_atrous_dual_slope, ctx.L.rmd_denoise_atrous_dual_slope_region))
-    if region is None:
-        ctx.check(whole(*head, *tail))
-    else:
-        region = list(region)
-        ctx.check(regional(*head, tile_array(region), len(region), *tail))
+    counts = _dual_counts(rects, counts_a, counts_b)
+    counts += [None] if features is None and features_sq is None else _feature_counts(rects, counts_f)
+    _denoise_call(ctx, "rmd_denoise_atrous_dual", (half_a[0], half_a[1], half_b[0], half_b[1]), rects, counts,
+                  (int(levels), float(k), float(alpha), float(k_f), float(tau)), (out_framebuffer, error_image), features=(features, features_sq), region=region,
+                  slope=_slope(slope))
 
 
 def denoise_atrous_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, out_init=None, err_init=None, features=None,
@@ -460,28 +443,10 @@ def denoise_atrous_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects,
     out (None for the latter with want_err=False: the call is then made without an error image).  `out_init` / `err_init`: what the two outputs hold
     before the call — what a pixel outside `region` still holds after it.  `features` / `features_sq`: (H, W, 7) feature sums and sums of squares (with
     counts_f, k_f, tau among the params)."""
-    H, W = sums_a.shape[0], sums_a.shape[1]
-    opened = []
-    try:
-        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, out_init):
-            opened.append(Framebuffer(ctx, W, H))
-            if arr is not None:
-                opened[-1].upload(arr)
-        opened.append(ErrorImage(ctx, W, H))
-        if err_init is not None:
-            opened[-1].upload(err_init)
-        fbufs = [None, None]
-        if features is not None:
-            for i, arr in enumerate((features, features_sq)):
-                opened.append(FeatureBuffer(ctx, W, H))
-                opened[-1].upload(arr)
-                fbufs[i] = opened[-1]
-        denoise_atrous_dual(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, opened[4], opened[5] if want_err else None,
-                            features=fbufs[0], features_sq=fbufs[1], region=region, **params)
-        return opened[4].download(), opened[5].download() if want_err else None
-    finally:
-        for b in opened:
-            b.close()
+    with contextlib.ExitStack() as stack:
+        a, b, out, (err,), (f, f_sq) = _staged_dual(stack, ctx, (sums_a, sums_sq_a, sums_b, sums_sq_b), out_init, [(ErrorImage, err_init)], features, features_sq)
+        denoise_atrous_dual(ctx, a, b, rects, counts_a, counts_b, out, err if want_err else None, features=f, features_sq=f_sq, region=region, **params)
+        return out.download(), err.download() if want_err else None
 
 
 class WinnerImage(ErrorImage):
@@ -514,28 +479,15 @@ def denoise_dual_select(ctx, half_a, half_b, rects, counts_a, counts_b, candidat
     feature weight) by Stein's unbiased risk estimate, blended over the winners around the pixel.  `error_image` and `sure_image` (ErrorImages) and
     `winner_image` (a WinnerImage) are optional; `features`, `features_sq` and `counts_f` are needed by a guided candidate.  A candidate with a `slope`
     key makes the call rmd_denoise_dual_select_slope, with that candidate's slope (0.0 for one without the key)."""
-    counts_a = np.ascontiguousarray(counts_a, dtype=np.uint32)
-    counts_b = np.ascontiguousarray(counts_b, dtype=np.uint32)
-    if len(counts_a) != len(rects) or len(counts_b) != len(rects):
-        raise ValueError("one sample count per rect and half")
-    cf = None
-    if counts_f is not None:
-        counts_f = np.ascontiguousarray(counts_f, dtype=np.uint32)
-        if len(counts_f) != len(rects):
-            raise ValueError("one feature sample count per rect")
-        cf = counts_f.ctypes.data_as(C.POINTER(C.c_uint32))
+    counts = _dual_counts(rects, counts_a, counts_b)
+    counts += [None] if counts_f is None else _counts(rects, counts_f, what="one feature sample count per rect")
     candidates = list(candidates)
-    fb = half_a[0]
-    opt = lambda o: None if o is None else o.ptr  # noqa: E731
-    head = (ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, opt(features), opt(features_sq), fb.width, fb.height, tile_array(rects),
-            counts_a.ctypes.data_as(C.POINTER(C.c_uint32)), counts_b.ctypes.data_as(C.POINTER(C.c_uint32)), cf, len(rects), int(radius), int(patch_radius),
-            candidate_array(candidates))
-    tail = (len(candidates), int(sure_window), int(select_window), out_framebuffer.ptr, opt(error_image), opt(sure_image), opt(winner_image))
+    slopes = None  # (in this call the slopes follow the candidates they belong to, and the candidates' number follows them)
     if any("slope" in c for c in candidates):
         slopes = (C.c_double * len(candidates))(*[float(c.get("slope", 0.0)) for c in candidates])
-        ctx.check(ctx.L.rmd_denoise_dual_select_slope(*head, slopes, *tail))
-    else:
-        ctx.check(ctx.L.rmd_denoise_dual_select(*head, *tail))
+    _denoise_call(ctx, "rmd_denoise_dual_select", (half_a[0], half_a[1], half_b[0], half_b[1]), rects, counts,
+                  (int(radius), int(patch_radius), candidate_array(candidates)), (out_framebuffer, error_image, sure_image, winner_image),
+                  features=(features, features_sq), slope=slopes, after_slope=(len(candidates), int(sure_window), int(select_window)))
 
 
 def denoise_dual_select_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, candidates, features=None, features_sq=None,
@@ -543,36 +495,18 @@ def denoise_dual_select_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects,
     """denoise_dual_select() for host arrays: the two halves' (H, W, 3) sums and sums of squares in (and (H, W, 7) `features` / `features_sq` with counts_f
     among the params for guided candidates); a dict out with "out" (H, W, 3) and those of "err" (H, W), "sure" (H, W) and "win" (H, W) uint32 named in
     `want` — one left out is passed as NULL.  `init`: a dict of what the named outputs hold before the call."""
-    H, W = sums_a.shape[0], sums_a.shape[1]
     init = init or {}
-    opened = []
-    try:
-        for arr in (sums_a, sums_sq_a, sums_b, sums_sq_b, init.get("out")):
-            opened.append(Framebuffer(ctx, W, H))
-            if arr is not None:
-                opened[-1].upload(arr)
-        imgs = {}
-        for name in ("err", "sure", "win"):
-            if name in want:
-                imgs[name] = (WinnerImage if name == "win" else ErrorImage)(ctx, W, H)
-                opened.append(imgs[name])
-                if init.get(name) is not None:
-                    imgs[name].upload(init[name])
-        fbufs = [None, None]
-        if features is not None:
-            for i, arr in enumerate((features, features_sq)):
-                opened.append(FeatureBuffer(ctx, W, H))
-                opened[-1].upload(arr)
-                fbufs[i] = opened[-1]
-        denoise_dual_select(ctx, (opened[0], opened[1]), (opened[2], opened[3]), rects, counts_a, counts_b, candidates, opened[4], imgs.get("err"),
-                            imgs.get("sure"), imgs.get("win"), features=fbufs[0], features_sq=fbufs[1], **params)
-        res = {"out": opened[4].download()}
+    names = [name for name in ("err", "sure", "win") if name in want]
+    with contextlib.ExitStack() as stack:
+        a, b, out, made, (f, f_sq) = _staged_dual(stack, ctx, (sums_a, sums_sq_a, sums_b, sums_sq_b), init.get("out"),
+                                                  [(WinnerImage if name == "win" else ErrorImage, init.get(name)) for name in names], features, features_sq)
+        imgs = dict(zip(names, made))
+        denoise_dual_select(ctx, a, b, rects, counts_a, counts_b, candidates, out, imgs.get("err"), imgs.get("sure"), imgs.get("win"), features=f, features_sq=f_sq,
+                            **params)
+        res = {"out": out.download()}
         for name, img in imgs.items():
             res[name] = img.download()
         return res
-    finally:
-        for b in opened:
-            b.close()
 
 
 def tile_error_dual(ctx, error_image, tiles):
@@ -599,19 +533,11 @@ def resolve_tonemap_tiles(ctx, framebuffer, rects, counts, exposure=1.0, gamma=2
     (h, w, 3) uint8 array per rect (views of one packed block, in download_tiles's order).  `second` (a Framebuffer): a dual-buffer render's other
     half, whose sums are added to `framebuffer`'s before the division; counts then hold both halves' samples."""
     rects = list(rects)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if len(counts) != len(rects):
-        raise ValueError("one sample count per rect")
-    n = sum(w * h for (_, _, w, h) in rects)
-    out = np.empty(n * 3, dtype=np.uint8)
-    ctx.check(ctx.L.rmd_resolve_tonemap_tiles(ctx.handle, framebuffer.ptr, None if second is None else second.ptr, framebuffer.width, framebuffer.height,
-                                              tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), float(exposure), float(gamma),
-                                              out.ctypes.data_as(C.c_void_p)))
-    views, at = [], 0
-    for (_, _, w, h) in rects:
-        views.append(out[at : at + w * h * 3].reshape(h, w, 3))
-        at += w * h * 3
-    return views
+    (counts,) = _counts(rects, counts)
+    out = np.empty(3 * sum(w * h for (_, _, w, h) in rects), dtype=np.uint8)
+    ctx.check(ctx.L.rmd_resolve_tonemap_tiles(ctx.handle, framebuffer.ptr, _ptr(second), framebuffer.width, framebuffer.height, tile_array(rects), _u32(counts),
+                                              len(rects), float(exposure), float(gamma), out.ctypes.data_as(C.c_void_p)))
+    return _tile_views(out, rects)
 
 
 def scatter_tiles(rects, tiles, width=None, height=None, out=None):
@@ -671,12 +597,10 @@ class LumaHistogram:
 def luminance_histogram(ctx, framebuffer, rects, counts, second=None):
     """rmd_luminance_histogram_tiles: the luminance histogram of the pixels resolve_tonemap_tiles would resolve with the same arguments -> LumaHistogram."""
     rects = list(rects)
-    counts = np.ascontiguousarray(counts, dtype=np.uint32)
-    if len(counts) != len(rects):
-        raise ValueError("one sample count per rect")
+    (counts,) = _counts(rects, counts)
     out = abi.LumaHistogram()
-    ctx.check(ctx.L.rmd_luminance_histogram_tiles(ctx.handle, framebuffer.ptr, None if second is None else second.ptr, framebuffer.width, framebuffer.height,
-                                                  tile_array(rects), counts.ctypes.data_as(C.POINTER(C.c_uint32)), len(rects), C.byref(out)))
+    ctx.check(ctx.L.rmd_luminance_histogram_tiles(ctx.handle, framebuffer.ptr, _ptr(second), framebuffer.width, framebuffer.height, tile_array(rects),
+                                                  _u32(counts), len(rects), C.byref(out)))
     return LumaHistogram.from_struct(out)
 
 
@@ -694,6 +618,14 @@ def exposure_from_histogram(hist, percentile=0.99, target=0.8):
 
 
 # ---------------------------------------------------------------- the reference-shaped API
+def _guide(settings, features, counts_f, atrous=False):
+    """The keywords that make a dual filter call (denoise_dual, or with `atrous` denoise_atrous_dual; their *_arrays forms alike) the guided one: `features`,
+    a (sums, sums of squares) pair at counts_f[i] samples in rect i, with the settings' feature weight and slope.  features=None: {}, the unguided call."""
+    if features is None:
+        return {}
+    return dict(features=features[0], features_sq=features[1], counts_f=counts_f, **settings.guide_keywords(atrous))
+
+
 class Tile:  # core/src/tile.rs:7-14
     def __init__(self, left, top, width, height, sample_count, data, error=None, data_sq=None):
         self.left, self.top, self.width, self.height = left, top, width, height
@@ -704,6 +636,14 @@ class Tile:  # core/src/tile.rs:7-14
         # dual-buffer renders (an extension): the finished tile's two sample halves — sums, sums of squares (like data) and samples per pixel —;
         # data and data_sq are then the halves' sums added, sample_count = count_a + count_b.  Else None
         self.data_a = self.data_sq_a = self.count_a = self.data_b = self.data_sq_b = self.count_b = None
+
+    @property
+    def rect(self):
+        return (self.left, self.top, self.width, self.height)
+
+    def put(self, frame, data):
+        """`data` into this tile's pixels of the (H, W, ..) array `frame`."""
+        frame[self.top : self.top + self.height, self.left : self.left + self.width] = data
 
 
 class Message:  # src/trace.rs:62-66
@@ -756,6 +696,14 @@ class TaskHandle:  # src/trace.rs:70-135
             elif self.callback:
                 self.callback(m.tile)
 
+    def _finished_tiles(self):
+        """The tiles of the TileFinished messages at the head of the queue: the reference stops collecting at the first other message (:101-103)."""
+        while self._messages:
+            m = self._messages.pop(0)
+            if m.kind != "TileFinished":
+                break
+            yield m.tile
+
     def await_(self):
         """`await`: W*H radiance values, row-major, each the tile sum divided by its sample count (:93-99).
 
@@ -766,58 +714,46 @@ class TaskHandle:  # src/trace.rs:70-135
         denoise_atrous_levels and denoise_atrous_k, guided by the same features when denoise_features is on.
         With settings.despike: the assembled sums and sums of squares first go through rmd_despike on `device`, and the plain divide or whichever filter
         is on takes its outputs in their place."""
-        cam = self.settings.camera_settings
+        st = self.settings
+        cam = st.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
-        out = np.zeros(shape, dtype=np.float64)
-        if self.settings.denoise and self.settings.denoise_dual:
+        if st.denoise and st.denoise_dual:
             return self._await_dual()
-        denoised = self.settings.denoise
-        if denoised and self.settings.denoise_atrous:
-            self.settings.check_denoise()
-        if denoised and self.settings.denoise_features:
-            self.settings.check_denoise()
-            if self.scene is None:
-                raise ValueError("settings.denoise_features: this TaskHandle was made without the scene whose features await_() has to render")
-        despiked = self.settings.despike
-        if despiked:
-            self.settings.check_despike()
-        if denoised or despiked:
-            sums, sums_sq, rects, counts = np.zeros(shape), np.zeros(shape), [], []
-        while self._messages:
-            m = self._messages.pop(0)
-            if m.kind != "TileFinished":
-                break  # the reference stops collecting at the first non-TileFinished message (:101-103)
-            t = m.tile
-            if denoised or despiked:
-                sums[t.top : t.top + t.height, t.left : t.left + t.width] = t.data
-                sums_sq[t.top : t.top + t.height, t.left : t.left + t.width] = t.data_sq
-                rects.append((t.left, t.top, t.width, t.height))
-                counts.append(t.sample_count)
-            else:
-                out[t.top : t.top + t.height, t.left : t.left + t.width] = t.data / float(t.sample_count)
-        if despiked and not denoised:  # the plain divide, of the despiked sums
-            with Context(self.device) as ctx:
-                sums, _, _ = despike_arrays(ctx, sums, sums_sq, rects, counts, want_replaced=False, **self.settings.despike_keywords())
-            for (l, t, w, h), n in zip(rects, counts):
-                out[t : t + h, l : l + w] = sums[t : t + h, l : l + w] / float(n)
-        if denoised:
-            st = self.settings
-            with Context(self.device) as ctx:
-                if despiked:  # before anything else: every filter below takes the despiked sums in place of the raw ones
-                    sums, sums_sq, _ = despike_arrays(ctx, sums, sums_sq, rects, counts, want_replaced=False, **st.despike_keywords())
-                params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
-                if st.denoise_atrous:
-                    feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts) if st.denoise_features else (None, None)
-                    out = denoise_atrous_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, levels=st.denoise_atrous_levels, k=st.denoise_atrous_k,
-                                                alpha=st.denoise_alpha, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau, **st.atrous_slope_keyword())
-                elif st.denoise_features:
-                    feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts)
-                    out = denoise_guided_arrays(ctx, sums, sums_sq, feats, feats_sq, rects, counts, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
-                                                **st.slope_keyword(), **params)
-                else:
-                    out = denoise_arrays(ctx, sums, sums_sq, rects, counts, **params)
+        if st.denoise and (st.denoise_atrous or st.denoise_features):
+            st.check_denoise()
+        if st.denoise and st.denoise_features and self.scene is None:
+            raise ValueError("settings.denoise_features: this TaskHandle was made without the scene whose features await_() has to render")
+        if st.despike:
+            st.check_despike()
+        out = np.zeros(shape, dtype=np.float64)
+        if not (st.denoise or st.despike):
+            for t in self._finished_tiles():
+                t.put(out, t.data / float(t.sample_count))
+            return out
+        sums, sums_sq, rects, counts = np.zeros(shape), np.zeros(shape), [], []
+        for t in self._finished_tiles():
+            t.put(sums, t.data)
+            t.put(sums_sq, t.data_sq)
+            rects.append(t.rect)
+            counts.append(t.sample_count)
+        with Context(self.device) as ctx:
+            if st.despike:  # before anything else: the divide or filter below takes the despiked sums in place of the raw ones
+                sums, sums_sq, _ = despike_arrays(ctx, sums, sums_sq, rects, counts, want_replaced=False, **st.despike_keywords())
+            if st.denoise:
+                return self._filtered(ctx, sums, sums_sq, rects, counts)
+        for (l, t, w, h), n in zip(rects, counts):  # the plain divide, of the despiked sums
+            out[t : t + h, l : l + w] = sums[t : t + h, l : l + w] / float(n)
         return out
 
+    def _filtered(self, ctx, sums, sums_sq, rects, counts):
+        """await_()'s frame through the single-buffer filter the settings name."""
+        st = self.settings
+        feats = finished_tile_features(ctx, self.scene, st, rects, counts) if st.denoise_features else (None, None)
+        if st.denoise_atrous:
+            return denoise_atrous_arrays(ctx, sums, sums_sq, *feats, rects, counts, **st.atrous_keywords(), **st.guide_keywords(atrous=True))
+        if st.denoise_features:
+            return denoise_guided_arrays(ctx, sums, sums_sq, *feats, rects, counts, **st.guide_keywords(), **st.nlm_keywords())
+        return denoise_arrays(ctx, sums, sums_sq, rects, counts, **st.nlm_keywords())
 
     def _await_dual(self):
         """await_() with settings.denoise_dual: the finished tiles' two halves through rmd_denoise_dual on `device`.  With settings.denoise_dual_features:
@@ -827,46 +763,30 @@ class TaskHandle:  # src/trace.rs:70-135
         rmd_denoise_atrous_dual's at denoise_atrous_levels and denoise_atrous_k, guided by the same features when denoise_dual_features is on."""
         st = self.settings
         st.check_denoise()
-        if (st.denoise_dual_features or st.denoise_dual_select) and self.scene is None:
+        featured = st.denoise_dual_features or st.denoise_dual_select
+        if featured and self.scene is None:
             raise ValueError("settings.denoise_dual_features / denoise_dual_select: this TaskHandle was made without the scene whose features await_() has to render")
         cam = st.camera_settings
         shape = (cam.backbuffer_height, cam.backbuffer_width, 3)
         halves = [np.zeros(shape) for _ in range(4)]
         rects, counts_a, counts_b = [], [], []
-        while self._messages:
-            m = self._messages.pop(0)
-            if m.kind != "TileFinished":
-                break
-            t = m.tile
+        for t in self._finished_tiles():
             for dst, src in zip(halves, (t.data_a, t.data_sq_a, t.data_b, t.data_sq_b)):
-                dst[t.top : t.top + t.height, t.left : t.left + t.width] = src
-            rects.append((t.left, t.top, t.width, t.height))
+                t.put(dst, src)
+            rects.append(t.rect)
             counts_a.append(t.count_a)
             counts_b.append(t.count_b)
+        counts_f = [a + b for a, b in zip(counts_a, counts_b)]
         with Context(self.device) as ctx:
-            params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
+            feats = finished_tile_features(ctx, self.scene, st, rects, counts_f) if featured else None
             if st.denoise_dual_atrous:
-                guide = {}
-                if st.denoise_dual_features:
-                    counts_f = [a + b for a, b in zip(counts_a, counts_b)]
-                    feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
-                    guide = dict(features=feats, features_sq=feats_sq, counts_f=counts_f, k_f=st.denoise_feature_k, tau=st.denoise_feature_tau,
-                                 **st.atrous_slope_keyword())
-                out, _ = denoise_atrous_dual_arrays(ctx, *halves, rects, counts_a, counts_b, levels=st.denoise_atrous_levels, k=st.denoise_atrous_k,
-                                                    alpha=st.denoise_alpha, **guide)
+                out, _ = denoise_atrous_dual_arrays(ctx, *halves, rects, counts_a, counts_b, **st.atrous_keywords(), **_guide(st, feats, counts_f, atrous=True))
             elif st.denoise_dual_select:
-                counts_f = [a + b for a, b in zip(counts_a, counts_b)]
-                feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
-                out = denoise_dual_select_arrays(ctx, *halves, rects, counts_a, counts_b, st.select_candidates(), features=feats, features_sq=feats_sq,
+                out = denoise_dual_select_arrays(ctx, *halves, rects, counts_a, counts_b, st.select_candidates(), features=feats[0], features_sq=feats[1],
                                                  counts_f=counts_f, want=(), radius=st.denoise_radius, patch_radius=st.denoise_patch, sure_window=2,
                                                  select_window=2)["out"]
-            elif st.denoise_dual_features:
-                counts_f = [a + b for a, b in zip(counts_a, counts_b)]
-                feats, feats_sq = finished_tile_features(ctx, self.scene, st, rects, counts_f)
-                out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, features=feats, features_sq=feats_sq, counts_f=counts_f,
-                                             k_f=st.denoise_feature_k, tau=st.denoise_feature_tau, **st.slope_keyword(), **params)
             else:
-                out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, **params)
+                out, _ = denoise_dual_arrays(ctx, *halves, rects, counts_a, counts_b, **st.nlm_keywords(), **_guide(st, feats, counts_f))
         return out
 
 
@@ -875,26 +795,160 @@ def finished_tile_features(ctx, scene, settings, rects, counts):
     distinct sample count, each tile at its own count, with the settings' seed and DOF flag.  Pixels no rect covers stay zero."""
     cam = settings.camera_settings
     W, H = cam.backbuffer_width, cam.backbuffer_height
-    opened = []  # closed in reverse order whichever way the body leaves, each on its own
-    try:
-        ds = DeviceScene(ctx, scene)
-        opened.append(ds)
-        fb = FeatureBuffer(ctx, W, H)
-        opened.append(fb)
-        fb_sq = FeatureBuffer(ctx, W, H)
-        opened.append(fb_sq)
+    with contextlib.ExitStack() as stack:
+        ds = stack.enter_context(DeviceScene(ctx, scene))
+        fb = stack.enter_context(FeatureBuffer(ctx, W, H))
+        fb_sq = stack.enter_context(FeatureBuffer(ctx, W, H))
         for n in sorted(set(int(c) for c in counts)):
             share = [r for r, c in zip(rects, counts) if int(c) == n]
             if n > 0:
                 render_features(ctx, ds, cam, settings, share, fb, 0, n, sync=False, features_sq=fb_sq)
         ctx.synchronize()
         return fb.download(), fb_sq.download()
-    finally:
-        for o in reversed(opened):
-            try:
-                o.close()
-            except Exception:  # noqa: BLE001 (a failing close must not keep the others open, nor hide the body's own error)
-                pass
+
+
+def _preview(settings, W, H, pass_index, sample_count, calls):
+    """The Message.FramePreview of one pass.  `calls`: per device, the (ctx, framebuffer, rects, counts, second) its rmd_resolve_tonemap_tiles call takes.
+    With preview_auto_exposure every device first histograms exactly that, the histograms are added and the sum's exposure replaces preview_exposure;
+    then every device resolves its tiles and the packed 8-bit tiles are scattered into one frame here."""
+    st = settings
+    exposure = None
+    if st.preview_auto_exposure:
+        hist = LumaHistogram()
+        for ctx, fb, rects, counts, second in calls:
+            hist = add_histograms(hist, luminance_histogram(ctx, fb, rects, counts, second=second))
+        exposure = exposure_from_histogram(hist, st.auto_exposure_percentile, st.auto_exposure_target)
+    frame = np.zeros((H, W, 3), dtype=np.uint8)
+    for ctx, fb, rects, counts, second in calls:
+        scatter_tiles(rects, resolve_tonemap_tiles(ctx, fb, rects, counts, st.preview_exposure if exposure is None else exposure, st.preview_gamma, second=second),
+                      out=frame)
+    return Message.FramePreview(frame, pass_index, sample_count, exposure)
+
+
+class _Worker:
+    """One device of render_tiled: its context, scene and sum buffers; `live`, the tiles of its share that still take passes; `early`, the
+    (rect, sample count) of those that finished before the last pass."""
+
+    def __init__(self, stack, device, scene, W, H, moments):
+        self.ctx = stack.enter_context(Context(device))
+        self.ds = stack.enter_context(DeviceScene(self.ctx, scene))
+        self.fb = stack.enter_context(Framebuffer(self.ctx, W, H))
+        self.fb_sq = stack.enter_context(Framebuffer(self.ctx, W, H)) if moments else None
+        self.live, self.early = [], []
+
+    def whole_frame(self, done):
+        """The rects and counts of everything this device holds: the tiles that finished early at their counts, the live ones at `done`."""
+        return [r for r, _ in self.early] + self.live, [c for _, c in self.early] + [done] * len(self.live)
+
+
+class _TiledLoop:
+    """render_tiled's single-buffer loop: the state its steps share.  Every device object is opened on `stack`."""
+
+    def __init__(self, stack, scene, settings, devices):
+        st = self.st = settings
+        cam = st.camera_settings
+        self.W, self.H = cam.backbuffer_width, cam.backbuffer_height
+        self.adaptive = st.adaptive_threshold > 0.0
+        self.preview_filtered = st.preview_every > 0 and st.preview_denoise
+        moments = self.adaptive or st.denoise or self.preview_filtered or st.despike
+        self.with_sq = st.denoise or st.despike  # the finished tiles carry their sums of squares: await_() reads them
+        self.workers = [_Worker(stack, d, scene, self.W, self.H, moments) for d in devices]
+        first = self.workers[0].ctx
+        self.filtered_fb = stack.enter_context(Framebuffer(first, self.W, self.H)) if self.preview_filtered else None  # (one device: check_preview)
+        # despike with the adaptive check: two spare buffers for the despiked sums the check reads (one device: check_despike); the passes' own stay raw
+        self.spare = tuple(stack.enter_context(Framebuffer(first, self.W, self.H)) for _ in range(2)) if st.despike and self.adaptive else None
+        tiles = generate_tiles(self.W, self.H, st.tile_size)
+        for i, w in enumerate(self.workers):
+            w.live = tiles[i :: len(self.workers)]
+        self.messages, self.finished = [], []
+        self.done = self.passes = 0
+
+    def render_pass(self, n):
+        st = self.st
+        for w in self.workers:
+            if w.live:
+                render_tiles(w.ctx, w.ds, st.camera_settings, st, w.live, w.fb, self.done, n, sync=False, framebuffer_sq=w.fb_sq)
+        for w in self.workers:
+            w.ctx.synchronize()
+        self.done += n
+        self.passes += 1
+
+    def adaptive_check(self, w):
+        """rmd_tile_error of `w`'s live tiles (None each without adaptive_threshold); with despike, on the despiked sums of all its tiles at their counts."""
+        st = self.st
+        if not (self.adaptive and w.live):
+            return [None] * len(w.live)
+        fb, fb_sq = w.fb, w.fb_sq
+        if self.spare is not None:
+            rects, counts = w.whole_frame(self.done)
+            despike(w.ctx, fb, fb_sq, rects, counts, out=self.spare, want_replaced=False, **st.despike_keywords())
+            fb, fb_sq = self.spare
+        return tile_error(w.ctx, fb, fb_sq, self.done, st.adaptive_floor, w.live)
+
+    def finish(self, w, rect, sample_count, data, error=None, data_sq=None):
+        l, t, width, height = rect
+        self.finished.append(Message.TileFinished(Tile(l, t, width, height, sample_count, data, error, data_sq)))
+        if sample_count < self.st.sample_count:  # converged between passes: the previews and the despiked check go on reading it at this count
+            w.early.append((rect, sample_count))
+
+    def snapshots(self, w, errors):
+        """After a pass that leaves the render unfinished: `w`'s converged tiles finish at the samples they have, the others are sent as TileProgressed —
+        from one download of the whole frame, or with progress_tiles off from the converged tiles' pixels alone and without a message for the rest."""
+        st, done = self.st, self.done
+        converged = [self.adaptive and e <= st.adaptive_threshold for e in errors]
+        conv = [r for r, c in zip(w.live, converged) if c]
+        if not st.progress_tiles:
+            data = w.fb.download_tiles(conv) if conv else []
+            data_sq = w.fb_sq.download_tiles(conv) if conv and self.with_sq else [None] * len(conv)
+            for rect, e, d, d_sq in zip(conv, [e for e, c in zip(errors, converged) if c], data, data_sq):
+                self.finish(w, rect, done, d.copy(), float(e), None if d_sq is None else d_sq.copy())
+        else:
+            img = w.fb.download()
+            img_sq = w.fb_sq.download() if self.with_sq else None
+            for (l, t, width, height), e, c in zip(w.live, errors, converged):
+                data = img[t : t + height, l : l + width].copy()
+                if c:
+                    self.finish(w, (l, t, width, height), done, data, float(e), None if img_sq is None else img_sq[t : t + height, l : l + width].copy())
+                else:
+                    self.messages.append(Message.TileProgressed(Tile(l, t, width, height, done, data, None if e is None else float(e))))
+        w.live = [r for r, c in zip(w.live, converged) if not c]
+
+    def preview(self):
+        """Every device with tiles resolves its whole frame; with preview_denoise, rmd_denoise_atrous's means of it at count 1."""
+        st = self.st
+        calls = []
+        for w in self.workers:
+            rects, counts = w.whole_frame(self.done)
+            if not rects:
+                continue
+            fb = w.fb
+            if self.preview_filtered:
+                denoise_atrous(w.ctx, w.fb, w.fb_sq, rects, counts, self.filtered_fb, **st.atrous_keywords())
+                fb, counts = self.filtered_fb, [1] * len(rects)  # (means)
+            calls.append((w.ctx, fb, rects, counts, None))
+        self.messages.append(_preview(st, self.W, self.H, self.passes, self.done, calls))
+
+    def finish_all(self):
+        """The last pass is through: every tile still live finishes at sample_count."""
+        for w in self.workers:
+            img = w.fb.download()
+            img_sq = w.fb_sq.download() if self.with_sq else None
+            for (l, t, width, height) in w.live:
+                sq = None if img_sq is None else img_sq[t : t + height, l : l + width].copy()
+                self.finish(w, (l, t, width, height), self.st.sample_count, img[t : t + height, l : l + width].copy(), data_sq=sq)
+
+    def run(self):
+        st = self.st
+        step = st.samples_per_iteration if st.samples_per_iteration else st.sample_count
+        while self.done < st.sample_count:
+            self.render_pass(min(step, st.sample_count - self.done))
+            if self.done < st.sample_count and st.samples_per_iteration:
+                for w in self.workers:
+                    self.snapshots(w, self.adaptive_check(w))
+                if st.preview_every and self.passes % st.preview_every == 0 and any(w.live for w in self.workers):  # (no live tile: the render is finished)
+                    self.preview()
+        self.finish_all()
+        return self.messages + self.finished  # progress snapshots (and previews) first, then the finished tiles
 
 
 def render_tiled(scene, settings, devices=(0,)):
@@ -921,121 +975,125 @@ def render_tiled(scene, settings, devices=(0,)):
     all tiles — live ones at the current count, those that finished early at theirs — into two spare buffers and rmd_tile_error reads those; the buffers the
     passes add to, every message's data and the previews stay the raw sums.
 
-    Dual-buffer (settings.denoise_dual, an extension): _render_tiled_dual."""
+    Dual-buffer (settings.denoise_dual, an extension): _render_tiled_dual.
+
+    Whichever way a loop ends, the device objects it opened are closed in reverse order of opening."""
     settings.check_adaptive()
     settings.check_denoise()
     settings.check_preview(len(devices))
     settings.check_despike(len(devices))
     if settings.denoise_dual:
         return _render_tiled_dual(scene, settings, devices)
-    adaptive = settings.adaptive_threshold > 0.0
-    preview_filtered = settings.preview_every > 0 and settings.preview_denoise
-    moments = adaptive or settings.denoise or preview_filtered or settings.despike
-    with_sq = settings.denoise or settings.despike  # the finished tiles carry their sums of squares: await_() reads them
-    cam = settings.camera_settings
-    W, H = cam.backbuffer_width, cam.backbuffer_height
-    tiles = generate_tiles(W, H, settings.tile_size)
-    workers = []
-    for d in devices:
-        ctx = Context(d)
-        workers.append((ctx, DeviceScene(ctx, scene), Framebuffer(ctx, W, H), Framebuffer(ctx, W, H) if moments else None))
-    filtered_fb = Framebuffer(workers[0][0], W, H) if preview_filtered else None  # (one device: check_preview)
-    # despike with the adaptive check: two spare buffers for the despiked sums the check reads (one device: check_despike); the passes' own stay raw
-    spare = (Framebuffer(workers[0][0], W, H), Framebuffer(workers[0][0], W, H)) if settings.despike and adaptive else None
-    shares = [tiles[i :: len(workers)] for i in range(len(workers))]  # adaptive: the tiles of a share that are still live
-    early = [[] for _ in workers]  # previews: per worker, the (rect, sample count) of the tiles that finished early
-    step = settings.samples_per_iteration if settings.samples_per_iteration else settings.sample_count
-    messages = []
-    finished = []
-    done = passes = 0
-    try:
-        while done < settings.sample_count:
-            n = min(step, settings.sample_count - done)
-            for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
-                if share:
-                    render_tiles(ctx, ds, cam, settings, share, fb, done, n, sync=False, framebuffer_sq=fb_sq)
-            for ctx, _, _, _ in workers:
-                ctx.synchronize()
-            done += n
-            passes += 1
-            if done < settings.sample_count and settings.samples_per_iteration:
-                for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
-                    share = shares[i]
-                    if adaptive and share and spare is not None:  # all tiles at their current counts; the error of the live ones on the despiked sums
-                        despike(ctx, fb, fb_sq, [r for r, _ in early[i]] + share, [c for _, c in early[i]] + [done] * len(share), out=spare,
-                                want_replaced=False, **settings.despike_keywords())
-                        errors = tile_error(ctx, spare[0], spare[1], done, settings.adaptive_floor, share)
-                    else:
-                        errors = tile_error(ctx, fb, fb_sq, done, settings.adaptive_floor, share) if adaptive and share else [None] * len(share)
-                    if not settings.progress_tiles:  # no snapshots: only the converged tiles' pixels come to the host
-                        is_conv = [adaptive and e <= settings.adaptive_threshold for e in errors]
-                        conv = [r for r, c in zip(share, is_conv) if c]
-                        data = fb.download_tiles(conv) if conv else []
-                        data_sq = fb_sq.download_tiles(conv) if conv and with_sq else [None] * len(conv)
-                        for (l, t, w, h), e, d, d_sq in zip(conv, [e for e, c in zip(errors, is_conv) if c], data, data_sq):
-                            finished.append(Message.TileFinished(Tile(l, t, w, h, done, d.copy(), float(e), None if d_sq is None else d_sq.copy())))
-                            early[i].append(((l, t, w, h), done))
-                        shares[i] = [r for r, c in zip(share, is_conv) if not c]
-                        continue
-                    img = fb.download()
-                    img_sq = fb_sq.download() if with_sq else None
-                    live = []
-                    for (l, t, w, h), e in zip(share, errors):
-                        tile = Tile(l, t, w, h, done, img[t : t + h, l : l + w].copy(), None if e is None else float(e))
-                        if adaptive and e <= settings.adaptive_threshold:
-                            if img_sq is not None:
-                                tile.data_sq = img_sq[t : t + h, l : l + w].copy()
-                            finished.append(Message.TileFinished(tile))  # converged: finished at the samples it has
-                            early[i].append(((l, t, w, h), done))
-                        else:
-                            messages.append(Message.TileProgressed(tile))
-                            live.append((l, t, w, h))
-                    shares[i] = live
-                if settings.preview_every and passes % settings.preview_every == 0 and any(shares):  # (no live tile: the render is finished)
-                    # every device resolves the tiles of its share — live ones at `done`, those that finished early at their own counts — and the
-                    # packed 8-bit tiles are scattered into one frame here
-                    frame = np.zeros((H, W, 3), dtype=np.uint8)
-                    calls = []  # per device with tiles: what its resolve call takes
-                    for i, (ctx, ds, fb, fb_sq) in enumerate(workers):
-                        rects = [r for r, _ in early[i]] + shares[i]
-                        counts = [c for _, c in early[i]] + [done] * len(shares[i])
-                        if not rects:
-                            continue
-                        if preview_filtered:
-                            denoise_atrous(ctx, fb, fb_sq, rects, counts, filtered_fb, levels=settings.denoise_atrous_levels, k=settings.denoise_atrous_k,
-                                           alpha=settings.denoise_alpha)
-                            fb, counts = filtered_fb, [1] * len(rects)  # (means)
-                        calls.append((ctx, fb, rects, counts))
-                    exposure = None
-                    if settings.preview_auto_exposure:  # one exposure for the frame: the devices' histograms added
-                        hist = LumaHistogram()
-                        for ctx, fb, rects, counts in calls:
-                            hist = add_histograms(hist, luminance_histogram(ctx, fb, rects, counts))
-                        exposure = exposure_from_histogram(hist, settings.auto_exposure_percentile, settings.auto_exposure_target)
-                    for ctx, fb, rects, counts in calls:
-                        scatter_tiles(rects, resolve_tonemap_tiles(ctx, fb, rects, counts, settings.preview_exposure if exposure is None else exposure,
-                                                                   settings.preview_gamma), out=frame)
-                    messages.append(Message.FramePreview(frame, passes, done, exposure))
-        for (ctx, ds, fb, fb_sq), share in zip(workers, shares):
-            img = fb.download()
-            img_sq = fb_sq.download() if with_sq else None
-            for (l, t, w, h) in share:
-                sq = None if img_sq is None else img_sq[t : t + h, l : l + w].copy()
-                finished.append(Message.TileFinished(Tile(l, t, w, h, settings.sample_count, img[t : t + h, l : l + w].copy(), data_sq=sq)))
-        messages = messages + finished  # progress snapshots (and previews) first, then the finished tiles
-    finally:
-        if filtered_fb is not None:
-            filtered_fb.close()
-        for b in spare or ():
-            b.close()
-        for ctx, ds, fb, fb_sq in workers:
-            fb.close()
-            if fb_sq is not None:
-                fb_sq.close()
-            ds.close()
-            ctx.close()
-    handle = TaskHandle(settings, messages, devices[0], scene if settings.denoise_features else None)
-    return handle
+    with contextlib.ExitStack() as stack:
+        messages = _TiledLoop(stack, scene, settings, devices).run()
+    return TaskHandle(settings, messages, devices[0], scene if settings.denoise_features else None)
+
+
+class _DualLoop:
+    """The dual-buffer loop (_render_tiled_dual, which describes it): the state its steps share.  Every device object is opened on `stack`."""
+
+    def __init__(self, stack, scene, settings, device):
+        st = self.st = settings
+        cam = st.camera_settings
+        W, H = self.W, self.H = cam.backbuffer_width, cam.backbuffer_height
+        self.adaptive = st.adaptive_denoised_threshold > 0.0
+        ctx = self.ctx = stack.enter_context(Context(device))
+        self.ds = stack.enter_context(DeviceScene(ctx, scene))
+        self.fbs = [stack.enter_context(Framebuffer(ctx, W, H)) for _ in range(4)]  # S_A, Q_A, S_B, Q_B
+        if self.adaptive:
+            self.out_fb, self.err_img = stack.enter_context(Framebuffer(ctx, W, H)), stack.enter_context(ErrorImage(ctx, W, H))
+        # the feature buffers (sums, sums of squares) the guided check reads, or None: this loop keeps none
+        self.feat_fbs = [stack.enter_context(FeatureBuffer(ctx, W, H)) for _ in range(2)] if self.adaptive and st.denoise_dual_features else None
+        self.preview_fb = stack.enter_context(Framebuffer(ctx, W, H)) if st.preview_every and st.preview_denoise else None
+        self.live = generate_tiles(W, H, st.tile_size)
+        self.done_rects, self.done_a, self.done_b = [], [], []  # the finished tiles and the counts they finished with
+        self.n_half = [0, 0]  # samples per pixel of a live tile in A and B
+        self.done = self.passes = 0
+        self.messages, self.finished = [], []
+
+    def render_pass(self, n):
+        st, cam, half = self.st, self.st.camera_settings, self.passes & 1
+        render_tiles(self.ctx, self.ds, cam, st, self.live, self.fbs[2 * half], self.done, n, sync=False, framebuffer_sq=self.fbs[2 * half + 1])
+        if self.feat_fbs is not None:
+            render_features(self.ctx, self.ds, cam, st, self.live, self.feat_fbs[0], self.done, n, sync=False, features_sq=self.feat_fbs[1])
+        self.ctx.synchronize()
+        self.done, self.passes = self.done + n, self.passes + 1
+        self.n_half[half] += n
+
+    def whole_frame(self, live):
+        """The rects and the two halves' counts of the whole frame: the finished tiles at the counts they finished with, `live` ones at n_A and n_B."""
+        return self.done_rects + live, self.done_a + [self.n_half[0]] * len(live), self.done_b + [self.n_half[1]] * len(live)
+
+    def filter_whole_frame(self, live, out_fb, err_img, atrous, **where):
+        """The dual filter over whole_frame(live) into `out_fb` (and `err_img`): rmd_denoise_atrous_dual with `atrous`, else rmd_denoise_dual; guided when
+        the loop keeps the feature buffers.  `where`: region=..., or nothing for the whole-frame call."""
+        st = self.st
+        rects, all_a, all_b = self.whole_frame(live)
+        guide = _guide(st, self.feat_fbs, [a + b for a, b in zip(all_a, all_b)], atrous)
+        halves = ((self.fbs[0], self.fbs[1]), (self.fbs[2], self.fbs[3]))
+        if atrous:
+            denoise_atrous_dual(self.ctx, *halves, rects, all_a, all_b, out_fb, err_img, **st.atrous_keywords(), **guide, **where)
+        else:
+            denoise_dual(self.ctx, *halves, rects, all_a, all_b, out_fb, err_img, **where, **st.nlm_keywords(), **guide)
+
+    def adaptive_check(self):
+        """rmd_tile_error_dual of the live tiles after the settings' filter, or None each when no check is due."""
+        st = self.st
+        if not (self.adaptive and self.passes % 2 == 0 and self.done >= st.adaptive_min_samples):
+            return [None] * len(self.live)
+        if st.denoise_dual_atrous:  # the whole frame; (region off: exactly the call made before the region form existed)
+            self.filter_whole_frame(self.live, self.out_fb, self.err_img, True, **(dict(region=self.live) if st.denoise_dual_atrous_region else {}))
+        else:  # only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
+            self.filter_whole_frame(self.live, self.out_fb, self.err_img, False, region=self.live)
+        return tile_error_dual(self.ctx, self.err_img, self.live)
+
+    def finish(self, rects, errors=None):
+        """TileFinished for `rects`: both halves' sums and sums of squares, the tiles' pixels only."""
+        if not rects:
+            return
+        n_a, n_b = self.n_half
+        packed = [fb.download_tiles(rects) for fb in self.fbs]
+        for i, rect in enumerate(rects):
+            l, t, w, h = rect
+            a, a_sq, b, b_sq = (p[i].copy() for p in packed)
+            tile = Tile(l, t, w, h, n_a + n_b, a + b, None if errors is None else errors[i], a_sq + b_sq)
+            tile.data_a, tile.data_sq_a, tile.count_a, tile.data_b, tile.data_sq_b, tile.count_b = a, a_sq, n_a, b, b_sq, n_b
+            self.finished.append(Message.TileFinished(tile))
+            self.done_rects.append(rect), self.done_a.append(n_a), self.done_b.append(n_b)
+
+    def snapshots(self, still, errors):
+        """TileProgressed for the tiles that go on: the two halves' sums added."""
+        pa, pb = self.fbs[0].download_tiles(still), self.fbs[2].download_tiles(still)
+        for (l, t, w, h), e, a, b in zip(still, errors, pa, pb):
+            self.messages.append(Message.TileProgressed(Tile(l, t, w, h, self.done, a + b, None if e is None else float(e))))
+
+    def preview(self, still):
+        """The whole frame: finished tiles at the counts they finished with, live ones at n_A + n_B, the two halves' sums added on the device; with
+        preview_denoise, rmd_denoise_atrous_dual's means of it at count 1."""
+        rects, all_a, all_b = self.whole_frame(still)
+        if self.preview_fb is None:
+            call = (self.ctx, self.fbs[0], rects, [a + b for a, b in zip(all_a, all_b)], self.fbs[2])
+        else:
+            self.filter_whole_frame(still, self.preview_fb, None, True)
+            call = (self.ctx, self.preview_fb, rects, [1] * len(rects), None)  # (means)
+        self.messages.append(_preview(self.st, self.W, self.H, self.passes, self.done, [call]))
+
+    def run(self):
+        st = self.st
+        while self.done < st.sample_count and self.live:
+            self.render_pass(min(st.samples_per_iteration, st.sample_count - self.done))
+            if self.done < st.sample_count:
+                errors = self.adaptive_check()
+                conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
+                self.finish([r for r, c in zip(self.live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
+                still = [r for r, c in zip(self.live, conv) if not c]
+                if still and st.progress_tiles:
+                    self.snapshots(still, [e for e, c in zip(errors, conv) if not c])
+                if still and st.preview_every and self.passes % st.preview_every == 0:
+                    self.preview(still)
+                self.live = still
+        self.finish(self.live)
+        return self.messages + self.finished  # progress snapshots first, then the finished tiles
 
 
 def _render_tiled_dual(scene, settings, devices):
@@ -1045,7 +1103,8 @@ def _render_tiled_dual(scene, settings, devices):
 
     With settings.adaptive_denoised_threshold > 0: after every even number of passes that leaves live tiles below sample_count with at least
     adaptive_min_samples samples, rmd_denoise_dual_region filters the live tiles' pixels of the whole frame (finished tiles at the counts they
-    finished with: the bytes rmd_denoise_dual would give those pixels), rmd_tile_error_dual runs over the live tiles, and a live tile at or below the threshold is sent as TileFinished, with that error, and takes no further passes.
+    finished with: the bytes rmd_denoise_dual would give those pixels), rmd_tile_error_dual runs over the live tiles, and a live tile at or below the
+    threshold is sent as TileFinished, with that error, and takes no further passes.
 
     With settings.denoise_dual_features the adaptive check needs the features: two feature buffers beside the four, into which rmd_render_features
     adds, after each pass, the live tiles' first-hit features of the same samples [done, done + n), so a tile's features hold count_a + count_b
@@ -1062,112 +1121,6 @@ def _render_tiled_dual(scene, settings, devices):
     settings.preview_auto_exposure the exposure comes from rmd_luminance_histogram_tiles on what that resolve call takes, as in render_tiled."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
-    st = settings
-    cam = st.camera_settings
-    W, H = cam.backbuffer_width, cam.backbuffer_height
-    tiles = generate_tiles(W, H, st.tile_size)
-    adaptive = st.adaptive_denoised_threshold > 0.0
-    params = dict(radius=st.denoise_radius, patch_radius=st.denoise_patch, k=st.denoise_k, alpha=st.denoise_alpha)
-    opened = []  # closed in reverse order whichever way the body leaves
-    messages, finished = [], []
-    try:
-        ctx = Context(devices[0])
-        opened.append(ctx)
-        ds = DeviceScene(ctx, scene)
-        opened.append(ds)
-        fbs = [Framebuffer(ctx, W, H) for _ in range(4)]  # S_A, Q_A, S_B, Q_B
-        opened.extend(fbs)
-        if adaptive:
-            out_fb, err_img = Framebuffer(ctx, W, H), ErrorImage(ctx, W, H)
-            opened.extend([out_fb, err_img])
-        guided = adaptive and st.denoise_dual_features
-        guide = {}
-        if guided:
-            feat_fbs = [FeatureBuffer(ctx, W, H) for _ in range(2)]
-            opened.extend(feat_fbs)
-        preview_fb = None
-        if st.preview_every and st.preview_denoise:
-            preview_fb = Framebuffer(ctx, W, H)
-            opened.append(preview_fb)
-        live = list(tiles)
-        done_rects, done_a, done_b = [], [], []  # the finished tiles and the counts they finished with
-        n_half = [0, 0]  # samples per pixel of a live tile in A and B
-        done, j = 0, 0
-
-        def finish(rects, errors=None):
-            """TileFinished for `rects`: both halves' sums and sums of squares, the tiles' pixels only."""
-            if not rects:
-                return
-            packed = [fb.download_tiles(rects) for fb in fbs]
-            for i, rect in enumerate(rects):
-                l, t, w, h = rect
-                a, a_sq, b, b_sq = (p[i].copy() for p in packed)
-                tile = Tile(l, t, w, h, n_half[0] + n_half[1], a + b, None if errors is None else errors[i], a_sq + b_sq)
-                tile.data_a, tile.data_sq_a, tile.count_a, tile.data_b, tile.data_sq_b, tile.count_b = a, a_sq, n_half[0], b, b_sq, n_half[1]
-                finished.append(Message.TileFinished(tile))
-                done_rects.append(rect), done_a.append(n_half[0]), done_b.append(n_half[1])
-
-        while done < st.sample_count and live:
-            n = min(st.samples_per_iteration, st.sample_count - done)
-            half = j & 1
-            render_tiles(ctx, ds, cam, st, live, fbs[2 * half], done, n, sync=False, framebuffer_sq=fbs[2 * half + 1])
-            if guided:
-                render_features(ctx, ds, cam, st, live, feat_fbs[0], done, n, sync=False, features_sq=feat_fbs[1])
-            ctx.synchronize()
-            done, j = done + n, j + 1
-            n_half[half] += n
-            if done < st.sample_count:
-                errors = [None] * len(live)
-                if adaptive and j % 2 == 0 and done >= st.adaptive_min_samples:
-                    # only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
-                    all_a, all_b = done_a + [n_half[0]] * len(live), done_b + [n_half[1]] * len(live)
-                    if guided:
-                        guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
-                                     tau=st.denoise_feature_tau)
-                    if st.denoise_dual_atrous:
-                        where = dict(region=live) if st.denoise_dual_atrous_region else {}  # (off: exactly the call made before the region form existed)
-                        slope = st.atrous_slope_keyword() if guided else {}  # (set: the check is rmd_denoise_atrous_dual_slope[_region])
-                        denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img,
-                                            levels=st.denoise_atrous_levels, k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **where, **slope)
-                    else:
-                        slope = st.slope_keyword() if guided else {}  # (set: the check is rmd_denoise_dual_guided_slope_region)
-                        denoise_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), done_rects + live, all_a, all_b, out_fb, err_img, region=live, **params, **guide, **slope)
-                    errors = tile_error_dual(ctx, err_img, live)
-                conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
-                finish([r for r, c in zip(live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
-                still = [r for r, c in zip(live, conv) if not c]
-                if still and st.progress_tiles:  # progress snapshots: the two halves' sums added
-                    pa, pb = fbs[0].download_tiles(still), fbs[2].download_tiles(still)
-                    for (l, t, w, h), e, a, b in zip(still, [e for e, c in zip(errors, conv) if not c], pa, pb):
-                        messages.append(Message.TileProgressed(Tile(l, t, w, h, done, a + b, None if e is None else float(e))))
-                if still and st.preview_every and j % st.preview_every == 0:
-                    # the whole frame: finished tiles at the counts they finished with, live ones at n_A + n_B, the two halves' sums added on the device
-                    rects = done_rects + still
-                    all_a, all_b = done_a + [n_half[0]] * len(still), done_b + [n_half[1]] * len(still)
-                    if preview_fb is None:
-                        src, src_counts, second = fbs[0], [a + b for a, b in zip(all_a, all_b)], fbs[2]
-                    else:
-                        if guided:
-                            guide = dict(features=feat_fbs[0], features_sq=feat_fbs[1], counts_f=[a + b for a, b in zip(all_a, all_b)], k_f=st.denoise_feature_k,
-                                         tau=st.denoise_feature_tau)
-                        slope = st.atrous_slope_keyword() if guided else {}  # (set: the preview is rmd_denoise_atrous_dual_slope's)
-                        denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), rects, all_a, all_b, preview_fb, None, levels=st.denoise_atrous_levels,
-                                            k=st.denoise_atrous_k, alpha=st.denoise_alpha, **guide, **slope)
-                        src, src_counts, second = preview_fb, [1] * len(rects), None  # (means)
-                    exposure = None
-                    if st.preview_auto_exposure:
-                        exposure = exposure_from_histogram(luminance_histogram(ctx, src, rects, src_counts, second=second), st.auto_exposure_percentile,
-                                                           st.auto_exposure_target)
-                    packed = resolve_tonemap_tiles(ctx, src, rects, src_counts, st.preview_exposure if exposure is None else exposure, st.preview_gamma,
-                                                   second=second)
-                    messages.append(Message.FramePreview(scatter_tiles(rects, packed, W, H), j, done, exposure))
-                live = still
-        finish(live)
-        messages = messages + finished  # progress snapshots first, then the finished tiles
-    finally:
-        for o in reversed(opened):
-            try:
-                o.close()
-            except Exception:  # noqa: BLE001 (a failing close must not keep the others open, nor hide the body's own error)
-                pass
+    with contextlib.ExitStack() as stack:
+        messages = _DualLoop(stack, scene, settings, devices[0]).run()
     return TaskHandle(settings, messages, devices[0], scene if settings.denoise_dual_features or settings.denoise_dual_select else None)

@@ -390,6 +390,19 @@ class Settings:
         return [dict(k=self.denoise_k, alpha=self.denoise_alpha), dict(k=1.0, alpha=self.denoise_alpha, guided=True, k_f=self.denoise_feature_k,
                                                                       tau=self.denoise_feature_tau, **self.slope_keyword())]
 
+    def nlm_keywords(self):
+        """The non-local-means filters' parameters (render.denoise, denoise_guided, denoise_dual) from the settings."""
+        return dict(radius=self.denoise_radius, patch_radius=self.denoise_patch, k=self.denoise_k, alpha=self.denoise_alpha)
+
+    def atrous_keywords(self):
+        """The a-trous filters' parameters (render.denoise_atrous, denoise_atrous_dual) from the settings."""
+        return dict(levels=self.denoise_atrous_levels, k=self.denoise_atrous_k, alpha=self.denoise_alpha)
+
+    def guide_keywords(self, atrous=False):
+        """The feature weight's parameters for a guided filter — a non-local-means one, or with `atrous` an a-trous one —: k_f, tau and that family's slope
+        keyword.  The feature buffers and their counts are the caller's (render._guide)."""
+        return dict(k_f=self.denoise_feature_k, tau=self.denoise_feature_tau, **(self.atrous_slope_keyword() if atrous else self.slope_keyword()))
+
     def slope_keyword(self):
         """{} while denoise_feature_slope is off — the calls made are then those made before it existed —, else dict(slope=denoise_feature_slope)."""
         return dict(slope=self.denoise_feature_slope) if self.denoise_feature_slope > 0.0 else {}
