@@ -135,6 +135,11 @@ rmd_status rmd_probe_denoise_scratch(uint32_t form, uint32_t width, uint32_t hei
  * features then hold the seven slope planes behind every other part, each of which keeps its offset.  (A value of its own: 1 leaves the a-trous forms alone.) */
 rmd_status rmd_probe_denoise_scratch_slope(uint32_t form, uint32_t width, uint32_t height, uint32_t n_rects, uint32_t guided, uint32_t sloped, uint32_t n_cands,
                                            uint64_t n_table, uint64_t *out3, uint64_t *total);
+/* Host only: the workgroup tile of the non-local-means kernels at a window (raymond_amd/csrc/denoise.hip: denoise_tile_width and denoise_lds_bytes — the
+ * functions every launcher of rmd_denoise, rmd_denoise_dual, their guided, region and slope forms and rmd_denoise_dual_select sizes its launch with).
+ * out4[0] = the tile width the launch takes (32 or 24), out4[1] = its dynamic LDS in bytes, out4[2] = the 32-wide tile's LDS in bytes, out4[3] = the LDS
+ * budget in bytes.  RMD_ERR_INVALID_ARGUMENT past the header's limits (radius > 12, patch_radius > 4). */
+rmd_status rmd_probe_denoise_tile(uint32_t radius, uint32_t patch_radius, uint64_t *out4);
 /* The slope floors of the _slope denoise calls as the device makes them (raymond_amd/csrc/denoise.hip: feature_slope_kernel, through the launcher the entry
  * points call): fplanes7 = the seven planar per-pixel feature means f (W*H doubles each, HOST memory; a NaN in plane 0 marks a pixel that is not
  * feature-valid), mplanes7 = the seven planes m_j = (slope * slope) * (h_j + v_j) of include/raymond_hip.h, zeros at a pixel that is not feature-valid. */

@@ -331,6 +331,13 @@ rmd_status rmd_probe_denoise_scratch_slope(uint32_t form, uint32_t width, uint32
 	return RMD_OK;
 }
 
+rmd_status rmd_probe_denoise_tile(uint32_t radius, uint32_t patch_radius, uint64_t *out4) {
+	if (radius > rmd::kDenoiseMaxRadius || patch_radius > rmd::kDenoiseMaxPatch || !out4) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	const uint32_t tw = rmd::denoise_tile_width(radius, patch_radius);
+	out4[0] = tw, out4[1] = rmd::denoise_lds_bytes(tw, radius, patch_radius), out4[2] = rmd::denoise_lds_bytes(32u, radius, patch_radius), out4[3] = rmd::kLdsBudgetBytes;
+	return RMD_OK;
+}
+
 rmd_status rmd_probe_feature_slope(rmd_context *ctx, const double *fplanes7, uint32_t width, uint32_t height, double slope, double *mplanes7) {
 	if (!ctx || !fplanes7 || !mplanes7 || width == 0 || height == 0) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
 	RMD_HIP(ctx, hipSetDevice(ctx->device));

@@ -44,6 +44,7 @@ _SIGS = {
     "rmd_probe_feature_slope": [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp],
     "rmd_probe_atrous_region_slope_planes": [_vp, C.c_uint32, C.c_uint32, _vp],
     "rmd_probe_denoise_scratch_slope": [C.c_uint32] * 7 + [C.c_uint64, _vp, _P(C.c_uint64)],
+    "rmd_probe_denoise_tile": [C.c_uint32, C.c_uint32, _vp],
 }
 PATH_STRIDE = 17
 _ready = False
@@ -352,3 +353,11 @@ def denoise_scratch(form, width, height, n_rects, guided=False, n_cands=0, n_tab
         _host_check(L.rmd_probe_denoise_scratch_slope(SCRATCH_FORMS.index(form), width, height, n_rects, int(guided), int(sloped), n_cands, n_table, _p(out),
                                                       C.byref(total)), "rmd_probe_denoise_scratch_slope")
     return {name: (int(o), int(b)) for name, (used, o, b) in zip(SCRATCH_PARTS, out) if used}, total.value
+
+
+def denoise_tile(radius, patch_radius):
+    """Host only: the non-local-means kernels' workgroup tile at a window -> (tile width, its LDS bytes, the 32-wide tile's LDS bytes, the LDS budget), from
+    the functions the launchers size their launch with.  api: rmd_probe_denoise_tile."""
+    out = np.zeros(4, dtype=np.uint64)
+    _host_check(_L().rmd_probe_denoise_tile(int(radius), int(patch_radius), _p(out)), "rmd_probe_denoise_tile")
+    return tuple(int(v) for v in out)
