@@ -258,7 +258,8 @@ enum {
 	                              axis-aligned room) tested with one component of the ray: 0 = the library's choice (yes, in scenes of regular
 	                              parameters — and, in such a scene without a grid, a launch without the thin lens gives the generation trips of the
 	                              spheres kernel their own candidate sets: the spheres and the one pair their tile's primary rays can hit),
-	                              1 = never (every pair takes the general test, no candidate sets), 2 = the pairs as for 0, no candidate sets.
+	                              1 = never (every pair takes the general test, no candidate sets), 2 = the pairs as for 0, no candidate sets,
+	                              3 = as 0 without the tile classes (work items whose tile sees one emitting or one black wall: every item is general).
 	                              Same samples, bit for bit, whatever the value                                                              */
 	RMD_TUNE_PATH_QUEUES = 9,  /* RMD_PATH_QUEUES: persistent split launches of scenes with grids keep their paths in queues in device memory — ray
 	                              compaction between bounces: a wave's trips are 64 new samples, 64 parked hits or one grid walk for 64 parked rays

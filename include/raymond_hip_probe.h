@@ -90,6 +90,13 @@ rmd_status rmd_probe_triangle_sphere(size_t n, const double *pos9, double *out5)
  * predicate drops to the oracle's primary rays. */
 rmd_status rmd_probe_primary_candidates(const rmd_camera *cam, const rmd_settings *settings, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids,
                                         int64_t axis_pairs_tunable, size_t n_tiles, const uint32_t *tiles4, uint64_t *launch3, uint64_t *out2);
+/* Host only (no device needed): the tile class the role-sorted spheres kernel gives a work item of each 8x8 wave tile (raymond_amd/csrc/
+ * primary_candidates.hpp: primary_one_wall, primary_wall_class — the functions the kernel itself evaluates once per work item).  Arguments as
+ * rmd_probe_primary_candidates'.  launch1[0] = whether the classes are on for this launch (the candidate sets' conditions, RMD_TUNE_AXIS_PAIRS = 0
+ * and black paths ended); out2 = per tile the class (0 general, 1 emitter, 2 black) and the object every primary ray of the tile hits (-1 for a
+ * general tile).  tests/test_tile_classes.py holds both to the oracle. */
+rmd_status rmd_probe_tile_classes(const rmd_camera *cam, const rmd_settings *settings, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids,
+                                  int64_t axis_pairs_tunable, size_t n_tiles, const uint32_t *tiles4, uint32_t *launch1, int32_t *out2);
 /* Host only (no device needed): the form of a render launch as launch_render chooses it (raymond_amd/csrc/launch.hpp: LaunchPlan).  mode 0 = tiles
  * (direct), 1 = tiles buffered (split), 2 = list; grid = 1: the grid instantiation.  Per entry in5 = n_objects, mask_words_total, flags (1 = path
  * queues attached, 2 = persistence asked for — CUs and a work counter given —, 4 = chain_items, 8 = the squares asked for), n_waves, n_cus;

@@ -208,9 +208,9 @@ bool primary_cull_allowed(const RenderParams &P) {
 // in a scene of regular parameters.  The reference's sample is then NaN unless the plane emits, so the two rules that end a path with L = 0 — a hit
 // at the bounce limit, a diffuse bounce off a black surface — do not hold for such a launch (make_params).  "On": the numerator dot(o - cam, -n) of
 // the plane test is zero, or so small (1e-9 of the sum of its terms' magnitudes: a distance no frame shows) that cam + t rd may round to cam.
-static bool camera_on_a_plane(const rmd_scene *scene, const rmd_camera *cam) {
-	for (size_t i = 0; i + 6 <= scene->planes.size(); i += 6) {
-		const double *o = &scene->planes[i], *n = o + 3;
+bool camera_on_a_plane(const std::vector<double> &planes, const rmd_camera *cam) {
+	for (size_t i = 0; i + 6 <= planes.size(); i += 6) {
+		const double *o = &planes[i], *n = o + 3;
 		double num = 0.0, scale = 0.0;
 		for (int a = 0; a < 3; a++) num += (o[a] - cam->position[a]) * -n[a], scale += (std::fabs(o[a]) + std::fabs(cam->position[a])) * std::fabs(n[a]);
 		if (!(std::fabs(num) > 1e-9 * scale)) return true; // (a NaN too)
@@ -244,12 +244,13 @@ RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const r
 	// — AND whose parameters are all inside the class for which that is proved (rmd_scene::regular: an Emission of (inf, 0, 0), a NaN colour, a
 	// material of roughness 0 or a sphere of radius 0 make non-finite radiance reachable without a mesh; such a scene is traced like one with a grid)
 	// — AND whose camera does not lie on one of its planes (camera_on_a_plane: the view direction of a hit at t = 0 is NaN)
-	const bool on_plane = scene && camera_on_a_plane(scene, cam);
-	P.end_black_paths = (st->flags & RMD_RENDER_TRACE_BLACK_PATHS) ? 0u : ((st->flags & RMD_RENDER_END_BLACK_PATHS) || !scene || (scene->n_grids == 0u && scene->regular && !on_plane)) ? 1u : 0u;
+	const bool on_plane = scene && rmd::camera_on_a_plane(scene->planes, cam);
+	P.end_black_paths = rmd::end_black_paths_rule(st->flags, scene != nullptr, scene ? scene->n_grids : 0u, scene ? scene->regular : false, on_plane) ? 1u : 0u;
 	P.shade_last_depth = (scene && (!scene->regular || on_plane)) ? 1u : 0u;
 	P.axis_pairs = scene ? scene->axis_pairs : 0u;
 	P.visit_mask = scene ? scene->visit_mask : ~0ull, P.grid_mask = scene ? scene->grid_mask : ~0ull;
-	P.primary_cull = (scene && scene->primary_cull && rmd::primary_cull_allowed(P)) ? 1u : 0u;
+	// (bit 1, the tile classes, only where a black bounce is ended: primary_candidates.hpp)
+	P.primary_cull = (scene && rmd::primary_cull_allowed(P)) ? (scene->primary_cull & (P.end_black_paths != 0u ? 3u : 1u)) : 0u;
 	P.fault = ctx ? ctx->d_fault : nullptr;
 	P.walk_batch = rmd::kWalkBatchDefault;
 	if (ctx && ctx->tunable[RMD_TUNE_WALK_BATCH] > 0) P.walk_batch = (uint32_t)ctx->tunable[RMD_TUNE_WALK_BATCH]; // any value gives the same image
@@ -528,8 +529,9 @@ static rmd_status scene_create_impl(rmd_context *ctx, const rmd_object *objects,
 	sc->visit_mask = derived.visit_mask, sc->grid_mask = derived.grid_mask;
 	for (uint32_t i = 0; i < n_objects; i++)
 		if (objects[i].geometry_kind == RMD_GEOM_PLANE) sc->planes.insert(sc->planes.end(), objects[i].origin, objects[i].origin + 3), sc->planes.insert(sc->planes.end(), objects[i].normal, objects[i].normal + 3);
-	// the generation trips' own candidate sets (primary_candidates.hpp): a regular scene without a grid, unless RMD_TUNE_AXIS_PAIRS says 1 or 2
-	sc->primary_cull = regular && n_grids == 0u && ctx->tunable[RMD_TUNE_AXIS_PAIRS] == 0;
+	// the generation trips' own candidate sets and the items' tile classes (primary_candidates.hpp): a regular scene without a grid, unless
+	// RMD_TUNE_AXIS_PAIRS says 1 or 2 (neither) or 3 (no tile classes)
+	sc->primary_cull = rmd::primary_cull_bits(regular, n_grids, ctx->tunable[RMD_TUNE_AXIS_PAIRS]);
 	for (uint32_t i = 0; i < n_objects; i++) sc->n_grid_objects += objects[i].geometry_kind == RMD_GEOM_GRID ? 1u : 0u;
 	auto upload = [&](const void *src, size_t bytes, void **dst) -> hipError_t {
 		*dst = nullptr;
@@ -794,8 +796,8 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, settings);
 	P.n_work = ctx->n_wave_tiles;
 	if (P.debug_flags & 24u) {
-		RMD_HIP(ctx, ctx->debug_counters.grow(48 * sizeof(unsigned long long)));
-		RMD_HIP(ctx, hipMemsetAsync(ctx->debug_counters.as<void>(), 0, 48 * sizeof(unsigned long long), ctx->stream));
+		RMD_HIP(ctx, ctx->debug_counters.grow(64 * sizeof(unsigned long long)));
+		RMD_HIP(ctx, hipMemsetAsync(ctx->debug_counters.as<void>(), 0, 64 * sizeof(unsigned long long), ctx->stream));
 		P.debug_counters = ctx->debug_counters.as<unsigned long long>();
 	}
 	bool buffered = false;
@@ -906,7 +908,7 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 	RMD_HIP(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
 	ctx->timed = true;
 	if (P.debug_flags & 24u) {
-		unsigned long long h[48];
+		unsigned long long h[64];
 		RMD_HIP(ctx, hipMemcpyAsync(h, ctx->debug_counters.as<void>(), sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
 		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		if ((P.debug_flags & 16u) && ctx->last_launch.queued) {
@@ -930,6 +932,9 @@ static rmd_status render_tiles_async_impl(rmd_context *ctx, const rmd_scene *sce
 		if ((P.debug_flags & 16u) == 0u && ctx->last_launch.buffered && scene->n_grids == 0u) // (the role-sorted spheres kernel: render_wave_sorted)
 			std::fprintf(stderr, "[rmd debug] lobe trips: diffuse trips=%llu diffuse hits shaded=%llu ggx trips=%llu ggx hits shaded=%llu | hits parked: diffuse=%llu ggx=%llu\n", h[37], h[38], h[39],
 			             h[40], h[41], h[42]);
+		if ((P.debug_flags & 16u) == 0u && ctx->last_launch.buffered && scene->n_grids == 0u) // (its items' tile classes: primary_candidates.hpp)
+			std::fprintf(stderr, "[rmd debug] tile classes: general items=%llu emitter items=%llu black items=%llu | black rounds=%llu cut short=%llu samples ended in pass A=%llu survivors=%llu | samples checked against their full path=%llu that are not what the class says (must be 0)=%llu rays that hit another object than the wall (must be 0)=%llu\n",
+			             h[48], h[49], h[50], h[52], h[54], h[51], h[53], h[55], h[56], h[57]);
 		if ((P.debug_flags & 16u) == 0u && ctx->last_launch.queued)
 			std::fprintf(stderr, "[rmd debug] path queues: rays pushed=%llu (of them walks put aside=%llu) rays held in their lanes=%llu hits pushed=%llu hits held in their lanes=%llu\n", h[19], h[22], h[23], h[20], h[21]);
 	}

@@ -116,7 +116,7 @@ struct RenderParams {
 	uint32_t split_k;          // >1: each wave tile's sample range is split over split_k waves writing to sample_buf
 	double *sample_buf;        // [wave tile][sample - sample_begin][lane][3] f64, only when split_k > 1
 	uint32_t debug_flags;      // diagnostics (RMD_DEBUG env): 1 = skip triangle tests, 2 = skip grid walks (timing only, wrong results), 8 = count walk events
-	unsigned long long *debug_counters; // 48 counters (api.cpp), only touched when debug_flags & 8 / 16
+	unsigned long long *debug_counters; // 64 counters (api.cpp), only touched when debug_flags & 8 / 16
 	uint32_t *work_counter;             // persistent launches: the next work item (zeroed by the host before the launch)
 	uint32_t *tile_done;                // split launches: finished waves per wave tile (zeroed by the host); the last one adds the tile's samples
 	uint32_t end_black_paths;           // 1: a path whose throughput is exactly (0, 0, 0) is ended — scenes without grids unless RMD_RENDER_TRACE_BLACK_PATHS, scenes with grids only with RMD_RENDER_END_BLACK_PATHS (api.cpp: make_params)

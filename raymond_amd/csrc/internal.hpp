@@ -124,7 +124,8 @@ struct rmd_scene {
 	uint32_t axis_pairs = 0; // RenderParams::axis_pairs
 	unsigned long long visit_mask = ~0ull, grid_mask = ~0ull; // RenderParams::visit_mask / grid_mask
 	uint32_t walk_steps_bound = 0; // RenderParams::walk_steps_bound
-	bool primary_cull = false; // the scene's half of RenderParams::primary_cull: regular, no grid, RMD_TUNE_AXIS_PAIRS = 0 when it was created
+	uint32_t primary_cull = 0; // the scene's half of RenderParams::primary_cull: regular, no grid; by RMD_TUNE_AXIS_PAIRS when it was created 3 (candidate
+	                           // sets and tile classes: 0), 1 (candidate sets only: 3) or 0 (neither: 1, 2)
 	bool regular = true; // every parameter the kernel reads is finite and inside the class for which ending zero-throughput paths is exact (api.cpp: rmd_scene_create)
 	std::vector<double> planes; // origin and normal of every plane object, six numbers each: make_params asks whether the camera lies ON one
 	rmd::DevObject *d_objects = nullptr;
@@ -256,6 +257,17 @@ bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t wid
 rmd_status check_fault(rmd_context *ctx);
 RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const rmd_camera *cam, const rmd_settings *st);
 bool primary_cull_allowed(const RenderParams &P);
+// RenderParams::primary_cull of a launch whose own half holds: bit 0 the candidate sets, bit 1 the tile classes (primary_candidates.hpp)
+inline uint32_t primary_cull_bits(bool regular, uint32_t n_grids, int64_t axis_pairs_tunable) {
+	if (!regular || n_grids != 0u) return 0u;
+	return axis_pairs_tunable == 0 ? 3u : axis_pairs_tunable == 3 ? 1u : 0u;
+}
+// RenderParams::end_black_paths of a launch (make_params has the argument): TRACE never ends a zero-throughput path, END always, flags 0 only where it is exact
+inline bool end_black_paths_rule(uint32_t flags, bool has_scene, uint32_t n_grids, bool regular, bool on_plane) {
+	return (flags & RMD_RENDER_TRACE_BLACK_PATHS) ? false : ((flags & RMD_RENDER_END_BLACK_PATHS) || !has_scene || (n_grids == 0u && regular && !on_plane));
+}
+// Does the camera lie on (or within 1e-9 of) one of the planes?  planes: origin and normal, six numbers each (api.cpp)
+bool camera_on_a_plane(const std::vector<double> &planes, const rmd_camera *cam);
 // The role-sorted spheres kernel's two-part work list (api.cpp, beside choose_split; work_list.hpp has the mapping the kernel shares)
 WorkPlan plan_work_list(uint32_t wave_slots, uint32_t n_tiles, uint32_t sample_count, uint32_t k_uniform, uint32_t min_samples = kTailMinSamples,
                         uint32_t tail_x2 = kTailTilesPerSlotX2, uint32_t tail_parts = kTailParts, uint32_t n_tail_forced = 0u);

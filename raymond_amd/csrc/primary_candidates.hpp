@@ -133,38 +133,104 @@ RMD_HD bool primary_sphere_cleared(const TileCone &T, const CullCamera &c, const
 	return in_front && D > r + margin && K <= 1e150;
 }
 
-// The 10-bit fields of `axis_pairs` that stay for the tile's primary rays: all of them, or the one pair that holds every ray's closest wall hit.
-RMD_HD uint32_t primary_pairs_kept(const TileCone &T, const CullCamera &c, const AxisWalls walls[3], uint32_t axis_pairs) {
-	if (!T.ok) return axis_pairs;
+// The one axis pair that holds every ray's closest wall hit, if there is one: its axis k, and whether the rays face the wall with normal -e_k
+// (u_k > 0 over the whole rectangle: coordinate o_minus, object idx_minus) or the one with normal +e_k.  false: no pair qualifies.
+RMD_HD bool primary_pair_alone(const TileCone &T, const CullCamera &c, const AxisWalls walls[3], uint32_t axis_pairs, int &k_alone, bool &faces_minus) {
+	if (!T.ok) return false;
 	double s_lo[3], s_hi[3]; // per paired axis: lower bound of t / |u| of whatever the pair registers; upper bound if it qualifies to be kept (else -1)
-	bool paired[3];
+	bool paired[3], minus[3];
+#pragma unroll
 	for (int k = 0; k < 3; k++) {
 		paired[k] = ((axis_pairs >> (10 * k)) & 1023u) != 0u;
-		s_lo[k] = 0.0, s_hi[k] = -1.0;
+		s_lo[k] = 0.0, s_hi[k] = -1.0, minus[k] = false;
 		if (!paired[k]) continue;
 		const double num_plus = c.pos[k] - walls[k].o_plus, num_minus = walls[k].o_minus - c.pos[k];
-		if (!(num_plus > 0.0 && num_minus > 0.0)) return axis_pairs; // the camera is not strictly inside the room on this axis (or a NaN)
+		if (!(num_plus > 0.0 && num_minus > 0.0)) return false; // the camera is not strictly inside the room on this axis (or a NaN)
 		const double lo = k < 2 ? T.lo[k] : 1.0, hi = k < 2 ? T.hi[k] : 1.0;
 		// the nearest hit the pair can register: over the part of the interval that faces the -e_k wall (u_k > 0) and the part that faces the other
 		double nearest = 1e300; // (num / max |u_k| of each part; a part that does not exist registers nothing)
 		if (hi > 0.0) nearest = cull_min(nearest, num_minus / hi);
 		if (lo < 0.0) nearest = cull_min(nearest, num_plus / -lo);
 		s_lo[k] = nearest;
-		if (!(s_lo[k] > 0.0)) return axis_pairs;
+		if (!(s_lo[k] > 0.0)) return false;
 		const bool pos = lo > 0.0, neg = hi < 0.0;
 		if (pos || neg) {
 			const double u_lo = pos ? lo : -hi;
-			if (u_lo > kCullFacing * T.u_max) s_hi[k] = (pos ? num_minus : num_plus) / u_lo;
+			if (u_lo > kCullFacing * T.u_max) s_hi[k] = (pos ? num_minus : num_plus) / u_lo, minus[k] = pos;
 		}
 	}
+	bool found = false; // (the first pair that qualifies; written without an early exit: the kernel keeps all of this in registers)
+#pragma unroll
 	for (int k = 0; k < 3; k++) {
-		if (!paired[k] || !(s_hi[k] > 0.0)) continue;
-		bool alone = true;
+		bool alone = paired[k] && s_hi[k] > 0.0 && !found;
+#pragma unroll
 		for (int j = 0; j < 3; j++)
 			if (j != k && paired[j]) alone = alone && s_hi[k] * (1.0 + kCullPairMargin) < s_lo[j];
-		if (alone) return axis_pairs & (1023u << (10 * k));
+		if (alone) found = true, k_alone = k, faces_minus = minus[k];
 	}
-	return axis_pairs;
+	return found;
+}
+// The 10-bit fields of `axis_pairs` that stay for the tile's primary rays: all of them, or the one pair that holds every ray's closest wall hit.
+RMD_HD uint32_t primary_pairs_kept(const TileCone &T, const CullCamera &c, const AxisWalls walls[3], uint32_t axis_pairs) {
+	int k = 0;
+	bool faces_minus = false;
+	return primary_pair_alone(T, c, walls, axis_pairs, k, faces_minus) ? axis_pairs & (1023u << (10 * k)) : axis_pairs;
+}
+
+// TILE CLASSES.  What the role-sorted spheres kernel knows of a work item's samples before it draws one of them (render_kernel.hpp:
+// render_wave_sorted).  Admission: the candidate sets' own (RenderParams::primary_cull — a regular scene without a grid, no thin lens, a finite
+// camera) and RenderParams::end_black_paths != 0; anything else is kTileGeneral and runs the general code.
+//
+// ONE WALL.  The tile's primary rays all end on one and the same wall when
+//   (a) the scene has at most 64 objects and the candidate visit mask is EMPTY: every sphere among them is cleared (primary_sphere_cleared: it
+//       registers no hit for any ray of the cone) and no other object has a turn in the object loop — an unpaired plane, a plane pair that is
+//       not an axis pair and an object from 64 on all keep theirs, and make the tile general;
+//   (b) primary_pair_alone holds for a pair k.  Its conditions are the ones a definite wall needs, with the margins derived above: (1) u_k keeps
+//       one sign over the widened rectangle, so every ray faces the same wall of the pair — the one with normal -e_k for u_k > 0 —, and
+//       |rd_k| >= min |u_k| / max |u| > 2e-6, twice axis_pair_test's facing threshold against <= 3 eps of rounding: the denominator test
+//       `|rd_k| > 1e-6` passes in every lane; (2) the wall's numerator, the very subtraction axis_pair_test makes (o_minus - ro_k resp.
+//       ro_k - o_plus, ro = cam_pos exactly), is positive: a subtraction's sign is exact, so t = num / |rd_k| > 0 >= 0 registers, and it is finite
+//       (num <= 2e150, |rd_k| > 1e-6) and so beats the loop's initial kFMax; (3) every other pair's hit is strictly farther.
+// Then Scene::intersect returns that wall's object for every ray of the tile, whatever its jitter: nothing else registers a hit, or a closer one.
+//
+// FROM THE WALL'S RECORD.  kTileEmitter when material_kind == 2: the sample is hadamard((1, 1, 1), colour) = the colour, bit for bit (1.0 * x = x
+// for every finite x, and a regular scene's colours are finite), and no random number enters it.  kTileBlack when kObjBlackDiffuse is set and
+// prob_d = lerp(0.5, 0, metalness) = 0.5 + metalness * (0 - 0.5) compares equal to 0.5 — then `lobe_bits < 2^21`, the classification's test, and
+// bounce_is_diffuse (lobe_bits * 2^-22 < prob_d) are the same statement: a sample whose block 0 has lobe_bits < 2^21 is (0, 0, 0), any other is
+// parked as a GGX hit.  Anything else: general.
+// The classification ends such a hit only if finite_inputs holds (the normal's and the hit point's components sum to something finite).  Here it
+// does: the wall's normal is +-e_k exactly, and frag = cam_pos + rd * t with |cam_pos_a| <= 1e150 (cull_camera_ok: part of the admission), |rd_a| <= 1 + 3 eps and
+// 0 < t <= 2e150 / 1e-6: every component below 3e156.  The wall coordinates are tame (|o| <= 1e150: the scene is regular) and compared with
+// the camera's in (2); a NaN there fails the comparison and the tile is general.
+enum : uint32_t { kTileGeneral = 0u, kTileEmitter = 1u, kTileBlack = 2u };
+constexpr uint32_t kTileClassShift = 30u; // the class rides in the two bits the three 10-bit pair fields leave free (render_kernel.hpp: item_candidates)
+// The object every primary ray of the tile hits, or -1.  alone, faces_minus: primary_pair_alone's answer for the tile (one evaluation serves the
+// candidate pairs and the class), pair: the kept pair's record (the kernel reads it where the scene keeps it: a copy of the three records indexed
+// by k would live in scratch memory); `visit` is the tile's candidate visit mask (the launch's mask less the cleared spheres).
+RMD_HD int primary_one_wall(bool alone, bool faces_minus, const AxisWalls &pair, unsigned long long visit, uint32_t n_objects) {
+	return (alone && visit == 0ull && n_objects - 1u < 64u) ? // (1 .. 64 objects: a pair that is alone has two)
+	       (int)(faces_minus ? pair.idx_minus : pair.idx_plus) : -1;
+}
+RMD_HD uint32_t primary_wall_class(uint32_t material_kind, uint32_t flags, double metalness);
+// The whole composition, for the kernel (item_candidates) and the host probe alike: the class of a tile whose candidate visit mask is `visit` and
+// whose pair test answered (alone, k_alone, faces_minus), and in `wall` the object every primary ray of a classed tile hits.  walls: the scene's three
+// records where it keeps them; objs: its object table (the kernel's staged copy).
+RMD_HD uint32_t primary_tile_class(bool alone, int k_alone, bool faces_minus, const AxisWalls *walls, unsigned long long visit, uint32_t n_objects, const DevObject *objs,
+                                   uint32_t &wall);
+RMD_HD uint32_t primary_wall_class(uint32_t material_kind, uint32_t flags, double metalness) {
+	if (material_kind == 2u) return kTileEmitter;
+	const double prob_d = 0.5 + metalness * (0.0 - 0.5); // device_core.hpp: lerp(0.5, 0.0, metal), bounce_is_diffuse's operand
+	return ((flags & kObjBlackDiffuse) != 0u && prob_d == 0.5) ? kTileBlack : kTileGeneral;
+}
+RMD_HD uint32_t primary_tile_class(bool alone, int k_alone, bool faces_minus, const AxisWalls *walls, unsigned long long visit, uint32_t n_objects, const DevObject *objs,
+                                   uint32_t &wall) {
+	wall = 0u;
+	const int w = primary_one_wall(alone, faces_minus, walls[alone ? k_alone : 0], visit, n_objects);
+	if (w < 0) return kTileGeneral;
+	const DevObject &o = objs[w];
+	const uint32_t cls = primary_wall_class(o.material_kind, o.flags, o.metalness);
+	if (cls != kTileGeneral) wall = (uint32_t)w;
+	return cls;
 }
 
 } // namespace rmd

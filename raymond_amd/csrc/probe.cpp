@@ -251,7 +251,7 @@ rmd_status rmd_probe_primary_candidates(const rmd_camera *cam, const rmd_setting
 		if (rmd_status s = rmd::derive_scene_objects(nullptr, objects, n_objects, n_grids, axis_pairs_tunable, sc)) return s;
 		// (the launch's parameters as make_params makes them; the scene's half of the switch as rmd_scene_create sets it)
 		const rmd::RenderParams P = rmd::make_params(nullptr, nullptr, cam, settings);
-		const bool on = sc.regular && n_grids == 0u && axis_pairs_tunable == 0 && rmd::primary_cull_allowed(P);
+		const bool on = (rmd::primary_cull_bits(sc.regular, n_grids, axis_pairs_tunable) & 1u) != 0u && rmd::primary_cull_allowed(P);
 		launch3[0] = sc.visit_mask, launch3[1] = sc.axis_pairs, launch3[2] = on ? 1u : 0u;
 		rmd::CullCamera cc;
 		for (int a = 0; a < 3; a++) cc.pos[a] = P.cam_pos[a];
@@ -268,6 +268,44 @@ rmd_status rmd_probe_primary_candidates(const rmd_camera *cam, const rmd_setting
 				pairs = rmd::primary_pairs_kept(cone, cc, sc.walls, sc.axis_pairs);
 			}
 			out2[i * 2] = visit, out2[i * 2 + 1] = pairs;
+		}
+		return RMD_OK;
+	});
+}
+
+rmd_status rmd_probe_tile_classes(const rmd_camera *cam, const rmd_settings *settings, const rmd_object *objects, uint32_t n_objects, uint32_t n_grids,
+                                  int64_t axis_pairs_tunable, size_t n_tiles, const uint32_t *tiles4, uint32_t *launch1, int32_t *out2) {
+	if (!cam || !settings || (n_objects && !objects) || !launch1 || (n_tiles != 0 && (!tiles4 || !out2))) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	return rmd::guarded(nullptr, "rmd_probe_tile_classes", [&]() -> rmd_status {
+		rmd::SceneObjects sc;
+		if (rmd_status s = rmd::derive_scene_objects(nullptr, objects, n_objects, n_grids, axis_pairs_tunable, sc)) return s;
+		// (the launch's parameters as make_params makes them for a scene: end_black_paths asks for a regular scene without a grid whose planes the
+		// camera does not lie on, unless the settings say otherwise)
+		const rmd::RenderParams P = rmd::make_params(nullptr, nullptr, cam, settings);
+		std::vector<double> planes;
+		for (uint32_t i = 0; i < n_objects; i++)
+			if (objects[i].geometry_kind == RMD_GEOM_PLANE) planes.insert(planes.end(), objects[i].origin, objects[i].origin + 3), planes.insert(planes.end(), objects[i].normal, objects[i].normal + 3);
+		const bool end_black = rmd::end_black_paths_rule(settings->flags, true, n_grids, sc.regular, rmd::camera_on_a_plane(planes, cam)); // (make_params' own rule)
+		const bool on = rmd::primary_cull_bits(sc.regular, n_grids, axis_pairs_tunable) == 3u && rmd::primary_cull_allowed(P) && end_black;
+		launch1[0] = on ? 1u : 0u;
+		rmd::CullCamera cc;
+		for (int a = 0; a < 3; a++) cc.pos[a] = P.cam_pos[a];
+		cc.width = P.width, cc.height = P.height, cc.aspect = P.aspect, cc.tan_half_fov = P.tan_half_fov;
+		for (size_t i = 0; i < n_tiles; i++) {
+			const uint32_t *t = tiles4 + i * 4;
+			out2[i * 2] = (int32_t)rmd::kTileGeneral, out2[i * 2 + 1] = -1;
+			if (!on) continue;
+			if (t[2] == 0u || t[2] > 8u || t[3] == 0u || t[3] > 8u || t[0] > 65535u || t[1] > 65535u) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: a wave tile is 1..8 pixels a side");
+			const rmd::TileCone cone = rmd::primary_tile_cone(cc, t[0], t[1], t[2], t[3]);
+			uint64_t visit = sc.visit_mask;
+			for (uint32_t j = 0; j < n_objects && j < 64u; j++)
+				if (sc.objs[j].geometry_kind == 1u && rmd::primary_sphere_cleared(cone, cc, sc.objs[j].origin, sc.objs[j].radius)) visit &= ~(1ull << j);
+			int k_alone = 0;
+			bool faces_minus = false;
+			const bool alone = rmd::primary_pair_alone(cone, cc, sc.walls, sc.axis_pairs, k_alone, faces_minus);
+			uint32_t wall = 0u;
+			const uint32_t cls = rmd::primary_tile_class(alone, k_alone, faces_minus, sc.walls, visit, n_objects, sc.objs.data(), wall); // (item_candidates' own call)
+			out2[i * 2] = (int32_t)cls, out2[i * 2 + 1] = cls == rmd::kTileGeneral ? -1 : (int32_t)wall;
 		}
 		return RMD_OK;
 	});

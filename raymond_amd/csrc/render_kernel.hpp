@@ -8,6 +8,7 @@
 #include "launch.hpp"
 #include "lobe_trips.hpp"
 #include "primary_candidates.hpp"
+#include <type_traits>
 #include "scene_split.hpp"
 #include "work_list.hpp"
 
@@ -190,7 +191,9 @@ RMD_DEV void finish_sample_range(const RenderParams &P, const WaveTile &tile, ui
 		V3 sum = ld3(out + pix);
 		[[maybe_unused]] V3 sq = mk(0.0, 0.0, 0.0);
 		if constexpr (MOM) sq = ld3(out_sq + pix);
-		const RMD_GLOBAL double *src = (const RMD_GLOBAL double *)P.sample_buf + ((size_t)wt * P.sample_count * 64u + lane) * kSampleStride;
+		uint32_t sector = lane; // (opaque: the lane's own offset into the buffer is the same for every item — hoisted out of a persistent wave's work loop it
+		asm volatile("" : "+v"(sector)); // holds a register pair across the trip loop, in a kernel that has none to spare)
+		const RMD_GLOBAL double *src = (const RMD_GLOBAL double *)P.sample_buf + ((size_t)wt * P.sample_count * 64u + sector) * kSampleStride;
 		// 16 samples' loads in flight at a time (the additions stay in sample order); 8 beside the squares' sums (at 16 the kernel spilled two registers)
 		constexpr uint32_t kInFlight = MOM ? 8u : 16u;
 		uint32_t k = 0;
@@ -697,6 +700,14 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 // trip while the item has pairs and both stacks together leave room for the 64 hits it may park, else a shading trip of the fuller stack, until
 // the item runs out of pairs; the remaining hits are then shaded in ever smaller trips.
 constexpr int kSortObjPrio = 1; // s_setprio level of the closest-hit loop over the objects in the role-sorted spheres kernel
+// pairs a generation round of a BLACK item draws block 0 for (render_wave_sorted, pass A): about half survive, and the round's one ray pass
+// serves at most 64 of them.  The build knob is the sweep's (tools/round_pairs_sweep.py, which also compares the frames of its builds:
+// profiles/r25_tile_classes/round_pairs_sweep.txt has 96 .. 128); the tests run the value shipped.
+#ifndef RMD_ROUND_PAIRS
+#define RMD_ROUND_PAIRS 128
+#endif
+constexpr uint32_t kRoundPairs = RMD_ROUND_PAIRS;
+static_assert(kRoundPairs > 64u && kRoundPairs <= 128u, "a round is two lane passes, the first a whole one");
 // The wave's parked hits: a dense STACK in LDS (round 5; round 4 kept a path in a fixed slot of a pool and two lists of slot numbers).  A hit is
 // pushed where the stack ends — the lanes of a trip that park write to consecutive entries — and a shading trip pops the top 64, lane i entry
 // n_hit - 64 + i: every access of a trip is 64 consecutive 8-byte (or 4-byte) words, the one pattern the LDS serves without a bank conflict
@@ -722,6 +733,9 @@ using SortPool = HitStack;
 // for the spheres among objects 0 .. 63 — and handed to the generation trips in place of the launch's visit mask and axis pairs; shading trips,
 // whose rays go anywhere, keep the launch's.  The two values wait in the wave's LDS head (sets[0]: pairs, sets[1 .. 2]: mask) rather than in
 // scalar registers across the trip loop: the kernel sits at 128 vector registers, and measured in spilled registers the head costs none.
+// The item's TILE CLASS (primary_candidates.hpp) rides in bits 30 .. 31 of sets[0]: kTileEmitter — every sample of the item is the emitting wall's
+// colour, and a generation trip of render_wave_sorted stores it without a block or a ray —, kTileBlack — every primary ray ends on one black diffuse wall, and a generation trip
+// becomes a generation ROUND that draws block 0 first and makes rays for the survivors only —, or kTileGeneral.
 RMD_DEV void item_candidates(KernargWords kernarg_params, WaveTile tile, const DevObject *__restrict__ objs, const DevObject *lobjs, uint32_t *sets) {
 	const uint32_t lane = threadIdx.x & 63u;
 	// the launch's parameters, re-read from the kernel arguments as a trip does (render_wave: the empty asm keeps what is computed from them here,
@@ -735,6 +749,7 @@ RMD_DEV void item_candidates(KernargWords kernarg_params, WaveTile tile, const D
 	__builtin_memcpy(&P, w, sizeof(P));
 	unsigned long long visit = P.visit_mask;
 	uint32_t pairs = P.axis_pairs;
+	uint32_t cls = kTileGeneral, wall_obj = 0u;
 	if (P.primary_cull != 0u) {
 		CullCamera cc;
 		cc.pos[0] = P.cam_pos[0], cc.pos[1] = P.cam_pos[1], cc.pos[2] = P.cam_pos[2];
@@ -746,15 +761,50 @@ RMD_DEV void item_candidates(KernargWords kernarg_params, WaveTile tile, const D
 		visit &= ~__ballot(cleared);
 		const AxisWalls *walls = reinterpret_cast<const AxisWalls *>(objs + P.n_objects);
 		const AxisWalls w3[3] = {walls[0], walls[1], walls[2]};
-		pairs = primary_pairs_kept(cone, cc, w3, P.axis_pairs);
+		int k_alone = 0;
+		bool faces_minus = false;
+		const bool alone = primary_pair_alone(cone, cc, w3, P.axis_pairs, k_alone, faces_minus);
+		if (alone) pairs = P.axis_pairs & (1023u << (10 * k_alone)); // (primary_pairs_kept)
+		// the item's tile class (primary_candidates.hpp: TILE CLASSES; make_params sets bit 1 only where black bounces are ended)
+		if ((P.primary_cull & 2u) != 0u) {
+			cls = primary_tile_class(alone, k_alone, faces_minus, walls, visit, P.n_objects, lobjs, wall_obj);
+		}
 	}
-	if (lane == 0u) sets[0] = pairs, sets[1] = (uint32_t)visit, sets[2] = (uint32_t)(visit >> 32);
+	// (the class in the two bits the pair fields leave free; a classed item's visit mask is empty by definition, and the mask's first word holds its wall)
+	if (lane == 0u) sets[0] = pairs | (cls << kTileClassShift), sets[1] = cls != kTileGeneral ? wall_obj : (uint32_t)visit, sets[2] = (uint32_t)(visit >> 32);
 	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 // A register pair the compiler may fill with anything: the value of a variable in the lanes that never use it.
 #define RMD_UNDEF3(v) RMD_UNDEF(v.x) RMD_UNDEF(v.y) RMD_UNDEF(v.z)
+#if RMD_DIAG
+// RMD_DEBUG bits 8 | 512: the full path of every sample a BLACK item's pass A ends, beside it — the jitter, the ray, the FULL visit and the
+// classification's rule: [55] samples checked, [56] samples that are not a zero sample (stays 0).  The generation trips' own cross-check counts
+// every sample of a launch once: [32] lanes whose full visit ran, [34] results that differ.
+RMD_DEV void diag_check_black_zero(const RenderParams &Pt, const DevObject *__restrict__ objs, const DevObject *lobjs, const DevGrid *__restrict__ grids, const WaveTile &tile,
+                                   uint32_t item, bool ended, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int wall) {
+	WalkScratch *no_scratch = nullptr;
+	double t_full = 0.0;
+	uint32_t sub_full = 0;
+	V3 fro, frd;
+	primary_ray(Pt, tile.x0 + (item & 7u), tile.y0 + ((item >> 3) & 7u), Rng::to_unit(w0, w1), Rng::to_unit(w2, w3), fro, frd);
+	const int oi_full = scene_intersect_wave<false>(objs, Pt.n_objects, grids, nullptr, *no_scratch, ended, fro, frd, t_full, sub_full, Pt.axis_pairs, 0u, nullptr, false, Pt.visit_mask);
+	bool zero = false;
+	if (oi_full >= 0) {
+		const DevObject &fo = lobjs[oi_full];
+		const V3 ffrag = fro + frd * t_full;
+		const double probe_sum = ((fo.normal[0] + fo.normal[1]) + fo.normal[2]) + ((ffrag.x + ffrag.y) + ffrag.z);
+		zero = fo.material_kind != 2u && fo.geometry_kind == 0u && (fo.flags & kObjBlackDiffuse) != 0u && Rng::spare22(w0, w2) < (1u << 21) && __builtin_fabs(probe_sum) < __builtin_inf();
+	}
+	const unsigned long long cm = __ballot(ended), bm = __ballot(ended && !zero), om = __ballot(ended && oi_full != wall);
+	if ((threadIdx.x & 63u) == 0u) {
+		atomicAdd(&Pt.debug_counters[57], (unsigned long long)__popcll(om)); // rays that hit another object than the predicted wall
+		atomicAdd(&Pt.debug_counters[55], (unsigned long long)__popcll(cm)), atomicAdd(&Pt.debug_counters[56], (unsigned long long)__popcll(bm));
+		atomicAdd(&Pt.debug_counters[32], (unsigned long long)__popcll(cm)), atomicAdd(&Pt.debug_counters[34], (unsigned long long)__popcll(bm));
+	}
+}
+#endif
 template <bool MOM = false>
 RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_params, const DevObject *__restrict__ objs, const DevGrid *__restrict__ grids,
                                 const void *__restrict__ work, double *__restrict__ out, const DevObject *lobjs, unsigned char *wave_lds, uint32_t work_item,
@@ -776,11 +826,23 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 	item_candidates(kernarg_params, tile, objs, lobjs, item_sets);
 
 	uint32_t n_d = 0, n_g = 0, next_item = 0; // wave-uniform: entries on the diffuse and on the GGX stack, pairs handed out
+#if RMD_DIAG
+	if ((P.debug_flags & 8u) && P.debug_counters && lane == 0u) { // [48] / [49] / [50]: general / emitter / black items
+		const uint32_t cls = (uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[0]) >> kTileClassShift;
+		atomicAdd(&P.debug_counters[cls == kTileEmitter ? 49 : cls == kTileBlack ? 50 : 48], 1ull);
+	}
+#endif
 	// the trip loop's bound (report_fault): every trip hands out 64 pairs or advances at least one path by a segment
 	unsigned long long trips_left = lobe_trip_bound(pool_items, kTripBoundPerPair);
 #if RMD_DIAG
 	if (P.debug_flags & 32u) trips_left = 1ull; // tests/test_gpu_faults.py: forces the bound
 #endif
+	// The trip loop, compiled TWICE and chosen per item: for a general item the loop as it is without the tile classes — its generation branch reads
+	// no class and holds none of the rounds' code, so a launch without classed items runs the instructions it ran before they existed — and for an
+	// EMITTER or BLACK item the loop with the class's generation branch.  (One loop for both cost every general trip the class read, two branches
+	// and the register pressure of the rounds' code beside it: 0.9 % on the frame with every path traced.)
+	auto trip_loop = [&](auto classed_item) {
+	constexpr bool CLASSED = decltype(classed_item)::value;
 	for (;;) {
 		// the launch parameters a trip needs, re-read from the kernel arguments (see render_wave)
 		KernargWords src = kernarg_params;
@@ -818,6 +880,9 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 		V3 ro, rd, T;
 		RMD_UNDEF3(ro) RMD_UNDEF3(rd) RMD_UNDEF3(T)
 		bool failed = false; // lens_failed / cut: the path ends with the sample T (.) 0
+#if RMD_DIAG
+		bool diag_emitter = false; // the lanes of an EMITTER item's generation trip whose pair was finished without a ray (cross-check below)
+#endif
 		unsigned long long turns = Pt.visit_mask; // the object loop's turns and the axis pairs of this trip: the launch's, or (GI) the item's own
 		uint32_t pairs = Pt.axis_pairs;
 		if (shade_trip) {
@@ -858,21 +923,125 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			}
 		} else {
 			// ---------------- GI: the work item's next 64 (pixel, sample) pairs, one per lane (slots outside a ragged tile are skipped)
+			//
+			// On a BLACK item (primary_candidates.hpp: every primary ray of the tile ends on one black diffuse wall) the trip is a generation ROUND.  A
+			// sample's fate there is decided by the spare bits of its block 0 alone: lobe_bits < 2^21 and the classification below ends it with (0, 0, 0)
+			// — half of the samples, for which the jitter's conversions, the ray and the visit compute nothing.  So the round draws block 0 FIRST, for
+			// kRoundPairs pairs in two lane passes (pass A: 64 pairs, then kRoundPairs - 64): a pair below 2^21 gets its zeros there and then; a
+			// survivor's number and its four Philox words are staged in the hit stacks' free entries n_d .. n_d + 63 (a generation trip runs only while
+			// 64 entries are free; item / state / lobe_bits / frag[0] hold the five words) at its rank among the survivors.  Then lane i takes survivor i
+			// (pass B) and goes on exactly as a generation trip does from the Philox words on — same operations on the same values, only in another lane,
+			// which changes no bit (the RNG is keyed by pixel and sample, the samples are added in order afterwards).  A general item is the first lane
+			// pass alone, its words staying in their lanes.  (Written without a loop over the lane passes: a loop's carried counts are scalar registers
+			// live across block 0, in a kernel that spills scalar registers as it is — measured 2 % on the frame with every path traced.)
+			// A round stages at most 64 survivors: the second pass is cut short in front of the lane that holds the 65th — the pairs from there on are
+			// simply not handed out yet (next_item advances by the lanes taken, so it need not be a multiple of 64) and open the next round.  The first
+			// pass is never cut, so a round hands out at least 64 pairs or all that are left, and parks at most 64 hits: the trip loop's progress argument
+			// and its bound stand as written above, for every kRoundPairs.
+			const uint32_t head0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[0]);
+			// On an EMITTER item (every primary ray of the tile ends on one emitting wall) a sample is T (.) L with T = (1, 1, 1) and L the wall's colour:
+			// neither a random number nor a ray enters it.  Its generation trips draw no block and make no ray: they store the colour for the trip's 64
+			// pairs here and leave the rest of the trip without a lane — nothing behind the visit knows of them (a flag read there is a scalar register
+			// live across the visit, or an instruction in every trip of every item).  One store per trip, in the trip loop where the samples' stores
+			// are: a loop of stores of its own ahead of the trip loop cost the closest-hit loop its scalar loads of the object records.
+			// finish_sample_range adds the sectors in sample order as it does any other item's.
+			const bool emitter_item = CLASSED && head0 >> kTileClassShift == kTileEmitter;
+			uint32_t w0, w1, w2, w3;
+			RMD_UNDEF(w0) RMD_UNDEF(w1) RMD_UNDEF(w2) RMD_UNDEF(w3)
 			item = next_item + lane;
 			next_item += 64u;
 			active = item < pool_items && (item & 7u) < tile.w && ((item >> 3) & 7u) < tile.h;
-			const uint32_t x = tile.x0 + (item & 7u), y = tile.y0 + ((item >> 3) & 7u);
-			rng.pixel = y * Pt.W + x, rng.sample = Pt.sample_begin + pool_first + (item >> 6);
+			rng.pixel = (tile.y0 + ((item >> 3) & 7u)) * Pt.W + tile.x0 + (item & 7u), rng.sample = Pt.sample_begin + pool_first + (item >> 6);
+			if (emitter_item) {
+				if (active) {
+					const V3 L = hadamard(mk(1.0, 1.0, 1.0), ld3(lobjs[(uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[1])].color)); // T (.) L, T = (1, 1, 1)
+					RMD_GLOBAL double *dst = (RMD_GLOBAL double *)Pt.sample_buf + (((size_t)wt * Pt.sample_count + pool_first + (item >> 6)) * 64u + (item & 63u)) * kSampleStride;
+					store_sample(dst, L);
+				}
+#if RMD_DIAG
+				diag_emitter = active;
+#endif
+				active = false;
+			} else philox4x32_10(rng.pixel, rng.sample, 0u, 0u, Pt.key0, Pt.key1, w0, w1, w2, w3); // block 0: the pixel jitter (:326-327) and the first bounce's lobe bits
+			if (CLASSED && head0 >> kTileClassShift == kTileBlack) {
+				// ---- pass A, first lane pass: at most 64 survivors, ranks 0 ..
+				bool survivor = active && Rng::spare22(w0, w2) >= (1u << 21);
+				unsigned long long sm = __ballot(survivor);
+				uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+				if (active && !survivor) { // L = 0 (the classification's black_bounce rule; finite_inputs holds: primary_candidates.hpp)
+					double zero = 0.0; // (made here: as a constant it is hoisted out of the persistent work loop and held — spilled — across the kernel)
+					asm volatile("" : "+v"(zero));
+					RMD_GLOBAL double *dst = (RMD_GLOBAL double *)Pt.sample_buf + (((size_t)wt * Pt.sample_count + pool_first + (item >> 6)) * 64u + (item & 63u)) * kSampleStride;
+					store_sample(dst, mk(zero, zero, zero));
+				}
+				if (survivor) {
+					const uint32_t e = n_d + rank;
+					stack.item[e] = item, stack.state[e] = w0, stack.lobe_bits[e] = w1;
+					stack.frag[0][e] = __builtin_bit_cast(double, (unsigned long long)w2 | (unsigned long long)w3 << 32);
+				}
+				uint32_t staged = (uint32_t)__popcll(sm);
+#if RMD_DIAG
+				[[maybe_unused]] bool ended = active && !survivor; // [51] samples ended in pass A, [52] rounds, [53] survivors, [54] rounds cut short at the 65th survivor
+				if ((Pt.debug_flags & 8u) && Pt.debug_counters) {
+					const unsigned long long em = __ballot(ended);
+					if (lane == 0u) atomicAdd(&Pt.debug_counters[51], (unsigned long long)__popcll(em)), atomicAdd(&Pt.debug_counters[53], (unsigned long long)staged), atomicAdd(&Pt.debug_counters[52], 1ull);
+					if (Pt.debug_flags & 512u) diag_check_black_zero(Pt, objs, lobjs, grids, tile, item, ended, w0, w1, w2, w3, __builtin_amdgcn_readfirstlane((int)item_sets[1]));
+				}
+#endif
+				if (next_item < pool_items) {
+					// ---- second lane pass: the next kRoundPairs - 64 pairs, cut in front of the 65th survivor
+					item = next_item + lane;
+					active = lane < kRoundPairs - 64u && item < pool_items && (item & 7u) < tile.w && ((item >> 3) & 7u) < tile.h;
+					rng.pixel = (tile.y0 + ((item >> 3) & 7u)) * Pt.W + tile.x0 + (item & 7u), rng.sample = Pt.sample_begin + pool_first + (item >> 6);
+					philox4x32_10(rng.pixel, rng.sample, 0u, 0u, Pt.key0, Pt.key1, w0, w1, w2, w3);
+					survivor = active && Rng::spare22(w0, w2) >= (1u << 21);
+					sm = __ballot(survivor);
+					rank = staged + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+					const unsigned long long over = __ballot(survivor && rank >= 64u);
+					const uint32_t used = over != 0ull ? (uint32_t)__builtin_ctzll(over) : kRoundPairs - 64u; // the lanes in front of the 65th survivor
+					if (active && lane < used && !survivor) {
+						double zero = 0.0;
+						asm volatile("" : "+v"(zero));
+						RMD_GLOBAL double *dst = (RMD_GLOBAL double *)Pt.sample_buf + (((size_t)wt * Pt.sample_count + pool_first + (item >> 6)) * 64u + (item & 63u)) * kSampleStride;
+						store_sample(dst, mk(zero, zero, zero));
+					}
+					if (survivor && lane < used) {
+						const uint32_t e = n_d + rank;
+						stack.item[e] = item, stack.state[e] = w0, stack.lobe_bits[e] = w1;
+						stack.frag[0][e] = __builtin_bit_cast(double, (unsigned long long)w2 | (unsigned long long)w3 << 32);
+					}
+					const uint32_t more = (uint32_t)__popcll(__ballot(survivor && lane < used));
+					staged += more, next_item += used;
+#if RMD_DIAG
+					ended = active && lane < used && !survivor;
+					if ((Pt.debug_flags & 8u) && Pt.debug_counters) {
+						const unsigned long long em = __ballot(ended);
+						if (lane == 0u) atomicAdd(&Pt.debug_counters[51], (unsigned long long)__popcll(em)), atomicAdd(&Pt.debug_counters[53], (unsigned long long)more), atomicAdd(&Pt.debug_counters[54], over != 0ull ? 1ull : 0ull);
+						if (Pt.debug_flags & 512u) diag_check_black_zero(Pt, objs, lobjs, grids, tile, item, ended, w0, w1, w2, w3, __builtin_amdgcn_readfirstlane((int)item_sets[1]));
+					}
+#endif
+				}
+				// ---- pass B: lane i takes survivor i
+				__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+				__builtin_amdgcn_wave_barrier();
+				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+				active = lane < staged;
+				const uint32_t e = n_d + (active ? lane : 0u); // (a lane without a survivor holds whatever entry n_d holds: nobody reads what it makes of it)
+				const unsigned long long w23 = __builtin_bit_cast(unsigned long long, stack.frag[0][e]);
+				item = stack.item[e], w0 = stack.state[e], w1 = stack.lobe_bits[e], w2 = (uint32_t)w23, w3 = (uint32_t)(w23 >> 32);
+				rng.pixel = (tile.y0 + ((item >> 3) & 7u)) * Pt.W + tile.x0 + (item & 7u), rng.sample = Pt.sample_begin + pool_first + (item >> 6);
+			}
+			rng.block = 1u, rng.lobe_bits = Rng::spare22(w0, w2); // (Rng::next2, from the words on)
 			T = mk(1.0, 1.0, 1.0);
-			{ // (likewise: a lane without a pair computes the ray of a pixel position outside the tile, which nobody reads)
-				double u0, u1;
-				rng.next2(Pt.key0, Pt.key1, u0, u1); // block 0: the pixel jitter (:326-327)
-				primary_ray(Pt, x, y, u0, u1, ro, rd);
+			if (!emitter_item) { // (likewise: a lane without a pair computes the ray of a pixel position outside the tile, which nobody reads)
+				primary_ray(Pt, tile.x0 + (item & 7u), tile.y0 + ((item >> 3) & 7u), Rng::to_unit(w0, w1), Rng::to_unit(w2, w3), ro, rd);
 				if (Pt.use_dof) failed = active && !thin_lens_from_pinhole(Pt, ro, rd, rng, ro, rd); // the reference panics there; the sample contributes zero
 			}
 			// what this tile's primary rays can hit (item_candidates)
-			pairs = (uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[0]);
+			pairs = CLASSED ? head0 & ((1u << kTileClassShift) - 1u) : head0; // (a general item's class bits are zero)
 			turns = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[1]) | (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[2]) << 32;
+			if (CLASSED) turns = 0ull; // (a classed item's head holds its wall where the mask was: the mask is empty, that is what classed it)
+			if (emitter_item) pairs = 0u; // (no lane of the trip enters the visit)
 		}
 		// ---------------- src/trace.rs:239 — closest hit of every lane that has a ray
 		const bool want = active && !failed;
@@ -905,6 +1074,41 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 				atomicAdd(&Pt.debug_counters[34], (unsigned long long)__popcll(dm)), atomicAdd(&Pt.debug_counters[35], (unsigned long long)__popcll(dropped));
 				atomicAdd(&Pt.debug_counters[36], pairs != Pt.axis_pairs ? 1ull : 0ull);
 			}
+		}
+#endif
+#if RMD_DIAG
+		// RMD_DEBUG bits 8 | 512, a generation trip of an EMITTER item: every sample's full path beside it — block 0, the ray, the FULL visit: [55] samples
+		// checked, [56] samples whose full path does not end on an emitter of the wall's colour, [57] rays that hit another object than the predicted wall
+		// (both stay 0).  The generation trips' own cross-check counts every sample of a launch once: [32] lanes whose full visit ran, [34] hits that differ.
+		if (__ballot(diag_emitter) != 0ull && (Pt.debug_flags & 512u) && (Pt.debug_flags & 8u) && Pt.debug_counters) {
+			const bool active = diag_emitter; // (the lanes whose pair the trip finished)
+			const int wall = __builtin_amdgcn_readfirstlane((int)item_sets[1]);
+			Rng r;
+			r.init(rng.pixel, rng.sample);
+			double u0, u1, t_full = 0.0;
+			uint32_t sub_full = 0;
+			V3 fro, frd;
+			r.next2(Pt.key0, Pt.key1, u0, u1);
+			primary_ray(Pt, tile.x0 + (item & 7u), tile.y0 + ((item >> 3) & 7u), u0, u1, fro, frd);
+			const int oi_full = scene_intersect_wave<false>(objs, Pt.n_objects, grids, nullptr, *no_scratch, active, fro, frd, t_full, sub_full, Pt.axis_pairs, 0u, nullptr, false, Pt.visit_mask);
+			bool bad_sample = true;
+			if (oi_full >= 0) {
+				const V3 c = hadamard(mk(1.0, 1.0, 1.0), ld3(lobjs[oi_full].color)), L = hadamard(T, ld3(lobjs[wall].color));
+				bad_sample = lobjs[oi_full].material_kind != 2u || __builtin_bit_cast(unsigned long long, c.x) != __builtin_bit_cast(unsigned long long, L.x) ||
+				             __builtin_bit_cast(unsigned long long, c.y) != __builtin_bit_cast(unsigned long long, L.y) || __builtin_bit_cast(unsigned long long, c.z) != __builtin_bit_cast(unsigned long long, L.z);
+			}
+			const unsigned long long cm = __ballot(active), bm = __ballot(active && bad_sample), om = __ballot(active && oi_full != wall);
+			if (lane == 0u) {
+				atomicAdd(&Pt.debug_counters[55], (unsigned long long)__popcll(cm)), atomicAdd(&Pt.debug_counters[56], (unsigned long long)__popcll(bm)), atomicAdd(&Pt.debug_counters[57], (unsigned long long)__popcll(om));
+				atomicAdd(&Pt.debug_counters[32], (unsigned long long)__popcll(cm)), atomicAdd(&Pt.debug_counters[34], (unsigned long long)__popcll(om));
+			}
+		}
+#endif
+#if RMD_DIAG
+		// RMD_DEBUG bits 8 | 512: [57] rays of a classed item's generation trip (a BLACK item's survivors) whose closest hit is not the predicted wall (stays 0)
+		if (CLASSED && !shade_trip && (Pt.debug_flags & 512u) && (Pt.debug_flags & 8u) && Pt.debug_counters) {
+			const unsigned long long om = __ballot(want && oi != __builtin_amdgcn_readfirstlane((int)item_sets[1]));
+			if (lane == 0u) atomicAdd(&Pt.debug_counters[57], (unsigned long long)__popcll(om));
 		}
 #endif
 		// ---------------- classification (the rules of render_wave's phase C)
@@ -969,6 +1173,9 @@ RMD_DEV void render_wave_sorted(const RenderParams &P, KernargWords kernarg_para
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		}
 	}
+	};
+	if ((uint32_t)__builtin_amdgcn_readfirstlane((int)item_sets[0]) >> kTileClassShift != kTileGeneral) trip_loop(std::true_type{});
+	else trip_loop(std::false_type{});
 	// (whether the item is a whole one is asked of the launch parameters again, not carried across the trip loop: work_list_item's `whole` and `parts`)
 	finish_sample_range<MOM>(P, tile, wt, P.split_k, work_item < P.n_whole, lane, out, out_sq);
 }
@@ -1506,6 +1713,13 @@ RMD_DEV void render_kernel_body(const RenderParams &P, const DevObject *__restri
 		if ((tid & 63u) == 0u) *last_draw = 0u;
 		for (;;) {
 			uint32_t item = 0, floor = 0;
+			if constexpr (kSortedTrips<MODE, GRID>) {
+				// (the head's address made again from the wave's area at every draw: as a loop invariant it is a register pair held across the trip loop,
+				// which the role-sorted kernel does not have — the other instantiations are compiled as they were)
+				unsigned char *area = wave_lds;
+				asm volatile("" : "+v"(area));
+				last_draw = reinterpret_cast<volatile uint32_t *>(area + wave_lds_of<MODE, GRID, QUEUED>(P.n_grids) - kWaveHeadBytes);
+			}
 			if ((tid & 63u) == 0u) {
 				item = atomicAdd(P.work_counter, 1u);
 				floor = *last_draw;

@@ -34,6 +34,7 @@ _SIGS = {
     "rmd_probe_triangle_sphere": [_sz, _vp, _vp],
     "rmd_probe_pretest_pairs": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "rmd_probe_primary_candidates": [_P(abi.Camera), _P(abi.Settings), _P(abi.Object), C.c_uint32, C.c_uint32, C.c_int64, _sz, _vp, _vp, _vp],
+    "rmd_probe_tile_classes": [_P(abi.Camera), _P(abi.Settings), _P(abi.Object), C.c_uint32, C.c_uint32, C.c_int64, _sz, _vp, _vp, _vp],
     "rmd_probe_launch_plan": [C.c_uint32, C.c_uint32, _sz, _vp, _vp],
     "rmd_probe_launch_sizes": [C.c_uint32, C.c_uint32, _vp],
     "rmd_probe_work_plan": [_vp, _sz, _vp, _vp],
@@ -224,6 +225,24 @@ def primary_candidates(cam, settings, scene, tiles, axis_pairs_tunable=0):
     if st != abi.RMD_OK:
         raise RuntimeError("rmd_probe_primary_candidates: status %d" % st)
     return int(launch[0]), int(launch[1]), bool(launch[2]), out[:, 0].copy(), out[:, 1].astype(np.uint32)
+
+
+TILE_GENERAL, TILE_EMITTER, TILE_BLACK = 0, 1, 2
+
+
+def tile_classes(cam, settings, scene, tiles, axis_pairs_tunable=0):
+    """Host only (no GPU): the class the spheres kernel gives a work item of each wave tile (x0, y0, w, h) ->
+    (on bool, cls int32[n] (TILE_*), wall int32[n]: the object every primary ray of the tile hits, -1 = general); api: rmd_probe_tile_classes."""
+    L = _L()
+    objs, n, _descs, ng, keep = scene.flatten()
+    tiles = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1, 4)
+    launch, out = np.zeros(1, dtype=np.uint32), np.zeros((tiles.shape[0], 2), dtype=np.int32)
+    c, s = cam.pod(), settings.pod()
+    st = L.rmd_probe_tile_classes(C.byref(c), C.byref(s), objs, n, ng, int(axis_pairs_tunable), tiles.shape[0], _p(tiles), _p(launch), _p(out))
+    del keep
+    if st != abi.RMD_OK:
+        raise RuntimeError("rmd_probe_tile_classes: status %d" % st)
+    return bool(launch[0]), out[:, 0].copy(), out[:, 1].copy()
 
 
 # rmd_probe_launch_plan: modes, input flags and output columns
