@@ -60,7 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike,
+	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_tile_luma_error,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
@@ -945,6 +945,51 @@ rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *
                        const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
                        uint32_t radius, uint32_t rank, double k, double ratio, double floor,
                        double *out_accum_dev, double *out_accum_sq_dev, uint32_t *replaced_host /* n_rects, may be NULL */);
+/*
+ * A TILE'S LUMINANCE NOISE, the adaptive check's second measure (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct or entry point changes,
+ * found by its symbol).  rmd_tile_error is a maximum over channels of a maximum over pixels: one dark pixel's one dim channel holds its whole tile.  This
+ * call aggregates over the tile and weighs the channels as rmd_luminance_histogram_tiles and the tone-map do.
+ * S = accum_dev, Q = accum_sq_dev (W*H*3 doubles each); rect j is reduced on its own at n = rect_counts[j].  Everything is unfused binary64: every product
+ * rounded, the additions as bracketed.  Per pixel of rect j, with s and q its six sums:
+ *     the pixel is VALID if n >= 2 and its six sums are finite                                              (rmd_despike's rule)
+ *     u_c = s_c / n;   v_c = max(0, (q_c - s_c*u_c) / (n - 1)) / n
+ *     Y = (0.2126 * u_0 + 0.7152 * u_1) + 0.0722 * u_2                    the luminance of the means
+ *     V = (A0 * v_0 + A1 * v_1) + A2 * v_2                                the variance of that luminance's mean; A_c = the weight times itself
+ *     d = |Y|; if (!(d > floor)) d = floor;      R = (V / d) / d          two divisions, never V / (d * d); no square root; no input makes R NaN
+ * Sum order: the rect's pixels are numbered row-major WITHIN THE RECT, i = 0, 1, ...  Lane t of 256 adds Y, V and R of the valid pixels among
+ * i = t, t + 256, t + 512, ... in that order into three running sums that start at +0.0, and counts the valid and the invalid pixels.  The 256 partials of
+ * each sum are added exactly as rmd_tile_error_dual adds its partials: within each wave of 64 lanes the lanes 32 apart first, then 16, 8, 4, 2, 1; then
+ * the four waves' sums as (w0 + w1) + (w2 + w3).  This gives SY, SV, SR and m = (double)valid.  Then
+ *     mean_luma = m ? SY / m : 0;   mean_variance = m ? SV / m : 0;   mean_rel_variance = m ? SR / m : 0
+ *     D = |mean_luma|; if (!(D > floor)) D = floor
+ *     tile_rms = sqrt(mean_variance) / D;          pixel_rms = sqrt(mean_rel_variance)
+ * A rect without pixels gives all zeros.  A rect with pixels and invalid > 0 gives tile_rms = pixel_rms = +inf — its means are still those over the valid
+ * pixels —: a tile with a bad pixel never finishes on this rule, as under rmd_tile_error.  A tile_rms or pixel_rms that comes out NaN (inf / inf when the
+ * sums overflow) is reported as +inf.  The five fields other than tile_rms and pixel_rms are the same bits on every device and on the host; those two pass
+ * through the device's square root.
+ * What the two measures mean:
+ *   - tile_rms is the RMS standard error of the tile's luminance over the tile's own mean luminance: dark pixels inside a lit tile no longer count for
+ *     more than lit ones;
+ *   - pixel_rms is the RMS over the tile of each pixel's relative luminance error: a mean instead of a maximum, luminance instead of the worst channel,
+ *     but still normalised per pixel.
+ * Together with rmd_tile_error they separate the three suspects of an adaptive rule that holds its tiles too long: the maximum, the channel and the
+ * normalisation.
+ * Rects only have to lie inside the W x H frame; they may overlap or repeat (rmd_tile_error's rule, not the filters').  out_host: a HOST array of n_rects.
+ * RMD_ERR_INVALID_ARGUMENT, all checked before the device is touched, in this order: a NULL buffer, width or height 0, or n_rects > 0 with rects, rect_counts
+ * or out_host NULL; accum_sq_dev aliasing accum_dev; floor not finite or not > 0; a rect outside the framebuffer; and only then a NULL context.
+ * n_rects == 0 is RMD_OK with nothing launched.  Synchronous, like rmd_tile_error; the call's device scratch (rects, counts, results) stays on the context
+ * and grows on demand.  One workgroup per rect: made for the adaptive check's tiles, slow for a whole frame passed as one rect.
+ */
+typedef struct rmd_tile_luma {
+	double tile_rms;          /* sqrt(mean_variance) / max(|mean_luma|, floor)                   */
+	double pixel_rms;         /* sqrt(mean_rel_variance)                                          */
+	double mean_luma;         /* SY / m                                                           */
+	double mean_variance;     /* SV / m                                                           */
+	double mean_rel_variance; /* SR / m                                                           */
+	uint32_t valid, invalid;  /* pixels of the rect that are / are not valid                      */
+} rmd_tile_luma;              /* 48 bytes */
+rmd_status rmd_tile_luma_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                               const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, double floor, rmd_tile_luma *out_host);
 
 /* ---- multi-GPU (no reference counterpart; the reference has no collectives) ---- */
 #define RMD_COMM_ID_BYTES 128

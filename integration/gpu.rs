@@ -169,6 +169,24 @@ extern "C" {
     fn rmd_despike(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                    rect_sample_counts: *const u32, n_rects: u32, radius: u32, rank: u32, k: f64, ratio: f64, floor: f64, out_accum_dev: *mut f64,
                    out_accum_sq_dev: *mut f64, replaced_host: *mut u32) -> i32;
+    // a tile's luminance noise, the adaptive check's other measures (settings.adaptive_measure of the C++ mirror): rect i at rect_counts[i], rects inside the
+    // frame (they may overlap or repeat), out_host n_rects rmd_tile_luma; tile_rms or pixel_rms is what meets the threshold
+    fn rmd_tile_luma_error(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                           rect_counts: *const u32, n_rects: u32, floor: f64, out_host: *mut rmd_tile_luma) -> i32;
+}
+
+/// rmd_tile_luma_error's result for one rect (include/raymond_hip.h: rmd_tile_luma, 48 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+#[allow(non_camel_case_types, dead_code)]
+pub struct rmd_tile_luma {
+    pub tile_rms: f64,          // sqrt(mean_variance) / max(|mean_luma|, floor)
+    pub pixel_rms: f64,         // sqrt(mean_rel_variance)
+    pub mean_luma: f64,
+    pub mean_variance: f64,
+    pub mean_rel_variance: f64,
+    pub valid: u32,
+    pub invalid: u32,
 }
 
 /// One candidate of rmd_denoise_dual_select (include/raymond_hip.h: rmd_denoise_candidate); `reserved` is 0

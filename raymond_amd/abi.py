@@ -135,6 +135,21 @@ RMD_LUMA_BINS = 256  # rmd_luma_histogram: four bins an octave over 2^-32 .. 2^3
 DESPIKE_MAX_RADIUS = 3  # rmd_despike: 1 <= radius <= 3, rank <= (2 * radius + 1)^2 - 2
 
 
+class TileLuma(C.Structure):  # rmd_tile_luma: rmd_tile_luma_error's result for one rect, 48 bytes
+    _fields_ = [
+        ("tile_rms", C.c_double),
+        ("pixel_rms", C.c_double),
+        ("mean_luma", C.c_double),
+        ("mean_variance", C.c_double),
+        ("mean_rel_variance", C.c_double),
+        ("valid", C.c_uint32),
+        ("invalid", C.c_uint32),
+    ]
+
+
+ADAPTIVE_MEASURES = ("channel_max", "luma_tile", "luma_pixel")  # Settings.adaptive_measure: rmd_tile_error, rmd_tile_luma_error's tile_rms, its pixel_rms
+
+
 class LumaHistogram(C.Structure):  # rmd_luma_histogram
     _fields_ = [
         ("bins", C.c_uint64 * RMD_LUMA_BINS),

@@ -1,4 +1,5 @@
-// C-ABI implementation (include/raymond_hip.h) of the denoise entry points and rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip.
+// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error and rmd_tile_error_dual.  Host code only; the
+// kernels are in denoise*.hip, despike.hip and tile_luma.hip.
 // Every entry point is its argument checks in its own order and then, inside rmd::guarded: the rect checks, the context, one carved scratch block
 // (denoise_host.hpp has the layouts), one upload of the rects, its launcher (launch.hpp) and the wait.
 #define RMD_WITH_HIP 1
@@ -7,6 +8,7 @@
 #include "despike_rule.hpp"
 #include "internal.hpp"
 #include "launch.hpp"
+#include "tile_luma_rule.hpp"
 
 namespace rmd {
 // Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
@@ -476,6 +478,39 @@ rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *
 		                                 out_accum_dev, out_accum_sq_dev, d_replaced));
 		if (d_replaced) RMD_HIP(ctx, hipMemcpyAsync(replaced_host, d_replaced, (size_t)n_rects * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 		return finish(ctx);
+	});
+}
+
+// rmd_tile_luma_error (tile_luma.hip).  Its refusals in the header's order, the context last; the rects follow rmd_tile_error's rule (inside the frame; they
+// may overlap or repeat), not the filters'
+rmd_status rmd_tile_luma_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                               const uint32_t *rect_counts, uint32_t n_rects, double floor, rmd_tile_luma *out_host) {
+	static_assert(sizeof(rmd::TileLuma) == sizeof(rmd_tile_luma) && offsetof(rmd::TileLuma, tile_rms) == offsetof(rmd_tile_luma, tile_rms) &&
+	                  offsetof(rmd::TileLuma, pixel_rms) == offsetof(rmd_tile_luma, pixel_rms) && offsetof(rmd::TileLuma, mean_luma) == offsetof(rmd_tile_luma, mean_luma) &&
+	                  offsetof(rmd::TileLuma, mean_variance) == offsetof(rmd_tile_luma, mean_variance) &&
+	                  offsetof(rmd::TileLuma, mean_rel_variance) == offsetof(rmd_tile_luma, mean_rel_variance) && offsetof(rmd::TileLuma, valid) == offsetof(rmd_tile_luma, valid) &&
+	                  offsetof(rmd::TileLuma, invalid) == offsetof(rmd_tile_luma, invalid),
+	              "tile_luma_rule.hpp's TileLuma is rmd_tile_luma");
+	const std::string name = "rmd_tile_luma_error: ";
+	return rmd::guarded(ctx, "rmd_tile_luma_error", [&] {
+		if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_counts || !out_host))) return fail(ctx, kInvalid, name + "bad argument");
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		if (any_overlap({{accum_dev, bytes}, {accum_sq_dev, bytes}})) return fail(ctx, kInvalid, name + "accum_sq_dev must not alias accum_dev");
+		if (!(floor > 0.0) || !std::isfinite(floor)) return fail(ctx, kInvalid, name + "floor must be finite and > 0");
+		for (uint32_t i = 0; i < n_rects; i++)
+			if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
+				return fail(ctx, kInvalid, name + "tile rectangle outside the framebuffer");
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		if (n_rects != 0) {
+			DenoiseInput in = single_input(accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_counts, n_rects);
+			Scratch sc; // (the context's block: kept between calls)
+			if (rmd_status s = sc.carve(ctx, rmd::tile_luma_scratch_layout(n_rects), &ctx->tile_luma_scratch)) return s;
+			if (rmd_status s = upload_rects(ctx, sc, in)) return s;
+			rmd::TileLuma *d_out = sc.part<rmd::TileLuma>(rmd::kPartTileErrors);
+			RMD_HIP(ctx, rmd::launch_tile_luma(ctx->stream, in, floor, d_out));
+			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(rmd_tile_luma), hipMemcpyDeviceToHost, ctx->stream));
+		}
+		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
 	});
 }
 

@@ -109,6 +109,18 @@ inline ScratchLayout despike_scratch_layout(uint32_t W, uint32_t H, uint32_t n_r
 	return L;
 }
 
+// rmd_tile_luma_error's block, in the parts' existing names: kPartRects and kPartCountsA the rects and their counts, kPartTileErrors the per-rect results
+// (n_rects rmd_tile_luma).  Like rmd_despike's it is not one of the forms above
+inline ScratchLayout tile_luma_scratch_layout(uint32_t n_rects) {
+	ScratchLayout L;
+	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
+		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
+		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
+	};
+	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, sizeof(uint32_t), n_rects), part(kPartTileErrors, sizeof(rmd_tile_luma), n_rects);
+	return L;
+}
+
 // ---------------------------------------------------------------- the block tables of the region forms
 // rmd_denoise_dual_region: each region rect cut into tiles of the kernel's own shape (tw x th) from the rect's corner, row by row
 inline std::vector<DualBlock> dual_region_table(const rmd_tile_rect *region, uint32_t n_region, uint32_t tw, uint32_t th) {

@@ -219,6 +219,10 @@ hipError_t launch_luma_histogram(hipStream_t stream, const double *accum, const 
 // not read (may be null).  radius is 1 .. 3; the other arguments are checked by the caller
 hipError_t launch_despike(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t rank, double k, double ratio, double floor, uint32_t *n_img,
                           uint32_t *rect_img, double *out_accum, double *out_accum_sq, uint32_t *replaced);
+// rmd_tile_luma_error (tile_luma.hip): out[i] = rect i's result (tile_luma_rule.hpp: TileLuma, rmd_tile_luma's layout) from in.accum_a / in.accum_sq_a at
+// in.counts_a[i], one workgroup per rect; the rects, the counts and `out` are device memory.  Nothing else of `in` is read.  floor is checked by the caller
+struct TileLuma;
+hipError_t launch_tile_luma(hipStream_t stream, const DenoiseInput &in, double floor, TileLuma *out);
 hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in, int in_stride, double *out, int out_stride,
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,

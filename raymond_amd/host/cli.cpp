@@ -3,6 +3,10 @@
 //
 //   raymond_cli render <spheres|dragon[:n]> W H SPP BOUNCES out.ppm [--raw out.f64] [--gpus N] [--spi K] [--aperture R] [--end-black-paths 1]
 //                                                                    [--adaptive THRESHOLD [--adaptive-floor F]]   (needs --spi)
+//                                                                    [--adaptive-measure channel_max|luma_tile|luma_pixel]   (what --adaptive compares with
+//                                                                      THRESHOLD: rmd_tile_error, or rmd_tile_luma_error's tile_rms or pixel_rms; not with --denoise-dual)
+//                                                                    [--dump-tiles FILE]   (one "left top width height sample_count error" line per finished tile)
+//                                                                    [--tile-size N]   (N x N tiles instead of 32 x 32)
 //                                                                    [--denoise 1 [--denoise-radius R] [--denoise-patch F] [--denoise-k K]
 //                                                                     [--denoise-alpha A]]   (the image is rmd_denoise's, on GPU 0)
 //                                                                    [--denoise-features 1 [--denoise-feature-k K] [--denoise-feature-tau T]]
@@ -54,6 +58,10 @@
 //                                         rmd_despike made on the host (raymond::despike_host, from the header the kernel is built from) over raw W*H*3 f64
 //                                         sums and sums of squares; rects.txt: one "left top width height count" per line; K, Q and F are read as C99
 //                                         hexadecimal or decimal doubles; prints one line of the spikes per rect
+//   raymond_cli tile-luma-error S.f64 Q.f64 W H rects.txt FLOOR
+//                                         rmd_tile_luma_error made on the host (raymond::tile_luma_error_host, from the header the kernel is built from) over raw
+//                                         W*H*3 f64 sums and sums of squares; rects.txt as for despike; FLOOR is read as a C99 hexadecimal or decimal double;
+//                                         prints per rect "tile_rms pixel_rms mean_luma mean_variance mean_rel_variance valid invalid", doubles as %.17g
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
 //                                         what a drop-in caller gets: one JSON line with the wall time of render_tiled -> last TileFinished
 //   (render also accepts `project:in.json` as its scene)
@@ -216,6 +224,27 @@ int main(int argc, char **argv) {
 			std::printf("\n");
 			return 0;
 		}
+		if (argc >= 8 && !std::strcmp(argv[1], "tile-luma-error")) {
+			const size_t W = (size_t)std::atoll(argv[4]), H = (size_t)std::atoll(argv[5]);
+			std::vector<Vector3> sums(W * H), sums_sq(W * H);
+			for (int i = 0; i < 2; i++) {
+				std::ifstream f(argv[2 + i], std::ios::binary);
+				std::vector<Vector3> &dst = i ? sums_sq : sums;
+				if (!f || !f.read(reinterpret_cast<char *>(dst.data()), (std::streamsize)(dst.size() * sizeof(Vector3))))
+					throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2 + i]);
+			}
+			std::vector<rmd_tile_rect> rects;
+			std::vector<uint32_t> counts;
+			std::ifstream rf(argv[6]);
+			for (rmd_tile_rect r; rf >> r.left >> r.top >> r.width >> r.height;) {
+				uint32_t n = 0;
+				rf >> n;
+				rects.push_back(r), counts.push_back(n);
+			}
+			for (const rmd_tile_luma &t : tile_luma_error_host(sums, sums_sq, W, H, rects, counts, std::strtod(argv[7], nullptr)))
+				std::printf("%.17g %.17g %.17g %.17g %.17g %u %u\n", t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid);
+			return 0;
+		}
 		if (argc >= 6 && !std::strcmp(argv[1], "tiles")) {
 			for (const rmd_tile_rect &t : generate_tiles(std::atoi(argv[2]), std::atoi(argv[3]), {std::atoi(argv[4]), std::atoi(argv[5])}))
 				std::printf("%u %u %u %u\n", t.left, t.top, t.width, t.height);
@@ -273,7 +302,7 @@ int main(int argc, char **argv) {
 		}
 		if (argc >= 8 && !std::strcmp(argv[1], "render")) {
 			const auto t0 = std::chrono::steady_clock::now(); // cli_old/src/main.rs:36
-			std::string what = argv[2], raw, dump_features, preview_prefix;
+			std::string what = argv[2], raw, dump_features, preview_prefix, dump_tiles;
 			bool auto_exposure = false;
 			Settings st;
 			st.camera_settings.backbuffer_width = std::atoi(argv[3]);
@@ -290,7 +319,10 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--end-black-paths")) st.end_black_paths = std::atoi(argv[i + 1]) != 0; // opt-in on mesh scenes (raymond_hip.h)
 				else if (!std::strcmp(argv[i], "--adaptive")) st.adaptive_threshold = std::atof(argv[i + 1]); // (render_tiled refuses it without --spi)
 				else if (!std::strcmp(argv[i], "--adaptive-floor")) st.adaptive_floor = std::atof(argv[i + 1]);
-				else if (!std::strcmp(argv[i], "--denoise")) st.denoise = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--adaptive-measure")) st.adaptive_measure = argv[i + 1]; // (render_tiled checks it)
+				else if (!std::strcmp(argv[i], "--dump-tiles")) dump_tiles = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--tile-size")) st.tile_size = {(size_t)std::strtoull(argv[i + 1], nullptr, 10), (size_t)std::strtoull(argv[i + 1], nullptr, 10)};
+				else if (!std::strcmp(argv[i], "--denoise"))st.denoise = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-radius")) st.denoise_radius = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--denoise-patch")) st.denoise_patch = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-k")) st.denoise_k = std::atof(argv[i + 1]);
@@ -339,7 +371,7 @@ int main(int argc, char **argv) {
 			// (--dump-features: every message is taken by consume, which keeps the finished tiles' rects and counts)
 			std::vector<double> feature_means;
 			std::vector<Tile> finished;
-			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty();
+			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty() || !dump_tiles.empty();
 			std::vector<Vector3> image = by_consume ? consume(handle, st, progressed, nullptr, t0, &scene, dump_features.empty() ? nullptr : &feature_means, &finished, preview_prefix)
 			                                        : handle.await();
 			const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
@@ -356,6 +388,14 @@ int main(int argc, char **argv) {
 				}
 				std::ofstream f(dump_features, std::ios::binary);
 				f.write(reinterpret_cast<const char *>(feature_means.data()), (std::streamsize)(feature_means.size() * 8));
+			}
+			if (!dump_tiles.empty()) { // the finished tiles in the order they arrived: which tile stopped at which count, and by what error
+				std::ofstream f(dump_tiles);
+				char line[128];
+				for (const Tile &t : finished) {
+					std::snprintf(line, sizeof(line), "%zu %zu %zu %zu %zu %.17g\n", t.left, t.top, t.width, t.height, t.sample_count, t.error);
+					f << line;
+				}
 			}
 			double exposure = 1.0; // :165
 			if (auto_exposure) { // the final frame is on the host already: its histogram is made here, with the lines the device's kernel is built from

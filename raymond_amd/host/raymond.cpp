@@ -4,6 +4,7 @@
 
 #include "../csrc/despike_rule.hpp"
 #include "../csrc/luma_bins.hpp"
+#include "../csrc/tile_luma_rule.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -430,6 +431,7 @@ struct TileWorker : Worker {
 	const size_t workers, batch;
 	// previews (one worker: render_tiled): every batch is then one pass over all live tiles, which all hold the same count
 	const bool preview, preview_filtered, adaptive, moments;
+	const bool luma_measure;  // settings.adaptive_measure is "luma_tile" or "luma_pixel": the check is rmd_tile_luma_error
 	const bool despike_check; // settings.despike in an adaptive render (one worker: check_settings): the check reads despiked copies of the sums
 	const size_t step;
 	Frame fb, fb_sq;    // fb_sq: the sums of squares of an adaptive, denoised or despiked render
@@ -454,7 +456,8 @@ struct TileWorker : Worker {
 
 	TileWorker(TaskHandle::Shared &sh, int device, int me, size_t workers, const Scene &scene, const Settings &st, size_t batch)
 	    : Worker(sh, device, scene, st), me(me), workers(workers), batch(batch), preview(st.preview_every > 0), preview_filtered(preview && st.preview_denoise),
-	      adaptive(st.adaptive_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered || st.despike), despike_check(st.despike && adaptive),
+	      adaptive(st.adaptive_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered || st.despike), luma_measure(st.adaptive_measure != "channel_max"),
+	      despike_check(st.despike && adaptive),
 	      step(st.samples_per_iteration ? st.samples_per_iteration : st.sample_count), fb(frame()), fb_sq(frame(moments)), fb_preview(frame(preview_filtered)),
 	      fb_spare(frame(despike_check)), fb_spare_sq(frame(despike_check)) {}
 
@@ -545,7 +548,9 @@ struct TileWorker : Worker {
 
 	// adaptive: the error of every tile this pass has left below sample_count, one rmd_tile_error per sample count (it waits for the pass); a
 	// tile at or below the threshold is finished at the samples it has
-	std::vector<bool> converged_tiles(const std::vector<Tile> &mine) {
+	// With a luma measure (settings.adaptive_measure): ONE rmd_tile_luma_error over all of them, each rect at its own count; its tile_rms or pixel_rms
+	// decides and stays with the tile as `error`
+	std::vector<bool> converged_tiles(std::vector<Tile> &mine) {
 		std::vector<bool> converged(mine.size(), false);
 		if (!adaptive) return converged;
 		std::map<size_t, std::vector<size_t>> live;
@@ -562,6 +567,22 @@ struct TileWorker : Worker {
 			      ctx, "rmd_despike");
 			s = fb_spare, s_sq = fb_spare_sq;
 		}
+		if (luma_measure) {
+			std::vector<size_t> which;
+			std::vector<uint32_t> counts;
+			for (size_t i = 0; i < mine.size(); i++)
+				if (mine[i].sample_count < st.sample_count) which.push_back(i), counts.push_back((uint32_t)mine[i].sample_count);
+			const std::vector<rmd_tile_rect> rects = rects_of(mine, which);
+			std::vector<rmd_tile_luma> luma(rects.size());
+			if (!rects.empty())
+				check(rmd_tile_luma_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.adaptive_floor, luma.data()), ctx,
+				      "rmd_tile_luma_error");
+			for (size_t k = 0; k < luma.size(); k++) {
+				const double e = st.adaptive_measure == "luma_tile" ? luma[k].tile_rms : luma[k].pixel_rms;
+				mine[which[k]].error = e, converged[which[k]] = e <= st.adaptive_threshold;
+			}
+			live.clear(); // (no rmd_tile_error call below)
+		}
 		for (auto &grp : live) {
 			const std::vector<rmd_tile_rect> rects = rects_of(mine, grp.second);
 			std::vector<double> err(rects.size());
@@ -575,7 +596,7 @@ struct TileWorker : Worker {
 		return converged;
 	}
 
-	std::vector<Fate> decide(const std::vector<Tile> &mine) {
+	std::vector<Fate> decide(std::vector<Tile> &mine) {
 		const std::vector<bool> converged = converged_tiles(mine);
 		std::vector<Fate> fate(mine.size());
 		for (size_t i = 0; i < mine.size(); i++) {
@@ -891,6 +912,8 @@ std::string check_settings(const Settings &st) {
 	if (!(st.adaptive_threshold >= 0.0)) return "adaptive_threshold must be >= 0 (0 = off)";
 	if (st.adaptive_threshold > 0.0 && st.samples_per_iteration == 0) return "adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)";
 	if (!positive(st.adaptive_floor)) return "adaptive_floor must be finite and > 0";
+	if (st.adaptive_measure != "channel_max" && st.adaptive_measure != "luma_tile" && st.adaptive_measure != "luma_pixel")
+		return "adaptive_measure must be \"channel_max\", \"luma_tile\" or \"luma_pixel\"";
 	if (st.denoise_dual && !st.denoise) return "denoise_dual needs denoise";
 	if (st.denoise_dual && st.samples_per_iteration == 0) return "denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)";
 	if (st.denoise_dual && st.denoise_features) return "denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight";
@@ -903,6 +926,7 @@ std::string check_settings(const Settings &st) {
 	if (!(st.adaptive_denoised_threshold >= 0.0)) return "adaptive_denoised_threshold must be >= 0 (0 = off)";
 	if (st.adaptive_denoised_threshold > 0.0 && !st.denoise_dual) return "adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)";
 	if (st.adaptive_denoised_threshold > 0.0 && st.adaptive_threshold > 0.0) return "adaptive_denoised_threshold and adaptive_threshold are mutually exclusive";
+	if (st.denoise_dual && st.adaptive_measure != "channel_max") return "adaptive_measure cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual";
 	if (st.denoise_dual && st.worker_count > 1) return "denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own";
 	if (!(st.denoise_feature_slope >= 0.0) || !std::isfinite(st.denoise_feature_slope)) return "denoise_feature_slope must be finite and >= 0 (0 = off)";
 	if (st.denoise_feature_slope > 0.0 && (st.denoise_atrous || st.denoise_dual_atrous))
@@ -1141,6 +1165,20 @@ std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::
 			}
 		}
 	return replaced;
+}
+
+std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
+                                                const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double floor) {
+	if (sums.size() != width * height || sums_sq.size() != width * height || rects.size() != counts.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_luma_error_host: bad argument");
+	std::vector<rmd_tile_luma> out(rects.size());
+	const double *S = sums.empty() ? nullptr : sums[0].data(), *Q = sums_sq.empty() ? nullptr : sums_sq[0].data();
+	for (size_t j = 0; j < rects.size(); j++) {
+		const rmd_tile_rect &r = rects[j];
+		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_luma_error_host: tile rectangle outside the framebuffer");
+		const rmd::TileLuma t = rmd::tile_luma_rect_host(S, Q, (uint32_t)width, r.left, r.top, r.width, r.height, counts[j], floor);
+		out[j] = rmd_tile_luma{t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid};
+	}
+	return out;
 }
 
 std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors, const Scene *scene) {

@@ -128,6 +128,11 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// samples_per_iteration > 0; render_tiled throws raymond::Error otherwise, and for a negative threshold.
 	double adaptive_threshold = 0.0;
 	double adaptive_floor = 1e-3;
+	// What that check compares with the threshold: "channel_max", rmd_tile_error — the worst channel of the worst pixel —, or one rmd_tile_luma_error call's
+	// tile_rms ("luma_tile": the RMS standard error of the tile's luminance over the tile's mean luminance) or pixel_rms ("luma_pixel": the RMS of the pixels'
+	// relative luminance errors), both at `adaptive_floor`; a finished tile's `error` is then that value.  The three thresholds are not comparable numbers.
+	// render_tiled throws for any other value whether or not adaptive sampling is on, and for a luma measure with denoise_dual, whose check is its own.
+	std::string adaptive_measure = "channel_max";
 	// Denoising (an extension; false = off): await() returns the assembled frame filtered by rmd_denoise (raymond_hip.h) with these parameters; the
 	// passes then render with second moments and TileFinished tiles carry them in `data_sq`.  render_tiled throws raymond::Error for values
 	// rmd_denoise refuses (radius <= 12, patch <= 4, k finite and > 0, alpha finite and >= 0).
@@ -252,7 +257,9 @@ struct Tile { // core/src/tile.rs:7-14
 	// `data_sq` are then the halves' sums added and sample_count = count_a + count_b.  Empty / 0 otherwise
 	TileData data_a, data_sq_a, data_b, data_sq_b;
 	size_t count_a = 0, count_b = 0;
-	double error = -1.0; // dual-buffer adaptive renders: the tile's rmd_tile_error_dual when it was last checked; -1: never
+	// dual-buffer adaptive renders: the tile's rmd_tile_error_dual when it was last checked; adaptive renders by a luma measure (settings.adaptive_measure):
+	// its rmd_tile_luma_error tile_rms or pixel_rms, whichever decides; -1: never
+	double error = -1.0;
 };
 // An extension (settings.preview_every): the frame after pass `pass_index` (counted from 1), row-major RGB bytes; sample_count: the samples per pixel
 // of a tile that is still live (tiles that finished early are in the frame at the count they finished with)
@@ -344,6 +351,11 @@ rmd_luma_histogram luminance_histogram(const std::vector<Vector3> &image);
 std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height, const std::vector<rmd_tile_rect> &rects,
                                    const std::vector<uint32_t> &counts, uint32_t radius, uint32_t rank, double k, double ratio, double floor,
                                    std::vector<Vector3> &out_sums, std::vector<Vector3> &out_sums_sq);
+// rmd_tile_luma_error on the host, from the header the kernel is built from (raymond_amd/csrc/tile_luma_rule.hpp: 256 emulated lanes and the kernel's
+// combine): rect i of the width * height sums and sums of squares at counts[i].  No argument is checked beyond the sizes; rects are inside the frame.  What
+// raymond_cli tile-luma-error runs, and what holds the header to the numpy restatement without a GPU
+std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
+                                                const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double floor);
 // await() with settings.despike alone: the finished tiles' sums and sums of squares assembled, despiked on `device` (rmd_despike) and divided by each
 // tile's count
 std::vector<Vector3> despike_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device);

@@ -181,6 +181,10 @@ SIGNATURES = {
         [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double,
          _vp, _vp, _P(C.c_uint32)],
     ),
+    "rmd_tile_luma_error": (
+        C.c_int32,
+        [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_double, _P(abi.TileLuma)],
+    ),
     "rmd_comm_prepare_process": (C.c_int32, []),
     "rmd_comm_unique_id": (C.c_int32, [_vp]),
     "rmd_comm_create": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _P(_vp)]),

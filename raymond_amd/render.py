@@ -2,7 +2,7 @@
 
 Bottom up:
   * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], despike, the denoise family (every rmd_denoise* call is laid out
+  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, despike, the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -272,6 +272,30 @@ def despike_arrays(ctx, sums, sums_sq, rects, counts, **params):
         s, q, s_out, q_out = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq), (Framebuffer, None), (Framebuffer, None))
         _, _, replaced = despike(ctx, s, q, rects, counts, out=(s_out, q_out), **params)
         return s_out.download(), q_out.download(), replaced
+
+
+TILE_LUMA_DTYPE = np.dtype([("tile_rms", "<f8"), ("pixel_rms", "<f8"), ("mean_luma", "<f8"), ("mean_variance", "<f8"), ("mean_rel_variance", "<f8"),
+                            ("valid", "<u4"), ("invalid", "<u4")])  # rmd_tile_luma, field for field
+assert TILE_LUMA_DTYPE.itemsize == C.sizeof(abi.TileLuma)
+
+
+def tile_luma_error(ctx, framebuffer, framebuffer_sq, tiles, counts, floor):
+    """rmd_tile_luma_error: per tile, at its own sample count, the aggregated noise of its luminance — a numpy structured array with rmd_tile_luma's fields:
+    tile_rms (the RMS standard error of the luminance over the tile's mean luminance), pixel_rms (the RMS of the pixels' relative luminance errors), the
+    three means they are made of, and the valid / invalid pixel counts.  Tiles may overlap or repeat."""
+    tiles = list(tiles)
+    (counts,) = _counts(tiles, counts)
+    out = np.zeros(max(1, len(tiles)), dtype=TILE_LUMA_DTYPE)
+    ctx.check(ctx.L.rmd_tile_luma_error(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(tiles), _u32(counts),
+                                        len(tiles), float(floor), out.ctypes.data_as(C.POINTER(abi.TileLuma))))
+    return out[: len(tiles)]
+
+
+def tile_luma_error_arrays(ctx, sums, sums_sq, tiles, counts, floor):
+    """tile_luma_error() for host arrays: (H, W, 3) sums and sums of squares in, the structured array out."""
+    with contextlib.ExitStack() as stack:
+        s, q = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq))
+        return tile_luma_error(ctx, s, q, tiles, counts, floor)
 
 
 _GUIDED = {"rmd_denoise": "rmd_denoise_guided", "rmd_denoise_dual": "rmd_denoise_dual_guided"}  # the stems whose name says that the features are there
@@ -631,7 +655,9 @@ class Tile:  # core/src/tile.rs:7-14
         self.left, self.top, self.width, self.height = left, top, width, height
         self.sample_count = sample_count
         self.data = data  # (height, width, 3) running sums, like Tile.data
-        self.error = error  # adaptive renders (an extension): the tile's rmd_tile_error at sample_count when it was checked, else None
+        # adaptive renders (an extension): the measure that decided — the tile's rmd_tile_error, or with settings.adaptive_measure "luma_tile" / "luma_pixel"
+        # its rmd_tile_luma_error tile_rms / pixel_rms — at sample_count when it was checked, else None
+        self.error = error
         self.data_sq = data_sq  # denoised renders (an extension): the finished tile's running sums of squares, like data; else None
         # dual-buffer renders (an extension): the finished tile's two sample halves — sums, sums of squares (like data) and samples per pixel —;
         # data and data_sq are then the halves' sums added, sample_count = count_a + count_b.  Else None
@@ -874,7 +900,8 @@ class _TiledLoop:
         self.passes += 1
 
     def adaptive_check(self, w):
-        """rmd_tile_error of `w`'s live tiles (None each without adaptive_threshold); with despike, on the despiked sums of all its tiles at their counts."""
+        """The settings' adaptive measure of `w`'s live tiles (None each without adaptive_threshold): rmd_tile_error, or with a luma measure one
+        rmd_tile_luma_error call's tile_rms or pixel_rms; with despike, on the despiked sums of all its tiles at their counts."""
         st = self.st
         if not (self.adaptive and w.live):
             return [None] * len(w.live)
@@ -883,6 +910,9 @@ class _TiledLoop:
             rects, counts = w.whole_frame(self.done)
             despike(w.ctx, fb, fb_sq, rects, counts, out=self.spare, want_replaced=False, **st.despike_keywords())
             fb, fb_sq = self.spare
+        if st.adaptive_measure != "channel_max":
+            luma = tile_luma_error(w.ctx, fb, fb_sq, w.live, [self.done] * len(w.live), st.adaptive_floor)
+            return luma["tile_rms" if st.adaptive_measure == "luma_tile" else "pixel_rms"]
         return tile_error(w.ctx, fb, fb_sq, self.done, st.adaptive_floor, w.live)
 
     def finish(self, w, rect, sample_count, data, error=None, data_sq=None):
@@ -956,7 +986,8 @@ def render_tiled(scene, settings, devices=(0,)):
 
     Adaptive (settings.adaptive_threshold > 0, an extension): every pass renders the tiles that are still live with their second moments, and
     after each pass that leaves them below sample_count a tile whose rmd_tile_error is at most the threshold is sent as TileFinished at its
-    current sample count and takes no further passes; the others are sent as TileProgressed and go on.
+    current sample count and takes no further passes; the others are sent as TileProgressed and go on.  With settings.adaptive_measure "luma_tile" or
+    "luma_pixel" the check is one rmd_tile_luma_error call over the live tiles instead, and its tile_rms or pixel_rms is what meets the threshold.
 
     Denoised (settings.denoise, an extension): the passes render with second moments, every TileFinished tile carries them as `data_sq`, and
     TaskHandle.await_() denoises the assembled frame on the first of `devices`.

@@ -250,7 +250,8 @@ class Settings:
                  denoise_atrous_levels=5, denoise_atrous_k=3.0, denoise_dual_atrous=False, denoise_dual_atrous_region=False, preview_every=0,
                  preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, preview_auto_exposure=False,
                  auto_exposure_percentile=0.99, auto_exposure_target=0.8, denoise_feature_slope=0.0,
-                 denoise_atrous_slope=0.0, despike=False, despike_radius=2, despike_rank=2, despike_k=6.0, despike_ratio=2.0, despike_floor=0.0):
+                 denoise_atrous_slope=0.0, despike=False, despike_radius=2, despike_rank=2, despike_k=6.0, despike_ratio=2.0, despike_floor=0.0,
+                 adaptive_measure="channel_max"):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -270,6 +271,11 @@ class Settings:
         # error (raymond_hip.h: rmd_tile_error, with `adaptive_floor` as its floor) is at most `adaptive_threshold` is finished at the samples it has.
         self.adaptive_threshold = float(adaptive_threshold)
         self.adaptive_floor = float(adaptive_floor)
+        # What the adaptive_threshold check compares with the threshold: "channel_max", rmd_tile_error — the worst channel of the worst pixel —, or one
+        # rmd_tile_luma_error call's tile_rms ("luma_tile": the RMS standard error of the tile's luminance over the tile's mean luminance) or pixel_rms
+        # ("luma_pixel": the RMS of the pixels' relative luminance errors), both with `adaptive_floor` as the floor.  The three thresholds are not comparable
+        # numbers.  Checked whether or not adaptive sampling is on; no effect on the dual loop, and refused with denoise_dual.
+        self.adaptive_measure = adaptive_measure
         self.check_adaptive()
         # Denoising (an extension; False = off): TaskHandle.await_() returns the assembled frame filtered by rmd_denoise (raymond_hip.h) with
         # these parameters; render_tiled then renders with second moments.
@@ -419,6 +425,8 @@ class Settings:
             raise ValueError("adaptive_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)")
         if not (self.adaptive_floor > 0.0 and np.isfinite(self.adaptive_floor)):
             raise ValueError("adaptive_floor must be finite and > 0")
+        if not (isinstance(self.adaptive_measure, str) and self.adaptive_measure in abi.ADAPTIVE_MEASURES):
+            raise ValueError('adaptive_measure must be "channel_max", "luma_tile" or "luma_pixel"')
 
     def check_denoise(self):
         """Raises ValueError for denoise settings rmd_denoise / rmd_denoise_guided refuse (checked whether or not denoise is on)."""
@@ -481,6 +489,8 @@ class Settings:
         v = self.adaptive_min_samples
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
             raise ValueError("adaptive_min_samples must be an integer >= 0")
+        if self.denoise_dual and self.adaptive_measure != "channel_max":
+            raise ValueError("adaptive_measure cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual")
 
     def check_preview(self, n_devices=1):
         """Raises ValueError for preview settings render_tiled cannot follow on `n_devices` devices."""
