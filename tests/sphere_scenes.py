@@ -8,6 +8,15 @@ decisions into its other states.  tests/test_sphere_scenes_host.py holds the ora
 what makes the oracle's answer a reference for them) and asserts through the host probe that a class exercises what it names;
 tests/test_gpu_sphere_scenes.py then holds every launch form of the device to form A byte for byte, and to the oracle.
 
+Twelve classes are aimed at the scene table and the candidate sets: shuffled_room, signed_zero_normals, partial_room, duplicate_walls, tilted_pairs,
+camera_on_walls, coincident_spheres, table_edges, one_lobe, rough_extremes, fov_and_aspect, irregular.  Five (TILE_CLASS_CLASSES) are aimed at the
+TILE CLASSES of primary_candidates.hpp — the work items that see one wall and end their samples as an EMITTER or a BLACK item, which the twelve
+barely reach: one_wall_mixed (EMITTER, BLACK and general tiles in one frame, bounce limits 1, 2, 5, 16; with a thin-lens variant),
+emitter_colours (every tile EMITTER; signed zeros, denormals, a negative component, 1e150), black_walls (every tile BLACK; the wall's colour as
+signed zeros, roughness 512 and 1e-12, first and last in the table, a black Metal wall that must stay general), class_table_edge (63, 64 and 65
+objects: the last table length with classes and the first without) and ragged_one_wall (frames from 1x1 to 41x25: classed tiles one pixel wide
+and high).
+
 One function per class, seeded and deterministic: f(seed, lens=False) -> (Scene, CameraSettings, dict of Settings keywords, note).  CLASSES names
 them, SEEDS gives each class's seeds (at least two), LENS_CLASSES the classes that also yield a thin-lens variant (use_dof with C5's aperture:
 the candidate sets must switch themselves off).  cases() lists (class, seed, lens); build(case) makes one.
@@ -374,12 +383,167 @@ def irregular(seed, lens=False):
     return scene, cam, kw, note + ", a roughness-0 sphere"
 
 
+# ---------------------------------------------------------------- the tile classes (primary_candidates.hpp: TILE CLASSES)
+# The classes above leave most wave tiles general: over all their cases the host probe finds 15 BLACK and 37 EMITTER tiles.  The ones below are
+# rooms looked at so that whole wave tiles see ONE wall, which a work item of the role-sorted kernel then ends as an EMITTER or a BLACK item.
+def _plain(rng):
+    """a coloured Diffuse or a Metal: a wall that is neither black nor a light"""
+    return (_diffuse, _metal)[int(rng.integers(0, 2))](rng)
+
+
+def _walls_by_role(lo, hi, mats):
+    """the six walls, keyed (axis, plus); mats: {(axis, plus): Material}"""
+    return {(k, plus): Object(_wall(k, plus, lo[k] if plus else hi[k]), mats[(k, plus)]) for k in range(3) for plus in (True, False)}
+
+
+def _scene_of(objects):
+    scene = Scene()
+    scene.objects = list(objects)
+    return scene
+
+
+ONE_WALL_MIXED = ((40, 24), (56, 40), (56, 40), (40, 24), (56, 40), (40, 24))  # the frame per seed; the bounce limit is BOUNCE_LIMITS[seed % 4]
+
+
+def one_wall_mixed(seed, lens=False):
+    """Six axis walls, the camera near one side wall: that wall emits and fills the frame's columns on its side, the back wall is black Diffuse and
+    fills the others, and the seam between them (and, in the corners, the floor's and the ceiling's) crosses the tiles in between, which stay
+    general.  EMITTER, BLACK and GENERAL items in one launch, at every bounce limit (BOUNCE_LIMITS[seed % 4]: a BLACK item at limit 1 parks every
+    survivor and ends it); odd seeds put one small sphere in front of the back wall.  The thin-lens variant switches every class off."""
+    rng = np.random.default_rng([13, seed])
+    frame = ONE_WALL_MIXED[seed % len(ONE_WALL_MIXED)]
+    lo = [-_dyadic(rng, 1.5, 2.5), -_dyadic(rng, 2.0, 2.5), -_dyadic(rng, 0.5, 1.5)]
+    hi = [_dyadic(rng, 1.5, 2.5), _dyadic(rng, 2.0, 2.5), _dyadic(rng, 3.0, 4.0)]
+    right = frame == (40, 24) and seed != 3  # the side wall the camera is near (on the wide frame the left one: the rect lists of the GPU test end at x = 37)
+    side = (0, not right)  # (the wall at hi[0] has the normal -e_x)
+    mats = {(k, plus): _plain(rng) for k in range(3) for plus in (True, False)}
+    mats[side], mats[(2, False)] = _emission(rng), _black(rng)
+    near = _dyadic(rng, 0.625, 1.0)
+    pos = (hi[0] - near if right else lo[0] + near, _dyadic(rng, -0.25, 0.25), 0.0)
+    walls = _walls_by_role(lo, hi, mats)
+    others = [Object(Sphere((pos[0] + (-1.0 if right else 1.0), -0.75, 2.5), 0.125), _material(rng))] if seed % 2 else []
+    objs = list(walls.values()) + others
+    scene = _scene_of(objs[i] for i in rng.permutation(len(objs)))
+    fov = (35.0, 55.0)[frame == (56, 40)]
+    kw = _kw(rng, seed, lens, bounce_limit=BOUNCE_LIMITS[seed % 4])
+    return scene, _camera(pos, frame=frame, fov=fov, lens=lens), kw, "camera %.3f from the emitting %s wall, back wall black, fov %g" % (near, "right" if right else "left", fov)
+
+
+# one colour per seed: signed zeros, a negative component, the smallest denormal, the smallest normal, the regular class's bound, three ordinary values
+EMITTER_COLOURS = ((0.0, -0.0, 1.0), (0.75, -0.5, 1.25), (5e-324, 1.0, -5e-324), (2.0**-1022, 0.5, -(2.0**-1022)), (1e150, 5e-324, -1e150), (0.3, 1.7, 0.9))
+
+
+def emitter_colours(seed, lens=False):
+    """A narrow view of the emitting back wall: every wave tile is an EMITTER item, whose samples are the wall's colour stored as it stands in the
+    table — EMITTER_COLOURS[seed].  1e150 is the regular class's bound: 1.0 * x = x, the sum of 160 of them and the moments' 1e300 stay finite, a
+    denormal's square underflows to 0; -0.0 must add as the reference's -0.0 does."""
+    rng = np.random.default_rng([14, seed])
+    colour = EMITTER_COLOURS[seed % len(EMITTER_COLOURS)]
+    lo, hi = _bounds(rng)
+    mats = {(k, plus): _material(rng) for k in range(3) for plus in (True, False)}
+    mats[(2, False)] = Material.Emission(colour)
+    objs = list(_walls_by_role(lo, hi, mats).values())
+    scene = _scene_of(objs[i] for i in rng.permutation(len(objs)))
+    fov = float(rng.uniform(12.0, 20.0))
+    pos = (_dyadic(rng, -0.25, 0.25), _dyadic(rng, -0.25, 0.25), 0.0)
+    return scene, _camera(pos, fov=fov), _kw(rng, seed, bounce_limit=BOUNCE_LIMITS[seed % 4]), "the back wall emits %r, fov %.1f" % (colour, fov)
+
+
+# (what, the black wall's colour, its roughness, its place in the table, the bounce limit)
+BLACK_WALLS = (("signed zeros", (-0.0, 0.0, -0.0), 0.375, "first", 2), ("roughness 512", (0.0, 0.0, 0.0), 512.0, "last", 5),
+               ("roughness 1e-12", (0.0, 0.0, 0.0), 1e-12, "any", 16), ("a black Metal wall beside it", (0.0, 0.0, 0.0), 0.25, "any", 2),
+               ("roughness -512", (0.0, -0.0, 0.0), -512.0, "any", 5))
+
+
+def black_metal_wall(scene):
+    """index of the black Metal wall of a scene, or None"""
+    return next((i for i, o in enumerate(scene.objects) if o.material.kind == abi.RMD_MAT_METAL and tuple(o.material.color) == (0.0, 0.0, 0.0)), None)
+
+
+def black_walls(seed, lens=False):
+    """A narrow view of the black Diffuse back wall: every wave tile is a BLACK item, every generation trip of the launch a round.  BLACK_WALLS[seed]:
+    the colour as signed zeros (kObjBlackDiffuse is set by == 0.0), the roughness the survivors' GGX hits take (512, 1e-12, -512), the wall first
+    and last in the table.  Seed 3 looks wider from near the left wall, which is black METAL: prob_d = 0, every sample of it is a specular bounce
+    whose Fresnel term (1 - cos)^5 is not zero, and its tiles must stay general.  The ceiling and the wall behind the camera emit, so survivors carry
+    light from their second vertex on (no frame is black: a BLACK item at bounce limit 1 is one_wall_mixed's); at roughness 1e-12 that light is
+    too faint to show in a sum, and one tile holds a small emitting sphere."""
+    rng = np.random.default_rng([15, seed])
+    what, colour, rough, place, bounces = BLACK_WALLS[seed % len(BLACK_WALLS)]
+    lo, hi = _bounds(rng)
+    mats = {(k, plus): _plain(rng) for k in range(3) for plus in (True, False)}
+    mats[(2, False)] = Material.Diffuse(colour, rough)
+    mats[(1, False)], mats[(2, True)] = _emission(rng), _emission(rng)
+    metal = "Metal" in what
+    pos, fov = (_dyadic(rng, -0.25, 0.25), _dyadic(rng, -0.25, 0.25), 0.0), float(rng.uniform(12.0, 20.0))
+    if metal:
+        mats[(0, True)] = Material.Metal((0.0, 0.0, 0.0), 0.875)  # (rough: its lobe reaches the emitting ceiling at the second vertex)
+        pos, fov = (lo[0] + 0.75, pos[1], 0.0), 35.0
+    walls = _walls_by_role(lo, hi, mats)
+    back = walls.pop((2, False))
+    rest = list(walls.values())
+    if rough == 1e-12:  # what such a mirror returns is 1e-15 a sample: a small light in the middle of ONE tile (28, 4) or (28, 20), which is then general
+        ey = math.tan(math.radians(fov) / 2.0)
+        rest.append(Object(Sphere((pos[0] + 2.0 * 0.4 * ey * FRAME[0] / FRAME[1], pos[1] + 2.0 * (2.0 / 3.0) * ey, 2.0), 0.03125), _emission(rng)))
+    rest = [rest[i] for i in rng.permutation(len(rest))]
+    at = {"first": 0, "last": len(rest)}.get(place, int(rng.integers(1, len(rest))))
+    scene = _scene_of(rest[:at] + [back] + rest[at:])
+    return scene, _camera(pos, fov=fov), _kw(rng, seed, bounce_limit=bounces), "the back wall black Diffuse at %d of the table: %s" % (at, what)
+
+
+CLASS_TABLE_EDGE = (63, 64, 65)  # objects
+
+
+def class_table_edge(seed, lens=False):
+    """63, 64 and 65 objects (CLASS_TABLE_EDGE[seed]): the six walls first, then small spheres in a lattice in one corner of the view, which the
+    other tiles' cones clear, and LAST one small sphere apart from them in front of the black back wall.  With 63 and 64 objects that sphere has a
+    bit in the visit mask, its tile is general and the tiles that clear every sphere are classed; with 65 it is object 64, which no mask reaches,
+    and NO tile may be classed (primary_one_wall: n_objects - 1 < 64) — a rule that looked at the mask alone would class the tile it sits in."""
+    rng = np.random.default_rng([16, seed])
+    n = CLASS_TABLE_EDGE[seed % len(CLASS_TABLE_EDGE)]
+    lo, hi = [-1.25, -0.875, -1.0], [2.5, 2.0, 3.5]  # (0.8 lo at z = 1.5: the frame's lower left corner at fov 55)
+    mats = {(k, plus): _plain(rng) for k in range(3) for plus in (True, False)}
+    mats[(2, False)], mats[(1, False)], mats[(1, True)] = _black(rng), _emission(rng), _emission(rng)
+    objs = list(_walls_by_role(lo, hi, mats).values())
+    objs = [objs[i] for i in rng.permutation(6)]
+    for s in range(n - 7):
+        i, j = s % 8, s // 8
+        objs.append(Object(Sphere((0.8 * lo[0] + 0.02 * i, 0.8 * lo[1] + 0.02 * j, 1.5), 0.03), _material(rng)))
+    objs.append(Object(Sphere((0.5, 0.25, 2.5), 0.125), _emission(rng)))  # apart from the others, and the table's last object
+    assert len(objs) == n
+    return _scene_of(objs), _camera(frame=(56, 40)), _kw(rng, seed, bounce_limit=(5, 2, 5)[seed % 3]), "%d objects, the last a sphere apart from the cluster" % n
+
+
+# (frame, fov, what the back wall is, the bounce limit)
+RAGGED_ONE_WALL = (((1, 1), 12.0, "black", 2), ((1, 8), 12.0, "emitter", 2), ((9, 9), 12.0, "black", 2), ((41, 25), 35.0, "emitter", 5),
+                   ((7, 33), 20.0, "black", 16), ((33, 7), 12.0, "black", 2), ((9, 9), 12.0, "emitter", 5))
+
+
+def ragged_one_wall(seed, lens=False):
+    """Frames of 1x1, 1x8, 9x9, 41x25, 7x33 and 33x7 pixels (RAGGED_ONE_WALL[seed]) that look at the back wall alone, black Diffuse or emitting:
+    classed wave tiles one pixel wide and one pixel high, a generation round over a single pixel's samples.  The tiny frames at fov 12."""
+    rng = np.random.default_rng([17, seed])
+    frame, fov, what, bounces = RAGGED_ONE_WALL[seed % len(RAGGED_ONE_WALL)]
+    lo, hi = _bounds(rng)
+    mats = {(k, plus): _plain(rng) for k in range(3) for plus in (True, False)}
+    mats[(1, False)], mats[(2, True)] = _emission(rng), _emission(rng)  # (the ceiling, and the wall behind the camera: a survivor's second vertex)
+    mats[(2, False)] = _black(rng) if what == "black" else _emission(rng)
+    objs = list(_walls_by_role(lo, hi, mats).values())
+    scene = _scene_of(objs[i] for i in rng.permutation(len(objs)))
+    pos = (_dyadic(rng, -0.25, 0.25), _dyadic(rng, -0.25, 0.25), 0.0)
+    return scene, _camera(pos, frame=frame, fov=fov), _kw(rng, seed, bounce_limit=bounces), "%dx%d at fov %g, the back wall %s" % (frame[0], frame[1], fov, what)
+
+
+TILE_CLASS_CLASSES = ("one_wall_mixed", "emitter_colours", "black_walls", "class_table_edge", "ragged_one_wall")
 CLASSES = {f.__name__: f for f in (shuffled_room, signed_zero_normals, partial_room, duplicate_walls, tilted_pairs, camera_on_walls, coincident_spheres,
-                                   table_edges, one_lobe, rough_extremes, fov_and_aspect, irregular)}
+                                   table_edges, one_lobe, rough_extremes, fov_and_aspect, irregular, one_wall_mixed, emitter_colours, black_walls,
+                                   class_table_edge, ragged_one_wall)}
 SEEDS = {"shuffled_room": (0, 1, 2), "signed_zero_normals": (0, 1), "partial_room": (0, 1, 2, 3), "duplicate_walls": (0, 1), "tilted_pairs": (0, 1, 2),
          "camera_on_walls": tuple(range(len(CAMERA_ON_WALLS))), "coincident_spheres": (0, 1), "table_edges": tuple(range(len(TABLE_EDGES))),
-         "one_lobe": (0, 1, 2, 3), "rough_extremes": (0, 1), "fov_and_aspect": tuple(range(len(FOV_AND_ASPECT))), "irregular": (0, 1)}
-LENS_CLASSES = ("shuffled_room", "partial_room", "camera_on_walls", "coincident_spheres")
+         "one_lobe": (0, 1, 2, 3), "rough_extremes": (0, 1), "fov_and_aspect": tuple(range(len(FOV_AND_ASPECT))), "irregular": (0, 1),
+         "one_wall_mixed": tuple(range(len(ONE_WALL_MIXED))), "emitter_colours": tuple(range(len(EMITTER_COLOURS))),
+         "black_walls": tuple(range(len(BLACK_WALLS))), "class_table_edge": tuple(range(len(CLASS_TABLE_EDGE))),
+         "ragged_one_wall": tuple(range(len(RAGGED_ONE_WALL)))}
+LENS_CLASSES = ("shuffled_room", "partial_room", "camera_on_walls", "coincident_spheres", "one_wall_mixed")
 LENS_SEEDS = (0, 1)  # the seeds whose thin-lens variant is yielded
 
 
