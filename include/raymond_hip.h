@@ -60,7 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_tile_luma_error,
+	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
@@ -990,6 +990,65 @@ typedef struct rmd_tile_luma {
 } rmd_tile_luma;              /* 48 bytes */
 rmd_status rmd_tile_luma_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
                                const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects, double floor, rmd_tile_luma *out_host);
+/*
+ * A TILE'S VARIANCE WEIGHTED BY LUMINANCE, the adaptive check's measure of the error where the frame is looked at (an addition within ABI 6:
+ * RMD_ABI_VERSION stays 6, no struct or entry point changes, found by its symbol).  Every pixel's variance of its luminance's mean is multiplied by a
+ * weight that depends on the pixel's luminance alone, and the weight is an entry of a table of RMD_LUMA_WEIGHTS doubles the caller passes — one per
+ * counter of rmd_luminance_histogram_tiles, in rmd_luma_histogram's order: the 256 bins, then below, above, zero, negative; not_finite has none.  The
+ * device evaluates no transcendental function: a table lookup, one product and the sums.  Any weighting of variance by luminance is such a table:
+ * rmd_display_weights makes the squared slope of the library's tone curve (the displayed error, in fractions of the display's full scale: 1/255 is one
+ * 8-bit level); all ones is the tile's absolute RMS standard error; 1 / Y^2 per bin approximates rmd_tile_luma_error's pixel_rms.
+ * S = accum_dev, Q = accum_sq_dev (W*H*3 doubles each); rect j is reduced on its own at n = rect_counts[j].  Everything is unfused binary64: every product
+ * rounded, the additions as bracketed.  Per pixel of rect j, with s and q its six sums:
+ *     the pixel is VALID if n >= 2 and its six sums are finite                                              (rmd_despike's rule)
+ *     u_c = s_c / n;   v_c = max(0, (q_c - s_c*u_c) / (n - 1)) / n
+ *     Y = (0.2126 * u_0 + 0.7152 * u_1) + 0.0722 * u_2                    the luminance of the means
+ *     V = (A0 * v_0 + A1 * v_1) + A2 * v_2                                the variance of that luminance's mean; A_c = the weight times itself
+ *     k = the counter rmd_luminance_histogram_tiles makes from the 64 bits of Y (E its unbiased exponent, M its top two mantissa bits; -32 <= E < 32:
+ *         (E + 32) * 4 + M; positive below 2^-32: 256; at or over 2^32: 257; +-0: 258; Y < 0: 259); a valid pixel whose Y is not finite counts as
+ *         INVALID (its sums are finite, so this should not occur)
+ *     w = weights[k];   E = (w == 0.0) ? 0.0 : w * V                      one rounded product; V may be +inf, and a zero weight still gives 0
+ * Sum order: the rect's pixels are numbered row-major WITHIN THE RECT, i = 0, 1, ...  Lane t of 256 adds Y, V and E of the valid pixels among
+ * i = t, t + 256, t + 512, ... in that order into three running sums that start at +0.0, and counts the valid and the invalid pixels.  The 256 partials of
+ * each sum are added exactly as rmd_tile_luma_error adds its partials: within each wave of 64 lanes the lanes 32 apart first, then 16, 8, 4, 2, 1; then
+ * the four waves' sums as (w0 + w1) + (w2 + w3).  This gives SY, SV, SE and m = (double)valid.  Then
+ *     mean_luma = m ? SY / m : 0;   mean_variance = m ? SV / m : 0;   mean_weighted_variance = m ? SE / m : 0
+ *     rms = sqrt(mean_weighted_variance)
+ * A rect without pixels gives all zeros.  A rect with pixels and invalid > 0 gives rms = +inf — its means are still those over the valid pixels —: a tile
+ * with a bad pixel never finishes on this rule, as under rmd_tile_error.  An rms that comes out NaN is reported as +inf.  The five fields other than rms
+ * are the same bits on every device and on the host; rms passes through the device's square root.  With all-ones weights mean_luma, mean_variance, valid
+ * and invalid are rmd_tile_luma_error's, bit for bit.
+ * Rects only have to lie inside the W x H frame; they may overlap or repeat.  weights_host: a HOST array of RMD_LUMA_WEIGHTS; out_host: a HOST array of
+ * n_rects.  RMD_ERR_INVALID_ARGUMENT, all checked before the device is touched, in this order: a NULL buffer, width or height 0, or n_rects > 0 with rects,
+ * rect_counts, weights_host or out_host NULL; accum_sq_dev aliasing accum_dev; a weight that is NaN, infinite or negative; a rect outside the framebuffer;
+ * and only then a NULL context.  n_rects == 0 is RMD_OK with nothing launched.  Synchronous, like rmd_tile_error; the call's device scratch (rects, counts,
+ * weights, results) stays on the context and grows on demand; one upload, one launch, one download.  One workgroup per rect: made for the adaptive check's
+ * tiles, slow for a whole frame passed as one rect.
+ */
+#define RMD_LUMA_WEIGHTS 260u   /* the 256 bins, then below, above, zero, negative: luma_bins.hpp's counter order without not_finite */
+typedef struct rmd_tile_weighted {
+	double rms;                    /* sqrt(mean_weighted_variance) */
+	double mean_weighted_variance; /* SE / m */
+	double mean_luma;              /* SY / m */
+	double mean_variance;          /* SV / m */
+	uint32_t valid, invalid;       /* pixels of the rect that are / are not valid */
+} rmd_tile_weighted;               /* 40 bytes */
+rmd_status rmd_tile_weighted_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height,
+                                   const rmd_tile_rect *rects, const uint32_t *rect_counts, uint32_t n_rects,
+                                   const double *weights_host /* RMD_LUMA_WEIGHTS */, rmd_tile_weighted *out_host);
+/* The weights that make rmd_tile_weighted_error measure the DISPLAYED error: per counter the squared slope of the library's own tone curve
+ * D(y) = (1 - exp(-y e))^(1/g) at the counter's luminance, e = exposure, g = gamma.  A host function: no context, no device; the host's libm.
+ *     t(y) = -expm1(-y * e);   slope(y) = (1/g) * pow(t, 1/g - 1) * e * exp(-y * e);   y_floor = -log1p(-pow(display_floor, g)) / e
+ * Bin i, with E = i / 4 - 32 and M = i % 4: y_c = ldexp(1.0 + (M + 0.5) * 0.25, E), the bin's centre, exact; out[i] = slope(max(y_c, y_floor))^2.
+ * below, zero and negative take slope(y_floor)^2; above takes slope(2^32)^2, which is 0 at any sane exposure.  Luminances under the one that displays at
+ * display_floor take that luminance's slope: D's slope grows without bound towards black for g > 1, and this cap keeps the weight finite (1/255, the first
+ * 8-bit level, is the value to start from).  rms is then in fractions of the display's full scale.  The weight is a function of luminance only: it stands
+ * for a tone curve applied per channel.
+ * Every output is finite and >= 0 for every accepted input: a square that overflows is clamped to the largest finite double (DBL_MAX), and a NaN — inf * 0,
+ * when 1/g overflows or pow(display_floor, g) underflows — is written as 0.
+ * RMD_ERR_INVALID_ARGUMENT (text through rmd_last_error(NULL)): out_weights NULL; exposure or gamma not finite or not > 0; display_floor not finite or
+ * outside (0, 1). */
+rmd_status rmd_display_weights(double exposure, double gamma, double display_floor, double *out_weights /* RMD_LUMA_WEIGHTS */);
 
 /* ---- multi-GPU (no reference counterpart; the reference has no collectives) ---- */
 #define RMD_COMM_ID_BYTES 128

@@ -173,6 +173,26 @@ extern "C" {
     // frame (they may overlap or repeat), out_host n_rects rmd_tile_luma; tile_rms or pixel_rms is what meets the threshold
     fn rmd_tile_luma_error(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                            rect_counts: *const u32, n_rects: u32, floor: f64, out_host: *mut rmd_tile_luma) -> i32;
+    // a tile's variance weighted by its pixels' luminance, the check of settings.adaptive_display_threshold in the C++ mirror: rect i at rect_counts[i], rects
+    // inside the frame (they may overlap or repeat), weights_host RMD_LUMA_WEIGHTS (260) doubles — one per counter of rmd_luma_histogram without not_finite —,
+    // out_host n_rects rmd_tile_weighted; rms is what meets the threshold
+    fn rmd_tile_weighted_error(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                               rect_counts: *const u32, n_rects: u32, weights_host: *const f64, out_host: *mut rmd_tile_weighted) -> i32;
+    // the table that makes rms the displayed error: the squared slope of the tone curve per luminance counter (host only, no context)
+    fn rmd_display_weights(exposure: f64, gamma: f64, display_floor: f64, out_weights: *mut f64) -> i32;
+}
+
+/// rmd_tile_weighted_error's result for one rect (include/raymond_hip.h: rmd_tile_weighted, 40 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+#[allow(non_camel_case_types, dead_code)]
+pub struct rmd_tile_weighted {
+    pub rms: f64,                    // sqrt(mean_weighted_variance)
+    pub mean_weighted_variance: f64,
+    pub mean_luma: f64,
+    pub mean_variance: f64,
+    pub valid: u32,
+    pub invalid: u32,
 }
 
 /// rmd_tile_luma_error's result for one rect (include/raymond_hip.h: rmd_tile_luma, 48 bytes)

@@ -147,6 +147,20 @@ class TileLuma(C.Structure):  # rmd_tile_luma: rmd_tile_luma_error's result for 
     ]
 
 
+LUMA_WEIGHTS = 260  # RMD_LUMA_WEIGHTS: rmd_tile_weighted_error's table, one weight per counter of rmd_luma_histogram without not_finite
+
+
+class TileWeighted(C.Structure):  # rmd_tile_weighted: rmd_tile_weighted_error's result for one rect, 40 bytes
+    _fields_ = [
+        ("rms", C.c_double),
+        ("mean_weighted_variance", C.c_double),
+        ("mean_luma", C.c_double),
+        ("mean_variance", C.c_double),
+        ("valid", C.c_uint32),
+        ("invalid", C.c_uint32),
+    ]
+
+
 ADAPTIVE_MEASURES = ("channel_max", "luma_tile", "luma_pixel")  # Settings.adaptive_measure: rmd_tile_error, rmd_tile_luma_error's tile_rms, its pixel_rms
 
 

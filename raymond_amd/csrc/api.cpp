@@ -1454,4 +1454,31 @@ rmd_status rmd_exposure_from_histogram(const rmd_luma_histogram *h, double perce
 	});
 }
 
+// The squared slope of the library's tone curve per luminance counter, for rmd_tile_weighted_error: host arithmetic only, no context, no device.
+rmd_status rmd_display_weights(double exposure, double gamma, double display_floor, double *out_weights) {
+	return rmd::guarded(nullptr, "rmd_display_weights", [&]() -> rmd_status {
+		const char *name = "rmd_display_weights: ";
+		if (!out_weights) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "null pointer");
+		if (!(exposure > 0.0) || !std::isfinite(exposure)) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "exposure must be finite and > 0");
+		if (!(gamma > 0.0) || !std::isfinite(gamma)) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "gamma must be finite and > 0");
+		if (!(display_floor > 0.0 && display_floor < 1.0)) // (a NaN fails both)
+			return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, std::string(name) + "display_floor must be finite and in (0, 1)");
+		const double inv_g = 1.0 / gamma;
+		const double y_floor = -std::log1p(-std::pow(display_floor, gamma)) / exposure;
+		auto weight = [&](double y) {
+			const double t = -std::expm1(-y * exposure);
+			const double slope = inv_g * std::pow(t, inv_g - 1.0) * exposure * std::exp(-y * exposure);
+			const double w = slope * slope;
+			if (!(w == w)) return 0.0;                                      // inf * 0: a factor has vanished
+			return w > 1.7976931348623157e308 ? 1.7976931348623157e308 : w; // overflow: the largest finite double
+		};
+		// the bin's centre, exact: 2^E (1 + (M + 0.5) / 4); luminances under the one that displays at display_floor take that luminance's slope
+		for (uint32_t i = 0; i < RMD_LUMA_BINS; i++)
+			out_weights[i] = weight(std::max(std::ldexp(1.0 + ((double)(i % 4u) + 0.5) * 0.25, (int)(i / 4u) + rmd::kLumaMinExponent), y_floor));
+		out_weights[rmd::kLumaBelow] = out_weights[rmd::kLumaZero] = out_weights[rmd::kLumaNegative] = weight(y_floor);
+		out_weights[rmd::kLumaAbove] = weight(0x1p32);
+		return RMD_OK;
+	});
+}
+
 } // extern "C"

@@ -1,5 +1,5 @@
-// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error and rmd_tile_error_dual.  Host code only; the
-// kernels are in denoise*.hip, despike.hip and tile_luma.hip.
+// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error and
+// rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, tile_luma.hip and tile_weighted.hip.
 // Every entry point is its argument checks in its own order and then, inside rmd::guarded: the rect checks, the context, one carved scratch block
 // (denoise_host.hpp has the layouts), one upload of the rects, its launcher (launch.hpp) and the wait.
 #define RMD_WITH_HIP 1
@@ -9,6 +9,7 @@
 #include "internal.hpp"
 #include "launch.hpp"
 #include "tile_luma_rule.hpp"
+#include "tile_weighted_rule.hpp"
 
 namespace rmd {
 // Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
@@ -509,6 +510,49 @@ rmd_status rmd_tile_luma_error(rmd_context *ctx, const double *accum_dev, const 
 			rmd::TileLuma *d_out = sc.part<rmd::TileLuma>(rmd::kPartTileErrors);
 			RMD_HIP(ctx, rmd::launch_tile_luma(ctx->stream, in, floor, d_out));
 			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(rmd_tile_luma), hipMemcpyDeviceToHost, ctx->stream));
+		}
+		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
+	});
+}
+
+// rmd_tile_weighted_error (tile_weighted.hip).  Its refusals in the header's order, the context last; the rects follow rmd_tile_error's rule (inside the
+// frame; they may overlap or repeat).  The rects, the counts and the weights go up in ONE copy from a host block laid out like the device's
+rmd_status rmd_tile_weighted_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                   const uint32_t *rect_counts, uint32_t n_rects, const double *weights_host, rmd_tile_weighted *out_host) {
+	static_assert(sizeof(rmd::TileWeighted) == sizeof(rmd_tile_weighted) && sizeof(rmd_tile_weighted) == 40 && offsetof(rmd::TileWeighted, rms) == offsetof(rmd_tile_weighted, rms) &&
+	                  offsetof(rmd::TileWeighted, mean_weighted_variance) == offsetof(rmd_tile_weighted, mean_weighted_variance) &&
+	                  offsetof(rmd::TileWeighted, mean_luma) == offsetof(rmd_tile_weighted, mean_luma) &&
+	                  offsetof(rmd::TileWeighted, mean_variance) == offsetof(rmd_tile_weighted, mean_variance) && offsetof(rmd::TileWeighted, valid) == offsetof(rmd_tile_weighted, valid) &&
+	                  offsetof(rmd::TileWeighted, invalid) == offsetof(rmd_tile_weighted, invalid),
+	              "tile_weighted_rule.hpp's TileWeighted is rmd_tile_weighted");
+	static_assert(rmd::kLumaWeights == RMD_LUMA_WEIGHTS, "tile_weighted_rule.hpp's table is the header's");
+	const std::string name = "rmd_tile_weighted_error: ";
+	return rmd::guarded(ctx, "rmd_tile_weighted_error", [&] {
+		if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_counts || !weights_host || !out_host)))
+			return fail(ctx, kInvalid, name + "bad argument");
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		if (any_overlap({{accum_dev, bytes}, {accum_sq_dev, bytes}})) return fail(ctx, kInvalid, name + "accum_sq_dev must not alias accum_dev");
+		for (uint32_t k = 0; weights_host && k < RMD_LUMA_WEIGHTS; k++)
+			if (!(weights_host[k] >= 0.0) || !std::isfinite(weights_host[k])) return fail(ctx, kInvalid, name + "every weight must be finite and >= 0");
+		for (uint32_t i = 0; i < n_rects; i++)
+			if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
+				return fail(ctx, kInvalid, name + "tile rectangle outside the framebuffer");
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		std::vector<unsigned char> staged; // (read by the copy until finish() has waited)
+		if (n_rects != 0) {
+			DenoiseInput in = single_input(accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_counts, n_rects);
+			size_t upload_bytes = 0;
+			Scratch sc; // (the context's block: kept between calls)
+			if (rmd_status s = sc.carve(ctx, rmd::tile_weighted_scratch_layout(n_rects, &upload_bytes), &ctx->tile_weighted_scratch)) return s;
+			staged.assign(upload_bytes, 0);
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartRects], rects, (size_t)n_rects * sizeof(rmd_tile_rect));
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartCountsA], rect_counts, (size_t)n_rects * sizeof(uint32_t));
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartTable], weights_host, (size_t)RMD_LUMA_WEIGHTS * sizeof(double));
+			RMD_HIP(ctx, hipMemcpyAsync(sc.base, staged.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+			in.rects = sc.part<rmd_tile_rect>(rmd::kPartRects), in.counts_a = sc.part<uint32_t>(rmd::kPartCountsA);
+			rmd::TileWeighted *d_out = sc.part<rmd::TileWeighted>(rmd::kPartTileErrors);
+			RMD_HIP(ctx, rmd::launch_tile_weighted(ctx->stream, in, sc.part<double>(rmd::kPartTable), d_out));
+			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(rmd_tile_weighted), hipMemcpyDeviceToHost, ctx->stream));
 		}
 		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
 	});

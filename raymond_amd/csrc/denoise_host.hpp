@@ -121,6 +121,21 @@ inline ScratchLayout tile_luma_scratch_layout(uint32_t n_rects) {
 	return L;
 }
 
+// rmd_tile_weighted_error's block, in the parts' existing names: kPartRects and kPartCountsA the rects and their counts, kPartTable the call's
+// RMD_LUMA_WEIGHTS weights (doubles), kPartTileErrors the per-rect results (n_rects rmd_tile_weighted, 40 B each).  The first three parts are what the call
+// uploads, in one copy: they lie at the block's start in this order, each padded to 16 bytes; `upload_bytes` is where the results begin
+inline ScratchLayout tile_weighted_scratch_layout(uint32_t n_rects, size_t *upload_bytes = nullptr) {
+	ScratchLayout L;
+	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
+		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
+		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
+	};
+	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, sizeof(uint32_t), n_rects), part(kPartTable, sizeof(double), RMD_LUMA_WEIGHTS);
+	if (upload_bytes) *upload_bytes = L.total;
+	part(kPartTileErrors, sizeof(rmd_tile_weighted), n_rects);
+	return L;
+}
+
 // ---------------------------------------------------------------- the block tables of the region forms
 // rmd_denoise_dual_region: each region rect cut into tiles of the kernel's own shape (tw x th) from the rect's corner, row by row
 inline std::vector<DualBlock> dual_region_table(const rmd_tile_rect *region, uint32_t n_region, uint32_t tw, uint32_t th) {

@@ -223,6 +223,11 @@ hipError_t launch_despike(hipStream_t stream, const DenoiseInput &in, uint32_t r
 // in.counts_a[i], one workgroup per rect; the rects, the counts and `out` are device memory.  Nothing else of `in` is read.  floor is checked by the caller
 struct TileLuma;
 hipError_t launch_tile_luma(hipStream_t stream, const DenoiseInput &in, double floor, TileLuma *out);
+// rmd_tile_weighted_error (tile_weighted.hip): out[i] = rect i's result (tile_weighted_rule.hpp: TileWeighted, rmd_tile_weighted's layout) from in.accum_a /
+// in.accum_sq_a at in.counts_a[i], one workgroup per rect; the rects, the counts, the RMD_LUMA_WEIGHTS `weights` and `out` are device memory.  Nothing else
+// of `in` is read.  The weights are checked by the caller
+struct TileWeighted;
+hipError_t launch_tile_weighted(hipStream_t stream, const DenoiseInput &in, const double *weights, TileWeighted *out);
 hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in, int in_stride, double *out, int out_stride,
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,

@@ -5,6 +5,11 @@
 //                                                                    [--adaptive THRESHOLD [--adaptive-floor F]]   (needs --spi)
 //                                                                    [--adaptive-measure channel_max|luma_tile|luma_pixel]   (what --adaptive compares with
 //                                                                      THRESHOLD: rmd_tile_error, or rmd_tile_luma_error's tile_rms or pixel_rms; not with --denoise-dual)
+//                                                                    [--adaptive-display T [--adaptive-display-exposure E] [--adaptive-display-gamma G]
+//                                                                     [--adaptive-display-floor F] [--adaptive-display-auto-exposure 1]]   (needs --spi; in
+//                                                                      place of --adaptive: a tile stops when rmd_tile_weighted_error's rms under
+//                                                                      rmd_display_weights' table — its RMS error after exposure and gamma, in fractions of
+//                                                                      the display's full scale — is at most T; not with --denoise-dual)
 //                                                                    [--dump-tiles FILE]   (one "left top width height sample_count error" line per finished tile)
 //                                                                    [--tile-size N]   (N x N tiles instead of 32 x 32)
 //                                                                    [--denoise 1 [--denoise-radius R] [--denoise-patch F] [--denoise-k K]
@@ -62,6 +67,13 @@
 //                                         rmd_tile_luma_error made on the host (raymond::tile_luma_error_host, from the header the kernel is built from) over raw
 //                                         W*H*3 f64 sums and sums of squares; rects.txt as for despike; FLOOR is read as a C99 hexadecimal or decimal double;
 //                                         prints per rect "tile_rms pixel_rms mean_luma mean_variance mean_rel_variance valid invalid", doubles as %.17g
+//   raymond_cli tile-weighted-error S.f64 Q.f64 W H rects.txt EXPOSURE GAMMA FLOOR | S.f64 Q.f64 W H rects.txt --weights weights.f64
+//                                         rmd_tile_weighted_error made on the host (raymond::tile_weighted_error_host, from the header the kernel is built from)
+//                                         over raw W*H*3 f64 sums and sums of squares, under rmd_display_weights' table at EXPOSURE, GAMMA and FLOOR (C99
+//                                         hexadecimal or decimal doubles) or under the 260 raw f64 weights of weights.f64; rects.txt as for despike; prints per
+//                                         rect "rms mean_weighted_variance mean_luma mean_variance valid invalid", doubles as their 64 bits in hexadecimal
+//   raymond_cli display-weights EXPOSURE GAMMA FLOOR
+//                                         rmd_display_weights: its 260 weights, one per line, as their 64 bits in hexadecimal
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
 //                                         what a drop-in caller gets: one JSON line with the wall time of render_tiled -> last TileFinished
 //   (render also accepts `project:in.json` as its scene)
@@ -245,6 +257,49 @@ int main(int argc, char **argv) {
 				std::printf("%.17g %.17g %.17g %.17g %.17g %u %u\n", t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid);
 			return 0;
 		}
+		if (argc >= 5 && !std::strcmp(argv[1], "display-weights")) {
+			for (double w : display_weights(std::strtod(argv[2], nullptr), std::strtod(argv[3], nullptr), std::strtod(argv[4], nullptr))) {
+				uint64_t bits;
+				std::memcpy(&bits, &w, sizeof(bits));
+				std::printf("%016llx\n", (unsigned long long)bits);
+			}
+			return 0;
+		}
+		if (argc >= 9 && !std::strcmp(argv[1], "tile-weighted-error")) {
+			const size_t W = (size_t)std::atoll(argv[4]), H = (size_t)std::atoll(argv[5]);
+			std::vector<Vector3> sums(W * H), sums_sq(W * H);
+			for (int i = 0; i < 2; i++) {
+				std::ifstream f(argv[2 + i], std::ios::binary);
+				std::vector<Vector3> &dst = i ? sums_sq : sums;
+				if (!f || !f.read(reinterpret_cast<char *>(dst.data()), (std::streamsize)(dst.size() * sizeof(Vector3))))
+					throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2 + i]);
+			}
+			std::vector<rmd_tile_rect> rects;
+			std::vector<uint32_t> counts;
+			std::ifstream rf(argv[6]);
+			for (rmd_tile_rect r; rf >> r.left >> r.top >> r.width >> r.height;) {
+				uint32_t n = 0;
+				rf >> n;
+				rects.push_back(r), counts.push_back(n);
+			}
+			std::vector<double> weights(RMD_LUMA_WEIGHTS);
+			if (!std::strcmp(argv[7], "--weights")) {
+				std::ifstream f(argv[8], std::ios::binary);
+				if (!f || !f.read(reinterpret_cast<char *>(weights.data()), (std::streamsize)(weights.size() * sizeof(double))))
+					throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[8]);
+			} else {
+				if (argc < 10) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile-weighted-error: EXPOSURE GAMMA FLOOR or --weights FILE");
+				weights = display_weights(std::strtod(argv[7], nullptr), std::strtod(argv[8], nullptr), std::strtod(argv[9], nullptr));
+			}
+			for (const rmd_tile_weighted &t : tile_weighted_error_host(sums, sums_sq, W, H, rects, counts, weights)) {
+				uint64_t bits[4];
+				const double fields[4] = {t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance};
+				std::memcpy(bits, fields, sizeof(bits));
+				std::printf("%016llx %016llx %016llx %016llx %u %u\n", (unsigned long long)bits[0], (unsigned long long)bits[1], (unsigned long long)bits[2],
+				            (unsigned long long)bits[3], t.valid, t.invalid);
+			}
+			return 0;
+		}
 		if (argc >= 6 && !std::strcmp(argv[1], "tiles")) {
 			for (const rmd_tile_rect &t : generate_tiles(std::atoi(argv[2]), std::atoi(argv[3]), {std::atoi(argv[4]), std::atoi(argv[5])}))
 				std::printf("%u %u %u %u\n", t.left, t.top, t.width, t.height);
@@ -320,6 +375,11 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--adaptive")) st.adaptive_threshold = std::atof(argv[i + 1]); // (render_tiled refuses it without --spi)
 				else if (!std::strcmp(argv[i], "--adaptive-floor")) st.adaptive_floor = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--adaptive-measure")) st.adaptive_measure = argv[i + 1]; // (render_tiled checks it)
+				else if (!std::strcmp(argv[i], "--adaptive-display")) st.adaptive_display_threshold = std::atof(argv[i + 1]); // (render_tiled checks them)
+				else if (!std::strcmp(argv[i], "--adaptive-display-exposure")) st.adaptive_display_exposure = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--adaptive-display-gamma")) st.adaptive_display_gamma = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--adaptive-display-floor")) st.adaptive_display_floor = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--adaptive-display-auto-exposure")) st.adaptive_display_auto_exposure = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--dump-tiles")) dump_tiles = argv[i + 1];
 				else if (!std::strcmp(argv[i], "--tile-size")) st.tile_size = {(size_t)std::strtoull(argv[i + 1], nullptr, 10), (size_t)std::strtoull(argv[i + 1], nullptr, 10)};
 				else if (!std::strcmp(argv[i], "--denoise"))st.denoise = std::atoi(argv[i + 1]) != 0;

@@ -5,6 +5,7 @@
 #include "../csrc/despike_rule.hpp"
 #include "../csrc/luma_bins.hpp"
 #include "../csrc/tile_luma_rule.hpp"
+#include "../csrc/tile_weighted_rule.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -432,12 +433,15 @@ struct TileWorker : Worker {
 	// previews (one worker: render_tiled): every batch is then one pass over all live tiles, which all hold the same count
 	const bool preview, preview_filtered, adaptive, moments;
 	const bool luma_measure;  // settings.adaptive_measure is "luma_tile" or "luma_pixel": the check is rmd_tile_luma_error
+	const bool display_measure; // settings.adaptive_display_threshold > 0: the check is rmd_tile_weighted_error under the tone curve's weights
+	const double threshold;     // what a tile's measure has to meet: adaptive_display_threshold with the display measure, else adaptive_threshold
+	std::vector<double> weights; // display_measure: rmd_display_weights' table — made once, or with adaptive_display_auto_exposure by every check
 	const bool despike_check; // settings.despike in an adaptive render (one worker: check_settings): the check reads despiked copies of the sums
 	const size_t step;
 	Frame fb, fb_sq;    // fb_sq: the sums of squares of an adaptive, denoised or despiked render
 	Frame fb_preview;   // settings.preview_denoise: the filtered means of a preview
 	Frame fb_spare, fb_spare_sq; // despike_check: rmd_despike's outputs, which rmd_tile_error reads; fb and fb_sq stay raw
-	std::vector<rmd_tile_rect> converged_rects; // despike_check: the tiles that finished early and the counts they finished with
+	std::vector<rmd_tile_rect> converged_rects; // despike_check, adaptive_display_auto_exposure: the tiles that finished early and the counts they finished with
 	std::vector<uint32_t> converged_counts;
 	std::shared_ptr<BlockPool> pool = BlockPool::shared(); // process-wide: page-locking 50 MB costs about as much as moving them
 	std::vector<rmd_tile_rect> early_rects; // previews: the tiles that finished early and the counts they finished with
@@ -456,7 +460,10 @@ struct TileWorker : Worker {
 
 	TileWorker(TaskHandle::Shared &sh, int device, int me, size_t workers, const Scene &scene, const Settings &st, size_t batch)
 	    : Worker(sh, device, scene, st), me(me), workers(workers), batch(batch), preview(st.preview_every > 0), preview_filtered(preview && st.preview_denoise),
-	      adaptive(st.adaptive_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered || st.despike), luma_measure(st.adaptive_measure != "channel_max"),
+	      adaptive(st.adaptive_threshold > 0.0 || st.adaptive_display_threshold > 0.0), moments(adaptive || st.denoise || preview_filtered || st.despike),
+	      luma_measure(st.adaptive_measure != "channel_max"), display_measure(st.adaptive_display_threshold > 0.0),
+	      threshold(display_measure ? st.adaptive_display_threshold : st.adaptive_threshold),
+	      weights(display_measure ? display_weights(st.adaptive_display_exposure, st.adaptive_display_gamma, st.adaptive_display_floor) : std::vector<double>()),
 	      despike_check(st.despike && adaptive),
 	      step(st.samples_per_iteration ? st.samples_per_iteration : st.sample_count), fb(frame()), fb_sq(frame(moments)), fb_preview(frame(preview_filtered)),
 	      fb_spare(frame(despike_check)), fb_spare_sq(frame(despike_check)) {}
@@ -550,6 +557,9 @@ struct TileWorker : Worker {
 	// tile at or below the threshold is finished at the samples it has
 	// With a luma measure (settings.adaptive_measure): ONE rmd_tile_luma_error over all of them, each rect at its own count; its tile_rms or pixel_rms
 	// decides and stays with the tile as `error`
+	// With the display measure (settings.adaptive_display_threshold): ONE rmd_tile_weighted_error over all of them, each rect at its own count, under
+	// rmd_display_weights' table; with adaptive_display_auto_exposure the table is first made anew from the histogram of the whole frame — the tiles that
+	// finished early at their counts and the batch, which with one worker is every other tile — on the sums the check reads
 	std::vector<bool> converged_tiles(std::vector<Tile> &mine) {
 		std::vector<bool> converged(mine.size(), false);
 		if (!adaptive) return converged;
@@ -567,6 +577,29 @@ struct TileWorker : Worker {
 			      ctx, "rmd_despike");
 			s = fb_spare, s_sq = fb_spare_sq;
 		}
+		if (display_measure && !live.empty()) {
+			if (st.adaptive_display_auto_exposure) {
+				std::vector<rmd_tile_rect> rects(converged_rects);
+				std::vector<uint32_t> counts(converged_counts);
+				for (const Tile &t : mine) rects.push_back(rect_of(t)), counts.push_back((uint32_t)t.sample_count);
+				rmd_luma_histogram hist;
+				check(rmd_luminance_histogram_tiles(ctx, s, nullptr, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), &hist), ctx,
+				      "rmd_luminance_histogram_tiles");
+				double exposure = 1.0;
+				check(rmd_exposure_from_histogram(&hist, st.auto_exposure_percentile, st.auto_exposure_target, &exposure), nullptr, "rmd_exposure_from_histogram");
+				weights = display_weights(exposure, st.adaptive_display_gamma, st.adaptive_display_floor);
+			}
+			std::vector<size_t> which;
+			std::vector<uint32_t> counts;
+			for (size_t i = 0; i < mine.size(); i++)
+				if (mine[i].sample_count < st.sample_count) which.push_back(i), counts.push_back((uint32_t)mine[i].sample_count);
+			const std::vector<rmd_tile_rect> rects = rects_of(mine, which);
+			std::vector<rmd_tile_weighted> weighted(rects.size());
+			check(rmd_tile_weighted_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), weights.data(), weighted.data()), ctx,
+			      "rmd_tile_weighted_error");
+			for (size_t k = 0; k < weighted.size(); k++) mine[which[k]].error = weighted[k].rms, converged[which[k]] = weighted[k].rms <= threshold;
+			live.clear(); // (no rmd_tile_error call below)
+		}
 		if (luma_measure) {
 			std::vector<size_t> which;
 			std::vector<uint32_t> counts;
@@ -579,7 +612,7 @@ struct TileWorker : Worker {
 				      "rmd_tile_luma_error");
 			for (size_t k = 0; k < luma.size(); k++) {
 				const double e = st.adaptive_measure == "luma_tile" ? luma[k].tile_rms : luma[k].pixel_rms;
-				mine[which[k]].error = e, converged[which[k]] = e <= st.adaptive_threshold;
+				mine[which[k]].error = e, converged[which[k]] = e <= threshold;
 			}
 			live.clear(); // (no rmd_tile_error call below)
 		}
@@ -588,9 +621,9 @@ struct TileWorker : Worker {
 			std::vector<double> err(rects.size());
 			check(rmd_tile_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, (uint32_t)grp.first, st.adaptive_floor, rects.data(), (uint32_t)rects.size(), err.data()), ctx,
 			      "rmd_tile_error");
-			for (size_t k = 0; k < err.size(); k++) converged[grp.second[k]] = err[k] <= st.adaptive_threshold;
+			for (size_t k = 0; k < err.size(); k++) converged[grp.second[k]] = err[k] <= threshold;
 		}
-		if (despike_check)
+		if (despike_check || (display_measure && st.adaptive_display_auto_exposure))
 			for (size_t i = 0; i < mine.size(); i++)
 				if (converged[i]) converged_rects.push_back(rect_of(mine[i])), converged_counts.push_back((uint32_t)mine[i].sample_count);
 		return converged;
@@ -914,6 +947,15 @@ std::string check_settings(const Settings &st) {
 	if (!positive(st.adaptive_floor)) return "adaptive_floor must be finite and > 0";
 	if (st.adaptive_measure != "channel_max" && st.adaptive_measure != "luma_tile" && st.adaptive_measure != "luma_pixel")
 		return "adaptive_measure must be \"channel_max\", \"luma_tile\" or \"luma_pixel\"";
+	if (!(st.adaptive_display_threshold >= 0.0) || !std::isfinite(st.adaptive_display_threshold)) return "adaptive_display_threshold must be finite and >= 0 (0 = off)";
+	if (st.adaptive_display_threshold > 0.0 && st.samples_per_iteration == 0)
+		return "adaptive_display_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)";
+	if (st.adaptive_display_threshold > 0.0 && st.adaptive_threshold > 0.0) return "adaptive_display_threshold and adaptive_threshold are mutually exclusive";
+	if (st.adaptive_display_threshold > 0.0 && st.adaptive_measure != "channel_max")
+		return "adaptive_display_threshold cannot be combined with adaptive_measure: the display rule is a measure of its own";
+	if (!positive(st.adaptive_display_exposure)) return "adaptive_display_exposure must be finite and > 0";
+	if (!positive(st.adaptive_display_gamma)) return "adaptive_display_gamma must be finite and > 0";
+	if (!(st.adaptive_display_floor > 0.0 && st.adaptive_display_floor < 1.0)) return "adaptive_display_floor must be finite and in (0, 1)";
 	if (st.denoise_dual && !st.denoise) return "denoise_dual needs denoise";
 	if (st.denoise_dual && st.samples_per_iteration == 0) return "denoise_dual needs samples_per_iteration > 0 (the passes alternate between the two half buffers)";
 	if (st.denoise_dual && st.denoise_features) return "denoise_dual cannot be combined with denoise_features: rmd_denoise_dual has no feature weight";
@@ -927,6 +969,9 @@ std::string check_settings(const Settings &st) {
 	if (st.adaptive_denoised_threshold > 0.0 && !st.denoise_dual) return "adaptive_denoised_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)";
 	if (st.adaptive_denoised_threshold > 0.0 && st.adaptive_threshold > 0.0) return "adaptive_denoised_threshold and adaptive_threshold are mutually exclusive";
 	if (st.denoise_dual && st.adaptive_measure != "channel_max") return "adaptive_measure cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual";
+	if (st.denoise_dual && st.adaptive_display_threshold > 0.0) return "adaptive_display_threshold cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual";
+	if (st.adaptive_display_threshold > 0.0 && st.adaptive_display_auto_exposure && st.worker_count > 1)
+		return "adaptive_display_auto_exposure renders on one device: every check histograms the whole frame";
 	if (st.denoise_dual && st.worker_count > 1) return "denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own";
 	if (!(st.denoise_feature_slope >= 0.0) || !std::isfinite(st.denoise_feature_slope)) return "denoise_feature_slope must be finite and >= 0 (0 = off)";
 	if (st.denoise_feature_slope > 0.0 && (st.denoise_atrous || st.denoise_dual_atrous))
@@ -944,6 +989,8 @@ std::string check_settings(const Settings &st) {
 	if (st.despike && st.denoise_dual) return "despike cannot be combined with denoise_dual: the halves are not yet despiked";
 	if (st.despike && st.adaptive_threshold > 0.0 && st.worker_count > 1)
 		return "despike with adaptive_threshold renders on one device: the window crosses the tiles that several devices would own";
+	if (st.despike && st.adaptive_display_threshold > 0.0 && st.worker_count > 1)
+		return "despike with adaptive_display_threshold renders on one device: the window crosses the tiles that several devices would own";
 	return "";
 }
 } // namespace
@@ -1179,6 +1226,27 @@ std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums
 		out[j] = rmd_tile_luma{t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid};
 	}
 	return out;
+}
+
+std::vector<rmd_tile_weighted> tile_weighted_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
+                                                        const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, const std::vector<double> &weights) {
+	if (sums.size() != width * height || sums_sq.size() != width * height || rects.size() != counts.size() || weights.size() != RMD_LUMA_WEIGHTS)
+		throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_weighted_error_host: bad argument");
+	std::vector<rmd_tile_weighted> out(rects.size());
+	const double *S = sums.empty() ? nullptr : sums[0].data(), *Q = sums_sq.empty() ? nullptr : sums_sq[0].data();
+	for (size_t j = 0; j < rects.size(); j++) {
+		const rmd_tile_rect &r = rects[j];
+		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_weighted_error_host: tile rectangle outside the framebuffer");
+		const rmd::TileWeighted t = rmd::tile_weighted_rect_host(S, Q, (uint32_t)width, r.left, r.top, r.width, r.height, counts[j], weights.data());
+		out[j] = rmd_tile_weighted{t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance, t.valid, t.invalid};
+	}
+	return out;
+}
+
+std::vector<double> display_weights(double exposure, double gamma, double display_floor) {
+	std::vector<double> weights(RMD_LUMA_WEIGHTS);
+	check(rmd_display_weights(exposure, gamma, display_floor, weights.data()), nullptr, "rmd_display_weights");
+	return weights;
 }
 
 std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device, std::vector<double> *tile_errors, const Scene *scene) {

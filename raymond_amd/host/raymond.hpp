@@ -133,6 +133,18 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// relative luminance errors), both at `adaptive_floor`; a finished tile's `error` is then that value.  The three thresholds are not comparable numbers.
 	// render_tiled throws for any other value whether or not adaptive sampling is on, and for a luma measure with denoise_dual, whose check is its own.
 	std::string adaptive_measure = "channel_max";
+	// Adaptive sampling by the DISPLAYED error (an extension; 0 = off; in place of adaptive_threshold, needs samples_per_iteration > 0): the check is one
+	// rmd_tile_weighted_error call over the live tiles under rmd_display_weights' table — every pixel's luminance variance times the squared slope of the tone
+	// curve (1 - exp(-y exposure))^(1 / gamma) at its luminance — and a tile whose rms is at most the threshold is finished at the samples it has; its
+	// `error` is that rms.  The threshold is a fraction of the display's full scale: 1 / 255 is one 8-bit level.  adaptive_display_floor: luminances that
+	// display below it take the slope at it.  adaptive_display_auto_exposure: every check first takes the exposure its own histogram of the whole frame asks
+	// for (auto_exposure_percentile, auto_exposure_target) in place of adaptive_display_exposure; one device.  render_tiled throws with adaptive_threshold,
+	// with an adaptive_measure other than "channel_max" and with denoise_dual.
+	double adaptive_display_threshold = 0.0;
+	double adaptive_display_exposure = 1.0;
+	double adaptive_display_gamma = 2.2;
+	double adaptive_display_floor = 1.0 / 255.0;
+	bool adaptive_display_auto_exposure = false;
 	// Denoising (an extension; false = off): await() returns the assembled frame filtered by rmd_denoise (raymond_hip.h) with these parameters; the
 	// passes then render with second moments and TileFinished tiles carry them in `data_sq`.  render_tiled throws raymond::Error for values
 	// rmd_denoise refuses (radius <= 12, patch <= 4, k finite and > 0, alpha finite and >= 0).
@@ -258,7 +270,8 @@ struct Tile { // core/src/tile.rs:7-14
 	TileData data_a, data_sq_a, data_b, data_sq_b;
 	size_t count_a = 0, count_b = 0;
 	// dual-buffer adaptive renders: the tile's rmd_tile_error_dual when it was last checked; adaptive renders by a luma measure (settings.adaptive_measure):
-	// its rmd_tile_luma_error tile_rms or pixel_rms, whichever decides; -1: never
+	// its rmd_tile_luma_error tile_rms or pixel_rms, whichever decides; adaptive renders by the displayed error (settings.adaptive_display_threshold): its
+	// rmd_tile_weighted_error rms; -1: never
 	double error = -1.0;
 };
 // An extension (settings.preview_every): the frame after pass `pass_index` (counted from 1), row-major RGB bytes; sample_count: the samples per pixel
@@ -356,6 +369,13 @@ std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::
 // raymond_cli tile-luma-error runs, and what holds the header to the numpy restatement without a GPU
 std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
                                                 const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double floor);
+// rmd_tile_weighted_error on the host, from the header the kernel is built from (raymond_amd/csrc/tile_weighted_rule.hpp: 256 emulated lanes and the kernel's
+// combine): rect i of the width * height sums and sums of squares at counts[i], under `weights` (RMD_LUMA_WEIGHTS entries).  No argument is checked beyond
+// the sizes; rects are inside the frame.  What raymond_cli tile-weighted-error runs, and what holds the header to the numpy restatement without a GPU
+std::vector<rmd_tile_weighted> tile_weighted_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
+                                                        const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, const std::vector<double> &weights);
+// rmd_display_weights: the RMD_LUMA_WEIGHTS weights of the displayed error at an exposure, a gamma and a display floor; throws for arguments it refuses
+std::vector<double> display_weights(double exposure, double gamma, double display_floor);
 // await() with settings.despike alone: the finished tiles' sums and sums of squares assembled, despiked on `device` (rmd_despike) and divided by each
 // tile's count
 std::vector<Vector3> despike_tiles(const std::vector<Tile> &tiles, const Settings &settings, int device);

@@ -2,7 +2,7 @@
 
 Bottom up:
   * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, despike, the denoise family (every rmd_denoise* call is laid out
+  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, tile_weighted_error, display_weights, despike, the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -296,6 +296,47 @@ def tile_luma_error_arrays(ctx, sums, sums_sq, tiles, counts, floor):
     with contextlib.ExitStack() as stack:
         s, q = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq))
         return tile_luma_error(ctx, s, q, tiles, counts, floor)
+
+
+TILE_WEIGHTED_DTYPE = np.dtype([("rms", "<f8"), ("mean_weighted_variance", "<f8"), ("mean_luma", "<f8"), ("mean_variance", "<f8"), ("valid", "<u4"),
+                                ("invalid", "<u4")])  # rmd_tile_weighted, field for field
+assert TILE_WEIGHTED_DTYPE.itemsize == C.sizeof(abi.TileWeighted)
+
+
+def _weights(weights):
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    if weights.shape != (abi.LUMA_WEIGHTS,):
+        raise ValueError("a weight table has %d entries" % abi.LUMA_WEIGHTS)
+    return weights
+
+
+def tile_weighted_error(ctx, framebuffer, framebuffer_sq, tiles, counts, weights):
+    """rmd_tile_weighted_error: per tile, at its own sample count, the variance of its pixels' luminance weighted by `weights` — abi.LUMA_WEIGHTS doubles,
+    one per counter of the luminance histogram (256 bins, below, above, zero, negative); a pixel takes the entry its luminance's bits name — as a numpy
+    structured array with rmd_tile_weighted's fields: rms (what an adaptive check compares with its threshold), mean_weighted_variance, mean_luma,
+    mean_variance and the valid / invalid pixel counts.  display_weights() makes the table of the displayed error.  Tiles may overlap or repeat."""
+    tiles = list(tiles)
+    (counts,) = _counts(tiles, counts)
+    weights = _weights(weights)
+    out = np.zeros(max(1, len(tiles)), dtype=TILE_WEIGHTED_DTYPE)
+    ctx.check(ctx.L.rmd_tile_weighted_error(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(tiles), _u32(counts),
+                                            len(tiles), weights.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(abi.TileWeighted))))
+    return out[: len(tiles)]
+
+
+def tile_weighted_error_arrays(ctx, sums, sums_sq, tiles, counts, weights):
+    """tile_weighted_error() for host arrays: (H, W, 3) sums and sums of squares in, the structured array out."""
+    with contextlib.ExitStack() as stack:
+        s, q = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq))
+        return tile_weighted_error(ctx, s, q, tiles, counts, weights)
+
+
+def display_weights(exposure=1.0, gamma=2.2, display_floor=1.0 / 255.0):
+    """rmd_display_weights: the table that makes tile_weighted_error measure the displayed error — per luminance counter the squared slope of the tone curve
+    (1 - exp(-y exposure))^(1 / gamma), capped at the luminance that displays at `display_floor` (a host function) -> abi.LUMA_WEIGHTS float64."""
+    out = np.zeros(abi.LUMA_WEIGHTS, dtype=np.float64)
+    _lib.check(_lib.load().rmd_display_weights(float(exposure), float(gamma), float(display_floor), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
 
 
 _GUIDED = {"rmd_denoise": "rmd_denoise_guided", "rmd_denoise_dual": "rmd_denoise_dual_guided"}  # the stems whose name says that the features are there
@@ -874,7 +915,12 @@ class _TiledLoop:
         st = self.st = settings
         cam = st.camera_settings
         self.W, self.H = cam.backbuffer_width, cam.backbuffer_height
-        self.adaptive = st.adaptive_threshold > 0.0
+        self.display = st.adaptive_display_threshold > 0.0  # the check is rmd_tile_weighted_error under the tone curve's weights
+        self.adaptive = st.adaptive_threshold > 0.0 or self.display
+        self.threshold = st.adaptive_display_threshold if self.display else st.adaptive_threshold  # what a tile's measure has to meet
+        # with a fixed exposure the weights are made once; with adaptive_display_auto_exposure every check makes its own (check_weights)
+        self.weights = display_weights(st.adaptive_display_exposure, st.adaptive_display_gamma, st.adaptive_display_floor) if self.display else None
+        self.despiked_at = None  # the pass whose despiked sums the spare buffers hold
         self.preview_filtered = st.preview_every > 0 and st.preview_denoise
         moments = self.adaptive or st.denoise or self.preview_filtered or st.despike
         self.with_sq = st.denoise or st.despike  # the finished tiles carry their sums of squares: await_() reads them
@@ -899,17 +945,40 @@ class _TiledLoop:
         self.done += n
         self.passes += 1
 
+    def check_buffers(self, w):
+        """The sums this pass's check reads on `w`: its own, or with despike the despiked sums of all its tiles at their counts, made once a pass."""
+        if self.spare is None:
+            return w.fb, w.fb_sq
+        if self.despiked_at != self.passes:
+            rects, counts = w.whole_frame(self.done)
+            despike(w.ctx, w.fb, w.fb_sq, rects, counts, out=self.spare, want_replaced=False, **self.st.despike_keywords())
+            self.despiked_at = self.passes
+        return self.spare
+
+    def check_weights(self):
+        """adaptive_display_auto_exposure: before a check, every device histograms its whole frame at its tiles' own counts — the sums the check reads —,
+        the histograms are added, and the weights are the tone curve's at the exposure the sum asks for."""
+        st = self.st
+        if not (self.display and st.adaptive_display_auto_exposure and any(w.live for w in self.workers)):
+            return
+        hist = LumaHistogram()
+        for w in self.workers:
+            rects, counts = w.whole_frame(self.done)
+            if rects:
+                hist = add_histograms(hist, luminance_histogram(w.ctx, self.check_buffers(w)[0], rects, counts))
+        exposure = exposure_from_histogram(hist, st.auto_exposure_percentile, st.auto_exposure_target)
+        self.weights = display_weights(exposure, st.adaptive_display_gamma, st.adaptive_display_floor)
+
     def adaptive_check(self, w):
-        """The settings' adaptive measure of `w`'s live tiles (None each without adaptive_threshold): rmd_tile_error, or with a luma measure one
-        rmd_tile_luma_error call's tile_rms or pixel_rms; with despike, on the despiked sums of all its tiles at their counts."""
+        """The settings' adaptive measure of `w`'s live tiles (None each without a threshold): rmd_tile_error, or with a luma measure one
+        rmd_tile_luma_error call's tile_rms or pixel_rms, or with adaptive_display_threshold one rmd_tile_weighted_error call's rms under the tone curve's
+        weights; with despike, on the despiked sums of all its tiles at their counts."""
         st = self.st
         if not (self.adaptive and w.live):
             return [None] * len(w.live)
-        fb, fb_sq = w.fb, w.fb_sq
-        if self.spare is not None:
-            rects, counts = w.whole_frame(self.done)
-            despike(w.ctx, fb, fb_sq, rects, counts, out=self.spare, want_replaced=False, **st.despike_keywords())
-            fb, fb_sq = self.spare
+        fb, fb_sq = self.check_buffers(w)
+        if self.display:
+            return tile_weighted_error(w.ctx, fb, fb_sq, w.live, [self.done] * len(w.live), self.weights)["rms"]
         if st.adaptive_measure != "channel_max":
             luma = tile_luma_error(w.ctx, fb, fb_sq, w.live, [self.done] * len(w.live), st.adaptive_floor)
             return luma["tile_rms" if st.adaptive_measure == "luma_tile" else "pixel_rms"]
@@ -925,7 +994,7 @@ class _TiledLoop:
         """After a pass that leaves the render unfinished: `w`'s converged tiles finish at the samples they have, the others are sent as TileProgressed —
         from one download of the whole frame, or with progress_tiles off from the converged tiles' pixels alone and without a message for the rest."""
         st, done = self.st, self.done
-        converged = [self.adaptive and e <= st.adaptive_threshold for e in errors]
+        converged = [self.adaptive and e <= self.threshold for e in errors]
         conv = [r for r, c in zip(w.live, converged) if c]
         if not st.progress_tiles:
             data = w.fb.download_tiles(conv) if conv else []
@@ -973,6 +1042,7 @@ class _TiledLoop:
         while self.done < st.sample_count:
             self.render_pass(min(step, st.sample_count - self.done))
             if self.done < st.sample_count and st.samples_per_iteration:
+                self.check_weights()
                 for w in self.workers:
                     self.snapshots(w, self.adaptive_check(w))
                 if st.preview_every and self.passes % st.preview_every == 0 and any(w.live for w in self.workers):  # (no live tile: the render is finished)
@@ -988,6 +1058,9 @@ def render_tiled(scene, settings, devices=(0,)):
     after each pass that leaves them below sample_count a tile whose rmd_tile_error is at most the threshold is sent as TileFinished at its
     current sample count and takes no further passes; the others are sent as TileProgressed and go on.  With settings.adaptive_measure "luma_tile" or
     "luma_pixel" the check is one rmd_tile_luma_error call over the live tiles instead, and its tile_rms or pixel_rms is what meets the threshold.
+    With settings.adaptive_display_threshold > 0 (instead of adaptive_threshold) the check is one rmd_tile_weighted_error call over the live tiles under
+    rmd_display_weights' table — the tile's RMS error after exposure and gamma, in fractions of the display's full scale — at adaptive_display_exposure, or
+    with adaptive_display_auto_exposure at the exposure every check's own histogram of the whole frame asks for (several devices' histograms are added).
 
     Denoised (settings.denoise, an extension): the passes render with second moments, every TileFinished tile carries them as `data_sq`, and
     TaskHandle.await_() denoises the assembled frame on the first of `devices`.

@@ -251,7 +251,8 @@ class Settings:
                  preview_exposure=1.0, preview_gamma=2.2, preview_denoise=False, progress_tiles=True, preview_auto_exposure=False,
                  auto_exposure_percentile=0.99, auto_exposure_target=0.8, denoise_feature_slope=0.0,
                  denoise_atrous_slope=0.0, despike=False, despike_radius=2, despike_rank=2, despike_k=6.0, despike_ratio=2.0, despike_floor=0.0,
-                 adaptive_measure="channel_max"):
+                 adaptive_measure="channel_max", adaptive_display_threshold=0.0, adaptive_display_exposure=1.0, adaptive_display_gamma=2.2,
+                 adaptive_display_floor=1.0 / 255.0, adaptive_display_auto_exposure=False):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -276,6 +277,18 @@ class Settings:
         # ("luma_pixel": the RMS of the pixels' relative luminance errors), both with `adaptive_floor` as the floor.  The three thresholds are not comparable
         # numbers.  Checked whether or not adaptive sampling is on; no effect on the dual loop, and refused with denoise_dual.
         self.adaptive_measure = adaptive_measure
+        # Adaptive sampling by the DISPLAYED error (an extension; 0 = off; in place of adaptive_threshold, needs samples_per_iteration > 0): the check is one
+        # rmd_tile_weighted_error call over the live tiles under rmd_display_weights' table — every pixel's luminance variance times the squared slope of the
+        # tone curve (1 - exp(-y exposure))^(1 / gamma) at its luminance — and a tile whose rms is at most the threshold is finished at the samples it has.
+        # The threshold is a fraction of the display's full scale: 1 / 255 is one 8-bit level.  adaptive_display_floor: luminances that display below it take
+        # the slope at it (the cap that keeps the weight finite).  adaptive_display_auto_exposure: every check first takes the exposure its own histogram of
+        # the whole frame asks for (auto_exposure_percentile, auto_exposure_target) in place of adaptive_display_exposure.  Refused with adaptive_threshold,
+        # with an adaptive_measure other than "channel_max" and with denoise_dual.
+        self.adaptive_display_threshold = float(adaptive_display_threshold)
+        self.adaptive_display_exposure = float(adaptive_display_exposure)
+        self.adaptive_display_gamma = float(adaptive_display_gamma)
+        self.adaptive_display_floor = float(adaptive_display_floor)
+        self.adaptive_display_auto_exposure = bool(adaptive_display_auto_exposure)
         self.check_adaptive()
         # Denoising (an extension; False = off): TaskHandle.await_() returns the assembled frame filtered by rmd_denoise (raymond_hip.h) with
         # these parameters; render_tiled then renders with second moments.
@@ -389,6 +402,8 @@ class Settings:
             raise ValueError("despike cannot be combined with denoise_dual: the halves are not yet despiked")
         if self.despike and self.adaptive_threshold > 0.0 and n_devices != 1:
             raise ValueError("despike with adaptive_threshold renders on one device: the window crosses the tiles that several devices would own")
+        if self.despike and self.adaptive_display_threshold > 0.0 and n_devices != 1:
+            raise ValueError("despike with adaptive_display_threshold renders on one device: the window crosses the tiles that several devices would own")
 
     def select_candidates(self):
         """The candidates of denoise_dual_select, as render.denoise_dual_select takes them: the unguided filter at denoise_k, and the guided one at k = 1.0
@@ -427,6 +442,20 @@ class Settings:
             raise ValueError("adaptive_floor must be finite and > 0")
         if not (isinstance(self.adaptive_measure, str) and self.adaptive_measure in abi.ADAPTIVE_MEASURES):
             raise ValueError('adaptive_measure must be "channel_max", "luma_tile" or "luma_pixel"')
+        if not (self.adaptive_display_threshold >= 0.0 and np.isfinite(self.adaptive_display_threshold)):
+            raise ValueError("adaptive_display_threshold must be finite and >= 0 (0 = off)")
+        if self.adaptive_display_threshold > 0.0 and self.samples_per_iteration == 0:
+            raise ValueError("adaptive_display_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)")
+        if self.adaptive_display_threshold > 0.0 and self.adaptive_threshold > 0.0:
+            raise ValueError("adaptive_display_threshold and adaptive_threshold are mutually exclusive")
+        if self.adaptive_display_threshold > 0.0 and self.adaptive_measure != "channel_max":
+            raise ValueError("adaptive_display_threshold cannot be combined with adaptive_measure: the display rule is a measure of its own")
+        if not (self.adaptive_display_exposure > 0.0 and np.isfinite(self.adaptive_display_exposure)):
+            raise ValueError("adaptive_display_exposure must be finite and > 0")
+        if not (self.adaptive_display_gamma > 0.0 and np.isfinite(self.adaptive_display_gamma)):
+            raise ValueError("adaptive_display_gamma must be finite and > 0")
+        if not 0.0 < self.adaptive_display_floor < 1.0:
+            raise ValueError("adaptive_display_floor must be finite and in (0, 1)")
 
     def check_denoise(self):
         """Raises ValueError for denoise settings rmd_denoise / rmd_denoise_guided refuse (checked whether or not denoise is on)."""
@@ -491,6 +520,8 @@ class Settings:
             raise ValueError("adaptive_min_samples must be an integer >= 0")
         if self.denoise_dual and self.adaptive_measure != "channel_max":
             raise ValueError("adaptive_measure cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual")
+        if self.denoise_dual and self.adaptive_display_threshold > 0.0:
+            raise ValueError("adaptive_display_threshold cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual")
 
     def check_preview(self, n_devices=1):
         """Raises ValueError for preview settings render_tiled cannot follow on `n_devices` devices."""

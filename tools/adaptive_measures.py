@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""DESIGN.md section 10's table again, for the three adaptive measures, and what rmd_tile_luma_error costs:
+"""DESIGN.md section 10's table again, for the adaptive measures, and what rmd_tile_luma_error and rmd_tile_weighted_error cost:
 
-    python tools/adaptive_measures.py table [--scene spheres|mesh] [--out profiles/r24_tile_luma/table_spheres.json]
-    python tools/adaptive_measures.py time  [--runs 15] [--out profiles/r24_tile_luma/call_time.json]
+    python tools/adaptive_measures.py table [--scene spheres|mesh] [--out profiles/r25_tile_weighted/table_spheres.json]
+    python tools/adaptive_measures.py time  [--runs 15] [--out profiles/r25_tile_weighted/call_time.json]
 
 table: the scene at 1920x1080, up to 256 spp in passes of 16, 2,040 tiles of 32 x 32; RMSE against a 2,048 spp frame of another seed.  ONE progressive
 render is made, every tile live to the end.  After every pass the three measures of every tile are taken (rmd_tile_error, and rmd_tile_luma_error's
@@ -13,9 +13,13 @@ measure's own values that bring the mean spp to about 245, 230, 215, 200, 180 an
 tiles stopped early, mean spp, RMSE, and the RMSE of a uniform frame rendered at the same (rounded) mean spp.  One point per measure is then rendered
 for real through render_tiled with Settings.adaptive_measure and must stop the same tiles at the same counts and give the frame's bytes.  A fourth
 measure that is no setting is replayed beside them from the same records: sqrt(mean_variance), the tile's absolute RMS standard error of luminance.
+A fifth, "display", is Settings.adaptive_display_threshold's: rmd_tile_weighted_error's rms under rmd_display_weights' table at exposure 1, gamma 2.2 and
+floor 1 / 255 — the tile's RMS error after the tone curve; its loop check goes through that setting.  Every cell carries two errors: the RMSE in linear
+radiance, and the RMSE in display space — the frame's and the reference's pixels through D(x) = (1 - exp(-x))^(1 / 2.2) per channel (numpy; negative
+values as 0) — each beside the uniform frame's.
 
 time: 2,040 tiles at one count on a 16 spp frame; rmd_tile_luma_error and rmd_tile_error on the same list, alternated, HIP events around the whole
-synchronous call, medians of `runs` after a warm-up, min - max."""
+synchronous call, medians of `runs` after a warm-up, min - max; rmd_tile_weighted_error under the same display table is alternated with them on the same list."""
 import argparse
 import ctypes as C
 import json
@@ -31,7 +35,23 @@ TARGETS = (245, 230, 215, 200, 180, 160)
 MEASURES = ("channel_max", "luma_tile", "luma_pixel")
 # ... and one that is no setting, read off the same records: sqrt(mean_variance), the tile's ABSOLUTE RMS standard error of luminance — what an RMSE in linear
 # radiance is made of.  It separates "relative" from everything else the three have in common
-REPLAYED = MEASURES + ("luma_absolute",)
+REPLAYED = MEASURES + ("luma_absolute", "display")
+DISPLAY = dict(exposure=1.0, gamma=2.2, display_floor=1.0 / 255.0)  # the tone curve the "display" measure is replayed at
+
+
+def displayed(x):
+    """The library's tone curve per channel at DISPLAY's exposure and gamma, before quantisation; negative values display as 0."""
+    import numpy as np
+
+    with np.errstate(invalid="ignore"):
+        return (-np.expm1(-np.maximum(x, 0.0) * DISPLAY["exposure"])) ** (1.0 / DISPLAY["gamma"])
+
+
+def rmse_display(a, b):
+    import numpy as np
+
+    both = np.isfinite(a) & np.isfinite(b)
+    return float(np.sqrt(np.mean((displayed(a[both]) - displayed(b[both])) ** 2)))
 
 
 def rmse(a, b):
@@ -56,7 +76,8 @@ def table(a):
     checks = list(range(PASS, MAX_SPP, PASS))  # the counts a check sees: 16 .. 240
     measures = {m: np.zeros((len(checks), n_tiles)) for m in REPLAYED}
     snapshots = []  # the sums after every pass, float64 (H, W, 3)
-    result = {"scene": a.scene, "width": W, "height": H, "bounces": BOUNCES, "max_spp": MAX_SPP, "pass": PASS, "reference_spp": REF_SPP, "tiles": n_tiles,
+    weights = render.display_weights(**DISPLAY)
+    result = {"display": DISPLAY, "scene": a.scene, "width": W, "height": H, "bounces": BOUNCES, "max_spp": MAX_SPP, "pass": PASS, "reference_spp": REF_SPP, "tiles": n_tiles,
               "adaptive_floor": floor, "library": os.path.relpath(lib.LIB_PATH, ROOT)}
     t0 = time.perf_counter()
     with render.Context(0) as ctx, render.DeviceScene(ctx, scene) as ds, render.Framebuffer(ctx, W, H) as fb, render.Framebuffer(ctx, W, H) as fb_sq:
@@ -68,7 +89,8 @@ def table(a):
         def uniform(spp):
             fb.zero()
             render.render_tiles(ctx, ds, cam, st, tiles, fb, 0, spp)
-            return rmse(fb.download() / float(spp), reference)
+            img = fb.download() / float(spp)
+            return rmse(img, reference), rmse_display(img, reference)
 
         fb.zero()
         for k, done in enumerate(range(PASS, MAX_SPP + 1, PASS)):
@@ -79,8 +101,10 @@ def table(a):
                 luma = render.tile_luma_error(ctx, fb, fb_sq, tiles, [done] * n_tiles, floor)
                 measures["luma_tile"][k], measures["luma_pixel"][k] = luma["tile_rms"], luma["pixel_rms"]
                 measures["luma_absolute"][k] = np.where(luma["invalid"] == 0, np.sqrt(luma["mean_variance"]), np.inf)
+                measures["display"][k] = render.tile_weighted_error(ctx, fb, fb_sq, tiles, [done] * n_tiles, weights)["rms"]
         print("progressive render recorded, %.1f s" % (time.perf_counter() - t0), flush=True)
         result["uniform_256_rmse"] = rmse(snapshots[-1] / float(MAX_SPP), reference)
+        result["uniform_256_display_rmse"] = rmse_display(snapshots[-1] / float(MAX_SPP), reference)
         result["median_at_16_spp"] = {m: float(np.median(measures[m][0])) for m in REPLAYED}
         result["median_at_240_spp"] = {m: float(np.median(measures[m][-1])) for m in REPLAYED}
         result["pixels_not_finite_at_256_spp"] = int((~np.isfinite(snapshots[-1])).any(axis=2).sum())
@@ -116,20 +140,25 @@ def table(a):
                 spp_u = int(round(mean_spp))
                 if spp_u not in uniform_cache:
                     uniform_cache[spp_u] = uniform(spp_u)
+                frame = frame_of(counts)
                 row = {"target_spp": target, "threshold": threshold, "tiles_stopped_early": int((counts < MAX_SPP).sum()), "mean_spp": mean_spp,
-                       "rmse": rmse(frame_of(counts), reference), "uniform_spp": spp_u, "uniform_rmse": uniform_cache[spp_u]}
+                       "rmse": rmse(frame, reference), "uniform_spp": spp_u, "uniform_rmse": uniform_cache[spp_u][0],
+                       "display_rmse": rmse_display(frame, reference), "uniform_display_rmse": uniform_cache[spp_u][1]}
                 row["rmse_over_uniform"] = row["rmse"] / row["uniform_rmse"]
+                row["display_rmse_over_uniform"] = row["display_rmse"] / row["uniform_display_rmse"]
                 rows[m].append(row)
-                print("%-13s threshold %-12.6g stopped %4d  mean spp %6.1f  rmse %.6f  uniform at %3d spp %.6f  ratio %.4f" % (
-                    m, threshold, row["tiles_stopped_early"], mean_spp, row["rmse"], spp_u, row["uniform_rmse"], row["rmse_over_uniform"]), flush=True)
+                print("%-13s threshold %-12.6g stopped %4d  mean spp %6.1f  rmse %.6f  uniform at %3d spp %.6f  ratio %.4f  display rmse %.6f  uniform %.6f  ratio %.4f" % (
+                    m, threshold, row["tiles_stopped_early"], mean_spp, row["rmse"], spp_u, row["uniform_rmse"], row["rmse_over_uniform"], row["display_rmse"],
+                    row["uniform_display_rmse"], row["display_rmse_over_uniform"]), flush=True)
         result["rows"] = rows
         print("table made, %.1f s" % (time.perf_counter() - t0), flush=True)
     # one point per measure through the loop itself: the same tiles at the same counts, the same bytes
     result["loop_check"] = {}
-    for m in MEASURES:
+    for m in MEASURES + ("display",):
         row = rows[m][2]
-        loop_st = Settings(cam, sample_count=MAX_SPP, bounce_limit=BOUNCES, seed=scenes.SEED, samples_per_iteration=PASS, adaptive_threshold=row["threshold"],
-                           adaptive_measure=m, progress_tiles=False)
+        how = dict(adaptive_display_threshold=row["threshold"], adaptive_display_exposure=DISPLAY["exposure"], adaptive_display_gamma=DISPLAY["gamma"],
+                   adaptive_display_floor=DISPLAY["display_floor"]) if m == "display" else dict(adaptive_threshold=row["threshold"], adaptive_measure=m)
+        loop_st = Settings(cam, sample_count=MAX_SPP, bounce_limit=BOUNCES, seed=scenes.SEED, samples_per_iteration=PASS, progress_tiles=False, **how)
         handle = render.render_tiled(scene, loop_st)
         got = {t.rect: t.sample_count for t in (msg.tile for msg in handle._messages if msg.kind == "TileFinished")}
         want = dict(zip(tiles, (int(c) for c in outcome(m, row["threshold"]))))
@@ -183,6 +212,7 @@ def call_time(a):
     import numpy as np
 
     import tile_luma_ref
+    import tile_weighted_ref
     from raymond_amd import abi, lib, render, scenes
     from raymond_amd.scene import Settings, generate_tiles, tile_array
 
@@ -204,11 +234,18 @@ def call_time(a):
         want = tile_luma_ref.tile_luma_error(S, Q, some, [spp] * len(some), st.adaptive_floor)
         for name in ("valid", "invalid", "mean_luma", "mean_variance", "mean_rel_variance"):
             assert got[name].tobytes() == want[name].tobytes(), name
+        weights = render.display_weights(**DISPLAY)
+        got = render.tile_weighted_error(ctx, fb, fb_sq, some, [spp] * len(some), weights)
+        want = tile_weighted_ref.tile_weighted_error(S, Q, some, [spp] * len(some), weights)
+        for name in ("valid", "invalid", "mean_luma", "mean_variance", "mean_weighted_variance"):
+            assert got[name].tobytes() == want[name].tobytes(), name
         arr = tile_array(tiles)
         counts = np.full(len(tiles), spp, dtype=np.uint32)
         cptr = counts.ctypes.data_as(C.POINTER(C.c_uint32))
         out_luma = np.zeros(len(tiles), dtype=render.TILE_LUMA_DTYPE)
         out_err = np.zeros(len(tiles))
+        out_weighted = np.zeros(len(tiles), dtype=render.TILE_WEIGHTED_DTYPE)
+        wptr = weights.ctypes.data_as(C.POINTER(C.c_double))
 
         def luma():
             ctx.check(ctx.L.rmd_tile_luma_error(ctx.handle, fb.ptr, fb_sq.ptr, W, H, arr, cptr, len(tiles), st.adaptive_floor, out_luma.ctypes.data_as(C.POINTER(abi.TileLuma))))
@@ -216,7 +253,10 @@ def call_time(a):
         def channel_max():
             ctx.check(ctx.L.rmd_tile_error(ctx.handle, fb.ptr, fb_sq.ptr, W, H, spp, st.adaptive_floor, arr, len(tiles), out_err.ctypes.data_as(C.c_void_p)))
 
-        fns = {"rmd_tile_luma_error": luma, "rmd_tile_error": channel_max}
+        def weighted():
+            ctx.check(ctx.L.rmd_tile_weighted_error(ctx.handle, fb.ptr, fb_sq.ptr, W, H, arr, cptr, len(tiles), wptr, out_weighted.ctypes.data_as(C.POINTER(abi.TileWeighted))))
+
+        fns = {"rmd_tile_weighted_error": weighted, "rmd_tile_luma_error": luma, "rmd_tile_error": channel_max}
         for fn in fns.values():
             fn(), fn()  # warm-up: code objects, the context's scratch
         start, stop = hip.event(), hip.event()
@@ -230,9 +270,11 @@ def call_time(a):
             print("%-22s event %.3f ms (min %.3f, max %.3f)  wall %.3f ms" % (n, v["event"]["median_ms"], v["event"]["min_ms"], v["event"]["max_ms"], v["wall"]["median_ms"]),
                   flush=True)
         result["luma_over_channel_max"] = result["calls"]["rmd_tile_luma_error"]["event"]["median_ms"] / result["calls"]["rmd_tile_error"]["event"]["median_ms"]
+        result["weighted_over_luma"] = result["calls"]["rmd_tile_weighted_error"]["event"]["median_ms"] / result["calls"]["rmd_tile_luma_error"]["event"]["median_ms"]
         result["medians_of_the_frame"] = {"rmd_tile_error": float(np.median(out_err)), "tile_rms": float(np.median(out_luma["tile_rms"])),
-                                          "pixel_rms": float(np.median(out_luma["pixel_rms"]))}
-        print(json.dumps({"luma_over_channel_max": result["luma_over_channel_max"], "medians": result["medians_of_the_frame"]}), flush=True)
+                                          "pixel_rms": float(np.median(out_luma["pixel_rms"])), "display_rms": float(np.median(out_weighted["rms"]))}
+        print(json.dumps({"luma_over_channel_max": result["luma_over_channel_max"], "weighted_over_luma": result["weighted_over_luma"],
+                          "medians": result["medians_of_the_frame"]}), flush=True)
     return result
 
 
