@@ -3,6 +3,8 @@
 // Every entry point is its argument checks in its own order and then, inside rmd::guarded: the rect checks, the context, one carved scratch block
 // (denoise_host.hpp has the layouts), one upload of the rects, its launcher (launch.hpp) and the wait.
 #define RMD_WITH_HIP 1
+#include <hip/hip_runtime.h> // (tile_reduce.hpp's combine, which the rule headers bring along under hipcc, names the device runtime)
+
 #include <initializer_list>
 
 #include "despike_rule.hpp"
@@ -12,16 +14,21 @@
 #include "tile_weighted_rule.hpp"
 
 namespace rmd {
+// Every rect lies inside the frame (64-bit sums: left + width may pass 2^32), and what a call says when one does not
+static const char *const kRectOutside = "tile rectangle outside the framebuffer";
+static bool rects_inside(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height) {
+	for (uint32_t i = 0; i < n_rects; i++)
+		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height) return false;
+	return true;
+}
 // Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
 // start before it ends.
 bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height, const char **why) {
 	// (*why: the rule that was broken; the caller puts its own name in front)
+	if (!rects_inside(rects, n_rects, width, height)) return *why = kRectOutside, false;
 	std::vector<uint32_t> order;
-	for (uint32_t i = 0; i < n_rects; i++) {
-		const rmd_tile_rect &r = rects[i];
-		if ((uint64_t)r.left + r.width > width || (uint64_t)r.top + r.height > height) return *why = "tile rectangle outside the framebuffer", false;
-		if (r.width != 0 && r.height != 0) order.push_back(i);
-	}
+	for (uint32_t i = 0; i < n_rects; i++)
+		if (rects[i].width != 0 && rects[i].height != 0) order.push_back(i);
 	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rects[a].left < rects[b].left; });
 	for (size_t i = 0; i < order.size(); i++) {
 		const rmd_tile_rect &a = rects[order[i]];
@@ -297,6 +304,46 @@ rmd_status denoise_dual_select(const char *what, rmd_context *ctx, const double 
 		return finish(ctx);
 	});
 }
+
+// ---------------------------------------------------------------- the per-tile measures (tile_luma.hip, tile_weighted.hip)
+// rmd_tile_luma_error and rmd_tile_weighted_error.  Their refusals in the header's order, the context last: bad_param() is the rule's own parameter check
+// — the refusal's text, or null — in its place in that order; the rects follow rmd_tile_error's rule (inside the frame; they may overlap or repeat), not the
+// filters'.  table_host: the call's n_table doubles (luma: none).  The rects, the counts and the table go up in ONE copy from a host block laid out like the
+// device's.  keep: the context's block of this measure, kept between calls; launch(in, table_dev, out_dev): the rule's launcher on the uploaded rects
+template <class Result, class BadParam, class Launch>
+rmd_status tile_measure(const char *what, rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                        const uint32_t *rect_counts, uint32_t n_rects, const double *table_host, uint32_t n_table, Result *out_host, rmd::DeviceBuffer rmd_context::*keep,
+                        BadParam bad_param, Launch launch) {
+	const std::string name = std::string(what) + ": ";
+	return rmd::guarded(ctx, what, [&] {
+		if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_counts || (n_table && !table_host) || !out_host)))
+			return fail(ctx, kInvalid, name + "bad argument");
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		if (any_overlap({{accum_dev, bytes}, {accum_sq_dev, bytes}})) return fail(ctx, kInvalid, name + "accum_sq_dev must not alias accum_dev");
+		if (const char *why = bad_param()) return fail(ctx, kInvalid, name + why);
+		if (!rmd::rects_inside(rects, n_rects, width, height)) return fail(ctx, kInvalid, name + rmd::kRectOutside);
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		std::vector<unsigned char> staged; // (read by the copy until finish() has waited)
+		if (n_rects != 0) {
+			DenoiseInput in = single_input(accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_counts, n_rects);
+			size_t upload_bytes = 0;
+			Scratch sc; // (the context's block: kept between calls)
+			if (rmd_status s = sc.carve(ctx, rmd::tile_measure_scratch_layout(n_rects, sizeof(Result), n_table, &upload_bytes), &(ctx->*keep))) return s;
+			staged.assign(upload_bytes, 0);
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartRects], rects, (size_t)n_rects * sizeof(rmd_tile_rect));
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartCountsA], rect_counts, (size_t)n_rects * sizeof(uint32_t));
+			if (n_table) std::memcpy(staged.data() + sc.layout.offset[rmd::kPartTable], table_host, (size_t)n_table * sizeof(double));
+			RMD_HIP(ctx, hipMemcpyAsync(sc.base, staged.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+			in.rects = sc.part<rmd_tile_rect>(rmd::kPartRects), in.counts_a = sc.part<uint32_t>(rmd::kPartCountsA);
+			Result *d_out = sc.part<Result>(rmd::kPartTileErrors);
+			RMD_HIP(ctx, launch(in, sc.part<double>(rmd::kPartTable), d_out));
+			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(Result), hipMemcpyDeviceToHost, ctx->stream));
+		}
+		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
+	});
+}
+// A rule header's result struct is the C header's: the same size, and field `f` at the same offset
+#define RMD_SAME_FIELD(A, B, f) (sizeof(A) == sizeof(B) && offsetof(A, f) == offsetof(B, f))
 } // namespace
 
 extern "C" {
@@ -482,88 +529,42 @@ rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *
 	});
 }
 
-// rmd_tile_luma_error (tile_luma.hip).  Its refusals in the header's order, the context last; the rects follow rmd_tile_error's rule (inside the frame; they
-// may overlap or repeat), not the filters'
 rmd_status rmd_tile_luma_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
                                const uint32_t *rect_counts, uint32_t n_rects, double floor, rmd_tile_luma *out_host) {
-	static_assert(sizeof(rmd::TileLuma) == sizeof(rmd_tile_luma) && offsetof(rmd::TileLuma, tile_rms) == offsetof(rmd_tile_luma, tile_rms) &&
-	                  offsetof(rmd::TileLuma, pixel_rms) == offsetof(rmd_tile_luma, pixel_rms) && offsetof(rmd::TileLuma, mean_luma) == offsetof(rmd_tile_luma, mean_luma) &&
-	                  offsetof(rmd::TileLuma, mean_variance) == offsetof(rmd_tile_luma, mean_variance) &&
-	                  offsetof(rmd::TileLuma, mean_rel_variance) == offsetof(rmd_tile_luma, mean_rel_variance) && offsetof(rmd::TileLuma, valid) == offsetof(rmd_tile_luma, valid) &&
-	                  offsetof(rmd::TileLuma, invalid) == offsetof(rmd_tile_luma, invalid),
+	using A = rmd::TileLuma;
+	using B = rmd_tile_luma;
+	static_assert(RMD_SAME_FIELD(A, B, tile_rms) && RMD_SAME_FIELD(A, B, pixel_rms) && RMD_SAME_FIELD(A, B, mean_luma) && RMD_SAME_FIELD(A, B, mean_variance) &&
+	                  RMD_SAME_FIELD(A, B, mean_rel_variance) && RMD_SAME_FIELD(A, B, valid) && RMD_SAME_FIELD(A, B, invalid),
 	              "tile_luma_rule.hpp's TileLuma is rmd_tile_luma");
-	const std::string name = "rmd_tile_luma_error: ";
-	return rmd::guarded(ctx, "rmd_tile_luma_error", [&] {
-		if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_counts || !out_host))) return fail(ctx, kInvalid, name + "bad argument");
-		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		if (any_overlap({{accum_dev, bytes}, {accum_sq_dev, bytes}})) return fail(ctx, kInvalid, name + "accum_sq_dev must not alias accum_dev");
-		if (!(floor > 0.0) || !std::isfinite(floor)) return fail(ctx, kInvalid, name + "floor must be finite and > 0");
-		for (uint32_t i = 0; i < n_rects; i++)
-			if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
-				return fail(ctx, kInvalid, name + "tile rectangle outside the framebuffer");
-		if (rmd_status s = rmd::bind(ctx)) return s;
-		if (n_rects != 0) {
-			DenoiseInput in = single_input(accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_counts, n_rects);
-			Scratch sc; // (the context's block: kept between calls)
-			if (rmd_status s = sc.carve(ctx, rmd::tile_luma_scratch_layout(n_rects), &ctx->tile_luma_scratch)) return s;
-			if (rmd_status s = upload_rects(ctx, sc, in)) return s;
-			rmd::TileLuma *d_out = sc.part<rmd::TileLuma>(rmd::kPartTileErrors);
-			RMD_HIP(ctx, rmd::launch_tile_luma(ctx->stream, in, floor, d_out));
-			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(rmd_tile_luma), hipMemcpyDeviceToHost, ctx->stream));
-		}
-		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
-	});
+	return tile_measure(
+	    "rmd_tile_luma_error", ctx, accum_dev, accum_sq_dev, width, height, rects, rect_counts, n_rects, nullptr, 0u, out_host, &rmd_context::tile_luma_scratch,
+	    [&]() -> const char * { return !(floor > 0.0) || !std::isfinite(floor) ? "floor must be finite and > 0" : nullptr; },
+	    [&](const DenoiseInput &in, const double *, B *d_out) { return rmd::launch_tile_luma(ctx->stream, in, floor, reinterpret_cast<A *>(d_out)); });
 }
 
-// rmd_tile_weighted_error (tile_weighted.hip).  Its refusals in the header's order, the context last; the rects follow rmd_tile_error's rule (inside the
-// frame; they may overlap or repeat).  The rects, the counts and the weights go up in ONE copy from a host block laid out like the device's
 rmd_status rmd_tile_weighted_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
                                    const uint32_t *rect_counts, uint32_t n_rects, const double *weights_host, rmd_tile_weighted *out_host) {
-	static_assert(sizeof(rmd::TileWeighted) == sizeof(rmd_tile_weighted) && sizeof(rmd_tile_weighted) == 40 && offsetof(rmd::TileWeighted, rms) == offsetof(rmd_tile_weighted, rms) &&
-	                  offsetof(rmd::TileWeighted, mean_weighted_variance) == offsetof(rmd_tile_weighted, mean_weighted_variance) &&
-	                  offsetof(rmd::TileWeighted, mean_luma) == offsetof(rmd_tile_weighted, mean_luma) &&
-	                  offsetof(rmd::TileWeighted, mean_variance) == offsetof(rmd_tile_weighted, mean_variance) && offsetof(rmd::TileWeighted, valid) == offsetof(rmd_tile_weighted, valid) &&
-	                  offsetof(rmd::TileWeighted, invalid) == offsetof(rmd_tile_weighted, invalid),
+	using A = rmd::TileWeighted;
+	using B = rmd_tile_weighted;
+	static_assert(sizeof(B) == 40 && RMD_SAME_FIELD(A, B, rms) && RMD_SAME_FIELD(A, B, mean_weighted_variance) && RMD_SAME_FIELD(A, B, mean_luma) &&
+	                  RMD_SAME_FIELD(A, B, mean_variance) && RMD_SAME_FIELD(A, B, valid) && RMD_SAME_FIELD(A, B, invalid),
 	              "tile_weighted_rule.hpp's TileWeighted is rmd_tile_weighted");
 	static_assert(rmd::kLumaWeights == RMD_LUMA_WEIGHTS, "tile_weighted_rule.hpp's table is the header's");
-	const std::string name = "rmd_tile_weighted_error: ";
-	return rmd::guarded(ctx, "rmd_tile_weighted_error", [&] {
-		if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !rect_counts || !weights_host || !out_host)))
-			return fail(ctx, kInvalid, name + "bad argument");
-		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
-		if (any_overlap({{accum_dev, bytes}, {accum_sq_dev, bytes}})) return fail(ctx, kInvalid, name + "accum_sq_dev must not alias accum_dev");
-		for (uint32_t k = 0; weights_host && k < RMD_LUMA_WEIGHTS; k++)
-			if (!(weights_host[k] >= 0.0) || !std::isfinite(weights_host[k])) return fail(ctx, kInvalid, name + "every weight must be finite and >= 0");
-		for (uint32_t i = 0; i < n_rects; i++)
-			if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
-				return fail(ctx, kInvalid, name + "tile rectangle outside the framebuffer");
-		if (rmd_status s = rmd::bind(ctx)) return s;
-		std::vector<unsigned char> staged; // (read by the copy until finish() has waited)
-		if (n_rects != 0) {
-			DenoiseInput in = single_input(accum_dev, accum_sq_dev, nullptr, nullptr, width, height, rects, rect_counts, n_rects);
-			size_t upload_bytes = 0;
-			Scratch sc; // (the context's block: kept between calls)
-			if (rmd_status s = sc.carve(ctx, rmd::tile_weighted_scratch_layout(n_rects, &upload_bytes), &ctx->tile_weighted_scratch)) return s;
-			staged.assign(upload_bytes, 0);
-			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartRects], rects, (size_t)n_rects * sizeof(rmd_tile_rect));
-			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartCountsA], rect_counts, (size_t)n_rects * sizeof(uint32_t));
-			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartTable], weights_host, (size_t)RMD_LUMA_WEIGHTS * sizeof(double));
-			RMD_HIP(ctx, hipMemcpyAsync(sc.base, staged.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-			in.rects = sc.part<rmd_tile_rect>(rmd::kPartRects), in.counts_a = sc.part<uint32_t>(rmd::kPartCountsA);
-			rmd::TileWeighted *d_out = sc.part<rmd::TileWeighted>(rmd::kPartTileErrors);
-			RMD_HIP(ctx, rmd::launch_tile_weighted(ctx->stream, in, sc.part<double>(rmd::kPartTable), d_out));
-			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(rmd_tile_weighted), hipMemcpyDeviceToHost, ctx->stream));
-		}
-		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
-	});
+	return tile_measure(
+	    "rmd_tile_weighted_error", ctx, accum_dev, accum_sq_dev, width, height, rects, rect_counts, n_rects, weights_host, RMD_LUMA_WEIGHTS, out_host,
+	    &rmd_context::tile_weighted_scratch,
+	    [&]() -> const char * {
+		    for (uint32_t k = 0; weights_host && k < RMD_LUMA_WEIGHTS; k++)
+			    if (!(weights_host[k] >= 0.0) || !std::isfinite(weights_host[k])) return "every weight must be finite and >= 0";
+		    return nullptr;
+	    },
+	    [&](const DenoiseInput &in, const double *weights, B *d_out) { return rmd::launch_tile_weighted(ctx->stream, in, weights, reinterpret_cast<A *>(d_out)); });
 }
 
 rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
                                double *out_err_host) {
 	if (!err_dev || width == 0 || height == 0 || (n_rects && (!rects || !out_err_host))) return fail(ctx, kInvalid, "rmd_tile_error_dual: bad argument");
-	for (uint32_t i = 0; i < n_rects; i++)
-		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height)
-			return fail(ctx, kInvalid, "rmd_tile_error_dual: tile rectangle outside the framebuffer");
+	if (!rmd::rects_inside(rects, n_rects, width, height)) return fail(ctx, kInvalid, std::string("rmd_tile_error_dual: ") + rmd::kRectOutside);
 	return rmd::guarded(ctx, "rmd_tile_error_dual", [&] {
 		if (rmd_status s = rmd::bind(ctx)) return s;
 		Scratch sc; // (it outlives the wait below)

@@ -109,30 +109,20 @@ inline ScratchLayout despike_scratch_layout(uint32_t W, uint32_t H, uint32_t n_r
 	return L;
 }
 
-// rmd_tile_luma_error's block, in the parts' existing names: kPartRects and kPartCountsA the rects and their counts, kPartTileErrors the per-rect results
-// (n_rects rmd_tile_luma).  Like rmd_despike's it is not one of the forms above
-inline ScratchLayout tile_luma_scratch_layout(uint32_t n_rects) {
+// The block of rmd_tile_luma_error (n_table 0) and rmd_tile_weighted_error (n_table RMD_LUMA_WEIGHTS), in the parts' existing names: kPartRects and
+// kPartCountsA the rects and their counts, kPartTable the call's table of n_table doubles, kPartTileErrors the per-rect results of result_bytes each.  All
+// but the results is what the call uploads, in one copy: those parts lie at the block's start in this order, each padded to 16 bytes; `upload_bytes` is
+// where the results begin.  Like rmd_despike's it is not one of the forms above
+inline ScratchLayout tile_measure_scratch_layout(uint32_t n_rects, size_t result_bytes, size_t n_table, size_t *upload_bytes) {
 	ScratchLayout L;
 	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
 		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
 		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
 	};
-	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, sizeof(uint32_t), n_rects), part(kPartTileErrors, sizeof(rmd_tile_luma), n_rects);
-	return L;
-}
-
-// rmd_tile_weighted_error's block, in the parts' existing names: kPartRects and kPartCountsA the rects and their counts, kPartTable the call's
-// RMD_LUMA_WEIGHTS weights (doubles), kPartTileErrors the per-rect results (n_rects rmd_tile_weighted, 40 B each).  The first three parts are what the call
-// uploads, in one copy: they lie at the block's start in this order, each padded to 16 bytes; `upload_bytes` is where the results begin
-inline ScratchLayout tile_weighted_scratch_layout(uint32_t n_rects, size_t *upload_bytes = nullptr) {
-	ScratchLayout L;
-	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
-		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
-		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
-	};
-	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, sizeof(uint32_t), n_rects), part(kPartTable, sizeof(double), RMD_LUMA_WEIGHTS);
-	if (upload_bytes) *upload_bytes = L.total;
-	part(kPartTileErrors, sizeof(rmd_tile_weighted), n_rects);
+	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, sizeof(uint32_t), n_rects);
+	if (n_table != 0u) part(kPartTable, sizeof(double), n_table);
+	*upload_bytes = L.total;
+	part(kPartTileErrors, result_bytes, n_rects);
 	return L;
 }
 

@@ -5,8 +5,9 @@
 // tile_luma_kernel — one workgroup of 256 threads (four waves of 64) per rect:
 //   1. lane t takes the rect's row-major pixels t, t + 256, ...: 2 x 24 bytes a pixel, neighbouring lanes neighbouring records; it keeps the sums of Y, V
 //      and R over its valid pixels and counts the valid and the invalid ones;
-//   2. within a wave the five values meet by __shfl_xor over 32, 16, 8, 4, 2, 1; lane 0 of each wave leaves them in LDS;
-//   3. thread 0 adds the four waves' as (w0 + w1) + (w2 + w3), takes the final step and writes the rect's 48 bytes with plain stores.
+//   2. tile_reduce.hpp's combine: within a wave the five values meet by the xor exchange over 32, 16, 8, 4, 2, 1; lane 0 of each wave leaves them in LDS;
+//      thread 0 adds the four waves' as (w0 + w1) + (w2 + w3);
+//   3. thread 0 takes the final step and writes the rect's 48 bytes with plain stores.
 // No atomics: the bits do not depend on scheduling.  f64 throughout, built with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
@@ -15,41 +16,20 @@
 
 namespace rmd {
 
-static_assert(kTileLumaLanes == 256u && kTileLumaWave == 64u, "the combine below is written for four waves of 64");
-
 __global__ __launch_bounds__(256) void tile_luma_kernel(const double *__restrict__ S, const double *__restrict__ Q, const rmd_tile_rect *__restrict__ rects,
                                                          const uint32_t *__restrict__ counts, uint32_t W, double floor, TileLuma *__restrict__ out) {
 	const rmd_tile_rect r = rects[blockIdx.x];
 	const uint32_t n = counts[blockIdx.x];
 	const uint64_t n_px = (uint64_t)r.width * r.height;
-	TileLumaSums a;
-	for (uint64_t i = threadIdx.x; i < n_px; i += kTileLumaLanes) {
-		const size_t pix = (size_t)(r.left + (uint32_t)(i % r.width)) + (size_t)(r.top + (uint32_t)(i / r.width)) * W;
+	TileSums a;
+	for (uint64_t i = threadIdx.x; i < n_px; i += kTileLanes) {
+		const size_t pix = tile_pixel_index(i, r.left, r.top, r.width, W);
 		double s[3], q[3];
 #pragma unroll
 		for (int c = 0; c < 3; c++) s[c] = S[pix * 3 + c], q[c] = Q[pix * 3 + c];
 		tile_luma_add(a, s, q, n, floor);
 	}
-	for (int off = 32; off > 0; off >>= 1) {
-		a.sy = a.sy + __shfl_xor(a.sy, off, 64), a.sv = a.sv + __shfl_xor(a.sv, off, 64), a.sr = a.sr + __shfl_xor(a.sr, off, 64);
-		a.valid += __shfl_xor(a.valid, off, 64), a.invalid += __shfl_xor(a.invalid, off, 64);
-	}
-	__shared__ double wave_sum[3][4];
-	__shared__ uint32_t wave_count[2][4];
-	if ((threadIdx.x & 63u) == 0u) {
-		const uint32_t w = threadIdx.x >> 6;
-		wave_sum[0][w] = a.sy, wave_sum[1][w] = a.sv, wave_sum[2][w] = a.sr;
-		wave_count[0][w] = a.valid, wave_count[1][w] = a.invalid;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0u) {
-		const double SY = (wave_sum[0][0] + wave_sum[0][1]) + (wave_sum[0][2] + wave_sum[0][3]);
-		const double SV = (wave_sum[1][0] + wave_sum[1][1]) + (wave_sum[1][2] + wave_sum[1][3]);
-		const double SR = (wave_sum[2][0] + wave_sum[2][1]) + (wave_sum[2][2] + wave_sum[2][3]);
-		const uint32_t valid = (wave_count[0][0] + wave_count[0][1]) + (wave_count[0][2] + wave_count[0][3]);
-		const uint32_t invalid = (wave_count[1][0] + wave_count[1][1]) + (wave_count[1][2] + wave_count[1][3]);
-		out[blockIdx.x] = tile_luma_final(SY, SV, SR, valid, invalid, n_px, floor);
-	}
+	if (tile_sums_combine(a)) out[blockIdx.x] = tile_luma_final(a.sy, a.sv, a.se, a.valid, a.invalid, n_px, floor);
 }
 
 hipError_t launch_tile_luma(hipStream_t stream, const DenoiseInput &in, double floor, TileLuma *out) {

@@ -560,6 +560,27 @@ struct TileWorker : Worker {
 	// With the display measure (settings.adaptive_display_threshold): ONE rmd_tile_weighted_error over all of them, each rect at its own count, under
 	// rmd_display_weights' table; with adaptive_display_auto_exposure the table is first made anew from the histogram of the whole frame — the tiles that
 	// finished early at their counts and the batch, which with one worker is every other tile — on the sums the check reads
+	// What converged_tiles hands to the library: rects (or the indices in `mine` of the tiles they are cut from) and each one's count
+	struct Counted {
+		std::vector<size_t> which;
+		std::vector<rmd_tile_rect> rects;
+		std::vector<uint32_t> counts;
+	};
+	// the tiles below sample_count at their counts, which the luma and the display measure take in one call
+	Counted below_sample_count(const std::vector<Tile> &mine) const {
+		Counted c;
+		for (size_t i = 0; i < mine.size(); i++)
+			if (mine[i].sample_count < st.sample_count) c.which.push_back(i), c.counts.push_back((uint32_t)mine[i].sample_count);
+		c.rects = rects_of(mine, c.which);
+		return c;
+	}
+	// every tile at its current count, which rmd_despike and the histogram take: the tiles that finished early, then `mine`
+	Counted finished_and_current(const std::vector<Tile> &mine) const {
+		Counted c;
+		c.rects = converged_rects, c.counts = converged_counts;
+		for (const Tile &t : mine) c.rects.push_back(rect_of(t)), c.counts.push_back((uint32_t)t.sample_count);
+		return c;
+	}
 	std::vector<bool> converged_tiles(std::vector<Tile> &mine) {
 		std::vector<bool> converged(mine.size(), false);
 		if (!adaptive) return converged;
@@ -569,50 +590,38 @@ struct TileWorker : Worker {
 		const double *s = fb, *s_sq = fb_sq;
 		if (despike_check && !live.empty()) {
 			// one worker: the batch is every tile that has not finished.  All tiles at their current counts go through rmd_despike into the spare buffers
-			std::vector<rmd_tile_rect> rects(converged_rects);
-			std::vector<uint32_t> counts(converged_counts);
-			for (const Tile &t : mine) rects.push_back(rect_of(t)), counts.push_back((uint32_t)t.sample_count);
-			check(rmd_despike(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.despike_radius, st.despike_rank, st.despike_k,
+			const Counted all = finished_and_current(mine);
+			check(rmd_despike(ctx, fb, fb_sq, (uint32_t)W, (uint32_t)H, all.rects.data(), all.counts.data(), (uint32_t)all.rects.size(), st.despike_radius, st.despike_rank, st.despike_k,
 			                  st.despike_ratio, st.despike_floor, fb_spare, fb_spare_sq, nullptr),
 			      ctx, "rmd_despike");
 			s = fb_spare, s_sq = fb_spare_sq;
 		}
 		if (display_measure && !live.empty()) {
 			if (st.adaptive_display_auto_exposure) {
-				std::vector<rmd_tile_rect> rects(converged_rects);
-				std::vector<uint32_t> counts(converged_counts);
-				for (const Tile &t : mine) rects.push_back(rect_of(t)), counts.push_back((uint32_t)t.sample_count);
+				const Counted all = finished_and_current(mine);
 				rmd_luma_histogram hist;
-				check(rmd_luminance_histogram_tiles(ctx, s, nullptr, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), &hist), ctx,
+				check(rmd_luminance_histogram_tiles(ctx, s, nullptr, (uint32_t)W, (uint32_t)H, all.rects.data(), all.counts.data(), (uint32_t)all.rects.size(), &hist), ctx,
 				      "rmd_luminance_histogram_tiles");
 				double exposure = 1.0;
 				check(rmd_exposure_from_histogram(&hist, st.auto_exposure_percentile, st.auto_exposure_target, &exposure), nullptr, "rmd_exposure_from_histogram");
 				weights = display_weights(exposure, st.adaptive_display_gamma, st.adaptive_display_floor);
 			}
-			std::vector<size_t> which;
-			std::vector<uint32_t> counts;
-			for (size_t i = 0; i < mine.size(); i++)
-				if (mine[i].sample_count < st.sample_count) which.push_back(i), counts.push_back((uint32_t)mine[i].sample_count);
-			const std::vector<rmd_tile_rect> rects = rects_of(mine, which);
-			std::vector<rmd_tile_weighted> weighted(rects.size());
-			check(rmd_tile_weighted_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), weights.data(), weighted.data()), ctx,
+			const Counted b = below_sample_count(mine);
+			std::vector<rmd_tile_weighted> weighted(b.rects.size());
+			check(rmd_tile_weighted_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, b.rects.data(), b.counts.data(), (uint32_t)b.rects.size(), weights.data(), weighted.data()), ctx,
 			      "rmd_tile_weighted_error");
-			for (size_t k = 0; k < weighted.size(); k++) mine[which[k]].error = weighted[k].rms, converged[which[k]] = weighted[k].rms <= threshold;
+			for (size_t k = 0; k < weighted.size(); k++) mine[b.which[k]].error = weighted[k].rms, converged[b.which[k]] = weighted[k].rms <= threshold;
 			live.clear(); // (no rmd_tile_error call below)
 		}
 		if (luma_measure) {
-			std::vector<size_t> which;
-			std::vector<uint32_t> counts;
-			for (size_t i = 0; i < mine.size(); i++)
-				if (mine[i].sample_count < st.sample_count) which.push_back(i), counts.push_back((uint32_t)mine[i].sample_count);
-			const std::vector<rmd_tile_rect> rects = rects_of(mine, which);
-			std::vector<rmd_tile_luma> luma(rects.size());
-			if (!rects.empty())
-				check(rmd_tile_luma_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, rects.data(), counts.data(), (uint32_t)rects.size(), st.adaptive_floor, luma.data()), ctx,
+			const Counted b = below_sample_count(mine);
+			std::vector<rmd_tile_luma> luma(b.rects.size());
+			if (!b.rects.empty())
+				check(rmd_tile_luma_error(ctx, s, s_sq, (uint32_t)W, (uint32_t)H, b.rects.data(), b.counts.data(), (uint32_t)b.rects.size(), st.adaptive_floor, luma.data()), ctx,
 				      "rmd_tile_luma_error");
 			for (size_t k = 0; k < luma.size(); k++) {
 				const double e = st.adaptive_measure == "luma_tile" ? luma[k].tile_rms : luma[k].pixel_rms;
-				mine[which[k]].error = e, converged[which[k]] = e <= threshold;
+				mine[b.which[k]].error = e, converged[b.which[k]] = e <= threshold;
 			}
 			live.clear(); // (no rmd_tile_error call below)
 		}
@@ -1214,33 +1223,37 @@ std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::
 	return replaced;
 }
 
-std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
-                                                const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double floor) {
-	if (sums.size() != width * height || sums_sq.size() != width * height || rects.size() != counts.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_luma_error_host: bad argument");
-	std::vector<rmd_tile_luma> out(rects.size());
+// tile_luma_error_host and tile_weighted_error_host: the checks, then each rect through the rule's tile_*_rect_host.  measure(S, Q, rect, count): the rule's result
+template <class Result, class Measure>
+static std::vector<Result> tile_measure_host(const std::string &name, const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
+                                             const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, bool bad_parameter, Measure measure) {
+	if (sums.size() != width * height || sums_sq.size() != width * height || rects.size() != counts.size() || bad_parameter) throw Error(RMD_ERR_INVALID_ARGUMENT, name + ": bad argument");
+	std::vector<Result> out(rects.size());
 	const double *S = sums.empty() ? nullptr : sums[0].data(), *Q = sums_sq.empty() ? nullptr : sums_sq[0].data();
 	for (size_t j = 0; j < rects.size(); j++) {
 		const rmd_tile_rect &r = rects[j];
-		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_luma_error_host: tile rectangle outside the framebuffer");
-		const rmd::TileLuma t = rmd::tile_luma_rect_host(S, Q, (uint32_t)width, r.left, r.top, r.width, r.height, counts[j], floor);
-		out[j] = rmd_tile_luma{t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid};
+		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height) throw Error(RMD_ERR_INVALID_ARGUMENT, name + ": tile rectangle outside the framebuffer");
+		out[j] = measure(S, Q, r, counts[j]);
 	}
 	return out;
 }
 
+std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
+                                                const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double floor) {
+	const auto measure = [&](const double *S, const double *Q, const rmd_tile_rect &r, uint32_t n) {
+		const rmd::TileLuma t = rmd::tile_luma_rect_host(S, Q, (uint32_t)width, r.left, r.top, r.width, r.height, n, floor);
+		return rmd_tile_luma{t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid};
+	};
+	return tile_measure_host<rmd_tile_luma>("tile_luma_error_host", sums, sums_sq, width, height, rects, counts, false, measure);
+}
+
 std::vector<rmd_tile_weighted> tile_weighted_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
                                                         const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, const std::vector<double> &weights) {
-	if (sums.size() != width * height || sums_sq.size() != width * height || rects.size() != counts.size() || weights.size() != RMD_LUMA_WEIGHTS)
-		throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_weighted_error_host: bad argument");
-	std::vector<rmd_tile_weighted> out(rects.size());
-	const double *S = sums.empty() ? nullptr : sums[0].data(), *Q = sums_sq.empty() ? nullptr : sums_sq[0].data();
-	for (size_t j = 0; j < rects.size(); j++) {
-		const rmd_tile_rect &r = rects[j];
-		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile_weighted_error_host: tile rectangle outside the framebuffer");
-		const rmd::TileWeighted t = rmd::tile_weighted_rect_host(S, Q, (uint32_t)width, r.left, r.top, r.width, r.height, counts[j], weights.data());
-		out[j] = rmd_tile_weighted{t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance, t.valid, t.invalid};
-	}
-	return out;
+	const auto measure = [&](const double *S, const double *Q, const rmd_tile_rect &r, uint32_t n) {
+		const rmd::TileWeighted t = rmd::tile_weighted_rect_host(S, Q, (uint32_t)width, r.left, r.top, r.width, r.height, n, weights.data());
+		return rmd_tile_weighted{t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance, t.valid, t.invalid};
+	};
+	return tile_measure_host<rmd_tile_weighted>("tile_weighted_error_host", sums, sums_sq, width, height, rects, counts, weights.size() != RMD_LUMA_WEIGHTS, measure);
 }
 
 std::vector<double> display_weights(double exposure, double gamma, double display_floor) {

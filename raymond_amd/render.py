@@ -279,23 +279,35 @@ TILE_LUMA_DTYPE = np.dtype([("tile_rms", "<f8"), ("pixel_rms", "<f8"), ("mean_lu
 assert TILE_LUMA_DTYPE.itemsize == C.sizeof(abi.TileLuma)
 
 
+def _tile_measure(entry, dtype, result, ctx, framebuffer, framebuffer_sq, tiles, counts, parameter):
+    """One per-tile measure: `entry` of the library over the tiles at their own counts, into a structured array of `dtype` (the C struct `result`, field for
+    field).  parameter(): the measure's own argument as ctypes takes it, made once the counts are checked."""
+    tiles = list(tiles)
+    (counts,) = _counts(tiles, counts)
+    parameter = parameter()
+    out = np.zeros(max(1, len(tiles)), dtype=dtype)
+    ctx.check(getattr(ctx.L, entry)(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(tiles), _u32(counts), len(tiles),
+                                    parameter, out.ctypes.data_as(C.POINTER(result))))
+    return out[: len(tiles)]
+
+
+def _tile_measure_arrays(measure, ctx, sums, sums_sq, tiles, counts, parameter):
+    """`measure` (tile_luma_error, tile_weighted_error) for host arrays: (H, W, 3) sums and sums of squares in, the structured array out."""
+    with contextlib.ExitStack() as stack:
+        s, q = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq))
+        return measure(ctx, s, q, tiles, counts, parameter)
+
+
 def tile_luma_error(ctx, framebuffer, framebuffer_sq, tiles, counts, floor):
     """rmd_tile_luma_error: per tile, at its own sample count, the aggregated noise of its luminance — a numpy structured array with rmd_tile_luma's fields:
     tile_rms (the RMS standard error of the luminance over the tile's mean luminance), pixel_rms (the RMS of the pixels' relative luminance errors), the
     three means they are made of, and the valid / invalid pixel counts.  Tiles may overlap or repeat."""
-    tiles = list(tiles)
-    (counts,) = _counts(tiles, counts)
-    out = np.zeros(max(1, len(tiles)), dtype=TILE_LUMA_DTYPE)
-    ctx.check(ctx.L.rmd_tile_luma_error(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(tiles), _u32(counts),
-                                        len(tiles), float(floor), out.ctypes.data_as(C.POINTER(abi.TileLuma))))
-    return out[: len(tiles)]
+    return _tile_measure("rmd_tile_luma_error", TILE_LUMA_DTYPE, abi.TileLuma, ctx, framebuffer, framebuffer_sq, tiles, counts, lambda: float(floor))
 
 
 def tile_luma_error_arrays(ctx, sums, sums_sq, tiles, counts, floor):
     """tile_luma_error() for host arrays: (H, W, 3) sums and sums of squares in, the structured array out."""
-    with contextlib.ExitStack() as stack:
-        s, q = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq))
-        return tile_luma_error(ctx, s, q, tiles, counts, floor)
+    return _tile_measure_arrays(tile_luma_error, ctx, sums, sums_sq, tiles, counts, floor)
 
 
 TILE_WEIGHTED_DTYPE = np.dtype([("rms", "<f8"), ("mean_weighted_variance", "<f8"), ("mean_luma", "<f8"), ("mean_variance", "<f8"), ("valid", "<u4"),
@@ -315,20 +327,13 @@ def tile_weighted_error(ctx, framebuffer, framebuffer_sq, tiles, counts, weights
     one per counter of the luminance histogram (256 bins, below, above, zero, negative); a pixel takes the entry its luminance's bits name — as a numpy
     structured array with rmd_tile_weighted's fields: rms (what an adaptive check compares with its threshold), mean_weighted_variance, mean_luma,
     mean_variance and the valid / invalid pixel counts.  display_weights() makes the table of the displayed error.  Tiles may overlap or repeat."""
-    tiles = list(tiles)
-    (counts,) = _counts(tiles, counts)
-    weights = _weights(weights)
-    out = np.zeros(max(1, len(tiles)), dtype=TILE_WEIGHTED_DTYPE)
-    ctx.check(ctx.L.rmd_tile_weighted_error(ctx.handle, framebuffer.ptr, framebuffer_sq.ptr, framebuffer.width, framebuffer.height, tile_array(tiles), _u32(counts),
-                                            len(tiles), weights.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(abi.TileWeighted))))
-    return out[: len(tiles)]
+    return _tile_measure("rmd_tile_weighted_error", TILE_WEIGHTED_DTYPE, abi.TileWeighted, ctx, framebuffer, framebuffer_sq, tiles, counts,
+                         lambda: _weights(weights).ctypes.data_as(C.POINTER(C.c_double)))
 
 
 def tile_weighted_error_arrays(ctx, sums, sums_sq, tiles, counts, weights):
     """tile_weighted_error() for host arrays: (H, W, 3) sums and sums of squares in, the structured array out."""
-    with contextlib.ExitStack() as stack:
-        s, q = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq))
-        return tile_weighted_error(ctx, s, q, tiles, counts, weights)
+    return _tile_measure_arrays(tile_weighted_error, ctx, sums, sums_sq, tiles, counts, weights)
 
 
 def display_weights(exposure=1.0, gamma=2.2, display_floor=1.0 / 255.0):

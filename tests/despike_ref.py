@@ -2,8 +2,7 @@
 through view(np.uint64).  Also rmd_tile_error restated, for the tile the stage exists for.  No GPU, no library."""
 import numpy as np
 
-WR, WG, WB = np.float64(0.2126), np.float64(0.7152), np.float64(0.0722)
-A0, A1, A2 = WR * WR, WG * WG, WB * WB  # the binary64 product of each weight with itself
+from tile_reduce_ref import A0, A1, A2, WB, WG, WR  # the luminance weights, and the binary64 product of each with itself
 
 
 def count_image(width, height, rects, counts):

@@ -88,11 +88,16 @@ def test_the_cpp_mirrors_host_function_on_the_wide_frame_and_on_no_rects(cli, tm
 
 def test_the_rule_header_agrees_with_a_plain_reading_under_sanitizers(tmp_path):
     header = open(os.path.join(CSRC, "tile_luma_rule.hpp")).read()
-    assert re.findall(r"#include [<\"]([^>\"]+)[>\"]", header) == ["stdint.h", "despike_rule.hpp"]  # nothing else of the project, nothing of HIP
+    assert re.findall(r"#include [<\"]([^>\"]+)[>\"]", header) == ["stdint.h", "despike_rule.hpp", "tile_reduce.hpp"]  # nothing else of the project, nothing of HIP
+    order = open(os.path.join(CSRC, "tile_reduce.hpp")).read()
+    assert re.findall(r"#include [<\"]([^>\"]+)[>\"]", order) == ["stdint.h"]
     kernel = open(os.path.join(CSRC, "tile_luma.hip")).read()
-    for fn in ("tile_luma_add(", "tile_luma_final(", "__shfl_xor(", "__launch_bounds__(256)"):
+    for fn in ("tile_luma_add(", "tile_luma_final(", "tile_sums_combine(", "__launch_bounds__(256)"):
         assert fn in kernel, fn  # the kernel reads the same lines
-    assert "asm" not in kernel and "atomic" not in kernel.replace("No atomics", "")
+    for fn in ("__shfl_xor(", "__syncthreads()", "tile_sums_combine(", "tile_rect_sums_host("):
+        assert fn in order, fn  # ... and takes the order its sums are added in from where the host emulation takes it
+    assert "tile_rect_sums_host(" in header
+    assert "asm" not in kernel and "atomic" not in kernel.replace("No atomics", "") and "asm" not in order and "atomic" not in order
     assert "tile_luma_pixel(" in header and "despike_pixel(" in header
     mirror = open(os.path.join(ROOT, "raymond_amd", "host", "raymond.cpp")).read()
     assert '#include "../csrc/tile_luma_rule.hpp"' in mirror and "rmd::tile_luma_rect_host(" in mirror  # ... and so does the C++ mirror

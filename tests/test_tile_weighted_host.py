@@ -112,13 +112,18 @@ def test_the_cpp_mirrors_host_function_on_the_wide_frame_on_no_rects_and_with_th
 
 def test_the_rule_header_agrees_with_a_plain_reading_under_sanitizers(tmp_path):
     header = open(os.path.join(CSRC, "tile_weighted_rule.hpp")).read()
-    assert re.findall(r"#include [<\"]([^>\"]+)[>\"]", header) == ["stdint.h", "luma_bins.hpp", "despike_rule.hpp"]  # nothing else of the project, nothing of HIP
+    assert re.findall(r"#include [<\"]([^>\"]+)[>\"]", header) == ["stdint.h", "luma_bins.hpp", "despike_rule.hpp", "tile_reduce.hpp"]  # nothing else of the project, nothing of HIP
+    order = open(os.path.join(CSRC, "tile_reduce.hpp")).read()
+    assert re.findall(r"#include [<\"]([^>\"]+)[>\"]", order) == ["stdint.h"]
     kernel = open(os.path.join(CSRC, "tile_weighted.hip")).read()
-    for fn in ("tile_weighted_add(", "tile_weighted_final(", "__shfl_xor(", "__launch_bounds__(256)", "__shared__ double lds_weights[kLumaWeights]", "__syncthreads()"):
+    for fn in ("tile_weighted_add(", "tile_weighted_final(", "tile_sums_combine(", "__launch_bounds__(256)", "__shared__ double lds_weights[kLumaWeights]", "__syncthreads()"):
         assert fn in kernel, fn  # the kernel reads the same lines
-    assert "asm" not in kernel and "atomic" not in kernel.replace("No atomics", "")
+    for fn in ("__shfl_xor(", "__syncthreads()", "tile_sums_combine(", "tile_rect_sums_host("):
+        assert fn in order, fn  # ... and takes the order its sums are added in from where the host emulation takes it
+    assert "tile_rect_sums_host(" in header
+    assert "asm" not in kernel and "atomic" not in kernel.replace("No atomics", "") and "asm" not in order and "atomic" not in order
     for fn in ("exp(", "pow(", "log(", "expm1("):
-        assert fn not in kernel and fn not in header, fn  # no transcendental function on the device
+        assert fn not in kernel and fn not in header and fn not in order, fn  # no transcendental function on the device
     assert "tile_weighted_pixel(" in header and "despike_pixel(" in header and "luma_counter(luma_bits(Y))" in header
     mirror = open(os.path.join(ROOT, "raymond_amd", "host", "raymond.cpp")).read()
     assert '#include "../csrc/tile_weighted_rule.hpp"' in mirror and "rmd::tile_weighted_rect_host(" in mirror  # ... and so does the C++ mirror
@@ -428,7 +433,7 @@ def test_the_frame_classes_are_what_they_name():
     shapes = sorted((w, h) for (_, _, w, h) in rects)
     for want in ((1, 1), (16, 16), (17, 15), (32, 32), (33, 31)):
         assert want in shapes
-    assert len(rects) == 13 and (frames.W, frames.H) == (67, 45) and {1, 2, 3, 17, 2**32 - 1} == set(counts)
+    assert len(rects) == 16 and sorted(w * h for (_, _, w, h) in rects)[4:7] == [63, 64, 65] and (frames.W, frames.H) == (67, 45) and {1, 2, 3, 17, 2**32 - 1} == set(counts)
     assert sorted((w, h) for (_, _, w, h), _ in frames.WIDE_RECTS)[1:] == [(1, 257), (255, 1)] and frames.WIDE == 300
     lit = [j for j, ((_, _, w, h), c) in enumerate(zip(rects, counts)) if w * h and c >= 2]
 

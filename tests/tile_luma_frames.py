@@ -21,6 +21,9 @@ RECTS = [
     ((40, 36, 9, 9), NMAX),    # one rect given twice
     ((40, 36, 9, 9), NMAX),
     ((0, 40, 6, 5), 1),        # a count of 1: every pixel invalid
+    ((55, 0, 9, 7), 3),        # 63: one wave, its last lane none
+    ((0, 30, 8, 8), 17),       # 64: exactly one wave, the other three add zeros
+    ((60, 32, 5, 13), 2),      # 65: one lane of the second wave
 ]
 BAD_PIXEL = (12, 20)  # (x, y) inside the 32 x 32 rect and no other rect of the list
 BAD_RECT = 3

@@ -1,11 +1,10 @@
 """rmd_tile_weighted_error and rmd_display_weights restated in numpy (include/raymond_hip.h has the definitions): np.float64 operations only — elementwise
-array arithmetic is the same rounded IEEE operation per element, nothing fused —, the weight's index taken from the 64 bits of the luminance, 256 lanes that
-each add their pixels in order, and the kernel's combine spelt out.  No GPU, no library."""
+array arithmetic is the same rounded IEEE operation per element, nothing fused —, the weight's index taken from the 64 bits of the luminance.  The rule is
+here: the counter, E and the final step; a pixel's validity, Y and V and the kernel's summation order are tile_reduce_ref.py's.  No GPU, no library."""
 import numpy as np
 
-WR, WG, WB = np.float64(0.2126), np.float64(0.7152), np.float64(0.0722)
-A0, A1, A2 = WR * WR, WG * WG, WB * WB  # the binary64 product of each weight with itself
-LANES, WAVE = 256, 64
+from tile_reduce_ref import A0, A1, A2, LANES, WAVE, WB, WG, WR, combine, moments, rect_sums, same_bits  # noqa: F401 — the order, and the names callers know
+
 N_WEIGHTS = 260
 BELOW, ABOVE, ZERO, NEGATIVE, NOT_FINITE = 256, 257, 258, 259, 260  # the luminance histogram's side counters, in its order
 
@@ -33,15 +32,8 @@ def pixels(s, q, n, weights):
     s, q = np.asarray(s, dtype=np.float64).reshape(-1, 3), np.asarray(q, dtype=np.float64).reshape(-1, 3)
     weights = np.asarray(weights, dtype=np.float64)
     assert weights.shape == (N_WEIGHTS,)
+    valid, Y, V = moments(s, q, n)
     with np.errstate(all="ignore"):
-        valid = (np.isfinite(s).all(axis=1) & np.isfinite(q).all(axis=1)) if n >= 2 else np.zeros(len(s), dtype=bool)
-        nd = np.float64(n)
-        u = s / nd
-        t = (q - s * u) / (nd - np.float64(1.0))
-        t = np.where(t > 0.0, t, np.float64(0.0))
-        v = t / nd
-        Y = (WR * u[:, 0] + WG * u[:, 1]) + WB * u[:, 2]
-        V = (A0 * v[:, 0] + A1 * v[:, 1]) + A2 * v[:, 2]
         k = counter(Y)
         valid = valid & (k < N_WEIGHTS)  # a luminance that is not finite: the pixel counts as invalid
         w = weights[np.minimum(k, N_WEIGHTS - 1)]
@@ -49,35 +41,13 @@ def pixels(s, q, n, weights):
     return valid, Y, V, E
 
 
-def combine(partials):
-    """256 lane partials -> one value, as the kernel adds them: within each wave of 64 the lanes 32 apart, then 16, 8, 4, 2, 1; then (w0 + w1) + (w2 + w3)."""
-    p = np.array(partials).reshape(LANES // WAVE, WAVE)
-    lane = np.arange(WAVE)
-    off = WAVE // 2
-    with np.errstate(all="ignore"):
-        while off:
-            p = p + p[:, lane ^ off]
-            off //= 2
-        return (p[0, 0] + p[1, 0]) + (p[2, 0] + p[3, 0])
-
-
 def reduce_rect(valid, Y, V, E):
     """One rect from its pixels' values in the rect's row-major order: rmd_tile_weighted's fields as a tuple."""
     n_px = len(valid)
     if n_px == 0:
         return (0.0, 0.0, 0.0, 0.0, 0, 0)
-    rows = -(-n_px // LANES)
-    pad = rows * LANES - n_px
-    grid = lambda a, fill: np.concatenate([a, np.full(pad, fill, dtype=a.dtype)]).reshape(rows, LANES)  # noqa: E731 — [k, t] is pixel t + 256 k
-    ok = grid(valid, False)
-    sums = []
+    sums, n_valid = rect_sums(valid, Y, V, E)
     with np.errstate(all="ignore"):
-        for values in (Y, V, E):
-            vals, acc = grid(values, np.float64(0.0)), np.zeros(LANES, dtype=np.float64)
-            for k in range(rows):  # lane t meets its pixels in the order t, t + 256, ...
-                acc = np.where(ok[k], acc + vals[k], acc)
-            sums.append(combine(acc))
-        n_valid = int(combine(ok.sum(axis=0).astype(np.uint32)))
         n_invalid = n_px - n_valid
         m = np.float64(n_valid)
         mean_y, mean_v, mean_e = [(s / m if n_valid else np.float64(0.0)) for s in sums]
@@ -123,7 +93,3 @@ def display_weights(exposure, gamma, display_floor):
         out[BELOW] = out[ZERO] = out[NEGATIVE] = slope2(y_floor)
         out[ABOVE] = slope2(np.float64(2.0**32))
     return out, y_floor
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a, dtype=np.float64).view(np.uint64), np.ascontiguousarray(b, dtype=np.float64).view(np.uint64))
