@@ -64,7 +64,7 @@ enum {
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
-	                                 rmd_tile_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
+	                                 rmd_tile_error_dual, rmd_tile_weighted_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
 	                                 rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope,
 	                                 rmd_denoise_dual_guided_slope_region, rmd_denoise_dual_select_slope,
 	                                 rmd_denoise_atrous_slope, rmd_denoise_atrous_dual_slope,
@@ -1049,6 +1049,44 @@ rmd_status rmd_tile_weighted_error(rmd_context *ctx, const double *accum_dev, co
  * RMD_ERR_INVALID_ARGUMENT (text through rmd_last_error(NULL)): out_weights NULL; exposure or gamma not finite or not > 0; display_floor not finite or
  * outside (0, 1). */
 rmd_status rmd_display_weights(double exposure, double gamma, double display_floor, double *out_weights /* RMD_LUMA_WEIGHTS */);
+/*
+ * THE DISPLAYED ERROR OF THE FILTERED FRAME, the dual-buffer loop's check by what the viewer sees (an addition within ABI 6: RMD_ABI_VERSION stays 6, no
+ * struct or entry point changes, found by its symbol).  rmd_tile_weighted_error weighs the variance of the RAW sums; this call weighs rmd_denoise_dual's
+ * per-pixel error estimate of the frame that is DELIVERED, by the luminance of that frame.  out_dev: the filtered means (W*H*3 doubles, any
+ * rmd_denoise_dual* or rmd_denoise_atrous_dual* call's out_dev); err_dev: that call's error image (W*H doubles).  The table is rmd_tile_weighted_error's:
+ * RMD_LUMA_WEIGHTS doubles, rmd_display_weights' for the displayed error.  Everything is unfused binary64: every product rounded, the additions as
+ * bracketed.  Per pixel of rect j, with o_0..2 its three doubles of out_dev and e its double of err_dev:
+ *     the pixel is VALID if e is not NaN and o_0, o_1, o_2 are finite.  A pixel that is not dual-valid has err = NaN by rmd_denoise_dual's definition;
+ *         e = +inf is valid (h*h overflows at large scales); a negative e is added as it is
+ *     Y = (0.2126 * o_0 + 0.7152 * o_1) + 0.0722 * o_2                    rmd_luminance_histogram_tiles's luminance, of the filtered means
+ *     k = the counter rmd_luminance_histogram_tiles makes from the 64 bits of Y (rmd_tile_weighted_error states it); a valid pixel whose Y is not
+ *         finite (the means are finite, their weighted sum overflowed) counts as INVALID
+ *     w = weights[k];   E = (w == 0.0) ? 0.0 : w * e                      one rounded product; e may be +inf, and a zero weight still gives 0
+ * Sum order: rmd_tile_weighted_error's, unchanged — the rect's pixels numbered row-major WITHIN THE RECT, lane t of 256 adding Y, e and E of the valid pixels
+ * among i = t, t + 256, ... into three sums that start at +0.0 and counting the valid and the invalid pixels; within each wave of 64 the lanes 32 apart
+ * first, then 16, 8, 4, 2, 1; then the four waves' sums as (w0 + w1) + (w2 + w3).  This gives SY, SV, SE and m = (double)valid.  Then
+ *     mean_luma = m ? SY / m : 0;   mean_variance = m ? SV / m : 0   (the mean of err over the valid pixels);   mean_weighted_variance = m ? SE / m : 0
+ *     rms = sqrt(mean_weighted_variance)
+ * A rect without pixels gives all zeros.  A rect with pixels and invalid > 0 gives rms = +inf, with the means of the valid pixels.  An rms that comes out
+ * NaN (a negative or an inf - inf mean) is reported as +inf.  The means themselves are not guarded: a rect whose err holds negative entries beside +inf, or
+ * sums that overflow both ways, has a NaN mean_variance or mean_weighted_variance; with no negative err in the rect — rmd_denoise_dual's err is a mean of
+ * squares — every term is >= 0 and no field is NaN.  The five fields other than rms are the same bits on every device and on the host; rms passes
+ * through the device's square root.
+ * With all-ones weights and a rect without an invalid pixel, rms is rmd_tile_error_dual's result bit for bit on the same device — the same lanes, the same
+ * combine, 1.0 * e is exact, m is the pixel count, both take the device's square root — and mean_variance is that result's radicand.
+ * What the measure is and is not: err is the mean over the channels of the squared half-difference of the two halves' filtered frames.  As the variance of
+ * the LUMINANCE it is exact for a grey difference and an approximation otherwise.  The measure inherits what rmd_denoise_dual says of err: it reads low
+ * (it sees variance, not the filter's bias), and it ranks tiles.
+ * Rects only have to lie inside the W x H frame; they may overlap or repeat.  weights_host: a HOST array of RMD_LUMA_WEIGHTS; out_host: a HOST array of
+ * n_rects.  RMD_ERR_INVALID_ARGUMENT, all checked before the device is touched, in this order: out_dev or err_dev NULL, width or height 0, or n_rects > 0
+ * with rects, weights_host or out_host NULL; the ranges of out_dev (W*H*3 doubles) and err_dev (W*H doubles) overlapping; a weight that is NaN, infinite
+ * or negative; a rect outside the framebuffer; and only then a NULL context.  n_rects == 0 is RMD_OK with nothing launched.  Synchronous, like
+ * rmd_tile_error_dual, and reports an earlier device fault like it; the call's device scratch (rects, weights, results) stays on the context and grows on
+ * demand; one upload (rects and weights staged together), one launch, one download.  One workgroup per rect: made for the adaptive check's tiles.
+ */
+rmd_status rmd_tile_weighted_error_dual(rmd_context *ctx, const double *out_dev /* W*H*3 means */, const double *err_dev /* W*H */,
+                                        uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
+                                        const double *weights_host /* RMD_LUMA_WEIGHTS */, rmd_tile_weighted *out_host);
 
 /* ---- multi-GPU (no reference counterpart; the reference has no collectives) ---- */
 #define RMD_COMM_ID_BYTES 128

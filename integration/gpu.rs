@@ -178,6 +178,10 @@ extern "C" {
     // out_host n_rects rmd_tile_weighted; rms is what meets the threshold
     fn rmd_tile_weighted_error(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                                rect_counts: *const u32, n_rects: u32, weights_host: *const f64, out_host: *mut rmd_tile_weighted) -> i32;
+    // the displayed error of the FILTERED frame, the check of settings.adaptive_denoised_display_threshold in the C++ mirror: out_dev a dual filter's W*H*3
+    // means, err_dev its W*H error image, the same table and result; rects inside the frame (they may overlap or repeat); rms is what meets the threshold
+    fn rmd_tile_weighted_error_dual(ctx: *mut rmd_context, out_dev: *const f64, err_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
+                                    n_rects: u32, weights_host: *const f64, out_host: *mut rmd_tile_weighted) -> i32;
     // the table that makes rms the displayed error: the squared slope of the tone curve per luminance counter (host only, no context)
     fn rmd_display_weights(exposure: f64, gamma: f64, display_floor: f64, out_weights: *mut f64) -> i32;
 }

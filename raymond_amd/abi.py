@@ -150,7 +150,7 @@ class TileLuma(C.Structure):  # rmd_tile_luma: rmd_tile_luma_error's result for 
 LUMA_WEIGHTS = 260  # RMD_LUMA_WEIGHTS: rmd_tile_weighted_error's table, one weight per counter of rmd_luma_histogram without not_finite
 
 
-class TileWeighted(C.Structure):  # rmd_tile_weighted: rmd_tile_weighted_error's result for one rect, 40 bytes
+class TileWeighted(C.Structure):  # rmd_tile_weighted: rmd_tile_weighted_error's and rmd_tile_weighted_error_dual's result for one rect, 40 bytes
     _fields_ = [
         ("rms", C.c_double),
         ("mean_weighted_variance", C.c_double),

@@ -1,5 +1,6 @@
-// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error and
-// rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, tile_luma.hip and tile_weighted.hip.
+// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error,
+// rmd_tile_weighted_error_dual and rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, tile_luma.hip, tile_weighted.hip and
+// tile_weighted_dual.hip.
 // Every entry point is its argument checks in its own order and then, inside rmd::guarded: the rect checks, the context, one carved scratch block
 // (denoise_host.hpp has the layouts), one upload of the rects, its launcher (launch.hpp) and the wait.
 #define RMD_WITH_HIP 1
@@ -11,6 +12,7 @@
 #include "internal.hpp"
 #include "launch.hpp"
 #include "tile_luma_rule.hpp"
+#include "tile_weighted_dual_rule.hpp"
 #include "tile_weighted_rule.hpp"
 
 namespace rmd {
@@ -559,6 +561,38 @@ rmd_status rmd_tile_weighted_error(rmd_context *ctx, const double *accum_dev, co
 		    return nullptr;
 	    },
 	    [&](const DenoiseInput &in, const double *weights, B *d_out) { return rmd::launch_tile_weighted(ctx->stream, in, weights, reinterpret_cast<A *>(d_out)); });
+}
+
+// The filtered frame's measure: no counts, and the two ranges differ in size, so it is not tile_measure's body; the same order of refusals, the same staged upload
+rmd_status rmd_tile_weighted_error_dual(rmd_context *ctx, const double *out_dev, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects,
+                                        uint32_t n_rects, const double *weights_host, rmd_tile_weighted *out_host) {
+	using A = rmd::TileWeighted;
+	using B = rmd_tile_weighted;
+	const std::string name = "rmd_tile_weighted_error_dual: ";
+	return rmd::guarded(ctx, "rmd_tile_weighted_error_dual", [&] {
+		if (!out_dev || !err_dev || width == 0 || height == 0 || (n_rects && (!rects || !weights_host || !out_host))) return fail(ctx, kInvalid, name + "bad argument");
+		const unsigned __int128 bytes = (unsigned __int128)width * height * sizeof(double);
+		if (any_overlap({{out_dev, bytes * 3u}, {err_dev, bytes}})) return fail(ctx, kInvalid, name + "err_dev must not alias out_dev");
+		for (uint32_t k = 0; weights_host && k < RMD_LUMA_WEIGHTS; k++)
+			if (!(weights_host[k] >= 0.0) || !std::isfinite(weights_host[k])) return fail(ctx, kInvalid, name + "every weight must be finite and >= 0");
+		if (!rmd::rects_inside(rects, n_rects, width, height)) return fail(ctx, kInvalid, name + rmd::kRectOutside);
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		std::vector<unsigned char> staged; // (read by the copy until finish() has waited)
+		if (n_rects != 0) {
+			size_t upload_bytes = 0;
+			Scratch sc; // (the context's block: kept between calls)
+			if (rmd_status s = sc.carve(ctx, rmd::tile_weighted_dual_scratch_layout(n_rects, sizeof(B), RMD_LUMA_WEIGHTS, &upload_bytes), &ctx->tile_weighted_dual_scratch)) return s;
+			staged.assign(upload_bytes, 0);
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartRects], rects, (size_t)n_rects * sizeof(rmd_tile_rect));
+			std::memcpy(staged.data() + sc.layout.offset[rmd::kPartTable], weights_host, (size_t)RMD_LUMA_WEIGHTS * sizeof(double));
+			RMD_HIP(ctx, hipMemcpyAsync(sc.base, staged.data(), upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+			B *d_out = sc.part<B>(rmd::kPartTileErrors);
+			RMD_HIP(ctx, rmd::launch_tile_weighted_dual(ctx->stream, out_dev, err_dev, sc.part<rmd_tile_rect>(rmd::kPartRects), n_rects, width, sc.part<double>(rmd::kPartTable),
+			                                            reinterpret_cast<A *>(d_out)));
+			RMD_HIP(ctx, hipMemcpyAsync(out_host, d_out, (size_t)n_rects * sizeof(B), hipMemcpyDeviceToHost, ctx->stream));
+		}
+		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
+	});
 }
 
 rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,

@@ -126,6 +126,20 @@ inline ScratchLayout tile_measure_scratch_layout(uint32_t n_rects, size_t result
 	return L;
 }
 
+// The block of rmd_tile_weighted_error_dual: kPartRects the rects and kPartTable the RMD_LUMA_WEIGHTS weights, uploaded in one copy of `upload_bytes` from
+// the block's start, then kPartTileErrors the per-rect results.  The measure reads no counts, so the block has none
+inline ScratchLayout tile_weighted_dual_scratch_layout(uint32_t n_rects, size_t result_bytes, size_t n_table, size_t *upload_bytes) {
+	ScratchLayout L;
+	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
+		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
+		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
+	};
+	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartTable, sizeof(double), n_table);
+	*upload_bytes = L.total;
+	part(kPartTileErrors, result_bytes, n_rects);
+	return L;
+}
+
 // ---------------------------------------------------------------- the block tables of the region forms
 // rmd_denoise_dual_region: each region rect cut into tiles of the kernel's own shape (tw x th) from the rect's corner, row by row
 inline std::vector<DualBlock> dual_region_table(const rmd_tile_rect *region, uint32_t n_region, uint32_t tw, uint32_t th) {

@@ -228,6 +228,11 @@ hipError_t launch_tile_luma(hipStream_t stream, const DenoiseInput &in, double f
 // of `in` is read.  The weights are checked by the caller
 struct TileWeighted;
 hipError_t launch_tile_weighted(hipStream_t stream, const DenoiseInput &in, const double *weights, TileWeighted *out);
+// rmd_tile_weighted_error_dual (tile_weighted_dual.hip): out[i] = rect i's result (rmd_tile_weighted's layout) from the filtered frame `out_img` (3 doubles a
+// pixel) and the error image `err` (one), rows W pixels apart, one workgroup per rect; the rects, the RMD_LUMA_WEIGHTS `weights` and `out` are device
+// memory.  The rects and the weights are checked by the caller
+hipError_t launch_tile_weighted_dual(hipStream_t stream, const double *out_img, const double *err, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t W,
+                                     const double *weights, TileWeighted *out);
 hipError_t launch_probe(hipStream_t stream, int op, uint32_t n, const double *in, int in_stride, double *out, int out_stride,
                         const RenderParams &P);
 hipError_t launch_probe_scene(hipStream_t stream, int mode, uint32_t g, uint32_t n, const DevObject *objs, uint32_t n_objects,

@@ -29,6 +29,10 @@
 //                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
 //                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
 //                                                                       the image is rmd_denoise_dual's; T: tiles finish by rmd_tile_error_dual)
+//                                                                    [--adaptive-denoised-display T]   (needs --denoise-dual 1 and --spi, in place of
+//                                                                      --adaptive-denoised: tiles finish when rmd_tile_weighted_error_dual's rms — the filtered
+//                                                                      frame's error after exposure and gamma, under rmd_display_weights' table at the
+//                                                                      --adaptive-display-exposure / -gamma / -floor / -auto-exposure options — is at most T)
 //                                                                    [--denoise-dual-features 1]   (needs --denoise-dual 1: first-hit features guide the dual
 //                                                                      filter, rmd_denoise_dual_guided, with --denoise-feature-k / --denoise-feature-tau)
 //                                                                    [--denoise-dual-select 1]     (needs --denoise-dual 1: per pixel the better of the unguided
@@ -72,6 +76,11 @@
 //                                         over raw W*H*3 f64 sums and sums of squares, under rmd_display_weights' table at EXPOSURE, GAMMA and FLOOR (C99
 //                                         hexadecimal or decimal doubles) or under the 260 raw f64 weights of weights.f64; rects.txt as for despike; prints per
 //                                         rect "rms mean_weighted_variance mean_luma mean_variance valid invalid", doubles as their 64 bits in hexadecimal
+//   raymond_cli tile-weighted-error-dual OUT.f64 ERR.f64 W H rects.txt EXPOSURE GAMMA FLOOR | OUT.f64 ERR.f64 W H rects.txt --weights weights.f64
+//                                         rmd_tile_weighted_error_dual made on the host (raymond::tile_weighted_error_dual_host, from the header the kernel is
+//                                         built from) over the raw W*H*3 f64 filtered means OUT and the W*H f64 error image ERR, under the table as above;
+//                                         rects.txt as for despike, its count column read and ignored; prints per rect
+//                                         "rms mean_weighted_variance mean_luma mean_variance valid invalid", doubles as their 64 bits in hexadecimal
 //   raymond_cli display-weights EXPOSURE GAMMA FLOOR
 //                                         rmd_display_weights: its 260 weights, one per line, as their 64 bits in hexadecimal
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
@@ -300,6 +309,40 @@ int main(int argc, char **argv) {
 			}
 			return 0;
 		}
+		if (argc >= 9 && !std::strcmp(argv[1], "tile-weighted-error-dual")) {
+			const size_t W = (size_t)std::atoll(argv[4]), H = (size_t)std::atoll(argv[5]);
+			std::vector<Vector3> out(W * H);
+			std::vector<double> err(W * H);
+			{
+				std::ifstream f(argv[2], std::ios::binary), g(argv[3], std::ios::binary);
+				if (!f || !f.read(reinterpret_cast<char *>(out.data()), (std::streamsize)(out.size() * sizeof(Vector3)))) throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2]);
+				if (!g || !g.read(reinterpret_cast<char *>(err.data()), (std::streamsize)(err.size() * sizeof(double)))) throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[3]);
+			}
+			std::vector<rmd_tile_rect> rects;
+			std::ifstream rf(argv[6]);
+			for (rmd_tile_rect r; rf >> r.left >> r.top >> r.width >> r.height;) {
+				uint32_t n = 0;
+				rf >> n; // (the sibling's count column: read and ignored)
+				rects.push_back(r);
+			}
+			std::vector<double> weights(RMD_LUMA_WEIGHTS);
+			if (!std::strcmp(argv[7], "--weights")) {
+				std::ifstream f(argv[8], std::ios::binary);
+				if (!f || !f.read(reinterpret_cast<char *>(weights.data()), (std::streamsize)(weights.size() * sizeof(double))))
+					throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[8]);
+			} else {
+				if (argc < 10) throw Error(RMD_ERR_INVALID_ARGUMENT, "tile-weighted-error-dual: EXPOSURE GAMMA FLOOR or --weights FILE");
+				weights = display_weights(std::strtod(argv[7], nullptr), std::strtod(argv[8], nullptr), std::strtod(argv[9], nullptr));
+			}
+			for (const rmd_tile_weighted &t : tile_weighted_error_dual_host(out, err, W, H, rects, weights)) {
+				uint64_t bits[4];
+				const double fields[4] = {t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance};
+				std::memcpy(bits, fields, sizeof(bits));
+				std::printf("%016llx %016llx %016llx %016llx %u %u\n", (unsigned long long)bits[0], (unsigned long long)bits[1], (unsigned long long)bits[2],
+				            (unsigned long long)bits[3], t.valid, t.invalid);
+			}
+			return 0;
+		}
 		if (argc >= 6 && !std::strcmp(argv[1], "tiles")) {
 			for (const rmd_tile_rect &t : generate_tiles(std::atoi(argv[2]), std::atoi(argv[3]), {std::atoi(argv[4]), std::atoi(argv[5])}))
 				std::printf("%u %u %u %u\n", t.left, t.top, t.width, t.height);
@@ -393,6 +436,7 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-dual-atrous")) st.denoise_dual_atrous = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-dual-atrous-region")) st.denoise_dual_atrous_region = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--adaptive-denoised")) st.adaptive_denoised_threshold = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--adaptive-denoised-display")) st.adaptive_denoised_display_threshold = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--adaptive-min")) st.adaptive_min_samples = (size_t)std::strtoull(argv[i + 1], nullptr, 10);
 				else if (!std::strcmp(argv[i], "--denoise-features")) st.denoise_features = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-feature-k")) st.denoise_feature_k = std::atof(argv[i + 1]);

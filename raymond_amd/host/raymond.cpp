@@ -5,6 +5,7 @@
 #include "../csrc/despike_rule.hpp"
 #include "../csrc/luma_bins.hpp"
 #include "../csrc/tile_luma_rule.hpp"
+#include "../csrc/tile_weighted_dual_rule.hpp"
 #include "../csrc/tile_weighted_rule.hpp"
 
 #include <algorithm>
@@ -748,7 +749,10 @@ struct TileWorker : Worker {
 // With denoise_dual_atrous the check is rmd_denoise_atrous_dual on the whole frame, at the same rects, counts and feature buffers; with
 // denoise_dual_atrous_region it is rmd_denoise_atrous_dual_region over the live tiles, which gives the pixels read here the same bytes.
 struct DualWorker : Worker {
+	const bool display; // adaptive_denoised_display_threshold: the check is rmd_tile_weighted_error_dual under the tone curve's weights
 	const bool adaptive;
+	const double threshold; // what a tile's measure has to meet
+	std::vector<double> weights; // display: rmd_display_weights' table — made once, or with adaptive_display_auto_exposure by every check
 	const bool guided; // (without the adaptive check nothing here would read the features: await() renders its own)
 	Frame fbs[6];      // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
 	Frame feat[2];     // guided: the feature sums and sums of squares
@@ -760,7 +764,10 @@ struct DualWorker : Worker {
 	size_t n_half[2] = {0, 0}, done = 0, j = 0;
 
 	DualWorker(TaskHandle::Shared &sh, int device, const Scene &scene, const Settings &st)
-	    : Worker(sh, device, scene, st), adaptive(st.adaptive_denoised_threshold > 0.0), guided(adaptive && st.denoise_dual_features), preview_st(st),
+	    : Worker(sh, device, scene, st), display(st.adaptive_denoised_display_threshold > 0.0), adaptive(st.adaptive_denoised_threshold > 0.0 || display),
+	      threshold(display ? st.adaptive_denoised_display_threshold : st.adaptive_denoised_threshold),
+	      weights(display ? display_weights(st.adaptive_display_exposure, st.adaptive_display_gamma, st.adaptive_display_floor) : std::vector<double>()),
+	      guided(adaptive && st.denoise_dual_features), preview_st(st),
 	      live(generate_tiles(W, H, st.tile_size)) {
 		for (int i = 0; i < (adaptive ? 6 : 4); i++) fbs[i] = frame();
 		for (Frame &f : feat) f = frame(guided, Frame::Features);
@@ -776,7 +783,7 @@ struct DualWorker : Worker {
 			std::vector<rmd_tile_rect> converged, still;
 			std::vector<double> converged_err, still_err;
 			for (size_t k = 0; k < live.size(); k++) {
-				const bool conv = !errors.empty() && errors[k] <= st.adaptive_denoised_threshold;
+				const bool conv = !errors.empty() && errors[k] <= threshold;
 				(conv ? converged : still).push_back(live[k]);
 				if (!errors.empty()) (conv ? converged_err : still_err).push_back(errors[k]);
 			}
@@ -819,13 +826,32 @@ struct DualWorker : Worker {
 		return f;
 	}
 
-	// the live tiles' rmd_tile_error_dual after the filter the settings select; only the live tiles' filtered pixels are read, so they are the filter's region
+	// the live tiles' rmd_tile_error_dual after the filter the settings select; only the live tiles' filtered pixels are read, so they are the filter's region.
+	// With adaptive_denoised_display_threshold: one rmd_tile_weighted_error_dual call's rms on the filtered frame and the error image instead; with
+	// adaptive_display_auto_exposure the table is first made anew from one histogram of the whole frame's RAW sums — S_A with S_B as the second buffer, at the
+	// counts a raw preview of this moment resolves (the region forms leave the filtered frame's finished tiles unwritten)
 	std::vector<double> adaptive_check() {
 		std::vector<double> errors;
 		if (!(adaptive && j % 2 == 0 && done >= st.adaptive_min_samples)) return errors;
 		const FrameCounts f = whole_frame(live);
 		denoise_dual_frame(ctx, st, W, H, fbs, feat[0], feat[1], f.rects, f.a, f.b, live.data(), live.size(), fbs[4], fbs[5]);
 		errors.resize(live.size());
+		if (display) {
+			if (st.adaptive_display_auto_exposure) {
+				rmd_luma_histogram hist;
+				const std::vector<uint32_t> counts = sum_counts(f.a, f.b);
+				check(rmd_luminance_histogram_tiles(ctx, fbs[0], fbs[2], (uint32_t)W, (uint32_t)H, f.rects.data(), counts.data(), (uint32_t)f.rects.size(), &hist), ctx,
+				      "rmd_luminance_histogram_tiles");
+				double exposure = 1.0;
+				check(rmd_exposure_from_histogram(&hist, st.auto_exposure_percentile, st.auto_exposure_target, &exposure), nullptr, "rmd_exposure_from_histogram");
+				weights = display_weights(exposure, st.adaptive_display_gamma, st.adaptive_display_floor);
+			}
+			std::vector<rmd_tile_weighted> weighted(live.size());
+			check(rmd_tile_weighted_error_dual(ctx, fbs[4], fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), weights.data(), weighted.data()), ctx,
+			      "rmd_tile_weighted_error_dual");
+			for (size_t k = 0; k < weighted.size(); k++) errors[k] = weighted[k].rms;
+			return errors;
+		}
 		check(rmd_tile_error_dual(ctx, fbs[5], (uint32_t)W, (uint32_t)H, live.data(), (uint32_t)live.size(), errors.data()), ctx, "rmd_tile_error_dual");
 		return errors;
 	}
@@ -979,6 +1005,16 @@ std::string check_settings(const Settings &st) {
 	if (st.adaptive_denoised_threshold > 0.0 && st.adaptive_threshold > 0.0) return "adaptive_denoised_threshold and adaptive_threshold are mutually exclusive";
 	if (st.denoise_dual && st.adaptive_measure != "channel_max") return "adaptive_measure cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual";
 	if (st.denoise_dual && st.adaptive_display_threshold > 0.0) return "adaptive_display_threshold cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual";
+	if (!(st.adaptive_denoised_display_threshold >= 0.0) || !std::isfinite(st.adaptive_denoised_display_threshold))
+		return "adaptive_denoised_display_threshold must be finite and >= 0 (0 = off)";
+	if (st.adaptive_denoised_display_threshold > 0.0 && st.samples_per_iteration == 0)
+		return "adaptive_denoised_display_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)";
+	if (st.adaptive_denoised_display_threshold > 0.0 && !st.denoise_dual)
+		return "adaptive_denoised_display_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)";
+	if (st.adaptive_denoised_display_threshold > 0.0 && st.adaptive_denoised_threshold > 0.0)
+		return "adaptive_denoised_display_threshold and adaptive_denoised_threshold are mutually exclusive";
+	if (st.adaptive_denoised_display_threshold > 0.0 && st.adaptive_threshold > 0.0)
+		return "adaptive_denoised_display_threshold and adaptive_threshold are mutually exclusive";
 	if (st.adaptive_display_threshold > 0.0 && st.adaptive_display_auto_exposure && st.worker_count > 1)
 		return "adaptive_display_auto_exposure renders on one device: every check histograms the whole frame";
 	if (st.denoise_dual && st.worker_count > 1) return "denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own";
@@ -1254,6 +1290,21 @@ std::vector<rmd_tile_weighted> tile_weighted_error_host(const std::vector<Vector
 		return rmd_tile_weighted{t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance, t.valid, t.invalid};
 	};
 	return tile_measure_host<rmd_tile_weighted>("tile_weighted_error_host", sums, sums_sq, width, height, rects, counts, weights.size() != RMD_LUMA_WEIGHTS, measure);
+}
+
+std::vector<rmd_tile_weighted> tile_weighted_error_dual_host(const std::vector<Vector3> &out, const std::vector<double> &err, size_t width, size_t height,
+                                                             const std::vector<rmd_tile_rect> &rects, const std::vector<double> &weights) {
+	const std::string name = "tile_weighted_error_dual_host";
+	if (out.size() != width * height || err.size() != width * height || weights.size() != RMD_LUMA_WEIGHTS) throw Error(RMD_ERR_INVALID_ARGUMENT, name + ": bad argument");
+	std::vector<rmd_tile_weighted> result(rects.size());
+	const double *O = out.empty() ? nullptr : out[0].data();
+	for (size_t j = 0; j < rects.size(); j++) {
+		const rmd_tile_rect &r = rects[j];
+		if ((size_t)r.left + r.width > width || (size_t)r.top + r.height > height) throw Error(RMD_ERR_INVALID_ARGUMENT, name + ": tile rectangle outside the framebuffer");
+		const rmd::TileWeighted t = rmd::tile_weighted_dual_rect_host(O, err.data(), (uint32_t)width, r.left, r.top, r.width, r.height, weights.data());
+		result[j] = rmd_tile_weighted{t.rms, t.mean_weighted_variance, t.mean_luma, t.mean_variance, t.valid, t.invalid};
+	}
+	return result;
 }
 
 std::vector<double> display_weights(double exposure, double gamma, double display_floor) {

@@ -196,6 +196,12 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// rmd_tile_error_dual — an absolute RMS in linear radiance that reads low — is at most the threshold is finished at the samples it has.
 	double adaptive_denoised_threshold = 0.0;
 	size_t adaptive_min_samples = 32;
+	// Adaptive sampling by the DISPLAYED error of the filtered frame (needs denoise_dual and samples_per_iteration > 0, excludes
+	// adaptive_denoised_threshold > 0 and adaptive_threshold > 0; 0 = off): the same checks at the same passes, but after the filter call one
+	// rmd_tile_weighted_error_dual call over the live tiles — the filter's error image weighted, by the filtered frame's luminance, under rmd_display_weights'
+	// table at adaptive_display_exposure, adaptive_display_gamma and adaptive_display_floor (adaptive_display_auto_exposure: at the exposure every check's own
+	// histogram of the whole frame's raw sums asks for) — and a tile whose rms is at most the threshold is finished.  A fraction of the display's full scale.
+	double adaptive_denoised_display_threshold = 0.0;
 	// Frame previews during a progressive render (needs samples_per_iteration > 0; 0 = off): after every preview_every-th pass that leaves the render
 	// unfinished — the passes after which TileProgressed is sent — one Message::FramePreview follows that pass's TileProgressed messages: the whole frame
 	// as W*H*3 bytes, every tile resolved and tone-mapped on the GPU at its own sample count (rmd_resolve_tonemap_tiles) with preview_exposure and
@@ -374,6 +380,11 @@ std::vector<rmd_tile_luma> tile_luma_error_host(const std::vector<Vector3> &sums
 // the sizes; rects are inside the frame.  What raymond_cli tile-weighted-error runs, and what holds the header to the numpy restatement without a GPU
 std::vector<rmd_tile_weighted> tile_weighted_error_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
                                                         const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, const std::vector<double> &weights);
+// rmd_tile_weighted_error_dual on the host, from the header the kernel is built from (raymond_amd/csrc/tile_weighted_dual_rule.hpp): rect i of the
+// width * height filtered means `out` and error image `err`, under `weights` (RMD_LUMA_WEIGHTS entries).  No argument is checked beyond the sizes; rects
+// are inside the frame.  What raymond_cli tile-weighted-error-dual runs, and what holds the header to the numpy restatement without a GPU
+std::vector<rmd_tile_weighted> tile_weighted_error_dual_host(const std::vector<Vector3> &out, const std::vector<double> &err, size_t width, size_t height,
+                                                             const std::vector<rmd_tile_rect> &rects, const std::vector<double> &weights);
 // rmd_display_weights: the RMD_LUMA_WEIGHTS weights of the displayed error at an exposure, a gamma and a display floor; throws for arguments it refuses
 std::vector<double> display_weights(double exposure, double gamma, double display_floor);
 // await() with settings.despike alone: the finished tiles' sums and sums of squares assembled, despiked on `device` (rmd_despike) and divided by each

@@ -189,6 +189,10 @@ SIGNATURES = {
         C.c_int32,
         [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, _P(C.c_double), _P(abi.TileWeighted)],
     ),
+    "rmd_tile_weighted_error_dual": (
+        C.c_int32,
+        [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), C.c_uint32, _P(C.c_double), _P(abi.TileWeighted)],
+    ),
     "rmd_display_weights": (C.c_int32, [C.c_double, C.c_double, C.c_double, _P(C.c_double)]),
     "rmd_comm_prepare_process": (C.c_int32, []),
     "rmd_comm_unique_id": (C.c_int32, [_vp]),

@@ -2,7 +2,7 @@
 
 Bottom up:
   * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, tile_weighted_error, display_weights, despike, the denoise family (every rmd_denoise* call is laid out
+  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike, the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -588,6 +588,17 @@ def tile_error_dual(ctx, error_image, tiles):
     return out[: len(tiles)]
 
 
+def tile_weighted_error_dual(ctx, out_fb, err_img, tiles, weights):
+    """rmd_tile_weighted_error_dual: per tile, `err_img` (a dual filter's per-pixel error estimate) weighted by `weights` — abi.LUMA_WEIGHTS doubles, a
+    pixel taking the entry the luminance of its filtered means in `out_fb` names — as the structured array tile_weighted_error returns; rms is +inf for a
+    tile with a pixel that is not dual-valid.  display_weights() makes the table of the displayed error.  Tiles may overlap or repeat."""
+    tiles = list(tiles)
+    out = np.zeros(max(1, len(tiles)), dtype=TILE_WEIGHTED_DTYPE)
+    ctx.check(ctx.L.rmd_tile_weighted_error_dual(ctx.handle, out_fb.ptr, err_img.ptr, out_fb.width, out_fb.height, tile_array(tiles), len(tiles),
+                                                 _weights(weights).ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(abi.TileWeighted))))
+    return out[: len(tiles)]
+
+
 def resolve_tonemap(ctx, framebuffer, sample_count, exposure=1.0, gamma=2.2):
     """TaskHandle::await's divide + cli_old's tone-map/gamma/u8 cast (cli_old/src/main.rs:161-181) -> (H, W, 3) uint8."""
     out = np.empty((framebuffer.height, framebuffer.width, 3), dtype=np.uint8)
@@ -1105,7 +1116,11 @@ class _DualLoop:
         st = self.st = settings
         cam = st.camera_settings
         W, H = self.W, self.H = cam.backbuffer_width, cam.backbuffer_height
-        self.adaptive = st.adaptive_denoised_threshold > 0.0
+        self.display = st.adaptive_denoised_display_threshold > 0.0  # the check is rmd_tile_weighted_error_dual under the tone curve's weights
+        self.adaptive = st.adaptive_denoised_threshold > 0.0 or self.display
+        self.threshold = st.adaptive_denoised_display_threshold if self.display else st.adaptive_denoised_threshold  # what a tile's measure has to meet
+        # with a fixed exposure the weights are made once; with adaptive_display_auto_exposure every check makes its own (check_weights)
+        self.weights = display_weights(st.adaptive_display_exposure, st.adaptive_display_gamma, st.adaptive_display_floor) if self.display else None
         ctx = self.ctx = stack.enter_context(Context(device))
         self.ds = stack.enter_context(DeviceScene(ctx, scene))
         self.fbs = [stack.enter_context(Framebuffer(ctx, W, H)) for _ in range(4)]  # S_A, Q_A, S_B, Q_B
@@ -1145,8 +1160,19 @@ class _DualLoop:
         else:
             denoise_dual(self.ctx, *halves, rects, all_a, all_b, out_fb, err_img, **where, **st.nlm_keywords(), **guide)
 
+    def check_weights(self):
+        """adaptive_display_auto_exposure: before a check, one histogram of the whole frame on the RAW sums — S_A with S_B as the second buffer, live tiles at
+        n_A + n_B, finished ones at the counts they finished with: what a raw preview of this moment resolves; the region forms leave the filtered
+        frame's finished tiles unwritten — and the weights are the tone curve's at the exposure it asks for."""
+        st = self.st
+        rects, all_a, all_b = self.whole_frame(self.live)
+        hist = luminance_histogram(self.ctx, self.fbs[0], rects, [a + b for a, b in zip(all_a, all_b)], self.fbs[2])
+        exposure = exposure_from_histogram(hist, st.auto_exposure_percentile, st.auto_exposure_target)
+        self.weights = display_weights(exposure, st.adaptive_display_gamma, st.adaptive_display_floor)
+
     def adaptive_check(self):
-        """rmd_tile_error_dual of the live tiles after the settings' filter, or None each when no check is due."""
+        """rmd_tile_error_dual of the live tiles after the settings' filter — with adaptive_denoised_display_threshold one rmd_tile_weighted_error_dual call's
+        rms on the filtered frame and the error image instead —, or None each when no check is due."""
         st = self.st
         if not (self.adaptive and self.passes % 2 == 0 and self.done >= st.adaptive_min_samples):
             return [None] * len(self.live)
@@ -1154,6 +1180,10 @@ class _DualLoop:
             self.filter_whole_frame(self.live, self.out_fb, self.err_img, True, **(dict(region=self.live) if st.denoise_dual_atrous_region else {}))
         else:  # only the live tiles' filtered pixels are read below: the region form writes those, with the whole-frame call's bytes
             self.filter_whole_frame(self.live, self.out_fb, self.err_img, False, region=self.live)
+        if self.display:
+            if st.adaptive_display_auto_exposure:
+                self.check_weights()
+            return tile_weighted_error_dual(self.ctx, self.out_fb, self.err_img, self.live, self.weights)["rms"]
         return tile_error_dual(self.ctx, self.err_img, self.live)
 
     def finish(self, rects, errors=None):
@@ -1193,7 +1223,7 @@ class _DualLoop:
             self.render_pass(min(st.samples_per_iteration, st.sample_count - self.done))
             if self.done < st.sample_count:
                 errors = self.adaptive_check()
-                conv = [e is not None and e <= st.adaptive_denoised_threshold for e in errors]
+                conv = [e is not None and e <= self.threshold for e in errors]
                 self.finish([r for r, c in zip(self.live, conv) if c], [float(e) for e, c in zip(errors, conv) if c])  # converged: finished at the samples they have
                 still = [r for r, c in zip(self.live, conv) if not c]
                 if still and st.progress_tiles:
@@ -1214,6 +1244,12 @@ def _render_tiled_dual(scene, settings, devices):
     adaptive_min_samples samples, rmd_denoise_dual_region filters the live tiles' pixels of the whole frame (finished tiles at the counts they
     finished with: the bytes rmd_denoise_dual would give those pixels), rmd_tile_error_dual runs over the live tiles, and a live tile at or below the
     threshold is sent as TileFinished, with that error, and takes no further passes.
+
+    With settings.adaptive_denoised_display_threshold > 0 (instead of adaptive_denoised_threshold) the same filter call is followed by one
+    rmd_tile_weighted_error_dual call over the live tiles on the filtered frame and the error image, under rmd_display_weights' table at
+    adaptive_display_exposure, gamma and floor — the filtered tile's RMS error after exposure and gamma, in fractions of the display's full scale —, and its
+    rms is what meets the threshold and what the tile carries.  With adaptive_display_auto_exposure every check first histograms the whole frame's RAW sums
+    (S_A with S_B as the second buffer, at the counts a raw preview would resolve) and makes the weights at the exposure that histogram asks for.
 
     With settings.denoise_dual_features the adaptive check needs the features: two feature buffers beside the four, into which rmd_render_features
     adds, after each pass, the live tiles' first-hit features of the same samples [done, done + n), so a tile's features hold count_a + count_b

@@ -252,7 +252,7 @@ class Settings:
                  auto_exposure_percentile=0.99, auto_exposure_target=0.8, denoise_feature_slope=0.0,
                  denoise_atrous_slope=0.0, despike=False, despike_radius=2, despike_rank=2, despike_k=6.0, despike_ratio=2.0, despike_floor=0.0,
                  adaptive_measure="channel_max", adaptive_display_threshold=0.0, adaptive_display_exposure=1.0, adaptive_display_gamma=2.2,
-                 adaptive_display_floor=1.0 / 255.0, adaptive_display_auto_exposure=False):
+                 adaptive_display_floor=1.0 / 255.0, adaptive_display_auto_exposure=False, adaptive_denoised_display_threshold=0.0):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -323,6 +323,13 @@ class Settings:
         # radiance that reads low (raymond_hip.h) — is at most the threshold is finished at the samples it has.
         self.adaptive_denoised_threshold = float(adaptive_denoised_threshold)
         self.adaptive_min_samples = adaptive_min_samples
+        # Adaptive sampling by the DISPLAYED error of the filtered frame (0.0 = off; needs denoise_dual and samples_per_iteration > 0, excludes
+        # adaptive_denoised_threshold > 0 and adaptive_threshold > 0): the same checks at the same passes, but after the filter call one
+        # rmd_tile_weighted_error_dual call over the live tiles — the filter's error image weighted, by the filtered frame's luminance, under
+        # rmd_display_weights' table at adaptive_display_exposure, adaptive_display_gamma and adaptive_display_floor (adaptive_display_auto_exposure: at the
+        # exposure every check's own histogram of the whole frame's raw sums asks for) — and a tile whose rms is at most the threshold is finished.  The
+        # threshold is a fraction of the display's full scale: 1 / 255 is one 8-bit level.
+        self.adaptive_denoised_display_threshold = float(adaptive_denoised_display_threshold)
         # Feature weights in the dual-buffer filter (False = off; needs denoise_dual): the filter is rmd_denoise_dual_guided, with the first-hit
         # features at count_a + count_b samples per tile, k_f = denoise_feature_k and tau = denoise_feature_tau; the adaptive check is its region form.
         self.denoise_dual_features = bool(denoise_dual_features)
@@ -522,6 +529,16 @@ class Settings:
             raise ValueError("adaptive_measure cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual")
         if self.denoise_dual and self.adaptive_display_threshold > 0.0:
             raise ValueError("adaptive_display_threshold cannot be combined with denoise_dual: the dual loop's check is rmd_tile_error_dual")
+        if not (self.adaptive_denoised_display_threshold >= 0.0 and np.isfinite(self.adaptive_denoised_display_threshold)):
+            raise ValueError("adaptive_denoised_display_threshold must be finite and >= 0 (0 = off)")
+        if self.adaptive_denoised_display_threshold > 0.0 and self.samples_per_iteration == 0:
+            raise ValueError("adaptive_denoised_display_threshold > 0 needs samples_per_iteration > 0 (the error is checked between passes)")
+        if self.adaptive_denoised_display_threshold > 0.0 and not self.denoise_dual:
+            raise ValueError("adaptive_denoised_display_threshold > 0 needs denoise_dual (the error is that of the dual-buffer filter)")
+        if self.adaptive_denoised_display_threshold > 0.0 and self.adaptive_denoised_threshold > 0.0:
+            raise ValueError("adaptive_denoised_display_threshold and adaptive_denoised_threshold are mutually exclusive")
+        if self.adaptive_denoised_display_threshold > 0.0 and self.adaptive_threshold > 0.0:
+            raise ValueError("adaptive_denoised_display_threshold and adaptive_threshold are mutually exclusive")
 
     def check_preview(self, n_devices=1):
         """Raises ValueError for preview settings render_tiled cannot follow on `n_devices` devices."""

@@ -3,6 +3,8 @@
 
     python tools/adaptive_measures.py table [--scene spheres|mesh] [--out profiles/r25_tile_weighted/table_spheres.json]
     python tools/adaptive_measures.py time  [--runs 15] [--out profiles/r25_tile_weighted/call_time.json]
+    python tools/adaptive_measures.py dual-table [--out profiles/r27_tile_weighted_dual/table_dual.json]
+    python tools/adaptive_measures.py dual-time  [--runs 15] [--out profiles/r27_tile_weighted_dual/call_time.json]
 
 table: the scene at 1920x1080, up to 256 spp in passes of 16, 2,040 tiles of 32 x 32; RMSE against a 2,048 spp frame of another seed.  ONE progressive
 render is made, every tile live to the end.  After every pass the three measures of every tile are taken (rmd_tile_error, and rmd_tile_luma_error's
@@ -19,8 +21,20 @@ radiance, and the RMSE in display space — the frame's and the reference's pixe
 values as 0) — each beside the uniform frame's.
 
 time: 2,040 tiles at one count on a 16 spp frame; rmd_tile_luma_error and rmd_tile_error on the same list, alternated, HIP events around the whole
-synchronous call, medians of `runs` after a warm-up, min - max; rmd_tile_weighted_error under the same display table is alternated with them on the same list."""
+synchronous call, medians of `runs` after a warm-up, min - max; rmd_tile_weighted_error under the same display table is alternated with them on the same list.
+
+dual-table: the two rules of the dual-buffer loop at DESIGN.md section 13's set-up — both bundled scenes at 256x144, 5 bounces, 32 x 32 tiles, passes of 8,
+at most 128 spp, no check below 32, against a 2,048 spp frame of seed + 1.  Settings.adaptive_denoised_threshold runs at the 30 %, 50 % and 70 % quantile
+of its own measure at the first check; Settings.adaptive_denoised_display_threshold (exposure 1, gamma 2.2, floor 1 / 255) is then bisected to the threshold
+whose mean samples per pixel comes closest to that point's.  Each cell: tiles stopped early, mean spp, and the RMSE of the DELIVERED (filtered) frame against
+the reference, in linear radiance and in display space, each over the uniform dual-buffer frame at the mean spp rounded to a whole pass.  A display-space
+RMSE under the rule's own curve favours the rule, and err sees variance and not the filter's bias: both columns are filtered frames, whose error is partly
+bias no threshold on err controls.
+
+dual-time: 2,040 tiles on a 1080p frame filtered by rmd_denoise_atrous_dual at 8 + 8 spp; rmd_tile_weighted_error_dual, rmd_tile_error_dual and
+rmd_tile_weighted_error on the same list, alternated, as `time` times its calls."""
 import argparse
+import contextlib
 import ctypes as C
 import json
 import os
@@ -278,14 +292,171 @@ def call_time(a):
     return result
 
 
+DW, DH, DSPI, DMAX, DMIN = 256, 144, 8, 128, 32  # DESIGN.md section 13's set-up
+
+
+def dual_table(a):
+    import numpy as np
+
+    from raymond_amd import lib, render, scenes
+    from raymond_amd.scene import Settings, generate_tiles
+
+    lib.load()
+    cam = scenes.camera(DW, DH)
+    tiles = generate_tiles(DW, DH, (32, 32))
+    result = {"display": DISPLAY, "width": DW, "height": DH, "bounces": BOUNCES, "max_spp": DMAX, "pass": DSPI, "adaptive_min_samples": DMIN, "reference_spp": REF_SPP,
+              "tiles": len(tiles), "library": os.path.relpath(lib.LIB_PATH, ROOT), "scenes": {}}
+    t0 = time.perf_counter()
+
+    def settings(spp, **kw):
+        return Settings(cam, sample_count=spp, tile_size=(32, 32), bounce_limit=BOUNCES, seed=scenes.SEED, samples_per_iteration=DSPI, denoise=True, denoise_dual=True,
+                        progress_tiles=False, **kw)
+
+    def rule(name, threshold):
+        if name == "denoised":
+            return dict(adaptive_denoised_threshold=threshold, adaptive_min_samples=DMIN)
+        return dict(adaptive_denoised_display_threshold=threshold, adaptive_min_samples=DMIN, adaptive_display_exposure=DISPLAY["exposure"],
+                    adaptive_display_gamma=DISPLAY["gamma"], adaptive_display_floor=DISPLAY["display_floor"])
+
+    for scene_name, scene in (("spheres", scenes.reflective_spheres()), ("mesh", scenes.gold_dragon_standin(n=24))):
+        with render.Context(0) as ctx, render.DeviceScene(ctx, scene) as ds, render.Framebuffer(ctx, DW, DH) as fb:
+            ref_st = Settings(cam, sample_count=REF_SPP, bounce_limit=BOUNCES, seed=scenes.SEED + 1)
+            render.render_tiles(ctx, ds, cam, ref_st, tiles, fb, 0, REF_SPP)
+            reference = fb.download() / float(REF_SPP)
+
+        def run(name, threshold):
+            handle = render.render_tiled(scene, settings(DMAX, **rule(name, threshold)))
+            done = [m.tile for m in handle._messages if m.kind == "TileFinished"]
+            frame = handle.await_()
+            mean_spp = sum(t.sample_count * t.width * t.height for t in done) / float(DW * DH)
+            return {"threshold": threshold, "tiles_stopped_early": sum(t.sample_count < DMAX for t in done), "mean_spp": mean_spp, "rmse": rmse(frame, reference),
+                    "display_rmse": rmse_display(frame, reference)}, done
+
+        uniform_cache = {}
+
+        def uniform(spp):
+            if spp not in uniform_cache:
+                frame = render.render_tiled(scene, settings(spp)).await_()
+                uniform_cache[spp] = (rmse(frame, reference), rmse_display(frame, reference))
+            return uniform_cache[spp]
+
+        def against_uniform(row):
+            spp_u = max(DSPI * 2, int(round(row["mean_spp"] / DSPI)) * DSPI)
+            row["uniform_spp"], (row["uniform_rmse"], row["uniform_display_rmse"]) = spp_u, uniform(spp_u)
+            row["rmse_over_uniform"], row["display_rmse_over_uniform"] = row["rmse"] / row["uniform_rmse"], row["display_rmse"] / row["uniform_display_rmse"]
+            return row
+
+        first = {}
+        for name in ("denoised", "display"):  # the first check's measure of every tile: under a threshold everything meets every tile stops there and carries it
+            probe = render.render_tiled(scene, settings(DMIN + 2 * DSPI, **rule(name, 1e300)))
+            seen = np.array([np.inf if m.tile.error is None else m.tile.error for m in probe._messages if m.kind == "TileFinished"], dtype=np.float64)
+            first[name] = seen[np.isfinite(seen)]  # (a tile with a pixel that is not dual-valid reads +inf and never stops: it takes no part in the quantiles)
+            assert len(seen) == len(tiles) and len(first[name]) >= len(tiles) // 2
+        rows = []
+        for q in (0.3, 0.5, 0.7):
+            row, _ = run("denoised", float(np.quantile(first["denoised"], q)))
+            lo, hi = float(first["display"].min()) * 0.25, float(first["display"].max()) * 4.0
+            best = None
+            for _ in range(9):  # mean spp falls as the threshold rises: bisection in the logarithm
+                mid = float(np.sqrt(lo * hi))
+                cand, _ = run("display", mid)
+                if best is None or abs(cand["mean_spp"] - row["mean_spp"]) < abs(best["mean_spp"] - row["mean_spp"]):
+                    best = cand
+                if cand["mean_spp"] > row["mean_spp"]:
+                    lo = mid
+                else:
+                    hi = mid
+            rows.append({"quantile": q, "denoised": against_uniform(row), "display": against_uniform(best)})
+            for name in ("denoised", "display"):
+                r = rows[-1][name]
+                print("%-8s %-9s threshold %-12.6g stopped %3d  mean spp %6.1f  rmse %.6f  uniform at %3d spp %.6f  ratio %.4f  display rmse %.6f  uniform %.6f  ratio %.4f" % (
+                    scene_name, name, r["threshold"], r["tiles_stopped_early"], r["mean_spp"], r["rmse"], r["uniform_spp"], r["uniform_rmse"], r["rmse_over_uniform"],
+                    r["display_rmse"], r["uniform_display_rmse"], r["display_rmse_over_uniform"]), flush=True)
+        result["scenes"][scene_name] = {"rows": rows, "first_check_median": {n: float(np.median(v)) for n, v in first.items()}}
+        print(scene_name, "done, %.1f s" % (time.perf_counter() - t0), flush=True)
+    result["seconds"] = time.perf_counter() - t0
+    return result
+
+
+def dual_call_time(a):
+    import numpy as np
+
+    import tile_weighted_dual_ref
+    from raymond_amd import abi, lib, render, scenes
+    from raymond_amd.scene import Settings, generate_tiles, tile_array
+
+    lib.load()
+    hip = Hip()
+    half = 8
+    st = Settings(scenes.camera(W, H), sample_count=2 * half, bounce_limit=BOUNCES, seed=scenes.SEED)
+    tiles = generate_tiles(W, H, (32, 32))
+    result = {"width": W, "height": H, "spp": 2 * half, "tiles": len(tiles), "library": os.path.relpath(lib.LIB_PATH, ROOT), "filter": "rmd_denoise_atrous_dual",
+              "how": "HIP events on the context's stream around the whole synchronous call (event), and the wall clock (wall); alternated, medians"}
+    stream = hip.stream()
+    with contextlib.ExitStack() as stack:
+        ctx = stack.enter_context(render.Context(0, stream=stream.value))
+        ds = stack.enter_context(render.DeviceScene(ctx, scenes.reflective_spheres()))
+        fbs = [stack.enter_context(render.Framebuffer(ctx, W, H)) for _ in range(5)]  # S_A, Q_A, S_B, Q_B, the filtered frame
+        err = stack.enter_context(render.ErrorImage(ctx, W, H))
+        for k in range(2):
+            render.render_tiles(ctx, ds, st.camera_settings, st, tiles, fbs[2 * k], k * half, half, framebuffer_sq=fbs[2 * k + 1])
+        render.denoise_atrous_dual(ctx, (fbs[0], fbs[1]), (fbs[2], fbs[3]), tiles, [half] * len(tiles), [half] * len(tiles), fbs[4], err, **st.atrous_keywords())
+        weights = render.display_weights(**DISPLAY)
+        # held to the restatement first, on the frame's first 64 tiles
+        some = tiles[:64]
+        got = render.tile_weighted_error_dual(ctx, fbs[4], err, some, weights)
+        want = tile_weighted_dual_ref.tile_weighted_error_dual(fbs[4].download(), err.download(), some, weights)
+        for name in ("valid", "invalid", "mean_luma", "mean_variance", "mean_weighted_variance"):
+            assert got[name].tobytes() == want[name].tobytes(), name
+        ones = render.tile_weighted_error_dual(ctx, fbs[4], err, tiles, np.ones(abi.LUMA_WEIGHTS))
+        assert ones["rms"].tobytes() == render.tile_error_dual(ctx, err, tiles).tobytes()  # the tie, on a rendered frame
+        arr = tile_array(tiles)
+        counts = np.full(len(tiles), half, dtype=np.uint32)
+        cptr = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        out_dual, out_raw = np.zeros(len(tiles), dtype=render.TILE_WEIGHTED_DTYPE), np.zeros(len(tiles), dtype=render.TILE_WEIGHTED_DTYPE)
+        out_err = np.zeros(len(tiles))
+        wptr = weights.ctypes.data_as(C.POINTER(C.c_double))
+
+        def weighted_dual():
+            ctx.check(ctx.L.rmd_tile_weighted_error_dual(ctx.handle, fbs[4].ptr, err.ptr, W, H, arr, len(tiles), wptr, out_dual.ctypes.data_as(C.POINTER(abi.TileWeighted))))
+
+        def error_dual():
+            ctx.check(ctx.L.rmd_tile_error_dual(ctx.handle, err.ptr, W, H, arr, len(tiles), out_err.ctypes.data_as(C.c_void_p)))
+
+        def weighted():
+            ctx.check(ctx.L.rmd_tile_weighted_error(ctx.handle, fbs[0].ptr, fbs[1].ptr, W, H, arr, cptr, len(tiles), wptr, out_raw.ctypes.data_as(C.POINTER(abi.TileWeighted))))
+
+        fns = {"rmd_tile_weighted_error_dual": weighted_dual, "rmd_tile_error_dual": error_dual, "rmd_tile_weighted_error": weighted}
+        for fn in fns.values():
+            fn(), fn()  # warm-up: code objects, the context's scratch
+        start, stop = hip.event(), hip.event()
+        ev, wall = {n: [] for n in fns}, {n: [] for n in fns}
+        for r in range(a.runs):
+            for name in (list(fns) if r % 2 == 0 else list(reversed(fns))):  # alternated: drift falls on both alike
+                e, w = hip.timed(stream, start, stop, fns[name])
+                ev[name].append(e), wall[name].append(w)
+        result["calls"] = {n: {"event": stats(ev[n]), "wall": stats(wall[n])} for n in fns}
+        for n, v in result["calls"].items():
+            print("%-28s event %.3f ms (min %.3f, max %.3f)  wall %.3f ms" % (n, v["event"]["median_ms"], v["event"]["min_ms"], v["event"]["max_ms"], v["wall"]["median_ms"]),
+                  flush=True)
+        base = result["calls"]["rmd_tile_error_dual"]["event"]["median_ms"]
+        result["weighted_dual_over_error_dual"] = result["calls"]["rmd_tile_weighted_error_dual"]["event"]["median_ms"] / base
+        result["weighted_over_error_dual"] = result["calls"]["rmd_tile_weighted_error"]["event"]["median_ms"] / base
+        result["bytes_read_per_pixel"] = {"rmd_tile_weighted_error_dual": 32, "rmd_tile_error_dual": 8, "rmd_tile_weighted_error": 48}
+        result["medians_of_the_frame"] = {"rmd_tile_error_dual": float(np.median(out_err)), "display_rms_filtered": float(np.median(out_dual["rms"])),
+                                          "display_rms_raw_half": float(np.median(out_raw["rms"]))}
+        print(json.dumps({k: result[k] for k in ("weighted_dual_over_error_dual", "weighted_over_error_dual", "medians_of_the_frame")}), flush=True)
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("table", "time"))
+    ap.add_argument("what", choices=("table", "time", "dual-table", "dual-time"))
     ap.add_argument("--scene", choices=("spheres", "mesh"), default="spheres")
     ap.add_argument("--runs", type=int, default=15)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    result = table(a) if a.what == "table" else call_time(a)
+    result = {"table": table, "time": call_time, "dual-table": dual_table, "dual-time": dual_call_time}[a.what](a)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
