@@ -1,12 +1,10 @@
 // C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error,
-// rmd_tile_weighted_error_dual and rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, tile_luma.hip, tile_weighted.hip and
-// tile_weighted_dual.hip.
+// rmd_tile_weighted_error_dual, rmd_tile_error and rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, tile_luma.hip,
+// tile_weighted.hip, tile_weighted_dual.hip and, rmd_tile_error's, kernels.hip.
 // Every entry point is its argument checks in its own order and then, inside rmd::guarded: the rect checks, the context, one carved scratch block
 // (denoise_host.hpp has the layouts), one upload of the rects, its launcher (launch.hpp) and the wait.
 #define RMD_WITH_HIP 1
 #include <hip/hip_runtime.h> // (tile_reduce.hpp's combine, which the rule headers bring along under hipcc, names the device runtime)
-
-#include <initializer_list>
 
 #include "despike_rule.hpp"
 #include "internal.hpp"
@@ -16,13 +14,6 @@
 #include "tile_weighted_rule.hpp"
 
 namespace rmd {
-// Every rect lies inside the frame (64-bit sums: left + width may pass 2^32), and what a call says when one does not
-static const char *const kRectOutside = "tile rectangle outside the framebuffer";
-static bool rects_inside(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height) {
-	for (uint32_t i = 0; i < n_rects; i++)
-		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height) return false;
-	return true;
-}
 // Rects inside the frame and pairwise disjoint (rects without pixels cover nothing): sorted by left edge, each rect is compared with the ones that
 // start before it ends.
 bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height, const char **why) {
@@ -46,6 +37,7 @@ bool denoise_rects_ok(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t wid
 namespace {
 using rmd::DenoiseInput;
 using rmd::DenoiseWeights;
+using rmd::any_overlap;
 using rmd::fail;
 constexpr rmd_status kInvalid = RMD_ERR_INVALID_ARGUMENT;
 
@@ -86,19 +78,6 @@ rmd_status check_slope(rmd_context *ctx, const std::string &name, double slope) 
 rmd_status check_rects(rmd_context *ctx, const std::string &name, const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height) {
 	const char *why = nullptr;
 	return rmd::denoise_rects_ok(rects, n_rects, width, height, &why) ? RMD_OK : fail(ctx, kInvalid, name + why);
-}
-// Whether any two of the byte ranges overlap; a null pointer is no range.  128-bit sums: a range may end past 2^64
-struct Range {
-	const void *at;
-	unsigned __int128 bytes;
-};
-bool any_overlap(std::initializer_list<Range> ranges) {
-	for (const Range *i = ranges.begin(); i != ranges.end(); i++)
-		for (const Range *j = i + 1; j != ranges.end(); j++) {
-			const unsigned __int128 a = (uintptr_t)i->at, b = (uintptr_t)j->at;
-			if (i->at && j->at && a < b + j->bytes && b < a + i->bytes) return true;
-		}
-	return false;
 }
 
 // The caller's frame as the checks and the upload take it: the single-buffer forms have one pair of sums and one count array, the dual forms two and,
@@ -343,6 +322,21 @@ rmd_status tile_measure(const char *what, rmd_context *ctx, const double *accum_
 		}
 		return finish(ctx); // (n_rects == 0: nothing is launched; the call still waits and reports an earlier fault)
 	});
+}
+// rmd_tile_error and rmd_tile_error_dual behind their checks and the context: the rects go up, launch(rects_dev, out_dev) writes a double per rect
+// (kScratchTileError: the rects, then the results), the results come down, the wait
+template <class Launch>
+rmd_status tile_errors(rmd_context *ctx, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host, Launch launch) {
+	Scratch sc; // (it outlives the wait below)
+	if (n_rects != 0) {
+		if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(rmd::kScratchTileError, width, height, n_rects, false, 0u, 0u))) return s;
+		rmd_tile_rect *d_rects = sc.part<rmd_tile_rect>(rmd::kPartRects); // (no counts, no count image: not upload_rects's pass over the rects)
+		double *d_out = sc.part<double>(rmd::kPartTileErrors);
+		RMD_HIP(ctx, hipMemcpyAsync(d_rects, rects, (size_t)n_rects * sizeof(rmd_tile_rect), hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, launch(d_rects, d_out));
+		RMD_HIP(ctx, hipMemcpyAsync(out_err_host, d_out, (size_t)n_rects * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+	}
+	return finish(ctx);
 }
 // A rule header's result struct is the C header's: the same size, and field `f` at the same offset
 #define RMD_SAME_FIELD(A, B, f) (sizeof(A) == sizeof(B) && offsetof(A, f) == offsetof(B, f))
@@ -595,23 +589,29 @@ rmd_status rmd_tile_weighted_error_dual(rmd_context *ctx, const double *out_dev,
 	});
 }
 
+// The raw frame's measure (kernels.hip: tile_error_kernel).  The context comes before the rects here
+rmd_status rmd_tile_error(rmd_context *ctx, const double *accum_dev, const double *accum_sq_dev, uint32_t width, uint32_t height, uint32_t sample_count,
+                          double floor, const rmd_tile_rect *rects, uint32_t n_rects, double *out_err_host) {
+	if (!accum_dev || !accum_sq_dev || width == 0 || height == 0 || (n_rects && (!rects || !out_err_host))) return fail(ctx, kInvalid, "rmd_tile_error: bad argument");
+	if (accum_sq_dev == accum_dev) return fail(ctx, kInvalid, "rmd_tile_error: accum_sq_dev must not alias accum_dev");
+	if (!(floor > 0.0) || !std::isfinite(floor)) return fail(ctx, kInvalid, "rmd_tile_error: floor must be finite and > 0");
+	return rmd::guarded(ctx, "rmd_tile_error", [&] {
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		if (!rmd::rects_inside(rects, n_rects, width, height)) return fail(ctx, kInvalid, std::string("rmd_tile_error: ") + rmd::kRectOutside);
+		return tile_errors(ctx, width, height, rects, n_rects, out_err_host, [&](const rmd_tile_rect *d_rects, double *d_out) {
+			return rmd::launch_tile_error(ctx->stream, accum_dev, accum_sq_dev, d_rects, n_rects, width, sample_count, floor, d_out);
+		});
+	});
+}
+
 rmd_status rmd_tile_error_dual(rmd_context *ctx, const double *err_dev, uint32_t width, uint32_t height, const rmd_tile_rect *rects, uint32_t n_rects,
                                double *out_err_host) {
 	if (!err_dev || width == 0 || height == 0 || (n_rects && (!rects || !out_err_host))) return fail(ctx, kInvalid, "rmd_tile_error_dual: bad argument");
 	if (!rmd::rects_inside(rects, n_rects, width, height)) return fail(ctx, kInvalid, std::string("rmd_tile_error_dual: ") + rmd::kRectOutside);
 	return rmd::guarded(ctx, "rmd_tile_error_dual", [&] {
 		if (rmd_status s = rmd::bind(ctx)) return s;
-		Scratch sc; // (it outlives the wait below)
-		if (n_rects != 0) {
-			DenoiseInput in{};
-			in.rects = rects, in.n_rects = n_rects;
-			if (rmd_status s = sc.carve(ctx, rmd::denoise_scratch_layout(rmd::kScratchTileError, width, height, n_rects, false, 0u, 0u))) return s;
-			if (rmd_status s = upload_rects(ctx, sc, in)) return s;
-			double *d_out = sc.part<double>(rmd::kPartTileErrors);
-			RMD_HIP(ctx, rmd::launch_tile_error_dual(ctx->stream, err_dev, in.rects, n_rects, width, d_out));
-			RMD_HIP(ctx, hipMemcpyAsync(out_err_host, d_out, (size_t)n_rects * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-		}
-		return finish(ctx);
+		return tile_errors(ctx, width, height, rects, n_rects, out_err_host,
+		                   [&](const rmd_tile_rect *d_rects, double *d_out) { return rmd::launch_tile_error_dual(ctx->stream, err_dev, d_rects, n_rects, width, d_out); });
 	});
 }
 

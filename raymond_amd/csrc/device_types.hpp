@@ -1,4 +1,4 @@
-// Device-resident scene layout shared by the kernels (kernels.hip) and the C-ABI host code (api.cpp).
+// Device-resident scene layout shared by the kernels (kernels.hip) and the C-ABI host code (api*.cpp).
 // HBM layout is described in DESIGN.md §"Data layout in HBM".
 #pragma once
 #include <stdint.h>
@@ -122,7 +122,7 @@ struct RenderParams {
 	uint32_t end_black_paths;           // 1: a path whose throughput is exactly (0, 0, 0) is ended — scenes without grids unless RMD_RENDER_TRACE_BLACK_PATHS, scenes with grids only with RMD_RENDER_END_BLACK_PATHS (api.cpp: make_params)
 	uint32_t walk_cut;                  // K: a walk call puts the walks of its last K lanes aside for the wave's next call (grid_walk.hpp); 0 = never.  Any value gives the same image
 	uint32_t shade_last_depth;          // 1: the hit at the bounce limit is shaded although its result is its weight times the zero the recursive call returns
-	                                    // (src/trace.rs:235-237) — a scene outside the regular parameter class (api.cpp: rmd_scene::regular), where that weight can be
+	                                    // (src/trace.rs:235-237) — a scene outside the regular parameter class (api_scene.cpp: rmd_scene::regular), where that weight can be
 	                                    // NaN with finite inputs (roughness 0: 0 / 0 in geometry_schlick_ggx) and the reference's sample NaN x 0 = NaN
 	uint32_t chain_items;               // 1: persistent waves of a split launch of a scene with grids draw their next work item while the last paths of the current one
 	                                    // finish (render_kernel.hpp: render_wave, CHAIN) — launches of few samples per pixel, where an item's drain is a fifth of it

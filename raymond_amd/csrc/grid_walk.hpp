@@ -357,7 +357,7 @@ RMD_DEV void grid_intersect_wave(const DevGrid &g, const uint32_t *lds_mask, Wal
 	const int32_t rx = (int32_t)g.res[0], ry = (int32_t)g.res[1], rz = (int32_t)g.res[2];
 	const uint64_t resx = g.res[0], resz = g.res[2], n_cells = g.n_cells;
 	const uint32_t mask_shift = g.mask_shift;
-	const uint32_t mask_pad_bit = g.mask_n_words * 32u - 32u; // first bit of the all-zero word that ends every mask (api.cpp)
+	const uint32_t mask_pad_bit = g.mask_n_words * 32u - 32u; // first bit of the all-zero word that ends every mask (api_scene.cpp)
 	// Every cell index is tested against the cell array (:129-131) — with Q5, or a start cell beyond the grid on an axis
 	// that is never stepped, an index can pass the array while all range tests hold.  n_cells <= 2^31 and one step moves
 	// the index by less than 2^31, so the wrapped 32-bit index is out of range exactly when the reference's usize one is.

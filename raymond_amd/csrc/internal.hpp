@@ -1,4 +1,4 @@
-// Library-internal declarations shared by api.cpp, api_denoise.cpp, probe.cpp, comm.cpp, grid_build.cpp and grid_build_gpu.hip.
+// Library-internal declarations shared by api.cpp, api_scene.cpp, api_frame.cpp, api_denoise.cpp, probe.cpp, comm.cpp, grid_build.cpp and grid_build_gpu.hip.
 #pragma once
 #include <stdint.h>
 
@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -87,10 +88,12 @@ struct rmd_context {
 	rmd::DeviceBuffer debug_counters; // walk diagnostics (DIAG builds, RMD_DEBUG=8|16)
 	rmd::DeviceBuffer atrous_region_scratch; // rmd_denoise_atrous_dual_region's planes, count images and tables (api_denoise.cpp): grown when a call needs more, kept between calls
 	size_t atrous_region_slope_offset = 0, atrous_region_slope_pixels = 0; // the last sloped region call's slope planes in that block and its W*H (0: none yet), for rmd_probe_atrous_region_slope_planes
-	rmd::DeviceBuffer resolve_tiles_scratch; // rmd_resolve_tonemap_tiles's packed bytes, flag count, flag list and run table (api.cpp): grown when a call needs more, kept between calls
-	std::vector<unsigned char> resolve_tiles_table; // ... and the host copy of the table, alive until its upload has completed
-	rmd::DeviceBuffer luma_scratch; // rmd_luminance_histogram_tiles's 261 counters and run table (api.cpp): grown when a call needs more, kept between calls
-	std::vector<unsigned char> luma_table; // ... and the host copy of the table, alive until its upload has completed
+	// A run-table call's block, [head][runs] (api_frame.cpp: upload_run_table), grown when a call needs more and kept between calls, and the table's host copy, alive until
+	// its upload has completed.  The head: rmd_resolve_tonemap_tiles's packed bytes, flag count and flag list; rmd_luminance_histogram_tiles's 261 counters
+	struct RunTable {
+		rmd::DeviceBuffer block;
+		std::vector<unsigned char> host;
+	} resolve_tiles, luma;
 	rmd::DeviceBuffer despike_scratch; // rmd_despike's count image, rect-index image, rects, counts and per-rect spike counters (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer tile_luma_scratch; // rmd_tile_luma_error's rects, counts and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer tile_weighted_scratch; // rmd_tile_weighted_error's rects, counts, weights and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls
@@ -98,7 +101,7 @@ struct rmd_context {
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound
 	// writes here; the host looks after every wait for the stream (api.cpp: check_fault) — a plain host load, no copy
 	uint32_t *h_fault = nullptr, *d_fault = nullptr;
-	// tile transfers (rmd_framebuffer_{download,upload}_tiles): two staging slots — packed pixels, rect table, prefix table on the device — so that a
+	// tile transfers (rmd_framebuffer_{download,upload}_tiles, api_frame.cpp): two staging slots — packed pixels, rect table, prefix table on the device — so that a
 	// second download can be packed while the first is still being copied; the copy stream; per slot the event its copy ends with
 	struct TransferSlot {
 		rmd::DeviceBuffer packed; // doubles
@@ -129,12 +132,12 @@ struct rmd_scene {
 	uint32_t walk_steps_bound = 0; // RenderParams::walk_steps_bound
 	uint32_t primary_cull = 0; // the scene's half of RenderParams::primary_cull: regular, no grid; by RMD_TUNE_AXIS_PAIRS when it was created 3 (candidate
 	                           // sets and tile classes: 0), 1 (candidate sets only: 3) or 0 (neither: 1, 2)
-	bool regular = true; // every parameter the kernel reads is finite and inside the class for which ending zero-throughput paths is exact (api.cpp: rmd_scene_create)
+	bool regular = true; // every parameter the kernel reads is finite and inside the class for which ending zero-throughput paths is exact (api_scene.cpp: derive_scene_objects)
 	std::vector<double> planes; // origin and normal of every plane object, six numbers each: make_params asks whether the camera lies ON one
 	rmd::DevObject *d_objects = nullptr;
 	rmd::DevGrid *d_grids = nullptr;
 	std::vector<rmd::DeviceBuffer> owned; // every device allocation of this scene
-	~rmd_scene(); // waits for the context's stream before they are freed (api.cpp)
+	~rmd_scene(); // waits for the context's stream before they are freed (api_scene.cpp)
 };
 #endif
 
@@ -144,7 +147,7 @@ struct rmd_grid_build {
 	uint32_t res[3];
 	std::vector<uint32_t> cells, mapping;
 	std::vector<double> pos, nrm;
-	// what rmd_scene_create derives from these arrays (api.cpp: GridDerived), kept for the next upload of the same grid
+	// what rmd_scene_create derives from these arrays (api_scene.cpp: GridDerived), kept for the next upload of the same grid
 	std::shared_ptr<void> derived;
 	std::mutex derived_mutex;
 };
@@ -251,6 +254,26 @@ rmd_status guarded(rmd_context *ctx, const char *what, F &&body) noexcept {
 		return fail_noexcept(ctx, RMD_ERR_HIP, what, "unknown exception");
 	}
 }
+// Every rect lies inside the frame (64-bit sums: left + width may pass 2^32), and what a call says when one does not
+constexpr const char *kRectOutside = "tile rectangle outside the framebuffer";
+static inline bool rects_inside(const rmd_tile_rect *rects, uint32_t n_rects, uint32_t width, uint32_t height) {
+	for (uint32_t i = 0; i < n_rects; i++)
+		if ((uint64_t)rects[i].left + rects[i].width > width || (uint64_t)rects[i].top + rects[i].height > height) return false;
+	return true;
+}
+// Whether any two of the byte ranges overlap; a null pointer is no range.  128-bit sums: a range may end past 2^64
+struct Range {
+	const void *at;
+	unsigned __int128 bytes;
+};
+static inline bool any_overlap(std::initializer_list<Range> ranges) {
+	for (const Range *i = ranges.begin(); i != ranges.end(); i++)
+		for (const Range *j = i + 1; j != ranges.end(); j++) {
+			const unsigned __int128 a = (uintptr_t)i->at, b = (uintptr_t)j->at;
+			if (i->at && j->at && a < b + j->bytes && b < a + i->bytes) return true;
+		}
+	return false;
+}
 #ifdef RMD_WITH_HIP
 // What an entry point does with its context first (api.cpp): "null context", or the context's device made current.
 rmd_status bind(rmd_context *ctx);
@@ -275,7 +298,7 @@ bool camera_on_a_plane(const std::vector<double> &planes, const rmd_camera *cam)
 WorkPlan plan_work_list(uint32_t wave_slots, uint32_t n_tiles, uint32_t sample_count, uint32_t k_uniform, uint32_t min_samples = kTailMinSamples,
                         uint32_t tail_x2 = kTailTilesPerSlotX2, uint32_t tail_parts = kTailParts, uint32_t n_tail_forced = 0u);
 WorkPlan context_work_plan(const rmd_context *ctx, bool has_grid, uint32_t n_tiles, uint32_t sample_count, uint32_t pass_samples);
-// The host half of rmd_scene_create (api.cpp), also for the host-only probe of the primary rays' candidate sets (probe.cpp)
+// The host half of rmd_scene_create (api_scene.cpp), also for the host-only probe of the primary rays' candidate sets (probe.cpp)
 struct SceneObjects {
 	std::vector<DevObject> objs;
 	bool regular = true;

@@ -107,7 +107,7 @@ hipError_t launch_tile_error(hipStream_t stream, const double *accum, const doub
 // The reference's 8-bit value is trunc(255 * (1 - exp(-p * exposure))^(1/gamma)) with the HOST libm's exp and powf.  The device's exp / pow
 // differ from a host libm by an ulp or two, which can only change the byte when 255 * tm lies within a few 1e-13 of an integer.  So the
 // kernel computes every pixel and FLAGS the few whose value is within kTonemapGuard of a truncation boundary (1 .. 255); the host
-// recomputes exactly those with its libm (api.cpp: rmd_resolve_tonemap) — byte-exact output, and a pixel in ~10^6 takes the slow road.
+// recomputes exactly those with its libm (api_frame.cpp: rmd_resolve_tonemap) — byte-exact output, and a pixel in ~10^6 takes the slow road.
 // Two exact cases need no flag: an argument <= -40 gives exp < 2^-57, 1 - exp = 1, pow(1, y) = 1 and 255 exactly with ANY libm
 // (saturated pixels); and values that truncate to 0 either way (|255 tm| < 1 - guard: black pixels).
 __global__ __launch_bounds__(256) void tonemap_kernel(const double *__restrict__ accum, uint8_t *__restrict__ rgb8, size_t n_pixels,

@@ -8,7 +8,7 @@
 //   * a sphere whose distance from every line of the tile's bounding cone exceeds its radius registers no hit (sphere_test_flat: `!(p > r2)`);
 //   * of the room's (up to) three axis pairs (scene_split.hpp: axis_pair_test) one is nearer than the other two for every ray of the tile, so
 //     the other two never hold the closest hit.
-// The host turns this on (RenderParams::primary_cull) only for a scene of regular parameters (api.cpp: rmd_scene::regular — every coordinate and
+// The host turns this on (RenderParams::primary_cull) only for a scene of regular parameters (api_scene.cpp: rmd_scene::regular — every coordinate and
 // radius finite and tame) without a grid, a launch without the thin lens (whose rays leave from the lens disc, not from cam_pos), and a camera
 // whose position, tan_half_fov, aspect, width and height are finite, the last four positive.  Every comparison below is written so that a NaN
 // keeps the object.

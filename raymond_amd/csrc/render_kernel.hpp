@@ -466,7 +466,7 @@ RMD_DEV void render_wave(const RenderParams &P, KernargWords kernarg_params, con
 					}
 					// At the bounce limit the recursive call returns 0 at once (:235-237) and this depth's result is its weight times
 					// that zero (:281-282 / :315-318): exactly zero whenever the weight is finite, so the shading is not evaluated.
-					// In a scene of regular parameters (api.cpp: rmd_scene::regular) a weight is non-finite only through a non-finite input — the
+					// In a scene of regular parameters (api_scene.cpp: rmd_scene::regular) a weight is non-finite only through a non-finite input — the
 					// Heron normal of a degenerate hit, a hit point at infinity — (then the reference's sample is NaN, and so is this one: the
 					// lane shades and multiplies by zero on its next trip), or through r1 = 0 exactly in the diffuse pdf (probability 2^-53 per
 					// path; there the reference returns NaN and this kernel 0).  Outside that class — a NaN colour, roughness 0 (0 / 0 in

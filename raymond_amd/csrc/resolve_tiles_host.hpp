@@ -1,4 +1,4 @@
-// The host arithmetic of rmd_resolve_tonemap_tiles (api.cpp; the kernel is resolve_tiles.hip): where a rect's pixels lie in the packed output, the
+// The host arithmetic of rmd_resolve_tonemap_tiles (api_frame.cpp; the kernel is resolve_tiles.hip): where a rect's pixels lie in the packed output, the
 // table that gives every workgroup its pixels, and the way back from a flagged packed pixel to its rect and frame position.  Needs only <stdint.h>
 // and the standard library — `Rect` is any struct with left, top, width, height (rmd_tile_rect) — so that it can be run on the CPU by itself
 // (tests/resolve_tiles_table_main.cpp drives it through random rect lists).

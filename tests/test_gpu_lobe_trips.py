@@ -17,7 +17,7 @@ sample the same bits:
     parked by lobe — and both lobes' trip counts are non-zero.
 
 Not covered: a material of metalness 0.5 (prob_d = 0.25).  The library's materials are Diffuse (metalness 0, prob_d 0.5) and Metal (metalness 1,
-prob_d 0): api.cpp derives the metalness from the kind and no entry point sets another value, so such a room cannot be built through the C-ABI."""
+prob_d 0): api_scene.cpp derives the metalness from the kind and no entry point sets another value, so such a room cannot be built through the C-ABI."""
 import os
 import re
 import subprocess

@@ -657,7 +657,7 @@ def test_black_path_modes_on_a_mesh_with_nan_normals(gpu_ctx, oracle):
 
 
 def _irregular_scenes():
-    """Grid-less scenes whose parameters lie OUTSIDE the class for which ending a zero-throughput path is exact (api.cpp: rmd_scene::regular) —
+    """Grid-less scenes whose parameters lie OUTSIDE the class for which ending a zero-throughput path is exact (api_scene.cpp: rmd_scene::regular) —
     each makes a non-finite radiance reachable behind a black bounce without any mesh (src/trace.rs:250-252, :281-282, :315-318)."""
     from raymond_amd.scene import Material, Object, Plane, Scene, Sphere
 
