@@ -60,7 +60,7 @@ enum {
 	                                 Reported by the first call that waits for the launch (rmd_render_tiles,
 	                                 rmd_context_synchronize, rmd_last_kernel_ms, rmd_framebuffer_download[_tiles],
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
-	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error,
+	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_despike_dual, rmd_tile_luma_error, rmd_tile_weighted_error,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
 	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
@@ -945,6 +945,45 @@ rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *
                        const rmd_tile_rect *rects, const uint32_t *rect_sample_counts, uint32_t n_rects,
                        uint32_t radius, uint32_t rank, double k, double ratio, double floor,
                        double *out_accum_dev, double *out_accum_sq_dev, uint32_t *replaced_host /* n_rects, may be NULL */);
+/*
+ * FIREFLY REJECTION FOR THE TWO HALVES of a dual-buffer frame, the stage in front of rmd_denoise_dual, its guided, a-trous, region and select forms and
+ * rmd_tile_error_dual (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes, found by its symbol).  A firefly is one sample, so it sits in
+ * one half only: err = |f_A - f_B| / 2 is large there and wherever the filter smears it, and the cross filter still averages it into the frame.  The call
+ * makes exactly the decisions rmd_despike would make on all the samples, and keeps the two halves two independent sample sets.
+ * S_A = accum_a_dev, Q_A = accum_sq_a_dev, S_B = accum_b_dev, Q_B = accum_sq_b_dev, rects, rect_counts_a and rect_counts_b mean what they mean in
+ * rmd_denoise_dual: n_Ai and n_Bi are the counts of the rect that covers pixel i, 0 if no rect covers it.  Everything is unfused binary64.
+ * The MERGED pixel:
+ *     n_i = n_Ai + n_Bi;   S_ic = S_Aic + S_Bic;   Q_ic = Q_Aic + Q_Bic      one rounded addition each (rmd_luminance_histogram_tiles's rule for accum2_dev)
+ *     pixel i is VALID if n_Ai >= 1, n_Bi >= 1 and its six MERGED sums are finite
+ * Finite merged sums imply finite halves; two finite halves whose sum overflows are not valid.  A pixel with an empty half is never a spike and never a
+ * donor: the scaled copy below divides by the donor's half count.
+ * The decision: u, v, Y, V, the OTHERS of a valid p, their order, the DONOR q* at 0-based index `rank`, e = (Y_p - ratio * Y_q*) - floor and the test
+ * e > 0 and e * e > (k * k) * V_q* are rmd_despike's, word for word, on (S, Q, n) with this call's validity.  One decision per pixel serves both halves,
+ * and every decision reads the INPUT only.
+ * Output (out_accum_a_dev = S'_A, out_accum_sq_a_dev = Q'_A, out_accum_b_dev = S'_B, out_accum_sq_b_dev = Q'_B): a pixel that is not a spike is a bit copy
+ * of its twelve input values.  For a spike p with donor q*, each half h on its own:
+ *     n_ph == n_q*h:   the six values of half h are bit copies of the donor's half-h values;
+ *     otherwise:       S'_phc = (S_q*hc / n_q*h) * n_ph,   Q'_phc = (Q_q*hc / n_q*h) * n_ph
+ * A spike takes the donor's HALF sums, never a split of the merged ones: half A of the output holds only half-A samples and stays independent of half B,
+ * which the cross filter and err rest on.  The outputs keep the rects' two counts: every dual call takes them in place of the inputs.
+ * replaced_host (a HOST array of n_rects words, may be NULL): replaced_host[j] = the number of spikes in rect j, an exact integer.
+ * What the definition makes true:
+ *   (a) where every rect has both counts >= 1, the spike set and replaced_host equal those of rmd_despike on the buffers S_A + S_B, Q_A + Q_B at n_A + n_B;
+ *   (b) where in addition every spike's counts agree with its donor's half by half, S'_A + S'_B and Q'_A + Q'_B (one rounded addition) are rmd_despike's
+ *       outputs bit for bit.
+ * Bias: the decision is made from the merged sums, so it couples the two halves through the CHOICE of pixels — a selection, not a value: no sample of one
+ * half enters the other's sums.  The call removes energy and is BIASED as rmd_despike is.
+ * RMD_ERR_INVALID_ARGUMENT, all checked before the device is touched and with the outputs untouched, in this order: rmd_despike's frame and rect rules
+ * (width, height > 0; rects, rect_counts_a and rect_counts_b non-NULL when n_rects > 0; every rect inside the frame, no two overlapping); a rect whose two
+ * counts add to more than 2^32 - 1; 1 <= radius <= 3; rank <= (2 * radius + 1)^2 - 2; k finite and >= 0, ratio finite and >= 1, floor finite and >= 0; the
+ * eight buffers non-NULL and no two of the eight W*H*3-double ranges overlapping; and only then a NULL context.  Synchronous, like rmd_despike, and reports
+ * an earlier device fault like it; the call's device scratch (three W*H-word images, the rects, both counts and the counters) stays on the context and grows
+ * on demand.  Values to start from (not tuned): rmd_despike's.
+ */
+rmd_status rmd_despike_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                            uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b,
+                            uint32_t n_rects, uint32_t radius, uint32_t rank, double k, double ratio, double floor, double *out_accum_a_dev,
+                            double *out_accum_sq_a_dev, double *out_accum_b_dev, double *out_accum_sq_b_dev, uint32_t *replaced_host /* n_rects, may be NULL */);
 /*
  * A TILE'S LUMINANCE NOISE, the adaptive check's second measure (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct or entry point changes,
  * found by its symbol).  rmd_tile_error is a maximum over channels of a maximum over pixels: one dark pixel's one dim channel holds its whole tile.  This

@@ -169,6 +169,12 @@ extern "C" {
     fn rmd_despike(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,
                    rect_sample_counts: *const u32, n_rects: u32, radius: u32, rank: u32, k: f64, ratio: f64, floor: f64, out_accum_dev: *mut f64,
                    out_accum_sq_dev: *mut f64, replaced_host: *mut u32) -> i32;
+    // the same stage for the two halves of a dual-buffer frame (settings.despike_dual of the C++ mirror): one decision per pixel from the merged sums, each
+    // half replaced from its donor's half; the four outputs take the place of the halves in every dual call, at the same rects and counts
+    fn rmd_despike_dual(ctx: *mut rmd_context, accum_a_dev: *const f64, accum_sq_a_dev: *const f64, accum_b_dev: *const f64, accum_sq_b_dev: *const f64,
+                        width: u32, height: u32, rects: *const rmd_tile_rect, rect_counts_a: *const u32, rect_counts_b: *const u32, n_rects: u32, radius: u32,
+                        rank: u32, k: f64, ratio: f64, floor: f64, out_accum_a_dev: *mut f64, out_accum_sq_a_dev: *mut f64, out_accum_b_dev: *mut f64,
+                        out_accum_sq_b_dev: *mut f64, replaced_host: *mut u32) -> i32;
     // a tile's luminance noise, the adaptive check's other measures (settings.adaptive_measure of the C++ mirror): rect i at rect_counts[i], rects inside the
     // frame (they may overlap or repeat), out_host n_rects rmd_tile_luma; tile_rms or pixel_rms is what meets the threshold
     fn rmd_tile_luma_error(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, width: u32, height: u32, rects: *const rmd_tile_rect,

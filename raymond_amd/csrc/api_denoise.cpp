@@ -1,5 +1,5 @@
-// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_tile_luma_error, rmd_tile_weighted_error,
-// rmd_tile_weighted_error_dual, rmd_tile_error and rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, tile_luma.hip,
+// C-ABI implementation (include/raymond_hip.h) of the denoise entry points, rmd_despike, rmd_despike_dual, rmd_tile_luma_error, rmd_tile_weighted_error,
+// rmd_tile_weighted_error_dual, rmd_tile_error and rmd_tile_error_dual.  Host code only; the kernels are in denoise*.hip, despike.hip, despike_dual.hip, tile_luma.hip,
 // tile_weighted.hip, tile_weighted_dual.hip and, rmd_tile_error's, kernels.hip.
 // Every entry point is its argument checks in its own order and then, inside rmd::guarded: the rect checks, the context, one carved scratch block
 // (denoise_host.hpp has the layouts), one upload of the rects, its launcher (launch.hpp) and the wait.
@@ -520,6 +520,41 @@ rmd_status rmd_despike(rmd_context *ctx, const double *accum_dev, const double *
 		uint32_t *d_replaced = replaced_host && n_rects ? sc.part<uint32_t>(rmd::kPartTileErrors) : nullptr;
 		RMD_HIP(ctx, rmd::launch_despike(ctx->stream, in, radius, rank, k, ratio, floor, sc.part<uint32_t>(rmd::kPartCountImg), sc.part<uint32_t>(rmd::kPartWinImg),
 		                                 out_accum_dev, out_accum_sq_dev, d_replaced));
+		if (d_replaced) RMD_HIP(ctx, hipMemcpyAsync(replaced_host, d_replaced, (size_t)n_rects * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+		return finish(ctx);
+	});
+}
+
+// rmd_despike_dual (despike_dual.hip).  rmd_despike's refusals in its order and texts, with the counts' sum after the rects and eight buffers in place of four
+rmd_status rmd_despike_dual(rmd_context *ctx, const double *accum_a_dev, const double *accum_sq_a_dev, const double *accum_b_dev, const double *accum_sq_b_dev,
+                            uint32_t width, uint32_t height, const rmd_tile_rect *rects, const uint32_t *rect_counts_a, const uint32_t *rect_counts_b, uint32_t n_rects,
+                            uint32_t radius, uint32_t rank, double k, double ratio, double floor, double *out_accum_a_dev, double *out_accum_sq_a_dev,
+                            double *out_accum_b_dev, double *out_accum_sq_b_dev, uint32_t *replaced_host) {
+	const std::string name = "rmd_despike_dual: ";
+	return rmd::guarded(ctx, "rmd_despike_dual", [&] {
+		if (width == 0 || height == 0 || (n_rects && (!rects || !rect_counts_a || !rect_counts_b))) return fail(ctx, kInvalid, name + "bad argument");
+		if (rmd_status s = check_rects(ctx, name, rects, n_rects, width, height)) return s;
+		for (uint32_t j = 0; j < n_rects; j++)
+			if ((uint64_t)rect_counts_a[j] + rect_counts_b[j] > 0xFFFFFFFFull) return fail(ctx, kInvalid, name + "a rect's two counts must not add to more than 2^32 - 1");
+		if (radius < 1u || radius > rmd::kDespikeMaxRadius) return fail(ctx, kInvalid, name + "radius must be 1 .. 3");
+		if (rank > (2u * radius + 1u) * (2u * radius + 1u) - 2u) return fail(ctx, kInvalid, name + "rank must be <= (2 * radius + 1)^2 - 2");
+		if (!(k >= 0.0) || !std::isfinite(k)) return fail(ctx, kInvalid, name + "k must be finite and >= 0");
+		if (!(ratio >= 1.0) || !std::isfinite(ratio)) return fail(ctx, kInvalid, name + "ratio must be finite and >= 1");
+		if (!(floor >= 0.0) || !std::isfinite(floor)) return fail(ctx, kInvalid, name + "floor must be finite and >= 0");
+		if (!accum_a_dev || !accum_sq_a_dev || !accum_b_dev || !accum_sq_b_dev || !out_accum_a_dev || !out_accum_sq_a_dev || !out_accum_b_dev || !out_accum_sq_b_dev)
+			return fail(ctx, kInvalid, name + "the eight sum buffers must not be NULL");
+		const unsigned __int128 bytes = (unsigned __int128)width * height * 3u * sizeof(double);
+		if (any_overlap({{accum_a_dev, bytes}, {accum_sq_a_dev, bytes}, {accum_b_dev, bytes}, {accum_sq_b_dev, bytes}, {out_accum_a_dev, bytes}, {out_accum_sq_a_dev, bytes},
+		                 {out_accum_b_dev, bytes}, {out_accum_sq_b_dev, bytes}}))
+			return fail(ctx, kInvalid, name + "the four input and the four output sum buffers must not alias");
+		if (rmd_status s = rmd::bind(ctx)) return s;
+		DenoiseInput in = dual_input(accum_a_dev, accum_sq_a_dev, accum_b_dev, accum_sq_b_dev, nullptr, nullptr, width, height, rects, rect_counts_a, rect_counts_b, nullptr, n_rects);
+		Scratch sc; // (the context's block: kept between calls)
+		if (rmd_status s = sc.carve(ctx, rmd::despike_dual_scratch_layout(width, height, n_rects), &ctx->despike_dual_scratch)) return s;
+		if (rmd_status s = upload_rects(ctx, sc, in)) return s;
+		uint32_t *d_replaced = replaced_host && n_rects ? sc.part<uint32_t>(rmd::kPartTileErrors) : nullptr;
+		RMD_HIP(ctx, rmd::launch_despike_dual(ctx->stream, in, radius, rank, k, ratio, floor, sc.part<uint32_t>(rmd::kPartCountImg), sc.part<uint32_t>(rmd::kPartWinImg),
+		                                      out_accum_a_dev, out_accum_sq_a_dev, out_accum_b_dev, out_accum_sq_b_dev, d_replaced));
 		if (d_replaced) RMD_HIP(ctx, hipMemcpyAsync(replaced_host, d_replaced, (size_t)n_rects * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
 		return finish(ctx);
 	});

@@ -109,6 +109,20 @@ inline ScratchLayout despike_scratch_layout(uint32_t W, uint32_t H, uint32_t n_r
 	return L;
 }
 
+// rmd_despike_dual's block: rmd_despike's with both halves' count images in kPartCountImg (2 * W*H uint32, half A's first) and kPartCountsB beside
+// kPartCountsA
+inline ScratchLayout despike_dual_scratch_layout(uint32_t W, uint32_t H, uint32_t n_rects) {
+	ScratchLayout L;
+	const size_t N = (size_t)W * H, u32 = sizeof(uint32_t);
+	auto part = [&](ScratchPart p, size_t elem_bytes, size_t count) {
+		L.used[p] = true, L.offset[p] = L.total, L.bytes[p] = elem_bytes * count;
+		L.total += (L.bytes[p] + 15u) & ~(size_t)15u;
+	};
+	part(kPartCountImg, u32, 2u * N), part(kPartWinImg, u32, N);
+	part(kPartRects, sizeof(rmd_tile_rect), n_rects), part(kPartCountsA, u32, n_rects), part(kPartCountsB, u32, n_rects), part(kPartTileErrors, u32, n_rects);
+	return L;
+}
+
 // The block of rmd_tile_luma_error (n_table 0) and rmd_tile_weighted_error (n_table RMD_LUMA_WEIGHTS), in the parts' existing names: kPartRects and
 // kPartCountsA the rects and their counts, kPartTable the call's table of n_table doubles, kPartTileErrors the per-rect results of result_bytes each.  All
 // but the results is what the call uploads, in one copy: those parts lie at the block's start in this order, each padded to 16 bytes; `upload_bytes` is

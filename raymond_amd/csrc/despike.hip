@@ -114,16 +114,20 @@ __global__ __launch_bounds__(kDespikeThreads) void despike_kernel(const double *
 	}
 }
 
+hipError_t launch_rect_index_image(hipStream_t stream, const DenoiseInput &in, uint32_t *rect_img, uint32_t *replaced) {
+	hipError_t e = hipMemsetAsync(replaced, 0, (size_t)in.n_rects * sizeof(uint32_t), stream);
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(rect_index_image_kernel, dim3(in.n_rects, in.count_image_columns), dim3(256), 0, stream, in.rects, in.W, rect_img);
+	return hipGetLastError();
+}
+
 hipError_t launch_despike(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t rank, double k, double ratio, double floor, uint32_t *n_img,
                           uint32_t *rect_img, double *out_accum, double *out_accum_sq, uint32_t *replaced) {
 	if (radius < 1u || radius > kDespikeMaxRadius || n_img == nullptr || (replaced != nullptr && rect_img == nullptr)) return hipErrorInvalidValue;
 	hipError_t e = launch_denoise_planes(stream, in, n_img, nullptr); // the count image: zeroed, then painted rect by rect
 	if (e != hipSuccess) return e;
-	if (replaced != nullptr && in.n_rects != 0u) {
-		if ((e = hipMemsetAsync(replaced, 0, (size_t)in.n_rects * sizeof(uint32_t), stream)) != hipSuccess) return e;
-		hipLaunchKernelGGL(rect_index_image_kernel, dim3(in.n_rects, in.count_image_columns), dim3(256), 0, stream, in.rects, in.W, rect_img);
-		if ((e = hipGetLastError()) != hipSuccess) return e;
-	}
+	if (replaced != nullptr && in.n_rects != 0u)
+		if ((e = launch_rect_index_image(stream, in, rect_img, replaced)) != hipSuccess) return e;
 	const dim3 grid((in.W + kDespikeTileW - 1u) / kDespikeTileW, (in.H + kDespikeTileH - 1u) / kDespikeTileH);
 	hipLaunchKernelGGL(despike_kernel, grid, dim3(kDespikeThreads), 0, stream, in.accum_a, in.accum_sq_a, n_img, rect_img, in.W, in.H, radius, rank, k, ratio, floor,
 	                   out_accum, out_accum_sq, in.n_rects != 0u ? replaced : nullptr);

@@ -95,6 +95,7 @@ struct rmd_context {
 		std::vector<unsigned char> host;
 	} resolve_tiles, luma;
 	rmd::DeviceBuffer despike_scratch; // rmd_despike's count image, rect-index image, rects, counts and per-rect spike counters (api_denoise.cpp): grown when a call needs more, kept between calls
+	rmd::DeviceBuffer despike_dual_scratch; // rmd_despike_dual's two count images, rect-index image, rects, both counts and per-rect spike counters (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer tile_luma_scratch; // rmd_tile_luma_error's rects, counts and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer tile_weighted_scratch; // rmd_tile_weighted_error's rects, counts, weights and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer tile_weighted_dual_scratch; // rmd_tile_weighted_error_dual's rects, weights and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls

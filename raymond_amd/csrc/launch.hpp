@@ -219,6 +219,15 @@ hipError_t launch_luma_histogram(hipStream_t stream, const double *accum, const 
 // not read (may be null).  radius is 1 .. 3; the other arguments are checked by the caller
 hipError_t launch_despike(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t rank, double k, double ratio, double floor, uint32_t *n_img,
                           uint32_t *rect_img, double *out_accum, double *out_accum_sq, uint32_t *replaced);
+// launch_despike's counting preamble on its own (despike.hip), for rmd_despike_dual: `replaced` (in.n_rects words, n_rects > 0) zeroed and rect_img painted
+// with each covered pixel's rect index
+hipError_t launch_rect_index_image(hipStream_t stream, const DenoiseInput &in, uint32_t *rect_img, uint32_t *replaced);
+// rmd_despike_dual (despike_dual.hip): the four outputs = the two halves' sums with every spike of the MERGED pixel replaced half by half from its donor
+// (despike_dual_rule.hpp over despike_rule.hpp has the rule).  in's four sum buffers, the rects, counts_a and counts_b are read.  Scratch: n_img 2 * W*H
+// uint32 — half A's per-pixel counts, then half B's, each painted by launch_denoise_planes —, rect_img and `replaced` as launch_despike's.  radius is
+// 1 .. 3; the other arguments, and that no rect's two counts add past 2^32 - 1, are checked by the caller
+hipError_t launch_despike_dual(hipStream_t stream, const DenoiseInput &in, uint32_t radius, uint32_t rank, double k, double ratio, double floor, uint32_t *n_img,
+                               uint32_t *rect_img, double *out_accum_a, double *out_accum_sq_a, double *out_accum_b, double *out_accum_sq_b, uint32_t *replaced);
 // rmd_tile_luma_error (tile_luma.hip): out[i] = rect i's result (tile_luma_rule.hpp: TileLuma, rmd_tile_luma's layout) from in.accum_a / in.accum_sq_a at
 // in.counts_a[i], one workgroup per rect; the rects, the counts and `out` are device memory.  Nothing else of `in` is read.  floor is checked by the caller
 struct TileLuma;

@@ -56,6 +56,8 @@
 //                                                                     [--despike-floor F]]   (firefly rejection, rmd_despike at 2, 2, 6, 2, 0, in front of
 //                                                                      the plain divide or of whichever --denoise filter is on, and of the --adaptive check;
 //                                                                      not with --denoise-dual)
+//                                                                    [--despike-dual 1]   (with --denoise-dual: rmd_despike_dual at the --despike-* values in front
+//                                                                      of the dual filter, in await() and in every filter call of the dual loop)
 //   raymond_cli mesh N out.bin            procedural stand-in mesh as raw f64 (tri_pos then tri_nrm)
 //   raymond_cli ply in.ply out.bin        Mesh::load_ply + bake_transform(0,-0.3,2.9), raw f64 as above
 //   raymond_cli tiles W H TW TH           tile generation order of render_tiled, one "left top width height" per line
@@ -67,6 +69,9 @@
 //                                         rmd_despike made on the host (raymond::despike_host, from the header the kernel is built from) over raw W*H*3 f64
 //                                         sums and sums of squares; rects.txt: one "left top width height count" per line; K, Q and F are read as C99
 //                                         hexadecimal or decimal doubles; prints one line of the spikes per rect
+//   raymond_cli despike-dual SA.f64 QA.f64 SB.f64 QB.f64 W H rects.txt R N K Q F outSA.f64 outQA.f64 outSB.f64 outQB.f64
+//                                         rmd_despike_dual made on the host (raymond::despike_dual_host) over the two halves' raw W*H*3 f64 sums and sums of
+//                                         squares; rects.txt: one "left top width height count_a count_b" per line; the rest as for despike
 //   raymond_cli tile-luma-error S.f64 Q.f64 W H rects.txt FLOOR
 //                                         rmd_tile_luma_error made on the host (raymond::tile_luma_error_host, from the header the kernel is built from) over raw
 //                                         W*H*3 f64 sums and sums of squares; rects.txt as for despike; FLOOR is read as a C99 hexadecimal or decimal double;
@@ -240,6 +245,34 @@ int main(int argc, char **argv) {
 				std::ofstream f(argv[12 + i], std::ios::binary);
 				const std::vector<Vector3> &src = i ? out_sq : out;
 				f.write(reinterpret_cast<const char *>(src.data()), (std::streamsize)(src.size() * sizeof(Vector3)));
+			}
+			for (uint32_t n : replaced) std::printf("%u ", n);
+			std::printf("\n");
+			return 0;
+		}
+		if (argc >= 18 && !std::strcmp(argv[1], "despike-dual")) {
+			const size_t W = (size_t)std::atoll(argv[6]), H = (size_t)std::atoll(argv[7]);
+			std::vector<Vector3> in[4], out[4]; // SA, QA, SB, QB
+			for (int i = 0; i < 4; i++) {
+				in[i].resize(W * H);
+				std::ifstream f(argv[2 + i], std::ios::binary);
+				if (!f || !f.read(reinterpret_cast<char *>(in[i].data()), (std::streamsize)(in[i].size() * sizeof(Vector3))))
+					throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2 + i]);
+			}
+			std::vector<rmd_tile_rect> rects;
+			std::vector<uint32_t> counts_a, counts_b;
+			std::ifstream rf(argv[8]);
+			for (rmd_tile_rect r; rf >> r.left >> r.top >> r.width >> r.height;) {
+				uint32_t na = 0, nb = 0;
+				rf >> na >> nb;
+				rects.push_back(r), counts_a.push_back(na), counts_b.push_back(nb);
+			}
+			const std::vector<uint32_t> replaced =
+			    despike_dual_host(in[0], in[1], in[2], in[3], W, H, rects, counts_a, counts_b, (uint32_t)std::atoi(argv[9]), (uint32_t)std::atoi(argv[10]), std::strtod(argv[11], nullptr),
+			                      std::strtod(argv[12], nullptr), std::strtod(argv[13], nullptr), out[0], out[1], out[2], out[3]);
+			for (int i = 0; i < 4; i++) {
+				std::ofstream f(argv[14 + i], std::ios::binary);
+				f.write(reinterpret_cast<const char *>(out[i].data()), (std::streamsize)(out[i].size() * sizeof(Vector3)));
 			}
 			for (uint32_t n : replaced) std::printf("%u ", n);
 			std::printf("\n");
@@ -457,6 +490,7 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--auto-exposure-percentile")) st.auto_exposure_percentile = std::atof(argv[i + 1]); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--auto-exposure-target")) st.auto_exposure_target = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--despike")) st.despike = std::atoi(argv[i + 1]) != 0;
+				else if (!std::strcmp(argv[i], "--despike-dual")) st.despike_dual = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--despike-radius")) st.despike_radius = (uint32_t)std::atoi(argv[i + 1]); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--despike-rank")) st.despike_rank = (uint32_t)std::atoi(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--despike-k")) st.despike_k = std::atof(argv[i + 1]);

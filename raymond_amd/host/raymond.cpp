@@ -2,6 +2,7 @@
 // rmd_render_tiles; nothing here evaluates a ray.
 #include "raymond.hpp"
 
+#include "../csrc/despike_dual_rule.hpp"
 #include "../csrc/despike_rule.hpp"
 #include "../csrc/luma_bins.hpp"
 #include "../csrc/tile_luma_rule.hpp"
@@ -757,6 +758,8 @@ struct DualWorker : Worker {
 	Frame fbs[6];      // S_A, Q_A, S_B, Q_B; adaptive: the filtered frame and the error image
 	Frame feat[2];     // guided: the feature sums and sums of squares
 	Frame fb_preview;  // settings.preview_denoise: the filtered means of a preview
+	Frame spare[4];    // settings.despike_dual, when this loop filters (the check, the filtered preview): rmd_despike_dual's outputs, which every dual filter call here reads; fbs stay raw
+	size_t despiked_at = ~(size_t)0; // the pass whose despiked halves `spare` holds
 	Settings preview_st; // ... which are always the fast filter's, whichever filter the settings select for the frame: `st` with denoise_dual_atrous on
 	std::vector<rmd_tile_rect> live, done_rects;
 	std::vector<uint32_t> done_a, done_b;
@@ -772,6 +775,7 @@ struct DualWorker : Worker {
 		for (int i = 0; i < (adaptive ? 6 : 4); i++) fbs[i] = frame();
 		for (Frame &f : feat) f = frame(guided, Frame::Features);
 		fb_preview = frame(st.preview_every > 0 && st.preview_denoise);
+		for (Frame &f : spare) f = frame(st.despike_dual && (adaptive || fb_preview));
 		preview_st.denoise_dual_atrous = true;
 	}
 
@@ -826,6 +830,19 @@ struct DualWorker : Worker {
 		return f;
 	}
 
+	// the halves a dual filter call of this pass reads: the loop's own, or with despike_dual the despiked halves of the whole frame `f`, made once a pass by one
+	// rmd_despike_dual call (a later call of the same pass has the same tiles at the same counts)
+	const Frame *filter_halves(const FrameCounts &f) {
+		if (!spare[0]) return fbs;
+		if (despiked_at != j) {
+			check(rmd_despike_dual(ctx, fbs[0], fbs[1], fbs[2], fbs[3], (uint32_t)W, (uint32_t)H, f.rects.data(), f.a.data(), f.b.data(), (uint32_t)f.rects.size(), st.despike_radius,
+			                       st.despike_rank, st.despike_k, st.despike_ratio, st.despike_floor, spare[0], spare[1], spare[2], spare[3], nullptr),
+			      ctx, "rmd_despike_dual");
+			despiked_at = j;
+		}
+		return spare;
+	}
+
 	// the live tiles' rmd_tile_error_dual after the filter the settings select; only the live tiles' filtered pixels are read, so they are the filter's region.
 	// With adaptive_denoised_display_threshold: one rmd_tile_weighted_error_dual call's rms on the filtered frame and the error image instead; with
 	// adaptive_display_auto_exposure the table is first made anew from one histogram of the whole frame's RAW sums — S_A with S_B as the second buffer, at the
@@ -834,7 +851,7 @@ struct DualWorker : Worker {
 		std::vector<double> errors;
 		if (!(adaptive && j % 2 == 0 && done >= st.adaptive_min_samples)) return errors;
 		const FrameCounts f = whole_frame(live);
-		denoise_dual_frame(ctx, st, W, H, fbs, feat[0], feat[1], f.rects, f.a, f.b, live.data(), live.size(), fbs[4], fbs[5]);
+		denoise_dual_frame(ctx, st, W, H, filter_halves(f), feat[0], feat[1], f.rects, f.a, f.b, live.data(), live.size(), fbs[4], fbs[5]);
 		errors.resize(live.size());
 		if (display) {
 			if (st.adaptive_display_auto_exposure) {
@@ -918,7 +935,7 @@ struct DualWorker : Worker {
 	Message preview(const std::vector<rmd_tile_rect> &still) {
 		const FrameCounts f = whole_frame(still);
 		if (!fb_preview) return preview_message(ctx, fbs[0], fbs[2], W, H, f.rects, sum_counts(f.a, f.b), st, j, done);
-		denoise_dual_frame(ctx, preview_st, W, H, fbs, feat[0], feat[1], f.rects, f.a, f.b, nullptr, 0, fb_preview, nullptr);
+		denoise_dual_frame(ctx, preview_st, W, H, filter_halves(f), feat[0], feat[1], f.rects, f.a, f.b, nullptr, 0, fb_preview, nullptr);
 		return preview_message(ctx, fb_preview, nullptr, W, H, f.rects, std::vector<uint32_t>(f.rects.size(), 1u), st, j, done); // (means)
 	}
 };
@@ -1036,6 +1053,7 @@ std::string check_settings(const Settings &st) {
 		return "despike with adaptive_threshold renders on one device: the window crosses the tiles that several devices would own";
 	if (st.despike && st.adaptive_display_threshold > 0.0 && st.worker_count > 1)
 		return "despike with adaptive_display_threshold renders on one device: the window crosses the tiles that several devices would own";
+	if (st.despike_dual && !st.denoise_dual) return "despike_dual needs denoise_dual: it despikes the two halves"; // (after every older rule: each of their texts is still raised first)
 	return "";
 }
 } // namespace
@@ -1259,6 +1277,52 @@ std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::
 	return replaced;
 }
 
+std::vector<uint32_t> despike_dual_host(const std::vector<Vector3> &sums_a, const std::vector<Vector3> &sums_sq_a, const std::vector<Vector3> &sums_b,
+                                        const std::vector<Vector3> &sums_sq_b, size_t width, size_t height, const std::vector<rmd_tile_rect> &rects,
+                                        const std::vector<uint32_t> &counts_a, const std::vector<uint32_t> &counts_b, uint32_t radius, uint32_t rank, double k, double ratio,
+                                        double floor, std::vector<Vector3> &out_a, std::vector<Vector3> &out_sq_a, std::vector<Vector3> &out_b, std::vector<Vector3> &out_sq_b) {
+	const size_t N = width * height;
+	bool bad = sums_a.size() != N || sums_sq_a.size() != N || sums_b.size() != N || sums_sq_b.size() != N || rects.size() != counts_a.size() || rects.size() != counts_b.size() ||
+	           radius < 1 || radius > rmd::kDespikeMaxRadius;
+	for (size_t j = 0; !bad && j < rects.size(); j++) bad = (uint64_t)counts_a[j] + counts_b[j] > 0xFFFFFFFFull;
+	if (bad) throw Error(RMD_ERR_INVALID_ARGUMENT, "despike_dual_host: bad argument");
+	const size_t r = radius, AW = width + 2 * r, AH = height + 2 * r;
+	std::vector<uint32_t> na(N, 0u), nb(N, 0u), rect_of_pixel(N, 0u), replaced(rects.size(), 0u);
+	for (size_t j = 0; j < rects.size(); j++)
+		for (size_t y = rects[j].top; y < (size_t)rects[j].top + rects[j].height; y++)
+			for (size_t x = rects[j].left; x < (size_t)rects[j].left + rects[j].width; x++)
+				na[y * width + x] = counts_a[j], nb[y * width + x] = counts_b[j], rect_of_pixel[y * width + x] = (uint32_t)j;
+	// the kernel's apron, for the whole frame at once: Y and V of the merged pixel, a NaN Y where there is no other
+	std::vector<double> Y(AW * AH, std::nan("")), V(AW * AH, 0.0);
+	for (size_t y = 0; y < height; y++)
+		for (size_t x = 0; x < width; x++) {
+			const size_t p = y * width + x;
+			double yy, vv;
+			if (rmd::despike_dual_pixel(sums_a[p].data(), sums_sq_a[p].data(), na[p], sums_b[p].data(), sums_sq_b[p].data(), nb[p], yy, vv))
+				Y[(y + r) * AW + x + r] = yy, V[(y + r) * AW + x + r] = vv;
+		}
+	out_a = sums_a, out_sq_a = sums_sq_a, out_b = sums_b, out_sq_b = sums_sq_b;
+	const int side = 2 * (int)radius + 1;
+	for (size_t y = 0; y < height; y++)
+		for (size_t x = 0; x < width; x++) {
+			const size_t centre = (y + r) * AW + x + r, p = y * width + x;
+			const double yp = Y[centre];
+			const double *win = Y.data() + (centre - r * AW - r);
+			if (!(yp == yp) || rmd::despike_settled(rmd::despike_at_or_above(win, (uint32_t)AW, radius, yp), rank, yp)) continue;
+			const int donor = rmd::despike_donor(win, (uint32_t)AW, radius, rank);
+			if (donor < 0) continue;
+			const int dy = donor / side - (int)radius, dx = donor % side - (int)radius;
+			const size_t at = (size_t)((int64_t)centre + dy * (int64_t)AW + dx), q = (size_t)((int64_t)p + dy * (int64_t)width + dx);
+			if (!rmd::despike_is_spike(yp, Y[at], V[at], k, ratio, floor)) continue;
+			replaced[rect_of_pixel[p]]++;
+			for (int c = 0; c < 3; c++) {
+				out_a[p][c] = rmd::despike_dual_take(sums_a[q][c], na[q], na[p]), out_sq_a[p][c] = rmd::despike_dual_take(sums_sq_a[q][c], na[q], na[p]);
+				out_b[p][c] = rmd::despike_dual_take(sums_b[q][c], nb[q], nb[p]), out_sq_b[p][c] = rmd::despike_dual_take(sums_sq_b[q][c], nb[q], nb[p]);
+			}
+		}
+	return replaced;
+}
+
 // tile_luma_error_host and tile_weighted_error_host: the checks, then each rect through the rule's tile_*_rect_host.  measure(S, Q, rect, count): the rule's result
 template <class Result, class Measure>
 static std::vector<Result> tile_measure_host(const std::string &name, const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height,
@@ -1339,7 +1403,16 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 		for (Frame &f : fdev) f = Frame(ctx, W, H, Frame::Features);
 		render_features_on(ctx, *scene, settings, rects, sum_counts(counts_a, counts_b), fdev[0], fdev[1]);
 	}
-	denoise_dual_frame(ctx, settings, W, H, dev, fdev[0], fdev[1], rects, counts_a, counts_b, nullptr, 0, dev[4], tile_errors ? (double *)dev[5] : nullptr);
+	Frame clean[4]; // settings.despike_dual: before anything else, the filter takes the despiked halves in place of the raw ones
+	if (settings.despike_dual) {
+		for (Frame &f : clean) f = Frame(ctx, W, H);
+		check(rmd_despike_dual(ctx, dev[0], dev[1], dev[2], dev[3], (uint32_t)W, (uint32_t)H, rects.data(), counts_a.data(), counts_b.data(), (uint32_t)rects.size(),
+		                       settings.despike_radius, settings.despike_rank, settings.despike_k, settings.despike_ratio, settings.despike_floor, clean[0], clean[1], clean[2],
+		                       clean[3], nullptr),
+		      ctx, "rmd_despike_dual");
+	}
+	denoise_dual_frame(ctx, settings, W, H, settings.despike_dual ? clean : dev, fdev[0], fdev[1], rects, counts_a, counts_b, nullptr, 0, dev[4],
+	                   tile_errors ? (double *)dev[5] : nullptr);
 	if (tile_errors) {
 		tile_errors->assign(rects.size(), 0.0);
 		check(rmd_tile_error_dual(ctx, dev[5], (uint32_t)W, (uint32_t)H, rects.data(), (uint32_t)rects.size(), tile_errors->data()), ctx, "rmd_tile_error_dual");

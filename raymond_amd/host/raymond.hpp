@@ -226,11 +226,17 @@ struct Settings { // src/trace.rs:42-55 (+ the RNG seed the reference lacks)
 	// >= 0, despike_ratio finite and >= 1, despike_floor finite and >= 0) before the plain divide, denoise, denoise_features or denoise_atrous; the passes then
 	// render with second moments, as for denoise.  The adaptive_threshold check despikes all tiles at their current counts into two spare buffers and runs
 	// rmd_tile_error on those (worker_count == 1 only); the sums the passes add to, every message's data and the previews stay the raw sums.  render_tiled
-	// throws for values out of range whether or not the setting is on, with denoise_dual (the halves are not yet despiked) and with adaptive_threshold on
+	// throws for values out of range whether or not the setting is on, with denoise_dual (whose halves despike_dual despikes) and with adaptive_threshold on
 	// several workers.  2, 2, 6, 2 and 0 are values to start from.
 	bool despike = false;
 	uint32_t despike_radius = 2, despike_rank = 2;
 	double despike_k = 6.0, despike_ratio = 2.0, despike_floor = 0.0;
+	// Firefly rejection for the two halves of the dual-buffer paths (false = off: no buffer, launch or copy is added; needs denoise_dual), at the five
+	// despike_* values above (raymond_hip.h: rmd_despike_dual).  await() despikes the assembled halves on its GPU before whichever dual filter the settings
+	// choose.  In the dual loop every call of the dual filter — the adaptive check and the filtered preview — reads despiked copies: four spare buffers,
+	// filled once per pass by one rmd_despike_dual call over the whole frame, finished tiles at the counts they finished with and live tiles at n_A / n_B.
+	// The sums the passes add to, every message's data, raw previews and the auto-exposure histogram stay the raw sums.
+	bool despike_dual = false;
 };
 // What render_tiled refuses in the preview settings (it throws this text as a raymond::Error); empty: nothing.  One policy with raymond_amd/scene.py's
 // Settings.check_preview.
@@ -370,6 +376,13 @@ rmd_luma_histogram luminance_histogram(const std::vector<Vector3> &image);
 std::vector<uint32_t> despike_host(const std::vector<Vector3> &sums, const std::vector<Vector3> &sums_sq, size_t width, size_t height, const std::vector<rmd_tile_rect> &rects,
                                    const std::vector<uint32_t> &counts, uint32_t radius, uint32_t rank, double k, double ratio, double floor,
                                    std::vector<Vector3> &out_sums, std::vector<Vector3> &out_sums_sq);
+// rmd_despike_dual on the host, from the headers the kernel is built from (raymond_amd/csrc/despike_dual_rule.hpp over despike_rule.hpp): the two halves'
+// sums and sums of squares in, the four despiked buffers out (resized), the spikes per rect returned.  Checked: the sizes, the radius and that no rect's two
+// counts add past 2^32 - 1; rects are inside the frame and disjoint.  What raymond_cli despike-dual runs
+std::vector<uint32_t> despike_dual_host(const std::vector<Vector3> &sums_a, const std::vector<Vector3> &sums_sq_a, const std::vector<Vector3> &sums_b,
+                                        const std::vector<Vector3> &sums_sq_b, size_t width, size_t height, const std::vector<rmd_tile_rect> &rects,
+                                        const std::vector<uint32_t> &counts_a, const std::vector<uint32_t> &counts_b, uint32_t radius, uint32_t rank, double k, double ratio,
+                                        double floor, std::vector<Vector3> &out_a, std::vector<Vector3> &out_sq_a, std::vector<Vector3> &out_b, std::vector<Vector3> &out_sq_b);
 // rmd_tile_luma_error on the host, from the header the kernel is built from (raymond_amd/csrc/tile_luma_rule.hpp: 256 emulated lanes and the kernel's
 // combine): rect i of the width * height sums and sums of squares at counts[i].  No argument is checked beyond the sizes; rects are inside the frame.  What
 // raymond_cli tile-luma-error runs, and what holds the header to the numpy restatement without a GPU

@@ -2,7 +2,7 @@
 
 Bottom up:
   * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike, the denoise family (every rmd_denoise* call is laid out
+  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -272,6 +272,35 @@ def despike_arrays(ctx, sums, sums_sq, rects, counts, **params):
         s, q, s_out, q_out = _staged(stack, ctx, sums, (Framebuffer, sums), (Framebuffer, sums_sq), (Framebuffer, None), (Framebuffer, None))
         _, _, replaced = despike(ctx, s, q, rects, counts, out=(s_out, q_out), **params)
         return s_out.download(), q_out.download(), replaced
+
+
+def despike_dual(ctx, half_a, half_b, rects, counts_a, counts_b, radius=2, rank=2, k=6.0, ratio=2.0, floor=0.0, out=None, want_replaced=True):
+    """rmd_despike_dual: firefly rejection for the two halves of a dual-buffer frame.  half_a and half_b are (Framebuffer S, Framebuffer Q) pairs.  The
+    decision is despike()'s on the merged pixel (S_A + S_B, Q_A + Q_B at n_A + n_B; both halves must hold a sample); a spike takes, half by half, its
+    donor's sums of that half at its own half count, so the halves stay independent sample sets.
+    Returns ((S'_A, Q'_A), (S'_B, Q'_B), replaced): four new sum buffers (the caller closes them), which every dual call takes in place of the inputs with
+    the same rects and counts, and the number of pixels replaced in each rect (uint32 array).  `out`: ((Framebuffer, Framebuffer), (Framebuffer,
+    Framebuffer)) to write into instead of four new ones.  want_replaced=False passes NULL for the counts and returns None for them."""
+    rects = list(rects)
+    counts_a, counts_b = _counts(rects, counts_a, counts_b, what="one sample count per rect and half")
+    W, H = half_a[0].width, half_a[0].height
+    with contextlib.ExitStack() as made:
+        if out is None:
+            out = tuple((made.enter_context(Framebuffer(ctx, W, H)), made.enter_context(Framebuffer(ctx, W, H))) for _ in range(2))
+        replaced = np.zeros(max(1, len(rects)), dtype=np.uint32) if want_replaced else None
+        ctx.check(ctx.L.rmd_despike_dual(ctx.handle, half_a[0].ptr, half_a[1].ptr, half_b[0].ptr, half_b[1].ptr, W, H, tile_array(rects), _u32(counts_a),
+                                         _u32(counts_b), len(rects), int(radius), int(rank), float(k), float(ratio), float(floor), out[0][0].ptr, out[0][1].ptr,
+                                         out[1][0].ptr, out[1][1].ptr, _u32(replaced)))
+        made.pop_all()  # (the call went through: the new buffers are the caller's)
+    return (out[0][0], out[0][1]), (out[1][0], out[1][1]), None if replaced is None else replaced[: len(rects)]
+
+
+def despike_dual_arrays(ctx, sums_a, sums_sq_a, sums_b, sums_sq_b, rects, counts_a, counts_b, **params):
+    """despike_dual() for host arrays: four (H, W, 3) arrays in; the four despiked ones, in the same order, and the per-rect replaced counts out."""
+    with contextlib.ExitStack() as stack:
+        bufs = _staged(stack, ctx, sums_a, (Framebuffer, sums_a), (Framebuffer, sums_sq_a), (Framebuffer, sums_b), (Framebuffer, sums_sq_b), *[(Framebuffer, None)] * 4)
+        _, _, replaced = despike_dual(ctx, bufs[0:2], bufs[2:4], rects, counts_a, counts_b, out=(bufs[4:6], bufs[6:8]), **params)
+        return bufs[4].download(), bufs[5].download(), bufs[6].download(), bufs[7].download(), replaced
 
 
 TILE_LUMA_DTYPE = np.dtype([("tile_rms", "<f8"), ("pixel_rms", "<f8"), ("mean_luma", "<f8"), ("mean_variance", "<f8"), ("mean_rel_variance", "<f8"),
@@ -861,6 +890,9 @@ class TaskHandle:  # src/trace.rs:70-135
             counts_b.append(t.count_b)
         counts_f = [a + b for a, b in zip(counts_a, counts_b)]
         with Context(self.device) as ctx:
+            if st.despike_dual:  # before anything else: whichever dual filter is on takes the despiked halves in place of the raw ones
+                st.check_despike()
+                halves = list(despike_dual_arrays(ctx, *halves, rects, counts_a, counts_b, want_replaced=False, **st.despike_keywords())[:4])
             feats = finished_tile_features(ctx, self.scene, st, rects, counts_f) if featured else None
             if st.denoise_dual_atrous:
                 out, _ = denoise_atrous_dual_arrays(ctx, *halves, rects, counts_a, counts_b, **st.atrous_keywords(), **_guide(st, feats, counts_f, atrous=True))
@@ -1129,6 +1161,10 @@ class _DualLoop:
         # the feature buffers (sums, sums of squares) the guided check reads, or None: this loop keeps none
         self.feat_fbs = [stack.enter_context(FeatureBuffer(ctx, W, H)) for _ in range(2)] if self.adaptive and st.denoise_dual_features else None
         self.preview_fb = stack.enter_context(Framebuffer(ctx, W, H)) if st.preview_every and st.preview_denoise else None
+        # despike_dual: four spare buffers for the despiked halves every dual filter call of this loop reads (the check, the filtered preview); the passes' own stay raw
+        filters = self.adaptive or self.preview_fb is not None
+        self.spare = [stack.enter_context(Framebuffer(ctx, W, H)) for _ in range(4)] if st.despike_dual and filters else None
+        self.despiked_at = None  # the pass whose despiked halves the spare buffers hold
         self.live = generate_tiles(W, H, st.tile_size)
         self.done_rects, self.done_a, self.done_b = [], [], []  # the finished tiles and the counts they finished with
         self.n_half = [0, 0]  # samples per pixel of a live tile in A and B
@@ -1154,11 +1190,22 @@ class _DualLoop:
         st = self.st
         rects, all_a, all_b = self.whole_frame(live)
         guide = _guide(st, self.feat_fbs, [a + b for a, b in zip(all_a, all_b)], atrous)
-        halves = ((self.fbs[0], self.fbs[1]), (self.fbs[2], self.fbs[3]))
+        halves = self.filter_halves(rects, all_a, all_b)
         if atrous:
             denoise_atrous_dual(self.ctx, *halves, rects, all_a, all_b, out_fb, err_img, **st.atrous_keywords(), **guide, **where)
         else:
             denoise_dual(self.ctx, *halves, rects, all_a, all_b, out_fb, err_img, **where, **st.nlm_keywords(), **guide)
+
+    def filter_halves(self, rects, all_a, all_b):
+        """The two halves a dual filter call of this pass reads: the loop's own, or with despike_dual the despiked halves of the whole frame at its counts,
+        made once a pass by one rmd_despike_dual call (a later call of the same pass has the same tiles at the same counts)."""
+        if self.spare is None:
+            return (self.fbs[0], self.fbs[1]), (self.fbs[2], self.fbs[3])
+        out = (self.spare[0], self.spare[1]), (self.spare[2], self.spare[3])
+        if self.despiked_at != self.passes:
+            despike_dual(self.ctx, (self.fbs[0], self.fbs[1]), (self.fbs[2], self.fbs[3]), rects, all_a, all_b, out=out, want_replaced=False, **self.st.despike_keywords())
+            self.despiked_at = self.passes
+        return out
 
     def check_weights(self):
         """adaptive_display_auto_exposure: before a check, one histogram of the whole frame on the RAW sums — S_A with S_B as the second buffer, live tiles at
@@ -1263,7 +1310,12 @@ def _render_tiled_dual(scene, settings, devices):
     With settings.preview_every > 0 a Message.FramePreview follows the snapshots of every preview_every-th pass that leaves live tiles: the two halves'
     sums added on the device (rmd_resolve_tonemap_tiles with the other half as its second buffer) at n_A + n_B, finished tiles at the counts they
     finished with; with settings.preview_denoise, rmd_denoise_atrous_dual's frame at those counts, guided when this loop keeps the feature buffers.  With
-    settings.preview_auto_exposure the exposure comes from rmd_luminance_histogram_tiles on what that resolve call takes, as in render_tiled."""
+    settings.preview_auto_exposure the exposure comes from rmd_luminance_histogram_tiles on what that resolve call takes, as in render_tiled.
+
+    With settings.despike_dual every call of the dual filter this loop makes — the adaptive check, the filtered preview — reads despiked copies of the
+    halves: four spare buffers, filled once per pass by one rmd_despike_dual call over the whole frame (finished tiles at the counts they finished with,
+    live ones at n_A / n_B); the region forms then filter the live tiles of those copies.  The sums the passes add to, the TileFinished / TileProgressed
+    data, raw previews and the auto-exposure histogram stay the raw sums; await_() despikes the assembled halves itself."""
     if len(devices) != 1:
         raise ValueError("denoise_dual renders on one device: the filter's window crosses the tiles that several devices would own")
     with contextlib.ExitStack() as stack:

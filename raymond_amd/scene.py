@@ -252,7 +252,7 @@ class Settings:
                  auto_exposure_percentile=0.99, auto_exposure_target=0.8, denoise_feature_slope=0.0,
                  denoise_atrous_slope=0.0, despike=False, despike_radius=2, despike_rank=2, despike_k=6.0, despike_ratio=2.0, despike_floor=0.0,
                  adaptive_measure="channel_max", adaptive_display_threshold=0.0, adaptive_display_exposure=1.0, adaptive_display_gamma=2.2,
-                 adaptive_display_floor=1.0 / 255.0, adaptive_display_auto_exposure=False, adaptive_denoised_display_threshold=0.0):
+                 adaptive_display_floor=1.0 / 255.0, adaptive_display_auto_exposure=False, adaptive_denoised_display_threshold=0.0, despike_dual=False):
         self.camera_settings = camera_settings
         self.sample_count = int(sample_count)
         self.tile_size = (int(tile_size[0]), int(tile_size[1]))
@@ -378,13 +378,20 @@ class Settings:
         # despike_ratio and despike_floor) before the plain divide, denoise, denoise_features or denoise_atrous; render_tiled then renders with second
         # moments, as for denoise.  The adaptive_threshold check despikes all tiles at their current counts into two spare buffers and runs rmd_tile_error on
         # those (one device only); the sums the passes add to, the TileFinished / TileProgressed data and the previews stay the raw sums.  Refused with
-        # denoise_dual: the halves are not yet despiked.  2, 2, 6, 2 and 0 are values to start from.
+        # denoise_dual, whose halves despike_dual (below) despikes.  2, 2, 6, 2 and 0 are values to start from.
         self.despike = bool(despike)
         self.despike_radius = despike_radius
         self.despike_rank = despike_rank
         self.despike_k = float(despike_k)
         self.despike_ratio = float(despike_ratio)
         self.despike_floor = float(despike_floor)
+        # Firefly rejection for the two halves of the dual-buffer paths (an extension; False = off: no buffer, launch or copy is added; needs denoise_dual).
+        # It reads despike_radius, despike_rank, despike_k, despike_ratio and despike_floor (raymond_hip.h: rmd_despike_dual).  await_()
+        # despikes the assembled halves on its device before whichever dual filter the settings choose; in the dual loop every call of the dual filter — the
+        # adaptive check and the filtered preview — reads despiked copies, four spare buffers filled once per pass by one call over the whole frame, finished
+        # tiles at the counts they finished with and live tiles at n_A / n_B.  The sums the passes add to, the TileFinished / TileProgressed data, raw
+        # previews and the auto-exposure histogram stay the raw sums.  `despike` itself stays refused with denoise_dual.
+        self.despike_dual = bool(despike_dual)
         self.check_despike()
 
     def despike_keywords(self):
@@ -411,6 +418,8 @@ class Settings:
             raise ValueError("despike with adaptive_threshold renders on one device: the window crosses the tiles that several devices would own")
         if self.despike and self.adaptive_display_threshold > 0.0 and n_devices != 1:
             raise ValueError("despike with adaptive_display_threshold renders on one device: the window crosses the tiles that several devices would own")
+        if self.despike_dual and not self.denoise_dual:  # (after every older rule: each of their texts is still raised first)
+            raise ValueError("despike_dual needs denoise_dual: it despikes the two halves")
 
     def select_candidates(self):
         """The candidates of denoise_dual_select, as render.denoise_dual_select takes them: the unguided filter at denoise_k, and the guided one at k = 1.0

@@ -2,6 +2,8 @@
 
 * `reflective_spheres()`  — the README's ReflectiveSpheres scene, reconstructed from the commented-out
   sphere in cli_old/src/main.rs:56-58 plus the live objects of :48-55 and :77-127.
+* `firefly_spheres()`     — reflective_spheres() plus one small, very bright emitter that no primary ray sees: fireflies by construction
+  (no benchmark configuration).
 * `gold_dragon_standin()` — cli_old/src/main.rs:45-127 verbatim, with the missing assets/meshes/dragon_vrip.ply
   replaced by a deterministic procedural closed mesh of ~100k triangles.
 The mesh generator uses only IEEE-exact operations (+ - * / sqrt), so it yields bit-identical
@@ -31,6 +33,19 @@ def reflective_spheres():
     scene.objects.append(Object(Sphere((-1.0, -0.5, 3.5), 0.5), Material.Diffuse((1.0, 0.0, 0.0), 0.02)))
     scene.objects.append(Object(Sphere((0.74, -0.25, 3.5), 0.75), Material.Metal((0.05, 0.25, 1.0), 0.01)))
     scene.objects.extend(_room_planes())
+    return scene
+
+
+FIREFLY_EMITTER = ((0.0, 1.0, -1.0), 0.05, (1500.0, 1500.0, 1500.0))  # centre, radius, emission: 1000 times the ceiling's radiance
+
+
+def firefly_spheres():
+    """reflective_spheres() plus one small emitting sphere behind the camera that no primary ray sees (tests/test_firefly_scene_host.py checks it with the
+    oracle): its light reaches the image only through a bounce that happens to hit it, and with no next-event estimation in this renderer that is a firefly
+    by construction.  The emitter is the scene's LAST object, so every other object keeps its index.  Python only; not a benchmark configuration."""
+    scene = reflective_spheres()
+    centre, radius, emission = FIREFLY_EMITTER
+    scene.objects.append(Object(Sphere(centre, radius), Material.Emission(emission, (1.0, 1.0, 1.0), 0.27, 0.0)))
     return scene
 
 
