@@ -181,6 +181,11 @@ SIGNATURES = {
         [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double,
          _vp, _vp, _P(C.c_uint32)],
     ),
+    "rmd_despike_dual": (
+        C.c_int32,
+        [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
+         C.c_double, C.c_double, _vp, _vp, _vp, _vp, _P(C.c_uint32)],
+    ),
     "rmd_tile_luma_error": (
         C.c_int32,
         [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), C.c_uint32, C.c_double, _P(abi.TileLuma)],
@@ -205,16 +210,6 @@ SIGNATURES = {
     "rmd_grid_build_describe": (C.c_int32, [_vp, _P(abi.GridDesc)]),
     "rmd_grid_build_destroy": (None, [_vp]),
 }
-# Entry points declared after tests/golden/binding_trace.json was recorded.  SIGNATURES is the set that recording is held to be complete for
-# (tests/test_binding_trace.py) and the set its stand-in library is made from; the recording's scenarios never reach these calls, so they are kept apart
-# until it is made again.  load() declares both tables alike; tests/test_despike_dual_host.py records these calls on the same stand-in.
-SIGNATURES_SINCE_RECORDING = {
-    "rmd_despike_dual": (
-        C.c_int32,
-        [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, _P(abi.TileRect), _P(C.c_uint32), _P(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint32, C.c_double,
-         C.c_double, C.c_double, _vp, _vp, _vp, _vp, _P(C.c_uint32)],
-    ),
-}
 
 
 class RaymondError(RuntimeError):
@@ -234,7 +229,7 @@ def load():
             "(there is no CPU fallback)" % LIB_PATH
         )
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SINCE_RECORDING.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

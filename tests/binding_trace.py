@@ -4,8 +4,15 @@ FakeLibrary builds, for every name in lib.SIGNATURES, a ctypes.CFUNCTYPE(restype
 of raymond_amd/render.py exactly as it would for the real library; no .so and no GPU is needed.  A call is recorded as one line, `name(arg, ...)`:
 scalars as they arrive; what a pointer points to and never its address — rect, count, candidate and slope arrays as lists, the camera and settings
 structs as their fields —; device objects as the label their fake constructor handed out (ctx0, scene0, fb3, feat1).  Host outputs are filled
-deterministically: downloads with ones, rmd_tile_error[_dual] from `tile_errors`, rmd_despike's counts with 1, 2, ..., histograms with one bin, and
+deterministically: downloads with ones, rmd_tile_error[_dual] from `tile_errors`, rmd_despike[_dual]'s counts with 1, 2, ..., histograms with one bin, and
 rmd_exposure_from_histogram with a value that differs from call to call, so that a trace shows which exposure reaches which resolve call.
+
+The three tile measures (rmd_tile_luma_error, rmd_tile_weighted_error[_dual]) fill their per-rect structs from `tile_errors` as well, each deciding
+field at its own offset from the hook's value e — tile_rms = e + 1/8, pixel_rms = e + 1/4; rms = e + 1/8, mean_weighted_variance = e + 3/8 —, so that both
+stay on e's side of the scenarios' threshold of 0.5 and a message's Tile.error shows which field the loop read; `valid` is the rect's pixel count, every
+other field 0.  rmd_display_weights fills all abi.LUMA_WEIGHTS entries with 1024 * exposure + gamma + display_floor.  A weight table, going out or coming
+in, is recorded as `weights(<entry>)` when all its entries are equal (`weights(<first>..<last>)` otherwise), so that a trace shows which exposure's table
+reached which measure call.
 
 `with installed() as fake:` makes raymond_amd.lib.load() return the fake for the duration.  SCENARIOS maps a name to a function of the fake that drives
 render.py and returns further lines (messages, results); run(name) gives a scenario's whole trace.  tools/record_binding_trace.py writes the golden
@@ -38,6 +45,16 @@ def _rect_pixels(ptr, n):
     return sum(ptr[i].width * ptr[i].height for i in range(n))
 
 
+def _weights_token(ptr):
+    table = [ptr[i] for i in range(abi.LUMA_WEIGHTS)]
+    return "weights(%r)" % table[0] if all(v == table[0] for v in table) else "weights(%r..%r)" % (table[0], table[-1])
+
+
+_TABLES = {"rmd_tile_weighted_error": 8, "rmd_tile_weighted_error_dual": 7, "rmd_display_weights": 3}  # entry point: the argument that is a weight table
+_MEASURES = {"rmd_tile_luma_error": (("tile_rms", 0.125), ("pixel_rms", 0.25)), "rmd_tile_weighted_error": (("rms", 0.125), ("mean_weighted_variance", 0.375)),
+             "rmd_tile_weighted_error_dual": (("rms", 0.125), ("mean_weighted_variance", 0.375))}  # entry point: its deciding fields, and what each adds to tile_errors
+
+
 def _fill(kind, address, n, value):
     if address and n:
         np.ctypeslib.as_array((kind * n).from_address(address))[:] = value
@@ -46,7 +63,7 @@ def _fill(kind, address, n, value):
 class FakeLibrary:
     def __init__(self):
         self.fail = ()  # entry points whose names start with one of these return RMD_ERR_INVALID_ARGUMENT (after being recorded)
-        self.tile_errors = lambda rect, check: 1.0  # rmd_tile_error[_dual]: the error of tile `rect` at the check-th call of that entry point
+        self.tile_errors = lambda rect, check: 1.0  # rmd_tile_error[_dual] and the tile measures: the error of tile `rect` at the check-th call of that entry point
         self.reset()
         for name, (res, args) in lib.SIGNATURES.items():
             if res is C.c_char_p:  # (not a callback's result type)
@@ -90,6 +107,8 @@ class FakeLibrary:
                     shown.append([_fields(a[j]) for j in range(args[count_after(i)])])
                 elif t._type_ in (C.c_uint32, C.c_double) and any(argtypes[j] is C.c_uint32 for j in range(i + 1, len(argtypes))):
                     shown.append(list(a[: args[count_after(i)]]))
+                elif _TABLES.get(name) == i:
+                    shown.append(None)  # (read below, once the stand-in has written what it writes)
                 elif t._type_ is abi.LumaHistogram and name == "rmd_exposure_from_histogram":
                     shown.append("hist(pixels=%d)" % a[0].pixels)
                 else:
@@ -99,6 +118,8 @@ class FakeLibrary:
             failed = any(name.startswith(f) for f in self.fail)
             if not failed:
                 self._act(name, args, check)
+            if name in _TABLES and args[_TABLES[name]]:
+                shown[_TABLES[name]] = _weights_token(args[_TABLES[name]])
             if name in _RELEASES:
                 self.live.remove(shown[-1])
             self.lines.append("%s(%s)%s" % (name, _show(shown)[1:-1], " -> 1" if failed else ""))
@@ -117,8 +138,17 @@ class FakeLibrary:
         elif name in ("rmd_tile_error", "rmd_tile_error_dual"):
             rects, n, out = a[-3], a[-2], a[-1]
             _fill(C.c_double, out, n, [self.tile_errors(tuple(_fields(rects[i])), check) for i in range(n)])
-        elif name == "rmd_despike" and a[-1]:
-            for i in range(a[7]):
+        elif name in _MEASURES:
+            rects, n, out = a[5], a[6 if name.endswith("_dual") else 7], a[-1]
+            for i in range(n):
+                e = self.tile_errors(tuple(_fields(rects[i])), check)
+                for field, offset in _MEASURES[name]:
+                    setattr(out[i], field, e + offset)
+                out[i].valid = rects[i].width * rects[i].height
+        elif name == "rmd_display_weights":
+            _fill(C.c_double, C.addressof(a[3].contents), abi.LUMA_WEIGHTS, 1024.0 * a[0] + a[1] + a[2])
+        elif name in ("rmd_despike", "rmd_despike_dual") and a[-1]:
+            for i in range(a[7 if name == "rmd_despike" else 10]):
                 a[-1][i] = i + 1
         elif name == "rmd_resolve_tonemap":
             _fill(C.c_uint8, a[7], 3 * a[2] * a[3], 128)
@@ -371,6 +401,55 @@ def _(b, lines):
     _raises(lines, render.luminance_histogram, b.ctx, b.fbs[0], RECTS, COUNTS[:3])
 
 
+TABLE = np.full(abi.LUMA_WEIGHTS, 3.0)  # a weight table no rmd_display_weights call of the stand-in makes
+
+
+@wrapper_scenario("tile_measures")
+def _(b, lines):
+    measures = (("tile_luma_error", lambda tiles, counts, table: render.tile_luma_error(b.ctx, b.fbs[0], b.fbs[1], tiles, counts, 1e-3)),
+                ("tile_weighted_error", lambda tiles, counts, table: render.tile_weighted_error(b.ctx, b.fbs[0], b.fbs[1], tiles, counts, table)),
+                ("tile_weighted_error_dual", lambda tiles, counts, table: render.tile_weighted_error_dual(b.ctx, b.fbs[4], b.err, tiles, table)))
+    lib.load().tile_errors = first_converges
+    for name, measure in measures:
+        for tiles, counts in ((RECTS, COUNTS), (iter(RECTS[:2]), COUNTS[:2]), ([], []), (RECTS, np.array(COUNTS))):
+            lines.append("%s %r" % (name, measure(tiles, counts, TABLE).tolist()))
+        if name != "tile_luma_error":  # (which takes no table)
+            _raises(lines, measure, RECTS, COUNTS, TABLE[:-1])
+        if name != "tile_weighted_error_dual":  # (which takes no counts)
+            _raises(lines, measure, RECTS, COUNTS[:3], TABLE)
+    lib.load().fail = ("rmd_tile_",)
+    for name, measure in measures:
+        _raises(lines, measure, RECTS, COUNTS, TABLE)
+
+
+@wrapper_scenario("display_weights")
+def _(b, lines):
+    for args in ((), (2.0, 1.8, 0.0625)):
+        table = render.display_weights(*args)
+        lines.append("display_weights %r %s of %r" % (table.shape, table.dtype, sorted(set(table.tolist()))))
+        render.tile_weighted_error(b.ctx, b.fbs[0], b.fbs[1], RECTS, COUNTS, table)  # the table handed on is that call's
+        render.tile_weighted_error_dual(b.ctx, b.fbs[4], b.err, RECTS, table)
+    lib.load().fail = ("rmd_display",)
+    _raises(lines, render.display_weights)
+
+
+@wrapper_scenario("despike_dual")
+def _(b, lines):
+    a, bb, n = render.despike_dual(b.ctx, b.half_a, b.half_b, RECTS, COUNTS, COUNTS_B)
+    lines.append("new buffers %s, replaced %r" % (len({id(fb) for fb in a + bb + b.half_a + b.half_b}) == 8, n.tolist()))
+    for fb in a + bb:
+        fb.close()
+    outs = ((b.fbs[4], b.fbs[5]), (b.feats[0], b.feats[1]))  # (the stand-in asks no kind of a buffer: four labels that differ)
+    a, bb, n = render.despike_dual(b.ctx, b.half_a, b.half_b, iter(RECTS[:2]), COUNTS[:2], COUNTS_B[:2], 3, 1, 5.0, 1.5, 0.25, out=outs, want_replaced=False)
+    lines.append("out given back %s, replaced %r" % ((a, bb) == outs, n))
+    a, bb, n = render.despike_dual(b.ctx, b.half_a, b.half_b, [], [], [], out=outs)
+    lines.append("zero rects: replaced %r" % n.tolist())
+    _raises(lines, render.despike_dual, b.ctx, b.half_a, b.half_b, RECTS, COUNTS[:3], COUNTS_B)
+    _raises(lines, render.despike_dual, b.ctx, b.half_a, b.half_b, RECTS, COUNTS, COUNTS_B[:3])
+    lib.load().fail = ("rmd_despike_dual",)
+    _raises(lines, render.despike_dual, b.ctx, b.half_a, b.half_b, RECTS, COUNTS, COUNTS_B)  # its four new buffers are freed
+
+
 # ---- the *_arrays helpers: the order of alloc, upload, call, download and free; with the filter call failing, the frees still happen
 def _shapes(res):
     if isinstance(res, dict):
@@ -387,7 +466,7 @@ def arrays_scenario(name, fn, cases):
             lines = []
             with render.Context(0) as ctx:
                 if failing:
-                    fake.fail = ("rmd_denoise", "rmd_despike")
+                    fake.fail = ("rmd_denoise", "rmd_despike", "rmd_tile_")
                     _raises(lines, fn, ctx, *args, **kwargs)
                 else:
                     lines.append("-> %r" % (_shapes(fn(ctx, *args, **kwargs)),))
@@ -403,6 +482,15 @@ HALVES = (S3, S3, S3, S3)
 arrays_scenario("despike_arrays", render.despike_arrays, {
     "plain": ((S3, S3, RECTS, COUNTS), {}),
     "params": ((S3, S3, RECTS[:2], COUNTS[:2]), dict(radius=1, rank=0, k=5.0, ratio=1.5, floor=0.5, want_replaced=False))})
+arrays_scenario("despike_dual_arrays", render.despike_dual_arrays, {
+    "plain": ((*HALVES, RECTS, COUNTS, COUNTS_B), {}),
+    "params": ((*HALVES, RECTS[:2], COUNTS[:2], COUNTS_B[:2]), dict(radius=1, rank=0, k=5.0, ratio=1.5, floor=0.5, want_replaced=False))})
+arrays_scenario("tile_luma_error_arrays", render.tile_luma_error_arrays, {
+    "plain": ((S3, S3, RECTS, COUNTS, 1e-3), {}),
+    "some": ((S3, S3, iter(RECTS[1:3]), np.array(COUNTS[1:3]), 0.5), {})})
+arrays_scenario("tile_weighted_error_arrays", render.tile_weighted_error_arrays, {
+    "plain": ((S3, S3, RECTS, COUNTS, TABLE), {}),
+    "some": ((S3, S3, iter(RECTS[1:3]), np.array(COUNTS[1:3]), TABLE.tolist()), {})})
 arrays_scenario("denoise_arrays", render.denoise_arrays, {
     "plain": ((S3, S3, RECTS, COUNTS), {}),
     "params": ((S3, S3, RECTS, COUNTS), dict(radius=4, patch_radius=2, k=0.5, alpha=0.75))})
@@ -500,6 +588,20 @@ loop_scenario("preview_denoise", preview_every=1, preview_denoise=True, denoise_
 loop_scenario("preview_auto_exposure", preview_every=1, preview_auto_exposure=True, sample_count=3, auto_exposure_percentile=0.9, auto_exposure_target=0.5)
 loop_scenario("preview_denoise_auto_exposure", preview_every=1, preview_denoise=True, preview_auto_exposure=True)
 
+LUMA = dict(sample_count=3, adaptive_threshold=0.5, errors=first_converges)
+DISPLAY = dict(sample_count=3, adaptive_display_threshold=0.5, errors=first_converges)
+AUTO = dict(DISPLAY, adaptive_display_auto_exposure=True, auto_exposure_percentile=0.9, auto_exposure_target=0.5, adaptive_display_gamma=1.8, adaptive_display_floor=0.0625)
+DESPIKE = dict(despike_radius=1, despike_rank=1, despike_k=5.0, despike_ratio=1.5, despike_floor=0.25)
+loop_scenario("adaptive_luma_tile", adaptive_measure="luma_tile", adaptive_floor=0.25, **LUMA)
+loop_scenario("adaptive_luma_pixel", adaptive_measure="luma_pixel", **LUMA)
+loop_scenario("adaptive_display", adaptive_display_exposure=2.0, adaptive_display_gamma=1.8, adaptive_display_floor=0.0625, **DISPLAY)
+loop_scenario("adaptive_display_auto_exposure", **AUTO)
+loop_scenario("adaptive_display_auto_exposure_two_devices", devices=(0, 1), **AUTO)
+loop_scenario("despike_adaptive_luma_tile", despike=True, adaptive_measure="luma_tile", **DESPIKE, **LUMA)
+loop_scenario("despike_adaptive_display", despike=True, adaptive_display_exposure=2.0, **DESPIKE, **DISPLAY)
+loop_scenario("despike_adaptive_display_auto_exposure", despike=True, **DESPIKE, **AUTO)
+loop_scenario("preview_adaptive_display_auto_exposure", preview_every=1, preview_auto_exposure=True, **AUTO)
+
 DUAL = dict(denoise=True, denoise_dual=True, sample_count=4)
 DUAL_ADAPTIVE = dict(DUAL, adaptive_denoised_threshold=0.5, adaptive_min_samples=2, sample_count=6, errors=first_converges)
 loop_scenario("dual", **DUAL, denoise_radius=4, denoise_patch=2, denoise_k=0.5, denoise_alpha=0.75)
@@ -525,6 +627,20 @@ loop_scenario("dual_preview_denoise", **DUAL, preview_every=1, preview_denoise=T
 loop_scenario("dual_preview_denoise_adaptive_features", **DUAL_ADAPTIVE, preview_every=1, preview_denoise=True, denoise_dual_features=True)
 loop_scenario("dual_preview_denoise_adaptive_atrous_slope", **DUAL_ADAPTIVE, preview_every=2, preview_denoise=True, denoise_dual_atrous=True,
               denoise_dual_features=True, denoise_atrous_slope=3.0)
+DUAL_DISPLAY = dict(DUAL, adaptive_denoised_display_threshold=0.5, adaptive_min_samples=2, sample_count=6, errors=first_converges)
+DUAL_AUTO = dict(DUAL_DISPLAY, adaptive_display_auto_exposure=True, auto_exposure_percentile=0.9, auto_exposure_target=0.5, adaptive_display_gamma=1.8)
+loop_scenario("dual_adaptive_display", **DUAL_DISPLAY, adaptive_display_exposure=2.0, adaptive_display_gamma=1.8, adaptive_display_floor=0.0625)
+loop_scenario("dual_adaptive_display_features", **DUAL_DISPLAY, denoise_dual_features=True, denoise_feature_k=1.5, denoise_feature_tau=0.02)
+loop_scenario("dual_adaptive_display_atrous", **DUAL_DISPLAY, denoise_dual_atrous=True)
+loop_scenario("dual_adaptive_display_atrous_region", **DUAL_DISPLAY, denoise_dual_atrous=True, denoise_dual_atrous_region=True)
+loop_scenario("dual_adaptive_display_auto_exposure", **DUAL_AUTO)
+loop_scenario("dual_adaptive_display_no_progress_tiles", **DUAL_DISPLAY, progress_tiles=False)
+loop_scenario("dual_despike", **DUAL, despike_dual=True, **DESPIKE)
+loop_scenario("dual_despike_adaptive", **DUAL_ADAPTIVE, despike_dual=True, **DESPIKE)
+loop_scenario("dual_despike_adaptive_atrous_region", **DUAL_ADAPTIVE, despike_dual=True, denoise_dual_atrous=True, denoise_dual_atrous_region=True)
+loop_scenario("dual_despike_select", **DUAL, despike_dual=True, denoise_dual_select=True)
+loop_scenario("dual_despike_preview_denoise", **DUAL_ADAPTIVE, despike_dual=True, preview_every=1, preview_denoise=True)
+loop_scenario("dual_despike_adaptive_display_auto_exposure", **DUAL_AUTO, despike_dual=True)
 
 
 @scenario("render_tiled/failing_pass")
@@ -551,6 +667,45 @@ def _(fake):
     _raises(lines, handle.await_)
     handle = render.TaskHandle(_settings(**DUAL, denoise_dual_select=True), [])
     return _raises(lines, handle.await_)
+
+
+def _later(**changed):
+    """Settings that were valid when made and had `changed` set afterwards: what only render_tiled's own checks can refuse."""
+    st = _settings()
+    for name, value in changed.items():
+        setattr(st, name, value)
+    return st
+
+
+@scenario("render_tiled/refusals_measures")
+def _(fake):
+    """Every rule of check_adaptive, check_denoise and check_despike that names adaptive_measure, adaptive_display_*, adaptive_denoised_display_threshold or
+    despike_dual, by its text; none of them opens a device first."""
+    dual = dict(denoise=True, denoise_dual=True)
+    lines = []
+    for devices, changed in (
+            ((0,), dict(adaptive_measure="median")),
+            ((0,), dict(adaptive_measure=None)),
+            ((0,), dict(adaptive_display_threshold=-0.5)),
+            ((0,), dict(adaptive_display_threshold=float("nan"))),
+            ((0,), dict(adaptive_display_threshold=0.5, samples_per_iteration=0)),
+            ((0,), dict(adaptive_display_threshold=0.5, adaptive_threshold=0.5)),
+            ((0,), dict(adaptive_display_threshold=0.5, adaptive_measure="luma_tile")),
+            ((0,), dict(adaptive_display_exposure=0.0)),
+            ((0,), dict(adaptive_display_gamma=float("inf"))),
+            ((0,), dict(adaptive_display_floor=1.0)),
+            ((0,), dict(dual, adaptive_measure="luma_pixel")),
+            ((0,), dict(dual, adaptive_display_threshold=0.5)),
+            ((0,), dict(dual, adaptive_denoised_display_threshold=float("inf"))),
+            ((0,), dict(adaptive_denoised_display_threshold=0.5, samples_per_iteration=0)),
+            ((0,), dict(adaptive_denoised_display_threshold=0.5)),
+            ((0,), dict(dual, adaptive_denoised_display_threshold=0.5, adaptive_denoised_threshold=0.5)),
+            ((0,), dict(dual, adaptive_denoised_display_threshold=0.5, adaptive_threshold=0.5)),
+            ((0, 1), dict(despike=True, adaptive_display_threshold=0.5)),
+            ((0,), dict(despike_dual=True))):
+        _raises(lines, render.render_tiled, scenes.reflective_spheres(), _later(**changed), devices)
+        lines.append("C calls so far: %r" % fake.lines)
+    return lines
 
 
 def _releases_sorted(lines):

@@ -1,7 +1,6 @@
 """rmd_despike_dual without a GPU: the export, the C++ mirror (raymond_cli despike-dual: the rule headers driven the way the kernel drives them) against the
 numpy restatement tests/despike_dual_ref.py byte for byte, the hand-derived classes, the restatement told from four wrong readings of the definition, the
 two statements the definition makes true against tests/despike_ref.py, the rule header under the host sanitizers, and the settings rule in both mirrors."""
-import contextlib
 import ctypes as C
 import os
 import re
@@ -11,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import binding_trace as bt
 import despike_dual_frames as frames
 import despike_dual_ref as ref
 import despike_ref
@@ -25,7 +25,7 @@ CLI = os.path.join(ROOT, "raymond_amd", "host", "raymond_cli")
 def test_entry_point_is_exported_and_declared(product_lib):
     out = subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], check=True, capture_output=True, text=True).stdout
     assert re.search(r"\bT rmd_despike_dual\b", out)
-    assert "rmd_despike_dual" in lib.SIGNATURES_SINCE_RECORDING and "rmd_despike_dual" not in lib.SIGNATURES and callable(render.despike_dual) and callable(render.despike_dual_arrays)
+    assert "rmd_despike_dual" in lib.SIGNATURES and callable(render.despike_dual) and callable(render.despike_dual_arrays)
     header = open(os.path.join(ROOT, "include", "raymond_hip.h")).read()
     assert "#define RMD_ABI_VERSION 6" in header and "rmd_status rmd_despike_dual(rmd_context *ctx," in header
     assert re.search(r"rmd_despike, rmd_despike_dual, rmd_tile_luma_error", header)  # in the list of calls that report RMD_ERR_DEVICE_FAULT
@@ -256,33 +256,20 @@ def test_cli_parses_the_flag_and_holds_the_rule_in_the_same_words(cli, tmp_path)
         assert '"' + NEEDS + '"' in open(path).read()  # the same words in both mirrors
 
 
-# ---------------------------------------------------------------- the binding's C calls, on tests/binding_trace.py's recording stand-in
-@contextlib.contextmanager
-def stand_in():
-    """tests/binding_trace.py's stand-in library, which is made from lib.SIGNATURES, with a recorder of the same kind for every entry point declared since
-    its recording was made (lib.SIGNATURES_SINCE_RECORDING): (the module, the stand-in)."""
-    import binding_trace as bt
-
-    with bt.installed() as fake:
-        for name, (res, args) in lib.SIGNATURES_SINCE_RECORDING.items():
-            if not hasattr(fake, name):
-                setattr(fake, name, C.CFUNCTYPE(res, *args)(fake._recorder(name, res, args)))
-        yield bt, fake
-
-
-def test_the_loader_declares_both_tables(product_lib):
+# ---------------------------------------------------------------- the binding's C calls, on tests/binding_trace.py's recording stand-in (bt.installed())
+def test_the_loader_declares_the_entry_point(product_lib):
     fn = product_lib.rmd_despike_dual
-    assert fn.restype is C.c_int32 and len(fn.argtypes) == 21 and list(fn.argtypes) == lib.SIGNATURES_SINCE_RECORDING["rmd_despike_dual"][1]
-    assert not set(lib.SIGNATURES) & set(lib.SIGNATURES_SINCE_RECORDING)
+    assert fn.restype is C.c_int32 and len(fn.argtypes) == 21 and list(fn.argtypes) == lib.SIGNATURES["rmd_despike_dual"][1]
+    assert "rmd_despike_dual" in lib.SIGNATURES and len(lib.SIGNATURES["rmd_despike_dual"][1]) == 21
 
 
 def test_the_wrappers_make_the_call_with_the_arguments_in_the_headers_order():
-    with stand_in() as (bt, fake):
+    with bt.installed() as fake:
         b = bt.Bench()
         try:
             outs = ((b.fbs[4], b.fbs[5]), (b.fbs[0], b.fbs[1]))  # (the stand-in checks no aliasing)
             a, bb, replaced = render.despike_dual(b.ctx, b.half_a, b.half_b, bt.RECTS, bt.COUNTS, bt.COUNTS_B, radius=1, rank=3, k=5.0, ratio=1.5, floor=0.25, out=outs)
-            assert (a, bb) == outs and list(replaced) == [0, 0, 0, 0]
+            assert (a, bb) == outs and list(replaced) == [1, 2, 3, 4]  # (what the stand-in writes: the array that comes back is the one the call was given)
             rects = "[" + ",".join("[%d,%d,%d,%d]" % r for r in bt.RECTS) + "]"
             assert fake.lines[-1] == "rmd_despike_dual(ctx0,fb0,fb1,fb2,fb3,8,6,%s,[2,2,3,3],[1,2,3,4],4,1,3,5.0,1.5,0.25,fb4,fb5,fb0,fb1,out)" % rects
             made = render.despike_dual(b.ctx, b.half_a, b.half_b, bt.RECTS, bt.COUNTS, bt.COUNTS_B, want_replaced=False)  # four new buffers, NULL for the counts
@@ -311,7 +298,7 @@ def test_the_dual_loop_and_await_despike_before_every_filter_call(extra, filter_
     """The dual loop on the stand-in: one rmd_despike_dual call in front of each of the two checks' filter calls and one in front of await_()'s, each filter
     call on that call's four outputs — and with the setting off the same run makes none and allocates four buffers fewer."""
     def run(**kw):
-        with stand_in() as (bt, fake):
+        with bt.installed() as fake:
             fake.tile_errors = bt.first_converges
             handle = render.render_tiled(scenes.reflective_spheres(), bt._settings(**dict(bt.DUAL, adaptive_denoised_threshold=0.5, adaptive_min_samples=2, sample_count=6), **extra, **kw))
             assert fake.live == []
