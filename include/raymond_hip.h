@@ -62,7 +62,7 @@ enum {
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_despike_dual, rmd_tile_luma_error, rmd_tile_weighted_error,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
-	                                 rmd_denoise, rmd_render_features, rmd_denoise_guided, rmd_denoise_dual,
+	                                 rmd_denoise, rmd_render_features, rmd_render_ids, rmd_ids_matte, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
 	                                 rmd_tile_error_dual, rmd_tile_weighted_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
 	                                 rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope,
@@ -405,6 +405,46 @@ rmd_status rmd_render_features(rmd_context *ctx, const rmd_scene *scene, const r
                                const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev);
 rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
                                      const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev);
+/*
+ * FIRST-HIT OBJECT IDS WITH COVERAGE, AND MATTES (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes; a caller finds the
+ * functions by their symbols).  Which object a pixel shows, and how much of the pixel it covers.  A mean of object indices means nothing, so an
+ * ID buffer is a small table per pixel: W*H*RMD_ID_WORDS uint32_t words, pixel-interleaved, the record of pixel i = x + y*W at ids[i*10 ..]:
+ *     words 2j, 2j+1 (j = 0 .. RMD_ID_SLOTS-1)   key_j, count_j
+ *     word 8                                      other
+ *     word 9                                      samples
+ * A key is 0 (an empty slot), o + 1 (object o, the index into rmd_scene_create's `objects`; for a grid object the grid object's own index) or
+ * RMD_ID_MISS (a miss, or a sample for which the thin lens yields no ray: the class rmd_render_features turns into seven zeros).
+ * The rule for one sample with key k: for j = 0, 1, 2, 3 in order — if key_j == k then count_j += 1 and stop; if key_j == 0 then key_j = k,
+ * count_j = 1 and stop.  If no slot took it, other += 1.  Then samples += 1.  So the slots are in first-seen order, empty slots trail, and
+ * sum(count_j) + other == samples.  Every count, `other` and `samples` are modulo 2^32.
+ * A record is 40 bytes = 5 doubles: rmd_id_buffer_alloc allocates a zeroed buffer, and rmd_framebuffer_free / _zero / _download / _upload serve it
+ * as they are with n_doubles = W*H*5.
+ * rmd_render_ids: for every pixel of every rect and s = sample_begin .. sample_begin + sample_count - 1, in that order, the primary ray exactly as
+ * rmd_render_features takes it (Philox block 0, then the lens' rounds under RMD_RENDER_DOF) is intersected with the scene once, and the rule is
+ * applied with the hit's object, or with RMD_ID_MISS.  The contract is rmd_render_features': calls over [0, k) and [k, n) leave the words of one
+ * call over [0, n), the words do not depend on how the rects cut the frame, and a pixel no rect covers keeps its words.  So is the rest: bounce_limit
+ * and the black-path flags are ignored (both together are still refused); ids_dev NULL, tiles NULL with n_tiles > 0, a rect outside the frame or two
+ * rects that overlap are RMD_ERR_INVALID_ARGUMENT, in that order, before the device is touched; a scene whose object table the launch cannot hold
+ * is RMD_ERR_UNSUPPORTED with the buffer untouched; the pass does not change what rmd_last_launch_info and rmd_last_kernel_ms report; rmd_render_ids
+ * waits like rmd_render_features and reports an earlier device fault as it does, the pass itself raises none; the _async form only enqueues.
+ * rmd_ids_matte: `objects` (HOST memory, n_objects <= 2048) is a SET of object indices, RMD_ID_MISS standing for the background; duplicates are
+ * allowed.  Per pixel, c = the sum, as a 64-bit integer, of count_j over the slots whose key is in the set; matte = (double)c / (double)samples, one
+ * correctly rounded division, and 0.0 where samples == 0.  `other` is never counted — which objects it holds is unknown —, and
+ * *other_pixels_host (may be NULL) receives the exact number of pixels with other != 0: at 0 the matte is exact.  Alpha is 1 - matte({RMD_ID_MISS}).
+ * n_objects == 0 writes zeros.  RMD_ERR_INVALID_ARGUMENT before the device is touched, in this order: width or height 0; ids_dev or matte_dev NULL;
+ * objects NULL with n_objects > 0; n_objects > 2048; an entry equal to 0xFFFFFFFE (its key would be RMD_ID_MISS); the two ranges overlapping; then a
+ * NULL context.  The call waits; its scratch (the sorted distinct keys and one counter) stays on the context.
+ */
+#define RMD_ID_SLOTS 4u
+#define RMD_ID_WORDS 10u /* key_0 count_0 .. key_3 count_3 other samples */
+#define RMD_ID_MISS 0xFFFFFFFFu
+rmd_status rmd_id_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, uint32_t **out_dev); /* zeroed W*H*10 words */
+rmd_status rmd_render_ids(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                          const rmd_tile_rect *tiles, uint32_t n_tiles, uint32_t *ids_dev);
+rmd_status rmd_render_ids_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                const rmd_tile_rect *tiles, uint32_t n_tiles, uint32_t *ids_dev);
+rmd_status rmd_ids_matte(rmd_context *ctx, const uint32_t *ids_dev, uint32_t width, uint32_t height, const uint32_t *objects, uint32_t n_objects,
+                         double *matte_dev, uint64_t *other_pixels_host);
 /*
  * rmd_denoise with a FEATURE WEIGHT (Rousselle, Manzi and Zwicker, "Robust Denoising using Feature and Color Information", 2013; an addition
  * within ABI 6).  Everything rmd_denoise defines stays word for word (validity, D(p, q), w_c = exp(-max(0, D)), clamping, sum orders, the output

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <new>
 
+#include "ids_rule.hpp"
 #include "internal.hpp"
 #include "launch.hpp"
 
@@ -657,6 +658,74 @@ rmd_status rmd_render_features(rmd_context *ctx, const rmd_scene *scene, const r
                                const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev) {
 	if (rmd_status s = rmd_render_features_async(ctx, scene, camera, settings, tiles, n_tiles, feat_dev, feat_sq_dev)) return s;
 	return rmd_context_synchronize(ctx);
+}
+
+// First-hit object IDs (ids.hip): rmd_render_features' host side with the ID buffer in place of the two feature buffers
+static rmd_status render_ids_impl(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
+                                  uint32_t n_tiles, uint32_t *ids_dev) {
+	rmd_settings st = *settings;
+	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
+	{
+		const char *why = nullptr;
+		if (!rmd::denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string("rmd_render_ids: ") + why);
+	}
+	if (rmd_status s = bind(ctx)) return s;
+	if (rmd_status s = check_render_args(ctx, scene, camera, &st)) return s;
+	if (rmd_status s = prepare_wave_tiles(ctx, camera, tiles, n_tiles)) return s;
+	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, &st);
+	P.n_work = ctx->n_wave_tiles;
+	// (neither the context's events nor its launch record are touched: rmd_last_kernel_ms / rmd_last_launch_info keep describing the last render)
+	RMD_HIP(ctx, rmd::launch_ids(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), ids_dev));
+	return RMD_OK;
+}
+
+rmd_status rmd_render_ids_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
+                                uint32_t n_tiles, uint32_t *ids_dev) {
+	if (!scene || !camera || !settings) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ids: null scene/camera/settings");
+	if (!ids_dev || (n_tiles && !tiles)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ids: null tiles/ids pointer");
+	return rmd::guarded(ctx, "rmd_render_ids", [&] { return render_ids_impl(ctx, scene, camera, settings, tiles, n_tiles, ids_dev); });
+}
+
+rmd_status rmd_render_ids(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
+                          uint32_t n_tiles, uint32_t *ids_dev) {
+	if (rmd_status s = rmd_render_ids_async(ctx, scene, camera, settings, tiles, n_tiles, ids_dev)) return s;
+	return rmd_context_synchronize(ctx);
+}
+
+// The matte of a set of objects from an ID buffer.  The refusals in the header's order, the context last.  The block: [counter: 16 bytes][keys]
+rmd_status rmd_ids_matte(rmd_context *ctx, const uint32_t *ids_dev, uint32_t width, uint32_t height, const uint32_t *objects, uint32_t n_objects, double *matte_dev,
+                         uint64_t *other_pixels_host) {
+	return rmd::guarded(ctx, "rmd_ids_matte", [&]() -> rmd_status {
+		const std::string name = "rmd_ids_matte: ";
+		if (width == 0 || height == 0) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "width or height is 0");
+		if (!ids_dev || !matte_dev) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "null ids/matte pointer");
+		if (n_objects && !objects) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "null objects with n_objects > 0");
+		if (n_objects > rmd::kIdsMatteMaxObjects) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "more than 2048 objects");
+		std::vector<uint32_t> keys(n_objects);
+		for (uint32_t i = 0; i < n_objects; i++) {
+			if (objects[i] == RMD_ID_MISS - 1u) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "object index 0xFFFFFFFE: its key would be RMD_ID_MISS");
+			keys[i] = rmd::ids_key_of(objects[i]);
+		}
+		const unsigned __int128 n = (unsigned __int128)width * height;
+		if (rmd::any_overlap({{ids_dev, n * RMD_ID_WORDS * sizeof(uint32_t)}, {matte_dev, n * sizeof(double)}}))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "matte_dev overlaps ids_dev");
+		if (rmd_status s = bind(ctx)) return s;
+		std::sort(keys.begin(), keys.end());
+		keys.erase(std::unique(keys.begin(), keys.end()), keys.end()); // duplicates are allowed: it is a set
+		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the call waits for the frame's passes in any case: the keys go up on an idle stream, from pageable memory
+		RMD_HIP(ctx, ctx->ids_matte_scratch.grow(16 + (size_t)rmd::kIdsMatteMaxObjects * sizeof(uint32_t)));
+		unsigned long long *d_other = ctx->ids_matte_scratch.as<unsigned long long>();
+		uint32_t *d_keys = reinterpret_cast<uint32_t *>(ctx->ids_matte_scratch.as<unsigned char>() + 16);
+		RMD_HIP(ctx, hipMemsetAsync(d_other, 0, 16, ctx->stream));
+		if (!keys.empty()) RMD_HIP(ctx, hipMemcpyAsync(d_keys, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+		RMD_HIP(ctx, rmd::launch_ids_matte(ctx->stream, ids_dev, (uint64_t)width * height, d_keys, (uint32_t)keys.size(), matte_dev, d_other));
+		unsigned long long other = 0;
+		RMD_HIP(ctx, hipMemcpyAsync(&other, d_other, sizeof(other), hipMemcpyDeviceToHost, ctx->stream));
+		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (other_pixels_host) *other_pixels_host = other;
+		return rmd::check_fault(ctx);
+	});
 }
 
 rmd_status rmd_render_tiles_host(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,

@@ -150,6 +150,11 @@ rmd_status rmd_framebuffer_alloc(rmd_context *ctx, uint32_t width, uint32_t heig
 rmd_status rmd_feature_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, double **out_dev) {
 	return alloc_zeroed(ctx, "rmd_feature_buffer_alloc: bad argument", width, height, RMD_FEATURE_CHANNELS, out_dev);
 }
+// ID buffers (ids.hip): RMD_ID_WORDS words a pixel, which is a whole number of doubles
+static_assert(RMD_ID_WORDS * sizeof(uint32_t) % sizeof(double) == 0, "an ID record is a whole number of doubles: the framebuffer helpers serve ID buffers");
+rmd_status rmd_id_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, uint32_t **out_dev) {
+	return alloc_zeroed(ctx, "rmd_id_buffer_alloc: bad argument", width, height, RMD_ID_WORDS * sizeof(uint32_t) / sizeof(double), reinterpret_cast<double **>(out_dev));
+}
 rmd_status rmd_framebuffer_free(rmd_context *ctx, double *dev) {
 	if (rmd_status s = bind(ctx)) return s;
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));

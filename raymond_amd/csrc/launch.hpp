@@ -193,6 +193,12 @@ hipError_t launch_tile_error_dual(hipStream_t stream, const double *err, const r
 // added to feat (and their squares to feat_sq when it is not null), W*H*RMD_FEATURE_CHANNELS doubles each
 hipError_t launch_features(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const WaveTile *wave_tiles, double *feat,
                            double *feat_sq);
+// rmd_render_ids (ids.hip): for each of the P.n_work wave tiles, the first-hit keys of samples P.sample_begin .. + P.sample_count - 1 entered into the
+// pixels' records of `ids`, W*H*RMD_ID_WORDS words (ids_rule.hpp: ids_insert)
+hipError_t launch_ids(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const WaveTile *wave_tiles, uint32_t *ids);
+// rmd_ids_matte (ids.hip): matte[i] = pixel i's matte over the n_keys ascending, distinct keys (ids_rule.hpp: ids_matte_pixel; device memory, at most 2048),
+// and *other_pixels (zeroed by the caller) += the pixels whose record has other != 0
+hipError_t launch_ids_matte(hipStream_t stream, const uint32_t *ids, uint64_t n_pixels, const uint32_t *keys, uint32_t n_keys, double *matte, unsigned long long *other_pixels);
 hipError_t launch_render_list(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
                               const ListWork *list, double *rgb_out, int32_t *path_obj, uint32_t *path_sub);
 // tile rectangles of a frame <-> a packed buffer (kernels.hip: tile_copy_kernel); `first[i]` = pixels in front of rect i

@@ -26,6 +26,10 @@
 //                                                                      or --denoise-dual-atrous 1 with --denoise-dual-features 1: the feature-slope term at G
 //                                                                      pixels in rmd_denoise_atrous_slope / rmd_denoise_atrous_dual_slope[_region]; 3 to start from)
 //                                                                    [--dump-features FILE]   (the W*H*7 feature means as raw f64: the AOVs)
+//                                                                    [--dump-ids FILE]   (the W*H*10 first-hit ID words as raw little-endian uint32, rmd_render_ids over
+//                                                                      the finished tiles at their own counts: key_0 count_0 .. key_3 count_3 other samples)
+//                                                                    [--dump-matte FILE --matte-objects 0,3,miss]   (rmd_ids_matte of those words for the listed
+//                                                                      object indices, `miss` the background, as raw f64; prints the pixels whose table overflowed)
 //                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
 //                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
 //                                                                       the image is rmd_denoise_dual's; T: tiles finish by rmd_tile_error_dual)
@@ -86,6 +90,9 @@
 //                                         built from) over the raw W*H*3 f64 filtered means OUT and the W*H f64 error image ERR, under the table as above;
 //                                         rects.txt as for despike, its count column read and ignored; prints per rect
 //                                         "rms mean_weighted_variance mean_luma mean_variance valid invalid", doubles as their 64 bits in hexadecimal
+//   raymond_cli ids-matte IDS.u32 W H LIST OUT.f64
+//                                         rmd_ids_matte made on the host (raymond::ids_matte_host, from the header the kernel is built from; no GPU) over raw
+//                                         W*H*10 uint32 ID words; LIST: object indices and `miss`, comma-separated, or `none`; prints the pixels with other != 0
 //   raymond_cli display-weights EXPOSURE GAMMA FLOOR
 //                                         rmd_display_weights: its 260 weights, one per line, as their 64 bits in hexadecimal
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
@@ -154,6 +161,21 @@ static std::vector<Vector3> consume(TaskHandle &handle, const Settings &st, size
 	for (const Tile &t : finished_tiles) place_tile(t, t.data, W, image, (double)t.sample_count); // :95
 	handle.await(); // waits for the workers to leave (they free their device memory after their last message); rethrows a worker's error
 	return image;
+}
+
+// "0,3,miss" -> object indices, `miss` = RMD_ID_MISS; "none" or "" = the empty set
+static std::vector<uint32_t> parse_objects(const std::string &list) {
+	std::vector<uint32_t> out;
+	if (list == "none") return out;
+	for (size_t at = 0; at < list.size();) {
+		const size_t end = std::min(list.find(',', at), list.size());
+		const std::string word = list.substr(at, end - at);
+		if (word == "miss") out.push_back(RMD_ID_MISS);
+		else if (!word.empty() && word.find_first_not_of("0123456789") == std::string::npos) out.push_back((uint32_t)std::strtoul(word.c_str(), nullptr, 10));
+		else throw Error(RMD_ERR_INVALID_ARGUMENT, "object list: an index or `miss`, not '" + word + "'");
+		at = end + 1;
+	}
+	return out;
 }
 
 static void dump_mesh(const Mesh &m, const std::string &path) {
@@ -299,6 +321,19 @@ int main(int argc, char **argv) {
 				std::printf("%.17g %.17g %.17g %.17g %.17g %u %u\n", t.tile_rms, t.pixel_rms, t.mean_luma, t.mean_variance, t.mean_rel_variance, t.valid, t.invalid);
 			return 0;
 		}
+		if (argc >= 7 && !std::strcmp(argv[1], "ids-matte")) {
+			const size_t W = (size_t)std::atoll(argv[3]), H = (size_t)std::atoll(argv[4]);
+			std::vector<uint32_t> words(W * H * RMD_ID_WORDS);
+			std::ifstream f(argv[2], std::ios::binary);
+			if (!f || (!words.empty() && !f.read(reinterpret_cast<char *>(words.data()), (std::streamsize)(words.size() * sizeof(uint32_t)))))
+				throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2]);
+			uint64_t other = 0;
+			const std::vector<double> matte = ids_matte_host(words, W, H, parse_objects(argv[5]), &other);
+			std::ofstream o(argv[6], std::ios::binary);
+			o.write(reinterpret_cast<const char *>(matte.data()), (std::streamsize)(matte.size() * 8));
+			std::printf("%llu\n", (unsigned long long)other);
+			return 0;
+		}
 		if (argc >= 5 && !std::strcmp(argv[1], "display-weights")) {
 			for (double w : display_weights(std::strtod(argv[2], nullptr), std::strtod(argv[3], nullptr), std::strtod(argv[4], nullptr))) {
 				uint64_t bits;
@@ -433,7 +468,7 @@ int main(int argc, char **argv) {
 		}
 		if (argc >= 8 && !std::strcmp(argv[1], "render")) {
 			const auto t0 = std::chrono::steady_clock::now(); // cli_old/src/main.rs:36
-			std::string what = argv[2], raw, dump_features, preview_prefix, dump_tiles;
+			std::string what = argv[2], raw, dump_features, preview_prefix, dump_tiles, dump_ids, dump_matte, matte_objects;
 			bool auto_exposure = false;
 			Settings st;
 			st.camera_settings.backbuffer_width = std::atoi(argv[3]);
@@ -479,6 +514,9 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--denoise-atrous")) st.denoise_atrous = std::atoi(argv[i + 1]) != 0;
 				else if (!std::strcmp(argv[i], "--denoise-atrous-levels")) st.denoise_atrous_levels = (uint32_t)std::strtoul(argv[i + 1], nullptr, 10); // (render_tiled checks them)
 				else if (!std::strcmp(argv[i], "--denoise-atrous-k")) st.denoise_atrous_k = std::atof(argv[i + 1]);
+				else if (!std::strcmp(argv[i], "--dump-ids")) dump_ids = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--dump-matte")) dump_matte = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--matte-objects")) matte_objects = argv[i + 1];
 				else if (!std::strcmp(argv[i], "--dump-features")) dump_features = argv[i + 1];
 				else if (!std::strcmp(argv[i], "--preview-every")) st.preview_every = (size_t)std::strtoull(argv[i + 1], nullptr, 10); // (render_tiled refuses it without --spi)
 				else if (!std::strcmp(argv[i], "--preview-prefix")) preview_prefix = argv[i + 1];
@@ -509,7 +547,9 @@ int main(int argc, char **argv) {
 			// (--dump-features: every message is taken by consume, which keeps the finished tiles' rects and counts)
 			std::vector<double> feature_means;
 			std::vector<Tile> finished;
-			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty() || !dump_tiles.empty();
+			const bool want_ids = !dump_ids.empty() || !dump_matte.empty(); // (--dump-ids / --dump-matte: the finished tiles' rects and counts likewise)
+			const std::vector<uint32_t> matte_set = parse_objects(matte_objects);
+			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty() || !dump_tiles.empty() || want_ids;
 			std::vector<Vector3> image = by_consume ? consume(handle, st, progressed, nullptr, t0, &scene, dump_features.empty() ? nullptr : &feature_means, &finished, preview_prefix)
 			                                        : handle.await();
 			const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
@@ -526,6 +566,26 @@ int main(int argc, char **argv) {
 				}
 				std::ofstream f(dump_features, std::ios::binary);
 				f.write(reinterpret_cast<const char *>(feature_means.data()), (std::streamsize)(feature_means.size() * 8));
+			}
+			if (want_ids) { // an ID pass of its own over the finished tiles, each at its count
+				std::vector<rmd_tile_rect> rects;
+				std::vector<uint32_t> counts;
+				for (const Tile &t : finished) {
+					rects.push_back(rect_of(t));
+					counts.push_back((uint32_t)t.sample_count);
+				}
+				const std::vector<uint32_t> words = render_ids(scene, st, rects, counts, 0);
+				if (!dump_ids.empty()) {
+					std::ofstream f(dump_ids, std::ios::binary);
+					f.write(reinterpret_cast<const char *>(words.data()), (std::streamsize)(words.size() * sizeof(uint32_t)));
+				}
+				if (!dump_matte.empty()) {
+					uint64_t other = 0;
+					const std::vector<double> matte = ids_matte(words, W, H, matte_set, 0, &other);
+					std::ofstream f(dump_matte, std::ios::binary);
+					f.write(reinterpret_cast<const char *>(matte.data()), (std::streamsize)(matte.size() * 8));
+					std::printf("matte: %llu pixels with other != 0\n", (unsigned long long)other);
+				}
 			}
 			if (!dump_tiles.empty()) { // the finished tiles in the order they arrived: which tile stopped at which count, and by what error
 				std::ofstream f(dump_tiles);

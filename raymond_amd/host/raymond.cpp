@@ -4,6 +4,7 @@
 
 #include "../csrc/despike_dual_rule.hpp"
 #include "../csrc/despike_rule.hpp"
+#include "../csrc/ids_rule.hpp"
 #include "../csrc/luma_bins.hpp"
 #include "../csrc/tile_luma_rule.hpp"
 #include "../csrc/tile_weighted_dual_rule.hpp"
@@ -206,12 +207,13 @@ class DeviceScene { // a Scene flattened and uploaded to a context's GPU
 	rmd_scene *p_ = nullptr;
 };
 
-class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, or the features' RMD_FEATURE_CHANNELS; empty (a null pointer) until one is moved in
+class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, the features' RMD_FEATURE_CHANNELS, or an ID buffer's 5 (RMD_ID_WORDS words); empty (a null pointer) until one is moved in
   public:
-	enum Kind { Colour, Features };
+	enum Kind { Colour, Features, Ids };
 	Frame() = default;
 	Frame(rmd_context *ctx, size_t W, size_t H, Kind kind = Colour) : ctx_(ctx) {
 		if (kind == Features) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_feature_buffer_alloc");
+		else if (kind == Ids) check(rmd_id_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, reinterpret_cast<uint32_t **>(&p_)), ctx, "rmd_id_buffer_alloc");
 		else check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_framebuffer_alloc");
 	}
 	~Frame() {
@@ -1145,6 +1147,65 @@ std::vector<double> render_features(const Scene &scene, const Settings &settings
 	render_features_on(ctx, scene, settings, rects, counts, dev[0], sums_sq ? (double *)dev[1] : nullptr);
 	check(rmd_framebuffer_download(ctx, dev[0], out.data(), out.size()), ctx, "rmd_framebuffer_download");
 	if (sums_sq) check(rmd_framebuffer_download(ctx, dev[1], sums_sq->data(), sums_sq->size()), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+std::vector<uint32_t> render_ids(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, int device) {
+	if (rects.size() != counts.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_ids: one sample count per rect");
+	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
+	std::vector<uint32_t> out(W * H * RMD_ID_WORDS);
+	const Context ctx(device);
+	const Frame dev(ctx, W, H, Frame::Ids);
+	{ // one call per distinct sample count, each rect at its own count (as render_features_on does)
+		const DeviceScene dscene(ctx, scene);
+		const rmd_camera cam = camera_pod(settings);
+		std::vector<uint32_t> distinct(counts);
+		std::sort(distinct.begin(), distinct.end());
+		distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+		for (uint32_t n : distinct) {
+			if (n == 0) continue;
+			std::vector<rmd_tile_rect> share;
+			for (size_t i = 0; i < rects.size(); i++)
+				if (counts[i] == n) share.push_back(rects[i]);
+			const rmd_settings s = settings_pod(settings, 0, n, feature_flags(settings));
+			check(rmd_render_ids_async(ctx, dscene, &cam, &s, share.data(), (uint32_t)share.size(), reinterpret_cast<uint32_t *>((double *)dev)), ctx, "rmd_render_ids");
+		}
+		check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize");
+	}
+	check(rmd_framebuffer_download(ctx, dev, reinterpret_cast<double *>(out.data()), out.size() / 2), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+std::vector<double> ids_matte(const std::vector<uint32_t> &words, size_t width, size_t height, const std::vector<uint32_t> &objects, int device, uint64_t *other_pixels) {
+	if (words.size() != width * height * RMD_ID_WORDS) throw Error(RMD_ERR_INVALID_ARGUMENT, "ids_matte: width * height * RMD_ID_WORDS words");
+	std::vector<double> out(width * height);
+	const Context ctx(device);
+	const Frame ids(ctx, width, height, Frame::Ids), matte(ctx, width, height);
+	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(words.data()), ids, words.size() / 2), ctx, "rmd_framebuffer_upload");
+	check(rmd_ids_matte(ctx, reinterpret_cast<const uint32_t *>((double *)ids), (uint32_t)width, (uint32_t)height, objects.data(), (uint32_t)objects.size(), matte, other_pixels), ctx,
+	      "rmd_ids_matte");
+	check(rmd_framebuffer_download(ctx, matte, out.data(), out.size()), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+std::vector<double> ids_matte_host(const std::vector<uint32_t> &words, size_t width, size_t height, const std::vector<uint32_t> &objects, uint64_t *other_pixels) {
+	if (words.size() != width * height * RMD_ID_WORDS) throw Error(RMD_ERR_INVALID_ARGUMENT, "ids_matte_host: width * height * RMD_ID_WORDS words");
+	if (objects.size() > rmd::kIdsMatteMaxObjects) throw Error(RMD_ERR_INVALID_ARGUMENT, "ids_matte_host: more than 2048 objects");
+	std::vector<uint32_t> keys;
+	for (uint32_t o : objects) {
+		if (o == RMD_ID_MISS - 1u) throw Error(RMD_ERR_INVALID_ARGUMENT, "ids_matte_host: object index 0xFFFFFFFE: its key would be RMD_ID_MISS");
+		keys.push_back(rmd::ids_key_of(o));
+	}
+	std::sort(keys.begin(), keys.end());
+	keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+	std::vector<double> out(width * height);
+	uint64_t other = 0;
+	for (size_t i = 0; i < width * height; i++) {
+		const uint32_t *rec = &words[i * RMD_ID_WORDS];
+		out[i] = rmd::ids_matte_pixel(rec, keys.data(), (uint32_t)keys.size());
+		other += rec[rmd::kIdOther] != 0u;
+	}
+	if (other_pixels) *other_pixels = other;
 	return out;
 }
 

@@ -347,6 +347,16 @@ std::vector<Vector3> denoise_dual_tiles(const std::vector<Tile> &tiles, const Se
 // with the settings' camera, seed and DOF flag: the AOVs (normal xyz, albedo rgb, depth) of raymond_hip.h's rmd_render_features.
 std::vector<double> render_features(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
                                     int device = 0, std::vector<double> *sums_sq = nullptr);
+// The W*H*RMD_ID_WORDS first-hit ID words (raymond_hip.h's rmd_render_ids: per pixel key_0 count_0 .. key_3 count_3 other samples) of a frame whose rect i
+// holds counts[i] samples, rendered on GPU `device` with the settings' camera, seed and DOF flag: one call per distinct count.
+std::vector<uint32_t> render_ids(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, int device = 0);
+// rmd_ids_matte on GPU `device` over host words: per pixel the share of its samples whose first hit is one of `objects` (indices; RMD_ID_MISS: the
+// background).  other_pixels (optional): the pixels whose table overflowed, where the matte is a lower bound.
+std::vector<double> ids_matte(const std::vector<uint32_t> &words, size_t width, size_t height, const std::vector<uint32_t> &objects, int device = 0,
+                              uint64_t *other_pixels = nullptr);
+// ... and on the host, from the header the kernel is built from (raymond_amd/csrc/ids_rule.hpp): no GPU.  What raymond_cli ids-matte runs, and what holds
+// the header to the numpy restatement
+std::vector<double> ids_matte_host(const std::vector<uint32_t> &words, size_t width, size_t height, const std::vector<uint32_t> &objects, uint64_t *other_pixels = nullptr);
 
 // rmd_resolve_tonemap_tiles on `ctx`: the rects of the width x height device framebuffer `accum_dev`, rect i at counts[i] samples per pixel, tone-mapped
 // into packed bytes — rect after rect, each row-major, 3 bytes per pixel.  accum2_dev (or null): a dual-buffer render's other half, added first.

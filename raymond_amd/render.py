@@ -1,8 +1,8 @@
 """The Python binding of the C-ABI (include/raymond_hip.h), and the reference-shaped render API on top of it.
 
 Bottom up:
-  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
+  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, IdBuffer, ErrorImage, WinnerImage —, each a context manager;
+  * one thin wrapper per entry point: render_tiles, render_features, render_ids, ids_matte, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -192,6 +192,31 @@ class FeatureBuffer(Framebuffer):
         return (self.height, self.width, abi.RMD_FEATURE_CHANNELS)
 
 
+class IdBuffer(Framebuffer):
+    """W*H*10 uint32 first-hit object IDs with coverage in HBM (rmd_id_buffer_alloc): per pixel key_0 count_0 .. key_3 count_3 other samples.  A key is
+    0 (empty), object index + 1, or abi.RMD_ID_MISS.  The framebuffer calls serve it with 5 doubles a pixel."""
+
+    ALLOC = "rmd_id_buffer_alloc"
+    download_tiles = upload_tiles = _no_tile_transfers("ID buffers")
+
+    def __init__(self, ctx, width, height):
+        Framebuffer.__init__(self, ctx, width, height)
+        self.n = self.n // 2  # (in doubles: what zero() and the transfers count in)
+
+    def _shape(self):
+        return (self.height, self.width, abi.RMD_ID_WORDS)
+
+    def download(self):
+        out = np.empty(self.shape, dtype=np.uint32)
+        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
+        return out
+
+    def upload(self, arr):
+        arr = np.ascontiguousarray(arr, dtype=np.uint32)
+        assert arr.size == 2 * self.n
+        self.ctx.check(self.ctx.L.rmd_framebuffer_upload(self.ctx.handle, arr.ctypes.data_as(C.c_void_p), self.ptr, self.n))
+
+
 def _render_call(ctx, stem, sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, *buffers):
     """rmd_render_*[_async]: `stem` or its _async form over `tiles` — a list of rects, or a ready (abi.TileRect array, n) pair."""
     cam = camera_settings.pod()
@@ -205,6 +230,47 @@ def render_features(ctx, dscene, camera_settings, settings, tiles, features, sam
     """rmd_render_features[_async]: add the first-hit features (normal, albedo, depth) of `sample_count` samples per pixel of `tiles` into the
     FeatureBuffer `features`, and their squares into `features_sq` when given."""
     _render_call(ctx, "rmd_render_features", sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, features.ptr, _ptr(features_sq))
+
+
+def render_ids(ctx, dscene, camera_settings, settings, tiles, ids, sample_begin=0, sample_count=None, sync=True):
+    """rmd_render_ids[_async]: enter the first-hit object of `sample_count` samples per pixel of `tiles` into the IdBuffer `ids`."""
+    _render_call(ctx, "rmd_render_ids", sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, ids.ptr)
+
+
+def ids_matte(ctx, ids, objects):
+    """rmd_ids_matte: the share of each pixel's samples whose first hit is one of `objects` — object indices, abi.RMD_ID_MISS for the background; a set,
+    duplicates allowed, at most 2048 — from the IdBuffer `ids`.  Returns ((H, W) float64, other_pixels): the matte and the number of pixels whose table
+    overflowed (other != 0), where the matte is a lower bound; at 0 it is exact.  Alpha is 1 - ids_matte(ctx, ids, [abi.RMD_ID_MISS])[0]."""
+    objects = np.ascontiguousarray(objects, dtype=np.uint32).reshape(-1)
+    W, H = ids.width, ids.height
+    other = C.c_uint64()
+    with ErrorImage(ctx, W, H) as matte:
+        ctx.check(ctx.L.rmd_ids_matte(ctx.handle, ids.ptr, W, H, _u32(objects) if len(objects) else None, len(objects), matte.ptr, C.byref(other)))
+        return matte.download(), other.value
+
+
+def render_ids_arrays(ctx, scene, settings, rects, counts):
+    """The (H, W, 10) uint32 ID words of a frame whose rect i holds counts[i] samples: one rmd_render_ids call per distinct sample count, each tile at
+    its own count, with the settings' seed and DOF flag (as finished_tile_features renders the features).  Pixels no rect covers stay zero."""
+    cam = settings.camera_settings
+    with contextlib.ExitStack() as stack:
+        ds = stack.enter_context(DeviceScene(ctx, scene))
+        ids = stack.enter_context(IdBuffer(ctx, cam.backbuffer_width, cam.backbuffer_height))
+        for n in sorted(set(int(c) for c in counts)):
+            share = [r for r, c in zip(rects, counts) if int(c) == n]
+            if n > 0:
+                render_ids(ctx, ds, cam, settings, share, ids, 0, n, sync=False)
+        ctx.synchronize()
+        return ids.download()
+
+
+def ids_ranked(words):
+    """Plain numpy: the slots of (..., 10) ID words ordered per pixel by count descending, ties by slot -> (keys, counts), each (..., 4).  Empty slots
+    (key 0, count 0) trail unless a count has wrapped to 0."""
+    words = np.asarray(words, dtype=np.uint32)
+    keys, counts = words[..., 0:8:2], words[..., 1:8:2]
+    order = np.argsort(-counts.astype(np.int64), axis=-1, kind="stable")
+    return np.take_along_axis(keys, order, axis=-1), np.take_along_axis(counts, order, axis=-1)
 
 
 def render_tiles(ctx, dscene, camera_settings, settings, tiles, framebuffer, sample_begin=0, sample_count=None, sync=True, framebuffer_sq=None):
