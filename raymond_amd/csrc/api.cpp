@@ -265,6 +265,27 @@ RenderParams make_params(const rmd_context *ctx, const rmd_scene *scene, const r
 
 } // namespace rmd
 
+// The host side the first-hit passes share (first_hit.hpp): `launch` enqueues the pass's kernel for the launch parameters P on ctx->stream and
+// returns the call's status
+template <class Launch>
+static rmd_status first_hit_call(rmd_context *ctx, const char *name, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                                 const rmd_tile_rect *tiles, uint32_t n_tiles, Launch launch) {
+	rmd_settings st = *settings;
+	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
+	{
+		const char *why = nullptr;
+		if (!rmd::denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string(name) + ": " + why);
+	}
+	if (rmd_status s = bind(ctx)) return s;
+	if (rmd_status s = check_render_args(ctx, scene, camera, &st)) return s;
+	if (rmd_status s = prepare_wave_tiles(ctx, camera, tiles, n_tiles)) return s;
+	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, &st);
+	P.n_work = ctx->n_wave_tiles;
+	// (neither the context's events nor its launch record are touched: rmd_last_kernel_ms / rmd_last_launch_info keep describing the last render)
+	return launch(P);
+}
+
 extern "C" {
 
 uint32_t rmd_abi_version(void) { return RMD_ABI_VERSION; }
@@ -625,25 +646,6 @@ rmd_status rmd_render_tiles_moments(rmd_context *ctx, const rmd_scene *scene, co
 
 
 
-static rmd_status render_features_impl(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
-                                       const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev) {
-	rmd_settings st = *settings;
-	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
-	{
-		const char *why = nullptr;
-		if (!rmd::denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string("rmd_render_features: ") + why);
-	}
-	if (rmd_status s = bind(ctx)) return s;
-	if (rmd_status s = check_render_args(ctx, scene, camera, &st)) return s;
-	if (rmd_status s = prepare_wave_tiles(ctx, camera, tiles, n_tiles)) return s;
-	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, &st);
-	P.n_work = ctx->n_wave_tiles;
-	// (neither the context's events nor its launch record are touched: rmd_last_kernel_ms / rmd_last_launch_info keep describing the last render)
-	RMD_HIP(ctx, rmd::launch_features(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), feat_dev, feat_sq_dev));
-	return RMD_OK;
-}
-
 rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
                                      const rmd_tile_rect *tiles, uint32_t n_tiles, double *feat_dev, double *feat_sq_dev) {
 	if (!scene || !camera || !settings) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_features: null scene/camera/settings");
@@ -651,7 +653,12 @@ rmd_status rmd_render_features_async(rmd_context *ctx, const rmd_scene *scene, c
 	// the two W*H*7-double ranges must not overlap
 	const unsigned __int128 bytes = (unsigned __int128)camera->backbuffer_width * camera->backbuffer_height * RMD_FEATURE_CHANNELS * sizeof(double);
 	if (rmd::any_overlap({{feat_dev, bytes}, {feat_sq_dev, bytes}})) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_features: feat_sq_dev must not alias feat_dev");
-	return rmd::guarded(ctx, "rmd_render_features", [&] { return render_features_impl(ctx, scene, camera, settings, tiles, n_tiles, feat_dev, feat_sq_dev); });
+	return rmd::guarded(ctx, "rmd_render_features", [&] {
+		return first_hit_call(ctx, "rmd_render_features", scene, camera, settings, tiles, n_tiles, [&](const rmd::RenderParams &P) -> rmd_status {
+			RMD_HIP(ctx, rmd::launch_features(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), feat_dev, feat_sq_dev));
+			return RMD_OK;
+		});
+	});
 }
 
 rmd_status rmd_render_features(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
@@ -661,30 +668,16 @@ rmd_status rmd_render_features(rmd_context *ctx, const rmd_scene *scene, const r
 }
 
 // First-hit object IDs (ids.hip): rmd_render_features' host side with the ID buffer in place of the two feature buffers
-static rmd_status render_ids_impl(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
-                                  uint32_t n_tiles, uint32_t *ids_dev) {
-	rmd_settings st = *settings;
-	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
-	{
-		const char *why = nullptr;
-		if (!rmd::denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
-			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, std::string("rmd_render_ids: ") + why);
-	}
-	if (rmd_status s = bind(ctx)) return s;
-	if (rmd_status s = check_render_args(ctx, scene, camera, &st)) return s;
-	if (rmd_status s = prepare_wave_tiles(ctx, camera, tiles, n_tiles)) return s;
-	rmd::RenderParams P = rmd::make_params(ctx, scene, camera, &st);
-	P.n_work = ctx->n_wave_tiles;
-	// (neither the context's events nor its launch record are touched: rmd_last_kernel_ms / rmd_last_launch_info keep describing the last render)
-	RMD_HIP(ctx, rmd::launch_ids(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), ids_dev));
-	return RMD_OK;
-}
-
 rmd_status rmd_render_ids_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
                                 uint32_t n_tiles, uint32_t *ids_dev) {
 	if (!scene || !camera || !settings) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ids: null scene/camera/settings");
 	if (!ids_dev || (n_tiles && !tiles)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ids: null tiles/ids pointer");
-	return rmd::guarded(ctx, "rmd_render_ids", [&] { return render_ids_impl(ctx, scene, camera, settings, tiles, n_tiles, ids_dev); });
+	return rmd::guarded(ctx, "rmd_render_ids", [&] {
+		return first_hit_call(ctx, "rmd_render_ids", scene, camera, settings, tiles, n_tiles, [&](const rmd::RenderParams &P) -> rmd_status {
+			RMD_HIP(ctx, rmd::launch_ids(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), ids_dev));
+			return RMD_OK;
+		});
+	});
 }
 
 rmd_status rmd_render_ids(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,

@@ -1116,9 +1116,10 @@ std::vector<Vector3> TaskHandle::await() {
 }
 
 namespace {
-// the feature sums of the rects, each at its own count, into feat / feat_sq (zeroed device buffers of ctx): one call per distinct sample count
-void render_features_on(rmd_context *ctx, const Scene &scene, const Settings &st, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
-                        double *feat, double *feat_sq) {
+// A first-hit pass over the rects, each at its own count, from sample 0 with the settings' seed and DOF flag: one async call per distinct non-zero
+// count over the rects that share it, then synchronise.  call(scene, camera, settings, rects, n_rects) enqueues one.
+template <class Call>
+void first_hit_per_count(rmd_context *ctx, const Scene &scene, const Settings &st, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, Call call) {
 	const DeviceScene dscene(ctx, scene);
 	const rmd_camera cam = camera_pod(st);
 	std::vector<uint32_t> distinct(counts);
@@ -1130,9 +1131,17 @@ void render_features_on(rmd_context *ctx, const Scene &scene, const Settings &st
 		for (size_t i = 0; i < rects.size(); i++)
 			if (counts[i] == n) share.push_back(rects[i]);
 		const rmd_settings s = settings_pod(st, 0, n, feature_flags(st));
-		check(rmd_render_features_async(ctx, dscene, &cam, &s, share.data(), (uint32_t)share.size(), feat, feat_sq), ctx, "rmd_render_features");
+		call(dscene, &cam, &s, share.data(), (uint32_t)share.size());
 	}
 	check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize");
+}
+
+// the feature sums of the rects into feat / feat_sq (zeroed device buffers of ctx)
+void render_features_on(rmd_context *ctx, const Scene &scene, const Settings &st, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts,
+                        double *feat, double *feat_sq) {
+	first_hit_per_count(ctx, scene, st, rects, counts, [&](const rmd_scene *ds, const rmd_camera *cam, const rmd_settings *s, const rmd_tile_rect *r, uint32_t n) {
+		check(rmd_render_features_async(ctx, ds, cam, s, r, n, feat, feat_sq), ctx, "rmd_render_features");
+	});
 }
 } // namespace
 
@@ -1156,22 +1165,9 @@ std::vector<uint32_t> render_ids(const Scene &scene, const Settings &settings, c
 	std::vector<uint32_t> out(W * H * RMD_ID_WORDS);
 	const Context ctx(device);
 	const Frame dev(ctx, W, H, Frame::Ids);
-	{ // one call per distinct sample count, each rect at its own count (as render_features_on does)
-		const DeviceScene dscene(ctx, scene);
-		const rmd_camera cam = camera_pod(settings);
-		std::vector<uint32_t> distinct(counts);
-		std::sort(distinct.begin(), distinct.end());
-		distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-		for (uint32_t n : distinct) {
-			if (n == 0) continue;
-			std::vector<rmd_tile_rect> share;
-			for (size_t i = 0; i < rects.size(); i++)
-				if (counts[i] == n) share.push_back(rects[i]);
-			const rmd_settings s = settings_pod(settings, 0, n, feature_flags(settings));
-			check(rmd_render_ids_async(ctx, dscene, &cam, &s, share.data(), (uint32_t)share.size(), reinterpret_cast<uint32_t *>((double *)dev)), ctx, "rmd_render_ids");
-		}
-		check(rmd_context_synchronize(ctx), ctx, "rmd_context_synchronize");
-	}
+	first_hit_per_count(ctx, scene, settings, rects, counts, [&](const rmd_scene *ds, const rmd_camera *cam, const rmd_settings *s, const rmd_tile_rect *r, uint32_t n) {
+		check(rmd_render_ids_async(ctx, ds, cam, s, r, n, reinterpret_cast<uint32_t *>((double *)dev)), ctx, "rmd_render_ids");
+	});
 	check(rmd_framebuffer_download(ctx, dev, reinterpret_cast<double *>(out.data()), out.size() / 2), ctx, "rmd_framebuffer_download");
 	return out;
 }

@@ -249,19 +249,25 @@ def ids_matte(ctx, ids, objects):
         return matte.download(), other.value
 
 
-def render_ids_arrays(ctx, scene, settings, rects, counts):
-    """The (H, W, 10) uint32 ID words of a frame whose rect i holds counts[i] samples: one rmd_render_ids call per distinct sample count, each tile at
-    its own count, with the settings' seed and DOF flag (as finished_tile_features renders the features).  Pixels no rect covers stay zero."""
+def _first_hit_arrays(ctx, scene, settings, rects, counts, buffer_types, render):
+    """A first-hit pass over a frame whose rect i holds counts[i] samples, into zeroed buffers of `buffer_types`: one render(dscene, camera, rects, n,
+    *buffers) per distinct non-zero sample count n over the rects that share it, then a synchronize.  Returns the buffers' downloads."""
     cam = settings.camera_settings
     with contextlib.ExitStack() as stack:
         ds = stack.enter_context(DeviceScene(ctx, scene))
-        ids = stack.enter_context(IdBuffer(ctx, cam.backbuffer_width, cam.backbuffer_height))
+        buffers = [stack.enter_context(t(ctx, cam.backbuffer_width, cam.backbuffer_height)) for t in buffer_types]
         for n in sorted(set(int(c) for c in counts)):
-            share = [r for r, c in zip(rects, counts) if int(c) == n]
             if n > 0:
-                render_ids(ctx, ds, cam, settings, share, ids, 0, n, sync=False)
+                render(ds, cam, [r for r, c in zip(rects, counts) if int(c) == n], n, *buffers)
         ctx.synchronize()
-        return ids.download()
+        return tuple(b.download() for b in buffers)
+
+
+def render_ids_arrays(ctx, scene, settings, rects, counts):
+    """The (H, W, 10) uint32 ID words of a frame whose rect i holds counts[i] samples: one rmd_render_ids call per distinct sample count, each tile at
+    its own count, with the settings' seed and DOF flag (as finished_tile_features renders the features).  Pixels no rect covers stay zero."""
+    return _first_hit_arrays(ctx, scene, settings, rects, counts, (IdBuffer,),
+                             lambda ds, cam, share, n, ids: render_ids(ctx, ds, cam, settings, share, ids, 0, n, sync=False))[0]
 
 
 def ids_ranked(words):
@@ -974,18 +980,8 @@ class TaskHandle:  # src/trace.rs:70-135
 def finished_tile_features(ctx, scene, settings, rects, counts):
     """The (H, W, 7) first-hit feature sums and sums of squares of a frame whose rect i holds counts[i] samples: one rmd_render_features call per
     distinct sample count, each tile at its own count, with the settings' seed and DOF flag.  Pixels no rect covers stay zero."""
-    cam = settings.camera_settings
-    W, H = cam.backbuffer_width, cam.backbuffer_height
-    with contextlib.ExitStack() as stack:
-        ds = stack.enter_context(DeviceScene(ctx, scene))
-        fb = stack.enter_context(FeatureBuffer(ctx, W, H))
-        fb_sq = stack.enter_context(FeatureBuffer(ctx, W, H))
-        for n in sorted(set(int(c) for c in counts)):
-            share = [r for r, c in zip(rects, counts) if int(c) == n]
-            if n > 0:
-                render_features(ctx, ds, cam, settings, share, fb, 0, n, sync=False, features_sq=fb_sq)
-        ctx.synchronize()
-        return fb.download(), fb_sq.download()
+    return _first_hit_arrays(ctx, scene, settings, rects, counts, (FeatureBuffer, FeatureBuffer),
+                             lambda ds, cam, share, n, fb, fb_sq: render_features(ctx, ds, cam, settings, share, fb, 0, n, sync=False, features_sq=fb_sq))
 
 
 def _preview(settings, W, H, pass_index, sample_count, calls):

@@ -218,9 +218,11 @@ def test_the_rule_header_agrees_with_a_plain_reading_under_sanitizers(tmp_path):
     body = header.split("inline void ids_insert", 1)[1].split("// Whether", 1)[0]
     assert not re.search(r"\b(for|while)\b", body) and set(re.findall(r"rec\[(\w+)\]", body)) <= set("01234567") | {"kIdWords", "kIdOther", "kIdSamples"}  # unrolled: every index a constant
     kernel = open(os.path.join(CSRC, "ids.hip")).read()
-    for fn in ("ids_insert(rec,", "ids_matte_pixel(rec,", "scene_intersect_wave<GRID>("):
-        assert fn in kernel, fn  # the kernels read the same lines
-    assert "asm" not in kernel
+    shared = open(os.path.join(CSRC, "first_hit.hpp")).read()  # the first-hit passes' shared body: ids.hip is its ID sink, and the matte kernel
+    assert '#include "first_hit.hpp"' in kernel
+    for fn, text in (("ids_insert(rec,", kernel), ("ids_matte_pixel(rec,", kernel), ("scene_intersect_wave<GRID>(", shared)):
+        assert fn in text, fn  # the kernels read the same lines
+    assert "asm" not in kernel and "asm" not in shared
     mirror = open(os.path.join(ROOT, "raymond_amd", "host", "raymond.cpp")).read()
     assert '#include "../csrc/ids_rule.hpp"' in mirror and "rmd::ids_matte_pixel(" in mirror  # ... and so does the C++ mirror
     cxx = shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
