@@ -62,7 +62,7 @@ enum {
 	                                 rmd_framebuffer_upload_tiles, rmd_context_wait_transfers, rmd_resolve_tonemap,
 	                                 rmd_resolve_tonemap_tiles, rmd_luminance_histogram_tiles, rmd_despike, rmd_despike_dual, rmd_tile_luma_error, rmd_tile_weighted_error,
 	                                 rmd_reduce_framebuffer, rmd_render_tiles_moments, rmd_tile_error,
-	                                 rmd_denoise, rmd_render_features, rmd_render_ids, rmd_ids_matte, rmd_denoise_guided, rmd_denoise_dual,
+	                                 rmd_denoise, rmd_render_features, rmd_render_ids, rmd_ids_matte, rmd_render_ao, rmd_ao_resolve, rmd_denoise_guided, rmd_denoise_dual,
 	                                 rmd_denoise_atrous_dual, rmd_denoise_atrous_dual_region,
 	                                 rmd_tile_error_dual, rmd_tile_weighted_error_dual, rmd_denoise_dual_region, rmd_denoise_dual_guided,
 	                                 rmd_denoise_guided_slope, rmd_denoise_dual_guided_slope,
@@ -445,6 +445,48 @@ rmd_status rmd_render_ids_async(rmd_context *ctx, const rmd_scene *scene, const 
                                 const rmd_tile_rect *tiles, uint32_t n_tiles, uint32_t *ids_dev);
 rmd_status rmd_ids_matte(rmd_context *ctx, const uint32_t *ids_dev, uint32_t width, uint32_t height, const uint32_t *objects, uint32_t n_objects,
                          double *matte_dev, uint64_t *other_pixels_host);
+/*
+ * AMBIENT OCCLUSION OF THE FIRST HIT, AS EXACT COUNTS (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct changes; a caller finds the
+ * functions by their symbols).  How much of the hemisphere above the first hit is blocked within a distance: the contact shadows that none of
+ * normal, albedo, depth or ID carries.  Each sample's outcome is one bit, so an AO buffer holds counts: W*H*RMD_AO_WORDS uint32_t words,
+ * pixel-interleaved, the record of pixel i = x + y*W at ao[i*4 ..]:
+ *     word 0   occluded
+ *     word 1   open
+ *     word 2   none
+ *     word 3   samples
+ * All four are modulo 2^32, and occluded + open + none == samples.  A record is 16 bytes = 2 doubles: rmd_ao_buffer_alloc allocates a zeroed
+ * buffer, and rmd_framebuffer_free / _zero / _download / _upload serve it as they are with n_doubles = W*H*2.
+ * rmd_render_ao: for every pixel of every rect and s = sample_begin .. sample_begin + sample_count - 1, in that order:
+ *   1  the primary ray exactly as rmd_render_features takes it (Philox block 0, then the lens' rounds under RMD_RENDER_DOF) is intersected with
+ *      the scene once.  A miss, or a sample the thin lens yields no ray for, does none += 1, samples += 1 and ends there.
+ *   2  for a hit on object o at distance t: frag = ro + rd*t, and N is the normal rmd_render_features defines (the plane's as stored, the sphere's
+ *      normalised, the grid's interpolated, possibly NaN).  The material is ignored: Emission and Metal included, the construction is the diffuse one.
+ *   3  (r1, r2) = the first and second 53-bit uniform of the sample's NEXT Philox block: block 1 for the pinhole, block 1 + the lens' rounds
+ *      otherwise — the block the render's first shaded depth draws.  The block's 22-bit uniform is not used.
+ *   4  the bounce ray of trace()'s diffuse branch (src/trace.rs:261-269, 396-416): (T, B) = onb(N), l = cosine_hemisphere(r1, r2),
+ *      dir = normalize(Matrix3::from_cols(T, N, B) * l), origin = frag + N * 0.00001.
+ *   5  Scene::intersect(origin, dir) gives (o2, t2).  The sample is OCCLUDED if o2 is an object and t2 < max_distance; otherwise it is OPEN — a NaN
+ *      t2, or a NaN ray that hits nothing, is open.  Then samples += 1.  The closest hit compared with max_distance is the definition.
+ * The contract is rmd_render_features': calls over [0, k) and [k, n) leave the words of one call over [0, n), the words do not depend on how the
+ * rects cut the frame, and a pixel no rect covers keeps its words.  So is the rest: bounce_limit and the black-path flags are ignored (both together
+ * are still refused); the pass does not change what rmd_last_launch_info and rmd_last_kernel_ms report; rmd_render_ao waits like rmd_render_features
+ * and reports an earlier device fault as it does, the pass itself raises none; the _async form only enqueues.  Refused before the device is touched,
+ * in this order: scene, camera or settings NULL; ao_dev NULL, or tiles NULL with n_tiles > 0; max_distance not > 0 (NaN is refused; +inf is allowed
+ * and means "any hit"); a rect outside the frame or two rects that overlap, then the context and the render arguments, as rmd_render_features does —
+ * all RMD_ERR_INVALID_ARGUMENT; a scene whose object table the launch cannot hold is RMD_ERR_UNSUPPORTED with the buffer untouched.
+ * rmd_ao_resolve writes W*H doubles: out = (double)open / (double)(open + occluded) — the sum a 64-bit integer, one correctly rounded division —,
+ * and empty_value where open + occluded == 0; *empty_pixels_host (may be NULL) receives the exact number of such pixels.
+ * RMD_ERR_INVALID_ARGUMENT before the device is touched, in this order: width or height 0; ao_dev or out_dev NULL; empty_value not finite; the two
+ * ranges overlapping; then a NULL context.  The call waits; its scratch (one counter, 16 bytes) stays on the context.
+ */
+#define RMD_AO_WORDS 4u /* occluded open none samples */
+rmd_status rmd_ao_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, uint32_t **out_dev); /* zeroed W*H*4 words */
+rmd_status rmd_render_ao(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                         const rmd_tile_rect *tiles, uint32_t n_tiles, double max_distance, uint32_t *ao_dev);
+rmd_status rmd_render_ao_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
+                               const rmd_tile_rect *tiles, uint32_t n_tiles, double max_distance, uint32_t *ao_dev);
+rmd_status rmd_ao_resolve(rmd_context *ctx, const uint32_t *ao_dev, uint32_t width, uint32_t height, double empty_value, double *out_dev,
+                          uint64_t *empty_pixels_host);
 /*
  * rmd_denoise with a FEATURE WEIGHT (Rousselle, Manzi and Zwicker, "Robust Denoising using Feature and Color Information", 2013; an addition
  * within ABI 6).  Everything rmd_denoise defines stays word for word (validity, D(p, q), w_c = exp(-max(0, D)), clamping, sum orders, the output

@@ -88,6 +88,18 @@ extern "C" {
     #[allow(dead_code)]
     fn rmd_ids_matte(ctx: *mut rmd_context, ids_dev: *const u32, width: u32, height: u32, objects: *const u32, n_objects: u32, matte_dev: *mut f64,
                      other_pixels_host: *mut u64) -> i32;
+    // ambient occlusion of the first hit as exact counts (W*H*4 u32: occluded open none samples) and open / (open + occluded) from them
+    #[allow(dead_code)]
+    fn rmd_ao_buffer_alloc(ctx: *mut rmd_context, width: u32, height: u32, out_dev: *mut *mut u32) -> i32;
+    #[allow(dead_code)]
+    fn rmd_render_ao(ctx: *mut rmd_context, scene: *const rmd_scene, camera: *const rmd_camera, settings: *const rmd_settings,
+                     tiles: *const rmd_tile_rect, n_tiles: u32, max_distance: f64, ao_dev: *mut u32) -> i32;
+    #[allow(dead_code)]
+    fn rmd_render_ao_async(ctx: *mut rmd_context, scene: *const rmd_scene, camera: *const rmd_camera, settings: *const rmd_settings,
+                           tiles: *const rmd_tile_rect, n_tiles: u32, max_distance: f64, ao_dev: *mut u32) -> i32;
+    #[allow(dead_code)]
+    fn rmd_ao_resolve(ctx: *mut rmd_context, ao_dev: *const u32, width: u32, height: u32, empty_value: f64, out_dev: *mut f64,
+                      empty_pixels_host: *mut u64) -> i32;
     fn rmd_denoise_guided(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
                           width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, radius: u32,
                           patch_radius: u32, k: f64, alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64) -> i32;

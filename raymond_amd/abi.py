@@ -39,6 +39,7 @@ RMD_MAT_DIFFUSE, RMD_MAT_METAL, RMD_MAT_EMISSION = 0, 1, 2
 RMD_MAX_BOUNCE_LIMIT = 16
 RMD_FEATURE_CHANNELS = 7  # first-hit feature buffers: 0..2 normal xyz, 3..5 albedo rgb, 6 depth
 RMD_ID_SLOTS, RMD_ID_WORDS, RMD_ID_MISS = 4, 10, 0xFFFFFFFF  # ID buffers: key_0 count_0 .. key_3 count_3 other samples; the key of a miss
+RMD_AO_WORDS = 4  # AO buffers: occluded open none samples
 RMD_ATROUS_MAX_LEVELS = 8  # rmd_denoise_atrous: the most levels a call may ask for
 RMD_RENDER_DOF = 1  # rmd_settings.flags
 RMD_RENDER_TRACE_BLACK_PATHS = 2  # never end a zero-throughput path early

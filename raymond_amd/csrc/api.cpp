@@ -2,6 +2,7 @@
 // api_scene.cpp; framebuffers, tile transfers, the resolve/tone-map epilogue and the histogram in api_frame.cpp; the denoise entry points and the
 // per-tile measures in api_denoise.cpp.  Host code only; kernels are in kernels.hip.
 #define RMD_WITH_HIP 1
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <new>
@@ -271,7 +272,7 @@ template <class Launch>
 static rmd_status first_hit_call(rmd_context *ctx, const char *name, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings,
                                  const rmd_tile_rect *tiles, uint32_t n_tiles, Launch launch) {
 	rmd_settings st = *settings;
-	st.bounce_limit = 1u; // ignored: the pass traces the first segment only
+	st.bounce_limit = 1u; // ignored: a pass traces the first segment, and rmd_render_ao one more whatever the limit
 	{
 		const char *why = nullptr;
 		if (!rmd::denoise_rects_ok(tiles, n_tiles, camera->backbuffer_width, camera->backbuffer_height, &why))
@@ -717,6 +718,49 @@ rmd_status rmd_ids_matte(rmd_context *ctx, const uint32_t *ids_dev, uint32_t wid
 		RMD_HIP(ctx, hipMemcpyAsync(&other, d_other, sizeof(other), hipMemcpyDeviceToHost, ctx->stream));
 		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
 		if (other_pixels_host) *other_pixels_host = other;
+		return rmd::check_fault(ctx);
+	});
+}
+
+// Ambient occlusion of the first hit (ao.hip): rmd_render_ids' host side with max_distance checked in front of first_hit_call's own refusals
+rmd_status rmd_render_ao_async(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
+                               uint32_t n_tiles, double max_distance, uint32_t *ao_dev) {
+	if (!scene || !camera || !settings) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ao: null scene/camera/settings");
+	if (!ao_dev || (n_tiles && !tiles)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ao: null tiles/ao pointer");
+	if (!(max_distance > 0.0)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, "rmd_render_ao: max_distance must be > 0"); // (NaN: refused; +inf: any hit)
+	return rmd::guarded(ctx, "rmd_render_ao", [&] {
+		return first_hit_call(ctx, "rmd_render_ao", scene, camera, settings, tiles, n_tiles, [&](const rmd::RenderParams &P) -> rmd_status {
+			RMD_HIP(ctx, rmd::launch_ao(ctx->stream, P, scene->d_objects, scene->d_grids, ctx->wave_tiles.as<rmd::WaveTile>(), ao_dev, max_distance));
+			return RMD_OK;
+		});
+	});
+}
+
+rmd_status rmd_render_ao(rmd_context *ctx, const rmd_scene *scene, const rmd_camera *camera, const rmd_settings *settings, const rmd_tile_rect *tiles,
+                         uint32_t n_tiles, double max_distance, uint32_t *ao_dev) {
+	if (rmd_status s = rmd_render_ao_async(ctx, scene, camera, settings, tiles, n_tiles, max_distance, ao_dev)) return s;
+	return rmd_context_synchronize(ctx);
+}
+
+// The openness of every pixel from an AO buffer.  The refusals in the header's order, the context last.  The block: [counter: 16 bytes]
+rmd_status rmd_ao_resolve(rmd_context *ctx, const uint32_t *ao_dev, uint32_t width, uint32_t height, double empty_value, double *out_dev, uint64_t *empty_pixels_host) {
+	return rmd::guarded(ctx, "rmd_ao_resolve", [&]() -> rmd_status {
+		const std::string name = "rmd_ao_resolve: ";
+		if (width == 0 || height == 0) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "width or height is 0");
+		if (!ao_dev || !out_dev) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "null ao/out pointer");
+		if (!std::isfinite(empty_value)) return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "empty_value is not finite");
+		const unsigned __int128 n = (unsigned __int128)width * height;
+		if (rmd::any_overlap({{ao_dev, n * RMD_AO_WORDS * sizeof(uint32_t)}, {out_dev, n * sizeof(double)}}))
+			return rmd::fail(ctx, RMD_ERR_INVALID_ARGUMENT, name + "out_dev overlaps ao_dev");
+		if (rmd_status s = bind(ctx)) return s;
+		RMD_HIP(ctx, ctx->ao_resolve_scratch.grow(16));
+		unsigned long long *d_empty = ctx->ao_resolve_scratch.as<unsigned long long>();
+		RMD_HIP(ctx, hipMemsetAsync(d_empty, 0, 16, ctx->stream));
+		RMD_HIP(ctx, rmd::launch_ao_resolve(ctx->stream, ao_dev, (uint64_t)width * height, empty_value, out_dev, d_empty));
+		unsigned long long empty = 0;
+		RMD_HIP(ctx, hipMemcpyAsync(&empty, d_empty, sizeof(empty), hipMemcpyDeviceToHost, ctx->stream));
+		RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));
+		if (empty_pixels_host) *empty_pixels_host = empty;
 		return rmd::check_fault(ctx);
 	});
 }

@@ -155,6 +155,11 @@ static_assert(RMD_ID_WORDS * sizeof(uint32_t) % sizeof(double) == 0, "an ID reco
 rmd_status rmd_id_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, uint32_t **out_dev) {
 	return alloc_zeroed(ctx, "rmd_id_buffer_alloc: bad argument", width, height, RMD_ID_WORDS * sizeof(uint32_t) / sizeof(double), reinterpret_cast<double **>(out_dev));
 }
+// AO buffers (ao.hip): RMD_AO_WORDS words a pixel, two doubles
+static_assert(RMD_AO_WORDS * sizeof(uint32_t) % sizeof(double) == 0, "an AO record is a whole number of doubles: the framebuffer helpers serve AO buffers");
+rmd_status rmd_ao_buffer_alloc(rmd_context *ctx, uint32_t width, uint32_t height, uint32_t **out_dev) {
+	return alloc_zeroed(ctx, "rmd_ao_buffer_alloc: bad argument", width, height, RMD_AO_WORDS * sizeof(uint32_t) / sizeof(double), reinterpret_cast<double **>(out_dev));
+}
 rmd_status rmd_framebuffer_free(rmd_context *ctx, double *dev) {
 	if (rmd_status s = bind(ctx)) return s;
 	RMD_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -1,4 +1,5 @@
-// The first-hit passes' shared device body and launcher (rmd_render_features: features.hip; rmd_render_ids: ids.hip, section 34).
+// The first-hit passes' shared device body and launcher (rmd_render_features: features.hip; rmd_render_ids: ids.hip, section 34;
+// rmd_render_ao: ao.hip, section 35).
 // A pass is a sink — what a lane keeps of a sample's first hit, and the buffers it loads and stores — around the one body below.
 //
 // first_hit_body<GRID> — one wave per 8 x 8 wave tile, lane = pixel.  For each sample of the call, in order: the primary ray exactly as the render
@@ -14,10 +15,23 @@
 //   load(alive, pixel)                                  the lane's state from its buffers (pixel = x + y * W; a lane that is not alive reads nothing)
 //   add<GRID>(hit, oi, lobjs, grids, ro, rd, t, sub)    one sample; called by all 64 lanes, `hit` false for a miss and for a lane without a ray
 //   store(pixel)                                        the state back; called only where alive
+// A sink that declares `static constexpr bool kSecondRay = true` follows one more segment per sample (rmd_render_ao: ao.hip) and also offers
+//   second_ray(P, rng, origin, dir) -> want2            after add: the follow-up ray of the lane's sample — rng stands at the sample's next block —, want2 false where
+//                                                       the lane has none; called by all 64 lanes
+//   second_hit(hit2, t2)                                what Scene::intersect gave on it (the same wave-cooperative call, want2 marking the lanes); hit2 false for a
+//                                                       miss and for a lane without a follow-up ray; called by all 64 lanes
+// The other sinks' kernels hold none of this.
 #pragma once
+#include <type_traits>
+
 #include "render_kernel.hpp"
 
 namespace rmd {
+
+template <class Sink, class = void>
+struct sink_second_ray : std::false_type {};
+template <class Sink>
+struct sink_second_ray<Sink, std::void_t<decltype(Sink::kSecondRay)>> : std::bool_constant<Sink::kSecondRay> {};
 
 // Stage the object table and, with grids, their occupancy masks in LDS: coalesced, once per workgroup (the caller's barrier follows).
 // render_kernel_body keeps its own copy of these lines: calling this from there changed the render kernels' register allocation, which is at its limit.
@@ -74,6 +88,16 @@ RMD_DEV void first_hit_body(const RenderParams &P, const DevObject *__restrict__
 		uint32_t sub = 0;
 		const int oi = scene_intersect_wave<GRID>(objs, P.n_objects, grids, lds_masks, scr, want, ro, rd, t, sub, P.axis_pairs, 0u, nullptr, false, P.visit_mask);
 		sink.template add<GRID>(want && oi >= 0, oi, lobjs, grids, ro, rd, t, sub);
+		if constexpr (sink_second_ray<Sink>::value) {
+			V3 ro2, rd2;
+			const bool want2 = sink.second_ray(P, rng, ro2, rd2);
+			double t2 = 0.0;
+			uint32_t sub2 = 0;
+			int oi2 = -1;
+			if (__builtin_amdgcn_ballot_w64(want2) != 0ull) // (uniform per wave: a wave none of whose lanes has a first hit skips the call)
+				oi2 = scene_intersect_wave<GRID>(objs, P.n_objects, grids, lds_masks, scr, want2, ro2, rd2, t2, sub2, P.axis_pairs, 0u, nullptr, false, P.visit_mask);
+			sink.second_hit(want2 && oi2 >= 0, t2);
+		}
 	}
 
 	if (alive) sink.store(pixel);

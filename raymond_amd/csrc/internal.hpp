@@ -100,6 +100,7 @@ struct rmd_context {
 	rmd::DeviceBuffer tile_weighted_scratch; // rmd_tile_weighted_error's rects, counts, weights and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer tile_weighted_dual_scratch; // rmd_tile_weighted_error_dual's rects, weights and per-rect results (api_denoise.cpp): grown when a call needs more, kept between calls
 	rmd::DeviceBuffer ids_matte_scratch; // rmd_ids_matte's counter of pixels with other != 0 and its sorted distinct keys (api.cpp): grown when a call needs more, kept between calls
+	rmd::DeviceBuffer ao_resolve_scratch; // rmd_ao_resolve's counter of pixels without a first hit, 16 bytes (api.cpp): allocated by the first call, kept between calls
 	// fault words (device_types.hpp: kFault*): pinned host memory mapped into the device's address space.  A wave whose loop runs past its bound
 	// writes here; the host looks after every wait for the stream (api.cpp: check_fault) — a plain host load, no copy
 	uint32_t *h_fault = nullptr, *d_fault = nullptr;

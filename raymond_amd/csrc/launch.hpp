@@ -199,6 +199,12 @@ hipError_t launch_ids(hipStream_t stream, const RenderParams &P, const DevObject
 // rmd_ids_matte (ids.hip): matte[i] = pixel i's matte over the n_keys ascending, distinct keys (ids_rule.hpp: ids_matte_pixel; device memory, at most 2048),
 // and *other_pixels (zeroed by the caller) += the pixels whose record has other != 0
 hipError_t launch_ids_matte(hipStream_t stream, const uint32_t *ids, uint64_t n_pixels, const uint32_t *keys, uint32_t n_keys, double *matte, unsigned long long *other_pixels);
+// rmd_render_ao (ao.hip): for each of the P.n_work wave tiles, samples P.sample_begin .. + P.sample_count - 1 counted into the pixels' records of `ao`,
+// W*H*RMD_AO_WORDS words (ao_rule.hpp: ao_count): occluded where the diffuse bounce ray off the first hit meets an object nearer than max_distance
+hipError_t launch_ao(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, const WaveTile *wave_tiles, uint32_t *ao, double max_distance);
+// rmd_ao_resolve (ao.hip): out[i] = pixel i's open / (open + occluded), empty_value where the sum is 0 (ao_rule.hpp: ao_resolve_pixel), and
+// *empty_pixels (zeroed by the caller) += the pixels where it is
+hipError_t launch_ao_resolve(hipStream_t stream, const uint32_t *ao, uint64_t n_pixels, double empty_value, double *out, unsigned long long *empty_pixels);
 hipError_t launch_render_list(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
                               const ListWork *list, double *rgb_out, int32_t *path_obj, uint32_t *path_sub);
 // tile rectangles of a frame <-> a packed buffer (kernels.hip: tile_copy_kernel); `first[i]` = pixels in front of rect i

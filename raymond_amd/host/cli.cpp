@@ -30,6 +30,10 @@
 //                                                                      the finished tiles at their own counts: key_0 count_0 .. key_3 count_3 other samples)
 //                                                                    [--dump-matte FILE --matte-objects 0,3,miss]   (rmd_ids_matte of those words for the listed
 //                                                                      object indices, `miss` the background, as raw f64; prints the pixels whose table overflowed)
+//                                                                    [--dump-ao FILE --ao-distance D [--ao-empty V]]   (rmd_render_ao over the finished tiles at their own
+//                                                                      counts, the bounce ray off the first hit occluded by a hit nearer than D — inf: any hit —, and
+//                                                                      rmd_ao_resolve of it as raw f64: open / (open + occluded), V, by default 1, where no sample has
+//                                                                      a first hit; prints the number of such pixels)
 //                                                                    [--denoise-dual 1 [--adaptive-denoised T [--adaptive-min N]]]
 //                                                                      (needs --denoise 1 and --spi, one GPU: passes alternate between two half buffers,
 //                                                                       the image is rmd_denoise_dual's; T: tiles finish by rmd_tile_error_dual)
@@ -93,6 +97,9 @@
 //   raymond_cli ids-matte IDS.u32 W H LIST OUT.f64
 //                                         rmd_ids_matte made on the host (raymond::ids_matte_host, from the header the kernel is built from; no GPU) over raw
 //                                         W*H*10 uint32 ID words; LIST: object indices and `miss`, comma-separated, or `none`; prints the pixels with other != 0
+//   raymond_cli ao-resolve AO.u32 W H OUT.f64 [EMPTY]
+//                                         rmd_ao_resolve made on the host (raymond::ao_resolve_host, from the header the kernel is built from; no GPU) over raw
+//                                         W*H*4 uint32 AO words; EMPTY: the value of a pixel without a first hit, by default 1; prints the number of such pixels
 //   raymond_cli display-weights EXPOSURE GAMMA FLOOR
 //                                         rmd_display_weights: its 260 weights, one per line, as their 64 bits in hexadecimal
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
@@ -334,6 +341,19 @@ int main(int argc, char **argv) {
 			std::printf("%llu\n", (unsigned long long)other);
 			return 0;
 		}
+		if (argc >= 6 && !std::strcmp(argv[1], "ao-resolve")) {
+			const size_t W = (size_t)std::atoll(argv[3]), H = (size_t)std::atoll(argv[4]);
+			std::vector<uint32_t> words(W * H * RMD_AO_WORDS);
+			std::ifstream f(argv[2], std::ios::binary);
+			if (!f || (!words.empty() && !f.read(reinterpret_cast<char *>(words.data()), (std::streamsize)(words.size() * sizeof(uint32_t)))))
+				throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("cannot read ") + argv[2]);
+			uint64_t empty = 0;
+			const std::vector<double> out = ao_resolve_host(words, W, H, argc >= 7 ? std::strtod(argv[6], nullptr) : 1.0, &empty);
+			std::ofstream o(argv[5], std::ios::binary);
+			o.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)(out.size() * 8));
+			std::printf("%llu\n", (unsigned long long)empty);
+			return 0;
+		}
 		if (argc >= 5 && !std::strcmp(argv[1], "display-weights")) {
 			for (double w : display_weights(std::strtod(argv[2], nullptr), std::strtod(argv[3], nullptr), std::strtod(argv[4], nullptr))) {
 				uint64_t bits;
@@ -468,7 +488,8 @@ int main(int argc, char **argv) {
 		}
 		if (argc >= 8 && !std::strcmp(argv[1], "render")) {
 			const auto t0 = std::chrono::steady_clock::now(); // cli_old/src/main.rs:36
-			std::string what = argv[2], raw, dump_features, preview_prefix, dump_tiles, dump_ids, dump_matte, matte_objects;
+			std::string what = argv[2], raw, dump_features, preview_prefix, dump_tiles, dump_ids, dump_matte, matte_objects, dump_ao;
+			double ao_distance = 0.0, ao_empty = 1.0;
 			bool auto_exposure = false;
 			Settings st;
 			st.camera_settings.backbuffer_width = std::atoi(argv[3]);
@@ -517,6 +538,9 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--dump-ids")) dump_ids = argv[i + 1];
 				else if (!std::strcmp(argv[i], "--dump-matte")) dump_matte = argv[i + 1];
 				else if (!std::strcmp(argv[i], "--matte-objects")) matte_objects = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--dump-ao")) dump_ao = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--ao-distance")) ao_distance = std::strtod(argv[i + 1], nullptr); // (inf: any hit)
+				else if (!std::strcmp(argv[i], "--ao-empty")) ao_empty = std::strtod(argv[i + 1], nullptr);
 				else if (!std::strcmp(argv[i], "--dump-features")) dump_features = argv[i + 1];
 				else if (!std::strcmp(argv[i], "--preview-every")) st.preview_every = (size_t)std::strtoull(argv[i + 1], nullptr, 10); // (render_tiled refuses it without --spi)
 				else if (!std::strcmp(argv[i], "--preview-prefix")) preview_prefix = argv[i + 1];
@@ -535,6 +559,8 @@ int main(int argc, char **argv) {
 				else if (!std::strcmp(argv[i], "--despike-ratio")) st.despike_ratio = std::atof(argv[i + 1]);
 				else if (!std::strcmp(argv[i], "--despike-floor")) st.despike_floor = std::atof(argv[i + 1]);
 			}
+			const bool want_ao = !dump_ao.empty(); // (--dump-ao: the finished tiles' rects and counts, as for --dump-ids)
+			if (want_ao && !(ao_distance > 0.0)) throw Error(RMD_ERR_INVALID_ARGUMENT, "--dump-ao needs --ao-distance D with D > 0"); // (before anything is rendered)
 			st.preview_auto_exposure = auto_exposure && st.preview_every > 0; // (a render without previews: the final frame alone)
 			Scene scene;
 			if (what == "spheres") scene = reflective_spheres();
@@ -549,7 +575,7 @@ int main(int argc, char **argv) {
 			std::vector<Tile> finished;
 			const bool want_ids = !dump_ids.empty() || !dump_matte.empty(); // (--dump-ids / --dump-matte: the finished tiles' rects and counts likewise)
 			const std::vector<uint32_t> matte_set = parse_objects(matte_objects);
-			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty() || !dump_tiles.empty() || want_ids;
+			const bool by_consume = st.samples_per_iteration != 0 || !dump_features.empty() || !dump_tiles.empty() || want_ids || want_ao;
 			std::vector<Vector3> image = by_consume ? consume(handle, st, progressed, nullptr, t0, &scene, dump_features.empty() ? nullptr : &feature_means, &finished, preview_prefix)
 			                                        : handle.await();
 			const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
@@ -586,6 +612,19 @@ int main(int argc, char **argv) {
 					f.write(reinterpret_cast<const char *>(matte.data()), (std::streamsize)(matte.size() * 8));
 					std::printf("matte: %llu pixels with other != 0\n", (unsigned long long)other);
 				}
+			}
+			if (want_ao) { // an AO pass of its own over the finished tiles, each at its count
+				std::vector<rmd_tile_rect> rects;
+				std::vector<uint32_t> counts;
+				for (const Tile &t : finished) {
+					rects.push_back(rect_of(t));
+					counts.push_back((uint32_t)t.sample_count);
+				}
+				uint64_t empty = 0;
+				const std::vector<double> out = ao_resolve(render_ao(scene, st, rects, counts, ao_distance, 0), W, H, ao_empty, 0, &empty);
+				std::ofstream f(dump_ao, std::ios::binary);
+				f.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)(out.size() * 8));
+				std::printf("ao: %llu pixels without a first hit\n", (unsigned long long)empty);
 			}
 			if (!dump_tiles.empty()) { // the finished tiles in the order they arrived: which tile stopped at which count, and by what error
 				std::ofstream f(dump_tiles);

@@ -2,6 +2,7 @@
 // rmd_render_tiles; nothing here evaluates a ray.
 #include "raymond.hpp"
 
+#include "../csrc/ao_rule.hpp"
 #include "../csrc/despike_dual_rule.hpp"
 #include "../csrc/despike_rule.hpp"
 #include "../csrc/ids_rule.hpp"
@@ -207,13 +208,14 @@ class DeviceScene { // a Scene flattened and uploaded to a context's GPU
 	rmd_scene *p_ = nullptr;
 };
 
-class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, the features' RMD_FEATURE_CHANNELS, or an ID buffer's 5 (RMD_ID_WORDS words); empty (a null pointer) until one is moved in
+class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, the features' RMD_FEATURE_CHANNELS, an ID buffer's 5 (RMD_ID_WORDS words), or an AO buffer's 2 (RMD_AO_WORDS words); empty (a null pointer) until one is moved in
   public:
-	enum Kind { Colour, Features, Ids };
+	enum Kind { Colour, Features, Ids, Ao };
 	Frame() = default;
 	Frame(rmd_context *ctx, size_t W, size_t H, Kind kind = Colour) : ctx_(ctx) {
 		if (kind == Features) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_feature_buffer_alloc");
 		else if (kind == Ids) check(rmd_id_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, reinterpret_cast<uint32_t **>(&p_)), ctx, "rmd_id_buffer_alloc");
+		else if (kind == Ao) check(rmd_ao_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, reinterpret_cast<uint32_t **>(&p_)), ctx, "rmd_ao_buffer_alloc");
 		else check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_framebuffer_alloc");
 	}
 	~Frame() {
@@ -1202,6 +1204,45 @@ std::vector<double> ids_matte_host(const std::vector<uint32_t> &words, size_t wi
 		other += rec[rmd::kIdOther] != 0u;
 	}
 	if (other_pixels) *other_pixels = other;
+	return out;
+}
+
+std::vector<uint32_t> render_ao(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double max_distance,
+                                int device) {
+	if (rects.size() != counts.size()) throw Error(RMD_ERR_INVALID_ARGUMENT, "render_ao: one sample count per rect");
+	const size_t W = settings.camera_settings.backbuffer_width, H = settings.camera_settings.backbuffer_height;
+	std::vector<uint32_t> out(W * H * RMD_AO_WORDS);
+	const Context ctx(device);
+	const Frame dev(ctx, W, H, Frame::Ao);
+	first_hit_per_count(ctx, scene, settings, rects, counts, [&](const rmd_scene *ds, const rmd_camera *cam, const rmd_settings *s, const rmd_tile_rect *r, uint32_t n) {
+		check(rmd_render_ao_async(ctx, ds, cam, s, r, n, max_distance, reinterpret_cast<uint32_t *>((double *)dev)), ctx, "rmd_render_ao");
+	});
+	check(rmd_framebuffer_download(ctx, dev, reinterpret_cast<double *>(out.data()), out.size() / 2), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+std::vector<double> ao_resolve(const std::vector<uint32_t> &words, size_t width, size_t height, double empty_value, int device, uint64_t *empty_pixels) {
+	if (words.size() != width * height * RMD_AO_WORDS) throw Error(RMD_ERR_INVALID_ARGUMENT, "ao_resolve: width * height * RMD_AO_WORDS words");
+	std::vector<double> out(width * height);
+	const Context ctx(device);
+	const Frame ao(ctx, width, height, Frame::Ao), res(ctx, width, height);
+	check(rmd_framebuffer_upload(ctx, reinterpret_cast<const double *>(words.data()), ao, words.size() / 2), ctx, "rmd_framebuffer_upload");
+	check(rmd_ao_resolve(ctx, reinterpret_cast<const uint32_t *>((double *)ao), (uint32_t)width, (uint32_t)height, empty_value, res, empty_pixels), ctx, "rmd_ao_resolve");
+	check(rmd_framebuffer_download(ctx, res, out.data(), out.size()), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+std::vector<double> ao_resolve_host(const std::vector<uint32_t> &words, size_t width, size_t height, double empty_value, uint64_t *empty_pixels) {
+	if (words.size() != width * height * RMD_AO_WORDS) throw Error(RMD_ERR_INVALID_ARGUMENT, "ao_resolve_host: width * height * RMD_AO_WORDS words");
+	if (!std::isfinite(empty_value)) throw Error(RMD_ERR_INVALID_ARGUMENT, "ao_resolve_host: empty_value is not finite");
+	std::vector<double> out(width * height);
+	uint64_t n_empty = 0;
+	for (size_t i = 0; i < width * height; i++) {
+		bool empty = false;
+		out[i] = rmd::ao_resolve_pixel(&words[i * RMD_AO_WORDS], empty_value, &empty);
+		n_empty += empty;
+	}
+	if (empty_pixels) *empty_pixels = n_empty;
 	return out;
 }
 

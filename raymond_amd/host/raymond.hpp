@@ -358,6 +358,18 @@ std::vector<double> ids_matte(const std::vector<uint32_t> &words, size_t width, 
 // the header to the numpy restatement
 std::vector<double> ids_matte_host(const std::vector<uint32_t> &words, size_t width, size_t height, const std::vector<uint32_t> &objects, uint64_t *other_pixels = nullptr);
 
+// The W*H*RMD_AO_WORDS ambient-occlusion words (raymond_hip.h's rmd_render_ao: per pixel occluded open none samples, the diffuse bounce ray off the first
+// hit tested against max_distance) of a frame whose rect i holds counts[i] samples, rendered on GPU `device` with the settings' camera, seed and DOF
+// flag: one call per distinct count.
+std::vector<uint32_t> render_ao(const Scene &scene, const Settings &settings, const std::vector<rmd_tile_rect> &rects, const std::vector<uint32_t> &counts, double max_distance,
+                                int device = 0);
+// rmd_ao_resolve on GPU `device` over host words: per pixel open / (open + occluded), empty_value where no sample has a first hit.  empty_pixels
+// (optional): the number of such pixels.
+std::vector<double> ao_resolve(const std::vector<uint32_t> &words, size_t width, size_t height, double empty_value = 1.0, int device = 0, uint64_t *empty_pixels = nullptr);
+// ... and on the host, from the header the kernel is built from (raymond_amd/csrc/ao_rule.hpp): no GPU.  What raymond_cli ao-resolve runs, and what holds
+// the header to the numpy restatement
+std::vector<double> ao_resolve_host(const std::vector<uint32_t> &words, size_t width, size_t height, double empty_value = 1.0, uint64_t *empty_pixels = nullptr);
+
 // rmd_resolve_tonemap_tiles on `ctx`: the rects of the width x height device framebuffer `accum_dev`, rect i at counts[i] samples per pixel, tone-mapped
 // into packed bytes — rect after rect, each row-major, 3 bytes per pixel.  accum2_dev (or null): a dual-buffer render's other half, added first.
 std::vector<uint8_t> resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, size_t width, size_t height,

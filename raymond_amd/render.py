@@ -1,8 +1,8 @@
 """The Python binding of the C-ABI (include/raymond_hip.h), and the reference-shaped render API on top of it.
 
 Bottom up:
-  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, IdBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, render_ids, ids_matte, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
+  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, IdBuffer, AoBuffer, ErrorImage, WinnerImage —, each a context manager;
+  * one thin wrapper per entry point: render_tiles, render_features, render_ids, ids_matte, render_ao, ao_resolve, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -217,6 +217,17 @@ class IdBuffer(Framebuffer):
         self.ctx.check(self.ctx.L.rmd_framebuffer_upload(self.ctx.handle, arr.ctypes.data_as(C.c_void_p), self.ptr, self.n))
 
 
+class AoBuffer(IdBuffer):
+    """W*H*4 uint32 ambient-occlusion counts of the first hit in HBM (rmd_ao_buffer_alloc): per pixel occluded open none samples.  The framebuffer
+    calls serve it with 2 doubles a pixel."""
+
+    ALLOC = "rmd_ao_buffer_alloc"
+    download_tiles = upload_tiles = _no_tile_transfers("AO buffers")
+
+    def _shape(self):
+        return (self.height, self.width, abi.RMD_AO_WORDS)
+
+
 def _render_call(ctx, stem, sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, *buffers):
     """rmd_render_*[_async]: `stem` or its _async form over `tiles` — a list of rects, or a ready (abi.TileRect array, n) pair."""
     cam = camera_settings.pod()
@@ -249,6 +260,22 @@ def ids_matte(ctx, ids, objects):
         return matte.download(), other.value
 
 
+def render_ao(ctx, dscene, camera_settings, settings, tiles, max_distance, ao, sample_begin=0, sample_count=None, sync=True):
+    """rmd_render_ao[_async]: count, for `sample_count` samples per pixel of `tiles`, whether the diffuse bounce ray off the first hit meets an object
+    nearer than `max_distance` (> 0; inf: any hit) into the AoBuffer `ao`."""
+    _render_call(ctx, "rmd_render_ao", sync, dscene, camera_settings, settings, tiles, sample_begin, sample_count, C.c_double(max_distance), ao.ptr)
+
+
+def ao_resolve(ctx, ao, empty_value=1.0):
+    """rmd_ao_resolve: open / (open + occluded) per pixel of the AoBuffer `ao`, `empty_value` where no sample has a first hit.  Returns ((H, W)
+    float64, empty_pixels): the openness and the number of such pixels."""
+    W, H = ao.width, ao.height
+    empty = C.c_uint64()
+    with ErrorImage(ctx, W, H) as out:
+        ctx.check(ctx.L.rmd_ao_resolve(ctx.handle, ao.ptr, W, H, C.c_double(empty_value), out.ptr, C.byref(empty)))
+        return out.download(), empty.value
+
+
 def _first_hit_arrays(ctx, scene, settings, rects, counts, buffer_types, render):
     """A first-hit pass over a frame whose rect i holds counts[i] samples, into zeroed buffers of `buffer_types`: one render(dscene, camera, rects, n,
     *buffers) per distinct non-zero sample count n over the rects that share it, then a synchronize.  Returns the buffers' downloads."""
@@ -268,6 +295,13 @@ def render_ids_arrays(ctx, scene, settings, rects, counts):
     its own count, with the settings' seed and DOF flag (as finished_tile_features renders the features).  Pixels no rect covers stay zero."""
     return _first_hit_arrays(ctx, scene, settings, rects, counts, (IdBuffer,),
                              lambda ds, cam, share, n, ids: render_ids(ctx, ds, cam, settings, share, ids, 0, n, sync=False))[0]
+
+
+def render_ao_arrays(ctx, scene, settings, rects, counts, max_distance):
+    """The (H, W, 4) uint32 AO words of a frame whose rect i holds counts[i] samples: one rmd_render_ao call per distinct sample count, each tile at
+    its own count, with the settings' seed and DOF flag (as render_ids_arrays renders the IDs).  Pixels no rect covers stay zero."""
+    return _first_hit_arrays(ctx, scene, settings, rects, counts, (AoBuffer,),
+                             lambda ds, cam, share, n, ao: render_ao(ctx, ds, cam, settings, share, max_distance, ao, 0, n, sync=False))[0]
 
 
 def ids_ranked(words):
