@@ -488,6 +488,52 @@ rmd_status rmd_render_ao_async(rmd_context *ctx, const rmd_scene *scene, const r
 rmd_status rmd_ao_resolve(rmd_context *ctx, const uint32_t *ao_dev, uint32_t width, uint32_t height, double empty_value, double *out_dev,
                           uint64_t *empty_pixels_host);
 /*
+ * CLOSEST-HIT QUERIES FOR CALLER-SUPPLIED RAYS (an addition within ABI 6: RMD_ABI_VERSION stays 6, no struct of an earlier version changes; a caller
+ * finds the functions by their symbols).  The passes above answer "what does this pixel see" for rays the library makes itself; these answer it for
+ * rays the caller hands in: picking, visibility between scene points, a pass of the caller's own built from hits.
+ * A RAY is RMD_RAY_DOUBLES = 6 doubles: origin x y z, direction x y z.  The direction is used as given and never normalised; t is in units of it, as in
+ * Scene::intersect (core/src/scene.rs:54-74).  Any bit pattern is allowed in any component.  A HIT is one rmd_ray_hit, 40 bytes = RMD_HIT_DOUBLES = 5
+ * doubles, so the framebuffer helpers serve both kinds of buffer as they are (n_doubles = 6n and 5n): rmd_framebuffer_zero / _download / _upload,
+ * and rmd_framebuffer_free, which frees any device block the library handed out — ray and hit buffers have no free call of their own, as ID and AO
+ * buffers have none.
+ * rmd_intersect_rays: for every i < n_rays, hits[i] is Scene::intersect on ray i — the closest hit over all objects, the comparison a strict '<', so
+ * the lower index wins a tie — with the normal rmd_render_features defines at frag = origin + direction * t: a plane's stored normal as stored,
+ * normalize(frag - centre) for a sphere, the interpolated triangle normal for a mesh (NaN included).  `triangle` is the grid's triangle index for a
+ * mesh object and 0 otherwise.  A miss writes {0, {0, 0, 0}, -1, 0} in full: hit buffers compare byte for byte.  Nothing else is written; a ray's
+ * record does not depend on n_rays, on the ray's index or on its neighbours.  rays_dev and hits_dev are device memory and must not overlap.
+ * rmd_intersect_rays waits for the context's stream and reports an earlier device fault, as rmd_render_features does; the _async form only enqueues
+ * (rmd_context_synchronize ends it).  rmd_intersect_rays_host is the convenience form on host memory — allocate, upload, call, download, free — and
+ * gives the same bytes.  None of them changes what rmd_last_launch_info and rmd_last_kernel_ms report.
+ * rmd_camera_rays writes, for every i < n_rays, the pinhole generate_primary_ray (src/trace.rs:322-333) of pixel (xy_host[2i], xy_host[2i + 1]) at the
+ * jitter uniforms (uv_host[2i], uv_host[2i + 1]) to rays_dev[6i ..]; uv_host NULL means 0.5, 0.5 everywhere, the pixel's centre, bit for bit.  Only
+ * position, fov_vert and the backbuffer size of the camera are read: there is no thin lens, whose rays need the sample's random stream.  Its output
+ * feeds rmd_intersect_rays without leaving the device.  Synchronous.
+ * Refused before the device is touched and with the buffers untouched, in this order:
+ *   1  a NULL pointer — scene, rays, hits, out_dev, camera, xy_host —: RMD_ERR_INVALID_ARGUMENT.  A NULL ray, hit or xy buffer is allowed only
+ *      when n_rays == 0;
+ *   2  n_rays > RMD_MAX_RAYS (2^30: the batch index stays a uint32_t): RMD_ERR_INVALID_ARGUMENT;
+ *   3  (rmd_camera_rays) a backbuffer width or height of 0 or above 65535, or a pixel outside the frame: RMD_ERR_INVALID_ARGUMENT;
+ *   4  a NULL context, then the scene's own refusals as a render makes them: a scene of another context is RMD_ERR_INVALID_ARGUMENT, a scene whose
+ *      object table and grid masks the launch cannot hold in a CU's LDS is RMD_ERR_UNSUPPORTED.
+ * n_rays == 0 is success with no launch (after the refusals).  rmd_ray_buffer_alloc / rmd_hit_buffer_alloc hand out zeroed buffers for n_rays
+ * rays (n_rays of 0 or above RMD_MAX_RAYS, or out_dev NULL: RMD_ERR_INVALID_ARGUMENT).
+ */
+#define RMD_RAY_DOUBLES 6u
+#define RMD_HIT_DOUBLES 5u
+#define RMD_MAX_RAYS (1ull << 30)
+typedef struct rmd_ray_hit {
+	double t;          /* distance of the closest hit; 0 on a miss */
+	double normal[3];  /* the normal the shading would use there; zeros on a miss */
+	int32_t object;    /* index into the scene's objects; -1 on a miss */
+	uint32_t triangle; /* the grid's triangle index for a mesh object, else 0 */
+} rmd_ray_hit;         /* 40 bytes */
+rmd_status rmd_ray_buffer_alloc(rmd_context *ctx, uint64_t n_rays, double **out_dev);      /* zeroed n*6 doubles */
+rmd_status rmd_hit_buffer_alloc(rmd_context *ctx, uint64_t n_rays, rmd_ray_hit **out_dev); /* zeroed n records */
+rmd_status rmd_intersect_rays(rmd_context *ctx, const rmd_scene *scene, const double *rays_dev, uint64_t n_rays, rmd_ray_hit *hits_dev);
+rmd_status rmd_intersect_rays_async(rmd_context *ctx, const rmd_scene *scene, const double *rays_dev, uint64_t n_rays, rmd_ray_hit *hits_dev);
+rmd_status rmd_intersect_rays_host(rmd_context *ctx, const rmd_scene *scene, const double *rays_host, uint64_t n_rays, rmd_ray_hit *hits_host);
+rmd_status rmd_camera_rays(rmd_context *ctx, const rmd_camera *camera, const uint32_t *xy_host, const double *uv_host, uint64_t n_rays, double *rays_dev);
+/*
  * rmd_denoise with a FEATURE WEIGHT (Rousselle, Manzi and Zwicker, "Robust Denoising using Feature and Color Information", 2013; an addition
  * within ABI 6).  Everything rmd_denoise defines stays word for word (validity, D(p, q), w_c = exp(-max(0, D)), clamping, sum orders, the output
  * for a pixel that is not valid).  Added, with F = feat_dev, G = feat_sq_dev (feature buffers as rmd_render_features writes them) and n_i the

@@ -120,6 +120,10 @@ rmd_status rmd_probe_work_items(uint32_t n_tiles, uint32_t n_whole, uint32_t k_t
                                 uint32_t *n_items);
 /* Host only: the LDS layout of an uploaded scene — objects in the table, grids, and words of the grids' occupancy masks. */
 rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total);
+/* Host code only (no kernel runs): the launch rmd_intersect_rays would make for n_rays rays on an uploaded scene, from the functions its launcher
+ * calls (raymond_amd/csrc/rays.hip: plan_rays_launch over rays_plan.hpp) — out6 = batches, waves per workgroup, workgroups, total waves, the
+ * workgroup's dynamic LDS in bytes, the context's CU count.  n_rays above RMD_MAX_RAYS is refused. */
+rmd_status rmd_probe_rays_plan(const rmd_scene *scene, uint64_t n_rays, uint64_t *out6);
 /* Host code only (no kernel runs; the grids' records are copied back from the scene's device): what rmd_scene_create decided once for an uploaded
  * scene and every launch of it reads — out8 = n_grid_objects, regular, walk_steps_bound, axis_pairs, visit_mask, grid_mask, n_grids, 0 — and, for the
  * first n of its grids, shift_bits2 = mask_shift and mask_bits per grid.  tests/test_gpu_mesh_scenes.py asserts from it that a class of

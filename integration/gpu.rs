@@ -46,6 +46,10 @@ pub struct rmd_settings { pub bounce_limit: u32, pub sample_begin: u32, pub samp
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct rmd_tile_rect { pub left: u32, pub top: u32, pub width: u32, pub height: u32 }
+/// rmd_intersect_rays' record for one ray, 40 bytes: a miss is t 0, a zero normal, object -1, triangle 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct rmd_ray_hit { pub t: f64, pub normal: [f64; 3], pub object: i32, pub triangle: u32 }
 pub enum rmd_context {}
 pub enum rmd_scene {}
 
@@ -100,6 +104,20 @@ extern "C" {
     #[allow(dead_code)]
     fn rmd_ao_resolve(ctx: *mut rmd_context, ao_dev: *const u32, width: u32, height: u32, empty_value: f64, out_dev: *mut f64,
                       empty_pixels_host: *mut u64) -> i32;
+    // closest-hit queries for the caller's own rays (6 f64 a ray: origin, direction as given; one 40-byte rmd_ray_hit a ray) and the pinhole camera's rays
+    // for explicit pixels; rmd_framebuffer_free frees both kinds of buffer
+    #[allow(dead_code)]
+    fn rmd_ray_buffer_alloc(ctx: *mut rmd_context, n_rays: u64, out_dev: *mut *mut f64) -> i32;
+    #[allow(dead_code)]
+    fn rmd_hit_buffer_alloc(ctx: *mut rmd_context, n_rays: u64, out_dev: *mut *mut rmd_ray_hit) -> i32;
+    #[allow(dead_code)]
+    fn rmd_intersect_rays(ctx: *mut rmd_context, scene: *const rmd_scene, rays_dev: *const f64, n_rays: u64, hits_dev: *mut rmd_ray_hit) -> i32;
+    #[allow(dead_code)]
+    fn rmd_intersect_rays_async(ctx: *mut rmd_context, scene: *const rmd_scene, rays_dev: *const f64, n_rays: u64, hits_dev: *mut rmd_ray_hit) -> i32;
+    #[allow(dead_code)]
+    fn rmd_intersect_rays_host(ctx: *mut rmd_context, scene: *const rmd_scene, rays_host: *const f64, n_rays: u64, hits_host: *mut rmd_ray_hit) -> i32;
+    #[allow(dead_code)]
+    fn rmd_camera_rays(ctx: *mut rmd_context, camera: *const rmd_camera, xy_host: *const u32, uv_host: *const f64, n_rays: u64, rays_dev: *mut f64) -> i32;
     fn rmd_denoise_guided(ctx: *mut rmd_context, accum_dev: *const f64, accum_sq_dev: *const f64, feat_dev: *const f64, feat_sq_dev: *const f64,
                           width: u32, height: u32, rects: *const rmd_tile_rect, rect_sample_counts: *const u32, n_rects: u32, radius: u32,
                           patch_radius: u32, k: f64, alpha: f64, k_f: f64, tau: f64, out_dev: *mut f64) -> i32;

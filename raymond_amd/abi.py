@@ -40,6 +40,9 @@ RMD_MAX_BOUNCE_LIMIT = 16
 RMD_FEATURE_CHANNELS = 7  # first-hit feature buffers: 0..2 normal xyz, 3..5 albedo rgb, 6 depth
 RMD_ID_SLOTS, RMD_ID_WORDS, RMD_ID_MISS = 4, 10, 0xFFFFFFFF  # ID buffers: key_0 count_0 .. key_3 count_3 other samples; the key of a miss
 RMD_AO_WORDS = 4  # AO buffers: occluded open none samples
+RMD_RAY_DOUBLES = 6  # a caller-supplied ray: origin xyz, direction xyz
+RMD_HIT_DOUBLES = 5  # rmd_ray_hit, 40 bytes: a hit buffer is 5 * n doubles to the framebuffer helpers
+RMD_MAX_RAYS = 1 << 30  # rmd_intersect_rays, rmd_camera_rays: the most rays of one call
 RMD_ATROUS_MAX_LEVELS = 8  # rmd_denoise_atrous: the most levels a call may ask for
 RMD_RENDER_DOF = 1  # rmd_settings.flags
 RMD_RENDER_TRACE_BLACK_PATHS = 2  # never end a zero-throughput path early
@@ -116,6 +119,15 @@ class TileRect(C.Structure):
         ("top", C.c_uint32),
         ("width", C.c_uint32),
         ("height", C.c_uint32),
+    ]
+
+
+class RayHit(C.Structure):  # rmd_ray_hit: rmd_intersect_rays' record for one ray, 40 bytes
+    _fields_ = [
+        ("t", C.c_double),
+        ("normal", C.c_double * 3),
+        ("object", C.c_int32),
+        ("triangle", C.c_uint32),
     ]
 
 

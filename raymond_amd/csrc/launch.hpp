@@ -205,6 +205,15 @@ hipError_t launch_ao(hipStream_t stream, const RenderParams &P, const DevObject 
 // rmd_ao_resolve (ao.hip): out[i] = pixel i's open / (open + occluded), empty_value where the sum is 0 (ao_rule.hpp: ao_resolve_pixel), and
 // *empty_pixels (zeroed by the caller) += the pixels where it is
 hipError_t launch_ao_resolve(hipStream_t stream, const uint32_t *ao, uint64_t n_pixels, double empty_value, double *out, unsigned long long *empty_pixels);
+// rmd_intersect_rays (rays.hip): hits[i] = Scene::intersect on ray i with rmd_render_features' normal, i < n_rays <= RMD_MAX_RAYS; of P the scene's fields
+// are read (n_objects, n_grids, mask_words_total, axis_pairs, visit_mask).  n_cus sizes the launch (rays_plan.hpp)
+hipError_t launch_rays(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids, uint32_t n_cus, const double *rays, uint64_t n_rays,
+                       rmd_ray_hit *hits);
+// the launch that would be (rays.hip): the plan, the workgroup's dynamic LDS and its per-wave area (both may be null); false: the scene's tables do not fit
+struct RaysPlan;
+bool plan_rays_launch(const RenderParams &P, uint64_t n_rays, uint32_t n_cus, RaysPlan &plan, size_t *lds, size_t *wave_lds);
+// rmd_camera_rays (rays.hip): rays[6i ..] = the pinhole primary ray of pixel xy[2i], xy[2i + 1] at uv[2i], uv[2i + 1] (uv null: 0.5, 0.5); device memory
+hipError_t launch_camera_rays(hipStream_t stream, const RenderParams &P, const uint32_t *xy, const double *uv, uint64_t n_rays, double *rays);
 hipError_t launch_render_list(hipStream_t stream, const RenderParams &P, const DevObject *objs, const DevGrid *grids,
                               const ListWork *list, double *rgb_out, int32_t *path_obj, uint32_t *path_sub);
 // tile rectangles of a frame <-> a packed buffer (kernels.hip: tile_copy_kernel); `first[i]` = pixels in front of rect i

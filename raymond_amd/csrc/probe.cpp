@@ -7,6 +7,7 @@
 #include "../../include/raymond_hip_probe.h"
 #include "internal.hpp"
 #include "launch.hpp"
+#include "rays_plan.hpp"
 
 namespace {
 
@@ -403,6 +404,18 @@ rmd_status rmd_probe_atrous_region_slope_planes(rmd_context *ctx, uint32_t width
 rmd_status rmd_probe_scene_layout(const rmd_scene *scene, uint32_t *n_objects, uint32_t *n_grids, uint32_t *mask_words_total) {
 	if (!scene || !n_objects || !n_grids || !mask_words_total) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
 	*n_objects = scene->n_objects, *n_grids = scene->n_grids, *mask_words_total = scene->mask_words_total;
+	return RMD_OK;
+}
+
+rmd_status rmd_probe_rays_plan(const rmd_scene *scene, uint64_t n_rays, uint64_t *out6) {
+	if (!scene || !scene->ctx || !out6 || n_rays > RMD_MAX_RAYS) return rmd::fail(nullptr, RMD_ERR_INVALID_ARGUMENT, "probe: bad argument");
+	rmd::RenderParams P;
+	std::memset(&P, 0, sizeof(P));
+	P.n_objects = scene->n_objects, P.n_grids = scene->n_grids, P.mask_words_total = scene->mask_words_total; // what the plan reads of a launch's parameters
+	rmd::RaysPlan plan;
+	size_t lds = 0;
+	if (!rmd::plan_rays_launch(P, n_rays, scene->ctx->n_cus, plan, &lds, nullptr)) return rmd::fail(nullptr, RMD_ERR_UNSUPPORTED, "probe: the scene's tables do not fit a CU's LDS");
+	out6[0] = plan.batches, out6[1] = plan.waves_per_wg, out6[2] = plan.workgroups, out6[3] = plan.total_waves, out6[4] = lds, out6[5] = scene->ctx->n_cus;
 	return RMD_OK;
 }
 

@@ -100,6 +100,17 @@
 //   raymond_cli ao-resolve AO.u32 W H OUT.f64 [EMPTY]
 //                                         rmd_ao_resolve made on the host (raymond::ao_resolve_host, from the header the kernel is built from; no GPU) over raw
 //                                         W*H*4 uint32 AO words; EMPTY: the value of a pixel without a first hit, by default 1; prints the number of such pixels
+//   raymond_cli intersect SCENE --rays IN.f64 --out OUT.hits
+//                                         rmd_intersect_rays (raymond::intersect_rays, GPU 0) on the rays of IN.f64: raw f64, 6 a ray — origin xyz, direction xyz,
+//                                         the direction used as given; a file whose size is no multiple of 48 bytes is refused.  OUT.hits: one raw 40-byte
+//                                         rmd_ray_hit a ray (t, normal xyz as f64, object as int32, triangle as uint32; a miss is 0, zeros, -1, 0).  SCENE:
+//                                         spheres, dragon[:n], project:in.json, or the path of a project file.  Prints the number of rays and of hits
+//   raymond_cli pick SCENE --pixel X,Y [--size W,H] [--fov DEGREES] [--position X,Y,Z]
+//                                         what pixel (X, Y) of a W x H frame (by default 1920,1080) sees through its centre, from a camera of vertical field of view
+//                                         DEGREES (55) at X,Y,Z (0,0,0): rmd_camera_rays and rmd_intersect_rays on GPU 0 (raymond::pick).  Prints ONE line,
+//                                         "object triangle t nx ny nz": the object's index in the scene (-1: the background) and the mesh triangle (0 for a plane,
+//                                         a sphere and the background) as decimal integers, the distance and the normal as %.17g doubles.  A pixel outside the
+//                                         frame, a malformed option or one without its value is refused before the scene is built
 //   raymond_cli display-weights EXPOSURE GAMMA FLOOR
 //                                         rmd_display_weights: its 260 weights, one per line, as their 64 bits in hexadecimal
 //   raymond_cli hostapi <spheres|dragon[:n]> W H SPP BOUNCES SPI [--end-black-paths 1] [--preview-every N [--preview-denoise 1]] [--progress-tiles 0]
@@ -183,6 +194,43 @@ static std::vector<uint32_t> parse_objects(const std::string &list) {
 		at = end + 1;
 	}
 	return out;
+}
+
+// spheres | dragon[:n] | project:in.json | in.json (render's scene words, and a bare project path)
+static Scene scene_of(const std::string &what) {
+	if (what == "spheres") return reflective_spheres();
+	if (what.rfind("dragon", 0) == 0) return gold_dragon_standin(what.size() > 7 ? std::atoi(what.c_str() + 7) : 91);
+	if (what.rfind("project:", 0) == 0) return Project::load(what.substr(8)).build_scene(); // core/src/project.rs
+	if (what.size() > 5 && what.compare(what.size() - 5, 5, ".json") == 0) return Project::load(what).build_scene();
+	throw Error(RMD_ERR_INVALID_ARGUMENT, "unknown scene " + what);
+}
+
+// "a,b[,c]" -> exactly n numbers, each read whole by `read`; anything else is refused under the option's name
+template <class T, class Read>
+static std::vector<T> parse_list(const char *option, const std::string &text, size_t n, Read read) {
+	std::vector<T> out;
+	for (size_t at = 0; at <= text.size();) {
+		const size_t end = std::min(text.find(',', at), text.size());
+		const std::string word = text.substr(at, end - at);
+		char *stop = nullptr;
+		const T v = read(word.c_str(), &stop);
+		if (word.empty() || word[0] == ' ' || *stop != '\0') throw Error(RMD_ERR_INVALID_ARGUMENT, std::string(option) + ": not a number: '" + word + "'");
+		out.push_back(v);
+		at = end + 1;
+	}
+	if (out.size() != n) throw Error(RMD_ERR_INVALID_ARGUMENT, std::string(option) + ": " + std::to_string(n) + " comma-separated values, not '" + text + "'");
+	return out;
+}
+static std::vector<uint32_t> parse_u32s(const char *option, const std::string &text, size_t n) {
+	return parse_list<uint32_t>(option, text, n, [&](const char *w, char **stop) -> uint32_t {
+		if (*w < '0' || *w > '9') throw Error(RMD_ERR_INVALID_ARGUMENT, std::string(option) + ": not an unsigned integer: '" + w + "'");
+		const unsigned long long v = std::strtoull(w, stop, 10);
+		if (v > 0xFFFFFFFFull) throw Error(RMD_ERR_INVALID_ARGUMENT, std::string(option) + ": above 2^32 - 1: '" + w + "'");
+		return (uint32_t)v;
+	});
+}
+static std::vector<double> parse_doubles(const char *option, const std::string &text, size_t n) {
+	return parse_list<double>(option, text, n, [](const char *w, char **stop) { return std::strtod(w, stop); });
 }
 
 static void dump_mesh(const Mesh &m, const std::string &path) {
@@ -352,6 +400,58 @@ int main(int argc, char **argv) {
 			std::ofstream o(argv[5], std::ios::binary);
 			o.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)(out.size() * 8));
 			std::printf("%llu\n", (unsigned long long)empty);
+			return 0;
+		}
+		if (argc >= 2 && !std::strcmp(argv[1], "intersect")) {
+			std::string rays_path, out_path;
+			if (argc < 3 || (argc - 3) % 2 != 0) throw Error(RMD_ERR_INVALID_ARGUMENT, "intersect: SCENE --rays IN.f64 --out OUT.hits");
+			for (int i = 3; i + 1 < argc; i += 2) {
+				if (!std::strcmp(argv[i], "--rays")) rays_path = argv[i + 1];
+				else if (!std::strcmp(argv[i], "--out")) out_path = argv[i + 1];
+				else throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("intersect: unknown option ") + argv[i]);
+			}
+			if (rays_path.empty() || out_path.empty()) throw Error(RMD_ERR_INVALID_ARGUMENT, "intersect: --rays and --out are both needed");
+			std::ifstream f(rays_path, std::ios::binary | std::ios::ate);
+			if (!f) throw Error(RMD_ERR_INVALID_ARGUMENT, "cannot read " + rays_path);
+			const size_t bytes = (size_t)f.tellg();
+			if (bytes % (RMD_RAY_DOUBLES * sizeof(double)) != 0)
+				throw Error(RMD_ERR_INVALID_ARGUMENT, rays_path + ": " + std::to_string(bytes) + " bytes is no whole number of 48-byte rays");
+			if (bytes / (RMD_RAY_DOUBLES * sizeof(double)) > RMD_MAX_RAYS) throw Error(RMD_ERR_INVALID_ARGUMENT, rays_path + ": more than RMD_MAX_RAYS rays");
+			std::vector<double> rays(bytes / sizeof(double));
+			f.seekg(0);
+			if (!rays.empty() && !f.read(reinterpret_cast<char *>(rays.data()), (std::streamsize)bytes)) throw Error(RMD_ERR_INVALID_ARGUMENT, "cannot read " + rays_path);
+			const std::vector<rmd_ray_hit> hits = rays.empty() ? std::vector<rmd_ray_hit>() : intersect_rays(scene_of(argv[2]), rays, 0);
+			std::ofstream o(out_path, std::ios::binary);
+			o.write(reinterpret_cast<const char *>(hits.data()), (std::streamsize)(hits.size() * sizeof(rmd_ray_hit)));
+			if (!o) throw Error(RMD_ERR_INVALID_ARGUMENT, "cannot write " + out_path);
+			size_t n_hit = 0;
+			for (const rmd_ray_hit &h : hits) n_hit += h.object >= 0;
+			std::printf("%zu rays, %zu hits\n", hits.size(), n_hit);
+			return 0;
+		}
+		if (argc >= 2 && !std::strcmp(argv[1], "pick")) {
+			if (argc < 3 || (argc - 3) % 2 != 0) throw Error(RMD_ERR_INVALID_ARGUMENT, "pick: SCENE --pixel X,Y [--size W,H] [--fov DEGREES] [--position X,Y,Z]");
+			Settings st;
+			st.camera_settings.backbuffer_width = 1920, st.camera_settings.backbuffer_height = 1080;
+			st.camera_settings.fov_vert = 55.0, st.camera_settings.focal_length = 2.5;
+			std::vector<uint32_t> pixel;
+			for (int i = 3; i + 1 < argc; i += 2) {
+				if (!std::strcmp(argv[i], "--pixel")) pixel = parse_u32s("--pixel", argv[i + 1], 2);
+				else if (!std::strcmp(argv[i], "--size")) {
+					const std::vector<uint32_t> size = parse_u32s("--size", argv[i + 1], 2);
+					st.camera_settings.backbuffer_width = size[0], st.camera_settings.backbuffer_height = size[1];
+				} else if (!std::strcmp(argv[i], "--fov")) st.camera_settings.fov_vert = parse_doubles("--fov", argv[i + 1], 1)[0];
+				else if (!std::strcmp(argv[i], "--position")) {
+					const std::vector<double> at = parse_doubles("--position", argv[i + 1], 3);
+					st.camera_settings.transform.position = {at[0], at[1], at[2]};
+				} else throw Error(RMD_ERR_INVALID_ARGUMENT, std::string("pick: unknown option ") + argv[i]);
+			}
+			if (pixel.empty()) throw Error(RMD_ERR_INVALID_ARGUMENT, "pick: --pixel X,Y is needed");
+			const size_t W = st.camera_settings.backbuffer_width, H = st.camera_settings.backbuffer_height;
+			if (W == 0 || H == 0 || W > 65535 || H > 65535) throw Error(RMD_ERR_INVALID_ARGUMENT, "pick: --size must be 1..65535 per axis");
+			if (pixel[0] >= W || pixel[1] >= H) throw Error(RMD_ERR_INVALID_ARGUMENT, "pick: pixel outside the frame");
+			const rmd_ray_hit h = pick(scene_of(argv[2]), st, pixel[0], pixel[1], 0);
+			std::printf("%d %u %.17g %.17g %.17g %.17g\n", h.object, h.triangle, h.t, h.normal[0], h.normal[1], h.normal[2]);
 			return 0;
 		}
 		if (argc >= 5 && !std::strcmp(argv[1], "display-weights")) {

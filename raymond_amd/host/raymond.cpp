@@ -208,14 +208,16 @@ class DeviceScene { // a Scene flattened and uploaded to a context's GPU
 	rmd_scene *p_ = nullptr;
 };
 
-class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, the features' RMD_FEATURE_CHANNELS, an ID buffer's 5 (RMD_ID_WORDS words), or an AO buffer's 2 (RMD_AO_WORDS words); empty (a null pointer) until one is moved in
+class Frame { // a zeroed W x H device buffer of sums: 3 doubles a pixel, the features' RMD_FEATURE_CHANNELS, an ID buffer's 5 (RMD_ID_WORDS words), or an AO buffer's 2 (RMD_AO_WORDS words) — or W * H rays (6 doubles each) or hit records (5); empty (a null pointer) until one is moved in
   public:
-	enum Kind { Colour, Features, Ids, Ao };
+	enum Kind { Colour, Features, Ids, Ao, Rays, Hits };
 	Frame() = default;
 	Frame(rmd_context *ctx, size_t W, size_t H, Kind kind = Colour) : ctx_(ctx) {
 		if (kind == Features) check(rmd_feature_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_feature_buffer_alloc");
 		else if (kind == Ids) check(rmd_id_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, reinterpret_cast<uint32_t **>(&p_)), ctx, "rmd_id_buffer_alloc");
 		else if (kind == Ao) check(rmd_ao_buffer_alloc(ctx, (uint32_t)W, (uint32_t)H, reinterpret_cast<uint32_t **>(&p_)), ctx, "rmd_ao_buffer_alloc");
+		else if (kind == Rays) check(rmd_ray_buffer_alloc(ctx, (uint64_t)W * H, &p_), ctx, "rmd_ray_buffer_alloc");
+		else if (kind == Hits) check(rmd_hit_buffer_alloc(ctx, (uint64_t)W * H, reinterpret_cast<rmd_ray_hit **>(&p_)), ctx, "rmd_hit_buffer_alloc");
 		else check(rmd_framebuffer_alloc(ctx, (uint32_t)W, (uint32_t)H, &p_), ctx, "rmd_framebuffer_alloc");
 	}
 	~Frame() {
@@ -1243,6 +1245,46 @@ std::vector<double> ao_resolve_host(const std::vector<uint32_t> &words, size_t w
 		n_empty += empty;
 	}
 	if (empty_pixels) *empty_pixels = n_empty;
+	return out;
+}
+
+std::vector<rmd_ray_hit> intersect_rays(const Scene &scene, const std::vector<double> &rays, int device) {
+	if (rays.size() % RMD_RAY_DOUBLES != 0) throw Error(RMD_ERR_INVALID_ARGUMENT, "intersect_rays: RMD_RAY_DOUBLES doubles a ray");
+	const size_t n = rays.size() / RMD_RAY_DOUBLES;
+	std::vector<rmd_ray_hit> out(n);
+	if (n == 0) return out;
+	const Context ctx(device);
+	const DeviceScene ds(ctx, scene);
+	const Frame d_rays(ctx, n, 1, Frame::Rays), d_hits(ctx, n, 1, Frame::Hits);
+	check(rmd_framebuffer_upload(ctx, rays.data(), d_rays, rays.size()), ctx, "rmd_framebuffer_upload");
+	check(rmd_intersect_rays(ctx, ds, d_rays, n, reinterpret_cast<rmd_ray_hit *>((double *)d_hits)), ctx, "rmd_intersect_rays");
+	check(rmd_framebuffer_download(ctx, d_hits, reinterpret_cast<double *>(out.data()), n * RMD_HIT_DOUBLES), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+std::vector<double> camera_rays(const Settings &settings, const std::vector<uint32_t> &xy, const std::vector<double> *uv, int device) {
+	if (xy.size() % 2 != 0 || (uv && uv->size() != xy.size())) throw Error(RMD_ERR_INVALID_ARGUMENT, "camera_rays: one x, y pair a ray, and one u, v pair when uv is given");
+	const size_t n = xy.size() / 2;
+	std::vector<double> out(n * RMD_RAY_DOUBLES);
+	if (n == 0) return out;
+	const rmd_camera cam = camera_pod(settings);
+	const Context ctx(device);
+	const Frame d_rays(ctx, n, 1, Frame::Rays);
+	check(rmd_camera_rays(ctx, &cam, xy.data(), uv ? uv->data() : nullptr, n, d_rays), ctx, "rmd_camera_rays");
+	check(rmd_framebuffer_download(ctx, d_rays, out.data(), out.size()), ctx, "rmd_framebuffer_download");
+	return out;
+}
+
+rmd_ray_hit pick(const Scene &scene, const Settings &settings, uint32_t x, uint32_t y, int device) {
+	const rmd_camera cam = camera_pod(settings);
+	const uint32_t xy[2] = {x, y};
+	rmd_ray_hit out;
+	const Context ctx(device);
+	const DeviceScene ds(ctx, scene);
+	const Frame d_rays(ctx, 1, 1, Frame::Rays), d_hits(ctx, 1, 1, Frame::Hits);
+	check(rmd_camera_rays(ctx, &cam, xy, nullptr, 1, d_rays), ctx, "rmd_camera_rays");
+	check(rmd_intersect_rays(ctx, ds, d_rays, 1, reinterpret_cast<rmd_ray_hit *>((double *)d_hits)), ctx, "rmd_intersect_rays");
+	check(rmd_framebuffer_download(ctx, d_hits, reinterpret_cast<double *>(&out), RMD_HIT_DOUBLES), ctx, "rmd_framebuffer_download");
 	return out;
 }
 

@@ -370,6 +370,15 @@ std::vector<double> ao_resolve(const std::vector<uint32_t> &words, size_t width,
 // the header to the numpy restatement
 std::vector<double> ao_resolve_host(const std::vector<uint32_t> &words, size_t width, size_t height, double empty_value = 1.0, uint64_t *empty_pixels = nullptr);
 
+// Closest-hit queries for the caller's own rays (raymond_hip.h's rmd_intersect_rays): rays holds 6 doubles a ray — origin xyz, direction xyz, the direction
+// used as given —, the result one rmd_ray_hit a ray (a miss: object -1, t 0, a zero normal, triangle 0).  The scene is uploaded to GPU `device` for the call.
+std::vector<rmd_ray_hit> intersect_rays(const Scene &scene, const std::vector<double> &rays, int device = 0);
+// rmd_camera_rays on GPU `device`: the pinhole primary rays of the settings' camera for the pixels xy (x, y pairs) at the jitter uniforms uv (pairs, or
+// null: 0.5, 0.5 — the pixel centres), 6 doubles a ray
+std::vector<double> camera_rays(const Settings &settings, const std::vector<uint32_t> &xy, const std::vector<double> *uv = nullptr, int device = 0);
+// What pixel (x, y) of the settings' camera sees through its centre: the ray is made and intersected on the device
+rmd_ray_hit pick(const Scene &scene, const Settings &settings, uint32_t x, uint32_t y, int device = 0);
+
 // rmd_resolve_tonemap_tiles on `ctx`: the rects of the width x height device framebuffer `accum_dev`, rect i at counts[i] samples per pixel, tone-mapped
 // into packed bytes — rect after rect, each row-major, 3 bytes per pixel.  accum2_dev (or null): a dual-buffer render's other half, added first.
 std::vector<uint8_t> resolve_tonemap_tiles(rmd_context *ctx, const double *accum_dev, const double *accum2_dev, size_t width, size_t height,

@@ -176,6 +176,12 @@ SIGNATURES = {
         [_vp, _vp, _P(abi.Camera), _P(abi.Settings), _P(abi.TileRect), C.c_uint32, C.c_double, _vp],
     ),
     "rmd_ao_resolve": (C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp, _P(C.c_uint64)]),
+    "rmd_ray_buffer_alloc": (C.c_int32, [_vp, C.c_uint64, _P(_vp)]),
+    "rmd_hit_buffer_alloc": (C.c_int32, [_vp, C.c_uint64, _P(_vp)]),
+    "rmd_intersect_rays": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, _vp]),
+    "rmd_intersect_rays_async": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, _vp]),
+    "rmd_intersect_rays_host": (C.c_int32, [_vp, _vp, _vp, C.c_uint64, _vp]),
+    "rmd_camera_rays": (C.c_int32, [_vp, _P(abi.Camera), _vp, _vp, C.c_uint64, _vp]),
     "rmd_context_synchronize": (C.c_int32, [_vp]),
     "rmd_render_tiles_host": (
         C.c_int32,

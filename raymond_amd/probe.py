@@ -41,6 +41,7 @@ _SIGS = {
     "rmd_probe_work_items": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _sz, _vp, _P(C.c_uint32)],
     "rmd_probe_scene_layout": [_vp, _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)],
     "rmd_probe_scene_plan": [_vp, _vp, _sz, _vp],
+    "rmd_probe_rays_plan": [_vp, C.c_uint64, _vp],
     "rmd_probe_denoise_scratch": [C.c_uint32] * 6 + [C.c_uint64, _vp, _P(C.c_uint64)],
     "rmd_probe_feature_slope": [_vp, _vp, C.c_uint32, C.c_uint32, C.c_double, _vp],
     "rmd_probe_atrous_region_slope_planes": [_vp, C.c_uint32, C.c_uint32, _vp],
@@ -310,6 +311,17 @@ def scene_layout(dscene):
     n, g, m = C.c_uint32(), C.c_uint32(), C.c_uint32()
     _host_check(L.rmd_probe_scene_layout(dscene.handle, C.byref(n), C.byref(g), C.byref(m)), "rmd_probe_scene_layout")
     return n.value, g.value, m.value
+
+
+RAYS_PLAN_FIELDS = ("batches", "waves_per_wg", "workgroups", "total_waves", "lds", "n_cus")
+
+
+def rays_plan(dscene, n_rays):
+    """The launch rmd_intersect_rays would make for `n_rays` rays on an uploaded scene -> dict keyed by RAYS_PLAN_FIELDS.  api: rmd_probe_rays_plan."""
+    L = _L()
+    out = np.zeros(6, dtype=np.uint64)
+    _host_check(L.rmd_probe_rays_plan(dscene.handle, int(n_rays), _p(out)), "rmd_probe_rays_plan")
+    return dict(zip(RAYS_PLAN_FIELDS, (int(v) for v in out)))
 
 
 SCENE_PLAN_FIELDS = ("n_grid_objects", "regular", "walk_steps_bound", "axis_pairs", "visit_mask", "grid_mask", "n_grids")

@@ -1,8 +1,8 @@
 """The Python binding of the C-ABI (include/raymond_hip.h), and the reference-shaped render API on top of it.
 
 Bottom up:
-  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, IdBuffer, AoBuffer, ErrorImage, WinnerImage —, each a context manager;
-  * one thin wrapper per entry point: render_tiles, render_features, render_ids, ids_matte, render_ao, ao_resolve, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
+  * the device objects — Context, DeviceScene, Framebuffer and its kinds FeatureBuffer, IdBuffer, AoBuffer, ErrorImage, WinnerImage, and RayBuffer / HitBuffer —, each a context manager;
+  * one thin wrapper per entry point: render_tiles, render_features, render_ids, ids_matte, render_ao, ao_resolve, intersect_rays[_dev[_async]], camera_rays, pick, tile_error[_dual], tile_luma_error, tile_weighted_error[_dual], display_weights, despike[_dual], the denoise family (every rmd_denoise* call is laid out
     by _denoise_call), resolve_tonemap[_tiles], luminance_histogram;
   * the *_arrays helpers, the same calls for host arrays (_staged puts the arrays on the device);
   * `render_tiled(scene, settings) -> TaskHandle`, which keeps the reference's shape (src/trace.rs:137-230, TaskHandle :70-135): the framebuffer is split
@@ -15,6 +15,7 @@ Bottom up:
 
 tests/binding_trace.py pins which C call every function here makes, with which arguments in which order, against a recording stand-in for the library.
 """
+import collections
 import contextlib
 import ctypes as C
 
@@ -274,6 +275,105 @@ def ao_resolve(ctx, ao, empty_value=1.0):
     with ErrorImage(ctx, W, H) as out:
         ctx.check(ctx.L.rmd_ao_resolve(ctx.handle, ao.ptr, W, H, C.c_double(empty_value), out.ptr, C.byref(empty)))
         return out.download(), empty.value
+
+
+class RayBuffer(_Scoped):
+    """n rays in HBM (rmd_ray_buffer_alloc): 6 f64 a ray, origin xyz then direction xyz.  The framebuffer calls serve it with 6 doubles a ray."""
+
+    ALLOC, DOUBLES = "rmd_ray_buffer_alloc", abi.RMD_RAY_DOUBLES
+
+    def __init__(self, ctx, n):
+        self.ctx, self.count = ctx, int(n)
+        self.n = self.count * self.DOUBLES  # (in doubles: what the transfers count in)
+        self.ptr = C.c_void_p()
+        ctx.check(getattr(ctx.L, self.ALLOC)(ctx.handle, self.count, C.byref(self.ptr)))
+
+    def _host(self, arr=None):
+        return np.empty((self.count, self.DOUBLES), dtype=np.float64) if arr is None else np.ascontiguousarray(arr, dtype=np.float64)
+
+    def download(self):
+        out = self._host()
+        self.ctx.check(self.ctx.L.rmd_framebuffer_download(self.ctx.handle, self.ptr, out.ctypes.data_as(C.c_void_p), self.n))
+        return out
+
+    def upload(self, arr):
+        arr = self._host(arr)
+        assert arr.nbytes == 8 * self.n
+        self.ctx.check(self.ctx.L.rmd_framebuffer_upload(self.ctx.handle, arr.ctypes.data_as(C.c_void_p), self.ptr, self.n))
+
+    def close(self):
+        if self.ptr:
+            self.ctx.L.rmd_framebuffer_free(self.ctx.handle, self.ptr)
+            self.ptr = C.c_void_p()
+
+
+HIT_DTYPE = np.dtype([("t", "<f8"), ("normal", "<f8", (3,)), ("object", "<i4"), ("triangle", "<u4")])  # rmd_ray_hit, 40 bytes
+Hits = collections.namedtuple("Hits", "object triangle t normal")
+
+
+def hits_of(records):
+    """The Hits views — object int32, triangle uint32, t f64, normal (n, 3) f64 — of one structured array of HIT_DTYPE records."""
+    return Hits(records["object"], records["triangle"], records["t"], records["normal"])
+
+
+class HitBuffer(RayBuffer):
+    """n rmd_ray_hit records in HBM (rmd_hit_buffer_alloc), 40 bytes each.  The framebuffer calls serve it with 5 doubles a record; download() returns
+    a structured array of HIT_DTYPE and upload() takes one."""
+
+    ALLOC, DOUBLES = "rmd_hit_buffer_alloc", abi.RMD_HIT_DOUBLES
+
+    def _host(self, arr=None):
+        return np.empty(self.count, dtype=HIT_DTYPE) if arr is None else np.ascontiguousarray(arr, dtype=HIT_DTYPE)
+
+
+def intersect_rays_dev(ctx, dscene, rays, hits, n=None, sync=True):
+    """rmd_intersect_rays[_async]: the closest hit of each of the first `n` (default: all) rays of the RayBuffer `rays` into the HitBuffer `hits`."""
+    n = rays.count if n is None else int(n)
+    fn = ctx.L.rmd_intersect_rays if sync else ctx.L.rmd_intersect_rays_async
+    ctx.check(fn(ctx.handle, dscene.handle, rays.ptr, n, hits.ptr))
+
+
+def intersect_rays_dev_async(ctx, dscene, rays, hits, n=None):
+    """rmd_intersect_rays_async: only enqueued on the context's stream; ctx.synchronize() ends it."""
+    intersect_rays_dev(ctx, dscene, rays, hits, n, sync=False)
+
+
+def intersect_rays(ctx, dscene, rays):
+    """rmd_intersect_rays_host: the closest hit of each ray of the (n, 6) array `rays` (origin xyz, direction xyz; the direction is used as given).
+    Returns Hits(object, triangle, t, normal), views of one structured download; a miss is object -1, t 0, a zero normal and triangle 0."""
+    rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, abi.RMD_RAY_DOUBLES)
+    out = np.empty(len(rays), dtype=HIT_DTYPE)
+    if len(rays):
+        ctx.check(ctx.L.rmd_intersect_rays_host(ctx.handle, dscene.handle, rays.ctypes.data_as(C.c_void_p), len(rays), out.ctypes.data_as(C.c_void_p)))
+    return hits_of(out)
+
+
+def camera_rays(ctx, camera, xy, uv=None, out=None):
+    """rmd_camera_rays: the pinhole primary rays of the pixels `xy` ((n, 2) x, y) at the jitter uniforms `uv` ((n, 2), or None: 0.5, 0.5, the pixel
+    centres) into a RayBuffer — `out`, or a new one the caller closes."""
+    xy = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+    if uv is not None:
+        uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+        assert len(uv) == len(xy)
+    rays = RayBuffer(ctx, len(xy)) if out is None else out
+    assert rays.count >= len(xy)
+    try:
+        ctx.check(ctx.L.rmd_camera_rays(ctx.handle, C.byref(camera.pod()), xy.ctypes.data_as(C.c_void_p), None if uv is None else uv.ctypes.data_as(C.c_void_p),
+                                        len(xy), rays.ptr))
+    except Exception:
+        if out is None:
+            rays.close()
+        raise
+    return rays
+
+
+def pick(ctx, dscene, camera, x, y):
+    """What pixel (x, y) sees through its centre: (object, triangle, t, normal) of the closest hit, object -1 for the background.  The ray is made and
+    intersected on the device (rmd_camera_rays, rmd_intersect_rays)."""
+    with camera_rays(ctx, camera, [[x, y]]) as rays, HitBuffer(ctx, 1) as hits:
+        intersect_rays_dev(ctx, dscene, rays, hits)
+        h = hits.download()[0]
+    return int(h["object"]), int(h["triangle"]), float(h["t"]), h["normal"].copy()
 
 
 def _first_hit_arrays(ctx, scene, settings, rects, counts, buffer_types, render):
